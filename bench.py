@@ -28,6 +28,18 @@ What the line reports (north_star: "rocprof FETCH_SIZE/WRITE_SIZE reported as ac
                SpMV stands for; above the traffic figure where 16-bit column copies and untouched x shrink what moves.
   cpu_baseline = the CPU oracle (oracle/, checker code) walking a bounded row sample of the same
                matrix on the host cores, timed in the same run; a baseline, not a target.
+
+Plain run and --full:
+  `bench.py --gpus 1 --steps K --warmup W` sets up, warms up, times the K steps, writes its outputs (--dump-outputs)
+  and prints the line: metric, value, unit, higher_is_better, dtype and ms_per_step (wall time of one timed step).
+  Its `value` charges the counter-measured bytes of one SpMV committed in profiles/traffic.json, used only while this
+  run's plan is the one they were taken with (otherwise the CSR-algorithmic bytes, and the metric says so).
+  --full adds everything else the line reports: the two counter passes measured in the run (traffic, --traffic
+  measure), the kernel alone and its roofline, the CPU baseline and parity sample, the other workloads with rocSPARSE
+  beside them, the vendor dense slot, and for N > 1 the exchange alone and the other exchange modes (--exchange all).
+  --dump-outputs DIR writes y of the last timed step as DIR/y.npy (float32); a y larger than 64 MB is written as
+  DIR/y_sample.npy instead: its values at DUMP_SAMPLE_ROWS rows drawn without replacement, in ascending order, by
+  numpy's default_rng(DUMP_SEED) -- the same rows for the same arguments, so two builds compare output for output.
 """
 from __future__ import annotations
 
@@ -53,8 +65,8 @@ ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
 import __graft_entry__ as ge  # noqa: E402
 
-HBM_PEAK_GBS = 8000.0      # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
-COPY_CEILING_GBS = 6290.0  # same guide: what a float4 copy reaches (79 % of spec)
+HBM_PEAK_GBS = 8000.0      # MI355X: HBM3E 8.0 TB/s spec
+COPY_CEILING_GBS = 6290.0  # what a float4 copy reaches on it (79 % of spec)
 L2_LINE_PEAK_G = 270.0     # profiles/r03_gather_lines_ubench.jsonl: 128-byte line requests per second the L2s serve (G/s)
 
 # the other column laws / configs of the line (N = 1): (config, band); "c5" = config 5's per-GPU shard
@@ -64,13 +76,22 @@ CAL_STREAM_BYTES = 1 << 30
 CAL_TABLE_LINES = 1 << 24      # 2 GiB: beyond every cache
 CAL_STORE_BYTES = 1 << 28
 TRAFFIC_RUNS = 2               # launches per workload in a counter pass
+DUMP_BUDGET_BYTES = 64 * 10 ** 6   # --dump-outputs writes at most this much
+DUMP_SAMPLE_ROWS = 1 << 22         # rows of y kept when y is larger than the budget
+DUMP_SEED = 20251031
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the counter passes in the run, the kernel alone and its roofline, the "
+                         "CPU baseline, the other workloads with rocSPARSE, the vendor dense slot, the other exchange modes (N > 1)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write y of the last timed step to DIR/y.npy (float32; DIR/y_sample.npy, a fixed seeded sample of its "
+                         "rows, where y is larger than 64 MB)")
     ap.add_argument("--variant", default=os.environ.get("SPMV_BENCH_VARIANT", "auto"),
                     help="auto (default: the library picks from the matrix) | tiled | panel | adaptive | ...")
     ap.add_argument("--config", default="c4", choices=["c2", "c3", "c4", "c5shard"],
@@ -78,12 +99,13 @@ def parse():
                          "and the full 512 MiB x: what ONE MI355X of the 8 multiplies")
     ap.add_argument("--band", type=int, default=int(os.environ.get("SPMV_BENCH_BAND", "8192")),
                     help="column law: >0 = diagonal band of that many columns (default 8192), 0 = uniform random")
-    ap.add_argument("--no-extras", action="store_true", help="skip the other column laws / configs (N=1 only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--traffic", default=os.environ.get("SPMV_BENCH_TRAFFIC", "measure"), choices=["measure", "replay", "off"],
-                    help="HBM traffic per SpMV: 'measure' (default) = two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE) of "
-                         "this file in --traffic-child mode before the first GPU call, falling back to 'replay' (the figure "
-                         "committed in profiles/traffic.json, only under the same plan) when rocprofv3 is missing or fails")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the other column laws / configs (N=1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--traffic", default=os.environ.get("SPMV_BENCH_TRAFFIC"), choices=["measure", "replay", "off"],
+                    help="HBM traffic per SpMV: 'measure' (default with --full, and for N > 1 where nothing is committed to replay) = "
+                         "two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE) of this file in --traffic-child mode before the "
+                         "first GPU call, falling back to 'replay' (the figure committed in profiles/traffic.json, only under the "
+                         "same plan) when rocprofv3 is missing or fails; 'replay' (default of a plain N = 1 run) = that figure alone")
     ap.add_argument("--traffic-timeout", type=float, default=420.0,
                     help="seconds the two counter passes may take together (a cold box spends minutes on the first import of "
                          "torch under the profiler; past the budget the line falls back to the replayed figure)")
@@ -105,9 +127,10 @@ def parse():
                     help="weak (default): 16Mi rows per rank, the matrix grows with N; strong: config 5's (128Mi)^2 matrix "
                          "for every N (--total-blocks row blocks dealt over the ranks)")
     ap.add_argument("--total-blocks", type=int, default=32, help="--scaling strong: row blocks of the fixed matrix")
-    ap.add_argument("--exchange", default=os.environ.get("SPMV_BENCH_EXCHANGE", "all"), choices=["all", "allgather", "p2p"],
-                    help="N>1: how y is concatenated.  'allgather' = RCCL's all-gather (the north-star; ALWAYS what `value` is "
-                         "measured with unless 'p2p' is forced), 'p2p' = one direct send/recv pair per peer, 'all' (default) = "
+    ap.add_argument("--exchange", default=os.environ.get("SPMV_BENCH_EXCHANGE"), choices=["all", "allgather", "p2p"],
+                    help="N>1: how y is concatenated.  'allgather' (default of a plain run) = RCCL's all-gather (the north-star; "
+                         "ALWAYS what `value` is measured with unless 'p2p' is forced), 'p2p' = one direct send/recv pair per peer, "
+                         "'all' (default with --full) = "
                          "the headline with the all-gather, then the other exchanges timed back to back in the same run under "
                          "a watchdog: torch p2p, the C++ pipeline (libspmv_dist.so) with all-gather and p2p, and the "
                          "one-process peer-store pipeline (bin/spmv_dist_selftest) -> exchange_modes{...}")
@@ -120,7 +143,23 @@ def parse():
                          "pipelined step, include/spmv_dist.h; torch.distributed/gloo only carries the id, the barrier and the "
                          "timing reduction; with fewer devices than ranks: all ranks in ONE process, peer stores) | gloo (rehearsal "
                          "of the N>1 path with ranks sharing one GPU)")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.traffic is None:
+        # a plain N = 1 line replays the committed counter figure; nothing is committed for the N > 1 / strong / native jobs
+        replayable = args.gpus == 1 and args.scaling == "weak" and args.backend != "native"
+        args.traffic = "replay" if replayable and not args.full else "measure"
+    if args.exchange is None:
+        args.exchange = "all" if args.full else "allgather"
+    elif args.exchange == "all" and args.gpus > 1 and not args.full:
+        ap.error("--exchange all times the other exchange modes beside the headline: it goes with --full")
+    return args
+
+
+def with_extras(args):
+    """The other column laws / configs of the line: --full only."""
+    return args.full and not args.no_extras
 
 
 # =====================================================================================================================
@@ -296,7 +335,7 @@ def traffic_child(args):
                 h.run(variant, d_x, d_y[s_ * sub_rows:(s_ + 1) * sub_rows])
         one(0, "rank", w.describe(), handles, run_all, plan_all)
     else:
-        todo = [(args.config, args.band)] + ([] if args.no_extras else extra_list(args))
+        todo = [(args.config, args.band)] + (extra_list(args) if with_extras(args) else [])
         for ident, (cname, band) in enumerate(todo):
             B = Built(torch, capi, W, dev, cname, band)
             one(ident, wkey(cname, band), B.label, [B.A], lambda B=B: B.A.run(variant, B.d_x, B.d_y), lambda B=B: B.A.plan(variant))
@@ -326,7 +365,7 @@ def write_probe_job(args, W, variant_id, world, device, tmp):
             synth(0, w, b * sub_rows, sub_rows)
         listed.append((0, "rank", w.describe()))
     else:
-        todo = [(args.config, args.band)] + ([] if args.no_extras else extra_list(args))
+        todo = [(args.config, args.band)] + (extra_list(args) if with_extras(args) else [])
         for ident, (cname, band) in enumerate(todo):
             if cname == "stencil7":
                 n3, rp, ci, va = W.stencil7(200)
@@ -387,7 +426,7 @@ def measure_traffic(args, world=1, device=0):
     t0 = time.perf_counter()
     fwd = ["--variant", args.variant, "--config", args.config, "--band", str(args.band), "--gpus", str(args.gpus),
            "--rows-per-gpu", str(args.rows_per_gpu), "--pipeline", str(args.pipeline), "--scaling", args.scaling,
-           "--total-blocks", str(args.total_blocks)] + (["--no-extras"] if args.no_extras else [])
+           "--total-blocks", str(args.total_blocks)] + (["--full"] if args.full else []) + (["--no-extras"] if args.no_extras else [])
     env = dict(os.environ, TMPDIR="/tmp", SPMV_TRAFFIC_WORLD=str(world), SPMV_TRAFFIC_DEVICE=str(device))
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID", "GROUP_RANK",
               "LOCAL_WORLD_SIZE", "ROLE_RANK", "ROLE_WORLD_SIZE"):
@@ -572,6 +611,10 @@ def selftest_line(n, per, S, band, steps, exchange, local, verify):
 def native_local(args, n, ndev):
     """--backend native with fewer devices than ranks: RCCL refuses two ranks on one device, so the C++ pipeline runs with
     all ranks in ONE process (spmv_dist_init_local, peer stores) -- a rehearsal of the plumbing, the line says so."""
+    if args.dump_outputs:
+        print("bench.py --backend native (local ranks): the steps run inside bin/spmv_dist_selftest, --dump-outputs has no y "
+              "to write", file=sys.stderr)
+        return 1
     per = min(args.rows_per_gpu, 1 << 20)
     S = max(1, args.pipeline)
     per = max(per // (S << 16), 1) * (S << 16)
@@ -663,6 +706,24 @@ def dominant_kernel(resolved, plan_now):
 
 
 # =====================================================================================================================
+# --dump-outputs: what the timed path computed
+# =====================================================================================================================
+
+def dump_outputs(directory, torch, y):
+    """y of the last timed step as DIR/y.npy (float32), or, where y is larger than DUMP_BUDGET_BYTES, its values at
+    DUMP_SAMPLE_ROWS rows drawn without replacement by default_rng(DUMP_SEED), ascending, as DIR/y_sample.npy."""
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    n = y.numel()
+    if 4 * n <= DUMP_BUDGET_BYTES:
+        np.save(d / "y.npy", y.detach().cpu().numpy().astype(np.float32, copy=False))
+        return
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE_ROWS, replace=False))
+    sample = y[torch.from_numpy(rows).to(y.device)]
+    np.save(d / "y_sample.npy", sample.detach().cpu().numpy().astype(np.float32, copy=False))
+
+
+# =====================================================================================================================
 # one rank
 # =====================================================================================================================
 
@@ -696,12 +757,13 @@ def main():
             traffic, traffic_source = j["result"], j["source"]
         else:
             traffic, traffic_source = measure_traffic(args, world=world if (world > 1 or strong) else 1, device=local_rank)
-        print(f"[bench] traffic passes done at {time.perf_counter() - t_main:.1f} s: {traffic_source[:90]}", file=sys.stderr, flush=True)
+        if args.traffic == "measure":
+            print(f"[bench] traffic passes done at {time.perf_counter() - t_main:.1f} s: {traffic_source[:90]}", file=sys.stderr, flush=True)
     # The vendor library is MAPPED now, while this process has no HIP context yet: a library that registers its code objects
     # with a live context has all of them loaded at once -- 156-180 s of a freshly booted box for librocsparse.so's 0.5 GB,
     # spent inside the first comparison -- while one registered before the context exists loads what is launched, when it is
     vendor_early = None
-    if single and rank == 0 and args.vendor != "off" and not args.no_extras:
+    if single and rank == 0 and args.vendor != "off" and with_extras(args):
         try:
             import ctypes
             t_e = time.perf_counter()
@@ -873,12 +935,14 @@ def main():
         return el, ms_ev
 
     elapsed, step_ms_events = timed_steps(step, finish)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, d_y if single else sh.y_full)     # y of the last timed step
 
     # per step, per rank: vals+col_idx, row_ptr of every owned block, y written, x read once
     bytes_rank = 8 * nnz_local + 4 * (rows_local + len(owned)) + 4 * rows_local + 4 * w.cols
     gflops = 2.0 * nnz_local * world * args.steps / elapsed / 1e9
 
-    # ---- the kernel alone (no collective): mean launch time by HIP events on its stream -----------
+    # ---- --full: the kernel alone (no collective), mean launch time by HIP events on its stream ---------------------
     iters = max(10, args.steps)
 
     def timed_exchange(xo, fin):
@@ -890,10 +954,10 @@ def main():
         ev1.record()
         torch.cuda.synchronize(); barrier()
         return ev0.elapsed_time(ev1) / iters
-    exchange_ms = None
-    if single:
+    exchange_ms = kernel_ms = None
+    if args.full and single:
         kernel_ms = A.time(variant, d_x, d_y, iters)          # spmv_csr_time: events inside the library
-    else:
+    elif args.full:
         ev0.record()
         for _ in range(iters):
             multiply_only()
@@ -924,36 +988,38 @@ def main():
                 head_src = f"{traffic_source}; {rs}"
         basis = hbm_bytes if hbm_bytes is not None else bytes_rank
         value = basis * world * args.steps / elapsed / 1e9
-        moved = basis / (kernel_ms * 1e-3) / 1e9
-        eff = bytes_rank / (kernel_ms * 1e-3) / 1e9
-        roof = {"bound": "hbm", "achieved": round(moved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(moved / HBM_PEAK_GBS, 4), "traffic": hbm_bytes, "traffic_source": head_src,
-                "frac_basis": ("FETCH_SIZE + WRITE_SIZE bytes of one SpMV (corrected) / kernel_ms / 8 TB/s" if hbm_bytes is not None else
-                               "CSR-ALGORITHMIC bytes / kernel_ms / 8 TB/s -- no counter figure in this run (see traffic_source): "
-                               "may exceed what the chip can move"),
-                "effective_achieved": round(eff, 2), "effective_frac": round(eff / HBM_PEAK_GBS, 4),
-                "effective_definition": "CSR-algorithmic bytes of one SpMV (8/nnz + row_ptr + x + y) / kernel_ms: the work done, not "
-                                        "the bytes moved (16-bit column copies and x never referenced shrink the traffic)",
-                "traffic_over_algorithmic": None if hbm_bytes is None else round(hbm_bytes / bytes_rank, 4),
-                "frac_of_copy_ceiling": round(moved / COPY_CEILING_GBS, 4),
-                "kernel": dominant_kernel(resolved, plan_now),
-                "kernel_ms": round(kernel_ms, 5), "timing": "HIP events on the launch stream"}
-        if tinfo is not None:
-            roof["counters"] = {k: tinfo[k] for k in ("FETCH_SIZE_KiB", "WRITE_SIZE_KiB", "dispatches_per_spmv", "dominant_kernel")}
-        if traffic is not None:
-            roof["calibration"] = traffic["calibration"]
-            roof["traffic_passes_s"] = traffic["seconds"]
-            roof["traffic_child_s"] = traffic.get("child_seconds")
-        for flag_rate, name in ((moved if hbm_bytes is not None else 0.0, "exceeds_copy_ceiling"), (eff, "effective_exceeds_copy_ceiling")):
-            if flag_rate > COPY_CEILING_GBS:
-                roof[name] = (f"{flag_rate:.0f} GB/s is above the {COPY_CEILING_GBS:.0f} GB/s a copy reaches: "
-                              + ("the kernel does not move the algorithmic byte count (x columns never referenced, 16-bit column "
-                                 "copies) -- read frac" if name.startswith("effective") else
-                                 "FETCH_SIZE counts L2 <-> fabric requests, Infinity Cache hits included"))
+        if args.full:
+            moved = basis / (kernel_ms * 1e-3) / 1e9
+            eff = bytes_rank / (kernel_ms * 1e-3) / 1e9
+            roof = {"bound": "hbm", "achieved": round(moved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(moved / HBM_PEAK_GBS, 4), "traffic": hbm_bytes, "traffic_source": head_src,
+                    "frac_basis": ("FETCH_SIZE + WRITE_SIZE bytes of one SpMV (corrected) / kernel_ms / 8 TB/s" if hbm_bytes is not None else
+                                   "CSR-ALGORITHMIC bytes / kernel_ms / 8 TB/s -- no counter figure in this run (see traffic_source): "
+                                   "may exceed what the chip can move"),
+                    "effective_achieved": round(eff, 2), "effective_frac": round(eff / HBM_PEAK_GBS, 4),
+                    "effective_definition": "CSR-algorithmic bytes of one SpMV (8/nnz + row_ptr + x + y) / kernel_ms: the work done, not "
+                                            "the bytes moved (16-bit column copies and x never referenced shrink the traffic)",
+                    "traffic_over_algorithmic": None if hbm_bytes is None else round(hbm_bytes / bytes_rank, 4),
+                    "frac_of_copy_ceiling": round(moved / COPY_CEILING_GBS, 4),
+                    "kernel": dominant_kernel(resolved, plan_now),
+                    "kernel_ms": round(kernel_ms, 5), "timing": "HIP events on the launch stream"}
+            if tinfo is not None:
+                roof["counters"] = {k: tinfo[k] for k in ("FETCH_SIZE_KiB", "WRITE_SIZE_KiB", "dispatches_per_spmv", "dominant_kernel")}
+            if traffic is not None:
+                roof["calibration"] = traffic["calibration"]
+                roof["traffic_passes_s"] = traffic["seconds"]
+                roof["traffic_child_s"] = traffic.get("child_seconds")
+            for flag_rate, name in ((moved if hbm_bytes is not None else 0.0, "exceeds_copy_ceiling"), (eff, "effective_exceeds_copy_ceiling")):
+                if flag_rate > COPY_CEILING_GBS:
+                    roof[name] = (f"{flag_rate:.0f} GB/s is above the {COPY_CEILING_GBS:.0f} GB/s a copy reaches: "
+                                  + ("the kernel does not move the algorithmic byte count (x columns never referenced, 16-bit column "
+                                     "copies) -- read frac" if name.startswith("effective") else
+                                     "FETCH_SIZE counts L2 <-> fabric requests, Infinity Cache hits included"))
         out = {
             "metric": ("fp32 CSR SpMV: achieved HBM GB/s (rocprofv3 FETCH_SIZE + WRITE_SIZE bytes of the K steps / wall time)"
                        if hbm_bytes is not None else
-                       "fp32 CSR SpMV throughput in CSR-algorithmic bytes per second (no counter figure in this run: see roofline.traffic_source)"),
+                       "fp32 CSR SpMV throughput in CSR-algorithmic bytes per second (no counter figure in this run: see "
+                       + ("roofline.traffic_source)" if args.full else "traffic_source)")),
             "value": round(value, 2), "unit": "GB/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 5),
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f32",
@@ -979,16 +1045,17 @@ def main():
             "effective_value": round(bytes_rank * world * args.steps / elapsed / 1e9, 2),
             "effective_value_definition": "CSR-algorithmic bytes of all ranks x K / wall time",
             "gflops": round(gflops, 1),
-            "roofline": roof,
-            "step_ms_events": round(step_ms_events, 5), "multiply_only_ms": round(kernel_ms, 5),
-            "exchange_only_ms": None if exchange_ms is None else round(exchange_ms, 5),
+            **({"roofline": roof} if args.full else {"traffic_source": head_src}),
+            "step_ms_events": round(step_ms_events, 5),
+            **({"multiply_only_ms": round(kernel_ms, 5),
+                "exchange_only_ms": None if exchange_ms is None else round(exchange_ms, 5)} if args.full else {}),
             "plan_ms": round(plan_ms, 4), "plan_bytes": sum(h.plan_bytes(variant) for h in handles),
-            "plan_amortised_over": round(plan_ms / kernel_ms, 1),
+            **({"plan_amortised_over": round(plan_ms / kernel_ms, 1)} if args.full else {}),
             "plan": plan_now,
             "setup_s": round(setup_s, 2),
         }
         print(f"[bench] headline measured at {time.perf_counter() - t_main:.1f} s", file=sys.stderr, flush=True)
-        if single and args.vendor != "off" and not args.no_extras:
+        if single and args.vendor != "off" and with_extras(args):
             # rocSPARSE for the comparison fields: a child loads the library and runs it once on a tiny matrix while this process
             # is busy on the CPU (the baseline below) -- what a load touches of the 0.5 GB file is then in the page cache and
             # the dlopen here is quick; no GPU work of this process is timed while the child runs
@@ -996,7 +1063,7 @@ def main():
                                           stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
             t_vendor = time.perf_counter()
 
-    # ---- N > 1, --exchange all: the other exchanges back to back, under a watchdog ---------------------------------
+    # ---- N > 1, --full (--exchange all): the other exchanges back to back, under a watchdog ------------------------
     if world > 1 and args.exchange == "all" and not args.footprint:
         modes = {}
         if rank == 0:
@@ -1048,8 +1115,8 @@ def main():
             out["exchange_modes"] = modes
         done.set()
 
-    # ---- CPU baseline: rank 0, N = 1 only, bounded sample of the same matrix ------------------------
-    if rank == 0 and single and not args.no_cpu_baseline:
+    # ---- --full, CPU baseline: rank 0, N = 1 only, bounded sample of the same matrix ------------------
+    if rank == 0 and single and args.full and not args.no_cpu_baseline:
         orc = ge.load_oracle()
         n = min(args.cpu_sample_rows, rows_local)
         s0 = ((rows_local - n) // 2 // W.BLOCK_ROWS) * W.BLOCK_ROWS  # a window from the middle of the matrix
@@ -1092,8 +1159,8 @@ def main():
                                 "bit_identical_rows_vs_seq_oracle": int(np.sum(d_y[s0:s1].cpu().numpy() == y_cpu))}
         print(f"[bench] cpu baseline done at {time.perf_counter() - t_main:.1f} s", file=sys.stderr, flush=True)
 
-    # ---- the other column laws and configs, kernel time only (N = 1) ------------------------------
-    if rank == 0 and single and not args.no_extras:
+    # ---- --full, the other column laws and configs, kernel time only (N = 1) ----------------------
+    if rank == 0 and single and with_extras(args):
         del A, d_rp, d_ci, d_va, d_x, d_y, handles, keep
         torch.cuda.empty_cache()
         extras = []

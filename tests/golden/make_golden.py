@@ -20,8 +20,14 @@ AWSPMatrix, AWSPRefMatrix; src/wsp.cpp, src/awsp.cpp, src/awsp_ref.cpp) with the
 (``nz_max_m``, ``nz_bk_max_``, ``warp_nz_offset_[4]``), and a checksum of ASPMatrix's re-tiled values.
 
 Fixtures are data only (inputs and expected outputs).  Usage:  python tests/golden/make_golden.py
+
+``ref_launcher_prototypes.json`` holds the launcher prototypes of the reference's src/include/kernel.hpp:8-17 -- names and
+parameter types only, what tests/test_host_logic.py holds include/kernel.hpp to.  Usage:
+python tests/golden/make_golden.py --prototypes REFERENCE_DIR
 """
 import ctypes
+import json
+import re
 import sys
 from pathlib import Path
 
@@ -172,5 +178,23 @@ def main():
         print(f"{name}: {M}x{N} nnz={len(va)} -> {(HERE / (name + '.npz')).stat().st_size} bytes")
 
 
+def launcher_prototypes(text):
+    """{name: [parameter types]} of the `void <name>_gemv_gpu(...);` prototypes of a kernel.hpp."""
+    out = {}
+    for m in re.finditer(r"^void\s+(\w+_gemv_gpu)\s*\(([^)]*)\)\s*;", text, flags=re.M):
+        params = [re.sub(r"\s+", " ", p.strip()) for p in m.group(2).split(",")]
+        out[m.group(1)] = [re.sub(r"\s*\w+$", "", p).replace(" *", "*").strip() for p in params]   # types only
+    return out
+
+
+def write_prototypes(ref_dir):
+    protos = launcher_prototypes((Path(ref_dir) / "src" / "include" / "kernel.hpp").read_text())
+    (HERE / "ref_launcher_prototypes.json").write_text(json.dumps(protos, indent=1) + "\n")
+    print(f"ref_launcher_prototypes.json: {len(protos)} launchers")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:2] == ["--prototypes"]:
+        write_prototypes(sys.argv[2])
+    else:
+        main()

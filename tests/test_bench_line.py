@@ -1,14 +1,16 @@
 """bench.py as the driver calls it: the pieces that need no GPU here, the whole line on the GPU box.
 
-The line's roofline is the north-star's quantity (rocprofv3 FETCH_SIZE / WRITE_SIZE bytes over the kernel time), measured
-by child passes inside the run; `python3 bench.py --gpus N` starts its own ranks (the reference drives everything from one
-process, /root/reference/test/main.cpp:3-7)."""
+A plain run times the headline alone (and writes y with --dump-outputs); --full adds the rest.  The full line's roofline
+is the north-star's quantity (rocprofv3 FETCH_SIZE / WRITE_SIZE bytes over the kernel time), measured by child passes
+inside the run; `python3 bench.py --gpus N` starts its own ranks (the reference drives everything from one process,
+its test/main.cpp:3-7)."""
 import json
 import os
 import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -70,6 +72,41 @@ def test_replay_only_under_the_same_plan():
     assert b is None and "another plan" in src
 
 
+def test_plain_run_leaves_the_rest_to_full():
+    """A plain run replays the committed traffic figure and times the headline only; --full measures the traffic in the
+    run and adds the extras (N = 1) or the other exchange modes (N > 1); --steps is the number of timed steps."""
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.full, a.steps, a.warmup, a.traffic, a.exchange, bench.with_extras(a)) == (False, 7, 2, "replay", "allgather", False)
+    f = bench.parse(["--gpus", "1", "--full"])
+    assert (f.traffic, f.exchange, bench.with_extras(f)) == ("measure", "all", True)
+    assert not bench.with_extras(bench.parse(["--full", "--no-extras"]))
+    assert bench.parse(["--gpus", "2"]).traffic == "measure"          # nothing committed to replay for N > 1
+    assert bench.parse(["--traffic", "off"]).traffic == "off"
+    for bad in (["--steps", "0"], ["--gpus", "2", "--exchange", "all"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_dump_outputs_is_whole_or_a_fixed_sample_within_the_budget(tmp_path):
+    """--dump-outputs: a y that fits is written whole; a larger one as the same seeded sample of rows every time, float32,
+    within the budget."""
+    import torch
+    import bench
+    small = torch.arange(1000, dtype=torch.float32)
+    bench.dump_outputs(tmp_path / "s", torch, small)
+    assert [p.name for p in (tmp_path / "s").iterdir()] == ["y.npy"]
+    assert np.array_equal(np.load(tmp_path / "s" / "y.npy"), small.numpy())
+    big = torch.arange(bench.DUMP_BUDGET_BYTES // 4 + 1, dtype=torch.float32)   # the values are the row numbers (< 2^24)
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, torch, big)
+        assert [p.name for p in (tmp_path / d).iterdir()] == ["y_sample.npy"]
+        assert (tmp_path / d / "y_sample.npy").stat().st_size <= bench.DUMP_BUDGET_BYTES
+    a, b = np.load(tmp_path / "a" / "y_sample.npy"), np.load(tmp_path / "b" / "y_sample.npy")
+    assert a.dtype == np.float32 and a.size == bench.DUMP_SAMPLE_ROWS and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and a[-1] < big.numel()             # distinct rows, ascending
+
+
 def _line(cmd, timeout):
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
@@ -89,7 +126,7 @@ def test_headline_traffic_is_measured_in_the_run(built, gpu):
     import shutil
     if shutil.which("rocprofv3") is None and not Path("/opt/rocm/bin/rocprofv3").exists():
         pytest.skip("no rocprofv3 on this box")
-    out, err = _line(["--config", "c2", "--band", "8192", "--no-extras", "--no-cpu-baseline", "--steps", "5", "--warmup", "2"], 900)
+    out, err = _line(["--full", "--config", "c2", "--band", "8192", "--no-extras", "--no-cpu-baseline", "--steps", "5", "--warmup", "2"], 900)
     r = out["roofline"]
     assert "measured in this run" in r["traffic_source"], (r["traffic_source"], err[-1500:])
     assert r["traffic"] > 0 and abs(r["frac"] - r["traffic"] / (r["kernel_ms"] * 1e-3) / 8e12) < 2e-3
@@ -108,7 +145,7 @@ def test_headline_traffic_is_measured_in_the_run(built, gpu):
 def test_bench_starts_its_own_ranks_gloo(built, gpu):
     """`python3 bench.py --gpus 2` with no launcher: two ranks appear, share the one device (the line says so), y is
     exchanged through gloo; the extra exchange modes of --exchange all run under the watchdog."""
-    out, err = _line(["--gpus", "2", "--backend", "gloo", "--no-extras", "--no-cpu-baseline", "--steps", "2", "--warmup", "1",
+    out, err = _line(["--full", "--gpus", "2", "--backend", "gloo", "--no-extras", "--no-cpu-baseline", "--steps", "2", "--warmup", "1",
                       "--rows-per-gpu", str(1 << 20), "--traffic", "off"], 900)
     assert out["n_gpus"] == 2 and "RANKS SHARE DEVICES" in out["config"]["devices"]
     assert out["config"]["launch"] == "bench.py started its own ranks"
@@ -130,3 +167,30 @@ def test_bench_starts_its_own_ranks_native(built, gpu):
     out, err = _line(["--gpus", "2", "--backend", "native", "--no-extras", "--no-cpu-baseline", "--steps", "2"], 900)
     assert out["n_gpus"] == 2 and "RANKS SHARE DEVICES" in out["config"]["devices"]
     assert out["rows_differing_from_single_handle"] == 0
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_what_they_computed(built, gpu, oracle, tmp_path):
+    """A plain N = 1 run: exactly --steps timed steps, the headline fields and nothing of --full; --dump-outputs writes the
+    y of the timed path, within 1e-5 of the fp64 oracle and bit for bit the same in a second run with the same arguments."""
+    from _util import assert_close_to_oracle
+    ys = []
+    for d in ("a", "b"):
+        out, err = _line(["--gpus", "1", "--config", "c2", "--band", "8192", "--steps", "7", "--warmup", "2",
+                          "--dump-outputs", str(tmp_path / d)], 600)
+        assert (out["steps"], out["warmup"], out["unit"], out["higher_is_better"], out["dtype"]) == (7, 2, "GB/s", True, "f32")
+        assert out["metric"].startswith("fp32 CSR SpMV") and out["value"] > 0 and out["ms_per_step"] > 0
+        basis = out["config"]["hbm_bytes_per_gpu"] or out["config"]["algorithmic_bytes_per_gpu"]
+        assert out["value"] == pytest.approx(basis / (out["ms_per_step"] * 1e-3) / 1e9, rel=2e-3)
+        for key in ("roofline", "cpu_baseline", "other_workloads", "multiply_only_ms", "vendor_dense_slot"):
+            assert key not in out, key
+        ys.append(np.load(tmp_path / d / "y.npy"))
+    pkg = built
+    W = pkg.workloads
+    w = W.config("c2", band=8192)
+    rp = W.row_ptr(w)
+    ci, va = oracle.synth_fill(w.seed, 0, w.rows, w.rows, w.cols, w.band, rp)
+    y64, mag = oracle.spmv_f64(rp, ci, va, oracle.synth_x(w.seed, 0, w.cols))
+    assert ys[0].dtype == np.float32 and ys[0].shape == (w.rows,)
+    assert_close_to_oracle(ys[0], y64, mag, "bench --dump-outputs")
+    assert np.array_equal(ys[0].view(np.uint32), ys[1].view(np.uint32))

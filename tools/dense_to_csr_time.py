@@ -1,5 +1,6 @@
 import sys, time, json
-sys.path.insert(0, "/root/repo")
+from pathlib import Path
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import __graft_entry__ as ge
 import numpy as np, torch
 pkg = ge.load_package(); capi = pkg.capi; W = pkg.workloads
