@@ -331,6 +331,15 @@ SPMV_API int spmv_calib_gather(const float *d_table, int64_t table_lines, int64_
 SPMV_API int spmv_calib_store(float *d_dst, int64_t bytes, int width, void *stream);
 SPMV_API int spmv_calib_marker(int id, void *stream);
 
+/* ---- TEST ONLY: the bounds-checked build ---------------------------------------------------------------------
+ * lib/libspmv_hip_checked.so is this library compiled with SPMV_CHECK_BOUNDS: the streams of the panel family that
+ * read or write past a tile's or a bin's end check every access against the array's allocation, record a violation
+ * instead of issuing the access, and go on.  spmv_debug_bounds waits for the current device, writes up to n records
+ * {site, violations, largest overrun in bytes} (three int64 each) of the sites that recorded any since the last call,
+ * clears the tables and returns how many sites did (>= 0; may exceed n).  Site numbers: csrc/spmv_internal.hpp
+ * BoundsSite.  The normal library returns SPMV_ERR_INVALID ("not instrumented"). */
+SPMV_API int spmv_debug_bounds(int64_t *records, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,7 +82,14 @@ SIGNATURES = {
     "spmv_calib_gather": (C.c_int, [_f32p, C.c_int64, C.c_int64, C.c_int, _f32p, _vp]),
     "spmv_calib_store": (C.c_int, [_f32p, C.c_int64, C.c_int, _vp]),
     "spmv_calib_marker": (C.c_int, [C.c_int, _vp]),
+    "spmv_debug_bounds": (C.c_int, [_vp, C.c_int]),
 }
+# test only: the bounds-checked build of the library (SPMV_CHECK_BOUNDS) and its sites (csrc/spmv_internal.hpp BoundsSite)
+CHECKED_LIB_PATH = PKG_DIR / "lib" / "libspmv_hip_checked.so"
+BOUNDS_SITES = ("k_bs_sums prod", "k_bs_sums acc", "k_bin_sums prod", "k_bin_sums r16", "k_bs_products c16",
+                "k_bs_products pvals", "k_bs_products prod store", "k_bs_group store", "k_bs_place load",
+                "k_bs_place acc store", "k_bs_place c16/pvals store", "k_bs_fill acc store", "k_bs_fill c16/pvals store",
+                "k_panel packed", "k_panel pvals")
 
 
 class SpmvError(RuntimeError):
@@ -432,3 +439,14 @@ def calib_store(dst, nbytes: int, width: int, stream=None) -> None:
 
 def calib_marker(ident: int, stream=None) -> None:
     check(lib().spmv_calib_marker(ident, _stream_handle(stream)))
+
+
+def debug_bounds(max_records: int = 64) -> list:
+    """TEST ONLY (the checked build): [(site name, violations, largest overrun in bytes)] recorded since the last call, which
+    clears them.  The normal library raises SpmvError (SPMV_ERR_INVALID: not instrumented)."""
+    import numpy as np
+    rec = np.zeros(3 * max_records, np.int64)
+    n = lib().spmv_debug_bounds(rec.ctypes.data, max_records)
+    if n < 0:
+        check(n)
+    return [(BOUNDS_SITES[int(rec[3 * i])], int(rec[3 * i + 1]), int(rec[3 * i + 2])) for i in range(min(n, max_records))]

@@ -101,6 +101,35 @@ const char *spmv_last_error(void) { return g_err; }
 
 float spmv_last_first_launch_ms(void) { return g_first_launch_ms; }
 
+int spmv_debug_bounds(int64_t *records, int n)
+{
+#if defined(SPMV_CHECK_BOUNDS)
+    if (n < 0 || (n > 0 && !records)) {
+        spmv::set_error("spmv_debug_bounds: n = %d records at %p", n, (void *)records);
+        return SPMV_ERR_INVALID;
+    }
+    unsigned long long t[spmv::kBoundsSites][2] = {};
+    if (int rc = spmv::bounds_collect_binned(t)) return rc;
+    if (int rc = spmv::bounds_collect_panel(t)) return rc;
+    int hit = 0;
+    for (int i = 0; i < spmv::kBoundsSites; ++i) {
+        if (t[i][0] == 0) continue;
+        if (hit < n) {
+            records[3 * hit] = i;
+            records[3 * hit + 1] = (int64_t)t[i][0];
+            records[3 * hit + 2] = (int64_t)t[i][1];
+        }
+        ++hit;
+    }
+    return hit;
+#else
+    (void)records;
+    (void)n;
+    spmv::set_error("spmv_debug_bounds: not instrumented (this is the normal build; lib/libspmv_hip_checked.so is the checked one)");
+    return SPMV_ERR_INVALID;
+#endif
+}
+
 const char *spmv_variant_name(int variant)
 {
     switch (variant) {

@@ -42,6 +42,7 @@ constexpr int kProdThreads = 1024;         // one 16-wavefront workgroup per CU 
 constexpr int kMaxPanels = 4096;           // (panel_tile_ptr's histogram) -> at most 2^27 columns
 constexpr int kSumWaves = 4;               // wavefronts per workgroup of the sum launch
 constexpr int kSpare = 512;                // spare sums per bin for its long rows (see k_bin_runs)
+constexpr int kBinSlack = 264;             // entries behind d_prod / d_r16 (mode 4): a piece of the sum launch reads up to 256 past a tile's end
 
 
 using u4 = unsigned __attribute__((ext_vector_type(4)));
@@ -219,6 +220,16 @@ __global__ __launch_bounds__(kProdThreads) void k_bin_products(int splits, int64
 constexpr int kBlk = 512;                  // interleave block of the panel-major arrays: lane l of a wavefront holds entries l, 64 + l, ...
 constexpr int kPool = 1024;                // spare accumulators of a bin (8192 + 1024 + 64 words: four wavefronts per CU)
 constexpr int kBmPiece = 256;              // entries of the bin-major arrays per wavefront instruction group
+#ifndef SPMV_BS_DEPTH
+#define SPMV_BS_DEPTH 4
+#endif
+constexpr int kBsDepth = SPMV_BS_DEPTH;    // pieces per register set of the sum launch (k_bs_sums: two sets in flight)
+// Slack behind the bin-major arrays (d_prod, d_r16 = the accumulator numbers), in entries.  The sum launch's stream issues
+// two sets of kBsDepth pieces ahead of the trip it consumes, without a branch: a bin of p pieces reads (ceil(p / 2kD) + 1)
+// 2kD pieces from its base, up to 4 kD - 1 pieces past its end -- the last bin's end is the arrays' end (the bins are
+// whole pieces).  The panels' pad slots also store there (entries bm .. bm + kBlk - 1, k_bs_runs).
+constexpr int kBsSlack = 4 * kBsDepth * kBmPiece;
+static_assert(kBsSlack >= (4 * kBsDepth - 1) * kBmPiece && kBsSlack >= kBlk + 16, "bin-major slack: the sum launch's read-ahead, the pad slots");
 constexpr int kRunBit = 1 << kPwBits;      // bit 15 of a panel-major column: this entry is the first of its run
 
 __device__ __forceinline__ int interleaved(int q) { return (q & ~(kBlk - 1)) | ((q & 63) << 3) | ((q >> 6) & 7); }
@@ -313,7 +324,8 @@ __global__ __launch_bounds__(256) void k_bs_fill(int nb, int np, const int32_t *
                                                  const int32_t *__restrict__ col_idx, const float *__restrict__ vals,
                                                  const uint16_t *__restrict__ rowloc, const int32_t *__restrict__ tile_ptr,
                                                  const int32_t *__restrict__ pm, const int32_t *__restrict__ bbase,
-                                                 uint16_t *__restrict__ c16, float *__restrict__ pvals, uint16_t *__restrict__ acc)
+                                                 uint16_t *__restrict__ c16, float *__restrict__ pvals, uint16_t *__restrict__ acc,
+                                                 int64_t nslot, int64_t bslot)
 {
     extern __shared__ int cursor_all[];     // 4 x np cursors, 4 x 256 tags
     const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
@@ -355,10 +367,13 @@ __global__ __launch_bounds__(256) void k_bs_fill(int nb, int np, const int32_t *
             todo &= ~m;
         }
         if (valid) {
+            SPMV_BOUNDS_STORE(kSiteBsFillAcc, 2 * ((int64_t)dest + shift), 2, 2 * bslot)
             acc[dest + shift] = (uint16_t)rl;                  // (k_bs_accs turns rows into accumulators)
             const int q = interleaved(qp[p] + (dest - tp[p]));
-            c16[q] = (uint16_t)((col & (kPw - 1)) | (dest == tp[p] ? kRunBit : 0));   // the first entry of its tile starts a run
-            pvals[q] = v;
+            SPMV_BOUNDS_STORE(kSiteBsFillC16, 4 * (int64_t)q, 4, 4 * nslot) {
+                c16[q] = (uint16_t)((col & (kPw - 1)) | (dest == tp[p] ? kRunBit : 0));   // the first entry of its tile starts a run
+                pvals[q] = v;
+            }
         }
     }
 }
@@ -377,7 +392,8 @@ constexpr int kGroupBits = 6;              // panels per group: 64 (a lane's wor
 __global__ __launch_bounds__(256) void k_bs_group(int nb, int np, const int32_t *__restrict__ brow, const int32_t *__restrict__ row_ptr,
                                                   const int32_t *__restrict__ col_idx, const float *__restrict__ vals,
                                                   const uint16_t *__restrict__ rowloc, const int32_t *__restrict__ tile_ptr,
-                                                  int32_t *__restrict__ tcol, float *__restrict__ tval, uint16_t *__restrict__ trow)
+                                                  int32_t *__restrict__ tcol, float *__restrict__ tval, uint16_t *__restrict__ trow,
+                                                  int64_t tlen)
 {
     __shared__ int cursor_all[4][64];
     const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
@@ -403,7 +419,7 @@ __global__ __launch_bounds__(256) void k_bs_group(int nb, int np, const int32_t 
         // ~40 trips per step -- an LDS atomic with return hands out the places; the order inside a group is then the order
         // the LDS serves the lanes in, the same on every run, and nothing downstream needs the rows of a tile ascending)
         const int dest = valid ? atomicAdd(&cursor[g], 1) : 0;
-        if (valid) {
+        if (valid) SPMV_BOUNDS_STORE(kSiteBsGroupStore, 4 * (int64_t)dest, 4, 4 * tlen) {   // (tcol, tval, trow: tlen entries)
             tcol[dest] = col;
             tval[dest] = v;
             trow[dest] = (uint16_t)rl;
@@ -415,7 +431,8 @@ __global__ __launch_bounds__(256) void k_bs_group(int nb, int np, const int32_t 
 __global__ __launch_bounds__(256) void k_bs_place(int nb, int np, int nitems, const int32_t *__restrict__ src_col, const float *__restrict__ src_val,
                                                   const uint16_t *__restrict__ src_row, const int32_t *__restrict__ tile_ptr,
                                                   const int32_t *__restrict__ pm, const int32_t *__restrict__ bbase,
-                                                  uint16_t *__restrict__ c16, float *__restrict__ pvals, uint16_t *__restrict__ acc)
+                                                  uint16_t *__restrict__ c16, float *__restrict__ pvals, uint16_t *__restrict__ acc,
+                                                  int64_t src_len, int64_t nslot, int64_t bslot)
 {
     __shared__ int cursor_all[4][64];
     const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x >> 6;
@@ -437,9 +454,11 @@ __global__ __launch_bounds__(256) void k_bs_place(int nb, int np, int nitems, co
         int col = 0, rl = 0;
         float v = 0.0f;
         if (valid) {
-            col = src_col[k];
-            rl = src_row[k];
-            v = src_val[k];
+            int ks = k;
+            SPMV_BOUNDS_LOAD(oks, kSiteBsPlaceLoad, ks, 4 * (int64_t)k, 4, 4 * src_len);
+            col = SPMV_BOUNDS_VALUE(oks, src_col[ks]);
+            rl = SPMV_BOUNDS_VALUE(oks, (int)src_row[ks]);
+            v = SPMV_BOUNDS_VALUE(oks, src_val[ks]);
         }
         const int p = col >> kPwBits, j = p - p0;
         int dest = valid ? atomicAdd(&cursor[j], 1) : 0;
@@ -455,10 +474,13 @@ __global__ __launch_bounds__(256) void k_bs_place(int nb, int np, int nitems, co
                 const int a = (int)((unsigned)r / (unsigned)m), bq = r - a * m;
                 dest = t0 + (bq << 8) + a;
             }
+            SPMV_BOUNDS_STORE(kSiteBsPlaceAcc, 2 * ((int64_t)dest + shift), 2, 2 * bslot)
             acc[dest + shift] = (uint16_t)rl;                  // (k_bs_accs turns rows into accumulators)
             const int q = interleaved(qp[p] + (dest - tp[p]));
-            c16[q] = (uint16_t)((col & (kPw - 1)) | (dest == tp[p] ? kRunBit : 0));   // the first entry of its tile starts a run
-            pvals[q] = v;
+            SPMV_BOUNDS_STORE(kSiteBsPlaceC16, 4 * (int64_t)q, 4, 4 * nslot) {
+                c16[q] = (uint16_t)((col & (kPw - 1)) | (dest == tp[p] ? kRunBit : 0));   // the first entry of its tile starts a run
+                pvals[q] = v;
+            }
         }
     }
 }
@@ -587,7 +609,7 @@ __global__ __launch_bounds__(kWave) void k_bs_accs(const int32_t *__restrict__ b
 __global__ __launch_bounds__(kProdThreads) void k_bs_products(int splits, int np, int64_t cols, const int32_t *__restrict__ pbase,
                                                               const uint16_t *__restrict__ c16, const float *__restrict__ pvals,
                                                               const int32_t *__restrict__ first_run, const int32_t *__restrict__ offset,
-                                                              const float *__restrict__ x, float *__restrict__ prod)
+                                                              const float *__restrict__ x, float *__restrict__ prod, int64_t nslot, int64_t bslot)
 {
     extern __shared__ __attribute__((aligned(16))) float xp[];      // the panel: kPw floats
     const int tid = threadIdx.x, lane = tid & (kWave - 1);
@@ -635,9 +657,12 @@ __global__ __launch_bounds__(kProdThreads) void k_bs_products(int splits, int np
         if (k >= b) continue;
         const int blk = __builtin_amdgcn_readfirstlane(k >> 9);
         const int t0 = first_run[blk];
-        const u4 c = __builtin_nontemporal_load(reinterpret_cast<const u4 *>(c16 + k));
-        const f4 v0 = __builtin_nontemporal_load(reinterpret_cast<const f4 *>(pvals + k));
-        const f4 v1 = __builtin_nontemporal_load(reinterpret_cast<const f4 *>(pvals + k + 4));
+        int kc = k, kv = k;                                         // (c16, pvals: nslot entries)
+        SPMV_BOUNDS_LOAD(okc, kSiteBsProductsC16, kc, 2 * (int64_t)k, 16, 2 * nslot);
+        SPMV_BOUNDS_LOAD(okv, kSiteBsProductsVals, kv, 4 * (int64_t)k, 32, 4 * nslot);
+        const u4 c = SPMV_BOUNDS_VALUE(okc, __builtin_nontemporal_load(reinterpret_cast<const u4 *>(c16 + kc)));
+        const f4 v0 = SPMV_BOUNDS_VALUE(okv, __builtin_nontemporal_load(reinterpret_cast<const f4 *>(pvals + kv)));
+        const f4 v1 = SPMV_BOUNDS_VALUE(okv, __builtin_nontemporal_load(reinterpret_cast<const f4 *>(pvals + kv + 4)));
         const unsigned cw[8] = {c.x & 0xffffu, c.x >> 16, c.y & 0xffffu, c.y >> 16, c.z & 0xffffu, c.z >> 16, c.w & 0xffffu, c.w >> 16};
         const float vw[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
         int run = t0;                                               // (scalar) runs begun before store j's entries, from t0
@@ -648,6 +673,7 @@ __global__ __launch_bounds__(kProdThreads) void k_bs_products(int splits, int np
             const int d = offset[run + __popcll(starts & le)];
             run += __popcll(starts);
             const float o = xp[cw[j] & (unsigned)(kPw - 1)] * vw[j];
+            SPMV_BOUNDS_STORE(kSiteBsProductsStore, 4 * ((int64_t)q + 64 * j + d), 4, 4 * bslot)
 #ifdef SPMV_BS_NT_STORE
             __builtin_nontemporal_store(o, prod + (q + 64 * j + d));
 #else
@@ -665,13 +691,11 @@ __global__ __launch_bounds__(kWave) void k_bs_sums(const int32_t *__restrict__ b
                                                    const uint32_t *__restrict__ lrow, float *__restrict__ y, uint32_t prod_bytes,
                                                    uint32_t acc_bytes)
 {
-#ifndef SPMV_BS_DEPTH
-#define SPMV_BS_DEPTH 4
-#endif
 #ifndef SPMV_BS_LOAD_AUX
 #define SPMV_BS_LOAD_AUX 2      // cache-policy bits of the sum launch's loads: non-temporal (0: 398 -> 360 us at config 5's shard; the products are read once)
 #endif
-    constexpr int kDummy = RB + kPool, kD = SPMV_BS_DEPTH;           // pieces per register set (two sets in flight)
+    constexpr int kDummy = RB + kPool, kD = kBsDepth;                // pieces per register set (two sets in flight)
+    static_assert((4 * kD - 1) * kBmPiece <= kBsSlack, "stream() reads up to 4 kD - 1 pieces past a bin's end");
     extern __shared__ float sums[];                                 // RB + kPool + kWave
     const int lane = threadIdx.x, b = blockIdx.x;
     const int row0 = brow[b], nrows = brow[b + 1] - row0;
@@ -683,12 +707,18 @@ __global__ __launch_bounds__(kWave) void k_bs_sums(const int32_t *__restrict__ b
     using u2v = decltype(__builtin_amdgcn_raw_buffer_load_b64(rr, 0, 0, 0));
     struct Set { u4v v[kD]; u2v a[kD]; };                           // as loaded: unpacking here would wait for the loads at once
     __builtin_amdgcn_s_waitcnt(0x0F70);                             // (the table numbers are in: the waits below count piece loads only)
-    auto issue = [&](int pi0, Set &c) {                             // no branch: a piece past the end reads on (slack) and counts for nothing
+    // No branch: a piece past the bin's end reads on into the next bins and the arrays' slack (kBsSlack: the position is the
+    // SCALAR offset of the loads, which the descriptor's range check leaves out) and counts for nothing
+    auto issue = [&](int pi0, Set &c) {
 #pragma unroll
         for (int u = 0; u < kD; ++u) {
             const unsigned at = (unsigned)base + (unsigned)(pi0 + u) * kBmPiece;
-            c.v[u] = __builtin_amdgcn_raw_buffer_load_b128(pr, lane * 16, (int)(at * 4u), SPMV_BS_LOAD_AUX);
-            c.a[u] = __builtin_amdgcn_raw_buffer_load_b64(rr, lane * 8, (int)(at * 2u), SPMV_BS_LOAD_AUX);
+            int pv = lane * 16, ps = (int)(at * 4u);
+            SPMV_BOUNDS_BUF(okp, kSiteBsSumsProd, pv, ps, 16, prod_bytes);
+            c.v[u] = SPMV_BOUNDS_VALUE(okp, __builtin_amdgcn_raw_buffer_load_b128(pr, pv, ps, SPMV_BS_LOAD_AUX));
+            int av = lane * 8, as = (int)(at * 2u);
+            SPMV_BOUNDS_BUF(oka, kSiteBsSumsAcc, av, as, 8, acc_bytes);
+            c.a[u] = SPMV_BOUNDS_VALUE(oka, __builtin_amdgcn_raw_buffer_load_b64(rr, av, as, SPMV_BS_LOAD_AUX));
             // the SAME order of loads before the loop and inside it: the wait counts are static, and a first trip that needs
             // "everything" (the scheduler had turned the sets round) makes every trip wait for everything
             __builtin_amdgcn_sched_barrier(0);
@@ -847,24 +877,28 @@ __global__ __launch_bounds__(kSumWaves *kWave) void k_bin_sums(int nb, int np, c
                 c.q[u] = q + off;                                   // (bit 31 of q: the tile is flagged)
                 c.s[u] = s + off;
                 // buffer loads: the piece's position is the SCALAR offset, the lane's share a constant vector offset -- no
-                // address arithmetic per piece on the vector side (reads past the arrays' ends return 0)
+                // address arithmetic per piece on the vector side.  The descriptor's range check leaves the scalar offset
+                // out: a piece starts inside its tile (a dead one at a tile's start) and reads kPiece <= 256 entries: kBinSlack holds that
                 const unsigned qb = (unsigned)((q & 0x7fffffff) + off) * 4u, sb = (unsigned)(s + off) * 2u;
+                int pvo = lane * 4 * E, pso = (int)qb, rvo = lane * 2 * E, rso = (int)sb;
+                SPMV_BOUNDS_BUF(okp, kSiteBinSumsProd, pvo, pso, 4 * E, prod_bytes);
+                SPMV_BOUNDS_BUF(okr, kSiteBinSumsR16, rvo, rso, 2 * E, r16_bytes);
                 if (E == 4) {
-                    const auto pv = __builtin_amdgcn_raw_buffer_load_b128(pr, lane * 16, (int)qb, SPMV_BIN_LOAD_AUX);
+                    const auto pv = SPMV_BOUNDS_VALUE(okp, __builtin_amdgcn_raw_buffer_load_b128(pr, pvo, pso, SPMV_BIN_LOAD_AUX));
                     c.v[u][0] = __uint_as_float(pv[0]); c.v[u][1] = __uint_as_float(pv[1]);
                     c.v[u][2] = __uint_as_float(pv[2]); c.v[u][3] = __uint_as_float(pv[3]);
                 } else {
-                    const auto pv = __builtin_amdgcn_raw_buffer_load_b64(pr, lane * 8, (int)qb, SPMV_BIN_LOAD_AUX);
+                    const auto pv = SPMV_BOUNDS_VALUE(okp, __builtin_amdgcn_raw_buffer_load_b64(pr, pvo, pso, SPMV_BIN_LOAD_AUX));
                     c.v[u][0] = __uint_as_float(pv[0]); c.v[u][1] = __uint_as_float(pv[1]);
                 }
                 // (the rows of a lane: one load; a tile starts at any entry, so the address is 2-byte aligned only -- the
                 // memory pipeline takes that, as it does for the global loads the compiler makes of a uint16_t pointer)
                 if (E == 4) {
-                    const auto rv = __builtin_amdgcn_raw_buffer_load_b64(rr, lane * 8, (int)sb, SPMV_BIN_LOAD_AUX);
+                    const auto rv = SPMV_BOUNDS_VALUE(okr, __builtin_amdgcn_raw_buffer_load_b64(rr, rvo, rso, SPMV_BIN_LOAD_AUX));
                     c.r[u][0] = (int)(rv[0] & 0xffffu); c.r[u][1] = (int)(rv[0] >> 16);
                     c.r[u][2] = (int)(rv[1] & 0xffffu); c.r[u][3] = (int)(rv[1] >> 16);
                 } else {
-                    const unsigned rv = __builtin_amdgcn_raw_buffer_load_b32(rr, lane * 4, (int)sb, SPMV_BIN_LOAD_AUX);
+                    const unsigned rv = SPMV_BOUNDS_VALUE(okr, __builtin_amdgcn_raw_buffer_load_b32(rr, rvo, rso, SPMV_BIN_LOAD_AUX));
                     c.r[u][0] = (int)(rv & 0xffffu); c.r[u][1] = (int)(rv >> 16);
                 }
             }
@@ -1078,11 +1112,11 @@ static int plan_scatter(spmv_csr &h, PanelPlan &p, int rb, int32_t padded, DevPt
     SPMV_HIP_TRY(hipMemcpyAsync(&bm, total.p, sizeof bm, hipMemcpyDeviceToHost, s));
     SPMV_HIP_TRY(hipMemcpyAsync(bbase.p + nb, total.p, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     SPMV_HIP_TRY(hipStreamSynchronize(s));
-    if (bm < 0 || (int64_t)bm > (1ll << 30) - 1024) {   // ((bm + 528) * 4 bytes must fit the buffer descriptors' 32 bits)
+    if (bm < 0 || (int64_t)bm + kBsSlack >= (1ll << 30)) {   // ((bm + kBsSlack) * 4 bytes must fit the buffer descriptors' 32 bits)
         set_error("spmv_csr_plan(panel, binned, scattered products): %d bins pad nnz %lld beyond 2^30 entries", nb, (long long)h.nnz);
         return SPMV_ERR_INVALID;
     }
-    const size_t nslot = (size_t)padded + 8, bslot = (size_t)bm + kBlk + 16;       // (entries bm ...: where the pad slots of the panels store)
+    const size_t nslot = (size_t)padded + 8, bslot = (size_t)bm + kBsSlack;      // (entries bm ...: the pad slots of the panels, the read-ahead)
     SPMV_HIP_TRY(c16.alloc(nslot));
     SPMV_HIP_TRY(pvals.alloc(nslot));
     SPMV_HIP_TRY(prod.alloc(bslot));
@@ -1115,7 +1149,8 @@ static int plan_scatter(spmv_csr &h, PanelPlan &p, int rb, int32_t padded, DevPt
         if (const char *e = getenv("SPMV_BS_FILL")) one_pass = atoi(e) == 1;   // (A/B runs: the one-pass fill)
         if (one_pass) {
             k_bs_fill<<<dim3((unsigned)((nb + 3) / 4)), dim3(256), sizeof(int) * 4 * ((size_t)np + 256), s>>>(
-                nb, np, brow.p, h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.p, tiles.p, pm.p, bbase.p, c16.p, pvals.p, acc.p);
+                nb, np, brow.p, h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.p, tiles.p, pm.p, bbase.p, c16.p, pvals.p, acc.p,
+                (int64_t)nslot, (int64_t)bslot);
             if ((rc = check("k_bs_fill"))) return rc;
         } else {
             const int ng = (np + 63) >> kGroupBits;
@@ -1125,20 +1160,22 @@ static int plan_scatter(spmv_csr &h, PanelPlan &p, int rb, int32_t padded, DevPt
             const int32_t *src_col = h.d_col_idx;
             const float *src_val = h.d_vals;
             const uint16_t *src_row = rowloc.p;
+            int64_t src_len = h.nnz;                                // (the CSR arrays; the grouped copies: nnz + 8)
             if (ng > 1) {                                           // (one group: the bins' CSR ranges are grouped as they are)
                 SPMV_HIP_TRY(tcol.alloc((size_t)h.nnz + 8));
                 SPMV_HIP_TRY(tval.alloc((size_t)h.nnz + 8));
                 SPMV_HIP_TRY(trow.alloc((size_t)h.nnz + 8));
                 k_bs_group<<<dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s>>>(nb, np, brow.p, h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.p,
-                                                                                 tiles.p, tcol.p, tval.p, trow.p);
+                                                                                 tiles.p, tcol.p, tval.p, trow.p, h.nnz + 8);
                 if ((rc = check("k_bs_group"))) return rc;
-                src_col = tcol.p; src_val = tval.p; src_row = trow.p;
+                src_col = tcol.p; src_val = tval.p; src_row = trow.p; src_len = h.nnz + 8;
             }
             const int64_t nitems64 = (int64_t)ng * nb;
             if (nitems64 > INT_MAX / 2) { set_error("spmv_csr_plan(panel, binned, scattered products): %lld fill items", (long long)nitems64); return SPMV_ERR_INVALID; }
             const int nitems = (int)nitems64, nwg = (nitems + 3) / 4;
             k_bs_place<<<dim3(8u * (unsigned)((nwg + 7) / 8)), dim3(256), 0, s>>>(nb, np, nitems, src_col, src_val, src_row, tiles.p, pm.p,
-                                                                                 bbase.p, c16.p, pvals.p, acc.p);
+                                                                                 bbase.p, c16.p, pvals.p, acc.p, src_len, (int64_t)nslot,
+                                                                                 (int64_t)bslot);
             if ((rc = check("k_bs_place"))) return rc;
             SPMV_HIP_TRY(hipStreamSynchronize(s));                  // the grouped copies are freed here
         }
@@ -1178,6 +1215,7 @@ static int plan_scatter(spmv_csr &h, PanelPlan &p, int rb, int32_t padded, DevPt
     SPMV_HIP_TRY(hipStreamSynchronize(s));   // the temporaries (tiles, pm, rowloc) are freed on return
     p.padded = padded;
     p.bm_entries = bm;
+    p.bm_alloc = (int64_t)bslot;
     p.flagged_tiles = st[0];                 // (bins, in this flavour)
     p.long_rows = st[1];
     p.d_c16 = c16.release();
@@ -1274,12 +1312,12 @@ int plan_binned(spmv_csr &h, PanelPlan &p, int want_rows, bool scatter, hipStrea
     k_bin_pm<<<dim3((unsigned)np), dim3(256), 0, s>>>(nb, np, tiles.p, pbase.p, pm.p);
     if ((rc = check("k_bin_pm"))) return rc;
     if (scatter) return plan_scatter(h, p, rb, padded, brow, tiles, pm, pbase, s);
-    const size_t nslot = (size_t)padded + 264;                             // (a piece reads up to 256 entries past a tile's end)
+    const size_t nslot = (size_t)padded + kBinSlack;
     SPMV_HIP_TRY(c16.alloc(nslot));
     SPMV_HIP_TRY(pvals.alloc(nslot));
     SPMV_HIP_TRY(prod.alloc(nslot));
-    SPMV_HIP_TRY(r16.alloc((size_t)h.nnz + 264));
-    SPMV_HIP_TRY(hipMemsetAsync(r16.p + h.nnz, 0, sizeof(uint16_t) * 264, s));
+    SPMV_HIP_TRY(r16.alloc((size_t)h.nnz + kBinSlack));
+    SPMV_HIP_TRY(hipMemsetAsync(r16.p + h.nnz, 0, sizeof(uint16_t) * kBinSlack, s));
     SPMV_HIP_TRY(rowloc.alloc((size_t)h.nnz + 8));
     SPMV_HIP_TRY(hipMemsetAsync(c16.p, 0, sizeof(uint16_t) * nslot, s));     // (the pad slots of every panel: column 0, value 0)
     SPMV_HIP_TRY(hipMemsetAsync(pvals.p, 0, sizeof(float) * nslot, s));
@@ -1352,7 +1390,7 @@ static int launch_sums_e(const spmv_csr &h, const PanelPlan &p, float *y, hipStr
     static LdsOptIn optin;
     if (int rc = optin.ensure(reinterpret_cast<const void *>(&k_bin_sums<RB, E>), h.device, (int)lds)) return rc;
     k_bin_sums<RB, E><<<grid, block, lds, s>>>(p.nblocks, p.npanels, p.d_brow, p.d_tile_ptr, p.d_pm, p.d_r16, p.d_prod, p.d_lptr,
-                                               p.d_lrow, p.d_lcnt, y, (uint32_t)((p.padded + 264) * 4), (uint32_t)((h.nnz + 264) * 2));
+                                               p.d_lrow, p.d_lcnt, y, (uint32_t)((p.padded + kBinSlack) * 4), (uint32_t)((h.nnz + kBinSlack) * 2));
     return check("k_bin_sums");
 }
 template <int RB>
@@ -1368,7 +1406,7 @@ static int launch_bs_sums(const spmv_csr &h, const PanelPlan &p, float *y, hipSt
     static LdsOptIn optin;
     if (int rc = optin.ensure(reinterpret_cast<const void *>(&k_bs_sums<RB>), h.device, (int)lds)) return rc;
     k_bs_sums<RB><<<dim3((unsigned)p.nblocks), dim3(kWave), lds, s>>>(p.d_brow, p.d_bbase, p.d_bcnt, p.d_r16, p.d_prod, p.d_nlong, p.d_lrow, y,
-                                                                      (uint32_t)((p.bm_entries + kBlk + 16) * 4), (uint32_t)((p.bm_entries + kBlk + 16) * 2));
+                                                                      (uint32_t)(p.bm_alloc * 4), (uint32_t)(p.bm_alloc * 2));
     return check("k_bs_sums");
 }
 
@@ -1381,7 +1419,8 @@ int launch_binned(const spmv_csr &h, const PanelPlan &p, const float *x, float *
         if (int rc = optin.ensure(reinterpret_cast<const void *>(&k_bs_products), h.device, (int)lds)) return rc;
         const unsigned grid = p.splits == 1 ? 256u * (unsigned)((p.npanels + 255) / 256) : (unsigned)(p.npanels * p.splits);
         k_bs_products<<<dim3(grid), dim3(kProdThreads), lds, s>>>(p.splits, p.npanels, h.cols, p.d_pbase, p.d_c16,
-                                                                                              p.d_pvals, p.d_first_run, p.d_offset, x, p.d_prod);
+                                                                                              p.d_pvals, p.d_first_run, p.d_offset, x, p.d_prod,
+                                                                                              p.padded + 8, p.bm_alloc);
         if (int rc = check("k_bs_products")) return rc;
         return p.bin_rows == 16384 ? launch_bs_sums<16384>(h, p, y, s) : p.bin_rows == 8192 ? launch_bs_sums<8192>(h, p, y, s) : launch_bs_sums<4096>(h, p, y, s);
     }
@@ -1395,6 +1434,16 @@ int launch_binned(const spmv_csr &h, const PanelPlan &p, const float *x, float *
     }
     return p.bin_rows == 8192 ? launch_sums<8192>(h, p, y, s) : p.bin_rows == 4096 ? launch_sums<4096>(h, p, y, s) :
            p.bin_rows == 2048 ? launch_sums<2048>(h, p, y, s) : launch_sums<1024>(h, p, y, s);
+}
+
+int bounds_collect_binned(unsigned long long out[kBoundsSites][2])
+{
+#if defined(SPMV_CHECK_BOUNDS)
+    return bounds_collect_local(out);
+#else
+    (void)out;
+    return SPMV_ERR_INVALID;
+#endif
 }
 
 }  // namespace spmv

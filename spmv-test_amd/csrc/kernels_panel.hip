@@ -265,13 +265,16 @@ struct GatherRegs {   // one step between its gathers and its sums
 
 template <int kVec>
 __device__ __forceinline__ void panel_load(const u4 *__restrict__ c4, const f4 *__restrict__ v4, int base, int lane,
-                                           StepRegs<kVec> &r)
+                                           StepRegs<kVec> &r, int64_t slots)
 {
 #pragma unroll
     for (int j = 0; j < kVec; ++j) {
-        const int i = (base >> 2) + j * kWave + lane;
-        r.c[j] = __builtin_nontemporal_load(&c4[i]);
-        r.v[j] = __builtin_nontemporal_load(&v4[i]);
+        int i = (base >> 2) + j * kWave + lane;
+        int iv = i;                                                 // (packed, pvals: `slots` entries, panel_slots)
+        SPMV_BOUNDS_LOAD(okc, kSitePanelPacked, i, 16 * (int64_t)i, 16, 4 * slots);
+        SPMV_BOUNDS_LOAD(okv, kSitePanelVals, iv, 16 * (int64_t)iv, 16, 4 * slots);
+        r.c[j] = SPMV_BOUNDS_VALUE(okc, __builtin_nontemporal_load(&c4[i]));
+        r.v[j] = SPMV_BOUNDS_VALUE(okv, __builtin_nontemporal_load(&v4[iv]));
     }
 }
 
@@ -282,7 +285,7 @@ __global__ __launch_bounds__(kWave *kWavesPerWg) void k_panel(int wb0, int wb1, 
                                                               const uint32_t *__restrict__ packed,
                                                               const float *__restrict__ pvals,
                                                               const float *__restrict__ x, float *__restrict__ y,
-                                                              int np, int pw_bits)
+                                                              int np, int pw_bits, int64_t slots)
 {
     constexpr int kStep = kWave * 4 * kVec;
     __shared__ float ys_all[kWavesPerWg][kRw];
@@ -375,20 +378,20 @@ __global__ __launch_bounds__(kWave *kWavesPerWg) void k_panel(int wb0, int wb1, 
     GatherRegs<kVec> g0, g1;
     auto step_base = [&](int st) { return k0 + st * kStep; };
     if (nsteps > 0) {
-        panel_load(c4, v4, step_base(0), lane, s0);
-        if (nsteps > 1) panel_load(c4, v4, step_base(1), lane, s1);
+        panel_load(c4, v4, step_base(0), lane, s0, slots);
+        if (nsteps > 1) panel_load(c4, v4, step_base(1), lane, s1, slots);
         gather(step_base(0), s0, g0);
-        if (nsteps > 2) panel_load(c4, v4, step_base(2), lane, s0);
+        if (nsteps > 2) panel_load(c4, v4, step_base(2), lane, s0, slots);
     }
     for (int st = 0; st < nsteps; st += 2) {
         if (st + 1 < nsteps) {
             gather(step_base(st + 1), s1, g1);
-            if (st + 3 < nsteps) panel_load(c4, v4, step_base(st + 3), lane, s1);
+            if (st + 3 < nsteps) panel_load(c4, v4, step_base(st + 3), lane, s1, slots);
         }
         sum(step_base(st), g0);
         if (st + 2 < nsteps) {
             gather(step_base(st + 2), s0, g0);
-            if (st + 4 < nsteps) panel_load(c4, v4, step_base(st + 4), lane, s0);
+            if (st + 4 < nsteps) panel_load(c4, v4, step_base(st + 4), lane, s0, slots);
         }
         if (st + 1 < nsteps) sum(step_base(st + 1), g1);
     }
@@ -472,6 +475,9 @@ __global__ __launch_bounds__(kLdsWaves *kWave) void k_panel_lds(int nblocks, int
     __syncthreads();
     for (int i = lane; i < n; i += kWave) y[row0 + i] = ys[i];
 }
+
+// entries of d_packed / d_pvals of the sweep's plan: the last step of a block reads past its end
+size_t panel_slots(int64_t nnz) { return (size_t)nnz + 2 * kStepMax + 8; }
 
 int check_launch(const char *what)
 {
@@ -653,7 +659,7 @@ int build_panel(spmv_csr &h, PanelPlan &dst, int want_bits, int want_waves, int 
     DevPtr<float> pvals;
     DevPtr<int32_t> tiles;
     DevPtr<uint16_t> rowloc;
-    const size_t slots = (size_t)h.nnz + 2 * kStepMax + 8;   // the last step of a block reads past its end
+    const size_t slots = panel_slots(h.nnz);
     SPMV_HIP_TRY(packed.alloc(slots));
     SPMV_HIP_TRY(pvals.alloc(slots));
     SPMV_HIP_TRY(tiles.alloc((size_t)p.nblocks * (size_t)(p.npanels + 1)));
@@ -723,14 +729,26 @@ int launch_panel_plan(const spmv_csr &h, const PanelPlan &p, const float *x, flo
         const int g = (b1 - b0 + kWavesPerWg - 1) / kWavesPerWg;
         if (p.step_vecs == 4)
             k_panel<4><<<dim3((unsigned)g), dim3(kWave * kWavesPerWg), 0, s>>>(b0, b1, p.d_brow, h.d_row_ptr, p.d_tile_ptr,
-                                                                               p.d_packed, p.d_pvals, x, y, p.npanels, p.pw_bits);
+                                                                               p.d_packed, p.d_pvals, x, y, p.npanels, p.pw_bits,
+                                                                               panel_slots(h.nnz));
         else
             k_panel<8><<<dim3((unsigned)g), dim3(kWave * kWavesPerWg), 0, s>>>(b0, b1, p.d_brow, h.d_row_ptr, p.d_tile_ptr,
-                                                                               p.d_packed, p.d_pvals, x, y, p.npanels, p.pw_bits);
+                                                                               p.d_packed, p.d_pvals, x, y, p.npanels, p.pw_bits,
+                                                                               panel_slots(h.nnz));
         const int rc = check_launch("k_panel");
         if (rc) return rc;
     }
     return SPMV_OK;
+}
+
+int bounds_collect_panel(unsigned long long out[kBoundsSites][2])
+{
+#if defined(SPMV_CHECK_BOUNDS)
+    return bounds_collect_local(out);
+#else
+    (void)out;
+    return SPMV_ERR_INVALID;
+#endif
 }
 
 }  // namespace spmv

@@ -153,6 +153,7 @@ struct PanelPlan {
     int32_t *d_bcnt = nullptr;     // [nblocks] entries of the bin
     int32_t *d_nlong = nullptr;    // [nblocks] rows with spare accumulators (-1: the bin adds with LDS atomics)
     int64_t bm_entries = 0;        // entries of the bin-major arrays
+    int64_t bm_alloc = 0;          // ... as allocated: bm_entries + the slack of the sum launch's read-ahead (kernels_binned.hip kBsSlack)
 };
 
 // SPMV_XSKIP (kernels_xskip.hip): the matrix in input-major segments per block of 1024 outputs
@@ -299,6 +300,70 @@ int synth_fill(uint64_t seed, int64_t row0, int64_t n_local, int64_t rows, int64
                const int32_t *d_row_ptr, int32_t *d_col_idx, float *d_vals, hipStream_t s);
 int synth_x(uint64_t seed, int64_t j0, int64_t n, float *d_x, hipStream_t s);
 
+
+// ---- bounds-checked build (SPMV_CHECK_BOUNDS: lib/libspmv_hip_checked.so, a test aid) --------------------------------
+// The streams that read or write past a tile's or a bin's end on purpose (and rely on slack allocated behind the arrays)
+// check every access's byte range [lo, lo + len) against the array's allocated bytes.  A violation is recorded in a
+// table of the translation unit (no -fgpu-rdc: every .hip file has its own; site -> count, largest overrun in bytes) and
+// the access is NOT issued: a load is redirected to offset 0 and its value replaced by zero, a store is skipped.  Without
+// the define every macro below expands to nothing (or to its plain operand): the library's device code is unchanged.
+//   SPMV_BOUNDS_LOAD(ok, site, var, lo, len, limit)   declares bool ok; out of range: var (the offset the load uses) = 0
+//   SPMV_BOUNDS_VALUE(ok, v)                           v, or zero where !ok
+//   SPMV_BOUNDS_BUF(ok, site, voff, soff, len, limit)  a buffer load at voff + soff: out of range, both become 0 (else
+//                                                      the sum moves to voff: the scalar offset may not diverge)
+//   SPMV_BOUNDS_STORE(site, lo, len, limit) stmt;      the store runs only when in range
+enum BoundsSite {
+    kSiteBsSumsProd = 0, kSiteBsSumsAcc, kSiteBinSumsProd, kSiteBinSumsR16, kSiteBsProductsC16, kSiteBsProductsVals,
+    kSiteBsProductsStore, kSiteBsGroupStore, kSiteBsPlaceLoad, kSiteBsPlaceAcc, kSiteBsPlaceC16, kSiteBsFillAcc,
+    kSiteBsFillC16, kSitePanelPacked, kSitePanelVals,
+    kBoundsSites
+};
+#if defined(SPMV_CHECK_BOUNDS)
+namespace {
+// [site][0] = violations, [site][1] = largest overrun in bytes (this translation unit's kernels only)
+__device__ __attribute__((unused)) unsigned long long g_bounds[kBoundsSites][2];
+}
+#if defined(__HIPCC__)
+__device__ __forceinline__ bool bounds_in(int site, int64_t lo, int64_t len, int64_t limit)
+{
+    if (lo >= 0 && lo + len <= limit) return true;
+    atomicAdd(&g_bounds[site][0], 1ull);
+    atomicMax(&g_bounds[site][1], (unsigned long long)(lo < 0 ? -lo : lo + len - limit));
+    return false;
+}
+#endif
+// host: add this translation unit's table into out[site][2] and clear it (the device is synchronised first)
+static inline int bounds_collect_local(unsigned long long out[kBoundsSites][2])
+{
+    unsigned long long t[kBoundsSites][2] = {};
+    SPMV_HIP_TRY(hipDeviceSynchronize());
+    SPMV_HIP_TRY(hipMemcpyFromSymbol(t, HIP_SYMBOL(g_bounds), sizeof t));
+    const unsigned long long zero[kBoundsSites][2] = {};
+    SPMV_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_bounds), zero, sizeof zero));
+    for (int i = 0; i < kBoundsSites; ++i) {
+        out[i][0] += t[i][0];
+        if (t[i][1] > out[i][1]) out[i][1] = t[i][1];
+    }
+    return SPMV_OK;
+}
+#define SPMV_BOUNDS_LOAD(ok, site, var, lo, len, limit) \
+    const bool ok = ::spmv::bounds_in((site), (int64_t)(lo), (int64_t)(len), (int64_t)(limit)); \
+    if (!ok) var = 0
+#define SPMV_BOUNDS_VALUE(ok, v) ((ok) ? (v) : decltype(v){})
+#define SPMV_BOUNDS_BUF(ok, site, voff, soff, len, limit) \
+    const bool ok = ::spmv::bounds_in((site), (int64_t)(uint32_t)(voff) + (int64_t)(uint32_t)(soff), (int64_t)(len), (int64_t)(limit)); \
+    voff = ok ? voff + soff : 0; \
+    soff = 0
+#define SPMV_BOUNDS_STORE(site, lo, len, limit) if (::spmv::bounds_in((site), (int64_t)(lo), (int64_t)(len), (int64_t)(limit)))
+#else
+#define SPMV_BOUNDS_LOAD(ok, site, var, lo, len, limit)
+#define SPMV_BOUNDS_VALUE(ok, v) (v)
+#define SPMV_BOUNDS_BUF(ok, site, voff, soff, len, limit)
+#define SPMV_BOUNDS_STORE(site, lo, len, limit)
+#endif
+// kernels_binned.hip / kernels_panel.hip: their tables, added into out (SPMV_ERR_INVALID in the normal build)
+int bounds_collect_binned(unsigned long long out[kBoundsSites][2]);
+int bounds_collect_panel(unsigned long long out[kBoundsSites][2]);
 
 #if defined(__HIPCC__)
 // Stable scatter by key, 64 entries per step (k_panel_fill, k_bin_fill, k_bs_fill): which lanes hold a key that NO other lane of

@@ -39,6 +39,24 @@ def test_library_exports_nothing_else(pkg):
     assert syms and all(s.startswith("spmv_") for s in syms), syms
 
 
+def test_checked_library_exports_the_same_symbols_and_the_normal_one_is_not_instrumented(pkg):
+    """lib/libspmv_hip_checked.so (SPMV_CHECK_BOUNDS, tests/test_gpu_bounds.py) is the same C ABI; only it answers
+    spmv_debug_bounds -- the normal build says it is not instrumented (no device needed for that answer)."""
+    capi = pkg.capi
+
+    def exports(path):
+        out = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
+        return sorted(l.split()[-1] for l in out.splitlines() if " T " in l)
+
+    assert capi.CHECKED_LIB_PATH.exists(), f"{capi.CHECKED_LIB_PATH} missing: build() makes it"
+    normal = exports(capi.LIB_PATH)
+    assert "spmv_debug_bounds" in normal and exports(capi.CHECKED_LIB_PATH) == normal
+    assert capi.BOUNDS_SITES and len(set(capi.BOUNDS_SITES)) == len(capi.BOUNDS_SITES)
+    with pytest.raises(capi.SpmvError) as ei:
+        capi.debug_bounds()
+    assert ei.value.status == capi.ERR_INVALID and "not instrumented" in str(ei.value)
+
+
 def test_dist_library_exports_every_declared_symbol(pkg):
     """include/spmv_dist.h (the row-block exchange over RCCL for a C++ caller) vs libspmv_dist.so."""
     text = (ROOT / "include" / "spmv_dist.h").read_text()
