@@ -15,6 +15,12 @@
  *   CSR row i   = output index i in [0, rows)   (column i of the dense A)
  *   column idx  = input index j in [0, cols)    (row j of the dense A)
  *   y[i] = sum_k vals[k] * x[col_idx[k]],  k in [row_ptr[i], row_ptr[i+1])
+ *   Every term of row i counts and nothing else does: a column may repeat
+ *   (each occurrence adds its term), rows need not be sorted, IEEE rules hold
+ *   (Inf * 0 = NaN, +Inf + -Inf = NaN, subnormals kept), an x entry no row
+ *   refers to is never read into a sum, and an empty row is 0.  Only the
+ *   order of the fp32 additions is the variant's own.  SPMV_XSKIP differs
+ *   (see the enum): it leaves out the terms whose x is +-0.
  *   row_ptr has rows+1 int32 entries (row_ptr[rows] == nnz); the reference's
  *   CSRMatrix omits the last one and csr_naive.cu:15 substitutes nnz for it.
  *   nnz < 2^31 per handle; larger problems are row-block shards, one handle each.
@@ -106,6 +112,8 @@ enum spmv_variant {
                         /*   (awsp.cu:127-134), awsp_ref_kernel (awsp_ref.cu:52).  For dense-ish matrices (the    */
                         /*   reference's regime): the plan refuses when ceil(rows/1024) x cols exceeds 2^27, and  */
                         /*   rows must be sorted and duplicate-free.  Its plan COPIES the values, like PANEL.  */
+                        /* Its sum leaves out every term whose x is +-0, like the reference's asp skip: a    */
+                        /* value of Inf or NaN against x == 0 adds nothing here (NaN everywhere else).       */
     SPMV_VARIANT_COUNT = 9
 };
 
