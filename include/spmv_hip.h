@@ -244,6 +244,32 @@ SPMV_API int spmv_csr_time(spmv_csr_t *h, int variant, const float *d_x, float *
 SPMV_API int spmv_csr_run_host(spmv_csr_t *h, int variant, const float *x_host, float *y_host,
                                float *kernel_ms);
 
+/* ---- SpMM: one handle times k right-hand sides at once -------------------------------------------------------
+ * Y = A X, where X holds k vectors side by side: X is cols rows of ldx floats, row-major (column c of X is
+ * X[j*ldx + c], j < cols), Y is rows rows of ldy floats.  Column c < k of Y is A times column c of X under the CSR
+ * semantics above: every term counts and a repeated column adds each of its terms, rows need not be sorted, IEEE rules
+ * hold and subnormals are kept, an empty row gives 0, and an X row no nonzero refers to is never read into a sum.
+ * Limits: 1 <= k <= 64, ldx >= k, ldy >= k; d_X and d_Y 16-byte aligned (d_X may be NULL when cols == 0, d_Y when
+ * rows == 0).  Any ld >= k works; ldx % 4 == 0 and ldy % 4 == 0 together are the fast path (16-byte loads and stores;
+ * a run then reads the whole 16-byte block that holds X[j*ldx + k-1]).  Anything else, a null handle or another current
+ * device than the handle's is SPMV_ERR_INVALID, and nothing is launched.  Y[i*ldy + c] for c >= k is never written, and
+ * X[j*ldx + c] for c >= k is never read into a sum.
+ * spmv_csr_spmm_plan: a function of the pattern (row_ptr) alone -- not of the values, of k or of timing.  It reads row_ptr
+ * back and waits for the stream; it is idempotent, and spmv_csr_destroy frees it.  Its scratch for the partial sums of
+ * long rows is sized for k = 64.  vals are read live on every run: after an in-place update the next run uses them.
+ * spmv_csr_spmm: enqueue Y = A X on `stream`; asynchronous, allocates nothing, never waits: graph-capturable once the
+ * plan exists; SPMV_ERR_NOT_PLANNED without it.  Runs of one handle must be stream-ordered (the plan owns the scratch).
+ * Batch invariance: for one plan, Y[:, c] is bit-identical whatever k, ldx and ldy are, whichever position the column
+ * has in the batch and whatever the other columns of X hold (NaN and Inf included); two runs, and two handles of the same
+ * matrix, agree bit for bit.  The order of the fp32 additions of a row is the plan's own: fused multiply-adds in storage
+ * order, rows of more than 512 nonzeros summed per piece of 512 and the pieces added in order (no variant's order).
+ * spmv_csr_spmm_plan_bytes: device bytes of the plan (0 when not planned; negative for a null handle).
+ * spmv_csr_spmm_describe: the plan in one line ("row_cap=512 piece_len=512 long_rows=... pieces=..."). */
+SPMV_API int spmv_csr_spmm_plan(spmv_csr_t *h, void *stream);
+SPMV_API int spmv_csr_spmm(spmv_csr_t *h, int k, const float *d_X, int64_t ldx, float *d_Y, int64_t ldy, void *stream);
+SPMV_API int64_t spmv_csr_spmm_plan_bytes(const spmv_csr_t *h);
+SPMV_API int spmv_csr_spmm_describe(const spmv_csr_t *h, char *buf, int n);
+
 /* ---- dense baselines (reference slots cublas / naive / tiling) ---------
  * y[i] = sum_j x[j] * A[j*N+i] on the dense device matrix.
  * replaces: cublas_gemv_gpu (cublas.cu:4-44), naive_kernel (naive.cu:4-11),

@@ -48,6 +48,10 @@ SIGNATURES = {
     "spmv_csr_plan": (C.c_int, [_H, C.c_int, _vp]),
     "spmv_csr_run": (C.c_int, [_H, C.c_int, _f32p, _f32p, _vp]),
     "spmv_csr_values_changed": (C.c_int, [_H]),
+    "spmv_csr_spmm_plan": (C.c_int, [_H, _vp]),
+    "spmv_csr_spmm": (C.c_int, [_H, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, _vp]),
+    "spmv_csr_spmm_plan_bytes": (C.c_int64, [_H]),
+    "spmv_csr_spmm_describe": (C.c_int, [_H, C.c_char_p, C.c_int]),
     "spmv_csr_plan_get": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int32)]),
     "spmv_csr_plan_set": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int32), _vp]),
     "spmv_csr_plan_like": (C.c_int, [_H, _H, C.c_int, _vp]),
@@ -213,6 +217,34 @@ class CsrMatrix:
         lo, hi = C.c_int64(), C.c_int64()
         check(lib().spmv_csr_column_range(self._h, C.byref(lo), C.byref(hi), _stream_handle(stream)))
         return lo.value, hi.value
+
+    # -- SpMM: k right-hand sides at once (spmv_csr_spmm) ---------------------------------------------------------
+    def spmm_plan(self, stream=None) -> None:
+        """The plan of spmv_csr_spmm (a function of row_ptr; reads it back and waits for the stream once)."""
+        check(lib().spmv_csr_spmm_plan(self._h, _stream_handle(stream)))
+
+    def spmm(self, X, Y, stream=None) -> None:
+        """Enqueue Y[:, :k] = A X with k = X.shape[1].  X: (cols, k) and Y: (rows, k or more) 2-D float32 device tensors
+        with stride(1) == 1; the leading dimensions are their stride(0).  Y's columns from k on are not written."""
+        import torch
+        for name, t in (("X", X), ("Y", Y)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1:
+                raise ValueError(f"spmm: {name} must be a 2-D float32 tensor with stride(1) == 1")
+        k = X.shape[1]
+        if X.shape[0] != self.cols or Y.shape[0] != self.rows or Y.shape[1] < k:
+            raise ValueError(f"spmm: X {tuple(X.shape)} and Y {tuple(Y.shape)} do not fit a {self.rows} x {self.cols} matrix")
+        check(lib().spmv_csr_spmm(self._h, k, _ptr(X), X.stride(0), _ptr(Y), Y.stride(0), _stream_handle(stream)))
+
+    def spmm_describe(self) -> str:
+        buf = C.create_string_buffer(256)
+        check(lib().spmv_csr_spmm_describe(self._h, buf, 256))
+        return buf.value.decode()
+
+    def spmm_plan_bytes(self) -> int:
+        n = lib().spmv_csr_spmm_plan_bytes(self._h)
+        if n < 0:
+            check(n)
+        return n
 
     def values_changed(self) -> None:
         """The caller rewrote vals (borrowed arrays): plans that hold a copy of them are stale from here on."""

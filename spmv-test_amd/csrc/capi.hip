@@ -479,6 +479,47 @@ int spmv_csr_run(spmv_csr_t *h, int variant, const float *d_x, float *d_y, void 
     }
 }
 
+int spmv_csr_spmm_plan(spmv_csr_t *h, void *stream)
+{
+    if (!h) { set_error("spmv_csr_spmm_plan: null handle"); return SPMV_ERR_INVALID; }
+    if (int rc = require_current(h->device, "spmv_csr_spmm_plan")) return rc;
+    return plan_spmm(*h, (hipStream_t)stream);
+}
+
+int spmv_csr_spmm(spmv_csr_t *h, int k, const float *d_X, int64_t ldx, float *d_Y, int64_t ldy, void *stream)
+{
+    if (!h) { set_error("spmv_csr_spmm: null handle"); return SPMV_ERR_INVALID; }
+    if (k < 1 || k > 64 || ldx < k || ldy < k) {
+        set_error("spmv_csr_spmm: k = %d, ldx = %lld, ldy = %lld (need 1 <= k <= 64, ldx >= k, ldy >= k)", k, (long long)ldx,
+                  (long long)ldy);
+        return SPMV_ERR_INVALID;
+    }
+    if ((!d_X && h->cols > 0) || (!d_Y && h->rows > 0)) { set_error("spmv_csr_spmm: null X or Y"); return SPMV_ERR_INVALID; }
+    if (!aligned16(d_X) || !aligned16(d_Y)) { set_error("spmv_csr_spmm: X and Y must be 16-byte aligned"); return SPMV_ERR_INVALID; }
+    if (ldx > INT64_MAX / 4 / (h->cols > 0 ? h->cols : 1) || ldy > INT64_MAX / 4 / (h->rows > 0 ? h->rows : 1)) {
+        set_error("spmv_csr_spmm: ldx = %lld or ldy = %lld overflows 64-bit byte offsets", (long long)ldx, (long long)ldy);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(h->device, "spmv_csr_spmm")) return rc;
+    if (!h->plan_spmm.ready) { set_error("spmv_csr_spmm used before spmv_csr_spmm_plan"); return SPMV_ERR_NOT_PLANNED; }
+    return launch_spmm(*h, k, d_X, ldx, d_Y, ldy, (hipStream_t)stream);
+}
+
+int64_t spmv_csr_spmm_plan_bytes(const spmv_csr_t *h)
+{
+    if (!h) { set_error("spmv_csr_spmm_plan_bytes: null handle"); return SPMV_ERR_INVALID; }
+    return spmm_plan_bytes(*h);
+}
+
+int spmv_csr_spmm_describe(const spmv_csr_t *h, char *buf, int n)
+{
+    if (!h || !buf || n <= 0) { set_error("spmv_csr_spmm_describe: bad argument"); return SPMV_ERR_INVALID; }
+    const SpmmPlan &p = h->plan_spmm;
+    if (!p.ready) snprintf(buf, (size_t)n, "not planned");
+    else snprintf(buf, (size_t)n, "row_cap=%d piece_len=%d long_rows=%d pieces=%d", p.row_cap, p.piece_len, p.n_long, p.pieces);
+    return SPMV_OK;
+}
+
 int spmv_csr_values_changed(spmv_csr_t *h)
 {
     if (!h) { set_error("spmv_csr_values_changed: null handle"); return SPMV_ERR_INVALID; }

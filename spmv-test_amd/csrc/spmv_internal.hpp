@@ -186,6 +186,19 @@ struct WavePlan {
     int64_t blocks = 0, win_blocks = 0;   // blocks of block_rows rows, and how many have a window
 };
 
+// spmv_csr_spmm (kernels_spmm.hip): the rows too long for one lane group, cut into pieces at plan-fixed boundaries
+struct SpmmPlan {
+    bool ready = false;
+    int n_long = 0, pieces = 0;
+    int row_cap = 0, piece_len = 0;   // rows of more than row_cap nonzeros go in pieces of piece_len
+    int32_t *d_order = nullptr;       // [rows] the rows in the order the row kernel takes them (by length per 4096 rows)
+    int32_t *d_long_row = nullptr;    // [n_long] the rows, ascending
+    int32_t *d_long_first = nullptr;  // [n_long + 1] first piece of every row
+    int32_t *d_piece_k0 = nullptr;    // [pieces] first nonzero of a piece
+    int32_t *d_piece_len = nullptr;   // [pieces] its length
+    float *d_partial = nullptr;       // [pieces * 64] scratch of a run: a piece's sums of up to 64 columns
+};
+
 }  // namespace spmv
 
 struct spmv_tcsr;    // kernels_tcsr.hip
@@ -209,6 +222,7 @@ struct spmv_csr {
     bool auto_made_tiled = false;  // SPMV_AUTO made the TILED plan it looked at (and may release it)
     spmv::XskipPlan plan_xskip;    // SPMV_XSKIP
     spmv::WavePlan plan_wave;      // SPMV_WAVE_PIPE
+    spmv::SpmmPlan plan_spmm;      // spmv_csr_spmm
     int auto_variant = -1;         // SPMV_AUTO: the variant its plan chose (-1 = not planned)
     uint64_t values_gen = 0;       // bumped by spmv_csr_values_changed: plans that copied vals before that are stale
 };
@@ -256,6 +270,11 @@ int launch_binned(const spmv_csr &h, const PanelPlan &p, const float *x, float *
 void destroy_binned(PanelPlan &p);
 double binned_tile_nonzeros(const spmv_csr &h, int bin_rows);
 void destroy_plans(spmv_csr &h);
+// kernels_spmm.hip: spmv_csr_spmm
+int plan_spmm(spmv_csr &h, hipStream_t s);
+int launch_spmm(const spmv_csr &h, int k, const float *X, int64_t ldx, float *Y, int64_t ldy, hipStream_t s);
+int64_t spmm_plan_bytes(const spmv_csr &h);
+void destroy_spmm(SpmmPlan &p);
 void drop_tiled_plan(spmv_csr &h);   // SPMV_AUTO resolved to another variant: the TILED plan it looked at is released
 
 int dense_to_csr(int M, int N, const float *d_A, hipStream_t s, spmv_csr_t **out);

@@ -1,0 +1,167 @@
+#!/usr/bin/env python3
+"""tools/spmm_time.py -- spmv_csr_spmm (k right-hand sides at once) against k back-to-back SPMV_AUTO runs and rocSPARSE.
+
+One JSON line per (workload, k): the plan's time and bytes, the SpMM time, the time of k spmv_csr_run(SPMV_AUTO) calls on
+the same data (each column of X copied out to a contiguous x first, outside the timed window), the algorithmic bytes
+4 (rows + 1) + 8 nnz + 4 k (cols + rows) and their share of 8 TB/s, and rocsparse_spmm (CSR, row-major dense B and C, loaded
+with ctypes as tools/vendor_compare.py loads rocSPARSE) with its largest difference to our Y.  Times: HIP events, warmed up,
+median of --reps windows of --iters launches.
+
+    python tools/spmm_time.py [--workloads c2:8192,c2:0,c3:8192,c3:0,c4:8192,c4:0] [--ks 1,4,8,16,32,64] [--out FILE]
+"""
+import argparse
+import ctypes
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tools"))
+import __graft_entry__ as ge  # noqa: E402
+from vendor_compare import F32, I32, RocSparse  # noqa: E402
+
+PEAK_BPS = 8e12
+ROW_ORDER = 0                                          # rocsparse_order_row
+SPMM_SIZE, SPMM_PREP, SPMM_COMPUTE = 1, 2, 3           # rocsparse_spmm_stage_*
+
+
+def timed(fn, iters, reps):
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(3):
+        fn()
+    out = []
+    for _ in range(reps):
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1) / iters)
+    return statistics.median(out)
+
+
+def rocsparse_spmm(rs, rows, cols, nnz, d_rp, d_ci, d_va, X, Y, iters, reps):
+    """(ms per call, preprocess ms) of rocsparse_spmm with the default algorithm; Y receives its result."""
+    import torch
+    L = rs.L
+    vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int
+    L.rocsparse_create_dnmat_descr.argtypes = [ctypes.POINTER(vp), i64, i64, i64, vp, i32, i32]
+    L.rocsparse_destroy_dnmat_descr.argtypes = [vp]
+    L.rocsparse_spmm.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, ctypes.POINTER(ctypes.c_size_t), vp]
+    one, zero = ctypes.c_float(1.0), ctypes.c_float(0.0)
+    mat, mb, mc = vp(), vp(), vp()
+    k = X.shape[1]
+    rs._ok(L.rocsparse_create_csr_descr(ctypes.byref(mat), rows, cols, nnz, d_rp.data_ptr(), d_ci.data_ptr(),
+                                        d_va.data_ptr(), I32, I32, 0, F32), "create_csr")
+    rs._ok(L.rocsparse_create_dnmat_descr(ctypes.byref(mb), cols, k, X.stride(0), X.data_ptr(), F32, ROW_ORDER), "dnmat B")
+    rs._ok(L.rocsparse_create_dnmat_descr(ctypes.byref(mc), rows, k, Y.stride(0), Y.data_ptr(), F32, ROW_ORDER), "dnmat C")
+    size = ctypes.c_size_t(0)
+
+    def call(stage, buf):
+        return L.rocsparse_spmm(rs.h, 111, 111, ctypes.byref(one), mat, mb, ctypes.byref(zero), mc, F32, 0, stage,
+                                ctypes.byref(size), buf)
+    try:
+        rs._ok(call(SPMM_SIZE, None), "spmm buffer_size")
+        buf = torch.empty(max(int(size.value), 16), dtype=torch.uint8, device=X.device)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        rs._ok(call(SPMM_PREP, buf.data_ptr()), "spmm preprocess")
+        e1.record()
+        torch.cuda.synchronize()
+        prep = e0.elapsed_time(e1)
+        Y.zero_()
+        ms = timed(lambda: call(SPMM_COMPUTE, buf.data_ptr()), iters, reps)
+        return ms, prep
+    finally:
+        L.rocsparse_destroy_dnmat_descr(mb)
+        L.rocsparse_destroy_dnmat_descr(mc)
+        L.rocsparse_destroy_spmat_descr(mat)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workloads", default="c2:8192,c2:0,c3:8192,c3:0,c4:8192,c4:0")
+    ap.add_argument("--ks", default="1,4,8,16,32,64")
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--no-rocsparse", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+    pkg = ge.load_package()
+    capi, W = pkg.capi, pkg.workloads
+    dev = torch.device("cuda:0")
+    out = open(a.out, "a") if a.out else None
+    rs = None if a.no_rocsparse else RocSparse()
+    if rs is not None:
+        rs._ok(rs.L.rocsparse_set_stream(rs.h, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "set_stream")
+
+    def emit(**kv):
+        line = json.dumps(kv)
+        print(line, flush=True)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+
+    for spec in a.workloads.split(","):
+        name, band = spec.split(":")
+        w = W.config(name, band=int(band))
+        rp = W.row_ptr(w)
+        nnz = int(rp[-1])
+        d_rp = torch.from_numpy(rp).to(dev)
+        d_ci = torch.empty(nnz, dtype=torch.int32, device=dev)
+        d_va = torch.empty(nnz, dtype=torch.float32, device=dev)
+        capi.synth_fill(w.seed, 0, w.rows, w.rows, w.cols, w.band, d_rp, d_ci, d_va)
+        A = capi.CsrMatrix.from_device(w.rows, w.cols, d_rp, d_ci, d_va)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        A.spmm_plan()
+        plan_ms = (time.perf_counter() - t0) * 1e3
+        A.plan(capi.AUTO)
+        label = f"{name}_band{band}"
+        for k in (int(s) for s in a.ks.split(",")):
+            X = torch.randn((w.cols, k), generator=torch.Generator(device=dev).manual_seed(k), device=dev)
+            Y = torch.empty((w.rows, k), dtype=torch.float32, device=dev)
+            ms = timed(lambda: A.spmm(X, Y), a.iters, a.reps)
+            xs = [X[:, c].contiguous() for c in range(k)]
+            ys = [torch.empty(w.rows, dtype=torch.float32, device=dev) for _ in range(k)]
+
+            def loop():
+                for c in range(k):
+                    A.run(capi.AUTO, xs[c], ys[c])
+            ms_loop = timed(loop, max(1, a.iters // k), a.reps)
+            torch.cuda.synchronize()
+            diff_auto = max(float((Y[:, c] - ys[c]).abs().max()) for c in range(k))
+            B = 4 * (w.rows + 1) + 8 * nnz + 4 * k * (w.cols + w.rows)
+            row = dict(workload=label, k=k, rows=w.rows, cols=w.cols, nnz=nnz, plan_ms=round(plan_ms, 2),
+                       plan_bytes=A.spmm_plan_bytes(), plan=A.spmm_describe(), spmm_ms=round(ms, 4),
+                       k_auto_runs_ms=round(ms_loop, 4), speedup_vs_k_auto=round(ms_loop / ms, 2),
+                       algorithmic_bytes=B, frac_of_8TBs=round(B / (ms * 1e-3) / PEAK_BPS, 3),
+                       max_diff_vs_auto=diff_auto, auto_plan=A.plan_describe(capi.AUTO))
+            del xs, ys
+            if rs is not None:
+                Yr = torch.empty_like(Y)
+                try:
+                    rms, rprep = rocsparse_spmm(rs, w.rows, w.cols, nnz, d_rp, d_ci, d_va, X, Yr, a.iters, a.reps)
+                    torch.cuda.synchronize()
+                    row.update(rocsparse_ms=round(rms, 4), rocsparse_prep_ms=round(rprep, 2),
+                               rocsparse_max_diff=float((Yr - Y).abs().max()))
+                except RuntimeError as e:
+                    row.update(rocsparse_error=str(e))
+                del Yr
+            emit(**row)
+            del X, Y
+            torch.cuda.empty_cache()
+        A.close()
+        del d_rp, d_ci, d_va
+        torch.cuda.empty_cache()
+    if rs is not None:
+        rs.close()
+
+
+if __name__ == "__main__":
+    main()
