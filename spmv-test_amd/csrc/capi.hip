@@ -81,6 +81,34 @@ int require_current(int device, const char *what)
 
 static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// The host-buffer conveniences time two launches: the reference's TIME_KERNEL (kernel.hpp:31-48) times a single COLD
+// launch, code object load included -- that figure is kept (spmv_last_first_launch_ms); *kernel_ms is the second launch:
+// the kernel.  Each launch runs on the null stream and is followed by a device synchronisation.
+template <typename Launch>
+static int time_cold_then_warm(const Launch &launch, float *kernel_ms)
+{
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    const int rc = [&]() -> int {
+        SPMV_HIP_TRY(hipEventCreate(&ev[0]));
+        SPMV_HIP_TRY(hipEventCreate(&ev[1]));
+        float ms = 0.0f;
+        for (int i = 0; i < 2; ++i) {
+            SPMV_HIP_TRY(hipEventRecord(ev[0], nullptr));
+            const int r = launch();
+            SPMV_HIP_TRY(hipEventRecord(ev[1], nullptr));
+            SPMV_HIP_TRY(hipEventSynchronize(ev[1]));
+            if (r) return r;
+            SPMV_HIP_TRY(hipEventElapsedTime(i == 0 ? &g_first_launch_ms : &ms, ev[0], ev[1]));
+            SPMV_HIP_TRY(hipDeviceSynchronize());
+        }
+        if (kernel_ms) *kernel_ms = ms;
+        return SPMV_OK;
+    }();
+    for (hipEvent_t e : ev)
+        if (e) (void)hipEventDestroy(e);
+    return rc;
+}
+
 }  // namespace spmv
 
 using namespace spmv;
@@ -164,10 +192,10 @@ int spmv_csr_validate(const spmv_csr_t *h, void *stream)
     int32_t bad[4];
     DevPtr<int32_t> d_bad;
     SPMV_HIP_TRY(d_bad.alloc(4));
-    SPMV_HIP_TRY(hipMemcpyAsync(d_bad.p, init, sizeof init, hipMemcpyHostToDevice, st));
-    int rc = launch_validate(h, d_bad.p, st);
+    SPMV_HIP_TRY(hipMemcpyAsync(d_bad.get(), init, sizeof init, hipMemcpyHostToDevice, st));
+    int rc = launch_validate(h, d_bad.get(), st);
     if (rc) return rc;
-    SPMV_HIP_TRY(hipMemcpyAsync(bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost, st));
+    SPMV_HIP_TRY(hipMemcpyAsync(bad, d_bad.get(), sizeof bad, hipMemcpyDeviceToHost, st));
     SPMV_HIP_TRY(hipStreamSynchronize(st));
     if (bad[2] != 0 || (int64_t)bad[3] != h->nnz) {
         set_error("malformed CSR: row_ptr[0]=%d row_ptr[rows]=%d, expected 0 and nnz=%lld", bad[2], bad[3],
@@ -205,17 +233,17 @@ int spmv_csr_create_host(int64_t rows, int64_t cols, int64_t nnz, const int32_t 
     SPMV_HIP_TRY(rp.alloc((size_t)rows + 1));
     SPMV_HIP_TRY(ci.alloc((size_t)nnz));
     SPMV_HIP_TRY(va.alloc((size_t)nnz));
-    SPMV_HIP_TRY(hipMemcpy(rp.p, row_ptr, sizeof(int32_t) * ((size_t)rows + 1), hipMemcpyHostToDevice));
+    SPMV_HIP_TRY(hipMemcpy(rp.get(), row_ptr, sizeof(int32_t) * ((size_t)rows + 1), hipMemcpyHostToDevice));
     if (nnz > 0) {
-        SPMV_HIP_TRY(hipMemcpy(ci.p, col_idx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
-        SPMV_HIP_TRY(hipMemcpy(va.p, vals, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice));
+        SPMV_HIP_TRY(hipMemcpy(ci.get(), col_idx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
+        SPMV_HIP_TRY(hipMemcpy(va.get(), vals, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice));
     }
     spmv_csr *h = new (std::nothrow) spmv_csr();
     if (!h) { set_error("out of host memory"); return SPMV_ERR_INVALID; }
     h->rows = rows; h->cols = cols; h->nnz = nnz;
-    h->owns_arrays = true;
     if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
-    h->d_row_ptr = rp.release(); h->d_col_idx = ci.release(); h->d_vals = va.release();
+    h->d_row_ptr = rp; h->d_col_idx = ci; h->d_vals = va;
+    h->own_row_ptr = std::move(rp); h->own_col_idx = std::move(ci); h->own_vals = std::move(va);
     if ((rc = spmv_csr_validate(h, nullptr))) {
         spmv_csr_destroy(h);
         return rc;
@@ -242,7 +270,6 @@ int spmv_csr_create_device(int64_t rows, int64_t cols, int64_t nnz, const int32_
     if (!h) { set_error("out of host memory"); return SPMV_ERR_INVALID; }
     h->rows = rows; h->cols = cols; h->nnz = nnz;
     h->d_row_ptr = d_row_ptr; h->d_col_idx = d_col_idx; h->d_vals = d_vals;
-    h->owns_arrays = false;
     if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
     if ((rc = spmv_csr_validate(h, nullptr))) {
         delete h;
@@ -272,13 +299,11 @@ int spmv_csr_from_dense_host(int M, int N, const float *A_host, void *stream, sp
     int rc = require_device();
     if (rc) return rc;
     const size_t bytes = sizeof(float) * (size_t)M * (size_t)N;
-    float *d_A = nullptr;
-    SPMV_HIP_TRY(hipMalloc((void **)&d_A, bytes ? bytes : 4));
-    hipError_t e = hipMemcpyAsync(d_A, A_host, bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e != hipSuccess) { (void)hipFree(d_A); return hip_fail(e, "hipMemcpyAsync(A)", __FILE__, __LINE__); }
-    rc = dense_to_csr(M, N, d_A, (hipStream_t)stream, out);
+    DevPtr<float> dA;
+    SPMV_HIP_TRY(dA.alloc((size_t)M * (size_t)N));
+    SPMV_HIP_TRY(hipMemcpyAsync(dA.get(), A_host, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+    rc = dense_to_csr(M, N, dA.get(), (hipStream_t)stream, out);
     (void)hipStreamSynchronize((hipStream_t)stream);
-    (void)hipFree(d_A);
     return rc;
 }
 
@@ -309,10 +334,10 @@ int spmv_csr_column_range(const spmv_csr_t *h, int64_t *col_min, int64_t *col_ma
     hipStream_t st = (hipStream_t)stream;
     DevPtr<int32_t> d;
     SPMV_HIP_TRY(d.alloc(2));
-    int rc = launch_column_range(*h, d.p, st);
+    int rc = launch_column_range(*h, d.get(), st);
     if (rc) return rc;
     int32_t out[2] = {0, 0};
-    SPMV_HIP_TRY(hipMemcpyAsync(out, d.p, sizeof out, hipMemcpyDeviceToHost, st));
+    SPMV_HIP_TRY(hipMemcpyAsync(out, d.get(), sizeof out, hipMemcpyDeviceToHost, st));
     SPMV_HIP_TRY(hipStreamSynchronize(st));
     *col_min = out[1] < 0 ? h->cols : (int64_t)out[0];
     *col_max = (int64_t)out[1];
@@ -323,11 +348,8 @@ int spmv_csr_destroy(spmv_csr_t *h)
 {
     if (!h) return SPMV_OK;
     int rc = SPMV_OK;
-    auto fr = [&](const void *p) {
-        if (p && hipFree(const_cast<void *>(p)) != hipSuccess) rc = SPMV_ERR_HIP;
-    };
-    if (h->owns_arrays) { fr(h->d_row_ptr); fr(h->d_col_idx); fr(h->d_vals); }
-    destroy_plans(*h);
+    for (hipError_t e : {h->own_row_ptr.reset(), h->own_col_idx.reset(), h->own_vals.reset()})
+        if (e != hipSuccess) rc = SPMV_ERR_HIP;
     delete h;
     if (rc) set_error("hipFree failed in spmv_csr_destroy");
     return rc;
@@ -352,7 +374,7 @@ static int plan_auto(spmv_csr &h, hipStream_t s)
     if (rc) return rc;
     // a TILED plan the caller made stays; one made here for a look is released when another variant is chosen (up to
     // 6 bytes per nonzero of column copies nobody would read)
-    auto release_tiled = [&]() { if (h.auto_made_tiled) drop_tiled_plan(h); h.auto_made_tiled = false; };
+    auto release_tiled = [&]() { if (h.auto_made_tiled) h.plan_tiled = ChunkPlan{}; h.auto_made_tiled = false; };
     const ChunkPlan &p = h.plan_tiled;
     const double cost_tiled = p.model_cost;
     const bool little_staged = p.nchunks > 0 && 2 * ((int64_t)p.staged_full + p.nsorted) < p.nchunks &&
@@ -379,7 +401,7 @@ static int plan_auto(spmv_csr &h, hipStream_t s)
                     release_tiled();
                     return SPMV_OK;
                 }
-                destroy_panel(h.plan_auto_panel);
+                h.plan_auto_panel = PanelPlan{};
             } else if (rc != SPMV_ERR_INVALID) {
                 return rc;   // INVALID: outside the layout's limits -> on with the other candidates
             }
@@ -592,7 +614,7 @@ int spmv_csr_plan_set(spmv_csr_t *h, int variant, const int32_t params[8], void 
         case SPMV_ADAPTIVE: rc = plan_adaptive_with(*h, params[1], s); break;
         case SPMV_TILED: rc = plan_tiled_with(*h, params[1], params[2], params[3] != 0, s); break;
         case SPMV_PANEL: rc = build_panel(*h, variant == SPMV_AUTO ? h->plan_auto_panel : h->plan_panel, params[4], params[5], params[6], s); break;
-        case SPMV_XSKIP: destroy_xskip(h->plan_xskip); rc = plan_xskip(*h, s); break;   // always rebuilt: the values are a copy
+        case SPMV_XSKIP: h->plan_xskip = XskipPlan{}; rc = plan_xskip(*h, s); break;   // always rebuilt: the values are a copy
         default: set_error("spmv_csr_plan_set: unknown variant %d", target); return SPMV_ERR_VARIANT;
     }
     if (rc == SPMV_OK && variant == SPMV_AUTO) h->auto_variant = target;
@@ -717,19 +739,6 @@ int spmv_csr_time(spmv_csr_t *h, int variant, const float *d_x, float *d_y, int 
     return rc;
 }
 
-// RAII for the host-buffer conveniences
-namespace {
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 4); }
-};
-struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-}  // namespace
-
 int spmv_csr_run_host(spmv_csr_t *h, int variant, const float *x_host, float *y_host, float *kernel_ms)
 {
     if (!h || (!x_host && h->cols > 0) || (!y_host && h->rows > 0)) {
@@ -738,32 +747,13 @@ int spmv_csr_run_host(spmv_csr_t *h, int variant, const float *x_host, float *y_
     }
     int rc = spmv_csr_plan(h, variant, nullptr);
     if (rc) return rc;
-    DevBuf dx, dy;
-    EventPair ev;
-    SPMV_HIP_TRY(dx.alloc(sizeof(float) * (size_t)h->cols));
-    SPMV_HIP_TRY(dy.alloc(sizeof(float) * (size_t)h->rows));
-    SPMV_HIP_TRY(hipMemcpy(dx.p, x_host, sizeof(float) * (size_t)h->cols, hipMemcpyHostToDevice));
-    SPMV_HIP_TRY(hipEventCreate(&ev.a));
-    SPMV_HIP_TRY(hipEventCreate(&ev.b));
-    // two launches: the reference's TIME_KERNEL (kernel.hpp:31-48) times a single COLD launch, code object load
-    // included -- that figure is kept (spmv_last_first_launch_ms); *kernel_ms is the second launch: the kernel
-    SPMV_HIP_TRY(hipEventRecord(ev.a, nullptr));
-    rc = spmv_csr_run(h, variant, (const float *)dx.p, (float *)dy.p, nullptr);
-    SPMV_HIP_TRY(hipEventRecord(ev.b, nullptr));
-    SPMV_HIP_TRY(hipEventSynchronize(ev.b));
-    if (rc) return rc;
-    SPMV_HIP_TRY(hipEventElapsedTime(&g_first_launch_ms, ev.a, ev.b));   // what the reference's macro would have printed
-    SPMV_HIP_TRY(hipDeviceSynchronize());
-    SPMV_HIP_TRY(hipEventRecord(ev.a, nullptr));
-    rc = spmv_csr_run(h, variant, (const float *)dx.p, (float *)dy.p, nullptr);
-    SPMV_HIP_TRY(hipEventRecord(ev.b, nullptr));
-    SPMV_HIP_TRY(hipEventSynchronize(ev.b));
-    if (rc) return rc;
-    float ms = 0.0f;
-    SPMV_HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-    if (kernel_ms) *kernel_ms = ms;
-    SPMV_HIP_TRY(hipDeviceSynchronize());
-    SPMV_HIP_TRY(hipMemcpy(y_host, dy.p, sizeof(float) * (size_t)h->rows, hipMemcpyDeviceToHost));
+    DevPtr<float> dx, dy;
+    SPMV_HIP_TRY(dx.alloc((size_t)h->cols));
+    SPMV_HIP_TRY(dy.alloc((size_t)h->rows));
+    SPMV_HIP_TRY(hipMemcpy(dx.get(), x_host, sizeof(float) * (size_t)h->cols, hipMemcpyHostToDevice));
+    if ((rc = time_cold_then_warm([&] { return spmv_csr_run(h, variant, dx.get(), dy.get(), nullptr); }, kernel_ms)))
+        return rc;
+    SPMV_HIP_TRY(hipMemcpy(y_host, dy.get(), sizeof(float) * (size_t)h->rows, hipMemcpyDeviceToHost));
     return SPMV_OK;
 }
 
@@ -776,32 +766,15 @@ int spmv_dense_gemv_host(int M, int N, const float *A_host, const float *x_host,
     }
     int rc = require_device();
     if (rc) return rc;
-    DevBuf dA, dx, dy;
-    EventPair ev;
-    SPMV_HIP_TRY(dA.alloc(sizeof(float) * (size_t)M * (size_t)N));
-    SPMV_HIP_TRY(dx.alloc(sizeof(float) * (size_t)M));
-    SPMV_HIP_TRY(dy.alloc(sizeof(float) * (size_t)N));
-    SPMV_HIP_TRY(hipMemcpy(dA.p, A_host, sizeof(float) * (size_t)M * (size_t)N, hipMemcpyHostToDevice));
-    SPMV_HIP_TRY(hipMemcpy(dx.p, x_host, sizeof(float) * (size_t)M, hipMemcpyHostToDevice));
-    SPMV_HIP_TRY(hipEventCreate(&ev.a));
-    SPMV_HIP_TRY(hipEventCreate(&ev.b));
-    SPMV_HIP_TRY(hipEventRecord(ev.a, nullptr));
-    rc = dense_gemv(M, N, (const float *)dA.p, (const float *)dx.p, (float *)dy.p, mode, nullptr);   // the first, cold launch
-    SPMV_HIP_TRY(hipEventRecord(ev.b, nullptr));
-    SPMV_HIP_TRY(hipEventSynchronize(ev.b));
-    if (rc) return rc;
-    SPMV_HIP_TRY(hipEventElapsedTime(&g_first_launch_ms, ev.a, ev.b));
-    SPMV_HIP_TRY(hipDeviceSynchronize());
-    SPMV_HIP_TRY(hipEventRecord(ev.a, nullptr));
-    rc = dense_gemv(M, N, (const float *)dA.p, (const float *)dx.p, (float *)dy.p, mode, nullptr);
-    SPMV_HIP_TRY(hipEventRecord(ev.b, nullptr));
-    SPMV_HIP_TRY(hipEventSynchronize(ev.b));
-    if (rc) return rc;
-    float ms = 0.0f;
-    SPMV_HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-    if (kernel_ms) *kernel_ms = ms;
-    SPMV_HIP_TRY(hipDeviceSynchronize());
-    SPMV_HIP_TRY(hipMemcpy(y_host, dy.p, sizeof(float) * (size_t)N, hipMemcpyDeviceToHost));
+    DevPtr<float> dA, dx, dy;
+    SPMV_HIP_TRY(dA.alloc((size_t)M * (size_t)N));
+    SPMV_HIP_TRY(dx.alloc((size_t)M));
+    SPMV_HIP_TRY(dy.alloc((size_t)N));
+    SPMV_HIP_TRY(hipMemcpy(dA.get(), A_host, sizeof(float) * (size_t)M * (size_t)N, hipMemcpyHostToDevice));
+    SPMV_HIP_TRY(hipMemcpy(dx.get(), x_host, sizeof(float) * (size_t)M, hipMemcpyHostToDevice));
+    if ((rc = time_cold_then_warm([&] { return dense_gemv(M, N, dA.get(), dx.get(), dy.get(), mode, nullptr); }, kernel_ms)))
+        return rc;
+    SPMV_HIP_TRY(hipMemcpy(y_host, dy.get(), sizeof(float) * (size_t)N, hipMemcpyDeviceToHost));
     return SPMV_OK;
 }
 
@@ -825,11 +798,11 @@ int spmv_tcsr_from_dense_host(int M, int N, const float *A_host, void *stream, s
 {
     int rc = tcsr_check_dims(M, N, A_host, out);
     if (rc) return rc;
-    DevBuf dA;
+    DevPtr<float> dA;
     const size_t bytes = sizeof(float) * (size_t)M * (size_t)N;
-    SPMV_HIP_TRY(dA.alloc(bytes));
-    SPMV_HIP_TRY(hipMemcpyAsync(dA.p, A_host, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
-    rc = tcsr_from_dense(M, N, (const float *)dA.p, (hipStream_t)stream, out);
+    SPMV_HIP_TRY(dA.alloc((size_t)M * (size_t)N));
+    SPMV_HIP_TRY(hipMemcpyAsync(dA.get(), A_host, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+    rc = tcsr_from_dense(M, N, dA.get(), (hipStream_t)stream, out);
     (void)hipStreamSynchronize((hipStream_t)stream);
     return rc;
 }
@@ -859,35 +832,18 @@ int spmv_tcsr_run_host(const spmv_tcsr_t *h, const float *x_host, float *y_host,
     tcsr_sizes(*h, &nb, &nw, &nv);
     int M = 0, N = 0;
     tcsr_dims(*h, &M, &N);
-    DevBuf dx, dy;
-    EventPair ev;
-    SPMV_HIP_TRY(dx.alloc(sizeof(float) * (size_t)M));
-    SPMV_HIP_TRY(dy.alloc(sizeof(float) * (size_t)N));
-    SPMV_HIP_TRY(hipMemcpy(dx.p, x_host, sizeof(float) * (size_t)M, hipMemcpyHostToDevice));
-    SPMV_HIP_TRY(hipEventCreate(&ev.a));
-    SPMV_HIP_TRY(hipEventCreate(&ev.b));
-    SPMV_HIP_TRY(hipEventRecord(ev.a, nullptr));
-    int rc = tcsr_run(*h, (const float *)dx.p, (float *)dy.p, nullptr);   // the first, cold launch
-    SPMV_HIP_TRY(hipEventRecord(ev.b, nullptr));
-    SPMV_HIP_TRY(hipEventSynchronize(ev.b));
-    if (rc) return rc;
-    SPMV_HIP_TRY(hipEventElapsedTime(&g_first_launch_ms, ev.a, ev.b));
-    SPMV_HIP_TRY(hipDeviceSynchronize());
-    SPMV_HIP_TRY(hipEventRecord(ev.a, nullptr));
-    rc = tcsr_run(*h, (const float *)dx.p, (float *)dy.p, nullptr);
-    SPMV_HIP_TRY(hipEventRecord(ev.b, nullptr));
-    SPMV_HIP_TRY(hipEventSynchronize(ev.b));
-    if (rc) return rc;
-    float ms = 0.0f;
-    SPMV_HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-    if (kernel_ms) *kernel_ms = ms;
-    SPMV_HIP_TRY(hipMemcpy(y_host, dy.p, sizeof(float) * (size_t)N, hipMemcpyDeviceToHost));
+    DevPtr<float> dx, dy;
+    SPMV_HIP_TRY(dx.alloc((size_t)M));
+    SPMV_HIP_TRY(dy.alloc((size_t)N));
+    SPMV_HIP_TRY(hipMemcpy(dx.get(), x_host, sizeof(float) * (size_t)M, hipMemcpyHostToDevice));
+    if (int rc = time_cold_then_warm([&] { return tcsr_run(*h, dx.get(), dy.get(), nullptr); }, kernel_ms)) return rc;
+    SPMV_HIP_TRY(hipMemcpy(y_host, dy.get(), sizeof(float) * (size_t)N, hipMemcpyDeviceToHost));
     return SPMV_OK;
 }
 
 int spmv_tcsr_destroy(spmv_tcsr_t *h)
 {
-    tcsr_free(h);
+    delete h;
     return SPMV_OK;
 }
 
@@ -912,11 +868,11 @@ int spmv_bitmap_from_dense_host(int format, int M, int N, const float *A_host, v
 {
     int rc = bitmap_check_dims(format, M, N, A_host, out);
     if (rc) return rc;
-    DevBuf dA;
+    DevPtr<float> dA;
     const size_t bytes = sizeof(float) * (size_t)M * (size_t)N;
-    SPMV_HIP_TRY(dA.alloc(bytes));
-    SPMV_HIP_TRY(hipMemcpyAsync(dA.p, A_host, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
-    rc = bitmap_from_dense(format, M, N, (const float *)dA.p, (hipStream_t)stream, out);
+    SPMV_HIP_TRY(dA.alloc((size_t)M * (size_t)N));
+    SPMV_HIP_TRY(hipMemcpyAsync(dA.get(), A_host, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+    rc = bitmap_from_dense(format, M, N, dA.get(), (hipStream_t)stream, out);
     (void)hipStreamSynchronize((hipStream_t)stream);
     return rc;
 }
@@ -946,35 +902,18 @@ int spmv_bitmap_run_host(const spmv_bitmap_t *h, const float *x_host, float *y_h
     if (!h || !x_host || !y_host) { set_error("spmv_bitmap_run_host: null argument"); return SPMV_ERR_INVALID; }
     int M = 0, N = 0;
     bitmap_info(*h, nullptr, &M, &N, nullptr, nullptr, nullptr);
-    DevBuf dx, dy;
-    EventPair ev;
-    SPMV_HIP_TRY(dx.alloc(sizeof(float) * (size_t)M));
-    SPMV_HIP_TRY(dy.alloc(sizeof(float) * (size_t)N));
-    SPMV_HIP_TRY(hipMemcpy(dx.p, x_host, sizeof(float) * (size_t)M, hipMemcpyHostToDevice));
-    SPMV_HIP_TRY(hipEventCreate(&ev.a));
-    SPMV_HIP_TRY(hipEventCreate(&ev.b));
-    SPMV_HIP_TRY(hipEventRecord(ev.a, nullptr));
-    int rc = bitmap_run(*h, (const float *)dx.p, (float *)dy.p, nullptr);   // the first, cold launch
-    SPMV_HIP_TRY(hipEventRecord(ev.b, nullptr));
-    SPMV_HIP_TRY(hipEventSynchronize(ev.b));
-    if (rc) return rc;
-    SPMV_HIP_TRY(hipEventElapsedTime(&g_first_launch_ms, ev.a, ev.b));
-    SPMV_HIP_TRY(hipDeviceSynchronize());
-    SPMV_HIP_TRY(hipEventRecord(ev.a, nullptr));
-    rc = bitmap_run(*h, (const float *)dx.p, (float *)dy.p, nullptr);
-    SPMV_HIP_TRY(hipEventRecord(ev.b, nullptr));
-    SPMV_HIP_TRY(hipEventSynchronize(ev.b));
-    if (rc) return rc;
-    float ms = 0.0f;
-    SPMV_HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-    if (kernel_ms) *kernel_ms = ms;
-    SPMV_HIP_TRY(hipMemcpy(y_host, dy.p, sizeof(float) * (size_t)N, hipMemcpyDeviceToHost));
+    DevPtr<float> dx, dy;
+    SPMV_HIP_TRY(dx.alloc((size_t)M));
+    SPMV_HIP_TRY(dy.alloc((size_t)N));
+    SPMV_HIP_TRY(hipMemcpy(dx.get(), x_host, sizeof(float) * (size_t)M, hipMemcpyHostToDevice));
+    if (int rc = time_cold_then_warm([&] { return bitmap_run(*h, dx.get(), dy.get(), nullptr); }, kernel_ms)) return rc;
+    SPMV_HIP_TRY(hipMemcpy(y_host, dy.get(), sizeof(float) * (size_t)N, hipMemcpyDeviceToHost));
     return SPMV_OK;
 }
 
 int spmv_bitmap_destroy(spmv_bitmap_t *h)
 {
-    bitmap_free(h);
+    delete h;
     return SPMV_OK;
 }
 

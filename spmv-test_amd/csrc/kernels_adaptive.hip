@@ -1160,27 +1160,6 @@ __global__ void k_plan_spans(int nchunks, int chunk, const int32_t *__restrict__
 }
 
 // ---------------------------------------------------------------------------
-static int check_launch(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return SPMV_OK;
-}
-
-static void free_plan(ChunkPlan &p)
-{
-    if (p.d_lb) (void)hipFree(p.d_lb);
-    if (p.d_carry) (void)hipFree(p.d_carry);
-    if (p.d_win) (void)hipFree(p.d_win);
-    if (p.d_col16) (void)hipFree(p.d_col16);
-    if (p.d_list16) (void)hipFree(p.d_list16);
-    if (p.d_list32) (void)hipFree(p.d_list32);
-    if (p.d_perm) (void)hipFree(p.d_perm);
-    if (p.d_list_sorted) (void)hipFree(p.d_list_sorted);
-    if (p.d_blk) (void)hipFree(p.d_blk);
-    p = ChunkPlan();
-}
-
 static int default_passes(int block) { return block == 1024 ? 12 : (block == 512 ? 4 : 2); }
 
 
@@ -1190,14 +1169,14 @@ static int build_plan_impl(const spmv_csr &h, int block, int maxpass, hipStream_
 static int build_plan(const spmv_csr &h, int block, int maxpass, hipStream_t s, ChunkPlan &p, int *single, int *full)
 {
     const int rc = build_plan_impl(h, block, maxpass, s, p, single, full);
-    if (rc) free_plan(p);
+    if (rc) p = ChunkPlan{};
     return rc;
 }
 
 static int build_plan_impl(const spmv_csr &h, int block, int maxpass, hipStream_t s, ChunkPlan &p, int *single, int *full)
 {
     const bool windows = maxpass > 0;
-    free_plan(p);
+    p = ChunkPlan{};
     p.block = block;
     p.maxpass = maxpass;
     // LDS region: what 2048 resident threads per CU allow (a 144 KiB region with one 1024-thread
@@ -1229,8 +1208,8 @@ static int build_plan_impl(const spmv_csr &h, int block, int maxpass, hipStream_
     if (single) *single = 0;
     if (full) *full = 0;
     if (p.nchunks == 0) return SPMV_OK;
-    SPMV_HIP_TRY(hipMalloc((void **)&p.d_lb, sizeof(int32_t) * ((size_t)p.nchunks + 1)));
-    SPMV_HIP_TRY(hipMalloc((void **)&p.d_carry, sizeof(float) * (size_t)p.nchunks));
+    SPMV_HIP_TRY(p.d_lb.alloc((size_t)p.nchunks + 1));
+    SPMV_HIP_TRY(p.d_carry.alloc((size_t)p.nchunks));
     hipLaunchKernelGGL(k_plan_chunks, dim3((p.nchunks + 1 + 255) / 256), dim3(256), 0, s, h.rows, p.nchunks, chunk,
                        h.d_row_ptr, p.d_lb);
     int rc = check_launch("k_plan_chunks");
@@ -1238,20 +1217,20 @@ static int build_plan_impl(const spmv_csr &h, int block, int maxpass, hipStream_
     {
         DevPtr<int32_t> cnt;
         SPMV_HIP_TRY(cnt.alloc(1));
-        SPMV_HIP_TRY(hipMemsetAsync(cnt.p, 0, sizeof(int32_t), s));
+        SPMV_HIP_TRY(hipMemsetAsync(cnt.get(), 0, sizeof(int32_t), s));
         if (p.nchunks > 1) {
             hipLaunchKernelGGL(k_plan_spans, dim3((p.nchunks - 1 + 255) / 256), dim3(256), 0, s, p.nchunks, chunk,
-                               h.d_row_ptr, p.d_lb, cnt.p);
+                               h.d_row_ptr, p.d_lb, cnt.get());
             if ((rc = check_launch("k_plan_spans"))) return rc;
         }
         int32_t spans = 0;
-        SPMV_HIP_TRY(hipMemcpyAsync(&spans, cnt.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        SPMV_HIP_TRY(hipMemcpyAsync(&spans, cnt.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
         SPMV_HIP_TRY(hipStreamSynchronize(s));
         p.spanning_rows = spans;
     }
     if (windows) {
         // [2*nchunks] windows + 6 words of statistics (the last two: the 64-bit sum of the modelled chunk costs)
-        SPMV_HIP_TRY(hipMalloc((void **)&p.d_win, sizeof(int32_t) * (2 * (size_t)p.nchunks + 6)));
+        SPMV_HIP_TRY(p.d_win.alloc(2 * (size_t)p.nchunks + 6));
         int32_t *d_stats = p.d_win + 2 * (size_t)p.nchunks;
         SPMV_HIP_TRY(hipMemsetAsync(d_stats, 0, 6 * sizeof(int32_t), s));
         hipLaunchKernelGGL(k_plan_windows, dim3(p.nchunks), dim3(256), 0, s, h.nnz, h.cols, p.nchunks, chunk,
@@ -1296,19 +1275,19 @@ static int build_col16(const spmv_csr &h, ChunkPlan &p, hipStream_t s)
     SPMV_HIP_TRY(flags.alloc((size_t)p.nchunks));
     SPMV_HIP_TRY(pos.alloc((size_t)p.nchunks));
     SPMV_HIP_TRY(total.alloc(1));
-    SPMV_HIP_TRY(hipMalloc((void **)&p.d_col16, sizeof(uint16_t) * chunk * (size_t)p.nchunks));
+    SPMV_HIP_TRY(p.d_col16.alloc(chunk * (size_t)p.nchunks));
     // block lists (kBlkMax ids per chunk): SPMV_BLOCKS=0 keeps contiguous windows only
     bool want_blocks = true;
     if (const char *e = getenv("SPMV_BLOCKS")) want_blocks = atoi(e) != 0;
     DevPtr<int32_t> nblk;
     SPMV_HIP_TRY(nblk.alloc(1));
-    SPMV_HIP_TRY(hipMemsetAsync(nblk.p, 0, sizeof(int32_t), s));
-    if (want_blocks) SPMV_HIP_TRY(hipMalloc((void **)&p.d_blk, sizeof(int32_t) * (size_t)kBlkMax * (size_t)p.nchunks));
+    SPMV_HIP_TRY(hipMemsetAsync(nblk.get(), 0, sizeof(int32_t), s));
+    if (want_blocks) SPMV_HIP_TRY(p.d_blk.alloc((size_t)kBlkMax * (size_t)p.nchunks));
     int rc;
     auto run = [&](const int32_t *blk_arg, int dry) {
-        if (p.block == 256) return launch_plan_col16<256>(h, p, flags.p, nblk.p, blk_arg, dry, s);
-        if (p.block == 512) return launch_plan_col16<512>(h, p, flags.p, nblk.p, blk_arg, dry, s);
-        return launch_plan_col16<1024>(h, p, flags.p, nblk.p, blk_arg, dry, s);
+        if (p.block == 256) return launch_plan_col16<256>(h, p, flags.get(), nblk.get(), blk_arg, dry, s);
+        if (p.block == 512) return launch_plan_col16<512>(h, p, flags.get(), nblk.get(), blk_arg, dry, s);
+        return launch_plan_col16<1024>(h, p, flags.get(), nblk.get(), blk_arg, dry, s);
     };
     if (want_blocks) {
         // counting run first: the block-list instantiation of the kernel costs every chunk a few percent (spills),
@@ -1316,23 +1295,20 @@ static int build_col16(const spmv_csr &h, ChunkPlan &p, hipStream_t s)
         // chunks among power-law rows: not worth it)
         if ((rc = run(p.d_blk, 1))) return rc;
         int32_t cand = 0;
-        SPMV_HIP_TRY(hipMemcpyAsync(&cand, nblk.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        SPMV_HIP_TRY(hipMemcpyAsync(&cand, nblk.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
         SPMV_HIP_TRY(hipStreamSynchronize(s));
-        if (4 * (int64_t)cand < p.nchunks) {
-            (void)hipFree(p.d_blk);
-            p.d_blk = nullptr;
-        }
-        SPMV_HIP_TRY(hipMemsetAsync(nblk.p, 0, sizeof(int32_t), s));
+        if (4 * (int64_t)cand < p.nchunks) (void)p.d_blk.reset();
+        SPMV_HIP_TRY(hipMemsetAsync(nblk.get(), 0, sizeof(int32_t), s));
     }
     if ((rc = run(p.d_blk, 0))) return rc;
-    SPMV_HIP_TRY(hipMemcpyAsync(pos.p, flags.p, sizeof(int32_t) * (size_t)p.nchunks, hipMemcpyDeviceToDevice, s));
-    if ((rc = exclusive_scan_i32(pos.p, p.nchunks, total.p, s))) return rc;
+    SPMV_HIP_TRY(hipMemcpyAsync(pos.get(), flags.get(), sizeof(int32_t) * (size_t)p.nchunks, hipMemcpyDeviceToDevice, s));
+    if ((rc = exclusive_scan_i32(pos.get(), p.nchunks, total.get(), s))) return rc;
     int32_t n16 = 0, nb = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&n16, total.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipMemcpyAsync(&nb, nblk.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(&n16, total.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(&nb, nblk.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
     SPMV_HIP_TRY(hipStreamSynchronize(s));
     p.nblk_chunks = nb;
-    if (nb == 0 && p.d_blk) { (void)hipFree(p.d_blk); p.d_blk = nullptr; }
+    if (nb == 0) (void)p.d_blk.reset();
     // too few eligible chunks to pay for the 2-byte copy (counting the sorted chunks with them: those read 4 bytes of
     // perm instead of col_idx either way): back to 32-bit columns
     if (2 * ((int64_t)n16 + p.nsorted_marked) < p.nchunks) {
@@ -1340,8 +1316,8 @@ static int build_col16(const spmv_csr &h, ChunkPlan &p, hipStream_t s)
         if ((rc = check_launch("k_plan_unblock"))) return rc;
         SPMV_HIP_TRY(hipStreamSynchronize(s));
         p.nblk_chunks = 0;
-        (void)hipFree(p.d_col16); p.d_col16 = nullptr;
-        if (p.d_blk) { (void)hipFree(p.d_blk); p.d_blk = nullptr; }
+        (void)p.d_col16.reset();
+        (void)p.d_blk.reset();
     }
     return SPMV_OK;
 }
@@ -1355,14 +1331,14 @@ static int count_block_list_chunks(const spmv_csr &h, ChunkPlan &p, hipStream_t 
     DevPtr<int32_t> nblk, some;
     SPMV_HIP_TRY(nblk.alloc(1));
     SPMV_HIP_TRY(some.alloc(1));   // a non-null list pointer turns the block analysis on; a counting run never writes it
-    SPMV_HIP_TRY(hipMemsetAsync(nblk.p, 0, sizeof(int32_t), s));
+    SPMV_HIP_TRY(hipMemsetAsync(nblk.get(), 0, sizeof(int32_t), s));
     int rc;
-    if (p.block == 256) rc = launch_plan_col16<256>(h, p, nullptr, nblk.p, some.p, 1, s);
-    else if (p.block == 512) rc = launch_plan_col16<512>(h, p, nullptr, nblk.p, some.p, 1, s);
-    else rc = launch_plan_col16<1024>(h, p, nullptr, nblk.p, some.p, 1, s);
+    if (p.block == 256) rc = launch_plan_col16<256>(h, p, nullptr, nblk.get(), some.get(), 1, s);
+    else if (p.block == 512) rc = launch_plan_col16<512>(h, p, nullptr, nblk.get(), some.get(), 1, s);
+    else rc = launch_plan_col16<1024>(h, p, nullptr, nblk.get(), some.get(), 1, s);
     if (rc) return rc;
     int32_t cnt = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&cnt, nblk.p, sizeof cnt, hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(&cnt, nblk.get(), sizeof cnt, hipMemcpyDeviceToHost, s));
     SPMV_HIP_TRY(hipStreamSynchronize(s));
     *out = cnt;
     return SPMV_OK;
@@ -1379,10 +1355,10 @@ static int launch_plan_sorted(const spmv_csr &h, ChunkPlan &p, const int32_t *d_
 // (16-bit / sorted / 32-bit) the launch walks.
 static int build_lists(const spmv_csr &h, ChunkPlan &p, hipStream_t s)
 {
-    if (p.d_list16) { (void)hipFree(p.d_list16); p.d_list16 = nullptr; }
-    if (p.d_list32) { (void)hipFree(p.d_list32); p.d_list32 = nullptr; }
-    if (p.d_list_sorted) { (void)hipFree(p.d_list_sorted); p.d_list_sorted = nullptr; }
-    if (p.d_perm) { (void)hipFree(p.d_perm); p.d_perm = nullptr; }
+    (void)p.d_list16.reset();
+    (void)p.d_list32.reset();
+    (void)p.d_list_sorted.reset();
+    (void)p.d_perm.reset();
     p.n16 = p.nsorted = 0;
     if (p.nchunks == 0 || !p.d_win || p.persist) return SPMV_OK;
     int rc;
@@ -1392,29 +1368,29 @@ static int build_lists(const spmv_csr &h, ChunkPlan &p, hipStream_t s)
     SPMV_HIP_TRY(t16.alloc(1));
     SPMV_HIP_TRY(ts.alloc(1));
     const unsigned g = (unsigned)((p.nchunks + 255) / 256);
-    hipLaunchKernelGGL(k_plan_kinds, dim3(g), dim3(256), 0, s, p.nchunks, p.d_win, f16.p, fs.p);
+    hipLaunchKernelGGL(k_plan_kinds, dim3(g), dim3(256), 0, s, p.nchunks, p.d_win, f16.get(), fs.get());
     if ((rc = check_launch("k_plan_kinds"))) return rc;
-    if ((rc = exclusive_scan_i32(f16.p, p.nchunks, t16.p, s))) return rc;
-    if ((rc = exclusive_scan_i32(fs.p, p.nchunks, ts.p, s))) return rc;
+    if ((rc = exclusive_scan_i32(f16.get(), p.nchunks, t16.get(), s))) return rc;
+    if ((rc = exclusive_scan_i32(fs.get(), p.nchunks, ts.get(), s))) return rc;
     int32_t n16 = 0, ns = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&n16, t16.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipMemcpyAsync(&ns, ts.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(&n16, t16.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(&ns, ts.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
     SPMV_HIP_TRY(hipStreamSynchronize(s));
     p.n16 = n16;
     p.nsorted = ns;
     if (n16 == 0 && ns == 0) return SPMV_OK;   // every chunk runs the 32-bit body: no lists needed
-    SPMV_HIP_TRY(hipMalloc((void **)&p.d_list16, sizeof(int32_t) * (size_t)(n16 ? n16 : 1)));
-    SPMV_HIP_TRY(hipMalloc((void **)&p.d_list_sorted, sizeof(int32_t) * (size_t)(ns ? ns : 1)));
-    SPMV_HIP_TRY(hipMalloc((void **)&p.d_list32, sizeof(int32_t) * (size_t)(p.nchunks - n16 - ns ? p.nchunks - n16 - ns : 1)));
-    hipLaunchKernelGGL(k_plan_lists, dim3(g), dim3(256), 0, s, p.nchunks, p.d_win, f16.p, fs.p, p.d_list16, p.d_list_sorted,
+    SPMV_HIP_TRY(p.d_list16.alloc((size_t)n16));
+    SPMV_HIP_TRY(p.d_list_sorted.alloc((size_t)ns));
+    SPMV_HIP_TRY(p.d_list32.alloc((size_t)(p.nchunks - n16 - ns)));
+    hipLaunchKernelGGL(k_plan_lists, dim3(g), dim3(256), 0, s, p.nchunks, p.d_win, f16.get(), fs.get(), p.d_list16, p.d_list_sorted,
                        p.d_list32);
     if ((rc = check_launch("k_plan_lists"))) return rc;
     if (ns > 0) {
-        // one slot of chunk words per SORTED chunk (fs.p: its rank among them, the order of list_sorted)
-        SPMV_HIP_TRY(hipMalloc((void **)&p.d_perm, sizeof(uint32_t) * (size_t)chunk_of(p.block) * (size_t)ns));
-        if (p.block == 256) rc = launch_plan_sorted<256>(h, p, fs.p, s);
-        else if (p.block == 512) rc = launch_plan_sorted<512>(h, p, fs.p, s);
-        else rc = launch_plan_sorted<1024>(h, p, fs.p, s);
+        // one slot of chunk words per SORTED chunk (fs.get(): its rank among them, the order of list_sorted)
+        SPMV_HIP_TRY(p.d_perm.alloc((size_t)chunk_of(p.block) * (size_t)ns));
+        if (p.block == 256) rc = launch_plan_sorted<256>(h, p, fs.get(), s);
+        else if (p.block == 512) rc = launch_plan_sorted<512>(h, p, fs.get(), s);
+        else rc = launch_plan_sorted<1024>(h, p, fs.get(), s);
         if (rc) return rc;
     }
     SPMV_HIP_TRY(hipStreamSynchronize(s));   // the scans' temporaries are freed on return
@@ -1431,7 +1407,7 @@ static int finish_tiled(spmv_csr &h, bool col16, hipStream_t s)
 {
     int rc = col16 ? build_col16(h, h.plan_tiled, s) : SPMV_OK;
     if (rc == SPMV_OK) rc = build_lists(h, h.plan_tiled, s);
-    if (rc) free_plan(h.plan_tiled);
+    if (rc) h.plan_tiled = ChunkPlan{};
     return rc;
 }
 
@@ -1444,7 +1420,7 @@ int plan_tiled_with(spmv_csr &h, int block, int maxpass, bool col16, hipStream_t
     int rc = build_plan(h, block, maxpass, s, h.plan_tiled, nullptr, nullptr);
     if (rc == SPMV_OK && col16) rc = build_col16(h, h.plan_tiled, s);
     if (rc == SPMV_OK) rc = build_lists(h, h.plan_tiled, s);
-    if (rc) free_plan(h.plan_tiled);
+    if (rc) h.plan_tiled = ChunkPlan{};
     return rc;
 }
 
@@ -1506,7 +1482,7 @@ int plan_adaptive(spmv_csr &h, bool tiled, hipStream_t s)
                 int rc = build_plan(h, cands[k], default_passes(cands[k]), s, h.plan_tiled, nullptr, nullptr);
                 if (rc) return rc;
                 int lists = 0;
-                if ((rc = count_block_list_chunks(h, h.plan_tiled, s, &lists))) { free_plan(h.plan_tiled); return rc; }
+                if ((rc = count_block_list_chunks(h, h.plan_tiled, s, &lists))) { h.plan_tiled = ChunkPlan{}; return rc; }
                 if (lists >= 0.9 * h.plan_tiled.nchunks) return finish_tiled(h, true, s);
             }
         }
@@ -1557,7 +1533,7 @@ int plan_adaptive(spmv_csr &h, bool tiled, hipStream_t s)
     DevPtr<float> xt, yt;
     SPMV_HIP_TRY(xt.alloc((size_t)h.cols));
     SPMV_HIP_TRY(yt.alloc((size_t)h.rows));
-    SPMV_HIP_TRY(hipMemsetAsync(xt.p, 0, sizeof(float) * (size_t)(h.cols ? h.cols : 1), s));
+    SPMV_HIP_TRY(hipMemsetAsync(xt.get(), 0, sizeof(float) * (size_t)(h.cols ? h.cols : 1), s));
     hipEvent_t e0, e1;
     SPMV_HIP_TRY(hipEventCreate(&e0));
     SPMV_HIP_TRY(hipEventCreate(&e1));
@@ -1569,11 +1545,11 @@ int plan_adaptive(spmv_csr &h, bool tiled, hipStream_t s)
     // slower one every other run
     auto time_plan = [&](int reps, int launches, float &ms) -> int {
         int r = SPMV_OK;
-        for (int i = 0; i < 2 && r == SPMV_OK; ++i) r = launch_adaptive(h, xt.p, yt.p, true, s);
+        for (int i = 0; i < 2 && r == SPMV_OK; ++i) r = launch_adaptive(h, xt.get(), yt.get(), true, s);
         bool timed = true;
         for (int rep = 0; rep < reps && timed && r == SPMV_OK; ++rep) {
             timed = hipEventRecord(e0, s) == hipSuccess;
-            for (int i = 0; i < launches && r == SPMV_OK; ++i) r = launch_adaptive(h, xt.p, yt.p, true, s);
+            for (int i = 0; i < launches && r == SPMV_OK; ++i) r = launch_adaptive(h, xt.get(), yt.get(), true, s);
             timed = timed && hipEventRecord(e1, s) == hipSuccess && hipEventSynchronize(e1) == hipSuccess;
             float t = 0.0f;
             timed = timed && hipEventElapsedTime(&t, e0, e1) == hipSuccess;
@@ -1625,24 +1601,11 @@ int plan_adaptive(spmv_csr &h, bool tiled, hipStream_t s)
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    if (rc) { free_plan(h.plan_tiled); return rc; }
+    if (rc) { h.plan_tiled = ChunkPlan{}; return rc; }
     if (!best.set) return SPMV_OK;  // no nonzeros: the (empty) plan built last stands
     // rebuild the winner (plans are cheap next to the trials)
     if ((rc = build_plan(h, best.block, best.maxpass, s, h.plan_tiled, nullptr, nullptr))) return rc;
     return finish_tiled(h, best.narrow != 0, s);
-}
-
-void drop_tiled_plan(spmv_csr &h) { free_plan(h.plan_tiled); }
-
-void destroy_plans(spmv_csr &h)
-{
-    free_plan(h.plan_adaptive);
-    free_plan(h.plan_tiled);
-    destroy_panel(h.plan_panel);
-    destroy_panel(h.plan_auto_panel);
-    destroy_xskip(h.plan_xskip);
-    destroy_wave(h.plan_wave);
-    destroy_spmm(h.plan_spmm);
 }
 
 static int resident_workgroups(int device, int block, int waves_simd)

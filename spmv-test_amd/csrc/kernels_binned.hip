@@ -48,13 +48,6 @@ constexpr int kBinSlack = 264;             // entries behind d_prod / d_r16 (mod
 using u4 = unsigned __attribute__((ext_vector_type(4)));
 using f4 = float __attribute__((ext_vector_type(4)));
 
-int check(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return SPMV_OK;
-}
-
 // ---- plan kernels ------------------------------------------------------------------------------------------------
 // nonzeros of every panel: total[p] = sum over bins of the tile counts, rounded up to a multiple of 8 (16-byte loads)
 __global__ __launch_bounds__(256) void k_bin_panel_totals(int nb, int np, int round, const int32_t *__restrict__ tile_ptr, int32_t *__restrict__ total)
@@ -1058,31 +1051,6 @@ __global__ __launch_bounds__(256) void k_bin_rewrite(int np, int e, int rb, cons
 
 }  // namespace
 
-void destroy_binned(PanelPlan &p)
-{
-    if (p.d_c16) (void)hipFree(p.d_c16);
-    if (p.d_r16) (void)hipFree(p.d_r16);
-    if (p.d_pm) (void)hipFree(p.d_pm);
-    if (p.d_pbase) (void)hipFree(p.d_pbase);
-    if (p.d_prod) (void)hipFree(p.d_prod);
-    if (p.d_lptr) (void)hipFree(p.d_lptr);
-    if (p.d_lrow) (void)hipFree(p.d_lrow);
-    if (p.d_lcnt) (void)hipFree(p.d_lcnt);
-    if (p.d_offset) (void)hipFree(p.d_offset);
-    if (p.d_first_run) (void)hipFree(p.d_first_run);
-    if (p.d_bbase) (void)hipFree(p.d_bbase);
-    if (p.d_bcnt) (void)hipFree(p.d_bcnt);
-    if (p.d_nlong) (void)hipFree(p.d_nlong);
-    p.d_offset = p.d_first_run = p.d_bbase = p.d_bcnt = p.d_nlong = nullptr;
-    p.scatter_mode = false;
-    p.d_lptr = p.d_lcnt = nullptr;
-    p.d_lrow = nullptr;
-    p.d_c16 = p.d_r16 = nullptr;
-    p.d_pm = p.d_pbase = nullptr;
-    p.d_prod = nullptr;
-    p.binned_mode = false;
-}
-
 // mean nonzeros of a (bin, panel) tile: what a piece of the sum launch can hope to hold
 double binned_tile_nonzeros(const spmv_csr &h, int bin_rows)
 {
@@ -1105,12 +1073,12 @@ static int plan_scatter(spmv_csr &h, PanelPlan &p, int rb, int32_t padded, DevPt
     SPMV_HIP_TRY(bbase.alloc((size_t)nb + 1));
     SPMV_HIP_TRY(bcnt.alloc((size_t)nb));
     SPMV_HIP_TRY(total.alloc(1));
-    k_bs_counts<<<dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s>>>(nb, np, tiles.p, bcnt.p, bbase.p);
-    if ((rc = check("k_bs_counts"))) return rc;
-    if ((rc = exclusive_scan_i32(bbase.p, nb, total.p, s))) return rc;
+    k_bs_counts<<<dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s>>>(nb, np, tiles.get(), bcnt.get(), bbase.get());
+    if ((rc = check_launch("k_bs_counts"))) return rc;
+    if ((rc = exclusive_scan_i32(bbase.get(), nb, total.get(), s))) return rc;
     int32_t bm = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&bm, total.p, sizeof bm, hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipMemcpyAsync(bbase.p + nb, total.p, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(&bm, total.get(), sizeof bm, hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(bbase.get() + nb, total.get(), sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     SPMV_HIP_TRY(hipStreamSynchronize(s));
     if (bm < 0 || (int64_t)bm + kBsSlack >= (1ll << 30)) {   // ((bm + kBsSlack) * 4 bytes must fit the buffer descriptors' 32 bits)
         set_error("spmv_csr_plan(panel, binned, scattered products): %d bins pad nnz %lld beyond 2^30 entries", nb, (long long)h.nnz);
@@ -1127,31 +1095,31 @@ static int plan_scatter(spmv_csr &h, PanelPlan &p, int rb, int32_t padded, DevPt
     SPMV_HIP_TRY(stats.alloc(2));
     // the runs of the panel-major order (nonempty tiles + one slot per panel for its pad slots)
     SPMV_HIP_TRY(run0.alloc((size_t)np + 1));
-    k_bs_nruns<<<dim3((unsigned)np), dim3(256), 0, s>>>(nb, np, tiles.p, run0.p);
-    if ((rc = check("k_bs_nruns"))) return rc;
-    if ((rc = exclusive_scan_i32(run0.p, np, total.p, s))) return rc;
+    k_bs_nruns<<<dim3((unsigned)np), dim3(256), 0, s>>>(nb, np, tiles.get(), run0.get());
+    if ((rc = check_launch("k_bs_nruns"))) return rc;
+    if ((rc = exclusive_scan_i32(run0.get(), np, total.get(), s))) return rc;
     int32_t nruns = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&nruns, total.p, sizeof nruns, hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(&nruns, total.get(), sizeof nruns, hipMemcpyDeviceToHost, s));
     SPMV_HIP_TRY(hipStreamSynchronize(s));
     SPMV_HIP_TRY(offset.alloc((size_t)nruns + 1));
     SPMV_HIP_TRY(first_run.alloc((size_t)padded / kBlk + 1));
-    SPMV_HIP_TRY(hipMemsetAsync(offset.p, 0, sizeof(int32_t) * ((size_t)nruns + 1), s));
-    SPMV_HIP_TRY(hipMemsetAsync(first_run.p, 0, sizeof(int32_t) * ((size_t)padded / kBlk + 1), s));
-    SPMV_HIP_TRY(hipMemsetAsync(c16.p, 0, sizeof(uint16_t) * nslot, s));     // the pad slots of every panel: column 0, value 0 ...
-    SPMV_HIP_TRY(hipMemsetAsync(pvals.p, 0, sizeof(float) * nslot, s));
-    SPMV_HIP_TRY(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(acc.p), (unsigned short)(rb + kPool), bslot, s));   // pad entries: the dummy word
-    SPMV_HIP_TRY(hipMemsetAsync(prod.p, 0, sizeof(float) * bslot, s));
-    SPMV_HIP_TRY(hipMemsetAsync(stats.p, 0, sizeof(int32_t) * 2, s));
+    SPMV_HIP_TRY(hipMemsetAsync(offset.get(), 0, sizeof(int32_t) * ((size_t)nruns + 1), s));
+    SPMV_HIP_TRY(hipMemsetAsync(first_run.get(), 0, sizeof(int32_t) * ((size_t)padded / kBlk + 1), s));
+    SPMV_HIP_TRY(hipMemsetAsync(c16.get(), 0, sizeof(uint16_t) * nslot, s));     // the pad slots of every panel: column 0, value 0 ...
+    SPMV_HIP_TRY(hipMemsetAsync(pvals.get(), 0, sizeof(float) * nslot, s));
+    SPMV_HIP_TRY(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(acc.get()), (unsigned short)(rb + kPool), bslot, s));   // pad entries: the dummy word
+    SPMV_HIP_TRY(hipMemsetAsync(prod.get(), 0, sizeof(float) * bslot, s));
+    SPMV_HIP_TRY(hipMemsetAsync(stats.get(), 0, sizeof(int32_t) * 2, s));
     int32_t st[2] = {0, 0};
     if (h.nnz > 0) {
-        if ((rc = panel_rowloc(h, brow.p, nb, rowloc.p, s))) return rc;
+        if ((rc = panel_rowloc(h, brow.get(), nb, rowloc.get(), s))) return rc;
         bool one_pass = false;
         if (const char *e = getenv("SPMV_BS_FILL")) one_pass = atoi(e) == 1;   // (A/B runs: the one-pass fill)
         if (one_pass) {
             k_bs_fill<<<dim3((unsigned)((nb + 3) / 4)), dim3(256), sizeof(int) * 4 * ((size_t)np + 256), s>>>(
-                nb, np, brow.p, h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.p, tiles.p, pm.p, bbase.p, c16.p, pvals.p, acc.p,
+                nb, np, brow.get(), h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.get(), tiles.get(), pm.get(), bbase.get(), c16.get(), pvals.get(), acc.get(),
                 (int64_t)nslot, (int64_t)bslot);
-            if ((rc = check("k_bs_fill"))) return rc;
+            if ((rc = check_launch("k_bs_fill"))) return rc;
         } else {
             const int ng = (np + 63) >> kGroupBits;
             DevPtr<int32_t> tcol;
@@ -1159,51 +1127,51 @@ static int plan_scatter(spmv_csr &h, PanelPlan &p, int rb, int32_t padded, DevPt
             DevPtr<uint16_t> trow;
             const int32_t *src_col = h.d_col_idx;
             const float *src_val = h.d_vals;
-            const uint16_t *src_row = rowloc.p;
+            const uint16_t *src_row = rowloc.get();
             int64_t src_len = h.nnz;                                // (the CSR arrays; the grouped copies: nnz + 8)
             if (ng > 1) {                                           // (one group: the bins' CSR ranges are grouped as they are)
                 SPMV_HIP_TRY(tcol.alloc((size_t)h.nnz + 8));
                 SPMV_HIP_TRY(tval.alloc((size_t)h.nnz + 8));
                 SPMV_HIP_TRY(trow.alloc((size_t)h.nnz + 8));
-                k_bs_group<<<dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s>>>(nb, np, brow.p, h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.p,
-                                                                                 tiles.p, tcol.p, tval.p, trow.p, h.nnz + 8);
-                if ((rc = check("k_bs_group"))) return rc;
-                src_col = tcol.p; src_val = tval.p; src_row = trow.p; src_len = h.nnz + 8;
+                k_bs_group<<<dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s>>>(nb, np, brow.get(), h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.get(),
+                                                                                 tiles.get(), tcol.get(), tval.get(), trow.get(), h.nnz + 8);
+                if ((rc = check_launch("k_bs_group"))) return rc;
+                src_col = tcol.get(); src_val = tval.get(); src_row = trow.get(); src_len = h.nnz + 8;
             }
             const int64_t nitems64 = (int64_t)ng * nb;
             if (nitems64 > INT_MAX / 2) { set_error("spmv_csr_plan(panel, binned, scattered products): %lld fill items", (long long)nitems64); return SPMV_ERR_INVALID; }
             const int nitems = (int)nitems64, nwg = (nitems + 3) / 4;
-            k_bs_place<<<dim3(8u * (unsigned)((nwg + 7) / 8)), dim3(256), 0, s>>>(nb, np, nitems, src_col, src_val, src_row, tiles.p, pm.p,
-                                                                                 bbase.p, c16.p, pvals.p, acc.p, src_len, (int64_t)nslot,
+            k_bs_place<<<dim3(8u * (unsigned)((nwg + 7) / 8)), dim3(256), 0, s>>>(nb, np, nitems, src_col, src_val, src_row, tiles.get(), pm.get(),
+                                                                                 bbase.get(), c16.get(), pvals.get(), acc.get(), src_len, (int64_t)nslot,
                                                                                  (int64_t)bslot);
-            if ((rc = check("k_bs_place"))) return rc;
+            if ((rc = check_launch("k_bs_place"))) return rc;
             SPMV_HIP_TRY(hipStreamSynchronize(s));                  // the grouped copies are freed here
         }
-        k_bs_runs<<<dim3((unsigned)np), dim3(256), 0, s>>>(nb, np, bm, tiles.p, pm.p, pbase.p, bbase.p, run0.p, offset.p, first_run.p, c16.p);
-        if ((rc = check("k_bs_runs"))) return rc;
+        k_bs_runs<<<dim3((unsigned)np), dim3(256), 0, s>>>(nb, np, bm, tiles.get(), pm.get(), pbase.get(), bbase.get(), run0.get(), offset.get(), first_run.get(), c16.get());
+        if ((rc = check_launch("k_bs_runs"))) return rc;
         const size_t lds = sizeof(int) * 2 * (size_t)rb;
         if (rb == 16384) {
             static LdsOptIn optin;
             if ((rc = optin.ensure(reinterpret_cast<const void *>(&k_bs_accs<16384>), h.device, (int)lds))) return rc;
-            k_bs_accs<16384><<<dim3((unsigned)nb), dim3(kWave), lds, s>>>(brow.p, bbase.p, bcnt.p, acc.p, nlong.p, lrow.p, stats.p);
+            k_bs_accs<16384><<<dim3((unsigned)nb), dim3(kWave), lds, s>>>(brow.get(), bbase.get(), bcnt.get(), acc.get(), nlong.get(), lrow.get(), stats.get());
         } else if (rb == 8192) {
             static LdsOptIn optin;
             if ((rc = optin.ensure(reinterpret_cast<const void *>(&k_bs_accs<8192>), h.device, (int)lds))) return rc;
-            k_bs_accs<8192><<<dim3((unsigned)nb), dim3(kWave), lds, s>>>(brow.p, bbase.p, bcnt.p, acc.p, nlong.p, lrow.p, stats.p);
+            k_bs_accs<8192><<<dim3((unsigned)nb), dim3(kWave), lds, s>>>(brow.get(), bbase.get(), bcnt.get(), acc.get(), nlong.get(), lrow.get(), stats.get());
         } else {
-            k_bs_accs<4096><<<dim3((unsigned)nb), dim3(kWave), lds, s>>>(brow.p, bbase.p, bcnt.p, acc.p, nlong.p, lrow.p, stats.p);
+            k_bs_accs<4096><<<dim3((unsigned)nb), dim3(kWave), lds, s>>>(brow.get(), bbase.get(), bcnt.get(), acc.get(), nlong.get(), lrow.get(), stats.get());
         }
-        if ((rc = check("k_bs_accs"))) return rc;
-        SPMV_HIP_TRY(hipMemcpyAsync(st, stats.p, sizeof st, hipMemcpyDeviceToHost, s));
+        if ((rc = check_launch("k_bs_accs"))) return rc;
+        SPMV_HIP_TRY(hipMemcpyAsync(st, stats.get(), sizeof st, hipMemcpyDeviceToHost, s));
     } else {
-        SPMV_HIP_TRY(hipMemsetAsync(nlong.p, 0, sizeof(int32_t) * (size_t)nb, s));
+        SPMV_HIP_TRY(hipMemsetAsync(nlong.get(), 0, sizeof(int32_t) * (size_t)nb, s));
     }
     // the product launch: at least two rounds of CUs over the panels that HOLD something (a banded shard fills a fraction of
     // its panels), their streams shared by `splits` workgroups where they are fewer
     const int cus = device_cus(h.device);
     {
         std::vector<int32_t> hb((size_t)np + 1);
-        SPMV_HIP_TRY(hipMemcpyAsync(hb.data(), pbase.p, sizeof(int32_t) * ((size_t)np + 1), hipMemcpyDeviceToHost, s));
+        SPMV_HIP_TRY(hipMemcpyAsync(hb.data(), pbase.get(), sizeof(int32_t) * ((size_t)np + 1), hipMemcpyDeviceToHost, s));
         SPMV_HIP_TRY(hipStreamSynchronize(s));
         int holding = 0;
         for (int q = 0; q < np; ++q) holding += hb[(size_t)q + 1] > hb[(size_t)q] ? 1 : 0;
@@ -1218,19 +1186,19 @@ static int plan_scatter(spmv_csr &h, PanelPlan &p, int rb, int32_t padded, DevPt
     p.bm_alloc = (int64_t)bslot;
     p.flagged_tiles = st[0];                 // (bins, in this flavour)
     p.long_rows = st[1];
-    p.d_c16 = c16.release();
-    p.d_pvals = pvals.release();
-    p.d_offset = offset.release();
-    p.d_first_run = first_run.release();
+    p.d_c16 = std::move(c16);
+    p.d_pvals = std::move(pvals);
+    p.d_offset = std::move(offset);
+    p.d_first_run = std::move(first_run);
     p.runs = nruns;
-    p.d_prod = prod.release();
-    p.d_r16 = acc.release();
-    p.d_pbase = pbase.release();
-    p.d_bbase = bbase.release();
-    p.d_bcnt = bcnt.release();
-    p.d_nlong = nlong.release();
-    p.d_lrow = lrow.release();
-    p.d_brow = brow.release();
+    p.d_prod = std::move(prod);
+    p.d_r16 = std::move(acc);
+    p.d_pbase = std::move(pbase);
+    p.d_bbase = std::move(bbase);
+    p.d_bcnt = std::move(bcnt);
+    p.d_nlong = std::move(nlong);
+    p.d_lrow = std::move(lrow);
+    p.d_brow = std::move(brow);
     p.ready = true;
     return SPMV_OK;
 }
@@ -1301,31 +1269,31 @@ int plan_binned(spmv_csr &h, PanelPlan &p, int want_rows, bool scatter, hipStrea
     SPMV_HIP_TRY(pm.alloc((size_t)nb * (size_t)np));
     SPMV_HIP_TRY(pbase.alloc((size_t)np + 1));
     SPMV_HIP_TRY(total.alloc(1));
-    if ((rc = panel_tile_ptr(h, brow.p, nb, kPwBits, np, tiles.p, s))) return rc;
-    k_bin_panel_totals<<<dim3((unsigned)np), dim3(256), 0, s>>>(nb, np, scatter ? kBlk : 8, tiles.p, pbase.p);
-    if ((rc = check("k_bin_panel_totals"))) return rc;
-    if ((rc = exclusive_scan_i32(pbase.p, np, total.p, s))) return rc;
+    if ((rc = panel_tile_ptr(h, brow.get(), nb, kPwBits, np, tiles.get(), s))) return rc;
+    k_bin_panel_totals<<<dim3((unsigned)np), dim3(256), 0, s>>>(nb, np, scatter ? kBlk : 8, tiles.get(), pbase.get());
+    if ((rc = check_launch("k_bin_panel_totals"))) return rc;
+    if ((rc = exclusive_scan_i32(pbase.get(), np, total.get(), s))) return rc;
     int32_t padded = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&padded, total.p, sizeof padded, hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipMemcpyAsync(pbase.p + np, total.p, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(&padded, total.get(), sizeof padded, hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(pbase.get() + np, total.get(), sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     SPMV_HIP_TRY(hipStreamSynchronize(s));
-    k_bin_pm<<<dim3((unsigned)np), dim3(256), 0, s>>>(nb, np, tiles.p, pbase.p, pm.p);
-    if ((rc = check("k_bin_pm"))) return rc;
+    k_bin_pm<<<dim3((unsigned)np), dim3(256), 0, s>>>(nb, np, tiles.get(), pbase.get(), pm.get());
+    if ((rc = check_launch("k_bin_pm"))) return rc;
     if (scatter) return plan_scatter(h, p, rb, padded, brow, tiles, pm, pbase, s);
     const size_t nslot = (size_t)padded + kBinSlack;
     SPMV_HIP_TRY(c16.alloc(nslot));
     SPMV_HIP_TRY(pvals.alloc(nslot));
     SPMV_HIP_TRY(prod.alloc(nslot));
     SPMV_HIP_TRY(r16.alloc((size_t)h.nnz + kBinSlack));
-    SPMV_HIP_TRY(hipMemsetAsync(r16.p + h.nnz, 0, sizeof(uint16_t) * kBinSlack, s));
+    SPMV_HIP_TRY(hipMemsetAsync(r16.get() + h.nnz, 0, sizeof(uint16_t) * kBinSlack, s));
     SPMV_HIP_TRY(rowloc.alloc((size_t)h.nnz + 8));
-    SPMV_HIP_TRY(hipMemsetAsync(c16.p, 0, sizeof(uint16_t) * nslot, s));     // (the pad slots of every panel: column 0, value 0)
-    SPMV_HIP_TRY(hipMemsetAsync(pvals.p, 0, sizeof(float) * nslot, s));
+    SPMV_HIP_TRY(hipMemsetAsync(c16.get(), 0, sizeof(uint16_t) * nslot, s));     // (the pad slots of every panel: column 0, value 0)
+    SPMV_HIP_TRY(hipMemsetAsync(pvals.get(), 0, sizeof(float) * nslot, s));
     if (h.nnz > 0) {
-        if ((rc = panel_rowloc(h, brow.p, nb, rowloc.p, s))) return rc;
+        if ((rc = panel_rowloc(h, brow.get(), nb, rowloc.get(), s))) return rc;
         k_bin_fill<<<dim3((unsigned)((nb + 3) / 4)), dim3(256), sizeof(int) * 4 * ((size_t)np + 256), s>>>(
-            nb, np, brow.p, h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.p, tiles.p, pm.p, c16.p, pvals.p, r16.p);
-        if ((rc = check("k_bin_fill"))) return rc;
+            nb, np, brow.get(), h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.get(), tiles.get(), pm.get(), c16.get(), pvals.get(), r16.get());
+        if ((rc = check_launch("k_bin_fill"))) return rc;
     }
     // the product launch: every panel's stream shared by `splits` workgroups so that the launch is at least two rounds of CUs
     p.splits = np >= 2 * cus ? 1 : (2 * cus + np - 1) / np;
@@ -1339,45 +1307,45 @@ int plan_binned(spmv_csr &h, PanelPlan &p, int want_rows, bool scatter, hipStrea
     DevPtr<uint32_t> lrow;
     const int e = p.wide_pieces ? 4 : 2;
     SPMV_HIP_TRY(lptr.alloc((size_t)nb + 1));
-    SPMV_HIP_TRY(hipMemsetAsync(lptr.p, 0, sizeof(int32_t) * ((size_t)nb + 1), s));
+    SPMV_HIP_TRY(hipMemsetAsync(lptr.get(), 0, sizeof(int32_t) * ((size_t)nb + 1), s));
     if (h.nnz > 0) {
         SPMV_HIP_TRY(maxrun.alloc((size_t)h.rows));
         SPMV_HIP_TRY(spare.alloc((size_t)nb));
-        SPMV_HIP_TRY(hipMemsetAsync(maxrun.p, 0, sizeof(int32_t) * (size_t)h.rows, s));
-        k_bin_runs<<<dim3((unsigned)nb), dim3(256), 0, s>>>(np, e, brow.p, tiles.p, r16.p, maxrun.p);
-        if ((rc = check("k_bin_runs"))) return rc;
-        k_bin_spare<<<dim3((unsigned)nb), dim3(256), 0, s>>>(e, brow.p, maxrun.p, spare.p, lptr.p);
-        if ((rc = check("k_bin_spare"))) return rc;
-        if ((rc = exclusive_scan_i32(lptr.p, nb, total.p, s))) return rc;
-        SPMV_HIP_TRY(hipMemcpyAsync(&nlong_total, total.p, sizeof nlong_total, hipMemcpyDeviceToHost, s));
-        SPMV_HIP_TRY(hipMemcpyAsync(lptr.p + nb, total.p, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        SPMV_HIP_TRY(hipMemsetAsync(maxrun.get(), 0, sizeof(int32_t) * (size_t)h.rows, s));
+        k_bin_runs<<<dim3((unsigned)nb), dim3(256), 0, s>>>(np, e, brow.get(), tiles.get(), r16.get(), maxrun.get());
+        if ((rc = check_launch("k_bin_runs"))) return rc;
+        k_bin_spare<<<dim3((unsigned)nb), dim3(256), 0, s>>>(e, brow.get(), maxrun.get(), spare.get(), lptr.get());
+        if ((rc = check_launch("k_bin_spare"))) return rc;
+        if ((rc = exclusive_scan_i32(lptr.get(), nb, total.get(), s))) return rc;
+        SPMV_HIP_TRY(hipMemcpyAsync(&nlong_total, total.get(), sizeof nlong_total, hipMemcpyDeviceToHost, s));
+        SPMV_HIP_TRY(hipMemcpyAsync(lptr.get() + nb, total.get(), sizeof(int32_t), hipMemcpyDeviceToDevice, s));
         SPMV_HIP_TRY(hipStreamSynchronize(s));
     }
     SPMV_HIP_TRY(lrow.alloc((size_t)nlong_total + 1));
     SPMV_HIP_TRY(lcnt.alloc((size_t)nlong_total + 1));
     if (h.nnz > 0) {
-        SPMV_HIP_TRY(hipMemsetAsync(total.p, 0, sizeof(int32_t), s));
-        k_bin_rewrite<<<dim3((unsigned)nb), dim3(256), 0, s>>>(np, e, rb, brow.p, tiles.p, maxrun.p, spare.p, lptr.p, r16.p, pm.p, lrow.p,
-                                                               lcnt.p, total.p);
-        if ((rc = check("k_bin_rewrite"))) return rc;
-        SPMV_HIP_TRY(hipMemcpyAsync(&flagged, total.p, sizeof flagged, hipMemcpyDeviceToHost, s));
+        SPMV_HIP_TRY(hipMemsetAsync(total.get(), 0, sizeof(int32_t), s));
+        k_bin_rewrite<<<dim3((unsigned)nb), dim3(256), 0, s>>>(np, e, rb, brow.get(), tiles.get(), maxrun.get(), spare.get(), lptr.get(), r16.get(), pm.get(), lrow.get(),
+                                                               lcnt.get(), total.get());
+        if ((rc = check_launch("k_bin_rewrite"))) return rc;
+        SPMV_HIP_TRY(hipMemcpyAsync(&flagged, total.get(), sizeof flagged, hipMemcpyDeviceToHost, s));
     }
     if ((rc = stamp_values(h, s, p.stamp))) return rc;
     SPMV_HIP_TRY(hipStreamSynchronize(s));   // the temporaries are freed on return
     p.padded = padded;
     p.flagged_tiles = flagged;
     p.long_rows = nlong_total;
-    p.d_lptr = lptr.release();
-    p.d_lrow = lrow.release();
-    p.d_lcnt = lcnt.release();
-    p.d_c16 = c16.release();
-    p.d_pvals = pvals.release();
-    p.d_prod = prod.release();
-    p.d_r16 = r16.release();
-    p.d_pm = pm.release();
-    p.d_pbase = pbase.release();
-    p.d_tile_ptr = tiles.release();
-    p.d_brow = brow.release();
+    p.d_lptr = std::move(lptr);
+    p.d_lrow = std::move(lrow);
+    p.d_lcnt = std::move(lcnt);
+    p.d_c16 = std::move(c16);
+    p.d_pvals = std::move(pvals);
+    p.d_prod = std::move(prod);
+    p.d_r16 = std::move(r16);
+    p.d_pm = std::move(pm);
+    p.d_pbase = std::move(pbase);
+    p.d_tile_ptr = std::move(tiles);
+    p.d_brow = std::move(brow);
     p.ready = true;
     return SPMV_OK;
 }
@@ -1391,7 +1359,7 @@ static int launch_sums_e(const spmv_csr &h, const PanelPlan &p, float *y, hipStr
     if (int rc = optin.ensure(reinterpret_cast<const void *>(&k_bin_sums<RB, E>), h.device, (int)lds)) return rc;
     k_bin_sums<RB, E><<<grid, block, lds, s>>>(p.nblocks, p.npanels, p.d_brow, p.d_tile_ptr, p.d_pm, p.d_r16, p.d_prod, p.d_lptr,
                                                p.d_lrow, p.d_lcnt, y, (uint32_t)((p.padded + kBinSlack) * 4), (uint32_t)((h.nnz + kBinSlack) * 2));
-    return check("k_bin_sums");
+    return check_launch("k_bin_sums");
 }
 template <int RB>
 static int launch_sums(const spmv_csr &h, const PanelPlan &p, float *y, hipStream_t s)
@@ -1407,7 +1375,7 @@ static int launch_bs_sums(const spmv_csr &h, const PanelPlan &p, float *y, hipSt
     if (int rc = optin.ensure(reinterpret_cast<const void *>(&k_bs_sums<RB>), h.device, (int)lds)) return rc;
     k_bs_sums<RB><<<dim3((unsigned)p.nblocks), dim3(kWave), lds, s>>>(p.d_brow, p.d_bbase, p.d_bcnt, p.d_r16, p.d_prod, p.d_nlong, p.d_lrow, y,
                                                                       (uint32_t)(p.bm_alloc * 4), (uint32_t)(p.bm_alloc * 2));
-    return check("k_bs_sums");
+    return check_launch("k_bs_sums");
 }
 
 int launch_binned(const spmv_csr &h, const PanelPlan &p, const float *x, float *y, hipStream_t s)
@@ -1421,7 +1389,7 @@ int launch_binned(const spmv_csr &h, const PanelPlan &p, const float *x, float *
         k_bs_products<<<dim3(grid), dim3(kProdThreads), lds, s>>>(p.splits, p.npanels, h.cols, p.d_pbase, p.d_c16,
                                                                                               p.d_pvals, p.d_first_run, p.d_offset, x, p.d_prod,
                                                                                               p.padded + 8, p.bm_alloc);
-        if (int rc = check("k_bs_products")) return rc;
+        if (int rc = check_launch("k_bs_products")) return rc;
         return p.bin_rows == 16384 ? launch_bs_sums<16384>(h, p, y, s) : p.bin_rows == 8192 ? launch_bs_sums<8192>(h, p, y, s) : launch_bs_sums<4096>(h, p, y, s);
     }
     {
@@ -1430,7 +1398,7 @@ int launch_binned(const spmv_csr &h, const PanelPlan &p, const float *x, float *
         if (int rc = optin.ensure(reinterpret_cast<const void *>(&k_bin_products), h.device, (int)lds)) return rc;
         k_bin_products<<<dim3((unsigned)(p.npanels * p.splits)), dim3(kProdThreads), lds, s>>>(p.splits, h.cols, p.d_pbase, p.d_c16,
                                                                                                p.d_pvals, x, p.d_prod);
-        if (int rc = check("k_bin_products")) return rc;
+        if (int rc = check_launch("k_bin_products")) return rc;
     }
     return p.bin_rows == 8192 ? launch_sums<8192>(h, p, y, s) : p.bin_rows == 4096 ? launch_sums<4096>(h, p, y, s) :
            p.bin_rows == 2048 ? launch_sums<2048>(h, p, y, s) : launch_sums<1024>(h, p, y, s);

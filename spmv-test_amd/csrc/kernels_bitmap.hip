@@ -24,18 +24,8 @@
 // The builders run on the device from the dense matrix (the reference: single-threaded host loops, 0.18-0.32 s at
 // 4096^2) and are checked bit for bit against the reference-built arrays in tests/golden/.
 #include <climits>
+#include <memory>
 #include "spmv_internal.hpp"
-
-struct spmv_bitmap {
-    int format = 0;                 // enum spmv_bitmap_format
-    int M = 0, N = 0;
-    int device = 0;
-    int64_t n_bitmaps = 0, n_vals = 0;
-    int32_t stats[4] = {0, 0, 0, 0};   // WSP {nz_max_m, nz_max_n}, AWSP {nz_bk_max_}, AWSPRef warp_nz_offset_[4]
-    uint32_t *d_bitmaps = nullptr;
-    float *d_vals = nullptr;
-    float *d_partial = nullptr;     // AWSP/AWSPRef: [4][N] quarter partials
-};
 
 namespace spmv {
 
@@ -43,13 +33,6 @@ namespace {
 
 constexpr int kQuarters = 4;        // awsp_ref.cpp:12 "warp_id < 4": quarters of the input dimension
 constexpr int kRowWaves = 8;        // wavefronts that share one (strip, quarter)
-
-int check_launch(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return SPMV_OK;
-}
 
 // ---- builders ---------------------------------------------------------------------------------------------------
 // AWSP / AWSPRef bitmap: word s*M + j, bit c <-> A[j][32s + c] != 0.  A wavefront reads 64 consecutive floats of a row
@@ -299,28 +282,18 @@ __global__ __launch_bounds__(kBlock) void k_wsp_spmv(int M, int N, int nz_max_m,
 }  // namespace
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-void bitmap_free(spmv_bitmap *h)
-{
-    if (!h) return;
-    if (h->d_bitmaps) (void)hipFree(h->d_bitmaps);
-    if (h->d_vals) (void)hipFree(h->d_vals);
-    if (h->d_partial) (void)hipFree(h->d_partial);
-    delete h;
-}
-
 int bitmap_from_dense(int format, int M, int N, const float *d_A, hipStream_t s, spmv_bitmap_t **out)
 {
     int rc;
-    spmv_bitmap *h = new spmv_bitmap();
-    struct Guard { spmv_bitmap *&p; ~Guard() { if (p) bitmap_free(p); } } guard{h};
+    std::unique_ptr<spmv_bitmap> h(new spmv_bitmap());
     h->format = format; h->M = M; h->N = N;
     if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
     const size_t nwords = (size_t)M * (size_t)N / 32;
     h->n_bitmaps = (int64_t)nwords;
-    SPMV_HIP_TRY(hipMalloc((void **)&h->d_bitmaps, sizeof(uint32_t) * (nwords ? nwords : 1)));
+    SPMV_HIP_TRY(h->d_bitmaps.alloc(nwords));
     DevPtr<int32_t> d_stats;
     SPMV_HIP_TRY(d_stats.alloc(4));
-    SPMV_HIP_TRY(hipMemsetAsync(d_stats.p, 0, 4 * sizeof(int32_t), s));
+    SPMV_HIP_TRY(hipMemsetAsync(d_stats.get(), 0, 4 * sizeof(int32_t), s));
 
     if (format == SPMV_FMT_WSP) {
         // the values are the CSR of A^T with every row moved to a stride of nz_max_m (wsp.cpp:31-37)
@@ -332,14 +305,14 @@ int bitmap_from_dense(int format, int M, int N, const float *d_A, hipStream_t s,
             if ((rc = check_launch("k_colwords"))) return rc;
         }
         if (N > 0) {
-            hipLaunchKernelGGL(k_rowlen_max, dim3((N + 255) / 256), dim3(256), 0, s, N, csr->d_row_ptr, d_stats.p);
+            hipLaunchKernelGGL(k_rowlen_max, dim3((N + 255) / 256), dim3(256), 0, s, N, csr->d_row_ptr, d_stats.get());
             if ((rc = check_launch("k_rowlen_max"))) return rc;
         }
-        SPMV_HIP_TRY(hipMemcpyAsync(h->stats, d_stats.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        SPMV_HIP_TRY(hipMemcpyAsync(h->stats, d_stats.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
         SPMV_HIP_TRY(hipStreamSynchronize(s));
         h->stats[1] = N;                                       // nz_max_n (wsp.cpp:7)
         h->n_vals = (int64_t)N * h->stats[0];
-        SPMV_HIP_TRY(hipMalloc((void **)&h->d_vals, sizeof(float) * (size_t)(h->n_vals ? h->n_vals : 1)));
+        SPMV_HIP_TRY(h->d_vals.alloc((size_t)h->n_vals));
         SPMV_HIP_TRY(hipMemsetAsync(h->d_vals, 0, sizeof(float) * (size_t)h->n_vals, s));
         if (h->n_vals) {
             hipLaunchKernelGGL(k_wsp_pad, dim3((N + 3) / 4), dim3(kBlock), 0, s, N, h->stats[0], csr->d_row_ptr, csr->d_vals,
@@ -352,49 +325,48 @@ int bitmap_from_dense(int format, int M, int N, const float *d_A, hipStream_t s,
         DevPtr<int32_t> pre, total;
         SPMV_HIP_TRY(pre.alloc(nwords + 1));
         SPMV_HIP_TRY(total.alloc(1));
-        SPMV_HIP_TRY(hipMemsetAsync(total.p, 0, sizeof(int32_t), s));
+        SPMV_HIP_TRY(hipMemsetAsync(total.get(), 0, sizeof(int32_t), s));
         if (nwords) {
             hipLaunchKernelGGL(k_rowwords, dim3((N + kWave - 1) / kWave, (M + 3) / 4), dim3(kBlock), 0, s, M, N, d_A,
-                               h->d_bitmaps, pre.p);
+                               h->d_bitmaps, pre.get());
             if ((rc = check_launch("k_rowwords"))) return rc;
-            if ((rc = exclusive_scan_i32(pre.p, (int64_t)nwords, total.p, s))) return rc;
+            if ((rc = exclusive_scan_i32(pre.get(), (int64_t)nwords, total.get(), s))) return rc;
         }
-        hipLaunchKernelGGL(k_append_total, dim3(1), dim3(1), 0, s, (int64_t)nwords, total.p, pre.p);
+        hipLaunchKernelGGL(k_append_total, dim3(1), dim3(1), 0, s, (int64_t)nwords, total.get(), pre.get());
         if ((rc = check_launch("k_append_total"))) return rc;
         const int len = ref ? M / kQuarters : 32;
         const int64_t ngroups = len ? (int64_t)nwords / len : 0;
         if (ngroups) {
             hipLaunchKernelGGL(k_group_max, dim3((unsigned)((ngroups + 255) / 256)), dim3(256), 0, s, ngroups, len,
-                               ref ? kQuarters : 1, pre.p, d_stats.p);
+                               ref ? kQuarters : 1, pre.get(), d_stats.get());
             if ((rc = check_launch("k_group_max"))) return rc;
         }
         if (ref) {
-            hipLaunchKernelGGL(k_prefix4, dim3(1), dim3(1), 0, s, d_stats.p);
+            hipLaunchKernelGGL(k_prefix4, dim3(1), dim3(1), 0, s, d_stats.get());
             if ((rc = check_launch("k_prefix4"))) return rc;
         }
-        SPMV_HIP_TRY(hipMemcpyAsync(h->stats, d_stats.p, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        SPMV_HIP_TRY(hipMemcpyAsync(h->stats, d_stats.get(), 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         SPMV_HIP_TRY(hipStreamSynchronize(s));
         h->n_vals = ref ? (int64_t)(N / 32) * h->stats[3] : (int64_t)(M / 32) * (N / 32) * h->stats[0];
         if (h->n_vals >= (1ll << 31)) {
             set_error("bitmap format: %lld padded values exceed 2^31", (long long)h->n_vals);
             return SPMV_ERR_INVALID;
         }
-        SPMV_HIP_TRY(hipMalloc((void **)&h->d_vals, sizeof(float) * (size_t)(h->n_vals ? h->n_vals : 1)));
+        SPMV_HIP_TRY(h->d_vals.alloc((size_t)h->n_vals));
         SPMV_HIP_TRY(hipMemsetAsync(h->d_vals, 0, sizeof(float) * (size_t)h->n_vals, s));
         if (nwords && h->n_vals) {
             const dim3 grid(N / 32, (M + 7) / 8);
-            if (ref) hipLaunchKernelGGL(k_rowvals<true>, grid, dim3(kBlock), 0, s, M, N, d_A, h->d_bitmaps, pre.p, d_stats.p, h->d_vals);
-            else hipLaunchKernelGGL(k_rowvals<false>, grid, dim3(kBlock), 0, s, M, N, d_A, h->d_bitmaps, pre.p, d_stats.p, h->d_vals);
+            if (ref) hipLaunchKernelGGL(k_rowvals<true>, grid, dim3(kBlock), 0, s, M, N, d_A, h->d_bitmaps, pre.get(), d_stats.get(), h->d_vals);
+            else hipLaunchKernelGGL(k_rowvals<false>, grid, dim3(kBlock), 0, s, M, N, d_A, h->d_bitmaps, pre.get(), d_stats.get(), h->d_vals);
             if ((rc = check_launch("k_rowvals"))) return rc;
         }
         // [4][N] quarter partials, then a device copy of the four statistics for the multiply kernels
-        SPMV_HIP_TRY(hipMalloc((void **)&h->d_partial, sizeof(float) * ((size_t)kQuarters * (size_t)N + 4)));
-        SPMV_HIP_TRY(hipMemcpyAsync(h->d_partial + (size_t)kQuarters * N, d_stats.p, 4 * sizeof(int32_t),
+        SPMV_HIP_TRY(h->d_partial.alloc((size_t)kQuarters * (size_t)N + 4));
+        SPMV_HIP_TRY(hipMemcpyAsync(h->d_partial + (size_t)kQuarters * N, d_stats.get(), 4 * sizeof(int32_t),
                                     hipMemcpyDeviceToDevice, s));
         SPMV_HIP_TRY(hipStreamSynchronize(s));                 // pre / d_stats are released on return
     }
-    *out = h;
-    guard.p = nullptr;
+    *out = h.release();
     return SPMV_OK;
 }
 

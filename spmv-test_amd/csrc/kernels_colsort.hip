@@ -56,13 +56,6 @@ using u4 = unsigned __attribute__((ext_vector_type(4)));
 using f4 = float __attribute__((ext_vector_type(4)));
 using us4 = unsigned short __attribute__((ext_vector_type(4)));
 
-int check_launch(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return SPMV_OK;
-}
-
 __device__ __forceinline__ int xcd_block(int bid, int n)   // XCD j = bid % 8 gets a contiguous range of blocks
 {
     const int q = n / kXcds, rem = n % kXcds;
@@ -678,18 +671,6 @@ __global__ __launch_bounds__(WAVES *kWave) void k_colsort(int nblocks, const int
 
 }  // namespace
 
-void destroy_colsort(PanelPlan &p)
-{
-    if (p.d_ubeg) (void)hipFree(p.d_ubeg);
-    if (p.d_usimple) (void)hipFree(p.d_usimple);
-    if (p.d_uend) (void)hipFree(p.d_uend);
-    if (p.d_tbeg) (void)hipFree(p.d_tbeg);
-    if (p.d_trow) (void)hipFree(p.d_trow);
-    if (p.d_ubase) (void)hipFree(p.d_ubase);
-    p.d_ubeg = p.d_usimple = p.d_uend = p.d_ubase = p.d_tbeg = nullptr;
-    p.d_trow = nullptr;
-}
-
 // A cheap look at the matrix before SPMV_AUTO pays for this plan (one pass over row_ptr, two columns per row):
 //   long_frac = share of the nonzeros that sit in rows of more than 256 (they would go to the tails),
 //   wide_frac = share of the 4096-row blocks whose short rows reach over 2^20 columns or more (first and last column of
@@ -753,7 +734,7 @@ static int build_colsort(spmv_csr &h, PanelPlan &p, int rows_cap, hipStream_t s)
     int64_t nb0 = (h.rows + rows_cap - 1) / rows_cap;
     if ((rc = panel_row_blocks(h, nb0, rows_cap, s, brow, &p.nblocks))) return rc;
     if ((int64_t)p.nblocks * 100 > nb0 * 101) {
-        (void)hipFree(brow.release());
+        (void)brow.reset();
         nb0 = (h.rows + rows_cap * 15 / 16 - 1) / (rows_cap * 15 / 16);
         if ((rc = panel_row_blocks(h, nb0, rows_cap, s, brow, &p.nblocks))) return rc;
     }
@@ -766,15 +747,15 @@ static int build_colsort(spmv_csr &h, PanelPlan &p, int rows_cap, hipStream_t s)
     SPMV_HIP_TRY(nshort.alloc((size_t)p.nblocks));
     SPMV_HIP_TRY(fail.alloc(1));
     SPMV_HIP_TRY(stats.alloc(3));
-    SPMV_HIP_TRY(hipMemsetAsync(fail.p, 0, sizeof(int32_t), s));
-    SPMV_HIP_TRY(hipMemsetAsync(stats.p, 0, 3 * sizeof(unsigned long long), s));
+    SPMV_HIP_TRY(hipMemsetAsync(fail.get(), 0, sizeof(int32_t), s));
+    SPMV_HIP_TRY(hipMemsetAsync(stats.get(), 0, 3 * sizeof(unsigned long long), s));
     const unsigned gb = (unsigned)((p.nblocks + 255) / 256);
-    k_cb_units<<<dim3(gb), dim3(256), 0, s>>>(p.nblocks, brow.p, h.d_row_ptr, ubeg.p);
+    k_cb_units<<<dim3(gb), dim3(256), 0, s>>>(p.nblocks, brow.get(), h.d_row_ptr, ubeg.get());
     if ((rc = check_launch("k_cb_units"))) return rc;
-    if ((rc = exclusive_scan_i32(ubeg.p, p.nblocks, total.p, s))) return rc;
+    if ((rc = exclusive_scan_i32(ubeg.get(), p.nblocks, total.get(), s))) return rc;
     int32_t units = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&units, total.p, sizeof units, hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipMemcpyAsync(ubeg.p + p.nblocks, total.p, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(&units, total.get(), sizeof units, hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(ubeg.get() + p.nblocks, total.get(), sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     SPMV_HIP_TRY(hipStreamSynchronize(s));
     p.units = units;
     const size_t slots = (size_t)units * kCbUnit;
@@ -790,54 +771,54 @@ static int build_colsort(spmv_csr &h, PanelPlan &p, int rows_cap, hipStream_t s)
     SPMV_HIP_TRY(t_col.alloc((size_t)h.nnz));
     SPMV_HIP_TRY(t_row.alloc((size_t)h.nnz));
     SPMV_HIP_TRY(t_val.alloc((size_t)h.nnz));
-    SPMV_HIP_TRY(hipMemsetAsync(packed.p, 0, sizeof(uint32_t) * slots, s));
-    SPMV_HIP_TRY(hipMemsetAsync(pvals.p, 0, sizeof(float) * slots, s));
-    SPMV_HIP_TRY(hipMemsetAsync(o_row.p, 0xFF, sizeof(uint16_t) * slots, s));
+    SPMV_HIP_TRY(hipMemsetAsync(packed.get(), 0, sizeof(uint32_t) * slots, s));
+    SPMV_HIP_TRY(hipMemsetAsync(pvals.get(), 0, sizeof(float) * slots, s));
+    SPMV_HIP_TRY(hipMemsetAsync(o_row.get(), 0xFF, sizeof(uint16_t) * slots, s));
     if (h.nnz > 0) {
-        if ((rc = panel_rowloc(h, brow.p, p.nblocks, rowloc.p, s))) return rc;
+        if ((rc = panel_rowloc(h, brow.get(), p.nblocks, rowloc.get(), s))) return rc;
         // counters for the widest block at 32 columns each (wider blocks than kCbBins counters reach use coarser bins)
         int32_t widest = 0;
-        SPMV_HIP_TRY(hipMemsetAsync(total.p, 0, sizeof(int32_t), s));
-        k_cb_span<<<dim3((unsigned)p.nblocks), dim3(kBlock), 0, s>>>(brow.p, h.d_row_ptr, h.d_col_idx, total.p);
+        SPMV_HIP_TRY(hipMemsetAsync(total.get(), 0, sizeof(int32_t), s));
+        k_cb_span<<<dim3((unsigned)p.nblocks), dim3(kBlock), 0, s>>>(brow.get(), h.d_row_ptr, h.d_col_idx, total.get());
         if ((rc = check_launch("k_cb_span"))) return rc;
-        SPMV_HIP_TRY(hipMemcpyAsync(&widest, total.p, sizeof widest, hipMemcpyDeviceToHost, s));
+        SPMV_HIP_TRY(hipMemcpyAsync(&widest, total.get(), sizeof widest, hipMemcpyDeviceToHost, s));
         SPMV_HIP_TRY(hipStreamSynchronize(s));
         int nbins = 1024;
         while (nbins < kCbBins && (widest >> 5) >= nbins) nbins <<= 1;
         const size_t lds = sizeof(int) * (size_t)nbins;
         static LdsOptIn optin;
         if ((rc = optin.ensure(reinterpret_cast<const void *>(&k_cb_sort), h.device, (int)(sizeof(int) * (size_t)kCbBins)))) return rc;
-        k_cb_sort<<<dim3((unsigned)p.nblocks), dim3(kBlock), lds, s>>>(brow.p, h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.p,
-                                                                        t_col.p, t_row.p, t_val.p, nshort.p, stats.p, nbins);
+        k_cb_sort<<<dim3((unsigned)p.nblocks), dim3(kBlock), lds, s>>>(brow.get(), h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.get(),
+                                                                        t_col.get(), t_row.get(), t_val.get(), nshort.get(), stats.get(), nbins);
         if ((rc = check_launch("k_cb_sort"))) return rc;
-        k_cb_groups<<<dim3((unsigned)p.nblocks), dim3(kWave), 0, s>>>(brow.p, h.d_row_ptr, ubeg.p, nshort.p, t_col.p, t_row.p,
-                                                                       t_val.p, reinterpret_cast<int32_t *>(packed.p), o_row.p,
-                                                                       pvals.p, usimple.p, uend.p, stats.p);
+        k_cb_groups<<<dim3((unsigned)p.nblocks), dim3(kWave), 0, s>>>(brow.get(), h.d_row_ptr, ubeg.get(), nshort.get(), t_col.get(), t_row.get(),
+                                                                       t_val.get(), reinterpret_cast<int32_t *>(packed.get()), o_row.get(),
+                                                                       pvals.get(), usimple.get(), uend.get(), stats.get());
         if ((rc = check_launch("k_cb_groups"))) return rc;
     } else {
-        SPMV_HIP_TRY(hipMemsetAsync(usimple.p, 0, sizeof(int32_t) * (size_t)p.nblocks, s));
-        SPMV_HIP_TRY(hipMemcpyAsync(uend.p, ubeg.p, sizeof(int32_t) * (size_t)p.nblocks, hipMemcpyDeviceToDevice, s));   // no units in use
+        SPMV_HIP_TRY(hipMemsetAsync(usimple.get(), 0, sizeof(int32_t) * (size_t)p.nblocks, s));
+        SPMV_HIP_TRY(hipMemcpyAsync(uend.get(), ubeg.get(), sizeof(int32_t) * (size_t)p.nblocks, hipMemcpyDeviceToDevice, s));   // no units in use
     }
     // the rows of the tail units, compact: tbeg[b] = the block's first unit in trow
     DevPtr<int32_t> tbeg, ttotal;
     DevPtr<uint16_t> trow;
     SPMV_HIP_TRY(tbeg.alloc((size_t)p.nblocks));
     SPMV_HIP_TRY(ttotal.alloc(1));
-    k_cb_tail_units<<<dim3(gb), dim3(256), 0, s>>>(p.nblocks, ubeg.p, usimple.p, uend.p, tbeg.p);
+    k_cb_tail_units<<<dim3(gb), dim3(256), 0, s>>>(p.nblocks, ubeg.get(), usimple.get(), uend.get(), tbeg.get());
     if ((rc = check_launch("k_cb_tail_units"))) return rc;
-    if ((rc = exclusive_scan_i32(tbeg.p, p.nblocks, ttotal.p, s))) return rc;
+    if ((rc = exclusive_scan_i32(tbeg.get(), p.nblocks, ttotal.get(), s))) return rc;
     int32_t tunits = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&tunits, ttotal.p, sizeof tunits, hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(&tunits, ttotal.get(), sizeof tunits, hipMemcpyDeviceToHost, s));
     SPMV_HIP_TRY(hipStreamSynchronize(s));
     p.tail_units = tunits;
     SPMV_HIP_TRY(trow.alloc((size_t)tunits * kCbUnit));
-    k_cb_pack<<<dim3((unsigned)((units + 3) / 4)), dim3(kBlock), 0, s>>>((int64_t)units, rows_cap, p.nblocks, ubeg.p, usimple.p, uend.p,
-                                                                         tbeg.p, packed.p, o_row.p, ubase.p, trow.p, fail.p);
+    k_cb_pack<<<dim3((unsigned)((units + 3) / 4)), dim3(kBlock), 0, s>>>((int64_t)units, rows_cap, p.nblocks, ubeg.get(), usimple.get(), uend.get(),
+                                                                         tbeg.get(), packed.get(), o_row.get(), ubase.get(), trow.get(), fail.get());
     if ((rc = check_launch("k_cb_pack"))) return rc;
     int32_t failed = 0;
     unsigned long long st[3] = {0, 0, 0};
-    SPMV_HIP_TRY(hipMemcpyAsync(&failed, fail.p, sizeof failed, hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipMemcpyAsync(st, stats.p, sizeof st, hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(&failed, fail.get(), sizeof failed, hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(st, stats.get(), sizeof st, hipMemcpyDeviceToHost, s));
     SPMV_HIP_TRY(hipStreamSynchronize(s));   // (the temporaries are freed on return)
     if (failed) {
         set_error("spmv_csr_plan(panel, sorted blocks): 256 neighbouring nonzeros (in column order) of the short rows of a block of "
@@ -849,15 +830,15 @@ static int build_colsort(spmv_csr &h, PanelPlan &p, int rows_cap, hipStream_t s)
     p.lines = (int64_t)st[0];
     p.tail = (int64_t)st[1];
     p.wide_blocks = (int64_t)st[2];
-    p.d_packed = packed.release();
-    p.d_pvals = pvals.release();
-    p.d_brow = brow.release();
-    p.d_ubeg = ubeg.release();
-    p.d_usimple = usimple.release();
-    p.d_uend = uend.release();
-    p.d_tbeg = tbeg.release();
-    p.d_trow = trow.release();
-    p.d_ubase = ubase.release();
+    p.d_packed = std::move(packed);
+    p.d_pvals = std::move(pvals);
+    p.d_brow = std::move(brow);
+    p.d_ubeg = std::move(ubeg);
+    p.d_usimple = std::move(usimple);
+    p.d_uend = std::move(uend);
+    p.d_tbeg = std::move(tbeg);
+    p.d_trow = std::move(trow);
+    p.d_ubase = std::move(ubase);
     return SPMV_OK;
 }
 
@@ -873,33 +854,22 @@ int colsort_probe(const spmv_csr &h, hipStream_t s, double *long_frac, double *w
     SPMV_HIP_TRY(bmin.alloc((size_t)nb));
     SPMV_HIP_TRY(bmax.alloc((size_t)nb));
     SPMV_HIP_TRY(cnt.alloc(3));
-    SPMV_HIP_TRY(hipMemsetAsync(bmin.p, 0x7f, sizeof(int32_t) * (size_t)nb, s));
-    SPMV_HIP_TRY(hipMemsetAsync(bmax.p, 0xff, sizeof(int32_t) * (size_t)nb, s));   // -1
-    SPMV_HIP_TRY(hipMemsetAsync(cnt.p, 0, 3 * sizeof(unsigned long long), s));
-    k_cb_probe<<<dim3((unsigned)((h.rows + kBlock - 1) / kBlock)), dim3(kBlock), 0, s>>>(h.rows, h.d_row_ptr, h.d_col_idx, bmin.p, bmax.p,
-                                                                                         cnt.p);
+    SPMV_HIP_TRY(hipMemsetAsync(bmin.get(), 0x7f, sizeof(int32_t) * (size_t)nb, s));
+    SPMV_HIP_TRY(hipMemsetAsync(bmax.get(), 0xff, sizeof(int32_t) * (size_t)nb, s));   // -1
+    SPMV_HIP_TRY(hipMemsetAsync(cnt.get(), 0, 3 * sizeof(unsigned long long), s));
+    k_cb_probe<<<dim3((unsigned)((h.rows + kBlock - 1) / kBlock)), dim3(kBlock), 0, s>>>(h.rows, h.d_row_ptr, h.d_col_idx, bmin.get(), bmax.get(),
+                                                                                         cnt.get());
     int rc = check_launch("k_cb_probe");
     if (rc) return rc;
-    k_cb_probe_wide<<<dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s>>>(nb, h.rows, h.d_row_ptr, bmin.p, bmax.p, cnt.p + 1);
+    k_cb_probe_wide<<<dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s>>>(nb, h.rows, h.d_row_ptr, bmin.get(), bmax.get(), cnt.get() + 1);
     if ((rc = check_launch("k_cb_probe_wide"))) return rc;
     unsigned long long c[3] = {0, 0, 0};
-    SPMV_HIP_TRY(hipMemcpyAsync(c, cnt.p, sizeof c, hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(c, cnt.get(), sizeof c, hipMemcpyDeviceToHost, s));
     SPMV_HIP_TRY(hipStreamSynchronize(s));
     *long_frac = (double)c[0] / (double)h.nnz;
     *wide_frac = (double)c[1] / (double)nb;
     *lines_per_nnz = (double)c[2] / (double)h.nnz;
     return SPMV_OK;
-}
-
-static void release_colsort(PanelPlan &p)
-{
-    destroy_colsort(p);
-    if (p.d_packed) (void)hipFree(p.d_packed);
-    if (p.d_pvals) (void)hipFree(p.d_pvals);
-    if (p.d_brow) (void)hipFree(p.d_brow);
-    p.d_packed = nullptr;
-    p.d_pvals = nullptr;
-    p.d_brow = nullptr;
 }
 
 // Modelled time per nonzero of a sorted-blocks plan in the units of kernels_adaptive.hip's PlanCost (1 = a chunk that
@@ -945,7 +915,7 @@ int plan_colsort(spmv_csr &h, PanelPlan &p, int want_rows, int want_waves, hipSt
     }
     const int cus = device_cus(h.device);
     int rc = build_colsort(h, p, want_rows ? want_rows : 4096, s);
-    if (rc) { release_colsort(p); return rc; }
+    if (rc) return rc;
     auto waves_for = [&](const PanelPlan &q) {
         if (q.sb_rows > 4096) return 4;
         if (want_waves) return want_waves;
@@ -956,24 +926,14 @@ int plan_colsort(spmv_csr &h, PanelPlan &p, int want_rows, int want_waves, hipSt
     // nonzero when there are blocks enough to fill the chip with 4 wavefronts per CU (a band of 1M columns at config 4:
     // 0.44 -> 0.25 lines per nonzero, 37 -> 41 % of peak); kept when the model prices it lower.
     if (want_rows == 0 && h.nnz > 0 && (double)p.lines > 0.27 * (double)h.nnz && p.nblocks >= 16 * cus) {
-        PanelPlan q = p;
-        q.d_packed = nullptr; q.d_pvals = nullptr; q.d_brow = nullptr;
-        q.d_ubeg = q.d_usimple = q.d_uend = q.d_ubase = q.d_tbeg = nullptr;
-        q.d_trow = nullptr;
-        const int rc8 = build_colsort(h, q, 8192, s);
-        if (rc8 == SPMV_OK) {
+        PanelPlan q;   // what p was on entry (a fresh plan), then built for 8192 rows; freed here unless it wins
+        q.sorted_mode = true;
+        if (build_colsort(h, q, 8192, s) == SPMV_OK) {
             q.sb_waves = 4;
-            if (colsort_model_cost(q, h.nnz) < colsort_model_cost(p, h.nnz)) {
-                release_colsort(p);
-                p = q;
-            } else {
-                release_colsort(q);
-            }
-        } else {
-            release_colsort(q);
+            if (colsort_model_cost(q, h.nnz) < colsort_model_cost(p, h.nnz)) p = std::move(q);
         }
     }
-    if ((rc = stamp_values(h, s, p.stamp))) { release_colsort(p); return rc; }
+    if ((rc = stamp_values(h, s, p.stamp))) return rc;
     p.ready = true;
     return SPMV_OK;
 }

@@ -121,11 +121,11 @@ int exclusive_scan_i32(int32_t *d_data, int64_t n, int32_t *d_total, hipStream_t
     const int64_t tiles = (n + kScanTile - 1) / kScanTile;
     DevPtr<int32_t> sums;
     SPMV_HIP_TRY(sums.alloc((size_t)tiles));
-    hipLaunchKernelGGL(k_scan_tile_sums, dim3((unsigned)tiles), dim3(kBlock), 0, s, n, d_data, sums.p);
+    hipLaunchKernelGGL(k_scan_tile_sums, dim3((unsigned)tiles), dim3(kBlock), 0, s, n, d_data, sums.get());
     if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_scan_tile_sums", __FILE__, __LINE__);
-    hipLaunchKernelGGL(k_exclusive_scan, dim3(1), dim3(1024), 0, s, tiles, sums.p, d_total);
+    hipLaunchKernelGGL(k_exclusive_scan, dim3(1), dim3(1024), 0, s, tiles, sums.get(), d_total);
     if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_exclusive_scan", __FILE__, __LINE__);
-    hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)tiles), dim3(kBlock), 0, s, n, d_data, sums.p);
+    hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)tiles), dim3(kBlock), 0, s, n, d_data, sums.get());
     if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_scan_tiles", __FILE__, __LINE__);
     SPMV_HIP_TRY(hipStreamSynchronize(s));   // `sums` is freed on return
     return SPMV_OK;
@@ -172,13 +172,6 @@ __global__ __launch_bounds__(kBlock) void k_dense_fill(int M, int N, int S, cons
     }
 }
 
-static int check_launch(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return SPMV_OK;
-}
-
 int dense_to_csr(int M, int N, const float *d_A, hipStream_t s, spmv_csr_t **out)
 {
     int rc;
@@ -193,24 +186,24 @@ int dense_to_csr(int M, int N, const float *d_A, hipStream_t s, spmv_csr_t **out
     SPMV_HIP_TRY(counts.alloc(ncnt));
     SPMV_HIP_TRY(total.alloc(1));
     SPMV_HIP_TRY(row_ptr.alloc((size_t)N + 1));
-    SPMV_HIP_TRY(hipMemsetAsync(total.p, 0, sizeof(int32_t), s));
+    SPMV_HIP_TRY(hipMemsetAsync(total.get(), 0, sizeof(int32_t), s));
     if (N > 0) {
         const int gx = (N + kBlock - 1) / kBlock;
-        hipLaunchKernelGGL(k_dense_count, dim3(gx, S), dim3(kBlock), 0, s, M, N, S, d_A, counts.p);
+        hipLaunchKernelGGL(k_dense_count, dim3(gx, S), dim3(kBlock), 0, s, M, N, S, d_A, counts.get());
         if ((rc = check_launch("k_dense_count"))) return rc;
-        if ((rc = exclusive_scan_i32(counts.p, (int64_t)ncnt, total.p, s))) return rc;
+        if ((rc = exclusive_scan_i32(counts.get(), (int64_t)ncnt, total.get(), s))) return rc;
     }
     hipLaunchKernelGGL(k_row_ptr_from_offsets, dim3((N + 1 + kBlock - 1) / kBlock), dim3(kBlock), 0, s, N, S,
-                       counts.p, total.p, row_ptr.p);
+                       counts.get(), total.get(), row_ptr.get());
     if ((rc = check_launch("k_row_ptr_from_offsets"))) return rc;
     int32_t nnz = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&nnz, total.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(&nnz, total.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
     SPMV_HIP_TRY(hipStreamSynchronize(s));
     SPMV_HIP_TRY(col.alloc((size_t)nnz));
     SPMV_HIP_TRY(val.alloc((size_t)nnz));
     if (N > 0 && nnz > 0) {
-        hipLaunchKernelGGL(k_dense_fill, dim3((N + kWave - 1) / kWave, S), dim3(kBlock), 0, s, M, N, S, d_A, counts.p,
-                           col.p, val.p);
+        hipLaunchKernelGGL(k_dense_fill, dim3((N + kWave - 1) / kWave, S), dim3(kBlock), 0, s, M, N, S, d_A, counts.get(),
+                           col.get(), val.get());
         if ((rc = check_launch("k_dense_fill"))) return rc;
     }
     SPMV_HIP_TRY(hipStreamSynchronize(s));
@@ -219,11 +212,9 @@ int dense_to_csr(int M, int N, const float *d_A, hipStream_t s, spmv_csr_t **out
     h->rows = N;
     h->cols = M;
     h->nnz = nnz;
-    h->owns_arrays = true;
     if (hipGetDevice(&h->device) != hipSuccess) h->device = 0;
-    h->d_row_ptr = row_ptr.release();
-    h->d_col_idx = col.release();
-    h->d_vals = val.release();
+    h->d_row_ptr = row_ptr; h->d_col_idx = col; h->d_vals = val;
+    h->own_row_ptr = std::move(row_ptr); h->own_col_idx = std::move(col); h->own_vals = std::move(val);
     *out = h;
     return SPMV_OK;
 }
@@ -432,6 +423,8 @@ int asp_gemv_ws(int M, int N, const float *d_asp, const float *d_x, float *d_y, 
 // device, grown on demand, handed from call to call in STREAM ORDER -- a call on another stream than the last
 // user's first makes its stream wait for the event recorded behind that user's combine kernel.  So the entry is
 // asynchronous (no host wait) as long as the buffer is large enough; growing it waits for the last user once.
+// The buffer is a raw pointer, not a DevPtr: the table lives for the whole process, and a DevPtr's destructor would call
+// hipFree at exit, after the HIP runtime may be gone.
 namespace {
 struct DenseWorkspace {
     std::mutex mu;

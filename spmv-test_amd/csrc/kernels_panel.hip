@@ -479,13 +479,6 @@ __global__ __launch_bounds__(kLdsWaves *kWave) void k_panel_lds(int nblocks, int
 // entries of d_packed / d_pvals of the sweep's plan: the last step of a block reads past its end
 size_t panel_slots(int64_t nnz) { return (size_t)nnz + 2 * kStepMax + 8; }
 
-int check_launch(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return SPMV_OK;
-}
-
 }  // namespace
 
 // Row blocks of equal NONZERO counts (nb0 cuts of row_ptr), any cut of more than `cap` rows split evenly:
@@ -497,17 +490,17 @@ int panel_row_blocks(const spmv_csr &h, int64_t nb0, int cap, hipStream_t s, Dev
     SPMV_HIP_TRY(nsub.alloc((size_t)nb0));
     SPMV_HIP_TRY(total.alloc(1));
     const unsigned gb = (unsigned)((nb0 + 1 + 255) / 256);
-    k_panel_cuts<<<dim3(gb), dim3(256), 0, s>>>(h.rows, h.nnz, (int)nb0, h.d_row_ptr, cut.p);
+    k_panel_cuts<<<dim3(gb), dim3(256), 0, s>>>(h.rows, h.nnz, (int)nb0, h.d_row_ptr, cut.get());
     int rc = check_launch("k_panel_cuts");
     if (rc) return rc;
-    k_panel_nsub<<<dim3(gb), dim3(256), 0, s>>>((int)nb0, cap, cut.p, nsub.p);
+    k_panel_nsub<<<dim3(gb), dim3(256), 0, s>>>((int)nb0, cap, cut.get(), nsub.get());
     if ((rc = check_launch("k_panel_nsub"))) return rc;
-    if ((rc = exclusive_scan_i32(nsub.p, nb0, total.p, s))) return rc;
+    if ((rc = exclusive_scan_i32(nsub.get(), nb0, total.get(), s))) return rc;
     int32_t nblocks = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&nblocks, total.p, sizeof nblocks, hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(&nblocks, total.get(), sizeof nblocks, hipMemcpyDeviceToHost, s));
     SPMV_HIP_TRY(hipStreamSynchronize(s));
     SPMV_HIP_TRY(brow.alloc((size_t)nblocks + 1));
-    k_panel_brow<<<dim3(gb), dim3(256), 0, s>>>(h.rows, (int)nb0, cap, cut.p, nsub.p, total.p, brow.p);
+    k_panel_brow<<<dim3(gb), dim3(256), 0, s>>>(h.rows, (int)nb0, cap, cut.get(), nsub.get(), total.get(), brow.get());
     if ((rc = check_launch("k_panel_brow"))) return rc;
     SPMV_HIP_TRY(hipStreamSynchronize(s));   // the temporaries are freed on return
     *nblocks_out = nblocks;
@@ -527,17 +520,6 @@ int panel_tile_ptr(const spmv_csr &h, const int32_t *d_brow, int nblocks, int pw
     if (np > kMaxPanels) { set_error("panel_tile_ptr: %d panels (at most %d)", np, kMaxPanels); return SPMV_ERR_INVALID; }
     k_panel_tiles<<<dim3((unsigned)nblocks), dim3(256), 0, s>>>(d_brow, h.d_row_ptr, h.d_col_idx, pw_bits, np, d_tile_ptr);
     return check_launch("k_panel_tiles");
-}
-
-void destroy_panel(PanelPlan &p)
-{
-    destroy_binned(p);
-    destroy_colsort(p);
-    if (p.d_packed) (void)hipFree(p.d_packed);
-    if (p.d_pvals) (void)hipFree(p.d_pvals);
-    if (p.d_tile_ptr) (void)hipFree(p.d_tile_ptr);
-    if (p.d_brow) (void)hipFree(p.d_brow);
-    p = PanelPlan();
 }
 
 // one launch = one set of co-resident waves sweeping in step: 2 workgroups (4 waves) per CU
@@ -569,12 +551,12 @@ int plan_panel_with(spmv_csr &h, int want_bits, int want_waves, int want_mode, h
 //            5 = binned, the products stored in bin order by the product launch (thin tiles)
 int build_panel(spmv_csr &h, PanelPlan &dst, int want_bits, int want_waves, int want_mode, hipStream_t s)
 {
-    destroy_panel(dst);
+    dst = PanelPlan{};
     PanelPlan p;
     if (want_mode == 4 || want_mode == 5) {      // binned: two streaming launches, no gather from memory (kernels_binned.hip)
         const int rc = plan_binned(h, p, want_bits, want_mode == 5, s);
-        if (rc) { destroy_panel(p); return rc; }
-        dst = p;
+        if (rc) return rc;
+        dst = std::move(p);
         return SPMV_OK;
     }
     {
@@ -586,8 +568,8 @@ int build_panel(spmv_csr &h, PanelPlan &dst, int want_bits, int want_waves, int 
                 return SPMV_ERR_INVALID;
             }
             const int rc = plan_colsort(h, p, want_mode == 3 ? want_bits : 0, want_mode == 3 ? want_waves : 0, s);
-            if (rc) { destroy_panel(p); return rc; }
-            dst = p;
+            if (rc) return rc;
+            dst = std::move(p);
             return SPMV_OK;
         }
     }
@@ -639,7 +621,7 @@ int build_panel(spmv_csr &h, PanelPlan &dst, int want_bits, int want_waves, int 
     if (h.rows == 0) {
         p.ready = true;
         p.stamp.gen = h.values_gen;
-        dst = p;
+        dst = std::move(p);
         return SPMV_OK;
     }
     const int64_t launches0 =
@@ -664,32 +646,32 @@ int build_panel(spmv_csr &h, PanelPlan &dst, int want_bits, int want_waves, int 
     SPMV_HIP_TRY(pvals.alloc(slots));
     SPMV_HIP_TRY(tiles.alloc((size_t)p.nblocks * (size_t)(p.npanels + 1)));
     SPMV_HIP_TRY(rowloc.alloc((size_t)h.nnz));
-    SPMV_HIP_TRY(hipMemsetAsync(packed.p + h.nnz, 0, sizeof(uint32_t) * (slots - (size_t)h.nnz), s));
-    SPMV_HIP_TRY(hipMemsetAsync(pvals.p + h.nnz, 0, sizeof(float) * (slots - (size_t)h.nnz), s));
-    k_panel_tiles<<<dim3((unsigned)p.nblocks), dim3(256), 0, s>>>(brow.p, h.d_row_ptr, h.d_col_idx, p.pw_bits,
-                                                                   p.npanels, tiles.p);
+    SPMV_HIP_TRY(hipMemsetAsync(packed.get() + h.nnz, 0, sizeof(uint32_t) * (slots - (size_t)h.nnz), s));
+    SPMV_HIP_TRY(hipMemsetAsync(pvals.get() + h.nnz, 0, sizeof(float) * (slots - (size_t)h.nnz), s));
+    k_panel_tiles<<<dim3((unsigned)p.nblocks), dim3(256), 0, s>>>(brow.get(), h.d_row_ptr, h.d_col_idx, p.pw_bits,
+                                                                   p.npanels, tiles.get());
     if ((rc = check_launch("k_panel_tiles"))) return rc;
     if (h.nnz > 0) {
-        k_panel_rowloc<<<dim3((unsigned)p.nblocks), dim3(256), 0, s>>>(brow.p, h.d_row_ptr, rowloc.p);
+        k_panel_rowloc<<<dim3((unsigned)p.nblocks), dim3(256), 0, s>>>(brow.get(), h.d_row_ptr, rowloc.get());
         if ((rc = check_launch("k_panel_rowloc"))) return rc;
         k_panel_fill<<<dim3((unsigned)((p.nblocks + 3) / 4)), dim3(256), 0, s>>>(
-            p.nblocks, brow.p, h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.p, p.pw_bits, p.npanels, tiles.p, packed.p,
-            pvals.p);
+            p.nblocks, brow.get(), h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.get(), p.pw_bits, p.npanels, tiles.get(), packed.get(),
+            pvals.get());
         if ((rc = check_launch("k_panel_fill"))) return rc;
         if (!p.lds_mode) {   // the LDS kernel folds equal rows itself
-            k_panel_joins<<<dim3((unsigned)p.nblocks), dim3(256), 0, s>>>(brow.p, p.npanels, h.d_row_ptr, tiles.p,
-                                                                           packed.p);
+            k_panel_joins<<<dim3((unsigned)p.nblocks), dim3(256), 0, s>>>(brow.get(), p.npanels, h.d_row_ptr, tiles.get(),
+                                                                           packed.get());
             if ((rc = check_launch("k_panel_joins"))) return rc;
         }
     }
     if ((rc = stamp_values(h, s, p.stamp))) return rc;
     SPMV_HIP_TRY(hipStreamSynchronize(s));   // the temporaries are freed on return
-    p.d_packed = packed.release();
-    p.d_pvals = pvals.release();
-    p.d_tile_ptr = tiles.release();
-    p.d_brow = brow.release();
+    p.d_packed = std::move(packed);
+    p.d_pvals = std::move(pvals);
+    p.d_tile_ptr = std::move(tiles);
+    p.d_brow = std::move(brow);
     p.ready = true;
-    dst = p;
+    dst = std::move(p);
     return SPMV_OK;
 }
 

@@ -707,13 +707,6 @@ __global__ __launch_bounds__(kBlock) void k_vector(int64_t rows, const int32_t *
 }
 
 // ---------------------------------------------------------------------------
-static int check_launch(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return SPMV_OK;
-}
-
 static bool grid_ok(int64_t blocks)
 {
     if (blocks > 0x7fffffffLL) {
@@ -721,19 +714,6 @@ static bool grid_ok(int64_t blocks)
         return false;
     }
     return true;
-}
-
-void destroy_wave(WavePlan &p)
-{
-    (void)hipFree(p.d_long_row);
-    (void)hipFree(p.d_long_first);
-    (void)hipFree(p.d_piece_k0);
-    (void)hipFree(p.d_piece_len);
-    (void)hipFree(p.d_partial);
-    (void)hipFree(p.d_blk_lo);
-    (void)hipFree(p.d_col16);
-    (void)hipFree(p.d_piece_base);
-    p = WavePlan{};
 }
 
 template <int MODE, bool ORDERED, int BLOCK>
@@ -762,7 +742,7 @@ static void launch_bundle(const spmv_csr &h, const WavePlan &p, const float *x, 
 int plan_wave(spmv_csr &h, hipStream_t s)
 {
     if (h.plan_wave.ready) return SPMV_OK;
-    destroy_wave(h.plan_wave);
+    h.plan_wave = WavePlan{};
     WavePlan &p = h.plan_wave;
     if (h.rows == 0 || h.nnz > 32 * h.rows) { p.ready = true; return SPMV_OK; }   // (long-row matrices run k_wave<true>)
     const int64_t nblk = (h.rows + kWavePlanBlock - 1) / kWavePlanBlock;     // (of the two list kernels)
@@ -774,11 +754,11 @@ int plan_wave(spmv_csr &h, hipStream_t s)
     SPMV_HIP_TRY(d_bl.alloc((size_t)nblk));
     SPMV_HIP_TRY(d_bp.alloc((size_t)nblk + 1));
     SPMV_HIP_TRY(blk_lo.alloc((size_t)p.blocks));
-    hipLaunchKernelGGL(k_wave_plan_count, dim3((unsigned)nblk), dim3(kWavePlanBlock), 0, s, h.rows, h.d_row_ptr, d_bl.p, d_bp.p);
+    hipLaunchKernelGGL(k_wave_plan_count, dim3((unsigned)nblk), dim3(kWavePlanBlock), 0, s, h.rows, h.d_row_ptr, d_bl.get(), d_bp.get());
     if (int rc = check_launch("k_wave_plan_count")) return rc;
     std::vector<int32_t> bl((size_t)nblk), bp((size_t)nblk + 1);
-    SPMV_HIP_TRY(hipMemcpyAsync(bl.data(), d_bl.p, sizeof(int32_t) * (size_t)nblk, hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipMemcpyAsync(bp.data(), d_bp.p, sizeof(int32_t) * (size_t)nblk, hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(bl.data(), d_bl.get(), sizeof(int32_t) * (size_t)nblk, hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(bp.data(), d_bp.get(), sizeof(int32_t) * (size_t)nblk, hipMemcpyDeviceToHost, s));
     SPMV_HIP_TRY(hipStreamSynchronize(s));
     int64_t nl = 0, np = 0;
     for (int64_t i = 0; i < nblk; ++i) {
@@ -799,24 +779,24 @@ int plan_wave(spmv_csr &h, hipStream_t s)
     SPMV_HIP_TRY(k0.alloc((size_t)np));
     SPMV_HIP_TRY(ln.alloc((size_t)np));
     SPMV_HIP_TRY(part.alloc((size_t)np));
-    SPMV_HIP_TRY(hipMemcpyAsync(d_bl.p, bl.data(), sizeof(int32_t) * (size_t)nblk, hipMemcpyHostToDevice, s));
-    SPMV_HIP_TRY(hipMemcpyAsync(d_bp.p, bp.data(), sizeof(int32_t) * ((size_t)nblk + 1), hipMemcpyHostToDevice, s));
-    SPMV_HIP_TRY(hipMemcpyAsync(lf.p + nl, &bp[(size_t)nblk], sizeof(int32_t), hipMemcpyHostToDevice, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(d_bl.get(), bl.data(), sizeof(int32_t) * (size_t)nblk, hipMemcpyHostToDevice, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(d_bp.get(), bp.data(), sizeof(int32_t) * ((size_t)nblk + 1), hipMemcpyHostToDevice, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(lf.get() + nl, &bp[(size_t)nblk], sizeof(int32_t), hipMemcpyHostToDevice, s));
     if (nl) {
-        hipLaunchKernelGGL(k_wave_plan_fill, dim3((unsigned)nblk), dim3(kWavePlanBlock), 0, s, h.rows, h.d_row_ptr, d_bl.p, d_bp.p,
-                           lr.p, lf.p, k0.p, ln.p);
+        hipLaunchKernelGGL(k_wave_plan_fill, dim3((unsigned)nblk), dim3(kWavePlanBlock), 0, s, h.rows, h.d_row_ptr, d_bl.get(), d_bp.get(),
+                           lr.get(), lf.get(), k0.get(), ln.get());
         if (int rc = check_launch("k_wave_plan_fill")) return rc;
     }
-    p.d_long_row = lr.release();
-    p.d_long_first = lf.release();
-    p.d_piece_k0 = k0.release();
-    p.d_piece_len = ln.release();
-    p.d_partial = part.release();
+    p.d_long_row = std::move(lr);
+    p.d_long_first = std::move(lf);
+    p.d_piece_k0 = std::move(k0);
+    p.d_piece_len = std::move(ln);
+    p.d_partial = std::move(part);
     // the windows: the bundle kernel in its plan mode (the same runs and pieces, minimum and maximum column instead of products)
-    launch_bundle<2>(h, p, nullptr, nullptr, blk_lo.p, nullptr, s);
+    launch_bundle<2>(h, p, nullptr, nullptr, blk_lo.get(), nullptr, s);
     if (int rc = check_launch("k_wave_bundle<plan>")) return rc;
     std::vector<int32_t> wl((size_t)p.blocks);
-    SPMV_HIP_TRY(hipMemcpyAsync(wl.data(), blk_lo.p, sizeof(int32_t) * (size_t)p.blocks, hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(wl.data(), blk_lo.get(), sizeof(int32_t) * (size_t)p.blocks, hipMemcpyDeviceToHost, s));
     SPMV_HIP_TRY(hipStreamSynchronize(s));      // (also: bl / bp are host memory of this call)
     for (int64_t i = 0; i < p.blocks; ++i) p.win_blocks += wl[(size_t)i] >= 0;
     const char *c16env = getenv("SPMV_WAVE_COL16");
@@ -829,20 +809,20 @@ int plan_wave(spmv_csr &h, hipStream_t s)
         DevPtr<int32_t> pbase;
         SPMV_HIP_TRY(c16.alloc((size_t)h.nnz));
         if (p.windows) {
-            launch_bundle<3>(h, p, nullptr, nullptr, blk_lo.p, c16.p, s);
+            launch_bundle<3>(h, p, nullptr, nullptr, blk_lo.get(), c16.get(), s);
             if (int rc = check_launch("k_wave_bundle<col16>")) return rc;
         }
         if (np) {
             SPMV_HIP_TRY(pbase.alloc((size_t)np));
             hipLaunchKernelGGL(k_wave_plan_piece16, dim3((unsigned)((np + kBlock / kWave - 1) / (kBlock / kWave))), dim3(kBlock), 0, s,
-                               (int)np, p.d_piece_k0, p.d_piece_len, h.d_col_idx, pbase.p, c16.p);
+                               (int)np, p.d_piece_k0, p.d_piece_len, h.d_col_idx, pbase.get(), c16.get());
             if (int rc = check_launch("k_wave_plan_piece16")) return rc;
         }
         SPMV_HIP_TRY(hipStreamSynchronize(s));
-        p.d_col16 = c16.release();
-        p.d_piece_base = pbase.release();
+        p.d_col16 = std::move(c16);
+        p.d_piece_base = std::move(pbase);
     }
-    p.d_blk_lo = blk_lo.release();
+    p.d_blk_lo = std::move(blk_lo);
     p.ready = true;
     return SPMV_OK;
 }
@@ -1047,15 +1027,15 @@ int values_checksum(const spmv_csr &h, hipStream_t s, uint64_t *out)
 {
     DevPtr<unsigned long long> d;
     SPMV_HIP_TRY(d.alloc(1));
-    SPMV_HIP_TRY(hipMemsetAsync(d.p, 0, sizeof(unsigned long long), s));
+    SPMV_HIP_TRY(hipMemsetAsync(d.get(), 0, sizeof(unsigned long long), s));
     if (h.nnz > 0) {
         int64_t blocks = (h.nnz + 256 * 16 - 1) / (256 * 16);
         if (blocks > 256 * 16) blocks = 256 * 16;
-        k_values_checksum<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(h.nnz, h.d_vals, d.p);
+        k_values_checksum<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(h.nnz, h.d_vals, d.get());
         if (int rc = check_launch("k_values_checksum")) return rc;
     }
     unsigned long long v = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&v, d.p, sizeof v, hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(&v, d.get(), sizeof v, hipMemcpyDeviceToHost, s));
     SPMV_HIP_TRY(hipStreamSynchronize(s));
     *out = (uint64_t)v;
     return SPMV_OK;

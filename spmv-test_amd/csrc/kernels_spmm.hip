@@ -174,23 +174,12 @@ __global__ __launch_bounds__(kSpmmBlock) void k_spmm_combine(int n_long, const i
 
 }  // namespace
 
-void destroy_spmm(SpmmPlan &p)
-{
-    (void)hipFree(p.d_order);
-    (void)hipFree(p.d_long_row);
-    (void)hipFree(p.d_long_first);
-    (void)hipFree(p.d_piece_k0);
-    (void)hipFree(p.d_piece_len);
-    (void)hipFree(p.d_partial);
-    p = SpmmPlan{};
-}
-
 // The plan: the rows of more than kSpmmRowCap nonzeros and their pieces, in row order -- a function of row_ptr alone.
 // Reads row_ptr back to the host once and waits for the stream (not graph-capturable; spmv_csr_spmm is).
 int plan_spmm(spmv_csr &h, hipStream_t s)
 {
     if (h.plan_spmm.ready) return SPMV_OK;
-    destroy_spmm(h.plan_spmm);
+    h.plan_spmm = SpmmPlan{};
     std::vector<int32_t> rp((size_t)h.rows + 1);
     SPMV_HIP_TRY(hipMemcpyAsync(rp.data(), h.d_row_ptr, sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, s));
     SPMV_HIP_TRY(hipStreamSynchronize(s));
@@ -223,7 +212,7 @@ int plan_spmm(spmv_csr &h, hipStream_t s)
     p.pieces = (int)k0.size();
     DevPtr<int32_t> d_ord, d_lr, d_lf, d_k0, d_ln;
     SPMV_HIP_TRY(d_ord.alloc(order.size()));
-    SPMV_HIP_TRY(hipMemcpyAsync(d_ord.p, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(d_ord.get(), order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice, s));
     DevPtr<float> d_part;
     SPMV_HIP_TRY(d_lr.alloc(lr.size()));
     SPMV_HIP_TRY(d_lf.alloc(lf.size()));
@@ -231,22 +220,22 @@ int plan_spmm(spmv_csr &h, hipStream_t s)
     SPMV_HIP_TRY(d_ln.alloc(ln.size()));
     SPMV_HIP_TRY(d_part.alloc((size_t)p.pieces * kSpmmMaxK));
     if (p.n_long) {
-        SPMV_HIP_TRY(hipMemcpyAsync(d_lr.p, lr.data(), sizeof(int32_t) * lr.size(), hipMemcpyHostToDevice, s));
-        SPMV_HIP_TRY(hipMemcpyAsync(d_k0.p, k0.data(), sizeof(int32_t) * k0.size(), hipMemcpyHostToDevice, s));
-        SPMV_HIP_TRY(hipMemcpyAsync(d_ln.p, ln.data(), sizeof(int32_t) * ln.size(), hipMemcpyHostToDevice, s));
+        SPMV_HIP_TRY(hipMemcpyAsync(d_lr.get(), lr.data(), sizeof(int32_t) * lr.size(), hipMemcpyHostToDevice, s));
+        SPMV_HIP_TRY(hipMemcpyAsync(d_k0.get(), k0.data(), sizeof(int32_t) * k0.size(), hipMemcpyHostToDevice, s));
+        SPMV_HIP_TRY(hipMemcpyAsync(d_ln.get(), ln.data(), sizeof(int32_t) * ln.size(), hipMemcpyHostToDevice, s));
     }
-    SPMV_HIP_TRY(hipMemcpyAsync(d_lf.p, lf.data(), sizeof(int32_t) * lf.size(), hipMemcpyHostToDevice, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(d_lf.get(), lf.data(), sizeof(int32_t) * lf.size(), hipMemcpyHostToDevice, s));
     SPMV_HIP_TRY(hipStreamSynchronize(s));     // (the host vectors die with this call)
-    p.d_order = d_ord.release();
-    p.d_long_row = d_lr.release();
-    p.d_long_first = d_lf.release();
-    p.d_piece_k0 = d_k0.release();
-    p.d_piece_len = d_ln.release();
-    p.d_partial = d_part.release();
+    p.d_order = std::move(d_ord);
+    p.d_long_row = std::move(d_lr);
+    p.d_long_first = std::move(d_lf);
+    p.d_piece_k0 = std::move(d_k0);
+    p.d_piece_len = std::move(d_ln);
+    p.d_partial = std::move(d_part);
     p.row_cap = kSpmmRowCap;
     p.piece_len = kSpmmPiece;
     p.ready = true;
-    h.plan_spmm = p;
+    h.plan_spmm = std::move(p);
     return SPMV_OK;
 }
 

@@ -20,16 +20,6 @@
 
 using f4 = float __attribute__((ext_vector_type(4)));
 
-struct spmv_tcsr {
-    int M = 0, N = 0;
-    int64_t nnz = 0, nblocks = 0;
-    int32_t *d_blk_idx = nullptr;   // [nblocks+1]
-    uint32_t *d_bitmaps = nullptr;  // [M*N/32]
-    float *d_vals = nullptr;        // [nnz]
-    int nseg = 0;                   // input-dimension segments per strip pair
-    float *d_partial = nullptr;     // [nseg][N] partial sums, combined in segment order
-};
-
 namespace spmv {
 
 // ---- build ----------------------------------------------------------------------------------
@@ -174,13 +164,6 @@ __global__ __launch_bounds__(kBlock) void k_tcsr_combine(int N, int nseg, const 
     y[i] = s;
 }
 
-static int check_launch(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return SPMV_OK;
-}
-
 int tcsr_from_dense(int M, int N, const float *d_A, hipStream_t s, spmv_tcsr_t **out)
 {
     const int64_t nblk = (int64_t)(M / 32) * (N / 32);
@@ -190,26 +173,26 @@ int tcsr_from_dense(int M, int N, const float *d_A, hipStream_t s, spmv_tcsr_t *
     SPMV_HIP_TRY(blk_idx.alloc((size_t)nblk + 1));
     SPMV_HIP_TRY(total.alloc(1));
     SPMV_HIP_TRY(bitmaps.alloc((size_t)nblk * 32));
-    SPMV_HIP_TRY(hipMemsetAsync(total.p, 0, sizeof(int32_t), s));
+    SPMV_HIP_TRY(hipMemsetAsync(total.get(), 0, sizeof(int32_t), s));
     int rc;
     int32_t nnz = 0;
     if (nblk > 0) {
         const unsigned grid = (unsigned)((nblk + 7) / 8);
-        hipLaunchKernelGGL(k_tcsr_bits, dim3(grid), dim3(kBlock), 0, s, M, N, d_A, bitmaps.p, blk_idx.p);
+        hipLaunchKernelGGL(k_tcsr_bits, dim3(grid), dim3(kBlock), 0, s, M, N, d_A, bitmaps.get(), blk_idx.get());
         if ((rc = check_launch("k_tcsr_bits"))) return rc;
-        if ((rc = exclusive_scan_i32(blk_idx.p, nblk, total.p, s))) return rc;
-        hipLaunchKernelGGL(k_tcsr_sentinel, dim3(1), dim3(64), 0, s, nblk, total.p, blk_idx.p);
+        if ((rc = exclusive_scan_i32(blk_idx.get(), nblk, total.get(), s))) return rc;
+        hipLaunchKernelGGL(k_tcsr_sentinel, dim3(1), dim3(64), 0, s, nblk, total.get(), blk_idx.get());
         if ((rc = check_launch("k_tcsr_sentinel"))) return rc;
-        SPMV_HIP_TRY(hipMemcpyAsync(&nnz, total.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        SPMV_HIP_TRY(hipMemcpyAsync(&nnz, total.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
         SPMV_HIP_TRY(hipStreamSynchronize(s));
         SPMV_HIP_TRY(vals.alloc((size_t)nnz + 4));  // k_tcsr_spmv reads whole 16-byte vectors around a block
         if (nnz > 0) {
-            hipLaunchKernelGGL(k_tcsr_fill, dim3(grid), dim3(kBlock), 0, s, M, N, d_A, bitmaps.p, blk_idx.p, vals.p);
+            hipLaunchKernelGGL(k_tcsr_fill, dim3(grid), dim3(kBlock), 0, s, M, N, d_A, bitmaps.get(), blk_idx.get(), vals.get());
             if ((rc = check_launch("k_tcsr_fill"))) return rc;
         }
         SPMV_HIP_TRY(hipStreamSynchronize(s));
     } else {
-        SPMV_HIP_TRY(hipMemsetAsync(blk_idx.p, 0, sizeof(int32_t), s));
+        SPMV_HIP_TRY(hipMemsetAsync(blk_idx.get(), 0, sizeof(int32_t), s));
         SPMV_HIP_TRY(vals.alloc(1));
         SPMV_HIP_TRY(hipStreamSynchronize(s));
     }
@@ -222,10 +205,10 @@ int tcsr_from_dense(int M, int N, const float *d_A, hipStream_t s, spmv_tcsr_t *
     spmv_tcsr *h = new spmv_tcsr();
     h->M = M; h->N = N; h->nnz = nnz; h->nblocks = nblk;
     h->nseg = nseg;
-    h->d_partial = partial.release();
-    h->d_blk_idx = blk_idx.release();
-    h->d_bitmaps = bitmaps.release();
-    h->d_vals = vals.release();
+    h->d_partial = std::move(partial);
+    h->d_blk_idx = std::move(blk_idx);
+    h->d_bitmaps = std::move(bitmaps);
+    h->d_vals = std::move(vals);
     *out = h;
     return SPMV_OK;
 }
@@ -245,16 +228,6 @@ int tcsr_run(const spmv_tcsr &h, const float *d_x, float *d_y, hipStream_t s)
     if (rc) return rc;
     hipLaunchKernelGGL(k_tcsr_combine, dim3((h.N + kBlock - 1) / kBlock), dim3(kBlock), 0, s, h.N, h.nseg, h.d_partial, d_y);
     return check_launch("k_tcsr_combine");
-}
-
-void tcsr_free(spmv_tcsr *h)
-{
-    if (!h) return;
-    if (h->d_blk_idx) (void)hipFree(h->d_blk_idx);
-    if (h->d_bitmaps) (void)hipFree(h->d_bitmaps);
-    if (h->d_vals) (void)hipFree(h->d_vals);
-    if (h->d_partial) (void)hipFree(h->d_partial);
-    delete h;
 }
 
 void tcsr_dims(const spmv_tcsr &h, int *M, int *N) { *M = h.M; *N = h.N; }

@@ -31,13 +31,6 @@ constexpr int kXWaves = 4;          // wavefronts (= private copies) per workgro
 constexpr int kXSlabMax = 64;       // slabs per block: the combine kernel adds that many partials per output
 constexpr int64_t kXTableMax = 1ll << 27;
 
-int check_launch(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
-    return SPMV_OK;
-}
-
 // cnt[b*cols + j] = nonzeros of input j in output block b; dup[0] = 1 when a row holds the same column twice in a
 // row, dup[1] = 1 when the columns of a row do not ascend (then a duplicate need not be adjacent: [3, 5, 3] -- two lanes
 // of one segment would read-add-write the same LDS word, so the plan refuses unsorted rows outright)
@@ -172,21 +165,10 @@ __global__ __launch_bounds__(kBlock) void k_xs_combine(int64_t rows, int slabs, 
 
 }  // namespace
 
-void destroy_xskip(XskipPlan &p)
-{
-    if (p.d_block_seg) (void)hipFree(p.d_block_seg);
-    if (p.d_seg_input) (void)hipFree(p.d_seg_input);
-    if (p.d_seg_ptr) (void)hipFree(p.d_seg_ptr);
-    if (p.d_erow) (void)hipFree(p.d_erow);
-    if (p.d_evals) (void)hipFree(p.d_evals);
-    if (p.d_part) (void)hipFree(p.d_part);
-    p = XskipPlan();
-}
-
 int plan_xskip(spmv_csr &h, hipStream_t s)
 {
     if (h.plan_xskip.ready && h.plan_xskip.stamp.gen == h.values_gen) return SPMV_OK;   // (a stale copy is rebuilt)
-    destroy_xskip(h.plan_xskip);
+    h.plan_xskip = XskipPlan{};
     XskipPlan p;
     p.nblocks = (int)((h.rows + kXR - 1) / kXR);
     const int64_t table = (int64_t)p.nblocks * h.cols;
@@ -198,7 +180,7 @@ int plan_xskip(spmv_csr &h, hipStream_t s)
     if (h.rows == 0 || h.nnz == 0) {
         p.ready = true;
         p.stamp.gen = h.values_gen;
-        h.plan_xskip = p;
+        h.plan_xskip = std::move(p);
         return SPMV_OK;
     }
     int rc;
@@ -209,19 +191,19 @@ int plan_xskip(spmv_csr &h, hipStream_t s)
     SPMV_HIP_TRY(tot_nnz.alloc(1));
     SPMV_HIP_TRY(tot_seg.alloc(1));
     SPMV_HIP_TRY(dup.alloc(2));
-    SPMV_HIP_TRY(hipMemsetAsync(cnt.p, 0, sizeof(int32_t) * (size_t)table, s));
-    SPMV_HIP_TRY(hipMemsetAsync(dup.p, 0, 2 * sizeof(int32_t), s));
+    SPMV_HIP_TRY(hipMemsetAsync(cnt.get(), 0, sizeof(int32_t) * (size_t)table, s));
+    SPMV_HIP_TRY(hipMemsetAsync(dup.get(), 0, 2 * sizeof(int32_t), s));
     const unsigned grows = (unsigned)((h.rows + 3) / 4), gtab = (unsigned)((table + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_xs_count, dim3(grows), dim3(kBlock), 0, s, h.rows, h.cols, h.d_row_ptr, h.d_col_idx, cnt.p, dup.p);
+    hipLaunchKernelGGL(k_xs_count, dim3(grows), dim3(kBlock), 0, s, h.rows, h.cols, h.d_row_ptr, h.d_col_idx, cnt.get(), dup.get());
     if ((rc = check_launch("k_xs_count"))) return rc;
-    SPMV_HIP_TRY(hipMemcpyAsync(pos.p, cnt.p, sizeof(int32_t) * (size_t)table, hipMemcpyDeviceToDevice, s));
-    if ((rc = exclusive_scan_i32(pos.p, table, tot_nnz.p, s))) return rc;
-    hipLaunchKernelGGL(k_xs_flags, dim3(gtab), dim3(kBlock), 0, s, table, cnt.p, flag.p);
+    SPMV_HIP_TRY(hipMemcpyAsync(pos.get(), cnt.get(), sizeof(int32_t) * (size_t)table, hipMemcpyDeviceToDevice, s));
+    if ((rc = exclusive_scan_i32(pos.get(), table, tot_nnz.get(), s))) return rc;
+    hipLaunchKernelGGL(k_xs_flags, dim3(gtab), dim3(kBlock), 0, s, table, cnt.get(), flag.get());
     if ((rc = check_launch("k_xs_flags"))) return rc;
-    if ((rc = exclusive_scan_i32(flag.p, table, tot_seg.p, s))) return rc;
+    if ((rc = exclusive_scan_i32(flag.get(), table, tot_seg.get(), s))) return rc;
     int32_t nseg = 0, has_dup[2] = {0, 0};
-    SPMV_HIP_TRY(hipMemcpyAsync(&nseg, tot_seg.p, sizeof nseg, hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipMemcpyAsync(has_dup, dup.p, sizeof has_dup, hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(&nseg, tot_seg.get(), sizeof nseg, hipMemcpyDeviceToHost, s));
+    SPMV_HIP_TRY(hipMemcpyAsync(has_dup, dup.get(), sizeof has_dup, hipMemcpyDeviceToHost, s));
     SPMV_HIP_TRY(hipStreamSynchronize(s));
     if (has_dup[0]) {
         set_error("spmv_csr_plan(xskip): a row holds the same column twice; this variant needs sorted, duplicate-free rows");
@@ -241,11 +223,11 @@ int plan_xskip(spmv_csr &h, hipStream_t s)
     SPMV_HIP_TRY(seg_ptr.alloc((size_t)nseg + 1));
     SPMV_HIP_TRY(erow.alloc((size_t)h.nnz));
     SPMV_HIP_TRY(evals.alloc((size_t)h.nnz));
-    hipLaunchKernelGGL(k_xs_segments, dim3(gtab), dim3(kBlock), 0, s, (int64_t)p.nblocks, h.cols, cnt.p, pos.p, flag.p, tot_seg.p,
-                       tot_nnz.p, seg_input.p, seg_ptr.p, block_seg.p);
+    hipLaunchKernelGGL(k_xs_segments, dim3(gtab), dim3(kBlock), 0, s, (int64_t)p.nblocks, h.cols, cnt.get(), pos.get(), flag.get(), tot_seg.get(),
+                       tot_nnz.get(), seg_input.get(), seg_ptr.get(), block_seg.get());
     if ((rc = check_launch("k_xs_segments"))) return rc;
-    hipLaunchKernelGGL(k_xs_fill, dim3(grows), dim3(kBlock), 0, s, h.rows, h.cols, h.d_row_ptr, h.d_col_idx, h.d_vals, pos.p,
-                       erow.p, evals.p);
+    hipLaunchKernelGGL(k_xs_fill, dim3(grows), dim3(kBlock), 0, s, h.rows, h.cols, h.d_row_ptr, h.d_col_idx, h.d_vals, pos.get(),
+                       erow.get(), evals.get());
     if ((rc = check_launch("k_xs_fill"))) return rc;
     // slabs per block: enough workgroups to fill the chip four times, at least 8 segments each, at most 64
     int slabs = (4 * device_cus(h.device) + p.nblocks - 1) / p.nblocks;
@@ -255,15 +237,15 @@ int plan_xskip(spmv_csr &h, hipStream_t s)
     if (slabs < 1) slabs = 1;
     p.slabs = slabs;
     if ((rc = stamp_values(h, s, p.stamp))) return rc;
-    if (slabs > 1) SPMV_HIP_TRY(hipMalloc((void **)&p.d_part, sizeof(float) * (size_t)p.nblocks * slabs * kXR));
+    if (slabs > 1) SPMV_HIP_TRY(p.d_part.alloc((size_t)p.nblocks * slabs * kXR));
     SPMV_HIP_TRY(hipStreamSynchronize(s));   // the temporaries are freed on return
-    p.d_block_seg = block_seg.release();
-    p.d_seg_input = seg_input.release();
-    p.d_seg_ptr = seg_ptr.release();
-    p.d_erow = erow.release();
-    p.d_evals = evals.release();
+    p.d_block_seg = std::move(block_seg);
+    p.d_seg_input = std::move(seg_input);
+    p.d_seg_ptr = std::move(seg_ptr);
+    p.d_erow = std::move(erow);
+    p.d_evals = std::move(evals);
     p.ready = true;
-    h.plan_xskip = p;
+    h.plan_xskip = std::move(p);
     return SPMV_OK;
 }
 

@@ -4,6 +4,7 @@
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
+#include <utility>
 #include "spmv_hip.h"
 
 namespace spmv {
@@ -18,16 +19,45 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
         if (e__ != hipSuccess) return ::spmv::hip_fail(e__, #call, __FILE__, __LINE__); \
     } while (0)
 
-// Device allocation that frees itself unless release()d into a handle.
+static inline int check_launch(const char *what)
+{
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
+    return SPMV_OK;
+}
+
+// The one owner of a device array: move-only, freed when it is destroyed, reset() or assigned over.  Reads convert it to
+// T * (kernel arguments, offsets, null tests); it is written only by alloc(), a move or reset(), never from a raw pointer.
+// Not for anything of static storage duration: its destructor would call hipFree after the HIP runtime may be gone.
 template <typename T>
-struct DevPtr {
-    T *p = nullptr;
+class DevPtr {
+    T *p_ = nullptr;
+public:
     DevPtr() = default;
-    DevPtr(const DevPtr &) = delete;
-    DevPtr &operator=(const DevPtr &) = delete;
-    ~DevPtr() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t count) { return hipMalloc((void **)&p, sizeof(T) * (count ? count : 1)); }
-    T *release() { T *q = p; p = nullptr; return q; }
+    DevPtr(DevPtr &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevPtr &operator=(DevPtr &&o) noexcept
+    {
+        T *q = o.p_;
+        o.p_ = nullptr;
+        (void)reset();
+        p_ = q;
+        return *this;
+    }
+    ~DevPtr() { (void)reset(); }
+    DevPtr *operator&() = delete;   // no hipMalloc((void **)&d, ...) into it
+    hipError_t alloc(size_t count)   // at least one element, so that an empty array is not null
+    {
+        (void)reset();
+        return hipMalloc((void **)&p_, sizeof(T) * (count ? count : 1));
+    }
+    hipError_t reset()
+    {
+        T *q = p_;
+        p_ = nullptr;
+        return q ? hipFree(q) : hipSuccess;
+    }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
 };
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of (kernel, device): a function-local static of this type
@@ -61,23 +91,23 @@ constexpr int kShortSeg = SPMV_T_SHORT;            // row segments up to this lo
 struct ChunkPlan {
     int block = 0;             // 0 = not planned; 256 | 512 | 1024 threads per workgroup
     int nchunks = 0;           // ceil(nnz / (block*16))
-    int32_t *d_lb = nullptr;   // [nchunks+1] first row whose row_ptr >= c*chunk
-    float *d_carry = nullptr;  // [nchunks]   partial sum of the row continued from chunk c-1
-    int32_t *d_win = nullptr;  // [2*nchunks+2] TILED: first column, window length (0 = not staged); stats
+    DevPtr<int32_t> d_lb;      // [nchunks+1] first row whose row_ptr >= c*chunk
+    DevPtr<float> d_carry;     // [nchunks]   partial sum of the row continued from chunk c-1
+    DevPtr<int32_t> d_win;     // [2*nchunks+2] TILED: first column, window length (0 = not staged); stats
     // 16-bit columns (TILED): chunks whose span is fully staged also carry col - w0 as uint16
-    uint16_t *d_col16 = nullptr;   // [nchunks * chunk], lane layout of k_tiled16
-    int32_t *d_list16 = nullptr;   // [n16] chunks run by k_tiled16
-    int32_t *d_list32 = nullptr;   // [nchunks - n16 - nsorted] the others, run by the 32-bit body
+    DevPtr<uint16_t> d_col16;      // [nchunks * chunk], lane layout of k_tiled16
+    DevPtr<int32_t> d_list16;      // [n16] chunks run by k_tiled16
+    DevPtr<int32_t> d_list32;      // [nchunks - n16 - nsorted] the others, run by the 32-bit body
     int n16 = 0;
     // sorted chunks (TILED): spans of several LDS regions gather x in column order instead of staging it
-    uint32_t *d_perm = nullptr;        // [nsorted * chunk] position << 18 | column - w0 of the sorted chunks (list order), read INSTEAD of col_idx
-    int32_t *d_list_sorted = nullptr;  // [nsorted]
+    DevPtr<uint32_t> d_perm;           // [nsorted * chunk] position << 18 | column - w0 of the sorted chunks (list order), read INSTEAD of col_idx
+    DevPtr<int32_t> d_list_sorted;     // [nsorted]
     int nsorted = 0;                   // chunks run by the sorted body
     int nsorted_marked = 0;            // chunks the window pass marked (a few may still switch to a block list)
     int sorted_from = 0;               // -1: sorted where the modelled cost is lower; 0: never; n: from n passes on
     int long_piece_chunks = 0;         // chunks of three passes or more that hold a piece of a long row (> 512 nonzeros)
     double model_cost = 0.0;           // modelled time per nonzero of this plan (PlanCost units; compares block sizes)
-    int32_t *d_blk = nullptr;      // [64 * nchunks] ids of the staged 1024-column blocks of the chunks that use a list
+    DevPtr<int32_t> d_blk;         // [64 * nchunks] ids of the staged 1024-column blocks of the chunks that use a list
     int nblk_chunks = 0;           // how many chunks do
     int maxpass = 0;
     bool col16_wanted = false;     // the plan asked for the 16-bit copy (it is kept only where enough chunks qualify)
@@ -105,20 +135,20 @@ struct PanelPlan {
     int nblocks = 0;               // row blocks (<= 8192 rows, equal nonzero counts) = wavefronts of work
     int waves_per_launch = 0;      // what is resident at once: one launch = one sweep in step
     int step_vecs = 8;             // 16-byte vectors per lane and step of the sweep (8 | 4: thin tiles, kernels_panel.hip kVecMax)
-    uint32_t *d_packed = nullptr;  // [nnz + slack] row_in_block << 18 | join << 17 | column_in_panel (kernels_panel.hip)
-    float *d_pvals = nullptr;      // [nnz + slack] values in the same order (a COPY: re-plan after changing vals)
-    int32_t *d_tile_ptr = nullptr; // [nblocks * (npanels + 1)]
-    int32_t *d_brow = nullptr;     // [nblocks + 1] first row of every block
+    DevPtr<uint32_t> d_packed;     // [nnz + slack] row_in_block << 18 | join << 17 | column_in_panel (kernels_panel.hip)
+    DevPtr<float> d_pvals;         // [nnz + slack] values in the same order (a COPY: re-plan after changing vals)
+    DevPtr<int32_t> d_tile_ptr;    // [nblocks * (npanels + 1)]
+    DevPtr<int32_t> d_brow;        // [nblocks + 1] first row of every block
     ValuesStamp stamp;             // which state of vals d_pvals is a copy of
     // sorted blocks (mode 3, kernels_colsort.hip): blocks of <= 4096 rows streamed in column order, d_packed / d_pvals in
     // units of 256 slots (four groups of 64 nonzeros with distinct rows)
     bool sorted_mode = false;
-    int32_t *d_ubeg = nullptr;     // [nblocks + 1] first unit of every block
-    int32_t *d_usimple = nullptr;  // [nblocks] leading units of the block that hold groups (64 distinct rows per instruction)
-    int32_t *d_uend = nullptr;     // [nblocks] one past the last unit the block uses (groups, then its row-sorted tail)
-    int32_t *d_ubase = nullptr;    // [units] first column of every unit (packed holds offsets from it)
-    int32_t *d_tbeg = nullptr;     // [nblocks] first tail unit of the block in d_trow
-    uint16_t *d_trow = nullptr;    // [tail_units * 256] rows of the tail units (their packed words are whole columns)
+    DevPtr<int32_t> d_ubeg;        // [nblocks + 1] first unit of every block
+    DevPtr<int32_t> d_usimple;     // [nblocks] leading units of the block that hold groups (64 distinct rows per instruction)
+    DevPtr<int32_t> d_uend;        // [nblocks] one past the last unit the block uses (groups, then its row-sorted tail)
+    DevPtr<int32_t> d_ubase;       // [units] first column of every unit (packed holds offsets from it)
+    DevPtr<int32_t> d_tbeg;        // [nblocks] first tail unit of the block in d_trow
+    DevPtr<uint16_t> d_trow;       // [tail_units * 256] rows of the tail units (their packed words are whole columns)
     int64_t tail_units = 0;
     int sb_rows = 0, sb_waves = 0;   // rows per block (4096 | 8192), wavefronts per workgroup (8 | 4)
     int64_t wide_blocks = 0;       // blocks whose short rows span more than 32768 lines of x (4 MiB)
@@ -130,28 +160,28 @@ struct PanelPlan {
     // products); tile (bin b, panel p) is contiguous in both, rows ascending inside it
     bool binned_mode = false;
     int bin_rows = 0;              // most rows of a bin (4096 | 8192): a wavefront's private sums in LDS
-    uint16_t *d_c16 = nullptr;     // [padded] column - panel * 2^pw_bits, panel-major (every panel padded to a multiple of 8)
-    uint16_t *d_r16 = nullptr;     // [nnz] row - brow[bin], bin-major (d_tile_ptr positions)
-    int32_t *d_pm = nullptr;       // [nblocks * npanels] panel-major position of tile (b, p)
-    int32_t *d_pbase = nullptr;    // [npanels + 1] panel-major position of every panel's first entry
-    float *d_prod = nullptr;       // [padded] scratch of a run: the products, panel-major
+    DevPtr<uint16_t> d_c16;        // [padded] column - panel * 2^pw_bits, panel-major (every panel padded to a multiple of 8)
+    DevPtr<uint16_t> d_r16;        // [nnz] row - brow[bin], bin-major (d_tile_ptr positions)
+    DevPtr<int32_t> d_pm;          // [nblocks * npanels] panel-major position of tile (b, p)
+    DevPtr<int32_t> d_pbase;       // [npanels + 1] panel-major position of every panel's first entry
+    DevPtr<float> d_prod;          // [padded] scratch of a run: the products, panel-major
     int64_t padded = 0;            // entries of the panel-major arrays
     int splits = 1;                // workgroups per panel of the product launch
     bool wide_pieces = false;      // the sum launch takes four products per lane (fat tiles) instead of two
     int flagged_tiles = 0;         // tiles that go through the fold (bins whose long rows need more spare sums than there are)
     int long_rows = 0;             // rows with spare sums (more products in some tile than a lane takes)
-    int32_t *d_lptr = nullptr;     // [nblocks + 1] first long row of every bin in d_lrow / d_lcnt
-    uint32_t *d_lrow = nullptr;    // [long_rows] row in bin << 16 | first spare slot
-    int32_t *d_lcnt = nullptr;     // [long_rows] spare slots of the row
+    DevPtr<int32_t> d_lptr;        // [nblocks + 1] first long row of every bin in d_lrow / d_lcnt
+    DevPtr<uint32_t> d_lrow;       // [long_rows] row in bin << 16 | first spare slot
+    DevPtr<int32_t> d_lcnt;        // [long_rows] spare slots of the row
     // ... its scattered flavour: the product launch stores in bin order (d_offset, d_first_run; bit 15 of d_c16), the sum launch streams d_prod + d_r16 (here:
     // accumulator numbers) bin by bin; d_lrow = [nblocks * 1024] row << 17 | first spare accumulator << 7 | how many
     bool scatter_mode = false;
-    int32_t *d_offset = nullptr;   // [runs] bin-major minus panel-major position of a run (a nonempty tile, or a panel's pad slots)
-    int32_t *d_first_run = nullptr;   // [padded / 512] run of every 512-entry block's first entry (minus one where it starts a run)
+    DevPtr<int32_t> d_offset;      // [runs] bin-major minus panel-major position of a run (a nonempty tile, or a panel's pad slots)
+    DevPtr<int32_t> d_first_run;      // [padded / 512] run of every 512-entry block's first entry (minus one where it starts a run)
     int64_t runs = 0;
-    int32_t *d_bbase = nullptr;    // [nblocks + 1] first entry of every bin in d_prod / d_r16 (multiples of 256)
-    int32_t *d_bcnt = nullptr;     // [nblocks] entries of the bin
-    int32_t *d_nlong = nullptr;    // [nblocks] rows with spare accumulators (-1: the bin adds with LDS atomics)
+    DevPtr<int32_t> d_bbase;       // [nblocks + 1] first entry of every bin in d_prod / d_r16 (multiples of 256)
+    DevPtr<int32_t> d_bcnt;        // [nblocks] entries of the bin
+    DevPtr<int32_t> d_nlong;       // [nblocks] rows with spare accumulators (-1: the bin adds with LDS atomics)
     int64_t bm_entries = 0;        // entries of the bin-major arrays
     int64_t bm_alloc = 0;          // ... as allocated: bm_entries + the slack of the sum launch's read-ahead (kernels_binned.hip kBsSlack)
 };
@@ -160,12 +190,12 @@ struct PanelPlan {
 struct XskipPlan {
     bool ready = false;
     int nblocks = 0, nseg = 0, slabs = 0;
-    int32_t *d_block_seg = nullptr;   // [nblocks+1] first segment of every output block
-    int32_t *d_seg_input = nullptr;   // [nseg+1] input (column) of a segment
-    int32_t *d_seg_ptr = nullptr;     // [nseg+1] first entry of a segment
-    uint16_t *d_erow = nullptr;       // [nnz] output - 1024 * block
-    float *d_evals = nullptr;         // [nnz] values in segment order (a COPY: re-plan after changing vals)
-    float *d_part = nullptr;          // [nblocks * slabs * 1024] slab partials (slabs > 1)
+    DevPtr<int32_t> d_block_seg;      // [nblocks+1] first segment of every output block
+    DevPtr<int32_t> d_seg_input;      // [nseg+1] input (column) of a segment
+    DevPtr<int32_t> d_seg_ptr;        // [nseg+1] first entry of a segment
+    DevPtr<uint16_t> d_erow;          // [nnz] output - 1024 * block
+    DevPtr<float> d_evals;            // [nnz] values in segment order (a COPY: re-plan after changing vals)
+    DevPtr<float> d_part;             // [nblocks * slabs * 1024] slab partials (slabs > 1)
     ValuesStamp stamp;                // which state of vals d_evals is a copy of
 };
 
@@ -173,15 +203,15 @@ struct XskipPlan {
 struct WavePlan {
     bool ready = false;
     int n_long = 0, pieces = 0;
-    int32_t *d_long_row = nullptr;    // [n_long] the rows, ascending
-    int32_t *d_long_first = nullptr;  // [n_long + 1] first piece of every row
-    int32_t *d_piece_k0 = nullptr;    // [pieces] first nonzero of a piece
-    int32_t *d_piece_len = nullptr;   // [pieces] its length (<= 1024)
-    float *d_partial = nullptr;       // [pieces] scratch of a run: the pieces' sums
+    DevPtr<int32_t> d_long_row;       // [n_long] the rows, ascending
+    DevPtr<int32_t> d_long_first;     // [n_long + 1] first piece of every row
+    DevPtr<int32_t> d_piece_k0;       // [pieces] first nonzero of a piece
+    DevPtr<int32_t> d_piece_len;      // [pieces] its length (<= 1024)
+    DevPtr<float> d_partial;          // [pieces] scratch of a run: the pieces' sums
     int block_rows = 512;             // rows of a bundle workgroup (512 | 1024)
-    int32_t *d_blk_lo = nullptr;      // [blocks] first entry of the x window of every block of block_rows rows, -1: none
-    uint16_t *d_col16 = nullptr;      // [nnz] 16-bit column offsets: from blk_lo for windowed blocks' short rows, from piece_base for pieces (null: not built)
-    int32_t *d_piece_base = nullptr;  // [pieces] smallest column of a piece whose offsets are in d_col16, -1: 32-bit columns
+    DevPtr<int32_t> d_blk_lo;         // [blocks] first entry of the x window of every block of block_rows rows, -1: none
+    DevPtr<uint16_t> d_col16;         // [nnz] 16-bit column offsets: from blk_lo for windowed blocks' short rows, from piece_base for pieces (null: not built)
+    DevPtr<int32_t> d_piece_base;     // [pieces] smallest column of a piece whose offsets are in d_col16, -1: 32-bit columns
     bool windows = false;             // the bundle kernel stages windows (at least half of the blocks have one)
     int64_t blocks = 0, win_blocks = 0;   // blocks of block_rows rows, and how many have a window
 };
@@ -191,18 +221,16 @@ struct SpmmPlan {
     bool ready = false;
     int n_long = 0, pieces = 0;
     int row_cap = 0, piece_len = 0;   // rows of more than row_cap nonzeros go in pieces of piece_len
-    int32_t *d_order = nullptr;       // [rows] the rows in the order the row kernel takes them (by length per 4096 rows)
-    int32_t *d_long_row = nullptr;    // [n_long] the rows, ascending
-    int32_t *d_long_first = nullptr;  // [n_long + 1] first piece of every row
-    int32_t *d_piece_k0 = nullptr;    // [pieces] first nonzero of a piece
-    int32_t *d_piece_len = nullptr;   // [pieces] its length
-    float *d_partial = nullptr;       // [pieces * 64] scratch of a run: a piece's sums of up to 64 columns
+    DevPtr<int32_t> d_order;          // [rows] the rows in the order the row kernel takes them (by length per 4096 rows)
+    DevPtr<int32_t> d_long_row;       // [n_long] the rows, ascending
+    DevPtr<int32_t> d_long_first;     // [n_long + 1] first piece of every row
+    DevPtr<int32_t> d_piece_k0;       // [pieces] first nonzero of a piece
+    DevPtr<int32_t> d_piece_len;      // [pieces] its length
+    DevPtr<float> d_partial;          // [pieces * 64] scratch of a run: a piece's sums of up to 64 columns
 };
 
 }  // namespace spmv
 
-struct spmv_tcsr;    // kernels_tcsr.hip
-struct spmv_bitmap;  // kernels_bitmap.hip
 
 // The opaque handle of include/spmv_hip.h.
 struct spmv_csr {
@@ -210,7 +238,8 @@ struct spmv_csr {
     const int32_t *d_row_ptr = nullptr;
     const int32_t *d_col_idx = nullptr;
     const float *d_vals = nullptr;
-    bool owns_arrays = false;
+    spmv::DevPtr<int32_t> own_row_ptr, own_col_idx;   // the handle's own copies behind the views (empty: the caller's arrays)
+    spmv::DevPtr<float> own_vals;
     int device = 0;
 
     // plan state
@@ -227,22 +256,42 @@ struct spmv_csr {
     uint64_t values_gen = 0;       // bumped by spmv_csr_values_changed: plans that copied vals before that are stale
 };
 
+// The tiled bitmap-CSR handle (kernels_tcsr.hip).
+struct spmv_tcsr {
+    int M = 0, N = 0;
+    int64_t nnz = 0, nblocks = 0;
+    spmv::DevPtr<int32_t> d_blk_idx;   // [nblocks+1]
+    spmv::DevPtr<uint32_t> d_bitmaps;  // [M*N/32]
+    spmv::DevPtr<float> d_vals;        // [nnz]
+    int nseg = 0;                      // input-dimension segments per strip pair
+    spmv::DevPtr<float> d_partial;     // [nseg][N] partial sums, combined in segment order
+};
+
+// The WSP / AWSP / AWSPRef handle (kernels_bitmap.hip).
+struct spmv_bitmap {
+    int format = 0;                 // enum spmv_bitmap_format
+    int M = 0, N = 0;
+    int device = 0;
+    int64_t n_bitmaps = 0, n_vals = 0;
+    int32_t stats[4] = {0, 0, 0, 0};   // WSP {nz_max_m, nz_max_n}, AWSP {nz_bk_max_}, AWSPRef warp_nz_offset_[4]
+    spmv::DevPtr<uint32_t> d_bitmaps;
+    spmv::DevPtr<float> d_vals;
+    spmv::DevPtr<float> d_partial;  // AWSP/AWSPRef: [4][N] quarter partials
+};
+
 namespace spmv {
 
 // ---- kernel launchers (each enqueues on `s`, returns a status) -------------
 int launch_scalar(spmv_csr &h, const float *x, float *y, hipStream_t s);
 int launch_wave(spmv_csr &h, const float *x, float *y, bool pipelined, hipStream_t s);
 int plan_wave(spmv_csr &h, hipStream_t s);
-void destroy_wave(WavePlan &p);
 int launch_vector(const spmv_csr &h, const float *x, float *y, hipStream_t s);
 int launch_adaptive(const spmv_csr &h, const float *x, float *y, bool tiled, hipStream_t s);
 int launch_panel(const spmv_csr &h, const float *x, float *y, hipStream_t s);
 
 int plan_xskip(spmv_csr &h, hipStream_t s);
 int launch_xskip(const spmv_csr &h, const float *x, float *y, hipStream_t s);
-void destroy_xskip(XskipPlan &p);
 int plan_panel(spmv_csr &h, hipStream_t s);
-void destroy_panel(PanelPlan &p);
 int panel_launches(const PanelPlan &p);
 int plan_vector(spmv_csr &h, hipStream_t s);
 int plan_adaptive(spmv_csr &h, bool tiled, hipStream_t s);
@@ -262,20 +311,15 @@ double colsort_model_cost(const PanelPlan &p, int64_t nnz);
 double colsort_cost(int rows_per_block, double lines_per_nnz, double tail_frac);
 int colsort_probe(const spmv_csr &h, hipStream_t s, double *long_frac, double *wide_frac, double *lines_per_nnz);
 int launch_colsort(const spmv_csr &h, const PanelPlan &p, const float *x, float *y, hipStream_t s);
-void destroy_colsort(PanelPlan &p);
 // kernels_binned.hip: SPMV_PANEL mode 4
 int panel_tile_ptr(const spmv_csr &h, const int32_t *d_brow, int nblocks, int pw_bits, int np, int32_t *d_tile_ptr, hipStream_t s);
 int plan_binned(spmv_csr &h, PanelPlan &p, int want_rows, bool scatter, hipStream_t s);
 int launch_binned(const spmv_csr &h, const PanelPlan &p, const float *x, float *y, hipStream_t s);
-void destroy_binned(PanelPlan &p);
 double binned_tile_nonzeros(const spmv_csr &h, int bin_rows);
-void destroy_plans(spmv_csr &h);
 // kernels_spmm.hip: spmv_csr_spmm
 int plan_spmm(spmv_csr &h, hipStream_t s);
 int launch_spmm(const spmv_csr &h, int k, const float *X, int64_t ldx, float *Y, int64_t ldy, hipStream_t s);
 int64_t spmm_plan_bytes(const spmv_csr &h);
-void destroy_spmm(SpmmPlan &p);
-void drop_tiled_plan(spmv_csr &h);   // SPMV_AUTO resolved to another variant: the TILED plan it looked at is released
 
 int dense_to_csr(int M, int N, const float *d_A, hipStream_t s, spmv_csr_t **out);
 int dense_gemv(int M, int N, const float *d_A, const float *d_x, float *d_y, int mode, hipStream_t s);
@@ -304,7 +348,6 @@ int tcsr_from_dense(int M, int N, const float *d_A, hipStream_t s, spmv_tcsr_t *
 int tcsr_run(const spmv_tcsr &h, const float *d_x, float *d_y, hipStream_t s);
 int tcsr_sizes(const spmv_tcsr &h, int64_t *n_blk_idx, int64_t *n_bitmaps, int64_t *n_vals);
 int tcsr_download(const spmv_tcsr &h, int32_t *blk_idx, uint32_t *bitmaps, float *vals);
-void tcsr_free(spmv_tcsr *h);
 void tcsr_dims(const spmv_tcsr &h, int *M, int *N);
 
 // kernels_bitmap.hip: the reference's WSP / AWSP / AWSPRef formats
@@ -313,7 +356,6 @@ int bitmap_run(const spmv_bitmap &h, const float *d_x, float *d_y, hipStream_t s
 void bitmap_info(const spmv_bitmap &h, int *format, int *M, int *N, int64_t *n_bitmaps, int64_t *n_vals, int32_t stats[4]);
 int bitmap_download(const spmv_bitmap &h, uint32_t *bitmaps, float *vals);
 int bitmap_device(const spmv_bitmap &h);
-void bitmap_free(spmv_bitmap *h);
 
 int synth_fill(uint64_t seed, int64_t row0, int64_t n_local, int64_t rows, int64_t cols, int64_t band,
                const int32_t *d_row_ptr, int32_t *d_col_idx, float *d_vals, hipStream_t s);

@@ -274,3 +274,54 @@ def test_clustered_columns_take_the_block_list_plan(pkg, oracle, gpu):
         y64, mag = oracle.spmv_f64(rp, ci, va, x)
         assert_close_to_oracle(y, y64, mag, d)
     prob.A.close()
+
+
+def test_replanning_and_destroying_return_device_memory(pkg, oracle, gpu):
+    """Plans own their device arrays: four rounds of create, plan every variant (PANEL modes 1-5 with a refresh after
+    values_changed, SpMM), run and destroy end with as much free device memory as the first round did.  A leaked array
+    of any plan widens the gap by its size every round.  Long rows make the wave-pipe and SpMM pieces and the sorted
+    blocks' tails non-empty; 32 output blocks x 32768 columns is within XSKIP's table limit."""
+    import torch
+    capi = pkg.capi
+    rows = cols = 32768
+    rng = np.random.Generator(np.random.PCG64(32768))
+    L = rng.integers(8, 32, size=rows)
+    L[::2048] = 6000
+    rp = np.concatenate([[0], np.cumsum(L)]).astype(np.int32)
+    ci = np.concatenate([np.sort(rng.choice(cols, size=int(l), replace=False)) for l in L]).astype(np.int32)
+    va = rng.uniform(-1, 1, size=len(ci)).astype(np.float32)
+    x = rng.uniform(-1, 1, size=cols).astype(np.float32)
+    X = rng.uniform(-1, 1, size=(cols, 8)).astype(np.float32)
+    y64, mag = oracle.spmv_f64(rp, ci, va, x)
+    Y64, Ymag = oracle.spmv_f64(rp, ci, va, np.ascontiguousarray(X[:, 0]))
+    d_x, d_X = torch.from_numpy(x).to(gpu), torch.from_numpy(X).to(gpu)
+    d_y, d_Y = torch.empty(rows, dtype=torch.float32, device=gpu), torch.empty(rows, 8, dtype=torch.float32, device=gpu)
+
+    def run(A, v, what):
+        d_y.fill_(float("nan"))
+        A.run(v, d_x, d_y)
+        torch.cuda.synchronize()
+        assert_close_to_oracle(d_y.cpu().numpy(), y64, mag, what)
+
+    free = []
+    for _ in range(4):
+        A = capi.CsrMatrix.from_host(rows, cols, rp, ci, va)
+        for v in (capi.SCALAR, capi.WAVE_PIPE, capi.VECTOR, capi.ADAPTIVE, capi.TILED, capi.XSKIP, capi.AUTO):
+            A.plan(v)
+            run(A, v, A.plan_describe(v))
+        A.spmm_plan()
+        d_Y.fill_(float("nan"))
+        A.spmm(d_X, d_Y)
+        torch.cuda.synchronize()
+        assert_close_to_oracle(d_Y[:, 0].cpu().numpy(), Y64, Ymag, "spmm")
+        for mode in (1, 2, 3, 4, 5):
+            A.plan_set(capi.PANEL, [capi.PANEL, 0, 0, 0, 0, 0, mode, 0])
+            run(A, capi.PANEL, A.plan_describe(capi.PANEL))
+            if mode == 2:
+                A.values_changed()
+                A.plan(capi.PANEL)          # the stale copy is rebuilt as planned
+                run(A, capi.PANEL, "refreshed " + A.plan_describe(capi.PANEL))
+        A.close()
+        torch.cuda.synchronize()
+        free.append(torch.cuda.mem_get_info()[0])
+    assert abs(free[-1] - free[0]) <= 2 << 20, free
