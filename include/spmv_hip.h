@@ -183,7 +183,29 @@ SPMV_API int spmv_csr_destroy(spmv_csr_t *h);
  * Asynchronous; d_x has cols floats, d_y has rows floats and is fully
  * overwritten.  No allocation, no synchronisation: graph-capturable -- with
  * one exception: SPMV_SCALAR / SPMV_WAVE_PIPE on a handle that spmv_csr_plan
- * has not seen make their plan on the first run (an allocation and a wait). */
+ * has not seen make their plan on the first run (an allocation and a wait).
+ * Alignment: d_x must be 16-byte aligned (SPMV_ERR_INVALID otherwise, nothing launched: the kernels stage x with
+ * 16-byte loads); d_y needs only its natural 4 bytes -- a row block of a larger y (y_full + first_row) is fine, and
+ * nothing outside y[0, rows) is written.
+ *
+ * Limits of the layouts.  A handle admits rows, cols, nnz < 2^31, and SPMV_SCALAR, SPMV_WAVE, SPMV_WAVE_PIPE,
+ * SPMV_VECTOR, SPMV_ADAPTIVE and SPMV_TILED run every such handle (nnz up to 2^31 - 1, y and row_ptr beyond 4 GiB, x
+ * beyond 4 GiB).  The layouts that re-order the nonzeros hold less; a plan outside a limit fails with SPMV_ERR_INVALID
+ * and a message that names it, launches nothing and leaves the handle usable, and SPMV_AUTO passes on to the next
+ * layout that can hold the matrix (in the end SPMV_TILED):
+ *   SPMV_PANEL, panel sweep (params[6] = 1)   nnz <= INT_MAX - 8192 (the stream reads four steps of 2048 ahead);
+ *                                             cols <= 2^29 (4096 panels of 2^17 columns)
+ *   ... x panels in LDS (params[6] = 2)       the same nnz; cols <= 2^26 (4096 panels of 2^14 columns)
+ *   ... sorted blocks (params[6] = 3)         nnz <= INT_MAX / 17 * 16 - 4096 (2 021 156 976: a unit of 16 slots may
+ *                                             hold one pad slot, and the padded count stays a 32-bit number)
+ *   ... binned, both flavours (4, 5)          cols <= 2^27 (4096 panels of 2^15 columns); nnz <= 2^30 - 8 * panels - 512
+ *                                             (the products lie behind one buffer descriptor: 4 GiB); bins x (panels + 1)
+ *                                             <= 2^30 table entries; params[6] = 5 also: the entries padded per bin
+ *                                             stay below 2^30, bins x panel groups <= 2^30 fill items
+ *   SPMV_XSKIP                                ceil(rows / 1024) x cols <= 2^27 table entries; rows sorted, duplicate-free
+ *   spmv_csr_spmm                             rows x lanes per row < 2^32 (one launch): any handle up to k = 8,
+ *                                             rows < 2^30 up to k = 16, < 2^29 up to k = 32, < 2^28 up to k = 64
+ * (tests/test_gpu_limits.py runs every path on either side of these.) */
 SPMV_API int spmv_csr_plan(spmv_csr_t *h, int variant, void *stream);
 SPMV_API int spmv_csr_run(spmv_csr_t *h, int variant, const float *d_x, float *d_y, void *stream);
 
@@ -249,7 +271,7 @@ SPMV_API int spmv_csr_run_host(spmv_csr_t *h, int variant, const float *x_host, 
  * X[j*ldx + c], j < cols), Y is rows rows of ldy floats.  Column c < k of Y is A times column c of X under the CSR
  * semantics above: every term counts and a repeated column adds each of its terms, rows need not be sorted, IEEE rules
  * hold and subnormals are kept, an empty row gives 0, and an X row no nonzero refers to is never read into a sum.
- * Limits: 1 <= k <= 64, ldx >= k, ldy >= k; d_X and d_Y 16-byte aligned (d_X may be NULL when cols == 0, d_Y when
+ * Limits: 1 <= k <= 64, ldx >= k, ldy >= k, rows x lanes per row < 2^32 ("Limits of the layouts" above); d_X and d_Y 16-byte aligned (d_X may be NULL when cols == 0, d_Y when
  * rows == 0).  Any ld >= k works; ldx % 4 == 0 and ldy % 4 == 0 together are the fast path (16-byte loads and stores;
  * a run then reads the whole 16-byte block that holds X[j*ldx + k-1]).  Anything else, a null handle or another current
  * device than the handle's is SPMV_ERR_INVALID, and nothing is launched.  Y[i*ldy + c] for c >= k is never written, and

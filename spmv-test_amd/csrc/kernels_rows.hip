@@ -36,12 +36,15 @@ __device__ __forceinline__ float scalar_row_by_wave(int lane, int32_t b, int32_t
 {
 #pragma clang fp contract(off)
     float acc = 0.0f;       // wave-uniform
-    int32_t k = b + lane;
-    float p = k < e ? x[col_idx[k]] * vals[k] : 0.0f;
-    for (int32_t k0 = b; k0 < e; k0 += kWave) {
-        const int32_t kn = k0 + kWave + lane;
-        const float pn = kn < e ? x[col_idx[kn]] * vals[kn] : 0.0f;   // next trip, in flight during the chain
-        const int n = e - k0 < kWave ? e - k0 : kWave;
+    // (unsigned: with e up to 2^31 - 1, k0 + kWave and the look-ahead kn pass INT_MAX on a row that ends there; as signed
+    // numbers they wrapped, and the look-ahead then read vals[] two billion entries before the array)
+    const uint32_t ue = (uint32_t)e;
+    const uint32_t k = (uint32_t)b + lane;
+    float p = k < ue ? x[col_idx[k]] * vals[k] : 0.0f;
+    for (uint32_t k0 = (uint32_t)b; k0 < ue; k0 += kWave) {
+        const uint32_t kn = k0 + kWave + lane;
+        const float pn = kn < ue ? x[col_idx[kn]] * vals[kn] : 0.0f;   // next trip, in flight during the chain
+        const int n = ue - k0 < (uint32_t)kWave ? (int)(ue - k0) : kWave;
         if (n == kWave) {
 #pragma unroll
             for (int l = 0; l < kWave; ++l)
@@ -86,9 +89,9 @@ __global__ __launch_bounds__(kBlock) void k_scalar(int64_t rows, const int32_t *
     const int32_t wb = row_ptr[r0], we = row_ptr[rend];  // the workgroup's nonzero range
     const int32_t b = r < rows ? row_ptr[r] : 0, e = r < rows ? row_ptr[r + 1] : 0;
     if (we - wb <= kScalarCap) {
-        for (int32_t k = wb + (int32_t)threadIdx.x; k < we; k += kBlock) {
+        for (uint32_t k = (uint32_t)wb + threadIdx.x; k < (uint32_t)we; k += kBlock) {   // (unsigned: k + kBlock may pass INT_MAX)
             const float p = XG(col_idx[k], k) * vals[k];
-            prod[k - wb] = p;
+            prod[k - (uint32_t)wb] = p;
         }
         __syncthreads();
         if (r < rows) {
@@ -129,13 +132,13 @@ __global__ __launch_bounds__(kBlock) void k_scalar(int64_t rows, const int32_t *
 // lane-consecutive products per trip (coalesced, each rounded once, the next trip's loads already in flight), then
 // added IN ORDER -- lane 0's first -- through a readlane chain: the same sequence of roundings as the host loop,
 // so y stays bit-identical to SgemvCPU.
-__global__ __launch_bounds__(kBlock) void k_scalar_long(int64_t rows, const int32_t *__restrict__ row_ptr,
+__global__ __launch_bounds__(kBlock) void k_scalar_long(int64_t row0, int64_t rows, const int32_t *__restrict__ row_ptr,
                                                         const int32_t *__restrict__ col_idx,
                                                         const float *__restrict__ vals,
                                                         const float *__restrict__ x, float *__restrict__ y)
 {
     const int lane = threadIdx.x & (kWave - 1);
-    const int64_t r = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
+    const int64_t r = row0 + (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
     if (r >= rows) return;  // wave-uniform
     const float acc = scalar_row_by_wave(lane, row_ptr[r], row_ptr[r + 1], col_idx, vals, x);
     if (lane == 0) y[r] = acc;
@@ -152,11 +155,12 @@ __device__ __forceinline__ float wave_reduce_sum(float v)
 // one row by the whole wave: lanes stride the row (four 64-wide slices in flight per trip when PIPE), then the
 // __shfl_down tree; every lane returns the sum
 template <bool PIPE>
-__device__ __forceinline__ float wave_row(int lane, int32_t b, int32_t e, const int32_t *__restrict__ col_idx,
+__device__ __forceinline__ float wave_row(int lane, int32_t b, int32_t e_, const int32_t *__restrict__ col_idx,
                                           const float *__restrict__ vals, const float *__restrict__ x)
 {
     float acc = 0.0f;
-    int32_t k = b + lane;
+    const uint32_t e = (uint32_t)e_;   // (unsigned: k + 3 * kWave and k += kWave may pass INT_MAX on a row that ends near it)
+    uint32_t k = (uint32_t)b + lane;
     if (PIPE) {
         // 8 streamed loads then 4 gathers are issued before the first use
         float a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
@@ -180,13 +184,13 @@ __device__ __forceinline__ float wave_row(int lane, int32_t b, int32_t e, const 
 // is what SPMV_WAVE_PIPE runs on matrices of long rows (mean > 32 nonzeros, the reference's own 4096 x 4096 / 50 %
 // regime): the same mapping with four slices in flight per trip.
 template <bool PIPE>
-__global__ __launch_bounds__(kBlock) void k_wave(int64_t rows, const int32_t *__restrict__ row_ptr,
+__global__ __launch_bounds__(kBlock) void k_wave(int64_t row0, int64_t rows, const int32_t *__restrict__ row_ptr,
                                                  const int32_t *__restrict__ col_idx,
                                                  const float *__restrict__ vals,
                                                  const float *__restrict__ x, float *__restrict__ y)
 {
     const int lane = threadIdx.x & (kWave - 1);
-    const int64_t r = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
+    const int64_t r = row0 + (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
     if (r >= rows) return;  // wave-uniform
     const float acc = wave_row<PIPE>(lane, row_ptr[r], row_ptr[r + 1], col_idx, vals, x);
     if (lane == 0) y[r] = acc;
@@ -687,18 +691,18 @@ __global__ __launch_bounds__(kWavePlanBlock) void k_wave_plan_fill(int64_t rows,
 
 // ---------------------------------------------------------------------------
 template <int G>
-__global__ __launch_bounds__(kBlock) void k_vector(int64_t rows, const int32_t *__restrict__ row_ptr,
+__global__ __launch_bounds__(kBlock) void k_vector(int64_t row0, int64_t rows, const int32_t *__restrict__ row_ptr,
                                                    const int32_t *__restrict__ col_idx,
                                                    const float *__restrict__ vals,
                                                    const float *__restrict__ x, float *__restrict__ y)
 {
     constexpr int kRowsPerBlock = kBlock / G;
     const int sub = threadIdx.x % G;
-    const int64_t r = (int64_t)blockIdx.x * kRowsPerBlock + threadIdx.x / G;
+    const int64_t r = row0 + (int64_t)blockIdx.x * kRowsPerBlock + threadIdx.x / G;
     float acc = 0.0f;
     if (r < rows) {
         const int32_t b = row_ptr[r], e = row_ptr[r + 1];
-        for (int32_t k = b + sub; k < e; k += G) acc = fmaf(vals[k], x[col_idx[k]], acc);
+        for (uint32_t k = (uint32_t)b + sub; k < (uint32_t)e; k += G) acc = fmaf(vals[k], x[col_idx[k]], acc);   // (unsigned: k + G may pass INT_MAX)
     }
     // all 64 lanes take part in the shuffles (rows past the end carry zeros)
 #pragma unroll
@@ -714,6 +718,18 @@ static bool grid_ok(int64_t blocks)
         return false;
     }
     return true;
+}
+
+// A launch carries fewer than 2^32 work-items: the runtime hands grid x block on as one 32-bit number, and a larger
+// product wraps without an error -- the rows beyond it are never written (2^26 rows at a wavefront per row, 2^27 at 32
+// lanes per row).  The kernels that give a row more than one lane take their first row as an argument and are launched in
+// slices of 2^23 workgroups (2^31 work-items); every handle below those sizes is one launch, as before.
+constexpr int64_t kSliceBlocks = 1LL << 23;
+template <typename Launch>
+static void launch_row_slices(int64_t blocks, int rows_per_block, Launch &&launch)
+{
+    for (int64_t b0 = 0; b0 < blocks; b0 += kSliceBlocks)
+        launch(dim3((unsigned)(blocks - b0 < kSliceBlocks ? blocks - b0 : kSliceBlocks)), b0 * rows_per_block);
 }
 
 template <int MODE, bool ORDERED, int BLOCK>
@@ -835,8 +851,9 @@ int launch_scalar(spmv_csr &h, const float *x, float *y, hipStream_t s)
     if (h.nnz > 64 * h.rows) {   // long rows: a wavefront per row, still in the oracle's order
         const int64_t wblocks = (h.rows + (kBlock / kWave) - 1) / (kBlock / kWave);
         if (!grid_ok(wblocks)) return SPMV_ERR_INVALID;
-        hipLaunchKernelGGL(k_scalar_long, dim3((unsigned)wblocks), dim3(kBlock), 0, s, h.rows, h.d_row_ptr,
-                           h.d_col_idx, h.d_vals, x, y);
+        launch_row_slices(wblocks, kBlock / kWave, [&](dim3 grid, int64_t row0) {
+            hipLaunchKernelGGL(k_scalar_long, grid, dim3(kBlock), 0, s, row0, h.rows, h.d_row_ptr, h.d_col_idx, h.d_vals, x, y);
+        });
         return check_launch("k_scalar_long");
     }
     if (h.nnz <= 32 * h.rows) {
@@ -868,8 +885,9 @@ int launch_wave(spmv_csr &h, const float *x, float *y, bool pipelined, hipStream
     const bool plain_bundle = !pipelined && h.nnz <= 32 * h.rows && getenv("SPMV_WAVE_PER_ROW") == nullptr;
     const bool bundle = (pipelined && h.nnz <= 32 * h.rows) || plain_bundle;
     if (pipelined && !bundle) {
-        hipLaunchKernelGGL(k_wave<true>, dim3((unsigned)blocks), dim3(kBlock), 0, s, h.rows, h.d_row_ptr, h.d_col_idx,
-                           h.d_vals, x, y);
+        launch_row_slices(blocks, kRowsPerBlock, [&](dim3 grid, int64_t row0) {
+            hipLaunchKernelGGL(k_wave<true>, grid, dim3(kBlock), 0, s, row0, h.rows, h.d_row_ptr, h.d_col_idx, h.d_vals, x, y);
+        });
     } else if (bundle) {
         if (int rc = plan_wave(h, s)) return rc;        // (the first run of a handle that was not planned: allocates, waits)
         const WavePlan &p = h.plan_wave;
@@ -893,8 +911,9 @@ int launch_wave(spmv_csr &h, const float *x, float *y, bool pipelined, hipStream
         }
 #endif
     } else {
-        hipLaunchKernelGGL(k_wave<false>, dim3((unsigned)blocks), dim3(kBlock), 0, s, h.rows, h.d_row_ptr, h.d_col_idx,
-                           h.d_vals, x, y);
+        launch_row_slices(blocks, kRowsPerBlock, [&](dim3 grid, int64_t row0) {
+            hipLaunchKernelGGL(k_wave<false>, grid, dim3(kBlock), 0, s, row0, h.rows, h.d_row_ptr, h.d_col_idx, h.d_vals, x, y);
+        });
     }
     return check_launch("k_wave");
 }
@@ -915,8 +934,9 @@ static int launch_vector_g(const spmv_csr &h, const float *x, float *y, hipStrea
     constexpr int kRowsPerBlock = kBlock / G;
     int64_t blocks = (h.rows + kRowsPerBlock - 1) / kRowsPerBlock;
     if (!grid_ok(blocks)) return SPMV_ERR_INVALID;
-    hipLaunchKernelGGL(k_vector<G>, dim3((unsigned)blocks), dim3(kBlock), 0, s, h.rows, h.d_row_ptr,
-                       h.d_col_idx, h.d_vals, x, y);
+    launch_row_slices(blocks, kRowsPerBlock, [&](dim3 grid, int64_t row0) {
+        hipLaunchKernelGGL(k_vector<G>, grid, dim3(kBlock), 0, s, row0, h.rows, h.d_row_ptr, h.d_col_idx, h.d_vals, x, y);
+    });
     return check_launch("k_vector");
 }
 

@@ -189,9 +189,9 @@ int plan_spmm(spmv_csr &h, hipStream_t s)
         if (e - b <= kSpmmRowCap) continue;
         lr.push_back((int32_t)r);
         lf.push_back((int32_t)k0.size());
-        for (int32_t q = b; q < e; q += kSpmmPiece) {
-            k0.push_back(q);
-            ln.push_back(e - q < kSpmmPiece ? e - q : kSpmmPiece);
+        for (int64_t q = b; q < e; q += kSpmmPiece) {   // (64 bits: q + kSpmmPiece passes INT_MAX on a row that ends near it)
+            k0.push_back((int32_t)q);
+            ln.push_back((int32_t)(e - q < kSpmmPiece ? e - q : kSpmmPiece));
         }
     }
     lf.push_back((int32_t)k0.size());
@@ -252,7 +252,12 @@ static int launch_spmm_v(const spmv_csr &h, int k, const float *X, int64_t ldx, 
     const SpmmPlan &p = h.plan_spmm;
     constexpr int kRowsPerBlock = kSpmmBlock / V;
     const int64_t nblocks = (h.rows + kRowsPerBlock - 1) / kRowsPerBlock;
-    if (nblocks > 0x7fffffffLL) { set_error("spmv_csr_spmm: %lld row blocks exceed the grid limit", (long long)nblocks); return SPMV_ERR_INVALID; }
+    // (a launch carries fewer than 2^32 work-items -- the runtime passes grid x block on in 32 bits and a larger product wraps
+    // silently: rows x lanes per row < 2^32 -- any handle up to k = 8, rows < 2^30 / 2^29 / 2^28 up to k = 16 / 32 / 64)
+    if (nblocks * kSpmmBlock >= (1LL << 32)) {
+        set_error("spmv_csr_spmm: %lld rows x %d lanes per row reach the launch limit of 2^32 work-items", (long long)h.rows, V);
+        return SPMV_ERR_INVALID;
+    }
     hipLaunchKernelGGL((k_spmm_rows<V, VEC>), dim3((unsigned)nblocks), dim3(kSpmmBlock), 0, s, h.rows, nblocks,
                        V == 1 ? nullptr : p.d_order, h.d_row_ptr,
                        h.d_col_idx, h.d_vals, X, ldx, Y, ldy, k);

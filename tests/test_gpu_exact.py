@@ -18,7 +18,8 @@ other properties give per-row answers that do not depend on the order either:
 
 Signed zeros compare equal (an exact zero sum is +0 or -0 depending on whether a kernel seeds its accumulator with +0).
 Every run is made twice, into y filled with NaN and into y filled with a finite sentinel; the two must agree bit for
-bit, so a row a kernel leaves unwritten fails even where the expected value is NaN.
+bit, so a row a kernel leaves unwritten fails even where the expected value is NaN.  y is a view one float past a 16-byte
+boundary inside a buffer with 4096 guard floats on either side, which every run must leave untouched.
 
 Paths (PATHS below; a fresh handle per path, the knobs set in the environment for its plan and its runs; each path also
 checks that spmv_csr_plan_describe reports the plan it asked for):
@@ -56,6 +57,7 @@ import _exact as E
 from _util import assert_close_to_oracle
 
 SENTINEL = np.float32(-1.2345e30)
+GUARD, GUARD_N = np.float32(3.0e35), 4096
 KNOBS = ("SPMV_AUTOTUNE", "SPMV_TILED_BLOCK", "SPMV_MAXPASS", "SPMV_COL16", "SPMV_SORTED_FROM", "SPMV_BLOCKS",
          "SPMV_PERSIST", "SPMV_WAVE_BLOCK", "SPMV_WAVE_COL16", "SPMV_WAVE_PER_ROW", "SPMV_PANEL_STEP",
          "SPMV_BINNED_WIDE", "SPMV_BS_FILL", "SPMV_AUTO_SORTED_BLOCKS", "SPMV_AUTO_BINNED", "SPMV_PANEL_SORTED",
@@ -132,7 +134,12 @@ class _Dev:
         self.d_rp = torch.from_numpy(s.rp).to(gpu)
         self.d_ci = torch.from_numpy(s.ci).to(gpu)
         self.d_va = torch.from_numpy(np.ascontiguousarray(vals, np.float32)).to(gpu)
-        self.d_y = torch.empty(max(s.rows, 1), dtype=torch.float32, device=gpu)
+        # y: a view one float past a 16-byte boundary (spmv_csr_run asks 4-byte alignment of y only), GUARD_N guard floats
+        # on either side: a store outside y[0, rows), or a vector store that assumes alignment, shows in the guards
+        n = max(s.rows, 1)
+        self.buf = torch.full((GUARD_N + 1 + n + GUARD_N,), float(GUARD), dtype=torch.float32, device=gpu)
+        self.d_y = self.buf[GUARD_N + 1:GUARD_N + 1 + n]
+        assert self.d_y.data_ptr() % 16 == 4
         self.gpu = gpu
         self.cases = []          # (label, d_x, expected, oracle y64 or None, XSKIP's (expected, y64) or None)
 
@@ -151,6 +158,9 @@ class _Dev:
             A.run(v, d_x, self.d_y)
             torch.cuda.synchronize()
             ys.append(self.d_y[:self.s.rows].cpu().numpy())
+            lo, hi = self.buf[:GUARD_N + 1], self.buf[GUARD_N + 1 + self.d_y.numel():]
+            assert bool((lo == float(GUARD)).all()) and bool((hi == float(GUARD)).all()), \
+                f"{capi.lib().spmv_variant_name(v).decode()}: a run wrote outside y[0, rows)"
         return ys
 
 

@@ -4,7 +4,8 @@
                  NaN / +Inf / -Inf, non-finite, unsorted with duplicates); k in KS with ld = k, k + 3 and k rounded up to
                  4; every column of X its own integer vector, so every column of Y must equal its int64 expectation bit
                  for bit (non-finite form: per row the class of the fp64 oracle, finite rows exact).  Each case runs
-                 twice, into Y filled with NaN and with a sentinel: the two agree bit for bit.
+                 twice, into Y filled with NaN and with a sentinel: the two agree bit for bit.  Y lies between two bands
+                 of 4096 guard floats that every run must leave untouched.
   padding        Y's columns [k, ldy) keep their fill bit for bit; X's columns [k, ldx) hold NaN and change nothing.
   batch          for one plan, column c of a k = 64 run equals the k = 1 run of that column and the k = 13 run with the
                  column at another position, also with every other column NaN / Inf; two handles agree (config 3 with
@@ -32,6 +33,7 @@ pytestmark = pytest.mark.gpu
 KS = (1, 2, 3, 4, 5, 8, 13, 16, 31, 32, 33, 64)
 KINDS = ("exact", "subnormal", "poison", "nonfinite", "unsorted")
 SENTINEL = np.float32(-1.2345e30)
+GUARD, GUARD_N = np.float32(3.0e35), 4096
 
 
 def _lds(k):
@@ -80,13 +82,22 @@ class _Spmm:
         X = torch.full((s.cols, ldx), float("nan"), dtype=torch.float32, device=self.gpu)
         X[:, :k] = X64[:, :k]
         ys = []
+        bufs = []
         for fill in (float("nan"), float(SENTINEL)):
-            Y = torch.full((s.rows, ldy), fill, dtype=torch.float32, device=self.gpu)
+            # Y 16-byte aligned (the header asks it) between two bands of GUARD_N guard floats: nothing outside Y is written
+            buf = torch.full((2 * GUARD_N + s.rows * ldy,), float(GUARD), dtype=torch.float32, device=self.gpu)
+            Y = buf[GUARD_N:GUARD_N + s.rows * ldy].view(s.rows, ldy)
+            assert Y.data_ptr() % 16 == 0
+            Y.fill_(fill)
             self.A.spmm(X[:, :k], Y[:, :k])
             ys.append(Y)
+            bufs.append(buf)
         torch.cuda.synchronize()
         y0, y1 = ys
         bad = []
+        for buf in bufs:
+            if not (bool((buf[:GUARD_N] == float(GUARD)).all()) and bool((buf[GUARD_N + s.rows * ldy:] == float(GUARD)).all())):
+                bad.append("a run wrote outside Y")
         d = (y0[:, :k].view(torch.int32) != y1[:, :k].view(torch.int32)).sum().item()
         if d:
             bad.append(f"{d} entries unwritten")
