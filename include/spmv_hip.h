@@ -164,6 +164,54 @@ SPMV_API int spmv_csr_dims(const spmv_csr_t *h, int64_t *rows, int64_t *cols, in
 SPMV_API int spmv_csr_column_range(const spmv_csr_t *h, int64_t *col_min, int64_t *col_max, void *stream);
 SPMV_API int spmv_csr_destroy(spmv_csr_t *h);
 
+/* ---- the transpose -------------------------------------------------------
+ * The library multiplies by a handle's own orientation only; z = A^T u (the backward pass of a sparse layer, BiCG / LSQR,
+ * pull versus push) goes through an explicit transpose: T = A^T is an ordinary spmv_csr_t, so every variant, SPMV_AUTO,
+ * SpMM and the row-block exchange work on it as on any other handle, and the order of every sum stays a pure function of
+ * the matrix (a scatter-add kernel with float atomics would give that up).  The reference has no counterpart: it only
+ * multiplies one way.
+ *
+ * spmv_csr_transpose: T = A^T as a new handle on A's device, built on the device (no host pass over the nonzeros).
+ * T has rows = a.cols, cols = a.rows, nnz = a.nnz and owns its three arrays (spmv_csr_destroy frees them); every
+ * spmv_csr_* call accepts it; it has no plans yet.  `a` is only read and keeps its plans; it may own or borrow its arrays,
+ * be a whole matrix or a row block.
+ *   The order is part of the interface.  Row j of T lists the nonzeros of A whose column is j in ascending STORAGE POSITION
+ * k of A.  With perm = argsort(a.col_idx, stable):
+ *     t.row_ptr    = [0, cumsum(bincount(a.col_idx, minlength = a.cols))]
+ *     t.col_idx[i] = the row of A that holds position perm[i]
+ *     t.vals[i]    = a.vals[perm[i]]      (the bits are copied: NaN payloads, -0.0, subnormals)
+ *     map[i]       = perm[i]              (kept with keep_map = 1: 4 bytes per nonzero)
+ * So: the rows of T are always sorted (column indices non-decreasing), whatever the order inside A's rows; a column that
+ * A repeats inside a row gives a repeated column inside a row of T, in A's storage order; an empty column of A is an empty
+ * row of T; T is a pure function of A's arrays -- two calls, two handles of one matrix, any stream give the same bytes (no
+ * place is taken from the value an atomic returns).  transpose(transpose(A)) is A with every row stably sorted by column:
+ * A itself, bit for bit, when A's rows are sorted.
+ *   Like spmv_csr_plan it allocates, enqueues on `stream` and waits for it before it returns.  SPMV_ERR_INVALID (the
+ * message names the function, *out untouched) for a null `a` or `out`, keep_map other than 0 / 1, or another current device
+ * than a's; SPMV_ERR_HIP when an allocation fails (what was allocated is released, `a` stays usable); SPMV_ERR_NO_DEVICE as
+ * everywhere.  Every handle is admitted (rows, cols, nnz < 2^31): positions are unsigned 32-bit numbers, byte offsets 64-bit,
+ * t.row_ptr may pass 4 GiB, t.col_idx holds row numbers up to 2^31 - 2; nnz = 0, rows = 0 and cols = 0 work.
+ *   Device memory: T itself takes 8 nnz + 4 (a.cols + 1) bytes (+ 4 nnz for the map).  While the call runs it holds at
+ * most 16 nnz + 1024 ceil(nnz / 4096) + 4 ceil(nnz / 65536) + 4 ceil((a.cols + 1) / 4096) + 64 bytes more (two position
+ * and two key buffers of 4 nnz each -- one position buffer is the map, the others are freed on return --, the table of
+ * 256 counters per tile of 4096 nonzeros, the tile sums of the two scans): 24.25 bytes per nonzero + 4 per column at the
+ * peak, T included.
+ *
+ * spmv_csr_transpose_values: t.vals[i] = a.vals[map[i]] for a handle made with keep_map = 1 -- the values of A as they are
+ * now, in one gather launch.  Asynchronous, allocates nothing, never waits: graph-capturable.  `a` must have t's shape
+ * swapped and the same nnz and live on t's device (else SPMV_ERR_INVALID); that it still has the PATTERN t was made from
+ * is the caller's promise, as for plans.  It reads a's values live (borrowed arrays the caller has rewritten are the point)
+ * and then does for t what spmv_csr_values_changed(t) does: the plans of t that read vals live (SPMV_SCALAR ... SPMV_TILED,
+ * SpMM) use the new values on their next run, the plans that hold a copy (SPMV_PANEL, SPMV_XSKIP, SPMV_AUTO where it
+ * resolved to one of them) answer SPMV_ERR_STALE_PLAN until re-planned.  On a handle without a map (keep_map = 0, or not
+ * made by spmv_csr_transpose): SPMV_ERR_INVALID, nothing launched.
+ *
+ * spmv_csr_transpose_map_bytes: device bytes of the kept map (4 * nnz; 0 without one or for a handle not made by
+ * spmv_csr_transpose; < 0: null handle). */
+SPMV_API int spmv_csr_transpose(const spmv_csr_t *a, int keep_map, void *stream, spmv_csr_t **out);
+SPMV_API int spmv_csr_transpose_values(spmv_csr_t *t, const spmv_csr_t *a, void *stream);
+SPMV_API int64_t spmv_csr_transpose_map_bytes(const spmv_csr_t *t);
+
 /* ---- the hot path ------------------------------------------------------
  * spmv_csr_plan: one-off device-side preprocessing a variant needs (chunk
  * boundaries, column windows, for SPMV_TILED also a 16-bit copy of the column
@@ -205,6 +253,7 @@ SPMV_API int spmv_csr_destroy(spmv_csr_t *h);
  *   SPMV_XSKIP                                ceil(rows / 1024) x cols <= 2^27 table entries; rows sorted, duplicate-free
  *   spmv_csr_spmm                             rows x lanes per row < 2^32 (one launch): any handle up to k = 8,
  *                                             rows < 2^30 up to k = 16, < 2^29 up to k = 32, < 2^28 up to k = 64
+ *   spmv_csr_transpose                        any handle
  * (tests/test_gpu_limits.py runs every path on either side of these.) */
 SPMV_API int spmv_csr_plan(spmv_csr_t *h, int variant, void *stream);
 SPMV_API int spmv_csr_run(spmv_csr_t *h, int variant, const float *d_x, float *d_y, void *stream);

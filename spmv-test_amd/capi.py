@@ -45,6 +45,9 @@ SIGNATURES = {
     "spmv_csr_dims": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "spmv_csr_column_range": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _vp]),
     "spmv_csr_destroy": (C.c_int, [_H]),
+    "spmv_csr_transpose": (C.c_int, [_H, C.c_int, _vp, _HP]),
+    "spmv_csr_transpose_values": (C.c_int, [_H, _H, _vp]),
+    "spmv_csr_transpose_map_bytes": (C.c_int64, [_H]),
     "spmv_csr_plan": (C.c_int, [_H, C.c_int, _vp]),
     "spmv_csr_run": (C.c_int, [_H, C.c_int, _f32p, _f32p, _vp]),
     "spmv_csr_values_changed": (C.c_int, [_H]),
@@ -217,6 +220,26 @@ class CsrMatrix:
         lo, hi = C.c_int64(), C.c_int64()
         check(lib().spmv_csr_column_range(self._h, C.byref(lo), C.byref(hi), _stream_handle(stream)))
         return lo.value, hi.value
+
+    # -- the transpose (spmv_csr_transpose) ------------------------------------------------------------------------
+    def transpose(self, keep_map: bool = False, stream=None) -> "CsrMatrix":
+        """A^T as a new handle that owns its arrays, built on the device (waits for the stream).  Row j lists the
+        nonzeros of column j in this matrix's storage order.  ``keep_map=True`` keeps the 4-byte-per-nonzero map that
+        :meth:`transpose_values` needs."""
+        h = C.c_void_p()
+        check(lib().spmv_csr_transpose(self._h, 1 if keep_map else 0, _stream_handle(stream), C.byref(h)))
+        return CsrMatrix(h.value)
+
+    def transpose_values(self, a: "CsrMatrix", stream=None) -> None:
+        """Refresh this handle's values (made by ``a.transpose(keep_map=True)``) from ``a``'s values as they are now:
+        one gather launch, asynchronous, graph-capturable; then what :meth:`values_changed` does."""
+        check(lib().spmv_csr_transpose_values(self._h, a._h, _stream_handle(stream)))
+
+    def transpose_map_bytes(self) -> int:
+        n = lib().spmv_csr_transpose_map_bytes(self._h)
+        if n < 0:
+            check(n)
+        return n
 
     # -- SpMM: k right-hand sides at once (spmv_csr_spmm) ---------------------------------------------------------
     def spmm_plan(self, stream=None) -> None:

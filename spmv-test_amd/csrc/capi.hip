@@ -355,6 +355,47 @@ int spmv_csr_destroy(spmv_csr_t *h)
     return rc;
 }
 
+int spmv_csr_transpose(const spmv_csr_t *a, int keep_map, void *stream, spmv_csr_t **out)
+{
+    if (!a || !out) { set_error("spmv_csr_transpose: null argument"); return SPMV_ERR_INVALID; }
+    if (keep_map != 0 && keep_map != 1) {
+        set_error("spmv_csr_transpose: keep_map = %d (0 or 1)", keep_map);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_device()) return rc;
+    if (int rc = require_current(a->device, "spmv_csr_transpose")) return rc;
+    return transpose(*a, keep_map == 1, (hipStream_t)stream, out);
+}
+
+int spmv_csr_transpose_values(spmv_csr_t *t, const spmv_csr_t *a, void *stream)
+{
+    if (!t || !a) { set_error("spmv_csr_transpose_values: null argument"); return SPMV_ERR_INVALID; }
+    if (!t->transpose_map) {
+        set_error("spmv_csr_transpose_values: the handle has no map (it was not made by spmv_csr_transpose with keep_map = 1)");
+        return SPMV_ERR_INVALID;
+    }
+    if (a->rows != t->cols || a->cols != t->rows || a->nnz != t->nnz) {
+        set_error("spmv_csr_transpose_values: a is %lld x %lld with %lld nonzeros, the transpose of t would be %lld x %lld with %lld",
+                  (long long)a->rows, (long long)a->cols, (long long)a->nnz, (long long)t->cols, (long long)t->rows,
+                  (long long)t->nnz);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(t->device, "spmv_csr_transpose_values")) return rc;
+    if (a->device != t->device) {
+        set_error("spmv_csr_transpose_values: a lives on device %d, t on device %d", a->device, t->device);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = transpose_values(*t, *a, (hipStream_t)stream)) return rc;
+    ++t->values_gen;
+    return SPMV_OK;
+}
+
+int64_t spmv_csr_transpose_map_bytes(const spmv_csr_t *t)
+{
+    if (!t) { set_error("spmv_csr_transpose_map_bytes: null handle"); return SPMV_ERR_INVALID; }
+    return t->transpose_map ? 4 * t->nnz : 0;
+}
+
 // SPMV_AUTO.  TILED's plan is made first (cheap: a few passes over col_idx, no trial launches) and priced (model_cost,
 // in units of "a chunk that streams 8 bytes per nonzero with cache-resident gathers").
 //   1. It stages (nearly) everything in one or two passes (model_cost <= 1.20: bands up to ~60 000 columns at config 4): TILED.

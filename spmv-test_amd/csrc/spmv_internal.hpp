@@ -240,6 +240,7 @@ struct spmv_csr {
     const float *d_vals = nullptr;
     spmv::DevPtr<int32_t> own_row_ptr, own_col_idx;   // the handle's own copies behind the views (empty: the caller's arrays)
     spmv::DevPtr<float> own_vals;
+    spmv::DevPtr<uint32_t> transpose_map;   // [nnz] spmv_csr_transpose(keep_map = 1): vals[i] = the parent's vals[map[i]] (empty: no map)
     int device = 0;
 
     // plan state
@@ -320,6 +321,9 @@ double binned_tile_nonzeros(const spmv_csr &h, int bin_rows);
 int plan_spmm(spmv_csr &h, hipStream_t s);
 int launch_spmm(const spmv_csr &h, int k, const float *X, int64_t ldx, float *Y, int64_t ldy, hipStream_t s);
 int64_t spmm_plan_bytes(const spmv_csr &h);
+// kernels_transpose.hip: spmv_csr_transpose / spmv_csr_transpose_values
+int transpose(const spmv_csr &a, bool keep_map, hipStream_t s, spmv_csr_t **out);
+int transpose_values(spmv_csr &t, const spmv_csr &a, hipStream_t s);
 
 int dense_to_csr(int M, int N, const float *d_A, hipStream_t s, spmv_csr_t **out);
 int dense_gemv(int M, int N, const float *d_A, const float *d_x, float *d_y, int mode, hipStream_t s);

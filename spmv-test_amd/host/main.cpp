@@ -1,8 +1,9 @@
 // main.cpp -- the tester executable (reference: test/main.cpp:3-7 hard-codes 4096 x 4096).
 //   sparse_sgemv [M N]                          the reference flow on a random dense M x N matrix
-//   sparse_sgemv --mtx FILE [--variant NAME] [--out Y.txt] [--save FILE.csrbin] [--parse-only]
-//   sparse_sgemv --csrbin FILE [--variant NAME] [--out Y.txt]
-//        y = A * ones through the C ABI on a matrix from disk (row f-4), checked against a host walk
+//   sparse_sgemv --mtx FILE [--variant NAME] [--transpose] [--out Y.txt] [--save FILE.csrbin] [--parse-only]
+//   sparse_sgemv --csrbin FILE [--variant NAME] [--transpose] [--out Y.txt]
+//        y = A * ones through the C ABI on a matrix from disk (row f-4), checked against a host walk;
+//        --transpose: y = A^T * ones (x of `rows` ones, y of `cols` entries) through spmv_csr_transpose
 // $SPMV_SEED makes the random inputs reproducible.
 #include <cmath>
 #include <cstdio>
@@ -24,7 +25,7 @@ static int variant_by_name(const std::string &n)
 static int run_file(int argc, char **argv)
 {
     std::string mtx, bin, out, save, vname = "tiled";
-    bool parse_only = false;
+    bool parse_only = false, transpose = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> std::string { return i + 1 < argc ? argv[++i] : ""; };
@@ -34,6 +35,7 @@ static int run_file(int argc, char **argv)
         else if (a == "--save") save = next();
         else if (a == "--variant") vname = next();
         else if (a == "--parse-only") parse_only = true;
+        else if (a == "--transpose") transpose = true;
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     HostCsr m;
@@ -45,23 +47,32 @@ static int run_file(int argc, char **argv)
     const int variant = variant_by_name(vname);
     if (variant < 0) { std::fprintf(stderr, "unknown variant %s\n", vname.c_str()); return 2; }
 
-    std::vector<float> x((size_t)m.cols, 1.0f), y((size_t)m.rows, NAN), ref((size_t)m.rows, 0.0f);
+    const int64_t nx = transpose ? m.rows : m.cols, ny = transpose ? m.cols : m.rows;
+    std::vector<float> x((size_t)nx, 1.0f), y((size_t)ny, NAN), ref((size_t)ny, 0.0f), mag((size_t)ny, 0.0f);
     for (int64_t r = 0; r < m.rows; ++r) {  // the harness's own CPU check, like SgemvCPU (tester.cpp:36-45)
-        float acc = 0.0f;
-        for (int32_t k = m.row_ptr[r]; k < m.row_ptr[r + 1]; ++k) acc += x[m.col_idx[k]] * m.vals[k];
-        ref[r] = acc;
+        float acc = 0.0f, sum = 0.0f;
+        for (int32_t k = m.row_ptr[r]; k < m.row_ptr[r + 1]; ++k) {
+            if (transpose) {   // column sums in storage order: the order of T's rows
+                ref[m.col_idx[k]] += x[r] * m.vals[k];
+                mag[m.col_idx[k]] += std::fabs(m.vals[k]);
+            } else {
+                acc += x[m.col_idx[k]] * m.vals[k];
+                sum += std::fabs(m.vals[k]);
+            }
+        }
+        if (!transpose) { ref[r] = acc; mag[r] = sum; }
     }
-    spmv_csr_t *A = nullptr;
+    spmv_csr_t *A = nullptr, *T = nullptr;
     SPMV_CHECK(spmv_csr_create_host(m.rows, m.cols, m.nnz(), m.row_ptr.data(), m.col_idx.data(), m.vals.data(), &A));
+    if (transpose) SPMV_CHECK(spmv_csr_transpose(A, 0, nullptr, &T));
     float ms = 0.0f;
-    SPMV_CHECK(spmv_csr_run_host(A, variant, x.data(), y.data(), &ms));
-    std::printf("spmv_csr_run<%s> took %g ms\n", spmv_variant_name(variant), ms);
+    SPMV_CHECK(spmv_csr_run_host(transpose ? T : A, variant, x.data(), y.data(), &ms));
+    std::printf("spmv_csr_run<%s>%s took %g ms\n", spmv_variant_name(variant), transpose ? " on the transpose" : "", ms);
+    SPMV_CHECK(spmv_csr_destroy(T));
     SPMV_CHECK(spmv_csr_destroy(A));
     int bad = 0;
-    for (int64_t r = 0; r < m.rows; ++r) {
-        float mag = 0.0f;
-        for (int32_t k = m.row_ptr[r]; k < m.row_ptr[r + 1]; ++k) mag += std::fabs(m.vals[k]);
-        if (!(std::fabs(ref[r] - y[r]) <= 1e-5f * mag + 1e-30f)) {
+    for (int64_t r = 0; r < ny; ++r) {
+        if (!(std::fabs(ref[r] - y[r]) <= 1e-5f * mag[r] + 1e-30f)) {
             if (bad < 16) std::fprintf(stderr, "[row %lld] cpu: %g, gpu: %g\n", (long long)r, ref[r], y[r]);
             ++bad;
         }
