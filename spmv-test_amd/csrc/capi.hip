@@ -435,7 +435,7 @@ static int plan_auto(spmv_csr &h, hipStream_t s)
             const bool big = lines_est > 0.30 && h.rows >= 4096ll * 16 * device_cus(h.device);
             rc = build_panel(h, h.plan_auto_panel, big ? 8192 : 0, big ? 4 : 0, 3, s);
             if (rc == SPMV_OK) {
-                const PanelPlan &pp = h.plan_auto_panel;
+                const SortedBlocksPlan &pp = h.plan_auto_panel.sorted;
                 const bool fits = (double)pp.tail <= 0.10 * (double)h.nnz && 10 * pp.wide_blocks <= pp.nblocks;
                 if (fits && colsort_model_cost(pp, h.nnz) < 0.98 * cost_tiled) {   // (a tie goes to TILED: it reads vals live)
                     h.auto_variant = SPMV_PANEL;
@@ -468,7 +468,7 @@ static int plan_auto(spmv_csr &h, hipStream_t s)
             rc = build_panel(h, h.plan_auto_panel, 0, 0, try_binned, s);
             // (bins that ran out of spare accumulators add with LDS atomics, four times slower: rows with dozens of nonzeros in
             // one tile -- long rows over a band of a few million columns -- are the fetching flavour's case)
-            if (rc == SPMV_OK && try_binned == 5 && 32 * (int64_t)h.plan_auto_panel.flagged_tiles > h.plan_auto_panel.nblocks)
+            if (rc == SPMV_OK && try_binned == 5 && 32 * (int64_t)h.plan_auto_panel.scattered.flagged_bins > h.plan_auto_panel.scattered.nblocks)
                 rc = build_panel(h, h.plan_auto_panel, 0, 0, 4, s);
             if (rc == SPMV_OK) {
                 h.auto_variant = SPMV_PANEL;
@@ -502,7 +502,7 @@ int spmv_csr_plan(spmv_csr_t *h, int variant, void *stream)
         case SPMV_VECTOR: return plan_vector(*h, s);
         case SPMV_ADAPTIVE: return plan_adaptive(*h, false, s);
         case SPMV_TILED: return plan_adaptive(*h, true, s);
-        case SPMV_PANEL: return plan_panel(*h, s);
+        case SPMV_PANEL: return refresh_panel(*h, h->plan_panel, s);
         case SPMV_XSKIP: return plan_xskip(*h, s);
         default:
             set_error("spmv_csr_plan: unknown variant %d", variant);
@@ -534,7 +534,7 @@ int spmv_csr_run(spmv_csr_t *h, int variant, const float *d_x, float *d_y, void 
         case SPMV_VECTOR: return launch_vector(*h, d_x, d_y, s);
         case SPMV_ADAPTIVE: return launch_adaptive(*h, d_x, d_y, false, s);
         case SPMV_TILED: return launch_adaptive(*h, d_x, d_y, true, s);
-        case SPMV_PANEL: return launch_panel(*h, d_x, d_y, s);
+        case SPMV_PANEL: return launch_panel_plan(*h, h->plan_panel, d_x, d_y, s);
         case SPMV_XSKIP: return launch_xskip(*h, d_x, d_y, s);
         default:
             set_error("spmv_csr_run: unknown variant %d", variant);
@@ -616,11 +616,8 @@ int spmv_csr_plan_get(const spmv_csr_t *h, int variant, int32_t params[8])
             params[1] = h->plan_xskip.slabs;
             return SPMV_OK;
         case SPMV_PANEL:
-            if (!panel.ready) { set_error("spmv_csr_plan_get: panel is not planned"); return SPMV_ERR_NOT_PLANNED; }
-            params[4] = panel.pw_bits; params[5] = panel.waves_per_launch;
-            params[6] = panel.binned_mode ? (panel.scatter_mode ? 5 : 4) : panel.sorted_mode ? 3 : (panel.lds_mode ? 2 : 1);
-            if (panel.sorted_mode) { params[4] = panel.sb_rows; params[5] = panel.sb_waves; }
-            if (panel.binned_mode) { params[4] = panel.bin_rows; params[5] = 0; }
+            if (panel.layout == PanelLayout::none) { set_error("spmv_csr_plan_get: panel is not planned"); return SPMV_ERR_NOT_PLANNED; }
+            panel_params(panel, params);
             return SPMV_OK;
         default: set_error("spmv_csr_plan_get: unknown variant %d", variant); return SPMV_ERR_VARIANT;
     }
@@ -686,15 +683,7 @@ int64_t spmv_csr_plan_bytes(const spmv_csr_t *h, int variant)
         case SPMV_XSKIP:     // segment list + slab partials; erow16/evals (6 B per nonzero) REPLACE col_idx/vals (8 B)
             return (int64_t)h->plan_xskip.nseg * 8 + ((int64_t)h->plan_xskip.nblocks + 1) * 4 +
                    (h->plan_xskip.slabs > 1 ? (int64_t)h->plan_xskip.nblocks * h->plan_xskip.slabs * 1024 * 8 : 0);
-        case SPMV_PANEL:     // tile_ptr; packed/pvals REPLACE col_idx/vals byte for byte (sorted blocks: + the empty slots)
-            if (panel.binned_mode && panel.scatter_mode)   // panel-major: column 2 + value 4, an offset per run; bin-major: product 4 + accumulator 2; the lists
-                return panel.padded * (2 + 4) + panel.padded / 512 * 4 + panel.runs * 4 + panel.bm_entries * (4 + 2) +
-                       (int64_t)panel.nblocks * (1024 * 4 + 16) + ((int64_t)panel.npanels + 1) * 4;
-            if (panel.binned_mode)   // two tables per tile, 16-bit columns and rows, the products written and read back; pvals REPLACES vals
-                return (int64_t)panel.nblocks * (2 * (int64_t)panel.npanels + 2) * 4 + panel.padded * (2 + 4 + 4) + h->nnz * 2;
-            if (panel.sorted_mode)   // unit bases, block tables, the rows of the tail units, the empty slots of the units in use
-                return panel.units * 4 + (int64_t)panel.nblocks * 20 + panel.tail_units * 512;
-            return (int64_t)panel.nblocks * (panel.npanels + 1) * 4 + ((int64_t)panel.nblocks + 1) * 4;
+        case SPMV_PANEL: return panel_plan_bytes(panel, h->nnz);   // (its arrays REPLACE col_idx/vals: what comes on top of them)
         case SPMV_WAVE:      // (short rows: the same plan without the windows and the offsets; long rows: none)
             if (h->nnz > 32 * h->rows) return 0;
             return (int64_t)h->plan_wave.n_long * 8 + (int64_t)h->plan_wave.pieces * 16;
@@ -728,25 +717,7 @@ int spmv_csr_plan_describe(const spmv_csr_t *h, int variant, char *buf, int n)
                       h->plan_wave.pieces, h->plan_wave.block_rows, (long long)h->plan_wave.blocks, (long long)h->plan_wave.win_blocks,
                       h->plan_wave.d_col16 ? 1 : 0);
     }
-    else if (variant == SPMV_PANEL && panel->ready && panel->binned_mode && panel->scatter_mode)
-        snprintf(buf, (size_t)n, "binned scattered_products bins=%d rows_per_bin=%d panels=%d panel_columns=%d nonzeros_per_tile=%.1f rows_with_spare_sums=%d flagged_bins=%d product_workgroups_per_panel=%d padded=%lld bin_entries=%lld",
-                 panel->nblocks, panel->bin_rows, panel->npanels, 1 << panel->pw_bits,
-                 panel->nblocks ? (double)h->nnz / ((double)panel->nblocks * panel->npanels) : 0.0, panel->long_rows, panel->flagged_tiles,
-                 panel->splits, (long long)panel->padded, (long long)panel->bm_entries);
-    else if (variant == SPMV_PANEL && panel->ready && panel->binned_mode)
-        snprintf(buf, (size_t)n, "binned bins=%d rows_per_bin=%d panels=%d panel_columns=%d nonzeros_per_tile=%.1f products_per_lane=%d long_rows=%d flagged_tiles=%d product_workgroups_per_panel=%d padded=%lld",
-                 panel->nblocks, panel->bin_rows, panel->npanels, 1 << panel->pw_bits,
-                 panel->nblocks ? (double)h->nnz / ((double)panel->nblocks * panel->npanels) : 0.0, panel->wide_pieces ? 4 : 2, panel->long_rows, panel->flagged_tiles, panel->splits,
-                 (long long)panel->padded);
-    else if (variant == SPMV_PANEL && panel->ready && panel->sorted_mode)
-        snprintf(buf, (size_t)n, "sorted_blocks=%d rows_per_block=%d wavefronts=%d lines_per_nonzero=%.3f tail_nonzeros=%lld wide_blocks=%lld model_cost=%.3f",
-                 panel->nblocks, panel->sb_rows, panel->sb_waves,
-                 h->nnz ? (double)panel->lines / (double)h->nnz : 0.0, (long long)panel->tail,
-                 (long long)panel->wide_blocks, colsort_model_cost(*panel, h->nnz));
-    else if (variant == SPMV_PANEL && panel->ready)
-        snprintf(buf, (size_t)n, "panel_columns=%d panels=%d row_blocks=%d waves_per_launch=%d launches=%d x_panels_in=%s nonzeros_per_step=%d",
-                 1 << panel->pw_bits, panel->npanels, panel->nblocks,
-                 panel->waves_per_launch, panel_launches(*panel), panel->lds_mode ? "LDS" : "L2", panel->lds_mode ? 64 : 256 * panel->step_vecs);
+    else if (variant == SPMV_PANEL) panel_describe(*panel, *h, buf, n);
     else if (variant == SPMV_XSKIP && h->plan_xskip.ready)
         snprintf(buf, (size_t)n, "output_blocks=%d segments=%d slabs_per_block=%d", h->plan_xskip.nblocks, h->plan_xskip.nseg,
                  h->plan_xskip.slabs);

@@ -44,7 +44,6 @@ constexpr int kSumWaves = 4;               // wavefronts per workgroup of the su
 constexpr int kSpare = 512;                // spare sums per bin for its long rows (see k_bin_runs)
 constexpr int kBinSlack = 264;             // entries behind d_prod / d_r16 (mode 4): a piece of the sum launch reads up to 256 past a tile's end
 
-
 using u4 = unsigned __attribute__((ext_vector_type(4)));
 using f4 = float __attribute__((ext_vector_type(4)));
 
@@ -196,7 +195,7 @@ __global__ __launch_bounds__(kProdThreads) void k_bin_products(int splits, int64
 }
 
 
-// ==== the SCATTERED flavour (PanelPlan::scatter_mode): the products land in BIN-major order =============================
+// ==== the SCATTERED flavour (ScatteredPlan): the products land in BIN-major order =============================
 // The flavour above lets the sum launch FETCH tile (b, p) from the panel-major products: a piece of <= 64 E products of one
 // tile per instruction group.  That is as good as the tiles are fat -- config 5's shard has 10-20 products per tile, so
 // nine lanes in ten idle and every tile costs its table entries (4.1 ms against the sweep's 3.0).  Here the PRODUCT launch
@@ -217,7 +216,7 @@ constexpr int kBmPiece = 256;              // entries of the bin-major arrays pe
 #define SPMV_BS_DEPTH 4
 #endif
 constexpr int kBsDepth = SPMV_BS_DEPTH;    // pieces per register set of the sum launch (k_bs_sums: two sets in flight)
-// Slack behind the bin-major arrays (d_prod, d_r16 = the accumulator numbers), in entries.  The sum launch's stream issues
+// Slack behind the bin-major arrays (d_prod, d_acc16), in entries.  The sum launch's stream issues
 // two sets of kBsDepth pieces ahead of the trip it consumes, without a branch: a bin of p pieces reads (ceil(p / 2kD) + 1)
 // 2kD pieces from its base, up to 4 kD - 1 pieces past its end -- the last bin's end is the arrays' end (the bins are
 // whole pieces).  The panels' pad slots also store there (entries bm .. bm + kBlk - 1, k_bs_runs).
@@ -1059,153 +1058,14 @@ double binned_tile_nonzeros(const spmv_csr &h, int bin_rows)
     return (double)h.nnz / (nb * np);
 }
 
-
-// the rest of plan_binned for the scattered flavour: bin-major positions, the fill, the accumulators
-static int plan_scatter(spmv_csr &h, PanelPlan &p, int rb, int32_t padded, DevPtr<int32_t> &brow, DevPtr<int32_t> &tiles,
-                        DevPtr<int32_t> &pm, DevPtr<int32_t> &pbase, hipStream_t s)
-{
-    const int nb = p.nblocks, np = p.npanels;
-    int rc;
-    DevPtr<int32_t> bbase, bcnt, total, nlong, stats, run0, offset, first_run;
-    DevPtr<uint32_t> lrow;
-    DevPtr<uint16_t> rowloc, c16, acc;
-    DevPtr<float> pvals, prod;
-    SPMV_HIP_TRY(bbase.alloc((size_t)nb + 1));
-    SPMV_HIP_TRY(bcnt.alloc((size_t)nb));
-    SPMV_HIP_TRY(total.alloc(1));
-    k_bs_counts<<<dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s>>>(nb, np, tiles.get(), bcnt.get(), bbase.get());
-    if ((rc = check_launch("k_bs_counts"))) return rc;
-    if ((rc = exclusive_scan_i32(bbase.get(), nb, total.get(), s))) return rc;
-    int32_t bm = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&bm, total.get(), sizeof bm, hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipMemcpyAsync(bbase.get() + nb, total.get(), sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    SPMV_HIP_TRY(hipStreamSynchronize(s));
-    if (bm < 0 || (int64_t)bm + kBsSlack >= (1ll << 30)) {   // ((bm + kBsSlack) * 4 bytes must fit the buffer descriptors' 32 bits)
-        set_error("spmv_csr_plan(panel, binned, scattered products): %d bins pad nnz %lld beyond 2^30 entries", nb, (long long)h.nnz);
-        return SPMV_ERR_INVALID;
-    }
-    const size_t nslot = (size_t)padded + 8, bslot = (size_t)bm + kBsSlack;      // (entries bm ...: the pad slots of the panels, the read-ahead)
-    SPMV_HIP_TRY(c16.alloc(nslot));
-    SPMV_HIP_TRY(pvals.alloc(nslot));
-    SPMV_HIP_TRY(prod.alloc(bslot));
-    SPMV_HIP_TRY(acc.alloc(bslot));
-    SPMV_HIP_TRY(rowloc.alloc((size_t)h.nnz + 8));
-    SPMV_HIP_TRY(nlong.alloc((size_t)nb));
-    SPMV_HIP_TRY(lrow.alloc((size_t)nb * kPool));
-    SPMV_HIP_TRY(stats.alloc(2));
-    // the runs of the panel-major order (nonempty tiles + one slot per panel for its pad slots)
-    SPMV_HIP_TRY(run0.alloc((size_t)np + 1));
-    k_bs_nruns<<<dim3((unsigned)np), dim3(256), 0, s>>>(nb, np, tiles.get(), run0.get());
-    if ((rc = check_launch("k_bs_nruns"))) return rc;
-    if ((rc = exclusive_scan_i32(run0.get(), np, total.get(), s))) return rc;
-    int32_t nruns = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&nruns, total.get(), sizeof nruns, hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipStreamSynchronize(s));
-    SPMV_HIP_TRY(offset.alloc((size_t)nruns + 1));
-    SPMV_HIP_TRY(first_run.alloc((size_t)padded / kBlk + 1));
-    SPMV_HIP_TRY(hipMemsetAsync(offset.get(), 0, sizeof(int32_t) * ((size_t)nruns + 1), s));
-    SPMV_HIP_TRY(hipMemsetAsync(first_run.get(), 0, sizeof(int32_t) * ((size_t)padded / kBlk + 1), s));
-    SPMV_HIP_TRY(hipMemsetAsync(c16.get(), 0, sizeof(uint16_t) * nslot, s));     // the pad slots of every panel: column 0, value 0 ...
-    SPMV_HIP_TRY(hipMemsetAsync(pvals.get(), 0, sizeof(float) * nslot, s));
-    SPMV_HIP_TRY(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(acc.get()), (unsigned short)(rb + kPool), bslot, s));   // pad entries: the dummy word
-    SPMV_HIP_TRY(hipMemsetAsync(prod.get(), 0, sizeof(float) * bslot, s));
-    SPMV_HIP_TRY(hipMemsetAsync(stats.get(), 0, sizeof(int32_t) * 2, s));
-    int32_t st[2] = {0, 0};
-    if (h.nnz > 0) {
-        if ((rc = panel_rowloc(h, brow.get(), nb, rowloc.get(), s))) return rc;
-        bool one_pass = false;
-        if (const char *e = getenv("SPMV_BS_FILL")) one_pass = atoi(e) == 1;   // (A/B runs: the one-pass fill)
-        if (one_pass) {
-            k_bs_fill<<<dim3((unsigned)((nb + 3) / 4)), dim3(256), sizeof(int) * 4 * ((size_t)np + 256), s>>>(
-                nb, np, brow.get(), h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.get(), tiles.get(), pm.get(), bbase.get(), c16.get(), pvals.get(), acc.get(),
-                (int64_t)nslot, (int64_t)bslot);
-            if ((rc = check_launch("k_bs_fill"))) return rc;
-        } else {
-            const int ng = (np + 63) >> kGroupBits;
-            DevPtr<int32_t> tcol;
-            DevPtr<float> tval;
-            DevPtr<uint16_t> trow;
-            const int32_t *src_col = h.d_col_idx;
-            const float *src_val = h.d_vals;
-            const uint16_t *src_row = rowloc.get();
-            int64_t src_len = h.nnz;                                // (the CSR arrays; the grouped copies: nnz + 8)
-            if (ng > 1) {                                           // (one group: the bins' CSR ranges are grouped as they are)
-                SPMV_HIP_TRY(tcol.alloc((size_t)h.nnz + 8));
-                SPMV_HIP_TRY(tval.alloc((size_t)h.nnz + 8));
-                SPMV_HIP_TRY(trow.alloc((size_t)h.nnz + 8));
-                k_bs_group<<<dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s>>>(nb, np, brow.get(), h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.get(),
-                                                                                 tiles.get(), tcol.get(), tval.get(), trow.get(), h.nnz + 8);
-                if ((rc = check_launch("k_bs_group"))) return rc;
-                src_col = tcol.get(); src_val = tval.get(); src_row = trow.get(); src_len = h.nnz + 8;
-            }
-            const int64_t nitems64 = (int64_t)ng * nb;
-            if (nitems64 > INT_MAX / 2) { set_error("spmv_csr_plan(panel, binned, scattered products): %lld fill items", (long long)nitems64); return SPMV_ERR_INVALID; }
-            const int nitems = (int)nitems64, nwg = (nitems + 3) / 4;
-            k_bs_place<<<dim3(8u * (unsigned)((nwg + 7) / 8)), dim3(256), 0, s>>>(nb, np, nitems, src_col, src_val, src_row, tiles.get(), pm.get(),
-                                                                                 bbase.get(), c16.get(), pvals.get(), acc.get(), src_len, (int64_t)nslot,
-                                                                                 (int64_t)bslot);
-            if ((rc = check_launch("k_bs_place"))) return rc;
-            SPMV_HIP_TRY(hipStreamSynchronize(s));                  // the grouped copies are freed here
-        }
-        k_bs_runs<<<dim3((unsigned)np), dim3(256), 0, s>>>(nb, np, bm, tiles.get(), pm.get(), pbase.get(), bbase.get(), run0.get(), offset.get(), first_run.get(), c16.get());
-        if ((rc = check_launch("k_bs_runs"))) return rc;
-        const size_t lds = sizeof(int) * 2 * (size_t)rb;
-        if (rb == 16384) {
-            static LdsOptIn optin;
-            if ((rc = optin.ensure(reinterpret_cast<const void *>(&k_bs_accs<16384>), h.device, (int)lds))) return rc;
-            k_bs_accs<16384><<<dim3((unsigned)nb), dim3(kWave), lds, s>>>(brow.get(), bbase.get(), bcnt.get(), acc.get(), nlong.get(), lrow.get(), stats.get());
-        } else if (rb == 8192) {
-            static LdsOptIn optin;
-            if ((rc = optin.ensure(reinterpret_cast<const void *>(&k_bs_accs<8192>), h.device, (int)lds))) return rc;
-            k_bs_accs<8192><<<dim3((unsigned)nb), dim3(kWave), lds, s>>>(brow.get(), bbase.get(), bcnt.get(), acc.get(), nlong.get(), lrow.get(), stats.get());
-        } else {
-            k_bs_accs<4096><<<dim3((unsigned)nb), dim3(kWave), lds, s>>>(brow.get(), bbase.get(), bcnt.get(), acc.get(), nlong.get(), lrow.get(), stats.get());
-        }
-        if ((rc = check_launch("k_bs_accs"))) return rc;
-        SPMV_HIP_TRY(hipMemcpyAsync(st, stats.get(), sizeof st, hipMemcpyDeviceToHost, s));
-    } else {
-        SPMV_HIP_TRY(hipMemsetAsync(nlong.get(), 0, sizeof(int32_t) * (size_t)nb, s));
-    }
-    // the product launch: at least two rounds of CUs over the panels that HOLD something (a banded shard fills a fraction of
-    // its panels), their streams shared by `splits` workgroups where they are fewer
-    const int cus = device_cus(h.device);
-    {
-        std::vector<int32_t> hb((size_t)np + 1);
-        SPMV_HIP_TRY(hipMemcpyAsync(hb.data(), pbase.get(), sizeof(int32_t) * ((size_t)np + 1), hipMemcpyDeviceToHost, s));
-        SPMV_HIP_TRY(hipStreamSynchronize(s));
-        int holding = 0;
-        for (int q = 0; q < np; ++q) holding += hb[(size_t)q + 1] > hb[(size_t)q] ? 1 : 0;
-        if (holding < 1) holding = 1;
-        p.splits = holding >= 2 * cus ? 1 : (2 * cus + holding - 1) / holding;
-    }
-    if (const char *e = getenv("SPMV_BINNED_SPLITS")) { const int v = atoi(e); if (v > 0) p.splits = v; }
-    if ((rc = stamp_values(h, s, p.stamp))) return rc;
-    SPMV_HIP_TRY(hipStreamSynchronize(s));   // the temporaries (tiles, pm, rowloc) are freed on return
-    p.padded = padded;
-    p.bm_entries = bm;
-    p.bm_alloc = (int64_t)bslot;
-    p.flagged_tiles = st[0];                 // (bins, in this flavour)
-    p.long_rows = st[1];
-    p.d_c16 = std::move(c16);
-    p.d_pvals = std::move(pvals);
-    p.d_offset = std::move(offset);
-    p.d_first_run = std::move(first_run);
-    p.runs = nruns;
-    p.d_prod = std::move(prod);
-    p.d_r16 = std::move(acc);
-    p.d_pbase = std::move(pbase);
-    p.d_bbase = std::move(bbase);
-    p.d_bcnt = std::move(bcnt);
-    p.d_nlong = std::move(nlong);
-    p.d_lrow = std::move(lrow);
-    p.d_brow = std::move(brow);
-    p.ready = true;
-    return SPMV_OK;
-}
+struct BinTiles {   // what the two flavours' plans start from: the bins, the tiles and the two orders' positions
+    int32_t rb = 0, nb = 0, np = 0, padded = 0;   // rows per bin, bins (0: no rows -- nothing below is made), panels, entries of the panel-major arrays
+    DevPtr<int32_t> brow, tiles, pm, pbase;
+};
 
 // want_rows: 0 = the rule (8192 rows per bin where that still leaves two bins per resident wavefront, else 4096), 4096 | 8192
 // scatter: the flavour whose product launch stores in bin order (thin tiles)
-int plan_binned(spmv_csr &h, PanelPlan &p, int want_rows, bool scatter, hipStream_t s)
+static int bin_tiles(const spmv_csr &h, int want_rows, bool scatter, hipStream_t s, BinTiles &t)
 {
     if (scatter && want_rows != 0 && want_rows != 4096 && want_rows != 8192 && want_rows != 16384) {
         set_error("spmv_csr_plan(panel, binned, scattered products): rows per bin %d (4096, 8192 or 16384)", want_rows);
@@ -1228,18 +1088,9 @@ int plan_binned(spmv_csr &h, PanelPlan &p, int want_rows, bool scatter, hipStrea
     const int cus = device_cus(h.device);
     int rb = want_rows;
     if (rb == 0) rb = scatter ? 8192 : 4096;     // eight wavefronts per CU (8192: four; measured slower at every size tried: DESIGN.md); scattered: fatter tiles win
-    p.binned_mode = true;
-    p.scatter_mode = scatter;
-    p.bin_rows = rb;
-    p.pw_bits = kPwBits;
-    p.npanels = np;
-    p.splits = 1;
-    if (h.rows == 0) {
-        p.stamp.gen = h.values_gen;
-        p.stamp.have_sum = false;
-        p.ready = true;
-        return SPMV_OK;
-    }
+    t.rb = rb;
+    t.np = np;
+    if (h.rows == 0) return SPMV_OK;
     // bins: equal nonzero counts, at most rb rows, a whole number of rounds of the wavefronts the sum launch keeps resident
     // (wavefronts that carry equal loads finish together; the cuts aim at 0.8 rb rows so that hardly any needs splitting)
     const int64_t slots = (int64_t)cus * ((rb + kSpare + kWave) * 4 * kSumWaves <= 80 * 1024 ? 2 : 1) * kSumWaves;
@@ -1254,45 +1105,190 @@ int plan_binned(spmv_csr &h, PanelPlan &p, int want_rows, bool scatter, hipStrea
         if (const char *e = getenv("SPMV_BS_BINS")) { const long long v = atoll(e); if (v > 0) nb0 = v; }   // (A/B runs)
     }
     if (nb0 > h.rows) nb0 = h.rows;
-    DevPtr<int32_t> brow;
-    int rc = panel_row_blocks(h, nb0, rb, s, brow, &p.nblocks);
+    int rc = panel_row_blocks(h, nb0, rb, s, t.brow, &t.nb);
     if (rc) return rc;
-    const int nb = p.nblocks;
+    const int nb = t.nb;
     if ((int64_t)nb * (np + 1) > (int64_t)INT_MAX / 2) {
         set_error("spmv_csr_plan(panel, binned): %d bins x %d panels is more tiles than the tables hold", nb, np);
         return SPMV_ERR_INVALID;
     }
-    DevPtr<int32_t> tiles, pm, pbase, total;
-    DevPtr<uint16_t> rowloc, c16, r16;
-    DevPtr<float> pvals, prod;
-    SPMV_HIP_TRY(tiles.alloc((size_t)nb * (size_t)(np + 1)));
-    SPMV_HIP_TRY(pm.alloc((size_t)nb * (size_t)np));
-    SPMV_HIP_TRY(pbase.alloc((size_t)np + 1));
+    DevPtr<int32_t> total;
+    SPMV_HIP_TRY(t.tiles.alloc((size_t)nb * (size_t)(np + 1)));
+    SPMV_HIP_TRY(t.pm.alloc((size_t)nb * (size_t)np));
+    SPMV_HIP_TRY(t.pbase.alloc((size_t)np + 1));
     SPMV_HIP_TRY(total.alloc(1));
-    if ((rc = panel_tile_ptr(h, brow.get(), nb, kPwBits, np, tiles.get(), s))) return rc;
-    k_bin_panel_totals<<<dim3((unsigned)np), dim3(256), 0, s>>>(nb, np, scatter ? kBlk : 8, tiles.get(), pbase.get());
+    if ((rc = panel_tile_ptr(h, t.brow.get(), nb, kPwBits, np, t.tiles.get(), s))) return rc;
+    k_bin_panel_totals<<<dim3((unsigned)np), dim3(256), 0, s>>>(nb, np, scatter ? kBlk : 8, t.tiles.get(), t.pbase.get());
     if ((rc = check_launch("k_bin_panel_totals"))) return rc;
-    if ((rc = exclusive_scan_i32(pbase.get(), np, total.get(), s))) return rc;
-    int32_t padded = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&padded, total.get(), sizeof padded, hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipMemcpyAsync(pbase.get() + np, total.get(), sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    SPMV_HIP_TRY(hipStreamSynchronize(s));
-    k_bin_pm<<<dim3((unsigned)np), dim3(256), 0, s>>>(nb, np, tiles.get(), pbase.get(), pm.get());
-    if ((rc = check_launch("k_bin_pm"))) return rc;
-    if (scatter) return plan_scatter(h, p, rb, padded, brow, tiles, pm, pbase, s);
-    const size_t nslot = (size_t)padded + kBinSlack;
-    SPMV_HIP_TRY(c16.alloc(nslot));
-    SPMV_HIP_TRY(pvals.alloc(nslot));
-    SPMV_HIP_TRY(prod.alloc(nslot));
-    SPMV_HIP_TRY(r16.alloc((size_t)h.nnz + kBinSlack));
-    SPMV_HIP_TRY(hipMemsetAsync(r16.get() + h.nnz, 0, sizeof(uint16_t) * kBinSlack, s));
+    if ((rc = scan_offsets_i32(t.pbase.get(), np, total.get(), true, s, &t.padded))) return rc;
+    k_bin_pm<<<dim3((unsigned)np), dim3(256), 0, s>>>(nb, np, t.tiles.get(), t.pbase.get(), t.pm.get());
+    return check_launch("k_bin_pm");
+}
+
+// the scattered flavour: bin-major positions, the fill, the accumulators
+int plan_scatter(spmv_csr &h, ScatteredPlan &p, int want_rows, hipStream_t s)
+{
+    BinTiles t;
+    int rc = bin_tiles(h, want_rows, true, s, t);
+    if (rc) return rc;
+    const int rb = p.bin_rows = t.rb, nb = p.nblocks = t.nb, np = p.npanels = t.np, padded = t.padded;
+    if (h.rows == 0) return SPMV_OK;
+    DevPtr<int32_t> total, stats, run0;
+    DevPtr<uint16_t> rowloc;
+    SPMV_HIP_TRY(p.d_bbase.alloc((size_t)nb + 1));
+    SPMV_HIP_TRY(p.d_bcnt.alloc((size_t)nb));
+    SPMV_HIP_TRY(total.alloc(1));
+    k_bs_counts<<<dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s>>>(nb, np, t.tiles.get(), p.d_bcnt.get(), p.d_bbase.get());
+    if ((rc = check_launch("k_bs_counts"))) return rc;
+    int32_t bm = 0;
+    if ((rc = scan_offsets_i32(p.d_bbase.get(), nb, total.get(), true, s, &bm))) return rc;
+    if (bm < 0 || (int64_t)bm + kBsSlack >= (1ll << 30)) {   // ((bm + kBsSlack) * 4 bytes must fit the buffer descriptors' 32 bits)
+        set_error("spmv_csr_plan(panel, binned, scattered products): %d bins pad nnz %lld beyond 2^30 entries", nb, (long long)h.nnz);
+        return SPMV_ERR_INVALID;
+    }
+    const size_t nslot = (size_t)padded + 8, bslot = (size_t)bm + kBsSlack;      // (entries bm ...: the pad slots of the panels, the read-ahead)
+    SPMV_HIP_TRY(p.d_c16.alloc(nslot));
+    SPMV_HIP_TRY(p.d_pvals.alloc(nslot));
+    SPMV_HIP_TRY(p.d_prod.alloc(bslot));
+    SPMV_HIP_TRY(p.d_acc16.alloc(bslot));
     SPMV_HIP_TRY(rowloc.alloc((size_t)h.nnz + 8));
-    SPMV_HIP_TRY(hipMemsetAsync(c16.get(), 0, sizeof(uint16_t) * nslot, s));     // (the pad slots of every panel: column 0, value 0)
-    SPMV_HIP_TRY(hipMemsetAsync(pvals.get(), 0, sizeof(float) * nslot, s));
+    SPMV_HIP_TRY(p.d_nlong.alloc((size_t)nb));
+    SPMV_HIP_TRY(p.d_pool_rows.alloc((size_t)nb * kPool));
+    SPMV_HIP_TRY(stats.alloc(2));
+    // the runs of the panel-major order (nonempty tiles + one slot per panel for its pad slots)
+    SPMV_HIP_TRY(run0.alloc((size_t)np + 1));
+    k_bs_nruns<<<dim3((unsigned)np), dim3(256), 0, s>>>(nb, np, t.tiles.get(), run0.get());
+    if ((rc = check_launch("k_bs_nruns"))) return rc;
+    int32_t nruns = 0;
+    if ((rc = scan_offsets_i32(run0.get(), np, total.get(), false, s, &nruns))) return rc;
+    SPMV_HIP_TRY(p.d_offset.alloc((size_t)nruns + 1));
+    SPMV_HIP_TRY(p.d_first_run.alloc((size_t)padded / kBlk + 1));
+    SPMV_HIP_TRY(hipMemsetAsync(p.d_offset.get(), 0, sizeof(int32_t) * ((size_t)nruns + 1), s));
+    SPMV_HIP_TRY(hipMemsetAsync(p.d_first_run.get(), 0, sizeof(int32_t) * ((size_t)padded / kBlk + 1), s));
+    SPMV_HIP_TRY(hipMemsetAsync(p.d_c16.get(), 0, sizeof(uint16_t) * nslot, s));     // the pad slots of every panel: column 0, value 0 ...
+    SPMV_HIP_TRY(hipMemsetAsync(p.d_pvals.get(), 0, sizeof(float) * nslot, s));
+    SPMV_HIP_TRY(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(p.d_acc16.get()), (unsigned short)(rb + kPool), bslot, s));   // pad entries: the dummy word
+    SPMV_HIP_TRY(hipMemsetAsync(p.d_prod.get(), 0, sizeof(float) * bslot, s));
+    SPMV_HIP_TRY(hipMemsetAsync(stats.get(), 0, sizeof(int32_t) * 2, s));
+    int32_t st[2] = {0, 0};
     if (h.nnz > 0) {
-        if ((rc = panel_rowloc(h, brow.get(), nb, rowloc.get(), s))) return rc;
+        if ((rc = panel_rowloc(h, t.brow.get(), nb, rowloc.get(), s))) return rc;
+        bool one_pass = false;
+        if (const char *e = getenv("SPMV_BS_FILL")) one_pass = atoi(e) == 1;   // (A/B runs: the one-pass fill)
+        if (one_pass) {
+            k_bs_fill<<<dim3((unsigned)((nb + 3) / 4)), dim3(256), sizeof(int) * 4 * ((size_t)np + 256), s>>>(
+                nb, np, t.brow.get(), h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.get(), t.tiles.get(), t.pm.get(), p.d_bbase.get(), p.d_c16.get(), p.d_pvals.get(), p.d_acc16.get(),
+                (int64_t)nslot, (int64_t)bslot);
+            if ((rc = check_launch("k_bs_fill"))) return rc;
+        } else {
+            const int ng = (np + 63) >> kGroupBits;
+            DevPtr<int32_t> tcol;
+            DevPtr<float> tval;
+            DevPtr<uint16_t> trow;
+            const int32_t *src_col = h.d_col_idx;
+            const float *src_val = h.d_vals;
+            const uint16_t *src_row = rowloc.get();
+            int64_t src_len = h.nnz;                                // (the CSR arrays; the grouped copies: nnz + 8)
+            if (ng > 1) {                                           // (one group: the bins' CSR ranges are grouped as they are)
+                SPMV_HIP_TRY(tcol.alloc((size_t)h.nnz + 8));
+                SPMV_HIP_TRY(tval.alloc((size_t)h.nnz + 8));
+                SPMV_HIP_TRY(trow.alloc((size_t)h.nnz + 8));
+                k_bs_group<<<dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s>>>(nb, np, t.brow.get(), h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.get(),
+                                                                                 t.tiles.get(), tcol.get(), tval.get(), trow.get(), h.nnz + 8);
+                if ((rc = check_launch("k_bs_group"))) return rc;
+                src_col = tcol.get(); src_val = tval.get(); src_row = trow.get(); src_len = h.nnz + 8;
+            }
+            const int64_t nitems64 = (int64_t)ng * nb;
+            if (nitems64 > INT_MAX / 2) { set_error("spmv_csr_plan(panel, binned, scattered products): %lld fill items", (long long)nitems64); return SPMV_ERR_INVALID; }
+            const int nitems = (int)nitems64, nwg = (nitems + 3) / 4;
+            k_bs_place<<<dim3(8u * (unsigned)((nwg + 7) / 8)), dim3(256), 0, s>>>(nb, np, nitems, src_col, src_val, src_row, t.tiles.get(), t.pm.get(),
+                                                                                 p.d_bbase.get(), p.d_c16.get(), p.d_pvals.get(), p.d_acc16.get(), src_len, (int64_t)nslot,
+                                                                                 (int64_t)bslot);
+            if ((rc = check_launch("k_bs_place"))) return rc;
+            SPMV_HIP_TRY(hipStreamSynchronize(s));                  // the grouped copies are freed here
+        }
+        k_bs_runs<<<dim3((unsigned)np), dim3(256), 0, s>>>(nb, np, bm, t.tiles.get(), t.pm.get(), t.pbase.get(), p.d_bbase.get(), run0.get(), p.d_offset.get(), p.d_first_run.get(), p.d_c16.get());
+        if ((rc = check_launch("k_bs_runs"))) return rc;
+        const size_t lds = sizeof(int) * 2 * (size_t)rb;
+        if (rb == 16384) {
+            static LdsOptIn optin;
+            if ((rc = optin.ensure(reinterpret_cast<const void *>(&k_bs_accs<16384>), h.device, (int)lds))) return rc;
+            k_bs_accs<16384><<<dim3((unsigned)nb), dim3(kWave), lds, s>>>(t.brow.get(), p.d_bbase.get(), p.d_bcnt.get(), p.d_acc16.get(), p.d_nlong.get(), p.d_pool_rows.get(), stats.get());
+        } else if (rb == 8192) {
+            static LdsOptIn optin;
+            if ((rc = optin.ensure(reinterpret_cast<const void *>(&k_bs_accs<8192>), h.device, (int)lds))) return rc;
+            k_bs_accs<8192><<<dim3((unsigned)nb), dim3(kWave), lds, s>>>(t.brow.get(), p.d_bbase.get(), p.d_bcnt.get(), p.d_acc16.get(), p.d_nlong.get(), p.d_pool_rows.get(), stats.get());
+        } else {
+            k_bs_accs<4096><<<dim3((unsigned)nb), dim3(kWave), lds, s>>>(t.brow.get(), p.d_bbase.get(), p.d_bcnt.get(), p.d_acc16.get(), p.d_nlong.get(), p.d_pool_rows.get(), stats.get());
+        }
+        if ((rc = check_launch("k_bs_accs"))) return rc;
+        SPMV_HIP_TRY(hipMemcpyAsync(st, stats.get(), sizeof st, hipMemcpyDeviceToHost, s));
+    } else {
+        SPMV_HIP_TRY(hipMemsetAsync(p.d_nlong.get(), 0, sizeof(int32_t) * (size_t)nb, s));
+    }
+    // the product launch: at least two rounds of CUs over the panels that HOLD something (a banded shard fills a fraction of
+    // its panels), their streams shared by `splits` workgroups where they are fewer
+    const int cus = device_cus(h.device);
+    {
+        std::vector<int32_t> hb((size_t)np + 1);
+        SPMV_HIP_TRY(hipMemcpyAsync(hb.data(), t.pbase.get(), sizeof(int32_t) * ((size_t)np + 1), hipMemcpyDeviceToHost, s));
+        SPMV_HIP_TRY(hipStreamSynchronize(s));
+        int holding = 0;
+        for (int q = 0; q < np; ++q) holding += hb[(size_t)q + 1] > hb[(size_t)q] ? 1 : 0;
+        if (holding < 1) holding = 1;
+        p.splits = holding >= 2 * cus ? 1 : (2 * cus + holding - 1) / holding;
+    }
+    if (const char *e = getenv("SPMV_BINNED_SPLITS")) { const int v = atoi(e); if (v > 0) p.splits = v; }
+    SPMV_HIP_TRY(hipStreamSynchronize(s));   // the temporaries (tiles, pm, rowloc) are freed on return
+    p.padded = padded;
+    p.bm_entries = bm;
+    p.bm_alloc = (int64_t)bslot;
+    p.flagged_bins = st[0];
+    p.long_rows = st[1];
+    p.runs = nruns;
+    p.d_pbase = std::move(t.pbase);
+    p.d_brow = std::move(t.brow);
+    return SPMV_OK;
+}
+
+void scatter_params(const ScatteredPlan &p, int32_t params[8]) { params[4] = p.bin_rows; params[5] = 0; params[6] = 5; }
+// panel-major: column 2 + value 4, an offset per run; bin-major: product 4 + accumulator 2; the lists
+int64_t scatter_plan_bytes(const ScatteredPlan &p, int64_t)
+{
+    return p.padded * (2 + 4) + p.padded / 512 * 4 + p.runs * 4 + p.bm_entries * (4 + 2) + (int64_t)p.nblocks * (1024 * 4 + 16) + ((int64_t)p.npanels + 1) * 4;
+}
+void scatter_describe(const ScatteredPlan &p, const spmv_csr &h, char *buf, int n)
+{
+    snprintf(buf, (size_t)n, "binned scattered_products bins=%d rows_per_bin=%d panels=%d panel_columns=%d nonzeros_per_tile=%.1f rows_with_spare_sums=%d flagged_bins=%d product_workgroups_per_panel=%d padded=%lld bin_entries=%lld",
+             p.nblocks, p.bin_rows, p.npanels, kPw, p.nblocks ? (double)h.nnz / ((double)p.nblocks * p.npanels) : 0.0, p.long_rows, p.flagged_bins,
+             p.splits, (long long)p.padded, (long long)p.bm_entries);
+}
+
+// the fetching flavour (mode 4)
+int plan_binned(spmv_csr &h, BinnedPlan &p, int want_rows, hipStream_t s)
+{
+    BinTiles t;
+    int rc = bin_tiles(h, want_rows, false, s, t);
+    if (rc) return rc;
+    const int rb = p.bin_rows = t.rb, nb = p.nblocks = t.nb, np = p.npanels = t.np, padded = t.padded;
+    if (h.rows == 0) return SPMV_OK;
+    const int cus = device_cus(h.device);
+    DevPtr<int32_t> total;
+    DevPtr<uint16_t> rowloc;
+    SPMV_HIP_TRY(total.alloc(1));
+    const size_t nslot = (size_t)padded + kBinSlack;
+    SPMV_HIP_TRY(p.d_c16.alloc(nslot));
+    SPMV_HIP_TRY(p.d_pvals.alloc(nslot));
+    SPMV_HIP_TRY(p.d_prod.alloc(nslot));
+    SPMV_HIP_TRY(p.d_r16.alloc((size_t)h.nnz + kBinSlack));
+    SPMV_HIP_TRY(hipMemsetAsync(p.d_r16.get() + h.nnz, 0, sizeof(uint16_t) * kBinSlack, s));
+    SPMV_HIP_TRY(rowloc.alloc((size_t)h.nnz + 8));
+    SPMV_HIP_TRY(hipMemsetAsync(p.d_c16.get(), 0, sizeof(uint16_t) * nslot, s));     // (the pad slots of every panel: column 0, value 0)
+    SPMV_HIP_TRY(hipMemsetAsync(p.d_pvals.get(), 0, sizeof(float) * nslot, s));
+    if (h.nnz > 0) {
+        if ((rc = panel_rowloc(h, t.brow.get(), nb, rowloc.get(), s))) return rc;
         k_bin_fill<<<dim3((unsigned)((nb + 3) / 4)), dim3(256), sizeof(int) * 4 * ((size_t)np + 256), s>>>(
-            nb, np, brow.get(), h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.get(), tiles.get(), pm.get(), c16.get(), pvals.get(), r16.get());
+            nb, np, t.brow.get(), h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.get(), t.tiles.get(), t.pm.get(), p.d_c16.get(), p.d_pvals.get(), p.d_r16.get());
         if ((rc = check_launch("k_bin_fill"))) return rc;
     }
     // the product launch: every panel's stream shared by `splits` workgroups so that the launch is at least two rounds of CUs
@@ -1303,55 +1299,52 @@ int plan_binned(spmv_csr &h, PanelPlan &p, int want_rows, bool scatter, hipStrea
     if (const char *e = getenv("SPMV_BINNED_WIDE")) { if (*e) p.wide_pieces = atoi(e) != 0; }
     // rows that hold more products of a tile than a lane takes: spare sums (k_bin_runs); bins with too many of them: the fold
     int32_t flagged = 0, nlong_total = 0;
-    DevPtr<int32_t> maxrun, spare, lptr, lcnt;
-    DevPtr<uint32_t> lrow;
+    DevPtr<int32_t> maxrun, spare;
     const int e = p.wide_pieces ? 4 : 2;
-    SPMV_HIP_TRY(lptr.alloc((size_t)nb + 1));
-    SPMV_HIP_TRY(hipMemsetAsync(lptr.get(), 0, sizeof(int32_t) * ((size_t)nb + 1), s));
+    SPMV_HIP_TRY(p.d_lptr.alloc((size_t)nb + 1));
+    SPMV_HIP_TRY(hipMemsetAsync(p.d_lptr.get(), 0, sizeof(int32_t) * ((size_t)nb + 1), s));
     if (h.nnz > 0) {
         SPMV_HIP_TRY(maxrun.alloc((size_t)h.rows));
         SPMV_HIP_TRY(spare.alloc((size_t)nb));
         SPMV_HIP_TRY(hipMemsetAsync(maxrun.get(), 0, sizeof(int32_t) * (size_t)h.rows, s));
-        k_bin_runs<<<dim3((unsigned)nb), dim3(256), 0, s>>>(np, e, brow.get(), tiles.get(), r16.get(), maxrun.get());
+        k_bin_runs<<<dim3((unsigned)nb), dim3(256), 0, s>>>(np, e, t.brow.get(), t.tiles.get(), p.d_r16.get(), maxrun.get());
         if ((rc = check_launch("k_bin_runs"))) return rc;
-        k_bin_spare<<<dim3((unsigned)nb), dim3(256), 0, s>>>(e, brow.get(), maxrun.get(), spare.get(), lptr.get());
+        k_bin_spare<<<dim3((unsigned)nb), dim3(256), 0, s>>>(e, t.brow.get(), maxrun.get(), spare.get(), p.d_lptr.get());
         if ((rc = check_launch("k_bin_spare"))) return rc;
-        if ((rc = exclusive_scan_i32(lptr.get(), nb, total.get(), s))) return rc;
-        SPMV_HIP_TRY(hipMemcpyAsync(&nlong_total, total.get(), sizeof nlong_total, hipMemcpyDeviceToHost, s));
-        SPMV_HIP_TRY(hipMemcpyAsync(lptr.get() + nb, total.get(), sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-        SPMV_HIP_TRY(hipStreamSynchronize(s));
+        if ((rc = scan_offsets_i32(p.d_lptr.get(), nb, total.get(), true, s, &nlong_total))) return rc;
     }
-    SPMV_HIP_TRY(lrow.alloc((size_t)nlong_total + 1));
-    SPMV_HIP_TRY(lcnt.alloc((size_t)nlong_total + 1));
+    SPMV_HIP_TRY(p.d_lrow.alloc((size_t)nlong_total + 1));
+    SPMV_HIP_TRY(p.d_lcnt.alloc((size_t)nlong_total + 1));
     if (h.nnz > 0) {
         SPMV_HIP_TRY(hipMemsetAsync(total.get(), 0, sizeof(int32_t), s));
-        k_bin_rewrite<<<dim3((unsigned)nb), dim3(256), 0, s>>>(np, e, rb, brow.get(), tiles.get(), maxrun.get(), spare.get(), lptr.get(), r16.get(), pm.get(), lrow.get(),
-                                                               lcnt.get(), total.get());
+        k_bin_rewrite<<<dim3((unsigned)nb), dim3(256), 0, s>>>(np, e, rb, t.brow.get(), t.tiles.get(), maxrun.get(), spare.get(), p.d_lptr.get(), p.d_r16.get(), t.pm.get(), p.d_lrow.get(),
+                                                               p.d_lcnt.get(), total.get());
         if ((rc = check_launch("k_bin_rewrite"))) return rc;
         SPMV_HIP_TRY(hipMemcpyAsync(&flagged, total.get(), sizeof flagged, hipMemcpyDeviceToHost, s));
     }
-    if ((rc = stamp_values(h, s, p.stamp))) return rc;
     SPMV_HIP_TRY(hipStreamSynchronize(s));   // the temporaries are freed on return
     p.padded = padded;
     p.flagged_tiles = flagged;
     p.long_rows = nlong_total;
-    p.d_lptr = std::move(lptr);
-    p.d_lrow = std::move(lrow);
-    p.d_lcnt = std::move(lcnt);
-    p.d_c16 = std::move(c16);
-    p.d_pvals = std::move(pvals);
-    p.d_prod = std::move(prod);
-    p.d_r16 = std::move(r16);
-    p.d_pm = std::move(pm);
-    p.d_pbase = std::move(pbase);
-    p.d_tile_ptr = std::move(tiles);
-    p.d_brow = std::move(brow);
-    p.ready = true;
+    p.d_pm = std::move(t.pm);
+    p.d_pbase = std::move(t.pbase);
+    p.d_tile_ptr = std::move(t.tiles);
+    p.d_brow = std::move(t.brow);
     return SPMV_OK;
 }
 
+void binned_params(const BinnedPlan &p, int32_t params[8]) { params[4] = p.bin_rows; params[5] = 0; params[6] = 4; }
+// two tables per tile, 16-bit columns and rows, the products written and read back; pvals REPLACES vals
+int64_t binned_plan_bytes(const BinnedPlan &p, int64_t nnz) { return (int64_t)p.nblocks * (2 * (int64_t)p.npanels + 2) * 4 + p.padded * (2 + 4 + 4) + nnz * 2; }
+void binned_describe(const BinnedPlan &p, const spmv_csr &h, char *buf, int n)
+{
+    snprintf(buf, (size_t)n, "binned bins=%d rows_per_bin=%d panels=%d panel_columns=%d nonzeros_per_tile=%.1f products_per_lane=%d long_rows=%d flagged_tiles=%d product_workgroups_per_panel=%d padded=%lld",
+             p.nblocks, p.bin_rows, p.npanels, kPw, p.nblocks ? (double)h.nnz / ((double)p.nblocks * p.npanels) : 0.0, p.wide_pieces ? 4 : 2,
+             p.long_rows, p.flagged_tiles, p.splits, (long long)p.padded);
+}
+
 template <int RB, int E>
-static int launch_sums_e(const spmv_csr &h, const PanelPlan &p, float *y, hipStream_t s)
+static int launch_sums_e(const spmv_csr &h, const BinnedPlan &p, float *y, hipStream_t s)
 {
     const size_t lds = sizeof(float) * (size_t)(RB + kSpare + kWave) * kSumWaves;
     const dim3 grid((unsigned)((p.nblocks + kSumWaves - 1) / kSumWaves)), block(kSumWaves * kWave);
@@ -1362,44 +1355,43 @@ static int launch_sums_e(const spmv_csr &h, const PanelPlan &p, float *y, hipStr
     return check_launch("k_bin_sums");
 }
 template <int RB>
-static int launch_sums(const spmv_csr &h, const PanelPlan &p, float *y, hipStream_t s)
+static int launch_sums(const spmv_csr &h, const BinnedPlan &p, float *y, hipStream_t s)
 {
     return p.wide_pieces ? launch_sums_e<RB, 4>(h, p, y, s) : launch_sums_e<RB, 2>(h, p, y, s);
 }
 
 template <int RB>
-static int launch_bs_sums(const spmv_csr &h, const PanelPlan &p, float *y, hipStream_t s)
+static int launch_bs_sums(const spmv_csr &h, const ScatteredPlan &p, float *y, hipStream_t s)
 {
     const size_t lds = sizeof(float) * (size_t)(RB + kPool + kWave);
     static LdsOptIn optin;
     if (int rc = optin.ensure(reinterpret_cast<const void *>(&k_bs_sums<RB>), h.device, (int)lds)) return rc;
-    k_bs_sums<RB><<<dim3((unsigned)p.nblocks), dim3(kWave), lds, s>>>(p.d_brow, p.d_bbase, p.d_bcnt, p.d_r16, p.d_prod, p.d_nlong, p.d_lrow, y,
+    k_bs_sums<RB><<<dim3((unsigned)p.nblocks), dim3(kWave), lds, s>>>(p.d_brow, p.d_bbase, p.d_bcnt, p.d_acc16, p.d_prod, p.d_nlong, p.d_pool_rows, y,
                                                                       (uint32_t)(p.bm_alloc * 4), (uint32_t)(p.bm_alloc * 2));
     return check_launch("k_bs_sums");
 }
 
-int launch_binned(const spmv_csr &h, const PanelPlan &p, const float *x, float *y, hipStream_t s)
+int launch_scatter(const spmv_csr &h, const ScatteredPlan &p, const float *x, float *y, hipStream_t s)
 {
     if (p.nblocks == 0) return SPMV_OK;   // no rows
-    if (p.scatter_mode) {
-        const size_t lds = sizeof(float) * (size_t)kPw;
-        static LdsOptIn optin;
-        if (int rc = optin.ensure(reinterpret_cast<const void *>(&k_bs_products), h.device, (int)lds)) return rc;
-        const unsigned grid = p.splits == 1 ? 256u * (unsigned)((p.npanels + 255) / 256) : (unsigned)(p.npanels * p.splits);
-        k_bs_products<<<dim3(grid), dim3(kProdThreads), lds, s>>>(p.splits, p.npanels, h.cols, p.d_pbase, p.d_c16,
-                                                                                              p.d_pvals, p.d_first_run, p.d_offset, x, p.d_prod,
-                                                                                              p.padded + 8, p.bm_alloc);
-        if (int rc = check_launch("k_bs_products")) return rc;
-        return p.bin_rows == 16384 ? launch_bs_sums<16384>(h, p, y, s) : p.bin_rows == 8192 ? launch_bs_sums<8192>(h, p, y, s) : launch_bs_sums<4096>(h, p, y, s);
-    }
-    {
-        const size_t lds = sizeof(float) * (size_t)kPw;
-        static LdsOptIn optin;
-        if (int rc = optin.ensure(reinterpret_cast<const void *>(&k_bin_products), h.device, (int)lds)) return rc;
-        k_bin_products<<<dim3((unsigned)(p.npanels * p.splits)), dim3(kProdThreads), lds, s>>>(p.splits, h.cols, p.d_pbase, p.d_c16,
-                                                                                               p.d_pvals, x, p.d_prod);
-        if (int rc = check_launch("k_bin_products")) return rc;
-    }
+    const size_t lds = sizeof(float) * (size_t)kPw;
+    static LdsOptIn optin;
+    if (int rc = optin.ensure(reinterpret_cast<const void *>(&k_bs_products), h.device, (int)lds)) return rc;
+    const unsigned grid = p.splits == 1 ? 256u * (unsigned)((p.npanels + 255) / 256) : (unsigned)(p.npanels * p.splits);
+    k_bs_products<<<dim3(grid), dim3(kProdThreads), lds, s>>>(p.splits, p.npanels, h.cols, p.d_pbase, p.d_c16, p.d_pvals, p.d_first_run, p.d_offset,
+                                                              x, p.d_prod, p.padded + 8, p.bm_alloc);
+    if (int rc = check_launch("k_bs_products")) return rc;
+    return p.bin_rows == 16384 ? launch_bs_sums<16384>(h, p, y, s) : p.bin_rows == 8192 ? launch_bs_sums<8192>(h, p, y, s) : launch_bs_sums<4096>(h, p, y, s);
+}
+
+int launch_binned(const spmv_csr &h, const BinnedPlan &p, const float *x, float *y, hipStream_t s)
+{
+    if (p.nblocks == 0) return SPMV_OK;   // no rows
+    const size_t lds = sizeof(float) * (size_t)kPw;
+    static LdsOptIn optin;
+    if (int rc = optin.ensure(reinterpret_cast<const void *>(&k_bin_products), h.device, (int)lds)) return rc;
+    k_bin_products<<<dim3((unsigned)(p.npanels * p.splits)), dim3(kProdThreads), lds, s>>>(p.splits, h.cols, p.d_pbase, p.d_c16, p.d_pvals, x, p.d_prod);
+    if (int rc = check_launch("k_bin_products")) return rc;
     return p.bin_rows == 8192 ? launch_sums<8192>(h, p, y, s) : p.bin_rows == 4096 ? launch_sums<4096>(h, p, y, s) :
            p.bin_rows == 2048 ? launch_sums<2048>(h, p, y, s) : launch_sums<1024>(h, p, y, s);
 }

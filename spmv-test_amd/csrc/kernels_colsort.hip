@@ -15,7 +15,7 @@
 // Same role as kernels_panel.hip -- the reference's tiled format (TCSRMatrix src/tcsr.cpp:5-38 + csr_tiling_kernel
 // src/kernels/csr_tiling.cu:24-114: a tile of the matrix against a tile of x in shared memory) at sparse scale.
 //
-// Layout (PanelPlan, sorted_mode):
+// Layout (SortedBlocksPlan):
 //   rows are cut into blocks of <= 4096 rows with equal nonzero counts (brow[]);
 //   a block's nonzeros, stably sorted by 128-byte line of x, are dealt into GROUPS of 64 with distinct rows: a nonzero
 //   whose row is already in the group waits for the next one (at most 16 wait; more go to the block's "flagged" tail,
@@ -724,62 +724,56 @@ __global__ void k_cb_probe_wide(int nb, int64_t rows, const int32_t *__restrict_
 }
 
 // The layout for blocks of at most rows_cap rows (4096 | 8192).  Fills p (brow, packed, pvals, units, tail rows,
-// statistics); on failure p owns nothing new.
-static int build_colsort(spmv_csr &h, PanelPlan &p, int rows_cap, hipStream_t s)
+// statistics); on failure the caller drops p.
+static int build_colsort(spmv_csr &h, SortedBlocksPlan &p, int rows_cap, hipStream_t s)
 {
     int rc;
     // blocks of rows_cap rows where the rows are equally long (config 2: 256 blocks of 4096 for 256 CUs); where equal
     // nonzero counts make many cuts longer than that, a lower target so that few cuts have to be split in two
-    DevPtr<int32_t> brow;
     int64_t nb0 = (h.rows + rows_cap - 1) / rows_cap;
-    if ((rc = panel_row_blocks(h, nb0, rows_cap, s, brow, &p.nblocks))) return rc;
+    if ((rc = panel_row_blocks(h, nb0, rows_cap, s, p.d_brow, &p.nblocks))) return rc;
     if ((int64_t)p.nblocks * 100 > nb0 * 101) {
-        (void)brow.reset();
         nb0 = (h.rows + rows_cap * 15 / 16 - 1) / (rows_cap * 15 / 16);
-        if ((rc = panel_row_blocks(h, nb0, rows_cap, s, brow, &p.nblocks))) return rc;
+        if ((rc = panel_row_blocks(h, nb0, rows_cap, s, p.d_brow, &p.nblocks))) return rc;
     }
-    DevPtr<int32_t> ubeg, total, usimple, uend, nshort, fail;
+    DevPtr<int32_t> total, nshort, fail;
     DevPtr<unsigned long long> stats;
-    SPMV_HIP_TRY(ubeg.alloc((size_t)p.nblocks + 1));
+    SPMV_HIP_TRY(p.d_ubeg.alloc((size_t)p.nblocks + 1));
     SPMV_HIP_TRY(total.alloc(1));
-    SPMV_HIP_TRY(usimple.alloc((size_t)p.nblocks));
-    SPMV_HIP_TRY(uend.alloc((size_t)p.nblocks));
+    SPMV_HIP_TRY(p.d_usimple.alloc((size_t)p.nblocks));
+    SPMV_HIP_TRY(p.d_uend.alloc((size_t)p.nblocks));
     SPMV_HIP_TRY(nshort.alloc((size_t)p.nblocks));
     SPMV_HIP_TRY(fail.alloc(1));
     SPMV_HIP_TRY(stats.alloc(3));
     SPMV_HIP_TRY(hipMemsetAsync(fail.get(), 0, sizeof(int32_t), s));
     SPMV_HIP_TRY(hipMemsetAsync(stats.get(), 0, 3 * sizeof(unsigned long long), s));
     const unsigned gb = (unsigned)((p.nblocks + 255) / 256);
-    k_cb_units<<<dim3(gb), dim3(256), 0, s>>>(p.nblocks, brow.get(), h.d_row_ptr, ubeg.get());
+    k_cb_units<<<dim3(gb), dim3(256), 0, s>>>(p.nblocks, p.d_brow.get(), h.d_row_ptr, p.d_ubeg.get());
     if ((rc = check_launch("k_cb_units"))) return rc;
-    if ((rc = exclusive_scan_i32(ubeg.get(), p.nblocks, total.get(), s))) return rc;
     int32_t units = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&units, total.get(), sizeof units, hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipMemcpyAsync(ubeg.get() + p.nblocks, total.get(), sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    SPMV_HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = scan_offsets_i32(p.d_ubeg.get(), p.nblocks, total.get(), true, s, &units))) return rc;
     p.units = units;
     const size_t slots = (size_t)units * kCbUnit;
-    DevPtr<uint32_t> packed;
-    DevPtr<float> pvals, t_val;
-    DevPtr<int32_t> ubase, t_col;
+    DevPtr<float> t_val;
+    DevPtr<int32_t> t_col;
     DevPtr<uint16_t> rowloc, t_row, o_row;
-    SPMV_HIP_TRY(packed.alloc(slots));
-    SPMV_HIP_TRY(pvals.alloc(slots));
-    SPMV_HIP_TRY(ubase.alloc((size_t)units));
+    SPMV_HIP_TRY(p.d_packed.alloc(slots));
+    SPMV_HIP_TRY(p.d_pvals.alloc(slots));
+    SPMV_HIP_TRY(p.d_ubase.alloc((size_t)units));
     SPMV_HIP_TRY(o_row.alloc(slots));
     SPMV_HIP_TRY(rowloc.alloc((size_t)h.nnz));
     SPMV_HIP_TRY(t_col.alloc((size_t)h.nnz));
     SPMV_HIP_TRY(t_row.alloc((size_t)h.nnz));
     SPMV_HIP_TRY(t_val.alloc((size_t)h.nnz));
-    SPMV_HIP_TRY(hipMemsetAsync(packed.get(), 0, sizeof(uint32_t) * slots, s));
-    SPMV_HIP_TRY(hipMemsetAsync(pvals.get(), 0, sizeof(float) * slots, s));
+    SPMV_HIP_TRY(hipMemsetAsync(p.d_packed.get(), 0, sizeof(uint32_t) * slots, s));
+    SPMV_HIP_TRY(hipMemsetAsync(p.d_pvals.get(), 0, sizeof(float) * slots, s));
     SPMV_HIP_TRY(hipMemsetAsync(o_row.get(), 0xFF, sizeof(uint16_t) * slots, s));
     if (h.nnz > 0) {
-        if ((rc = panel_rowloc(h, brow.get(), p.nblocks, rowloc.get(), s))) return rc;
+        if ((rc = panel_rowloc(h, p.d_brow.get(), p.nblocks, rowloc.get(), s))) return rc;
         // counters for the widest block at 32 columns each (wider blocks than kCbBins counters reach use coarser bins)
         int32_t widest = 0;
         SPMV_HIP_TRY(hipMemsetAsync(total.get(), 0, sizeof(int32_t), s));
-        k_cb_span<<<dim3((unsigned)p.nblocks), dim3(kBlock), 0, s>>>(brow.get(), h.d_row_ptr, h.d_col_idx, total.get());
+        k_cb_span<<<dim3((unsigned)p.nblocks), dim3(kBlock), 0, s>>>(p.d_brow.get(), h.d_row_ptr, h.d_col_idx, total.get());
         if ((rc = check_launch("k_cb_span"))) return rc;
         SPMV_HIP_TRY(hipMemcpyAsync(&widest, total.get(), sizeof widest, hipMemcpyDeviceToHost, s));
         SPMV_HIP_TRY(hipStreamSynchronize(s));
@@ -788,32 +782,29 @@ static int build_colsort(spmv_csr &h, PanelPlan &p, int rows_cap, hipStream_t s)
         const size_t lds = sizeof(int) * (size_t)nbins;
         static LdsOptIn optin;
         if ((rc = optin.ensure(reinterpret_cast<const void *>(&k_cb_sort), h.device, (int)(sizeof(int) * (size_t)kCbBins)))) return rc;
-        k_cb_sort<<<dim3((unsigned)p.nblocks), dim3(kBlock), lds, s>>>(brow.get(), h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.get(),
+        k_cb_sort<<<dim3((unsigned)p.nblocks), dim3(kBlock), lds, s>>>(p.d_brow.get(), h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.get(),
                                                                         t_col.get(), t_row.get(), t_val.get(), nshort.get(), stats.get(), nbins);
         if ((rc = check_launch("k_cb_sort"))) return rc;
-        k_cb_groups<<<dim3((unsigned)p.nblocks), dim3(kWave), 0, s>>>(brow.get(), h.d_row_ptr, ubeg.get(), nshort.get(), t_col.get(), t_row.get(),
-                                                                       t_val.get(), reinterpret_cast<int32_t *>(packed.get()), o_row.get(),
-                                                                       pvals.get(), usimple.get(), uend.get(), stats.get());
+        k_cb_groups<<<dim3((unsigned)p.nblocks), dim3(kWave), 0, s>>>(p.d_brow.get(), h.d_row_ptr, p.d_ubeg.get(), nshort.get(), t_col.get(), t_row.get(),
+                                                                       t_val.get(), reinterpret_cast<int32_t *>(p.d_packed.get()), o_row.get(),
+                                                                       p.d_pvals.get(), p.d_usimple.get(), p.d_uend.get(), stats.get());
         if ((rc = check_launch("k_cb_groups"))) return rc;
     } else {
-        SPMV_HIP_TRY(hipMemsetAsync(usimple.get(), 0, sizeof(int32_t) * (size_t)p.nblocks, s));
-        SPMV_HIP_TRY(hipMemcpyAsync(uend.get(), ubeg.get(), sizeof(int32_t) * (size_t)p.nblocks, hipMemcpyDeviceToDevice, s));   // no units in use
+        SPMV_HIP_TRY(hipMemsetAsync(p.d_usimple.get(), 0, sizeof(int32_t) * (size_t)p.nblocks, s));
+        SPMV_HIP_TRY(hipMemcpyAsync(p.d_uend.get(), p.d_ubeg.get(), sizeof(int32_t) * (size_t)p.nblocks, hipMemcpyDeviceToDevice, s));   // no units in use
     }
     // the rows of the tail units, compact: tbeg[b] = the block's first unit in trow
-    DevPtr<int32_t> tbeg, ttotal;
-    DevPtr<uint16_t> trow;
-    SPMV_HIP_TRY(tbeg.alloc((size_t)p.nblocks));
+    DevPtr<int32_t> ttotal;
+    SPMV_HIP_TRY(p.d_tbeg.alloc((size_t)p.nblocks));
     SPMV_HIP_TRY(ttotal.alloc(1));
-    k_cb_tail_units<<<dim3(gb), dim3(256), 0, s>>>(p.nblocks, ubeg.get(), usimple.get(), uend.get(), tbeg.get());
+    k_cb_tail_units<<<dim3(gb), dim3(256), 0, s>>>(p.nblocks, p.d_ubeg.get(), p.d_usimple.get(), p.d_uend.get(), p.d_tbeg.get());
     if ((rc = check_launch("k_cb_tail_units"))) return rc;
-    if ((rc = exclusive_scan_i32(tbeg.get(), p.nblocks, ttotal.get(), s))) return rc;
     int32_t tunits = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&tunits, ttotal.get(), sizeof tunits, hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = scan_offsets_i32(p.d_tbeg.get(), p.nblocks, ttotal.get(), false, s, &tunits))) return rc;
     p.tail_units = tunits;
-    SPMV_HIP_TRY(trow.alloc((size_t)tunits * kCbUnit));
-    k_cb_pack<<<dim3((unsigned)((units + 3) / 4)), dim3(kBlock), 0, s>>>((int64_t)units, rows_cap, p.nblocks, ubeg.get(), usimple.get(), uend.get(),
-                                                                         tbeg.get(), packed.get(), o_row.get(), ubase.get(), trow.get(), fail.get());
+    SPMV_HIP_TRY(p.d_trow.alloc((size_t)tunits * kCbUnit));
+    k_cb_pack<<<dim3((unsigned)((units + 3) / 4)), dim3(kBlock), 0, s>>>((int64_t)units, rows_cap, p.nblocks, p.d_ubeg.get(), p.d_usimple.get(), p.d_uend.get(),
+                                                                         p.d_tbeg.get(), p.d_packed.get(), o_row.get(), p.d_ubase.get(), p.d_trow.get(), fail.get());
     if ((rc = check_launch("k_cb_pack"))) return rc;
     int32_t failed = 0;
     unsigned long long st[3] = {0, 0, 0};
@@ -830,15 +821,6 @@ static int build_colsort(spmv_csr &h, PanelPlan &p, int rows_cap, hipStream_t s)
     p.lines = (int64_t)st[0];
     p.tail = (int64_t)st[1];
     p.wide_blocks = (int64_t)st[2];
-    p.d_packed = std::move(packed);
-    p.d_pvals = std::move(pvals);
-    p.d_brow = std::move(brow);
-    p.d_ubeg = std::move(ubeg);
-    p.d_usimple = std::move(usimple);
-    p.d_uend = std::move(uend);
-    p.d_tbeg = std::move(tbeg);
-    p.d_trow = std::move(trow);
-    p.d_ubase = std::move(ubase);
     return SPMV_OK;
 }
 
@@ -885,20 +867,19 @@ double colsort_cost(int rows_per_block, double lines_per_nnz, double tail_frac)
     return c + tail_frac;
 }
 
-double colsort_model_cost(const PanelPlan &p, int64_t nnz)
+double colsort_model_cost(const SortedBlocksPlan &p, int64_t nnz)
 {
-    if (!p.sorted_mode || nnz <= 0) return 0.0;
+    if (nnz <= 0) return 0.0;
     return colsort_cost(p.sb_rows, (double)p.lines / (double)nnz, (double)p.tail / (double)nnz);
 }
 
 // want_rows: 0 = the rule below | 4096 | 8192; want_waves: 0 = the rule | 4 | 8 (8 only with 4096 rows)
-int plan_colsort(spmv_csr &h, PanelPlan &p, int want_rows, int want_waves, hipStream_t s)
+int plan_colsort(spmv_csr &h, SortedBlocksPlan &p, int want_rows, int want_waves, hipStream_t s)
 {
-    p.sorted_mode = true;
-    p.lds_mode = false;
-    p.pw_bits = 0;
-    p.npanels = 0;
-    p.waves_per_launch = 0;
+    if (h.nnz > (int64_t)INT_MAX / 17 * 16 - 4096) {
+        set_error("spmv_csr_plan(panel, sorted blocks): nnz %lld too close to 2^31 for one handle", (long long)h.nnz);
+        return SPMV_ERR_INVALID;
+    }
     if ((want_rows != 0 && want_rows != 4096 && want_rows != 8192) || (want_waves != 0 && want_waves != 4 && want_waves != 8) ||
         (want_rows == 8192 && want_waves == 8)) {
         set_error("spmv_csr_plan(panel, sorted blocks): rows per block %d / wavefronts %d outside 4096|8192 / 4|8 (8192 x 8 does not fit LDS)",
@@ -908,38 +889,36 @@ int plan_colsort(spmv_csr &h, PanelPlan &p, int want_rows, int want_waves, hipSt
     if (h.rows == 0) {
         p.sb_rows = want_rows ? want_rows : 4096;
         p.sb_waves = want_waves ? want_waves : 8;
-        p.stamp.gen = h.values_gen;     // nothing was copied, but the plan is as fresh as any other made now
-        p.stamp.have_sum = false;
-        p.ready = true;
         return SPMV_OK;
     }
     const int cus = device_cus(h.device);
-    int rc = build_colsort(h, p, want_rows ? want_rows : 4096, s);
-    if (rc) return rc;
-    auto waves_for = [&](const PanelPlan &q) {
-        if (q.sb_rows > 4096) return 4;
-        if (want_waves) return want_waves;
-        return q.nblocks >= 4 * cus ? 4 : 8;   // two workgroups of 4 per CU need blocks to go round
-    };
-    p.sb_waves = waves_for(p);
+    if (int rc = build_colsort(h, p, want_rows ? want_rows : 4096, s)) return rc;
+    p.sb_waves = p.sb_rows > 4096 ? 4 : want_waves ? want_waves : p.nblocks >= 4 * cus ? 4 : 8;   // two workgroups of 4 per CU need blocks to go round
     // 8192-row blocks: half the lines of x per nonzero, at half the wavefronts per CU -- worth trying from 0.27 lines per
     // nonzero when there are blocks enough to fill the chip with 4 wavefronts per CU (a band of 1M columns at config 4:
     // 0.44 -> 0.25 lines per nonzero, 37 -> 41 % of peak); kept when the model prices it lower.
     if (want_rows == 0 && h.nnz > 0 && (double)p.lines > 0.27 * (double)h.nnz && p.nblocks >= 16 * cus) {
-        PanelPlan q;   // what p was on entry (a fresh plan), then built for 8192 rows; freed here unless it wins
-        q.sorted_mode = true;
+        SortedBlocksPlan q;   // built for 8192 rows; freed here unless it wins
         if (build_colsort(h, q, 8192, s) == SPMV_OK) {
             q.sb_waves = 4;
             if (colsort_model_cost(q, h.nnz) < colsort_model_cost(p, h.nnz)) p = std::move(q);
         }
     }
-    if ((rc = stamp_values(h, s, p.stamp))) return rc;
-    p.ready = true;
     return SPMV_OK;
 }
 
+void colsort_params(const SortedBlocksPlan &p, int32_t params[8]) { params[4] = p.sb_rows; params[5] = p.sb_waves; params[6] = 3; }
+// (unit bases, block tables, the rows of the tail units, the empty slots of the units in use)
+int64_t colsort_plan_bytes(const SortedBlocksPlan &p, int64_t) { return p.units * 4 + (int64_t)p.nblocks * 20 + p.tail_units * 512; }
+void colsort_describe(const SortedBlocksPlan &p, const spmv_csr &h, char *buf, int n)
+{
+    snprintf(buf, (size_t)n, "sorted_blocks=%d rows_per_block=%d wavefronts=%d lines_per_nonzero=%.3f tail_nonzeros=%lld wide_blocks=%lld model_cost=%.3f",
+             p.nblocks, p.sb_rows, p.sb_waves, h.nnz ? (double)p.lines / (double)h.nnz : 0.0, (long long)p.tail,
+             (long long)p.wide_blocks, colsort_model_cost(p, h.nnz));
+}
+
 template <int ROWS, int WAVES>
-static int launch_colsort_t(const spmv_csr &h, const PanelPlan &p, const float *x, float *y, hipStream_t s)
+static int launch_colsort_t(const spmv_csr &h, const SortedBlocksPlan &p, const float *x, float *y, hipStream_t s)
 {
     const size_t lds = sizeof(float) * (size_t)WAVES * (ROWS + kWave);
     static LdsOptIn optin;
@@ -949,7 +928,7 @@ static int launch_colsort_t(const spmv_csr &h, const PanelPlan &p, const float *
     return check_launch("k_colsort");
 }
 
-int launch_colsort(const spmv_csr &h, const PanelPlan &p, const float *x, float *y, hipStream_t s)
+int launch_colsort(const spmv_csr &h, const SortedBlocksPlan &p, const float *x, float *y, hipStream_t s)
 {
     if (p.nblocks == 0) return SPMV_OK;
     if (p.sb_rows > 4096) return launch_colsort_t<8192, 4>(h, p, x, y, s);

@@ -131,6 +131,15 @@ int exclusive_scan_i32(int32_t *d_data, int64_t n, int32_t *d_total, hipStream_t
     return SPMV_OK;
 }
 
+int scan_offsets_i32(int32_t *d_data, int64_t n, int32_t *d_total, bool append_total, hipStream_t s, int32_t *total_host)
+{
+    if (int rc = exclusive_scan_i32(d_data, n, d_total, s)) return rc;
+    SPMV_HIP_TRY(hipMemcpyAsync(total_host, d_total, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (append_total) SPMV_HIP_TRY(hipMemcpyAsync(d_data + n, d_total, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    SPMV_HIP_TRY(hipStreamSynchronize(s));
+    return SPMV_OK;
+}
+
 // row_ptr[i] = offs[i*S] for i < N, row_ptr[N] = nnz
 __global__ void k_row_ptr_from_offsets(int N, int S, const int32_t *__restrict__ offs,
                                        const int32_t *__restrict__ total, int32_t *__restrict__ row_ptr)

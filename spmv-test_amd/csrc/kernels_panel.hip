@@ -17,7 +17,7 @@
 // src/kernels/csr_tiling.cu:24-114: 32 x 32 tiles, x tile and tile values in shared memory) is the same idea at
 // dense-matrix scale; this is its sparse-matrix, cache-sized counterpart.
 //
-// Layout (PanelPlan): for row block b (rows [brow[b], brow[b+1])) the nonzeros keep their CSR range
+// Layout (SweepPlan): for row block b (rows [brow[b], brow[b+1])) the nonzeros keep their CSR range
 // [row_ptr[brow[b]], row_ptr[brow[b+1]]) but are stably sorted by panel:
 //   packed[k] = row_in_block << 18 | join << 17 | column_in_panel     pvals[k] = value   (8 B per nonzero, as CSR)
 //   (join: the nonzero 4 places earlier in the same tile has the same row -- the two would meet in one instruction)
@@ -52,7 +52,7 @@ constexpr unsigned kJoinBit = 1u << kColBits;   // this nonzero and the one 4 pl
 constexpr int kRowShift = kColBits + 1;
 constexpr int kWavesPerWg = 2;             // 76 KiB of LDS per workgroup -> 2 workgroups = 4 waves per CU
 // 16-byte vectors per lane, step and array: a step of the sweep is 256 x VEC nonzeros of a wavefront's stream.  Two
-// instantiations, chosen when the plan is made (PanelPlan::step_vecs): 8 where the tiles are fat (+4 % over 4 at configs 3
+// instantiations, chosen when the plan is made (SweepPlan::step_vecs): 8 where the tiles are fat (+4 % over 4 at configs 3
 // and 4), 4 where a step of 2048 would span many panels -- config 5's shard, 128 nonzeros per tile: the gathers of ONE step
 // then cover 16 panels = 8 MiB of x, twice an L2, and the wavefronts of an XCD stop sharing lines (3.02 -> 2.41 ms,
 // profiles/r04_panel_step_size.jsonl; 6: 2.61, 3: 2.44, 2: 2.53, 1: 2.92)
@@ -398,7 +398,7 @@ __global__ __launch_bounds__(kWave *kWavesPerWg) void k_panel(int wb0, int wb1, 
     for (int i = lane; i < n; i += kWave) y[row0 + i] = ys[i];
 }
 
-// ---- the same sweep with the panel of x staged in LDS (PanelPlan::lds_mode) -----------------------------------------
+// ---- the same sweep with the panel of x staged in LDS (SweepPlan::lds) -----------------------------------------
 // For a SMALL x (config 2: 4 MiB) the panel does not have to come through L2 gather by gather -- one 128-byte line per
 // nonzero, 0.28 T gathers/s at best (tools/ubench_gather.hip) -- every workgroup can copy ALL of x through its LDS,
 // 16 Ki columns at a time with 16-byte LDS-DMA loads (22-27 TB/s chip-wide, same tool), and gather from LDS.  That is
@@ -495,15 +495,11 @@ int panel_row_blocks(const spmv_csr &h, int64_t nb0, int cap, hipStream_t s, Dev
     if (rc) return rc;
     k_panel_nsub<<<dim3(gb), dim3(256), 0, s>>>((int)nb0, cap, cut.get(), nsub.get());
     if ((rc = check_launch("k_panel_nsub"))) return rc;
-    if ((rc = exclusive_scan_i32(nsub.get(), nb0, total.get(), s))) return rc;
-    int32_t nblocks = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&nblocks, total.get(), sizeof nblocks, hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipStreamSynchronize(s));
-    SPMV_HIP_TRY(brow.alloc((size_t)nblocks + 1));
+    if ((rc = scan_offsets_i32(nsub.get(), nb0, total.get(), false, s, nblocks_out))) return rc;
+    SPMV_HIP_TRY(brow.alloc((size_t)*nblocks_out + 1));
     k_panel_brow<<<dim3(gb), dim3(256), 0, s>>>(h.rows, (int)nb0, cap, cut.get(), nsub.get(), total.get(), brow.get());
     if ((rc = check_launch("k_panel_brow"))) return rc;
     SPMV_HIP_TRY(hipStreamSynchronize(s));   // the temporaries are freed on return
-    *nblocks_out = nblocks;
     return SPMV_OK;
 }
 
@@ -522,68 +518,23 @@ int panel_tile_ptr(const spmv_csr &h, const int32_t *d_brow, int nblocks, int pw
     return check_launch("k_panel_tiles");
 }
 
-// one launch = one set of co-resident waves sweeping in step: 2 workgroups (4 waves) per CU
-static int resident_waves(int device) { return device_cus(device) * kWgPerCu * kWavesPerWg; }
-
 // spmv_csr_plan: idempotent like the other variants (spmv_csr_plan_set always re-plans: the way to refresh the copied values)
-// ... unless the caller has announced new values (spmv_csr_values_changed): the copy is then rebuilt as it was planned
-int plan_panel(spmv_csr &h, hipStream_t s) { return refresh_panel(h, h.plan_panel, s); }
-
+// ... unless the caller has announced new values (spmv_csr_values_changed): the copy is then rebuilt as it was planned.
 // `dst` is one of the handle's two panel plans: plan_panel (SPMV_PANEL) or plan_auto_panel (what SPMV_AUTO chose: its
 // own, so that planning AUTO never disturbs a PANEL plan the caller made, and the other way round)
 int refresh_panel(spmv_csr &h, PanelPlan &dst, hipStream_t s)
 {
-    if (!dst.ready) return build_panel(h, dst, 0, 0, 0, s);
+    if (dst.layout == PanelLayout::none) return build_panel(h, dst, 0, 0, 0, s);
     if (dst.stamp.gen == h.values_gen) return SPMV_OK;
-    if (dst.binned_mode) return build_panel(h, dst, dst.bin_rows, 0, dst.scatter_mode ? 5 : 4, s);
-    if (dst.sorted_mode) return build_panel(h, dst, dst.sb_rows, dst.sb_waves, 3, s);
-    return build_panel(h, dst, dst.pw_bits, dst.waves_per_launch, dst.lds_mode ? 2 : 1, s);
+    int32_t params[8];
+    panel_params(dst, params);
+    return build_panel(h, dst, params[4], params[5], params[6], s);
 }
 
-int plan_panel_with(spmv_csr &h, int want_bits, int want_waves, int want_mode, hipStream_t s)
+// want_bits: log2 of the panel width, want_waves: wavefronts per launch (0 = the rule for either); lds: the panels staged in LDS (k_panel_lds), not gathered through L2 (k_panel)
+static int plan_sweep(spmv_csr &h, SweepPlan &p, int want_bits, int want_waves, bool lds, hipStream_t s)
 {
-    return build_panel(h, h.plan_panel, want_bits, want_waves, want_mode, s);
-}
-
-// want_mode: 0 = the rule below, 1 = panels through L2 (k_panel), 2 = panels staged in LDS (k_panel_lds),
-//            3 = sorted blocks (kernels_colsort.hip; SPMV_PANEL_SORTED=1 makes it the rule's answer),
-//            4 = binned (kernels_binned.hip: products streamed in panel order, summed per row block; want_bits = rows per bin),
-//            5 = binned, the products stored in bin order by the product launch (thin tiles)
-int build_panel(spmv_csr &h, PanelPlan &dst, int want_bits, int want_waves, int want_mode, hipStream_t s)
-{
-    dst = PanelPlan{};
-    PanelPlan p;
-    if (want_mode == 4 || want_mode == 5) {      // binned: two streaming launches, no gather from memory (kernels_binned.hip)
-        const int rc = plan_binned(h, p, want_bits, want_mode == 5, s);
-        if (rc) return rc;
-        dst = std::move(p);
-        return SPMV_OK;
-    }
-    {
-        bool sorted = false;
-        if (const char *e = getenv("SPMV_PANEL_SORTED")) sorted = atoi(e) != 0;
-        if (want_mode == 3 || (want_mode == 0 && sorted)) {
-            if (h.nnz > (int64_t)INT_MAX / 17 * 16 - 4096) {
-                set_error("spmv_csr_plan(panel, sorted blocks): nnz %lld too close to 2^31 for one handle", (long long)h.nnz);
-                return SPMV_ERR_INVALID;
-            }
-            const int rc = plan_colsort(h, p, want_mode == 3 ? want_bits : 0, want_mode == 3 ? want_waves : 0, s);
-            if (rc) return rc;
-            dst = std::move(p);
-            return SPMV_OK;
-        }
-    }
-    {
-        // LDS mode (k_panel_lds) is never chosen by the library: it was built to test whether staging the panels of a
-        // SMALL x in LDS beats gathering them through L2 (VERDICT round 1, item 3) and measured slower where it had
-        // its best chance -- config 2, uniform columns: 0.135 ms against 0.087 ms; config 3: 3.5 ms against 0.86 ms
-        // (DESIGN.md section 4, "Uniform columns").  It stays selectable (params[6] = 2, SPMV_PANEL_LDS=1) and tested.
-        bool lds = false;
-        if (const char *e = getenv("SPMV_PANEL_LDS")) lds = atoi(e) != 0;
-        if (want_mode == 1) lds = false;
-        if (want_mode == 2) lds = true;
-        p.lds_mode = lds;
-    }
+    p.lds = lds;
     if (h.nnz > (int64_t)INT_MAX - 4 * kStepMax) {
         set_error("spmv_csr_plan(panel): nnz %lld too close to 2^31 for one handle", (long long)h.nnz);
         return SPMV_ERR_INVALID;
@@ -594,7 +545,7 @@ int build_panel(spmv_csr &h, PanelPlan &dst, int want_bits, int want_waves, int 
     if (bits < 8) bits = 8;
     if (bits > kColBits) bits = kColBits;
     while (bits < kColBits && ((h.cols + (1ll << bits) - 1) >> bits) > kMaxPanels) ++bits;
-    if (p.lds_mode) {
+    if (p.lds) {
         bits = kLdsPwBits;
         if (((h.cols + kLdsW - 1) >> kLdsPwBits) > kMaxPanels) {
             set_error("spmv_csr_plan(panel, LDS mode): %lld columns need more than %d panels of 2^%d columns", (long long)h.cols,
@@ -611,90 +562,72 @@ int build_panel(spmv_csr &h, PanelPlan &dst, int want_bits, int want_waves, int 
         return SPMV_ERR_INVALID;
     }
     // row blocks: equal nonzero counts, as many as fill the resident wave slots of every launch
-    p.waves_per_launch = resident_waves(h.device);
+    // (one launch = one set of co-resident waves sweeping in step: 2 workgroups (4 waves) per CU)
+    p.waves_per_launch = device_cus(h.device) * kWgPerCu * kWavesPerWg;
     if (const char *e = getenv("SPMV_PANEL_WAVES")) {
         const int v = atoi(e);
         if (v > 0) p.waves_per_launch = v;
     }
     if (want_waves > 0) p.waves_per_launch = want_waves;
-    if (p.lds_mode) p.waves_per_launch = device_cus(h.device) * kLdsWaves;   // one 16-wavefront workgroup per CU and round
-    if (h.rows == 0) {
-        p.ready = true;
-        p.stamp.gen = h.values_gen;
-        dst = std::move(p);
-        return SPMV_OK;
-    }
+    if (p.lds) p.waves_per_launch = device_cus(h.device) * kLdsWaves;   // one 16-wavefront workgroup per CU and round
+    if (h.rows == 0) return SPMV_OK;
     const int64_t launches0 =
         (h.rows + (int64_t)p.waves_per_launch * kRwTarget - 1) / ((int64_t)p.waves_per_launch * kRwTarget);
     int64_t nb0 = launches0 * p.waves_per_launch;
-    const int cap = p.lds_mode ? kRwLds : kRw;
-    if (p.lds_mode) nb0 = (h.rows + kRwLdsTarget - 1) / kRwLdsTarget;
+    const int cap = p.lds ? kRwLds : kRw;
+    if (p.lds) nb0 = (h.rows + kRwLdsTarget - 1) / kRwLdsTarget;
     if (nb0 > h.rows) nb0 = h.rows;
-    DevPtr<int32_t> brow;
-    int rc = panel_row_blocks(h, nb0, cap, s, brow, &p.nblocks);
+    int rc = panel_row_blocks(h, nb0, cap, s, p.d_brow, &p.nblocks);
     if (rc) return rc;
     // the step of the sweep: 1024 nonzeros where a step of 2048 would span eight tiles or more (see kVecMax)
     p.step_vecs = (double)h.nnz < 256.0 * (double)p.nblocks * (double)p.npanels ? 4 : 8;
     if (const char *e = getenv("SPMV_PANEL_STEP")) { const int v = atoi(e); if (v == 4 || v == 8) p.step_vecs = v; }
 
-    DevPtr<uint32_t> packed;
-    DevPtr<float> pvals;
-    DevPtr<int32_t> tiles;
     DevPtr<uint16_t> rowloc;
     const size_t slots = panel_slots(h.nnz);
-    SPMV_HIP_TRY(packed.alloc(slots));
-    SPMV_HIP_TRY(pvals.alloc(slots));
-    SPMV_HIP_TRY(tiles.alloc((size_t)p.nblocks * (size_t)(p.npanels + 1)));
+    SPMV_HIP_TRY(p.d_packed.alloc(slots));
+    SPMV_HIP_TRY(p.d_pvals.alloc(slots));
+    SPMV_HIP_TRY(p.d_tile_ptr.alloc((size_t)p.nblocks * (size_t)(p.npanels + 1)));
     SPMV_HIP_TRY(rowloc.alloc((size_t)h.nnz));
-    SPMV_HIP_TRY(hipMemsetAsync(packed.get() + h.nnz, 0, sizeof(uint32_t) * (slots - (size_t)h.nnz), s));
-    SPMV_HIP_TRY(hipMemsetAsync(pvals.get() + h.nnz, 0, sizeof(float) * (slots - (size_t)h.nnz), s));
-    k_panel_tiles<<<dim3((unsigned)p.nblocks), dim3(256), 0, s>>>(brow.get(), h.d_row_ptr, h.d_col_idx, p.pw_bits,
-                                                                   p.npanels, tiles.get());
-    if ((rc = check_launch("k_panel_tiles"))) return rc;
+    SPMV_HIP_TRY(hipMemsetAsync(p.d_packed.get() + h.nnz, 0, sizeof(uint32_t) * (slots - (size_t)h.nnz), s));
+    SPMV_HIP_TRY(hipMemsetAsync(p.d_pvals.get() + h.nnz, 0, sizeof(float) * (slots - (size_t)h.nnz), s));
+    if ((rc = panel_tile_ptr(h, p.d_brow.get(), p.nblocks, p.pw_bits, p.npanels, p.d_tile_ptr.get(), s))) return rc;
     if (h.nnz > 0) {
-        k_panel_rowloc<<<dim3((unsigned)p.nblocks), dim3(256), 0, s>>>(brow.get(), h.d_row_ptr, rowloc.get());
-        if ((rc = check_launch("k_panel_rowloc"))) return rc;
+        if ((rc = panel_rowloc(h, p.d_brow.get(), p.nblocks, rowloc.get(), s))) return rc;
         k_panel_fill<<<dim3((unsigned)((p.nblocks + 3) / 4)), dim3(256), 0, s>>>(
-            p.nblocks, brow.get(), h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.get(), p.pw_bits, p.npanels, tiles.get(), packed.get(),
-            pvals.get());
+            p.nblocks, p.d_brow.get(), h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.get(), p.pw_bits, p.npanels, p.d_tile_ptr.get(), p.d_packed.get(),
+            p.d_pvals.get());
         if ((rc = check_launch("k_panel_fill"))) return rc;
-        if (!p.lds_mode) {   // the LDS kernel folds equal rows itself
-            k_panel_joins<<<dim3((unsigned)p.nblocks), dim3(256), 0, s>>>(brow.get(), p.npanels, h.d_row_ptr, tiles.get(),
-                                                                           packed.get());
+        if (!p.lds) {   // the LDS kernel folds equal rows itself
+            k_panel_joins<<<dim3((unsigned)p.nblocks), dim3(256), 0, s>>>(p.d_brow.get(), p.npanels, h.d_row_ptr, p.d_tile_ptr.get(),
+                                                                           p.d_packed.get());
             if ((rc = check_launch("k_panel_joins"))) return rc;
         }
     }
-    if ((rc = stamp_values(h, s, p.stamp))) return rc;
     SPMV_HIP_TRY(hipStreamSynchronize(s));   // the temporaries are freed on return
-    p.d_packed = std::move(packed);
-    p.d_pvals = std::move(pvals);
-    p.d_tile_ptr = std::move(tiles);
-    p.d_brow = std::move(brow);
-    p.ready = true;
-    dst = std::move(p);
     return SPMV_OK;
 }
 
-int panel_launches(const PanelPlan &p)
+static int sweep_launches(const SweepPlan &p)
 {
-    if (p.binned_mode) return p.nblocks ? 2 : 0;
-    if (p.lds_mode || p.sorted_mode) return p.nblocks ? 1 : 0;
+    if (p.lds) return p.nblocks ? 1 : 0;
     return p.nblocks && p.waves_per_launch ? (p.nblocks + p.waves_per_launch - 1) / p.waves_per_launch : 0;
 }
 
-int launch_panel(const spmv_csr &h, const float *x, float *y, hipStream_t s) { return launch_panel_plan(h, h.plan_panel, x, y, s); }
-
-int launch_panel_plan(const spmv_csr &h, const PanelPlan &p, const float *x, float *y, hipStream_t s)
+static void sweep_params(const SweepPlan &p, int32_t params[8]) { params[4] = p.pw_bits; params[5] = p.waves_per_launch; params[6] = p.lds ? 2 : 1; }
+// tile_ptr; packed/pvals REPLACE col_idx/vals byte for byte
+static int64_t sweep_plan_bytes(const SweepPlan &p, int64_t) { return (int64_t)p.nblocks * (p.npanels + 1) * 4 + ((int64_t)p.nblocks + 1) * 4; }
+static void sweep_describe(const SweepPlan &p, const spmv_csr &, char *buf, int n)
 {
-    if (!p.ready) {
-        set_error("spmv_csr_run: variant panel is not planned (call spmv_csr_plan first)");
-        return SPMV_ERR_NOT_PLANNED;
-    }
-    if (int rc = require_fresh_values(h, p.stamp, s, "panel")) return rc;
-    if (p.binned_mode) return launch_binned(h, p, x, y, s);
-    if (p.sorted_mode) return launch_colsort(h, p, x, y, s);
-    if (p.lds_mode) {
-        if (p.nblocks == 0) return SPMV_OK;
+    snprintf(buf, (size_t)n, "panel_columns=%d panels=%d row_blocks=%d waves_per_launch=%d launches=%d x_panels_in=%s nonzeros_per_step=%d",
+             1 << p.pw_bits, p.npanels, p.nblocks, p.waves_per_launch, sweep_launches(p), p.lds ? "LDS" : "L2", p.lds ? 64 : 256 * p.step_vecs);
+}
+
+static int launch_sweep(const spmv_csr &h, const SweepPlan &p, const float *x, float *y, hipStream_t s)
+{
+    const int launches = sweep_launches(p);
+    if (launches == 0) return SPMV_OK;   // no rows
+    if (p.lds) {
         const size_t lds = sizeof(float) * (size_t)(2 * kLdsW + kLdsWaves * kRwLds);
         static LdsOptIn optin;
         if (int rc = optin.ensure(reinterpret_cast<const void *>(&k_panel_lds), h.device, (int)lds)) return rc;
@@ -703,24 +636,104 @@ int launch_panel_plan(const spmv_csr &h, const PanelPlan &p, const float *x, flo
         return check_launch("k_panel_lds");
     }
     // equal shares: 1536 blocks on 1024 slots run as 768 + 768, not 1024 + 512
-    const int launches = panel_launches(p);
-    if (launches == 0) return SPMV_OK;   // no rows
     const int share = (p.nblocks + launches - 1) / launches;
     for (int b0 = 0; b0 < p.nblocks; b0 += share) {
         const int b1 = b0 + share < p.nblocks ? b0 + share : p.nblocks;
         const int g = (b1 - b0 + kWavesPerWg - 1) / kWavesPerWg;
-        if (p.step_vecs == 4)
-            k_panel<4><<<dim3((unsigned)g), dim3(kWave * kWavesPerWg), 0, s>>>(b0, b1, p.d_brow, h.d_row_ptr, p.d_tile_ptr,
-                                                                               p.d_packed, p.d_pvals, x, y, p.npanels, p.pw_bits,
-                                                                               panel_slots(h.nnz));
-        else
-            k_panel<8><<<dim3((unsigned)g), dim3(kWave * kWavesPerWg), 0, s>>>(b0, b1, p.d_brow, h.d_row_ptr, p.d_tile_ptr,
-                                                                               p.d_packed, p.d_pvals, x, y, p.npanels, p.pw_bits,
-                                                                               panel_slots(h.nnz));
+        (p.step_vecs == 4 ? k_panel<4> : k_panel<8>)<<<dim3((unsigned)g), dim3(kWave * kWavesPerWg), 0, s>>>(
+            b0, b1, p.d_brow, h.d_row_ptr, p.d_tile_ptr, p.d_packed, p.d_pvals, x, y, p.npanels, p.pw_bits, panel_slots(h.nnz));
         const int rc = check_launch("k_panel");
         if (rc) return rc;
     }
     return SPMV_OK;
+}
+
+// want_mode: 0 = the rule below, 1 = panels through L2 (k_panel), 2 = panels staged in LDS (k_panel_lds),
+//            3 = sorted blocks (kernels_colsort.hip; SPMV_PANEL_SORTED=1 makes it the rule's answer),
+//            4 = binned (kernels_binned.hip: products streamed in panel order, summed per row block; want_bits = rows per bin),
+//            5 = binned, the products stored in bin order by the product launch (thin tiles)
+int build_panel(spmv_csr &h, PanelPlan &dst, int want_bits, int want_waves, int want_mode, hipStream_t s)
+{
+    dst = PanelPlan{};
+    PanelPlan p;
+    int rc;
+    bool sorted = false;
+    if (const char *e = getenv("SPMV_PANEL_SORTED")) sorted = atoi(e) != 0;
+    if (want_mode == 4) {        // binned: two streaming launches, no gather from memory (kernels_binned.hip)
+        p.layout = PanelLayout::binned;
+        rc = plan_binned(h, p.binned, want_bits, s);
+    } else if (want_mode == 5) {
+        p.layout = PanelLayout::binned_scattered;
+        rc = plan_scatter(h, p.scattered, want_bits, s);
+    } else if (want_mode == 3 || (want_mode == 0 && sorted)) {
+        p.layout = PanelLayout::sorted_blocks;
+        rc = plan_colsort(h, p.sorted, want_mode == 3 ? want_bits : 0, want_mode == 3 ? want_waves : 0, s);
+    } else {
+        // LDS mode (k_panel_lds) is never chosen by the library: it was built to test whether staging the panels of a
+        // SMALL x in LDS beats gathering them through L2 (VERDICT round 1, item 3) and measured slower where it had
+        // its best chance -- config 2, uniform columns: 0.135 ms against 0.087 ms; config 3: 3.5 ms against 0.86 ms
+        // (DESIGN.md section 4, "Uniform columns").  It stays selectable (params[6] = 2, SPMV_PANEL_LDS=1) and tested.
+        bool lds = false;
+        if (const char *e = getenv("SPMV_PANEL_LDS")) lds = atoi(e) != 0;
+        if (want_mode == 1) lds = false;
+        if (want_mode == 2) lds = true;
+        p.layout = lds ? PanelLayout::sweep_lds : PanelLayout::sweep_l2;
+        rc = plan_sweep(h, p.sweep, want_bits, want_waves, lds, s);
+    }
+    if (rc) return rc;
+    // which state of vals the layout copied (no rows: nothing was copied, but the plan is as fresh as any other made now)
+    if (h.rows == 0) p.stamp.gen = h.values_gen;
+    else if ((rc = stamp_values(h, s, p.stamp))) return rc;
+    dst = std::move(p);
+    return SPMV_OK;
+}
+
+// params[4..6] of spmv_csr_plan_get: what build_panel takes to make this plan again
+void panel_params(const PanelPlan &p, int32_t params[8])
+{
+    switch (p.layout) {
+        case PanelLayout::none: return;
+        case PanelLayout::sweep_l2: case PanelLayout::sweep_lds: return sweep_params(p.sweep, params);
+        case PanelLayout::sorted_blocks: return colsort_params(p.sorted, params);
+        case PanelLayout::binned: return binned_params(p.binned, params);
+        case PanelLayout::binned_scattered: return scatter_params(p.scattered, params);
+    }
+}
+
+int64_t panel_plan_bytes(const PanelPlan &p, int64_t nnz)
+{
+    switch (p.layout) {
+        case PanelLayout::sorted_blocks: return colsort_plan_bytes(p.sorted, nnz);
+        case PanelLayout::binned: return binned_plan_bytes(p.binned, nnz);
+        case PanelLayout::binned_scattered: return scatter_plan_bytes(p.scattered, nnz);
+        default: return sweep_plan_bytes(p.sweep, nnz);   // (not planned: the sweep's count of an empty plan, as ever)
+    }
+}
+
+void panel_describe(const PanelPlan &p, const spmv_csr &h, char *buf, int n)
+{
+    switch (p.layout) {
+        case PanelLayout::none: snprintf(buf, (size_t)n, "no plan"); return;
+        case PanelLayout::sweep_l2: case PanelLayout::sweep_lds: return sweep_describe(p.sweep, h, buf, n);
+        case PanelLayout::sorted_blocks: return colsort_describe(p.sorted, h, buf, n);
+        case PanelLayout::binned: return binned_describe(p.binned, h, buf, n);
+        case PanelLayout::binned_scattered: return scatter_describe(p.scattered, h, buf, n);
+    }
+}
+
+int launch_panel_plan(const spmv_csr &h, const PanelPlan &p, const float *x, float *y, hipStream_t s)
+{
+    if (p.layout == PanelLayout::none) {
+        set_error("spmv_csr_run: variant panel is not planned (call spmv_csr_plan first)");
+        return SPMV_ERR_NOT_PLANNED;
+    }
+    if (int rc = require_fresh_values(h, p.stamp, s, "panel")) return rc;
+    switch (p.layout) {
+        case PanelLayout::sorted_blocks: return launch_colsort(h, p.sorted, x, y, s);
+        case PanelLayout::binned: return launch_binned(h, p.binned, x, y, s);
+        case PanelLayout::binned_scattered: return launch_scatter(h, p.scattered, x, y, s);
+        default: return launch_sweep(h, p.sweep, x, y, s);
+    }
 }
 
 int bounds_collect_panel(unsigned long long out[kBoundsSites][2])

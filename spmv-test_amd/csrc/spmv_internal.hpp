@@ -126,12 +126,12 @@ struct ValuesStamp {
     bool have_sum = false;
 };
 
-// SPMV_PANEL (kernels_panel.hip): row blocks of at most 8192 rows and equal nonzero counts, each block's nonzeros stably sorted by column panel.
-struct PanelPlan {
-    bool ready = false;
-    bool lds_mode = false;         // panels of 2^14 columns staged in LDS by 16-wavefront workgroups (small x) instead of gathered through L2
-    int pw_bits = 0;               // log2(columns per panel)
-    int npanels = 0;
+// SPMV_PANEL is five layouts behind one variant number (params[6] of include/spmv_hip.h); each has a plan struct of its own.
+enum class PanelLayout { none = 0, sweep_l2 = 1, sweep_lds = 2, sorted_blocks = 3, binned = 4, binned_scattered = 5 };
+// the sweep (modes 1 and 2, kernels_panel.hip): row blocks of at most 8192 rows and equal nonzero counts, each block's nonzeros stably sorted by column panel.
+struct SweepPlan {
+    bool lds = false;              // panels of 2^14 columns staged in LDS by 16-wavefront workgroups (small x) instead of gathered through L2
+    int pw_bits = 0, npanels = 0;  // log2(columns per panel), panels
     int nblocks = 0;               // row blocks (<= 8192 rows, equal nonzero counts) = wavefronts of work
     int waves_per_launch = 0;      // what is resident at once: one launch = one sweep in step
     int step_vecs = 8;             // 16-byte vectors per lane and step of the sweep (8 | 4: thin tiles, kernels_panel.hip kVecMax)
@@ -139,51 +139,75 @@ struct PanelPlan {
     DevPtr<float> d_pvals;         // [nnz + slack] values in the same order (a COPY: re-plan after changing vals)
     DevPtr<int32_t> d_tile_ptr;    // [nblocks * (npanels + 1)]
     DevPtr<int32_t> d_brow;        // [nblocks + 1] first row of every block
-    ValuesStamp stamp;             // which state of vals d_pvals is a copy of
-    // sorted blocks (mode 3, kernels_colsort.hip): blocks of <= 4096 rows streamed in column order, d_packed / d_pvals in
-    // units of 256 slots (four groups of 64 nonzeros with distinct rows)
-    bool sorted_mode = false;
+};
+// sorted blocks (mode 3, kernels_colsort.hip): blocks of <= 4096 rows streamed in column order, d_packed / d_pvals (a COPY of vals) in
+// units of 256 slots (four groups of 64 nonzeros with distinct rows)
+struct SortedBlocksPlan {
+    int nblocks = 0, sb_rows = 0, sb_waves = 0;   // blocks, rows per block (4096 | 8192), wavefronts per workgroup (8 | 4)
+    DevPtr<uint32_t> d_packed;     // [units * 256] row_in_block << colbits | column - ubase[unit]
+    DevPtr<float> d_pvals;         // [units * 256]
+    DevPtr<int32_t> d_brow;        // [nblocks + 1] first row of every block
     DevPtr<int32_t> d_ubeg;        // [nblocks + 1] first unit of every block
     DevPtr<int32_t> d_usimple;     // [nblocks] leading units of the block that hold groups (64 distinct rows per instruction)
     DevPtr<int32_t> d_uend;        // [nblocks] one past the last unit the block uses (groups, then its row-sorted tail)
     DevPtr<int32_t> d_ubase;       // [units] first column of every unit (packed holds offsets from it)
     DevPtr<int32_t> d_tbeg;        // [nblocks] first tail unit of the block in d_trow
     DevPtr<uint16_t> d_trow;       // [tail_units * 256] rows of the tail units (their packed words are whole columns)
-    int64_t tail_units = 0;
-    int sb_rows = 0, sb_waves = 0;   // rows per block (4096 | 8192), wavefronts per workgroup (8 | 4)
+    int64_t units = 0, tail_units = 0;
     int64_t wide_blocks = 0;       // blocks whose short rows span more than 32768 lines of x (4 MiB)
-    int64_t units = 0;
     int64_t lines = 0;             // occupied 128-byte lines of x, summed over the blocks (plan statistic)
     int64_t tail = 0;              // nonzeros in the tails (long rows, what could not be grouped)
-    // binned (mode 4, kernels_binned.hip): the nonzeros twice over -- in PANEL-major order (d_c16 + d_pvals: what the
-    // product launch streams, its panel of x in LDS) and in BIN-major order (d_r16: what the sum launch streams beside the
-    // products); tile (bin b, panel p) is contiguous in both, rows ascending inside it
-    bool binned_mode = false;
+};
+// binned (mode 4, kernels_binned.hip): the nonzeros twice over -- in PANEL-major order (d_c16 + d_pvals: what the
+// product launch streams, its panel of x in LDS) and in BIN-major order (d_r16: what the sum launch streams beside the
+// products); tile (bin b, panel p) is contiguous in both, rows ascending inside it
+struct BinnedPlan {
     int bin_rows = 0;              // most rows of a bin (4096 | 8192): a wavefront's private sums in LDS
-    DevPtr<uint16_t> d_c16;        // [padded] column - panel * 2^pw_bits, panel-major (every panel padded to a multiple of 8)
+    int npanels = 0, nblocks = 0;  // panels of 2^15 columns, bins
+    int splits = 1;                // workgroups per panel of the product launch
+    bool wide_pieces = false;      // the sum launch takes four products per lane (fat tiles) instead of two
+    int64_t padded = 0;            // entries of the panel-major arrays
+    DevPtr<uint16_t> d_c16;        // [padded] column - panel * 2^15, panel-major (every panel padded to a multiple of 8)
+    DevPtr<float> d_pvals;         // [padded] values in the same order (a COPY: re-plan after changing vals)
+    DevPtr<float> d_prod;          // [padded] scratch of a run: the products, panel-major
     DevPtr<uint16_t> d_r16;        // [nnz] row - brow[bin], bin-major (d_tile_ptr positions)
     DevPtr<int32_t> d_pm;          // [nblocks * npanels] panel-major position of tile (b, p)
     DevPtr<int32_t> d_pbase;       // [npanels + 1] panel-major position of every panel's first entry
-    DevPtr<float> d_prod;          // [padded] scratch of a run: the products, panel-major
-    int64_t padded = 0;            // entries of the panel-major arrays
-    int splits = 1;                // workgroups per panel of the product launch
-    bool wide_pieces = false;      // the sum launch takes four products per lane (fat tiles) instead of two
+    DevPtr<int32_t> d_tile_ptr;    // [nblocks * (npanels + 1)]
+    DevPtr<int32_t> d_brow;        // [nblocks + 1] first row of every bin
     int flagged_tiles = 0;         // tiles that go through the fold (bins whose long rows need more spare sums than there are)
     int long_rows = 0;             // rows with spare sums (more products in some tile than a lane takes)
     DevPtr<int32_t> d_lptr;        // [nblocks + 1] first long row of every bin in d_lrow / d_lcnt
     DevPtr<uint32_t> d_lrow;       // [long_rows] row in bin << 16 | first spare slot
     DevPtr<int32_t> d_lcnt;        // [long_rows] spare slots of the row
-    // ... its scattered flavour: the product launch stores in bin order (d_offset, d_first_run; bit 15 of d_c16), the sum launch streams d_prod + d_r16 (here:
-    // accumulator numbers) bin by bin; d_lrow = [nblocks * 1024] row << 17 | first spare accumulator << 7 | how many
-    bool scatter_mode = false;
+};
+// ... its scattered flavour (mode 5): the product launch stores in bin order (d_offset, d_first_run; bit 15 of d_c16), the sum launch
+// streams d_prod + d_acc16 bin by bin.  bin_rows (4096 | 8192 | 16384) ... d_brow: as in BinnedPlan, the panels padded to multiples of 512
+struct ScatteredPlan {
+    int bin_rows = 0, npanels = 0, nblocks = 0, splits = 1;
+    int64_t padded = 0;
+    DevPtr<uint16_t> d_c16;
+    DevPtr<float> d_pvals;
+    DevPtr<int32_t> d_pbase, d_brow;
+    DevPtr<float> d_prod;          // [bm_alloc] scratch of a run: the products, bin-major
     DevPtr<int32_t> d_offset;      // [runs] bin-major minus panel-major position of a run (a nonempty tile, or a panel's pad slots)
-    DevPtr<int32_t> d_first_run;      // [padded / 512] run of every 512-entry block's first entry (minus one where it starts a run)
+    DevPtr<int32_t> d_first_run;   // [padded / 512] run of every 512-entry block's first entry (minus one where it starts a run)
     int64_t runs = 0;
-    DevPtr<int32_t> d_bbase;       // [nblocks + 1] first entry of every bin in d_prod / d_r16 (multiples of 256)
+    DevPtr<int32_t> d_bbase;       // [nblocks + 1] first entry of every bin in d_prod / d_acc16 (multiples of 256)
     DevPtr<int32_t> d_bcnt;        // [nblocks] entries of the bin
     DevPtr<int32_t> d_nlong;       // [nblocks] rows with spare accumulators (-1: the bin adds with LDS atomics)
     int64_t bm_entries = 0;        // entries of the bin-major arrays
     int64_t bm_alloc = 0;          // ... as allocated: bm_entries + the slack of the sum launch's read-ahead (kernels_binned.hip kBsSlack)
+    DevPtr<uint16_t> d_acc16;      // [bm_alloc] accumulator number of every product, bin-major
+    DevPtr<uint32_t> d_pool_rows;  // [nblocks * 1024] row << 17 | first spare accumulator << 7 | how many
+    int flagged_bins = 0;          // bins that ran out of spare accumulators (they add with LDS atomics)
+    int long_rows = 0;             // rows with spare accumulators
+};
+// One of the handle's two SPMV_PANEL slots: `layout` says which ONE of the four members is populated (none: not planned).
+struct PanelPlan {
+    PanelLayout layout = PanelLayout::none;
+    ValuesStamp stamp;             // which state of vals the layout's d_pvals is a copy of
+    SweepPlan sweep; SortedBlocksPlan sorted; BinnedPlan binned; ScatteredPlan scattered;
 };
 
 // SPMV_XSKIP (kernels_xskip.hip): the matrix in input-major segments per block of 1024 outputs
@@ -288,34 +312,44 @@ int launch_wave(spmv_csr &h, const float *x, float *y, bool pipelined, hipStream
 int plan_wave(spmv_csr &h, hipStream_t s);
 int launch_vector(const spmv_csr &h, const float *x, float *y, hipStream_t s);
 int launch_adaptive(const spmv_csr &h, const float *x, float *y, bool tiled, hipStream_t s);
-int launch_panel(const spmv_csr &h, const float *x, float *y, hipStream_t s);
 
 int plan_xskip(spmv_csr &h, hipStream_t s);
 int launch_xskip(const spmv_csr &h, const float *x, float *y, hipStream_t s);
-int plan_panel(spmv_csr &h, hipStream_t s);
-int panel_launches(const PanelPlan &p);
 int plan_vector(spmv_csr &h, hipStream_t s);
 int plan_adaptive(spmv_csr &h, bool tiled, hipStream_t s);
 // TILED with exactly these parameters (spmv_csr_plan_set); block 256|512|1024, maxpass >= 1
 int plan_tiled_with(spmv_csr &h, int block, int maxpass, bool col16, hipStream_t s);
 int plan_adaptive_with(spmv_csr &h, int block, hipStream_t s);
-int plan_panel_with(spmv_csr &h, int pw_bits, int waves_per_launch, int mode, hipStream_t s);   // 0 = library default
-int build_panel(spmv_csr &h, PanelPlan &dst, int pw_bits, int waves_per_launch, int mode, hipStream_t s);
+int build_panel(spmv_csr &h, PanelPlan &dst, int want_bits, int want_waves, int want_mode, hipStream_t s);   // params[4..6]; 0 = library default
 int refresh_panel(spmv_csr &h, PanelPlan &dst, hipStream_t s);
 int launch_panel_plan(const spmv_csr &h, const PanelPlan &p, const float *x, float *y, hipStream_t s);
+void panel_params(const PanelPlan &p, int32_t params[8]);   // fills params[4..6]
+int64_t panel_plan_bytes(const PanelPlan &p, int64_t nnz);
+void panel_describe(const PanelPlan &p, const spmv_csr &h, char *buf, int n);
 // kernels_panel.hip helpers shared with kernels_colsort.hip
 int panel_row_blocks(const spmv_csr &h, int64_t nb0, int cap, hipStream_t s, DevPtr<int32_t> &brow, int32_t *nblocks);
 int panel_rowloc(const spmv_csr &h, const int32_t *d_brow, int nblocks, uint16_t *d_rowloc, hipStream_t s);
 // kernels_colsort.hip: SPMV_PANEL mode 3
-int plan_colsort(spmv_csr &h, PanelPlan &p, int want_rows, int want_waves, hipStream_t s);
-double colsort_model_cost(const PanelPlan &p, int64_t nnz);
+int plan_colsort(spmv_csr &h, SortedBlocksPlan &p, int want_rows, int want_waves, hipStream_t s);
+void colsort_params(const SortedBlocksPlan &p, int32_t params[8]);
+int64_t colsort_plan_bytes(const SortedBlocksPlan &p, int64_t nnz);
+void colsort_describe(const SortedBlocksPlan &p, const spmv_csr &h, char *buf, int n);
+double colsort_model_cost(const SortedBlocksPlan &p, int64_t nnz);
 double colsort_cost(int rows_per_block, double lines_per_nnz, double tail_frac);
 int colsort_probe(const spmv_csr &h, hipStream_t s, double *long_frac, double *wide_frac, double *lines_per_nnz);
-int launch_colsort(const spmv_csr &h, const PanelPlan &p, const float *x, float *y, hipStream_t s);
-// kernels_binned.hip: SPMV_PANEL mode 4
+int launch_colsort(const spmv_csr &h, const SortedBlocksPlan &p, const float *x, float *y, hipStream_t s);
+// kernels_binned.hip: SPMV_PANEL modes 4 and 5
 int panel_tile_ptr(const spmv_csr &h, const int32_t *d_brow, int nblocks, int pw_bits, int np, int32_t *d_tile_ptr, hipStream_t s);
-int plan_binned(spmv_csr &h, PanelPlan &p, int want_rows, bool scatter, hipStream_t s);
-int launch_binned(const spmv_csr &h, const PanelPlan &p, const float *x, float *y, hipStream_t s);
+int plan_binned(spmv_csr &h, BinnedPlan &p, int want_rows, hipStream_t s);
+int launch_binned(const spmv_csr &h, const BinnedPlan &p, const float *x, float *y, hipStream_t s);
+void binned_params(const BinnedPlan &p, int32_t params[8]);
+int64_t binned_plan_bytes(const BinnedPlan &p, int64_t nnz);
+void binned_describe(const BinnedPlan &p, const spmv_csr &h, char *buf, int n);
+int plan_scatter(spmv_csr &h, ScatteredPlan &p, int want_rows, hipStream_t s);
+int launch_scatter(const spmv_csr &h, const ScatteredPlan &p, const float *x, float *y, hipStream_t s);
+void scatter_params(const ScatteredPlan &p, int32_t params[8]);
+int64_t scatter_plan_bytes(const ScatteredPlan &p, int64_t nnz);
+void scatter_describe(const ScatteredPlan &p, const spmv_csr &h, char *buf, int n);
 double binned_tile_nonzeros(const spmv_csr &h, int bin_rows);
 // kernels_spmm.hip: spmv_csr_spmm
 int plan_spmm(spmv_csr &h, hipStream_t s);
@@ -347,6 +381,8 @@ int require_fresh_values(const spmv_csr &h, const ValuesStamp &st, hipStream_t s
 int launch_column_range(const spmv_csr &h, int32_t *d_out2, hipStream_t s);
 // in-place exclusive scan of n int32 (one 1024-thread workgroup); the total goes to *d_total
 int exclusive_scan_i32(int32_t *d_data, int64_t n, int32_t *d_total, hipStream_t s);
+// ... for offset tables the host sizes arrays from: the total also comes to *total_host and, where append_total, into d_data[n]; waits for s
+int scan_offsets_i32(int32_t *d_data, int64_t n, int32_t *d_total, bool append_total, hipStream_t s, int32_t *total_host);
 
 int tcsr_from_dense(int M, int N, const float *d_A, hipStream_t s, spmv_tcsr_t **out);
 int tcsr_run(const spmv_tcsr &h, const float *d_x, float *d_y, hipStream_t s);

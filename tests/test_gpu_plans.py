@@ -325,3 +325,60 @@ def test_replanning_and_destroying_return_device_memory(pkg, oracle, gpu):
         torch.cuda.synchronize()
         free.append(torch.cuda.mem_get_info()[0])
     assert abs(free[-1] - free[0]) <= 2 << 20, free
+
+
+def test_stale_panel_plans_are_rebuilt_as_planned_in_both_slots(pkg, oracle, gpu):
+    """spmv_csr_plan on a stale plan rebuilds the layout it finds -- every mode of the panel family, in the PANEL slot
+    and in the slot SPMV_AUTO keeps for itself -- with the parameters it was planned with: plan_params, plan_describe
+    and plan_bytes read as before (they depend on the matrix's structure alone), y follows the new values, and a second
+    handle planned with plan_like reports the same and gives the same bits.  32768 x 70001, rows of 8..31 nonzeros and
+    every 2048th row 6000 long, columns uniform: three panels of 32768 columns, several bins and blocks, long rows for
+    the sorted blocks' tails and the binned layouts' spare sums."""
+    import torch
+    capi = pkg.capi
+    rows, cols = 32768, 70001
+    rng = np.random.Generator(np.random.PCG64(70001))
+    L = rng.integers(8, 32, size=rows)
+    L[::2048] = 6000
+    rp = np.concatenate([[0], np.cumsum(L)]).astype(np.int32)
+    ci = np.concatenate([np.sort(rng.choice(cols, size=int(l), replace=False)) for l in L]).astype(np.int32)
+    va = rng.uniform(-1, 1, size=len(ci)).astype(np.float32)
+    va2 = rng.uniform(-1, 1, size=len(ci)).astype(np.float32)
+    x = rng.uniform(-1, 1, size=cols).astype(np.float32)
+    ref, ref2 = oracle.spmv_f64(rp, ci, va, x), oracle.spmv_f64(rp, ci, va2, x)
+    prob = DeviceProblem(pkg, gpu, rows, cols, rp, ci, va, x)
+    A = prob.A
+    d_va2, d_va1 = torch.from_numpy(va2).to(gpu), torch.from_numpy(va).to(gpu)
+
+    def reports(M, slot):
+        return M.plan_params(slot), M.plan_describe(slot), M.plan_bytes(slot)
+
+    def run(M, slot):
+        prob.d_y.fill_(float("nan"))
+        M.run(slot, prob.d_x, prob.d_y)
+        torch.cuda.synchronize()
+        return prob.d_y[:rows].cpu().numpy()
+
+    for slot in (capi.PANEL, capi.AUTO):
+        for mode in (1, 2, 3, 4, 5):
+            what = f"{'auto' if slot == capi.AUTO else 'panel'} slot, mode {mode}"
+            prob.d_va.copy_(d_va1)
+            A.plan_set(slot, [capi.PANEL, 0, 0, 0, 0, 0, mode, 0])
+            planned = reports(A, slot)
+            assert planned[0][0] == capi.PANEL and planned[0][6] == mode, (what, planned)
+            assert_close_to_oracle(run(A, slot), *ref, what)
+            prob.d_va.copy_(d_va2)
+            A.values_changed()
+            with pytest.raises(capi.SpmvError) as ei:
+                A.run(slot, prob.d_x, prob.d_y)
+            assert ei.value.status == capi.ERR_STALE_PLAN, what
+            A.plan(slot)
+            assert reports(A, slot) == planned, what
+            y = run(A, slot)
+            assert_close_to_oracle(y, *ref2, what + ", refreshed")
+            B = capi.CsrMatrix.from_device(rows, cols, prob.d_rp, prob.d_ci, prob.d_va)
+            B.plan_like(A, slot)
+            assert reports(B, slot) == planned, what
+            assert np.array_equal(run(B, slot).view(np.uint32), y.view(np.uint32)), what
+            B.close()
+    A.close()
