@@ -253,6 +253,7 @@ SPMV_API int64_t spmv_csr_transpose_map_bytes(const spmv_csr_t *t);
  *   SPMV_XSKIP                                ceil(rows / 1024) x cols <= 2^27 table entries; rows sorted, duplicate-free
  *   spmv_csr_spmm                             rows x lanes per row < 2^32 (one launch): any handle up to k = 8,
  *                                             rows < 2^30 up to k = 16, < 2^29 up to k = 32, < 2^28 up to k = 64
+ *   spmv_csr_sddmm                            the same as spmv_csr_spmm (rows x lanes per row < 2^32); any nnz < 2^31
  *   spmv_csr_transpose                        any handle
  * (tests/test_gpu_limits.py runs every path on either side of these.) */
 SPMV_API int spmv_csr_plan(spmv_csr_t *h, int variant, void *stream);
@@ -340,6 +341,38 @@ SPMV_API int spmv_csr_spmm_plan(spmv_csr_t *h, void *stream);
 SPMV_API int spmv_csr_spmm(spmv_csr_t *h, int k, const float *d_X, int64_t ldx, float *d_Y, int64_t ldy, void *stream);
 SPMV_API int64_t spmv_csr_spmm_plan_bytes(const spmv_csr_t *h);
 SPMV_API int spmv_csr_spmm_describe(const spmv_csr_t *h, char *buf, int n);
+
+/* ---- SDDMM: a dense-dense product sampled at the handle's pattern ----------------------------------------------
+ * out[n] = sum over c < k of U[i*ldu + c] * X[j*ldx + c] for every storage position n in [row_ptr[i], row_ptr[i+1]) with
+ * j = col_idx[n]: the entries of U X^T at the stored nonzeros, in the storage order of h.  U is rows rows of ldu floats,
+ * row-major, X is cols rows of ldx floats, out holds nnz floats.  With Y = A X (spmv_csr_spmm) and a gradient dY this is
+ * the gradient for the VALUES of A, dvals = sddmm(dY, X); the gradient for X is spmv_csr_spmm on the transposed handle.
+ * Every stored nonzero gets its own result: a column repeated inside a row gives the same number at each occurrence, rows
+ * need not be sorted, IEEE rules hold and subnormals are kept.  An X row no nonzero refers to and the U row of an empty
+ * row never reach a result.  vals is never read, so d_out may be the caller's own borrowed vals array (followed by
+ * spmv_csr_values_changed).  Nothing outside out[0, nnz) is written.
+ * Limits: 1 <= k <= 64, ldu >= k, ldx >= k, rows x lanes per row < 2^32 ("Limits of the layouts" above; any nnz < 2^31:
+ * byte offsets into col_idx and out are 64-bit); d_U and d_X 16-byte aligned (d_U may be NULL when rows == 0, d_X when
+ * cols == 0, d_out when nnz == 0); d_out needs only its natural 4 bytes -- a row block may write into out_full +
+ * first_nnz.  Any ld >= k works; ldu % 4 == 0 and ldx % 4 == 0 together are the fast path (16-byte loads; a run then
+ * reads the whole 16-byte block that holds column k-1 of a row).  U[i*ldu + c] and X[j*ldx + c] for c >= k are never
+ * read into a sum (they are skipped, not multiplied by zero).
+ * The plan is spmv_csr_spmm_plan's (a function of row_ptr alone; one plan serves both calls); SPMV_ERR_NOT_PLANNED
+ * without it.  A row of more than 512 nonzeros is processed per plan piece; results are independent, so there is no
+ * scratch and runs of one handle need no stream order among themselves.  Asynchronous, allocates nothing, never waits:
+ * graph-capturable once the plan exists.  A null handle, k or an ld out of range, a misaligned or missing pointer or
+ * another current device than the handle's is SPMV_ERR_INVALID with a message that names the function; nothing is
+ * launched and out is untouched.
+ * The order of the sums is part of the interface.  With V = the power of two >= ceil(k / 4) (1, 2, 4, 8, 16):
+ *     p_s = +0;  p_s = fma(U[i][c], X[j][c], p_s) for c = 4s, 4s+1, 4s+2, 4s+3 while c < k        (s = 0 .. V-1)
+ *     for m = V/2, V/4, ..., 1:  p_s = p_s + p_(s xor m) for every s;      out[n] = p_0
+ * So out[n] is a pure function of the k floats of its U row, the k floats of its X row and k: not of ldu or ldx, of the
+ * fast or slow load path, of the nonzero's position in its row or the row's length, of whether the row went in pieces,
+ * of what other rows hold, of the stream or of the handle.  It is symmetric in its operands (fma(u, x, p) == fma(x, u,
+ * p)): with T = transpose(A) and perm = argsort(a.col_idx, stable), sddmm(T, X, U)[i] == sddmm(A, U, X)[perm[i]] bit for
+ * bit (for results that are not NaN; a NaN is a NaN on both sides). */
+SPMV_API int spmv_csr_sddmm(spmv_csr_t *h, int k, const float *d_U, int64_t ldu, const float *d_X, int64_t ldx,
+                            float *d_out, void *stream);
 
 /* ---- dense baselines (reference slots cublas / naive / tiling) ---------
  * y[i] = sum_j x[j] * A[j*N+i] on the dense device matrix.

@@ -55,6 +55,7 @@ SIGNATURES = {
     "spmv_csr_spmm": (C.c_int, [_H, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, _vp]),
     "spmv_csr_spmm_plan_bytes": (C.c_int64, [_H]),
     "spmv_csr_spmm_describe": (C.c_int, [_H, C.c_char_p, C.c_int]),
+    "spmv_csr_sddmm": (C.c_int, [_H, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, _f32p, _vp]),
     "spmv_csr_plan_get": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int32)]),
     "spmv_csr_plan_set": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int32), _vp]),
     "spmv_csr_plan_like": (C.c_int, [_H, _H, C.c_int, _vp]),
@@ -268,6 +269,24 @@ class CsrMatrix:
         if n < 0:
             check(n)
         return n
+
+    # -- SDDMM: U X^T sampled at the pattern (spmv_csr_sddmm; the plan is spmm_plan's) ------------------------------
+    def sddmm(self, U, X, out, stream=None) -> None:
+        """Enqueue out[n] = U[row(n), :k] . X[col(n), :k] for every stored nonzero n, k = U.shape[1] = X.shape[1].
+        U: (rows, k) and X: (cols, k) 2-D float32 device tensors with stride(1) == 1 (the leading dimensions are their
+        stride(0)); out: nnz float32, contiguous, in this matrix's storage order."""
+        import torch
+        for name, t in (("U", U), ("X", X)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1:
+                raise ValueError(f"sddmm: {name} must be a 2-D float32 tensor with stride(1) == 1")
+        if not isinstance(out, torch.Tensor) or out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("sddmm: out must be a contiguous 1-D float32 tensor")
+        k = U.shape[1]
+        if U.shape[0] != self.rows or X.shape[0] != self.cols or X.shape[1] != k or out.shape[0] != self.nnz:
+            raise ValueError(f"sddmm: U {tuple(U.shape)}, X {tuple(X.shape)} and out {tuple(out.shape)} do not fit a "
+                             f"{self.rows} x {self.cols} matrix with {self.nnz} nonzeros")
+        check(lib().spmv_csr_sddmm(self._h, k, _ptr(U), U.stride(0), _ptr(X), X.stride(0), _ptr(out),
+                                   _stream_handle(stream)))
 
     def values_changed(self) -> None:
         """The caller rewrote vals (borrowed arrays): plans that hold a copy of them are stale from here on."""

@@ -583,6 +583,29 @@ int spmv_csr_spmm_describe(const spmv_csr_t *h, char *buf, int n)
     return SPMV_OK;
 }
 
+int spmv_csr_sddmm(spmv_csr_t *h, int k, const float *d_U, int64_t ldu, const float *d_X, int64_t ldx, float *d_out, void *stream)
+{
+    if (!h) { set_error("spmv_csr_sddmm: null handle"); return SPMV_ERR_INVALID; }
+    if (k < 1 || k > 64 || ldu < k || ldx < k) {
+        set_error("spmv_csr_sddmm: k = %d, ldu = %lld, ldx = %lld (need 1 <= k <= 64, ldu >= k, ldx >= k)", k, (long long)ldu,
+                  (long long)ldx);
+        return SPMV_ERR_INVALID;
+    }
+    if ((!d_U && h->rows > 0) || (!d_X && h->cols > 0) || (!d_out && h->nnz > 0)) {
+        set_error("spmv_csr_sddmm: null U, X or out");
+        return SPMV_ERR_INVALID;
+    }
+    if (!aligned16(d_U) || !aligned16(d_X)) { set_error("spmv_csr_sddmm: U and X must be 16-byte aligned"); return SPMV_ERR_INVALID; }
+    if (reinterpret_cast<uintptr_t>(d_out) % 4 != 0) { set_error("spmv_csr_sddmm: out must be 4-byte aligned"); return SPMV_ERR_INVALID; }
+    if (ldu > INT64_MAX / 4 / (h->rows > 0 ? h->rows : 1) || ldx > INT64_MAX / 4 / (h->cols > 0 ? h->cols : 1)) {
+        set_error("spmv_csr_sddmm: ldu = %lld or ldx = %lld overflows 64-bit byte offsets", (long long)ldu, (long long)ldx);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(h->device, "spmv_csr_sddmm")) return rc;
+    if (!h->plan_spmm.ready) { set_error("spmv_csr_sddmm used before spmv_csr_spmm_plan"); return SPMV_ERR_NOT_PLANNED; }
+    return launch_sddmm(*h, k, d_U, ldu, d_X, ldx, d_out, (hipStream_t)stream);
+}
+
 int spmv_csr_values_changed(spmv_csr_t *h)
 {
     if (!h) { set_error("spmv_csr_values_changed: null handle"); return SPMV_ERR_INVALID; }

@@ -240,7 +240,8 @@ struct WavePlan {
     int64_t blocks = 0, win_blocks = 0;   // blocks of block_rows rows, and how many have a window
 };
 
-// spmv_csr_spmm (kernels_spmm.hip): the rows too long for one lane group, cut into pieces at plan-fixed boundaries
+// spmv_csr_spmm (kernels_spmm.hip) and spmv_csr_sddmm (kernels_sddmm.hip): the rows too long for one lane group, cut into
+// pieces at plan-fixed boundaries
 struct SpmmPlan {
     bool ready = false;
     int n_long = 0, pieces = 0;
@@ -355,6 +356,8 @@ double binned_tile_nonzeros(const spmv_csr &h, int bin_rows);
 int plan_spmm(spmv_csr &h, hipStream_t s);
 int launch_spmm(const spmv_csr &h, int k, const float *X, int64_t ldx, float *Y, int64_t ldy, hipStream_t s);
 int64_t spmm_plan_bytes(const spmv_csr &h);
+// kernels_sddmm.hip: spmv_csr_sddmm (on the plan of plan_spmm)
+int launch_sddmm(const spmv_csr &h, int k, const float *U, int64_t ldu, const float *X, int64_t ldx, float *out, hipStream_t s);
 // kernels_transpose.hip: spmv_csr_transpose / spmv_csr_transpose_values
 int transpose(const spmv_csr &a, bool keep_map, hipStream_t s, spmv_csr_t **out);
 int transpose_values(spmv_csr &t, const spmv_csr &a, hipStream_t s);

@@ -1,0 +1,78 @@
+"""Y = A X as a differentiable torch operation, on the three primitives of include/spmv_hip.h that a sparse layer needs:
+
+    forward    Y     = A X                 spmv_csr_spmm on A
+    backward   dX    = A^T dY              spmv_csr_spmm on T = transpose(A), its values refreshed by spmv_csr_transpose_values
+               dvals = (dY X^T) at A's pattern     spmv_csr_sddmm on A
+
+Plumbing that shows the primitives compose, not a framework: fp32, one device, a batch of k <= 64 columns.  Every product
+runs in the HIP library; there is no torch fallback.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import capi
+
+MAX_K = 64
+
+
+def _operand(t, name: str, rows: int):
+    """t as the library takes it: 2-D float32, stride(1) == 1, stride(0) >= k, 16-byte aligned (copied if it is not)."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
+        raise ValueError(f"SparseMatmul: {name} must be a 2-D float32 tensor")
+    if t.shape[0] != rows:
+        raise ValueError(f"SparseMatmul: {name} has {t.shape[0]} rows, the matrix needs {rows}")
+    if not 1 <= t.shape[1] <= MAX_K:
+        raise ValueError(f"SparseMatmul: {name} has {t.shape[1]} columns (1 <= k <= {MAX_K})")
+    if t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0:
+        return t
+    return torch.empty(t.shape, dtype=t.dtype, device=t.device).copy_(t)
+
+
+class SparseMatmul(torch.autograd.Function):
+    """``SparseMatmul.apply(layer, vals, X)`` = A X with A's values ``vals`` (the leaf ``layer`` borrows)."""
+
+    @staticmethod
+    def forward(ctx, layer, vals, X):
+        X = _operand(X, "X", layer.A.cols)
+        Y = torch.empty((layer.A.rows, X.shape[1]), dtype=torch.float32, device=X.device)
+        layer.A.spmm(X, Y)
+        ctx.layer = layer
+        ctx.save_for_backward(X)
+        return Y
+
+    @staticmethod
+    def backward(ctx, dY):
+        layer = ctx.layer
+        X, = ctx.saved_tensors
+        dY = _operand(dY, "dY", layer.A.rows)
+        dvals = dX = None
+        if ctx.needs_input_grad[1]:
+            dvals = torch.empty(layer.A.nnz, dtype=torch.float32, device=dY.device)
+            layer.A.sddmm(dY, X, dvals)
+        if ctx.needs_input_grad[2]:
+            dX = torch.empty((layer.A.cols, dY.shape[1]), dtype=torch.float32, device=dY.device)
+            layer.T.transpose_values(layer.A)      # A's values as they are now
+            layer.T.spmm(dY, dX)
+        return None, dvals, dX
+
+
+class SparseLayer:
+    """A rows x cols CSR matrix whose values are a torch leaf.  Borrows ``row_ptr``, ``col_idx`` (int32) and ``vals``
+    (float32, may require grad), all on one device; owns the handle of A, of T = A^T (with the map that refreshes T's
+    values) and both SpMM plans.  The pattern is fixed; ``vals`` may be updated in place (an optimizer step): the next
+    forward and backward follow the new values without a new plan."""
+
+    def __init__(self, rows: int, cols: int, row_ptr, col_idx, vals):
+        self.vals = vals
+        self.A = capi.CsrMatrix.from_device(rows, cols, row_ptr, col_idx, vals)
+        self.T = self.A.transpose(keep_map=True)
+        self.A.spmm_plan()
+        self.T.spmm_plan()
+
+    def __call__(self, X):
+        return SparseMatmul.apply(self, self.vals, X)
+
+    def close(self) -> None:
+        self.T.close()
+        self.A.close()
