@@ -254,6 +254,8 @@ SPMV_API int64_t spmv_csr_transpose_map_bytes(const spmv_csr_t *t);
  *   spmv_csr_spmm                             rows x lanes per row < 2^32 (one launch): any handle up to k = 8,
  *                                             rows < 2^30 up to k = 16, < 2^29 up to k = 32, < 2^28 up to k = 64
  *   spmv_csr_sddmm                            the same as spmv_csr_spmm (rows x lanes per row < 2^32); any nnz < 2^31
+ *   spmv_csr_row_softmax                      any handle (rows, nnz < 2^31; a wavefront per 64 rows, byte offsets 64-bit)
+ *   spmv_csr_row_softmax_backward             the same as spmv_csr_row_softmax
  *   spmv_csr_transpose                        any handle
  * (tests/test_gpu_limits.py runs every path on either side of these.) */
 SPMV_API int spmv_csr_plan(spmv_csr_t *h, int variant, void *stream);
@@ -373,6 +375,51 @@ SPMV_API int spmv_csr_spmm_describe(const spmv_csr_t *h, char *buf, int n);
  * bit (for results that are not NaN; a NaN is a NaN on both sides). */
 SPMV_API int spmv_csr_sddmm(spmv_csr_t *h, int k, const float *d_U, int64_t ldu, const float *d_X, int64_t ldx,
                             float *d_out, void *stream);
+
+/* ---- Row softmax over the handle's pattern, forward and backward -------------------------------------------------
+ * The step between the SDDMM that makes the scores of a sparse attention and the SpMM that applies them:
+ *     forward    S = sddmm(Q, K);  P = row_softmax(scale, S);  O = spmm(P, V)
+ *     backward   dV = spmm(P^T, dO);  dP = sddmm(dO, V);  dS = row_softmax_backward(scale, P, dP);  dQ = spmm(dS, K);
+ *                dK = spmm(dS^T, Q)
+ * all on one pattern, one SpMM plan and one transposed handle (spmv-test_amd/sparse_attention.py composes them).  Every
+ * array holds nnz floats in the storage order of h.  col_idx and vals are never read: only row_ptr and the SpMM plan.
+ * spmv_csr_row_softmax, for every row i with L = row_ptr[i+1] - row_ptr[i] > 0 and n in [row_ptr[i], row_ptr[i+1]):
+ *     t[n] = scale * scores[n]         (one fp32 rounding; never fused into the subtraction)
+ *     M    = max t                      (fmaxf: a NaN is ignored here)
+ *     e[n] = expf(t[n] - M)             (the device library's expf, 1 ulp)
+ *     S    = sum e                      (the order below)
+ *     r    = 1.0f / S                   (IEEE division)
+ *     out[n] = e[n] * r
+ * An empty row writes nothing.  IEEE rules decide every special case and agree with torch.softmax: t = -Inf beside a
+ * finite maximum gives exactly +0; a row that holds a NaN or a +Inf (or whose scale * s overflows to +Inf) is NaN
+ * throughout; a row whose every entry is -Inf is NaN throughout; subnormal results are kept.
+ * spmv_csr_row_softmax_backward, with P and dP whatever the caller passes (P need not come from the forward call):
+ *     dot = sum over the row of fp32(P[n] * dP[n])             (the products rounded, then summed in the order below)
+ *     dS[n] = scale * (P[n] * (dP[n] - dot))                   (three roundings)
+ * The order of the sums is part of the interface.  A piece is a whole row of at most 512 entries, or, in a row of more
+ * (the SpMM plan's row_cap), entries [512 j, 512 j + 512) of the row; x_0 .. x_(len-1) are a piece's terms:
+ *     q_l = +0;  q_l = q_l + x_(l + 64 i) for i = 0, 1, ... while l + 64 i < len            (l = 0 .. 63)
+ *     for m = 32, 16, ..., 1:  q_l = q_l + q_(l xor m) for every l;      the piece's sum is q_0
+ * and a row of several pieces adds its pieces' sums in piece order, starting from +0.  The maximum is exact in any order.
+ * So a row's results are a pure function of its L inputs in storage order, of L and of scale: not of other rows, of the
+ * row's position in the matrix, of the stream, of the handle, of running in place, or of whether the handle is a row
+ * block (row_ptr rebased, arrays at array_full + first_nnz) or the whole matrix.  (A short row runs in a group of
+ * G = pow2 >= L lanes; the lanes it leaves out would hold +0, and adding +0 changes no q, so the bits are the ones above.)
+ * Long rows take the three-read form: the pieces' maxima, the row's maximum, the pieces' sums of expf(t - M), the row's
+ * sum, then the store (backward: the pieces' dots, the row's dot, the store); rows of at most 512 entries are read once,
+ * held in registers and written once.  The scratch of the long rows is the SpMM plan's (64 floats per piece), so runs
+ * of one handle -- these two calls and spmv_csr_spmm alike -- must be stream-ordered; a handle without a long row uses none.
+ * Aliasing: d_out == d_scores, d_dS == d_P and d_dS == d_dP are allowed (the identical pointer only; a partial overlap
+ * is the caller's error and is not checked), and each array may be the handle's own borrowed vals (then follow with
+ * spmv_csr_values_changed).  Every pointer needs only its natural 4 bytes; nothing outside [0, nnz) is written.
+ * Asynchronous, allocates nothing, never waits: graph-capturable once spmv_csr_spmm_plan has run; SPMV_ERR_NOT_PLANNED
+ * without it.  Any handle is accepted (rows, nnz < 2^31; byte offsets are 64-bit).  A null handle, a null array while
+ * nnz > 0, a pointer that is not 4-byte aligned, a scale that is not finite or another current device than the handle's
+ * is SPMV_ERR_INVALID with a message that names the function; nothing is launched and the output is untouched.  With
+ * nnz == 0 the call returns SPMV_OK whatever the pointers are. */
+SPMV_API int spmv_csr_row_softmax(spmv_csr_t *h, float scale, const float *d_scores, float *d_out, void *stream);
+SPMV_API int spmv_csr_row_softmax_backward(spmv_csr_t *h, float scale, const float *d_P, const float *d_dP,
+                                           float *d_dS, void *stream);
 
 /* ---- dense baselines (reference slots cublas / naive / tiling) ---------
  * y[i] = sum_j x[j] * A[j*N+i] on the dense device matrix.

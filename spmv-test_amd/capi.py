@@ -56,6 +56,8 @@ SIGNATURES = {
     "spmv_csr_spmm_plan_bytes": (C.c_int64, [_H]),
     "spmv_csr_spmm_describe": (C.c_int, [_H, C.c_char_p, C.c_int]),
     "spmv_csr_sddmm": (C.c_int, [_H, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, _f32p, _vp]),
+    "spmv_csr_row_softmax": (C.c_int, [_H, C.c_float, _f32p, _f32p, _vp]),
+    "spmv_csr_row_softmax_backward": (C.c_int, [_H, C.c_float, _f32p, _f32p, _f32p, _vp]),
     "spmv_csr_plan_get": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int32)]),
     "spmv_csr_plan_set": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int32), _vp]),
     "spmv_csr_plan_like": (C.c_int, [_H, _H, C.c_int, _vp]),
@@ -287,6 +289,32 @@ class CsrMatrix:
                              f"{self.rows} x {self.cols} matrix with {self.nnz} nonzeros")
         check(lib().spmv_csr_sddmm(self._h, k, _ptr(U), U.stride(0), _ptr(X), X.stride(0), _ptr(out),
                                    _stream_handle(stream)))
+
+    # -- row softmax over the pattern and its backward (spmv_csr_row_softmax; the plan is spmm_plan's) ---------------
+    def _nnz_arrays(self, what: str, **arrays) -> None:
+        import torch
+        for name, t in arrays.items():
+            if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"{what}: {name} must be a contiguous 1-D float32 tensor")
+            if t.shape[0] != self.nnz:
+                raise ValueError(f"{what}: {name} holds {t.shape[0]} floats, the matrix has {self.nnz} nonzeros")
+
+    def row_softmax(self, scores, out, scale: float = 1.0, stream=None) -> None:
+        """Enqueue out = softmax of scale * scores over every row of the pattern (nnz float32 each, in this matrix's
+        storage order; ``out`` may be ``scores``).  An empty row writes nothing."""
+        import math
+        self._nnz_arrays("row_softmax", scores=scores, out=out)
+        if not math.isfinite(scale):
+            raise ValueError(f"row_softmax: scale = {scale} is not finite")
+        check(lib().spmv_csr_row_softmax(self._h, scale, _ptr(scores), _ptr(out), _stream_handle(stream)))
+
+    def row_softmax_backward(self, P, dP, dS, scale: float = 1.0, stream=None) -> None:
+        """Enqueue dS[n] = scale * P[n] * (dP[n] - sum over the row of P dP) (``dS`` may be ``P`` or ``dP``)."""
+        import math
+        self._nnz_arrays("row_softmax_backward", P=P, dP=dP, dS=dS)
+        if not math.isfinite(scale):
+            raise ValueError(f"row_softmax_backward: scale = {scale} is not finite")
+        check(lib().spmv_csr_row_softmax_backward(self._h, scale, _ptr(P), _ptr(dP), _ptr(dS), _stream_handle(stream)))
 
     def values_changed(self) -> None:
         """The caller rewrote vals (borrowed arrays): plans that hold a copy of them are stale from here on."""

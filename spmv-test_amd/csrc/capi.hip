@@ -606,6 +606,35 @@ int spmv_csr_sddmm(spmv_csr_t *h, int k, const float *d_U, int64_t ldu, const fl
     return launch_sddmm(*h, k, d_U, ldu, d_X, ldx, d_out, (hipStream_t)stream);
 }
 
+// what spmv_csr_row_softmax and its backward check alike: a finite scale; with nnz > 0 every array present and 4-byte
+// aligned; the handle's device current; the SpMM plan made
+static int softmax_args(const spmv_csr_t *h, float scale, const void *const *arrays, int n_arrays, const char *what)
+{
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (!(scale - scale == 0.0f)) { set_error("%s: scale must be finite", what); return SPMV_ERR_INVALID; }
+    for (int i = 0; i < n_arrays && h->nnz > 0; ++i) {
+        if (!arrays[i]) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
+        if (reinterpret_cast<uintptr_t>(arrays[i]) % 4 != 0) { set_error("%s: every array must be 4-byte aligned", what); return SPMV_ERR_INVALID; }
+    }
+    if (int rc = require_current(h->device, what)) return rc;
+    if (!h->plan_spmm.ready) { set_error("%s used before spmv_csr_spmm_plan", what); return SPMV_ERR_NOT_PLANNED; }
+    return SPMV_OK;
+}
+
+int spmv_csr_row_softmax(spmv_csr_t *h, float scale, const float *d_scores, float *d_out, void *stream)
+{
+    const void *arrays[] = {d_scores, d_out};
+    if (int rc = softmax_args(h, scale, arrays, 2, "spmv_csr_row_softmax")) return rc;
+    return launch_row_softmax(*h, scale, d_scores, d_out, (hipStream_t)stream);
+}
+
+int spmv_csr_row_softmax_backward(spmv_csr_t *h, float scale, const float *d_P, const float *d_dP, float *d_dS, void *stream)
+{
+    const void *arrays[] = {d_P, d_dP, d_dS};
+    if (int rc = softmax_args(h, scale, arrays, 3, "spmv_csr_row_softmax_backward")) return rc;
+    return launch_row_softmax_backward(*h, scale, d_P, d_dP, d_dS, (hipStream_t)stream);
+}
+
 int spmv_csr_values_changed(spmv_csr_t *h)
 {
     if (!h) { set_error("spmv_csr_values_changed: null handle"); return SPMV_ERR_INVALID; }

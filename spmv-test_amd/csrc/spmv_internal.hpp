@@ -240,8 +240,8 @@ struct WavePlan {
     int64_t blocks = 0, win_blocks = 0;   // blocks of block_rows rows, and how many have a window
 };
 
-// spmv_csr_spmm (kernels_spmm.hip) and spmv_csr_sddmm (kernels_sddmm.hip): the rows too long for one lane group, cut into
-// pieces at plan-fixed boundaries
+// spmv_csr_spmm (kernels_spmm.hip), spmv_csr_sddmm (kernels_sddmm.hip) and spmv_csr_row_softmax (kernels_softmax.hip): the
+// rows too long for one lane group, cut into pieces at plan-fixed boundaries
 struct SpmmPlan {
     bool ready = false;
     int n_long = 0, pieces = 0;
@@ -251,7 +251,8 @@ struct SpmmPlan {
     DevPtr<int32_t> d_long_first;     // [n_long + 1] first piece of every row
     DevPtr<int32_t> d_piece_k0;       // [pieces] first nonzero of a piece
     DevPtr<int32_t> d_piece_len;      // [pieces] its length
-    DevPtr<float> d_partial;          // [pieces * 64] scratch of a run: a piece's sums of up to 64 columns
+    DevPtr<float> d_partial;          // [pieces * 64] scratch of a run: a piece's sums of up to 64 columns (SpMM), a piece's
+                                      // maximum / sum / dot and its row's in slots 0 .. 3 (row softmax)
 };
 
 }  // namespace spmv
@@ -358,6 +359,9 @@ int launch_spmm(const spmv_csr &h, int k, const float *X, int64_t ldx, float *Y,
 int64_t spmm_plan_bytes(const spmv_csr &h);
 // kernels_sddmm.hip: spmv_csr_sddmm (on the plan of plan_spmm)
 int launch_sddmm(const spmv_csr &h, int k, const float *U, int64_t ldu, const float *X, int64_t ldx, float *out, hipStream_t s);
+// kernels_softmax.hip: spmv_csr_row_softmax / spmv_csr_row_softmax_backward (on the plan of plan_spmm and its scratch)
+int launch_row_softmax(const spmv_csr &h, float scale, const float *scores, float *out, hipStream_t s);
+int launch_row_softmax_backward(const spmv_csr &h, float scale, const float *P, const float *dP, float *dS, hipStream_t s);
 // kernels_transpose.hip: spmv_csr_transpose / spmv_csr_transpose_values
 int transpose(const spmv_csr &a, bool keep_map, hipStream_t s, spmv_csr_t **out);
 int transpose_values(spmv_csr &t, const spmv_csr &a, hipStream_t s);

@@ -1,0 +1,109 @@
+"""O = softmax_rows(scale * (Q K^T at the pattern)) V as a differentiable torch operation, on the primitives of
+include/spmv_hip.h that a sparse (or graph) attention needs, all on one pattern, one SpMM plan and one transposed handle:
+
+    forward    S  = Q K^T at A's pattern          spmv_csr_sddmm on A, into the work buffer A borrows as vals
+               P  = softmax of scale * S per row  spmv_csr_row_softmax, in place
+               O  = P V                           spmv_csr_spmm on A
+    backward   dV = P^T dO                        spmv_csr_transpose_values + spmv_csr_spmm on T = transpose(A)
+               dP = dO V^T at the pattern         spmv_csr_sddmm on A, into the work buffer
+               dS = scale * P * (dP - sum P dP)   spmv_csr_row_softmax_backward, dS over dP
+               dQ = dS K                          spmv_csr_spmm on A
+               dK = dS^T Q                        spmv_csr_transpose_values + spmv_csr_spmm on T
+
+Plumbing that shows the primitives compose, not a framework: fp32, one device, one head, k and kv <= 64.  Every product
+and the softmax run in the HIP library; there is no torch fallback.  The only temporaries of nnz floats are the work
+buffer and the clone of P that the backward pass needs.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+
+from . import capi
+
+MAX_K = 64
+
+
+def _operand(t, name: str, rows: int, k=None):
+    """t as the library takes it: 2-D float32, stride(1) == 1, stride(0) >= k, 16-byte aligned (copied if it is not)."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
+        raise ValueError(f"SparseAttention: {name} must be a 2-D float32 tensor")
+    if t.shape[0] != rows:
+        raise ValueError(f"SparseAttention: {name} has {t.shape[0]} rows, the pattern needs {rows}")
+    if not 1 <= t.shape[1] <= MAX_K:
+        raise ValueError(f"SparseAttention: {name} has {t.shape[1]} columns (1 <= k <= {MAX_K})")
+    if k is not None and t.shape[1] != k:
+        raise ValueError(f"SparseAttention: {name} has {t.shape[1]} columns, its partner has {k}")
+    if t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0:
+        return t
+    return torch.empty(t.shape, dtype=t.dtype, device=t.device).copy_(t)
+
+
+class SparseAttentionFunction(torch.autograd.Function):
+    """``SparseAttentionFunction.apply(att, Q, K, V)`` = softmax_rows(att.scale * Q K^T at the pattern) V."""
+
+    @staticmethod
+    def forward(ctx, att, Q, K, V):
+        A = att.A
+        Q = _operand(Q, "Q", A.rows)
+        K = _operand(K, "K", A.cols, Q.shape[1])
+        V = _operand(V, "V", A.cols)
+        A.sddmm(Q, K, att.work)
+        A.row_softmax(att.work, att.work, att.scale)
+        A.values_changed()
+        O = torch.empty((A.rows, V.shape[1]), dtype=torch.float32, device=V.device)
+        A.spmm(V, O)
+        ctx.att = att
+        ctx.save_for_backward(Q, K, V, att.work.clone())
+        return O
+
+    @staticmethod
+    def backward(ctx, dO):
+        att = ctx.att
+        A, T, W = att.A, att.T, att.work
+        Q, K, V, P = ctx.saved_tensors
+        dO = _operand(dO, "dO", A.rows, V.shape[1])
+        dQ = dK = dV = None
+        if ctx.needs_input_grad[3]:
+            W.copy_(P)
+            A.values_changed()
+            T.transpose_values(A)
+            dV = torch.empty_like(V, memory_format=torch.contiguous_format)
+            T.spmm(dO, dV)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            A.sddmm(dO, V, W)                                   # dP
+            A.row_softmax_backward(P, W, W, att.scale)          # dS over dP
+            A.values_changed()
+            if ctx.needs_input_grad[1]:
+                dQ = torch.empty_like(Q, memory_format=torch.contiguous_format)
+                A.spmm(K, dQ)
+            if ctx.needs_input_grad[2]:
+                T.transpose_values(A)
+                dK = torch.empty_like(K, memory_format=torch.contiguous_format)
+                T.spmm(Q, dK)
+        return None, dQ, dK, dV
+
+
+class SparseAttention:
+    """One attention pattern of rows queries by cols keys.  Borrows ``row_ptr`` and ``col_idx`` (int32, one device); owns
+    the work buffer of nnz floats that A borrows as its values, T = A^T (with the map that refreshes T's values) and both
+    SpMM plans.  ``att(Q, K, V)``: Q rows x k, K cols x k, V cols x kv, k and kv <= 64; a query without keys (an empty
+    row) gets a zero row of O.  Calls of one holder are stream-ordered: they share the work buffer and the plans' scratch."""
+
+    def __init__(self, rows: int, cols: int, row_ptr, col_idx, scale: float = 1.0):
+        if not math.isfinite(scale):
+            raise ValueError(f"SparseAttention: scale = {scale} is not finite")
+        self.scale = float(scale)
+        self.work = torch.zeros(int(col_idx.numel()), dtype=torch.float32, device=col_idx.device)
+        self.A = capi.CsrMatrix.from_device(rows, cols, row_ptr, col_idx, self.work)
+        self.T = self.A.transpose(keep_map=True)
+        self.A.spmm_plan()
+        self.T.spmm_plan()
+
+    def __call__(self, Q, K, V):
+        return SparseAttentionFunction.apply(self, Q, K, V)
+
+    def close(self) -> None:
+        self.T.close()
+        self.A.close()
