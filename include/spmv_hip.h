@@ -256,6 +256,8 @@ SPMV_API int64_t spmv_csr_transpose_map_bytes(const spmv_csr_t *t);
  *   spmv_csr_sddmm                            the same as spmv_csr_spmm (rows x lanes per row < 2^32); any nnz < 2^31
  *   spmv_csr_row_softmax                      any handle (rows, nnz < 2^31; a wavefront per 64 rows, byte offsets 64-bit)
  *   spmv_csr_row_softmax_backward             the same as spmv_csr_row_softmax
+ *   spmv_csr_attention_forward, _backward_q,  the same as spmv_csr_spmm with max(k, kv) in the place of k (rows x lanes per
+ *   _backward_kv                              row < 2^32; on the transposed handle its rows); any nnz < 2^31
  *   spmv_csr_transpose                        any handle
  * (tests/test_gpu_limits.py runs every path on either side of these.) */
 SPMV_API int spmv_csr_plan(spmv_csr_t *h, int variant, void *stream);
@@ -420,6 +422,67 @@ SPMV_API int spmv_csr_sddmm(spmv_csr_t *h, int k, const float *d_U, int64_t ldu,
 SPMV_API int spmv_csr_row_softmax(spmv_csr_t *h, float scale, const float *d_scores, float *d_out, void *stream);
 SPMV_API int spmv_csr_row_softmax_backward(spmv_csr_t *h, float scale, const float *d_P, const float *d_dP,
                                            float *d_dS, void *stream);
+
+/* ---- Fused attention: forward and backward on the pattern without an array of nnz floats ---------------------------
+ * O = softmax_rows(scale * Q K^T at the pattern of h) V and its gradients in three row-parallel passes.  What the
+ * composition above (SDDMM, row softmax, SpMM, transpose_values) does in nnz-sized arrays happens here in registers:
+ * no score, probability or gradient of one is stored, of nnz size only col_idx is read (4 bytes per nonzero and pass), no
+ * atomics, no transpose map.  h is queries x keys: Q is rows rows of k floats (leading dimension ldq), K cols rows of k,
+ * V cols rows of kv, O and dO rows rows of kv, dQ like Q, dK like K, dV like V; stats holds 2 rows floats, delta rows
+ * floats.  vals is never read (handle creation still wants the array).
+ *   spmv_csr_attention_forward(h)       writes O and stats: stats[2i] = M_i, the maximum of t = fp32(scale * s) over row i,
+ *                                       stats[2i+1] = r_i = 1.0f / l_i with l_i the row's sum of exponentials below -- not a
+ *                                       log-sum-exp.  An empty row gets a zero row of O and stats = (-Inf, +0).
+ *   spmv_csr_attention_backward_q(h)    reads O, dO and stats; writes delta_i = dO_i . O_i and dQ (0 for an empty row).
+ *   spmv_csr_attention_backward_kv(t)   t = the handle of the TRANSPOSED pattern (spmv_csr_transpose(h, keep_map = 0)): its
+ *                                       rows are keys, its columns queries.  Reads stats and delta; writes dK and dV (0 for a
+ *                                       key no query refers to).  Needs only t's pattern: no map, no values.
+ * The probability of a nonzero is p = expf(t - M_i) * r_i in both backward passes, and s is spmv_csr_sddmm's number bit
+ * for bit in all three passes and on both handles, so the passes agree on every p.
+ * Special cases agree with torch.softmax and with the row softmax above: t = -Inf beside a finite maximum contributes
+ * exactly nothing (also when a whole leading stretch of the row is -Inf); a row that holds a NaN or a +Inf score, or whose
+ * every score is -Inf, has a NaN row of O (and NaN gradients wherever it contributes).
+ * The plan: spmv_csr_attention_plan makes the SpMM plan if it is missing (spmv_csr_spmm_plan, unchanged) and allocates the
+ * scratch of the long rows: per piece of a row of more than 512 nonzeros 132 floats (m, l, and up to 128 partial sums at a
+ * 16-byte boundary); nothing for a handle without such a row.  Idempotent; h and t each need theirs.  After it the three
+ * calls allocate nothing and never wait: graph-capturable.  Calls on one handle must be stream-ordered (they share the
+ * scratch).  spmv_csr_attention_plan_bytes: device bytes of both plans together (0 when not planned).
+ * Limits and refusals as spmv_csr_sddmm: 1 <= k, kv <= 64, every ld >= its width, every matrix 16-byte aligned (stats
+ * 8-byte, delta 4-byte), a finite scale, the plan made (SPMV_ERR_NOT_PLANNED), rows x lanes per row < 2^32; anything else
+ * is SPMV_ERR_INVALID with a message that names the function, nothing is launched and every output is untouched.  With
+ * every ld % 4 == 0 the passes use 16-byte loads and stores, otherwise 4-byte ones; columns at or past the width are never
+ * read into a sum nor written.  Outputs must not overlap inputs (not checked).
+ * The order of the sums is part of the interface.  V = the power of two >= ceil(max(k, kv) / 4), T = max(V, 8):
+ *   s, dp    p_s = +0; p_s = fma(a[c], b[c], p_s) for c = 4s .. 4s+3 while c < width; then for m = V/2 .. 1: p_s = p_s +
+ *            p_(s xor m); the number is p_0 (a group wider than SDDMM's adds lanes that hold +0: the same bits).
+ *            s = Q_i . K_j over k, dp = dO_i . V_j over kv; t = scale * s, rounded.
+ *   forward  a span is a row of at most 512 nonzeros or one of the SpMM plan's pieces; m = -Inf, l = +0, acc = +0, then per
+ *            step of T consecutive nonzeros: m' = max(m, the step's t) (a NaN is ignored here); z = m' unless m' = -Inf,
+ *            then 0; a = expf(m - z); e_t = expf(t_t - z); l = l * a; acc[c] = acc[c] * a; then for the step's nonzeros in
+ *            storage order l = l + e_t, acc[c] = fma(e_t, V[j_t][c], acc[c]); m = m'.
+ *            A row of one span: r = 1.0f / l, O[i][c] = acc[c] * r, stats = (m, r).  A row in pieces: M = max m_p, z as
+ *            above, w_p = expf(m_p - z), and from +0 in piece order l = fma(l_p, w_p, l), acc[c] = fma(acc_p[c], w_p, acc[c]);
+ *            then r, O and stats = (M, r) alike.
+ *   delta_i  d_s = +0; d_s = fma(dO[i][c], O[i][c], d_s) over the lane's columns below kv; the same butterfly.
+ *   ds       = scale * (p * (dp - delta_i)), three roundings (as spmv_csr_row_softmax_backward)
+ *   dQ_i[c]  = fma(ds, K[j][c], dQ_i[c]) over a span in storage order from +0; the spans of a row added in piece order from +0
+ *   dV_j[c]  = fma(p, dO[i][c], dV_j[c]) and dK_j[c] = fma(ds, Q[i][c], dK_j[c]) over a span of t likewise
+ * So a row's outputs are a pure function of its column list in storage order, its operands, k, kv and scale: not of any
+ * ld or of the load path, of the row's position or neighbours, of the stream, of the handle, or of whether the handle is a
+ * row block (row_ptr rebased) or the whole matrix. */
+SPMV_API int spmv_csr_attention_plan(spmv_csr_t *h, void *stream);
+SPMV_API int64_t spmv_csr_attention_plan_bytes(const spmv_csr_t *h);
+SPMV_API int spmv_csr_attention_forward(spmv_csr_t *h, float scale, int k, const float *d_Q, int64_t ldq, const float *d_K,
+                                        int64_t ldk, int kv, const float *d_V, int64_t ldv, float *d_O, int64_t ldo,
+                                        float *d_stats, void *stream);
+SPMV_API int spmv_csr_attention_backward_q(spmv_csr_t *h, float scale, int k, const float *d_Q, int64_t ldq, const float *d_K,
+                                           int64_t ldk, int kv, const float *d_V, int64_t ldv, const float *d_O, int64_t ldo,
+                                           const float *d_dO, int64_t lddo, const float *d_stats, float *d_delta,
+                                           float *d_dQ, int64_t lddq, void *stream);
+SPMV_API int spmv_csr_attention_backward_kv(spmv_csr_t *t, float scale, int k, const float *d_Q, int64_t ldq,
+                                            const float *d_K, int64_t ldk, int kv, const float *d_V, int64_t ldv,
+                                            const float *d_dO, int64_t lddo, const float *d_stats, const float *d_delta,
+                                            float *d_dK, int64_t lddk, float *d_dV, int64_t lddv, void *stream);
 
 /* ---- dense baselines (reference slots cublas / naive / tiling) ---------
  * y[i] = sum_j x[j] * A[j*N+i] on the dense device matrix.

@@ -58,6 +58,16 @@ SIGNATURES = {
     "spmv_csr_sddmm": (C.c_int, [_H, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, _f32p, _vp]),
     "spmv_csr_row_softmax": (C.c_int, [_H, C.c_float, _f32p, _f32p, _vp]),
     "spmv_csr_row_softmax_backward": (C.c_int, [_H, C.c_float, _f32p, _f32p, _f32p, _vp]),
+    "spmv_csr_attention_plan": (C.c_int, [_H, _vp]),
+    "spmv_csr_attention_plan_bytes": (C.c_int64, [_H]),
+    "spmv_csr_attention_forward": (C.c_int, [_H, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, C.c_int, _f32p,
+                                             C.c_int64, _f32p, C.c_int64, _f32p, _vp]),
+    "spmv_csr_attention_backward_q": (C.c_int, [_H, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, C.c_int, _f32p,
+                                                C.c_int64, _f32p, C.c_int64, _f32p, C.c_int64, _f32p, _f32p, _f32p, C.c_int64,
+                                                _vp]),
+    "spmv_csr_attention_backward_kv": (C.c_int, [_H, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, C.c_int, _f32p,
+                                                 C.c_int64, _f32p, C.c_int64, _f32p, _f32p, _f32p, C.c_int64, _f32p, C.c_int64,
+                                                 _vp]),
     "spmv_csr_plan_get": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int32)]),
     "spmv_csr_plan_set": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int32), _vp]),
     "spmv_csr_plan_like": (C.c_int, [_H, _H, C.c_int, _vp]),
@@ -154,6 +164,11 @@ def _ptr(t) -> int:
     if hasattr(t, "data_ptr"):
         return t.data_ptr()
     return t.ctypes.data
+
+
+def _width(t):
+    """Columns of a 2-D tensor (None for anything else: the caller's shape check then names it)."""
+    return t.shape[1] if getattr(t, "ndim", 0) == 2 else None
 
 
 def _stream_handle(stream=None) -> int:
@@ -315,6 +330,68 @@ class CsrMatrix:
         if not math.isfinite(scale):
             raise ValueError(f"row_softmax_backward: scale = {scale} is not finite")
         check(lib().spmv_csr_row_softmax_backward(self._h, scale, _ptr(P), _ptr(dP), _ptr(dS), _stream_handle(stream)))
+
+    # -- fused attention (spmv_csr_attention_*; no array of nnz floats) ---------------------------------------------
+    def attention_plan(self, stream=None) -> None:
+        """The SpMM plan if it is missing, and the scratch of the long rows' pieces (waits for the stream once)."""
+        check(lib().spmv_csr_attention_plan(self._h, _stream_handle(stream)))
+
+    def attention_plan_bytes(self) -> int:
+        n = lib().spmv_csr_attention_plan_bytes(self._h)
+        if n < 0:
+            check(n)
+        return n
+
+    @staticmethod
+    def _attention_operands(what: str, scale: float, **mats) -> None:
+        """Every matrix as (tensor, rows, width or None): 2-D float32 with stride(1) == 1 (its ld is stride(0))."""
+        import math
+        import torch
+        if not math.isfinite(scale):
+            raise ValueError(f"{what}: scale = {scale} is not finite")
+        for name, (t, n, w) in mats.items():
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1:
+                raise ValueError(f"{what}: {name} must be a 2-D float32 tensor with stride(1) == 1")
+            if t.shape[0] != n or (w is not None and t.shape[1] != w):
+                raise ValueError(f"{what}: {name} is {tuple(t.shape)}, expected ({n}, {w if w is not None else 'width'})")
+
+    @staticmethod
+    def _attention_vectors(what: str, **vecs) -> None:
+        import torch
+        for name, (t, n) in vecs.items():
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+                raise ValueError(f"{what}: {name} must be a contiguous float32 tensor of {n} elements")
+
+    def attention_forward(self, Q, K, V, O, stats, scale: float = 1.0, stream=None) -> None:
+        """Enqueue O = softmax_rows(scale * Q K^T at the pattern) V and stats = (row maximum, 1 / row sum) per query.
+        Q: (rows, k), K: (cols, k), V: (cols, kv), O: (rows, kv), stats: (rows, 2)."""
+        k, kv = _width(Q), _width(V)
+        self._attention_operands("attention_forward", scale, Q=(Q, self.rows, k), K=(K, self.cols, k), V=(V, self.cols, kv),
+                                 O=(O, self.rows, kv))
+        self._attention_vectors("attention_forward", stats=(stats, 2 * self.rows))
+        check(lib().spmv_csr_attention_forward(self._h, scale, k, _ptr(Q), Q.stride(0), _ptr(K), K.stride(0), kv, _ptr(V),
+                                               V.stride(0), _ptr(O), O.stride(0), _ptr(stats), _stream_handle(stream)))
+
+    def attention_backward_q(self, Q, K, V, O, dO, stats, delta, dQ, scale: float = 1.0, stream=None) -> None:
+        """Enqueue delta[i] = dO[i] . O[i] and dQ; reads the forward call's O and stats.  delta: rows floats, dQ: (rows, k)."""
+        k, kv = _width(Q), _width(V)
+        self._attention_operands("attention_backward_q", scale, Q=(Q, self.rows, k), K=(K, self.cols, k), V=(V, self.cols, kv),
+                                 O=(O, self.rows, kv), dO=(dO, self.rows, kv), dQ=(dQ, self.rows, k))
+        self._attention_vectors("attention_backward_q", stats=(stats, 2 * self.rows), delta=(delta, self.rows))
+        check(lib().spmv_csr_attention_backward_q(self._h, scale, k, _ptr(Q), Q.stride(0), _ptr(K), K.stride(0), kv, _ptr(V),
+                                                  V.stride(0), _ptr(O), O.stride(0), _ptr(dO), dO.stride(0), _ptr(stats),
+                                                  _ptr(delta), _ptr(dQ), dQ.stride(0), _stream_handle(stream)))
+
+    def attention_backward_kv(self, Q, K, V, dO, stats, delta, dK, dV, scale: float = 1.0, stream=None) -> None:
+        """On the handle of the TRANSPOSED pattern (rows = keys, cols = queries): enqueue dK and dV from the forward call's
+        stats and backward_q's delta.  Q, dO: (cols, .), K, V, dK, dV: (rows, .)."""
+        k, kv = _width(Q), _width(V)
+        self._attention_operands("attention_backward_kv", scale, Q=(Q, self.cols, k), K=(K, self.rows, k), V=(V, self.rows, kv),
+                                 dO=(dO, self.cols, kv), dK=(dK, self.rows, k), dV=(dV, self.rows, kv))
+        self._attention_vectors("attention_backward_kv", stats=(stats, 2 * self.cols), delta=(delta, self.cols))
+        check(lib().spmv_csr_attention_backward_kv(self._h, scale, k, _ptr(Q), Q.stride(0), _ptr(K), K.stride(0), kv, _ptr(V),
+                                                   V.stride(0), _ptr(dO), dO.stride(0), _ptr(stats), _ptr(delta), _ptr(dK),
+                                                   dK.stride(0), _ptr(dV), dV.stride(0), _stream_handle(stream)))
 
     def values_changed(self) -> None:
         """The caller rewrote vals (borrowed arrays): plans that hold a copy of them are stale from here on."""

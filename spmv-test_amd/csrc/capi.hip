@@ -635,6 +635,99 @@ int spmv_csr_row_softmax_backward(spmv_csr_t *h, float scale, const float *d_P, 
     return launch_row_softmax_backward(*h, scale, d_P, d_dP, d_dS, (hipStream_t)stream);
 }
 
+// ---- fused attention (kernels_attention.hip) ---------------------------------------------------------------------------
+int spmv_csr_attention_plan(spmv_csr_t *h, void *stream)
+{
+    if (!h) { set_error("spmv_csr_attention_plan: null handle"); return SPMV_ERR_INVALID; }
+    if (int rc = require_current(h->device, "spmv_csr_attention_plan")) return rc;
+    return plan_attention(*h, (hipStream_t)stream);
+}
+
+int64_t spmv_csr_attention_plan_bytes(const spmv_csr_t *h)
+{
+    if (!h) { set_error("spmv_csr_attention_plan_bytes: null handle"); return SPMV_ERR_INVALID; }
+    return attention_plan_bytes(*h);
+}
+
+namespace {
+struct AttnOperand {
+    const char *name;
+    const void *p;
+    int64_t ld, n;     // n rows of ld floats, of which `width` are used
+    int width;
+};
+}  // namespace
+
+// what the three attention calls check alike: k, kv, the scale, every matrix (ld, presence, 16-byte alignment, 64-bit
+// byte offsets), the vectors stats (8-byte aligned) and delta (4-byte), the device and the plan
+static int attention_args(const spmv_csr_t *h, float scale, int k, int kv, const AttnOperand *ops, int n_ops, const void *stats,
+                          const void *delta, bool with_delta, int64_t n_queries, const char *what)
+{
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (k < 1 || k > 64 || kv < 1 || kv > 64) {
+        set_error("%s: k = %d, kv = %d (need 1 <= k <= 64 and 1 <= kv <= 64)", what, k, kv);
+        return SPMV_ERR_INVALID;
+    }
+    if (!(scale - scale == 0.0f)) { set_error("%s: scale must be finite", what); return SPMV_ERR_INVALID; }
+    for (int i = 0; i < n_ops; ++i) {
+        const AttnOperand &o = ops[i];
+        if (o.ld < o.width) { set_error("%s: ld of %s = %lld is below its width %d", what, o.name, (long long)o.ld, o.width); return SPMV_ERR_INVALID; }
+        if (!o.p && o.n > 0) { set_error("%s: null %s", what, o.name); return SPMV_ERR_INVALID; }
+        if (!aligned16(o.p)) { set_error("%s: %s must be 16-byte aligned", what, o.name); return SPMV_ERR_INVALID; }
+        if (o.ld > INT64_MAX / 4 / (o.n > 0 ? o.n : 1)) {
+            set_error("%s: ld of %s = %lld overflows 64-bit byte offsets", what, o.name, (long long)o.ld);
+            return SPMV_ERR_INVALID;
+        }
+    }
+    if (n_queries > 0 && (!stats || (with_delta && !delta))) { set_error("%s: null stats or delta", what); return SPMV_ERR_INVALID; }
+    if (reinterpret_cast<uintptr_t>(stats) % 8 != 0 || reinterpret_cast<uintptr_t>(delta) % 4 != 0) {
+        set_error("%s: stats must be 8-byte aligned and delta 4-byte aligned", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(h->device, what)) return rc;
+    if (!h->plan_attn.ready || !h->plan_spmm.ready) { set_error("%s used before spmv_csr_attention_plan", what); return SPMV_ERR_NOT_PLANNED; }
+    return SPMV_OK;
+}
+
+int spmv_csr_attention_forward(spmv_csr_t *h, float scale, int k, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk,
+                               int kv, const float *d_V, int64_t ldv, float *d_O, int64_t ldo, float *d_stats, void *stream)
+{
+    const char *what = "spmv_csr_attention_forward";
+    const int64_t rows = h ? h->rows : 0, cols = h ? h->cols : 0;
+    const AttnOperand ops[] = {{"Q", d_Q, ldq, rows, k}, {"K", d_K, ldk, cols, k}, {"V", d_V, ldv, cols, kv}, {"O", d_O, ldo, rows, kv}};
+    if (int rc = attention_args(h, scale, k, kv, ops, 4, d_stats, nullptr, false, rows, what)) return rc;
+    return launch_attention_forward(*h, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_O, ldo, d_stats, (hipStream_t)stream);
+}
+
+int spmv_csr_attention_backward_q(spmv_csr_t *h, float scale, int k, const float *d_Q, int64_t ldq, const float *d_K,
+                                  int64_t ldk, int kv, const float *d_V, int64_t ldv, const float *d_O, int64_t ldo,
+                                  const float *d_dO, int64_t lddo, const float *d_stats, float *d_delta, float *d_dQ,
+                                  int64_t lddq, void *stream)
+{
+    const char *what = "spmv_csr_attention_backward_q";
+    const int64_t rows = h ? h->rows : 0, cols = h ? h->cols : 0;
+    const AttnOperand ops[] = {{"Q", d_Q, ldq, rows, k}, {"K", d_K, ldk, cols, k}, {"V", d_V, ldv, cols, kv}, {"O", d_O, ldo, rows, kv},
+                               {"dO", d_dO, lddo, rows, kv}, {"dQ", d_dQ, lddq, rows, k}};
+    if (int rc = attention_args(h, scale, k, kv, ops, 6, d_stats, d_delta, true, rows, what)) return rc;
+    return launch_attention_backward_q(*h, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_O, ldo, d_dO, lddo, d_stats, d_delta,
+                                       d_dQ, lddq, (hipStream_t)stream);
+}
+
+// t is the handle of the TRANSPOSED pattern: t->rows keys, t->cols queries
+int spmv_csr_attention_backward_kv(spmv_csr_t *t, float scale, int k, const float *d_Q, int64_t ldq, const float *d_K,
+                                   int64_t ldk, int kv, const float *d_V, int64_t ldv, const float *d_dO, int64_t lddo,
+                                   const float *d_stats, const float *d_delta, float *d_dK, int64_t lddk, float *d_dV,
+                                   int64_t lddv, void *stream)
+{
+    const char *what = "spmv_csr_attention_backward_kv";
+    const int64_t keys = t ? t->rows : 0, queries = t ? t->cols : 0;
+    const AttnOperand ops[] = {{"Q", d_Q, ldq, queries, k}, {"K", d_K, ldk, keys, k}, {"V", d_V, ldv, keys, kv},
+                               {"dO", d_dO, lddo, queries, kv}, {"dK", d_dK, lddk, keys, k}, {"dV", d_dV, lddv, keys, kv}};
+    if (int rc = attention_args(t, scale, k, kv, ops, 6, d_stats, d_delta, true, queries, what)) return rc;
+    return launch_attention_backward_kv(*t, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_dO, lddo, d_stats, d_delta, d_dK,
+                                        lddk, d_dV, lddv, (hipStream_t)stream);
+}
+
 int spmv_csr_values_changed(spmv_csr_t *h)
 {
     if (!h) { set_error("spmv_csr_values_changed: null handle"); return SPMV_ERR_INVALID; }

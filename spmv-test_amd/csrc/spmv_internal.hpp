@@ -255,6 +255,12 @@ struct SpmmPlan {
                                       // maximum / sum / dot and its row's in slots 0 .. 3 (row softmax)
 };
 
+// spmv_csr_attention_* (kernels_attention.hip): on the SpMM plan, plus the scratch of the long rows' pieces
+struct AttnPlan {
+    bool ready = false;
+    DevPtr<float> d_scratch;          // [pieces * 132] a piece's (m, l) and up to 128 partial sums (empty: no long row)
+};
+
 }  // namespace spmv
 
 
@@ -279,6 +285,7 @@ struct spmv_csr {
     spmv::XskipPlan plan_xskip;    // SPMV_XSKIP
     spmv::WavePlan plan_wave;      // SPMV_WAVE_PIPE
     spmv::SpmmPlan plan_spmm;      // spmv_csr_spmm
+    spmv::AttnPlan plan_attn;      // spmv_csr_attention_*
     int auto_variant = -1;         // SPMV_AUTO: the variant its plan chose (-1 = not planned)
     uint64_t values_gen = 0;       // bumped by spmv_csr_values_changed: plans that copied vals before that are stale
 };
@@ -362,6 +369,18 @@ int launch_sddmm(const spmv_csr &h, int k, const float *U, int64_t ldu, const fl
 // kernels_softmax.hip: spmv_csr_row_softmax / spmv_csr_row_softmax_backward (on the plan of plan_spmm and its scratch)
 int launch_row_softmax(const spmv_csr &h, float scale, const float *scores, float *out, hipStream_t s);
 int launch_row_softmax_backward(const spmv_csr &h, float scale, const float *P, const float *dP, float *dS, hipStream_t s);
+// kernels_attention.hip: spmv_csr_attention_* (on the plan of plan_spmm and a scratch of its own)
+int plan_attention(spmv_csr &h, hipStream_t s);
+int64_t attention_plan_bytes(const spmv_csr &h);
+int launch_attention_forward(const spmv_csr &h, float scale, int k, const float *Q, int64_t ldq, const float *K, int64_t ldk,
+                             int kv, const float *V, int64_t ldv, float *O, int64_t ldo, float *stats, hipStream_t s);
+int launch_attention_backward_q(const spmv_csr &h, float scale, int k, const float *Q, int64_t ldq, const float *K, int64_t ldk,
+                                int kv, const float *V, int64_t ldv, const float *O, int64_t ldo, const float *dO,
+                                int64_t lddo, const float *stats, float *delta, float *dQ, int64_t lddq, hipStream_t s);
+int launch_attention_backward_kv(const spmv_csr &t, float scale, int k, const float *Q, int64_t ldq, const float *K,
+                                 int64_t ldk, int kv, const float *V, int64_t ldv, const float *dO, int64_t lddo,
+                                 const float *stats, const float *delta, float *dK, int64_t lddk, float *dV, int64_t lddv,
+                                 hipStream_t s);
 // kernels_transpose.hip: spmv_csr_transpose / spmv_csr_transpose_values
 int transpose(const spmv_csr &a, bool keep_map, hipStream_t s, spmv_csr_t **out);
 int transpose_values(spmv_csr &t, const spmv_csr &a, hipStream_t s);

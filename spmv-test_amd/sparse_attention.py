@@ -13,6 +13,10 @@ include/spmv_hip.h that a sparse (or graph) attention needs, all on one pattern,
 Plumbing that shows the primitives compose, not a framework: fp32, one device, one head, k and kv <= 64.  Every product
 and the softmax run in the HIP library; there is no torch fallback.  The only temporaries of nnz floats are the work
 buffer and the clone of P that the backward pass needs.
+
+FusedSparseAttention is the same operation on the three fused passes (spmv_csr_attention_forward, _backward_q on A and
+_backward_kv on T = transpose(A), include/spmv_hip.h "Fused attention"): nothing of nnz floats is written, saved or read
+but col_idx, so one holder serves any number of heads.
 """
 from __future__ import annotations
 
@@ -103,6 +107,111 @@ class SparseAttention:
 
     def __call__(self, Q, K, V):
         return SparseAttentionFunction.apply(self, Q, K, V)
+
+    def close(self) -> None:
+        self.T.close()
+        self.A.close()
+
+
+def _fused_operand(t, name: str, rows: int, k=None):
+    """A 2-D operand as _operand takes it, or (heads, rows, k): every head t[h] must itself be acceptable to the library
+    (a column block of a (rows, heads * k) tensor with k % 4 == 0 is); otherwise the whole tensor is copied once into
+    rows padded to a multiple of 4 floats, so that every head starts on a 16-byte boundary."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 3:
+        return _operand(t, name, rows, k)
+    if t.shape[0] < 1:
+        raise ValueError(f"SparseAttention: {name} has no heads")
+    _operand(t[0], name, rows, k)       # (dtype and shape)
+    w = t.shape[2]
+    if all(t.stride(2) == 1 and t.stride(1) >= w and t[h].data_ptr() % 16 == 0 for h in range(t.shape[0])):
+        return t
+    return _heads_empty(t.shape[0], rows, w, t.device).copy_(t)
+
+
+def _heads_empty(heads: int, rows: int, w: int, device):
+    """(heads, rows, w) float32 whose every head is 16-byte aligned (rows padded to a multiple of 4 floats if need be)."""
+    return torch.empty((heads, rows, (w + 3) // 4 * 4), dtype=torch.float32, device=device)[:, :, :w]
+
+
+class FusedSparseAttentionFunction(torch.autograd.Function):
+    """``FusedSparseAttentionFunction.apply(att, Q, K, V)``: as SparseAttentionFunction, 2-D operands or (heads, n, width)
+    ones.  Saved for backward: Q, K, V, O and stats (2 floats per query and head)."""
+
+    @staticmethod
+    def forward(ctx, att, Q, K, V):
+        A = att.A
+        if len({t.dim() if isinstance(t, torch.Tensor) else -1 for t in (Q, K, V)}) != 1:
+            raise ValueError("SparseAttention: Q, K and V must all be 2-D or all (heads, n, width)")
+        Q = _fused_operand(Q, "Q", A.rows)
+        K = _fused_operand(K, "K", A.cols, Q.shape[-1])
+        V = _fused_operand(V, "V", A.cols)
+        kv = V.shape[-1]
+        if Q.dim() == 3:
+            heads = Q.shape[0]
+            if K.shape[0] != heads or V.shape[0] != heads:
+                raise ValueError(f"SparseAttention: Q has {heads} heads, K {K.shape[0]} and V {V.shape[0]}")
+            O = _heads_empty(heads, A.rows, kv, V.device)
+            stats = torch.empty((heads, A.rows, 2), dtype=torch.float32, device=V.device)
+            for h in range(heads):
+                A.attention_forward(Q[h], K[h], V[h], O[h], stats[h], att.scale)
+        else:
+            O = torch.empty((A.rows, kv), dtype=torch.float32, device=V.device)
+            stats = torch.empty((A.rows, 2), dtype=torch.float32, device=V.device)
+            A.attention_forward(Q, K, V, O, stats, att.scale)
+        ctx.att = att
+        ctx.save_for_backward(Q, K, V, O, stats)
+        return O
+
+    @staticmethod
+    def backward(ctx, dO):
+        att = ctx.att
+        A, T = att.A, att.T
+        Q, K, V, O, stats = ctx.saved_tensors
+        need_q, need_k, need_v = ctx.needs_input_grad[1:4]
+        if not (need_q or need_k or need_v):
+            return None, None, None, None
+        batched = Q.dim() == 3
+        dO = _fused_operand(dO, "dO", A.rows, V.shape[-1])
+        if batched and dO.shape[0] != Q.shape[0]:
+            raise ValueError(f"SparseAttention: dO has {dO.shape[0]} heads, Q {Q.shape[0]}")
+
+        def like(t):
+            return _heads_empty(*t.shape, t.device) if batched else torch.empty(t.shape, dtype=torch.float32, device=t.device)
+
+        # backward_q also makes delta, which backward_kv reads: it runs whichever gradient is asked for
+        dQ = like(Q)
+        delta = torch.empty(O.shape[:-1], dtype=torch.float32, device=O.device)
+        dK = like(K) if need_k or need_v else None
+        dV = like(V) if need_k or need_v else None
+        heads = range(Q.shape[0]) if batched else (None,)
+        for h in heads:
+            at = (lambda t: t) if h is None else (lambda t, h=h: t[h])
+            A.attention_backward_q(at(Q), at(K), at(V), at(O), at(dO), at(stats), at(delta), at(dQ), att.scale)
+            if dK is not None:
+                T.attention_backward_kv(at(Q), at(K), at(V), at(dO), at(stats), at(delta), at(dK), at(dV), att.scale)
+        return None, dQ if need_q else None, dK if need_k else None, dV if need_v else None
+
+
+class FusedSparseAttention:
+    """One attention pattern of rows queries by cols keys on the fused passes.  Borrows ``row_ptr`` and ``col_idx`` (int32,
+    one device); owns T = A^T (pattern only: no map) and both attention plans.  ``att(Q, K, V)``: Q rows x k, K cols x k,
+    V cols x kv, k and kv <= 64, or (heads, rows, k), (heads, cols, k), (heads, cols, kv): the heads run one after the other
+    on the same A and T.  A head that is a strided view with stride(1) == 1 on a 16-byte boundary goes in without a copy.
+    A query without keys gets a zero row of O.  Calls of one holder are stream-ordered (the plans' scratch).  The values
+    array that handle creation still asks for is allocated once here and never read."""
+
+    def __init__(self, rows: int, cols: int, row_ptr, col_idx, scale: float = 1.0):
+        if not math.isfinite(scale):
+            raise ValueError(f"SparseAttention: scale = {scale} is not finite")
+        self.scale = float(scale)
+        vals = torch.zeros(int(col_idx.numel()), dtype=torch.float32, device=col_idx.device)
+        self.A = capi.CsrMatrix.from_device(rows, cols, row_ptr, col_idx, vals)
+        self.T = self.A.transpose(keep_map=False)
+        self.A.attention_plan()
+        self.T.attention_plan()
+
+    def __call__(self, Q, K, V):
+        return FusedSparseAttentionFunction.apply(self, Q, K, V)
 
     def close(self) -> None:
         self.T.close()

@@ -1,0 +1,296 @@
+"""The fused attention entry points without a device (include/spmv_hip.h "Fused attention"): every new symbol is declared,
+exported by the normal and the bounds-checked library and bound in capi, the CsrMatrix methods and the fused holder exist,
+and a null handle is refused.  A numpy emulation of the documented fp32 order of the three passes (online steps of T
+nonzeros, pieces of 512, the combine) is compared with fp64 dense attention on rows of 1 .. 5000 entries, and reproduces the
+exact case of tests/test_gpu_fused_attention.py bit for bit.
+
+The emulation rounds every operation to fp32 where the header says so.  fma(a, b, c) is taken as fp32(fp64(a) * fp64(b) + c):
+the product is exact in fp64, the sum is rounded twice, which differs from a true fma only in rare ties and by one ulp; expf is
+the correctly rounded one.  Neither matters to the bounds below, and the exact case has no rounding at all.
+
+The bound of the comparison, per row of L entries with D = max t - min t <= 32: the subtraction puts D 2^-24 into an exponent
+and expf gets 2 ulp, in the numerator and in the denominator; the fp32 scores themselves are left to RTOL (as in
+tests/test_gpu_sparse_attention.py).  A sum of n terms taken one after the other carries at most n 2^-24 of the sum of its
+terms' magnitudes, and a span has A = min(L, 512) additions, ceil(A / T) rescalings and, in a long row, ceil(L / 512) combine
+steps: (2 D + 12 + 2 (A + A / T + pieces)) 2^-24 + RTOL relative to sum p |v| for O.  dQ adds the three roundings of ds, the
+sums of dp and delta (at most kv + 4 each) and its own chain: RTOL + (2 D + 2 kv + 24 + 3 (A + A / T + pieces)) 2^-24 relative
+to the magnitude the GPU tests use, |scale| sum p (|dp| + sum p |dp|) |K|.
+"""
+import ctypes as C
+import re
+import subprocess
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+RTOL, EPS = 1e-5, 2.0 ** -24
+PIECE = 512
+f32, f64 = np.float32, np.float64
+NAMES = {"spmv_csr_attention_plan": 2, "spmv_csr_attention_plan_bytes": 1, "spmv_csr_attention_forward": 14,
+         "spmv_csr_attention_backward_q": 19, "spmv_csr_attention_backward_kv": 19}      # name -> number of arguments
+
+
+def _exports(path):
+    out = subprocess.run(["nm", "-D", "--defined-only", str(path)], capture_output=True, text=True, check=True).stdout
+    return {l.split()[-1] for l in out.splitlines() if " T " in l}
+
+
+def test_attention_symbols_declared_exported_and_bound(pkg):
+    header = (ROOT / "include" / "spmv_hip.h").read_text()
+    declared = set(re.findall(r"SPMV_API[^;(]*?\b(spmv_\w+)\s*\(", header))
+    capi = pkg.capi
+    normal, checked = _exports(capi.LIB_PATH), _exports(capi.CHECKED_LIB_PATH)
+    for name, nargs in NAMES.items():
+        assert name in declared, f"{name} not declared in include/spmv_hip.h"
+        assert name in capi.SIGNATURES, f"{name} not bound in capi.SIGNATURES"
+        assert len(capi.SIGNATURES[name][1]) == nargs
+        assert name in normal, f"{name} not exported by {capi.LIB_PATH.name}"
+        assert name in checked, f"{name} not exported by {capi.CHECKED_LIB_PATH.name}"
+    for name in ("spmv_csr_attention_forward", "spmv_csr_attention_backward_q", "spmv_csr_attention_backward_kv"):
+        assert capi.SIGNATURES[name][1][1] is C.c_float, "scale is a float"
+    flat = re.sub(r"\s+", " ", header)
+    limits = flat[flat.index("Limits of the layouts"):flat.index("tests/test_gpu_limits.py")]
+    assert "spmv_csr_attention_forward" in limits
+    for method in ("attention_plan", "attention_plan_bytes", "attention_forward", "attention_backward_q", "attention_backward_kv"):
+        assert callable(getattr(capi.CsrMatrix, method, None)), f"CsrMatrix.{method} missing"
+
+
+def test_fused_sparse_attention_imports(pkg):
+    import torch
+    sa = pkg.sparse_attention
+    assert issubclass(sa.FusedSparseAttentionFunction, torch.autograd.Function) and callable(sa.FusedSparseAttention)
+    assert issubclass(sa.SparseAttentionFunction, torch.autograd.Function) and callable(sa.SparseAttention)     # (untouched)
+
+
+def test_attention_refuses_a_null_handle(pkg):
+    capi = pkg.capi
+    lib = capi.lib()
+    buf = (C.c_float * 64)()
+    p = C.addressof(buf)
+    p -= p % 16
+    assert lib.spmv_csr_attention_plan(None, None) == capi.ERR_INVALID
+    assert "spmv_csr_attention_plan:" in lib.spmv_last_error().decode()
+    assert lib.spmv_csr_attention_plan_bytes(None) == capi.ERR_INVALID
+    assert lib.spmv_csr_attention_forward(None, 1.0, 4, p, 4, p, 4, 4, p, 4, p, 4, p, None) == capi.ERR_INVALID
+    assert "spmv_csr_attention_forward:" in lib.spmv_last_error().decode()
+    assert lib.spmv_csr_attention_backward_q(None, 1.0, 4, p, 4, p, 4, 4, p, 4, p, 4, p, 4, p, p, p, 4, None) == capi.ERR_INVALID
+    assert "spmv_csr_attention_backward_q:" in lib.spmv_last_error().decode()
+    assert lib.spmv_csr_attention_backward_kv(None, 1.0, 4, p, 4, p, 4, 4, p, 4, p, 4, p, p, p, 4, p, 4, None) == capi.ERR_INVALID
+    assert "spmv_csr_attention_backward_kv:" in lib.spmv_last_error().decode()
+
+
+# ---- the documented order in fp32 ------------------------------------------------------------------------------------
+def geometry(k, kv):
+    """(V, T): lanes per row and nonzeros per step."""
+    slices, V = (max(k, kv) + 3) // 4, 1
+    while V < slices:
+        V *= 2
+    return V, max(V, 8)
+
+
+def fma(a, b, c):
+    with np.errstate(invalid="ignore", over="ignore"):
+        return (np.asarray(a, f64) * np.asarray(b, f64) + np.asarray(c, f64)).astype(f32)
+
+
+def expf(x):
+    with np.errstate(invalid="ignore", over="ignore"):
+        return np.exp(np.asarray(x, f32).astype(f64)).astype(f32)
+
+
+def dot(a, B, V):
+    """a . B[n] for every row n of B in the documented order: lane partials by fma from +0, then the xor butterfly."""
+    B = np.asarray(B, f32).reshape(-1, len(a))
+    p = np.zeros((B.shape[0], V), f32)
+    for c in range(len(a)):
+        p[:, c // 4] = fma(a[c], B[:, c], p[:, c // 4])
+    lane, m = np.arange(V), V // 2
+    with np.errstate(invalid="ignore"):
+        while m:
+            p = p + p[:, lane ^ m]
+            m //= 2
+    return p[:, 0]
+
+
+def spans(n):
+    return [(0, n)] if n <= PIECE else [(b, min(b + PIECE, n)) for b in range(0, n, PIECE)]
+
+
+def forward_span(t, Vj, T):
+    m, l, acc = f32(-np.inf), f32(0), np.zeros(Vj.shape[1], f32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for kb in range(0, len(t), T):
+            tt = t[kb:kb + T]
+            mn = np.fmax(m, np.fmax.reduce(tt))
+            z = f32(0) if mn == -np.inf else mn
+            a, e = expf(m - z), expf(tt - z)
+            l, acc = f32(l * a), (acc * a).astype(f32)
+            for i in range(len(tt)):
+                l = f32(l + e[i])
+                acc = fma(e[i], Vj[kb + i], acc)
+            m = mn
+    return m, l, acc
+
+
+def forward_row(q, Kj, Vj, scale, V, T):
+    """(O row, M, r) of one query whose keys are the rows of Kj, Vj in storage order."""
+    n = Kj.shape[0]
+    if n == 0:
+        return np.zeros(Vj.shape[1], f32), f32(-np.inf), f32(0)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        t = (f32(scale) * dot(q, Kj, V)).astype(f32)
+        parts = [forward_span(t[b:e], Vj[b:e], T) for b, e in spans(n)]
+        if len(parts) == 1:
+            M, l, acc = parts[0]
+        else:
+            M = np.fmax.reduce(np.array([p[0] for p in parts], f32))
+            z = f32(0) if M == -np.inf else M
+            l, acc = f32(0), np.zeros(Vj.shape[1], f32)
+            for m_p, l_p, acc_p in parts:
+                w = expf(m_p - z)
+                l, acc = fma(l_p, w, l), fma(acc_p, w, acc)
+        r = f32(1) / f32(l)
+        return (acc * r).astype(f32), f32(M), f32(r)
+
+
+def probabilities(t, M, r):
+    with np.errstate(invalid="ignore", over="ignore"):
+        return (expf((t - M).astype(f32)) * r).astype(f32)
+
+
+def ordered_fma_sum(w, X):
+    """sum of w[n] X[n] over the spans of a row: fma in storage order from +0, the spans added in piece order from +0."""
+    parts = []
+    for b, e in spans(len(w)):
+        acc = np.zeros(X.shape[1], f32)
+        for n in range(b, e):
+            acc = fma(w[n], X[n], acc)
+        parts.append(acc)
+    if len(parts) == 1:
+        return parts[0]
+    acc = np.zeros(X.shape[1], f32)
+    for p in parts:
+        acc = (acc + p).astype(f32)
+    return acc
+
+
+def backward_q_row(q, Kj, Vj, o, do, M, r, scale, V):
+    """(dQ row, delta) of one query."""
+    if Kj.shape[0] == 0:
+        return np.zeros(len(q), f32), f32(0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        delta = dot(do, o[None], V)[0]
+        p = probabilities((f32(scale) * dot(q, Kj, V)).astype(f32), M, r)
+        ds = (f32(scale) * (p * (dot(do, Vj, V) - delta).astype(f32)).astype(f32)).astype(f32)
+    return ordered_fma_sum(ds, Kj), delta
+
+
+def backward_kv_row(kj, vj, Qi, dOi, Mi, ri, deltai, scale, V):
+    """(dK row, dV row) of one key whose queries are the rows of Qi, dOi in the transposed pattern's storage order."""
+    if Qi.shape[0] == 0:
+        return np.zeros(len(kj), f32), np.zeros(len(vj), f32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        p = probabilities((f32(scale) * dot(kj, Qi, V)).astype(f32), Mi, ri)
+        ds = (f32(scale) * (p * (dot(vj, dOi, V) - deltai).astype(f32)).astype(f32)).astype(f32)
+    return ordered_fma_sum(ds, Qi), ordered_fma_sum(p, dOi)
+
+
+def test_the_emulated_order_against_fp64_dense_attention():
+    worst = [0.0, 0.0]
+    for L in (1, 2, 7, 8, 9, 16, 17, 64, 511, 512, 513, 1024, 1025, 4100, 5000):
+        for k, kv in ((24, 24), (8, 40), (64, 4), (6, 10)):
+            rng = np.random.Generator(np.random.PCG64([L, k, kv]))
+            V, T = geometry(k, kv)
+            scale = 2.0 ** -2
+            q, Kj, Vj, do = (rng.standard_normal(s).astype(f32) for s in ((k,), (L, k), (L, kv), (kv,)))
+            o, M, r = forward_row(q, Kj, Vj, scale, V, T)
+            dq, delta = backward_q_row(q, Kj, Vj, o, do, M, r, scale, V)
+            # fp64
+            t = scale * (Kj.astype(f64) @ q.astype(f64))
+            D = t.max() - t.min()
+            assert D <= 32.0
+            p = np.exp(t - t.max())
+            p /= p.sum()
+            o64 = p @ Vj.astype(f64)
+            dp = Vj.astype(f64) @ do.astype(f64)
+            dq64 = (scale * p * (dp - p @ dp)) @ Kj.astype(f64)
+            A = min(L, PIECE)
+            chain = A + -(-A // T) + (-(-L // PIECE) if L > PIECE else 0)
+            bound_o = (RTOL + (2 * D + 12 + 2 * chain) * EPS) * (p @ np.abs(Vj).astype(f64))
+            mag = (abs(scale) * p * (np.abs(dp) + p @ np.abs(dp))) @ np.abs(Kj).astype(f64)
+            bound_q = (RTOL + (2 * D + 2 * kv + 24 + 3 * chain) * EPS) * mag
+            ro, rq = np.max(np.abs(o - o64) / bound_o), np.max(np.abs(dq - dq64) / bound_q)
+            worst = [max(worst[0], ro), max(worst[1], rq)]
+            assert ro <= 1.0, f"L={L} k={k} kv={kv}: O at {ro:.3g} of its bound"
+            assert rq <= 1.0, f"L={L} k={k} kv={kv}: dQ at {rq:.3g} of its bound"
+            assert M == np.max((f32(scale) * dot(q, Kj, V)).astype(f32))
+    print(f"the emulated order reaches {worst[0]:.3g} (O) and {worst[1]:.3g} (dQ) of the bounds")
+
+
+def test_the_emulation_handles_the_special_rows():
+    V, T = geometry(8, 8)
+    rng = np.random.Generator(np.random.PCG64(3))
+    Kj, Vj = rng.standard_normal((30, 8)).astype(f32), rng.standard_normal((30, 8)).astype(f32)
+    q = rng.standard_normal(8).astype(f32)
+    q[0] = 1.0
+    Km = Kj.copy()
+    Km[:20, 0] = -np.inf                     # two whole leading steps of -Inf, then a mixed one
+    o, M, r = forward_row(q, Km, Vj, 0.25, V, T)
+    # (not the bits of the 10 finite entries run alone: those take steps [8][2], these [4 masked + 4][6])
+    p = probabilities((f32(0.25) * dot(q, Km, V)).astype(f32), M, r)
+    assert np.isfinite(o).all() and np.all(p[:20] == 0) and np.all(p[20:] > 0) and abs(float(p.sum()) - 1) < 1e-6
+    # with the finite entries inside one step the masked ones leave the bits alone
+    o4, M4, r4 = forward_row(q, Km[:24], Vj[:24], 0.25, V, T)
+    o4b, M4b, r4b = forward_row(q, Kj[20:24], Vj[20:24], 0.25, V, T)
+    assert o4.tobytes() == o4b.tobytes() and (M4, r4) == (M4b, r4b)
+    Km[:, 0] = -np.inf
+    assert np.isnan(forward_row(q, Km, Vj, 0.25, V, T)[0]).all()             # a row masked entirely
+    qn = q.copy()
+    qn[1] = np.nan
+    assert np.isnan(forward_row(qn, Kj, Vj, 0.25, V, T)[0]).all()            # a NaN
+    Kp = Kj.copy()
+    Kp[25, 0] = np.inf
+    assert np.isnan(forward_row(q, Kp, Vj, 0.25, V, T)[0]).all()             # a +Inf
+    o0, M0, r0 = forward_row(q, Kj[:0], Vj[:0], 0.25, V, T)
+    assert not o0.any() and M0 == -np.inf and r0 == 0 and not np.signbit(r0)  # an empty row
+
+
+def test_the_emulation_reproduces_the_exact_case():
+    """The pattern and data of the GPU exact test: O, dQ, dK and dV of the emulation equal torch's fp64 dense autograd."""
+    import torch
+    rows, cols, k = 3000, 2000, 8
+    rng = np.random.Generator(np.random.PCG64(5))
+    lengths = 2 ** rng.integers(0, 5, size=rows)
+    lengths[:5] = (1, 2, 4, 8, 16)
+    rp = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    ci = np.concatenate([np.sort(rng.choice(cols, size=int(n), replace=False)) for n in lengths]).astype(np.int64)
+    row_of = np.repeat(np.arange(rows), lengths)
+    ints = lambda seed, shape: np.random.Generator(np.random.PCG64(seed)).integers(-4, 5, size=shape).astype(f32)   # noqa: E731
+    scale, (V, T) = 2.0 ** -2, geometry(k, k)
+    order = np.argsort(ci, kind="stable")                 # the transposed pattern's storage order
+    tp = np.concatenate([[0], np.cumsum(np.bincount(ci, minlength=cols))])
+    for step, zero in enumerate(("Q", "K")):
+        Q, K, Vm, dO = ints(10 + step, (rows, k)), ints(20 + step, (cols, k)), ints(30 + step, (cols, k)), ints(40 + step, (rows, k))
+        (Q if zero == "Q" else K)[:] = 0
+        O, stats, dQ, delta = np.empty((rows, k), f32), np.empty((rows, 2), f32), np.empty((rows, k), f32), np.empty(rows, f32)
+        for i in range(rows):
+            j = ci[rp[i]:rp[i + 1]]
+            O[i], stats[i, 0], stats[i, 1] = forward_row(Q[i], K[j], Vm[j], scale, V, T)
+            dQ[i], delta[i] = backward_q_row(Q[i], K[j], Vm[j], O[i], dO[i], stats[i, 0], stats[i, 1], scale, V)
+        dK, dV = np.empty((cols, k), f32), np.empty((cols, k), f32)
+        for j in range(cols):
+            i = row_of[order[tp[j]:tp[j + 1]]]
+            dK[j], dV[j] = backward_kv_row(K[j], Vm[j], Q[i], dO[i], stats[i, 0], stats[i, 1], delta[i], scale, V)
+        assert np.array_equal(stats[:, 1], (1.0 / lengths).astype(f32)) and not stats[:, 0].any()
+        mask = torch.zeros((rows, cols), dtype=torch.bool)
+        mask[torch.from_numpy(row_of), torch.from_numpy(ci)] = True
+        q, kk, v = (torch.from_numpy(t.astype(f64)).requires_grad_(True) for t in (Q, K, Vm))
+        scores = torch.where(mask, (q @ kk.t()) * scale, torch.tensor(float("-inf"), dtype=torch.float64))
+        Od = torch.softmax(scores, dim=1) @ v
+        Od.backward(torch.from_numpy(dO.astype(f64)))
+        for what, got, want in (("O", O, Od.detach()), ("dQ", dQ, q.grad), ("dK", dK, kk.grad), ("dV", dV, v.grad)):
+            want = want.numpy()
+            assert np.array_equal(want.astype(f32).astype(f64), want), f"{what}: the expectation is not an fp32 number"
+            assert np.array_equal(got + f32(0), want.astype(f32) + f32(0)), f"{zero} = 0: {what} differs"
+        assert (dQ if zero == "Q" else dK).any() and dV.any() and not (dK if zero == "Q" else dQ).any()

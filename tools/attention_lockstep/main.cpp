@@ -1,0 +1,172 @@
+// tools/attention_lockstep/main.cpp -- see run.sh.  One pattern whose rows (and whose transposed rows) cover empty rows, rows
+// inside one step, several steps, exactly 512, pieces of long rows; the three passes at four (k, kv) on the 16-byte and the
+// 4-byte load path, every array an exactly sized heap block, compared with a serial fp64 statement of attention.
+#include "kernels_attention.hip"
+#include <algorithm>
+#include <cstdlib>
+#include <random>
+using namespace spmv;
+
+template <class T> static T *heap(const std::vector<T> &v)
+{
+    T *p = (T *)malloc(sizeof(T) * v.size() + 1);
+    std::copy(v.begin(), v.end(), p);
+    return p;
+}
+
+struct Pattern {
+    int64_t rows, cols;
+    std::vector<int32_t> rp, ci;
+};
+
+// the handle of a pattern with the plan of plan_spmm: rows of more than 512 in pieces of 512, the rows in row order
+static spmv_csr make_handle(const Pattern &a, std::vector<void *> &owned)
+{
+    std::vector<int32_t> lr, lf, k0, ln, order((size_t)a.rows);
+    for (int64_t r = 0; r < a.rows; ++r) {
+        order[(size_t)r] = (int32_t)(a.rows - 1 - r);      // (any permutation serves)
+        if (a.rp[r + 1] - a.rp[r] <= 512) continue;
+        lr.push_back((int32_t)r);
+        lf.push_back((int32_t)k0.size());
+        for (int q = a.rp[r]; q < a.rp[r + 1]; q += 512) { k0.push_back(q); ln.push_back(std::min(512, a.rp[r + 1] - q)); }
+    }
+    lf.push_back((int32_t)k0.size());
+    spmv_csr h;
+    h.rows = a.rows, h.cols = a.cols, h.nnz = a.rp[a.rows];
+    int32_t *rp = heap(a.rp), *ci = heap(a.ci);
+    h.d_row_ptr = rp, h.d_col_idx = ci;
+    SpmmPlan &pl = h.plan_spmm;
+    pl.n_long = (int)lr.size(), pl.pieces = (int)k0.size();
+    pl.d_order.p = heap(order), pl.d_long_row.p = heap(lr), pl.d_long_first.p = heap(lf), pl.d_piece_k0.p = heap(k0), pl.d_piece_len.p = heap(ln);
+    if (plan_attention(h, nullptr) != SPMV_OK) abort();
+    for (void *p : {(void *)rp, (void *)ci, (void *)pl.d_order.p, (void *)pl.d_long_row.p, (void *)pl.d_long_first.p, (void *)pl.d_piece_k0.p,
+                    (void *)pl.d_piece_len.p, (void *)h.plan_attn.d_scratch.p})
+        owned.push_back(p);
+    return h;
+}
+
+static Pattern transpose(const Pattern &a)
+{
+    Pattern t{a.cols, a.rows, std::vector<int32_t>((size_t)a.cols + 1, 0), std::vector<int32_t>(a.ci.size())};
+    for (int32_t c : a.ci) ++t.rp[(size_t)c + 1];
+    for (int64_t j = 0; j < a.cols; ++j) t.rp[j + 1] += t.rp[j];
+    std::vector<int32_t> at(t.rp.begin(), t.rp.end() - 1);
+    for (int64_t r = 0; r < a.rows; ++r)
+        for (int n = a.rp[r]; n < a.rp[r + 1]; ++n) t.ci[(size_t)at[a.ci[n]]++] = (int32_t)r;
+    return t;
+}
+
+// rows x w floats of leading dimension ld in an exactly sized block (the last row ends at its width)
+static float *matrix(int64_t rows, int w, int64_t ld, std::mt19937 &rng, bool fill)
+{
+    const size_t n = rows ? (size_t)((rows - 1) * ld + (ld % 4 == 0 ? (w + 3) / 4 * 4 : w)) : 0;
+    float *p = (float *)aligned_alloc(16, (n * 4 + 15) / 16 * 16 + 16);
+    std::normal_distribution<float> nd(0.f, 1.f);
+    for (size_t i = 0; i < n; ++i) p[i] = fill ? nd(rng) : NAN;
+    return p;
+}
+
+int main()
+{
+    std::mt19937 rng(11);
+    Pattern a;
+    a.cols = 300;
+    std::vector<int> lens = {0, 1, 2, 7, 8, 9, 15, 16, 17, 33, 64, 100, 299, 0, 3, 5};
+    for (int i = 0; i < 1100; ++i) lens.push_back(i % 97 == 0 ? 0 : 1 + (int)(rng() % 4));     // (transposed rows of about 10)
+    a.rows = (int64_t)lens.size();
+    a.rp.assign(1, 0);
+    std::vector<int32_t> all((size_t)a.cols);
+    for (int i = 0; i < a.cols; ++i) all[i] = i;
+    for (int64_t r = 0; r < a.rows; ++r) {
+        std::shuffle(all.begin(), all.end(), rng);
+        std::vector<int32_t> row(all.begin(), all.begin() + lens[r]);
+        std::sort(row.begin(), row.end());
+        // columns 0 and 1 sit in most rows, so that the transposed pattern has two rows in pieces
+        if (r % 10 != 0 && lens[r] && row[0] != 0) row[0] = 0;
+        if (r % 7 != 0 && lens[r] > 1 && row[1] != 1 && row[0] == 0) row[1] = 1;
+        a.ci.insert(a.ci.end(), row.begin(), row.end());
+        a.rp.push_back((int32_t)a.ci.size());
+    }
+    // a long row of the pattern itself: 700 entries with repeats allowed
+    for (int i = 0; i < 700; ++i) a.ci.push_back((int32_t)(rng() % a.cols));
+    a.rp.push_back((int32_t)a.ci.size());
+    ++a.rows;
+    const Pattern t = transpose(a);
+    std::vector<void *> owned;
+    spmv_csr A = make_handle(a, owned), T = make_handle(t, owned);
+    printf("pattern %lld x %lld, nnz %lld; long rows %d (pieces %d), transposed %d (pieces %d)\n", (long long)a.rows, (long long)a.cols,
+           (long long)A.nnz, A.plan_spmm.n_long, A.plan_spmm.pieces, T.plan_spmm.n_long, T.plan_spmm.pieces);
+    if (!A.plan_spmm.n_long || T.plan_spmm.n_long < 2) return 2;
+    const float scale = 0.25f;
+    int status = 0;
+    double worst = 0.0;
+    const int shapes[][2] = {{24, 24}, {8, 40}, {64, 4}, {6, 10}};
+    for (auto &kk : shapes)
+        for (int odd = 0; odd < 2; ++odd) {
+            const int k = kk[0], kv = kk[1];
+            int V = 1;
+            while (4 * V < std::max(k, kv)) V *= 2;
+            g_group_lanes = V;
+            auto ld = [&](int w) { return (int64_t)(odd ? w + 1 + ((w + 1) % 4 == 0) : (w + 3) / 4 * 4 + 4); };
+            const int64_t R = a.rows, C = a.cols;
+            float *Q = matrix(R, k, ld(k), rng, true), *K = matrix(C, k, ld(k), rng, true), *Vm = matrix(C, kv, ld(kv), rng, true);
+            float *dO = matrix(R, kv, ld(kv), rng, true), *O = matrix(R, kv, ld(kv), rng, false), *dQ = matrix(R, k, ld(k), rng, false);
+            float *dK = matrix(C, k, ld(k), rng, false), *dV = matrix(C, kv, ld(kv), rng, false);
+            float *stats = (float *)malloc(8 * R), *delta = (float *)malloc(4 * R);
+            status |= launch_attention_forward(A, scale, k, Q, ld(k), K, ld(k), kv, Vm, ld(kv), O, ld(kv), stats, nullptr);
+            status |= launch_attention_backward_q(A, scale, k, Q, ld(k), K, ld(k), kv, Vm, ld(kv), O, ld(kv), dO, ld(kv), stats, delta, dQ, ld(k), nullptr);
+            status |= launch_attention_backward_kv(T, scale, k, Q, ld(k), K, ld(k), kv, Vm, ld(kv), dO, ld(kv), stats, delta, dK, ld(k), dV, ld(kv), nullptr);
+            // serial fp64
+            std::vector<double> rdK((size_t)(C * k), 0.0), rdV((size_t)(C * kv), 0.0), mK(rdK), mV(rdV);
+            auto err = [&](double got, double want, double mag) { worst = std::max(worst, std::fabs(got - want) / (mag + 1e-30)); };
+            for (int64_t i = 0; i < R; ++i) {
+                const int b = a.rp[i], e = a.rp[i + 1], L = e - b;
+                std::vector<double> p((size_t)L), dp((size_t)L);
+                double M = -INFINITY, S = 0.0, dot = 0.0, adot = 0.0;
+                for (int n = b; n < e; ++n) {
+                    double s = 0.0;
+                    for (int c = 0; c < k; ++c) s += (double)Q[i * ld(k) + c] * K[a.ci[n] * ld(k) + c];
+                    p[n - b] = s * scale;
+                    M = std::max(M, p[n - b]);
+                }
+                for (int n = 0; n < L; ++n) S += (p[n] = std::exp(p[n] - M));
+                for (int n = 0; n < L; ++n) {
+                    p[n] /= S;
+                    double s = 0.0, as = 0.0;
+                    for (int c = 0; c < kv; ++c) s += (double)dO[i * ld(kv) + c] * Vm[a.ci[b + n] * ld(kv) + c], as += std::fabs((double)dO[i * ld(kv) + c] * Vm[a.ci[b + n] * ld(kv) + c]);
+                    dp[n] = s, dot += p[n] * s, adot += p[n] * as;
+                }
+                for (int c = 0; c < kv; ++c) {
+                    double o = 0.0, ao = 0.0;
+                    for (int n = 0; n < L; ++n) o += p[n] * Vm[a.ci[b + n] * ld(kv) + c], ao += p[n] * std::fabs(Vm[a.ci[b + n] * ld(kv) + c]);
+                    if (L == 0 && O[i * ld(kv) + c] != 0.0f) status |= 4;
+                    err(O[i * ld(kv) + c], o, ao);
+                }
+                if (L == 0 && !(stats[2 * i] == -INFINITY && stats[2 * i + 1] == 0.0f)) status |= 8;
+                for (int c = 0; c < k; ++c) {
+                    double g = 0.0, ag = 0.0;
+                    for (int n = 0; n < L; ++n) {
+                        const double ds = scale * p[n] * (dp[n] - dot), ads = scale * p[n] * (std::fabs(dp[n]) + adot + 1e-3);
+                        g += ds * K[a.ci[b + n] * ld(k) + c], ag += ads * std::fabs(K[a.ci[b + n] * ld(k) + c]);
+                        rdK[(size_t)(a.ci[b + n] * k + c)] += ds * Q[i * ld(k) + c];
+                        mK[(size_t)(a.ci[b + n] * k + c)] += ads * std::fabs(Q[i * ld(k) + c]);
+                    }
+                    if (L == 0 && dQ[i * ld(k) + c] != 0.0f) status |= 16;
+                    err(dQ[i * ld(k) + c], g, ag);
+                }
+                for (int n = 0; n < L; ++n)
+                    for (int c = 0; c < kv; ++c) {
+                        rdV[(size_t)(a.ci[b + n] * kv + c)] += p[n] * dO[i * ld(kv) + c];
+                        mV[(size_t)(a.ci[b + n] * kv + c)] += p[n] * std::fabs(dO[i * ld(kv) + c]);
+                    }
+            }
+            for (int64_t j = 0; j < C; ++j) {
+                for (int c = 0; c < k; ++c) err(dK[j * ld(k) + c], rdK[(size_t)(j * k + c)], mK[(size_t)(j * k + c)] + (t.rp[j + 1] == t.rp[j] ? 1.0 : 0.0));
+                for (int c = 0; c < kv; ++c) err(dV[j * ld(kv) + c], rdV[(size_t)(j * kv + c)], mV[(size_t)(j * kv + c)] + (t.rp[j + 1] == t.rp[j] ? 1.0 : 0.0));
+            }
+            printf("k %d kv %d V %d %s: status %d, worst normalised error so far %.3g\n", k, kv, V, odd ? "4-byte path" : "16-byte path", status, worst);
+            for (void *p : {(void *)Q, (void *)K, (void *)Vm, (void *)dO, (void *)O, (void *)dQ, (void *)dK, (void *)dV, (void *)stats, (void *)delta}) free(p);
+        }
+    for (void *p : owned) free(p);
+    return status != 0 || !(worst <= 2e-5);
+}
