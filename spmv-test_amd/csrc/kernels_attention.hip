@@ -2,21 +2,16 @@
 // that never store a score, a probability or their gradients (spmv_csr_attention_forward, spmv_csr_attention_backward_q,
 // spmv_csr_attention_backward_kv, include/spmv_hip.h "Fused attention").  Of nnz size only col_idx is read, once per pass.
 //
-// The geometry is kernels_spmm.hip's and kernels_sddmm.hip's, and so is the plan (SpmmPlan: the order of the rows, the
-// pieces of the rows of more than 512 nonzeros).  A group of V = pow2 >= ceil(max(k, kv) / 4) lanes owns one row of the
-// pattern (or one plan piece): lane s keeps columns [4s, 4s+4) of the row's own operands in registers (Q_i; dO_i; K_j and
-// V_j on the transposed handle) and reads the same columns of every row the CSR row refers to.  A group walks its row in
-// steps of T = max(V, 8) nonzeros: it loads the step's col_idx coalesced, broadcasts them inside the group, issues all
-// gathers of the step (2 T slices per lane, and on the transposed handle the 12 bytes stats[2i], stats[2i+1], delta[i]
-// per nonzero, loaded by the lane that owns the nonzero), and only then computes.  The scores of a step go through
-// SDDMM's reduce-scatter; the lane that ends up with a score turns it into e, p or ds and broadcasts that.
+// The lane groups, their steps and the plan are lane_group.hpp's, with V = pow2 >= ceil(max(k, kv) / 4).  Lane s keeps
+// columns [4s, 4s+4) of the row's own operands in registers (Q_i; dO_i; K_j and V_j on the transposed handle).  Per step a
+// lane issues all its gathers (2 T slices, and on the transposed handle the 12 bytes stats[2i], stats[2i+1], delta[i] per
+// nonzero, loaded by the lane that owns the nonzero) and only then computes.  The scores of a step go through
+// reduce_scatter; the lane that ends up with a score turns it into e, p or ds and broadcasts that.
 //
 // The order of the fp32 operations (the header states it; tests/test_attention_host.py emulates it).  Nothing below is
 // contracted by the compiler (fp contract is off in this file): an fma is one where fmaf is written, and nowhere else.
-//   score    s = spmv_csr_sddmm's number for k: p_s = +0, p_s = fma(a[c], b[c], p_s) over the lane's columns below k, then
-//            the xor butterfly m = V/2 .. 1.  V may be wider than SDDMM's for this k (kv > k): the extra lanes hold +0, a
-//            partial is never -0, so the extra levels add +0 to a number that is not -0.  dp = dO_i . V_j likewise over kv.
-//            t = scale * s (rounded).
+//   score    s = spmv_csr_sddmm's number for k: the dot product of lane_group.hpp, which also says why a V wider than SDDMM's
+//            for this k (kv > k) changes no bit.  dp = dO_i . V_j likewise over kv.  t = scale * s (rounded).
 //   forward  a span is a whole row of at most 512 nonzeros or a plan piece; m = -Inf, l = +0, acc = +0; per step of T:
 //              m' = max(m, the step's t)  (fmaxf: a NaN is ignored here);  z = m' == -Inf ? 0 : m'
 //              a = expf(m - z);  e_t = expf(t_t - z);  l = l * a;  acc[c] = acc[c] * a
@@ -34,10 +29,9 @@
 // V, hence on max(k, kv) only.)
 //
 // The scratch of the long rows (AttnPlan): kAtSlots floats per piece: [0] m_p, [1] l_p, [4, 132) up to 128 partial sums
-// (forward acc_p[kv]; backward_q dQ_p[k]; backward_kv dK_p[k] at 4 and dV_p[kv] at 68).  Addresses are 64-bit; no buffer
-// descriptor and no range check is relied on.  With an ld % 4 != 0 the kernels read and store 4-byte elements below k / kv.
+// (forward acc_p[kv]; backward_q dQ_p[k]; backward_kv dK_p[k] at 4 and dV_p[kv] at 68).
 #include <initializer_list>
-#include "spmv_internal.hpp"
+#include "lane_group.hpp"
 
 #pragma clang fp contract(off)
 
@@ -45,7 +39,6 @@ namespace spmv {
 
 namespace {
 
-constexpr int kAtBlock = 256;     // 4 wavefronts
 constexpr int kAtSlots = 132;     // floats of scratch per piece
 constexpr int kAtSums = 4;        // where a piece's partial sums start (16-byte aligned)
 constexpr int kAtSums2 = 68;      // the second set of backward_kv (dV)
@@ -67,139 +60,12 @@ struct AttnArgs {
     float *delta;                      // backward_q
 };
 
-// the rows and pieces of a launch
-struct AttnRows {
-    int64_t rows, nblocks;
-    int row_cap;
-    const int32_t *order, *row_ptr, *col_idx;
-};
-struct AttnPieces {
-    int npieces, n_long;
-    const int32_t *long_row, *long_first, *piece_k0, *piece_len, *col_idx;
-    float *scratch;
-};
-
-// block b of the grid takes item at_xcd_item(b, n): as spmm_xcd_item, each XCD gets one contiguous range of row blocks
-__device__ __forceinline__ int64_t at_xcd_item(int64_t bid, int64_t n)
-{
-    const int64_t q = n / kXcds, rem = n % kXcds;
-    const int64_t j = bid % kXcds, idx = bid / kXcds;
-    return j * q + (j < rem ? j : rem) + idx;
-}
-
-__device__ __forceinline__ float4 zero4() { return make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
-
-// the four columns [c0, c0+4) of row j of a row-major matrix (c0 < w); VEC: one 16-byte load, else the columns below w only
-template <bool VEC>
-__device__ __forceinline__ float4 at_slice(const float *__restrict__ M, int64_t ld, int64_t j, int c0, int w)
-{
-    const float *p = M + j * ld + c0;
-    if (VEC) return *reinterpret_cast<const float4 *>(p);
-    float4 r = zero4();
-    r.x = p[0];
-    if (c0 + 1 < w) r.y = p[1];
-    if (c0 + 2 < w) r.z = p[2];
-    if (c0 + 3 < w) r.w = p[3];
-    return r;
-}
-
-// the columns [c0, c0+4) below w of one output row (c0 < w)
-template <bool VEC>
-__device__ __forceinline__ void at_store(float *__restrict__ p, float4 a, int c0, int w)
-{
-    if (VEC && c0 + 4 <= w) {
-        *reinterpret_cast<float4 *>(p) = a;
-        return;
-    }
-    p[0] = a.x;
-    if (c0 + 1 < w) p[1] = a.y;
-    if (c0 + 2 < w) p[2] = a.z;
-    if (c0 + 3 < w) p[3] = a.w;
-}
-
-// the lane's partial of a dot product: fma over its n1 = w - c0 columns (at most 4) from +0; +0 for an idle lane
-__device__ __forceinline__ float at_partial(float4 u, float4 x, int n1)
-{
-    float a = 0.0f;
-    if (n1 > 0) {
-        a = fmaf(u.x, x.x, a);
-        if (n1 > 1) a = fmaf(u.y, x.y, a);
-        if (n1 > 2) a = fmaf(u.z, x.z, a);
-        if (n1 > 3) a = fmaf(u.w, x.w, a);
-    }
-    return a;
-}
-
-// the xor butterfly over the group as a reduce-scatter (kernels_sddmm.hip): of results i*V + [0, V) lane `sub` ends with
-// result i*V + sub in p[i*V]; the bits are the full butterfly's
-template <int V, int T>
-__device__ __forceinline__ void at_reduce_scatter(float (&p)[T], int sub)
-{
-#pragma unroll
-    for (int i = 0; i < T / V; ++i) {
-#pragma unroll
-        for (int m = V / 2; m >= 1; m /= 2) {
-            const bool up = (sub & m) != 0;
-#pragma unroll
-            for (int j = 0; j < m; ++j) {
-                const float lo = p[i * V + j], hi = p[i * V + j + m];
-                const float keep = up ? hi : lo, send = up ? lo : hi;
-                p[i * V + j] = keep + __shfl_xor(send, m);
-            }
-        }
-    }
-}
-
-// what lane `sub` holds for nonzero i*V + sub, in every lane of the group
-template <int V, int T>
-__device__ __forceinline__ void at_bcast(const float (&w)[T / V], float (&wt)[T], int gbase)
-{
-#pragma unroll
-    for (int t = 0; t < T; ++t) wt[t] = V == 1 ? w[t] : __shfl(w[t / V], gbase + t % V);
-}
-
-template <int V>
-__device__ __forceinline__ float at_group_max(float x)
-{
-#pragma unroll
-    for (int m = V / 2; m >= 1; m /= 2) x = fmaxf(x, __shfl_xor(x, m));
-    return x;
-}
-
-template <int V>
-__device__ __forceinline__ float at_group_sum(float x)
-{
-#pragma unroll
-    for (int m = V / 2; m >= 1; m /= 2) x = x + __shfl_xor(x, m);
-    return x;
-}
-
-// the step's column indices: lane `sub` loads nonzeros kb + i*V + sub (0 past the end), every lane gets all T
-template <int V, int T>
-__device__ __forceinline__ void at_columns(int64_t kb, int64_t e, int sub, int gbase, const int32_t *__restrict__ col_idx,
-                                           int32_t (&c)[T / V], int32_t (&ct)[T])
-{
-#pragma unroll
-    for (int i = 0; i < T / V; ++i) {
-        const int64_t n = kb + (int64_t)i * V + sub;
-        c[i] = n < e ? col_idx[n] : 0;
-    }
-#pragma unroll
-    for (int t = 0; t < T; ++t) ct[t] = V == 1 ? c[t] : __shfl(c[t / V], gbase + t % V);
-}
-
-template <int V>
-struct AtGeom {
-    static constexpr int T = V > 8 ? V : 8;   // nonzeros per step
-    static constexpr int L = T / V;           // of which a lane owns L
-};
-
 // ---- forward: (m, l, acc) of the nonzeros [b, e) of the group's row.  All lanes of a group call it with the same b, e. ----
 template <int V, bool VEC>
 __device__ __forceinline__ void fwd_span(int lane, int64_t b, int64_t e, const AttnArgs &a, float4 q,
                                          const int32_t *__restrict__ col_idx, int c0, float &m, float &l, float4 &acc)
 {
-    constexpr int T = AtGeom<V>::T, L = AtGeom<V>::L;
+    constexpr int T = LaneGeom<V>::T, L = LaneGeom<V>::L;
     const int sub = lane & (V - 1), gbase = lane & ~(V - 1);
     const int nk = a.k - c0, nv = a.kv - c0;
     m = -INFINITY;
@@ -207,29 +73,29 @@ __device__ __forceinline__ void fwd_span(int lane, int64_t b, int64_t e, const A
     acc = zero4();
     for (int64_t kb = b; kb < e; kb += T) {
         int32_t c[L], ct[T];
-        at_columns<V, T>(kb, e, sub, gbase, col_idx, c, ct);
+        group_columns<V, T>(kb, e, sub, gbase, col_idx, c, ct);
         float4 xk[T], xv[T];
 #pragma unroll
-        for (int t = 0; t < T; ++t) xk[t] = (nk > 0 && kb + t < e) ? at_slice<VEC>(a.K, a.ldk, ct[t], c0, a.k) : zero4();
+        for (int t = 0; t < T; ++t) xk[t] = (nk > 0 && kb + t < e) ? load_slice<VEC>(a.K, a.ldk, ct[t], c0, a.k) : zero4();
 #pragma unroll
-        for (int t = 0; t < T; ++t) xv[t] = (nv > 0 && kb + t < e) ? at_slice<VEC>(a.V, a.ldv, ct[t], c0, a.kv) : zero4();
+        for (int t = 0; t < T; ++t) xv[t] = (nv > 0 && kb + t < e) ? load_slice<VEC>(a.V, a.ldv, ct[t], c0, a.kv) : zero4();
         float p[T];
 #pragma unroll
-        for (int t = 0; t < T; ++t) p[t] = at_partial(q, xk[t], nk);
-        at_reduce_scatter<V, T>(p, sub);
+        for (int t = 0; t < T; ++t) p[t] = dot_partial(q, xk[t], nk);
+        reduce_scatter<V, T>(p, sub);
         float tl[L], sm = -INFINITY;
 #pragma unroll
         for (int i = 0; i < L; ++i) {
             tl[i] = kb + i * V + sub < e ? a.scale * p[i * V] : -INFINITY;
             sm = fmaxf(sm, tl[i]);
         }
-        const float mn = fmaxf(m, at_group_max<V>(sm));
+        const float mn = fmaxf(m, group_max<V>(sm));
         const float z = mn == -INFINITY ? 0.0f : mn;
         const float alpha = expf(m - z);
         float el[L], et[T];
 #pragma unroll
         for (int i = 0; i < L; ++i) el[i] = expf(tl[i] - z);
-        at_bcast<V, T>(el, et, gbase);
+        group_bcast<V, T>(el, et, gbase);
         l = l * alpha;
         acc.x = acc.x * alpha;
         acc.y = acc.y * alpha;
@@ -256,63 +122,38 @@ __device__ __forceinline__ void store_stats(float *stats, int64_t r, float m, fl
     *reinterpret_cast<float2 *>(stats + 2 * r) = make_float2(m, rinv);
 }
 
-// the row of slot `threadIdx.x / V` of the block, or -1 (group-uniform: a group never splits here)
-template <int V>
-__device__ __forceinline__ int64_t at_row(const AttnRows &g)
-{
-    const int64_t slot = at_xcd_item(blockIdx.x, g.nblocks) * (kAtBlock / V) + threadIdx.x / V;
-    if (slot >= g.rows) return -1;
-    return g.order ? g.order[slot] : slot;
-}
-
-// the piece of the group and the index of its long row: long_first[lo] <= p < long_first[lo + 1]
-template <int V>
-__device__ __forceinline__ int64_t at_piece(const AttnPieces &g, int &lo)
-{
-    const int64_t p = (int64_t)blockIdx.x * (kAtBlock / V) + threadIdx.x / V;
-    if (p >= g.npieces) return -1;
-    int hi = g.n_long;
-    lo = 0;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) / 2;
-        if (g.long_first[mid] <= p) lo = mid;
-        else hi = mid;
-    }
-    return p;
-}
-
 template <int V, bool VEC>
-__global__ __launch_bounds__(kAtBlock) void k_attn_fwd_rows(AttnRows g, AttnArgs a)
+__global__ __launch_bounds__(kBlock) void k_attn_fwd_rows(GroupRows g, AttnArgs a)
 {
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
-    const int64_t r = at_row<V>(g);
+    const int64_t r = group_row<V>(g);
     if (r < 0) return;
     const int64_t b = g.row_ptr[r], e = g.row_ptr[r + 1];
     if (e - b > g.row_cap) return;
     if (e == b) {
-        if (c0 < a.kv) at_store<VEC>(a.out0 + r * a.ld0 + c0, zero4(), c0, a.kv);
+        if (c0 < a.kv) store_slice<VEC>(a.out0 + r * a.ld0 + c0, zero4(), c0, a.kv);
         if (sub == 0) store_stats(a.stats, r, -INFINITY, 0.0f);
         return;
     }
-    const float4 q = c0 < a.k ? at_slice<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
+    const float4 q = c0 < a.k ? load_slice<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
     float m, l;
     float4 acc;
     fwd_span<V, VEC>(lane, b, e, a, q, g.col_idx, c0, m, l, acc);
     const float rinv = 1.0f / l;
-    if (c0 < a.kv) at_store<VEC>(a.out0 + r * a.ld0 + c0, scaled4(acc, rinv), c0, a.kv);
+    if (c0 < a.kv) store_slice<VEC>(a.out0 + r * a.ld0 + c0, scaled4(acc, rinv), c0, a.kv);
     if (sub == 0) store_stats(a.stats, r, m, rinv);
 }
 
 template <int V, bool VEC>
-__global__ __launch_bounds__(kAtBlock) void k_attn_fwd_pieces(AttnPieces g, AttnArgs a)
+__global__ __launch_bounds__(kBlock) void k_attn_fwd_pieces(GroupPieces g, AttnArgs a)
 {
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     int lo;
-    const int64_t p = at_piece<V>(g, lo);
+    const int64_t p = group_piece<V>(g, lo);
     if (p < 0) return;
     const int64_t r = g.long_row[lo];
     const int64_t b = g.piece_k0[p], e = b + g.piece_len[p];
-    const float4 q = c0 < a.k ? at_slice<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
+    const float4 q = c0 < a.k ? load_slice<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
     float m, l;
     float4 acc;
     fwd_span<V, VEC>(lane, b, e, a, q, g.col_idx, c0, m, l, acc);
@@ -323,10 +164,10 @@ __global__ __launch_bounds__(kAtBlock) void k_attn_fwd_pieces(AttnPieces g, Attn
 
 // a group per long row: the pieces' (m_p, l_p, acc_p) folded in piece order
 template <int V, bool VEC>
-__global__ __launch_bounds__(kAtBlock) void k_attn_fwd_combine(AttnPieces g, AttnArgs a)
+__global__ __launch_bounds__(kBlock) void k_attn_fwd_combine(GroupPieces g, AttnArgs a)
 {
     const int sub = threadIdx.x & (V - 1), c0 = 4 * sub;
-    const int64_t i = (int64_t)blockIdx.x * (kAtBlock / V) + threadIdx.x / V;
+    const int64_t i = (int64_t)blockIdx.x * (kBlock / V) + threadIdx.x / V;
     if (i >= g.n_long) return;
     const int64_t r = g.long_row[i];
     const int f = g.long_first[i], n = g.long_first[i + 1];
@@ -348,7 +189,7 @@ __global__ __launch_bounds__(kAtBlock) void k_attn_fwd_combine(AttnPieces g, Att
         }
     }
     const float rinv = 1.0f / l;
-    if (c0 < a.kv) at_store<VEC>(a.out0 + r * a.ld0 + c0, scaled4(acc, rinv), c0, a.kv);
+    if (c0 < a.kv) store_slice<VEC>(a.out0 + r * a.ld0 + c0, scaled4(acc, rinv), c0, a.kv);
     if (sub == 0) store_stats(a.stats, r, M, rinv);
 }
 
@@ -357,26 +198,26 @@ template <int V, bool VEC>
 __device__ __forceinline__ float4 bwdq_span(int lane, int64_t b, int64_t e, const AttnArgs &a, float4 q, float4 g, float M,
                                             float rinv, float delta, const int32_t *__restrict__ col_idx, int c0)
 {
-    constexpr int T = AtGeom<V>::T, L = AtGeom<V>::L;
+    constexpr int T = LaneGeom<V>::T, L = LaneGeom<V>::L;
     const int sub = lane & (V - 1), gbase = lane & ~(V - 1);
     const int nk = a.k - c0, nv = a.kv - c0;
     float4 dq = zero4();
     for (int64_t kb = b; kb < e; kb += T) {
         int32_t c[L], ct[T];
-        at_columns<V, T>(kb, e, sub, gbase, col_idx, c, ct);
+        group_columns<V, T>(kb, e, sub, gbase, col_idx, c, ct);
         float4 xk[T], xv[T];
 #pragma unroll
-        for (int t = 0; t < T; ++t) xk[t] = (nk > 0 && kb + t < e) ? at_slice<VEC>(a.K, a.ldk, ct[t], c0, a.k) : zero4();
+        for (int t = 0; t < T; ++t) xk[t] = (nk > 0 && kb + t < e) ? load_slice<VEC>(a.K, a.ldk, ct[t], c0, a.k) : zero4();
 #pragma unroll
-        for (int t = 0; t < T; ++t) xv[t] = (nv > 0 && kb + t < e) ? at_slice<VEC>(a.V, a.ldv, ct[t], c0, a.kv) : zero4();
+        for (int t = 0; t < T; ++t) xv[t] = (nv > 0 && kb + t < e) ? load_slice<VEC>(a.V, a.ldv, ct[t], c0, a.kv) : zero4();
         float ps[T], pd[T];
 #pragma unroll
         for (int t = 0; t < T; ++t) {
-            ps[t] = at_partial(q, xk[t], nk);
-            pd[t] = at_partial(g, xv[t], nv);
+            ps[t] = dot_partial(q, xk[t], nk);
+            pd[t] = dot_partial(g, xv[t], nv);
         }
-        at_reduce_scatter<V, T>(ps, sub);
-        at_reduce_scatter<V, T>(pd, sub);
+        reduce_scatter<V, T>(ps, sub);
+        reduce_scatter<V, T>(pd, sub);
         float dl[L], dt[T];
 #pragma unroll
         for (int i = 0; i < L; ++i) {
@@ -384,7 +225,7 @@ __device__ __forceinline__ float4 bwdq_span(int lane, int64_t b, int64_t e, cons
             const float p = expf(t - M) * rinv;
             dl[i] = a.scale * (p * (pd[i * V] - delta));
         }
-        at_bcast<V, T>(dl, dt, gbase);
+        group_bcast<V, T>(dl, dt, gbase);
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             if (kb + t < e) {
@@ -405,46 +246,46 @@ __device__ __forceinline__ float at_delta(const AttnArgs &a, int64_t r, int c0, 
     float4 o = zero4();
     g = zero4();
     if (c0 < a.kv) {
-        g = at_slice<VEC>(a.dO, a.lddo, r, c0, a.kv);
-        o = at_slice<VEC>(a.O, a.ldo, r, c0, a.kv);
+        g = load_slice<VEC>(a.dO, a.lddo, r, c0, a.kv);
+        o = load_slice<VEC>(a.O, a.ldo, r, c0, a.kv);
     }
-    return at_group_sum<V>(at_partial(g, o, a.kv - c0));
+    return group_sum<V>(dot_partial(g, o, a.kv - c0));
 }
 
 template <int V, bool VEC>
-__global__ __launch_bounds__(kAtBlock) void k_attn_bwd_q_rows(AttnRows g, AttnArgs a)
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_q_rows(GroupRows g, AttnArgs a)
 {
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
-    const int64_t r = at_row<V>(g);
+    const int64_t r = group_row<V>(g);
     if (r < 0) return;
     const int64_t b = g.row_ptr[r], e = g.row_ptr[r + 1];
     if (e - b > g.row_cap) return;
     if (e == b) {
-        if (c0 < a.k) at_store<VEC>(a.out0 + r * a.ld0 + c0, zero4(), c0, a.k);
+        if (c0 < a.k) store_slice<VEC>(a.out0 + r * a.ld0 + c0, zero4(), c0, a.k);
         if (sub == 0) a.delta[r] = 0.0f;
         return;
     }
     float4 go;
     const float delta = at_delta<V, VEC>(a, r, c0, go);
-    const float4 q = c0 < a.k ? at_slice<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
+    const float4 q = c0 < a.k ? load_slice<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
     const float2 st = *reinterpret_cast<const float2 *>(a.stats_in + 2 * r);
     const float4 dq = bwdq_span<V, VEC>(lane, b, e, a, q, go, st.x, st.y, delta, g.col_idx, c0);
-    if (c0 < a.k) at_store<VEC>(a.out0 + r * a.ld0 + c0, dq, c0, a.k);
+    if (c0 < a.k) store_slice<VEC>(a.out0 + r * a.ld0 + c0, dq, c0, a.k);
     if (sub == 0) a.delta[r] = delta;
 }
 
 template <int V, bool VEC>
-__global__ __launch_bounds__(kAtBlock) void k_attn_bwd_q_pieces(AttnPieces g, AttnArgs a)
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_q_pieces(GroupPieces g, AttnArgs a)
 {
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     int lo;
-    const int64_t p = at_piece<V>(g, lo);
+    const int64_t p = group_piece<V>(g, lo);
     if (p < 0) return;
     const int64_t r = g.long_row[lo];
     const int64_t b = g.piece_k0[p], e = b + g.piece_len[p];
     float4 go;
     const float delta = at_delta<V, VEC>(a, r, c0, go);      // (every piece of the row computes the same bits)
-    const float4 q = c0 < a.k ? at_slice<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
+    const float4 q = c0 < a.k ? load_slice<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
     const float2 st = *reinterpret_cast<const float2 *>(a.stats_in + 2 * r);
     const float4 dq = bwdq_span<V, VEC>(lane, b, e, a, q, go, st.x, st.y, delta, g.col_idx, c0);
     if (c0 < a.k) *reinterpret_cast<float4 *>(g.scratch + p * kAtSlots + kAtSums + c0) = dq;
@@ -453,10 +294,10 @@ __global__ __launch_bounds__(kAtBlock) void k_attn_bwd_q_pieces(AttnPieces g, At
 
 // a group per long row: out[row][c] = the pieces' partial sums at scratch offset `off`, added in piece order from +0
 template <int V, bool VEC>
-__global__ __launch_bounds__(kAtBlock) void k_attn_add_pieces(AttnPieces g, int off, float *__restrict__ out, int64_t ld, int w)
+__global__ __launch_bounds__(kBlock) void k_attn_add_pieces(GroupPieces g, int off, float *__restrict__ out, int64_t ld, int w)
 {
     const int sub = threadIdx.x & (V - 1), c0 = 4 * sub;
-    const int64_t i = (int64_t)blockIdx.x * (kAtBlock / V) + threadIdx.x / V;
+    const int64_t i = (int64_t)blockIdx.x * (kBlock / V) + threadIdx.x / V;
     if (i >= g.n_long || c0 >= w) return;
     float4 acc = zero4();
     for (int p = g.long_first[i]; p < g.long_first[i + 1]; ++p) {
@@ -466,7 +307,7 @@ __global__ __launch_bounds__(kAtBlock) void k_attn_add_pieces(AttnPieces g, int 
         acc.z = acc.z + x.z;
         acc.w = acc.w + x.w;
     }
-    at_store<VEC>(out + (int64_t)g.long_row[i] * ld + c0, acc, c0, w);
+    store_slice<VEC>(out + (int64_t)g.long_row[i] * ld + c0, acc, c0, w);
 }
 
 // ---- backward_kv on the transposed pattern: (dK, dV) of the nonzeros [b, e) of row j, whose K and V slices the group holds
@@ -474,14 +315,14 @@ template <int V, bool VEC>
 __device__ __forceinline__ void bwdkv_span(int lane, int64_t b, int64_t e, const AttnArgs &a, float4 kj, float4 vj,
                                            const int32_t *__restrict__ col_idx, int c0, float4 &dk, float4 &dv)
 {
-    constexpr int T = AtGeom<V>::T, L = AtGeom<V>::L;
+    constexpr int T = LaneGeom<V>::T, L = LaneGeom<V>::L;
     const int sub = lane & (V - 1), gbase = lane & ~(V - 1);
     const int nk = a.k - c0, nv = a.kv - c0;
     dk = zero4();
     dv = zero4();
     for (int64_t kb = b; kb < e; kb += T) {
         int32_t c[L], ct[T];
-        at_columns<V, T>(kb, e, sub, gbase, col_idx, c, ct);
+        group_columns<V, T>(kb, e, sub, gbase, col_idx, c, ct);
         float2 st[L];
         float de[L];
 #pragma unroll
@@ -492,17 +333,17 @@ __device__ __forceinline__ void bwdkv_span(int lane, int64_t b, int64_t e, const
         }
         float4 xq[T], xg[T];
 #pragma unroll
-        for (int t = 0; t < T; ++t) xq[t] = (nk > 0 && kb + t < e) ? at_slice<VEC>(a.Q, a.ldq, ct[t], c0, a.k) : zero4();
+        for (int t = 0; t < T; ++t) xq[t] = (nk > 0 && kb + t < e) ? load_slice<VEC>(a.Q, a.ldq, ct[t], c0, a.k) : zero4();
 #pragma unroll
-        for (int t = 0; t < T; ++t) xg[t] = (nv > 0 && kb + t < e) ? at_slice<VEC>(a.dO, a.lddo, ct[t], c0, a.kv) : zero4();
+        for (int t = 0; t < T; ++t) xg[t] = (nv > 0 && kb + t < e) ? load_slice<VEC>(a.dO, a.lddo, ct[t], c0, a.kv) : zero4();
         float ps[T], pd[T];
 #pragma unroll
         for (int t = 0; t < T; ++t) {
-            ps[t] = at_partial(kj, xq[t], nk);
-            pd[t] = at_partial(vj, xg[t], nv);
+            ps[t] = dot_partial(kj, xq[t], nk);
+            pd[t] = dot_partial(vj, xg[t], nv);
         }
-        at_reduce_scatter<V, T>(ps, sub);
-        at_reduce_scatter<V, T>(pd, sub);
+        reduce_scatter<V, T>(ps, sub);
+        reduce_scatter<V, T>(pd, sub);
         float pl[L], dl[L], pt[T], dt[T];
 #pragma unroll
         for (int i = 0; i < L; ++i) {
@@ -510,8 +351,8 @@ __device__ __forceinline__ void bwdkv_span(int lane, int64_t b, int64_t e, const
             pl[i] = expf(t - st[i].x) * st[i].y;
             dl[i] = a.scale * (pl[i] * (pd[i * V] - de[i]));
         }
-        at_bcast<V, T>(pl, pt, gbase);
-        at_bcast<V, T>(dl, dt, gbase);
+        group_bcast<V, T>(pl, pt, gbase);
+        group_bcast<V, T>(dl, dt, gbase);
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             if (kb + t < e) {
@@ -529,34 +370,34 @@ __device__ __forceinline__ void bwdkv_span(int lane, int64_t b, int64_t e, const
 }
 
 template <int V, bool VEC>
-__global__ __launch_bounds__(kAtBlock) void k_attn_bwd_kv_rows(AttnRows g, AttnArgs a)
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows(GroupRows g, AttnArgs a)
 {
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
-    const int64_t r = at_row<V>(g);
+    const int64_t r = group_row<V>(g);
     if (r < 0) return;
     const int64_t b = g.row_ptr[r], e = g.row_ptr[r + 1];
     if (e - b > g.row_cap) return;
     float4 dk = zero4(), dv = zero4();
     if (e > b) {
-        const float4 kj = c0 < a.k ? at_slice<VEC>(a.K, a.ldk, r, c0, a.k) : zero4();
-        const float4 vj = c0 < a.kv ? at_slice<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
+        const float4 kj = c0 < a.k ? load_slice<VEC>(a.K, a.ldk, r, c0, a.k) : zero4();
+        const float4 vj = c0 < a.kv ? load_slice<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
         bwdkv_span<V, VEC>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv);
     }
-    if (c0 < a.k) at_store<VEC>(a.out0 + r * a.ld0 + c0, dk, c0, a.k);
-    if (c0 < a.kv) at_store<VEC>(a.out1 + r * a.ld1 + c0, dv, c0, a.kv);
+    if (c0 < a.k) store_slice<VEC>(a.out0 + r * a.ld0 + c0, dk, c0, a.k);
+    if (c0 < a.kv) store_slice<VEC>(a.out1 + r * a.ld1 + c0, dv, c0, a.kv);
 }
 
 template <int V, bool VEC>
-__global__ __launch_bounds__(kAtBlock) void k_attn_bwd_kv_pieces(AttnPieces g, AttnArgs a)
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_pieces(GroupPieces g, AttnArgs a)
 {
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     int lo;
-    const int64_t p = at_piece<V>(g, lo);
+    const int64_t p = group_piece<V>(g, lo);
     if (p < 0) return;
     const int64_t r = g.long_row[lo];
     const int64_t b = g.piece_k0[p], e = b + g.piece_len[p];
-    const float4 kj = c0 < a.k ? at_slice<VEC>(a.K, a.ldk, r, c0, a.k) : zero4();
-    const float4 vj = c0 < a.kv ? at_slice<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
+    const float4 kj = c0 < a.k ? load_slice<VEC>(a.K, a.ldk, r, c0, a.k) : zero4();
+    const float4 vj = c0 < a.kv ? load_slice<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
     float4 dk, dv;
     bwdkv_span<V, VEC>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv);
     float *s = g.scratch + p * kAtSlots;
@@ -564,69 +405,52 @@ __global__ __launch_bounds__(kAtBlock) void k_attn_bwd_kv_pieces(AttnPieces g, A
     if (c0 < a.kv) *reinterpret_cast<float4 *>(s + kAtSums2 + c0) = dv;
 }
 
-#define AT_LAUNCHED(name)                                                                                     \
-    if (hipError_t e_ = hipGetLastError(); e_ != hipSuccess) return hip_fail(e_, name, __FILE__, __LINE__)
-
 enum { kPassForward = 0, kPassBackwardQ = 1, kPassBackwardKV = 2 };
 
 template <int PASS, int V, bool VEC>
 int launch_attn_v(const spmv_csr &h, const AttnArgs &a, const char *what, hipStream_t s)
 {
     const SpmmPlan &p = h.plan_spmm;
-    constexpr int kPerBlock = kAtBlock / V;
-    const int64_t nblocks = (h.rows + kPerBlock - 1) / kPerBlock;
-    // (a launch carries fewer than 2^32 work-items, as in launch_spmm_v: rows x lanes per row < 2^32)
-    if (nblocks * kAtBlock >= (1LL << 32)) {
-        set_error("%s: %lld rows x %d lanes per row reach the launch limit of 2^32 work-items", what, (long long)h.rows, V);
-        return SPMV_ERR_INVALID;
-    }
-    const AttnRows g{h.rows, nblocks, p.row_cap, V == 1 ? nullptr : p.d_order.get(), h.d_row_ptr, h.d_col_idx};
-    const dim3 grid((unsigned)nblocks), block(kAtBlock);
+    const int64_t nblocks = group_row_blocks(what, h, V);
+    if (nblocks < 0) return SPMV_ERR_INVALID;
+    const GroupRows g = group_rows(h, V, nblocks);
+    const dim3 grid((unsigned)nblocks), block(kBlock);
     if constexpr (PASS == kPassForward) hipLaunchKernelGGL((k_attn_fwd_rows<V, VEC>), grid, block, 0, s, g, a);
     else if constexpr (PASS == kPassBackwardQ) hipLaunchKernelGGL((k_attn_bwd_q_rows<V, VEC>), grid, block, 0, s, g, a);
     else hipLaunchKernelGGL((k_attn_bwd_kv_rows<V, VEC>), grid, block, 0, s, g, a);
-    AT_LAUNCHED("k_attn_*_rows");
+    SPMV_LAUNCHED("k_attn_*_rows");
     if (!p.n_long) return SPMV_OK;
-    const AttnPieces q{p.pieces, p.n_long, p.d_long_row.get(), p.d_long_first.get(), p.d_piece_k0.get(), p.d_piece_len.get(),
-                       h.d_col_idx, h.plan_attn.d_scratch.get()};
-    const dim3 pgrid((unsigned)((p.pieces + kPerBlock - 1) / kPerBlock)), lgrid((unsigned)((p.n_long + kPerBlock - 1) / kPerBlock));
+    const GroupPieces q = group_pieces(h, h.plan_attn.d_scratch.get());
+    const dim3 pgrid = group_grid(p.pieces, V), lgrid = group_grid(p.n_long, V);
     if constexpr (PASS == kPassForward) {
         hipLaunchKernelGGL((k_attn_fwd_pieces<V, VEC>), pgrid, block, 0, s, q, a);
-        AT_LAUNCHED("k_attn_fwd_pieces");
+        SPMV_LAUNCHED("k_attn_fwd_pieces");
         hipLaunchKernelGGL((k_attn_fwd_combine<V, VEC>), lgrid, block, 0, s, q, a);
-        AT_LAUNCHED("k_attn_fwd_combine");
+        SPMV_LAUNCHED("k_attn_fwd_combine");
     } else if constexpr (PASS == kPassBackwardQ) {
         hipLaunchKernelGGL((k_attn_bwd_q_pieces<V, VEC>), pgrid, block, 0, s, q, a);
-        AT_LAUNCHED("k_attn_bwd_q_pieces");
+        SPMV_LAUNCHED("k_attn_bwd_q_pieces");
         hipLaunchKernelGGL((k_attn_add_pieces<V, VEC>), lgrid, block, 0, s, q, kAtSums, a.out0, a.ld0, a.k);
-        AT_LAUNCHED("k_attn_add_pieces");
+        SPMV_LAUNCHED("k_attn_add_pieces");
     } else {
         hipLaunchKernelGGL((k_attn_bwd_kv_pieces<V, VEC>), pgrid, block, 0, s, q, a);
-        AT_LAUNCHED("k_attn_bwd_kv_pieces");
+        SPMV_LAUNCHED("k_attn_bwd_kv_pieces");
         hipLaunchKernelGGL((k_attn_add_pieces<V, VEC>), lgrid, block, 0, s, q, kAtSums, a.out0, a.ld0, a.k);
-        AT_LAUNCHED("k_attn_add_pieces");
+        SPMV_LAUNCHED("k_attn_add_pieces");
         hipLaunchKernelGGL((k_attn_add_pieces<V, VEC>), lgrid, block, 0, s, q, kAtSums2, a.out1, a.ld1, a.kv);
-        AT_LAUNCHED("k_attn_add_pieces");
+        SPMV_LAUNCHED("k_attn_add_pieces");
     }
     return SPMV_OK;
-}
-
-template <int PASS, bool VEC>
-int launch_attn_vec(const spmv_csr &h, const AttnArgs &a, const char *what, hipStream_t s)
-{
-    const int slices = ((a.k > a.kv ? a.k : a.kv) + 3) / 4;
-    if (slices <= 1) return launch_attn_v<PASS, 1, VEC>(h, a, what, s);
-    if (slices <= 2) return launch_attn_v<PASS, 2, VEC>(h, a, what, s);
-    if (slices <= 4) return launch_attn_v<PASS, 4, VEC>(h, a, what, s);
-    if (slices <= 8) return launch_attn_v<PASS, 8, VEC>(h, a, what, s);
-    return launch_attn_v<PASS, 16, VEC>(h, a, what, s);
 }
 
 template <int PASS>
 int launch_attn(const spmv_csr &h, const AttnArgs &a, bool vec, const char *what, hipStream_t s)
 {
     if (h.rows == 0) return SPMV_OK;
-    return vec ? launch_attn_vec<PASS, true>(h, a, what, s) : launch_attn_vec<PASS, false>(h, a, what, s);
+    return dispatch_lanes(((a.k > a.kv ? a.k : a.kv) + 3) / 4, [&](auto v) {
+        constexpr int V = decltype(v)::value;
+        return vec ? launch_attn_v<PASS, V, true>(h, a, what, s) : launch_attn_v<PASS, V, false>(h, a, what, s);
+    });
 }
 
 bool vec4(std::initializer_list<int64_t> lds)

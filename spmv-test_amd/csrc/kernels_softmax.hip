@@ -4,7 +4,7 @@
 // row_ptr and the SpMM plan's long rows are read, never col_idx or vals.
 //
 // Geometry.  A wavefront owns 64 consecutive rows (a workgroup of 256 threads 256 rows, dealt per XCD as the SpMM blocks
-// are).  Lane l loads the bounds of row r0 + l; the longest of the 64 rows (rows of more than row_cap nonzeros count as
+// are: xcd_item64 of lane_group.hpp).  Lane l loads the bounds of row r0 + l; the longest of the 64 rows (rows of more than row_cap nonzeros count as
 // empty here) decides how the wavefront walks them:
 //   at most 64   groups of G = pow2 >= that length lanes, one row per group, 64 / G rows per pass, one element per lane:
 //                the rows are contiguous in storage, so a pass loads a nearly contiguous span;
@@ -30,7 +30,7 @@
 // Aliasing: out may be scores, dS may be P or dP (the identical pointer): every element is read by the lane that writes it,
 // and in the three-read walk the stores come in the last launch.  Hence no __restrict__ on these arrays.
 // Addresses are 64-bit; no buffer descriptor and no range check is relied on.
-#include "spmv_internal.hpp"
+#include "lane_group.hpp"
 
 #pragma clang fp contract(off)
 
@@ -43,14 +43,6 @@ constexpr int kSmWaves = kSmBlock / kWave;
 constexpr int kSmPiece = 512;                 // the most nonzeros a wavefront holds in registers
 constexpr int kSmRegs = kSmPiece / kWave;     // 8 per lane
 constexpr int kSmSlots = 64;                  // floats of plan scratch per piece (SpmmPlan::d_partial)
-
-// block b of the grid takes item sm_xcd_item(b, n): as spmm_xcd_item, each XCD gets one contiguous range of row blocks
-__device__ __forceinline__ int64_t sm_xcd_item(int64_t bid, int64_t n)
-{
-    const int64_t q = n / kXcds, rem = n % kXcds;
-    const int64_t j = bid % kXcds, idx = bid / kXcds;
-    return j * q + (j < rem ? j : rem) + idx;
-}
 
 // the xor-butterfly m = G/2 .. 1 inside every group of G lanes (G a power of two, wavefront-uniform)
 __device__ __forceinline__ float group_sum(float q, int G)
@@ -165,7 +157,7 @@ __global__ __launch_bounds__(kSmBlock) void k_softmax_rows(int64_t rows, int64_t
                                                            float *out)
 {
     const int lane = threadIdx.x & (kWave - 1);
-    const int64_t r0 = sm_xcd_item(blockIdx.x, nblocks) * kSmBlock + (threadIdx.x / kWave) * kWave;
+    const int64_t r0 = xcd_item64(blockIdx.x, nblocks) * kSmBlock + (threadIdx.x / kWave) * kWave;
     if (r0 >= rows) return;     // (wavefront-uniform, as every branch around a shuffle below)
     int b, len;
     const int lmax = wave_rows(r0, rows, row_cap, row_ptr, lane, b, len);
@@ -205,7 +197,7 @@ __global__ __launch_bounds__(kSmBlock) void k_softmax_bwd_rows(int64_t rows, int
                                                                const float *dP, float *dS)
 {
     const int lane = threadIdx.x & (kWave - 1);
-    const int64_t r0 = sm_xcd_item(blockIdx.x, nblocks) * kSmBlock + (threadIdx.x / kWave) * kWave;
+    const int64_t r0 = xcd_item64(blockIdx.x, nblocks) * kSmBlock + (threadIdx.x / kWave) * kWave;
     if (r0 >= rows) return;
     int b, len;
     const int lmax = wave_rows(r0, rows, row_cap, row_ptr, lane, b, len);
@@ -319,9 +311,6 @@ __global__ __launch_bounds__(kSmBlock) void k_softmax_fold(int n_long, const int
     partial[(int64_t)f * kSmSlots + dst] = acc;
 }
 
-#define SM_LAUNCHED(name)                                                                                     \
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, name, __FILE__, __LINE__)
-
 int check_plan(const SpmmPlan &p, const char *what)
 {
     if (p.row_cap > kSmPiece || p.piece_len > kSmPiece) {   // (a wavefront holds a row or a piece in 8 registers per lane)
@@ -342,21 +331,21 @@ int launch_row_softmax(const spmv_csr &h, float scale, const float *scores, floa
     const int64_t nblocks = (h.rows + kSmBlock - 1) / kSmBlock;      // (rows < 2^31: fewer than 2^23 blocks)
     hipLaunchKernelGGL(k_softmax_rows, dim3((unsigned)nblocks), dim3(kSmBlock), 0, s, h.rows, nblocks, p.row_cap, h.d_row_ptr,
                        scale, scores, out);
-    SM_LAUNCHED("k_softmax_rows");
+    SPMV_LAUNCHED("k_softmax_rows");
     if (!p.n_long) return SPMV_OK;
     const dim3 pg((unsigned)((p.pieces + kSmWaves - 1) / kSmWaves)), lg((unsigned)((p.n_long + kSmBlock - 1) / kSmBlock));
     const int32_t *lf = p.d_long_first.get(), *k0 = p.d_piece_k0.get(), *ln = p.d_piece_len.get();
     float *part = p.d_partial.get();
     hipLaunchKernelGGL(k_softmax_pieces<kPieceMax>, pg, dim3(kSmBlock), 0, s, p.pieces, p.n_long, lf, k0, ln, scale, scores, out, part);
-    SM_LAUNCHED("k_softmax_pieces<max>");
+    SPMV_LAUNCHED("k_softmax_pieces<max>");
     hipLaunchKernelGGL(k_softmax_fold<true>, lg, dim3(kSmBlock), 0, s, p.n_long, lf, part, 0, 2);
-    SM_LAUNCHED("k_softmax_fold<max>");
+    SPMV_LAUNCHED("k_softmax_fold<max>");
     hipLaunchKernelGGL(k_softmax_pieces<kPieceSum>, pg, dim3(kSmBlock), 0, s, p.pieces, p.n_long, lf, k0, ln, scale, scores, out, part);
-    SM_LAUNCHED("k_softmax_pieces<sum>");
+    SPMV_LAUNCHED("k_softmax_pieces<sum>");
     hipLaunchKernelGGL(k_softmax_fold<false>, lg, dim3(kSmBlock), 0, s, p.n_long, lf, part, 1, 3);
-    SM_LAUNCHED("k_softmax_fold<sum>");
+    SPMV_LAUNCHED("k_softmax_fold<sum>");
     hipLaunchKernelGGL(k_softmax_pieces<kPieceStore>, pg, dim3(kSmBlock), 0, s, p.pieces, p.n_long, lf, k0, ln, scale, scores, out, part);
-    SM_LAUNCHED("k_softmax_pieces<store>");
+    SPMV_LAUNCHED("k_softmax_pieces<store>");
     return SPMV_OK;
 }
 
@@ -368,17 +357,17 @@ int launch_row_softmax_backward(const spmv_csr &h, float scale, const float *P, 
     const int64_t nblocks = (h.rows + kSmBlock - 1) / kSmBlock;
     hipLaunchKernelGGL(k_softmax_bwd_rows, dim3((unsigned)nblocks), dim3(kSmBlock), 0, s, h.rows, nblocks, p.row_cap, h.d_row_ptr,
                        scale, P, dP, dS);
-    SM_LAUNCHED("k_softmax_bwd_rows");
+    SPMV_LAUNCHED("k_softmax_bwd_rows");
     if (!p.n_long) return SPMV_OK;
     const dim3 pg((unsigned)((p.pieces + kSmWaves - 1) / kSmWaves)), lg((unsigned)((p.n_long + kSmBlock - 1) / kSmBlock));
     const int32_t *lf = p.d_long_first.get(), *k0 = p.d_piece_k0.get(), *ln = p.d_piece_len.get();
     float *part = p.d_partial.get();
     hipLaunchKernelGGL(k_softmax_bwd_pieces<false>, pg, dim3(kSmBlock), 0, s, p.pieces, p.n_long, lf, k0, ln, scale, P, dP, dS, part);
-    SM_LAUNCHED("k_softmax_bwd_pieces<dot>");
+    SPMV_LAUNCHED("k_softmax_bwd_pieces<dot>");
     hipLaunchKernelGGL(k_softmax_fold<false>, lg, dim3(kSmBlock), 0, s, p.n_long, lf, part, 0, 2);
-    SM_LAUNCHED("k_softmax_fold<dot>");
+    SPMV_LAUNCHED("k_softmax_fold<dot>");
     hipLaunchKernelGGL(k_softmax_bwd_pieces<true>, pg, dim3(kSmBlock), 0, s, p.pieces, p.n_long, lf, k0, ln, scale, P, dP, dS, part);
-    SM_LAUNCHED("k_softmax_bwd_pieces<store>");
+    SPMV_LAUNCHED("k_softmax_bwd_pieces<store>");
     return SPMV_OK;
 }
 

@@ -1,0 +1,257 @@
+// lane_group.hpp -- the lane groups that SpMM, SDDMM and fused attention walk a CSR pattern with (kernels_spmm.hip,
+// kernels_sddmm.hip, kernels_attention.hip): the one statement of the model, of its device code and of the part of the
+// order-of-operations contract the three share.  Each kernel file states only what is its own.
+//
+// The model.  The operands are row-major matrices of k <= 64 columns (attention: k and kv, the wider decides).  A group
+// of V = pow2 >= ceil(k / 4) lanes (1, 2, 4, 8 or 16: dispatch_lanes) owns one row of the pattern, or one plan piece of a
+// row of more than row_cap = 512 nonzeros (SpmmPlan: the order of the rows, the long rows, their pieces of 512).  Lane s
+// of the group holds the slice [4s, 4s+4) of the columns: of the row's own operands in registers, and of every operand
+// row the CSR row refers to.  A workgroup is kBlock = 256 lanes, 256 / V groups; the row blocks are dealt so that each of
+// the 8 XCDs takes one contiguous range of them (xcd_item64: neighbouring rows share lines of the gathered operand in
+// that XCD's L2).  The groups take the rows in the plan's order (stably by length inside blocks of 4096 rows, so the rows a
+// wavefront walks side by side end at nearly the same step), except at V = 1: see group_rows.
+// A group walks its row in steps of T = max(V, 8) nonzeros (LaneGeom): lane s loads the step's column indices
+// kb + i V + s, i < L = T / V, coalesced (0 past the end), the group broadcasts them with shuffles (group_columns), every
+// lane issues all its gathers of the step, one slice per nonzero and operand (load_slice), and only then computes.
+// All lanes of a group run every step and every shuffle together: the exits (group_row, group_piece) are group-uniform.
+//
+// The order of the fp32 operations, as far as it is shared.  No function here holds a product followed by a sum but
+// where fmaf is written, so the floating-point contraction of the including file does not reach in.
+//   * A sum over a row's nonzeros runs in storage order from +0, one fma per nonzero and column.  A slot of the last step
+//     that lies past the end adds nothing: not even +0, which would turn an accumulator of -0 into +0.  Hence the
+//     `kb + t < e` around every accumulation of the kernels; the slot's gathers are not issued either.
+//   * A dot product over the columns (dot_partial, then the group): lane s forms p_s = +0, p_s = fma(a[c], b[c], p_s) for
+//     c = 4s .. 4s+3 while c < k (a column at or past k is skipped, not multiplied by zero; a lane whose slice starts at or
+//     past k keeps +0), then the V partials are added in the xor butterfly m = V/2, V/4, .., 1: p_s <- p_s + p_(s xor m).
+//   * reduce_scatter runs that butterfly for the V results of a step at once: after the exchange at distance m a lane
+//     keeps only the half of the results whose index has the lane's bit m, V - 1 shuffles per V results instead of
+//     V log2 V.  Each result still goes through the very additions of the full butterfly, in the same order of levels, and
+//     fp32 addition is commutative: the bits are the full butterfly's (group_sum's).
+//   * A wider V than ceil(k / 4) asks for (attention with kv > k against SDDMM at k) changes no bit: fma(a, b, +0) is never
+//     -0 and neither is a sum of two numbers that are not -0, so a partial is never -0; the extra lanes hold +0 and the
+//     extra levels, which run first, add +0 to a number that is not -0.
+// So a result is a function of the row's column list in storage order, the operands and k: not of V beyond that, of any
+// ld, of the load path, of the row's place, its pieces' neighbours or the handle.
+//
+// Addresses are 64-bit throughout (an operand may exceed 4 GiB; 4 n passes 2^32 in col_idx from nnz = 2^30 on); no buffer
+// descriptor and no range check is relied on.  The ld % 4 rule: where every ld of a call is a multiple of 4 (and the bases
+// are 16-byte aligned: the C ABI checks) a slice is one 16-byte access (VEC); the last slice of a k that is no multiple
+// of 4 is then read whole, inside its row's ld floats, and stored below k only.  Otherwise the kernels read and store
+// 4-byte elements, columns below k only.
+#pragma once
+#include <type_traits>
+#include "spmv_internal.hpp"
+
+namespace spmv {
+
+template <int V>
+struct LaneGeom {
+    static constexpr int T = V > 8 ? V : 8;   // nonzeros per step: T slice gathers in flight per lane and operand
+    static constexpr int L = T / V;           // of which a lane loads the column indices of L and ends with L results
+};
+
+// block b of the grid takes item xcd_item64(b, n): blocks are dealt round-robin over the 8 XCDs, so each XCD gets one
+// contiguous range of the n row blocks
+__device__ __forceinline__ int64_t xcd_item64(int64_t bid, int64_t n)
+{
+    const int64_t q = n / kXcds, rem = n % kXcds;
+    const int64_t j = bid % kXcds, idx = bid / kXcds;
+    return j * q + (j < rem ? j : rem) + idx;
+}
+
+__device__ __forceinline__ float4 zero4() { return make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+
+// the four columns [c0, c0+4) of row j of a row-major matrix (c0 < w); VEC: one 16-byte load, else the columns below w only
+template <bool VEC>
+__device__ __forceinline__ float4 load_slice(const float *__restrict__ M, int64_t ld, int64_t j, int c0, int w)
+{
+    const float *p = M + j * ld + c0;
+    if (VEC) return *reinterpret_cast<const float4 *>(p);
+    float4 r = zero4();
+    r.x = p[0];
+    if (c0 + 1 < w) r.y = p[1];
+    if (c0 + 2 < w) r.z = p[2];
+    if (c0 + 3 < w) r.w = p[3];
+    return r;
+}
+
+// the columns [c0, c0+4) below w of one output row (c0 < w; vector stores only)
+template <bool VEC>
+__device__ __forceinline__ void store_slice(float *__restrict__ p, float4 a, int c0, int w)
+{
+    if (VEC && c0 + 4 <= w) {
+        *reinterpret_cast<float4 *>(p) = a;
+        return;
+    }
+    p[0] = a.x;
+    if (c0 + 1 < w) p[1] = a.y;
+    if (c0 + 2 < w) p[2] = a.z;
+    if (c0 + 3 < w) p[3] = a.w;
+}
+
+// the lane's partial of a dot product: fma over its n1 = w - c0 columns (at most 4) from +0; +0 for an idle lane
+__device__ __forceinline__ float dot_partial(float4 u, float4 x, int n1)
+{
+    float a = 0.0f;
+    if (n1 > 0) {
+        a = fmaf(u.x, x.x, a);
+        if (n1 > 1) a = fmaf(u.y, x.y, a);
+        if (n1 > 2) a = fmaf(u.z, x.z, a);
+        if (n1 > 3) a = fmaf(u.w, x.w, a);
+    }
+    return a;
+}
+
+// the xor butterfly over the group as a reduce-scatter: of results i*V + [0, V) lane `sub` ends with result i*V + sub in
+// p[i*V]
+template <int V, int T>
+__device__ __forceinline__ void reduce_scatter(float (&p)[T], int sub)
+{
+#pragma unroll
+    for (int i = 0; i < T / V; ++i) {
+#pragma unroll
+        for (int m = V / 2; m >= 1; m /= 2) {
+            const bool up = (sub & m) != 0;
+#pragma unroll
+            for (int j = 0; j < m; ++j) {
+                const float lo = p[i * V + j], hi = p[i * V + j + m];
+                const float keep = up ? hi : lo, send = up ? lo : hi;
+                p[i * V + j] = keep + __shfl_xor(send, m);
+            }
+        }
+    }
+}
+
+// what lane `sub` holds for nonzero i*V + sub of the step, in every lane of the group
+template <int V, int T, typename X>
+__device__ __forceinline__ void group_bcast(const X (&w)[T / V], X (&wt)[T], int gbase)
+{
+#pragma unroll
+    for (int t = 0; t < T; ++t) wt[t] = V == 1 ? w[t] : __shfl(w[t / V], gbase + t % V);
+}
+
+template <int V>
+__device__ __forceinline__ float group_max(float x)
+{
+#pragma unroll
+    for (int m = V / 2; m >= 1; m /= 2) x = fmaxf(x, __shfl_xor(x, m));
+    return x;
+}
+
+template <int V>
+__device__ __forceinline__ float group_sum(float x)
+{
+#pragma unroll
+    for (int m = V / 2; m >= 1; m /= 2) x = x + __shfl_xor(x, m);
+    return x;
+}
+
+// the step's column indices: lane `sub` loads nonzeros kb + i*V + sub (0 past the end e), every lane gets all T
+template <int V, int T>
+__device__ __forceinline__ void group_columns(int64_t kb, int64_t e, int sub, int gbase, const int32_t *__restrict__ col_idx,
+                                              int32_t (&c)[T / V], int32_t (&ct)[T])
+{
+#pragma unroll
+    for (int i = 0; i < T / V; ++i) {
+        const int64_t n = kb + (int64_t)i * V + sub;
+        c[i] = n < e ? col_idx[n] : 0;
+    }
+    group_bcast<V, T>(c, ct, gbase);
+}
+
+// the rows and the pieces of a launch (kernel arguments, by value)
+struct GroupRows {
+    int64_t rows, nblocks;
+    int row_cap;
+    const int32_t *order, *row_ptr, *col_idx;
+};
+struct GroupPieces {
+    int npieces, n_long;
+    const int32_t *long_row, *long_first, *piece_k0, *piece_len, *col_idx;
+    float *scratch;     // the caller's floats per piece
+};
+
+// the row of slot `threadIdx.x / V` of the block, or -1 (group-uniform: a group never splits here)
+template <int V>
+__device__ __forceinline__ int64_t group_row(const GroupRows &g)
+{
+    const int64_t slot = xcd_item64(blockIdx.x, g.nblocks) * (kBlock / V) + threadIdx.x / V;
+    if (slot >= g.rows) return -1;
+    return g.order ? g.order[slot] : slot;
+}
+
+// the piece of the group, or -1 (group-uniform)
+template <int V>
+__device__ __forceinline__ int64_t group_piece(const GroupPieces &g)
+{
+    const int64_t p = (int64_t)blockIdx.x * (kBlock / V) + threadIdx.x / V;
+    return p < g.npieces ? p : -1;
+}
+
+// the same and the index of its long row: long_first[lo] <= p < long_first[lo + 1]  (long_first[0] = 0,
+// long_first[n_long] = npieces)
+template <int V>
+__device__ __forceinline__ int64_t group_piece(const GroupPieces &g, int &lo)
+{
+    const int64_t p = group_piece<V>(g);
+    if (p < 0) return -1;
+    int hi = g.n_long;
+    lo = 0;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) / 2;
+        if (g.long_first[mid] <= p) lo = mid;
+        else hi = mid;
+    }
+    return p;
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------
+// calls f(std::integral_constant<int, V>) for the V of `slices` = ceil(k / 4) slices, k <= 64
+template <typename F>
+int dispatch_lanes(int slices, F &&f)
+{
+    if (slices <= 1) return f(std::integral_constant<int, 1>{});
+    if (slices <= 2) return f(std::integral_constant<int, 2>{});
+    if (slices <= 4) return f(std::integral_constant<int, 4>{});
+    if (slices <= 8) return f(std::integral_constant<int, 8>{});
+    return f(std::integral_constant<int, 16>{});
+}
+
+// a grid of kBlock lanes for `groups` groups of V lanes
+inline dim3 group_grid(int64_t groups, int V)
+{
+    const int per = kBlock / V;
+    return dim3((unsigned)((groups + per - 1) / per));
+}
+
+// the row blocks of a launch over the rows of h, or -1 and `who`'s error.  (A launch carries fewer than 2^32 work-items --
+// the runtime passes grid x block on in 32 bits and a larger product wraps silently: rows x lanes per row < 2^32 -- any
+// handle up to k = 8, rows < 2^30 / 2^29 / 2^28 up to k = 16 / 32 / 64.)
+inline int64_t group_row_blocks(const char *who, const spmv_csr &h, int V)
+{
+    const int per = kBlock / V;
+    const int64_t nblocks = (h.rows + per - 1) / per;
+    if (nblocks * kBlock >= (1LL << 32)) {
+        set_error("%s: %lld rows x %d lanes per row reach the launch limit of 2^32 work-items", who, (long long)h.rows, V);
+        return -1;
+    }
+    return nblocks;
+}
+
+// V = 1 (k <= 4) keeps the row order: there each lane streams its own row's col_idx (and vals), and neighbouring rows keep
+// those loads on neighbouring lines (measured on SpMM: 2x faster at k = 1 and 4 on configs 3 and 4; from V = 2 on the
+// plan's sorted order wins, up to 2.5x)
+inline GroupRows group_rows(const spmv_csr &h, int V, int64_t nblocks)
+{
+    const SpmmPlan &p = h.plan_spmm;
+    return GroupRows{h.rows, nblocks, p.row_cap, V == 1 ? nullptr : p.d_order.get(), h.d_row_ptr, h.d_col_idx};
+}
+
+inline GroupPieces group_pieces(const spmv_csr &h, float *scratch)
+{
+    const SpmmPlan &p = h.plan_spmm;
+    return GroupPieces{p.pieces, p.n_long, p.d_long_row.get(), p.d_long_first.get(), p.d_piece_k0.get(), p.d_piece_len.get(),
+                       h.d_col_idx, scratch};
+}
+
+}  // namespace spmv

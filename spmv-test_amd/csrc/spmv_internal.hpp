@@ -26,6 +26,10 @@ static inline int check_launch(const char *what)
     return SPMV_OK;
 }
 
+// after a kernel launch in a function that returns an SPMV_* code: leaves with the launch's error, if any
+#define SPMV_LAUNCHED(name)                                                                                     \
+    if (hipError_t e__ = hipGetLastError(); e__ != hipSuccess) return ::spmv::hip_fail(e__, name, __FILE__, __LINE__)
+
 // The one owner of a device array: move-only, freed when it is destroyed, reset() or assigned over.  Reads convert it to
 // T * (kernel arguments, offsets, null tests); it is written only by alloc(), a move or reset(), never from a raw pointer.
 // Not for anything of static storage duration: its destructor would call hipFree after the HIP runtime may be gone.

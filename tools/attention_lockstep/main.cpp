@@ -1,7 +1,10 @@
 // tools/attention_lockstep/main.cpp -- see run.sh.  One pattern whose rows (and whose transposed rows) cover empty rows, rows
 // inside one step, several steps, exactly 512, pieces of long rows; the three passes at four (k, kv) on the 16-byte and the
-// 4-byte load path, every array an exactly sized heap block, compared with a serial fp64 statement of attention.
+// 4-byte load path, every array an exactly sized heap block, compared with a serial fp64 statement of attention.  SDDMM
+// at the same four k on the pattern and on its transpose, every out[n] compared bit for bit with a serial statement of
+// the documented order.
 #include "kernels_attention.hip"
+#include "kernels_sddmm.hip"
 #include <algorithm>
 #include <cstdlib>
 #include <random>
@@ -64,6 +67,41 @@ static float *matrix(int64_t rows, int w, int64_t ld, std::mt19937 &rng, bool fi
     std::normal_distribution<float> nd(0.f, 1.f);
     for (size_t i = 0; i < n; ++i) p[i] = fill ? nd(rng) : NAN;
     return p;
+}
+
+// SDDMM's documented order, serially: the lane partials by fmaf from +0 over the columns below k, then the pairwise tree
+// the xor butterfly spells
+static float sddmm_serial(const float *u, const float *x, int k, int V)
+{
+    float p[16], q[16];
+    for (int s = 0; s < V; ++s) {
+        p[s] = 0.0f;
+        for (int c = 4 * s; c < 4 * s + 4 && c < k; ++c) p[s] = fmaf(u[c], x[c], p[s]);
+    }
+    for (int m = V / 2; m >= 1; m /= 2) {
+        for (int s = 0; s < V; ++s) q[s] = p[s] + p[s ^ m];
+        std::copy(q, q + V, p);
+    }
+    return p[0];
+}
+
+// launch_sddmm on the handle h of pattern a into an exactly sized block: how many out[n] differ from the serial statement
+// in any bit (-1: the launch failed)
+static long sddmm_differing(const spmv_csr &h, const Pattern &a, int k, const float *U, int64_t ldu, const float *X, int64_t ldx)
+{
+    int V = 1;
+    while (4 * V < k) V *= 2;
+    g_group_lanes = V;
+    std::vector<float> nan((size_t)h.nnz, NAN);
+    float *out = heap(nan);
+    long bad = launch_sddmm(h, k, U, ldu, X, ldx, out, nullptr) == SPMV_OK ? 0 : -1;
+    for (int64_t r = 0; bad >= 0 && r < a.rows; ++r)
+        for (int n = a.rp[r]; n < a.rp[r + 1]; ++n) {
+            const float want = sddmm_serial(U + r * ldu, X + a.ci[n] * ldx, k, V);
+            bad += std::memcmp(&want, out + n, 4) != 0;
+        }
+    free(out);
+    return bad;
 }
 
 int main()
@@ -165,6 +203,11 @@ int main()
                 for (int c = 0; c < kv; ++c) err(dV[j * ld(kv) + c], rdV[(size_t)(j * kv + c)], mV[(size_t)(j * kv + c)] + (t.rp[j + 1] == t.rp[j] ? 1.0 : 0.0));
             }
             printf("k %d kv %d V %d %s: status %d, worst normalised error so far %.3g\n", k, kv, V, odd ? "4-byte path" : "16-byte path", status, worst);
+            // SDDMM at this k: U = Q, X = K on the pattern; the operands trade places on the transpose
+            const long sa = sddmm_differing(A, a, k, Q, ld(k), K, ld(k)), st = sddmm_differing(T, t, k, K, ld(k), Q, ld(k));
+            printf("sddmm k %d %s: %ld of %lld results differ in a bit on the pattern, %ld on its transpose\n", k,
+                   odd ? "4-byte path" : "16-byte path", sa, (long long)A.nnz, st);
+            if (sa != 0 || st != 0) status |= 32;
             for (void *p : {(void *)Q, (void *)K, (void *)Vm, (void *)dO, (void *)O, (void *)dQ, (void *)dK, (void *)dV, (void *)stats, (void *)delta}) free(p);
         }
     for (void *p : owned) free(p);

@@ -2,14 +2,17 @@
 # tools/attention_lockstep/run.sh -- csrc/kernels_attention.hip executed on the host, a thread per work-item, the lanes of a
 # group in lockstep at every shuffle, under AddressSanitizer and UBSan: forward, backward_q and backward_kv at four (k, kv)
 # on both load paths, rows and pieces on the pattern and on its transpose, every array an exactly sized heap block, against
-# a serial fp64 statement of attention (2e-5 of the magnitude).  Needs no device: a check of the kernels' logic, bounds
-# and alignment, not of the GPU.  The kernel file is copied beside the stubs so that its #include finds the stub.
+# a serial fp64 statement of attention (2e-5 of the magnitude); and csrc/kernels_sddmm.hip, built from the same
+# csrc/lane_group.hpp, at the same four k on the same patterns, every out[n] bit for bit against a serial statement of the
+# documented order.  Needs no device: a check of the kernels' logic, bounds and alignment, not of the GPU.  The kernel
+# files and lane_group.hpp are copied beside the stubs so that their #include "spmv_internal.hpp" finds the stub.
 set -euo pipefail
 here=$(cd "$(dirname "$0")" && pwd)
 work=$(mktemp -d)
 trap 'rm -rf "$work"' EXIT
 cp -r "$here"/hip "$here"/spmv_internal.hpp "$here"/main.cpp "$work"/
-cp "$here"/../../spmv-test_amd/csrc/kernels_attention.hip "$work"/
+cp "$here"/../../spmv-test_amd/csrc/kernels_attention.hip "$here"/../../spmv-test_amd/csrc/kernels_sddmm.hip \
+   "$here"/../../spmv-test_amd/csrc/lane_group.hpp "$work"/
 ${CXX:-clang++} -std=c++20 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off -I"$work" -x c++ "$work"/main.cpp -o "$work"/lockstep -lpthread
 "$work"/lockstep
 echo "lockstep ok"

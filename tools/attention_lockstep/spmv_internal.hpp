@@ -1,5 +1,6 @@
 #pragma once
-// tools/attention_lockstep: the few names of csrc/spmv_internal.hpp that csrc/kernels_attention.hip uses, without HIP
+// tools/attention_lockstep: the few names of csrc/spmv_internal.hpp that csrc/lane_group.hpp, csrc/kernels_attention.hip and
+// csrc/kernels_sddmm.hip use, without HIP
 #include <hip/hip_runtime.h>
 #include <cstdarg>
 #include <cstdio>
@@ -7,8 +8,9 @@
 #include <utility>
 enum { SPMV_OK = 0, SPMV_ERR_INVALID = -2 };
 #define SPMV_HIP_TRY(call) do { if ((call) != hipSuccess) return -3; } while (0)
+#define SPMV_LAUNCHED(name) if (hipGetLastError() != hipSuccess) return -3
 namespace spmv {
-constexpr int kWave = 64; constexpr int kXcds = 8;
+constexpr int kWave = 64; constexpr int kBlock = 256; constexpr int kXcds = 8;
 inline void set_error(const char *f, ...) { va_list a; va_start(a, f); vfprintf(stderr, f, a); va_end(a); }
 inline int hip_fail(hipError_t, const char *, const char *, int) { return -3; }
 template <class T> struct DevPtr {       // (exactly sized heap blocks; freed by main through free_all)

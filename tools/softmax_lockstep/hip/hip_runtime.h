@@ -15,6 +15,8 @@
 #define __forceinline__ inline
 #define __launch_bounds__(x)
 #define __restrict__
+struct alignas(16) float4 { float x, y, z, w; };     // (for csrc/lane_group.hpp; the softmax kernels use none)
+inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
 struct dim3 { unsigned x = 1, y = 1, z = 1; dim3(unsigned a = 1) : x(a) {} };
 typedef int hipError_t;
 typedef void *hipStream_t;
