@@ -3,20 +3,36 @@ attention") and sparse_attention.FusedSparseAttention on top of them.  Every dir
 outputs between guard bands of 4096 floats (and guard columns where ld exceeds the width) that must stay untouched.
 
 exact       the pattern and data of test_gpu_sparse_attention's exact test (row lengths 1 .. 16, powers of two; integer V and
-            dO; Q = 0 or K = 0): O, dQ, dK and dV equal torch's fp64 dense autograd bit for bit (+0 and -0 folded).
-scores      stats[:, 0] is bit for bit the row maximum of fp32(scale * A.sddmm(Q, K)).
+            dO; Q = 0 or K = 0): O, dQ, dK and dV equal torch's fp64 dense autograd bit for bit (+0 and -0 folded), at
+            scale = 2^-2 and at -0.375, where nothing is rounded either.
+scores      stats[:, 0] is bit for bit the row maximum of fp32(scale * A.sddmm(Q, K)), at 16, 8 and 1 lanes per row and at
+            scales 2^-2, 0.3 and -0.7 (there the scaled minimum of the scores).
 general     three patterns (short rows; rows of 512 .. 4100 beside short ones; 3000 queries on 48 keys, whose transposed rows
             lie on both sides of 512) times four (k, kv), one of them also with every ld % 4 != 0.  The error of O divided by
             P |V| and the gradients' errors divided by the magnitudes of test_gpu_sparse_attention are each at most
             max(4 x torch's fp32 dense autograd under the same normalisation, RTOL): another order of the sums at equal
             precision may differ by a small factor.  The composed SparseAttention's figures are printed beside the fused ones.
+            Four more (k, kv) with k, kv <= 4 run one lane per row (no plan order, no shuffle, 8 column indices per lane), on
+            both load paths; two patterns run at scales 0.3 and -1.7 as well (t and ds are rounded there; the reference
+            takes fp32(scale), what the kernel receives).
+zero        scale = +0 and -0: dQ = dK = 0, stats[:, 0] = 0, O and dV by the general rule (every p is 1 / L).
 masks       keys masked with K[j, 0] = -Inf (Q[:, 0] = 1): rows whose first 20 entries are masked, rows masked entirely, a row
             with a NaN, empty rows.  The reference is the dense autograd of the pattern WITHOUT the masked entries and with a
             finite K.  One deviation is IEEE's, not the kernel's: dQ[i][0] of a row that lists a masked key is 0 * -Inf = NaN
             in every implementation (torch's dense autograd and the composed path included), so that column is checked to be
             NaN there and everything else against the reference.
+special     tests/_attention_rows.py's rows on 2600 keys with masked stretches on both sides of the finite keys: 512 or 1024
+            leading or 512 trailing masked entries leave the bits of O, stats and dQ[:, 1:] to the finite entries alone
+            (whole masked pieces in the combine), masked entries across a piece boundary pass the general rule, long rows
+            that are masked entirely or hold a NaN or a +Inf are NaN rows, and three keys that 700 queries list run in
+            pieces on the transposed handle: the masked one gets dK = dV = 0, the one a NaN row lists NaN, the third is
+            compared.  Once with 4 lanes per row, once with 1.
 invariance  40 rows of 1 .. 700 entries give the same bits of O, stats and dQ among short rows, among rows of 300, as a row
-            block with a rebased row_ptr, with strided operands and on the 4-byte load path.
+            block with a rebased row_ptr, with strided operands and on the 4-byte load path; at 8 lanes per row and at 1.
+extreme     tests/_attention_rows.py's score profiles, every score exact: maxima that rise or fall at every step (by 0.5, or
+            by 128 and more so that the rescaling factor underflows), a spike of 200 first or last (at 513 entries the only
+            nonzero of the last piece), 0 and -200 in turn, scores near 256; lengths 1 .. 1025.  The general rule with an
+            absolute floor of 2^-90 for what underflows; every output finite.
 heads       three heads as column blocks of (rows, 24) tensors: no copy, and the bits of three single-head calls.
 memory      a forward plus backward step of the fused holder allocates less than 4 nnz bytes; the composed holder more.
 graph       the three passes captured on one stream and replayed with new data in place: the bits of the eager run.
@@ -28,6 +44,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import _attention_rows as R
 import _exact as E
 from _util import RTOL
 
@@ -165,7 +182,7 @@ def _randn(gpu, seed, *shapes):
 
 
 # ---- exact -----------------------------------------------------------------------------------------------------------
-def test_fused_attention_exact_against_dense_fp64_autograd(pkg, gpu):
+def _exact(pkg, gpu, SCALE):
     import torch
     s = _pow2_pattern(3000, 2000, 5)
     assert set(np.diff(s.rp)) == {1, 2, 4, 8, 16}
@@ -213,22 +230,41 @@ def test_fused_attention_exact_against_dense_fp64_autograd(pkg, gpu):
         a.close()
 
 
+def test_fused_attention_exact_against_dense_fp64_autograd(pkg, gpu):
+    _exact(pkg, gpu, SCALE)
+
+
+def test_fused_attention_exact_at_a_scale_that_is_no_power_of_two(pkg, gpu):
+    """scale = -0.375: the scores are 0 (or -0), p = 2^-m and ds a multiple of 2^-11 below 2^8, so every intermediate is
+    still an fp32 number and the bits are the fp64 autograd's; the composed path's as well."""
+    _exact(pkg, gpu, -0.375)
+
+
 # ---- the scores are SDDMM's ------------------------------------------------------------------------------------------
 def test_fused_attention_row_maximum_is_the_sddmm_scores(pkg, gpu):
     import torch
-    rows, cols, per, k = 512, 300, 24, 20
+    rows, cols, per = 512, 300, 24
     s = _rows_pattern([per] * rows, cols, 7)
     h = Handles(pkg, s, gpu)
-    Q, K, V, dO = _randn(gpu, 3, (rows, k), (cols, k), (cols, k), (rows, k))
-    got = _run(h, Q, K, V, dO, SCALE)
-    S = torch.empty(s.nnz, dtype=torch.float32, device=gpu)
-    h.A.sddmm(Q, K, S)
-    t = torch.tensor(SCALE, dtype=torch.float32, device=gpu) * S
-    assert torch.equal(_raw_bits(got["stats"][:, 0]), _raw_bits(t.view(rows, per).max(1).values))
-    # ... and on a wider group than SDDMM's for this k (kv = 40: V = 16 against 8)
-    V2, dO2 = _randn(gpu, 4, (cols, 40), (rows, 40))
-    got2 = _run(h, Q, K, V2, dO2, SCALE)
-    assert torch.equal(_raw_bits(got2["stats"][:, 0]), _raw_bits(got["stats"][:, 0]))
+    for k, kv in ((20, 20), (3, 4)):                         # (3, 4): one lane per row
+        Q, K, V, dO = _randn(gpu, 3, (rows, k), (cols, k), (cols, kv), (rows, kv))
+        S = torch.empty(s.nnz, dtype=torch.float32, device=gpu)
+        h.A.sddmm(Q, K, S)
+        assert bool((S.view(rows, per).max(1).values > 0).all()) and bool((S.view(rows, per).min(1).values < 0).all())
+        # 0.3 and -0.7: t = scale * s is rounded; at -0.7 the maximum of t is the scaled minimum of s
+        for scale in (SCALE, 0.3, -0.7):
+            got = _run(h, Q, K, V, dO, scale)
+            t = torch.tensor(scale, dtype=torch.float32, device=gpu) * S
+            assert t.dtype == torch.float32
+            assert torch.equal(_raw_bits(got["stats"][:, 0]), _raw_bits(t.view(rows, per).max(1).values)), f"k={k} scale={scale}"
+            if scale < 0:
+                assert torch.equal(got["stats"][:, 0], torch.tensor(scale, dtype=torch.float32, device=gpu) * S.view(rows, per).min(1).values)
+            if k != 20:
+                continue
+            # ... and on a wider group than SDDMM's for this k (kv = 40: V = 16 against 8)
+            V2, dO2 = _randn(gpu, 4, (cols, 40), (rows, 40))
+            got2 = _run(h, Q, K, V2, dO2, scale)
+            assert torch.equal(_raw_bits(got2["stats"][:, 0]), _raw_bits(got["stats"][:, 0]))
     h.close()
 
 
@@ -253,19 +289,20 @@ def _normalised(mask, scale, Q, K, V, dO, P):
     return {"O": P @ aV, "dQ": dS_abs @ aK, "dK": dS_abs.t() @ aQ, "dV": P.t() @ adO}
 
 
-def _check_general(tag, got, mask, scale, Q, K, V, dO, other=None, rows=None, cols=None):
+def _check_general(tag, got, mask, scale, Q, K, V, dO, other=None, rows=None, cols=None, whats=("O", "dQ", "dK", "dV")):
     """got[what] against the fp64 dense autograd, yardstick torch's fp32 dense autograd; `other`: results printed beside.
-    rows / cols: boolean selections of the queries / keys that are compared (None: all)."""
+    rows / cols: boolean selections of the queries / keys that are compared (None: all); whats: the outputs compared."""
     import torch
     *r64, P = _dense_autograd(mask, scale, Q, K, V, dO, torch.float64)
     r64 = dict(zip(("O", "dQ", "dK", "dV"), r64))
     r32 = dict(zip(("O", "dQ", "dK", "dV"), _dense_autograd(mask, scale, Q, K, V, dO, torch.float32)))
     mags = _normalised(mask, scale, Q, K, V, dO, P)
-    for what in ("O", "dQ", "dK", "dV"):
+    for what in whats:
         sel = rows if what in ("O", "dQ") else cols
         pick = (lambda t: t) if sel is None else (lambda t: t[sel])
         g, g64, g32, mag = pick(got[what]), pick(r64[what]), pick(r32[what]), pick(mags[what])
         live = mag > 0
+        assert bool(live.any()), f"{tag} {what}: nothing to compare"
         assert bool((g[~live] == 0).all()), f"{tag} {what}: a value where nothing contributes"
         ours = float(((g.double() - g64).abs()[live] / mag[live]).max())
         yard = float(((g32.double() - g64).abs()[live] / mag[live]).max())
@@ -276,13 +313,21 @@ def _check_general(tag, got, mask, scale, Q, K, V, dO, other=None, rows=None, co
         assert ours <= max(4.0 * yard, RTOL), f"{tag} {what}: {ours:.3g} against {yard:.3g} of torch's fp32 dense autograd"
 
 
-GENERAL = [(24, 24, False), (8, 40, False), (64, 4, False), (6, 10, False), (6, 10, True)]
+# (1, 1): contiguous ld = 1, the 4-byte path; (4, 4): ld = 4, the 16-byte path; all four new ones: one lane per row
+GENERAL = [(24, 24, False), (8, 40, False), (64, 4, False), (6, 10, False), (6, 10, True),
+           (1, 1, False), (4, 4, False), (3, 2, False), (2, 4, True)]
+# scales that are no power of two (t and ds are rounded), one of them negative (the row maximum is the minimum of s)
+GENERAL_CASES = [(name, k, kv, o, SCALE) for k, kv, o in GENERAL for name in ("odd_last_chunk", "wave_pipe_thresholds", "keys48")]
+GENERAL_CASES += [(name, k, kv, False, scale) for scale in (0.3, -1.7) for k, kv in ((24, 24), (3, 2))
+                  for name in ("wave_pipe_thresholds", "keys48")]
 
 
-@pytest.mark.parametrize("k,kv,odd_ld", GENERAL, ids=[f"k{k}-kv{kv}{'-oddld' if o else ''}" for k, kv, o in GENERAL])
-@pytest.mark.parametrize("name", ["odd_last_chunk", "wave_pipe_thresholds", "keys48"])
-def test_fused_attention_general_against_dense_autograd(pkg, oracle, gpu, name, k, kv, odd_ld):
+@pytest.mark.parametrize("name,k,kv,odd_ld,SCALE", GENERAL_CASES,
+                         ids=[f"{n}-k{k}-kv{kv}{'-oddld' if o else ''}{'' if sc == SCALE else f'-scale{sc}'}"
+                              for n, k, kv, o, sc in GENERAL_CASES])
+def test_fused_attention_general_against_dense_autograd(pkg, oracle, gpu, name, k, kv, odd_ld, SCALE):
     import torch
+    SCALE_REF = float(np.float32(SCALE))                       # what the kernel receives
     s = _general_structure(name, pkg, oracle)
     h = Handles(pkg, s, gpu)
     if name == "wave_pipe_thresholds":
@@ -309,10 +354,27 @@ def test_fused_attention_general_against_dense_autograd(pkg, oracle, gpu, name, 
         Oc.backward(dO)
         other = {"O": Oc.detach(), "dQ": Qc.grad, "dK": Kc.grad, "dV": Vc.grad}
         att.close()
-    _check_general(f"{name} k={k} kv={kv}{' odd ld' if odd_ld else ''}", got, mask, SCALE, Q, K, V, dO, other)
+    _check_general(f"{name} k={k} kv={kv}{' odd ld' if odd_ld else ''} scale={SCALE}", got, mask, SCALE_REF, Q, K, V, dO, other)
     L = torch.from_numpy(np.diff(s.rp)).to(gpu)
     assert bool((got["O"][L == 0] == 0).all()) and bool((got["dQ"][L == 0] == 0).all())
     assert bool((got["stats"][L == 0, 0] == float("-inf")).all()) and bool((got["stats"][L == 0, 1] == 0).all())
+    h.close()
+
+
+@pytest.mark.parametrize("scale", [0.0, -0.0], ids=["plus0", "minus0"])
+def test_fused_attention_at_scale_zero(pkg, oracle, gpu, scale):
+    """A scale of +0 or -0 is finite, so it is accepted: every p is 1 / L, O is the row mean of V, dQ = dK = 0."""
+    import torch
+    k, kv = 8, 12
+    s = E.structure("wave_pipe_thresholds", pkg, oracle)
+    h = Handles(pkg, s, gpu)
+    assert "long_rows=5 " in h.A.spmm_describe()
+    Q, K, V, dO = _randn(gpu, 97, (s.rows, k), (s.cols, k), (s.cols, kv), (s.rows, kv))
+    got = _run(h, Q, K, V, dO, scale)
+    assert bool((got["dQ"] == 0).all()) and bool((got["dK"] == 0).all())
+    _check_general(f"scale={scale}", got, _mask(s, gpu), scale, Q, K, V, dO, whats=("O", "dV"))
+    L = torch.from_numpy(np.diff(s.rp)).to(gpu)
+    assert bool((got["stats"][L > 0, 0] == 0).all()) and bool((got["stats"][L == 0, 0] == float("-inf")).all())
     h.close()
 
 
@@ -390,10 +452,93 @@ def test_fused_attention_masked_keys_nan_rows_and_empty_rows(pkg, gpu):
     h2.close()
 
 
-# ---- invariance ------------------------------------------------------------------------------------------------------
-def test_fused_attention_rows_do_not_depend_on_their_placement(pkg, gpu):
+@pytest.mark.parametrize("k,kv", [(8, 12), (3, 4)], ids=["k8-kv12", "k3-kv4"])
+def test_fused_attention_special_values_in_long_rows(pkg, gpu, k, kv):
+    """The rows of _attention_rows.special_rows: masked stretches before and after the finite keys of rows in pieces, long
+    rows that are masked entirely or hold a NaN or a +Inf, and keys 0 (masked), 1200 and 1201 that some 700 queries list,
+    so the transposed handle runs them in pieces as well.  (3, 4) is one lane per row."""
     import torch
-    cols, k, kv = 900, 12, 20
+    kinds, lists = R.special_rows()
+    cols = R.KEYS
+    rp = np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.int32)
+    s = E.Structure(len(lists), cols, rp, np.concatenate(lists).astype(np.int32))
+    h = Handles(pkg, s, gpu)
+    n_long = int((np.diff(rp) > 512).sum())
+    assert n_long >= 20 and f"long_rows={n_long} " in h.A.spmm_describe()
+    per_key = np.bincount(s.ci, minlength=cols)
+    assert all(per_key[j] > 512 for j in (R.KEY_MASKED0, R.KEY_A, R.KEY_B))
+    assert f"long_rows={int((per_key > 512).sum())} " in h.T.spmm_describe() and "long_rows=0 " not in h.T.spmm_describe()
+    is_kind = lambda *names: torch.from_numpy(np.isin(kinds, names)).to(gpu)       # noqa: E731
+    is_masked = torch.from_numpy(R.is_masked_key(np.arange(cols))).to(gpu)
+    Q, K, V, dO = _randn(gpu, 101 + k, (s.rows, k), (cols, k), (cols, kv), (s.rows, kv))
+    Q[:, 0] = 1.0
+    Q[:, 1] = 1.0
+    K_ref = K.clone()
+    K_ref[is_masked, 0] = 0.0
+    K_ref[R.KEY_INF, 1] = 0.0
+    K[is_masked, 0] = float("-inf")
+    K[R.KEY_INF, 1] = float("inf")
+    Qr = Q.clone()
+    Q[is_kind(*R.Q_NAN_KINDS), 2] = float("nan")
+    got = _run(h, Q, K, V, dO, SCALE)
+    bad_rows, good = is_kind(*R.NAN_KINDS), ~is_kind(*R.NAN_KINDS)
+    for kind in R.NAN_KINDS:
+        assert bool(got["O"][is_kind(kind)].isnan().all()) and bool(got["dQ"][is_kind(kind)].isnan().all()), kind
+    # a row masked entirely, long or short: l = 0, so stats = (-Inf, 1.0f / 0 = +Inf)
+    assert bool((got["stats"][is_kind("all_masked"), 0] == float("-inf")).all())
+    assert bool((got["stats"][is_kind("all_masked"), 1] == float("inf")).all())
+    assert bool((got["O"][is_kind("empty")] == 0).all()) and bool((got["dQ"][is_kind("empty")] == 0).all())
+    # the keys a NaN row refers to carry its NaN; the others must not
+    touched_np = np.zeros(cols, bool)
+    touched_np[np.concatenate([lists[r] for r in np.flatnonzero(np.isin(kinds, R.NAN_KINDS))])] = True
+    assert touched_np[R.KEY_B] and touched_np[R.KEY_INF] and not touched_np[R.KEY_A] and not touched_np[R.KEY_MASKED0]
+    touched = torch.from_numpy(touched_np).to(gpu)
+    assert bool(got["dV"][touched].isnan().all()) and bool(got["dK"][touched].isnan().all())
+    assert not bool(got["dV"][~touched].isnan().any()) and not bool(got["dK"][~touched].isnan().any())
+    # a masked key contributes nothing, also through the pieces of the transposed handle and their sum (key 0)
+    assert bool((~touched & is_masked).sum() > 100)
+    assert bool((got["dV"][~touched & is_masked] == 0).all()) and bool((got["dK"][~touched & is_masked] == 0).all())
+    assert bool((got["dV"][R.KEY_MASKED0] == 0).all()) and bool((got["dK"][R.KEY_MASKED0] == 0).all())
+    # everything else: the dense autograd of the pattern without the masked entries (and without the NaN rows), finite K
+    keep = ~R.is_masked_key(s.ci) & ~np.isin(kinds, R.NAN_KINDS)[s.row_of]
+    mask = _mask(s, gpu, keep)
+    lists_masked = torch.from_numpy(np.array([bool(R.is_masked_key(l).any()) for l in lists])).to(gpu) & good
+    assert bool(lists_masked[is_kind(*R.BIT_KINDS, "straddle", "shared", "ordinary")].all())
+    dq0 = got["dQ"][:, 0].clone()
+    assert bool(dq0[lists_masked].isnan().all()), "0 * -Inf is NaN by IEEE"
+    fixed = dict(got)
+    fixed["dQ"] = got["dQ"].clone()
+    ref_dq = _dense_autograd(mask, SCALE, Qr, K_ref, V, dO, torch.float64)[1]
+    fixed["dQ"][:, 0] = torch.where(lists_masked, ref_dq[:, 0].float(), dq0)        # (that column is checked above)
+    assert bool(got["O"][good].isfinite().all()) and bool(fixed["dQ"][good].isfinite().all())
+    assert bool((~touched)[R.KEY_A])                                                 # key 1200: a long transposed row, compared
+    _check_general(f"special k={k} kv={kv}", fixed, mask, SCALE, Qr, K_ref, V, dO, rows=good, cols=~touched)
+    # masked stretches contribute exactly nothing: the same rows without their masked entries give the same bits
+    keep_all = ~R.is_masked_key(s.ci)
+    lengths2 = np.bincount(s.row_of[keep_all], minlength=s.rows)
+    s2 = E.Structure(s.rows, cols, np.concatenate([[0], np.cumsum(lengths2)]).astype(np.int32), s.ci[keep_all])
+    h2 = Handles(pkg, s2, gpu)
+    got2 = _run(h2, Q, K, V, dO, SCALE)
+    # (a leading stretch of 512 or 1024 masked entries is one or two whole pieces, (m, l, acc) = (-Inf, 0, 0) with w = 0, and
+    # the finite entries keep their piece boundaries; 512 finite entries are one piece with w = expf(0) = 1 or, alone, a row
+    # of one span; trailing masked entries in a piece add e = 0.  An ordinary row is one step of 8 either way.)
+    for kind in R.BIT_KINDS + ("ordinary",):
+        live = is_kind(kind)
+        assert bool(live.any())
+        assert torch.equal(_bits(got["O"][live]), _bits(got2["O"][live])), kind
+        assert torch.equal(_raw_bits(got["stats"][live]), _raw_bits(got2["stats"][live])), kind
+        assert torch.equal(_bits(got["dQ"][live][:, 1:]), _bits(got2["dQ"][live][:, 1:])), kind
+    h.close()
+    h2.close()
+
+
+# ---- invariance ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k,kv", [(12, 20), (3, 2)], ids=["k12-kv20", "k3-kv2"])
+def test_fused_attention_rows_do_not_depend_on_their_placement(pkg, gpu, k, kv):
+    """(3, 2) is one lane per row: there placement changes a lane's neighbours in its wavefront, and the contiguous operands
+    (ld = 3 and 2) already take the 4-byte path, so "strided operands" is its 16-byte run."""
+    import torch
+    cols = 900
     rng = np.random.Generator(np.random.PCG64(29))
     lengths = np.concatenate([[1, 2, 7, 8, 9, 16, 17, 63, 64, 65, 511, 512, 513, 700], rng.integers(1, 701, size=26)])
     assert len(lengths) == 40
@@ -419,7 +564,7 @@ def test_fused_attention_rows_do_not_depend_on_their_placement(pkg, gpu):
         Q[at], dO[at] = Qs, dOs
         ins, ld = (Q, K, V, dO), None
         if strided:
-            ld = (lambda w: w + 5) if odd else (lambda w: (w + 11) // 4 * 4)
+            ld = (lambda w: w + 5 if (w + 5) % 4 else w + 6) if odd else (lambda w: (w + 11) // 4 * 4)
             ins = tuple(_strided(t, ld(t.shape[1])) for t in ins)
             assert all((t.stride(0) % 4 != 0) == odd for t in ins)
         got = _run(h, *ins, SCALE, ld)
@@ -434,6 +579,57 @@ def test_fused_attention_rows_do_not_depend_on_their_placement(pkg, gpu):
                        ("the 4-byte load path", run(*placement(3, 5), strided=True, odd=True))):
         for w in ("O", "stats", "dQ"):
             assert torch.equal(_raw_bits(base[w]), _raw_bits(other[w])), f"{w} differs {tag}"
+
+
+# ---- extreme score profiles ------------------------------------------------------------------------------------------
+def _check_with_floor(tag, got, mask, scale, Q, K, V, dO, floor):
+    """_check_general's rule with an absolute floor: |error| <= max(4 x yard, RTOL) x magnitude + floor, the yardstick's error
+    taken beyond the same floor.  For rows whose probabilities underflow: their magnitudes go down to 1e-84, and the device's
+    fp64 softmax returns 0 for a probability below fp32's normal range (seen: exp(-88) = 6e-39 comes out as 0), where the
+    kernels keep a subnormal.  So at magnitude 0 the rule is the floor alone, not an exact zero."""
+    import torch
+    *r64, P = _dense_autograd(mask, scale, Q, K, V, dO, torch.float64)
+    r64 = dict(zip(("O", "dQ", "dK", "dV"), r64))
+    r32 = dict(zip(("O", "dQ", "dK", "dV"), _dense_autograd(mask, scale, Q, K, V, dO, torch.float32)))
+    mags = _normalised(mask, scale, Q, K, V, dO, P)
+    for what in ("O", "dQ", "dK", "dV"):
+        g, g64, g32, mag = got[what], r64[what], r32[what], mags[what]
+        assert bool(g.isfinite().all()), f"{tag} {what}: not finite"
+        live = mag > 0
+        assert bool(live.any())
+        assert bool((g[~live].abs() <= floor).all()), f"{tag} {what}: a value beyond the floor where nothing contributes"
+        beyond = lambda x: ((x.double() - g64).abs()[live] - floor).clamp(min=0) / mag[live]      # noqa: E731
+        ours, yard = float(beyond(g).max()), float(beyond(g32).max())
+        print(f"{tag} {what}: normalised error beyond 2^-90 fused {ours:.3g}, torch fp32 dense autograd {yard:.3g}")
+        assert ours <= max(4.0 * yard, RTOL), f"{tag} {what}: {ours:.3g} against {yard:.3g} of torch's fp32 dense autograd"
+
+
+@pytest.mark.parametrize("k,kv", [(2, 1), (2, 40)], ids=["k2-kv1", "k2-kv40"])
+def test_fused_attention_extreme_score_profiles(pkg, gpu, k, kv):
+    """The rows of _attention_rows.extreme_rows, every score exact: maxima that rise at every step (a = expf(m - z) down to
+    0, where (l, acc) restart) or fall, a spike of 200 as the last entry (at 513 the single nonzero of the last piece) or
+    the first, 0 and -200 in turn, scores near 256.  (2, 1): one lane, steps of 8; (2, 40): 16 lanes, steps of 16."""
+    import torch
+    rows, cols = R.extreme_rows()
+    lengths = [n for _, n, _, _ in rows]
+    rp = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+    s = E.Structure(len(rows), cols, rp, np.arange(cols, dtype=np.int32))         # row r owns the keys [rp[r], rp[r + 1])
+    assert [first for _, _, first, _ in rows] == rp[:-1].tolist()
+    h = Handles(pkg, s, gpu)
+    assert f"long_rows={sum(n > 512 for n in lengths)} " in h.A.spmm_describe() and "long_rows=0 " in h.T.spmm_describe()
+    Q, K, V, dO = _randn(gpu, 103 + kv, (s.rows, k), (cols, k), (cols, kv), (s.rows, kv))
+    Q[:, 0], Q[:, 1] = 1.0, 0.0
+    t = torch.from_numpy(np.concatenate([t for _, _, _, t in rows])).to(gpu)
+    K[:, 0] = (t / R.EXTREME_SCALE).float()
+    assert torch.equal(K[:, 0].double() * R.EXTREME_SCALE, t)
+    got = _run(h, Q, K, V, dO, R.EXTREME_SCALE)
+    S = torch.empty(s.nnz, dtype=torch.float32, device=gpu)
+    h.A.sddmm(Q, K, S)
+    assert torch.equal(S.double() * R.EXTREME_SCALE, t), "the scores are not exact"
+    want_max = torch.tensor([float(t.max()) for _, _, _, t in rows], dtype=torch.float32, device=gpu)
+    assert torch.equal(got["stats"][:, 0], want_max)
+    _check_with_floor(f"extreme k={k} kv={kv}", got, _mask(s, gpu), R.EXTREME_SCALE, Q, K, V, dO, R.ABS_FLOOR)
+    h.close()
 
 
 # ---- heads -----------------------------------------------------------------------------------------------------------
