@@ -258,8 +258,12 @@ SPMV_API int64_t spmv_csr_transpose_map_bytes(const spmv_csr_t *t);
  *   spmv_csr_row_softmax_backward             the same as spmv_csr_row_softmax
  *   spmv_csr_attention_forward, _backward_q,  the same as spmv_csr_spmm with max(k, kv) in the place of k (rows x lanes per
  *   _backward_kv                              row < 2^32; on the transposed handle its rows); any nnz < 2^31
+ *   spmv_csr_attention_forward_heads,         the single-head limits with rows x lanes per row x heads < 2^32 (every head of a
+ *   _backward_q_heads, _backward_kv_heads     call is one launch) and heads <= 65535; where the long rows have more pieces
+ *                                             than the handle has rows, the pieces stand in the place of the rows
  *   spmv_csr_transpose                        any handle
- * (tests/test_gpu_limits.py runs every path on either side of these.) */
+ * (tests/test_gpu_limits.py runs every path on either side of these; the _heads calls' limits are refused and queried on
+ * either side in tests/test_gpu_attention_heads.py, where a launch at the limit itself would write 64 GiB.) */
 SPMV_API int spmv_csr_plan(spmv_csr_t *h, int variant, void *stream);
 SPMV_API int spmv_csr_run(spmv_csr_t *h, int variant, const float *d_x, float *d_y, void *stream);
 
@@ -483,6 +487,56 @@ SPMV_API int spmv_csr_attention_backward_kv(spmv_csr_t *t, float scale, int k, c
                                             const float *d_K, int64_t ldk, int kv, const float *d_V, int64_t ldv,
                                             const float *d_dO, int64_t lddo, const float *d_stats, const float *d_delta,
                                             float *d_dK, int64_t lddk, float *d_dV, int64_t lddv, void *stream);
+
+/* ---- Fused attention, all heads of one pattern in one launch ----------------------------------------------------------
+ * The three passes above for `heads` heads at once: one grid per kernel with the head in its y dimension, instead of one
+ * call (one to four launches) per head.  Every pointer argument is head 0's; spmv_attn_heads_t says how many floats lie
+ * between head y and head y + 1 of each operand.
+ * Semantics: head y of a _heads call is, bit for bit, the single-head call with every pointer advanced by y times its
+ * stride.  Nothing of the order of the sums above changes; the kernels are the same ones (a single-head call is heads = 1
+ * with every stride 0).  Each call reads only the strides of the operands it takes: forward q, k, v, o, stats;
+ * backward_q q, k, v, o, d_o, stats, delta, dq; backward_kv q, k, v, d_o, stats, delta, dk, dv.
+ * The plan: spmv_csr_attention_plan_heads makes the attention plan if it is missing and sizes the scratch of the long rows
+ * for `heads` heads: heads x pieces x 132 floats, head y using the slice at y x pieces x 132.  It only grows, and is
+ * idempotent when the plan already covers `heads`; like the other plan calls it allocates and waits for the stream.
+ * spmv_csr_attention_plan remains and means heads = 1.  spmv_csr_attention_plan_bytes reports the grown scratch
+ * ((heads - 1) x pieces x 132 x 4 bytes more; nothing more for a handle without a long row).  A _heads call with more heads
+ * than planned is SPMV_ERR_NOT_PLANNED, also on a handle without a long row (one rule).  After the plan the three calls
+ * allocate nothing and never wait: graph-capturable.  h and t each need theirs.
+ * Refusals (SPMV_ERR_INVALID, a message that names the function, nothing launched, every output untouched): a null hs,
+ * heads < 1, reserved != 0, heads > 65535 or rows x lanes per row x heads >= 2^32 ("Limits of the layouts";
+ * spmv_csr_attention_max_heads says how many heads fit); a negative
+ * stride; a stride of a matrix operand that is no multiple of 4 (every head stays 16-byte aligned), a stats stride that is
+ * odd (delta: any); with heads > 1 an output stride below the output's width (o: kv, dq and dk: k, dv: kv, stats: 2,
+ * delta: 1); and everything the single-head call refuses.
+ * Shared inputs: an input stride may be 0, so one K and V serve all heads (multi-query attention) without a copy; dK and
+ * dV then still come out per head, and the caller sums them.
+ * Not checked: overlap between the outputs of different heads beyond the width rule (a stride below rows x ld of a stacked
+ * output, say) is the caller's error, as "outputs must not overlap inputs" is.  Column blocks of one wide matrix
+ * (stride = k, ld = heads x k) are a legal layout: the heads' rows interleave without overlapping. */
+typedef struct spmv_attn_heads {
+    int32_t heads, reserved;                            /* reserved = 0 */
+    int64_t q, k, v, o, d_o, stats, delta, dq, dk, dv;  /* floats from head h to head h+1 */
+} spmv_attn_heads_t;
+
+SPMV_API int spmv_csr_attention_plan_heads(spmv_csr_t *h, int heads, void *stream);
+/* The most heads one _heads call on h takes at these widths (the launch limits above, from h's rows and the pieces of its
+ * long rows; 0: not even one; needs the plan, else SPMV_ERR_NOT_PLANNED; a negative status otherwise).  A caller with more
+ * heads splits them into several calls; h and t may differ. */
+SPMV_API int spmv_csr_attention_max_heads(const spmv_csr_t *h, int k, int kv);
+SPMV_API int spmv_csr_attention_forward_heads(spmv_csr_t *h, const spmv_attn_heads_t *hs, float scale, int k, const float *d_Q,
+                                              int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V,
+                                              int64_t ldv, float *d_O, int64_t ldo, float *d_stats, void *stream);
+SPMV_API int spmv_csr_attention_backward_q_heads(spmv_csr_t *h, const spmv_attn_heads_t *hs, float scale, int k,
+                                                 const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, int kv,
+                                                 const float *d_V, int64_t ldv, const float *d_O, int64_t ldo,
+                                                 const float *d_dO, int64_t lddo, const float *d_stats, float *d_delta,
+                                                 float *d_dQ, int64_t lddq, void *stream);
+SPMV_API int spmv_csr_attention_backward_kv_heads(spmv_csr_t *t, const spmv_attn_heads_t *hs, float scale, int k,
+                                                  const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, int kv,
+                                                  const float *d_V, int64_t ldv, const float *d_dO, int64_t lddo,
+                                                  const float *d_stats, const float *d_delta, float *d_dK, int64_t lddk,
+                                                  float *d_dV, int64_t lddv, void *stream);
 
 /* ---- dense baselines (reference slots cublas / naive / tiling) ---------
  * y[i] = sum_j x[j] * A[j*N+i] on the dense device matrix.

@@ -31,6 +31,15 @@ OK, ERR_NO_DEVICE, ERR_INVALID, ERR_HIP, ERR_VARIANT, ERR_NOT_PLANNED, ERR_STALE
 _i32p, _f32p, _vp = C.c_void_p, C.c_void_p, C.c_void_p   # raw addresses (host or device)
 _H = C.c_void_p                                           # spmv_csr_t*
 _HP = C.POINTER(C.c_void_p)
+
+
+class AttnHeads(C.Structure):
+    """spmv_attn_heads_t: the heads of one _heads call and, per operand, the floats from head h to head h + 1."""
+    _fields_ = [("heads", C.c_int32), ("reserved", C.c_int32)] + [(n, C.c_int64) for n in (
+        "q", "k", "v", "o", "d_o", "stats", "delta", "dq", "dk", "dv")]
+
+
+_HS = C.POINTER(AttnHeads)
 SIGNATURES = {
     "spmv_device_count": (C.c_int, []),
     "spmv_last_error": (C.c_char_p, []),
@@ -68,6 +77,16 @@ SIGNATURES = {
     "spmv_csr_attention_backward_kv": (C.c_int, [_H, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, C.c_int, _f32p,
                                                  C.c_int64, _f32p, C.c_int64, _f32p, _f32p, _f32p, C.c_int64, _f32p, C.c_int64,
                                                  _vp]),
+    "spmv_csr_attention_plan_heads": (C.c_int, [_H, C.c_int, _vp]),
+    "spmv_csr_attention_max_heads": (C.c_int, [_H, C.c_int, C.c_int]),
+    "spmv_csr_attention_forward_heads": (C.c_int, [_H, _HS, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, C.c_int,
+                                                   _f32p, C.c_int64, _f32p, C.c_int64, _f32p, _vp]),
+    "spmv_csr_attention_backward_q_heads": (C.c_int, [_H, _HS, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, C.c_int,
+                                                      _f32p, C.c_int64, _f32p, C.c_int64, _f32p, C.c_int64, _f32p, _f32p, _f32p,
+                                                      C.c_int64, _vp]),
+    "spmv_csr_attention_backward_kv_heads": (C.c_int, [_H, _HS, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, C.c_int,
+                                                       _f32p, C.c_int64, _f32p, C.c_int64, _f32p, _f32p, _f32p, C.c_int64, _f32p,
+                                                       C.c_int64, _vp]),
     "spmv_csr_plan_get": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int32)]),
     "spmv_csr_plan_set": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int32), _vp]),
     "spmv_csr_plan_like": (C.c_int, [_H, _H, C.c_int, _vp]),
@@ -392,6 +411,85 @@ class CsrMatrix:
         check(lib().spmv_csr_attention_backward_kv(self._h, scale, k, _ptr(Q), Q.stride(0), _ptr(K), K.stride(0), kv, _ptr(V),
                                                    V.stride(0), _ptr(dO), dO.stride(0), _ptr(stats), _ptr(delta), _ptr(dK),
                                                    dK.stride(0), _ptr(dV), dV.stride(0), _stream_handle(stream)))
+
+    # -- fused attention, the heads of one pattern in one launch (spmv_csr_attention_*_heads) -----------------------------
+    def attention_plan_heads(self, heads: int, stream=None) -> None:
+        """The attention plan with the long rows' scratch sized for ``heads`` heads (it only grows; waits for the stream)."""
+        check(lib().spmv_csr_attention_plan_heads(self._h, heads, _stream_handle(stream)))
+
+    def attention_max_heads(self, k: int, kv: int) -> int:
+        """The most heads one _heads call on this handle takes at these widths (the library's launch limits)."""
+        n = lib().spmv_csr_attention_max_heads(self._h, k, kv)
+        if n < 0:
+            check(n)
+        return n
+
+    @staticmethod
+    def _head_strides(heads: int, **tensors) -> dict:
+        """stride(0) of every tensor; 0 with one head, where torch's stride of a dimension of size 1 means nothing."""
+        return {n: (t.stride(0) if heads > 1 else 0) for n, t in tensors.items()}
+
+    @staticmethod
+    def _attention_heads(what: str, scale: float, mats: dict, vecs: dict):
+        """Every matrix as (tensor, rows, width or None): (heads, rows, width) float32 with stride(2) == 1, its ld stride(1)
+        and its head stride stride(0); stats (heads, rows, 2) with strides (., 2, 1), delta (heads, rows) with stride(1) == 1.
+        Returns the number of heads."""
+        import math
+        import torch
+        if not math.isfinite(scale):
+            raise ValueError(f"{what}: scale = {scale} is not finite")
+        heads = None
+        for name, (t, n, w) in mats.items():
+            if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.dtype != torch.float32 or t.stride(2) != 1:
+                raise ValueError(f"{what}: {name} must be a (heads, rows, width) float32 tensor with stride(2) == 1")
+            heads = t.shape[0] if heads is None else heads
+            if t.shape[0] != heads or t.shape[1] != n or (w is not None and t.shape[2] != w):
+                raise ValueError(f"{what}: {name} is {tuple(t.shape)}, expected ({heads}, {n}, {w if w is not None else 'width'})")
+        for name, (t, n, inner) in vecs.items():
+            shape = (heads, n) + ((inner,) if inner > 1 else ())
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape \
+                    or not t[0].is_contiguous():
+                raise ValueError(f"{what}: {name} must be a float32 tensor of shape {shape} whose heads are contiguous")
+        return heads
+
+    def attention_forward_heads(self, Q, K, V, O, stats, scale: float = 1.0, stream=None) -> None:
+        """attention_forward for all heads in one launch per kernel.  Q: (heads, rows, k), K: (heads, cols, k), V: (heads,
+        cols, kv), O: (heads, rows, kv), stats: (heads, rows, 2); an input may have stride(0) == 0 (shared by the heads)."""
+        what = "attention_forward_heads"
+        k, kv = (t.shape[2] if getattr(t, "ndim", 0) == 3 else None for t in (Q, V))
+        heads = self._attention_heads(what, scale, dict(Q=(Q, self.rows, k), K=(K, self.cols, k), V=(V, self.cols, kv),
+                                                        O=(O, self.rows, kv)), dict(stats=(stats, self.rows, 2)))
+        hs = AttnHeads(heads=heads, **self._head_strides(heads, q=Q, k=K, v=V, o=O, stats=stats))
+        check(lib().spmv_csr_attention_forward_heads(self._h, C.byref(hs), scale, k, _ptr(Q), Q.stride(1), _ptr(K), K.stride(1),
+                                                     kv, _ptr(V), V.stride(1), _ptr(O), O.stride(1), _ptr(stats),
+                                                     _stream_handle(stream)))
+
+    def attention_backward_q_heads(self, Q, K, V, O, dO, stats, delta, dQ, scale: float = 1.0, stream=None) -> None:
+        """attention_backward_q for all heads in one launch per kernel; delta: (heads, rows), dQ: (heads, rows, k)."""
+        what = "attention_backward_q_heads"
+        k, kv = (t.shape[2] if getattr(t, "ndim", 0) == 3 else None for t in (Q, V))
+        heads = self._attention_heads(what, scale, dict(Q=(Q, self.rows, k), K=(K, self.cols, k), V=(V, self.cols, kv),
+                                                        O=(O, self.rows, kv), dO=(dO, self.rows, kv), dQ=(dQ, self.rows, k)),
+                                      dict(stats=(stats, self.rows, 2), delta=(delta, self.rows, 1)))
+        hs = AttnHeads(heads=heads, **self._head_strides(heads, q=Q, k=K, v=V, o=O, d_o=dO, stats=stats, delta=delta, dq=dQ))
+        check(lib().spmv_csr_attention_backward_q_heads(self._h, C.byref(hs), scale, k, _ptr(Q), Q.stride(1), _ptr(K), K.stride(1),
+                                                        kv, _ptr(V), V.stride(1), _ptr(O), O.stride(1), _ptr(dO), dO.stride(1),
+                                                        _ptr(stats), _ptr(delta), _ptr(dQ), dQ.stride(1),
+                                                        _stream_handle(stream)))
+
+    def attention_backward_kv_heads(self, Q, K, V, dO, stats, delta, dK, dV, scale: float = 1.0, stream=None) -> None:
+        """On the handle of the TRANSPOSED pattern: attention_backward_kv for all heads in one launch per kernel.  With a
+        shared K or V (stride(0) == 0) dK and dV still come out per head."""
+        what = "attention_backward_kv_heads"
+        k, kv = (t.shape[2] if getattr(t, "ndim", 0) == 3 else None for t in (Q, V))
+        heads = self._attention_heads(what, scale, dict(Q=(Q, self.cols, k), K=(K, self.rows, k), V=(V, self.rows, kv),
+                                                        dO=(dO, self.cols, kv), dK=(dK, self.rows, k), dV=(dV, self.rows, kv)),
+                                      dict(stats=(stats, self.cols, 2), delta=(delta, self.cols, 1)))
+        hs = AttnHeads(heads=heads, **self._head_strides(heads, q=Q, k=K, v=V, d_o=dO, stats=stats, delta=delta, dk=dK, dv=dV))
+        check(lib().spmv_csr_attention_backward_kv_heads(self._h, C.byref(hs), scale, k, _ptr(Q), Q.stride(1), _ptr(K),
+                                                         K.stride(1), kv, _ptr(V), V.stride(1), _ptr(dO), dO.stride(1),
+                                                         _ptr(stats), _ptr(delta), _ptr(dK), dK.stride(1), _ptr(dV),
+                                                         dV.stride(1), _stream_handle(stream)))
 
     def values_changed(self) -> None:
         """The caller rewrote vals (borrowed arrays): plans that hold a copy of them are stale from here on."""

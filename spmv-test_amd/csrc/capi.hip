@@ -661,7 +661,7 @@ struct AttnOperand {
 // what the three attention calls check alike: k, kv, the scale, every matrix (ld, presence, 16-byte alignment, 64-bit
 // byte offsets), the vectors stats (8-byte aligned) and delta (4-byte), the device and the plan
 static int attention_args(const spmv_csr_t *h, float scale, int k, int kv, const AttnOperand *ops, int n_ops, const void *stats,
-                          const void *delta, bool with_delta, int64_t n_queries, const char *what)
+                          const void *delta, bool with_delta, int64_t n_queries, const char *what, int heads = 1)
 {
     if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
     if (k < 1 || k > 64 || kv < 1 || kv > 64) {
@@ -686,6 +686,10 @@ static int attention_args(const spmv_csr_t *h, float scale, int k, int kv, const
     }
     if (int rc = require_current(h->device, what)) return rc;
     if (!h->plan_attn.ready || !h->plan_spmm.ready) { set_error("%s used before spmv_csr_attention_plan", what); return SPMV_ERR_NOT_PLANNED; }
+    if (heads > h->plan_attn.heads) {
+        set_error("%s: %d heads, the plan covers %d (spmv_csr_attention_plan_heads)", what, heads, h->plan_attn.heads);
+        return SPMV_ERR_NOT_PLANNED;
+    }
     return SPMV_OK;
 }
 
@@ -726,6 +730,124 @@ int spmv_csr_attention_backward_kv(spmv_csr_t *t, float scale, int k, const floa
     if (int rc = attention_args(t, scale, k, kv, ops, 6, d_stats, d_delta, true, queries, what)) return rc;
     return launch_attention_backward_kv(*t, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_dO, lddo, d_stats, d_delta, d_dK,
                                         lddk, d_dV, lddv, (hipStream_t)stream);
+}
+
+// ---- fused attention, the heads of one pattern in one launch ------------------------------------------------------------
+int spmv_csr_attention_plan_heads(spmv_csr_t *h, int heads, void *stream)
+{
+    const char *what = "spmv_csr_attention_plan_heads";
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (heads < 1 || heads > kMaxHeads) { set_error("%s: heads = %d (need 1 <= heads <= %d)", what, heads, kMaxHeads); return SPMV_ERR_INVALID; }
+    if (int rc = require_current(h->device, what)) return rc;
+    return plan_attention_heads(*h, heads, (hipStream_t)stream);
+}
+
+int spmv_csr_attention_max_heads(const spmv_csr_t *h, int k, int kv)
+{
+    const char *what = "spmv_csr_attention_max_heads";
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (k < 1 || k > 64 || kv < 1 || kv > 64) {
+        set_error("%s: k = %d, kv = %d (need 1 <= k <= 64 and 1 <= kv <= 64)", what, k, kv);
+        return SPMV_ERR_INVALID;
+    }
+    if (!h->plan_spmm.ready) { set_error("%s used before spmv_csr_attention_plan", what); return SPMV_ERR_NOT_PLANNED; }
+    return attention_max_heads(*h, k > kv ? k : kv);
+}
+
+namespace {
+struct HeadStride {
+    const char *name;
+    int64_t stride;
+    int unit;        // the stride is a multiple of it: 4 for a matrix (16-byte aligned heads), 2 for stats, 1 for delta
+    int out_width;   // of an output: floats a head writes per row (its stride is at least that with heads > 1); 0: an input
+};
+}  // namespace
+
+static int attention_heads_header(const spmv_attn_heads_t *hs, const char *what)
+{
+    if (!hs) { set_error("%s: null hs", what); return SPMV_ERR_INVALID; }
+    if (hs->heads < 1 || hs->heads > kMaxHeads) {
+        set_error("%s: heads = %d (need 1 <= heads <= %d, the launch limit)", what, hs->heads, kMaxHeads);
+        return SPMV_ERR_INVALID;
+    }
+    if (hs->reserved != 0) { set_error("%s: reserved = %d (must be 0)", what, hs->reserved); return SPMV_ERR_INVALID; }
+    return SPMV_OK;
+}
+
+static int attention_heads_strides(int heads, const HeadStride *st, int n, const char *what)
+{
+    for (int i = 0; i < n; ++i) {
+        const HeadStride &o = st[i];
+        if (o.stride < 0) { set_error("%s: head stride of %s = %lld is negative", what, o.name, (long long)o.stride); return SPMV_ERR_INVALID; }
+        if (o.stride % o.unit != 0) {
+            set_error("%s: head stride of %s = %lld is no multiple of %d", what, o.name, (long long)o.stride, o.unit);
+            return SPMV_ERR_INVALID;
+        }
+        if (heads > 1 && o.stride < o.out_width) {
+            set_error("%s: head stride of the output %s = %lld is below its width %d", what, o.name, (long long)o.stride, o.out_width);
+            return SPMV_ERR_INVALID;
+        }
+        if (o.stride > INT64_MAX / 4 / heads) {
+            set_error("%s: head stride of %s = %lld overflows 64-bit byte offsets", what, o.name, (long long)o.stride);
+            return SPMV_ERR_INVALID;
+        }
+    }
+    return SPMV_OK;
+}
+
+int spmv_csr_attention_forward_heads(spmv_csr_t *h, const spmv_attn_heads_t *hs, float scale, int k, const float *d_Q,
+                                     int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V, int64_t ldv,
+                                     float *d_O, int64_t ldo, float *d_stats, void *stream)
+{
+    const char *what = "spmv_csr_attention_forward_heads";
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (int rc = attention_heads_header(hs, what)) return rc;
+    const HeadStride st[] = {{"Q", hs->q, 4, 0}, {"K", hs->k, 4, 0}, {"V", hs->v, 4, 0}, {"O", hs->o, 4, kv}, {"stats", hs->stats, 2, 2}};
+    if (int rc = attention_heads_strides(hs->heads, st, 5, what)) return rc;
+    const int64_t rows = h->rows, cols = h->cols;
+    const AttnOperand ops[] = {{"Q", d_Q, ldq, rows, k}, {"K", d_K, ldk, cols, k}, {"V", d_V, ldv, cols, kv}, {"O", d_O, ldo, rows, kv}};
+    if (int rc = attention_args(h, scale, k, kv, ops, 4, d_stats, nullptr, false, rows, what, hs->heads)) return rc;
+    return launch_attention_forward_heads(*h, *hs, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_O, ldo, d_stats, what,
+                                          (hipStream_t)stream);
+}
+
+int spmv_csr_attention_backward_q_heads(spmv_csr_t *h, const spmv_attn_heads_t *hs, float scale, int k, const float *d_Q,
+                                        int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V, int64_t ldv,
+                                        const float *d_O, int64_t ldo, const float *d_dO, int64_t lddo, const float *d_stats,
+                                        float *d_delta, float *d_dQ, int64_t lddq, void *stream)
+{
+    const char *what = "spmv_csr_attention_backward_q_heads";
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (int rc = attention_heads_header(hs, what)) return rc;
+    const HeadStride st[] = {{"Q", hs->q, 4, 0}, {"K", hs->k, 4, 0}, {"V", hs->v, 4, 0}, {"O", hs->o, 4, 0}, {"dO", hs->d_o, 4, 0},
+                             {"stats", hs->stats, 2, 0}, {"delta", hs->delta, 1, 1}, {"dQ", hs->dq, 4, k}};
+    if (int rc = attention_heads_strides(hs->heads, st, 8, what)) return rc;
+    const int64_t rows = h->rows, cols = h->cols;
+    const AttnOperand ops[] = {{"Q", d_Q, ldq, rows, k}, {"K", d_K, ldk, cols, k}, {"V", d_V, ldv, cols, kv}, {"O", d_O, ldo, rows, kv},
+                               {"dO", d_dO, lddo, rows, kv}, {"dQ", d_dQ, lddq, rows, k}};
+    if (int rc = attention_args(h, scale, k, kv, ops, 6, d_stats, d_delta, true, rows, what, hs->heads)) return rc;
+    return launch_attention_backward_q_heads(*h, *hs, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_O, ldo, d_dO, lddo, d_stats,
+                                             d_delta, d_dQ, lddq, what, (hipStream_t)stream);
+}
+
+// t is the handle of the TRANSPOSED pattern: t->rows keys, t->cols queries
+int spmv_csr_attention_backward_kv_heads(spmv_csr_t *t, const spmv_attn_heads_t *hs, float scale, int k, const float *d_Q,
+                                         int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V, int64_t ldv,
+                                         const float *d_dO, int64_t lddo, const float *d_stats, const float *d_delta,
+                                         float *d_dK, int64_t lddk, float *d_dV, int64_t lddv, void *stream)
+{
+    const char *what = "spmv_csr_attention_backward_kv_heads";
+    if (!t) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (int rc = attention_heads_header(hs, what)) return rc;
+    const HeadStride st[] = {{"Q", hs->q, 4, 0}, {"K", hs->k, 4, 0}, {"V", hs->v, 4, 0}, {"dO", hs->d_o, 4, 0}, {"stats", hs->stats, 2, 0},
+                             {"delta", hs->delta, 1, 0}, {"dK", hs->dk, 4, k}, {"dV", hs->dv, 4, kv}};
+    if (int rc = attention_heads_strides(hs->heads, st, 8, what)) return rc;
+    const int64_t keys = t->rows, queries = t->cols;
+    const AttnOperand ops[] = {{"Q", d_Q, ldq, queries, k}, {"K", d_K, ldk, keys, k}, {"V", d_V, ldv, keys, kv},
+                               {"dO", d_dO, lddo, queries, kv}, {"dK", d_dK, lddk, keys, k}, {"dV", d_dV, lddv, keys, kv}};
+    if (int rc = attention_args(t, scale, k, kv, ops, 6, d_stats, d_delta, true, queries, what, hs->heads)) return rc;
+    return launch_attention_backward_kv_heads(*t, *hs, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_dO, lddo, d_stats, d_delta,
+                                              d_dK, lddk, d_dV, lddv, what, (hipStream_t)stream);
 }
 
 int spmv_csr_values_changed(spmv_csr_t *h)

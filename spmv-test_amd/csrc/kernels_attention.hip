@@ -28,7 +28,11 @@
 // the 16-byte or 4-byte load path, of the row's place or neighbours, of a rebased row_ptr or of the handle.  (T depends on
 // V, hence on max(k, kv) only.)
 //
-// The scratch of the long rows (AttnPlan): kAtSlots floats per piece: [0] m_p, [1] l_p, [4, 132) up to 128 partial sums
+// Heads.  Every kernel serves blockIdx.y = the head of one launch: it advances its operand bases by head x stride once at
+// entry (at_head; wave-uniform) and uses the slice of the scratch at head x pieces x kAtSlots.  A call of one head is the
+// same kernel at a grid of y = 1 with every stride 0, so head y of a call is that call on the advanced pointers bit for bit.
+//
+// The scratch of the long rows (AttnPlan): per head, kAtSlots floats per piece: [0] m_p, [1] l_p, [4, 132) up to 128 partial sums
 // (forward acc_p[kv]; backward_q dQ_p[k]; backward_kv dK_p[k] at 4 and dV_p[kv] at 68).
 #include <initializer_list>
 #include "lane_group.hpp"
@@ -58,7 +62,40 @@ struct AttnArgs {
     float *out1;      int64_t ld1;     // backward_kv dV
     float *stats;                      // forward
     float *delta;                      // backward_q
+    // floats from head y to head y + 1 of every operand above (blockIdx.y is the head; all 0 in a call of one head)
+    int64_t hq, hk, hv, ho, hdo, hstats_in, hdelta_in, h0, h1, hstats, hdelta;
 };
+
+// the operands of the block's head: every base advanced once, by a wave-uniform number (scalar work)
+__device__ __forceinline__ AttnArgs at_head(AttnArgs a)
+{
+    const int64_t y = blockIdx.y;
+    a.Q += y * a.hq, a.K += y * a.hk, a.V += y * a.hv, a.O += y * a.ho, a.dO += y * a.hdo;
+    a.stats_in += y * a.hstats_in, a.delta_in += y * a.hdelta_in;
+    a.out0 += y * a.h0, a.out1 += y * a.h1, a.stats += y * a.hstats, a.delta += y * a.hdelta;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // each base is formed here, not where it is first used: its stride and the head then stop occupying scalar registers
+    // (an empty statement per pointer, so that one a pass does not use still disappears)
+    asm("" : "+s"(a.Q));
+    asm("" : "+s"(a.K));
+    asm("" : "+s"(a.V));
+    asm("" : "+s"(a.O));
+    asm("" : "+s"(a.dO));
+    asm("" : "+s"(a.stats_in));
+    asm("" : "+s"(a.delta_in));
+    asm("" : "+s"(a.out0));
+    asm("" : "+s"(a.out1));
+    asm("" : "+s"(a.stats));
+    asm("" : "+s"(a.delta));
+#endif
+    return a;
+}
+
+// the scratch of the block's head: head y owns the slice at y * pieces * kAtSlots
+__device__ __forceinline__ float *at_head_scratch(const GroupPieces &g)
+{
+    return g.scratch + (int64_t)blockIdx.y * g.npieces * kAtSlots;
+}
 
 // ---- forward: (m, l, acc) of the nonzeros [b, e) of the group's row.  All lanes of a group call it with the same b, e. ----
 template <int V, bool VEC>
@@ -123,8 +160,9 @@ __device__ __forceinline__ void store_stats(float *stats, int64_t r, float m, fl
 }
 
 template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_attn_fwd_rows(GroupRows g, AttnArgs a)
+__global__ __launch_bounds__(kBlock) void k_attn_fwd_rows(GroupRows g, AttnArgs a0)
 {
+    const AttnArgs a = at_head(a0);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     const int64_t r = group_row<V>(g);
     if (r < 0) return;
@@ -145,8 +183,9 @@ __global__ __launch_bounds__(kBlock) void k_attn_fwd_rows(GroupRows g, AttnArgs 
 }
 
 template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_attn_fwd_pieces(GroupPieces g, AttnArgs a)
+__global__ __launch_bounds__(kBlock) void k_attn_fwd_pieces(GroupPieces g, AttnArgs a0)
 {
+    const AttnArgs a = at_head(a0);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     int lo;
     const int64_t p = group_piece<V>(g, lo);
@@ -157,27 +196,29 @@ __global__ __launch_bounds__(kBlock) void k_attn_fwd_pieces(GroupPieces g, AttnA
     float m, l;
     float4 acc;
     fwd_span<V, VEC>(lane, b, e, a, q, g.col_idx, c0, m, l, acc);
-    float *s = g.scratch + p * kAtSlots;
+    float *s = at_head_scratch(g) + p * kAtSlots;
     if (sub == 0) *reinterpret_cast<float2 *>(s) = make_float2(m, l);
     if (c0 < a.kv) *reinterpret_cast<float4 *>(s + kAtSums + c0) = acc;
 }
 
 // a group per long row: the pieces' (m_p, l_p, acc_p) folded in piece order
 template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_attn_fwd_combine(GroupPieces g, AttnArgs a)
+__global__ __launch_bounds__(kBlock) void k_attn_fwd_combine(GroupPieces g, AttnArgs a0)
 {
+    const AttnArgs a = at_head(a0);
     const int sub = threadIdx.x & (V - 1), c0 = 4 * sub;
     const int64_t i = (int64_t)blockIdx.x * (kBlock / V) + threadIdx.x / V;
     if (i >= g.n_long) return;
     const int64_t r = g.long_row[i];
     const int f = g.long_first[i], n = g.long_first[i + 1];
+    const float *scratch = at_head_scratch(g);
     float M = -INFINITY;
-    for (int p = f; p < n; ++p) M = fmaxf(M, g.scratch[(int64_t)p * kAtSlots]);
+    for (int p = f; p < n; ++p) M = fmaxf(M, scratch[(int64_t)p * kAtSlots]);
     const float z = M == -INFINITY ? 0.0f : M;
     float l = 0.0f;
     float4 acc = zero4();
     for (int p = f; p < n; ++p) {
-        const float *s = g.scratch + (int64_t)p * kAtSlots;
+        const float *s = scratch + (int64_t)p * kAtSlots;
         const float w = expf(s[0] - z);
         l = fmaf(s[1], w, l);
         if (c0 < a.kv) {
@@ -253,8 +294,9 @@ __device__ __forceinline__ float at_delta(const AttnArgs &a, int64_t r, int c0, 
 }
 
 template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_attn_bwd_q_rows(GroupRows g, AttnArgs a)
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_q_rows(GroupRows g, AttnArgs a0)
 {
+    const AttnArgs a = at_head(a0);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     const int64_t r = group_row<V>(g);
     if (r < 0) return;
@@ -275,8 +317,9 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_q_rows(GroupRows g, AttnArg
 }
 
 template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_attn_bwd_q_pieces(GroupPieces g, AttnArgs a)
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_q_pieces(GroupPieces g, AttnArgs a0)
 {
+    const AttnArgs a = at_head(a0);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     int lo;
     const int64_t p = group_piece<V>(g, lo);
@@ -288,20 +331,24 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_q_pieces(GroupPieces g, Att
     const float4 q = c0 < a.k ? load_slice<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
     const float2 st = *reinterpret_cast<const float2 *>(a.stats_in + 2 * r);
     const float4 dq = bwdq_span<V, VEC>(lane, b, e, a, q, go, st.x, st.y, delta, g.col_idx, c0);
-    if (c0 < a.k) *reinterpret_cast<float4 *>(g.scratch + p * kAtSlots + kAtSums + c0) = dq;
+    if (c0 < a.k) *reinterpret_cast<float4 *>(at_head_scratch(g) + p * kAtSlots + kAtSums + c0) = dq;
     if (sub == 0 && p == g.long_first[lo]) a.delta[r] = delta;
 }
 
 // a group per long row: out[row][c] = the pieces' partial sums at scratch offset `off`, added in piece order from +0
+// (hout: floats from one head's out to the next)
 template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_attn_add_pieces(GroupPieces g, int off, float *__restrict__ out, int64_t ld, int w)
+__global__ __launch_bounds__(kBlock) void k_attn_add_pieces(GroupPieces g, int off, float *__restrict__ out, int64_t ld, int w,
+                                                            int64_t hout)
 {
     const int sub = threadIdx.x & (V - 1), c0 = 4 * sub;
     const int64_t i = (int64_t)blockIdx.x * (kBlock / V) + threadIdx.x / V;
     if (i >= g.n_long || c0 >= w) return;
+    const float *scratch = at_head_scratch(g);
+    out += (int64_t)blockIdx.y * hout;
     float4 acc = zero4();
     for (int p = g.long_first[i]; p < g.long_first[i + 1]; ++p) {
-        const float4 x = *reinterpret_cast<const float4 *>(g.scratch + (int64_t)p * kAtSlots + off + c0);
+        const float4 x = *reinterpret_cast<const float4 *>(scratch + (int64_t)p * kAtSlots + off + c0);
         acc.x = acc.x + x.x;
         acc.y = acc.y + x.y;
         acc.z = acc.z + x.z;
@@ -370,8 +417,9 @@ __device__ __forceinline__ void bwdkv_span(int lane, int64_t b, int64_t e, const
 }
 
 template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows(GroupRows g, AttnArgs a)
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows(GroupRows g, AttnArgs a0)
 {
+    const AttnArgs a = at_head(a0);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     const int64_t r = group_row<V>(g);
     if (r < 0) return;
@@ -388,8 +436,9 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows(GroupRows g, AttnAr
 }
 
 template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_pieces(GroupPieces g, AttnArgs a)
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_pieces(GroupPieces g, AttnArgs a0)
 {
+    const AttnArgs a = at_head(a0);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     int lo;
     const int64_t p = group_piece<V>(g, lo);
@@ -400,28 +449,29 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_pieces(GroupPieces g, At
     const float4 vj = c0 < a.kv ? load_slice<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
     float4 dk, dv;
     bwdkv_span<V, VEC>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv);
-    float *s = g.scratch + p * kAtSlots;
+    float *s = at_head_scratch(g) + p * kAtSlots;
     if (c0 < a.k) *reinterpret_cast<float4 *>(s + kAtSums + c0) = dk;
     if (c0 < a.kv) *reinterpret_cast<float4 *>(s + kAtSums2 + c0) = dv;
 }
 
 enum { kPassForward = 0, kPassBackwardQ = 1, kPassBackwardKV = 2 };
 
+// one grid per kernel for all heads: the head is blockIdx.y, x is what a call of one head launches
 template <int PASS, int V, bool VEC>
-int launch_attn_v(const spmv_csr &h, const AttnArgs &a, const char *what, hipStream_t s)
+int launch_attn_v(const spmv_csr &h, const AttnArgs &a, int heads, const char *what, hipStream_t s)
 {
     const SpmmPlan &p = h.plan_spmm;
-    const int64_t nblocks = group_row_blocks(what, h, V);
+    const int64_t nblocks = group_head_blocks(what, h, V, heads);
     if (nblocks < 0) return SPMV_ERR_INVALID;
     const GroupRows g = group_rows(h, V, nblocks);
-    const dim3 grid((unsigned)nblocks), block(kBlock);
+    const dim3 grid((unsigned)nblocks, (unsigned)heads), block(kBlock);
     if constexpr (PASS == kPassForward) hipLaunchKernelGGL((k_attn_fwd_rows<V, VEC>), grid, block, 0, s, g, a);
     else if constexpr (PASS == kPassBackwardQ) hipLaunchKernelGGL((k_attn_bwd_q_rows<V, VEC>), grid, block, 0, s, g, a);
     else hipLaunchKernelGGL((k_attn_bwd_kv_rows<V, VEC>), grid, block, 0, s, g, a);
     SPMV_LAUNCHED("k_attn_*_rows");
     if (!p.n_long) return SPMV_OK;
     const GroupPieces q = group_pieces(h, h.plan_attn.d_scratch.get());
-    const dim3 pgrid = group_grid(p.pieces, V), lgrid = group_grid(p.n_long, V);
+    const dim3 pgrid(group_grid(p.pieces, V).x, (unsigned)heads), lgrid(group_grid(p.n_long, V).x, (unsigned)heads);
     if constexpr (PASS == kPassForward) {
         hipLaunchKernelGGL((k_attn_fwd_pieces<V, VEC>), pgrid, block, 0, s, q, a);
         SPMV_LAUNCHED("k_attn_fwd_pieces");
@@ -430,26 +480,26 @@ int launch_attn_v(const spmv_csr &h, const AttnArgs &a, const char *what, hipStr
     } else if constexpr (PASS == kPassBackwardQ) {
         hipLaunchKernelGGL((k_attn_bwd_q_pieces<V, VEC>), pgrid, block, 0, s, q, a);
         SPMV_LAUNCHED("k_attn_bwd_q_pieces");
-        hipLaunchKernelGGL((k_attn_add_pieces<V, VEC>), lgrid, block, 0, s, q, kAtSums, a.out0, a.ld0, a.k);
+        hipLaunchKernelGGL((k_attn_add_pieces<V, VEC>), lgrid, block, 0, s, q, kAtSums, a.out0, a.ld0, a.k, a.h0);
         SPMV_LAUNCHED("k_attn_add_pieces");
     } else {
         hipLaunchKernelGGL((k_attn_bwd_kv_pieces<V, VEC>), pgrid, block, 0, s, q, a);
         SPMV_LAUNCHED("k_attn_bwd_kv_pieces");
-        hipLaunchKernelGGL((k_attn_add_pieces<V, VEC>), lgrid, block, 0, s, q, kAtSums, a.out0, a.ld0, a.k);
+        hipLaunchKernelGGL((k_attn_add_pieces<V, VEC>), lgrid, block, 0, s, q, kAtSums, a.out0, a.ld0, a.k, a.h0);
         SPMV_LAUNCHED("k_attn_add_pieces");
-        hipLaunchKernelGGL((k_attn_add_pieces<V, VEC>), lgrid, block, 0, s, q, kAtSums2, a.out1, a.ld1, a.kv);
+        hipLaunchKernelGGL((k_attn_add_pieces<V, VEC>), lgrid, block, 0, s, q, kAtSums2, a.out1, a.ld1, a.kv, a.h1);
         SPMV_LAUNCHED("k_attn_add_pieces");
     }
     return SPMV_OK;
 }
 
 template <int PASS>
-int launch_attn(const spmv_csr &h, const AttnArgs &a, bool vec, const char *what, hipStream_t s)
+int launch_attn(const spmv_csr &h, const AttnArgs &a, int heads, bool vec, const char *what, hipStream_t s)
 {
     if (h.rows == 0) return SPMV_OK;
     return dispatch_lanes(((a.k > a.kv ? a.k : a.kv) + 3) / 4, [&](auto v) {
         constexpr int V = decltype(v)::value;
-        return vec ? launch_attn_v<PASS, V, true>(h, a, what, s) : launch_attn_v<PASS, V, false>(h, a, what, s);
+        return vec ? launch_attn_v<PASS, V, true>(h, a, heads, what, s) : launch_attn_v<PASS, V, false>(h, a, heads, what, s);
     });
 }
 
@@ -460,46 +510,92 @@ bool vec4(std::initializer_list<int64_t> lds)
     return true;
 }
 
+const spmv_attn_heads_t kOneHead = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
 }  // namespace
 
-// The attention plan: the SpMM plan (made here if it is missing) and the scratch of the long rows' pieces.
-int plan_attention(spmv_csr &h, hipStream_t s)
+// The attention plan: the SpMM plan (made here if it is missing) and the scratch of the long rows' pieces, a slice of
+// pieces * kAtSlots floats per head.  It only grows; the scratch it replaces may still be read by work on `s`, so that is
+// waited for before the old block goes.
+int plan_attention_heads(spmv_csr &h, int heads, hipStream_t s)
 {
     if (int rc = plan_spmm(h, s)) return rc;
-    if (h.plan_attn.ready) return SPMV_OK;
+    if (h.plan_attn.ready && h.plan_attn.heads >= heads) return SPMV_OK;
     AttnPlan p;
-    if (h.plan_spmm.n_long) SPMV_HIP_TRY(p.d_scratch.alloc((size_t)h.plan_spmm.pieces * kAtSlots));
+    if (h.plan_spmm.n_long) SPMV_HIP_TRY(p.d_scratch.alloc((size_t)heads * (size_t)h.plan_spmm.pieces * kAtSlots));
+    p.heads = heads;
     p.ready = true;
+    if (h.plan_attn.ready) SPMV_HIP_TRY(hipStreamSynchronize(s));
     h.plan_attn = std::move(p);
     return SPMV_OK;
 }
 
+int plan_attention(spmv_csr &h, hipStream_t s) { return plan_attention_heads(h, 1, s); }
+
 int64_t attention_plan_bytes(const spmv_csr &h)
 {
     if (!h.plan_attn.ready) return 0;
-    return spmm_plan_bytes(h) + (h.plan_spmm.n_long ? (int64_t)h.plan_spmm.pieces * kAtSlots * 4 : 0);
+    return spmm_plan_bytes(h) + (h.plan_spmm.n_long ? (int64_t)h.plan_attn.heads * h.plan_spmm.pieces * kAtSlots * 4 : 0);
 }
 
-// arguments checked by the callers in capi.hip
-int launch_attention_forward(const spmv_csr &h, float scale, int k, const float *Q, int64_t ldq, const float *K, int64_t ldk,
-                             int kv, const float *V, int64_t ldv, float *O, int64_t ldo, float *stats, hipStream_t s)
+int attention_max_heads(const spmv_csr &h, int width)
+{
+    return dispatch_lanes((width + 3) / 4, [&](auto v) { return (int)group_max_heads(h, decltype(v)::value); });
+}
+
+// arguments checked by the callers in capi.hip; hs: the heads of the call and the strides of the operands it takes
+int launch_attention_forward_heads(const spmv_csr &h, const spmv_attn_heads_t &hs, float scale, int k, const float *Q,
+                                   int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv, float *O,
+                                   int64_t ldo, float *stats, const char *what, hipStream_t s)
 {
     AttnArgs a{};
     a.scale = scale, a.k = k, a.kv = kv;
     a.Q = Q, a.ldq = ldq, a.K = K, a.ldk = ldk, a.V = V, a.ldv = ldv;
     a.out0 = O, a.ld0 = ldo, a.stats = stats;
-    return launch_attn<kPassForward>(h, a, vec4({ldq, ldk, ldv, ldo}), "spmv_csr_attention_forward", s);
+    a.hq = hs.q, a.hk = hs.k, a.hv = hs.v, a.h0 = hs.o, a.hstats = hs.stats;
+    return launch_attn<kPassForward>(h, a, hs.heads, vec4({ldq, ldk, ldv, ldo}), what, s);
+}
+
+int launch_attention_backward_q_heads(const spmv_csr &h, const spmv_attn_heads_t &hs, float scale, int k, const float *Q,
+                                      int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv,
+                                      const float *O, int64_t ldo, const float *dO, int64_t lddo, const float *stats,
+                                      float *delta, float *dQ, int64_t lddq, const char *what, hipStream_t s)
+{
+    AttnArgs a{};
+    a.scale = scale, a.k = k, a.kv = kv;
+    a.Q = Q, a.ldq = ldq, a.K = K, a.ldk = ldk, a.V = V, a.ldv = ldv, a.O = O, a.ldo = ldo, a.dO = dO, a.lddo = lddo;
+    a.stats_in = stats, a.delta = delta, a.out0 = dQ, a.ld0 = lddq;
+    a.hq = hs.q, a.hk = hs.k, a.hv = hs.v, a.ho = hs.o, a.hdo = hs.d_o, a.hstats_in = hs.stats, a.hdelta = hs.delta, a.h0 = hs.dq;
+    return launch_attn<kPassBackwardQ>(h, a, hs.heads, vec4({ldq, ldk, ldv, ldo, lddo, lddq}), what, s);
+}
+
+int launch_attention_backward_kv_heads(const spmv_csr &t, const spmv_attn_heads_t &hs, float scale, int k, const float *Q,
+                                       int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv,
+                                       const float *dO, int64_t lddo, const float *stats, const float *delta, float *dK,
+                                       int64_t lddk, float *dV, int64_t lddv, const char *what, hipStream_t s)
+{
+    AttnArgs a{};
+    a.scale = scale, a.k = k, a.kv = kv;
+    a.Q = Q, a.ldq = ldq, a.K = K, a.ldk = ldk, a.V = V, a.ldv = ldv, a.dO = dO, a.lddo = lddo;
+    a.stats_in = stats, a.delta_in = delta, a.out0 = dK, a.ld0 = lddk, a.out1 = dV, a.ld1 = lddv;
+    a.hq = hs.q, a.hk = hs.k, a.hv = hs.v, a.hdo = hs.d_o, a.hstats_in = hs.stats, a.hdelta_in = hs.delta, a.h0 = hs.dk, a.h1 = hs.dv;
+    return launch_attn<kPassBackwardKV>(t, a, hs.heads, vec4({ldq, ldk, ldv, lddo, lddk, lddv}), what, s);
+}
+
+// one head: the same kernels at heads = 1 with every stride 0
+int launch_attention_forward(const spmv_csr &h, float scale, int k, const float *Q, int64_t ldq, const float *K, int64_t ldk,
+                             int kv, const float *V, int64_t ldv, float *O, int64_t ldo, float *stats, hipStream_t s)
+{
+    return launch_attention_forward_heads(h, kOneHead, scale, k, Q, ldq, K, ldk, kv, V, ldv, O, ldo, stats,
+                                          "spmv_csr_attention_forward", s);
 }
 
 int launch_attention_backward_q(const spmv_csr &h, float scale, int k, const float *Q, int64_t ldq, const float *K, int64_t ldk,
                                 int kv, const float *V, int64_t ldv, const float *O, int64_t ldo, const float *dO,
                                 int64_t lddo, const float *stats, float *delta, float *dQ, int64_t lddq, hipStream_t s)
 {
-    AttnArgs a{};
-    a.scale = scale, a.k = k, a.kv = kv;
-    a.Q = Q, a.ldq = ldq, a.K = K, a.ldk = ldk, a.V = V, a.ldv = ldv, a.O = O, a.ldo = ldo, a.dO = dO, a.lddo = lddo;
-    a.stats_in = stats, a.delta = delta, a.out0 = dQ, a.ld0 = lddq;
-    return launch_attn<kPassBackwardQ>(h, a, vec4({ldq, ldk, ldv, ldo, lddo, lddq}), "spmv_csr_attention_backward_q", s);
+    return launch_attention_backward_q_heads(h, kOneHead, scale, k, Q, ldq, K, ldk, kv, V, ldv, O, ldo, dO, lddo, stats, delta,
+                                             dQ, lddq, "spmv_csr_attention_backward_q", s);
 }
 
 int launch_attention_backward_kv(const spmv_csr &t, float scale, int k, const float *Q, int64_t ldq, const float *K,
@@ -507,11 +603,8 @@ int launch_attention_backward_kv(const spmv_csr &t, float scale, int k, const fl
                                  const float *stats, const float *delta, float *dK, int64_t lddk, float *dV, int64_t lddv,
                                  hipStream_t s)
 {
-    AttnArgs a{};
-    a.scale = scale, a.k = k, a.kv = kv;
-    a.Q = Q, a.ldq = ldq, a.K = K, a.ldk = ldk, a.V = V, a.ldv = ldv, a.dO = dO, a.lddo = lddo;
-    a.stats_in = stats, a.delta_in = delta, a.out0 = dK, a.ld0 = lddk, a.out1 = dV, a.ld1 = lddv;
-    return launch_attn<kPassBackwardKV>(t, a, vec4({ldq, ldk, ldv, lddo, lddk, lddv}), "spmv_csr_attention_backward_kv", s);
+    return launch_attention_backward_kv_heads(t, kOneHead, scale, k, Q, ldq, K, ldk, kv, V, ldv, dO, lddo, stats, delta, dK,
+                                              lddk, dV, lddv, "spmv_csr_attention_backward_kv", s);
 }
 
 }  // namespace spmv

@@ -10,6 +10,11 @@
 // the 8 XCDs takes one contiguous range of them (xcd_item64: neighbouring rows share lines of the gathered operand in
 // that XCD's L2).  The groups take the rows in the plan's order (stably by length inside blocks of 4096 rows, so the rows a
 // wavefront walks side by side end at nearly the same step), except at V = 1: see group_rows.
+// Heads (fused attention only).  A launch may carry several heads of one pattern as blockIdx.y; group_row, group_piece and
+// xcd_item64 keep reading blockIdx.x alone.  Workgroups are dispatched x-fastest, so the blocks of one head that an XCD sees
+// are still one residue class of blockIdx.x mod 8, which xcd_item64 still maps to one contiguous range of row blocks: the
+// L2 argument above holds head by head (where the grid's x extent is no multiple of 8 the class an XCD takes shifts from
+// one head to the next, and stays one class).  This is reasoning from the dispatch order, not a measurement.
 // A group walks its row in steps of T = max(V, 8) nonzeros (LaneGeom): lane s loads the step's column indices
 // kb + i V + s, i < L = T / V, coalesced (0 past the end), the group broadcasts them with shuffles (group_columns), every
 // lane issues all its gathers of the step, one slice per nonzero and operand (load_slice), and only then computes.
@@ -233,6 +238,35 @@ inline int64_t group_row_blocks(const char *who, const spmv_csr &h, int V)
     const int64_t nblocks = (h.rows + per - 1) / per;
     if (nblocks * kBlock >= (1LL << 32)) {
         set_error("%s: %lld rows x %d lanes per row reach the launch limit of 2^32 work-items", who, (long long)h.rows, V);
+        return -1;
+    }
+    return nblocks;
+}
+
+// the heads one launch over h's pattern may carry (blockIdx.y): no grid of the call -- row blocks, or the blocks of the long
+// rows' pieces where those are more -- may reach 2^32 work-items over all heads, and a grid's y extent ends at kMaxHeads.
+// 0: not even one head fits.
+inline int64_t group_max_heads(const spmv_csr &h, int V)
+{
+    const int per = kBlock / V;
+    const int64_t nblocks = (h.rows + per - 1) / per, pblocks = ((int64_t)h.plan_spmm.pieces + per - 1) / per;
+    const int64_t blocks = nblocks > pblocks ? nblocks : pblocks;
+    const int64_t fit = blocks ? ((1LL << 32) - 1) / (blocks * kBlock) : kMaxHeads;
+    return fit < kMaxHeads ? fit : kMaxHeads;
+}
+
+// group_row_blocks for a launch of `heads` heads, or -1 and `who`'s error
+inline int64_t group_head_blocks(const char *who, const spmv_csr &h, int V, int heads)
+{
+    const int64_t nblocks = group_row_blocks(who, h, V);
+    if (nblocks < 0) return -1;
+    if (heads > kMaxHeads) {
+        set_error("%s: %d heads exceed the launch limit of %d heads (the grid's y extent)", who, heads, kMaxHeads);
+        return -1;
+    }
+    if (heads > group_max_heads(h, V)) {
+        set_error("%s: %lld rows (%d pieces of long rows) x %d lanes per row x %d heads reach the launch limit of 2^32 work-items",
+                  who, (long long)h.rows, h.plan_spmm.pieces, V, heads);
         return -1;
     }
     return nblocks;

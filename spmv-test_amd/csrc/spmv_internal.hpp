@@ -78,6 +78,7 @@ int require_current(int device, const char *what);
 constexpr int kWave = 64;          // gfx950 wavefront
 constexpr int kBlock = 256;        // 4 waves: one per SIMD of a CU
 constexpr int kXcds = 8;           // MI355X: 8 XCDs, blocks dealt round-robin over them
+constexpr int kMaxHeads = 65535;   // heads of one spmv_csr_attention_*_heads launch: a grid's y extent
 
 // ADAPTIVE / TILED chunking: every lane streams kNnzPerThread consecutive-by-4 nonzeros
 // (col_idx + vals = 8 B each) with 16-byte loads; a workgroup of B threads owns B*16 nonzeros.
@@ -262,7 +263,8 @@ struct SpmmPlan {
 // spmv_csr_attention_* (kernels_attention.hip): on the SpMM plan, plus the scratch of the long rows' pieces
 struct AttnPlan {
     bool ready = false;
-    DevPtr<float> d_scratch;          // [pieces * 132] a piece's (m, l) and up to 128 partial sums (empty: no long row)
+    int heads = 0;                    // heads one launch may carry (spmv_csr_attention_plan: 1; _plan_heads grows it)
+    DevPtr<float> d_scratch;          // [heads * pieces * 132] per head and piece (m, l) and up to 128 partial sums (empty: no long row)
 };
 
 }  // namespace spmv
@@ -375,7 +377,21 @@ int launch_row_softmax(const spmv_csr &h, float scale, const float *scores, floa
 int launch_row_softmax_backward(const spmv_csr &h, float scale, const float *P, const float *dP, float *dS, hipStream_t s);
 // kernels_attention.hip: spmv_csr_attention_* (on the plan of plan_spmm and a scratch of its own)
 int plan_attention(spmv_csr &h, hipStream_t s);
+int plan_attention_heads(spmv_csr &h, int heads, hipStream_t s);
 int64_t attention_plan_bytes(const spmv_csr &h);
+int attention_max_heads(const spmv_csr &h, int width);   // heads one launch takes at operands of `width` columns (>= 0)
+// (the _heads launches: hs.heads heads in one grid, `what` names the caller in a refusal)
+int launch_attention_forward_heads(const spmv_csr &h, const spmv_attn_heads_t &hs, float scale, int k, const float *Q,
+                                   int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv, float *O,
+                                   int64_t ldo, float *stats, const char *what, hipStream_t s);
+int launch_attention_backward_q_heads(const spmv_csr &h, const spmv_attn_heads_t &hs, float scale, int k, const float *Q,
+                                      int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv,
+                                      const float *O, int64_t ldo, const float *dO, int64_t lddo, const float *stats,
+                                      float *delta, float *dQ, int64_t lddq, const char *what, hipStream_t s);
+int launch_attention_backward_kv_heads(const spmv_csr &t, const spmv_attn_heads_t &hs, float scale, int k, const float *Q,
+                                       int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv,
+                                       const float *dO, int64_t lddo, const float *stats, const float *delta, float *dK,
+                                       int64_t lddk, float *dV, int64_t lddv, const char *what, hipStream_t s);
 int launch_attention_forward(const spmv_csr &h, float scale, int k, const float *Q, int64_t ldq, const float *K, int64_t ldk,
                              int kv, const float *V, int64_t ldv, float *O, int64_t ldo, float *stats, hipStream_t s);
 int launch_attention_backward_q(const spmv_csr &h, float scale, int k, const float *Q, int64_t ldq, const float *K, int64_t ldk,

@@ -16,7 +16,8 @@ buffer and the clone of P that the backward pass needs.
 
 FusedSparseAttention is the same operation on the three fused passes (spmv_csr_attention_forward, _backward_q on A and
 _backward_kv on T = transpose(A), include/spmv_hip.h "Fused attention"): nothing of nnz floats is written, saved or read
-but col_idx, so one holder serves any number of heads.
+but col_idx, so one holder serves any number of heads: one after the other (heads="loop", the default) or all in one launch
+per kernel (heads="batched": spmv_csr_attention_*_heads).  Both give the same bits.
 """
 from __future__ import annotations
 
@@ -128,6 +129,19 @@ def _fused_operand(t, name: str, rows: int, k=None):
     return _heads_empty(t.shape[0], rows, w, t.device).copy_(t)
 
 
+def _batched_operand(t, name: str, rows: int, k=None):
+    """A (heads, rows, k) operand as one _heads call takes it: stride(2) == 1, stride(1) >= k, head 0 on a 16-byte boundary
+    and, with more than one head, a head stride that is a multiple of 4 floats (0: one head shared by all).  Stacked heads
+    and the column blocks of a (rows, heads * k) tensor with k % 4 == 0 are; anything else is copied once."""
+    if t.shape[0] < 1:
+        raise ValueError(f"SparseAttention: {name} has no heads")
+    _operand(t[0], name, rows, k)       # (dtype and shape)
+    w = t.shape[2]
+    if t.stride(2) == 1 and t.stride(1) >= w and t.data_ptr() % 16 == 0 and (t.shape[0] == 1 or t.stride(0) % 4 == 0):
+        return t
+    return _heads_empty(t.shape[0], rows, w, t.device).copy_(t)
+
+
 def _heads_empty(heads: int, rows: int, w: int, device):
     """(heads, rows, w) float32 whose every head is 16-byte aligned (rows padded to a multiple of 4 floats if need be)."""
     return torch.empty((heads, rows, (w + 3) // 4 * 4), dtype=torch.float32, device=device)[:, :, :w]
@@ -142,9 +156,11 @@ class FusedSparseAttentionFunction(torch.autograd.Function):
         A = att.A
         if len({t.dim() if isinstance(t, torch.Tensor) else -1 for t in (Q, K, V)}) != 1:
             raise ValueError("SparseAttention: Q, K and V must all be 2-D or all (heads, n, width)")
-        Q = _fused_operand(Q, "Q", A.rows)
-        K = _fused_operand(K, "K", A.cols, Q.shape[-1])
-        V = _fused_operand(V, "V", A.cols)
+        one_launch = att.heads == "batched" and isinstance(Q, torch.Tensor) and Q.dim() == 3
+        operand = _batched_operand if one_launch else _fused_operand
+        Q = operand(Q, "Q", A.rows)
+        K = operand(K, "K", A.cols, Q.shape[-1])
+        V = operand(V, "V", A.cols)
         kv = V.shape[-1]
         if Q.dim() == 3:
             heads = Q.shape[0]
@@ -152,8 +168,12 @@ class FusedSparseAttentionFunction(torch.autograd.Function):
                 raise ValueError(f"SparseAttention: Q has {heads} heads, K {K.shape[0]} and V {V.shape[0]}")
             O = _heads_empty(heads, A.rows, kv, V.device)
             stats = torch.empty((heads, A.rows, 2), dtype=torch.float32, device=V.device)
-            for h in range(heads):
-                A.attention_forward(Q[h], K[h], V[h], O[h], stats[h], att.scale)
+            if one_launch:
+                for lo, hi in att.head_chunks(heads, Q.shape[-1], kv):
+                    A.attention_forward_heads(Q[lo:hi], K[lo:hi], V[lo:hi], O[lo:hi], stats[lo:hi], att.scale)
+            else:
+                for h in range(heads):
+                    A.attention_forward(Q[h], K[h], V[h], O[h], stats[h], att.scale)
         else:
             O = torch.empty((A.rows, kv), dtype=torch.float32, device=V.device)
             stats = torch.empty((A.rows, 2), dtype=torch.float32, device=V.device)
@@ -171,7 +191,8 @@ class FusedSparseAttentionFunction(torch.autograd.Function):
         if not (need_q or need_k or need_v):
             return None, None, None, None
         batched = Q.dim() == 3
-        dO = _fused_operand(dO, "dO", A.rows, V.shape[-1])
+        one_launch = batched and att.heads == "batched"
+        dO = (_batched_operand if one_launch else _fused_operand)(dO, "dO", A.rows, V.shape[-1])
         if batched and dO.shape[0] != Q.shape[0]:
             raise ValueError(f"SparseAttention: dO has {dO.shape[0]} heads, Q {Q.shape[0]}")
 
@@ -183,6 +204,13 @@ class FusedSparseAttentionFunction(torch.autograd.Function):
         delta = torch.empty(O.shape[:-1], dtype=torch.float32, device=O.device)
         dK = like(K) if need_k or need_v else None
         dV = like(V) if need_k or need_v else None
+        if one_launch:
+            for lo, hi in att.head_chunks(Q.shape[0], Q.shape[-1], V.shape[-1]):
+                at = lambda t, lo=lo, hi=hi: t[lo:hi]       # noqa: E731
+                A.attention_backward_q_heads(at(Q), at(K), at(V), at(O), at(dO), at(stats), at(delta), at(dQ), att.scale)
+                if dK is not None:
+                    T.attention_backward_kv_heads(at(Q), at(K), at(V), at(dO), at(stats), at(delta), at(dK), at(dV), att.scale)
+            return None, dQ if need_q else None, dK if need_k else None, dV if need_v else None
         heads = range(Q.shape[0]) if batched else (None,)
         for h in heads:
             at = (lambda t: t) if h is None else (lambda t, h=h: t[h])
@@ -195,15 +223,24 @@ class FusedSparseAttentionFunction(torch.autograd.Function):
 class FusedSparseAttention:
     """One attention pattern of rows queries by cols keys on the fused passes.  Borrows ``row_ptr`` and ``col_idx`` (int32,
     one device); owns T = A^T (pattern only: no map) and both attention plans.  ``att(Q, K, V)``: Q rows x k, K cols x k,
-    V cols x kv, k and kv <= 64, or (heads, rows, k), (heads, cols, k), (heads, cols, kv): the heads run one after the other
-    on the same A and T.  A head that is a strided view with stride(1) == 1 on a 16-byte boundary goes in without a copy.
-    A query without keys gets a zero row of O.  Calls of one holder are stream-ordered (the plans' scratch).  The values
-    array that handle creation still asks for is allocated once here and never read."""
+    V cols x kv, k and kv <= 64, or (heads, rows, k), (heads, cols, k), (heads, cols, kv): with ``heads="loop"`` (the default)
+    the heads run one after the other on the same A and T; a head that is a strided view with stride(1) == 1 on a 16-byte
+    boundary goes in without a copy.  With ``heads="batched"`` all heads of a 3-D call run in one launch per kernel
+    (spmv_csr_attention_*_heads): the plans grow to the head count on first use (an allocation: not inside a graph capture),
+    stacked heads and column blocks of a (n, heads * k) tensor with k % 4 == 0 go in without a copy, and a head count beyond
+    a launch limit is split into the fewest chunks that fit.  Both modes give the same bits; 2-D operands behave alike in
+    both.  A query without keys gets a zero row of O.  Calls of one holder are stream-ordered (the plans' scratch).  The
+    values array that handle creation still asks for is allocated once here and never read."""
 
-    def __init__(self, rows: int, cols: int, row_ptr, col_idx, scale: float = 1.0):
+    def __init__(self, rows: int, cols: int, row_ptr, col_idx, scale: float = 1.0, heads: str = "loop"):
+        if heads not in ("loop", "batched"):
+            raise ValueError(f"SparseAttention: heads = {heads!r} (\"loop\" or \"batched\")")
         if not math.isfinite(scale):
             raise ValueError(f"SparseAttention: scale = {scale} is not finite")
+        self.heads = heads
         self.scale = float(scale)
+        self.max_heads = None       # a cap on the heads of one launch below the library's (None: the library's limit)
+        self._planned = 1
         vals = torch.zeros(int(col_idx.numel()), dtype=torch.float32, device=col_idx.device)
         self.A = capi.CsrMatrix.from_device(rows, cols, row_ptr, col_idx, vals)
         self.T = self.A.transpose(keep_map=False)
@@ -212,6 +249,19 @@ class FusedSparseAttention:
 
     def __call__(self, Q, K, V):
         return FusedSparseAttentionFunction.apply(self, Q, K, V)
+
+    def head_chunks(self, heads: int, k: int, kv: int):
+        """[(lo, hi)]: the fewest runs of heads that each fit one launch on A and on T at these widths (the library says how
+        many fit: spmv_csr_attention_max_heads).  Grows both plans to the largest run."""
+        fit = min(self.A.attention_max_heads(k, kv), self.T.attention_max_heads(k, kv))
+        fit = max(1, min(fit, self.max_heads or fit))      # (not even one: the call itself says why)
+        n = -(-heads // fit)
+        size = -(-heads // n)
+        if size > self._planned:
+            self.A.attention_plan_heads(size)
+            self.T.attention_plan_heads(size)
+            self._planned = size
+        return [(lo, min(lo + size, heads)) for lo in range(0, heads, size)]
 
     def close(self) -> None:
         self.T.close()

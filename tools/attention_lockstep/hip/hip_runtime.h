@@ -1,6 +1,6 @@
 #pragma once
 // tools/attention_lockstep: just enough of the HIP kernel language to run csrc/kernels_attention.hip on the host.  One
-// std::thread per work-item, a workgroup at a time.  The kernels shuffle only inside a group of V lanes, and every shuffle
+// std::thread per work-item of a workgroup.  The kernels shuffle only inside a group of V lanes, and every shuffle
 // sits in group-uniform control flow, so __shfl / __shfl_xor exchange through a per-group array between two barriers of
 // g_group_lanes threads (main sets it to the V of the launch).  Device memory is plain malloc memory, so AddressSanitizer
 // sees every access; float4 and float2 carry their device alignment, so UBSan sees a misaligned vector access.
@@ -20,14 +20,15 @@ struct alignas(16) float4 { float x, y, z, w; };
 struct alignas(8) float2 { float x, y; };
 inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
 inline float2 make_float2(float x, float y) { return float2{x, y}; }
-struct dim3 { unsigned x = 1, y = 1, z = 1; dim3(unsigned a = 1) : x(a) {} };
+struct dim3 { unsigned x = 1, y = 1, z = 1; dim3(unsigned a = 1, unsigned b = 1) : x(a), y(b) {} };
 typedef int hipError_t;
 typedef void *hipStream_t;
 constexpr int hipSuccess = 0;
 inline hipError_t hipGetLastError() { return 0; }
+inline hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
 inline int g_group_lanes = 1;
 struct GroupCtx { std::barrier<> bar; uint64_t slot[64]; explicit GroupCtx(int n) : bar(n) {} };
-struct Idx { unsigned x = 0; };
+struct Idx { unsigned x = 0, y = 0; };
 inline thread_local Idx threadIdx, blockIdx;
 inline thread_local GroupCtx *g_group = nullptr;
 template <class T> T __shfl(T v, int src)
@@ -42,15 +43,24 @@ template <class T> T __shfl(T v, int src)
     return out;
 }
 template <class T> T __shfl_xor(T v, int m) { return __shfl(v, (int)(threadIdx.x & 63) ^ m); }
+// One thread per work-item of a workgroup, started once per launch: thread t runs work-item t of every block of the grid in
+// turn (x fastest, as the device dispatches them).  Blocks do not talk to each other and a group's exits are group-uniform, so
+// the groups may run ahead of one another; the lanes of one group meet at their shuffles.
 template <class K, class... A> void emu_launch(K kernel, dim3 grid, dim3 block, A... args)
 {
-    for (unsigned b = 0; b < grid.x; ++b) {
-        std::vector<std::unique_ptr<GroupCtx>> groups;
-        for (unsigned g = 0; g < block.x / g_group_lanes; ++g) groups.emplace_back(new GroupCtx(g_group_lanes));
-        std::vector<std::thread> ts;
-        for (unsigned t = 0; t < block.x; ++t)
-            ts.emplace_back([&, t] { threadIdx.x = t; blockIdx.x = b; g_group = groups[t / g_group_lanes].get(); kernel(args...); g_group->bar.arrive_and_drop(); });
-        for (auto &th : ts) th.join();
-    }
+    std::vector<std::unique_ptr<GroupCtx>> groups;
+    for (unsigned g = 0; g < block.x / g_group_lanes; ++g) groups.emplace_back(new GroupCtx(g_group_lanes));
+    std::vector<std::thread> ts;
+    for (unsigned t = 0; t < block.x; ++t)
+        ts.emplace_back([&, t] {
+            threadIdx.x = t;
+            g_group = groups[t / g_group_lanes].get();
+            for (unsigned y = 0; y < grid.y; ++y)
+                for (unsigned b = 0; b < grid.x; ++b) {
+                    blockIdx.x = b, blockIdx.y = y;
+                    kernel(args...);
+                }
+        });
+    for (auto &th : ts) th.join();
 }
 #define hipLaunchKernelGGL(k, g, b, sh, st, ...) emu_launch(k, g, b, __VA_ARGS__)

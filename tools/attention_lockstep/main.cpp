@@ -2,7 +2,9 @@
 // inside one step, several steps, exactly 512, pieces of long rows; the three passes at four (k, kv) on the 16-byte and the
 // 4-byte load path, every array an exactly sized heap block, compared with a serial fp64 statement of attention.  SDDMM
 // at the same four k on the pattern and on its transpose, every out[n] compared bit for bit with a serial statement of
-// the documented order.
+// the documented order.  Then three heads in one launch (launch_attention_*_heads, the head in blockIdx.y) at the same
+// (k, kv) and load paths, as stacked operands with a padded head stride and as column blocks of one wide matrix, the scratch
+// sized for exactly three heads: every head bit for bit the program's own single-head run on that head's data.
 #include "kernels_attention.hip"
 #include "kernels_sddmm.hip"
 #include <algorithm>
@@ -43,9 +45,45 @@ static spmv_csr make_handle(const Pattern &a, std::vector<void *> &owned)
     pl.d_order.p = heap(order), pl.d_long_row.p = heap(lr), pl.d_long_first.p = heap(lf), pl.d_piece_k0.p = heap(k0), pl.d_piece_len.p = heap(ln);
     if (plan_attention(h, nullptr) != SPMV_OK) abort();
     for (void *p : {(void *)rp, (void *)ci, (void *)pl.d_order.p, (void *)pl.d_long_row.p, (void *)pl.d_long_first.p, (void *)pl.d_piece_k0.p,
-                    (void *)pl.d_piece_len.p, (void *)h.plan_attn.d_scratch.p})
-        owned.push_back(p);
+                    (void *)pl.d_piece_len.p})
+        owned.push_back(p);       // (the scratch is the plan's: main frees it at the end)
     return h;
+}
+
+// the scratch of h for exactly `heads` heads (the stub's DevPtr frees the block it replaces)
+static void plan_heads(spmv_csr &h, int heads)
+{
+    free(h.plan_attn.d_scratch.p);
+    h.plan_attn = AttnPlan{};
+    if (plan_attention_heads(h, heads, nullptr) != SPMV_OK || h.plan_attn.heads != heads) abort();
+}
+
+// `heads` heads of rows x w floats: head y at p + y * stride, its rows ld apart; one exactly sized block that ends where the
+// last row of the last head does (at its width; on the 16-byte path at the end of its last slice)
+struct HeadsMatrix {
+    float *p;
+    int64_t ld, stride;
+};
+
+static HeadsMatrix heads_matrix(int heads, int64_t rows, int w, int64_t ld, int64_t stride, bool vec)
+{
+    const size_t n = (size_t)((heads - 1) * stride + (rows - 1) * ld + (vec ? (w + 3) / 4 * 4 : w));
+    float *p = (float *)malloc(4 * n);       // (16-byte aligned, and exact: the sanitizer sees the first byte past it)
+    for (size_t i = 0; i < n; ++i) p[i] = NAN;
+    return HeadsMatrix{p, ld, stride};
+}
+
+static void put_head(const HeadsMatrix &m, int y, const float *src, int64_t src_ld, int64_t rows, int w)
+{
+    for (int64_t r = 0; r < rows; ++r) std::memcpy(m.p + y * m.stride + r * m.ld, src + r * src_ld, 4 * (size_t)w);
+}
+
+// how many of head y's rows x w floats differ in a bit from the single-head result
+static long head_differs(const HeadsMatrix &m, int y, const float *ref, int64_t ref_ld, int64_t rows, int w)
+{
+    long bad = 0;
+    for (int64_t r = 0; r < rows; ++r) bad += std::memcmp(m.p + y * m.stride + r * m.ld, ref + r * ref_ld, 4 * (size_t)w) != 0;
+    return bad;
 }
 
 static Pattern transpose(const Pattern &a)
@@ -102,6 +140,84 @@ static long sddmm_differing(const spmv_csr &h, const Pattern &a, int k, const fl
         }
     free(out);
     return bad;
+}
+
+// Three heads in one launch against three single-head runs, at the four (k, kv) on both load paths, stacked and as column
+// blocks.  The single-head runs come first, on a scratch of one head; then the plans grow to exactly three.
+static int heads_runs(spmv_csr &A, spmv_csr &T, const Pattern &a, float scale, std::mt19937 &rng)
+{
+    constexpr int H = 3;
+    const int shapes[][2] = {{24, 24}, {8, 40}, {64, 4}, {6, 10}};
+    const int64_t R = a.rows, C = a.cols;
+    int status = 0;
+    for (auto &kk : shapes)
+        for (int odd = 0; odd < 2; ++odd) {
+            const int k = kk[0], kv = kk[1];
+            int V = 1;
+            while (4 * V < std::max(k, kv)) V *= 2;
+            g_group_lanes = V;
+            auto ld = [&](int w) { return (int64_t)(odd ? w + 1 + ((w + 1) % 4 == 0) : (w + 3) / 4 * 4 + 4); };
+            const int64_t lk = ld(k), lv = ld(kv);
+            // the single-head runs, every head on arrays of its own
+            float *Q[H], *K[H], *Vm[H], *dO[H], *O[H], *dQ[H], *dK[H], *dV[H], *stats[H], *delta[H];
+            plan_heads(A, 1);
+            plan_heads(T, 1);
+            for (int y = 0; y < H; ++y) {
+                Q[y] = matrix(R, k, lk, rng, true), K[y] = matrix(C, k, lk, rng, true), Vm[y] = matrix(C, kv, lv, rng, true);
+                dO[y] = matrix(R, kv, lv, rng, true), O[y] = matrix(R, kv, lv, rng, false), dQ[y] = matrix(R, k, lk, rng, false);
+                dK[y] = matrix(C, k, lk, rng, false), dV[y] = matrix(C, kv, lv, rng, false);
+                stats[y] = (float *)malloc(8 * R), delta[y] = (float *)malloc(4 * R);
+                status |= launch_attention_forward(A, scale, k, Q[y], lk, K[y], lk, kv, Vm[y], lv, O[y], lv, stats[y], nullptr);
+                status |= launch_attention_backward_q(A, scale, k, Q[y], lk, K[y], lk, kv, Vm[y], lv, O[y], lv, dO[y], lv, stats[y], delta[y], dQ[y], lk, nullptr);
+                status |= launch_attention_backward_kv(T, scale, k, Q[y], lk, K[y], lk, kv, Vm[y], lv, dO[y], lv, stats[y], delta[y], dK[y], lk, dV[y], lv, nullptr);
+            }
+            plan_heads(A, H);
+            plan_heads(T, H);
+            for (int blocks = 0; blocks < 2; ++blocks) {
+                // stacked: rows ld apart as above, heads a padded multiple of 4 floats apart; column blocks: head y at
+                // columns [y s, y s + w) of rows that hold all heads, s = w rounded up to 4
+                auto make = [&](int64_t rows, int w) {
+                    const int64_t s4 = (w + 3) / 4 * 4;
+                    if (blocks) return heads_matrix(H, rows, w, H * s4 + odd, s4, !odd);
+                    return heads_matrix(H, rows, w, ld(w), (rows * ld(w) + 3) / 4 * 4 + 8, !odd);
+                };
+                HeadsMatrix hQ = make(R, k), hK = make(C, k), hV = make(C, kv), hdO = make(R, kv), hO = make(R, kv), hdQ = make(R, k),
+                            hdK = make(C, k), hdV = make(C, kv);
+                const int64_t sstats = 2 * R + 2 * blocks, sdelta = R + 3 * blocks;
+                float *hstats = (float *)malloc(4 * (size_t)((H - 1) * sstats + 2 * R)), *hdelta = (float *)malloc(4 * (size_t)((H - 1) * sdelta + R));
+                for (int y = 0; y < H; ++y) {
+                    put_head(hQ, y, Q[y], lk, R, k), put_head(hK, y, K[y], lk, C, k), put_head(hV, y, Vm[y], lv, C, kv);
+                    put_head(hdO, y, dO[y], lv, R, kv);
+                }
+                spmv_attn_heads_t hs{};
+                hs.heads = H;
+                hs.q = hQ.stride, hs.k = hK.stride, hs.v = hV.stride, hs.o = hO.stride, hs.d_o = hdO.stride, hs.stats = sstats, hs.delta = sdelta;
+                hs.dq = hdQ.stride, hs.dk = hdK.stride, hs.dv = hdV.stride;
+                status |= launch_attention_forward_heads(A, hs, scale, k, hQ.p, hQ.ld, hK.p, hK.ld, kv, hV.p, hV.ld, hO.p, hO.ld, hstats, "forward_heads", nullptr);
+                status |= launch_attention_backward_q_heads(A, hs, scale, k, hQ.p, hQ.ld, hK.p, hK.ld, kv, hV.p, hV.ld, hO.p, hO.ld, hdO.p, hdO.ld, hstats,
+                                                            hdelta, hdQ.p, hdQ.ld, "backward_q_heads", nullptr);
+                status |= launch_attention_backward_kv_heads(T, hs, scale, k, hQ.p, hQ.ld, hK.p, hK.ld, kv, hV.p, hV.ld, hdO.p, hdO.ld, hstats, hdelta,
+                                                             hdK.p, hdK.ld, hdV.p, hdV.ld, "backward_kv_heads", nullptr);
+                long bad = 0;
+                for (int y = 0; y < H; ++y) {
+                    bad += head_differs(hO, y, O[y], lv, R, kv) + head_differs(hdQ, y, dQ[y], lk, R, k);
+                    bad += head_differs(hdK, y, dK[y], lk, C, k) + head_differs(hdV, y, dV[y], lv, C, kv);
+                    bad += std::memcmp(hstats + y * sstats, stats[y], 8 * (size_t)R) != 0;
+                    bad += std::memcmp(hdelta + y * sdelta, delta[y], 4 * (size_t)R) != 0;
+                }
+                printf("heads %d k %d kv %d V %d %s, %s: status %d, %ld rows differ in a bit from the single-head runs\n", H, k, kv, V,
+                       odd ? "4-byte path" : "16-byte path", blocks ? "column blocks" : "stacked", status, bad);
+                if (bad) status |= 64;
+                for (void *p : {(void *)hQ.p, (void *)hK.p, (void *)hV.p, (void *)hdO.p, (void *)hO.p, (void *)hdQ.p, (void *)hdK.p, (void *)hdV.p,
+                                (void *)hstats, (void *)hdelta})
+                    free(p);
+            }
+            for (int y = 0; y < H; ++y)
+                for (void *p : {(void *)Q[y], (void *)K[y], (void *)Vm[y], (void *)dO[y], (void *)O[y], (void *)dQ[y], (void *)dK[y], (void *)dV[y],
+                                (void *)stats[y], (void *)delta[y]})
+                    free(p);
+        }
+    return status;
 }
 
 int main()
@@ -210,6 +326,9 @@ int main()
             if (sa != 0 || st != 0) status |= 32;
             for (void *p : {(void *)Q, (void *)K, (void *)Vm, (void *)dO, (void *)O, (void *)dQ, (void *)dK, (void *)dV, (void *)stats, (void *)delta}) free(p);
         }
+    status |= heads_runs(A, T, a, scale, rng);
     for (void *p : owned) free(p);
+    free(A.plan_attn.d_scratch.p);
+    free(T.plan_attn.d_scratch.p);
     return status != 0 || !(worst <= 2e-5);
 }

@@ -7,21 +7,25 @@
 #include <cstdlib>
 #include <utility>
 enum { SPMV_OK = 0, SPMV_ERR_INVALID = -2 };
+typedef struct spmv_attn_heads {         // (include/spmv_hip.h)
+    int32_t heads, reserved;
+    int64_t q, k, v, o, d_o, stats, delta, dq, dk, dv;
+} spmv_attn_heads_t;
 #define SPMV_HIP_TRY(call) do { if ((call) != hipSuccess) return -3; } while (0)
 #define SPMV_LAUNCHED(name) if (hipGetLastError() != hipSuccess) return -3
 namespace spmv {
-constexpr int kWave = 64; constexpr int kBlock = 256; constexpr int kXcds = 8;
+constexpr int kWave = 64; constexpr int kBlock = 256; constexpr int kXcds = 8; constexpr int kMaxHeads = 65535;
 inline void set_error(const char *f, ...) { va_list a; va_start(a, f); vfprintf(stderr, f, a); va_end(a); }
 inline int hip_fail(hipError_t, const char *, const char *, int) { return -3; }
 template <class T> struct DevPtr {       // (exactly sized heap blocks; freed by main through free_all)
     T *p = nullptr;
     T *get() const { return p; }
     operator T *() const { return p; }
-    hipError_t alloc(size_t n) { p = (T *)malloc(sizeof(T) * (n ? n : 1)); return p ? hipSuccess : 1; }
+    hipError_t alloc(size_t n) { free(p); p = (T *)malloc(sizeof(T) * (n ? n : 1)); return p ? hipSuccess : 1; }
 };
 struct SpmmPlan { bool ready = true; int n_long = 0, pieces = 0, row_cap = 512, piece_len = 512;
     DevPtr<int32_t> d_order, d_long_row, d_long_first, d_piece_k0, d_piece_len; DevPtr<float> d_partial; };
-struct AttnPlan { bool ready = false; DevPtr<float> d_scratch; };
+struct AttnPlan { bool ready = false; int heads = 0; DevPtr<float> d_scratch; };
 }
 struct spmv_csr { int64_t rows = 0, cols = 0, nnz = 0; const int32_t *d_row_ptr = nullptr, *d_col_idx = nullptr;
     spmv::SpmmPlan plan_spmm; spmv::AttnPlan plan_attn; };

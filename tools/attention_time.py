@@ -9,6 +9,16 @@ SpMM, transpose_values), so it is the yardstick; nothing here sets a threshold.
 
     python tools/attention_time.py [--workloads c2:8192,c2:0,c3:8192,c3:0,c4:8192,c4:0] [--ks 16,32,64] [--scale c4=1.0]
                                    [--out profiles/attention_sweep.jsonl]
+
+--heads H[,H..]: the other comparison.  On the same (H, n, w) tensors and the same pattern, FusedSparseAttention(heads="loop")
+(one call per head and pass: the behaviour before the _heads calls existed) against FusedSparseAttention(heads="batched") (all
+heads in one launch per kernel), by the same protocol.  One JSON line per (pattern, k = kv, H): both times, their ratio
+batched / loop (below 1: one launch is faster), the lowest and highest window of each, and whether O and the three gradients
+of the two holders are equal bit for bit.  The patterns: bandNxM = N queries and N keys, query i listing the M consecutive
+keys around i (a sliding window), or a config as above; "@H" after a pattern runs it at that head count only.
+
+    python tools/attention_time.py --heads 8,16 [--workloads band4096x64,...,c2:8192@8] [--ks 16,64]
+                                   [--out profiles/attention_heads.jsonl]
 """
 import argparse
 import json
@@ -32,8 +42,8 @@ def window(fn, iters):
     return e0.elapsed_time(e1) / iters
 
 
-def timed_pair(fa, fb, window_ms, reps, max_iters):
-    """Medians of `reps` windows of fa and of fb, alternating; the windows hold the same number of calls."""
+def timed_windows(fa, fb, window_ms, reps, max_iters):
+    """`reps` windows of fa and of fb, alternating; the windows hold the same number of calls."""
     for _ in range(2):
         fa()
         fb()
@@ -43,13 +53,97 @@ def timed_pair(fa, fb, window_ms, reps, max_iters):
     for _ in range(reps):
         a.append(window(fa, iters))
         b.append(window(fb, iters))
+    return a, b, iters
+
+
+def timed_pair(fa, fb, window_ms, reps, max_iters):
+    """Medians of the windows of timed_windows."""
+    a, b, iters = timed_windows(fa, fb, window_ms, reps, max_iters)
     return statistics.median(a), statistics.median(b), iters
+
+
+HEADS_WORKLOADS = "band4096x64,band4096x256,band16384x64,band16384x256,band65536x64,band65536x256,c2:8192@8"
+
+
+def heads_pattern(spec, capi, W, dev, scales):
+    """(name, rows, cols, row_ptr, col_idx) on the device of bandNxM (query i lists the M consecutive keys around i) or of
+    a config name:band."""
+    import torch
+    if spec.startswith("band"):
+        n, m = (int(v) for v in spec[4:].split("x"))
+        start = (torch.arange(n, device=dev) - m // 2).clamp(0, n - m)
+        ci = (start[:, None] + torch.arange(m, device=dev)[None, :]).to(torch.int32).reshape(-1).contiguous()
+        rp = (torch.arange(n + 1, device=dev) * m).to(torch.int32)
+        return spec, n, n, rp, ci
+    name, band = spec.split(":")
+    w = W.config(name, band=int(band), scale=scales.get(name, 1.0))
+    rp = W.row_ptr(w)
+    nnz = int(rp[-1])
+    d_rp = torch.from_numpy(rp).to(dev)
+    d_ci = torch.empty(nnz, dtype=torch.int32, device=dev)
+    d_va = torch.empty(nnz, dtype=torch.float32, device=dev)
+    capi.synth_fill(w.seed, 0, w.rows, w.rows, w.cols, w.band, d_rp, d_ci, d_va)
+    return f"{name}_band{band}", w.rows, w.cols, d_rp, d_ci
+
+
+def heads_main(a, emit):
+    """The loop over the heads against one launch for all heads (see the module docstring)."""
+    import torch
+    pkg = ge.load_package()
+    capi, W, SA = pkg.capi, pkg.workloads, pkg.sparse_attention
+    dev = torch.device("cuda:0")
+    scales = dict((s.split("=")[0], float(s.split("=")[1])) for s in a.scale.split(",") if s)
+    all_heads = [int(h) for h in a.heads.split(",")]
+    for spec in (a.workloads or HEADS_WORKLOADS).split(","):
+        spec, _, only = spec.partition("@")
+        name, rows, cols, d_rp, d_ci = heads_pattern(spec, capi, W, dev, scales)
+        loop = SA.FusedSparseAttention(rows, cols, d_rp, d_ci, scale=0.25, heads="loop")
+        batched = SA.FusedSparseAttention(rows, cols, d_rp, d_ci, scale=0.25, heads="batched")
+        for H in ([int(only)] if only else all_heads):
+            for k in (int(s) for s in a.ks.split(",")):
+                gen = torch.Generator(device=dev).manual_seed(k)
+                Q, K, V, dO = (torch.randn((H, n, k), generator=gen, device=dev) for n in (rows, cols, cols, rows))
+                q, kk, v = (t.clone().requires_grad_(True) for t in (Q, K, V))
+
+                def forward(att):
+                    with torch.no_grad():
+                        att(Q, K, V)
+
+                def step(att):
+                    att(q, kk, v).backward(dO)
+                    q.grad = kk.grad = v.grad = None
+
+                def results(att):
+                    O = att(q, kk, v)
+                    O.backward(dO)
+                    out = [t.detach().clone() for t in (O, q.grad, kk.grad, v.grad)]
+                    q.grad = kk.grad = v.grad = None
+                    return out
+
+                same = all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(results(loop), results(batched)))
+                l_f, b_f, it_f = timed_windows(lambda: forward(loop), lambda: forward(batched), a.window_ms, a.reps, a.max_iters)
+                l_s, b_s, it_s = timed_windows(lambda: step(loop), lambda: step(batched), a.window_ms, a.reps, a.max_iters)
+                med, r4 = statistics.median, lambda x: round(x, 4)      # noqa: E731
+                emit(workload=name, heads=H, k=k, kv=k, rows=rows, cols=cols, nnz=int(d_ci.numel()), plan=loop.A.spmm_describe(),
+                     plan_T=loop.T.spmm_describe(), iters_forward=it_f, iters_step=it_s, reps=a.reps,
+                     loop_forward_ms=r4(med(l_f)), batched_forward_ms=r4(med(b_f)), forward_ratio=round(med(b_f) / med(l_f), 3),
+                     loop_forward_windows=[r4(min(l_f)), r4(max(l_f))], batched_forward_windows=[r4(min(b_f)), r4(max(b_f))],
+                     loop_step_ms=r4(med(l_s)), batched_step_ms=r4(med(b_s)), step_ratio=round(med(b_s) / med(l_s), 3),
+                     loop_step_windows=[r4(min(l_s)), r4(max(l_s))], batched_step_windows=[r4(min(b_s)), r4(max(b_s))],
+                     equal_bits=same)
+                del Q, K, V, dO, q, kk, v
+                torch.cuda.empty_cache()
+        loop.close()
+        batched.close()
+        del d_rp, d_ci
+        torch.cuda.empty_cache()
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workloads", default="c2:8192,c2:0,c3:8192,c3:0,c4:8192,c4:0")
-    ap.add_argument("--ks", default="16,32,64")
+    ap.add_argument("--workloads", default=None, help="default: c2:8192,c2:0,c3:8192,c3:0,c4:8192,c4:0; with --heads: " + HEADS_WORKLOADS)
+    ap.add_argument("--ks", default=None, help="default: 16,32,64; with --heads: 16,64")
+    ap.add_argument("--heads", default=None, help="H[,H..]: time heads=\"loop\" against heads=\"batched\" at these head counts")
     ap.add_argument("--scale", default="", help="name=fraction of the rows, e.g. c4=0.5 where the memory does not hold the full size")
     ap.add_argument("--window-ms", type=float, default=200.0)
     ap.add_argument("--max-iters", type=int, default=50)
@@ -72,6 +166,11 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if a.heads:
+        a.ks = a.ks or "16,64"
+        heads_main(a, emit)
+        return
+    a.workloads, a.ks = a.workloads or "c2:8192,c2:0,c3:8192,c3:0,c4:8192,c4:0", a.ks or "16,32,64"
     for spec in a.workloads.split(","):
         name, band = spec.split(":")
         w = W.config(name, band=int(band), scale=scales.get(name, 1.0))
