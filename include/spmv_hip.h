@@ -510,7 +510,8 @@ SPMV_API int spmv_csr_attention_backward_kv(spmv_csr_t *t, float scale, int k, c
  * odd (delta: any); with heads > 1 an output stride below the output's width (o: kv, dq and dk: k, dv: kv, stats: 2,
  * delta: 1); and everything the single-head call refuses.
  * Shared inputs: an input stride may be 0, so one K and V serve all heads (multi-query attention) without a copy; dK and
- * dV then still come out per head, and the caller sums them.
+ * dV then still come out per head, and the caller sums them.  (The _gqa calls below share K and V in groups and sum dK
+ * and dV themselves.)
  * Not checked: overlap between the outputs of different heads beyond the width rule (a stride below rows x ld of a stacked
  * output, say) is the caller's error, as "outputs must not overlap inputs" is.  Column blocks of one wide matrix
  * (stride = k, ld = heads x k) are a legal layout: the heads' rows interleave without overlapping. */
@@ -537,6 +538,43 @@ SPMV_API int spmv_csr_attention_backward_kv_heads(spmv_csr_t *t, const spmv_attn
                                                   const float *d_V, int64_t ldv, const float *d_dO, int64_t lddo,
                                                   const float *d_stats, const float *d_delta, float *d_dK, int64_t lddk,
                                                   float *d_dV, int64_t lddv, void *stream);
+
+/* ---- Fused attention, grouped-query heads (GQA): H query heads on H / g K/V heads, dK and dV summed in the kernel ---------
+ * The three _heads passes for query heads that share K and V in groups: hs->heads = H query heads, group = g query heads
+ * per K/V head, query head y uses K/V head y / g.  hs->k, hs->v, hs->dk and hs->dv are the floats from one K/V head to the
+ * next (K, V, dK and dV hold H / g heads); every other stride is per query head as above.  spmv_attn_heads_t is unchanged
+ * (88 bytes, reserved = 0).  K and V are neither expanded nor copied, dK and dV come out once per K/V head: g times fewer
+ * rows written than by a _heads call on expanded K/V, and no reduction pass afterwards.
+ * The plan: the call needs the plan to cover hs->heads query heads (spmv_csr_attention_plan_heads), else
+ * SPMV_ERR_NOT_PLANNED; the scratch layout (a slice per query head), spmv_csr_attention_plan_bytes and
+ * spmv_csr_attention_max_heads are unchanged, and the limit of one launch is the _heads limit on hs->heads.  After the plan
+ * the calls allocate nothing and never wait: graph-capturable.
+ * Refusals (SPMV_ERR_INVALID, a message that names the function, nothing launched, every output untouched): group < 1,
+ * hs->heads % group != 0, and everything the _heads call refuses; the output-stride rule for dk and dv applies when there is
+ * more than one K/V head (hs->heads / group > 1).
+ * The order of the sums (part of the interface, beside the text of "Fused attention" above):
+ *   forward, backward_q   head y of a _gqa call is, bit for bit, the single-head call with Q, O, dO, stats, delta and dQ
+ *            advanced by y times their strides and K, V advanced by (y / g) times theirs.  group = 1 is the _heads call bit
+ *            for bit.
+ *   backward_kv   for K/V head c let dK^(i), dV^(i) be what the single-head spmv_csr_attention_backward_kv gives for query
+ *            head c g + i with K, V of head c (the order above: a span in storage order from +0, a long row's pieces added
+ *            in piece order from +0).  Then dK_c = (..((dK^(0) + dK^(1)) + dK^(2)) .. + dK^(g-1)): fp32 additions in head
+ *            order, starting from head 0's value and not from +0; dV_c alike.  It is not a sum over the heads inside a
+ *            piece.  group = 1 is therefore the _heads call bit for bit.  A key no query lists gets +0. */
+SPMV_API int spmv_csr_attention_forward_gqa(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, float scale, int k,
+                                            const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, int kv,
+                                            const float *d_V, int64_t ldv, float *d_O, int64_t ldo, float *d_stats,
+                                            void *stream);
+SPMV_API int spmv_csr_attention_backward_q_gqa(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, float scale, int k,
+                                               const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, int kv,
+                                               const float *d_V, int64_t ldv, const float *d_O, int64_t ldo,
+                                               const float *d_dO, int64_t lddo, const float *d_stats, float *d_delta,
+                                               float *d_dQ, int64_t lddq, void *stream);
+SPMV_API int spmv_csr_attention_backward_kv_gqa(spmv_csr_t *t, const spmv_attn_heads_t *hs, int group, float scale, int k,
+                                                const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, int kv,
+                                                const float *d_V, int64_t ldv, const float *d_dO, int64_t lddo,
+                                                const float *d_stats, const float *d_delta, float *d_dK, int64_t lddk,
+                                                float *d_dV, int64_t lddv, void *stream);
 
 /* ---- dense baselines (reference slots cublas / naive / tiling) ---------
  * y[i] = sum_j x[j] * A[j*N+i] on the dense device matrix.

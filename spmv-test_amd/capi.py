@@ -87,6 +87,14 @@ SIGNATURES = {
     "spmv_csr_attention_backward_kv_heads": (C.c_int, [_H, _HS, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, C.c_int,
                                                        _f32p, C.c_int64, _f32p, C.c_int64, _f32p, _f32p, _f32p, C.c_int64, _f32p,
                                                        C.c_int64, _vp]),
+    "spmv_csr_attention_forward_gqa": (C.c_int, [_H, _HS, C.c_int, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64,
+                                                 C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, _f32p, _vp]),
+    "spmv_csr_attention_backward_q_gqa": (C.c_int, [_H, _HS, C.c_int, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64,
+                                                    C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, _f32p, C.c_int64, _f32p, _f32p,
+                                                    _f32p, C.c_int64, _vp]),
+    "spmv_csr_attention_backward_kv_gqa": (C.c_int, [_H, _HS, C.c_int, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64,
+                                                     C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, _f32p, _f32p, _f32p, C.c_int64,
+                                                     _f32p, C.c_int64, _vp]),
     "spmv_csr_plan_get": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int32)]),
     "spmv_csr_plan_set": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int32), _vp]),
     "spmv_csr_plan_like": (C.c_int, [_H, _H, C.c_int, _vp]),
@@ -490,6 +498,62 @@ class CsrMatrix:
                                                          K.stride(1), kv, _ptr(V), V.stride(1), _ptr(dO), dO.stride(1),
                                                          _ptr(stats), _ptr(delta), _ptr(dK), dK.stride(1), _ptr(dV),
                                                          dV.stride(1), _stream_handle(stream)))
+
+    # -- fused attention, grouped-query heads (spmv_csr_attention_*_gqa) ----------------------------------------------------
+    @classmethod
+    def _attention_gqa(cls, what: str, scale: float, query_mats: dict, key_mats: dict, vecs: dict):
+        """The query-side matrices and vectors hold H heads, the key-side matrices H_kv; each side under the layout rules of
+        _attention_heads.  Returns (H, H_kv, g = H // H_kv); ValueError when H_kv does not divide H."""
+        heads = cls._attention_heads(what, scale, query_mats, vecs)
+        kv_heads = cls._attention_heads(what, scale, key_mats, {})
+        if kv_heads < 1 or heads % kv_heads != 0:
+            raise ValueError(f"{what}: {heads} query heads on {kv_heads} K/V heads (grouped-query attention needs H_kv to "
+                             f"divide H)")
+        return heads, kv_heads, heads // kv_heads
+
+    def attention_forward_gqa(self, Q, K, V, O, stats, scale: float = 1.0, stream=None) -> None:
+        """attention_forward_heads for grouped-query heads (GQA): Q, O: (H, rows, .), stats: (H, rows, 2), K: (H_kv, cols, k),
+        V: (H_kv, cols, kv) with H % H_kv == 0; query head y reads K[y // g], V[y // g], g = H // H_kv, without a copy."""
+        what = "attention_forward_gqa"
+        k, kv = (t.shape[2] if getattr(t, "ndim", 0) == 3 else None for t in (Q, V))
+        heads, kv_heads, g = self._attention_gqa(what, scale, dict(Q=(Q, self.rows, k), O=(O, self.rows, kv)),
+                                                 dict(K=(K, self.cols, k), V=(V, self.cols, kv)),
+                                                 dict(stats=(stats, self.rows, 2)))
+        hs = AttnHeads(heads=heads, **self._head_strides(heads, q=Q, o=O, stats=stats), **self._head_strides(kv_heads, k=K, v=V))
+        check(lib().spmv_csr_attention_forward_gqa(self._h, C.byref(hs), g, scale, k, _ptr(Q), Q.stride(1), _ptr(K), K.stride(1),
+                                                   kv, _ptr(V), V.stride(1), _ptr(O), O.stride(1), _ptr(stats),
+                                                   _stream_handle(stream)))
+
+    def attention_backward_q_gqa(self, Q, K, V, O, dO, stats, delta, dQ, scale: float = 1.0, stream=None) -> None:
+        """attention_backward_q_heads for grouped-query heads (GQA): K, V hold H_kv heads, everything else H."""
+        what = "attention_backward_q_gqa"
+        k, kv = (t.shape[2] if getattr(t, "ndim", 0) == 3 else None for t in (Q, V))
+        heads, kv_heads, g = self._attention_gqa(what, scale, dict(Q=(Q, self.rows, k), O=(O, self.rows, kv), dO=(dO, self.rows, kv),
+                                                                   dQ=(dQ, self.rows, k)),
+                                                 dict(K=(K, self.cols, k), V=(V, self.cols, kv)),
+                                                 dict(stats=(stats, self.rows, 2), delta=(delta, self.rows, 1)))
+        hs = AttnHeads(heads=heads, **self._head_strides(heads, q=Q, o=O, d_o=dO, stats=stats, delta=delta, dq=dQ),
+                       **self._head_strides(kv_heads, k=K, v=V))
+        check(lib().spmv_csr_attention_backward_q_gqa(self._h, C.byref(hs), g, scale, k, _ptr(Q), Q.stride(1), _ptr(K), K.stride(1),
+                                                      kv, _ptr(V), V.stride(1), _ptr(O), O.stride(1), _ptr(dO), dO.stride(1),
+                                                      _ptr(stats), _ptr(delta), _ptr(dQ), dQ.stride(1), _stream_handle(stream)))
+
+    def attention_backward_kv_gqa(self, Q, K, V, dO, stats, delta, dK, dV, scale: float = 1.0, stream=None) -> None:
+        """On the handle of the TRANSPOSED pattern: attention_backward_kv_heads for grouped-query heads (GQA).  K, V, dK, dV:
+        (H_kv, rows, .); Q, dO, stats, delta hold H heads.  dK[c], dV[c] are the per-head results of query heads c g .. c g +
+        g - 1 added in the kernel in head order, starting from the first head's value."""
+        what = "attention_backward_kv_gqa"
+        k, kv = (t.shape[2] if getattr(t, "ndim", 0) == 3 else None for t in (Q, V))
+        heads, kv_heads, g = self._attention_gqa(what, scale, dict(Q=(Q, self.cols, k), dO=(dO, self.cols, kv)),
+                                                 dict(K=(K, self.rows, k), V=(V, self.rows, kv), dK=(dK, self.rows, k),
+                                                      dV=(dV, self.rows, kv)),
+                                                 dict(stats=(stats, self.cols, 2), delta=(delta, self.cols, 1)))
+        hs = AttnHeads(heads=heads, **self._head_strides(heads, q=Q, d_o=dO, stats=stats, delta=delta),
+                       **self._head_strides(kv_heads, k=K, v=V, dk=dK, dv=dV))
+        check(lib().spmv_csr_attention_backward_kv_gqa(self._h, C.byref(hs), g, scale, k, _ptr(Q), Q.stride(1), _ptr(K),
+                                                       K.stride(1), kv, _ptr(V), V.stride(1), _ptr(dO), dO.stride(1),
+                                                       _ptr(stats), _ptr(delta), _ptr(dK), dK.stride(1), _ptr(dV),
+                                                       dV.stride(1), _stream_handle(stream)))
 
     def values_changed(self) -> None:
         """The caller rewrote vals (borrowed arrays): plans that hold a copy of them are stale from here on."""

@@ -760,6 +760,7 @@ struct HeadStride {
     int64_t stride;
     int unit;        // the stride is a multiple of it: 4 for a matrix (16-byte aligned heads), 2 for stats, 1 for delta
     int out_width;   // of an output: floats a head writes per row (its stride is at least that with heads > 1); 0: an input
+    int heads = 0;   // how many heads the operand holds where that is not the call's (dK and dV of a _gqa call); 0: the call's
 };
 }  // namespace
 
@@ -783,7 +784,7 @@ static int attention_heads_strides(int heads, const HeadStride *st, int n, const
             set_error("%s: head stride of %s = %lld is no multiple of %d", what, o.name, (long long)o.stride, o.unit);
             return SPMV_ERR_INVALID;
         }
-        if (heads > 1 && o.stride < o.out_width) {
+        if ((o.heads ? o.heads : heads) > 1 && o.stride < o.out_width) {
             set_error("%s: head stride of the output %s = %lld is below its width %d", what, o.name, (long long)o.stride, o.out_width);
             return SPMV_ERR_INVALID;
         }
@@ -848,6 +849,74 @@ int spmv_csr_attention_backward_kv_heads(spmv_csr_t *t, const spmv_attn_heads_t 
     if (int rc = attention_args(t, scale, k, kv, ops, 6, d_stats, d_delta, true, queries, what, hs->heads)) return rc;
     return launch_attention_backward_kv_heads(*t, *hs, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_dO, lddo, d_stats, d_delta,
                                               d_dK, lddk, d_dV, lddv, what, (hipStream_t)stream);
+}
+
+// ---- fused attention, grouped-query heads: hs->heads query heads, `group` of them per K/V head ------------------------------
+static int attention_gqa_header(const spmv_attn_heads_t *hs, int group, const char *what)
+{
+    if (int rc = attention_heads_header(hs, what)) return rc;
+    if (group < 1) { set_error("%s: group = %d (need group >= 1)", what, group); return SPMV_ERR_INVALID; }
+    if (hs->heads % group != 0) {
+        set_error("%s: heads = %d is no multiple of group = %d", what, hs->heads, group);
+        return SPMV_ERR_INVALID;
+    }
+    return SPMV_OK;
+}
+
+int spmv_csr_attention_forward_gqa(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, float scale, int k, const float *d_Q,
+                                   int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V, int64_t ldv,
+                                   float *d_O, int64_t ldo, float *d_stats, void *stream)
+{
+    const char *what = "spmv_csr_attention_forward_gqa";
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (int rc = attention_gqa_header(hs, group, what)) return rc;
+    const HeadStride st[] = {{"Q", hs->q, 4, 0}, {"K", hs->k, 4, 0}, {"V", hs->v, 4, 0}, {"O", hs->o, 4, kv}, {"stats", hs->stats, 2, 2}};
+    if (int rc = attention_heads_strides(hs->heads, st, 5, what)) return rc;
+    const int64_t rows = h->rows, cols = h->cols;
+    const AttnOperand ops[] = {{"Q", d_Q, ldq, rows, k}, {"K", d_K, ldk, cols, k}, {"V", d_V, ldv, cols, kv}, {"O", d_O, ldo, rows, kv}};
+    if (int rc = attention_args(h, scale, k, kv, ops, 4, d_stats, nullptr, false, rows, what, hs->heads)) return rc;
+    return launch_attention_forward_gqa(*h, *hs, group, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_O, ldo, d_stats, what,
+                                        (hipStream_t)stream);
+}
+
+int spmv_csr_attention_backward_q_gqa(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, float scale, int k,
+                                      const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V,
+                                      int64_t ldv, const float *d_O, int64_t ldo, const float *d_dO, int64_t lddo,
+                                      const float *d_stats, float *d_delta, float *d_dQ, int64_t lddq, void *stream)
+{
+    const char *what = "spmv_csr_attention_backward_q_gqa";
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (int rc = attention_gqa_header(hs, group, what)) return rc;
+    const HeadStride st[] = {{"Q", hs->q, 4, 0}, {"K", hs->k, 4, 0}, {"V", hs->v, 4, 0}, {"O", hs->o, 4, 0}, {"dO", hs->d_o, 4, 0},
+                             {"stats", hs->stats, 2, 0}, {"delta", hs->delta, 1, 1}, {"dQ", hs->dq, 4, k}};
+    if (int rc = attention_heads_strides(hs->heads, st, 8, what)) return rc;
+    const int64_t rows = h->rows, cols = h->cols;
+    const AttnOperand ops[] = {{"Q", d_Q, ldq, rows, k}, {"K", d_K, ldk, cols, k}, {"V", d_V, ldv, cols, kv}, {"O", d_O, ldo, rows, kv},
+                               {"dO", d_dO, lddo, rows, kv}, {"dQ", d_dQ, lddq, rows, k}};
+    if (int rc = attention_args(h, scale, k, kv, ops, 6, d_stats, d_delta, true, rows, what, hs->heads)) return rc;
+    return launch_attention_backward_q_gqa(*h, *hs, group, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_O, ldo, d_dO, lddo,
+                                           d_stats, d_delta, d_dQ, lddq, what, (hipStream_t)stream);
+}
+
+// t is the handle of the TRANSPOSED pattern; dK and dV hold heads / group heads (the output-stride rule counts those)
+int spmv_csr_attention_backward_kv_gqa(spmv_csr_t *t, const spmv_attn_heads_t *hs, int group, float scale, int k,
+                                       const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V,
+                                       int64_t ldv, const float *d_dO, int64_t lddo, const float *d_stats, const float *d_delta,
+                                       float *d_dK, int64_t lddk, float *d_dV, int64_t lddv, void *stream)
+{
+    const char *what = "spmv_csr_attention_backward_kv_gqa";
+    if (!t) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (int rc = attention_gqa_header(hs, group, what)) return rc;
+    const int kv_heads = hs->heads / group;
+    const HeadStride st[] = {{"Q", hs->q, 4, 0}, {"K", hs->k, 4, 0}, {"V", hs->v, 4, 0}, {"dO", hs->d_o, 4, 0}, {"stats", hs->stats, 2, 0},
+                             {"delta", hs->delta, 1, 0}, {"dK", hs->dk, 4, k, kv_heads}, {"dV", hs->dv, 4, kv, kv_heads}};
+    if (int rc = attention_heads_strides(hs->heads, st, 8, what)) return rc;
+    const int64_t keys = t->rows, queries = t->cols;
+    const AttnOperand ops[] = {{"Q", d_Q, ldq, queries, k}, {"K", d_K, ldk, keys, k}, {"V", d_V, ldv, keys, kv},
+                               {"dO", d_dO, lddo, queries, kv}, {"dK", d_dK, lddk, keys, k}, {"dV", d_dV, lddv, keys, kv}};
+    if (int rc = attention_args(t, scale, k, kv, ops, 6, d_stats, d_delta, true, queries, what, hs->heads)) return rc;
+    return launch_attention_backward_kv_gqa(*t, *hs, group, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_dO, lddo, d_stats,
+                                            d_delta, d_dK, lddk, d_dV, lddv, what, (hipStream_t)stream);
 }
 
 int spmv_csr_values_changed(spmv_csr_t *h)

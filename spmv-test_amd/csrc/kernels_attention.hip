@@ -28,9 +28,19 @@
 // the 16-byte or 4-byte load path, of the row's place or neighbours, of a rebased row_ptr or of the handle.  (T depends on
 // V, hence on max(k, kv) only.)
 //
-// Heads.  Every kernel serves blockIdx.y = the head of one launch: it advances its operand bases by head x stride once at
-// entry (at_head; wave-uniform) and uses the slice of the scratch at head x pieces x kAtSlots.  A call of one head is the
-// same kernel at a grid of y = 1 with every stride 0, so head y of a call is that call on the advanced pointers bit for bit.
+// Heads.  Every kernel serves one query head of a launch: head = blockIdx.z * gridDim.y + blockIdx.y (query_head).  The grid's
+// y extent is the group g of query heads that share one K/V head and z is that K/V head, so no kernel divides: it advances K
+// and V by z x stride and every other base by head x stride once at entry (at_head; wave-uniform) and uses the slice of the
+// scratch at head x pieces x kAtSlots.  The _heads calls launch with g = 1 (y extent 1, the head in z), a call of one head
+// is the same kernel at a grid of y = z = 1 with every stride 0: head y of a call is that call on the advanced pointers bit
+// for bit.  (k_attn_add_pieces takes no K or V and keeps the head in a 2-D grid's y; query_head reads that alike.)
+//
+// Grouped-query heads (the _gqa calls).  Forward, backward_q and every *_pieces kernel are the kernels above at g > 1.  Only
+// backward_kv's sum over the heads of a group is new: k_attn_bwd_kv_rows_gqa (a lane group keeps K_j, V_j and walks its row of T
+// once per query head of the group) and k_attn_add_pieces_gqa (the long rows) form, per K/V head c,
+//   dK_c = (..((dK^(0) + dK^(1)) + dK^(2)) .. + dK^(g-1)),  dV_c alike,
+// with dK^(i), dV^(i) the single-head numbers of query head c g + i (spans from +0, a long row's pieces in piece order from
+// +0), added in head order from head 0's value, not from +0.  g = 1 adds nothing: the _heads bits.
 //
 // The scratch of the long rows (AttnPlan): per head, kAtSlots floats per piece: [0] m_p, [1] l_p, [4, 132) up to 128 partial sums
 // (forward acc_p[kv]; backward_q dQ_p[k]; backward_kv dK_p[k] at 4 and dV_p[kv] at 68).
@@ -62,15 +72,20 @@ struct AttnArgs {
     float *out1;      int64_t ld1;     // backward_kv dV
     float *stats;                      // forward
     float *delta;                      // backward_q
-    // floats from head y to head y + 1 of every operand above (blockIdx.y is the head; all 0 in a call of one head)
+    // floats from head y to head y + 1 of every operand above (all 0 in a call of one head); hk, hv (and in backward_kv h0,
+    // h1): from one K/V head to the next
     int64_t hq, hk, hv, ho, hdo, hstats_in, hdelta_in, h0, h1, hstats, hdelta;
 };
 
-// the operands of the block's head: every base advanced once, by a wave-uniform number (scalar work)
+// the query head of the block: blockIdx.y within its group of gridDim.y heads, the group (= the K/V head) in blockIdx.z
+__device__ __forceinline__ int64_t query_head() { return (int64_t)blockIdx.z * gridDim.y + blockIdx.y; }
+
+// the operands of the block's head: every base advanced once, by a wave-uniform number (scalar work); K and V by the K/V
+// head, everything else by the query head
 __device__ __forceinline__ AttnArgs at_head(AttnArgs a)
 {
-    const int64_t y = blockIdx.y;
-    a.Q += y * a.hq, a.K += y * a.hk, a.V += y * a.hv, a.O += y * a.ho, a.dO += y * a.hdo;
+    const int64_t y = query_head(), c = blockIdx.z;
+    a.Q += y * a.hq, a.K += c * a.hk, a.V += c * a.hv, a.O += y * a.ho, a.dO += y * a.hdo;
     a.stats_in += y * a.hstats_in, a.delta_in += y * a.hdelta_in;
     a.out0 += y * a.h0, a.out1 += y * a.h1, a.stats += y * a.hstats, a.delta += y * a.hdelta;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -91,10 +106,14 @@ __device__ __forceinline__ AttnArgs at_head(AttnArgs a)
     return a;
 }
 
-// the scratch of the block's head: head y owns the slice at y * pieces * kAtSlots
+// the scratch of the block's head: query head y owns the slice at y * pieces * kAtSlots (formed at entry like the bases above)
 __device__ __forceinline__ float *at_head_scratch(const GroupPieces &g)
 {
-    return g.scratch + (int64_t)blockIdx.y * g.npieces * kAtSlots;
+    float *s = g.scratch + query_head() * g.npieces * kAtSlots;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+s"(s));
+#endif
+    return s;
 }
 
 // ---- forward: (m, l, acc) of the nonzeros [b, e) of the group's row.  All lanes of a group call it with the same b, e. ----
@@ -186,6 +205,7 @@ template <int V, bool VEC>
 __global__ __launch_bounds__(kBlock) void k_attn_fwd_pieces(GroupPieces g, AttnArgs a0)
 {
     const AttnArgs a = at_head(a0);
+    float *const scratch = at_head_scratch(g);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     int lo;
     const int64_t p = group_piece<V>(g, lo);
@@ -196,7 +216,7 @@ __global__ __launch_bounds__(kBlock) void k_attn_fwd_pieces(GroupPieces g, AttnA
     float m, l;
     float4 acc;
     fwd_span<V, VEC>(lane, b, e, a, q, g.col_idx, c0, m, l, acc);
-    float *s = at_head_scratch(g) + p * kAtSlots;
+    float *s = scratch + p * kAtSlots;
     if (sub == 0) *reinterpret_cast<float2 *>(s) = make_float2(m, l);
     if (c0 < a.kv) *reinterpret_cast<float4 *>(s + kAtSums + c0) = acc;
 }
@@ -320,6 +340,7 @@ template <int V, bool VEC>
 __global__ __launch_bounds__(kBlock) void k_attn_bwd_q_pieces(GroupPieces g, AttnArgs a0)
 {
     const AttnArgs a = at_head(a0);
+    float *const scratch = at_head_scratch(g);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     int lo;
     const int64_t p = group_piece<V>(g, lo);
@@ -331,7 +352,7 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_q_pieces(GroupPieces g, Att
     const float4 q = c0 < a.k ? load_slice<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
     const float2 st = *reinterpret_cast<const float2 *>(a.stats_in + 2 * r);
     const float4 dq = bwdq_span<V, VEC>(lane, b, e, a, q, go, st.x, st.y, delta, g.col_idx, c0);
-    if (c0 < a.k) *reinterpret_cast<float4 *>(at_head_scratch(g) + p * kAtSlots + kAtSums + c0) = dq;
+    if (c0 < a.k) *reinterpret_cast<float4 *>(scratch + p * kAtSlots + kAtSums + c0) = dq;
     if (sub == 0 && p == g.long_first[lo]) a.delta[r] = delta;
 }
 
@@ -345,7 +366,7 @@ __global__ __launch_bounds__(kBlock) void k_attn_add_pieces(GroupPieces g, int o
     const int64_t i = (int64_t)blockIdx.x * (kBlock / V) + threadIdx.x / V;
     if (i >= g.n_long || c0 >= w) return;
     const float *scratch = at_head_scratch(g);
-    out += (int64_t)blockIdx.y * hout;
+    out += query_head() * hout;
     float4 acc = zero4();
     for (int p = g.long_first[i]; p < g.long_first[i + 1]; ++p) {
         const float4 x = *reinterpret_cast<const float4 *>(scratch + (int64_t)p * kAtSlots + off + c0);
@@ -439,6 +460,7 @@ template <int V, bool VEC>
 __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_pieces(GroupPieces g, AttnArgs a0)
 {
     const AttnArgs a = at_head(a0);
+    float *const scratch = at_head_scratch(g);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     int lo;
     const int64_t p = group_piece<V>(g, lo);
@@ -449,33 +471,179 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_pieces(GroupPieces g, At
     const float4 vj = c0 < a.kv ? load_slice<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
     float4 dk, dv;
     bwdkv_span<V, VEC>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv);
-    float *s = at_head_scratch(g) + p * kAtSlots;
+    float *s = scratch + p * kAtSlots;
     if (c0 < a.k) *reinterpret_cast<float4 *>(s + kAtSums + c0) = dk;
     if (c0 < a.kv) *reinterpret_cast<float4 *>(s + kAtSums2 + c0) = dv;
 }
 
+__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+// What a lane of k_attn_bwd_kv_rows_gqa needs only between two heads waits in LDS while the next head's span runs: N 16-byte
+// slots of the lane's own (slot n of lane t at [n * kBlock + t]).  Only the owning lane reads and writes them, so there is no
+// barrier; park_fence keeps the compiler from forwarding a parked value in a register instead.  Slots 0 and 1 hold the four
+// head strides (every V: 8 KiB per workgroup); at V = 16 slots 2 to 5 hold the dK sum, the dV sum, the row's two output
+// addresses and its bounds (b, e) as well (24 KiB).
+template <int N>
+__device__ __forceinline__ float4 *park_lds()
+{
+    __shared__ float4 park[N * kBlock];
+    return park + threadIdx.x;
+}
+
+template <int N, typename X>
+__device__ __forceinline__ void park_put(int slot, X x)
+{
+    static_assert(sizeof(X) == 16, "a slot is 16 bytes");
+    __builtin_memcpy(park_lds<N>() + slot * kBlock, &x, 16);
+}
+
+template <int N, typename X>
+__device__ __forceinline__ X park_get(int slot)
+{
+    X x;
+    __builtin_memcpy(&x, park_lds<N>() + slot * kBlock, 16);
+    return x;
+}
+
+__device__ __forceinline__ void park_fence() { asm volatile("" ::: "memory"); }
+
+struct Strides2 {
+    int64_t a, b;
+};
+struct Pointers2 {
+    float *k, *v;
+};
+
+// a number every lane of the wavefront holds alike, as a scalar again
+__device__ __forceinline__ int64_t uniform64(int64_t x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((int)(uint32_t)x);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)x >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+#else
+    return x;
+#endif
+}
+
+// backward_kv of a group of `group` query heads that share K/V head c = blockIdx.y (grid: row blocks x K/V heads): the lane
+// group holds K_j, V_j of its row of T once, walks the row once per query head c * group + i from +0 (bwdkv_span: the
+// per-head numbers) and adds the heads' results in head order, starting from head 0's.  The per-head kernel leaves few
+// registers free (k_attn_bwd_kv_rows: up to 104 SGPRs; at V = 16 247 to 254 of the 256 VGPRs that two waves per SIMD allow),
+// so the head strides, and at V = 16 the running sums, the row's output addresses and its bounds, wait in LDS (park_lds).
+template <int V, bool VEC>
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows_gqa(GroupRows g, AttnArgs a, int group)
+{
+    constexpr bool kPark = V == 16;
+    constexpr int N = kPark ? 6 : 2;
+    {
+        const int64_t c = blockIdx.y, y0 = c * group;
+        a.K += c * a.hk, a.V += c * a.hv, a.out0 += c * a.h0, a.out1 += c * a.h1;
+        a.Q += y0 * a.hq, a.dO += y0 * a.hdo, a.stats_in += y0 * a.hstats_in, a.delta_in += y0 * a.hdelta_in;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm("" : "+s"(a.K));      // (as at_head: the bases are formed here; c and the K/V strides are dead from here on)
+        asm("" : "+s"(a.V));
+        asm("" : "+s"(a.out0));
+        asm("" : "+s"(a.out1));
+        asm("" : "+s"(a.Q));
+        asm("" : "+s"(a.dO));
+        asm("" : "+s"(a.stats_in));
+        asm("" : "+s"(a.delta_in));
+#endif
+    }
+    const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
+    const int64_t r = group_row<V>(g);
+    if (r < 0) return;
+    const int64_t b = g.row_ptr[r], e = g.row_ptr[r + 1];
+    if (e - b > g.row_cap) return;
+    Pointers2 out{a.out0 + r * a.ld0 + c0, a.out1 + r * a.ld1 + c0};
+    float4 dk = zero4(), dv = zero4();
+    if (e > b) {
+        const float4 kj = c0 < a.k ? load_slice<VEC>(a.K, a.ldk, r, c0, a.k) : zero4();
+        const float4 vj = c0 < a.kv ? load_slice<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
+        park_put<N>(0, Strides2{a.hq, a.hdo});
+        park_put<N>(1, Strides2{a.hstats_in, a.hdelta_in});
+        if constexpr (kPark) {
+            park_put<N>(4, out);
+            park_put<N>(5, Strides2{b, e});
+        }
+        float4 sk = zero4(), sv = zero4();
+        for (int left = group;;) {
+            park_fence();
+            if constexpr (kPark) {
+                const Strides2 be = park_get<N, Strides2>(5);
+                bwdkv_span<V, VEC>(lane, be.a, be.b, a, kj, vj, g.col_idx, c0, dk, dv);
+            } else {
+                bwdkv_span<V, VEC>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv);
+            }
+            if (left != group) {
+                if constexpr (kPark) sk = park_get<N, float4>(2), sv = park_get<N, float4>(3);
+                dk = add4(sk, dk);
+                dv = add4(sv, dv);
+            }
+            if (--left == 0) break;
+            if constexpr (kPark) {
+                park_put<N>(2, dk);
+                park_put<N>(3, dv);
+            } else {
+                sk = dk, sv = dv;
+            }
+            const Strides2 s0 = park_get<N, Strides2>(0), s1 = park_get<N, Strides2>(1);
+            a.Q += uniform64(s0.a), a.dO += uniform64(s0.b), a.stats_in += uniform64(s1.a), a.delta_in += uniform64(s1.b);
+        }
+        if constexpr (kPark) out = park_get<N, Pointers2>(4);
+    }
+    if (c0 < a.k) store_slice<VEC>(out.k, dk, c0, a.k);
+    if (c0 < a.kv) store_slice<VEC>(out.v, dv, c0, a.kv);
+}
+
+// a group per long row of T and K/V head c = blockIdx.y: for each query head c * group + i its pieces' partial sums at scratch
+// offset `off`, added in piece order from +0 (k_attn_add_pieces' number), then the heads in head order from head 0's
+template <int V, bool VEC>
+__global__ __launch_bounds__(kBlock) void k_attn_add_pieces_gqa(GroupPieces g, int off, float *__restrict__ out, int64_t ld, int w,
+                                                                int64_t hout, int group)
+{
+    const int sub = threadIdx.x & (V - 1), c0 = 4 * sub;
+    const int64_t i = (int64_t)blockIdx.x * (kBlock / V) + threadIdx.x / V;
+    if (i >= g.n_long || c0 >= w) return;
+    const int64_t c = blockIdx.y, slice = (int64_t)g.npieces * kAtSlots;
+    const float *scratch = g.scratch + c * group * slice;
+    float4 acc = zero4();
+    for (int y = 0; y < group; ++y, scratch += slice) {
+        float4 sum = zero4();
+        for (int p = g.long_first[i]; p < g.long_first[i + 1]; ++p)
+            sum = add4(sum, *reinterpret_cast<const float4 *>(scratch + (int64_t)p * kAtSlots + off + c0));
+        acc = y ? add4(acc, sum) : sum;
+    }
+    store_slice<VEC>(out + c * hout + (int64_t)g.long_row[i] * ld + c0, acc, c0, w);
+}
+
 enum { kPassForward = 0, kPassBackwardQ = 1, kPassBackwardKV = 2 };
 
-// one grid per kernel for all heads: the head is blockIdx.y, x is what a call of one head launches
+// one grid per kernel for all heads: x is what a call of one head launches, y the query head within its group of `group`, z
+// the group (the K/V head); group = 1 for the _heads calls.  gqa (backward_kv only): the _gqa call, which sums the heads of a
+// group (k_attn_bwd_kv_rows_gqa, k_attn_add_pieces_gqa; also at group = 1).
 template <int PASS, int V, bool VEC>
-int launch_attn_v(const spmv_csr &h, const AttnArgs &a, int heads, const char *what, hipStream_t s)
+int launch_attn_v(const spmv_csr &h, const AttnArgs &a, int heads, int group, bool gqa, const char *what, hipStream_t s)
 {
     const SpmmPlan &p = h.plan_spmm;
     const int64_t nblocks = group_head_blocks(what, h, V, heads);
     if (nblocks < 0) return SPMV_ERR_INVALID;
     const GroupRows g = group_rows(h, V, nblocks);
-    const dim3 grid((unsigned)nblocks, (unsigned)heads), block(kBlock);
+    const unsigned kv_heads = (unsigned)(heads / group);
+    const dim3 grid((unsigned)nblocks, (unsigned)group, kv_heads), block(kBlock);
     if constexpr (PASS == kPassForward) hipLaunchKernelGGL((k_attn_fwd_rows<V, VEC>), grid, block, 0, s, g, a);
     else if constexpr (PASS == kPassBackwardQ) hipLaunchKernelGGL((k_attn_bwd_q_rows<V, VEC>), grid, block, 0, s, g, a);
+    else if (gqa) hipLaunchKernelGGL((k_attn_bwd_kv_rows_gqa<V, VEC>), dim3((unsigned)nblocks, kv_heads), block, 0, s, g, a, group);
     else hipLaunchKernelGGL((k_attn_bwd_kv_rows<V, VEC>), grid, block, 0, s, g, a);
     SPMV_LAUNCHED("k_attn_*_rows");
     if (!p.n_long) return SPMV_OK;
     const GroupPieces q = group_pieces(h, h.plan_attn.d_scratch.get());
-    const dim3 pgrid(group_grid(p.pieces, V).x, (unsigned)heads), lgrid(group_grid(p.n_long, V).x, (unsigned)heads);
+    const dim3 pgrid(group_grid(p.pieces, V).x, (unsigned)group, kv_heads), lgrid(group_grid(p.n_long, V).x, (unsigned)heads);
     if constexpr (PASS == kPassForward) {
         hipLaunchKernelGGL((k_attn_fwd_pieces<V, VEC>), pgrid, block, 0, s, q, a);
         SPMV_LAUNCHED("k_attn_fwd_pieces");
-        hipLaunchKernelGGL((k_attn_fwd_combine<V, VEC>), lgrid, block, 0, s, q, a);
+        hipLaunchKernelGGL((k_attn_fwd_combine<V, VEC>), dim3(lgrid.x, (unsigned)group, kv_heads), block, 0, s, q, a);
         SPMV_LAUNCHED("k_attn_fwd_combine");
     } else if constexpr (PASS == kPassBackwardQ) {
         hipLaunchKernelGGL((k_attn_bwd_q_pieces<V, VEC>), pgrid, block, 0, s, q, a);
@@ -485,6 +653,14 @@ int launch_attn_v(const spmv_csr &h, const AttnArgs &a, int heads, const char *w
     } else {
         hipLaunchKernelGGL((k_attn_bwd_kv_pieces<V, VEC>), pgrid, block, 0, s, q, a);
         SPMV_LAUNCHED("k_attn_bwd_kv_pieces");
+        if (gqa) {
+            const dim3 cgrid(lgrid.x, kv_heads);
+            hipLaunchKernelGGL((k_attn_add_pieces_gqa<V, VEC>), cgrid, block, 0, s, q, kAtSums, a.out0, a.ld0, a.k, a.h0, group);
+            SPMV_LAUNCHED("k_attn_add_pieces_gqa");
+            hipLaunchKernelGGL((k_attn_add_pieces_gqa<V, VEC>), cgrid, block, 0, s, q, kAtSums2, a.out1, a.ld1, a.kv, a.h1, group);
+            SPMV_LAUNCHED("k_attn_add_pieces_gqa");
+            return SPMV_OK;
+        }
         hipLaunchKernelGGL((k_attn_add_pieces<V, VEC>), lgrid, block, 0, s, q, kAtSums, a.out0, a.ld0, a.k, a.h0);
         SPMV_LAUNCHED("k_attn_add_pieces");
         hipLaunchKernelGGL((k_attn_add_pieces<V, VEC>), lgrid, block, 0, s, q, kAtSums2, a.out1, a.ld1, a.kv, a.h1);
@@ -494,12 +670,13 @@ int launch_attn_v(const spmv_csr &h, const AttnArgs &a, int heads, const char *w
 }
 
 template <int PASS>
-int launch_attn(const spmv_csr &h, const AttnArgs &a, int heads, bool vec, const char *what, hipStream_t s)
+int launch_attn(const spmv_csr &h, const AttnArgs &a, int heads, int group, bool gqa, bool vec, const char *what, hipStream_t s)
 {
     if (h.rows == 0) return SPMV_OK;
     return dispatch_lanes(((a.k > a.kv ? a.k : a.kv) + 3) / 4, [&](auto v) {
         constexpr int V = decltype(v)::value;
-        return vec ? launch_attn_v<PASS, V, true>(h, a, heads, what, s) : launch_attn_v<PASS, V, false>(h, a, heads, what, s);
+        return vec ? launch_attn_v<PASS, V, true>(h, a, heads, group, gqa, what, s)
+                   : launch_attn_v<PASS, V, false>(h, a, heads, group, gqa, what, s);
     });
 }
 
@@ -544,16 +721,36 @@ int attention_max_heads(const spmv_csr &h, int width)
 }
 
 // arguments checked by the callers in capi.hip; hs: the heads of the call and the strides of the operands it takes
-int launch_attention_forward_heads(const spmv_csr &h, const spmv_attn_heads_t &hs, float scale, int k, const float *Q,
-                                   int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv, float *O,
-                                   int64_t ldo, float *stats, const char *what, hipStream_t s)
+int launch_attention_forward_gqa(const spmv_csr &h, const spmv_attn_heads_t &hs, int group, float scale, int k, const float *Q,
+                                 int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv, float *O,
+                                 int64_t ldo, float *stats, const char *what, hipStream_t s)
 {
     AttnArgs a{};
     a.scale = scale, a.k = k, a.kv = kv;
     a.Q = Q, a.ldq = ldq, a.K = K, a.ldk = ldk, a.V = V, a.ldv = ldv;
     a.out0 = O, a.ld0 = ldo, a.stats = stats;
     a.hq = hs.q, a.hk = hs.k, a.hv = hs.v, a.h0 = hs.o, a.hstats = hs.stats;
-    return launch_attn<kPassForward>(h, a, hs.heads, vec4({ldq, ldk, ldv, ldo}), what, s);
+    return launch_attn<kPassForward>(h, a, hs.heads, group, false, vec4({ldq, ldk, ldv, ldo}), what, s);
+}
+
+int launch_attention_forward_heads(const spmv_csr &h, const spmv_attn_heads_t &hs, float scale, int k, const float *Q,
+                                   int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv, float *O,
+                                   int64_t ldo, float *stats, const char *what, hipStream_t s)
+{
+    return launch_attention_forward_gqa(h, hs, 1, scale, k, Q, ldq, K, ldk, kv, V, ldv, O, ldo, stats, what, s);
+}
+
+int launch_attention_backward_q_gqa(const spmv_csr &h, const spmv_attn_heads_t &hs, int group, float scale, int k, const float *Q,
+                                    int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv,
+                                    const float *O, int64_t ldo, const float *dO, int64_t lddo, const float *stats,
+                                    float *delta, float *dQ, int64_t lddq, const char *what, hipStream_t s)
+{
+    AttnArgs a{};
+    a.scale = scale, a.k = k, a.kv = kv;
+    a.Q = Q, a.ldq = ldq, a.K = K, a.ldk = ldk, a.V = V, a.ldv = ldv, a.O = O, a.ldo = ldo, a.dO = dO, a.lddo = lddo;
+    a.stats_in = stats, a.delta = delta, a.out0 = dQ, a.ld0 = lddq;
+    a.hq = hs.q, a.hk = hs.k, a.hv = hs.v, a.ho = hs.o, a.hdo = hs.d_o, a.hstats_in = hs.stats, a.hdelta = hs.delta, a.h0 = hs.dq;
+    return launch_attn<kPassBackwardQ>(h, a, hs.heads, group, false, vec4({ldq, ldk, ldv, ldo, lddo, lddq}), what, s);
 }
 
 int launch_attention_backward_q_heads(const spmv_csr &h, const spmv_attn_heads_t &hs, float scale, int k, const float *Q,
@@ -561,12 +758,23 @@ int launch_attention_backward_q_heads(const spmv_csr &h, const spmv_attn_heads_t
                                       const float *O, int64_t ldo, const float *dO, int64_t lddo, const float *stats,
                                       float *delta, float *dQ, int64_t lddq, const char *what, hipStream_t s)
 {
+    return launch_attention_backward_q_gqa(h, hs, 1, scale, k, Q, ldq, K, ldk, kv, V, ldv, O, ldo, dO, lddo, stats, delta, dQ,
+                                           lddq, what, s);
+}
+
+// group >= 1: the _gqa call (k_attn_bwd_kv_rows_gqa and k_attn_add_pieces_gqa, also at group = 1); 0: the _heads call
+static int backward_kv_launch(const spmv_csr &t, const spmv_attn_heads_t &hs, int group, float scale, int k, const float *Q,
+                              int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv, const float *dO,
+                              int64_t lddo, const float *stats, const float *delta, float *dK, int64_t lddk, float *dV,
+                              int64_t lddv, const char *what, hipStream_t s)
+{
     AttnArgs a{};
     a.scale = scale, a.k = k, a.kv = kv;
-    a.Q = Q, a.ldq = ldq, a.K = K, a.ldk = ldk, a.V = V, a.ldv = ldv, a.O = O, a.ldo = ldo, a.dO = dO, a.lddo = lddo;
-    a.stats_in = stats, a.delta = delta, a.out0 = dQ, a.ld0 = lddq;
-    a.hq = hs.q, a.hk = hs.k, a.hv = hs.v, a.ho = hs.o, a.hdo = hs.d_o, a.hstats_in = hs.stats, a.hdelta = hs.delta, a.h0 = hs.dq;
-    return launch_attn<kPassBackwardQ>(h, a, hs.heads, vec4({ldq, ldk, ldv, ldo, lddo, lddq}), what, s);
+    a.Q = Q, a.ldq = ldq, a.K = K, a.ldk = ldk, a.V = V, a.ldv = ldv, a.dO = dO, a.lddo = lddo;
+    a.stats_in = stats, a.delta_in = delta, a.out0 = dK, a.ld0 = lddk, a.out1 = dV, a.ld1 = lddv;
+    a.hq = hs.q, a.hk = hs.k, a.hv = hs.v, a.hdo = hs.d_o, a.hstats_in = hs.stats, a.hdelta_in = hs.delta, a.h0 = hs.dk, a.h1 = hs.dv;
+    return launch_attn<kPassBackwardKV>(t, a, hs.heads, group ? group : 1, group > 0, vec4({ldq, ldk, ldv, lddo, lddk, lddv}), what,
+                                        s);
 }
 
 int launch_attention_backward_kv_heads(const spmv_csr &t, const spmv_attn_heads_t &hs, float scale, int k, const float *Q,
@@ -574,12 +782,16 @@ int launch_attention_backward_kv_heads(const spmv_csr &t, const spmv_attn_heads_
                                        const float *dO, int64_t lddo, const float *stats, const float *delta, float *dK,
                                        int64_t lddk, float *dV, int64_t lddv, const char *what, hipStream_t s)
 {
-    AttnArgs a{};
-    a.scale = scale, a.k = k, a.kv = kv;
-    a.Q = Q, a.ldq = ldq, a.K = K, a.ldk = ldk, a.V = V, a.ldv = ldv, a.dO = dO, a.lddo = lddo;
-    a.stats_in = stats, a.delta_in = delta, a.out0 = dK, a.ld0 = lddk, a.out1 = dV, a.ld1 = lddv;
-    a.hq = hs.q, a.hk = hs.k, a.hv = hs.v, a.hdo = hs.d_o, a.hstats_in = hs.stats, a.hdelta_in = hs.delta, a.h0 = hs.dk, a.h1 = hs.dv;
-    return launch_attn<kPassBackwardKV>(t, a, hs.heads, vec4({ldq, ldk, ldv, lddo, lddk, lddv}), what, s);
+    return backward_kv_launch(t, hs, 0, scale, k, Q, ldq, K, ldk, kv, V, ldv, dO, lddo, stats, delta, dK, lddk, dV, lddv, what, s);
+}
+
+int launch_attention_backward_kv_gqa(const spmv_csr &t, const spmv_attn_heads_t &hs, int group, float scale, int k, const float *Q,
+                                     int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv,
+                                     const float *dO, int64_t lddo, const float *stats, const float *delta, float *dK,
+                                     int64_t lddk, float *dV, int64_t lddv, const char *what, hipStream_t s)
+{
+    return backward_kv_launch(t, hs, group, scale, k, Q, ldq, K, ldk, kv, V, ldv, dO, lddo, stats, delta, dK, lddk, dV, lddv, what,
+                              s);
 }
 
 // one head: the same kernels at heads = 1 with every stride 0

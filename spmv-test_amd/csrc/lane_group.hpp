@@ -10,7 +10,8 @@
 // the 8 XCDs takes one contiguous range of them (xcd_item64: neighbouring rows share lines of the gathered operand in
 // that XCD's L2).  The groups take the rows in the plan's order (stably by length inside blocks of 4096 rows, so the rows a
 // wavefront walks side by side end at nearly the same step), except at V = 1: see group_rows.
-// Heads (fused attention only).  A launch may carry several heads of one pattern as blockIdx.y; group_row, group_piece and
+// Heads (fused attention only).  A launch may carry several heads of one pattern in blockIdx.y and blockIdx.z (the query head
+// within its group of heads that share K and V, and the group; kernels_attention.hip); group_row, group_piece and
 // xcd_item64 keep reading blockIdx.x alone.  Workgroups are dispatched x-fastest, so the blocks of one head that an XCD sees
 // are still one residue class of blockIdx.x mod 8, which xcd_item64 still maps to one contiguous range of row blocks: the
 // L2 argument above holds head by head (where the grid's x extent is no multiple of 8 the class an XCD takes shifts from

@@ -392,6 +392,18 @@ int launch_attention_backward_kv_heads(const spmv_csr &t, const spmv_attn_heads_
                                        int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv,
                                        const float *dO, int64_t lddo, const float *stats, const float *delta, float *dK,
                                        int64_t lddk, float *dV, int64_t lddv, const char *what, hipStream_t s);
+// (the _gqa launches: hs.heads query heads, `group` of them per K/V head; hs.k, hs.v, hs.dk, hs.dv step by K/V head)
+int launch_attention_forward_gqa(const spmv_csr &h, const spmv_attn_heads_t &hs, int group, float scale, int k, const float *Q,
+                                 int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv, float *O,
+                                 int64_t ldo, float *stats, const char *what, hipStream_t s);
+int launch_attention_backward_q_gqa(const spmv_csr &h, const spmv_attn_heads_t &hs, int group, float scale, int k, const float *Q,
+                                    int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv,
+                                    const float *O, int64_t ldo, const float *dO, int64_t lddo, const float *stats,
+                                    float *delta, float *dQ, int64_t lddq, const char *what, hipStream_t s);
+int launch_attention_backward_kv_gqa(const spmv_csr &t, const spmv_attn_heads_t &hs, int group, float scale, int k, const float *Q,
+                                     int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv,
+                                     const float *dO, int64_t lddo, const float *stats, const float *delta, float *dK,
+                                     int64_t lddk, float *dV, int64_t lddv, const char *what, hipStream_t s);
 int launch_attention_forward(const spmv_csr &h, float scale, int k, const float *Q, int64_t ldq, const float *K, int64_t ldk,
                              int kv, const float *V, int64_t ldv, float *O, int64_t ldo, float *stats, hipStream_t s);
 int launch_attention_backward_q(const spmv_csr &h, float scale, int k, const float *Q, int64_t ldq, const float *K, int64_t ldk,

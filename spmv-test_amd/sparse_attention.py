@@ -17,7 +17,8 @@ buffer and the clone of P that the backward pass needs.
 FusedSparseAttention is the same operation on the three fused passes (spmv_csr_attention_forward, _backward_q on A and
 _backward_kv on T = transpose(A), include/spmv_hip.h "Fused attention"): nothing of nnz floats is written, saved or read
 but col_idx, so one holder serves any number of heads: one after the other (heads="loop", the default) or all in one launch
-per kernel (heads="batched": spmv_csr_attention_*_heads).  Both give the same bits.
+per kernel (heads="batched": spmv_csr_attention_*_heads).  Both give the same bits.  Grouped-query heads (GQA: K and V
+with H_kv heads, H % H_kv == 0) run on spmv_csr_attention_*_gqa: K and V are not expanded, dK and dV come back per K/V head.
 """
 from __future__ import annotations
 
@@ -149,7 +150,8 @@ def _heads_empty(heads: int, rows: int, w: int, device):
 
 class FusedSparseAttentionFunction(torch.autograd.Function):
     """``FusedSparseAttentionFunction.apply(att, Q, K, V)``: as SparseAttentionFunction, 2-D operands or (heads, n, width)
-    ones.  Saved for backward: Q, K, V, O and stats (2 floats per query and head)."""
+    ones; K and V may hold H_kv heads with H % H_kv == 0 (grouped-query heads: query head h reads K[h // g], V[h // g],
+    g = H // H_kv).  Saved for backward: Q, K, V, O and stats (2 floats per query and head)."""
 
     @staticmethod
     def forward(ctx, att, Q, K, V):
@@ -164,16 +166,21 @@ class FusedSparseAttentionFunction(torch.autograd.Function):
         kv = V.shape[-1]
         if Q.dim() == 3:
             heads = Q.shape[0]
-            if K.shape[0] != heads or V.shape[0] != heads:
+            if K.shape[0] != V.shape[0] or heads % K.shape[0] != 0:
                 raise ValueError(f"SparseAttention: Q has {heads} heads, K {K.shape[0]} and V {V.shape[0]}")
+            g = heads // K.shape[0]
             O = _heads_empty(heads, A.rows, kv, V.device)
             stats = torch.empty((heads, A.rows, 2), dtype=torch.float32, device=V.device)
-            if one_launch:
-                for lo, hi in att.head_chunks(heads, Q.shape[-1], kv):
+            chunks = att.head_chunks(heads, Q.shape[-1], kv, g) if one_launch else None
+            if chunks and g == 1:
+                for lo, hi in chunks:
                     A.attention_forward_heads(Q[lo:hi], K[lo:hi], V[lo:hi], O[lo:hi], stats[lo:hi], att.scale)
+            elif chunks:
+                for lo, hi in chunks:
+                    A.attention_forward_gqa(Q[lo:hi], K[lo // g:hi // g], V[lo // g:hi // g], O[lo:hi], stats[lo:hi], att.scale)
             else:
                 for h in range(heads):
-                    A.attention_forward(Q[h], K[h], V[h], O[h], stats[h], att.scale)
+                    A.attention_forward(Q[h], K[h // g], V[h // g], O[h], stats[h], att.scale)
         else:
             O = torch.empty((A.rows, kv), dtype=torch.float32, device=V.device)
             stats = torch.empty((A.rows, 2), dtype=torch.float32, device=V.device)
@@ -204,19 +211,37 @@ class FusedSparseAttentionFunction(torch.autograd.Function):
         delta = torch.empty(O.shape[:-1], dtype=torch.float32, device=O.device)
         dK = like(K) if need_k or need_v else None
         dV = like(V) if need_k or need_v else None
-        if one_launch:
-            for lo, hi in att.head_chunks(Q.shape[0], Q.shape[-1], V.shape[-1]):
+        g = Q.shape[0] // K.shape[0] if batched else 1
+        chunks = att.head_chunks(Q.shape[0], Q.shape[-1], V.shape[-1], g) if one_launch else None
+        if chunks:
+            for lo, hi in chunks:
                 at = lambda t, lo=lo, hi=hi: t[lo:hi]       # noqa: E731
-                A.attention_backward_q_heads(at(Q), at(K), at(V), at(O), at(dO), at(stats), at(delta), at(dQ), att.scale)
+                kv = lambda t, lo=lo // g, hi=hi // g: t[lo:hi]       # noqa: E731  (the chunk's K/V heads)
+                if g == 1:
+                    A.attention_backward_q_heads(at(Q), at(K), at(V), at(O), at(dO), at(stats), at(delta), at(dQ), att.scale)
+                    if dK is not None:
+                        T.attention_backward_kv_heads(at(Q), at(K), at(V), at(dO), at(stats), at(delta), at(dK), at(dV), att.scale)
+                    continue
+                A.attention_backward_q_gqa(at(Q), kv(K), kv(V), at(O), at(dO), at(stats), at(delta), at(dQ), att.scale)
                 if dK is not None:
-                    T.attention_backward_kv_heads(at(Q), at(K), at(V), at(dO), at(stats), at(delta), at(dK), at(dV), att.scale)
+                    T.attention_backward_kv_gqa(at(Q), kv(K), kv(V), at(dO), at(stats), at(delta), kv(dK), kv(dV), att.scale)
             return None, dQ if need_q else None, dK if need_k else None, dV if need_v else None
         heads = range(Q.shape[0]) if batched else (None,)
+        # grouped-query heads: the heads of a group after the first write into dKh, dVh, which are then added to the group's
+        # dK, dV: fp32 adds in head order, starting from the first head's value (what the _gqa call does in its kernel)
+        dKh, dVh = (like(K[:1])[0], like(V[:1])[0]) if g > 1 and dK is not None else (None, None)
         for h in heads:
             at = (lambda t: t) if h is None else (lambda t, h=h: t[h])
-            A.attention_backward_q(at(Q), at(K), at(V), at(O), at(dO), at(stats), at(delta), at(dQ), att.scale)
-            if dK is not None:
-                T.attention_backward_kv(at(Q), at(K), at(V), at(dO), at(stats), at(delta), at(dK), at(dV), att.scale)
+            kv = (lambda t: t) if h is None else (lambda t, c=h // g: t[c])
+            A.attention_backward_q(at(Q), kv(K), kv(V), at(O), at(dO), at(stats), at(delta), at(dQ), att.scale)
+            if dK is None:
+                continue
+            first = h is None or h % g == 0
+            T.attention_backward_kv(at(Q), kv(K), kv(V), at(dO), at(stats), at(delta), kv(dK) if first else dKh,
+                                    kv(dV) if first else dVh, att.scale)
+            if not first:
+                torch.add(kv(dK), dKh, out=kv(dK))
+                torch.add(kv(dV), dVh, out=kv(dV))
         return None, dQ if need_q else None, dK if need_k else None, dV if need_v else None
 
 
@@ -229,7 +254,12 @@ class FusedSparseAttention:
     (spmv_csr_attention_*_heads): the plans grow to the head count on first use (an allocation: not inside a graph capture),
     stacked heads and column blocks of a (n, heads * k) tensor with k % 4 == 0 go in without a copy, and a head count beyond
     a launch limit is split into the fewest chunks that fit.  Both modes give the same bits; 2-D operands behave alike in
-    both.  A query without keys gets a zero row of O.  Calls of one holder are stream-ordered (the plans' scratch).  The
+    both.  Grouped-query heads (GQA): K and V may carry H_kv heads with H % H_kv == 0; query head h then reads K[h // g] and
+    V[h // g], g = H // H_kv, without a copy, and dK and dV come back (H_kv, cols, width).  "batched" issues one
+    spmv_csr_attention_*_gqa call per pass (the kernel adds the heads' dK, dV), in chunks of whole groups; where fewer than
+    g heads fit one launch that call runs by the loop.  "loop" runs the per-head calls on K[h // g] and adds each head's dK, dV
+    into its group's in head order, starting from the first head's value: the same bits again.  Any other head mismatch is a
+    ValueError.  A query without keys gets a zero row of O.  Calls of one holder are stream-ordered (the plans' scratch).  The
     values array that handle creation still asks for is allocated once here and never read."""
 
     def __init__(self, rows: int, cols: int, row_ptr, col_idx, scale: float = 1.0, heads: str = "loop"):
@@ -250,13 +280,20 @@ class FusedSparseAttention:
     def __call__(self, Q, K, V):
         return FusedSparseAttentionFunction.apply(self, Q, K, V)
 
-    def head_chunks(self, heads: int, k: int, kv: int):
+    def head_chunks(self, heads: int, k: int, kv: int, group: int = 1):
         """[(lo, hi)]: the fewest runs of heads that each fit one launch on A and on T at these widths (the library says how
-        many fit: spmv_csr_attention_max_heads).  Grows both plans to the largest run."""
+        many fit: spmv_csr_attention_max_heads).  Grows both plans to the largest run.  With ``group`` > 1 (grouped-query
+        heads) a run is whole groups; None when not even one group fits a launch (the caller then runs the heads in a loop)."""
         fit = min(self.A.attention_max_heads(k, kv), self.T.attention_max_heads(k, kv))
         fit = max(1, min(fit, self.max_heads or fit))      # (not even one: the call itself says why)
-        n = -(-heads // fit)
-        size = -(-heads // n)
+        if group > 1:
+            if fit < group:
+                return None
+            n = -(-heads // (fit // group * group))
+            size = -(-(heads // group) // n) * group
+        else:
+            n = -(-heads // fit)
+            size = -(-heads // n)
         if size > self._planned:
             self.A.attention_plan_heads(size)
             self.T.attention_plan_heads(size)

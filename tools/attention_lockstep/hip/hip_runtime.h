@@ -16,11 +16,12 @@
 #define __forceinline__ inline
 #define __launch_bounds__(x)
 #define __restrict__
+#define __shared__ static      // (a lane touches only slots of its own, and thread t is lane t of every block it runs)
 struct alignas(16) float4 { float x, y, z, w; };
 struct alignas(8) float2 { float x, y; };
 inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
 inline float2 make_float2(float x, float y) { return float2{x, y}; }
-struct dim3 { unsigned x = 1, y = 1, z = 1; dim3(unsigned a = 1, unsigned b = 1) : x(a), y(b) {} };
+struct dim3 { unsigned x = 1, y = 1, z = 1; dim3(unsigned a = 1, unsigned b = 1, unsigned c = 1) : x(a), y(b), z(c) {} };
 typedef int hipError_t;
 typedef void *hipStream_t;
 constexpr int hipSuccess = 0;
@@ -28,8 +29,8 @@ inline hipError_t hipGetLastError() { return 0; }
 inline hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
 inline int g_group_lanes = 1;
 struct GroupCtx { std::barrier<> bar; uint64_t slot[64]; explicit GroupCtx(int n) : bar(n) {} };
-struct Idx { unsigned x = 0, y = 0; };
-inline thread_local Idx threadIdx, blockIdx;
+struct Idx { unsigned x = 0, y = 0, z = 0; };
+inline thread_local Idx threadIdx, blockIdx, gridDim;
 inline thread_local GroupCtx *g_group = nullptr;
 template <class T> T __shfl(T v, int src)
 {
@@ -44,7 +45,7 @@ template <class T> T __shfl(T v, int src)
 }
 template <class T> T __shfl_xor(T v, int m) { return __shfl(v, (int)(threadIdx.x & 63) ^ m); }
 // One thread per work-item of a workgroup, started once per launch: thread t runs work-item t of every block of the grid in
-// turn (x fastest, as the device dispatches them).  Blocks do not talk to each other and a group's exits are group-uniform, so
+// turn (x fastest, then y, then z, as the device dispatches them).  Blocks do not talk to each other and a group's exits are group-uniform, so
 // the groups may run ahead of one another; the lanes of one group meet at their shuffles.
 template <class K, class... A> void emu_launch(K kernel, dim3 grid, dim3 block, A... args)
 {
@@ -55,11 +56,13 @@ template <class K, class... A> void emu_launch(K kernel, dim3 grid, dim3 block, 
         ts.emplace_back([&, t] {
             threadIdx.x = t;
             g_group = groups[t / g_group_lanes].get();
-            for (unsigned y = 0; y < grid.y; ++y)
-                for (unsigned b = 0; b < grid.x; ++b) {
-                    blockIdx.x = b, blockIdx.y = y;
-                    kernel(args...);
-                }
+            gridDim.x = grid.x, gridDim.y = grid.y, gridDim.z = grid.z;
+            for (unsigned z = 0; z < grid.z; ++z)
+                for (unsigned y = 0; y < grid.y; ++y)
+                    for (unsigned b = 0; b < grid.x; ++b) {
+                        blockIdx.x = b, blockIdx.y = y, blockIdx.z = z;
+                        kernel(args...);
+                    }
         });
     for (auto &th : ts) th.join();
 }

@@ -4,7 +4,11 @@
 // at the same four k on the pattern and on its transpose, every out[n] compared bit for bit with a serial statement of
 // the documented order.  Then three heads in one launch (launch_attention_*_heads, the head in blockIdx.y) at the same
 // (k, kv) and load paths, as stacked operands with a padded head stride and as column blocks of one wide matrix, the scratch
-// sized for exactly three heads: every head bit for bit the program's own single-head run on that head's data.
+// sized for exactly three heads: every head bit for bit the program's own single-head run on that head's data.  Then grouped-
+// query heads (launch_attention_*_gqa): four query heads on two K/V heads, the three passes on both load paths at a V below 16
+// and at V = 16 (where k_attn_bwd_kv_rows_gqa parks its sums in LDS), the scratch sized for exactly four heads: O, stats,
+// delta and dQ bit for bit the single-head runs on K, V of head y / 2, dK and dV bit for bit those runs' results added in
+// head order from the first head's value.
 #include "kernels_attention.hip"
 #include "kernels_sddmm.hip"
 #include <algorithm>
@@ -220,6 +224,81 @@ static int heads_runs(spmv_csr &A, spmv_csr &T, const Pattern &a, float scale, s
     return status;
 }
 
+// Four query heads on two K/V heads in one _gqa call per pass against the program's own single-head runs: head y on K, V of
+// head y / G; dK, dV of K/V head c = the runs' results of heads c G .. c G + G - 1 added in that order from the first one's.
+static int gqa_runs(spmv_csr &A, spmv_csr &T, const Pattern &a, float scale, std::mt19937 &rng)
+{
+    constexpr int H = 4, G = 2, C2 = H / G;
+    const int shapes[][2] = {{6, 10}, {40, 64}};
+    const int64_t R = a.rows, C = a.cols;
+    int status = 0;
+    for (auto &kk : shapes)
+        for (int odd = 0; odd < 2; ++odd) {
+            const int k = kk[0], kv = kk[1];
+            int V = 1;
+            while (4 * V < std::max(k, kv)) V *= 2;
+            g_group_lanes = V;
+            auto ld = [&](int w) { return (int64_t)(odd ? w + 1 + ((w + 1) % 4 == 0) : (w + 3) / 4 * 4 + 4); };
+            const int64_t lk = ld(k), lv = ld(kv);
+            float *Q[H], *K[C2], *Vm[C2], *dO[H], *O[H], *dQ[H], *dK[H], *dV[H], *stats[H], *delta[H];
+            plan_heads(A, 1);
+            plan_heads(T, 1);
+            for (int c = 0; c < C2; ++c) K[c] = matrix(C, k, lk, rng, true), Vm[c] = matrix(C, kv, lv, rng, true);
+            for (int y = 0; y < H; ++y) {
+                const int c = y / G;
+                Q[y] = matrix(R, k, lk, rng, true), dO[y] = matrix(R, kv, lv, rng, true), O[y] = matrix(R, kv, lv, rng, false);
+                dQ[y] = matrix(R, k, lk, rng, false), dK[y] = matrix(C, k, lk, rng, false), dV[y] = matrix(C, kv, lv, rng, false);
+                stats[y] = (float *)malloc(8 * R), delta[y] = (float *)malloc(4 * R);
+                status |= launch_attention_forward(A, scale, k, Q[y], lk, K[c], lk, kv, Vm[c], lv, O[y], lv, stats[y], nullptr);
+                status |= launch_attention_backward_q(A, scale, k, Q[y], lk, K[c], lk, kv, Vm[c], lv, O[y], lv, dO[y], lv, stats[y], delta[y], dQ[y], lk, nullptr);
+                status |= launch_attention_backward_kv(T, scale, k, Q[y], lk, K[c], lk, kv, Vm[c], lv, dO[y], lv, stats[y], delta[y], dK[y], lk, dV[y], lv, nullptr);
+            }
+            // the per-head dK, dV folded in head order into the first head's arrays of each group
+            for (int c = 0; c < C2; ++c)
+                for (int i = 1; i < G; ++i)
+                    for (int64_t j = 0; j < C; ++j) {
+                        for (int x = 0; x < k; ++x) dK[c * G][j * lk + x] = dK[c * G][j * lk + x] + dK[c * G + i][j * lk + x];
+                        for (int x = 0; x < kv; ++x) dV[c * G][j * lv + x] = dV[c * G][j * lv + x] + dV[c * G + i][j * lv + x];
+                    }
+            plan_heads(A, H);
+            plan_heads(T, H);
+            auto make = [&](int heads, int64_t rows, int w) { return heads_matrix(heads, rows, w, ld(w), (rows * ld(w) + 3) / 4 * 4 + 8, !odd); };
+            HeadsMatrix hQ = make(H, R, k), hK = make(C2, C, k), hV = make(C2, C, kv), hdO = make(H, R, kv), hO = make(H, R, kv),
+                        hdQ = make(H, R, k), hdK = make(C2, C, k), hdV = make(C2, C, kv);
+            const int64_t sstats = 2 * R + 2, sdelta = R + 3;
+            float *hstats = (float *)malloc(4 * (size_t)((H - 1) * sstats + 2 * R)), *hdelta = (float *)malloc(4 * (size_t)((H - 1) * sdelta + R));
+            for (int y = 0; y < H; ++y) put_head(hQ, y, Q[y], lk, R, k), put_head(hdO, y, dO[y], lv, R, kv);
+            for (int c = 0; c < C2; ++c) put_head(hK, c, K[c], lk, C, k), put_head(hV, c, Vm[c], lv, C, kv);
+            spmv_attn_heads_t hs{};
+            hs.heads = H;
+            hs.q = hQ.stride, hs.k = hK.stride, hs.v = hV.stride, hs.o = hO.stride, hs.d_o = hdO.stride, hs.stats = sstats, hs.delta = sdelta;
+            hs.dq = hdQ.stride, hs.dk = hdK.stride, hs.dv = hdV.stride;
+            status |= launch_attention_forward_gqa(A, hs, G, scale, k, hQ.p, hQ.ld, hK.p, hK.ld, kv, hV.p, hV.ld, hO.p, hO.ld, hstats, "forward_gqa", nullptr);
+            status |= launch_attention_backward_q_gqa(A, hs, G, scale, k, hQ.p, hQ.ld, hK.p, hK.ld, kv, hV.p, hV.ld, hO.p, hO.ld, hdO.p, hdO.ld, hstats,
+                                                      hdelta, hdQ.p, hdQ.ld, "backward_q_gqa", nullptr);
+            status |= launch_attention_backward_kv_gqa(T, hs, G, scale, k, hQ.p, hQ.ld, hK.p, hK.ld, kv, hV.p, hV.ld, hdO.p, hdO.ld, hstats, hdelta,
+                                                       hdK.p, hdK.ld, hdV.p, hdV.ld, "backward_kv_gqa", nullptr);
+            long bad = 0;
+            for (int y = 0; y < H; ++y) {
+                bad += head_differs(hO, y, O[y], lv, R, kv) + head_differs(hdQ, y, dQ[y], lk, R, k);
+                bad += std::memcmp(hstats + y * sstats, stats[y], 8 * (size_t)R) != 0;
+                bad += std::memcmp(hdelta + y * sdelta, delta[y], 4 * (size_t)R) != 0;
+            }
+            for (int c = 0; c < C2; ++c) bad += head_differs(hdK, c, dK[c * G], lk, C, k) + head_differs(hdV, c, dV[c * G], lv, C, kv);
+            printf("gqa heads %d group %d k %d kv %d V %d %s: status %d, %ld rows differ in a bit from the single-head runs folded in head order\n",
+                   H, G, k, kv, V, odd ? "4-byte path" : "16-byte path", status, bad);
+            if (bad) status |= 128;
+            for (void *p : {(void *)hQ.p, (void *)hK.p, (void *)hV.p, (void *)hdO.p, (void *)hO.p, (void *)hdQ.p, (void *)hdK.p, (void *)hdV.p,
+                            (void *)hstats, (void *)hdelta})
+                free(p);
+            for (int c = 0; c < C2; ++c) free(K[c]), free(Vm[c]);
+            for (int y = 0; y < H; ++y)
+                for (void *p : {(void *)Q[y], (void *)dO[y], (void *)O[y], (void *)dQ[y], (void *)dK[y], (void *)dV[y], (void *)stats[y], (void *)delta[y]})
+                    free(p);
+        }
+    return status;
+}
+
 int main()
 {
     std::mt19937 rng(11);
@@ -327,6 +406,7 @@ int main()
             for (void *p : {(void *)Q, (void *)K, (void *)Vm, (void *)dO, (void *)O, (void *)dQ, (void *)dK, (void *)dV, (void *)stats, (void *)delta}) free(p);
         }
     status |= heads_runs(A, T, a, scale, rng);
+    status |= gqa_runs(A, T, a, scale, rng);
     for (void *p : owned) free(p);
     free(A.plan_attn.d_scratch.p);
     free(T.plan_attn.d_scratch.p);

@@ -19,6 +19,17 @@ keys around i (a sliding window), or a config as above; "@H" after a pattern run
 
     python tools/attention_time.py --heads 8,16 [--workloads band4096x64,...,c2:8192@8] [--ks 16,64]
                                    [--out profiles/attention_heads.jsonl]
+
+--gqa G[,G..]: grouped-query heads.  On the same patterns as --heads, with H = 16 query heads (--gqa-heads) on H / G K/V heads,
+FusedSparseAttention(heads="batched") two ways in one process, the windows alternating: on the grouped K and V (the _gqa
+calls: K and V are not expanded, the kernel adds the heads' dK and dV), and on K and V expanded with repeat_interleave inside
+the timed window, with autograd's sum of dK and dV (what a caller did before the _gqa calls existed).  And backward_kv alone:
+one attention_backward_kv_gqa call against one attention_backward_kv_heads call on the expanded K and V (G per-head passes per
+K/V head into H sets of dK and dV, which nobody sums here).  One JSON line per (pattern, k = kv, G): the medians, the ratios
+grouped / expanded (below 1: grouped is faster), the lowest and highest window of each and the bytes a forward-plus-backward
+step allocates.  Nothing here sets a threshold.
+
+    python tools/attention_time.py --gqa 2,4,8 [--workloads band4096x64,...] [--ks 16,64] [--out profiles/attention_gqa.jsonl]
 """
 import argparse
 import json
@@ -139,11 +150,96 @@ def heads_main(a, emit):
         torch.cuda.empty_cache()
 
 
+def gqa_main(a, emit):
+    """Grouped K and V against K and V expanded by the caller (see the module docstring)."""
+    import torch
+    pkg = ge.load_package()
+    capi, W, SA = pkg.capi, pkg.workloads, pkg.sparse_attention
+    dev = torch.device("cuda:0")
+    scales = dict((s.split("=")[0], float(s.split("=")[1])) for s in a.scale.split(",") if s)
+    H = a.gqa_heads
+    med, r4 = statistics.median, lambda x: round(x, 4)      # noqa: E731
+    for spec in (a.workloads or HEADS_WORKLOADS).split(","):
+        spec = spec.partition("@")[0]
+        name, rows, cols, d_rp, d_ci = heads_pattern(spec, capi, W, dev, scales)
+        att = SA.FusedSparseAttention(rows, cols, d_rp, d_ci, scale=0.25, heads="batched")
+        for G in (int(g) for g in a.gqa.split(",")):
+            for k in (int(s) for s in a.ks.split(",")):
+                gen = torch.Generator(device=dev).manual_seed(k)
+                Q, K, V, dO = (torch.randn((h, n, k), generator=gen, device=dev)
+                               for h, n in ((H, rows), (H // G, cols), (H // G, cols), (H, rows)))
+                q, kk, v = (t.clone().requires_grad_(True) for t in (Q, K, V))
+                expand = lambda t: t.repeat_interleave(G, dim=0)      # noqa: E731
+
+                def forward(grouped):
+                    with torch.no_grad():
+                        att(Q, K, V) if grouped else att(Q, expand(K), expand(V))
+
+                def step(grouped):
+                    (att(q, kk, v) if grouped else att(q, expand(kk), expand(v))).backward(dO)
+                    q.grad = kk.grad = v.grad = None
+
+                def step_bytes(grouped):
+                    step(grouped)
+                    torch.cuda.synchronize()
+                    torch.cuda.reset_peak_memory_stats()
+                    before = torch.cuda.memory_allocated()
+                    step(grouped)
+                    torch.cuda.synchronize()
+                    return torch.cuda.max_memory_allocated() - before
+
+                def results(grouped):
+                    O = att(q, kk, v) if grouped else att(q, expand(kk), expand(v))
+                    O.backward(dO)
+                    out = [t.detach().clone() for t in (O, q.grad, kk.grad, v.grad)]
+                    q.grad = kk.grad = v.grad = None
+                    return out
+
+                rg, re = results(True), results(False)
+                same_O = all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(rg[:2], re[:2]))
+                diff = max(float((x - y).abs().max()) for x, y in zip(rg[2:], re[2:]))
+                g_f, e_f, it_f = timed_windows(lambda: forward(True), lambda: forward(False), a.window_ms, a.reps, a.max_iters)
+                g_s, e_s, it_s = timed_windows(lambda: step(True), lambda: step(False), a.window_ms, a.reps, a.max_iters)
+                # backward_kv alone, on the operands of one step (the plans cover H heads after the steps above)
+                with torch.no_grad():
+                    O = att(Q, K, V)
+                stats, delta = torch.empty((H, rows, 2), device=dev), torch.empty((H, rows), device=dev)
+                dQ = torch.empty_like(Q)
+                att.A.attention_forward_gqa(Q, K, V, O, stats, att.scale)
+                att.A.attention_backward_q_gqa(Q, K, V, O, dO, stats, delta, dQ, att.scale)
+                Ke, Ve = expand(K), expand(V)
+                dKg, dVg, dKe, dVe = torch.empty_like(K), torch.empty_like(V), torch.empty_like(Ke), torch.empty_like(Ve)
+                g_kv, e_kv, it_kv = timed_windows(
+                    lambda: att.T.attention_backward_kv_gqa(Q, K, V, dO, stats, delta, dKg, dVg, att.scale),
+                    lambda: att.T.attention_backward_kv_heads(Q, Ke, Ve, dO, stats, delta, dKe, dVe, att.scale),
+                    a.window_ms, a.reps, a.max_iters)
+                emit(workload=name, heads=H, group=G, k=k, kv=k, rows=rows, cols=cols, nnz=int(d_ci.numel()),
+                     plan=att.A.spmm_describe(), plan_T=att.T.spmm_describe(), iters_forward=it_f, iters_step=it_s,
+                     iters_backward_kv=it_kv, reps=a.reps,
+                     grouped_forward_ms=r4(med(g_f)), expanded_forward_ms=r4(med(e_f)), forward_ratio=round(med(g_f) / med(e_f), 3),
+                     grouped_forward_windows=[r4(min(g_f)), r4(max(g_f))], expanded_forward_windows=[r4(min(e_f)), r4(max(e_f))],
+                     grouped_step_ms=r4(med(g_s)), expanded_step_ms=r4(med(e_s)), step_ratio=round(med(g_s) / med(e_s), 3),
+                     grouped_step_windows=[r4(min(g_s)), r4(max(g_s))], expanded_step_windows=[r4(min(e_s)), r4(max(e_s))],
+                     grouped_backward_kv_ms=r4(med(g_kv)), per_head_backward_kv_ms=r4(med(e_kv)),
+                     backward_kv_ratio=round(med(g_kv) / med(e_kv), 3),
+                     grouped_backward_kv_windows=[r4(min(g_kv)), r4(max(g_kv))],
+                     per_head_backward_kv_windows=[r4(min(e_kv)), r4(max(e_kv))],
+                     grouped_step_bytes=step_bytes(True), expanded_step_bytes=step_bytes(False),
+                     equal_bits_O_dQ=same_O, max_abs_diff_dK_dV=diff)
+                del Q, K, V, dO, q, kk, v, Ke, Ve, dKg, dVg, dKe, dVe, O, stats, delta, dQ, rg, re
+                torch.cuda.empty_cache()
+        att.close()
+        del d_rp, d_ci
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default=None, help="default: c2:8192,c2:0,c3:8192,c3:0,c4:8192,c4:0; with --heads: " + HEADS_WORKLOADS)
     ap.add_argument("--ks", default=None, help="default: 16,32,64; with --heads: 16,64")
     ap.add_argument("--heads", default=None, help="H[,H..]: time heads=\"loop\" against heads=\"batched\" at these head counts")
+    ap.add_argument("--gqa", default=None, help="G[,G..]: time grouped K/V against K/V expanded with repeat_interleave at these group sizes")
+    ap.add_argument("--gqa-heads", type=int, default=16, help="query heads of the --gqa runs")
     ap.add_argument("--scale", default="", help="name=fraction of the rows, e.g. c4=0.5 where the memory does not hold the full size")
     ap.add_argument("--window-ms", type=float, default=200.0)
     ap.add_argument("--max-iters", type=int, default=50)
@@ -166,6 +262,10 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if a.gqa:
+        a.ks = a.ks or "16,64"
+        gqa_main(a, emit)
+        return
     if a.heads:
         a.ks = a.ks or "16,64"
         heads_main(a, emit)
