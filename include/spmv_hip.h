@@ -341,8 +341,10 @@ SPMV_API int spmv_csr_run_host(spmv_csr_t *h, int variant, const float *x_host, 
  * plan exists; SPMV_ERR_NOT_PLANNED without it.  Runs of one handle must be stream-ordered (the plan owns the scratch).
  * Batch invariance: for one plan, Y[:, c] is bit-identical whatever k, ldx and ldy are, whichever position the column
  * has in the batch and whatever the other columns of X hold (NaN and Inf included); two runs, and two handles of the same
- * matrix, agree bit for bit.  The order of the fp32 additions of a row is the plan's own: fused multiply-adds in storage
- * order, rows of more than 512 nonzeros summed per piece of 512 and the pieces added in order (no variant's order).
+ * matrix, agree bit for bit.  The order of the fp32 additions of a row is the plan's own and part of the interface: per
+ * output column acc = fma(vals[n], X[col_idx[n]][c], acc) over the row's nonzeros in storage order, from +0; a row of more
+ * than 512 nonzeros is summed per piece of 512 in the same way, each from +0, and the pieces' sums are added in piece order,
+ * from +0 (no variant's order).  tests/test_gpu_order.py holds the kernels to this bit for bit.
  * spmv_csr_spmm_plan_bytes: device bytes of the plan (0 when not planned; negative for a null handle).
  * spmv_csr_spmm_describe: the plan in one line ("row_cap=512 piece_len=512 long_rows=... pieces=..."). */
 SPMV_API int spmv_csr_spmm_plan(spmv_csr_t *h, void *stream);

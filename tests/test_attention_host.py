@@ -4,9 +4,9 @@ and a null handle is refused.  A numpy emulation of the documented fp32 order of
 nonzeros, pieces of 512, the combine) is compared with fp64 dense attention on rows of 1 .. 5000 entries, and reproduces the
 exact case of tests/test_gpu_fused_attention.py bit for bit.
 
-The emulation rounds every operation to fp32 where the header says so.  fma(a, b, c) is taken as fp32(fp64(a) * fp64(b) + c):
-the product is exact in fp64, the sum is rounded twice, which differs from a true fma only in rare ties and by one ulp; expf is
-the correctly rounded one.  Neither matters to the bounds below, and the exact case has no rounding at all.
+The emulation (tests/_attention_order.py) rounds every operation to fp32 where the header says so; its fma is the correctly
+rounded one and its expf the correctly rounded exponential, which the device's need not be.  That does not matter to the bounds
+below, and the exact case has no rounding at all.
 
 The bound of the comparison, per row of L entries with D = max t - min t <= 32: the subtraction puts D 2^-24 into an exponent
 and expf gets 2 ulp, in the numerator and in the denominator; the fp32 scores themselves are left to RTOL (as in
@@ -29,11 +29,11 @@ from pathlib import Path
 import numpy as np
 
 import _attention_rows as R
+from _attention_order import (PIECE, backward_kv_row, backward_q_row, dot, f32, f64, fma, forward_row, geometry,  # noqa: F401
+                              probabilities)
 
 ROOT = Path(__file__).resolve().parent.parent
 RTOL, EPS = 1e-5, 2.0 ** -24
-PIECE = 512
-f32, f64 = np.float32, np.float64
 NAMES = {"spmv_csr_attention_plan": 2, "spmv_csr_attention_plan_bytes": 1, "spmv_csr_attention_forward": 14,
          "spmv_csr_attention_backward_q": 19, "spmv_csr_attention_backward_kv": 19}      # name -> number of arguments
 
@@ -87,134 +87,7 @@ def test_attention_refuses_a_null_handle(pkg):
     assert "spmv_csr_attention_backward_kv:" in lib.spmv_last_error().decode()
 
 
-# ---- the documented order in fp32 ------------------------------------------------------------------------------------
-def geometry(k, kv):
-    """(V, T): lanes per row and nonzeros per step."""
-    slices, V = (max(k, kv) + 3) // 4, 1
-    while V < slices:
-        V *= 2
-    return V, max(V, 8)
-
-
-def fma(a, b, c):
-    with np.errstate(invalid="ignore", over="ignore"):
-        return (np.asarray(a, f64) * np.asarray(b, f64) + np.asarray(c, f64)).astype(f32)
-
-
-def expf(x):
-    with np.errstate(invalid="ignore", over="ignore"):
-        return np.exp(np.asarray(x, f32).astype(f64)).astype(f32)
-
-
-def dot(a, B, V):
-    """a . B[n] for every row n of B in the documented order: lane partials by fma from +0, then the xor butterfly."""
-    B = np.asarray(B, f32).reshape(-1, len(a))
-    p = np.zeros((B.shape[0], V), f32)
-    for c in range(len(a)):
-        p[:, c // 4] = fma(a[c], B[:, c], p[:, c // 4])
-    lane, m = np.arange(V), V // 2
-    with np.errstate(invalid="ignore"):
-        while m:
-            p = p + p[:, lane ^ m]
-            m //= 2
-    return p[:, 0]
-
-
-def spans(n):
-    return [(0, n)] if n <= PIECE else [(b, min(b + PIECE, n)) for b in range(0, n, PIECE)]
-
-
-WRONG = ("stale_maximum", "combine_keeps_minus_inf", "maximum_before_scaling")      # see forward_row
-
-
-def forward_span(t, Vj, T, wrong=None, s=None, scale=None):
-    m, l, acc = f32(-np.inf), f32(0), np.zeros(Vj.shape[1], f32)
-    with np.errstate(invalid="ignore", over="ignore"):
-        for kb in range(0, len(t), T):
-            tt = t[kb:kb + T]
-            mn = np.fmax(m, np.fmax.reduce(tt))
-            if wrong == "maximum_before_scaling":
-                mn = np.fmax(m, f32(f32(scale) * np.fmax.reduce(s[kb:kb + T])))
-            z = f32(0) if mn == -np.inf else mn
-            if wrong == "stale_maximum" and m != -np.inf:
-                z = m
-            a, e = expf(m - z), expf(tt - z)
-            l, acc = f32(l * a), (acc * a).astype(f32)
-            for i in range(len(tt)):
-                l = f32(l + e[i])
-                acc = fma(e[i], Vj[kb + i], acc)
-            m = mn
-    return m, l, acc
-
-
-def forward_row(q, Kj, Vj, scale, V, T, wrong=None):
-    """(O row, M, r) of one query whose keys are the rows of Kj, Vj in storage order.  wrong: None is the documented order;
-    the others are mistakes an online softmax invites, kept to show that the rows of the tests tell them apart:
-    "stale_maximum" takes a step's exponentials against the maximum before the step, "combine_keeps_minus_inf" leaves out
-    the combine's z = 0 for M = -Inf, "maximum_before_scaling" takes the maximum over s and scales it afterwards."""
-    assert wrong is None or wrong in WRONG
-    n = Kj.shape[0]
-    if n == 0:
-        return np.zeros(Vj.shape[1], f32), f32(-np.inf), f32(0)
-    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
-        s = dot(q, Kj, V)
-        t = (f32(scale) * s).astype(f32)
-        parts = [forward_span(t[b:e], Vj[b:e], T, wrong, s[b:e], scale) for b, e in spans(n)]
-        if len(parts) == 1:
-            M, l, acc = parts[0]
-        else:
-            M = np.fmax.reduce(np.array([p[0] for p in parts], f32))
-            z = f32(0) if M == -np.inf and wrong != "combine_keeps_minus_inf" else M
-            l, acc = f32(0), np.zeros(Vj.shape[1], f32)
-            for m_p, l_p, acc_p in parts:
-                w = expf(m_p - z)
-                l, acc = fma(l_p, w, l), fma(acc_p, w, acc)
-        r = f32(1) / f32(l)
-        return (acc * r).astype(f32), f32(M), f32(r)
-
-
-def probabilities(t, M, r):
-    with np.errstate(invalid="ignore", over="ignore"):
-        return (expf((t - M).astype(f32)) * r).astype(f32)
-
-
-def ordered_fma_sum(w, X):
-    """sum of w[n] X[n] over the spans of a row: fma in storage order from +0, the spans added in piece order from +0."""
-    parts = []
-    for b, e in spans(len(w)):
-        acc = np.zeros(X.shape[1], f32)
-        for n in range(b, e):
-            acc = fma(w[n], X[n], acc)
-        parts.append(acc)
-    if len(parts) == 1:
-        return parts[0]
-    acc = np.zeros(X.shape[1], f32)
-    for p in parts:
-        acc = (acc + p).astype(f32)
-    return acc
-
-
-def backward_q_row(q, Kj, Vj, o, do, M, r, scale, V):
-    """(dQ row, delta) of one query."""
-    if Kj.shape[0] == 0:
-        return np.zeros(len(q), f32), f32(0)
-    with np.errstate(invalid="ignore", over="ignore"):
-        delta = dot(do, o[None], V)[0]
-        p = probabilities((f32(scale) * dot(q, Kj, V)).astype(f32), M, r)
-        ds = (f32(scale) * (p * (dot(do, Vj, V) - delta).astype(f32)).astype(f32)).astype(f32)
-    return ordered_fma_sum(ds, Kj), delta
-
-
-def backward_kv_row(kj, vj, Qi, dOi, Mi, ri, deltai, scale, V):
-    """(dK row, dV row) of one key whose queries are the rows of Qi, dOi in the transposed pattern's storage order."""
-    if Qi.shape[0] == 0:
-        return np.zeros(len(kj), f32), np.zeros(len(vj), f32)
-    with np.errstate(invalid="ignore", over="ignore"):
-        p = probabilities((f32(scale) * dot(kj, Qi, V)).astype(f32), Mi, ri)
-        ds = (f32(scale) * (p * (dot(vj, dOi, V) - deltai).astype(f32)).astype(f32)).astype(f32)
-    return ordered_fma_sum(ds, Qi), ordered_fma_sum(p, dOi)
-
-
+# ---- the documented order in fp32: tests/_attention_order.py (shared with the GPU tests that compare bit for bit) -----------
 def test_the_emulated_order_against_fp64_dense_attention():
     worst = [0.0, 0.0]
     for L in (1, 2, 7, 8, 9, 16, 17, 64, 511, 512, 513, 1024, 1025, 4100, 5000):

@@ -1,5 +1,6 @@
 // tools/attention_lockstep/main.cpp -- see run.sh.  One pattern whose rows (and whose transposed rows) cover empty rows, rows
-// inside one step, several steps, exactly 512, pieces of long rows; the three passes at four (k, kv) on the 16-byte and the
+// inside one step, several steps, exactly 512, pieces of long rows; a third of the rows unsorted and a fifth drawn with
+// replacement, so keys repeat inside rows and queries inside transposed rows; the three passes at four (k, kv) on the 16-byte and the
 // 4-byte load path, every array an exactly sized heap block, compared with a serial fp64 statement of attention.  SDDMM
 // at the same four k on the pattern and on its transpose, every out[n] compared bit for bit with a serial statement of
 // the documented order.  Then three heads in one launch (launch_attention_*_heads, the head in blockIdx.y) at the same
@@ -310,13 +311,20 @@ int main()
     a.rp.assign(1, 0);
     std::vector<int32_t> all((size_t)a.cols);
     for (int i = 0; i < a.cols; ++i) all[i] = i;
+    long unsorted = 0, repeats = 0;       // rows that are not sorted; entries whose key the row already lists
     for (int64_t r = 0; r < a.rows; ++r) {
         std::shuffle(all.begin(), all.end(), rng);
         std::vector<int32_t> row(all.begin(), all.begin() + lens[r]);
-        std::sort(row.begin(), row.end());
+        // every fifth row draws its columns with replacement from a few keys (a key may repeat), every third stays unsorted;
+        // the rest are sorted
+        if (r % 5 == 2)
+            for (int32_t &c : row) c = (int32_t)(rng() % std::min<int64_t>(a.cols, 2 * lens[r] + 4));
+        if (r % 3 != 1) std::sort(row.begin(), row.end());
         // columns 0 and 1 sit in most rows, so that the transposed pattern has two rows in pieces
         if (r % 10 != 0 && lens[r] && row[0] != 0) row[0] = 0;
         if (r % 7 != 0 && lens[r] > 1 && row[1] != 1 && row[0] == 0) row[1] = 1;
+        unsorted += !std::is_sorted(row.begin(), row.end());
+        for (size_t i = 0; i < row.size(); ++i) repeats += std::count(row.begin(), row.begin() + (long)i, row[i]) > 0;
         a.ci.insert(a.ci.end(), row.begin(), row.end());
         a.rp.push_back((int32_t)a.ci.size());
     }
@@ -327,9 +335,10 @@ int main()
     const Pattern t = transpose(a);
     std::vector<void *> owned;
     spmv_csr A = make_handle(a, owned), T = make_handle(t, owned);
-    printf("pattern %lld x %lld, nnz %lld; long rows %d (pieces %d), transposed %d (pieces %d)\n", (long long)a.rows, (long long)a.cols,
-           (long long)A.nnz, A.plan_spmm.n_long, A.plan_spmm.pieces, T.plan_spmm.n_long, T.plan_spmm.pieces);
-    if (!A.plan_spmm.n_long || T.plan_spmm.n_long < 2) return 2;
+    printf("pattern %lld x %lld, nnz %lld; long rows %d (pieces %d), transposed %d (pieces %d); %ld rows unsorted, %ld repeated keys before the long row\n",
+           (long long)a.rows, (long long)a.cols, (long long)A.nnz, A.plan_spmm.n_long, A.plan_spmm.pieces, T.plan_spmm.n_long, T.plan_spmm.pieces,
+           unsorted, repeats);
+    if (!A.plan_spmm.n_long || T.plan_spmm.n_long < 2 || unsorted < 50 || repeats < 50) return 2;
     const float scale = 0.25f;
     int status = 0;
     double worst = 0.0;

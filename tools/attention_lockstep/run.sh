@@ -1,7 +1,8 @@
 #!/bin/bash
 # tools/attention_lockstep/run.sh -- csrc/kernels_attention.hip executed on the host, a thread per work-item, the lanes of a
 # group in lockstep at every shuffle, under AddressSanitizer and UBSan: forward, backward_q and backward_kv at four (k, kv)
-# on both load paths, rows and pieces on the pattern and on its transpose, every array an exactly sized heap block, against
+# on both load paths, rows and pieces on the pattern (a third of its rows unsorted, a fifth drawn with
+# replacement so that keys repeat) and on its transpose, every array an exactly sized heap block, against
 # a serial fp64 statement of attention (2e-5 of the magnitude); and csrc/kernels_sddmm.hip, built from the same
 # csrc/lane_group.hpp, at the same four k on the same patterns, every out[n] bit for bit against a serial statement of the
 # documented order; and three heads in one launch (the head in blockIdx.y) at the same (k, kv) and load paths, stacked and as
