@@ -69,32 +69,8 @@ SIGNATURES = {
     "spmv_csr_row_softmax_backward": (C.c_int, [_H, C.c_float, _f32p, _f32p, _f32p, _vp]),
     "spmv_csr_attention_plan": (C.c_int, [_H, _vp]),
     "spmv_csr_attention_plan_bytes": (C.c_int64, [_H]),
-    "spmv_csr_attention_forward": (C.c_int, [_H, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, C.c_int, _f32p,
-                                             C.c_int64, _f32p, C.c_int64, _f32p, _vp]),
-    "spmv_csr_attention_backward_q": (C.c_int, [_H, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, C.c_int, _f32p,
-                                                C.c_int64, _f32p, C.c_int64, _f32p, C.c_int64, _f32p, _f32p, _f32p, C.c_int64,
-                                                _vp]),
-    "spmv_csr_attention_backward_kv": (C.c_int, [_H, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, C.c_int, _f32p,
-                                                 C.c_int64, _f32p, C.c_int64, _f32p, _f32p, _f32p, C.c_int64, _f32p, C.c_int64,
-                                                 _vp]),
     "spmv_csr_attention_plan_heads": (C.c_int, [_H, C.c_int, _vp]),
     "spmv_csr_attention_max_heads": (C.c_int, [_H, C.c_int, C.c_int]),
-    "spmv_csr_attention_forward_heads": (C.c_int, [_H, _HS, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, C.c_int,
-                                                   _f32p, C.c_int64, _f32p, C.c_int64, _f32p, _vp]),
-    "spmv_csr_attention_backward_q_heads": (C.c_int, [_H, _HS, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, C.c_int,
-                                                      _f32p, C.c_int64, _f32p, C.c_int64, _f32p, C.c_int64, _f32p, _f32p, _f32p,
-                                                      C.c_int64, _vp]),
-    "spmv_csr_attention_backward_kv_heads": (C.c_int, [_H, _HS, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, C.c_int,
-                                                       _f32p, C.c_int64, _f32p, C.c_int64, _f32p, _f32p, _f32p, C.c_int64, _f32p,
-                                                       C.c_int64, _vp]),
-    "spmv_csr_attention_forward_gqa": (C.c_int, [_H, _HS, C.c_int, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64,
-                                                 C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, _f32p, _vp]),
-    "spmv_csr_attention_backward_q_gqa": (C.c_int, [_H, _HS, C.c_int, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64,
-                                                    C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, _f32p, C.c_int64, _f32p, _f32p,
-                                                    _f32p, C.c_int64, _vp]),
-    "spmv_csr_attention_backward_kv_gqa": (C.c_int, [_H, _HS, C.c_int, C.c_float, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64,
-                                                     C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, _f32p, _f32p, _f32p, C.c_int64,
-                                                     _f32p, C.c_int64, _vp]),
     "spmv_csr_plan_get": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int32)]),
     "spmv_csr_plan_set": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int32), _vp]),
     "spmv_csr_plan_like": (C.c_int, [_H, _H, C.c_int, _vp]),
@@ -131,6 +107,26 @@ SIGNATURES = {
     "spmv_calib_marker": (C.c_int, [C.c_int, _vp]),
     "spmv_debug_bounds": (C.c_int, [_vp, C.c_int]),
 }
+# Fused attention, one description per pass: the operands in C argument order as (name, side of this handle that counts its rows,
+# width, AttnHeads field, whether it holds the K/V heads of a _gqa call).  The width is "k" or "kv" for a matrix, which the C call
+# takes as (pointer, ld); for a vector it is the floats per query, and the C call takes the pointer alone.  `int kv` precedes V.
+_ATTN_PASSES = {
+    "forward": (("Q", "rows", "k", "q", False), ("K", "cols", "k", "k", True), ("V", "cols", "kv", "v", True),
+                ("O", "rows", "kv", "o", False), ("stats", "rows", 2, "stats", False)),
+    "backward_q": (("Q", "rows", "k", "q", False), ("K", "cols", "k", "k", True), ("V", "cols", "kv", "v", True),
+                   ("O", "rows", "kv", "o", False), ("dO", "rows", "kv", "d_o", False), ("stats", "rows", 2, "stats", False),
+                   ("delta", "rows", 1, "delta", False), ("dQ", "rows", "k", "dq", False)),
+    # (on the handle of the transposed pattern: rows = keys, cols = queries)
+    "backward_kv": (("Q", "cols", "k", "q", False), ("K", "rows", "k", "k", True), ("V", "rows", "kv", "v", True),
+                    ("dO", "cols", "kv", "d_o", False), ("stats", "cols", 2, "stats", False), ("delta", "cols", 1, "delta", False),
+                    ("dK", "rows", "k", "dk", True), ("dV", "rows", "kv", "dv", True)),
+}
+_ATTN_MODES = {"one": "", "heads": "_heads", "gqa": "_gqa"}      # the three calls of a pass: the suffix of their names
+for _pass, _ops in _ATTN_PASSES.items():
+    _tail = [a for n, _, w, _, _ in _ops for a in ([C.c_int] if n == "V" else []) + [_f32p] + ([C.c_int64] if isinstance(w, str) else [])]
+    for _mode, _suffix in _ATTN_MODES.items():
+        _head = [_H] + ([_HS] if _mode != "one" else []) + ([C.c_int] if _mode == "gqa" else [])      # handle, hs, group
+        SIGNATURES[f"spmv_csr_attention_{_pass}{_suffix}"] = (C.c_int, _head + [C.c_float, C.c_int] + _tail + [_vp])
 # test only: the bounds-checked build of the library (SPMV_CHECK_BOUNDS) and its sites (csrc/spmv_internal.hpp BoundsSite)
 CHECKED_LIB_PATH = PKG_DIR / "lib" / "libspmv_hip_checked.so"
 BOUNDS_SITES = ("k_bs_sums prod", "k_bs_sums acc", "k_bin_sums prod", "k_bin_sums r16", "k_bs_products c16",
@@ -193,9 +189,9 @@ def _ptr(t) -> int:
     return t.ctypes.data
 
 
-def _width(t):
-    """Columns of a 2-D tensor (None for anything else: the caller's shape check then names it)."""
-    return t.shape[1] if getattr(t, "ndim", 0) == 2 else None
+def _width(t, ndim: int = 2):
+    """Columns (the last extent) of an ndim-D tensor (None for anything else: the caller's shape check then names it)."""
+    return t.shape[ndim - 1] if getattr(t, "ndim", 0) == ndim else None
 
 
 def _stream_handle(stream=None) -> int:
@@ -392,33 +388,16 @@ class CsrMatrix:
     def attention_forward(self, Q, K, V, O, stats, scale: float = 1.0, stream=None) -> None:
         """Enqueue O = softmax_rows(scale * Q K^T at the pattern) V and stats = (row maximum, 1 / row sum) per query.
         Q: (rows, k), K: (cols, k), V: (cols, kv), O: (rows, kv), stats: (rows, 2)."""
-        k, kv = _width(Q), _width(V)
-        self._attention_operands("attention_forward", scale, Q=(Q, self.rows, k), K=(K, self.cols, k), V=(V, self.cols, kv),
-                                 O=(O, self.rows, kv))
-        self._attention_vectors("attention_forward", stats=(stats, 2 * self.rows))
-        check(lib().spmv_csr_attention_forward(self._h, scale, k, _ptr(Q), Q.stride(0), _ptr(K), K.stride(0), kv, _ptr(V),
-                                               V.stride(0), _ptr(O), O.stride(0), _ptr(stats), _stream_handle(stream)))
+        self._attention_call("forward", "one", (Q, K, V, O, stats), scale, stream)
 
     def attention_backward_q(self, Q, K, V, O, dO, stats, delta, dQ, scale: float = 1.0, stream=None) -> None:
         """Enqueue delta[i] = dO[i] . O[i] and dQ; reads the forward call's O and stats.  delta: rows floats, dQ: (rows, k)."""
-        k, kv = _width(Q), _width(V)
-        self._attention_operands("attention_backward_q", scale, Q=(Q, self.rows, k), K=(K, self.cols, k), V=(V, self.cols, kv),
-                                 O=(O, self.rows, kv), dO=(dO, self.rows, kv), dQ=(dQ, self.rows, k))
-        self._attention_vectors("attention_backward_q", stats=(stats, 2 * self.rows), delta=(delta, self.rows))
-        check(lib().spmv_csr_attention_backward_q(self._h, scale, k, _ptr(Q), Q.stride(0), _ptr(K), K.stride(0), kv, _ptr(V),
-                                                  V.stride(0), _ptr(O), O.stride(0), _ptr(dO), dO.stride(0), _ptr(stats),
-                                                  _ptr(delta), _ptr(dQ), dQ.stride(0), _stream_handle(stream)))
+        self._attention_call("backward_q", "one", (Q, K, V, O, dO, stats, delta, dQ), scale, stream)
 
     def attention_backward_kv(self, Q, K, V, dO, stats, delta, dK, dV, scale: float = 1.0, stream=None) -> None:
         """On the handle of the TRANSPOSED pattern (rows = keys, cols = queries): enqueue dK and dV from the forward call's
         stats and backward_q's delta.  Q, dO: (cols, .), K, V, dK, dV: (rows, .)."""
-        k, kv = _width(Q), _width(V)
-        self._attention_operands("attention_backward_kv", scale, Q=(Q, self.cols, k), K=(K, self.rows, k), V=(V, self.rows, kv),
-                                 dO=(dO, self.cols, kv), dK=(dK, self.rows, k), dV=(dV, self.rows, kv))
-        self._attention_vectors("attention_backward_kv", stats=(stats, 2 * self.cols), delta=(delta, self.cols))
-        check(lib().spmv_csr_attention_backward_kv(self._h, scale, k, _ptr(Q), Q.stride(0), _ptr(K), K.stride(0), kv, _ptr(V),
-                                                   V.stride(0), _ptr(dO), dO.stride(0), _ptr(stats), _ptr(delta), _ptr(dK),
-                                                   dK.stride(0), _ptr(dV), dV.stride(0), _stream_handle(stream)))
+        self._attention_call("backward_kv", "one", (Q, K, V, dO, stats, delta, dK, dV), scale, stream)
 
     # -- fused attention, the heads of one pattern in one launch (spmv_csr_attention_*_heads) -----------------------------
     def attention_plan_heads(self, heads: int, stream=None) -> None:
@@ -431,11 +410,6 @@ class CsrMatrix:
         if n < 0:
             check(n)
         return n
-
-    @staticmethod
-    def _head_strides(heads: int, **tensors) -> dict:
-        """stride(0) of every tensor; 0 with one head, where torch's stride of a dimension of size 1 means nothing."""
-        return {n: (t.stride(0) if heads > 1 else 0) for n, t in tensors.items()}
 
     @staticmethod
     def _attention_heads(what: str, scale: float, mats: dict, vecs: dict):
@@ -463,41 +437,16 @@ class CsrMatrix:
     def attention_forward_heads(self, Q, K, V, O, stats, scale: float = 1.0, stream=None) -> None:
         """attention_forward for all heads in one launch per kernel.  Q: (heads, rows, k), K: (heads, cols, k), V: (heads,
         cols, kv), O: (heads, rows, kv), stats: (heads, rows, 2); an input may have stride(0) == 0 (shared by the heads)."""
-        what = "attention_forward_heads"
-        k, kv = (t.shape[2] if getattr(t, "ndim", 0) == 3 else None for t in (Q, V))
-        heads = self._attention_heads(what, scale, dict(Q=(Q, self.rows, k), K=(K, self.cols, k), V=(V, self.cols, kv),
-                                                        O=(O, self.rows, kv)), dict(stats=(stats, self.rows, 2)))
-        hs = AttnHeads(heads=heads, **self._head_strides(heads, q=Q, k=K, v=V, o=O, stats=stats))
-        check(lib().spmv_csr_attention_forward_heads(self._h, C.byref(hs), scale, k, _ptr(Q), Q.stride(1), _ptr(K), K.stride(1),
-                                                     kv, _ptr(V), V.stride(1), _ptr(O), O.stride(1), _ptr(stats),
-                                                     _stream_handle(stream)))
+        self._attention_call("forward", "heads", (Q, K, V, O, stats), scale, stream)
 
     def attention_backward_q_heads(self, Q, K, V, O, dO, stats, delta, dQ, scale: float = 1.0, stream=None) -> None:
         """attention_backward_q for all heads in one launch per kernel; delta: (heads, rows), dQ: (heads, rows, k)."""
-        what = "attention_backward_q_heads"
-        k, kv = (t.shape[2] if getattr(t, "ndim", 0) == 3 else None for t in (Q, V))
-        heads = self._attention_heads(what, scale, dict(Q=(Q, self.rows, k), K=(K, self.cols, k), V=(V, self.cols, kv),
-                                                        O=(O, self.rows, kv), dO=(dO, self.rows, kv), dQ=(dQ, self.rows, k)),
-                                      dict(stats=(stats, self.rows, 2), delta=(delta, self.rows, 1)))
-        hs = AttnHeads(heads=heads, **self._head_strides(heads, q=Q, k=K, v=V, o=O, d_o=dO, stats=stats, delta=delta, dq=dQ))
-        check(lib().spmv_csr_attention_backward_q_heads(self._h, C.byref(hs), scale, k, _ptr(Q), Q.stride(1), _ptr(K), K.stride(1),
-                                                        kv, _ptr(V), V.stride(1), _ptr(O), O.stride(1), _ptr(dO), dO.stride(1),
-                                                        _ptr(stats), _ptr(delta), _ptr(dQ), dQ.stride(1),
-                                                        _stream_handle(stream)))
+        self._attention_call("backward_q", "heads", (Q, K, V, O, dO, stats, delta, dQ), scale, stream)
 
     def attention_backward_kv_heads(self, Q, K, V, dO, stats, delta, dK, dV, scale: float = 1.0, stream=None) -> None:
         """On the handle of the TRANSPOSED pattern: attention_backward_kv for all heads in one launch per kernel.  With a
         shared K or V (stride(0) == 0) dK and dV still come out per head."""
-        what = "attention_backward_kv_heads"
-        k, kv = (t.shape[2] if getattr(t, "ndim", 0) == 3 else None for t in (Q, V))
-        heads = self._attention_heads(what, scale, dict(Q=(Q, self.cols, k), K=(K, self.rows, k), V=(V, self.rows, kv),
-                                                        dO=(dO, self.cols, kv), dK=(dK, self.rows, k), dV=(dV, self.rows, kv)),
-                                      dict(stats=(stats, self.cols, 2), delta=(delta, self.cols, 1)))
-        hs = AttnHeads(heads=heads, **self._head_strides(heads, q=Q, k=K, v=V, d_o=dO, stats=stats, delta=delta, dk=dK, dv=dV))
-        check(lib().spmv_csr_attention_backward_kv_heads(self._h, C.byref(hs), scale, k, _ptr(Q), Q.stride(1), _ptr(K),
-                                                         K.stride(1), kv, _ptr(V), V.stride(1), _ptr(dO), dO.stride(1),
-                                                         _ptr(stats), _ptr(delta), _ptr(dK), dK.stride(1), _ptr(dV),
-                                                         dV.stride(1), _stream_handle(stream)))
+        self._attention_call("backward_kv", "heads", (Q, K, V, dO, stats, delta, dK, dV), scale, stream)
 
     # -- fused attention, grouped-query heads (spmv_csr_attention_*_gqa) ----------------------------------------------------
     @classmethod
@@ -514,46 +463,48 @@ class CsrMatrix:
     def attention_forward_gqa(self, Q, K, V, O, stats, scale: float = 1.0, stream=None) -> None:
         """attention_forward_heads for grouped-query heads (GQA): Q, O: (H, rows, .), stats: (H, rows, 2), K: (H_kv, cols, k),
         V: (H_kv, cols, kv) with H % H_kv == 0; query head y reads K[y // g], V[y // g], g = H // H_kv, without a copy."""
-        what = "attention_forward_gqa"
-        k, kv = (t.shape[2] if getattr(t, "ndim", 0) == 3 else None for t in (Q, V))
-        heads, kv_heads, g = self._attention_gqa(what, scale, dict(Q=(Q, self.rows, k), O=(O, self.rows, kv)),
-                                                 dict(K=(K, self.cols, k), V=(V, self.cols, kv)),
-                                                 dict(stats=(stats, self.rows, 2)))
-        hs = AttnHeads(heads=heads, **self._head_strides(heads, q=Q, o=O, stats=stats), **self._head_strides(kv_heads, k=K, v=V))
-        check(lib().spmv_csr_attention_forward_gqa(self._h, C.byref(hs), g, scale, k, _ptr(Q), Q.stride(1), _ptr(K), K.stride(1),
-                                                   kv, _ptr(V), V.stride(1), _ptr(O), O.stride(1), _ptr(stats),
-                                                   _stream_handle(stream)))
+        self._attention_call("forward", "gqa", (Q, K, V, O, stats), scale, stream)
 
     def attention_backward_q_gqa(self, Q, K, V, O, dO, stats, delta, dQ, scale: float = 1.0, stream=None) -> None:
         """attention_backward_q_heads for grouped-query heads (GQA): K, V hold H_kv heads, everything else H."""
-        what = "attention_backward_q_gqa"
-        k, kv = (t.shape[2] if getattr(t, "ndim", 0) == 3 else None for t in (Q, V))
-        heads, kv_heads, g = self._attention_gqa(what, scale, dict(Q=(Q, self.rows, k), O=(O, self.rows, kv), dO=(dO, self.rows, kv),
-                                                                   dQ=(dQ, self.rows, k)),
-                                                 dict(K=(K, self.cols, k), V=(V, self.cols, kv)),
-                                                 dict(stats=(stats, self.rows, 2), delta=(delta, self.rows, 1)))
-        hs = AttnHeads(heads=heads, **self._head_strides(heads, q=Q, o=O, d_o=dO, stats=stats, delta=delta, dq=dQ),
-                       **self._head_strides(kv_heads, k=K, v=V))
-        check(lib().spmv_csr_attention_backward_q_gqa(self._h, C.byref(hs), g, scale, k, _ptr(Q), Q.stride(1), _ptr(K), K.stride(1),
-                                                      kv, _ptr(V), V.stride(1), _ptr(O), O.stride(1), _ptr(dO), dO.stride(1),
-                                                      _ptr(stats), _ptr(delta), _ptr(dQ), dQ.stride(1), _stream_handle(stream)))
+        self._attention_call("backward_q", "gqa", (Q, K, V, O, dO, stats, delta, dQ), scale, stream)
 
     def attention_backward_kv_gqa(self, Q, K, V, dO, stats, delta, dK, dV, scale: float = 1.0, stream=None) -> None:
         """On the handle of the TRANSPOSED pattern: attention_backward_kv_heads for grouped-query heads (GQA).  K, V, dK, dV:
         (H_kv, rows, .); Q, dO, stats, delta hold H heads.  dK[c], dV[c] are the per-head results of query heads c g .. c g +
         g - 1 added in the kernel in head order, starting from the first head's value."""
-        what = "attention_backward_kv_gqa"
-        k, kv = (t.shape[2] if getattr(t, "ndim", 0) == 3 else None for t in (Q, V))
-        heads, kv_heads, g = self._attention_gqa(what, scale, dict(Q=(Q, self.cols, k), dO=(dO, self.cols, kv)),
-                                                 dict(K=(K, self.rows, k), V=(V, self.rows, kv), dK=(dK, self.rows, k),
-                                                      dV=(dV, self.rows, kv)),
-                                                 dict(stats=(stats, self.cols, 2), delta=(delta, self.cols, 1)))
-        hs = AttnHeads(heads=heads, **self._head_strides(heads, q=Q, d_o=dO, stats=stats, delta=delta),
-                       **self._head_strides(kv_heads, k=K, v=V, dk=dK, dv=dV))
-        check(lib().spmv_csr_attention_backward_kv_gqa(self._h, C.byref(hs), g, scale, k, _ptr(Q), Q.stride(1), _ptr(K),
-                                                       K.stride(1), kv, _ptr(V), V.stride(1), _ptr(dO), dO.stride(1),
-                                                       _ptr(stats), _ptr(delta), _ptr(dK), dK.stride(1), _ptr(dV),
-                                                       dV.stride(1), _stream_handle(stream)))
+        self._attention_call("backward_kv", "gqa", (Q, K, V, dO, stats, delta, dK, dV), scale, stream)
+
+    def _attention_call(self, spec: str, mode: str, tensors, scale: float, stream) -> None:
+        """All nine attention calls: pass `spec` of _ATTN_PASSES in `mode` of _ATTN_MODES on `tensors` in the spec's order."""
+        what, ops = f"attention_{spec}{_ATTN_MODES[mode]}", _ATTN_PASSES[spec]
+        t = dict(zip((o[0] for o in ops), tensors))
+        nd = 2 if mode == "one" else 3                       # a matrix: (rows, width) or (heads, rows, width)
+        width = {"k": _width(t["Q"], nd), "kv": _width(t["V"], nd)}
+        n = {"rows": self.rows, "cols": self.cols}
+        mats = [(name, kvh, (t[name], n[side], width[w])) for name, side, w, _, kvh in ops if isinstance(w, str)]
+        vecs = [(name, t[name], n[side], w) for name, side, w, _, _ in ops if not isinstance(w, str)]
+        if mode == "one":
+            self._attention_operands(what, scale, **{name: m for name, _, m in mats})
+            self._attention_vectors(what, **{name: (v, w * q) for name, v, q, w in vecs})
+            head = []
+        else:
+            vecs = {name: (v, q, w) for name, v, q, w in vecs}
+            if mode == "heads":
+                heads = kv_heads = self._attention_heads(what, scale, {name: m for name, _, m in mats}, vecs)
+                group = []
+            else:
+                heads, kv_heads, g = self._attention_gqa(what, scale, {name: m for name, kvh, m in mats if not kvh},
+                                                         {name: m for name, kvh, m in mats if kvh}, vecs)
+                group = [g]
+            # stride(0) of every tensor; 0 where it holds one head: torch's stride of a dimension of size 1 means nothing
+            hs = AttnHeads(heads=heads, **{f: (t[name].stride(0) if (kv_heads if kvh else heads) > 1 else 0)
+                                           for name, _, _, f, kvh in ops})
+            head = [C.byref(hs)] + group
+        args = []
+        for name, _, w, _, _ in ops:
+            args += ([width["kv"]] if name == "V" else []) + [_ptr(t[name])] + ([t[name].stride(nd - 2)] if isinstance(w, str) else [])
+        check(getattr(lib(), f"spmv_csr_{what}")(self._h, *head, scale, width["k"], *args, _stream_handle(stream)))
 
     def values_changed(self) -> None:
         """The caller rewrote vals (borrowed arrays): plans that hold a copy of them are stale from here on."""

@@ -649,90 +649,6 @@ int64_t spmv_csr_attention_plan_bytes(const spmv_csr_t *h)
     return attention_plan_bytes(*h);
 }
 
-namespace {
-struct AttnOperand {
-    const char *name;
-    const void *p;
-    int64_t ld, n;     // n rows of ld floats, of which `width` are used
-    int width;
-};
-}  // namespace
-
-// what the three attention calls check alike: k, kv, the scale, every matrix (ld, presence, 16-byte alignment, 64-bit
-// byte offsets), the vectors stats (8-byte aligned) and delta (4-byte), the device and the plan
-static int attention_args(const spmv_csr_t *h, float scale, int k, int kv, const AttnOperand *ops, int n_ops, const void *stats,
-                          const void *delta, bool with_delta, int64_t n_queries, const char *what, int heads = 1)
-{
-    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
-    if (k < 1 || k > 64 || kv < 1 || kv > 64) {
-        set_error("%s: k = %d, kv = %d (need 1 <= k <= 64 and 1 <= kv <= 64)", what, k, kv);
-        return SPMV_ERR_INVALID;
-    }
-    if (!(scale - scale == 0.0f)) { set_error("%s: scale must be finite", what); return SPMV_ERR_INVALID; }
-    for (int i = 0; i < n_ops; ++i) {
-        const AttnOperand &o = ops[i];
-        if (o.ld < o.width) { set_error("%s: ld of %s = %lld is below its width %d", what, o.name, (long long)o.ld, o.width); return SPMV_ERR_INVALID; }
-        if (!o.p && o.n > 0) { set_error("%s: null %s", what, o.name); return SPMV_ERR_INVALID; }
-        if (!aligned16(o.p)) { set_error("%s: %s must be 16-byte aligned", what, o.name); return SPMV_ERR_INVALID; }
-        if (o.ld > INT64_MAX / 4 / (o.n > 0 ? o.n : 1)) {
-            set_error("%s: ld of %s = %lld overflows 64-bit byte offsets", what, o.name, (long long)o.ld);
-            return SPMV_ERR_INVALID;
-        }
-    }
-    if (n_queries > 0 && (!stats || (with_delta && !delta))) { set_error("%s: null stats or delta", what); return SPMV_ERR_INVALID; }
-    if (reinterpret_cast<uintptr_t>(stats) % 8 != 0 || reinterpret_cast<uintptr_t>(delta) % 4 != 0) {
-        set_error("%s: stats must be 8-byte aligned and delta 4-byte aligned", what);
-        return SPMV_ERR_INVALID;
-    }
-    if (int rc = require_current(h->device, what)) return rc;
-    if (!h->plan_attn.ready || !h->plan_spmm.ready) { set_error("%s used before spmv_csr_attention_plan", what); return SPMV_ERR_NOT_PLANNED; }
-    if (heads > h->plan_attn.heads) {
-        set_error("%s: %d heads, the plan covers %d (spmv_csr_attention_plan_heads)", what, heads, h->plan_attn.heads);
-        return SPMV_ERR_NOT_PLANNED;
-    }
-    return SPMV_OK;
-}
-
-int spmv_csr_attention_forward(spmv_csr_t *h, float scale, int k, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk,
-                               int kv, const float *d_V, int64_t ldv, float *d_O, int64_t ldo, float *d_stats, void *stream)
-{
-    const char *what = "spmv_csr_attention_forward";
-    const int64_t rows = h ? h->rows : 0, cols = h ? h->cols : 0;
-    const AttnOperand ops[] = {{"Q", d_Q, ldq, rows, k}, {"K", d_K, ldk, cols, k}, {"V", d_V, ldv, cols, kv}, {"O", d_O, ldo, rows, kv}};
-    if (int rc = attention_args(h, scale, k, kv, ops, 4, d_stats, nullptr, false, rows, what)) return rc;
-    return launch_attention_forward(*h, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_O, ldo, d_stats, (hipStream_t)stream);
-}
-
-int spmv_csr_attention_backward_q(spmv_csr_t *h, float scale, int k, const float *d_Q, int64_t ldq, const float *d_K,
-                                  int64_t ldk, int kv, const float *d_V, int64_t ldv, const float *d_O, int64_t ldo,
-                                  const float *d_dO, int64_t lddo, const float *d_stats, float *d_delta, float *d_dQ,
-                                  int64_t lddq, void *stream)
-{
-    const char *what = "spmv_csr_attention_backward_q";
-    const int64_t rows = h ? h->rows : 0, cols = h ? h->cols : 0;
-    const AttnOperand ops[] = {{"Q", d_Q, ldq, rows, k}, {"K", d_K, ldk, cols, k}, {"V", d_V, ldv, cols, kv}, {"O", d_O, ldo, rows, kv},
-                               {"dO", d_dO, lddo, rows, kv}, {"dQ", d_dQ, lddq, rows, k}};
-    if (int rc = attention_args(h, scale, k, kv, ops, 6, d_stats, d_delta, true, rows, what)) return rc;
-    return launch_attention_backward_q(*h, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_O, ldo, d_dO, lddo, d_stats, d_delta,
-                                       d_dQ, lddq, (hipStream_t)stream);
-}
-
-// t is the handle of the TRANSPOSED pattern: t->rows keys, t->cols queries
-int spmv_csr_attention_backward_kv(spmv_csr_t *t, float scale, int k, const float *d_Q, int64_t ldq, const float *d_K,
-                                   int64_t ldk, int kv, const float *d_V, int64_t ldv, const float *d_dO, int64_t lddo,
-                                   const float *d_stats, const float *d_delta, float *d_dK, int64_t lddk, float *d_dV,
-                                   int64_t lddv, void *stream)
-{
-    const char *what = "spmv_csr_attention_backward_kv";
-    const int64_t keys = t ? t->rows : 0, queries = t ? t->cols : 0;
-    const AttnOperand ops[] = {{"Q", d_Q, ldq, queries, k}, {"K", d_K, ldk, keys, k}, {"V", d_V, ldv, keys, kv},
-                               {"dO", d_dO, lddo, queries, kv}, {"dK", d_dK, lddk, keys, k}, {"dV", d_dV, lddv, keys, kv}};
-    if (int rc = attention_args(t, scale, k, kv, ops, 6, d_stats, d_delta, true, queries, what)) return rc;
-    return launch_attention_backward_kv(*t, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_dO, lddo, d_stats, d_delta, d_dK,
-                                        lddk, d_dV, lddv, (hipStream_t)stream);
-}
-
-// ---- fused attention, the heads of one pattern in one launch ------------------------------------------------------------
 int spmv_csr_attention_plan_heads(spmv_csr_t *h, int heads, void *stream)
 {
     const char *what = "spmv_csr_attention_plan_heads";
@@ -742,119 +658,55 @@ int spmv_csr_attention_plan_heads(spmv_csr_t *h, int heads, void *stream)
     return plan_attention_heads(*h, heads, (hipStream_t)stream);
 }
 
-int spmv_csr_attention_max_heads(const spmv_csr_t *h, int k, int kv)
+static int attention_widths(int k, int kv, const char *what)
 {
-    const char *what = "spmv_csr_attention_max_heads";
-    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
     if (k < 1 || k > 64 || kv < 1 || kv > 64) {
         set_error("%s: k = %d, kv = %d (need 1 <= k <= 64 and 1 <= kv <= 64)", what, k, kv);
         return SPMV_ERR_INVALID;
     }
+    return SPMV_OK;
+}
+
+int spmv_csr_attention_max_heads(const spmv_csr_t *h, int k, int kv)
+{
+    const char *what = "spmv_csr_attention_max_heads";
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (int rc = attention_widths(k, kv, what)) return rc;
     if (!h->plan_spmm.ready) { set_error("%s used before spmv_csr_attention_plan", what); return SPMV_ERR_NOT_PLANNED; }
     return attention_max_heads(*h, k > kv ? k : kv);
 }
 
 namespace {
-struct HeadStride {
+// One operand of an attention call, as its checks see it: a matrix of n rows (the queries or the keys) of ld floats, of which
+// `width` (k or kv) are used, or a vector of `width` floats per query (stats: 2, delta: 1; ld unused).
+struct AttnOperand {
     const char *name;
-    int64_t stride;
-    int unit;        // the stride is a multiple of it: 4 for a matrix (16-byte aligned heads), 2 for stats, 1 for delta
-    int out_width;   // of an output: floats a head writes per row (its stride is at least that with heads > 1); 0: an input
-    int heads = 0;   // how many heads the operand holds where that is not the call's (dK and dV of a _gqa call); 0: the call's
+    const void *p;
+    int64_t ld, n;
+    int width;
+    int64_t stride;    // floats from one head to the next
+    int unit;          // the stride is a multiple of it: 4 for a matrix (16-byte aligned heads), 2 for stats, 1 for delta
+    bool out;          // an output: with more than one head its stride is at least its width
+    bool kv_heads;     // it holds the K/V heads (heads / group of them), not the query heads
+    bool vector() const { return unit != 4; }
 };
+constexpr bool kIn = false, kOut = true, kQHeads = false, kKVHeads = true;
+
+// a call of one head is the _heads call on this: one head, every stride 0
+const spmv_attn_heads_t kOneHead = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 }  // namespace
 
-static int attention_heads_header(const spmv_attn_heads_t *hs, const char *what)
+// what the attention calls check before an operand is looked at: the handle, the header of hs and the group (1 for a
+// call that has none)
+static int attention_header(const spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, const char *what)
 {
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
     if (!hs) { set_error("%s: null hs", what); return SPMV_ERR_INVALID; }
     if (hs->heads < 1 || hs->heads > kMaxHeads) {
         set_error("%s: heads = %d (need 1 <= heads <= %d, the launch limit)", what, hs->heads, kMaxHeads);
         return SPMV_ERR_INVALID;
     }
     if (hs->reserved != 0) { set_error("%s: reserved = %d (must be 0)", what, hs->reserved); return SPMV_ERR_INVALID; }
-    return SPMV_OK;
-}
-
-static int attention_heads_strides(int heads, const HeadStride *st, int n, const char *what)
-{
-    for (int i = 0; i < n; ++i) {
-        const HeadStride &o = st[i];
-        if (o.stride < 0) { set_error("%s: head stride of %s = %lld is negative", what, o.name, (long long)o.stride); return SPMV_ERR_INVALID; }
-        if (o.stride % o.unit != 0) {
-            set_error("%s: head stride of %s = %lld is no multiple of %d", what, o.name, (long long)o.stride, o.unit);
-            return SPMV_ERR_INVALID;
-        }
-        if ((o.heads ? o.heads : heads) > 1 && o.stride < o.out_width) {
-            set_error("%s: head stride of the output %s = %lld is below its width %d", what, o.name, (long long)o.stride, o.out_width);
-            return SPMV_ERR_INVALID;
-        }
-        if (o.stride > INT64_MAX / 4 / heads) {
-            set_error("%s: head stride of %s = %lld overflows 64-bit byte offsets", what, o.name, (long long)o.stride);
-            return SPMV_ERR_INVALID;
-        }
-    }
-    return SPMV_OK;
-}
-
-int spmv_csr_attention_forward_heads(spmv_csr_t *h, const spmv_attn_heads_t *hs, float scale, int k, const float *d_Q,
-                                     int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V, int64_t ldv,
-                                     float *d_O, int64_t ldo, float *d_stats, void *stream)
-{
-    const char *what = "spmv_csr_attention_forward_heads";
-    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
-    if (int rc = attention_heads_header(hs, what)) return rc;
-    const HeadStride st[] = {{"Q", hs->q, 4, 0}, {"K", hs->k, 4, 0}, {"V", hs->v, 4, 0}, {"O", hs->o, 4, kv}, {"stats", hs->stats, 2, 2}};
-    if (int rc = attention_heads_strides(hs->heads, st, 5, what)) return rc;
-    const int64_t rows = h->rows, cols = h->cols;
-    const AttnOperand ops[] = {{"Q", d_Q, ldq, rows, k}, {"K", d_K, ldk, cols, k}, {"V", d_V, ldv, cols, kv}, {"O", d_O, ldo, rows, kv}};
-    if (int rc = attention_args(h, scale, k, kv, ops, 4, d_stats, nullptr, false, rows, what, hs->heads)) return rc;
-    return launch_attention_forward_heads(*h, *hs, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_O, ldo, d_stats, what,
-                                          (hipStream_t)stream);
-}
-
-int spmv_csr_attention_backward_q_heads(spmv_csr_t *h, const spmv_attn_heads_t *hs, float scale, int k, const float *d_Q,
-                                        int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V, int64_t ldv,
-                                        const float *d_O, int64_t ldo, const float *d_dO, int64_t lddo, const float *d_stats,
-                                        float *d_delta, float *d_dQ, int64_t lddq, void *stream)
-{
-    const char *what = "spmv_csr_attention_backward_q_heads";
-    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
-    if (int rc = attention_heads_header(hs, what)) return rc;
-    const HeadStride st[] = {{"Q", hs->q, 4, 0}, {"K", hs->k, 4, 0}, {"V", hs->v, 4, 0}, {"O", hs->o, 4, 0}, {"dO", hs->d_o, 4, 0},
-                             {"stats", hs->stats, 2, 0}, {"delta", hs->delta, 1, 1}, {"dQ", hs->dq, 4, k}};
-    if (int rc = attention_heads_strides(hs->heads, st, 8, what)) return rc;
-    const int64_t rows = h->rows, cols = h->cols;
-    const AttnOperand ops[] = {{"Q", d_Q, ldq, rows, k}, {"K", d_K, ldk, cols, k}, {"V", d_V, ldv, cols, kv}, {"O", d_O, ldo, rows, kv},
-                               {"dO", d_dO, lddo, rows, kv}, {"dQ", d_dQ, lddq, rows, k}};
-    if (int rc = attention_args(h, scale, k, kv, ops, 6, d_stats, d_delta, true, rows, what, hs->heads)) return rc;
-    return launch_attention_backward_q_heads(*h, *hs, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_O, ldo, d_dO, lddo, d_stats,
-                                             d_delta, d_dQ, lddq, what, (hipStream_t)stream);
-}
-
-// t is the handle of the TRANSPOSED pattern: t->rows keys, t->cols queries
-int spmv_csr_attention_backward_kv_heads(spmv_csr_t *t, const spmv_attn_heads_t *hs, float scale, int k, const float *d_Q,
-                                         int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V, int64_t ldv,
-                                         const float *d_dO, int64_t lddo, const float *d_stats, const float *d_delta,
-                                         float *d_dK, int64_t lddk, float *d_dV, int64_t lddv, void *stream)
-{
-    const char *what = "spmv_csr_attention_backward_kv_heads";
-    if (!t) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
-    if (int rc = attention_heads_header(hs, what)) return rc;
-    const HeadStride st[] = {{"Q", hs->q, 4, 0}, {"K", hs->k, 4, 0}, {"V", hs->v, 4, 0}, {"dO", hs->d_o, 4, 0}, {"stats", hs->stats, 2, 0},
-                             {"delta", hs->delta, 1, 0}, {"dK", hs->dk, 4, k}, {"dV", hs->dv, 4, kv}};
-    if (int rc = attention_heads_strides(hs->heads, st, 8, what)) return rc;
-    const int64_t keys = t->rows, queries = t->cols;
-    const AttnOperand ops[] = {{"Q", d_Q, ldq, queries, k}, {"K", d_K, ldk, keys, k}, {"V", d_V, ldv, keys, kv},
-                               {"dO", d_dO, lddo, queries, kv}, {"dK", d_dK, lddk, keys, k}, {"dV", d_dV, lddv, keys, kv}};
-    if (int rc = attention_args(t, scale, k, kv, ops, 6, d_stats, d_delta, true, queries, what, hs->heads)) return rc;
-    return launch_attention_backward_kv_heads(*t, *hs, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_dO, lddo, d_stats, d_delta,
-                                              d_dK, lddk, d_dV, lddv, what, (hipStream_t)stream);
-}
-
-// ---- fused attention, grouped-query heads: hs->heads query heads, `group` of them per K/V head ------------------------------
-static int attention_gqa_header(const spmv_attn_heads_t *hs, int group, const char *what)
-{
-    if (int rc = attention_heads_header(hs, what)) return rc;
     if (group < 1) { set_error("%s: group = %d (need group >= 1)", what, group); return SPMV_ERR_INVALID; }
     if (hs->heads % group != 0) {
         set_error("%s: heads = %d is no multiple of group = %d", what, hs->heads, group);
@@ -863,20 +715,178 @@ static int attention_gqa_header(const spmv_attn_heads_t *hs, int group, const ch
     return SPMV_OK;
 }
 
+// and after it, in this order: every head stride (they read k and kv as given); k and kv; the scale; every matrix (ld,
+// presence, 16-byte alignment, 64-bit byte offsets); the vectors (presence, then stats 8-byte and delta 4-byte aligned); the
+// device; the plan and the heads it covers
+static int attention_operands(const spmv_csr_t *h, int heads, int group, float scale, int k, int kv, const AttnOperand *ops, size_t n_ops,
+                              const char *what)
+{
+    for (size_t i = 0; i < n_ops; ++i) {
+        const AttnOperand &o = ops[i];
+        if (o.stride < 0) { set_error("%s: head stride of %s = %lld is negative", what, o.name, (long long)o.stride); return SPMV_ERR_INVALID; }
+        if (o.stride % o.unit != 0) {
+            set_error("%s: head stride of %s = %lld is no multiple of %d", what, o.name, (long long)o.stride, o.unit);
+            return SPMV_ERR_INVALID;
+        }
+        if (o.out && (o.kv_heads ? heads / group : heads) > 1 && o.stride < o.width) {
+            set_error("%s: head stride of the output %s = %lld is below its width %d", what, o.name, (long long)o.stride, o.width);
+            return SPMV_ERR_INVALID;
+        }
+        if (o.stride > INT64_MAX / 4 / heads) {
+            set_error("%s: head stride of %s = %lld overflows 64-bit byte offsets", what, o.name, (long long)o.stride);
+            return SPMV_ERR_INVALID;
+        }
+    }
+    if (int rc = attention_widths(k, kv, what)) return rc;
+    if (!(scale - scale == 0.0f)) { set_error("%s: scale must be finite", what); return SPMV_ERR_INVALID; }
+    for (size_t i = 0; i < n_ops; ++i) {
+        const AttnOperand &o = ops[i];
+        if (o.vector()) continue;
+        if (o.ld < o.width) { set_error("%s: ld of %s = %lld is below its width %d", what, o.name, (long long)o.ld, o.width); return SPMV_ERR_INVALID; }
+        if (!o.p && o.n > 0) { set_error("%s: null %s", what, o.name); return SPMV_ERR_INVALID; }
+        if (!aligned16(o.p)) { set_error("%s: %s must be 16-byte aligned", what, o.name); return SPMV_ERR_INVALID; }
+        if (o.ld > INT64_MAX / 4 / (o.n > 0 ? o.n : 1)) {
+            set_error("%s: ld of %s = %lld overflows 64-bit byte offsets", what, o.name, (long long)o.ld);
+            return SPMV_ERR_INVALID;
+        }
+    }
+    for (size_t i = 0; i < n_ops; ++i)
+        if (ops[i].vector() && !ops[i].p && ops[i].n > 0) { set_error("%s: null stats or delta", what); return SPMV_ERR_INVALID; }
+    for (size_t i = 0; i < n_ops; ++i)
+        if (ops[i].vector() && reinterpret_cast<uintptr_t>(ops[i].p) % (4 * ops[i].unit) != 0) {
+            set_error("%s: stats must be 8-byte aligned and delta 4-byte aligned", what);
+            return SPMV_ERR_INVALID;
+        }
+    if (int rc = require_current(h->device, what)) return rc;
+    if (!h->plan_attn.ready || !h->plan_spmm.ready) { set_error("%s used before spmv_csr_attention_plan", what); return SPMV_ERR_NOT_PLANNED; }
+    if (heads > h->plan_attn.heads) {
+        set_error("%s: %d heads, the plan covers %d (spmv_csr_attention_plan_heads)", what, heads, h->plan_attn.heads);
+        return SPMV_ERR_NOT_PLANNED;
+    }
+    return SPMV_OK;
+}
+
+// The three passes.  Each is all nine entry points of its pass: hs->heads query heads, `group` of them per K/V head;
+// sum_group: backward_kv adds the heads of a group in the kernel (the _gqa call).
+static int attention_forward(const char *what, spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, bool sum_group, float scale,
+                             int k, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V,
+                             int64_t ldv, float *d_O, int64_t ldo, float *d_stats, void *stream)
+{
+    if (int rc = attention_header(h, hs, group, what)) return rc;
+    const int64_t rows = h->rows, cols = h->cols;
+    const AttnOperand ops[] = {{"Q", d_Q, ldq, rows, k, hs->q, 4, kIn, kQHeads}, {"K", d_K, ldk, cols, k, hs->k, 4, kIn, kKVHeads},
+                               {"V", d_V, ldv, cols, kv, hs->v, 4, kIn, kKVHeads}, {"O", d_O, ldo, rows, kv, hs->o, 4, kOut, kQHeads},
+                               {"stats", d_stats, 0, rows, 2, hs->stats, 2, kOut, kQHeads}};
+    if (int rc = attention_operands(h, hs->heads, group, scale, k, kv, ops, sizeof ops / sizeof *ops, what)) return rc;
+    AttnArgs a{};
+    a.scale = scale, a.k = k, a.kv = kv;
+    a.Q = d_Q, a.ldq = ldq, a.hq = hs->q, a.K = d_K, a.ldk = ldk, a.hk = hs->k, a.V = d_V, a.ldv = ldv, a.hv = hs->v;
+    a.out0 = d_O, a.ld0 = ldo, a.h0 = hs->o, a.stats = d_stats, a.hstats = hs->stats;
+    return launch_attention(kPassForward, *h, a, hs->heads, group, sum_group, what, (hipStream_t)stream);
+}
+
+static int attention_backward_q(const char *what, spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, bool sum_group, float scale,
+                                int k, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V,
+                                int64_t ldv, const float *d_O, int64_t ldo, const float *d_dO, int64_t lddo, const float *d_stats,
+                                float *d_delta, float *d_dQ, int64_t lddq, void *stream)
+{
+    if (int rc = attention_header(h, hs, group, what)) return rc;
+    const int64_t rows = h->rows, cols = h->cols;
+    const AttnOperand ops[] = {{"Q", d_Q, ldq, rows, k, hs->q, 4, kIn, kQHeads}, {"K", d_K, ldk, cols, k, hs->k, 4, kIn, kKVHeads},
+                               {"V", d_V, ldv, cols, kv, hs->v, 4, kIn, kKVHeads}, {"O", d_O, ldo, rows, kv, hs->o, 4, kIn, kQHeads},
+                               {"dO", d_dO, lddo, rows, kv, hs->d_o, 4, kIn, kQHeads}, {"stats", d_stats, 0, rows, 2, hs->stats, 2, kIn, kQHeads},
+                               {"delta", d_delta, 0, rows, 1, hs->delta, 1, kOut, kQHeads}, {"dQ", d_dQ, lddq, rows, k, hs->dq, 4, kOut, kQHeads}};
+    if (int rc = attention_operands(h, hs->heads, group, scale, k, kv, ops, sizeof ops / sizeof *ops, what)) return rc;
+    AttnArgs a{};
+    a.scale = scale, a.k = k, a.kv = kv;
+    a.Q = d_Q, a.ldq = ldq, a.hq = hs->q, a.K = d_K, a.ldk = ldk, a.hk = hs->k, a.V = d_V, a.ldv = ldv, a.hv = hs->v;
+    a.O = d_O, a.ldo = ldo, a.ho = hs->o, a.dO = d_dO, a.lddo = lddo, a.hdo = hs->d_o;
+    a.stats_in = d_stats, a.hstats_in = hs->stats, a.delta = d_delta, a.hdelta = hs->delta, a.out0 = d_dQ, a.ld0 = lddq, a.h0 = hs->dq;
+    return launch_attention(kPassBackwardQ, *h, a, hs->heads, group, sum_group, what, (hipStream_t)stream);
+}
+
+// t is the handle of the TRANSPOSED pattern: t->rows keys, t->cols queries.  dK and dV hold the K/V heads (the output-stride
+// rule counts those).
+static int attention_backward_kv(const char *what, spmv_csr_t *t, const spmv_attn_heads_t *hs, int group, bool sum_group, float scale,
+                                 int k, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V,
+                                 int64_t ldv, const float *d_dO, int64_t lddo, const float *d_stats, const float *d_delta,
+                                 float *d_dK, int64_t lddk, float *d_dV, int64_t lddv, void *stream)
+{
+    if (int rc = attention_header(t, hs, group, what)) return rc;
+    const int64_t keys = t->rows, queries = t->cols;
+    const AttnOperand ops[] = {{"Q", d_Q, ldq, queries, k, hs->q, 4, kIn, kQHeads}, {"K", d_K, ldk, keys, k, hs->k, 4, kIn, kKVHeads},
+                               {"V", d_V, ldv, keys, kv, hs->v, 4, kIn, kKVHeads}, {"dO", d_dO, lddo, queries, kv, hs->d_o, 4, kIn, kQHeads},
+                               {"stats", d_stats, 0, queries, 2, hs->stats, 2, kIn, kQHeads},
+                               {"delta", d_delta, 0, queries, 1, hs->delta, 1, kIn, kQHeads}, {"dK", d_dK, lddk, keys, k, hs->dk, 4, kOut, kKVHeads},
+                               {"dV", d_dV, lddv, keys, kv, hs->dv, 4, kOut, kKVHeads}};
+    if (int rc = attention_operands(t, hs->heads, group, scale, k, kv, ops, sizeof ops / sizeof *ops, what)) return rc;
+    AttnArgs a{};
+    a.scale = scale, a.k = k, a.kv = kv;
+    a.Q = d_Q, a.ldq = ldq, a.hq = hs->q, a.K = d_K, a.ldk = ldk, a.hk = hs->k, a.V = d_V, a.ldv = ldv, a.hv = hs->v;
+    a.dO = d_dO, a.lddo = lddo, a.hdo = hs->d_o;
+    a.stats_in = d_stats, a.hstats_in = hs->stats, a.delta_in = d_delta, a.hdelta_in = hs->delta;
+    a.out0 = d_dK, a.ld0 = lddk, a.h0 = hs->dk, a.out1 = d_dV, a.ld1 = lddv, a.h1 = hs->dv;
+    return launch_attention(kPassBackwardKV, *t, a, hs->heads, group, sum_group, what, (hipStream_t)stream);
+}
+
+// ---- the nine entry points: one head (kOneHead), the heads of one pattern in one launch, grouped-query heads ----------------
+int spmv_csr_attention_forward(spmv_csr_t *h, float scale, int k, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk,
+                               int kv, const float *d_V, int64_t ldv, float *d_O, int64_t ldo, float *d_stats, void *stream)
+{
+    return attention_forward("spmv_csr_attention_forward", h, &kOneHead, 1, false, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_O, ldo,
+                             d_stats, stream);
+}
+
+int spmv_csr_attention_backward_q(spmv_csr_t *h, float scale, int k, const float *d_Q, int64_t ldq, const float *d_K,
+                                  int64_t ldk, int kv, const float *d_V, int64_t ldv, const float *d_O, int64_t ldo,
+                                  const float *d_dO, int64_t lddo, const float *d_stats, float *d_delta, float *d_dQ,
+                                  int64_t lddq, void *stream)
+{
+    return attention_backward_q("spmv_csr_attention_backward_q", h, &kOneHead, 1, false, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_O,
+                                ldo, d_dO, lddo, d_stats, d_delta, d_dQ, lddq, stream);
+}
+
+int spmv_csr_attention_backward_kv(spmv_csr_t *t, float scale, int k, const float *d_Q, int64_t ldq, const float *d_K,
+                                   int64_t ldk, int kv, const float *d_V, int64_t ldv, const float *d_dO, int64_t lddo,
+                                   const float *d_stats, const float *d_delta, float *d_dK, int64_t lddk, float *d_dV,
+                                   int64_t lddv, void *stream)
+{
+    return attention_backward_kv("spmv_csr_attention_backward_kv", t, &kOneHead, 1, false, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv,
+                                 d_dO, lddo, d_stats, d_delta, d_dK, lddk, d_dV, lddv, stream);
+}
+
+int spmv_csr_attention_forward_heads(spmv_csr_t *h, const spmv_attn_heads_t *hs, float scale, int k, const float *d_Q,
+                                     int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V, int64_t ldv,
+                                     float *d_O, int64_t ldo, float *d_stats, void *stream)
+{
+    return attention_forward("spmv_csr_attention_forward_heads", h, hs, 1, false, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_O, ldo,
+                             d_stats, stream);
+}
+
+int spmv_csr_attention_backward_q_heads(spmv_csr_t *h, const spmv_attn_heads_t *hs, float scale, int k, const float *d_Q,
+                                        int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V, int64_t ldv,
+                                        const float *d_O, int64_t ldo, const float *d_dO, int64_t lddo, const float *d_stats,
+                                        float *d_delta, float *d_dQ, int64_t lddq, void *stream)
+{
+    return attention_backward_q("spmv_csr_attention_backward_q_heads", h, hs, 1, false, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_O,
+                                ldo, d_dO, lddo, d_stats, d_delta, d_dQ, lddq, stream);
+}
+
+int spmv_csr_attention_backward_kv_heads(spmv_csr_t *t, const spmv_attn_heads_t *hs, float scale, int k, const float *d_Q,
+                                         int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V, int64_t ldv,
+                                         const float *d_dO, int64_t lddo, const float *d_stats, const float *d_delta,
+                                         float *d_dK, int64_t lddk, float *d_dV, int64_t lddv, void *stream)
+{
+    return attention_backward_kv("spmv_csr_attention_backward_kv_heads", t, hs, 1, false, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv,
+                                 d_dO, lddo, d_stats, d_delta, d_dK, lddk, d_dV, lddv, stream);
+}
+
 int spmv_csr_attention_forward_gqa(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, float scale, int k, const float *d_Q,
                                    int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V, int64_t ldv,
                                    float *d_O, int64_t ldo, float *d_stats, void *stream)
 {
-    const char *what = "spmv_csr_attention_forward_gqa";
-    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
-    if (int rc = attention_gqa_header(hs, group, what)) return rc;
-    const HeadStride st[] = {{"Q", hs->q, 4, 0}, {"K", hs->k, 4, 0}, {"V", hs->v, 4, 0}, {"O", hs->o, 4, kv}, {"stats", hs->stats, 2, 2}};
-    if (int rc = attention_heads_strides(hs->heads, st, 5, what)) return rc;
-    const int64_t rows = h->rows, cols = h->cols;
-    const AttnOperand ops[] = {{"Q", d_Q, ldq, rows, k}, {"K", d_K, ldk, cols, k}, {"V", d_V, ldv, cols, kv}, {"O", d_O, ldo, rows, kv}};
-    if (int rc = attention_args(h, scale, k, kv, ops, 4, d_stats, nullptr, false, rows, what, hs->heads)) return rc;
-    return launch_attention_forward_gqa(*h, *hs, group, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_O, ldo, d_stats, what,
-                                        (hipStream_t)stream);
+    return attention_forward("spmv_csr_attention_forward_gqa", h, hs, group, false, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_O, ldo,
+                             d_stats, stream);
 }
 
 int spmv_csr_attention_backward_q_gqa(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, float scale, int k,
@@ -884,39 +894,17 @@ int spmv_csr_attention_backward_q_gqa(spmv_csr_t *h, const spmv_attn_heads_t *hs
                                       int64_t ldv, const float *d_O, int64_t ldo, const float *d_dO, int64_t lddo,
                                       const float *d_stats, float *d_delta, float *d_dQ, int64_t lddq, void *stream)
 {
-    const char *what = "spmv_csr_attention_backward_q_gqa";
-    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
-    if (int rc = attention_gqa_header(hs, group, what)) return rc;
-    const HeadStride st[] = {{"Q", hs->q, 4, 0}, {"K", hs->k, 4, 0}, {"V", hs->v, 4, 0}, {"O", hs->o, 4, 0}, {"dO", hs->d_o, 4, 0},
-                             {"stats", hs->stats, 2, 0}, {"delta", hs->delta, 1, 1}, {"dQ", hs->dq, 4, k}};
-    if (int rc = attention_heads_strides(hs->heads, st, 8, what)) return rc;
-    const int64_t rows = h->rows, cols = h->cols;
-    const AttnOperand ops[] = {{"Q", d_Q, ldq, rows, k}, {"K", d_K, ldk, cols, k}, {"V", d_V, ldv, cols, kv}, {"O", d_O, ldo, rows, kv},
-                               {"dO", d_dO, lddo, rows, kv}, {"dQ", d_dQ, lddq, rows, k}};
-    if (int rc = attention_args(h, scale, k, kv, ops, 6, d_stats, d_delta, true, rows, what, hs->heads)) return rc;
-    return launch_attention_backward_q_gqa(*h, *hs, group, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_O, ldo, d_dO, lddo,
-                                           d_stats, d_delta, d_dQ, lddq, what, (hipStream_t)stream);
+    return attention_backward_q("spmv_csr_attention_backward_q_gqa", h, hs, group, false, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_O,
+                                ldo, d_dO, lddo, d_stats, d_delta, d_dQ, lddq, stream);
 }
 
-// t is the handle of the TRANSPOSED pattern; dK and dV hold heads / group heads (the output-stride rule counts those)
 int spmv_csr_attention_backward_kv_gqa(spmv_csr_t *t, const spmv_attn_heads_t *hs, int group, float scale, int k,
                                        const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V,
                                        int64_t ldv, const float *d_dO, int64_t lddo, const float *d_stats, const float *d_delta,
                                        float *d_dK, int64_t lddk, float *d_dV, int64_t lddv, void *stream)
 {
-    const char *what = "spmv_csr_attention_backward_kv_gqa";
-    if (!t) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
-    if (int rc = attention_gqa_header(hs, group, what)) return rc;
-    const int kv_heads = hs->heads / group;
-    const HeadStride st[] = {{"Q", hs->q, 4, 0}, {"K", hs->k, 4, 0}, {"V", hs->v, 4, 0}, {"dO", hs->d_o, 4, 0}, {"stats", hs->stats, 2, 0},
-                             {"delta", hs->delta, 1, 0}, {"dK", hs->dk, 4, k, kv_heads}, {"dV", hs->dv, 4, kv, kv_heads}};
-    if (int rc = attention_heads_strides(hs->heads, st, 8, what)) return rc;
-    const int64_t keys = t->rows, queries = t->cols;
-    const AttnOperand ops[] = {{"Q", d_Q, ldq, queries, k}, {"K", d_K, ldk, keys, k}, {"V", d_V, ldv, keys, kv},
-                               {"dO", d_dO, lddo, queries, kv}, {"dK", d_dK, lddk, keys, k}, {"dV", d_dV, lddv, keys, kv}};
-    if (int rc = attention_args(t, scale, k, kv, ops, 6, d_stats, d_delta, true, queries, what, hs->heads)) return rc;
-    return launch_attention_backward_kv_gqa(*t, *hs, group, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv, d_dO, lddo, d_stats,
-                                            d_delta, d_dK, lddk, d_dV, lddv, what, (hipStream_t)stream);
+    return attention_backward_kv("spmv_csr_attention_backward_kv_gqa", t, hs, group, true, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv,
+                                 d_dO, lddo, d_stats, d_delta, d_dK, lddk, d_dV, lddv, stream);
 }
 
 int spmv_csr_values_changed(spmv_csr_t *h)

@@ -57,26 +57,6 @@ constexpr int kAtSlots = 132;     // floats of scratch per piece
 constexpr int kAtSums = 4;        // where a piece's partial sums start (16-byte aligned)
 constexpr int kAtSums2 = 68;      // the second set of backward_kv (dV)
 
-// the operands of the three passes (by value; a pass reads what it needs)
-struct AttnArgs {
-    float scale;
-    int k, kv;
-    const float *Q;   int64_t ldq;
-    const float *K;   int64_t ldk;
-    const float *V;   int64_t ldv;
-    const float *O;   int64_t ldo;     // backward_q
-    const float *dO;  int64_t lddo;    // backward
-    const float *stats_in;             // backward
-    const float *delta_in;             // backward_kv
-    float *out0;      int64_t ld0;     // forward O; backward_q dQ; backward_kv dK
-    float *out1;      int64_t ld1;     // backward_kv dV
-    float *stats;                      // forward
-    float *delta;                      // backward_q
-    // floats from head y to head y + 1 of every operand above (all 0 in a call of one head); hk, hv (and in backward_kv h0,
-    // h1): from one K/V head to the next
-    int64_t hq, hk, hv, ho, hdo, hstats_in, hdelta_in, h0, h1, hstats, hdelta;
-};
-
 // the query head of the block: blockIdx.y within its group of gridDim.y heads, the group (= the K/V head) in blockIdx.z
 __device__ __forceinline__ int64_t query_head() { return (int64_t)blockIdx.z * gridDim.y + blockIdx.y; }
 
@@ -618,8 +598,6 @@ __global__ __launch_bounds__(kBlock) void k_attn_add_pieces_gqa(GroupPieces g, i
     store_slice<VEC>(out + c * hout + (int64_t)g.long_row[i] * ld + c0, acc, c0, w);
 }
 
-enum { kPassForward = 0, kPassBackwardQ = 1, kPassBackwardKV = 2 };
-
 // one grid per kernel for all heads: x is what a call of one head launches, y the query head within its group of `group`, z
 // the group (the K/V head); group = 1 for the _heads calls.  gqa (backward_kv only): the _gqa call, which sums the heads of a
 // group (k_attn_bwd_kv_rows_gqa, k_attn_add_pieces_gqa; also at group = 1).
@@ -687,8 +665,6 @@ bool vec4(std::initializer_list<int64_t> lds)
     return true;
 }
 
-const spmv_attn_heads_t kOneHead = {1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-
 }  // namespace
 
 // The attention plan: the SpMM plan (made here if it is missing) and the scratch of the long rows' pieces, a slice of
@@ -720,103 +696,20 @@ int attention_max_heads(const spmv_csr &h, int width)
     return dispatch_lanes((width + 3) / 4, [&](auto v) { return (int)group_max_heads(h, decltype(v)::value); });
 }
 
-// arguments checked by the callers in capi.hip; hs: the heads of the call and the strides of the operands it takes
-int launch_attention_forward_gqa(const spmv_csr &h, const spmv_attn_heads_t &hs, int group, float scale, int k, const float *Q,
-                                 int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv, float *O,
-                                 int64_t ldo, float *stats, const char *what, hipStream_t s)
+// One call of any of the nine entry points (arguments checked by capi.hip, which also fills `a`): `heads` query heads, `group`
+// of them per K/V head (1 for the _heads calls and a call of one head).  sum_group (backward_kv only): a _gqa call, which sums the
+// heads of a group in the kernel, at group = 1 too.  The 16-byte load path needs every ld the pass uses to be a multiple of 4.
+int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgs &a, int heads, int group, bool sum_group, const char *what,
+                     hipStream_t s)
 {
-    AttnArgs a{};
-    a.scale = scale, a.k = k, a.kv = kv;
-    a.Q = Q, a.ldq = ldq, a.K = K, a.ldk = ldk, a.V = V, a.ldv = ldv;
-    a.out0 = O, a.ld0 = ldo, a.stats = stats;
-    a.hq = hs.q, a.hk = hs.k, a.hv = hs.v, a.h0 = hs.o, a.hstats = hs.stats;
-    return launch_attn<kPassForward>(h, a, hs.heads, group, false, vec4({ldq, ldk, ldv, ldo}), what, s);
-}
-
-int launch_attention_forward_heads(const spmv_csr &h, const spmv_attn_heads_t &hs, float scale, int k, const float *Q,
-                                   int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv, float *O,
-                                   int64_t ldo, float *stats, const char *what, hipStream_t s)
-{
-    return launch_attention_forward_gqa(h, hs, 1, scale, k, Q, ldq, K, ldk, kv, V, ldv, O, ldo, stats, what, s);
-}
-
-int launch_attention_backward_q_gqa(const spmv_csr &h, const spmv_attn_heads_t &hs, int group, float scale, int k, const float *Q,
-                                    int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv,
-                                    const float *O, int64_t ldo, const float *dO, int64_t lddo, const float *stats,
-                                    float *delta, float *dQ, int64_t lddq, const char *what, hipStream_t s)
-{
-    AttnArgs a{};
-    a.scale = scale, a.k = k, a.kv = kv;
-    a.Q = Q, a.ldq = ldq, a.K = K, a.ldk = ldk, a.V = V, a.ldv = ldv, a.O = O, a.ldo = ldo, a.dO = dO, a.lddo = lddo;
-    a.stats_in = stats, a.delta = delta, a.out0 = dQ, a.ld0 = lddq;
-    a.hq = hs.q, a.hk = hs.k, a.hv = hs.v, a.ho = hs.o, a.hdo = hs.d_o, a.hstats_in = hs.stats, a.hdelta = hs.delta, a.h0 = hs.dq;
-    return launch_attn<kPassBackwardQ>(h, a, hs.heads, group, false, vec4({ldq, ldk, ldv, ldo, lddo, lddq}), what, s);
-}
-
-int launch_attention_backward_q_heads(const spmv_csr &h, const spmv_attn_heads_t &hs, float scale, int k, const float *Q,
-                                      int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv,
-                                      const float *O, int64_t ldo, const float *dO, int64_t lddo, const float *stats,
-                                      float *delta, float *dQ, int64_t lddq, const char *what, hipStream_t s)
-{
-    return launch_attention_backward_q_gqa(h, hs, 1, scale, k, Q, ldq, K, ldk, kv, V, ldv, O, ldo, dO, lddo, stats, delta, dQ,
-                                           lddq, what, s);
-}
-
-// group >= 1: the _gqa call (k_attn_bwd_kv_rows_gqa and k_attn_add_pieces_gqa, also at group = 1); 0: the _heads call
-static int backward_kv_launch(const spmv_csr &t, const spmv_attn_heads_t &hs, int group, float scale, int k, const float *Q,
-                              int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv, const float *dO,
-                              int64_t lddo, const float *stats, const float *delta, float *dK, int64_t lddk, float *dV,
-                              int64_t lddv, const char *what, hipStream_t s)
-{
-    AttnArgs a{};
-    a.scale = scale, a.k = k, a.kv = kv;
-    a.Q = Q, a.ldq = ldq, a.K = K, a.ldk = ldk, a.V = V, a.ldv = ldv, a.dO = dO, a.lddo = lddo;
-    a.stats_in = stats, a.delta_in = delta, a.out0 = dK, a.ld0 = lddk, a.out1 = dV, a.ld1 = lddv;
-    a.hq = hs.q, a.hk = hs.k, a.hv = hs.v, a.hdo = hs.d_o, a.hstats_in = hs.stats, a.hdelta_in = hs.delta, a.h0 = hs.dk, a.h1 = hs.dv;
-    return launch_attn<kPassBackwardKV>(t, a, hs.heads, group ? group : 1, group > 0, vec4({ldq, ldk, ldv, lddo, lddk, lddv}), what,
-                                        s);
-}
-
-int launch_attention_backward_kv_heads(const spmv_csr &t, const spmv_attn_heads_t &hs, float scale, int k, const float *Q,
-                                       int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv,
-                                       const float *dO, int64_t lddo, const float *stats, const float *delta, float *dK,
-                                       int64_t lddk, float *dV, int64_t lddv, const char *what, hipStream_t s)
-{
-    return backward_kv_launch(t, hs, 0, scale, k, Q, ldq, K, ldk, kv, V, ldv, dO, lddo, stats, delta, dK, lddk, dV, lddv, what, s);
-}
-
-int launch_attention_backward_kv_gqa(const spmv_csr &t, const spmv_attn_heads_t &hs, int group, float scale, int k, const float *Q,
-                                     int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv,
-                                     const float *dO, int64_t lddo, const float *stats, const float *delta, float *dK,
-                                     int64_t lddk, float *dV, int64_t lddv, const char *what, hipStream_t s)
-{
-    return backward_kv_launch(t, hs, group, scale, k, Q, ldq, K, ldk, kv, V, ldv, dO, lddo, stats, delta, dK, lddk, dV, lddv, what,
-                              s);
-}
-
-// one head: the same kernels at heads = 1 with every stride 0
-int launch_attention_forward(const spmv_csr &h, float scale, int k, const float *Q, int64_t ldq, const float *K, int64_t ldk,
-                             int kv, const float *V, int64_t ldv, float *O, int64_t ldo, float *stats, hipStream_t s)
-{
-    return launch_attention_forward_heads(h, kOneHead, scale, k, Q, ldq, K, ldk, kv, V, ldv, O, ldo, stats,
-                                          "spmv_csr_attention_forward", s);
-}
-
-int launch_attention_backward_q(const spmv_csr &h, float scale, int k, const float *Q, int64_t ldq, const float *K, int64_t ldk,
-                                int kv, const float *V, int64_t ldv, const float *O, int64_t ldo, const float *dO,
-                                int64_t lddo, const float *stats, float *delta, float *dQ, int64_t lddq, hipStream_t s)
-{
-    return launch_attention_backward_q_heads(h, kOneHead, scale, k, Q, ldq, K, ldk, kv, V, ldv, O, ldo, dO, lddo, stats, delta,
-                                             dQ, lddq, "spmv_csr_attention_backward_q", s);
-}
-
-int launch_attention_backward_kv(const spmv_csr &t, float scale, int k, const float *Q, int64_t ldq, const float *K,
-                                 int64_t ldk, int kv, const float *V, int64_t ldv, const float *dO, int64_t lddo,
-                                 const float *stats, const float *delta, float *dK, int64_t lddk, float *dV, int64_t lddv,
-                                 hipStream_t s)
-{
-    return launch_attention_backward_kv_heads(t, kOneHead, scale, k, Q, ldq, K, ldk, kv, V, ldv, dO, lddo, stats, delta, dK,
-                                              lddk, dV, lddv, "spmv_csr_attention_backward_kv", s);
+    switch (pass) {
+        case kPassForward: return launch_attn<kPassForward>(h, a, heads, group, false, vec4({a.ldq, a.ldk, a.ldv, a.ld0}), what, s);
+        case kPassBackwardQ:
+            return launch_attn<kPassBackwardQ>(h, a, heads, group, false, vec4({a.ldq, a.ldk, a.ldv, a.ldo, a.lddo, a.ld0}), what, s);
+        case kPassBackwardKV:
+            return launch_attn<kPassBackwardKV>(h, a, heads, group, sum_group, vec4({a.ldq, a.ldk, a.ldv, a.lddo, a.ld0, a.ld1}), what, s);
+    }
+    return SPMV_ERR_INVALID;
 }
 
 }  // namespace spmv

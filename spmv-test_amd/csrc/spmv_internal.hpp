@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <utility>
 #include "spmv_hip.h"
+#include "attention_args.hpp"
 
 namespace spmv {
 
@@ -380,39 +381,10 @@ int plan_attention(spmv_csr &h, hipStream_t s);
 int plan_attention_heads(spmv_csr &h, int heads, hipStream_t s);
 int64_t attention_plan_bytes(const spmv_csr &h);
 int attention_max_heads(const spmv_csr &h, int width);   // heads one launch takes at operands of `width` columns (>= 0)
-// (the _heads launches: hs.heads heads in one grid, `what` names the caller in a refusal)
-int launch_attention_forward_heads(const spmv_csr &h, const spmv_attn_heads_t &hs, float scale, int k, const float *Q,
-                                   int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv, float *O,
-                                   int64_t ldo, float *stats, const char *what, hipStream_t s);
-int launch_attention_backward_q_heads(const spmv_csr &h, const spmv_attn_heads_t &hs, float scale, int k, const float *Q,
-                                      int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv,
-                                      const float *O, int64_t ldo, const float *dO, int64_t lddo, const float *stats,
-                                      float *delta, float *dQ, int64_t lddq, const char *what, hipStream_t s);
-int launch_attention_backward_kv_heads(const spmv_csr &t, const spmv_attn_heads_t &hs, float scale, int k, const float *Q,
-                                       int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv,
-                                       const float *dO, int64_t lddo, const float *stats, const float *delta, float *dK,
-                                       int64_t lddk, float *dV, int64_t lddv, const char *what, hipStream_t s);
-// (the _gqa launches: hs.heads query heads, `group` of them per K/V head; hs.k, hs.v, hs.dk, hs.dv step by K/V head)
-int launch_attention_forward_gqa(const spmv_csr &h, const spmv_attn_heads_t &hs, int group, float scale, int k, const float *Q,
-                                 int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv, float *O,
-                                 int64_t ldo, float *stats, const char *what, hipStream_t s);
-int launch_attention_backward_q_gqa(const spmv_csr &h, const spmv_attn_heads_t &hs, int group, float scale, int k, const float *Q,
-                                    int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv,
-                                    const float *O, int64_t ldo, const float *dO, int64_t lddo, const float *stats,
-                                    float *delta, float *dQ, int64_t lddq, const char *what, hipStream_t s);
-int launch_attention_backward_kv_gqa(const spmv_csr &t, const spmv_attn_heads_t &hs, int group, float scale, int k, const float *Q,
-                                     int64_t ldq, const float *K, int64_t ldk, int kv, const float *V, int64_t ldv,
-                                     const float *dO, int64_t lddo, const float *stats, const float *delta, float *dK,
-                                     int64_t lddk, float *dV, int64_t lddv, const char *what, hipStream_t s);
-int launch_attention_forward(const spmv_csr &h, float scale, int k, const float *Q, int64_t ldq, const float *K, int64_t ldk,
-                             int kv, const float *V, int64_t ldv, float *O, int64_t ldo, float *stats, hipStream_t s);
-int launch_attention_backward_q(const spmv_csr &h, float scale, int k, const float *Q, int64_t ldq, const float *K, int64_t ldk,
-                                int kv, const float *V, int64_t ldv, const float *O, int64_t ldo, const float *dO,
-                                int64_t lddo, const float *stats, float *delta, float *dQ, int64_t lddq, hipStream_t s);
-int launch_attention_backward_kv(const spmv_csr &t, float scale, int k, const float *Q, int64_t ldq, const float *K,
-                                 int64_t ldk, int kv, const float *V, int64_t ldv, const float *dO, int64_t lddo,
-                                 const float *stats, const float *delta, float *dK, int64_t lddk, float *dV, int64_t lddv,
-                                 hipStream_t s);
+// (one call of any of the nine entry points: `a` filled and checked by capi.hip; `heads` query heads, `group` of them per K/V head;
+// sum_group: backward_kv adds the heads of a group in the kernel, as the _gqa call does; `what` names the caller in a refusal)
+int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgs &a, int heads, int group, bool sum_group, const char *what,
+                     hipStream_t s);
 // kernels_transpose.hip: spmv_csr_transpose / spmv_csr_transpose_values
 int transpose(const spmv_csr &a, bool keep_map, hipStream_t s, spmv_csr_t **out);
 int transpose_values(spmv_csr &t, const spmv_csr &a, hipStream_t s);

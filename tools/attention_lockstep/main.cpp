@@ -3,10 +3,10 @@
 // replacement, so keys repeat inside rows and queries inside transposed rows; the three passes at four (k, kv) on the 16-byte and the
 // 4-byte load path, every array an exactly sized heap block, compared with a serial fp64 statement of attention.  SDDMM
 // at the same four k on the pattern and on its transpose, every out[n] compared bit for bit with a serial statement of
-// the documented order.  Then three heads in one launch (launch_attention_*_heads, the head in blockIdx.y) at the same
+// the documented order.  Then three heads in one launch (launch_attention at heads = 3, the head in blockIdx.z) at the same
 // (k, kv) and load paths, as stacked operands with a padded head stride and as column blocks of one wide matrix, the scratch
 // sized for exactly three heads: every head bit for bit the program's own single-head run on that head's data.  Then grouped-
-// query heads (launch_attention_*_gqa): four query heads on two K/V heads, the three passes on both load paths at a V below 16
+// query heads (launch_attention at group = 2): four query heads on two K/V heads, the three passes on both load paths at a V below 16
 // and at V = 16 (where k_attn_bwd_kv_rows_gqa parks its sums in LDS), the scratch sized for exactly four heads: O, stats,
 // delta and dQ bit for bit the single-head runs on K, V of head y / 2, dK and dV bit for bit those runs' results added in
 // head order from the first head's value.
@@ -81,6 +81,47 @@ static HeadsMatrix heads_matrix(int heads, int64_t rows, int w, int64_t ld, int6
 static void put_head(const HeadsMatrix &m, int y, const float *src, int64_t src_ld, int64_t rows, int w)
 {
     for (int64_t r = 0; r < rows; ++r) std::memcpy(m.p + y * m.stride + r * m.ld, src + r * src_ld, 4 * (size_t)w);
+}
+
+// The three passes through launch_attention, AttnArgs filled by name.  Every operand is a HeadsMatrix: a call of one head
+// passes {p, ld, 0}, a vector (stats, delta) {p, 0, its head stride}.
+static AttnArgs attn_inputs(float scale, int k, int kv, const HeadsMatrix &Q, const HeadsMatrix &K, const HeadsMatrix &V)
+{
+    AttnArgs a{};
+    a.scale = scale, a.k = k, a.kv = kv;
+    a.Q = Q.p, a.ldq = Q.ld, a.hq = Q.stride, a.K = K.p, a.ldk = K.ld, a.hk = K.stride, a.V = V.p, a.ldv = V.ld, a.hv = V.stride;
+    return a;
+}
+
+static int forward(const spmv_csr &A, int heads, int group, float scale, int k, int kv, const HeadsMatrix &Q, const HeadsMatrix &K,
+                   const HeadsMatrix &V, const HeadsMatrix &O, const HeadsMatrix &stats)
+{
+    AttnArgs a = attn_inputs(scale, k, kv, Q, K, V);
+    a.out0 = O.p, a.ld0 = O.ld, a.h0 = O.stride, a.stats = stats.p, a.hstats = stats.stride;
+    return launch_attention(kPassForward, A, a, heads, group, false, "forward", nullptr);
+}
+
+static int backward_q(const spmv_csr &A, int heads, int group, float scale, int k, int kv, const HeadsMatrix &Q, const HeadsMatrix &K,
+                      const HeadsMatrix &V, const HeadsMatrix &O, const HeadsMatrix &dO, const HeadsMatrix &stats,
+                      const HeadsMatrix &delta, const HeadsMatrix &dQ)
+{
+    AttnArgs a = attn_inputs(scale, k, kv, Q, K, V);
+    a.O = O.p, a.ldo = O.ld, a.ho = O.stride, a.dO = dO.p, a.lddo = dO.ld, a.hdo = dO.stride;
+    a.stats_in = stats.p, a.hstats_in = stats.stride, a.delta = delta.p, a.hdelta = delta.stride;
+    a.out0 = dQ.p, a.ld0 = dQ.ld, a.h0 = dQ.stride;
+    return launch_attention(kPassBackwardQ, A, a, heads, group, false, "backward_q", nullptr);
+}
+
+// sum_group: the _gqa call's kernels, which add the heads of a group
+static int backward_kv(const spmv_csr &T, int heads, int group, bool sum_group, float scale, int k, int kv, const HeadsMatrix &Q,
+                       const HeadsMatrix &K, const HeadsMatrix &V, const HeadsMatrix &dO, const HeadsMatrix &stats,
+                       const HeadsMatrix &delta, const HeadsMatrix &dK, const HeadsMatrix &dV)
+{
+    AttnArgs a = attn_inputs(scale, k, kv, Q, K, V);
+    a.dO = dO.p, a.lddo = dO.ld, a.hdo = dO.stride;
+    a.stats_in = stats.p, a.hstats_in = stats.stride, a.delta_in = delta.p, a.hdelta_in = delta.stride;
+    a.out0 = dK.p, a.ld0 = dK.ld, a.h0 = dK.stride, a.out1 = dV.p, a.ld1 = dV.ld, a.h1 = dV.stride;
+    return launch_attention(kPassBackwardKV, T, a, heads, group, sum_group, "backward_kv", nullptr);
 }
 
 // how many of head y's rows x w floats differ in a bit from the single-head result
@@ -172,9 +213,11 @@ static int heads_runs(spmv_csr &A, spmv_csr &T, const Pattern &a, float scale, s
                 dO[y] = matrix(R, kv, lv, rng, true), O[y] = matrix(R, kv, lv, rng, false), dQ[y] = matrix(R, k, lk, rng, false);
                 dK[y] = matrix(C, k, lk, rng, false), dV[y] = matrix(C, kv, lv, rng, false);
                 stats[y] = (float *)malloc(8 * R), delta[y] = (float *)malloc(4 * R);
-                status |= launch_attention_forward(A, scale, k, Q[y], lk, K[y], lk, kv, Vm[y], lv, O[y], lv, stats[y], nullptr);
-                status |= launch_attention_backward_q(A, scale, k, Q[y], lk, K[y], lk, kv, Vm[y], lv, O[y], lv, dO[y], lv, stats[y], delta[y], dQ[y], lk, nullptr);
-                status |= launch_attention_backward_kv(T, scale, k, Q[y], lk, K[y], lk, kv, Vm[y], lv, dO[y], lv, stats[y], delta[y], dK[y], lk, dV[y], lv, nullptr);
+                const HeadsMatrix q{Q[y], lk, 0}, kj{K[y], lk, 0}, vj{Vm[y], lv, 0}, o{O[y], lv, 0}, g{dO[y], lv, 0};
+                const HeadsMatrix ms{stats[y], 0, 0}, md{delta[y], 0, 0};
+                status |= forward(A, 1, 1, scale, k, kv, q, kj, vj, o, ms);
+                status |= backward_q(A, 1, 1, scale, k, kv, q, kj, vj, o, g, ms, md, {dQ[y], lk, 0});
+                status |= backward_kv(T, 1, 1, false, scale, k, kv, q, kj, vj, g, ms, md, {dK[y], lk, 0}, {dV[y], lv, 0});
             }
             plan_heads(A, H);
             plan_heads(T, H);
@@ -194,15 +237,10 @@ static int heads_runs(spmv_csr &A, spmv_csr &T, const Pattern &a, float scale, s
                     put_head(hQ, y, Q[y], lk, R, k), put_head(hK, y, K[y], lk, C, k), put_head(hV, y, Vm[y], lv, C, kv);
                     put_head(hdO, y, dO[y], lv, R, kv);
                 }
-                spmv_attn_heads_t hs{};
-                hs.heads = H;
-                hs.q = hQ.stride, hs.k = hK.stride, hs.v = hV.stride, hs.o = hO.stride, hs.d_o = hdO.stride, hs.stats = sstats, hs.delta = sdelta;
-                hs.dq = hdQ.stride, hs.dk = hdK.stride, hs.dv = hdV.stride;
-                status |= launch_attention_forward_heads(A, hs, scale, k, hQ.p, hQ.ld, hK.p, hK.ld, kv, hV.p, hV.ld, hO.p, hO.ld, hstats, "forward_heads", nullptr);
-                status |= launch_attention_backward_q_heads(A, hs, scale, k, hQ.p, hQ.ld, hK.p, hK.ld, kv, hV.p, hV.ld, hO.p, hO.ld, hdO.p, hdO.ld, hstats,
-                                                            hdelta, hdQ.p, hdQ.ld, "backward_q_heads", nullptr);
-                status |= launch_attention_backward_kv_heads(T, hs, scale, k, hQ.p, hQ.ld, hK.p, hK.ld, kv, hV.p, hV.ld, hdO.p, hdO.ld, hstats, hdelta,
-                                                             hdK.p, hdK.ld, hdV.p, hdV.ld, "backward_kv_heads", nullptr);
+                const HeadsMatrix ms{hstats, 0, sstats}, md{hdelta, 0, sdelta};
+                status |= forward(A, H, 1, scale, k, kv, hQ, hK, hV, hO, ms);
+                status |= backward_q(A, H, 1, scale, k, kv, hQ, hK, hV, hO, hdO, ms, md, hdQ);
+                status |= backward_kv(T, H, 1, false, scale, k, kv, hQ, hK, hV, hdO, ms, md, hdK, hdV);
                 long bad = 0;
                 for (int y = 0; y < H; ++y) {
                     bad += head_differs(hO, y, O[y], lv, R, kv) + head_differs(hdQ, y, dQ[y], lk, R, k);
@@ -250,9 +288,11 @@ static int gqa_runs(spmv_csr &A, spmv_csr &T, const Pattern &a, float scale, std
                 Q[y] = matrix(R, k, lk, rng, true), dO[y] = matrix(R, kv, lv, rng, true), O[y] = matrix(R, kv, lv, rng, false);
                 dQ[y] = matrix(R, k, lk, rng, false), dK[y] = matrix(C, k, lk, rng, false), dV[y] = matrix(C, kv, lv, rng, false);
                 stats[y] = (float *)malloc(8 * R), delta[y] = (float *)malloc(4 * R);
-                status |= launch_attention_forward(A, scale, k, Q[y], lk, K[c], lk, kv, Vm[c], lv, O[y], lv, stats[y], nullptr);
-                status |= launch_attention_backward_q(A, scale, k, Q[y], lk, K[c], lk, kv, Vm[c], lv, O[y], lv, dO[y], lv, stats[y], delta[y], dQ[y], lk, nullptr);
-                status |= launch_attention_backward_kv(T, scale, k, Q[y], lk, K[c], lk, kv, Vm[c], lv, dO[y], lv, stats[y], delta[y], dK[y], lk, dV[y], lv, nullptr);
+                const HeadsMatrix q{Q[y], lk, 0}, kj{K[c], lk, 0}, vj{Vm[c], lv, 0}, o{O[y], lv, 0}, g{dO[y], lv, 0};
+                const HeadsMatrix ms{stats[y], 0, 0}, md{delta[y], 0, 0};
+                status |= forward(A, 1, 1, scale, k, kv, q, kj, vj, o, ms);
+                status |= backward_q(A, 1, 1, scale, k, kv, q, kj, vj, o, g, ms, md, {dQ[y], lk, 0});
+                status |= backward_kv(T, 1, 1, false, scale, k, kv, q, kj, vj, g, ms, md, {dK[y], lk, 0}, {dV[y], lv, 0});
             }
             // the per-head dK, dV folded in head order into the first head's arrays of each group
             for (int c = 0; c < C2; ++c)
@@ -270,15 +310,10 @@ static int gqa_runs(spmv_csr &A, spmv_csr &T, const Pattern &a, float scale, std
             float *hstats = (float *)malloc(4 * (size_t)((H - 1) * sstats + 2 * R)), *hdelta = (float *)malloc(4 * (size_t)((H - 1) * sdelta + R));
             for (int y = 0; y < H; ++y) put_head(hQ, y, Q[y], lk, R, k), put_head(hdO, y, dO[y], lv, R, kv);
             for (int c = 0; c < C2; ++c) put_head(hK, c, K[c], lk, C, k), put_head(hV, c, Vm[c], lv, C, kv);
-            spmv_attn_heads_t hs{};
-            hs.heads = H;
-            hs.q = hQ.stride, hs.k = hK.stride, hs.v = hV.stride, hs.o = hO.stride, hs.d_o = hdO.stride, hs.stats = sstats, hs.delta = sdelta;
-            hs.dq = hdQ.stride, hs.dk = hdK.stride, hs.dv = hdV.stride;
-            status |= launch_attention_forward_gqa(A, hs, G, scale, k, hQ.p, hQ.ld, hK.p, hK.ld, kv, hV.p, hV.ld, hO.p, hO.ld, hstats, "forward_gqa", nullptr);
-            status |= launch_attention_backward_q_gqa(A, hs, G, scale, k, hQ.p, hQ.ld, hK.p, hK.ld, kv, hV.p, hV.ld, hO.p, hO.ld, hdO.p, hdO.ld, hstats,
-                                                      hdelta, hdQ.p, hdQ.ld, "backward_q_gqa", nullptr);
-            status |= launch_attention_backward_kv_gqa(T, hs, G, scale, k, hQ.p, hQ.ld, hK.p, hK.ld, kv, hV.p, hV.ld, hdO.p, hdO.ld, hstats, hdelta,
-                                                       hdK.p, hdK.ld, hdV.p, hdV.ld, "backward_kv_gqa", nullptr);
+            const HeadsMatrix ms{hstats, 0, sstats}, md{hdelta, 0, sdelta};
+            status |= forward(A, H, G, scale, k, kv, hQ, hK, hV, hO, ms);
+            status |= backward_q(A, H, G, scale, k, kv, hQ, hK, hV, hO, hdO, ms, md, hdQ);
+            status |= backward_kv(T, H, G, true, scale, k, kv, hQ, hK, hV, hdO, ms, md, hdK, hdV);
             long bad = 0;
             for (int y = 0; y < H; ++y) {
                 bad += head_differs(hO, y, O[y], lv, R, kv) + head_differs(hdQ, y, dQ[y], lk, R, k);
@@ -355,9 +390,11 @@ int main()
             float *dO = matrix(R, kv, ld(kv), rng, true), *O = matrix(R, kv, ld(kv), rng, false), *dQ = matrix(R, k, ld(k), rng, false);
             float *dK = matrix(C, k, ld(k), rng, false), *dV = matrix(C, kv, ld(kv), rng, false);
             float *stats = (float *)malloc(8 * R), *delta = (float *)malloc(4 * R);
-            status |= launch_attention_forward(A, scale, k, Q, ld(k), K, ld(k), kv, Vm, ld(kv), O, ld(kv), stats, nullptr);
-            status |= launch_attention_backward_q(A, scale, k, Q, ld(k), K, ld(k), kv, Vm, ld(kv), O, ld(kv), dO, ld(kv), stats, delta, dQ, ld(k), nullptr);
-            status |= launch_attention_backward_kv(T, scale, k, Q, ld(k), K, ld(k), kv, Vm, ld(kv), dO, ld(kv), stats, delta, dK, ld(k), dV, ld(kv), nullptr);
+            const HeadsMatrix q{Q, ld(k), 0}, kj{K, ld(k), 0}, vj{Vm, ld(kv), 0}, o{O, ld(kv), 0}, g{dO, ld(kv), 0};
+            const HeadsMatrix ms{stats, 0, 0}, md{delta, 0, 0};
+            status |= forward(A, 1, 1, scale, k, kv, q, kj, vj, o, ms);
+            status |= backward_q(A, 1, 1, scale, k, kv, q, kj, vj, o, g, ms, md, {dQ, ld(k), 0});
+            status |= backward_kv(T, 1, 1, false, scale, k, kv, q, kj, vj, g, ms, md, {dK, ld(k), 0}, {dV, ld(kv), 0});
             // serial fp64
             std::vector<double> rdK((size_t)(C * k), 0.0), rdV((size_t)(C * kv), 0.0), mK(rdK), mV(rdV);
             auto err = [&](double got, double want, double mag) { worst = std::max(worst, std::fabs(got - want) / (mag + 1e-30)); };

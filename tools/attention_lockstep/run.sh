@@ -5,18 +5,18 @@
 # replacement so that keys repeat) and on its transpose, every array an exactly sized heap block, against
 # a serial fp64 statement of attention (2e-5 of the magnitude); and csrc/kernels_sddmm.hip, built from the same
 # csrc/lane_group.hpp, at the same four k on the same patterns, every out[n] bit for bit against a serial statement of the
-# documented order; and three heads in one launch (the head in blockIdx.y) at the same (k, kv) and load paths, stacked and as
+# documented order; and three heads in one launch (the head in blockIdx.z) at the same (k, kv) and load paths, stacked and as
 # column blocks, on a scratch of exactly three heads, every head bit for bit the single-head run; and four grouped-query heads
 # on two K/V heads (the head within its group in blockIdx.y, the K/V head in blockIdx.z; backward_kv's sum over the heads of a
 # group in k_attn_bwd_kv_rows_gqa and k_attn_add_pieces_gqa) bit for bit the single-head runs folded in head order.  Needs no device: a check of the kernels' logic, bounds and alignment, not of the GPU.  The kernel
-# files and lane_group.hpp are copied beside the stubs so that their #include "spmv_internal.hpp" finds the stub.
+# files, lane_group.hpp and attention_args.hpp are copied beside the stubs so that their #include "spmv_internal.hpp" finds the stub.
 set -euo pipefail
 here=$(cd "$(dirname "$0")" && pwd)
 work=$(mktemp -d)
 trap 'rm -rf "$work"' EXIT
 cp -r "$here"/hip "$here"/spmv_internal.hpp "$here"/main.cpp "$work"/
 cp "$here"/../../spmv-test_amd/csrc/kernels_attention.hip "$here"/../../spmv-test_amd/csrc/kernels_sddmm.hip \
-   "$here"/../../spmv-test_amd/csrc/lane_group.hpp "$work"/
+   "$here"/../../spmv-test_amd/csrc/lane_group.hpp "$here"/../../spmv-test_amd/csrc/attention_args.hpp "$work"/
 ${CXX:-clang++} -std=c++20 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -ffp-contract=off -I"$work" -x c++ "$work"/main.cpp -o "$work"/lockstep -lpthread
 "$work"/lockstep
 echo "lockstep ok"

@@ -1,16 +1,13 @@
 #pragma once
 // tools/attention_lockstep: the few names of csrc/spmv_internal.hpp that csrc/lane_group.hpp, csrc/kernels_attention.hip and
-// csrc/kernels_sddmm.hip use, without HIP
+// csrc/kernels_sddmm.hip use, without HIP; csrc/attention_args.hpp (AttnArgs, AttnPass) is the real one, copied beside this file
 #include <hip/hip_runtime.h>
+#include "attention_args.hpp"
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <utility>
 enum { SPMV_OK = 0, SPMV_ERR_INVALID = -2 };
-typedef struct spmv_attn_heads {         // (include/spmv_hip.h)
-    int32_t heads, reserved;
-    int64_t q, k, v, o, d_o, stats, delta, dq, dk, dv;
-} spmv_attn_heads_t;
 #define SPMV_HIP_TRY(call) do { if ((call) != hipSuccess) return -3; } while (0)
 #define SPMV_LAUNCHED(name) if (hipGetLastError() != hipSuccess) return -3
 namespace spmv {

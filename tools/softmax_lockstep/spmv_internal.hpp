@@ -7,7 +7,7 @@
 enum { SPMV_OK = 0, SPMV_ERR_INVALID = -2 };
 #define SPMV_LAUNCHED(name) if (hipGetLastError() != hipSuccess) return -3
 namespace spmv {
-constexpr int kWave = 64; constexpr int kBlock = 256; constexpr int kXcds = 8;
+constexpr int kWave = 64; constexpr int kBlock = 256; constexpr int kXcds = 8; constexpr int kMaxHeads = 65535;
 inline void set_error(const char *f, ...) { va_list a; va_start(a, f); vfprintf(stderr, f, a); va_end(a); }
 inline int hip_fail(hipError_t, const char *, const char *, int) { return -3; }
 template <class T> struct DevPtr { T *p = nullptr; T *get() const { return p; } };
