@@ -578,6 +578,44 @@ SPMV_API int spmv_csr_attention_backward_kv_gqa(spmv_csr_t *t, const spmv_attn_h
                                                 const float *d_stats, const float *d_delta, float *d_dK, int64_t lddk,
                                                 float *d_dV, int64_t lddv, void *stream);
 
+/* ---- Fused attention on 16-bit matrices: bf16 or fp16 operands, fp32 sums, all three passes ---------------------------------
+ * The three _gqa passes with Q, K, V, O, dO, dQ, dK and dV stored as bf16 (dtype = SPMV_ATTN_BF16) or IEEE half
+ * (SPMV_ATTN_FP16), all of one dtype; stats, delta and the scratch of the long rows stay fp32 (the same plan, the same
+ * bytes).  Only the most general form exists: a _heads call is group = 1, one head is hs->heads = 1 with every stride 0.
+ * Units: every ld and every matrix stride of hs counts ELEMENTS of the dtype (2 bytes); the stats and delta strides count
+ * floats as before.
+ * The rounding contract (part of the interface, beside the order of the sums above).  An operand element is widened
+ * exactly to fp32 where it is used; every sum, expf, maximum and butterfly is the fp32 order stated under "Fused attention"
+ * and "grouped-query heads", unchanged; an output element is rounded to the dtype once, to nearest even, at its store.
+ * Nothing is accumulated in 16 bits.  So every element of O, dQ, dK and dV is, bit for bit, the round-to-nearest-even
+ * conversion to dtype of what the matching _gqa fp32 call writes on the same operands widened to fp32, and stats and delta
+ * are that call's bits.  backward_q forms delta from the 16-bit O it is given (the rounded one, if it is the forward call's).
+ * No conversion flushes a subnormal; a NaN is stored as a NaN of the dtype (payload unspecified); fp16 overflows to +-Inf
+ * as round-to-nearest-even says.
+ * The plan: spmv_csr_attention_plan_heads, _plan_bytes, _max_heads and SPMV_ERR_NOT_PLANNED as for the _gqa calls; after the
+ * plan the calls allocate nothing and never wait: graph-capturable.
+ * Loads and stores: a lane's slice is 4 elements, 8 bytes.  With every ld of the pass a multiple of 4 it is one 8-byte access
+ * (the last slice of a width that is no multiple of 4 is read whole inside its row's ld elements and stored below the width
+ * only); otherwise the passes use 2-byte accesses of the columns below the width only.
+ * Refusals (SPMV_ERR_INVALID, a message that names the function, nothing launched, every output untouched): a dtype other
+ * than the two; a matrix that is not 8-byte aligned; a matrix stride that is no multiple of 4 elements; and everything the
+ * _gqa call refuses. */
+enum { SPMV_ATTN_BF16 = 1, SPMV_ATTN_FP16 = 2 };
+SPMV_API int spmv_csr_attention_forward_16(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, int dtype, float scale, int k,
+                                           const void *d_Q, int64_t ldq, const void *d_K, int64_t ldk, int kv,
+                                           const void *d_V, int64_t ldv, void *d_O, int64_t ldo, float *d_stats,
+                                           void *stream);
+SPMV_API int spmv_csr_attention_backward_q_16(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, int dtype, float scale,
+                                              int k, const void *d_Q, int64_t ldq, const void *d_K, int64_t ldk, int kv,
+                                              const void *d_V, int64_t ldv, const void *d_O, int64_t ldo,
+                                              const void *d_dO, int64_t lddo, const float *d_stats, float *d_delta,
+                                              void *d_dQ, int64_t lddq, void *stream);
+SPMV_API int spmv_csr_attention_backward_kv_16(spmv_csr_t *t, const spmv_attn_heads_t *hs, int group, int dtype, float scale,
+                                               int k, const void *d_Q, int64_t ldq, const void *d_K, int64_t ldk, int kv,
+                                               const void *d_V, int64_t ldv, const void *d_dO, int64_t lddo,
+                                               const float *d_stats, const float *d_delta, void *d_dK, int64_t lddk,
+                                               void *d_dV, int64_t lddv, void *stream);
+
 /* ---- dense baselines (reference slots cublas / naive / tiling) ---------
  * y[i] = sum_j x[j] * A[j*N+i] on the dense device matrix.
  * replaces: cublas_gemv_gpu (cublas.cu:4-44), naive_kernel (naive.cu:4-11),

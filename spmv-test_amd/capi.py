@@ -127,6 +127,9 @@ for _pass, _ops in _ATTN_PASSES.items():
     for _mode, _suffix in _ATTN_MODES.items():
         _head = [_H] + ([_HS] if _mode != "one" else []) + ([C.c_int] if _mode == "gqa" else [])      # handle, hs, group
         SIGNATURES[f"spmv_csr_attention_{_pass}{_suffix}"] = (C.c_int, _head + [C.c_float, C.c_int] + _tail + [_vp])
+    # the 16-bit call of the pass: the _gqa arguments with `int dtype` after group; every matrix pointer is a void *
+    SIGNATURES[f"spmv_csr_attention_{_pass}_16"] = (C.c_int, [_H, _HS, C.c_int, C.c_int, C.c_float, C.c_int] + _tail + [_vp])
+ATTN_BF16, ATTN_FP16 = 1, 2      # enum of include/spmv_hip.h: the dtype of a _16 call
 # test only: the bounds-checked build of the library (SPMV_CHECK_BOUNDS) and its sites (csrc/spmv_internal.hpp BoundsSite)
 CHECKED_LIB_PATH = PKG_DIR / "lib" / "libspmv_hip_checked.so"
 BOUNDS_SITES = ("k_bs_sums prod", "k_bs_sums acc", "k_bin_sums prod", "k_bin_sums r16", "k_bs_products c16",
@@ -366,15 +369,17 @@ class CsrMatrix:
         return n
 
     @staticmethod
-    def _attention_operands(what: str, scale: float, **mats) -> None:
-        """Every matrix as (tensor, rows, width or None): 2-D float32 with stride(1) == 1 (its ld is stride(0))."""
+    def _attention_operands(what: str, scale: float, _dtype=None, **mats) -> None:
+        """Every matrix as (tensor, rows, width or None): 2-D float32 (or the call's 16-bit `_dtype`) with stride(1) == 1 (its
+        ld is stride(0))."""
         import math
         import torch
+        dtype, dname = _dtype or torch.float32, str(_dtype or torch.float32).replace("torch.", "")
         if not math.isfinite(scale):
             raise ValueError(f"{what}: scale = {scale} is not finite")
         for name, (t, n, w) in mats.items():
-            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1:
-                raise ValueError(f"{what}: {name} must be a 2-D float32 tensor with stride(1) == 1")
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != dtype or t.stride(1) != 1:
+                raise ValueError(f"{what}: {name} must be a 2-D {dname} tensor with stride(1) == 1")
             if t.shape[0] != n or (w is not None and t.shape[1] != w):
                 raise ValueError(f"{what}: {name} is {tuple(t.shape)}, expected ({n}, {w if w is not None else 'width'})")
 
@@ -412,18 +417,19 @@ class CsrMatrix:
         return n
 
     @staticmethod
-    def _attention_heads(what: str, scale: float, mats: dict, vecs: dict):
-        """Every matrix as (tensor, rows, width or None): (heads, rows, width) float32 with stride(2) == 1, its ld stride(1)
-        and its head stride stride(0); stats (heads, rows, 2) with strides (., 2, 1), delta (heads, rows) with stride(1) == 1.
-        Returns the number of heads."""
+    def _attention_heads(what: str, scale: float, mats: dict, vecs: dict, _dtype=None):
+        """Every matrix as (tensor, rows, width or None): (heads, rows, width) float32 (or the call's 16-bit `_dtype`) with
+        stride(2) == 1, its ld stride(1) and its head stride stride(0); stats (heads, rows, 2) with strides (., 2, 1), delta
+        (heads, rows) with stride(1) == 1, both float32 always.  Returns the number of heads."""
         import math
         import torch
+        dtype, dname = _dtype or torch.float32, str(_dtype or torch.float32).replace("torch.", "")
         if not math.isfinite(scale):
             raise ValueError(f"{what}: scale = {scale} is not finite")
         heads = None
         for name, (t, n, w) in mats.items():
-            if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.dtype != torch.float32 or t.stride(2) != 1:
-                raise ValueError(f"{what}: {name} must be a (heads, rows, width) float32 tensor with stride(2) == 1")
+            if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.dtype != dtype or t.stride(2) != 1:
+                raise ValueError(f"{what}: {name} must be a (heads, rows, width) {dname} tensor with stride(2) == 1")
             heads = t.shape[0] if heads is None else heads
             if t.shape[0] != heads or t.shape[1] != n or (w is not None and t.shape[2] != w):
                 raise ValueError(f"{what}: {name} is {tuple(t.shape)}, expected ({heads}, {n}, {w if w is not None else 'width'})")
@@ -450,11 +456,11 @@ class CsrMatrix:
 
     # -- fused attention, grouped-query heads (spmv_csr_attention_*_gqa) ----------------------------------------------------
     @classmethod
-    def _attention_gqa(cls, what: str, scale: float, query_mats: dict, key_mats: dict, vecs: dict):
+    def _attention_gqa(cls, what: str, scale: float, query_mats: dict, key_mats: dict, vecs: dict, _dtype=None):
         """The query-side matrices and vectors hold H heads, the key-side matrices H_kv; each side under the layout rules of
         _attention_heads.  Returns (H, H_kv, g = H // H_kv); ValueError when H_kv does not divide H."""
-        heads = cls._attention_heads(what, scale, query_mats, vecs)
-        kv_heads = cls._attention_heads(what, scale, key_mats, {})
+        heads = cls._attention_heads(what, scale, query_mats, vecs, _dtype)
+        kv_heads = cls._attention_heads(what, scale, key_mats, {}, _dtype)
         if kv_heads < 1 or heads % kv_heads != 0:
             raise ValueError(f"{what}: {heads} query heads on {kv_heads} K/V heads (grouped-query attention needs H_kv to "
                              f"divide H)")
@@ -476,26 +482,37 @@ class CsrMatrix:
         self._attention_call("backward_kv", "gqa", (Q, K, V, dO, stats, delta, dK, dV), scale, stream)
 
     def _attention_call(self, spec: str, mode: str, tensors, scale: float, stream) -> None:
-        """All nine attention calls: pass `spec` of _ATTN_PASSES in `mode` of _ATTN_MODES on `tensors` in the spec's order."""
+        """All nine attention calls: pass `spec` of _ATTN_PASSES in `mode` of _ATTN_MODES on `tensors` in the spec's order.
+        Matrices that are all torch.bfloat16 or all torch.float16 (stats and delta stay float32) go to the pass's _16 call: the
+        same layout rules, every ld and stride counted in elements; a call of one head is one head with every stride 0, a
+        _heads call a group of 1."""
+        import torch
         what, ops = f"attention_{spec}{_ATTN_MODES[mode]}", _ATTN_PASSES[spec]
         t = dict(zip((o[0] for o in ops), tensors))
+        d16 = {torch.bfloat16: ATTN_BF16, torch.float16: ATTN_FP16}.get(getattr(t["Q"], "dtype", None))
+        dt = t["Q"].dtype if d16 else None
+        if d16:
+            for name, _, w, _, _ in ops:
+                if isinstance(w, str) and isinstance(t[name], torch.Tensor) and t[name].dtype != dt:
+                    raise ValueError(f"{what}: {name} is {t[name].dtype}, Q is {dt} (the matrices of a 16-bit call share one dtype; "
+                                     f"stats and delta are float32)")
         nd = 2 if mode == "one" else 3                       # a matrix: (rows, width) or (heads, rows, width)
         width = {"k": _width(t["Q"], nd), "kv": _width(t["V"], nd)}
         n = {"rows": self.rows, "cols": self.cols}
         mats = [(name, kvh, (t[name], n[side], width[w])) for name, side, w, _, kvh in ops if isinstance(w, str)]
         vecs = [(name, t[name], n[side], w) for name, side, w, _, _ in ops if not isinstance(w, str)]
         if mode == "one":
-            self._attention_operands(what, scale, **{name: m for name, _, m in mats})
+            self._attention_operands(what, scale, dt, **{name: m for name, _, m in mats})
             self._attention_vectors(what, **{name: (v, w * q) for name, v, q, w in vecs})
-            head = []
+            head = [C.byref(AttnHeads(heads=1)), 1] if d16 else []
         else:
             vecs = {name: (v, q, w) for name, v, q, w in vecs}
             if mode == "heads":
-                heads = kv_heads = self._attention_heads(what, scale, {name: m for name, _, m in mats}, vecs)
-                group = []
+                heads = kv_heads = self._attention_heads(what, scale, {name: m for name, _, m in mats}, vecs, dt)
+                group = [1] if d16 else []
             else:
                 heads, kv_heads, g = self._attention_gqa(what, scale, {name: m for name, kvh, m in mats if not kvh},
-                                                         {name: m for name, kvh, m in mats if kvh}, vecs)
+                                                         {name: m for name, kvh, m in mats if kvh}, vecs, dt)
                 group = [g]
             # stride(0) of every tensor; 0 where it holds one head: torch's stride of a dimension of size 1 means nothing
             hs = AttnHeads(heads=heads, **{f: (t[name].stride(0) if (kv_heads if kvh else heads) > 1 else 0)
@@ -504,6 +521,9 @@ class CsrMatrix:
         args = []
         for name, _, w, _, _ in ops:
             args += ([width["kv"]] if name == "V" else []) + [_ptr(t[name])] + ([t[name].stride(nd - 2)] if isinstance(w, str) else [])
+        if d16:
+            check(getattr(lib(), f"spmv_csr_attention_{spec}_16")(self._h, *head, d16, scale, width["k"], *args, _stream_handle(stream)))
+            return
         check(getattr(lib(), f"spmv_csr_{what}")(self._h, *head, scale, width["k"], *args, _stream_handle(stream)))
 
     def values_changed(self) -> None:

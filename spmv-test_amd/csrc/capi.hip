@@ -677,15 +677,16 @@ int spmv_csr_attention_max_heads(const spmv_csr_t *h, int k, int kv)
 }
 
 namespace {
-// One operand of an attention call, as its checks see it: a matrix of n rows (the queries or the keys) of ld floats, of which
-// `width` (k or kv) are used, or a vector of `width` floats per query (stats: 2, delta: 1; ld unused).
+// One operand of an attention call, as its checks see it: a matrix of n rows (the queries or the keys) of ld elements, of which
+// `width` (k or kv) are used, or a vector of `width` floats per query (stats: 2, delta: 1; ld unused).  An element is a float,
+// or 2 bytes in the _16 calls (`elem` of attention_operands).
 struct AttnOperand {
     const char *name;
     const void *p;
     int64_t ld, n;
     int width;
-    int64_t stride;    // floats from one head to the next
-    int unit;          // the stride is a multiple of it: 4 for a matrix (16-byte aligned heads), 2 for stats, 1 for delta
+    int64_t stride;    // elements (a vector: floats) from one head to the next
+    int unit;          // the stride is a multiple of it: 4 for a matrix (heads aligned like head 0), 2 for stats, 1 for delta
     bool out;          // an output: with more than one head its stride is at least its width
     bool kv_heads;     // it holds the K/V heads (heads / group of them), not the query heads
     bool vector() const { return unit != 4; }
@@ -716,10 +717,10 @@ static int attention_header(const spmv_csr_t *h, const spmv_attn_heads_t *hs, in
 }
 
 // and after it, in this order: every head stride (they read k and kv as given); k and kv; the scale; every matrix (ld,
-// presence, 16-byte alignment, 64-bit byte offsets); the vectors (presence, then stats 8-byte and delta 4-byte aligned); the
-// device; the plan and the heads it covers
+// presence, alignment to four elements of `elem` bytes: 16 bytes of floats, 8 of 16-bit elements; 64-bit byte offsets); the
+// vectors (presence, then stats 8-byte and delta 4-byte aligned); the device; the plan and the heads it covers
 static int attention_operands(const spmv_csr_t *h, int heads, int group, float scale, int k, int kv, const AttnOperand *ops, size_t n_ops,
-                              const char *what)
+                              int elem, const char *what)
 {
     for (size_t i = 0; i < n_ops; ++i) {
         const AttnOperand &o = ops[i];
@@ -744,7 +745,7 @@ static int attention_operands(const spmv_csr_t *h, int heads, int group, float s
         if (o.vector()) continue;
         if (o.ld < o.width) { set_error("%s: ld of %s = %lld is below its width %d", what, o.name, (long long)o.ld, o.width); return SPMV_ERR_INVALID; }
         if (!o.p && o.n > 0) { set_error("%s: null %s", what, o.name); return SPMV_ERR_INVALID; }
-        if (!aligned16(o.p)) { set_error("%s: %s must be 16-byte aligned", what, o.name); return SPMV_ERR_INVALID; }
+        if (reinterpret_cast<uintptr_t>(o.p) % (4 * elem) != 0) { set_error("%s: %s must be %d-byte aligned", what, o.name, 4 * elem); return SPMV_ERR_INVALID; }
         if (o.ld > INT64_MAX / 4 / (o.n > 0 ? o.n : 1)) {
             set_error("%s: ld of %s = %lld overflows 64-bit byte offsets", what, o.name, (long long)o.ld);
             return SPMV_ERR_INVALID;
@@ -766,29 +767,33 @@ static int attention_operands(const spmv_csr_t *h, int heads, int group, float s
     return SPMV_OK;
 }
 
-// The three passes.  Each is all nine entry points of its pass: hs->heads query heads, `group` of them per K/V head;
-// sum_group: backward_kv adds the heads of a group in the kernel (the _gqa call).
+extern "C++" {      // (templates: this file is otherwise C linkage)
+// The three passes.  Each is every entry point of its pass: hs->heads query heads, `group` of them per K/V head;
+// sum_group: backward_kv adds the heads of a group in the kernel (the _gqa call).  E: float for the nine fp32 entry points,
+// bf16 or fp16 for the _16 one.
+template <typename E>
 static int attention_forward(const char *what, spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, bool sum_group, float scale,
-                             int k, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V,
-                             int64_t ldv, float *d_O, int64_t ldo, float *d_stats, void *stream)
+                             int k, const E *d_Q, int64_t ldq, const E *d_K, int64_t ldk, int kv, const E *d_V,
+                             int64_t ldv, E *d_O, int64_t ldo, float *d_stats, void *stream)
 {
     if (int rc = attention_header(h, hs, group, what)) return rc;
     const int64_t rows = h->rows, cols = h->cols;
     const AttnOperand ops[] = {{"Q", d_Q, ldq, rows, k, hs->q, 4, kIn, kQHeads}, {"K", d_K, ldk, cols, k, hs->k, 4, kIn, kKVHeads},
                                {"V", d_V, ldv, cols, kv, hs->v, 4, kIn, kKVHeads}, {"O", d_O, ldo, rows, kv, hs->o, 4, kOut, kQHeads},
                                {"stats", d_stats, 0, rows, 2, hs->stats, 2, kOut, kQHeads}};
-    if (int rc = attention_operands(h, hs->heads, group, scale, k, kv, ops, sizeof ops / sizeof *ops, what)) return rc;
-    AttnArgs a{};
+    if (int rc = attention_operands(h, hs->heads, group, scale, k, kv, ops, sizeof ops / sizeof *ops, (int)sizeof(E), what)) return rc;
+    AttnArgsT<E> a{};
     a.scale = scale, a.k = k, a.kv = kv;
     a.Q = d_Q, a.ldq = ldq, a.hq = hs->q, a.K = d_K, a.ldk = ldk, a.hk = hs->k, a.V = d_V, a.ldv = ldv, a.hv = hs->v;
     a.out0 = d_O, a.ld0 = ldo, a.h0 = hs->o, a.stats = d_stats, a.hstats = hs->stats;
     return launch_attention(kPassForward, *h, a, hs->heads, group, sum_group, what, (hipStream_t)stream);
 }
 
+template <typename E>
 static int attention_backward_q(const char *what, spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, bool sum_group, float scale,
-                                int k, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V,
-                                int64_t ldv, const float *d_O, int64_t ldo, const float *d_dO, int64_t lddo, const float *d_stats,
-                                float *d_delta, float *d_dQ, int64_t lddq, void *stream)
+                                int k, const E *d_Q, int64_t ldq, const E *d_K, int64_t ldk, int kv, const E *d_V,
+                                int64_t ldv, const E *d_O, int64_t ldo, const E *d_dO, int64_t lddo, const float *d_stats,
+                                float *d_delta, E *d_dQ, int64_t lddq, void *stream)
 {
     if (int rc = attention_header(h, hs, group, what)) return rc;
     const int64_t rows = h->rows, cols = h->cols;
@@ -796,8 +801,8 @@ static int attention_backward_q(const char *what, spmv_csr_t *h, const spmv_attn
                                {"V", d_V, ldv, cols, kv, hs->v, 4, kIn, kKVHeads}, {"O", d_O, ldo, rows, kv, hs->o, 4, kIn, kQHeads},
                                {"dO", d_dO, lddo, rows, kv, hs->d_o, 4, kIn, kQHeads}, {"stats", d_stats, 0, rows, 2, hs->stats, 2, kIn, kQHeads},
                                {"delta", d_delta, 0, rows, 1, hs->delta, 1, kOut, kQHeads}, {"dQ", d_dQ, lddq, rows, k, hs->dq, 4, kOut, kQHeads}};
-    if (int rc = attention_operands(h, hs->heads, group, scale, k, kv, ops, sizeof ops / sizeof *ops, what)) return rc;
-    AttnArgs a{};
+    if (int rc = attention_operands(h, hs->heads, group, scale, k, kv, ops, sizeof ops / sizeof *ops, (int)sizeof(E), what)) return rc;
+    AttnArgsT<E> a{};
     a.scale = scale, a.k = k, a.kv = kv;
     a.Q = d_Q, a.ldq = ldq, a.hq = hs->q, a.K = d_K, a.ldk = ldk, a.hk = hs->k, a.V = d_V, a.ldv = ldv, a.hv = hs->v;
     a.O = d_O, a.ldo = ldo, a.ho = hs->o, a.dO = d_dO, a.lddo = lddo, a.hdo = hs->d_o;
@@ -807,10 +812,11 @@ static int attention_backward_q(const char *what, spmv_csr_t *h, const spmv_attn
 
 // t is the handle of the TRANSPOSED pattern: t->rows keys, t->cols queries.  dK and dV hold the K/V heads (the output-stride
 // rule counts those).
+template <typename E>
 static int attention_backward_kv(const char *what, spmv_csr_t *t, const spmv_attn_heads_t *hs, int group, bool sum_group, float scale,
-                                 int k, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, int kv, const float *d_V,
-                                 int64_t ldv, const float *d_dO, int64_t lddo, const float *d_stats, const float *d_delta,
-                                 float *d_dK, int64_t lddk, float *d_dV, int64_t lddv, void *stream)
+                                 int k, const E *d_Q, int64_t ldq, const E *d_K, int64_t ldk, int kv, const E *d_V,
+                                 int64_t ldv, const E *d_dO, int64_t lddo, const float *d_stats, const float *d_delta,
+                                 E *d_dK, int64_t lddk, E *d_dV, int64_t lddv, void *stream)
 {
     if (int rc = attention_header(t, hs, group, what)) return rc;
     const int64_t keys = t->rows, queries = t->cols;
@@ -819,8 +825,8 @@ static int attention_backward_kv(const char *what, spmv_csr_t *t, const spmv_att
                                {"stats", d_stats, 0, queries, 2, hs->stats, 2, kIn, kQHeads},
                                {"delta", d_delta, 0, queries, 1, hs->delta, 1, kIn, kQHeads}, {"dK", d_dK, lddk, keys, k, hs->dk, 4, kOut, kKVHeads},
                                {"dV", d_dV, lddv, keys, kv, hs->dv, 4, kOut, kKVHeads}};
-    if (int rc = attention_operands(t, hs->heads, group, scale, k, kv, ops, sizeof ops / sizeof *ops, what)) return rc;
-    AttnArgs a{};
+    if (int rc = attention_operands(t, hs->heads, group, scale, k, kv, ops, sizeof ops / sizeof *ops, (int)sizeof(E), what)) return rc;
+    AttnArgsT<E> a{};
     a.scale = scale, a.k = k, a.kv = kv;
     a.Q = d_Q, a.ldq = ldq, a.hq = hs->q, a.K = d_K, a.ldk = ldk, a.hk = hs->k, a.V = d_V, a.ldv = ldv, a.hv = hs->v;
     a.dO = d_dO, a.lddo = lddo, a.hdo = hs->d_o;
@@ -828,6 +834,8 @@ static int attention_backward_kv(const char *what, spmv_csr_t *t, const spmv_att
     a.out0 = d_dK, a.ld0 = lddk, a.h0 = hs->dk, a.out1 = d_dV, a.ld1 = lddv, a.h1 = hs->dv;
     return launch_attention(kPassBackwardKV, *t, a, hs->heads, group, sum_group, what, (hipStream_t)stream);
 }
+
+}  // extern "C++"
 
 // ---- the nine entry points: one head (kOneHead), the heads of one pattern in one launch, grouped-query heads ----------------
 int spmv_csr_attention_forward(spmv_csr_t *h, float scale, int k, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk,
@@ -905,6 +913,61 @@ int spmv_csr_attention_backward_kv_gqa(spmv_csr_t *t, const spmv_attn_heads_t *h
 {
     return attention_backward_kv("spmv_csr_attention_backward_kv_gqa", t, hs, group, true, scale, k, d_Q, ldq, d_K, ldk, kv, d_V, ldv,
                                  d_dO, lddo, d_stats, d_delta, d_dK, lddk, d_dV, lddv, stream);
+}
+
+// ---- the same three passes on 16-bit matrices (bf16 or fp16 storage, fp32 sums): the most general form only ---------------
+static int attention_dtype(int dtype, const char *what)
+{
+    if (dtype == SPMV_ATTN_BF16 || dtype == SPMV_ATTN_FP16) return SPMV_OK;
+    set_error("%s: dtype = %d (need SPMV_ATTN_BF16 = %d or SPMV_ATTN_FP16 = %d)", what, dtype, (int)SPMV_ATTN_BF16, (int)SPMV_ATTN_FP16);
+    return SPMV_ERR_INVALID;
+}
+
+int spmv_csr_attention_forward_16(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, int dtype, float scale, int k,
+                                  const void *d_Q, int64_t ldq, const void *d_K, int64_t ldk, int kv, const void *d_V, int64_t ldv,
+                                  void *d_O, int64_t ldo, float *d_stats, void *stream)
+{
+    const char *what = "spmv_csr_attention_forward_16";
+    if (int rc = attention_header(h, hs, group, what)) return rc;
+    if (int rc = attention_dtype(dtype, what)) return rc;
+    auto run = [&](auto e) {
+        using E = decltype(e);
+        return attention_forward<E>(what, h, hs, group, false, scale, k, (const E *)d_Q, ldq, (const E *)d_K, ldk, kv, (const E *)d_V, ldv,
+                                    (E *)d_O, ldo, d_stats, stream);
+    };
+    return dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+}
+
+int spmv_csr_attention_backward_q_16(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, int dtype, float scale, int k,
+                                     const void *d_Q, int64_t ldq, const void *d_K, int64_t ldk, int kv, const void *d_V,
+                                     int64_t ldv, const void *d_O, int64_t ldo, const void *d_dO, int64_t lddo,
+                                     const float *d_stats, float *d_delta, void *d_dQ, int64_t lddq, void *stream)
+{
+    const char *what = "spmv_csr_attention_backward_q_16";
+    if (int rc = attention_header(h, hs, group, what)) return rc;
+    if (int rc = attention_dtype(dtype, what)) return rc;
+    auto run = [&](auto e) {
+        using E = decltype(e);
+        return attention_backward_q<E>(what, h, hs, group, false, scale, k, (const E *)d_Q, ldq, (const E *)d_K, ldk, kv, (const E *)d_V,
+                                       ldv, (const E *)d_O, ldo, (const E *)d_dO, lddo, d_stats, d_delta, (E *)d_dQ, lddq, stream);
+    };
+    return dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+}
+
+int spmv_csr_attention_backward_kv_16(spmv_csr_t *t, const spmv_attn_heads_t *hs, int group, int dtype, float scale, int k,
+                                      const void *d_Q, int64_t ldq, const void *d_K, int64_t ldk, int kv, const void *d_V,
+                                      int64_t ldv, const void *d_dO, int64_t lddo, const float *d_stats, const float *d_delta,
+                                      void *d_dK, int64_t lddk, void *d_dV, int64_t lddv, void *stream)
+{
+    const char *what = "spmv_csr_attention_backward_kv_16";
+    if (int rc = attention_header(t, hs, group, what)) return rc;
+    if (int rc = attention_dtype(dtype, what)) return rc;
+    auto run = [&](auto e) {
+        using E = decltype(e);
+        return attention_backward_kv<E>(what, t, hs, group, true, scale, k, (const E *)d_Q, ldq, (const E *)d_K, ldk, kv, (const E *)d_V,
+                                        ldv, (const E *)d_dO, lddo, d_stats, d_delta, (E *)d_dK, lddk, (E *)d_dV, lddv, stream);
+    };
+    return dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
 }
 
 int spmv_csr_values_changed(spmv_csr_t *h)

@@ -42,6 +42,14 @@
 // with dK^(i), dV^(i) the single-head numbers of query head c g + i (spans from +0, a long row's pieces in piece order from
 // +0), added in head order from head 0's value, not from +0.  g = 1 adds nothing: the _heads bits.
 //
+// Element types.  Every kernel, span function and launch function takes the element type E of the matrices (Q, K, V, O, dO, dQ, dK,
+// dV) as its last template argument: float (the nine fp32 entry points) or 16-bit storage (bf16, fp16: the _16 entry points).
+// The text above is E = float.  With 16-bit E nothing of the order changes: a step's gathered slices wait packed as loaded
+// (slice_t<E>, 2 registers per slice) and are widened exactly to fp32 at each use (widen, widen_again), the row's own operands
+// are widened once (load_wide), every sum above is the same fp32 operation, and store_slice rounds an output to E once, to
+// nearest even.  stats, delta, the scratch and the LDS slots of k_attn_bwd_kv_rows_gqa hold floats whatever E is.  So a 16-bit
+// call is, bit for bit, the fp32 call on the widened operands with O, dQ, dK and dV rounded once.
+//
 // The scratch of the long rows (AttnPlan): per head, kAtSlots floats per piece: [0] m_p, [1] l_p, [4, 132) up to 128 partial sums
 // (forward acc_p[kv]; backward_q dQ_p[k]; backward_kv dK_p[k] at 4 and dV_p[kv] at 68).
 #include <initializer_list>
@@ -62,7 +70,8 @@ __device__ __forceinline__ int64_t query_head() { return (int64_t)blockIdx.z * g
 
 // the operands of the block's head: every base advanced once, by a wave-uniform number (scalar work); K and V by the K/V
 // head, everything else by the query head
-__device__ __forceinline__ AttnArgs at_head(AttnArgs a)
+template <typename E>
+__device__ __forceinline__ AttnArgsT<E> at_head(AttnArgsT<E> a)
 {
     const int64_t y = query_head(), c = blockIdx.z;
     a.Q += y * a.hq, a.K += c * a.hk, a.V += c * a.hv, a.O += y * a.ho, a.dO += y * a.hdo;
@@ -97,8 +106,8 @@ __device__ __forceinline__ float *at_head_scratch(const GroupPieces &g)
 }
 
 // ---- forward: (m, l, acc) of the nonzeros [b, e) of the group's row.  All lanes of a group call it with the same b, e. ----
-template <int V, bool VEC>
-__device__ __forceinline__ void fwd_span(int lane, int64_t b, int64_t e, const AttnArgs &a, float4 q,
+template <int V, bool VEC, typename E>
+__device__ __forceinline__ void fwd_span(int lane, int64_t b, int64_t e, const AttnArgsT<E> &a, float4 q,
                                          const int32_t *__restrict__ col_idx, int c0, float &m, float &l, float4 &acc)
 {
     constexpr int T = LaneGeom<V>::T, L = LaneGeom<V>::L;
@@ -110,14 +119,14 @@ __device__ __forceinline__ void fwd_span(int lane, int64_t b, int64_t e, const A
     for (int64_t kb = b; kb < e; kb += T) {
         int32_t c[L], ct[T];
         group_columns<V, T>(kb, e, sub, gbase, col_idx, c, ct);
-        float4 xk[T], xv[T];
+        slice_t<E> xk[T], xv[T];      // as loaded: 16-bit elements stay packed until they are used
 #pragma unroll
-        for (int t = 0; t < T; ++t) xk[t] = (nk > 0 && kb + t < e) ? load_slice<VEC>(a.K, a.ldk, ct[t], c0, a.k) : zero4();
+        for (int t = 0; t < T; ++t) xk[t] = (nk > 0 && kb + t < e) ? load_slice<VEC>(a.K, a.ldk, ct[t], c0, a.k) : zero_slice<E>();
 #pragma unroll
-        for (int t = 0; t < T; ++t) xv[t] = (nv > 0 && kb + t < e) ? load_slice<VEC>(a.V, a.ldv, ct[t], c0, a.kv) : zero4();
+        for (int t = 0; t < T; ++t) xv[t] = (nv > 0 && kb + t < e) ? load_slice<VEC>(a.V, a.ldv, ct[t], c0, a.kv) : zero_slice<E>();
         float p[T];
 #pragma unroll
-        for (int t = 0; t < T; ++t) p[t] = dot_partial(q, xk[t], nk);
+        for (int t = 0; t < T; ++t) p[t] = dot_partial(q, widen<E>(xk[t]), nk);
         reduce_scatter<V, T>(p, sub);
         float tl[L], sm = -INFINITY;
 #pragma unroll
@@ -141,10 +150,11 @@ __device__ __forceinline__ void fwd_span(int lane, int64_t b, int64_t e, const A
         for (int t = 0; t < T; ++t) {
             if (kb + t < e) {
                 l = l + et[t];
-                acc.x = fmaf(et[t], xv[t].x, acc.x);
-                acc.y = fmaf(et[t], xv[t].y, acc.y);
-                acc.z = fmaf(et[t], xv[t].z, acc.z);
-                acc.w = fmaf(et[t], xv[t].w, acc.w);
+                const float4 wv = widen<E>(xv[t]);
+                acc.x = fmaf(et[t], wv.x, acc.x);
+                acc.y = fmaf(et[t], wv.y, acc.y);
+                acc.z = fmaf(et[t], wv.z, acc.z);
+                acc.w = fmaf(et[t], wv.w, acc.w);
             }
         }
         m = mn;
@@ -158,10 +168,10 @@ __device__ __forceinline__ void store_stats(float *stats, int64_t r, float m, fl
     *reinterpret_cast<float2 *>(stats + 2 * r) = make_float2(m, rinv);
 }
 
-template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_attn_fwd_rows(GroupRows g, AttnArgs a0)
+template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) void k_attn_fwd_rows(GroupRows g, AttnArgsT<E> a0)
 {
-    const AttnArgs a = at_head(a0);
+    const AttnArgsT<E> a = at_head(a0);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     const int64_t r = group_row<V>(g);
     if (r < 0) return;
@@ -172,19 +182,19 @@ __global__ __launch_bounds__(kBlock) void k_attn_fwd_rows(GroupRows g, AttnArgs 
         if (sub == 0) store_stats(a.stats, r, -INFINITY, 0.0f);
         return;
     }
-    const float4 q = c0 < a.k ? load_slice<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
+    const float4 q = c0 < a.k ? load_wide<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
     float m, l;
     float4 acc;
-    fwd_span<V, VEC>(lane, b, e, a, q, g.col_idx, c0, m, l, acc);
+    fwd_span<V, VEC, E>(lane, b, e, a, q, g.col_idx, c0, m, l, acc);
     const float rinv = 1.0f / l;
     if (c0 < a.kv) store_slice<VEC>(a.out0 + r * a.ld0 + c0, scaled4(acc, rinv), c0, a.kv);
     if (sub == 0) store_stats(a.stats, r, m, rinv);
 }
 
-template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_attn_fwd_pieces(GroupPieces g, AttnArgs a0)
+template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) void k_attn_fwd_pieces(GroupPieces g, AttnArgsT<E> a0)
 {
-    const AttnArgs a = at_head(a0);
+    const AttnArgsT<E> a = at_head(a0);
     float *const scratch = at_head_scratch(g);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     int lo;
@@ -192,20 +202,20 @@ __global__ __launch_bounds__(kBlock) void k_attn_fwd_pieces(GroupPieces g, AttnA
     if (p < 0) return;
     const int64_t r = g.long_row[lo];
     const int64_t b = g.piece_k0[p], e = b + g.piece_len[p];
-    const float4 q = c0 < a.k ? load_slice<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
+    const float4 q = c0 < a.k ? load_wide<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
     float m, l;
     float4 acc;
-    fwd_span<V, VEC>(lane, b, e, a, q, g.col_idx, c0, m, l, acc);
+    fwd_span<V, VEC, E>(lane, b, e, a, q, g.col_idx, c0, m, l, acc);
     float *s = scratch + p * kAtSlots;
     if (sub == 0) *reinterpret_cast<float2 *>(s) = make_float2(m, l);
     if (c0 < a.kv) *reinterpret_cast<float4 *>(s + kAtSums + c0) = acc;
 }
 
 // a group per long row: the pieces' (m_p, l_p, acc_p) folded in piece order
-template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_attn_fwd_combine(GroupPieces g, AttnArgs a0)
+template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) void k_attn_fwd_combine(GroupPieces g, AttnArgsT<E> a0)
 {
-    const AttnArgs a = at_head(a0);
+    const AttnArgsT<E> a = at_head(a0);
     const int sub = threadIdx.x & (V - 1), c0 = 4 * sub;
     const int64_t i = (int64_t)blockIdx.x * (kBlock / V) + threadIdx.x / V;
     if (i >= g.n_long) return;
@@ -235,8 +245,8 @@ __global__ __launch_bounds__(kBlock) void k_attn_fwd_combine(GroupPieces g, Attn
 }
 
 // ---- backward_q: dQ of the nonzeros [b, e) of row i, whose q, dO slice g, (M, rinv) and delta the group holds -------------
-template <int V, bool VEC>
-__device__ __forceinline__ float4 bwdq_span(int lane, int64_t b, int64_t e, const AttnArgs &a, float4 q, float4 g, float M,
+template <int V, bool VEC, typename E>
+__device__ __forceinline__ float4 bwdq_span(int lane, int64_t b, int64_t e, const AttnArgsT<E> &a, float4 q, float4 g, float M,
                                             float rinv, float delta, const int32_t *__restrict__ col_idx, int c0)
 {
     constexpr int T = LaneGeom<V>::T, L = LaneGeom<V>::L;
@@ -246,16 +256,16 @@ __device__ __forceinline__ float4 bwdq_span(int lane, int64_t b, int64_t e, cons
     for (int64_t kb = b; kb < e; kb += T) {
         int32_t c[L], ct[T];
         group_columns<V, T>(kb, e, sub, gbase, col_idx, c, ct);
-        float4 xk[T], xv[T];
+        slice_t<E> xk[T], xv[T];      // as loaded: 16-bit elements stay packed until they are used
 #pragma unroll
-        for (int t = 0; t < T; ++t) xk[t] = (nk > 0 && kb + t < e) ? load_slice<VEC>(a.K, a.ldk, ct[t], c0, a.k) : zero4();
+        for (int t = 0; t < T; ++t) xk[t] = (nk > 0 && kb + t < e) ? load_slice<VEC>(a.K, a.ldk, ct[t], c0, a.k) : zero_slice<E>();
 #pragma unroll
-        for (int t = 0; t < T; ++t) xv[t] = (nv > 0 && kb + t < e) ? load_slice<VEC>(a.V, a.ldv, ct[t], c0, a.kv) : zero4();
+        for (int t = 0; t < T; ++t) xv[t] = (nv > 0 && kb + t < e) ? load_slice<VEC>(a.V, a.ldv, ct[t], c0, a.kv) : zero_slice<E>();
         float ps[T], pd[T];
 #pragma unroll
         for (int t = 0; t < T; ++t) {
-            ps[t] = dot_partial(q, xk[t], nk);
-            pd[t] = dot_partial(g, xv[t], nv);
+            ps[t] = dot_partial(q, widen<E>(xk[t]), nk);
+            pd[t] = dot_partial(g, widen<E>(xv[t]), nv);
         }
         reduce_scatter<V, T>(ps, sub);
         reduce_scatter<V, T>(pd, sub);
@@ -270,10 +280,11 @@ __device__ __forceinline__ float4 bwdq_span(int lane, int64_t b, int64_t e, cons
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             if (kb + t < e) {
-                dq.x = fmaf(dt[t], xk[t].x, dq.x);
-                dq.y = fmaf(dt[t], xk[t].y, dq.y);
-                dq.z = fmaf(dt[t], xk[t].z, dq.z);
-                dq.w = fmaf(dt[t], xk[t].w, dq.w);
+                const float4 wk = widen_again<E>(xk[t]);
+                dq.x = fmaf(dt[t], wk.x, dq.x);
+                dq.y = fmaf(dt[t], wk.y, dq.y);
+                dq.z = fmaf(dt[t], wk.z, dq.z);
+                dq.w = fmaf(dt[t], wk.w, dq.w);
             }
         }
     }
@@ -281,22 +292,22 @@ __device__ __forceinline__ float4 bwdq_span(int lane, int64_t b, int64_t e, cons
 }
 
 // delta of row r (every lane of the group gets it) and the row's dO slice
-template <int V, bool VEC>
-__device__ __forceinline__ float at_delta(const AttnArgs &a, int64_t r, int c0, float4 &g)
+template <int V, bool VEC, typename E>
+__device__ __forceinline__ float at_delta(const AttnArgsT<E> &a, int64_t r, int c0, float4 &g)
 {
     float4 o = zero4();
     g = zero4();
     if (c0 < a.kv) {
-        g = load_slice<VEC>(a.dO, a.lddo, r, c0, a.kv);
-        o = load_slice<VEC>(a.O, a.ldo, r, c0, a.kv);
+        g = load_wide<VEC>(a.dO, a.lddo, r, c0, a.kv);
+        o = load_wide<VEC>(a.O, a.ldo, r, c0, a.kv);
     }
     return group_sum<V>(dot_partial(g, o, a.kv - c0));
 }
 
-template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_attn_bwd_q_rows(GroupRows g, AttnArgs a0)
+template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_q_rows(GroupRows g, AttnArgsT<E> a0)
 {
-    const AttnArgs a = at_head(a0);
+    const AttnArgsT<E> a = at_head(a0);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     const int64_t r = group_row<V>(g);
     if (r < 0) return;
@@ -308,18 +319,18 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_q_rows(GroupRows g, AttnArg
         return;
     }
     float4 go;
-    const float delta = at_delta<V, VEC>(a, r, c0, go);
-    const float4 q = c0 < a.k ? load_slice<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
+    const float delta = at_delta<V, VEC, E>(a, r, c0, go);
+    const float4 q = c0 < a.k ? load_wide<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
     const float2 st = *reinterpret_cast<const float2 *>(a.stats_in + 2 * r);
-    const float4 dq = bwdq_span<V, VEC>(lane, b, e, a, q, go, st.x, st.y, delta, g.col_idx, c0);
+    const float4 dq = bwdq_span<V, VEC, E>(lane, b, e, a, q, go, st.x, st.y, delta, g.col_idx, c0);
     if (c0 < a.k) store_slice<VEC>(a.out0 + r * a.ld0 + c0, dq, c0, a.k);
     if (sub == 0) a.delta[r] = delta;
 }
 
-template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_attn_bwd_q_pieces(GroupPieces g, AttnArgs a0)
+template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_q_pieces(GroupPieces g, AttnArgsT<E> a0)
 {
-    const AttnArgs a = at_head(a0);
+    const AttnArgsT<E> a = at_head(a0);
     float *const scratch = at_head_scratch(g);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     int lo;
@@ -328,18 +339,18 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_q_pieces(GroupPieces g, Att
     const int64_t r = g.long_row[lo];
     const int64_t b = g.piece_k0[p], e = b + g.piece_len[p];
     float4 go;
-    const float delta = at_delta<V, VEC>(a, r, c0, go);      // (every piece of the row computes the same bits)
-    const float4 q = c0 < a.k ? load_slice<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
+    const float delta = at_delta<V, VEC, E>(a, r, c0, go);      // (every piece of the row computes the same bits)
+    const float4 q = c0 < a.k ? load_wide<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
     const float2 st = *reinterpret_cast<const float2 *>(a.stats_in + 2 * r);
-    const float4 dq = bwdq_span<V, VEC>(lane, b, e, a, q, go, st.x, st.y, delta, g.col_idx, c0);
+    const float4 dq = bwdq_span<V, VEC, E>(lane, b, e, a, q, go, st.x, st.y, delta, g.col_idx, c0);
     if (c0 < a.k) *reinterpret_cast<float4 *>(scratch + p * kAtSlots + kAtSums + c0) = dq;
     if (sub == 0 && p == g.long_first[lo]) a.delta[r] = delta;
 }
 
 // a group per long row: out[row][c] = the pieces' partial sums at scratch offset `off`, added in piece order from +0
 // (hout: floats from one head's out to the next)
-template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_attn_add_pieces(GroupPieces g, int off, float *__restrict__ out, int64_t ld, int w,
+template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) void k_attn_add_pieces(GroupPieces g, int off, E *__restrict__ out, int64_t ld, int w,
                                                             int64_t hout)
 {
     const int sub = threadIdx.x & (V - 1), c0 = 4 * sub;
@@ -359,8 +370,8 @@ __global__ __launch_bounds__(kBlock) void k_attn_add_pieces(GroupPieces g, int o
 }
 
 // ---- backward_kv on the transposed pattern: (dK, dV) of the nonzeros [b, e) of row j, whose K and V slices the group holds
-template <int V, bool VEC>
-__device__ __forceinline__ void bwdkv_span(int lane, int64_t b, int64_t e, const AttnArgs &a, float4 kj, float4 vj,
+template <int V, bool VEC, typename E>
+__device__ __forceinline__ void bwdkv_span(int lane, int64_t b, int64_t e, const AttnArgsT<E> &a, float4 kj, float4 vj,
                                            const int32_t *__restrict__ col_idx, int c0, float4 &dk, float4 &dv)
 {
     constexpr int T = LaneGeom<V>::T, L = LaneGeom<V>::L;
@@ -379,16 +390,16 @@ __device__ __forceinline__ void bwdkv_span(int lane, int64_t b, int64_t e, const
             st[i] = in ? *reinterpret_cast<const float2 *>(a.stats_in + 2 * (int64_t)c[i]) : make_float2(0.0f, 0.0f);
             de[i] = in ? a.delta_in[c[i]] : 0.0f;
         }
-        float4 xq[T], xg[T];
+        slice_t<E> xq[T], xg[T];
 #pragma unroll
-        for (int t = 0; t < T; ++t) xq[t] = (nk > 0 && kb + t < e) ? load_slice<VEC>(a.Q, a.ldq, ct[t], c0, a.k) : zero4();
+        for (int t = 0; t < T; ++t) xq[t] = (nk > 0 && kb + t < e) ? load_slice<VEC>(a.Q, a.ldq, ct[t], c0, a.k) : zero_slice<E>();
 #pragma unroll
-        for (int t = 0; t < T; ++t) xg[t] = (nv > 0 && kb + t < e) ? load_slice<VEC>(a.dO, a.lddo, ct[t], c0, a.kv) : zero4();
+        for (int t = 0; t < T; ++t) xg[t] = (nv > 0 && kb + t < e) ? load_slice<VEC>(a.dO, a.lddo, ct[t], c0, a.kv) : zero_slice<E>();
         float ps[T], pd[T];
 #pragma unroll
         for (int t = 0; t < T; ++t) {
-            ps[t] = dot_partial(kj, xq[t], nk);
-            pd[t] = dot_partial(vj, xg[t], nv);
+            ps[t] = dot_partial(kj, widen<E>(xq[t]), nk);
+            pd[t] = dot_partial(vj, widen<E>(xg[t]), nv);
         }
         reduce_scatter<V, T>(ps, sub);
         reduce_scatter<V, T>(pd, sub);
@@ -404,23 +415,25 @@ __device__ __forceinline__ void bwdkv_span(int lane, int64_t b, int64_t e, const
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             if (kb + t < e) {
-                dv.x = fmaf(pt[t], xg[t].x, dv.x);
-                dv.y = fmaf(pt[t], xg[t].y, dv.y);
-                dv.z = fmaf(pt[t], xg[t].z, dv.z);
-                dv.w = fmaf(pt[t], xg[t].w, dv.w);
-                dk.x = fmaf(dt[t], xq[t].x, dk.x);
-                dk.y = fmaf(dt[t], xq[t].y, dk.y);
-                dk.z = fmaf(dt[t], xq[t].z, dk.z);
-                dk.w = fmaf(dt[t], xq[t].w, dk.w);
+                const float4 wg = widen_again<E>(xg[t]);
+                dv.x = fmaf(pt[t], wg.x, dv.x);
+                dv.y = fmaf(pt[t], wg.y, dv.y);
+                dv.z = fmaf(pt[t], wg.z, dv.z);
+                dv.w = fmaf(pt[t], wg.w, dv.w);
+                const float4 wq = widen_again<E>(xq[t]);
+                dk.x = fmaf(dt[t], wq.x, dk.x);
+                dk.y = fmaf(dt[t], wq.y, dk.y);
+                dk.z = fmaf(dt[t], wq.z, dk.z);
+                dk.w = fmaf(dt[t], wq.w, dk.w);
             }
         }
     }
 }
 
-template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows(GroupRows g, AttnArgs a0)
+template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows(GroupRows g, AttnArgsT<E> a0)
 {
-    const AttnArgs a = at_head(a0);
+    const AttnArgsT<E> a = at_head(a0);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     const int64_t r = group_row<V>(g);
     if (r < 0) return;
@@ -428,18 +441,18 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows(GroupRows g, AttnAr
     if (e - b > g.row_cap) return;
     float4 dk = zero4(), dv = zero4();
     if (e > b) {
-        const float4 kj = c0 < a.k ? load_slice<VEC>(a.K, a.ldk, r, c0, a.k) : zero4();
-        const float4 vj = c0 < a.kv ? load_slice<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
-        bwdkv_span<V, VEC>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv);
+        const float4 kj = c0 < a.k ? load_wide<VEC>(a.K, a.ldk, r, c0, a.k) : zero4();
+        const float4 vj = c0 < a.kv ? load_wide<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
+        bwdkv_span<V, VEC, E>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv);
     }
     if (c0 < a.k) store_slice<VEC>(a.out0 + r * a.ld0 + c0, dk, c0, a.k);
     if (c0 < a.kv) store_slice<VEC>(a.out1 + r * a.ld1 + c0, dv, c0, a.kv);
 }
 
-template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_pieces(GroupPieces g, AttnArgs a0)
+template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_pieces(GroupPieces g, AttnArgsT<E> a0)
 {
-    const AttnArgs a = at_head(a0);
+    const AttnArgsT<E> a = at_head(a0);
     float *const scratch = at_head_scratch(g);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     int lo;
@@ -447,10 +460,10 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_pieces(GroupPieces g, At
     if (p < 0) return;
     const int64_t r = g.long_row[lo];
     const int64_t b = g.piece_k0[p], e = b + g.piece_len[p];
-    const float4 kj = c0 < a.k ? load_slice<VEC>(a.K, a.ldk, r, c0, a.k) : zero4();
-    const float4 vj = c0 < a.kv ? load_slice<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
+    const float4 kj = c0 < a.k ? load_wide<VEC>(a.K, a.ldk, r, c0, a.k) : zero4();
+    const float4 vj = c0 < a.kv ? load_wide<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
     float4 dk, dv;
-    bwdkv_span<V, VEC>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv);
+    bwdkv_span<V, VEC, E>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv);
     float *s = scratch + p * kAtSlots;
     if (c0 < a.k) *reinterpret_cast<float4 *>(s + kAtSums + c0) = dk;
     if (c0 < a.kv) *reinterpret_cast<float4 *>(s + kAtSums2 + c0) = dv;
@@ -490,8 +503,9 @@ __device__ __forceinline__ void park_fence() { asm volatile("" ::: "memory"); }
 struct Strides2 {
     int64_t a, b;
 };
+template <typename E>
 struct Pointers2 {
-    float *k, *v;
+    E *k, *v;
 };
 
 // a number every lane of the wavefront holds alike, as a scalar again
@@ -511,8 +525,8 @@ __device__ __forceinline__ int64_t uniform64(int64_t x)
 // per-head numbers) and adds the heads' results in head order, starting from head 0's.  The per-head kernel leaves few
 // registers free (k_attn_bwd_kv_rows: up to 104 SGPRs; at V = 16 247 to 254 of the 256 VGPRs that two waves per SIMD allow),
 // so the head strides, and at V = 16 the running sums, the row's output addresses and its bounds, wait in LDS (park_lds).
-template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows_gqa(GroupRows g, AttnArgs a, int group)
+template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows_gqa(GroupRows g, AttnArgsT<E> a, int group)
 {
     constexpr bool kPark = V == 16;
     constexpr int N = kPark ? 6 : 2;
@@ -536,11 +550,11 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows_gqa(GroupRows g, At
     if (r < 0) return;
     const int64_t b = g.row_ptr[r], e = g.row_ptr[r + 1];
     if (e - b > g.row_cap) return;
-    Pointers2 out{a.out0 + r * a.ld0 + c0, a.out1 + r * a.ld1 + c0};
+    Pointers2<E> out{a.out0 + r * a.ld0 + c0, a.out1 + r * a.ld1 + c0};
     float4 dk = zero4(), dv = zero4();
     if (e > b) {
-        const float4 kj = c0 < a.k ? load_slice<VEC>(a.K, a.ldk, r, c0, a.k) : zero4();
-        const float4 vj = c0 < a.kv ? load_slice<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
+        const float4 kj = c0 < a.k ? load_wide<VEC>(a.K, a.ldk, r, c0, a.k) : zero4();
+        const float4 vj = c0 < a.kv ? load_wide<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
         park_put<N>(0, Strides2{a.hq, a.hdo});
         park_put<N>(1, Strides2{a.hstats_in, a.hdelta_in});
         if constexpr (kPark) {
@@ -552,9 +566,9 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows_gqa(GroupRows g, At
             park_fence();
             if constexpr (kPark) {
                 const Strides2 be = park_get<N, Strides2>(5);
-                bwdkv_span<V, VEC>(lane, be.a, be.b, a, kj, vj, g.col_idx, c0, dk, dv);
+                bwdkv_span<V, VEC, E>(lane, be.a, be.b, a, kj, vj, g.col_idx, c0, dk, dv);
             } else {
-                bwdkv_span<V, VEC>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv);
+                bwdkv_span<V, VEC, E>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv);
             }
             if (left != group) {
                 if constexpr (kPark) sk = park_get<N, float4>(2), sv = park_get<N, float4>(3);
@@ -571,7 +585,7 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows_gqa(GroupRows g, At
             const Strides2 s0 = park_get<N, Strides2>(0), s1 = park_get<N, Strides2>(1);
             a.Q += uniform64(s0.a), a.dO += uniform64(s0.b), a.stats_in += uniform64(s1.a), a.delta_in += uniform64(s1.b);
         }
-        if constexpr (kPark) out = park_get<N, Pointers2>(4);
+        if constexpr (kPark) out = park_get<N, Pointers2<E>>(4);
     }
     if (c0 < a.k) store_slice<VEC>(out.k, dk, c0, a.k);
     if (c0 < a.kv) store_slice<VEC>(out.v, dv, c0, a.kv);
@@ -579,8 +593,8 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows_gqa(GroupRows g, At
 
 // a group per long row of T and K/V head c = blockIdx.y: for each query head c * group + i its pieces' partial sums at scratch
 // offset `off`, added in piece order from +0 (k_attn_add_pieces' number), then the heads in head order from head 0's
-template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_attn_add_pieces_gqa(GroupPieces g, int off, float *__restrict__ out, int64_t ld, int w,
+template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) void k_attn_add_pieces_gqa(GroupPieces g, int off, E *__restrict__ out, int64_t ld, int w,
                                                                 int64_t hout, int group)
 {
     const int sub = threadIdx.x & (V - 1), c0 = 4 * sub;
@@ -601,8 +615,8 @@ __global__ __launch_bounds__(kBlock) void k_attn_add_pieces_gqa(GroupPieces g, i
 // one grid per kernel for all heads: x is what a call of one head launches, y the query head within its group of `group`, z
 // the group (the K/V head); group = 1 for the _heads calls.  gqa (backward_kv only): the _gqa call, which sums the heads of a
 // group (k_attn_bwd_kv_rows_gqa, k_attn_add_pieces_gqa; also at group = 1).
-template <int PASS, int V, bool VEC>
-int launch_attn_v(const spmv_csr &h, const AttnArgs &a, int heads, int group, bool gqa, const char *what, hipStream_t s)
+template <int PASS, int V, bool VEC, typename E>
+int launch_attn_v(const spmv_csr &h, const AttnArgsT<E> &a, int heads, int group, bool gqa, const char *what, hipStream_t s)
 {
     const SpmmPlan &p = h.plan_spmm;
     const int64_t nblocks = group_head_blocks(what, h, V, heads);
@@ -610,51 +624,51 @@ int launch_attn_v(const spmv_csr &h, const AttnArgs &a, int heads, int group, bo
     const GroupRows g = group_rows(h, V, nblocks);
     const unsigned kv_heads = (unsigned)(heads / group);
     const dim3 grid((unsigned)nblocks, (unsigned)group, kv_heads), block(kBlock);
-    if constexpr (PASS == kPassForward) hipLaunchKernelGGL((k_attn_fwd_rows<V, VEC>), grid, block, 0, s, g, a);
-    else if constexpr (PASS == kPassBackwardQ) hipLaunchKernelGGL((k_attn_bwd_q_rows<V, VEC>), grid, block, 0, s, g, a);
-    else if (gqa) hipLaunchKernelGGL((k_attn_bwd_kv_rows_gqa<V, VEC>), dim3((unsigned)nblocks, kv_heads), block, 0, s, g, a, group);
-    else hipLaunchKernelGGL((k_attn_bwd_kv_rows<V, VEC>), grid, block, 0, s, g, a);
+    if constexpr (PASS == kPassForward) hipLaunchKernelGGL((k_attn_fwd_rows<V, VEC, E>), grid, block, 0, s, g, a);
+    else if constexpr (PASS == kPassBackwardQ) hipLaunchKernelGGL((k_attn_bwd_q_rows<V, VEC, E>), grid, block, 0, s, g, a);
+    else if (gqa) hipLaunchKernelGGL((k_attn_bwd_kv_rows_gqa<V, VEC, E>), dim3((unsigned)nblocks, kv_heads), block, 0, s, g, a, group);
+    else hipLaunchKernelGGL((k_attn_bwd_kv_rows<V, VEC, E>), grid, block, 0, s, g, a);
     SPMV_LAUNCHED("k_attn_*_rows");
     if (!p.n_long) return SPMV_OK;
     const GroupPieces q = group_pieces(h, h.plan_attn.d_scratch.get());
     const dim3 pgrid(group_grid(p.pieces, V).x, (unsigned)group, kv_heads), lgrid(group_grid(p.n_long, V).x, (unsigned)heads);
     if constexpr (PASS == kPassForward) {
-        hipLaunchKernelGGL((k_attn_fwd_pieces<V, VEC>), pgrid, block, 0, s, q, a);
+        hipLaunchKernelGGL((k_attn_fwd_pieces<V, VEC, E>), pgrid, block, 0, s, q, a);
         SPMV_LAUNCHED("k_attn_fwd_pieces");
-        hipLaunchKernelGGL((k_attn_fwd_combine<V, VEC>), dim3(lgrid.x, (unsigned)group, kv_heads), block, 0, s, q, a);
+        hipLaunchKernelGGL((k_attn_fwd_combine<V, VEC, E>), dim3(lgrid.x, (unsigned)group, kv_heads), block, 0, s, q, a);
         SPMV_LAUNCHED("k_attn_fwd_combine");
     } else if constexpr (PASS == kPassBackwardQ) {
-        hipLaunchKernelGGL((k_attn_bwd_q_pieces<V, VEC>), pgrid, block, 0, s, q, a);
+        hipLaunchKernelGGL((k_attn_bwd_q_pieces<V, VEC, E>), pgrid, block, 0, s, q, a);
         SPMV_LAUNCHED("k_attn_bwd_q_pieces");
-        hipLaunchKernelGGL((k_attn_add_pieces<V, VEC>), lgrid, block, 0, s, q, kAtSums, a.out0, a.ld0, a.k, a.h0);
+        hipLaunchKernelGGL((k_attn_add_pieces<V, VEC, E>), lgrid, block, 0, s, q, kAtSums, a.out0, a.ld0, a.k, a.h0);
         SPMV_LAUNCHED("k_attn_add_pieces");
     } else {
-        hipLaunchKernelGGL((k_attn_bwd_kv_pieces<V, VEC>), pgrid, block, 0, s, q, a);
+        hipLaunchKernelGGL((k_attn_bwd_kv_pieces<V, VEC, E>), pgrid, block, 0, s, q, a);
         SPMV_LAUNCHED("k_attn_bwd_kv_pieces");
         if (gqa) {
             const dim3 cgrid(lgrid.x, kv_heads);
-            hipLaunchKernelGGL((k_attn_add_pieces_gqa<V, VEC>), cgrid, block, 0, s, q, kAtSums, a.out0, a.ld0, a.k, a.h0, group);
+            hipLaunchKernelGGL((k_attn_add_pieces_gqa<V, VEC, E>), cgrid, block, 0, s, q, kAtSums, a.out0, a.ld0, a.k, a.h0, group);
             SPMV_LAUNCHED("k_attn_add_pieces_gqa");
-            hipLaunchKernelGGL((k_attn_add_pieces_gqa<V, VEC>), cgrid, block, 0, s, q, kAtSums2, a.out1, a.ld1, a.kv, a.h1, group);
+            hipLaunchKernelGGL((k_attn_add_pieces_gqa<V, VEC, E>), cgrid, block, 0, s, q, kAtSums2, a.out1, a.ld1, a.kv, a.h1, group);
             SPMV_LAUNCHED("k_attn_add_pieces_gqa");
             return SPMV_OK;
         }
-        hipLaunchKernelGGL((k_attn_add_pieces<V, VEC>), lgrid, block, 0, s, q, kAtSums, a.out0, a.ld0, a.k, a.h0);
+        hipLaunchKernelGGL((k_attn_add_pieces<V, VEC, E>), lgrid, block, 0, s, q, kAtSums, a.out0, a.ld0, a.k, a.h0);
         SPMV_LAUNCHED("k_attn_add_pieces");
-        hipLaunchKernelGGL((k_attn_add_pieces<V, VEC>), lgrid, block, 0, s, q, kAtSums2, a.out1, a.ld1, a.kv, a.h1);
+        hipLaunchKernelGGL((k_attn_add_pieces<V, VEC, E>), lgrid, block, 0, s, q, kAtSums2, a.out1, a.ld1, a.kv, a.h1);
         SPMV_LAUNCHED("k_attn_add_pieces");
     }
     return SPMV_OK;
 }
 
-template <int PASS>
-int launch_attn(const spmv_csr &h, const AttnArgs &a, int heads, int group, bool gqa, bool vec, const char *what, hipStream_t s)
+template <int PASS, typename E>
+int launch_attn(const spmv_csr &h, const AttnArgsT<E> &a, int heads, int group, bool gqa, bool vec, const char *what, hipStream_t s)
 {
     if (h.rows == 0) return SPMV_OK;
     return dispatch_lanes(((a.k > a.kv ? a.k : a.kv) + 3) / 4, [&](auto v) {
         constexpr int V = decltype(v)::value;
-        return vec ? launch_attn_v<PASS, V, true>(h, a, heads, group, gqa, what, s)
-                   : launch_attn_v<PASS, V, false>(h, a, heads, group, gqa, what, s);
+        return vec ? launch_attn_v<PASS, V, true, E>(h, a, heads, group, gqa, what, s)
+                   : launch_attn_v<PASS, V, false, E>(h, a, heads, group, gqa, what, s);
     });
 }
 
@@ -696,11 +710,14 @@ int attention_max_heads(const spmv_csr &h, int width)
     return dispatch_lanes((width + 3) / 4, [&](auto v) { return (int)group_max_heads(h, decltype(v)::value); });
 }
 
-// One call of any of the nine entry points (arguments checked by capi.hip, which also fills `a`): `heads` query heads, `group`
+// One call of any of the entry points (arguments checked by capi.hip, which also fills `a`): `heads` query heads, `group`
 // of them per K/V head (1 for the _heads calls and a call of one head).  sum_group (backward_kv only): a _gqa call, which sums the
-// heads of a group in the kernel, at group = 1 too.  The 16-byte load path needs every ld the pass uses to be a multiple of 4.
-int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgs &a, int heads, int group, bool sum_group, const char *what,
-                     hipStream_t s)
+// heads of a group in the kernel, at group = 1 too.  The vector load path (16 bytes of floats, 8 bytes of 16-bit elements)
+// needs every ld the pass uses to be a multiple of 4.
+namespace {
+template <typename E>
+int launch_attention_e(AttnPass pass, const spmv_csr &h, const AttnArgsT<E> &a, int heads, int group, bool sum_group, const char *what,
+                       hipStream_t s)
 {
     switch (pass) {
         case kPassForward: return launch_attn<kPassForward>(h, a, heads, group, false, vec4({a.ldq, a.ldk, a.ldv, a.ld0}), what, s);
@@ -710,6 +727,26 @@ int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgs &a, int he
             return launch_attn<kPassBackwardKV>(h, a, heads, group, sum_group, vec4({a.ldq, a.ldk, a.ldv, a.lddo, a.ld0, a.ld1}), what, s);
     }
     return SPMV_ERR_INVALID;
+}
+}  // namespace
+
+int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgs &a, int heads, int group, bool sum_group, const char *what,
+                     hipStream_t s)
+{
+    return launch_attention_e(pass, h, a, heads, group, sum_group, what, s);
+}
+
+// the _16 entry points: the same kernels on 16-bit matrices
+int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgsT<bf16> &a, int heads, int group, bool sum_group, const char *what,
+                     hipStream_t s)
+{
+    return launch_attention_e(pass, h, a, heads, group, sum_group, what, s);
+}
+
+int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgsT<fp16> &a, int heads, int group, bool sum_group, const char *what,
+                     hipStream_t s)
+{
+    return launch_attention_e(pass, h, a, heads, group, sum_group, what, s);
 }
 
 }  // namespace spmv

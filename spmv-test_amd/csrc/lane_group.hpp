@@ -44,6 +44,9 @@
 // are 16-byte aligned: the C ABI checks) a slice is one 16-byte access (VEC); the last slice of a k that is no multiple
 // of 4 is then read whole, inside its row's ld floats, and stored below k only.  Otherwise the kernels read and store
 // 4-byte elements, columns below k only.
+// Fused attention also runs on 16-bit matrices (element type E below): a slice is then 8 bytes, bases are 8-byte aligned, the
+// ld % 4 rule decides between one 8-byte access and 2-byte ones, and nothing of the order above changes: an element is widened
+// exactly where it is used and a result is rounded once where it is stored.
 #pragma once
 #include <type_traits>
 #include "spmv_internal.hpp"
@@ -67,32 +70,152 @@ __device__ __forceinline__ int64_t xcd_item64(int64_t bid, int64_t n)
 
 __device__ __forceinline__ float4 zero4() { return make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
 
-// the four columns [c0, c0+4) of row j of a row-major matrix (c0 < w); VEC: one 16-byte load, else the columns below w only
-template <bool VEC>
-__device__ __forceinline__ float4 load_slice(const float *__restrict__ M, int64_t ld, int64_t j, int c0, int w)
+// ---- the element type E of a matrix: float, or 16-bit storage (fused attention only: bf16, fp16 of attention_args.hpp) ----
+// A 16-bit element is widened exactly to fp32 where it is used and an fp32 result is rounded to E once, to nearest even, where
+// it is stored; nothing in between is 16-bit.  Neither direction flushes a subnormal; a NaN stays a NaN (payload unspecified).
+// bf16 is plain integer code; fp16 is the compiler's _Float16 conversions (the host compiles both).
+template <typename E>
+constexpr bool kIs16 = !std::is_same<E, float>::value;
+
+// four 16-bit elements as loaded, 8 bytes: columns c0 and c0 + 1 in lo (the first in the low half), c0 + 2 and c0 + 3 in hi
+struct alignas(8) Packed4 {
+    uint32_t lo, hi;
+};
+
+// a lane's slice as it waits in registers between its load and its use: float4, or the 8 bytes of 16-bit elements
+template <typename E>
+using slice_t = std::conditional_t<kIs16<E>, Packed4, float4>;
+
+template <typename E>
+__device__ __forceinline__ slice_t<E> zero_slice()
 {
-    const float *p = M + j * ld + c0;
-    if (VEC) return *reinterpret_cast<const float4 *>(p);
-    float4 r = zero4();
-    r.x = p[0];
-    if (c0 + 1 < w) r.y = p[1];
-    if (c0 + 2 < w) r.z = p[2];
-    if (c0 + 3 < w) r.w = p[3];
-    return r;
+    if constexpr (kIs16<E>) return Packed4{0u, 0u};
+    else return zero4();
 }
 
-// the columns [c0, c0+4) below w of one output row (c0 < w; vector stores only)
-template <bool VEC>
-__device__ __forceinline__ void store_slice(float *__restrict__ p, float4 a, int c0, int w)
+template <typename E>
+__device__ __forceinline__ float widen16(uint32_t h)      // h < 2^16: the bits of one element
 {
-    if (VEC && c0 + 4 <= w) {
-        *reinterpret_cast<float4 *>(p) = a;
-        return;
+    if constexpr (std::is_same<E, bf16>::value) {
+        const uint32_t u = h << 16;
+        float f;
+        __builtin_memcpy(&f, &u, 4);
+        return f;
+    } else {
+        const uint16_t b = (uint16_t)h;
+        fp16 x;
+        __builtin_memcpy(&x, &b, 2);
+        return (float)x;
     }
-    p[0] = a.x;
-    if (c0 + 1 < w) p[1] = a.y;
-    if (c0 + 2 < w) p[2] = a.z;
-    if (c0 + 3 < w) p[3] = a.w;
+}
+
+// fp32 to the bits of E, round to nearest even (bf16: a NaN keeps its sign and gets the quiet bit; fp16 overflows to Inf)
+template <typename E>
+__device__ __forceinline__ uint32_t round16(float f)
+{
+    if constexpr (std::is_same<E, bf16>::value) {
+        uint32_t u;
+        __builtin_memcpy(&u, &f, 4);
+        if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
+        return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+    } else {
+#if defined(__HIP_DEVICE_COMPILE__)
+        // f is an fp32 number before it is converted: where it is a product (O = acc * r) the compiler would otherwise fold the
+        // multiplication into a mixed-precision fma that rounds the exact product to fp16 once, another number in rare cases
+        asm("" : "+v"(f));
+#endif
+        const fp16 x = (fp16)f;
+        uint16_t b;
+        __builtin_memcpy(&b, &x, 2);
+        return b;
+    }
+}
+
+// the slice as four floats (float: as it is)
+template <typename E>
+__device__ __forceinline__ float4 widen(slice_t<E> s)
+{
+    if constexpr (kIs16<E>)
+        return make_float4(widen16<E>(s.lo & 0xffffu), widen16<E>(s.lo >> 16), widen16<E>(s.hi & 0xffffu), widen16<E>(s.hi >> 16));
+    else return s;
+}
+
+template <typename E>
+__device__ __forceinline__ const uint16_t *bits16(const E *p) { return reinterpret_cast<const uint16_t *>(p); }
+template <typename E>
+__device__ __forceinline__ uint16_t *bits16(E *p) { return reinterpret_cast<uint16_t *>(p); }
+
+// the four columns [c0, c0+4) of row j of a row-major matrix (c0 < w); VEC: one 16-byte load (16-bit elements: one 8-byte
+// load), else the columns below w only, element by element
+template <bool VEC, typename E>
+__device__ __forceinline__ slice_t<E> load_slice(const E *__restrict__ M, int64_t ld, int64_t j, int c0, int w)
+{
+    const E *p = M + j * ld + c0;
+    if constexpr (kIs16<E>) {
+        if (VEC) return *reinterpret_cast<const Packed4 *>(p);
+        const uint16_t *h = bits16(p);
+        Packed4 r{h[0], 0u};
+        if (c0 + 1 < w) r.lo |= (uint32_t)h[1] << 16;
+        if (c0 + 2 < w) r.hi = h[2];
+        if (c0 + 3 < w) r.hi |= (uint32_t)h[3] << 16;
+        return r;
+    } else {
+        if (VEC) return *reinterpret_cast<const float4 *>(p);
+        float4 r = zero4();
+        r.x = p[0];
+        if (c0 + 1 < w) r.y = p[1];
+        if (c0 + 2 < w) r.z = p[2];
+        if (c0 + 3 < w) r.w = p[3];
+        return r;
+    }
+}
+
+// the same, widened: a row's own operand, which stays in registers as floats for the whole row
+template <bool VEC, typename E>
+__device__ __forceinline__ float4 load_wide(const E *__restrict__ M, int64_t ld, int64_t j, int c0, int w)
+{
+    return widen<E>(load_slice<VEC>(M, ld, j, c0, w));
+}
+
+// widen for a slice's second use in a step: the compiler must not keep the first use's four floats alive in between (they
+// would undo the packing: 4 registers per slice instead of 2), so the packed words pass through an empty statement
+template <typename E>
+__device__ __forceinline__ float4 widen_again(slice_t<E> s)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (kIs16<E>) {
+        asm("" : "+v"(s.lo));
+        asm("" : "+v"(s.hi));
+    }
+#endif
+    return widen<E>(s);
+}
+
+// the columns [c0, c0+4) below w of one output row (c0 < w; vector stores only); 16-bit elements are rounded here
+template <bool VEC, typename E>
+__device__ __forceinline__ void store_slice(E *__restrict__ p, float4 a, int c0, int w)
+{
+    if constexpr (kIs16<E>) {
+        const uint32_t x = round16<E>(a.x), y = round16<E>(a.y), z = round16<E>(a.z), v = round16<E>(a.w);
+        if (VEC && c0 + 4 <= w) {
+            *reinterpret_cast<Packed4 *>(p) = Packed4{x | (y << 16), z | (v << 16)};
+            return;
+        }
+        uint16_t *h = bits16(p);
+        h[0] = (uint16_t)x;
+        if (c0 + 1 < w) h[1] = (uint16_t)y;
+        if (c0 + 2 < w) h[2] = (uint16_t)z;
+        if (c0 + 3 < w) h[3] = (uint16_t)v;
+    } else {
+        if (VEC && c0 + 4 <= w) {
+            *reinterpret_cast<float4 *>(p) = a;
+            return;
+        }
+        p[0] = a.x;
+        if (c0 + 1 < w) p[1] = a.y;
+        if (c0 + 2 < w) p[2] = a.z;
+        if (c0 + 3 < w) p[3] = a.w;
+    }
 }
 
 // the lane's partial of a dot product: fma over its n1 = w - c0 columns (at most 4) from +0; +0 for an idle lane

@@ -385,6 +385,10 @@ int attention_max_heads(const spmv_csr &h, int width);   // heads one launch tak
 // sum_group: backward_kv adds the heads of a group in the kernel, as the _gqa call does; `what` names the caller in a refusal)
 int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgs &a, int heads, int group, bool sum_group, const char *what,
                      hipStream_t s);
+int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgsT<bf16> &a, int heads, int group, bool sum_group, const char *what,
+                     hipStream_t s);       // the _16 entry points: matrices of 16-bit elements, every ld and stride in elements
+int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgsT<fp16> &a, int heads, int group, bool sum_group, const char *what,
+                     hipStream_t s);
 // kernels_transpose.hip: spmv_csr_transpose / spmv_csr_transpose_values
 int transpose(const spmv_csr &a, bool keep_map, hipStream_t s, spmv_csr_t **out);
 int transpose_values(spmv_csr &t, const spmv_csr &a, hipStream_t s);

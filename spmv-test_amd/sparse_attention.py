@@ -19,6 +19,8 @@ _backward_kv on T = transpose(A), include/spmv_hip.h "Fused attention"): nothing
 but col_idx, so one holder serves any number of heads: one after the other (heads="loop", the default) or all in one launch
 per kernel (heads="batched": spmv_csr_attention_*_heads).  Both give the same bits.  Grouped-query heads (GQA: K and V
 with H_kv heads, H % H_kv == 0) run on spmv_csr_attention_*_gqa: K and V are not expanded, dK and dV come back per K/V head.
+Q, K and V may also be all torch.bfloat16 or all torch.float16 (spmv_csr_attention_*_16: 16-bit storage, fp32 sums, every output
+rounded once); O and the gradients then have that dtype, stats and delta stay float32.  The composed SparseAttention is fp32 only.
 """
 from __future__ import annotations
 
@@ -29,19 +31,21 @@ import torch
 from . import capi
 
 MAX_K = 64
+FUSED_DTYPES = (torch.float32, torch.bfloat16, torch.float16)      # what the fused passes take (all matrices of a call alike)
 
 
-def _operand(t, name: str, rows: int, k=None):
-    """t as the library takes it: 2-D float32, stride(1) == 1, stride(0) >= k, 16-byte aligned (copied if it is not)."""
-    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
-        raise ValueError(f"SparseAttention: {name} must be a 2-D float32 tensor")
+def _operand(t, name: str, rows: int, k=None, dtypes=(torch.float32,)):
+    """t as the library takes it: 2-D float32 (or another of `dtypes`), stride(1) == 1, stride(0) >= k, aligned to four
+    elements: 16 bytes of floats, 8 of 16-bit elements (copied if it is not)."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in dtypes:
+        raise ValueError(f"SparseAttention: {name} must be a 2-D {' or '.join(str(d).replace('torch.', '') for d in dtypes)} tensor")
     if t.shape[0] != rows:
         raise ValueError(f"SparseAttention: {name} has {t.shape[0]} rows, the pattern needs {rows}")
     if not 1 <= t.shape[1] <= MAX_K:
         raise ValueError(f"SparseAttention: {name} has {t.shape[1]} columns (1 <= k <= {MAX_K})")
     if k is not None and t.shape[1] != k:
         raise ValueError(f"SparseAttention: {name} has {t.shape[1]} columns, its partner has {k}")
-    if t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0:
+    if t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.data_ptr() % (4 * t.element_size()) == 0:
         return t
     return torch.empty(t.shape, dtype=t.dtype, device=t.device).copy_(t)
 
@@ -118,34 +122,38 @@ class SparseAttention:
 def _fused_operand(t, name: str, rows: int, k=None):
     """A 2-D operand as _operand takes it, or (heads, rows, k): every head t[h] must itself be acceptable to the library
     (a column block of a (rows, heads * k) tensor with k % 4 == 0 is); otherwise the whole tensor is copied once into
-    rows padded to a multiple of 4 floats, so that every head starts on a 16-byte boundary."""
+    rows padded to a multiple of 4 elements, so that every head starts on a boundary of four elements (16 bytes of floats, 8
+    of 16-bit elements)."""
     if not isinstance(t, torch.Tensor) or t.dim() != 3:
-        return _operand(t, name, rows, k)
+        return _operand(t, name, rows, k, FUSED_DTYPES)
     if t.shape[0] < 1:
         raise ValueError(f"SparseAttention: {name} has no heads")
-    _operand(t[0], name, rows, k)       # (dtype and shape)
-    w = t.shape[2]
-    if all(t.stride(2) == 1 and t.stride(1) >= w and t[h].data_ptr() % 16 == 0 for h in range(t.shape[0])):
+    _operand(t[0], name, rows, k, FUSED_DTYPES)       # (dtype and shape)
+    w, align = t.shape[2], 4 * t.element_size()
+    if all(t.stride(2) == 1 and t.stride(1) >= w and t[h].data_ptr() % align == 0 for h in range(t.shape[0])):
         return t
-    return _heads_empty(t.shape[0], rows, w, t.device).copy_(t)
+    return _heads_empty(t.shape[0], rows, w, t.device, t.dtype).copy_(t)
 
 
 def _batched_operand(t, name: str, rows: int, k=None):
-    """A (heads, rows, k) operand as one _heads call takes it: stride(2) == 1, stride(1) >= k, head 0 on a 16-byte boundary
-    and, with more than one head, a head stride that is a multiple of 4 floats (0: one head shared by all).  Stacked heads
-    and the column blocks of a (rows, heads * k) tensor with k % 4 == 0 are; anything else is copied once."""
+    """A (heads, rows, k) operand as one _heads call takes it: stride(2) == 1, stride(1) >= k, head 0 on a boundary of four
+    elements (16 bytes of floats, 8 of 16-bit elements) and, with more than one head, a head stride that is a multiple of 4
+    elements (0: one head shared by all).  Stacked heads and the column blocks of a (rows, heads * k) tensor with k % 4 == 0
+    are; anything else is copied once."""
     if t.shape[0] < 1:
         raise ValueError(f"SparseAttention: {name} has no heads")
-    _operand(t[0], name, rows, k)       # (dtype and shape)
+    _operand(t[0], name, rows, k, FUSED_DTYPES)       # (dtype and shape)
     w = t.shape[2]
-    if t.stride(2) == 1 and t.stride(1) >= w and t.data_ptr() % 16 == 0 and (t.shape[0] == 1 or t.stride(0) % 4 == 0):
+    if t.stride(2) == 1 and t.stride(1) >= w and t.data_ptr() % (4 * t.element_size()) == 0 \
+            and (t.shape[0] == 1 or t.stride(0) % 4 == 0):
         return t
-    return _heads_empty(t.shape[0], rows, w, t.device).copy_(t)
+    return _heads_empty(t.shape[0], rows, w, t.device, t.dtype).copy_(t)
 
 
-def _heads_empty(heads: int, rows: int, w: int, device):
-    """(heads, rows, w) float32 whose every head is 16-byte aligned (rows padded to a multiple of 4 floats if need be)."""
-    return torch.empty((heads, rows, (w + 3) // 4 * 4), dtype=torch.float32, device=device)[:, :, :w]
+def _heads_empty(heads: int, rows: int, w: int, device, dtype=torch.float32):
+    """(heads, rows, w) of `dtype` whose every head starts on a boundary of four elements (rows padded to a multiple of 4
+    elements if need be)."""
+    return torch.empty((heads, rows, (w + 3) // 4 * 4), dtype=dtype, device=device)[:, :, :w]
 
 
 class FusedSparseAttentionFunction(torch.autograd.Function):
@@ -163,13 +171,16 @@ class FusedSparseAttentionFunction(torch.autograd.Function):
         Q = operand(Q, "Q", A.rows)
         K = operand(K, "K", A.cols, Q.shape[-1])
         V = operand(V, "V", A.cols)
+        for name, t in (("K", K), ("V", V)):
+            if t.dtype != Q.dtype:
+                raise ValueError(f"SparseAttention: {name} is {t.dtype}, Q is {Q.dtype} (Q, K and V share one dtype)")
         kv = V.shape[-1]
         if Q.dim() == 3:
             heads = Q.shape[0]
             if K.shape[0] != V.shape[0] or heads % K.shape[0] != 0:
                 raise ValueError(f"SparseAttention: Q has {heads} heads, K {K.shape[0]} and V {V.shape[0]}")
             g = heads // K.shape[0]
-            O = _heads_empty(heads, A.rows, kv, V.device)
+            O = _heads_empty(heads, A.rows, kv, V.device, V.dtype)
             stats = torch.empty((heads, A.rows, 2), dtype=torch.float32, device=V.device)
             chunks = att.head_chunks(heads, Q.shape[-1], kv, g) if one_launch else None
             if chunks and g == 1:
@@ -182,7 +193,7 @@ class FusedSparseAttentionFunction(torch.autograd.Function):
                 for h in range(heads):
                     A.attention_forward(Q[h], K[h // g], V[h // g], O[h], stats[h], att.scale)
         else:
-            O = torch.empty((A.rows, kv), dtype=torch.float32, device=V.device)
+            O = torch.empty((A.rows, kv), dtype=V.dtype, device=V.device)
             stats = torch.empty((A.rows, 2), dtype=torch.float32, device=V.device)
             A.attention_forward(Q, K, V, O, stats, att.scale)
         ctx.att = att
@@ -202,9 +213,11 @@ class FusedSparseAttentionFunction(torch.autograd.Function):
         dO = (_batched_operand if one_launch else _fused_operand)(dO, "dO", A.rows, V.shape[-1])
         if batched and dO.shape[0] != Q.shape[0]:
             raise ValueError(f"SparseAttention: dO has {dO.shape[0]} heads, Q {Q.shape[0]}")
+        if dO.dtype != Q.dtype:
+            raise ValueError(f"SparseAttention: dO is {dO.dtype}, Q is {Q.dtype}")
 
         def like(t):
-            return _heads_empty(*t.shape, t.device) if batched else torch.empty(t.shape, dtype=torch.float32, device=t.device)
+            return _heads_empty(*t.shape, t.device, t.dtype) if batched else torch.empty(t.shape, dtype=t.dtype, device=t.device)
 
         # backward_q also makes delta, which backward_kv reads: it runs whichever gradient is asked for
         dQ = like(Q)
@@ -227,6 +240,17 @@ class FusedSparseAttentionFunction(torch.autograd.Function):
                     T.attention_backward_kv_gqa(at(Q), kv(K), kv(V), at(dO), at(stats), at(delta), kv(dK), kv(dV), att.scale)
             return None, dQ if need_q else None, dK if need_k else None, dV if need_v else None
         heads = range(Q.shape[0]) if batched else (None,)
+        if g > 1 and dK is not None and Q.dtype != torch.float32:
+            # 16-bit grouped-query heads: the sum over the heads of a group is fp32 and rounded once, so it stays in the kernel:
+            # one _gqa call per K/V head instead of per-head calls added here (which would round every head's dK and dV first)
+            att.plan_heads(g)
+            for h in heads:
+                A.attention_backward_q(Q[h], K[h // g], V[h // g], O[h], dO[h], stats[h], delta[h], dQ[h], att.scale)
+            for c in range(K.shape[0]):
+                qs = slice(c * g, c * g + g)
+                T.attention_backward_kv_gqa(Q[qs], K[c:c + 1], V[c:c + 1], dO[qs], stats[qs], delta[qs], dK[c:c + 1], dV[c:c + 1],
+                                            att.scale)
+            return None, dQ if need_q else None, dK if need_k else None, dV if need_v else None
         # grouped-query heads: the heads of a group after the first write into dKh, dVh, which are then added to the group's
         # dK, dV: fp32 adds in head order, starting from the first head's value (what the _gqa call does in its kernel)
         dKh, dVh = (like(K[:1])[0], like(V[:1])[0]) if g > 1 and dK is not None else (None, None)
@@ -259,7 +283,10 @@ class FusedSparseAttention:
     spmv_csr_attention_*_gqa call per pass (the kernel adds the heads' dK, dV), in chunks of whole groups; where fewer than
     g heads fit one launch that call runs by the loop.  "loop" runs the per-head calls on K[h // g] and adds each head's dK, dV
     into its group's in head order, starting from the first head's value: the same bits again.  Any other head mismatch is a
-    ValueError.  A query without keys gets a zero row of O.  Calls of one holder are stream-ordered (the plans' scratch).  The
+    ValueError.  16-bit operands: Q, K and V all torch.bfloat16 or all torch.float16 run on spmv_csr_attention_*_16 in every
+    layout above (alignment and strides then count 2-byte elements: a head starts on an 8-byte boundary); O, the saved O and
+    the gradients have that dtype, stats and delta stay float32; every output is the fp32 result rounded once, so with
+    grouped K/V "loop" leaves the sum over a group's heads to one _gqa call per K/V head.  A query without keys gets a zero row of O.  Calls of one holder are stream-ordered (the plans' scratch).  The
     values array that handle creation still asks for is allocated once here and never read."""
 
     def __init__(self, rows: int, cols: int, row_ptr, col_idx, scale: float = 1.0, heads: str = "loop"):
@@ -294,11 +321,15 @@ class FusedSparseAttention:
         else:
             n = -(-heads // fit)
             size = -(-heads // n)
-        if size > self._planned:
-            self.A.attention_plan_heads(size)
-            self.T.attention_plan_heads(size)
-            self._planned = size
+        self.plan_heads(size)
         return [(lo, min(lo + size, heads)) for lo in range(0, heads, size)]
+
+    def plan_heads(self, heads: int) -> None:
+        """Grow both plans to `heads` heads of one launch (an allocation: not inside a graph capture)."""
+        if heads > self._planned:
+            self.A.attention_plan_heads(heads)
+            self.T.attention_plan_heads(heads)
+            self._planned = heads
 
     def close(self) -> None:
         self.T.close()

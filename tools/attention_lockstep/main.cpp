@@ -9,7 +9,10 @@
 // query heads (launch_attention at group = 2): four query heads on two K/V heads, the three passes on both load paths at a V below 16
 // and at V = 16 (where k_attn_bwd_kv_rows_gqa parks its sums in LDS), the scratch sized for exactly four heads: O, stats,
 // delta and dQ bit for bit the single-head runs on K, V of head y / 2, dK and dV bit for bit those runs' results added in
-// head order from the first head's value.
+// head order from the first head's value.  Then the same four heads on two K/V heads on 16-bit matrices (bf16 and fp16; (6, 10)
+// and (40, 64); both load paths): every array an exactly sized heap block of 2-byte elements, O, dQ, dK and dV bit for bit the
+// program's own fp32 _gqa runs on the widened data, rounded to nearest even by a conversion written here, stats and delta those
+// runs' bits.
 #include "kernels_attention.hip"
 #include "kernels_sddmm.hip"
 #include <algorithm>
@@ -335,6 +338,151 @@ static int gqa_runs(spmv_csr &A, spmv_csr &T, const Pattern &a, float scale, std
     return status;
 }
 
+// ---- 16-bit matrices ------------------------------------------------------------------------------------------------------
+// fp32 to the bits of E, to nearest even, written apart from lane_group.hpp's round16: the two neighbours of f in E are found
+// by dropping bits, the nearer wins, a tie goes to the even one (fp16: the compiler's conversion, as in the kernels)
+template <typename E> static uint16_t to16(float f)
+{
+    if constexpr (std::is_same<E, fp16>::value) {
+        const fp16 x = (fp16)f;
+        uint16_t b;
+        std::memcpy(&b, &x, 2);
+        return b;
+    } else {
+        uint32_t u;
+        std::memcpy(&u, &f, 4);
+        if (f != f) return (uint16_t)((u >> 16) | 0x40u);
+        const uint32_t lo = u & 0xffff0000u, hi = lo + 0x10000u;        // (hi may be Inf: the magnitude bits just count up)
+        float fl, fh;
+        std::memcpy(&fl, &lo, 4);
+        std::memcpy(&fh, &hi, 4);
+        if (lo == u || std::isinf(f)) return (uint16_t)(u >> 16);
+        const double dl = std::fabs((double)f - (double)fl), dh = std::isinf(fh) ? std::ldexp(1.0, 120) : std::fabs((double)fh - (double)f);
+        const bool up = std::isinf(fh) ? (u & 0xffffu) >= 0x8000u : dh < dl || (dh == dl && ((lo >> 16) & 1u));
+        return (uint16_t)((up ? hi : lo) >> 16);
+    }
+}
+
+template <typename E> static float from16(uint16_t b)
+{
+    if constexpr (std::is_same<E, fp16>::value) {
+        fp16 x;
+        std::memcpy(&x, &b, 2);
+        return (float)x;
+    } else {
+        const uint32_t u = (uint32_t)b << 16;
+        float f;
+        std::memcpy(&f, &u, 4);
+        return f;
+    }
+}
+
+// the 16-bit twin of a HeadsMatrix: the same ld and stride in elements, an exactly sized block of 2-byte elements (8-byte
+// aligned; it ends where the last row of the last head does: at its width, on the 8-byte path at the end of its last slice);
+// src: the fp32 block whose elements it holds rounded, or none (an output: NaN bits)
+template <typename E> static E *twin16(const HeadsMatrix &m, int heads, int64_t rows, int w, bool vec, bool fill)
+{
+    const size_t n = (size_t)((heads - 1) * m.stride + (rows - 1) * m.ld + (vec ? (w + 3) / 4 * 4 : w));
+    uint16_t *p = (uint16_t *)malloc(2 * n);
+    for (size_t i = 0; i < n; ++i) p[i] = 0x7fffu;
+    if (fill)
+        for (int y = 0; y < heads; ++y)
+            for (int64_t r = 0; r < rows; ++r)
+                for (int c = 0; c < w; ++c) p[y * m.stride + r * m.ld + c] = to16<E>(m.p[y * m.stride + r * m.ld + c]);
+    return (E *)p;
+}
+
+// how many of the heads x rows x w elements differ in a bit from the fp32 block's, rounded (a NaN against a NaN is no difference)
+template <typename E> static long differs16(const E *got, const HeadsMatrix &m, int heads, int64_t rows, int w)
+{
+    long bad = 0;
+    const uint16_t *g = (const uint16_t *)got;
+    for (int y = 0; y < heads; ++y)
+        for (int64_t r = 0; r < rows; ++r)
+            for (int c = 0; c < w; ++c) {
+                const float want = m.p[y * m.stride + r * m.ld + c];
+                const uint16_t b = g[y * m.stride + r * m.ld + c];
+                bad += want != want ? from16<E>(b) == from16<E>(b) : b != to16<E>(want);
+            }
+    return bad;
+}
+
+// Four query heads on two K/V heads on 16-bit matrices against the program's own fp32 _gqa runs on the same, widened data.
+template <typename E> static int runs16(const char *name, spmv_csr &A, spmv_csr &T, const Pattern &a, float scale, std::mt19937 &rng)
+{
+    constexpr int H = 4, G = 2, C2 = H / G;
+    const int shapes[][2] = {{6, 10}, {40, 64}};
+    const int64_t R = a.rows, C = a.cols;
+    int status = 0;
+    plan_heads(A, H);
+    plan_heads(T, H);
+    for (auto &kk : shapes)
+        for (int odd = 0; odd < 2; ++odd) {
+            const int k = kk[0], kv = kk[1];
+            int V = 1;
+            while (4 * V < std::max(k, kv)) V *= 2;
+            g_group_lanes = V;
+            auto ld = [&](int w) { return (int64_t)(odd ? w + 1 + ((w + 1) % 4 == 0) : (w + 3) / 4 * 4 + 4); };
+            auto make = [&](int heads, int64_t rows, int w) { return heads_matrix(heads, rows, w, ld(w), (rows * ld(w) + 3) / 4 * 4 + 8, !odd); };
+            HeadsMatrix hQ = make(H, R, k), hK = make(C2, C, k), hV = make(C2, C, kv), hdO = make(H, R, kv), hO = make(H, R, kv),
+                        hdQ = make(H, R, k), hdK = make(C2, C, k), hdV = make(C2, C, kv);
+            // inputs: normal numbers with +0 and -0 among them, every one a number of E
+            std::normal_distribution<float> nd(0.f, 1.f);
+            auto fill = [&](const HeadsMatrix &m, int heads, int64_t rows, int w) {
+                for (int y = 0; y < heads; ++y)
+                    for (int64_t r = 0; r < rows; ++r)
+                        for (int c = 0; c < w; ++c) {
+                            const unsigned z = rng() % 64;
+                            m.p[y * m.stride + r * m.ld + c] = z == 0 ? 0.0f : z == 1 ? -0.0f : from16<E>(to16<E>(nd(rng)));
+                        }
+            };
+            fill(hQ, H, R, k), fill(hK, C2, C, k), fill(hV, C2, C, kv), fill(hdO, H, R, kv);
+            const int64_t sstats = 2 * R + 2, sdelta = R + 3;
+            const size_t nstats = (size_t)((H - 1) * sstats + 2 * R), ndelta = (size_t)((H - 1) * sdelta + R);
+            float *stats = (float *)malloc(4 * nstats), *delta = (float *)malloc(4 * ndelta);
+            float *stats16 = (float *)malloc(4 * nstats), *delta16 = (float *)malloc(4 * ndelta);
+            const HeadsMatrix ms{stats, 0, sstats}, md{delta, 0, sdelta};
+            // the fp32 runs; backward_q reads the rounded O, as the 16-bit call does
+            status |= forward(A, H, G, scale, k, kv, hQ, hK, hV, hO, ms);
+            HeadsMatrix hO16 = make(H, R, kv);
+            for (int y = 0; y < H; ++y)
+                for (int64_t r = 0; r < R; ++r)
+                    for (int c = 0; c < kv; ++c) hO16.p[y * hO.stride + r * hO.ld + c] = from16<E>(to16<E>(hO.p[y * hO.stride + r * hO.ld + c]));
+            status |= backward_q(A, H, G, scale, k, kv, hQ, hK, hV, hO16, hdO, ms, md, hdQ);
+            status |= backward_kv(T, H, G, true, scale, k, kv, hQ, hK, hV, hdO, ms, md, hdK, hdV);
+            // the 16-bit runs on exactly sized blocks of 2-byte elements
+            const bool vec = !odd;
+            E *Q = twin16<E>(hQ, H, R, k, vec, true), *K = twin16<E>(hK, C2, C, k, vec, true), *Vm = twin16<E>(hV, C2, C, kv, vec, true);
+            E *dO = twin16<E>(hdO, H, R, kv, vec, true), *O = twin16<E>(hO, H, R, kv, vec, false), *dQ = twin16<E>(hdQ, H, R, k, vec, false);
+            E *dK = twin16<E>(hdK, C2, C, k, vec, false), *dV = twin16<E>(hdV, C2, C, kv, vec, false);
+            AttnArgsT<E> in{};
+            in.scale = scale, in.k = k, in.kv = kv;
+            in.Q = Q, in.ldq = hQ.ld, in.hq = hQ.stride, in.K = K, in.ldk = hK.ld, in.hk = hK.stride, in.V = Vm, in.ldv = hV.ld, in.hv = hV.stride;
+            AttnArgsT<E> f = in, bq = in, bk = in;
+            f.out0 = O, f.ld0 = hO.ld, f.h0 = hO.stride, f.stats = stats16, f.hstats = sstats;
+            status |= launch_attention(kPassForward, A, f, H, G, false, "forward_16", nullptr);
+            bq.O = O, bq.ldo = hO.ld, bq.ho = hO.stride, bq.dO = dO, bq.lddo = hdO.ld, bq.hdo = hdO.stride;
+            bq.stats_in = stats16, bq.hstats_in = sstats, bq.delta = delta16, bq.hdelta = sdelta, bq.out0 = dQ, bq.ld0 = hdQ.ld, bq.h0 = hdQ.stride;
+            status |= launch_attention(kPassBackwardQ, A, bq, H, G, false, "backward_q_16", nullptr);
+            bk.dO = dO, bk.lddo = hdO.ld, bk.hdo = hdO.stride, bk.stats_in = stats16, bk.hstats_in = sstats, bk.delta_in = delta16, bk.hdelta_in = sdelta;
+            bk.out0 = dK, bk.ld0 = hdK.ld, bk.h0 = hdK.stride, bk.out1 = dV, bk.ld1 = hdV.ld, bk.h1 = hdV.stride;
+            status |= launch_attention(kPassBackwardKV, T, bk, H, G, true, "backward_kv_16", nullptr);
+            long bad = differs16<E>(O, hO, H, R, kv) + differs16<E>(dQ, hdQ, H, R, k) + differs16<E>(dK, hdK, C2, C, k) + differs16<E>(dV, hdV, C2, C, kv);
+            for (int y = 0; y < H; ++y) {
+                bad += std::memcmp(stats16 + y * sstats, stats + y * sstats, 8 * (size_t)R) != 0;
+                bad += std::memcmp(delta16 + y * sdelta, delta + y * sdelta, 4 * (size_t)R) != 0;
+            }
+            printf("%s heads %d group %d k %d kv %d V %d %s: status %d, %ld elements differ in a bit from the fp32 runs on the widened data, rounded\n",
+                   name, H, G, k, kv, V, odd ? "2-byte path" : "8-byte path", status, bad);
+            if (bad) status |= 256;
+            for (void *p : {(void *)hQ.p, (void *)hK.p, (void *)hV.p, (void *)hdO.p, (void *)hO.p, (void *)hO16.p, (void *)hdQ.p, (void *)hdK.p,
+                            (void *)hdV.p, (void *)stats, (void *)delta, (void *)stats16, (void *)delta16, (void *)Q, (void *)K, (void *)Vm,
+                            (void *)dO, (void *)O, (void *)dQ, (void *)dK, (void *)dV})
+                free(p);
+        }
+    return status;
+}
+
 int main()
 {
     std::mt19937 rng(11);
@@ -453,6 +601,8 @@ int main()
         }
     status |= heads_runs(A, T, a, scale, rng);
     status |= gqa_runs(A, T, a, scale, rng);
+    status |= runs16<bf16>("bf16", A, T, a, scale, rng);
+    status |= runs16<fp16>("fp16", A, T, a, scale, rng);
     for (void *p : owned) free(p);
     free(A.plan_attn.d_scratch.p);
     free(T.plan_attn.d_scratch.p);

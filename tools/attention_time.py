@@ -30,6 +30,15 @@ grouped / expanded (below 1: grouped is faster), the lowest and highest window o
 step allocates.  Nothing here sets a threshold.
 
     python tools/attention_time.py --gqa 2,4,8 [--workloads band4096x64,...] [--ks 16,64] [--out profiles/attention_gqa.jsonl]
+
+--dtype bf16[,fp16]: 16-bit operands.  On the same pattern arrays two FusedSparseAttention holders, one called on float32 Q, K, V
+and dO and one on the same numbers in the 16-bit dtype (spmv_csr_attention_*_16), by the same protocol: the windows alternating,
+median of --reps, the lowest and highest window of each.  One JSON line per (workload, k = kv, dtype): forward and
+forward-plus-backward time of both, the ratios 16-bit / fp32 (below 1: 16-bit is faster), and the bytes a step allocates.  The
+fp32 path is the yardstick; nothing here sets a threshold.
+
+    python tools/attention_time.py --dtype bf16,fp16 [--workloads c2:8192,c2:0,c3:8192,c3:0] [--ks 16,32,64]
+                                   [--out profiles/attention_16bit.jsonl]
 """
 import argparse
 import json
@@ -233,6 +242,67 @@ def gqa_main(a, emit):
         torch.cuda.empty_cache()
 
 
+def dtype_main(a, emit):
+    """16-bit operands against float32 ones on the fused passes (see the module docstring)."""
+    import torch
+    pkg = ge.load_package()
+    capi, W, SA = pkg.capi, pkg.workloads, pkg.sparse_attention
+    dev = torch.device("cuda:0")
+    scales = dict((s.split("=")[0], float(s.split("=")[1])) for s in a.scale.split(",") if s)
+    dtypes = {"bf16": torch.bfloat16, "fp16": torch.float16}
+    med, r4 = statistics.median, lambda x: round(x, 4)      # noqa: E731
+    for spec in (a.workloads or "c2:8192,c2:0,c3:8192,c3:0").split(","):
+        name, rows, cols, d_rp, d_ci = heads_pattern(spec.partition("@")[0], capi, W, dev, scales)
+        wide = SA.FusedSparseAttention(rows, cols, d_rp, d_ci, scale=0.25)
+        narrow = SA.FusedSparseAttention(rows, cols, d_rp, d_ci, scale=0.25)
+        for k in (int(s) for s in a.ks.split(",")):
+            for dname in a.dtype.split(","):
+                gen = torch.Generator(device=dev).manual_seed(k)
+                ops32 = [torch.randn((n, k), generator=gen, device=dev) for n in (rows, cols, cols, rows)]
+                ops16 = [t.to(dtypes[dname]) for t in ops32]
+                ops32 = [t.float() for t in ops16]                      # (the same numbers on both sides)
+                sets = {}
+                for att, (Q, K, V, dO) in ((wide, ops32), (narrow, ops16)):
+                    sets[att] = (Q, K, V, dO) + tuple(t.clone().requires_grad_(True) for t in (Q, K, V))
+
+                def forward(att):
+                    Q, K, V = sets[att][:3]
+                    with torch.no_grad():
+                        att(Q, K, V)
+
+                def step(att):
+                    dO, q, kk, v = sets[att][3:]
+                    att(q, kk, v).backward(dO)
+                    q.grad = kk.grad = v.grad = None
+
+                def step_bytes(att):
+                    step(att)
+                    torch.cuda.synchronize()
+                    torch.cuda.reset_peak_memory_stats()
+                    before = torch.cuda.memory_allocated()
+                    step(att)
+                    torch.cuda.synchronize()
+                    return torch.cuda.max_memory_allocated() - before
+
+                n_f, w_f, it_f = timed_windows(lambda: forward(narrow), lambda: forward(wide), a.window_ms, a.reps, a.max_iters)
+                n_s, w_s, it_s = timed_windows(lambda: step(narrow), lambda: step(wide), a.window_ms, a.reps, a.max_iters)
+                with torch.no_grad():
+                    diff = float((narrow(*ops16[:3]).float() - wide(*ops32[:3])).abs().max())
+                emit(workload=name, dtype=dname, k=k, kv=k, rows=rows, cols=cols, nnz=int(d_ci.numel()), plan=wide.A.spmm_describe(),
+                     plan_T=wide.T.spmm_describe(), iters_forward=it_f, iters_step=it_s, reps=a.reps,
+                     narrow_forward_ms=r4(med(n_f)), fp32_forward_ms=r4(med(w_f)), forward_ratio=round(med(n_f) / med(w_f), 3),
+                     narrow_forward_windows=[r4(min(n_f)), r4(max(n_f))], fp32_forward_windows=[r4(min(w_f)), r4(max(w_f))],
+                     narrow_step_ms=r4(med(n_s)), fp32_step_ms=r4(med(w_s)), step_ratio=round(med(n_s) / med(w_s), 3),
+                     narrow_step_windows=[r4(min(n_s)), r4(max(n_s))], fp32_step_windows=[r4(min(w_s)), r4(max(w_s))],
+                     narrow_step_bytes=step_bytes(narrow), fp32_step_bytes=step_bytes(wide), max_abs_diff_O=diff)
+                del ops32, ops16, sets
+                torch.cuda.empty_cache()
+        wide.close()
+        narrow.close()
+        del d_rp, d_ci
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default=None, help="default: c2:8192,c2:0,c3:8192,c3:0,c4:8192,c4:0; with --heads: " + HEADS_WORKLOADS)
@@ -240,6 +310,7 @@ def main():
     ap.add_argument("--heads", default=None, help="H[,H..]: time heads=\"loop\" against heads=\"batched\" at these head counts")
     ap.add_argument("--gqa", default=None, help="G[,G..]: time grouped K/V against K/V expanded with repeat_interleave at these group sizes")
     ap.add_argument("--gqa-heads", type=int, default=16, help="query heads of the --gqa runs")
+    ap.add_argument("--dtype", default=None, help="bf16[,fp16]: time 16-bit operands against float32 ones on the fused passes")
     ap.add_argument("--scale", default="", help="name=fraction of the rows, e.g. c4=0.5 where the memory does not hold the full size")
     ap.add_argument("--window-ms", type=float, default=200.0)
     ap.add_argument("--max-iters", type=int, default=50)
@@ -262,6 +333,10 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if a.dtype:
+        a.ks = a.ks or "16,32,64"
+        dtype_main(a, emit)
+        return
     if a.gqa:
         a.ks = a.ks or "16,64"
         gqa_main(a, emit)
