@@ -206,10 +206,20 @@ SPMV_API int spmv_csr_destroy(spmv_csr_t *h);
  * resolved to one of them) answer SPMV_ERR_STALE_PLAN until re-planned.  On a handle without a map (keep_map = 0, or not
  * made by spmv_csr_transpose): SPMV_ERR_INVALID, nothing launched.
  *
+ * spmv_csr_transpose_gather: dst[c * dst_stride + i] = src[c * src_stride + map[i]] for c < count, i < nnz, through the map of
+ * a handle made with keep_map = 1: `count` arrays of nnz 32-bit words in the parent's storage order brought into t's, copied
+ * as bits (a NaN keeps its payload, -0.0 its sign).  It is how the bias of the _bias attention calls below reaches
+ * backward_kv.  One launch that reads the map once; src and dst need 4-byte alignment only and must not overlap; strides
+ * count words.  Asynchronous, allocates nothing, never waits: graph-capturable.  It touches neither t's vals nor its plans.
+ * SPMV_ERR_INVALID, nothing launched: a handle without a map; count < 1; a null array while nnz > 0; an array that is not
+ * 4-byte aligned; a negative stride; dst_stride < nnz with count > 1.
+ *
  * spmv_csr_transpose_map_bytes: device bytes of the kept map (4 * nnz; 0 without one or for a handle not made by
  * spmv_csr_transpose; < 0: null handle). */
 SPMV_API int spmv_csr_transpose(const spmv_csr_t *a, int keep_map, void *stream, spmv_csr_t **out);
 SPMV_API int spmv_csr_transpose_values(spmv_csr_t *t, const spmv_csr_t *a, void *stream);
+SPMV_API int spmv_csr_transpose_gather(const spmv_csr_t *t, int count, const void *d_src, int64_t src_stride, void *d_dst,
+                                       int64_t dst_stride, void *stream);
 SPMV_API int64_t spmv_csr_transpose_map_bytes(const spmv_csr_t *t);
 
 /* ---- the hot path ------------------------------------------------------
@@ -615,6 +625,57 @@ SPMV_API int spmv_csr_attention_backward_kv_16(spmv_csr_t *t, const spmv_attn_he
                                                const void *d_V, int64_t ldv, const void *d_dO, int64_t lddo,
                                                const float *d_stats, const float *d_delta, void *d_dK, int64_t lddk,
                                                void *d_dV, int64_t lddv, void *stream);
+
+/* ---- Fused attention with an additive bias per nonzero, and the bias's gradient: all three passes ---------------------------
+ * O = softmax_rows(scale * Q K^T + B at the pattern) V with one fp32 number per (query, key) pair of the pattern: a
+ * relative-position table, ALiBi slopes, edge features, a soft mask, or -Inf to switch a listed key off without rebuilding
+ * the handle.  Only the most general form exists, as for _16: the arguments are the _16 call's with the bias arguments after
+ * dtype, and dtype also takes SPMV_ATTN_FP32 = 0 (fp32 matrices, the _gqa call's units and alignment; the _16 calls go on
+ * refusing 0).
+ * The bias.  d_bias holds nnz floats per query head in the storage order of the handle it is passed with: position n
+ * belongs to col_idx[n]; on a row block with a rebased row_ptr, n is the position in that handle's col_idx.  It is fp32
+ * whatever dtype is, and an array of its own: the handle's vals is still never read.  bias_stride counts floats from query
+ * head y to y + 1; 0 means one bias for all heads.  The bias belongs to the QUERY head: within a group each query head uses
+ * its own in backward_kv too.  backward_kv runs on the transposed handle and takes d_bias_t, the bias in t's storage order
+ * (bias_t[i] = bias[map[i]]): spmv_csr_transpose_gather makes it, for all heads in one call.
+ * The score (part of the interface).  The score of nonzero n is  t = fl(fl(scale * s) + bias[n]):  s is spmv_csr_sddmm's
+ * number, unchanged; the product is rounded first, then one fp32 addition is made (not an fma).  Everything after t is the
+ * documented order of "Fused attention", word for word, in all three passes: the online softmax, stats = (M, 1/l),
+ * p = expf(t - M_i) * r_i, delta, the chains and the pieces.  Both backward passes recompute t with the bias, so the three
+ * passes agree on every p.  Consequences:
+ *   - a bias of -0.0f everywhere gives, bit for bit, what the matching _gqa call (dtype 0) or _16 call gives: x + (-0) = x
+ *     for every x, -0 included;
+ *   - a bias of -Inf beside a finite maximum removes the nonzero exactly (e = +0, p = +0);
+ *   - a NaN or +Inf bias, or a row whose every t is -Inf, behaves as the same t does without a bias: a NaN row.
+ * The gradient.  dBias[n] = fl(p * fl(dp - delta_i)): the two inner roundings of ds, and ds = fl(scale * dBias[n]) keeps its
+ * bits.  backward_q writes it on the pattern handle, in storage order, per query head at y * dbias_stride (always per head:
+ * a caller who shares one bias sums dBias over the heads, as _heads callers do for a shared K and V).  Every position of
+ * [0, nnz) is written exactly once, positions of rows in pieces and positions whose p is 0 (they hold +-0) included; no
+ * atomics.  d_dbias may be NULL: nothing is written, dQ and delta are the same bits.  dbias_stride must be >= nnz when
+ * heads > 1 and needs to be a multiple of nothing.
+ * The plan, the scratch, _plan_heads, _max_heads and SPMV_ERR_NOT_PLANNED are the unbiased calls'; after the plan the calls
+ * allocate nothing and never wait: graph-capturable.  Of nnz size a pass reads col_idx and the bias (8 bytes per nonzero
+ * and head; backward_q with dBias 12).
+ * Refusals (SPMV_ERR_INVALID, a message that names the function, nothing launched, every output untouched), after the
+ * header of hs and the group and before the rest: a dtype outside {0, 1, 2}; a null d_bias while nnz > 0; a bias or dBias
+ * pointer that is not 4-byte aligned; a negative stride; dbias_stride < nnz with heads > 1 and a non-null d_dbias; then
+ * everything the _gqa call (dtype 0) or the _16 call of that dtype refuses. */
+enum { SPMV_ATTN_FP32 = 0 };
+SPMV_API int spmv_csr_attention_forward_bias(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, int dtype, const float *d_bias,
+                                             int64_t bias_stride, float scale, int k, const void *d_Q, int64_t ldq,
+                                             const void *d_K, int64_t ldk, int kv, const void *d_V, int64_t ldv, void *d_O,
+                                             int64_t ldo, float *d_stats, void *stream);
+SPMV_API int spmv_csr_attention_backward_q_bias(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, int dtype,
+                                                const float *d_bias, int64_t bias_stride, float *d_dbias, int64_t dbias_stride,
+                                                float scale, int k, const void *d_Q, int64_t ldq, const void *d_K, int64_t ldk,
+                                                int kv, const void *d_V, int64_t ldv, const void *d_O, int64_t ldo,
+                                                const void *d_dO, int64_t lddo, const float *d_stats, float *d_delta,
+                                                void *d_dQ, int64_t lddq, void *stream);
+SPMV_API int spmv_csr_attention_backward_kv_bias(spmv_csr_t *t, const spmv_attn_heads_t *hs, int group, int dtype,
+                                                 const float *d_bias_t, int64_t bias_stride, float scale, int k, const void *d_Q,
+                                                 int64_t ldq, const void *d_K, int64_t ldk, int kv, const void *d_V, int64_t ldv,
+                                                 const void *d_dO, int64_t lddo, const float *d_stats, const float *d_delta,
+                                                 void *d_dK, int64_t lddk, void *d_dV, int64_t lddv, void *stream);
 
 /* ---- dense baselines (reference slots cublas / naive / tiling) ---------
  * y[i] = sum_j x[j] * A[j*N+i] on the dense device matrix.

@@ -56,6 +56,7 @@ SIGNATURES = {
     "spmv_csr_destroy": (C.c_int, [_H]),
     "spmv_csr_transpose": (C.c_int, [_H, C.c_int, _vp, _HP]),
     "spmv_csr_transpose_values": (C.c_int, [_H, _H, _vp]),
+    "spmv_csr_transpose_gather": (C.c_int, [_H, C.c_int, _vp, C.c_int64, _vp, C.c_int64, _vp]),
     "spmv_csr_transpose_map_bytes": (C.c_int64, [_H]),
     "spmv_csr_plan": (C.c_int, [_H, C.c_int, _vp]),
     "spmv_csr_run": (C.c_int, [_H, C.c_int, _f32p, _f32p, _vp]),
@@ -129,7 +130,10 @@ for _pass, _ops in _ATTN_PASSES.items():
         SIGNATURES[f"spmv_csr_attention_{_pass}{_suffix}"] = (C.c_int, _head + [C.c_float, C.c_int] + _tail + [_vp])
     # the 16-bit call of the pass: the _gqa arguments with `int dtype` after group; every matrix pointer is a void *
     SIGNATURES[f"spmv_csr_attention_{_pass}_16"] = (C.c_int, [_H, _HS, C.c_int, C.c_int, C.c_float, C.c_int] + _tail + [_vp])
-ATTN_BF16, ATTN_FP16 = 1, 2      # enum of include/spmv_hip.h: the dtype of a _16 call
+    # the biased call of the pass: the _16 arguments with (bias, bias_stride) -- backward_q: and (dBias, dbias_stride) -- after dtype
+    SIGNATURES[f"spmv_csr_attention_{_pass}_bias"] = (C.c_int, [_H, _HS, C.c_int, C.c_int] + [_f32p, C.c_int64] * (2 if _pass == "backward_q" else 1)
+                                                      + [C.c_float, C.c_int] + _tail + [_vp])
+ATTN_FP32, ATTN_BF16, ATTN_FP16 = 0, 1, 2      # enums of include/spmv_hip.h: the dtype of a _16 call (1, 2) or a _bias call
 # test only: the bounds-checked build of the library (SPMV_CHECK_BOUNDS) and its sites (csrc/spmv_internal.hpp BoundsSite)
 CHECKED_LIB_PATH = PKG_DIR / "lib" / "libspmv_hip_checked.so"
 BOUNDS_SITES = ("k_bs_sums prod", "k_bs_sums acc", "k_bin_sums prod", "k_bin_sums r16", "k_bs_products c16",
@@ -278,6 +282,21 @@ class CsrMatrix:
         """Refresh this handle's values (made by ``a.transpose(keep_map=True)``) from ``a``'s values as they are now:
         one gather launch, asynchronous, graph-capturable; then what :meth:`values_changed` does."""
         check(lib().spmv_csr_transpose_values(self._h, a._h, _stream_handle(stream)))
+
+    def transpose_gather(self, src, dst, stream=None) -> None:
+        """On a handle made by ``a.transpose(keep_map=True)``: ``dst[..., i] = src[..., map[i]]``, arrays of nnz 32-bit elements
+        in ``a``'s storage order brought into this handle's (the bias of the _bias attention calls for backward_kv).  src, dst:
+        (nnz,) or (count, nnz) of one 4-byte dtype with stride(-1) == 1; copied as bits, in one launch."""
+        import torch
+        for name, t in (("src", src), ("dst", dst)):
+            if not isinstance(t, torch.Tensor) or t.dim() not in (1, 2) or t.element_size() != 4 or t.stride(-1) != 1 \
+                    or t.shape[-1] != self.nnz:
+                raise ValueError(f"transpose_gather: {name} must be (nnz,) or (count, nnz) of 4-byte elements with stride(-1) == 1")
+        if src.dtype != dst.dtype or src.shape != dst.shape:
+            raise ValueError(f"transpose_gather: src is {src.dtype} {tuple(src.shape)}, dst {dst.dtype} {tuple(dst.shape)}")
+        count = src.shape[0] if src.dim() == 2 else 1
+        stride = lambda t: t.stride(0) if count > 1 else 0
+        check(lib().spmv_csr_transpose_gather(self._h, count, _ptr(src), stride(src), _ptr(dst), stride(dst), _stream_handle(stream)))
 
     def transpose_map_bytes(self) -> int:
         n = lib().spmv_csr_transpose_map_bytes(self._h)
@@ -481,13 +500,41 @@ class CsrMatrix:
         g - 1 added in the kernel in head order, starting from the first head's value."""
         self._attention_call("backward_kv", "gqa", (Q, K, V, dO, stats, delta, dK, dV), scale, stream)
 
-    def _attention_call(self, spec: str, mode: str, tensors, scale: float, stream) -> None:
-        """All nine attention calls: pass `spec` of _ATTN_PASSES in `mode` of _ATTN_MODES on `tensors` in the spec's order.
+    # -- fused attention with an additive bias per nonzero (spmv_csr_attention_*_bias; the _gqa layout, any of the three dtypes) --
+    def attention_forward_bias(self, Q, K, V, bias, O, stats, scale: float = 1.0, stream=None) -> None:
+        """attention_forward_gqa on the scores scale * s + bias.  bias: float32 (nnz,), shared by the heads, or (H, nnz), in this
+        handle's storage order, whatever the dtype of the matrices (float32, bfloat16 or float16)."""
+        self._attention_call("forward", "gqa", (Q, K, V, O, stats), scale, stream, bias=(bias,))
+
+    def attention_backward_q_bias(self, Q, K, V, bias, O, dO, stats, delta, dQ, dBias=None, scale: float = 1.0, stream=None) -> None:
+        """attention_backward_q_gqa with the bias; dBias: float32 (H, nnz), the gradient of the bias per query head (sum it
+        over the heads for a shared bias), or None: not written."""
+        self._attention_call("backward_q", "gqa", (Q, K, V, O, dO, stats, delta, dQ), scale, stream, bias=(bias, dBias))
+
+    def attention_backward_kv_bias(self, Q, K, V, bias_t, dO, stats, delta, dK, dV, scale: float = 1.0, stream=None) -> None:
+        """On the handle of the TRANSPOSED pattern: attention_backward_kv_gqa with bias_t, the bias in this handle's storage
+        order (:meth:`transpose_gather` makes it)."""
+        self._attention_call("backward_kv", "gqa", (Q, K, V, dO, stats, delta, dK, dV), scale, stream, bias=(bias_t,))
+
+    def _attention_bias(self, what: str, heads: int, bias, dBias=None) -> list:
+        """The C arguments of a _bias call's bias: (pointer, stride) of the bias and, if the pass has one, of dBias."""
+        import torch
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or bias.stride(-1) != 1 \
+                or tuple(bias.shape) not in ((self.nnz,), (heads, self.nnz)):
+            raise ValueError(f"{what}: bias must be a float32 tensor of ({self.nnz},) or ({heads}, {self.nnz}) with stride(-1) == 1")
+        args = [_ptr(bias), bias.stride(0) if bias.dim() == 2 and heads > 1 else 0]
+        if dBias is not None and (not isinstance(dBias, torch.Tensor) or dBias.dtype != torch.float32 or dBias.stride(-1) != 1
+                                  or tuple(dBias.shape) != (heads, self.nnz)):
+            raise ValueError(f"{what}: dBias must be None or a float32 tensor of ({heads}, {self.nnz}) with stride(-1) == 1")
+        return args + [_ptr(dBias) if dBias is not None else None, dBias.stride(0) if dBias is not None and heads > 1 else 0]
+
+    def _attention_call(self, spec: str, mode: str, tensors, scale: float, stream, bias=None) -> None:
+        """Every attention call: pass `spec` of _ATTN_PASSES in `mode` of _ATTN_MODES on `tensors` in the spec's order.
         Matrices that are all torch.bfloat16 or all torch.float16 (stats and delta stay float32) go to the pass's _16 call: the
         same layout rules, every ld and stride counted in elements; a call of one head is one head with every stride 0, a
-        _heads call a group of 1."""
+        _heads call a group of 1.  bias: (bias,) or (bias, dBias) of a _bias call (mode "gqa"), which takes all three dtypes."""
         import torch
-        what, ops = f"attention_{spec}{_ATTN_MODES[mode]}", _ATTN_PASSES[spec]
+        what, ops = f"attention_{spec}{'_bias' if bias else _ATTN_MODES[mode]}", _ATTN_PASSES[spec]
         t = dict(zip((o[0] for o in ops), tensors))
         d16 = {torch.bfloat16: ATTN_BF16, torch.float16: ATTN_FP16}.get(getattr(t["Q"], "dtype", None))
         dt = t["Q"].dtype if d16 else None
@@ -521,6 +568,10 @@ class CsrMatrix:
         args = []
         for name, _, w, _, _ in ops:
             args += ([width["kv"]] if name == "V" else []) + [_ptr(t[name])] + ([t[name].stride(nd - 2)] if isinstance(w, str) else [])
+        if bias:
+            b = self._attention_bias(what, heads, *bias)[:4 if spec == "backward_q" else 2]
+            check(getattr(lib(), f"spmv_csr_{what}")(self._h, *head, d16 or ATTN_FP32, *b, scale, width["k"], *args, _stream_handle(stream)))
+            return
         if d16:
             check(getattr(lib(), f"spmv_csr_attention_{spec}_16")(self._h, *head, d16, scale, width["k"], *args, _stream_handle(stream)))
             return

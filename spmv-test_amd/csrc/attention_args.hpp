@@ -37,4 +37,12 @@ struct AttnArgsT {
 };
 using AttnArgs = AttnArgsT<float>;     // the nine fp32 entry points
 
+// The additive bias of the _bias entry points: a second by-value argument of the biased kernels only, so that AttnArgsT (and
+// with it the kernarg segment of every unbiased kernel) stays as it is.  Floats whatever E is, nnz of them per query head in
+// the storage order of the handle the call runs on (backward_kv: the transposed handle's).
+struct AttnBias {
+    const float *bias;    int64_t hbias;      // floats from query head y to y + 1; 0: one bias for all heads
+    float *dbias;         int64_t hdbias;     // backward_q: p (dp - delta) per nonzero and query head; null: not written
+};
+
 }  // namespace spmv

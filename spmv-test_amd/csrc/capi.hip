@@ -390,6 +390,37 @@ int spmv_csr_transpose_values(spmv_csr_t *t, const spmv_csr_t *a, void *stream)
     return SPMV_OK;
 }
 
+int spmv_csr_transpose_gather(const spmv_csr_t *t, int count, const void *d_src, int64_t src_stride, void *d_dst, int64_t dst_stride,
+                              void *stream)
+{
+    const char *what = "spmv_csr_transpose_gather";
+    if (!t) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (!t->transpose_map) {
+        set_error("%s: the handle has no map (it was not made by spmv_csr_transpose with keep_map = 1)", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (count < 1) { set_error("%s: count = %d (need count >= 1)", what, count); return SPMV_ERR_INVALID; }
+    if ((!d_src || !d_dst) && t->nnz > 0) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
+    if (reinterpret_cast<uintptr_t>(d_src) % 4 != 0 || reinterpret_cast<uintptr_t>(d_dst) % 4 != 0) {
+        set_error("%s: src and dst must be 4-byte aligned", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (src_stride < 0 || dst_stride < 0) {
+        set_error("%s: src_stride = %lld, dst_stride = %lld (a stride is not negative)", what, (long long)src_stride, (long long)dst_stride);
+        return SPMV_ERR_INVALID;
+    }
+    if (src_stride > INT64_MAX / 4 / count || dst_stride > INT64_MAX / 4 / count) {
+        set_error("%s: a stride overflows 64-bit byte offsets", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (count > 1 && dst_stride < t->nnz) {
+        set_error("%s: dst_stride = %lld is below nnz = %lld with count = %d", what, (long long)dst_stride, (long long)t->nnz, count);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(t->device, what)) return rc;
+    return transpose_gather(*t, count, d_src, src_stride, d_dst, dst_stride, (hipStream_t)stream);
+}
+
 int64_t spmv_csr_transpose_map_bytes(const spmv_csr_t *t)
 {
     if (!t) { set_error("spmv_csr_transpose_map_bytes: null handle"); return SPMV_ERR_INVALID; }
@@ -774,7 +805,7 @@ extern "C++" {      // (templates: this file is otherwise C linkage)
 template <typename E>
 static int attention_forward(const char *what, spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, bool sum_group, float scale,
                              int k, const E *d_Q, int64_t ldq, const E *d_K, int64_t ldk, int kv, const E *d_V,
-                             int64_t ldv, E *d_O, int64_t ldo, float *d_stats, void *stream)
+                             int64_t ldv, E *d_O, int64_t ldo, float *d_stats, void *stream, const AttnBias *bb = nullptr)
 {
     if (int rc = attention_header(h, hs, group, what)) return rc;
     const int64_t rows = h->rows, cols = h->cols;
@@ -786,14 +817,14 @@ static int attention_forward(const char *what, spmv_csr_t *h, const spmv_attn_he
     a.scale = scale, a.k = k, a.kv = kv;
     a.Q = d_Q, a.ldq = ldq, a.hq = hs->q, a.K = d_K, a.ldk = ldk, a.hk = hs->k, a.V = d_V, a.ldv = ldv, a.hv = hs->v;
     a.out0 = d_O, a.ld0 = ldo, a.h0 = hs->o, a.stats = d_stats, a.hstats = hs->stats;
-    return launch_attention(kPassForward, *h, a, hs->heads, group, sum_group, what, (hipStream_t)stream);
+    return launch_attention(kPassForward, *h, a, bb, hs->heads, group, sum_group, what, (hipStream_t)stream);
 }
 
 template <typename E>
 static int attention_backward_q(const char *what, spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, bool sum_group, float scale,
                                 int k, const E *d_Q, int64_t ldq, const E *d_K, int64_t ldk, int kv, const E *d_V,
                                 int64_t ldv, const E *d_O, int64_t ldo, const E *d_dO, int64_t lddo, const float *d_stats,
-                                float *d_delta, E *d_dQ, int64_t lddq, void *stream)
+                                float *d_delta, E *d_dQ, int64_t lddq, void *stream, const AttnBias *bb = nullptr)
 {
     if (int rc = attention_header(h, hs, group, what)) return rc;
     const int64_t rows = h->rows, cols = h->cols;
@@ -807,7 +838,7 @@ static int attention_backward_q(const char *what, spmv_csr_t *h, const spmv_attn
     a.Q = d_Q, a.ldq = ldq, a.hq = hs->q, a.K = d_K, a.ldk = ldk, a.hk = hs->k, a.V = d_V, a.ldv = ldv, a.hv = hs->v;
     a.O = d_O, a.ldo = ldo, a.ho = hs->o, a.dO = d_dO, a.lddo = lddo, a.hdo = hs->d_o;
     a.stats_in = d_stats, a.hstats_in = hs->stats, a.delta = d_delta, a.hdelta = hs->delta, a.out0 = d_dQ, a.ld0 = lddq, a.h0 = hs->dq;
-    return launch_attention(kPassBackwardQ, *h, a, hs->heads, group, sum_group, what, (hipStream_t)stream);
+    return launch_attention(kPassBackwardQ, *h, a, bb, hs->heads, group, sum_group, what, (hipStream_t)stream);
 }
 
 // t is the handle of the TRANSPOSED pattern: t->rows keys, t->cols queries.  dK and dV hold the K/V heads (the output-stride
@@ -816,7 +847,7 @@ template <typename E>
 static int attention_backward_kv(const char *what, spmv_csr_t *t, const spmv_attn_heads_t *hs, int group, bool sum_group, float scale,
                                  int k, const E *d_Q, int64_t ldq, const E *d_K, int64_t ldk, int kv, const E *d_V,
                                  int64_t ldv, const E *d_dO, int64_t lddo, const float *d_stats, const float *d_delta,
-                                 E *d_dK, int64_t lddk, E *d_dV, int64_t lddv, void *stream)
+                                 E *d_dK, int64_t lddk, E *d_dV, int64_t lddv, void *stream, const AttnBias *bb = nullptr)
 {
     if (int rc = attention_header(t, hs, group, what)) return rc;
     const int64_t keys = t->rows, queries = t->cols;
@@ -832,7 +863,7 @@ static int attention_backward_kv(const char *what, spmv_csr_t *t, const spmv_att
     a.dO = d_dO, a.lddo = lddo, a.hdo = hs->d_o;
     a.stats_in = d_stats, a.hstats_in = hs->stats, a.delta_in = d_delta, a.hdelta_in = hs->delta;
     a.out0 = d_dK, a.ld0 = lddk, a.h0 = hs->dk, a.out1 = d_dV, a.ld1 = lddv, a.h1 = hs->dv;
-    return launch_attention(kPassBackwardKV, *t, a, hs->heads, group, sum_group, what, (hipStream_t)stream);
+    return launch_attention(kPassBackwardKV, *t, a, bb, hs->heads, group, sum_group, what, (hipStream_t)stream);
 }
 
 }  // extern "C++"
@@ -968,6 +999,90 @@ int spmv_csr_attention_backward_kv_16(spmv_csr_t *t, const spmv_attn_heads_t *hs
                                         ldv, (const E *)d_dO, lddo, d_stats, d_delta, (E *)d_dK, lddk, (E *)d_dV, lddv, stream);
     };
     return dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+}
+
+// ---- the same three passes with an additive fp32 bias per nonzero (fp32, bf16 or fp16 matrices): the most general form only ------
+// What the _bias calls check of their bias arguments, after the header and the dtype and before everything the unbiased call
+// of that dtype checks.  d_dbias: backward_q's output (may be null: not written); has_dbias: the call has one at all.
+static int attention_bias(const spmv_csr_t *h, int heads, int dtype, const float *d_bias, int64_t bias_stride, bool has_dbias,
+                          const float *d_dbias, int64_t dbias_stride, const char *what)
+{
+    if (dtype != SPMV_ATTN_FP32 && dtype != SPMV_ATTN_BF16 && dtype != SPMV_ATTN_FP16) {
+        set_error("%s: dtype = %d (need SPMV_ATTN_FP32 = %d, SPMV_ATTN_BF16 = %d or SPMV_ATTN_FP16 = %d)", what, dtype, (int)SPMV_ATTN_FP32,
+                  (int)SPMV_ATTN_BF16, (int)SPMV_ATTN_FP16);
+        return SPMV_ERR_INVALID;
+    }
+    if (!d_bias && h->nnz > 0) { set_error("%s: null bias", what); return SPMV_ERR_INVALID; }
+    if (reinterpret_cast<uintptr_t>(d_bias) % 4 != 0 || reinterpret_cast<uintptr_t>(d_dbias) % 4 != 0) {
+        set_error("%s: bias and dBias must be 4-byte aligned", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (bias_stride < 0 || (has_dbias && dbias_stride < 0)) {
+        set_error("%s: head stride of the bias = %lld or of dBias = %lld is negative", what, (long long)bias_stride,
+                  (long long)(has_dbias ? dbias_stride : 0));
+        return SPMV_ERR_INVALID;
+    }
+    if (bias_stride > INT64_MAX / 4 / heads || (has_dbias && dbias_stride > INT64_MAX / 4 / heads)) {
+        set_error("%s: head stride of the bias or of dBias overflows 64-bit byte offsets", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (d_dbias && heads > 1 && dbias_stride < h->nnz) {
+        set_error("%s: head stride of the output dBias = %lld is below nnz = %lld", what, (long long)dbias_stride, (long long)h->nnz);
+        return SPMV_ERR_INVALID;
+    }
+    return SPMV_OK;
+}
+
+int spmv_csr_attention_forward_bias(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, int dtype, const float *d_bias,
+                                    int64_t bias_stride, float scale, int k, const void *d_Q, int64_t ldq, const void *d_K, int64_t ldk,
+                                    int kv, const void *d_V, int64_t ldv, void *d_O, int64_t ldo, float *d_stats, void *stream)
+{
+    const char *what = "spmv_csr_attention_forward_bias";
+    if (int rc = attention_header(h, hs, group, what)) return rc;
+    if (int rc = attention_bias(h, hs->heads, dtype, d_bias, bias_stride, false, nullptr, 0, what)) return rc;
+    const AttnBias bb{d_bias, bias_stride, nullptr, 0};
+    auto run = [&](auto e) {
+        using E = decltype(e);
+        return attention_forward<E>(what, h, hs, group, false, scale, k, (const E *)d_Q, ldq, (const E *)d_K, ldk, kv, (const E *)d_V, ldv,
+                                    (E *)d_O, ldo, d_stats, stream, &bb);
+    };
+    return dtype == SPMV_ATTN_FP32 ? run(float{}) : dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+}
+
+int spmv_csr_attention_backward_q_bias(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, int dtype, const float *d_bias,
+                                       int64_t bias_stride, float *d_dbias, int64_t dbias_stride, float scale, int k, const void *d_Q,
+                                       int64_t ldq, const void *d_K, int64_t ldk, int kv, const void *d_V, int64_t ldv, const void *d_O,
+                                       int64_t ldo, const void *d_dO, int64_t lddo, const float *d_stats, float *d_delta, void *d_dQ,
+                                       int64_t lddq, void *stream)
+{
+    const char *what = "spmv_csr_attention_backward_q_bias";
+    if (int rc = attention_header(h, hs, group, what)) return rc;
+    if (int rc = attention_bias(h, hs->heads, dtype, d_bias, bias_stride, true, d_dbias, dbias_stride, what)) return rc;
+    const AttnBias bb{d_bias, bias_stride, d_dbias, dbias_stride};
+    auto run = [&](auto e) {
+        using E = decltype(e);
+        return attention_backward_q<E>(what, h, hs, group, false, scale, k, (const E *)d_Q, ldq, (const E *)d_K, ldk, kv, (const E *)d_V,
+                                       ldv, (const E *)d_O, ldo, (const E *)d_dO, lddo, d_stats, d_delta, (E *)d_dQ, lddq, stream, &bb);
+    };
+    return dtype == SPMV_ATTN_FP32 ? run(float{}) : dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+}
+
+int spmv_csr_attention_backward_kv_bias(spmv_csr_t *t, const spmv_attn_heads_t *hs, int group, int dtype, const float *d_bias_t,
+                                        int64_t bias_stride, float scale, int k, const void *d_Q, int64_t ldq, const void *d_K,
+                                        int64_t ldk, int kv, const void *d_V, int64_t ldv, const void *d_dO, int64_t lddo,
+                                        const float *d_stats, const float *d_delta, void *d_dK, int64_t lddk, void *d_dV, int64_t lddv,
+                                        void *stream)
+{
+    const char *what = "spmv_csr_attention_backward_kv_bias";
+    if (int rc = attention_header(t, hs, group, what)) return rc;
+    if (int rc = attention_bias(t, hs->heads, dtype, d_bias_t, bias_stride, false, nullptr, 0, what)) return rc;
+    const AttnBias bb{d_bias_t, bias_stride, nullptr, 0};
+    auto run = [&](auto e) {
+        using E = decltype(e);
+        return attention_backward_kv<E>(what, t, hs, group, true, scale, k, (const E *)d_Q, ldq, (const E *)d_K, ldk, kv, (const E *)d_V,
+                                        ldv, (const E *)d_dO, lddo, d_stats, d_delta, (E *)d_dK, lddk, (E *)d_dV, lddv, stream, &bb);
+    };
+    return dtype == SPMV_ATTN_FP32 ? run(float{}) : dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
 }
 
 int spmv_csr_values_changed(spmv_csr_t *h)

@@ -50,6 +50,14 @@
 // nearest even.  stats, delta, the scratch and the LDS slots of k_attn_bwd_kv_rows_gqa hold floats whatever E is.  So a 16-bit
 // call is, bit for bit, the fp32 call on the widened operands with O, dQ, dK and dV rounded once.
 //
+// The additive bias (the _bias entry points; include/spmv_hip.h "Fused attention with an additive bias").  The spans take a
+// compile-time BIAS switch; off, they are the code above.  On, t = (scale * s) + bias[n], two roundings, where n is the nonzero's
+// position in the storage order of the handle the pass runs on (backward_kv: the transposed handle's, bias_t); everything after
+// t is the order above.  The lane that ends up with the score of a nonzero after reduce_scatter loads its bias (4 coalesced
+// bytes per nonzero, none past the span's end, with the step's gathers or after reduce_scatter: kBiasEarly) and, in
+// backward_q, stores dBias[n] = p * (dp - delta), whose product with scale is ds: every position once, no atomics.  The bias
+// pointers are a second kernel argument (AttnBias): AttnArgsT and the kernarg segment of the unbiased kernels stay as they are.
+//
 // The scratch of the long rows (AttnPlan): per head, kAtSlots floats per piece: [0] m_p, [1] l_p, [4, 132) up to 128 partial sums
 // (forward acc_p[kv]; backward_q dQ_p[k]; backward_kv dK_p[k] at 4 and dV_p[kv] at 68).
 #include <initializer_list>
@@ -105,11 +113,64 @@ __device__ __forceinline__ float *at_head_scratch(const GroupPieces &g)
     return s;
 }
 
-// ---- forward: (m, l, acc) of the nonzeros [b, e) of the group's row.  All lanes of a group call it with the same b, e. ----
-template <int V, bool VEC, typename E>
-__device__ __forceinline__ void fwd_span(int lane, int64_t b, int64_t e, const AttnArgsT<E> &a, float4 q,
-                                         const int32_t *__restrict__ col_idx, int c0, float &m, float &l, float4 &acc)
+// the bias of the block's query head (the _bias kernels; formed at entry like the bases above).  A null dbias stays null.
+__device__ __forceinline__ AttnBias at_head(AttnBias b)
 {
+    const int64_t y = query_head();
+    b.bias += y * b.hbias;
+    b.dbias = b.dbias ? b.dbias + y * b.hdbias : nullptr;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+s"(b.bias));
+    asm("" : "+s"(b.dbias));
+#endif
+    return b;
+}
+
+// The bias of the step's nonzeros kb + i V + sub, one coalesced 4-byte load per nonzero by the lane that ends up with its
+// score (0 past the end e: no load).  A span issues it with the step's gathers (kBiasEarly) or, where that costs the kernel
+// a register it does not have, after reduce_scatter; the bits are the same.
+template <int V>
+__device__ __forceinline__ void load_bias(const float *__restrict__ bias, int64_t kb, int64_t e, int sub, float (&bl)[LaneGeom<V>::L])
+{
+#pragma unroll
+    for (int i = 0; i < LaneGeom<V>::L; ++i) {
+        const int64_t n = kb + (int64_t)i * V + sub;
+        bl[i] = n < e ? bias[n] : 0.0f;
+    }
+}
+
+// where the early load would cost the kernel a wave per SIMD or a spill (profiles/lane_group_resource_usage.md, "with bias")
+template <int PASS, int V, typename E>
+constexpr bool kBiasEarly = PASS == kPassForward     ? !(kIs16<E> && V <= 2)
+                            : PASS == kPassBackwardQ ? !((kIs16<E> && V == 1) || V == 4 || V == 8)
+                                                     : !(V == 1 || (V == 8 && !kIs16<E>));
+
+// The waves per SIMD asked of a _bias kernel: its unbiased twin's, in the instantiations where the compiler then fits the bias's
+// registers without scratch (1: no floor; elsewhere a floor only turns registers into scratch).  This table and kBiasEarly
+// above are read off one compiler's register allocation: `python tools/attention_bias_resources.py` compiles this file,
+// prints every _bias kernel beside its twin (the table of profiles/lane_group_resource_usage.md) and fails on scratch, so
+// run it after a change to a span or a new ROCm and move the entries with what it shows.
+enum BiasKernel { kBiasBwdQRows, kBiasBwdKvRows };
+template <BiasKernel KERNEL, int V, bool VEC, typename E>
+constexpr int bias_waves()
+{
+    if (KERNEL == kBiasBwdQRows) return V == 8 && !VEC && std::is_same<E, bf16>::value ? 5 : 1;
+    return V == 1 && !VEC && kIs16<E> ? 4 : 1;       // kBiasBwdKvRows
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SPMV_BIAS_WAVES(KERNEL) __attribute__((amdgpu_waves_per_eu(bias_waves<KERNEL, V, VEC, E>())))
+#else
+#define SPMV_BIAS_WAVES(KERNEL)
+#endif
+
+// ---- forward: (m, l, acc) of the nonzeros [b, e) of the group's row.  All lanes of a group call it with the same b, e. ----
+// BIAS (here and in the two spans below): the score of nonzero n is t = (scale * s) + bias[n], two roundings.
+template <int V, bool VEC, typename E, bool BIAS = false>
+__device__ __forceinline__ void fwd_span(int lane, int64_t b, int64_t e, const AttnArgsT<E> &a, float4 q,
+                                         const int32_t *__restrict__ col_idx, int c0, float &m, float &l, float4 &acc,
+                                         const float *__restrict__ bias = nullptr)
+{
+    constexpr bool kEarly = kBiasEarly<kPassForward, V, E>;
     constexpr int T = LaneGeom<V>::T, L = LaneGeom<V>::L;
     const int sub = lane & (V - 1), gbase = lane & ~(V - 1);
     const int nk = a.k - c0, nv = a.kv - c0;
@@ -119,6 +180,8 @@ __device__ __forceinline__ void fwd_span(int lane, int64_t b, int64_t e, const A
     for (int64_t kb = b; kb < e; kb += T) {
         int32_t c[L], ct[T];
         group_columns<V, T>(kb, e, sub, gbase, col_idx, c, ct);
+        [[maybe_unused]] float bl[L];
+        if constexpr (BIAS && kEarly) load_bias<V>(bias, kb, e, sub, bl);
         slice_t<E> xk[T], xv[T];      // as loaded: 16-bit elements stay packed until they are used
 #pragma unroll
         for (int t = 0; t < T; ++t) xk[t] = (nk > 0 && kb + t < e) ? load_slice<VEC>(a.K, a.ldk, ct[t], c0, a.k) : zero_slice<E>();
@@ -128,10 +191,12 @@ __device__ __forceinline__ void fwd_span(int lane, int64_t b, int64_t e, const A
 #pragma unroll
         for (int t = 0; t < T; ++t) p[t] = dot_partial(q, widen<E>(xk[t]), nk);
         reduce_scatter<V, T>(p, sub);
+        if constexpr (BIAS && !kEarly) load_bias<V>(bias, kb, e, sub, bl);
         float tl[L], sm = -INFINITY;
 #pragma unroll
         for (int i = 0; i < L; ++i) {
-            tl[i] = kb + i * V + sub < e ? a.scale * p[i * V] : -INFINITY;
+            if constexpr (BIAS) tl[i] = kb + i * V + sub < e ? a.scale * p[i * V] + bl[i] : -INFINITY;
+            else tl[i] = kb + i * V + sub < e ? a.scale * p[i * V] : -INFINITY;
             sm = fmaxf(sm, tl[i]);
         }
         const float mn = fmaxf(m, group_max<V>(sm));
@@ -168,6 +233,8 @@ __device__ __forceinline__ void store_stats(float *stats, int64_t r, float m, fl
     *reinterpret_cast<float2 *>(stats + 2 * r) = make_float2(m, rinv);
 }
 
+// Each of the seven kernels that run a span is followed by its _bias twin: the same kernel with the bias of the block's query
+// head handed to the span; it takes the bias as one more argument (AttnBias), AttnArgsT being part of the unbiased kernels' code.
 template <int V, bool VEC, typename E>
 __global__ __launch_bounds__(kBlock) void k_attn_fwd_rows(GroupRows g, AttnArgsT<E> a0)
 {
@@ -192,6 +259,30 @@ __global__ __launch_bounds__(kBlock) void k_attn_fwd_rows(GroupRows g, AttnArgsT
 }
 
 template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) void k_attn_fwd_rows_bias(GroupRows g, AttnArgsT<E> a0, AttnBias bb)
+{
+    const AttnArgsT<E> a = at_head(a0);
+    const float *bias = at_head(bb).bias;
+    const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
+    const int64_t r = group_row<V>(g);
+    if (r < 0) return;
+    const int64_t b = g.row_ptr[r], e = g.row_ptr[r + 1];
+    if (e - b > g.row_cap) return;
+    if (e == b) {
+        if (c0 < a.kv) store_slice<VEC>(a.out0 + r * a.ld0 + c0, zero4(), c0, a.kv);
+        if (sub == 0) store_stats(a.stats, r, -INFINITY, 0.0f);
+        return;
+    }
+    const float4 q = c0 < a.k ? load_wide<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
+    float m, l;
+    float4 acc;
+    fwd_span<V, VEC, E, true>(lane, b, e, a, q, g.col_idx, c0, m, l, acc, bias);
+    const float rinv = 1.0f / l;
+    if (c0 < a.kv) store_slice<VEC>(a.out0 + r * a.ld0 + c0, scaled4(acc, rinv), c0, a.kv);
+    if (sub == 0) store_stats(a.stats, r, m, rinv);
+}
+
+template <int V, bool VEC, typename E>
 __global__ __launch_bounds__(kBlock) void k_attn_fwd_pieces(GroupPieces g, AttnArgsT<E> a0)
 {
     const AttnArgsT<E> a = at_head(a0);
@@ -206,6 +297,27 @@ __global__ __launch_bounds__(kBlock) void k_attn_fwd_pieces(GroupPieces g, AttnA
     float m, l;
     float4 acc;
     fwd_span<V, VEC, E>(lane, b, e, a, q, g.col_idx, c0, m, l, acc);
+    float *s = scratch + p * kAtSlots;
+    if (sub == 0) *reinterpret_cast<float2 *>(s) = make_float2(m, l);
+    if (c0 < a.kv) *reinterpret_cast<float4 *>(s + kAtSums + c0) = acc;
+}
+
+template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) void k_attn_fwd_pieces_bias(GroupPieces g, AttnArgsT<E> a0, AttnBias bb)
+{
+    const AttnArgsT<E> a = at_head(a0);
+    const float *bias = at_head(bb).bias;
+    float *const scratch = at_head_scratch(g);
+    const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
+    int lo;
+    const int64_t p = group_piece<V>(g, lo);
+    if (p < 0) return;
+    const int64_t r = g.long_row[lo];
+    const int64_t b = g.piece_k0[p], e = b + g.piece_len[p];
+    const float4 q = c0 < a.k ? load_wide<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
+    float m, l;
+    float4 acc;
+    fwd_span<V, VEC, E, true>(lane, b, e, a, q, g.col_idx, c0, m, l, acc, bias);
     float *s = scratch + p * kAtSlots;
     if (sub == 0) *reinterpret_cast<float2 *>(s) = make_float2(m, l);
     if (c0 < a.kv) *reinterpret_cast<float4 *>(s + kAtSums + c0) = acc;
@@ -245,10 +357,13 @@ __global__ __launch_bounds__(kBlock) void k_attn_fwd_combine(GroupPieces g, Attn
 }
 
 // ---- backward_q: dQ of the nonzeros [b, e) of row i, whose q, dO slice g, (M, rinv) and delta the group holds -------------
-template <int V, bool VEC, typename E>
+// BIAS: the lane that forms p (dp - delta) of a nonzero also stores it to dbias at the nonzero's position (if dbias is not null)
+template <int V, bool VEC, typename E, bool BIAS = false>
 __device__ __forceinline__ float4 bwdq_span(int lane, int64_t b, int64_t e, const AttnArgsT<E> &a, float4 q, float4 g, float M,
-                                            float rinv, float delta, const int32_t *__restrict__ col_idx, int c0)
+                                            float rinv, float delta, const int32_t *__restrict__ col_idx, int c0,
+                                            const float *__restrict__ bias = nullptr, float *__restrict__ dbias = nullptr)
 {
+    constexpr bool kEarly = kBiasEarly<kPassBackwardQ, V, E>;
     constexpr int T = LaneGeom<V>::T, L = LaneGeom<V>::L;
     const int sub = lane & (V - 1), gbase = lane & ~(V - 1);
     const int nk = a.k - c0, nv = a.kv - c0;
@@ -256,6 +371,8 @@ __device__ __forceinline__ float4 bwdq_span(int lane, int64_t b, int64_t e, cons
     for (int64_t kb = b; kb < e; kb += T) {
         int32_t c[L], ct[T];
         group_columns<V, T>(kb, e, sub, gbase, col_idx, c, ct);
+        [[maybe_unused]] float bl[L];
+        if constexpr (BIAS && kEarly) load_bias<V>(bias, kb, e, sub, bl);
         slice_t<E> xk[T], xv[T];      // as loaded: 16-bit elements stay packed until they are used
 #pragma unroll
         for (int t = 0; t < T; ++t) xk[t] = (nk > 0 && kb + t < e) ? load_slice<VEC>(a.K, a.ldk, ct[t], c0, a.k) : zero_slice<E>();
@@ -269,12 +386,22 @@ __device__ __forceinline__ float4 bwdq_span(int lane, int64_t b, int64_t e, cons
         }
         reduce_scatter<V, T>(ps, sub);
         reduce_scatter<V, T>(pd, sub);
+        if constexpr (BIAS && !kEarly) load_bias<V>(bias, kb, e, sub, bl);
         float dl[L], dt[T];
 #pragma unroll
         for (int i = 0; i < L; ++i) {
-            const float t = a.scale * ps[i * V];
-            const float p = expf(t - M) * rinv;
-            dl[i] = a.scale * (p * (pd[i * V] - delta));
+            if constexpr (BIAS) {
+                const float t = a.scale * ps[i * V] + bl[i];
+                const float p = expf(t - M) * rinv;
+                const float db = p * (pd[i * V] - delta);
+                const int64_t n = kb + (int64_t)i * V + sub;
+                if (dbias && n < e) dbias[n] = db;
+                dl[i] = a.scale * db;
+            } else {
+                const float t = a.scale * ps[i * V];
+                const float p = expf(t - M) * rinv;
+                dl[i] = a.scale * (p * (pd[i * V] - delta));
+            }
         }
         group_bcast<V, T>(dl, dt, gbase);
 #pragma unroll
@@ -328,6 +455,30 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_q_rows(GroupRows g, AttnArg
 }
 
 template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) SPMV_BIAS_WAVES(kBiasBwdQRows) void k_attn_bwd_q_rows_bias(GroupRows g, AttnArgsT<E> a0, AttnBias bb)
+{
+    const AttnArgsT<E> a = at_head(a0);
+    const AttnBias bi = at_head(bb);
+    const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
+    const int64_t r = group_row<V>(g);
+    if (r < 0) return;
+    const int64_t b = g.row_ptr[r], e = g.row_ptr[r + 1];
+    if (e - b > g.row_cap) return;
+    if (e == b) {
+        if (c0 < a.k) store_slice<VEC>(a.out0 + r * a.ld0 + c0, zero4(), c0, a.k);
+        if (sub == 0) a.delta[r] = 0.0f;
+        return;
+    }
+    float4 go;
+    const float delta = at_delta<V, VEC, E>(a, r, c0, go);
+    const float4 q = c0 < a.k ? load_wide<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
+    const float2 st = *reinterpret_cast<const float2 *>(a.stats_in + 2 * r);
+    const float4 dq = bwdq_span<V, VEC, E, true>(lane, b, e, a, q, go, st.x, st.y, delta, g.col_idx, c0, bi.bias, bi.dbias);
+    if (c0 < a.k) store_slice<VEC>(a.out0 + r * a.ld0 + c0, dq, c0, a.k);
+    if (sub == 0) a.delta[r] = delta;
+}
+
+template <int V, bool VEC, typename E>
 __global__ __launch_bounds__(kBlock) void k_attn_bwd_q_pieces(GroupPieces g, AttnArgsT<E> a0)
 {
     const AttnArgsT<E> a = at_head(a0);
@@ -343,6 +494,27 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_q_pieces(GroupPieces g, Att
     const float4 q = c0 < a.k ? load_wide<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
     const float2 st = *reinterpret_cast<const float2 *>(a.stats_in + 2 * r);
     const float4 dq = bwdq_span<V, VEC, E>(lane, b, e, a, q, go, st.x, st.y, delta, g.col_idx, c0);
+    if (c0 < a.k) *reinterpret_cast<float4 *>(scratch + p * kAtSlots + kAtSums + c0) = dq;
+    if (sub == 0 && p == g.long_first[lo]) a.delta[r] = delta;
+}
+
+template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_q_pieces_bias(GroupPieces g, AttnArgsT<E> a0, AttnBias bb)
+{
+    const AttnArgsT<E> a = at_head(a0);
+    const AttnBias bi = at_head(bb);
+    float *const scratch = at_head_scratch(g);
+    const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
+    int lo;
+    const int64_t p = group_piece<V>(g, lo);
+    if (p < 0) return;
+    const int64_t r = g.long_row[lo];
+    const int64_t b = g.piece_k0[p], e = b + g.piece_len[p];
+    float4 go;
+    const float delta = at_delta<V, VEC, E>(a, r, c0, go);      // (every piece of the row computes the same bits)
+    const float4 q = c0 < a.k ? load_wide<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
+    const float2 st = *reinterpret_cast<const float2 *>(a.stats_in + 2 * r);
+    const float4 dq = bwdq_span<V, VEC, E, true>(lane, b, e, a, q, go, st.x, st.y, delta, g.col_idx, c0, bi.bias, bi.dbias);
     if (c0 < a.k) *reinterpret_cast<float4 *>(scratch + p * kAtSlots + kAtSums + c0) = dq;
     if (sub == 0 && p == g.long_first[lo]) a.delta[r] = delta;
 }
@@ -370,10 +542,17 @@ __global__ __launch_bounds__(kBlock) void k_attn_add_pieces(GroupPieces g, int o
 }
 
 // ---- backward_kv on the transposed pattern: (dK, dV) of the nonzeros [b, e) of row j, whose K and V slices the group holds
-template <int V, bool VEC, typename E>
+// BIAS: `bias` is in the transposed handle's storage order (spmv_csr_transpose_gather made it)
+template <int V, bool VEC, typename E, bool BIAS = false>
 __device__ __forceinline__ void bwdkv_span(int lane, int64_t b, int64_t e, const AttnArgsT<E> &a, float4 kj, float4 vj,
-                                           const int32_t *__restrict__ col_idx, int c0, float4 &dk, float4 &dv)
+                                           const int32_t *__restrict__ col_idx, int c0, float4 &dk, float4 &dv,
+                                           const float *__restrict__ bias = nullptr)
 {
+    constexpr bool kEarly = kBiasEarly<kPassBackwardKV, V, E>;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // one lane per row on the 4-byte path: the pass is out of scalar registers (106), so the bias base waits in vector ones
+    if constexpr (BIAS && V == 1 && !VEC) asm("" : "+v"(bias));
+#endif
     constexpr int T = LaneGeom<V>::T, L = LaneGeom<V>::L;
     const int sub = lane & (V - 1), gbase = lane & ~(V - 1);
     const int nk = a.k - c0, nv = a.kv - c0;
@@ -390,6 +569,8 @@ __device__ __forceinline__ void bwdkv_span(int lane, int64_t b, int64_t e, const
             st[i] = in ? *reinterpret_cast<const float2 *>(a.stats_in + 2 * (int64_t)c[i]) : make_float2(0.0f, 0.0f);
             de[i] = in ? a.delta_in[c[i]] : 0.0f;
         }
+        [[maybe_unused]] float bl[L];
+        if constexpr (BIAS && kEarly) load_bias<V>(bias, kb, e, sub, bl);
         slice_t<E> xq[T], xg[T];
 #pragma unroll
         for (int t = 0; t < T; ++t) xq[t] = (nk > 0 && kb + t < e) ? load_slice<VEC>(a.Q, a.ldq, ct[t], c0, a.k) : zero_slice<E>();
@@ -403,10 +584,12 @@ __device__ __forceinline__ void bwdkv_span(int lane, int64_t b, int64_t e, const
         }
         reduce_scatter<V, T>(ps, sub);
         reduce_scatter<V, T>(pd, sub);
+        if constexpr (BIAS && !kEarly) load_bias<V>(bias, kb, e, sub, bl);
         float pl[L], dl[L], pt[T], dt[T];
 #pragma unroll
         for (int i = 0; i < L; ++i) {
-            const float t = a.scale * ps[i * V];
+            float t = a.scale * ps[i * V];
+            if constexpr (BIAS) t = t + bl[i];
             pl[i] = expf(t - st[i].x) * st[i].y;
             dl[i] = a.scale * (pl[i] * (pd[i * V] - de[i]));
         }
@@ -450,6 +633,26 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows(GroupRows g, AttnAr
 }
 
 template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) SPMV_BIAS_WAVES(kBiasBwdKvRows) void k_attn_bwd_kv_rows_bias(GroupRows g, AttnArgsT<E> a0, AttnBias bb)
+{
+    const AttnArgsT<E> a = at_head(a0);
+    const float *bias = at_head(bb).bias;
+    const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
+    const int64_t r = group_row<V>(g);
+    if (r < 0) return;
+    const int64_t b = g.row_ptr[r], e = g.row_ptr[r + 1];
+    if (e - b > g.row_cap) return;
+    float4 dk = zero4(), dv = zero4();
+    if (e > b) {
+        const float4 kj = c0 < a.k ? load_wide<VEC>(a.K, a.ldk, r, c0, a.k) : zero4();
+        const float4 vj = c0 < a.kv ? load_wide<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
+        bwdkv_span<V, VEC, E, true>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv, bias);
+    }
+    if (c0 < a.k) store_slice<VEC>(a.out0 + r * a.ld0 + c0, dk, c0, a.k);
+    if (c0 < a.kv) store_slice<VEC>(a.out1 + r * a.ld1 + c0, dv, c0, a.kv);
+}
+
+template <int V, bool VEC, typename E>
 __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_pieces(GroupPieces g, AttnArgsT<E> a0)
 {
     const AttnArgsT<E> a = at_head(a0);
@@ -468,6 +671,28 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_pieces(GroupPieces g, At
     if (c0 < a.k) *reinterpret_cast<float4 *>(s + kAtSums + c0) = dk;
     if (c0 < a.kv) *reinterpret_cast<float4 *>(s + kAtSums2 + c0) = dv;
 }
+
+template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_pieces_bias(GroupPieces g, AttnArgsT<E> a0, AttnBias bb)
+{
+    const AttnArgsT<E> a = at_head(a0);
+    const float *bias = at_head(bb).bias;
+    float *const scratch = at_head_scratch(g);
+    const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
+    int lo;
+    const int64_t p = group_piece<V>(g, lo);
+    if (p < 0) return;
+    const int64_t r = g.long_row[lo];
+    const int64_t b = g.piece_k0[p], e = b + g.piece_len[p];
+    const float4 kj = c0 < a.k ? load_wide<VEC>(a.K, a.ldk, r, c0, a.k) : zero4();
+    const float4 vj = c0 < a.kv ? load_wide<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
+    float4 dk, dv;
+    bwdkv_span<V, VEC, E, true>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv, bias);
+    float *s = scratch + p * kAtSlots;
+    if (c0 < a.k) *reinterpret_cast<float4 *>(s + kAtSums + c0) = dk;
+    if (c0 < a.kv) *reinterpret_cast<float4 *>(s + kAtSums2 + c0) = dv;
+}
+
 
 __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
@@ -525,6 +750,8 @@ __device__ __forceinline__ int64_t uniform64(int64_t x)
 // per-head numbers) and adds the heads' results in head order, starting from head 0's.  The per-head kernel leaves few
 // registers free (k_attn_bwd_kv_rows: up to 104 SGPRs; at V = 16 247 to 254 of the 256 VGPRs that two waves per SIMD allow),
 // so the head strides, and at V = 16 the running sums, the row's output addresses and its bounds, wait in LDS (park_lds).
+// The _bias twin: each query head of the group uses its own bias; the bias base advances per head like Q's, its stride waits
+// in one more slot (the last).
 template <int V, bool VEC, typename E>
 __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows_gqa(GroupRows g, AttnArgsT<E> a, int group)
 {
@@ -591,6 +818,78 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows_gqa(GroupRows g, At
     if (c0 < a.kv) store_slice<VEC>(out.v, dv, c0, a.kv);
 }
 
+template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows_gqa_bias(GroupRows g, AttnArgsT<E> a, int group, AttnBias bb)
+{
+    constexpr bool kPark = V == 16;
+    constexpr int N = (kPark ? 6 : 2) + 1;
+    const float *bias = bb.bias + (int64_t)blockIdx.y * group * bb.hbias;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+s"(bias));
+#endif
+    {
+        const int64_t c = blockIdx.y, y0 = c * group;
+        a.K += c * a.hk, a.V += c * a.hv, a.out0 += c * a.h0, a.out1 += c * a.h1;
+        a.Q += y0 * a.hq, a.dO += y0 * a.hdo, a.stats_in += y0 * a.hstats_in, a.delta_in += y0 * a.hdelta_in;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm("" : "+s"(a.K));      // (as at_head: the bases are formed here; c and the K/V strides are dead from here on)
+        asm("" : "+s"(a.V));
+        asm("" : "+s"(a.out0));
+        asm("" : "+s"(a.out1));
+        asm("" : "+s"(a.Q));
+        asm("" : "+s"(a.dO));
+        asm("" : "+s"(a.stats_in));
+        asm("" : "+s"(a.delta_in));
+#endif
+    }
+    const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
+    const int64_t r = group_row<V>(g);
+    if (r < 0) return;
+    const int64_t b = g.row_ptr[r], e = g.row_ptr[r + 1];
+    if (e - b > g.row_cap) return;
+    Pointers2<E> out{a.out0 + r * a.ld0 + c0, a.out1 + r * a.ld1 + c0};
+    float4 dk = zero4(), dv = zero4();
+    if (e > b) {
+        const float4 kj = c0 < a.k ? load_wide<VEC>(a.K, a.ldk, r, c0, a.k) : zero4();
+        const float4 vj = c0 < a.kv ? load_wide<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
+        park_put<N>(0, Strides2{a.hq, a.hdo});
+        park_put<N>(1, Strides2{a.hstats_in, a.hdelta_in});
+        park_put<N>(N - 1, Strides2{bb.hbias, 0});
+        if constexpr (kPark) {
+            park_put<N>(4, out);
+            park_put<N>(5, Strides2{b, e});
+        }
+        float4 sk = zero4(), sv = zero4();
+        for (int left = group;;) {
+            park_fence();
+            if constexpr (kPark) {
+                const Strides2 be = park_get<N, Strides2>(5);
+                bwdkv_span<V, VEC, E, true>(lane, be.a, be.b, a, kj, vj, g.col_idx, c0, dk, dv, bias);
+            } else {
+                bwdkv_span<V, VEC, E, true>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv, bias);
+            }
+            if (left != group) {
+                if constexpr (kPark) sk = park_get<N, float4>(2), sv = park_get<N, float4>(3);
+                dk = add4(sk, dk);
+                dv = add4(sv, dv);
+            }
+            if (--left == 0) break;
+            if constexpr (kPark) {
+                park_put<N>(2, dk);
+                park_put<N>(3, dv);
+            } else {
+                sk = dk, sv = dv;
+            }
+            const Strides2 s0 = park_get<N, Strides2>(0), s1 = park_get<N, Strides2>(1);
+            a.Q += uniform64(s0.a), a.dO += uniform64(s0.b), a.stats_in += uniform64(s1.a), a.delta_in += uniform64(s1.b);
+            bias += uniform64(park_get<N, Strides2>(N - 1).a);
+        }
+        if constexpr (kPark) out = park_get<N, Pointers2<E>>(4);
+    }
+    if (c0 < a.k) store_slice<VEC>(out.k, dk, c0, a.k);
+    if (c0 < a.kv) store_slice<VEC>(out.v, dv, c0, a.kv);
+}
+
 // a group per long row of T and K/V head c = blockIdx.y: for each query head c * group + i its pieces' partial sums at scratch
 // offset `off`, added in piece order from +0 (k_attn_add_pieces' number), then the heads in head order from head 0's
 template <int V, bool VEC, typename E>
@@ -615,8 +914,10 @@ __global__ __launch_bounds__(kBlock) void k_attn_add_pieces_gqa(GroupPieces g, i
 // one grid per kernel for all heads: x is what a call of one head launches, y the query head within its group of `group`, z
 // the group (the K/V head); group = 1 for the _heads calls.  gqa (backward_kv only): the _gqa call, which sums the heads of a
 // group (k_attn_bwd_kv_rows_gqa, k_attn_add_pieces_gqa; also at group = 1).
+// bb: the call's bias (a _bias entry point: the _bias twins of the seven span kernels run) or null
 template <int PASS, int V, bool VEC, typename E>
-int launch_attn_v(const spmv_csr &h, const AttnArgsT<E> &a, int heads, int group, bool gqa, const char *what, hipStream_t s)
+int launch_attn_v(const spmv_csr &h, const AttnArgsT<E> &a, const AttnBias *bb, int heads, int group, bool gqa, const char *what,
+                  hipStream_t s)
 {
     const SpmmPlan &p = h.plan_spmm;
     const int64_t nblocks = group_head_blocks(what, h, V, heads);
@@ -624,7 +925,12 @@ int launch_attn_v(const spmv_csr &h, const AttnArgsT<E> &a, int heads, int group
     const GroupRows g = group_rows(h, V, nblocks);
     const unsigned kv_heads = (unsigned)(heads / group);
     const dim3 grid((unsigned)nblocks, (unsigned)group, kv_heads), block(kBlock);
-    if constexpr (PASS == kPassForward) hipLaunchKernelGGL((k_attn_fwd_rows<V, VEC, E>), grid, block, 0, s, g, a);
+    if (bb) {
+        if constexpr (PASS == kPassForward) hipLaunchKernelGGL((k_attn_fwd_rows_bias<V, VEC, E>), grid, block, 0, s, g, a, *bb);
+        else if constexpr (PASS == kPassBackwardQ) hipLaunchKernelGGL((k_attn_bwd_q_rows_bias<V, VEC, E>), grid, block, 0, s, g, a, *bb);
+        else if (gqa) hipLaunchKernelGGL((k_attn_bwd_kv_rows_gqa_bias<V, VEC, E>), dim3((unsigned)nblocks, kv_heads), block, 0, s, g, a, group, *bb);
+        else hipLaunchKernelGGL((k_attn_bwd_kv_rows_bias<V, VEC, E>), grid, block, 0, s, g, a, *bb);
+    } else if constexpr (PASS == kPassForward) hipLaunchKernelGGL((k_attn_fwd_rows<V, VEC, E>), grid, block, 0, s, g, a);
     else if constexpr (PASS == kPassBackwardQ) hipLaunchKernelGGL((k_attn_bwd_q_rows<V, VEC, E>), grid, block, 0, s, g, a);
     else if (gqa) hipLaunchKernelGGL((k_attn_bwd_kv_rows_gqa<V, VEC, E>), dim3((unsigned)nblocks, kv_heads), block, 0, s, g, a, group);
     else hipLaunchKernelGGL((k_attn_bwd_kv_rows<V, VEC, E>), grid, block, 0, s, g, a);
@@ -633,17 +939,20 @@ int launch_attn_v(const spmv_csr &h, const AttnArgsT<E> &a, int heads, int group
     const GroupPieces q = group_pieces(h, h.plan_attn.d_scratch.get());
     const dim3 pgrid(group_grid(p.pieces, V).x, (unsigned)group, kv_heads), lgrid(group_grid(p.n_long, V).x, (unsigned)heads);
     if constexpr (PASS == kPassForward) {
-        hipLaunchKernelGGL((k_attn_fwd_pieces<V, VEC, E>), pgrid, block, 0, s, q, a);
+        if (bb) hipLaunchKernelGGL((k_attn_fwd_pieces_bias<V, VEC, E>), pgrid, block, 0, s, q, a, *bb);
+        else hipLaunchKernelGGL((k_attn_fwd_pieces<V, VEC, E>), pgrid, block, 0, s, q, a);
         SPMV_LAUNCHED("k_attn_fwd_pieces");
         hipLaunchKernelGGL((k_attn_fwd_combine<V, VEC, E>), dim3(lgrid.x, (unsigned)group, kv_heads), block, 0, s, q, a);
         SPMV_LAUNCHED("k_attn_fwd_combine");
     } else if constexpr (PASS == kPassBackwardQ) {
-        hipLaunchKernelGGL((k_attn_bwd_q_pieces<V, VEC, E>), pgrid, block, 0, s, q, a);
+        if (bb) hipLaunchKernelGGL((k_attn_bwd_q_pieces_bias<V, VEC, E>), pgrid, block, 0, s, q, a, *bb);
+        else hipLaunchKernelGGL((k_attn_bwd_q_pieces<V, VEC, E>), pgrid, block, 0, s, q, a);
         SPMV_LAUNCHED("k_attn_bwd_q_pieces");
         hipLaunchKernelGGL((k_attn_add_pieces<V, VEC, E>), lgrid, block, 0, s, q, kAtSums, a.out0, a.ld0, a.k, a.h0);
         SPMV_LAUNCHED("k_attn_add_pieces");
     } else {
-        hipLaunchKernelGGL((k_attn_bwd_kv_pieces<V, VEC, E>), pgrid, block, 0, s, q, a);
+        if (bb) hipLaunchKernelGGL((k_attn_bwd_kv_pieces_bias<V, VEC, E>), pgrid, block, 0, s, q, a, *bb);
+        else hipLaunchKernelGGL((k_attn_bwd_kv_pieces<V, VEC, E>), pgrid, block, 0, s, q, a);
         SPMV_LAUNCHED("k_attn_bwd_kv_pieces");
         if (gqa) {
             const dim3 cgrid(lgrid.x, kv_heads);
@@ -662,13 +971,14 @@ int launch_attn_v(const spmv_csr &h, const AttnArgsT<E> &a, int heads, int group
 }
 
 template <int PASS, typename E>
-int launch_attn(const spmv_csr &h, const AttnArgsT<E> &a, int heads, int group, bool gqa, bool vec, const char *what, hipStream_t s)
+int launch_attn(const spmv_csr &h, const AttnArgsT<E> &a, const AttnBias *bb, int heads, int group, bool gqa, bool vec, const char *what,
+                hipStream_t s)
 {
     if (h.rows == 0) return SPMV_OK;
     return dispatch_lanes(((a.k > a.kv ? a.k : a.kv) + 3) / 4, [&](auto v) {
         constexpr int V = decltype(v)::value;
-        return vec ? launch_attn_v<PASS, V, true, E>(h, a, heads, group, gqa, what, s)
-                   : launch_attn_v<PASS, V, false, E>(h, a, heads, group, gqa, what, s);
+        return vec ? launch_attn_v<PASS, V, true, E>(h, a, bb, heads, group, gqa, what, s)
+                   : launch_attn_v<PASS, V, false, E>(h, a, bb, heads, group, gqa, what, s);
     });
 }
 
@@ -716,37 +1026,37 @@ int attention_max_heads(const spmv_csr &h, int width)
 // needs every ld the pass uses to be a multiple of 4.
 namespace {
 template <typename E>
-int launch_attention_e(AttnPass pass, const spmv_csr &h, const AttnArgsT<E> &a, int heads, int group, bool sum_group, const char *what,
-                       hipStream_t s)
+int launch_attention_e(AttnPass pass, const spmv_csr &h, const AttnArgsT<E> &a, const AttnBias *bb, int heads, int group, bool sum_group,
+                       const char *what, hipStream_t s)
 {
     switch (pass) {
-        case kPassForward: return launch_attn<kPassForward>(h, a, heads, group, false, vec4({a.ldq, a.ldk, a.ldv, a.ld0}), what, s);
+        case kPassForward: return launch_attn<kPassForward>(h, a, bb, heads, group, false, vec4({a.ldq, a.ldk, a.ldv, a.ld0}), what, s);
         case kPassBackwardQ:
-            return launch_attn<kPassBackwardQ>(h, a, heads, group, false, vec4({a.ldq, a.ldk, a.ldv, a.ldo, a.lddo, a.ld0}), what, s);
+            return launch_attn<kPassBackwardQ>(h, a, bb, heads, group, false, vec4({a.ldq, a.ldk, a.ldv, a.ldo, a.lddo, a.ld0}), what, s);
         case kPassBackwardKV:
-            return launch_attn<kPassBackwardKV>(h, a, heads, group, sum_group, vec4({a.ldq, a.ldk, a.ldv, a.lddo, a.ld0, a.ld1}), what, s);
+            return launch_attn<kPassBackwardKV>(h, a, bb, heads, group, sum_group, vec4({a.ldq, a.ldk, a.ldv, a.lddo, a.ld0, a.ld1}), what, s);
     }
     return SPMV_ERR_INVALID;
 }
 }  // namespace
 
-int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgs &a, int heads, int group, bool sum_group, const char *what,
-                     hipStream_t s)
+int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgs &a, const AttnBias *bb, int heads, int group, bool sum_group,
+                     const char *what, hipStream_t s)
 {
-    return launch_attention_e(pass, h, a, heads, group, sum_group, what, s);
+    return launch_attention_e(pass, h, a, bb, heads, group, sum_group, what, s);
 }
 
 // the _16 entry points: the same kernels on 16-bit matrices
-int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgsT<bf16> &a, int heads, int group, bool sum_group, const char *what,
-                     hipStream_t s)
+int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgsT<bf16> &a, const AttnBias *bb, int heads, int group, bool sum_group,
+                     const char *what, hipStream_t s)
 {
-    return launch_attention_e(pass, h, a, heads, group, sum_group, what, s);
+    return launch_attention_e(pass, h, a, bb, heads, group, sum_group, what, s);
 }
 
-int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgsT<fp16> &a, int heads, int group, bool sum_group, const char *what,
-                     hipStream_t s)
+int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgsT<fp16> &a, const AttnBias *bb, int heads, int group, bool sum_group,
+                     const char *what, hipStream_t s)
 {
-    return launch_attention_e(pass, h, a, heads, group, sum_group, what, s);
+    return launch_attention_e(pass, h, a, bb, heads, group, sum_group, what, s);
 }
 
 }  // namespace spmv

@@ -382,16 +382,19 @@ int plan_attention_heads(spmv_csr &h, int heads, hipStream_t s);
 int64_t attention_plan_bytes(const spmv_csr &h);
 int attention_max_heads(const spmv_csr &h, int width);   // heads one launch takes at operands of `width` columns (>= 0)
 // (one call of any of the nine entry points: `a` filled and checked by capi.hip; `heads` query heads, `group` of them per K/V head;
-// sum_group: backward_kv adds the heads of a group in the kernel, as the _gqa call does; `what` names the caller in a refusal)
-int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgs &a, int heads, int group, bool sum_group, const char *what,
-                     hipStream_t s);
-int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgsT<bf16> &a, int heads, int group, bool sum_group, const char *what,
-                     hipStream_t s);       // the _16 entry points: matrices of 16-bit elements, every ld and stride in elements
-int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgsT<fp16> &a, int heads, int group, bool sum_group, const char *what,
-                     hipStream_t s);
+// sum_group: backward_kv adds the heads of a group in the kernel, as the _gqa call does; `what` names the caller in a refusal;
+// bb: the bias of a _bias entry point, null for every other call)
+int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgs &a, const AttnBias *bb, int heads, int group, bool sum_group,
+                     const char *what, hipStream_t s);
+int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgsT<bf16> &a, const AttnBias *bb, int heads, int group, bool sum_group,
+                     const char *what, hipStream_t s);       // 16-bit matrices: every ld and stride in elements
+int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgsT<fp16> &a, const AttnBias *bb, int heads, int group, bool sum_group,
+                     const char *what, hipStream_t s);
 // kernels_transpose.hip: spmv_csr_transpose / spmv_csr_transpose_values
 int transpose(const spmv_csr &a, bool keep_map, hipStream_t s, spmv_csr_t **out);
 int transpose_values(spmv_csr &t, const spmv_csr &a, hipStream_t s);
+// dst[c * dst_stride + i] = src[c * src_stride + map[i]] for c < count through t's map (spmv_csr_transpose_gather)
+int transpose_gather(const spmv_csr &t, int count, const void *src, int64_t src_stride, void *dst, int64_t dst_stride, hipStream_t s);
 
 int dense_to_csr(int M, int N, const float *d_A, hipStream_t s, spmv_csr_t **out);
 int dense_gemv(int M, int N, const float *d_A, const float *d_x, float *d_y, int mode, hipStream_t s);

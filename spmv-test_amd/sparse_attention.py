@@ -21,6 +21,8 @@ per kernel (heads="batched": spmv_csr_attention_*_heads).  Both give the same bi
 with H_kv heads, H % H_kv == 0) run on spmv_csr_attention_*_gqa: K and V are not expanded, dK and dV come back per K/V head.
 Q, K and V may also be all torch.bfloat16 or all torch.float16 (spmv_csr_attention_*_16: 16-bit storage, fp32 sums, every output
 rounded once); O and the gradients then have that dtype, stats and delta stay float32.  The composed SparseAttention is fp32 only.
+FusedSparseAttention(..., bias=True) adds a float32 number per nonzero (and head) to the score before the softmax, with its
+gradient (spmv_csr_attention_*_bias): of nnz size a step then holds the bias, its copy in T's order and dBias, nothing else.
 """
 from __future__ import annotations
 
@@ -269,6 +271,88 @@ class FusedSparseAttentionFunction(torch.autograd.Function):
         return None, dQ if need_q else None, dK if need_k else None, dV if need_v else None
 
 
+class BiasedFusedSparseAttentionFunction(torch.autograd.Function):
+    """``BiasedFusedSparseAttentionFunction.apply(att, Q, K, V, bias)`` = softmax_rows(att.scale * Q K^T + bias at the pattern) V
+    on the three _bias passes: operands as FusedSparseAttentionFunction takes them (a 2-D call is one head), bias float32
+    (nnz,) -- one for all heads -- or (heads, nnz), in the storage order of the pattern.  Saved for backward: Q, K, V, O,
+    stats and bias.  Backward makes bias_t (the bias in T's order, one gather) only when dK or dV is asked for, and dBias
+    (heads, nnz) only when the bias requires grad; a shared bias gets dBias summed over the heads."""
+
+    @staticmethod
+    def _runs(att, heads: int, k: int, kv: int, g: int):
+        """[(lo, hi)]: whole groups of query heads per _bias call: as many as fit one launch ("batched"), or one group ("loop")"""
+        runs = att.head_chunks(heads, k, kv, g) if att.heads == "batched" else None
+        if runs is None:
+            att.plan_heads(g)
+            runs = [(lo, lo + g) for lo in range(0, heads, g)]
+        return runs
+
+    @staticmethod
+    def forward(ctx, att, Q, K, V, bias):
+        A = att.A
+        if len({t.dim() if isinstance(t, torch.Tensor) else -1 for t in (Q, K, V)}) != 1 or Q.dim() not in (2, 3):
+            raise ValueError("SparseAttention: Q, K and V must all be 2-D or all (heads, n, width)")
+        flat = Q.dim() == 2
+        if flat:
+            Q, K, V = Q[None], K[None], V[None]
+        Q = _batched_operand(Q, "Q", A.rows)
+        K = _batched_operand(K, "K", A.cols, Q.shape[-1])
+        V = _batched_operand(V, "V", A.cols)
+        for name, t in (("K", K), ("V", V)):
+            if t.dtype != Q.dtype:
+                raise ValueError(f"SparseAttention: {name} is {t.dtype}, Q is {Q.dtype} (Q, K and V share one dtype)")
+        heads, kv = Q.shape[0], V.shape[-1]
+        if K.shape[0] != V.shape[0] or heads % K.shape[0] != 0:
+            raise ValueError(f"SparseAttention: Q has {heads} heads, K {K.shape[0]} and V {V.shape[0]}")
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) not in ((A.nnz,), (heads, A.nnz)):
+            raise ValueError(f"SparseAttention: bias must be a float32 tensor of ({A.nnz},) or ({heads}, {A.nnz})")
+        bias = bias if bias.stride(-1) == 1 else bias.contiguous()
+        g = heads // K.shape[0]
+        O = _heads_empty(heads, A.rows, kv, V.device, V.dtype)
+        stats = torch.empty((heads, A.rows, 2), dtype=torch.float32, device=V.device)
+        for lo, hi in BiasedFusedSparseAttentionFunction._runs(att, heads, Q.shape[-1], kv, g):
+            A.attention_forward_bias(Q[lo:hi], K[lo // g:hi // g], V[lo // g:hi // g], bias if bias.dim() == 1 else bias[lo:hi],
+                                     O[lo:hi], stats[lo:hi], att.scale)
+        ctx.att, ctx.flat = att, flat
+        ctx.save_for_backward(Q, K, V, O, stats, bias)
+        return O[0] if flat else O
+
+    @staticmethod
+    def backward(ctx, dO):
+        att = ctx.att
+        A, T = att.A, att.T
+        Q, K, V, O, stats, bias = ctx.saved_tensors
+        need_q, need_k, need_v, need_b = ctx.needs_input_grad[1:5]
+        if not (need_q or need_k or need_v or need_b):
+            return None, None, None, None, None
+        dO = _batched_operand(dO[None] if ctx.flat else dO, "dO", A.rows, V.shape[-1])
+        if dO.shape[0] != Q.shape[0] or dO.dtype != Q.dtype:
+            raise ValueError(f"SparseAttention: dO is {dO.dtype} with {dO.shape[0]} heads, Q {Q.dtype} with {Q.shape[0]}")
+        heads, g = Q.shape[0], Q.shape[0] // K.shape[0]
+        shared = bias.dim() == 1
+        # backward_q also makes delta, which backward_kv reads: it runs whichever gradient is asked for
+        dQ = _heads_empty(*Q.shape, Q.device, Q.dtype)
+        delta = torch.empty(O.shape[:-1], dtype=torch.float32, device=O.device)
+        dBias = torch.empty((heads, A.nnz), dtype=torch.float32, device=O.device) if need_b else None
+        dK = dV = bias_t = None
+        if need_k or need_v:
+            dK, dV = _heads_empty(*K.shape, K.device, K.dtype), _heads_empty(*V.shape, V.device, V.dtype)
+            bias_t = torch.empty_like(bias)
+            T.transpose_gather(bias, bias_t)
+        for lo, hi in BiasedFusedSparseAttentionFunction._runs(att, heads, Q.shape[-1], V.shape[-1], g):
+            at = lambda t, lo=lo, hi=hi: t[lo:hi]       # noqa: E731
+            kv = lambda t, lo=lo // g, hi=hi // g: t[lo:hi]       # noqa: E731  (the run's K/V heads)
+            A.attention_backward_q_bias(at(Q), kv(K), kv(V), bias if shared else at(bias), at(O), at(dO), at(stats), at(delta), at(dQ),
+                                        at(dBias) if need_b else None, att.scale)
+            if dK is not None:
+                T.attention_backward_kv_bias(at(Q), kv(K), kv(V), bias_t if shared else at(bias_t), at(dO), at(stats), at(delta),
+                                             kv(dK), kv(dV), att.scale)
+        if need_b and shared:
+            dBias = dBias[0] if heads == 1 else dBias.sum(0)
+        one = (lambda t: t[0]) if ctx.flat else (lambda t: t)
+        return None, one(dQ) if need_q else None, one(dK) if need_k else None, one(dV) if need_v else None, dBias
+
+
 class FusedSparseAttention:
     """One attention pattern of rows queries by cols keys on the fused passes.  Borrows ``row_ptr`` and ``col_idx`` (int32,
     one device); owns T = A^T (pattern only: no map) and both attention plans.  ``att(Q, K, V)``: Q rows x k, K cols x k,
@@ -287,9 +371,13 @@ class FusedSparseAttention:
     layout above (alignment and strides then count 2-byte elements: a head starts on an 8-byte boundary); O, the saved O and
     the gradients have that dtype, stats and delta stay float32; every output is the fp32 result rounded once, so with
     grouped K/V "loop" leaves the sum over a group's heads to one _gqa call per K/V head.  A query without keys gets a zero row of O.  Calls of one holder are stream-ordered (the plans' scratch).  The
-    values array that handle creation still asks for is allocated once here and never read."""
+    values array that handle creation still asks for is allocated once here and never read.
+    ``bias=True``: ``att(Q, K, V, bias)`` adds ``bias`` -- float32 (nnz,), shared by all heads, or (heads, nnz), in the storage
+    order of ``col_idx`` -- to the scaled scores before the softmax and is differentiable in it
+    (BiasedFusedSparseAttentionFunction); T then keeps its map (4 bytes per nonzero), which brings the bias into T's order in
+    backward.  Every layout and dtype above works; "loop" runs one call per K/V head, "batched" as many groups as fit."""
 
-    def __init__(self, rows: int, cols: int, row_ptr, col_idx, scale: float = 1.0, heads: str = "loop"):
+    def __init__(self, rows: int, cols: int, row_ptr, col_idx, scale: float = 1.0, heads: str = "loop", bias: bool = False):
         if heads not in ("loop", "batched"):
             raise ValueError(f"SparseAttention: heads = {heads!r} (\"loop\" or \"batched\")")
         if not math.isfinite(scale):
@@ -300,11 +388,16 @@ class FusedSparseAttention:
         self._planned = 1
         vals = torch.zeros(int(col_idx.numel()), dtype=torch.float32, device=col_idx.device)
         self.A = capi.CsrMatrix.from_device(rows, cols, row_ptr, col_idx, vals)
-        self.T = self.A.transpose(keep_map=False)
+        self.bias = bool(bias)
+        self.T = self.A.transpose(keep_map=self.bias)
         self.A.attention_plan()
         self.T.attention_plan()
 
-    def __call__(self, Q, K, V):
+    def __call__(self, Q, K, V, bias=None):
+        if self.bias != (bias is not None):
+            raise ValueError("SparseAttention: a holder made with bias=True takes att(Q, K, V, bias), any other att(Q, K, V)")
+        if bias is not None:
+            return BiasedFusedSparseAttentionFunction.apply(self, Q, K, V, bias)
         return FusedSparseAttentionFunction.apply(self, Q, K, V)
 
     def head_chunks(self, heads: int, k: int, kv: int, group: int = 1):

@@ -12,7 +12,12 @@
 // head order from the first head's value.  Then the same four heads on two K/V heads on 16-bit matrices (bf16 and fp16; (6, 10)
 // and (40, 64); both load paths): every array an exactly sized heap block of 2-byte elements, O, dQ, dK and dV bit for bit the
 // program's own fp32 _gqa runs on the widened data, rounded to nearest even by a conversion written here, stats and delta those
-// runs' bits.
+// runs' bits.  Then the additive bias (the _bias kernels through launch_attention with an AttnBias): the same four heads on two
+// K/V heads at (6, 10) and (40, 64) on both load paths, fp32 and bf16 matrices, a bias per query head and nonzero, bias, bias_t
+// (the bias in the transposed pattern's order) and dBias exactly sized heap blocks of floats with head strides that are
+// multiples of nothing, rows and transposed rows in pieces: O, dQ, dBias, dK and dV against a serial fp64 attention with bias
+// written here (fp32: 2e-5 of the magnitude; bf16: 2^-7 more: half an ulp, 2^-8, for the rounded output and as much for the delta
+// formed from the rounded O), and every position of dBias written.
 #include "kernels_attention.hip"
 #include "kernels_sddmm.hip"
 #include <algorithm>
@@ -101,7 +106,7 @@ static int forward(const spmv_csr &A, int heads, int group, float scale, int k, 
 {
     AttnArgs a = attn_inputs(scale, k, kv, Q, K, V);
     a.out0 = O.p, a.ld0 = O.ld, a.h0 = O.stride, a.stats = stats.p, a.hstats = stats.stride;
-    return launch_attention(kPassForward, A, a, heads, group, false, "forward", nullptr);
+    return launch_attention(kPassForward, A, a, nullptr, heads, group, false, "forward", nullptr);
 }
 
 static int backward_q(const spmv_csr &A, int heads, int group, float scale, int k, int kv, const HeadsMatrix &Q, const HeadsMatrix &K,
@@ -112,7 +117,7 @@ static int backward_q(const spmv_csr &A, int heads, int group, float scale, int 
     a.O = O.p, a.ldo = O.ld, a.ho = O.stride, a.dO = dO.p, a.lddo = dO.ld, a.hdo = dO.stride;
     a.stats_in = stats.p, a.hstats_in = stats.stride, a.delta = delta.p, a.hdelta = delta.stride;
     a.out0 = dQ.p, a.ld0 = dQ.ld, a.h0 = dQ.stride;
-    return launch_attention(kPassBackwardQ, A, a, heads, group, false, "backward_q", nullptr);
+    return launch_attention(kPassBackwardQ, A, a, nullptr, heads, group, false, "backward_q", nullptr);
 }
 
 // sum_group: the _gqa call's kernels, which add the heads of a group
@@ -124,7 +129,7 @@ static int backward_kv(const spmv_csr &T, int heads, int group, bool sum_group, 
     a.dO = dO.p, a.lddo = dO.ld, a.hdo = dO.stride;
     a.stats_in = stats.p, a.hstats_in = stats.stride, a.delta_in = delta.p, a.hdelta_in = delta.stride;
     a.out0 = dK.p, a.ld0 = dK.ld, a.h0 = dK.stride, a.out1 = dV.p, a.ld1 = dV.ld, a.h1 = dV.stride;
-    return launch_attention(kPassBackwardKV, T, a, heads, group, sum_group, "backward_kv", nullptr);
+    return launch_attention(kPassBackwardKV, T, a, nullptr, heads, group, sum_group, "backward_kv", nullptr);
 }
 
 // how many of head y's rows x w floats differ in a bit from the single-head result
@@ -460,13 +465,13 @@ template <typename E> static int runs16(const char *name, spmv_csr &A, spmv_csr 
             in.Q = Q, in.ldq = hQ.ld, in.hq = hQ.stride, in.K = K, in.ldk = hK.ld, in.hk = hK.stride, in.V = Vm, in.ldv = hV.ld, in.hv = hV.stride;
             AttnArgsT<E> f = in, bq = in, bk = in;
             f.out0 = O, f.ld0 = hO.ld, f.h0 = hO.stride, f.stats = stats16, f.hstats = sstats;
-            status |= launch_attention(kPassForward, A, f, H, G, false, "forward_16", nullptr);
+            status |= launch_attention(kPassForward, A, f, nullptr, H, G, false, "forward_16", nullptr);
             bq.O = O, bq.ldo = hO.ld, bq.ho = hO.stride, bq.dO = dO, bq.lddo = hdO.ld, bq.hdo = hdO.stride;
             bq.stats_in = stats16, bq.hstats_in = sstats, bq.delta = delta16, bq.hdelta = sdelta, bq.out0 = dQ, bq.ld0 = hdQ.ld, bq.h0 = hdQ.stride;
-            status |= launch_attention(kPassBackwardQ, A, bq, H, G, false, "backward_q_16", nullptr);
+            status |= launch_attention(kPassBackwardQ, A, bq, nullptr, H, G, false, "backward_q_16", nullptr);
             bk.dO = dO, bk.lddo = hdO.ld, bk.hdo = hdO.stride, bk.stats_in = stats16, bk.hstats_in = sstats, bk.delta_in = delta16, bk.hdelta_in = sdelta;
             bk.out0 = dK, bk.ld0 = hdK.ld, bk.h0 = hdK.stride, bk.out1 = dV, bk.ld1 = hdV.ld, bk.h1 = hdV.stride;
-            status |= launch_attention(kPassBackwardKV, T, bk, H, G, true, "backward_kv_16", nullptr);
+            status |= launch_attention(kPassBackwardKV, T, bk, nullptr, H, G, true, "backward_kv_16", nullptr);
             long bad = differs16<E>(O, hO, H, R, kv) + differs16<E>(dQ, hdQ, H, R, k) + differs16<E>(dK, hdK, C2, C, k) + differs16<E>(dV, hdV, C2, C, kv);
             for (int y = 0; y < H; ++y) {
                 bad += std::memcmp(stats16 + y * sstats, stats + y * sstats, 8 * (size_t)R) != 0;
@@ -478,6 +483,162 @@ template <typename E> static int runs16(const char *name, spmv_csr &A, spmv_csr 
             for (void *p : {(void *)hQ.p, (void *)hK.p, (void *)hV.p, (void *)hdO.p, (void *)hO.p, (void *)hO16.p, (void *)hdQ.p, (void *)hdK.p,
                             (void *)hdV.p, (void *)stats, (void *)delta, (void *)stats16, (void *)delta16, (void *)Q, (void *)K, (void *)Vm,
                             (void *)dO, (void *)O, (void *)dQ, (void *)dK, (void *)dV})
+                free(p);
+        }
+    return status;
+}
+
+// ---- the additive bias --------------------------------------------------------------------------------------------------------
+template <typename E> static float elem(const E *p, int64_t i)
+{
+    if constexpr (std::is_same<E, float>::value) {
+        return p[i];
+    } else {
+        uint16_t b;
+        std::memcpy(&b, (const uint16_t *)p + i, 2);
+        return from16<E>(b);
+    }
+}
+
+// an exactly sized block of E with the layout of m: the fp32 block itself, or its 16-bit twin
+template <typename E> static E *as_elements(const HeadsMatrix &m, int heads, int64_t rows, int w, bool vec, bool fill)
+{
+    if constexpr (std::is_same<E, float>::value) return m.p;
+    else return twin16<E>(m, heads, rows, w, vec, fill);
+}
+
+template <typename E> static int bias_runs(const char *name, spmv_csr &A, spmv_csr &T, const Pattern &a, const Pattern &t, float scale, std::mt19937 &rng)
+{
+    constexpr int H = 4, G = 2, C2 = H / G;
+    constexpr bool wide = std::is_same<E, float>::value;
+    const double tol = wide ? 2e-5 : 2e-5 + 1.0 / 128;
+    const int shapes[][2] = {{6, 10}, {40, 64}};
+    const int64_t R = a.rows, C = a.cols, nnz = A.nnz;
+    int status = 0;
+    plan_heads(A, H);
+    plan_heads(T, H);
+    // map[i]: the position in a of nonzero i of t (the stable order of transpose() above)
+    std::vector<int32_t> map((size_t)nnz), at(t.rp.begin(), t.rp.end() - 1);
+    for (int64_t r = 0; r < R; ++r)
+        for (int n = a.rp[r]; n < a.rp[r + 1]; ++n) map[(size_t)at[a.ci[n]]++] = n;
+    for (auto &kk : shapes)
+        for (int odd = 0; odd < 2; ++odd) {
+            const int k = kk[0], kv = kk[1];
+            int V = 1;
+            while (4 * V < std::max(k, kv)) V *= 2;
+            g_group_lanes = V;
+            const bool vec = !odd;
+            auto ld = [&](int w) { return (int64_t)(odd ? w + 1 + ((w + 1) % 4 == 0) : (w + 3) / 4 * 4 + 4); };
+            auto make = [&](int heads, int64_t rows, int w) { return heads_matrix(heads, rows, w, ld(w), (rows * ld(w) + 3) / 4 * 4 + 8, vec); };
+            HeadsMatrix hQ = make(H, R, k), hK = make(C2, C, k), hV = make(C2, C, kv), hdO = make(H, R, kv), hO = make(H, R, kv),
+                        hdQ = make(H, R, k), hdK = make(C2, C, k), hdV = make(C2, C, kv);
+            std::normal_distribution<float> nd(0.f, 1.f);
+            auto fill = [&](const HeadsMatrix &m, int heads, int64_t rows, int w) {
+                for (int y = 0; y < heads; ++y)
+                    for (int64_t r = 0; r < rows; ++r)
+                        for (int c = 0; c < w; ++c) {
+                            const float x = nd(rng);
+                            if constexpr (wide) m.p[y * m.stride + r * m.ld + c] = x;
+                            else m.p[y * m.stride + r * m.ld + c] = from16<E>(to16<E>(x));
+                        }
+            };
+            fill(hQ, H, R, k), fill(hK, C2, C, k), fill(hV, C2, C, kv), fill(hdO, H, R, kv);
+            const int64_t sstats = 2 * R + 2, sdelta = R + 3, sb = nnz + 3, sdb = nnz + 1;
+            float *stats = (float *)malloc(4 * (size_t)((H - 1) * sstats + 2 * R)), *delta = (float *)malloc(4 * (size_t)((H - 1) * sdelta + R));
+            float *bias = (float *)malloc(4 * (size_t)((H - 1) * sb + nnz)), *bias_t = (float *)malloc(4 * (size_t)((H - 1) * sb + nnz));
+            float *dbias = (float *)malloc(4 * (size_t)((H - 1) * sdb + nnz));
+            for (int64_t i = 0; i < (H - 1) * sb + nnz; ++i) bias[i] = bias_t[i] = NAN;
+            for (int64_t i = 0; i < (H - 1) * sdb + nnz; ++i) dbias[i] = NAN;
+            for (int y = 0; y < H; ++y) {
+                for (int64_t n = 0; n < nnz; ++n) bias[y * sb + n] = nd(rng);
+                for (int64_t i = 0; i < nnz; ++i) bias_t[y * sb + i] = bias[y * sb + map[(size_t)i]];
+            }
+            E *Q = as_elements<E>(hQ, H, R, k, vec, true), *K = as_elements<E>(hK, C2, C, k, vec, true), *Vm = as_elements<E>(hV, C2, C, kv, vec, true);
+            E *dO = as_elements<E>(hdO, H, R, kv, vec, true), *O = as_elements<E>(hO, H, R, kv, vec, false), *dQ = as_elements<E>(hdQ, H, R, k, vec, false);
+            E *dK = as_elements<E>(hdK, C2, C, k, vec, false), *dV = as_elements<E>(hdV, C2, C, kv, vec, false);
+            AttnArgsT<E> in{};
+            in.scale = scale, in.k = k, in.kv = kv;
+            in.Q = Q, in.ldq = hQ.ld, in.hq = hQ.stride, in.K = K, in.ldk = hK.ld, in.hk = hK.stride, in.V = Vm, in.ldv = hV.ld, in.hv = hV.stride;
+            AttnArgsT<E> f = in, bq = in, bk = in;
+            const AttnBias bf{bias, sb, nullptr, 0}, bqb{bias, sb, dbias, sdb}, bkb{bias_t, sb, nullptr, 0};
+            f.out0 = O, f.ld0 = hO.ld, f.h0 = hO.stride, f.stats = stats, f.hstats = sstats;
+            status |= launch_attention(kPassForward, A, f, &bf, H, G, false, "forward_bias", nullptr);
+            bq.O = O, bq.ldo = hO.ld, bq.ho = hO.stride, bq.dO = dO, bq.lddo = hdO.ld, bq.hdo = hdO.stride;
+            bq.stats_in = stats, bq.hstats_in = sstats, bq.delta = delta, bq.hdelta = sdelta, bq.out0 = dQ, bq.ld0 = hdQ.ld, bq.h0 = hdQ.stride;
+            status |= launch_attention(kPassBackwardQ, A, bq, &bqb, H, G, false, "backward_q_bias", nullptr);
+            bk.dO = dO, bk.lddo = hdO.ld, bk.hdo = hdO.stride, bk.stats_in = stats, bk.hstats_in = sstats, bk.delta_in = delta, bk.hdelta_in = sdelta;
+            bk.out0 = dK, bk.ld0 = hdK.ld, bk.h0 = hdK.stride, bk.out1 = dV, bk.ld1 = hdV.ld, bk.h1 = hdV.stride;
+            status |= launch_attention(kPassBackwardKV, T, bk, &bkb, H, G, true, "backward_kv_bias", nullptr);
+            // serial fp64 attention with bias, per query head; dK and dV summed over the heads of a group
+            double worst = 0.0;
+            long unwritten = 0;
+            auto err = [&](double got, double want, double mag) { worst = std::max(worst, std::fabs(got - want) / (mag + 1e-30)); };
+            std::vector<double> rdK((size_t)(C2 * C * k), 0.0), rdV((size_t)(C2 * C * kv), 0.0), mK(rdK), mV(rdV);
+            for (int y = 0; y < H; ++y) {
+                const int c2 = y / G;
+                const float *q = hQ.p + y * hQ.stride, *kj = hK.p + c2 * hK.stride, *vj = hV.p + c2 * hV.stride, *g = hdO.p + y * hdO.stride;
+                for (int64_t i = 0; i < R; ++i) {
+                    const int b = a.rp[i], e = a.rp[i + 1], L = e - b;
+                    std::vector<double> p((size_t)L), dp((size_t)L), adp((size_t)L);
+                    double M = -INFINITY, S = 0.0, dot = 0.0, adot = 0.0;
+                    for (int n = b; n < e; ++n) {
+                        double s = 0.0;
+                        for (int c = 0; c < k; ++c) s += (double)q[i * hQ.ld + c] * kj[a.ci[n] * hK.ld + c];
+                        p[n - b] = s * scale + bias[y * sb + n];
+                        M = std::max(M, p[n - b]);
+                    }
+                    for (int n = 0; n < L; ++n) S += (p[n] = std::exp(p[n] - M));
+                    for (int n = 0; n < L; ++n) {
+                        p[n] /= S;
+                        double s = 0.0, as = 0.0;
+                        for (int c = 0; c < kv; ++c) {
+                            const double x = (double)g[i * hdO.ld + c] * vj[a.ci[b + n] * hV.ld + c];
+                            s += x, as += std::fabs(x);
+                        }
+                        dp[n] = s, adp[n] = as, dot += p[n] * s, adot += p[n] * as;
+                    }
+                    for (int c = 0; c < kv; ++c) {
+                        double o = 0.0, ao = 0.0;
+                        for (int n = 0; n < L; ++n) o += p[n] * vj[a.ci[b + n] * hV.ld + c], ao += p[n] * std::fabs(vj[a.ci[b + n] * hV.ld + c]);
+                        err(elem<E>(O, y * hO.stride + i * hO.ld + c), o, ao + (L == 0));
+                    }
+                    for (int n = 0; n < L; ++n) {
+                        const double gb = p[n] * (dp[n] - dot), agb = p[n] * (adp[n] + adot + 1e-3);
+                        const float got = dbias[y * sdb + b + n];
+                        unwritten += got != got;
+                        err(got, gb, agb);
+                        for (int c = 0; c < k; ++c) {
+                            rdK[(size_t)((c2 * C + a.ci[b + n]) * k + c)] += scale * gb * q[i * hQ.ld + c];
+                            mK[(size_t)((c2 * C + a.ci[b + n]) * k + c)] += scale * agb * std::fabs(q[i * hQ.ld + c]);
+                        }
+                        for (int c = 0; c < kv; ++c) {
+                            rdV[(size_t)((c2 * C + a.ci[b + n]) * kv + c)] += p[n] * g[i * hdO.ld + c];
+                            mV[(size_t)((c2 * C + a.ci[b + n]) * kv + c)] += p[n] * std::fabs(g[i * hdO.ld + c]);
+                        }
+                    }
+                    for (int c = 0; c < k; ++c) {
+                        double d = 0.0, ad = 0.0;
+                        for (int n = 0; n < L; ++n) {
+                            d += scale * p[n] * (dp[n] - dot) * kj[a.ci[b + n] * hK.ld + c];
+                            ad += scale * p[n] * (adp[n] + adot + 1e-3) * std::fabs(kj[a.ci[b + n] * hK.ld + c]);
+                        }
+                        err(elem<E>(dQ, y * hdQ.stride + i * hdQ.ld + c), d, ad + (L == 0));
+                    }
+                }
+            }
+            for (int c2 = 0; c2 < C2; ++c2)
+                for (int64_t j = 0; j < C; ++j) {
+                    const double none = t.rp[j + 1] == t.rp[j] ? 1.0 : 0.0;
+                    for (int c = 0; c < k; ++c) err(elem<E>(dK, c2 * hdK.stride + j * hdK.ld + c), rdK[(size_t)((c2 * C + j) * k + c)], mK[(size_t)((c2 * C + j) * k + c)] + none);
+                    for (int c = 0; c < kv; ++c) err(elem<E>(dV, c2 * hdV.stride + j * hdV.ld + c), rdV[(size_t)((c2 * C + j) * kv + c)], mV[(size_t)((c2 * C + j) * kv + c)] + none);
+                }
+            printf("bias %s heads %d group %d k %d kv %d V %d %s: status %d, worst normalised error %.3g (allowed %.3g), %ld positions of dBias unwritten\n",
+                   name, H, G, k, kv, V, odd ? "scalar path" : "vector path", status, worst, tol, unwritten);
+            if (!(worst <= tol) || unwritten) status |= 512;
+            if constexpr (!wide)
+                for (void *p : {(void *)Q, (void *)K, (void *)Vm, (void *)dO, (void *)O, (void *)dQ, (void *)dK, (void *)dV}) free(p);
+            for (void *p : {(void *)hQ.p, (void *)hK.p, (void *)hV.p, (void *)hdO.p, (void *)hO.p, (void *)hdQ.p, (void *)hdK.p, (void *)hdV.p,
+                            (void *)stats, (void *)delta, (void *)bias, (void *)bias_t, (void *)dbias})
                 free(p);
         }
     return status;
@@ -603,6 +764,8 @@ int main()
     status |= gqa_runs(A, T, a, scale, rng);
     status |= runs16<bf16>("bf16", A, T, a, scale, rng);
     status |= runs16<fp16>("fp16", A, T, a, scale, rng);
+    status |= bias_runs<float>("fp32", A, T, a, t, scale, rng);
+    status |= bias_runs<bf16>("bf16", A, T, a, t, scale, rng);
     for (void *p : owned) free(p);
     free(A.plan_attn.d_scratch.p);
     free(T.plan_attn.d_scratch.p);

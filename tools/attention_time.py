@@ -39,6 +39,17 @@ fp32 path is the yardstick; nothing here sets a threshold.
 
     python tools/attention_time.py --dtype bf16,fp16 [--workloads c2:8192,c2:0,c3:8192,c3:0] [--ks 16,32,64]
                                    [--out profiles/attention_16bit.jsonl]
+
+--bias: the additive bias per nonzero.  On the same pattern arrays, in one process, the windows alternating, median of --reps:
+FusedSparseAttention(bias=True) called with a float32 bias of nnz numbers that requires grad (spmv_csr_attention_*_bias; the
+step includes the gather to T's order and dBias) against the unbiased FusedSparseAttention, the yardstick, and against the
+composed SparseAttention path with the bias added to the scaled scores by torch (SDDMM, mul and add on nnz floats, row softmax,
+SpMM; backward with dBias).  One JSON line per (workload, k = kv): the medians, the ratios biased / unbiased and
+biased / composed (below 1: the biased fused path is faster), the lowest and highest window of each, the bytes a step
+allocates.  Nothing here sets a threshold.
+
+    python tools/attention_time.py --bias [--workloads c2:8192,c2:0,c3:8192,c3:0] [--ks 16,32,64]
+                                   [--out profiles/attention_bias.jsonl]
 """
 import argparse
 import json
@@ -303,6 +314,109 @@ def dtype_main(a, emit):
         torch.cuda.empty_cache()
 
 
+def bias_main(a, emit):
+    """The biased fused holder against the unbiased one and against the composed path with a torch add (see the module docstring)."""
+    import torch
+    pkg = ge.load_package()
+    capi, W, SA = pkg.capi, pkg.workloads, pkg.sparse_attention
+    dev = torch.device("cuda:0")
+    scales = dict((s.split("=")[0], float(s.split("=")[1])) for s in a.scale.split(",") if s)
+    med, r4 = statistics.median, lambda x: round(x, 4)      # noqa: E731
+
+    class ComposedBias(torch.autograd.Function):
+        """SparseAttentionFunction with bias added to the scaled scores by torch; dBias is dS with respect to t."""
+
+        @staticmethod
+        def forward(ctx, att, Q, K, V, bias):
+            A = att.A
+            A.sddmm(Q, K, att.work)
+            att.work.mul_(att.scale).add_(bias)
+            A.row_softmax(att.work, att.work, 1.0)
+            A.values_changed()
+            O = torch.empty((A.rows, V.shape[1]), dtype=torch.float32, device=V.device)
+            A.spmm(V, O)
+            ctx.att = att
+            ctx.save_for_backward(Q, K, V, att.work.clone())
+            return O
+
+        @staticmethod
+        def backward(ctx, dO):
+            att = ctx.att
+            A, T, Wk = att.A, att.T, att.work
+            Q, K, V, P = ctx.saved_tensors
+            dO = dO.contiguous()
+            Wk.copy_(P)
+            A.values_changed()
+            T.transpose_values(A)
+            dV = torch.empty_like(V)
+            T.spmm(dO, dV)
+            A.sddmm(dO, V, Wk)
+            A.row_softmax_backward(P, Wk, Wk, 1.0)
+            dB = Wk.clone()
+            Wk.mul_(att.scale)
+            A.values_changed()
+            dQ, dK = torch.empty_like(Q), torch.empty_like(K)
+            A.spmm(K, dQ)
+            T.transpose_values(A)
+            T.spmm(Q, dK)
+            return None, dQ, dK, dV, dB
+
+    for spec in (a.workloads or "c2:8192,c2:0,c3:8192,c3:0").split(","):
+        name, rows, cols, d_rp, d_ci = heads_pattern(spec.partition("@")[0], capi, W, dev, scales)
+        nnz = int(d_ci.numel())
+        biased = SA.FusedSparseAttention(rows, cols, d_rp, d_ci, scale=0.25, bias=True)
+        plain = SA.FusedSparseAttention(rows, cols, d_rp, d_ci, scale=0.25)
+        composed = SA.SparseAttention(rows, cols, d_rp, d_ci, scale=0.25)
+        for k in (int(s) for s in a.ks.split(",")):
+            gen = torch.Generator(device=dev).manual_seed(k)
+            Q, K, V, dO = (torch.randn((n, k), generator=gen, device=dev) for n in (rows, cols, cols, rows))
+            B = torch.randn((nnz,), generator=gen, device=dev)
+            q, kk, v, b = (t.clone().requires_grad_(True) for t in (Q, K, V, B))
+            calls = {"biased": lambda *x: biased(*x), "plain": lambda Q, K, V, B: plain(Q, K, V),
+                     "composed": lambda *x: ComposedBias.apply(composed, *x)}
+
+            def forward(which):
+                with torch.no_grad():
+                    calls[which](Q, K, V, B)
+
+            def step(which):
+                calls[which](q, kk, v, b).backward(dO)
+                q.grad = kk.grad = v.grad = b.grad = None
+
+            def step_bytes(which):
+                step(which)
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                before = torch.cuda.memory_allocated()
+                step(which)
+                torch.cuda.synchronize()
+                return torch.cuda.max_memory_allocated() - before
+
+            with torch.no_grad():
+                diff = float((calls["biased"](Q, K, V, B) - calls["composed"](Q, K, V, B)).abs().max())
+            b_f, p_f, it_f = timed_windows(lambda: forward("biased"), lambda: forward("plain"), a.window_ms, a.reps, a.max_iters)
+            b_s, p_s, it_s = timed_windows(lambda: step("biased"), lambda: step("plain"), a.window_ms, a.reps, a.max_iters)
+            b_f2, c_f, _ = timed_windows(lambda: forward("biased"), lambda: forward("composed"), a.window_ms, a.reps, a.max_iters)
+            b_s2, c_s, _ = timed_windows(lambda: step("biased"), lambda: step("composed"), a.window_ms, a.reps, a.max_iters)
+            emit(workload=name, k=k, kv=k, rows=rows, cols=cols, nnz=nnz, plan=plain.A.spmm_describe(), plan_T=plain.T.spmm_describe(),
+                 iters_forward=it_f, iters_step=it_s, reps=a.reps,
+                 biased_forward_ms=r4(med(b_f)), unbiased_forward_ms=r4(med(p_f)), forward_ratio=round(med(b_f) / med(p_f), 3),
+                 biased_forward_windows=[r4(min(b_f)), r4(max(b_f))], unbiased_forward_windows=[r4(min(p_f)), r4(max(p_f))],
+                 biased_step_ms=r4(med(b_s)), unbiased_step_ms=r4(med(p_s)), step_ratio=round(med(b_s) / med(p_s), 3),
+                 biased_step_windows=[r4(min(b_s)), r4(max(b_s))], unbiased_step_windows=[r4(min(p_s)), r4(max(p_s))],
+                 composed_forward_ms=r4(med(c_f)), forward_ratio_to_composed=round(med(b_f2) / med(c_f), 3),
+                 composed_step_ms=r4(med(c_s)), step_ratio_to_composed=round(med(b_s2) / med(c_s), 3),
+                 biased_step_bytes=step_bytes("biased"), unbiased_step_bytes=step_bytes("plain"), composed_step_bytes=step_bytes("composed"),
+                 max_abs_diff_O_to_composed=diff)
+            del Q, K, V, dO, B, q, kk, v, b
+            torch.cuda.empty_cache()
+        biased.close()
+        plain.close()
+        composed.close()
+        del d_rp, d_ci
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", default=None, help="default: c2:8192,c2:0,c3:8192,c3:0,c4:8192,c4:0; with --heads: " + HEADS_WORKLOADS)
@@ -311,6 +425,7 @@ def main():
     ap.add_argument("--gqa", default=None, help="G[,G..]: time grouped K/V against K/V expanded with repeat_interleave at these group sizes")
     ap.add_argument("--gqa-heads", type=int, default=16, help="query heads of the --gqa runs")
     ap.add_argument("--dtype", default=None, help="bf16[,fp16]: time 16-bit operands against float32 ones on the fused passes")
+    ap.add_argument("--bias", action="store_true", help="time FusedSparseAttention(bias=True) against the unbiased and the composed path")
     ap.add_argument("--scale", default="", help="name=fraction of the rows, e.g. c4=0.5 where the memory does not hold the full size")
     ap.add_argument("--window-ms", type=float, default=200.0)
     ap.add_argument("--max-iters", type=int, default=50)
@@ -333,6 +448,10 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if a.bias:
+        a.ks = a.ks or "16,32,64"
+        bias_main(a, emit)
+        return
     if a.dtype:
         a.ks = a.ks or "16,32,64"
         dtype_main(a, emit)
