@@ -56,7 +56,9 @@
 // t is the order above.  The lane that ends up with the score of a nonzero after reduce_scatter loads its bias (4 coalesced
 // bytes per nonzero, none past the span's end, with the step's gathers or after reduce_scatter: kBiasEarly) and, in
 // backward_q, stores dBias[n] = p * (dp - delta), whose product with scale is ds: every position once, no atomics.  The bias
-// pointers are a second kernel argument (AttnBias): AttnArgsT and the kernarg segment of the unbiased kernels stay as they are.
+// pointers are one more kernel argument (AttnBias), the only element of the argument pack that ends each of the seven kernels
+// that run a span: k_attn_fwd_rows<V, VEC, E, AttnBias> is the biased kernel, k_attn_fwd_rows<V, VEC, E> with its empty pack the
+// unbiased one, whose AttnArgsT, kernarg segment and code hold nothing of the bias.
 //
 // The scratch of the long rows (AttnPlan): per head, kAtSlots floats per piece: [0] m_p, [1] l_p, [4, 132) up to 128 partial sums
 // (forward acc_p[kv]; backward_q dQ_p[k]; backward_kv dK_p[k] at 4 and dV_p[kv] at 68).
@@ -113,7 +115,12 @@ __device__ __forceinline__ float *at_head_scratch(const GroupPieces &g)
     return s;
 }
 
-// the bias of the block's query head (the _bias kernels; formed at entry like the bases above).  A null dbias stays null.
+// A kernel that runs a span ends in an argument pack `B... bb`: empty, or one AttnBias (BIAS = sizeof...(B) == 1), which
+// bias_of(bb...) reads.  The instantiation with the empty pack has neither the argument nor any code for it.
+__device__ __forceinline__ AttnBias bias_of() { return AttnBias{}; }
+__device__ __forceinline__ AttnBias bias_of(AttnBias b) { return b; }
+
+// the bias of the block's query head (formed at entry like the bases above).  A null dbias stays null.
 __device__ __forceinline__ AttnBias at_head(AttnBias b)
 {
     const int64_t y = query_head();
@@ -145,20 +152,22 @@ constexpr bool kBiasEarly = PASS == kPassForward     ? !(kIs16<E> && V <= 2)
                             : PASS == kPassBackwardQ ? !((kIs16<E> && V == 1) || V == 4 || V == 8)
                                                      : !(V == 1 || (V == 8 && !kIs16<E>));
 
-// The waves per SIMD asked of a _bias kernel: its unbiased twin's, in the instantiations where the compiler then fits the bias's
-// registers without scratch (1: no floor; elsewhere a floor only turns registers into scratch).  This table and kBiasEarly
-// above are read off one compiler's register allocation: `python tools/attention_bias_resources.py` compiles this file,
-// prints every _bias kernel beside its twin (the table of profiles/lane_group_resource_usage.md) and fails on scratch, so
-// run it after a change to a span or a new ROCm and move the entries with what it shows.
+// The waves per SIMD asked of a kernel with a bias: the unbiased instantiation's, where the compiler then fits the bias's
+// registers without scratch (1: no floor; elsewhere a floor only turns registers into scratch, and without a bias nothing is
+// asked).  This table and kBiasEarly above are read off one compiler's register allocation: `python
+// tools/attention_bias_resources.py` compiles this file, prints every biased instantiation beside its unbiased one (the
+// table of profiles/lane_group_resource_usage.md) and fails on scratch, so run it after a change to a span or a new ROCm and
+// move the entries with what it shows.
 enum BiasKernel { kBiasBwdQRows, kBiasBwdKvRows };
-template <BiasKernel KERNEL, int V, bool VEC, typename E>
+template <BiasKernel KERNEL, int V, bool VEC, typename E, typename... B>
 constexpr int bias_waves()
 {
+    if (sizeof...(B) == 0) return 1;
     if (KERNEL == kBiasBwdQRows) return V == 8 && !VEC && std::is_same<E, bf16>::value ? 5 : 1;
     return V == 1 && !VEC && kIs16<E> ? 4 : 1;       // kBiasBwdKvRows
 }
 #if defined(__HIP_DEVICE_COMPILE__)
-#define SPMV_BIAS_WAVES(KERNEL) __attribute__((amdgpu_waves_per_eu(bias_waves<KERNEL, V, VEC, E>())))
+#define SPMV_BIAS_WAVES(KERNEL) __attribute__((amdgpu_waves_per_eu(bias_waves<KERNEL, V, VEC, E, B...>())))
 #else
 #define SPMV_BIAS_WAVES(KERNEL)
 #endif
@@ -233,12 +242,15 @@ __device__ __forceinline__ void store_stats(float *stats, int64_t r, float m, fl
     *reinterpret_cast<float2 *>(stats + 2 * r) = make_float2(m, rinv);
 }
 
-// Each of the seven kernels that run a span is followed by its _bias twin: the same kernel with the bias of the block's query
-// head handed to the span; it takes the bias as one more argument (AttnBias), AttnArgsT being part of the unbiased kernels' code.
-template <int V, bool VEC, typename E>
-__global__ __launch_bounds__(kBlock) void k_attn_fwd_rows(GroupRows g, AttnArgsT<E> a0)
+// Each of the seven kernels that run a span is one template for both: <V, VEC, E> is the unbiased kernel, <V, VEC, E, AttnBias>
+// takes the bias as one more argument and hands that of the block's query head to the span (bias_of above).
+template <int V, bool VEC, typename E, typename... B>
+__global__ __launch_bounds__(kBlock) void k_attn_fwd_rows(GroupRows g, AttnArgsT<E> a0, B... bb)
 {
+    constexpr bool BIAS = sizeof...(B) == 1;
     const AttnArgsT<E> a = at_head(a0);
+    [[maybe_unused]] const float *bias = nullptr;
+    if constexpr (BIAS) bias = at_head(bias_of(bb...)).bias;
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     const int64_t r = group_row<V>(g);
     if (r < 0) return;
@@ -252,40 +264,19 @@ __global__ __launch_bounds__(kBlock) void k_attn_fwd_rows(GroupRows g, AttnArgsT
     const float4 q = c0 < a.k ? load_wide<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
     float m, l;
     float4 acc;
-    fwd_span<V, VEC, E>(lane, b, e, a, q, g.col_idx, c0, m, l, acc);
+    fwd_span<V, VEC, E, BIAS>(lane, b, e, a, q, g.col_idx, c0, m, l, acc, bias);
     const float rinv = 1.0f / l;
     if (c0 < a.kv) store_slice<VEC>(a.out0 + r * a.ld0 + c0, scaled4(acc, rinv), c0, a.kv);
     if (sub == 0) store_stats(a.stats, r, m, rinv);
 }
 
-template <int V, bool VEC, typename E>
-__global__ __launch_bounds__(kBlock) void k_attn_fwd_rows_bias(GroupRows g, AttnArgsT<E> a0, AttnBias bb)
+template <int V, bool VEC, typename E, typename... B>
+__global__ __launch_bounds__(kBlock) void k_attn_fwd_pieces(GroupPieces g, AttnArgsT<E> a0, B... bb)
 {
+    constexpr bool BIAS = sizeof...(B) == 1;
     const AttnArgsT<E> a = at_head(a0);
-    const float *bias = at_head(bb).bias;
-    const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
-    const int64_t r = group_row<V>(g);
-    if (r < 0) return;
-    const int64_t b = g.row_ptr[r], e = g.row_ptr[r + 1];
-    if (e - b > g.row_cap) return;
-    if (e == b) {
-        if (c0 < a.kv) store_slice<VEC>(a.out0 + r * a.ld0 + c0, zero4(), c0, a.kv);
-        if (sub == 0) store_stats(a.stats, r, -INFINITY, 0.0f);
-        return;
-    }
-    const float4 q = c0 < a.k ? load_wide<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
-    float m, l;
-    float4 acc;
-    fwd_span<V, VEC, E, true>(lane, b, e, a, q, g.col_idx, c0, m, l, acc, bias);
-    const float rinv = 1.0f / l;
-    if (c0 < a.kv) store_slice<VEC>(a.out0 + r * a.ld0 + c0, scaled4(acc, rinv), c0, a.kv);
-    if (sub == 0) store_stats(a.stats, r, m, rinv);
-}
-
-template <int V, bool VEC, typename E>
-__global__ __launch_bounds__(kBlock) void k_attn_fwd_pieces(GroupPieces g, AttnArgsT<E> a0)
-{
-    const AttnArgsT<E> a = at_head(a0);
+    [[maybe_unused]] const float *bias = nullptr;
+    if constexpr (BIAS) bias = at_head(bias_of(bb...)).bias;
     float *const scratch = at_head_scratch(g);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     int lo;
@@ -296,28 +287,7 @@ __global__ __launch_bounds__(kBlock) void k_attn_fwd_pieces(GroupPieces g, AttnA
     const float4 q = c0 < a.k ? load_wide<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
     float m, l;
     float4 acc;
-    fwd_span<V, VEC, E>(lane, b, e, a, q, g.col_idx, c0, m, l, acc);
-    float *s = scratch + p * kAtSlots;
-    if (sub == 0) *reinterpret_cast<float2 *>(s) = make_float2(m, l);
-    if (c0 < a.kv) *reinterpret_cast<float4 *>(s + kAtSums + c0) = acc;
-}
-
-template <int V, bool VEC, typename E>
-__global__ __launch_bounds__(kBlock) void k_attn_fwd_pieces_bias(GroupPieces g, AttnArgsT<E> a0, AttnBias bb)
-{
-    const AttnArgsT<E> a = at_head(a0);
-    const float *bias = at_head(bb).bias;
-    float *const scratch = at_head_scratch(g);
-    const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
-    int lo;
-    const int64_t p = group_piece<V>(g, lo);
-    if (p < 0) return;
-    const int64_t r = g.long_row[lo];
-    const int64_t b = g.piece_k0[p], e = b + g.piece_len[p];
-    const float4 q = c0 < a.k ? load_wide<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
-    float m, l;
-    float4 acc;
-    fwd_span<V, VEC, E, true>(lane, b, e, a, q, g.col_idx, c0, m, l, acc, bias);
+    fwd_span<V, VEC, E, BIAS>(lane, b, e, a, q, g.col_idx, c0, m, l, acc, bias);
     float *s = scratch + p * kAtSlots;
     if (sub == 0) *reinterpret_cast<float2 *>(s) = make_float2(m, l);
     if (c0 < a.kv) *reinterpret_cast<float4 *>(s + kAtSums + c0) = acc;
@@ -431,10 +401,13 @@ __device__ __forceinline__ float at_delta(const AttnArgsT<E> &a, int64_t r, int 
     return group_sum<V>(dot_partial(g, o, a.kv - c0));
 }
 
-template <int V, bool VEC, typename E>
-__global__ __launch_bounds__(kBlock) void k_attn_bwd_q_rows(GroupRows g, AttnArgsT<E> a0)
+template <int V, bool VEC, typename E, typename... B>
+__global__ __launch_bounds__(kBlock) SPMV_BIAS_WAVES(kBiasBwdQRows) void k_attn_bwd_q_rows(GroupRows g, AttnArgsT<E> a0, B... bb)
 {
+    constexpr bool BIAS = sizeof...(B) == 1;
     const AttnArgsT<E> a = at_head(a0);
+    [[maybe_unused]] AttnBias bi{};
+    if constexpr (BIAS) bi = at_head(bias_of(bb...));
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     const int64_t r = group_row<V>(g);
     if (r < 0) return;
@@ -449,39 +422,18 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_q_rows(GroupRows g, AttnArg
     const float delta = at_delta<V, VEC, E>(a, r, c0, go);
     const float4 q = c0 < a.k ? load_wide<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
     const float2 st = *reinterpret_cast<const float2 *>(a.stats_in + 2 * r);
-    const float4 dq = bwdq_span<V, VEC, E>(lane, b, e, a, q, go, st.x, st.y, delta, g.col_idx, c0);
+    const float4 dq = bwdq_span<V, VEC, E, BIAS>(lane, b, e, a, q, go, st.x, st.y, delta, g.col_idx, c0, bi.bias, bi.dbias);
     if (c0 < a.k) store_slice<VEC>(a.out0 + r * a.ld0 + c0, dq, c0, a.k);
     if (sub == 0) a.delta[r] = delta;
 }
 
-template <int V, bool VEC, typename E>
-__global__ __launch_bounds__(kBlock) SPMV_BIAS_WAVES(kBiasBwdQRows) void k_attn_bwd_q_rows_bias(GroupRows g, AttnArgsT<E> a0, AttnBias bb)
+template <int V, bool VEC, typename E, typename... B>
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_q_pieces(GroupPieces g, AttnArgsT<E> a0, B... bb)
 {
+    constexpr bool BIAS = sizeof...(B) == 1;
     const AttnArgsT<E> a = at_head(a0);
-    const AttnBias bi = at_head(bb);
-    const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
-    const int64_t r = group_row<V>(g);
-    if (r < 0) return;
-    const int64_t b = g.row_ptr[r], e = g.row_ptr[r + 1];
-    if (e - b > g.row_cap) return;
-    if (e == b) {
-        if (c0 < a.k) store_slice<VEC>(a.out0 + r * a.ld0 + c0, zero4(), c0, a.k);
-        if (sub == 0) a.delta[r] = 0.0f;
-        return;
-    }
-    float4 go;
-    const float delta = at_delta<V, VEC, E>(a, r, c0, go);
-    const float4 q = c0 < a.k ? load_wide<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
-    const float2 st = *reinterpret_cast<const float2 *>(a.stats_in + 2 * r);
-    const float4 dq = bwdq_span<V, VEC, E, true>(lane, b, e, a, q, go, st.x, st.y, delta, g.col_idx, c0, bi.bias, bi.dbias);
-    if (c0 < a.k) store_slice<VEC>(a.out0 + r * a.ld0 + c0, dq, c0, a.k);
-    if (sub == 0) a.delta[r] = delta;
-}
-
-template <int V, bool VEC, typename E>
-__global__ __launch_bounds__(kBlock) void k_attn_bwd_q_pieces(GroupPieces g, AttnArgsT<E> a0)
-{
-    const AttnArgsT<E> a = at_head(a0);
+    [[maybe_unused]] AttnBias bi{};
+    if constexpr (BIAS) bi = at_head(bias_of(bb...));
     float *const scratch = at_head_scratch(g);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     int lo;
@@ -493,28 +445,7 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_q_pieces(GroupPieces g, Att
     const float delta = at_delta<V, VEC, E>(a, r, c0, go);      // (every piece of the row computes the same bits)
     const float4 q = c0 < a.k ? load_wide<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
     const float2 st = *reinterpret_cast<const float2 *>(a.stats_in + 2 * r);
-    const float4 dq = bwdq_span<V, VEC, E>(lane, b, e, a, q, go, st.x, st.y, delta, g.col_idx, c0);
-    if (c0 < a.k) *reinterpret_cast<float4 *>(scratch + p * kAtSlots + kAtSums + c0) = dq;
-    if (sub == 0 && p == g.long_first[lo]) a.delta[r] = delta;
-}
-
-template <int V, bool VEC, typename E>
-__global__ __launch_bounds__(kBlock) void k_attn_bwd_q_pieces_bias(GroupPieces g, AttnArgsT<E> a0, AttnBias bb)
-{
-    const AttnArgsT<E> a = at_head(a0);
-    const AttnBias bi = at_head(bb);
-    float *const scratch = at_head_scratch(g);
-    const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
-    int lo;
-    const int64_t p = group_piece<V>(g, lo);
-    if (p < 0) return;
-    const int64_t r = g.long_row[lo];
-    const int64_t b = g.piece_k0[p], e = b + g.piece_len[p];
-    float4 go;
-    const float delta = at_delta<V, VEC, E>(a, r, c0, go);      // (every piece of the row computes the same bits)
-    const float4 q = c0 < a.k ? load_wide<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
-    const float2 st = *reinterpret_cast<const float2 *>(a.stats_in + 2 * r);
-    const float4 dq = bwdq_span<V, VEC, E, true>(lane, b, e, a, q, go, st.x, st.y, delta, g.col_idx, c0, bi.bias, bi.dbias);
+    const float4 dq = bwdq_span<V, VEC, E, BIAS>(lane, b, e, a, q, go, st.x, st.y, delta, g.col_idx, c0, bi.bias, bi.dbias);
     if (c0 < a.k) *reinterpret_cast<float4 *>(scratch + p * kAtSlots + kAtSums + c0) = dq;
     if (sub == 0 && p == g.long_first[lo]) a.delta[r] = delta;
 }
@@ -613,10 +544,13 @@ __device__ __forceinline__ void bwdkv_span(int lane, int64_t b, int64_t e, const
     }
 }
 
-template <int V, bool VEC, typename E>
-__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows(GroupRows g, AttnArgsT<E> a0)
+template <int V, bool VEC, typename E, typename... B>
+__global__ __launch_bounds__(kBlock) SPMV_BIAS_WAVES(kBiasBwdKvRows) void k_attn_bwd_kv_rows(GroupRows g, AttnArgsT<E> a0, B... bb)
 {
+    constexpr bool BIAS = sizeof...(B) == 1;
     const AttnArgsT<E> a = at_head(a0);
+    [[maybe_unused]] const float *bias = nullptr;
+    if constexpr (BIAS) bias = at_head(bias_of(bb...)).bias;
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     const int64_t r = group_row<V>(g);
     if (r < 0) return;
@@ -626,36 +560,19 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows(GroupRows g, AttnAr
     if (e > b) {
         const float4 kj = c0 < a.k ? load_wide<VEC>(a.K, a.ldk, r, c0, a.k) : zero4();
         const float4 vj = c0 < a.kv ? load_wide<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
-        bwdkv_span<V, VEC, E>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv);
+        bwdkv_span<V, VEC, E, BIAS>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv, bias);
     }
     if (c0 < a.k) store_slice<VEC>(a.out0 + r * a.ld0 + c0, dk, c0, a.k);
     if (c0 < a.kv) store_slice<VEC>(a.out1 + r * a.ld1 + c0, dv, c0, a.kv);
 }
 
-template <int V, bool VEC, typename E>
-__global__ __launch_bounds__(kBlock) SPMV_BIAS_WAVES(kBiasBwdKvRows) void k_attn_bwd_kv_rows_bias(GroupRows g, AttnArgsT<E> a0, AttnBias bb)
+template <int V, bool VEC, typename E, typename... B>
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_pieces(GroupPieces g, AttnArgsT<E> a0, B... bb)
 {
+    constexpr bool BIAS = sizeof...(B) == 1;
     const AttnArgsT<E> a = at_head(a0);
-    const float *bias = at_head(bb).bias;
-    const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
-    const int64_t r = group_row<V>(g);
-    if (r < 0) return;
-    const int64_t b = g.row_ptr[r], e = g.row_ptr[r + 1];
-    if (e - b > g.row_cap) return;
-    float4 dk = zero4(), dv = zero4();
-    if (e > b) {
-        const float4 kj = c0 < a.k ? load_wide<VEC>(a.K, a.ldk, r, c0, a.k) : zero4();
-        const float4 vj = c0 < a.kv ? load_wide<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
-        bwdkv_span<V, VEC, E, true>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv, bias);
-    }
-    if (c0 < a.k) store_slice<VEC>(a.out0 + r * a.ld0 + c0, dk, c0, a.k);
-    if (c0 < a.kv) store_slice<VEC>(a.out1 + r * a.ld1 + c0, dv, c0, a.kv);
-}
-
-template <int V, bool VEC, typename E>
-__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_pieces(GroupPieces g, AttnArgsT<E> a0)
-{
-    const AttnArgsT<E> a = at_head(a0);
+    [[maybe_unused]] const float *bias = nullptr;
+    if constexpr (BIAS) bias = at_head(bias_of(bb...)).bias;
     float *const scratch = at_head_scratch(g);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     int lo;
@@ -666,28 +583,7 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_pieces(GroupPieces g, At
     const float4 kj = c0 < a.k ? load_wide<VEC>(a.K, a.ldk, r, c0, a.k) : zero4();
     const float4 vj = c0 < a.kv ? load_wide<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
     float4 dk, dv;
-    bwdkv_span<V, VEC, E>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv);
-    float *s = scratch + p * kAtSlots;
-    if (c0 < a.k) *reinterpret_cast<float4 *>(s + kAtSums + c0) = dk;
-    if (c0 < a.kv) *reinterpret_cast<float4 *>(s + kAtSums2 + c0) = dv;
-}
-
-template <int V, bool VEC, typename E>
-__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_pieces_bias(GroupPieces g, AttnArgsT<E> a0, AttnBias bb)
-{
-    const AttnArgsT<E> a = at_head(a0);
-    const float *bias = at_head(bb).bias;
-    float *const scratch = at_head_scratch(g);
-    const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
-    int lo;
-    const int64_t p = group_piece<V>(g, lo);
-    if (p < 0) return;
-    const int64_t r = g.long_row[lo];
-    const int64_t b = g.piece_k0[p], e = b + g.piece_len[p];
-    const float4 kj = c0 < a.k ? load_wide<VEC>(a.K, a.ldk, r, c0, a.k) : zero4();
-    const float4 vj = c0 < a.kv ? load_wide<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
-    float4 dk, dv;
-    bwdkv_span<V, VEC, E, true>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv, bias);
+    bwdkv_span<V, VEC, E, BIAS>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv, bias);
     float *s = scratch + p * kAtSlots;
     if (c0 < a.k) *reinterpret_cast<float4 *>(s + kAtSums + c0) = dk;
     if (c0 < a.kv) *reinterpret_cast<float4 *>(s + kAtSums2 + c0) = dv;
@@ -750,13 +646,21 @@ __device__ __forceinline__ int64_t uniform64(int64_t x)
 // per-head numbers) and adds the heads' results in head order, starting from head 0's.  The per-head kernel leaves few
 // registers free (k_attn_bwd_kv_rows: up to 104 SGPRs; at V = 16 247 to 254 of the 256 VGPRs that two waves per SIMD allow),
 // so the head strides, and at V = 16 the running sums, the row's output addresses and its bounds, wait in LDS (park_lds).
-// The _bias twin: each query head of the group uses its own bias; the bias base advances per head like Q's, its stride waits
-// in one more slot (the last).
-template <int V, bool VEC, typename E>
-__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows_gqa(GroupRows g, AttnArgsT<E> a, int group)
+// With a bias (<..., AttnBias>) each query head of the group uses its own: the bias base advances per head like Q's, its
+// stride waits in one more slot (the last).
+template <int V, bool VEC, typename E, typename... B>
+__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows_gqa(GroupRows g, AttnArgsT<E> a, int group, B... bb)
 {
-    constexpr bool kPark = V == 16;
-    constexpr int N = kPark ? 6 : 2;
+    constexpr bool BIAS = sizeof...(B) == 1, kPark = V == 16;
+    constexpr int N = (kPark ? 6 : 2) + BIAS;
+    [[maybe_unused]] const AttnBias bi = bias_of(bb...);
+    [[maybe_unused]] const float *bias = nullptr;
+    if constexpr (BIAS) {
+        bias = bi.bias + (int64_t)blockIdx.y * group * bi.hbias;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm("" : "+s"(bias));
+#endif
+    }
     {
         const int64_t c = blockIdx.y, y0 = c * group;
         a.K += c * a.hk, a.V += c * a.hv, a.out0 += c * a.h0, a.out1 += c * a.h1;
@@ -784,6 +688,7 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows_gqa(GroupRows g, At
         const float4 vj = c0 < a.kv ? load_wide<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
         park_put<N>(0, Strides2{a.hq, a.hdo});
         park_put<N>(1, Strides2{a.hstats_in, a.hdelta_in});
+        if constexpr (BIAS) park_put<N>(N - 1, Strides2{bi.hbias, 0});
         if constexpr (kPark) {
             park_put<N>(4, out);
             park_put<N>(5, Strides2{b, e});
@@ -793,9 +698,9 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows_gqa(GroupRows g, At
             park_fence();
             if constexpr (kPark) {
                 const Strides2 be = park_get<N, Strides2>(5);
-                bwdkv_span<V, VEC, E>(lane, be.a, be.b, a, kj, vj, g.col_idx, c0, dk, dv);
+                bwdkv_span<V, VEC, E, BIAS>(lane, be.a, be.b, a, kj, vj, g.col_idx, c0, dk, dv, bias);
             } else {
-                bwdkv_span<V, VEC, E>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv);
+                bwdkv_span<V, VEC, E, BIAS>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv, bias);
             }
             if (left != group) {
                 if constexpr (kPark) sk = park_get<N, float4>(2), sv = park_get<N, float4>(3);
@@ -811,78 +716,7 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows_gqa(GroupRows g, At
             }
             const Strides2 s0 = park_get<N, Strides2>(0), s1 = park_get<N, Strides2>(1);
             a.Q += uniform64(s0.a), a.dO += uniform64(s0.b), a.stats_in += uniform64(s1.a), a.delta_in += uniform64(s1.b);
-        }
-        if constexpr (kPark) out = park_get<N, Pointers2<E>>(4);
-    }
-    if (c0 < a.k) store_slice<VEC>(out.k, dk, c0, a.k);
-    if (c0 < a.kv) store_slice<VEC>(out.v, dv, c0, a.kv);
-}
-
-template <int V, bool VEC, typename E>
-__global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_rows_gqa_bias(GroupRows g, AttnArgsT<E> a, int group, AttnBias bb)
-{
-    constexpr bool kPark = V == 16;
-    constexpr int N = (kPark ? 6 : 2) + 1;
-    const float *bias = bb.bias + (int64_t)blockIdx.y * group * bb.hbias;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm("" : "+s"(bias));
-#endif
-    {
-        const int64_t c = blockIdx.y, y0 = c * group;
-        a.K += c * a.hk, a.V += c * a.hv, a.out0 += c * a.h0, a.out1 += c * a.h1;
-        a.Q += y0 * a.hq, a.dO += y0 * a.hdo, a.stats_in += y0 * a.hstats_in, a.delta_in += y0 * a.hdelta_in;
-#if defined(__HIP_DEVICE_COMPILE__)
-        asm("" : "+s"(a.K));      // (as at_head: the bases are formed here; c and the K/V strides are dead from here on)
-        asm("" : "+s"(a.V));
-        asm("" : "+s"(a.out0));
-        asm("" : "+s"(a.out1));
-        asm("" : "+s"(a.Q));
-        asm("" : "+s"(a.dO));
-        asm("" : "+s"(a.stats_in));
-        asm("" : "+s"(a.delta_in));
-#endif
-    }
-    const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
-    const int64_t r = group_row<V>(g);
-    if (r < 0) return;
-    const int64_t b = g.row_ptr[r], e = g.row_ptr[r + 1];
-    if (e - b > g.row_cap) return;
-    Pointers2<E> out{a.out0 + r * a.ld0 + c0, a.out1 + r * a.ld1 + c0};
-    float4 dk = zero4(), dv = zero4();
-    if (e > b) {
-        const float4 kj = c0 < a.k ? load_wide<VEC>(a.K, a.ldk, r, c0, a.k) : zero4();
-        const float4 vj = c0 < a.kv ? load_wide<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
-        park_put<N>(0, Strides2{a.hq, a.hdo});
-        park_put<N>(1, Strides2{a.hstats_in, a.hdelta_in});
-        park_put<N>(N - 1, Strides2{bb.hbias, 0});
-        if constexpr (kPark) {
-            park_put<N>(4, out);
-            park_put<N>(5, Strides2{b, e});
-        }
-        float4 sk = zero4(), sv = zero4();
-        for (int left = group;;) {
-            park_fence();
-            if constexpr (kPark) {
-                const Strides2 be = park_get<N, Strides2>(5);
-                bwdkv_span<V, VEC, E, true>(lane, be.a, be.b, a, kj, vj, g.col_idx, c0, dk, dv, bias);
-            } else {
-                bwdkv_span<V, VEC, E, true>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv, bias);
-            }
-            if (left != group) {
-                if constexpr (kPark) sk = park_get<N, float4>(2), sv = park_get<N, float4>(3);
-                dk = add4(sk, dk);
-                dv = add4(sv, dv);
-            }
-            if (--left == 0) break;
-            if constexpr (kPark) {
-                park_put<N>(2, dk);
-                park_put<N>(3, dv);
-            } else {
-                sk = dk, sv = dv;
-            }
-            const Strides2 s0 = park_get<N, Strides2>(0), s1 = park_get<N, Strides2>(1);
-            a.Q += uniform64(s0.a), a.dO += uniform64(s0.b), a.stats_in += uniform64(s1.a), a.delta_in += uniform64(s1.b);
-            bias += uniform64(park_get<N, Strides2>(N - 1).a);
+            if constexpr (BIAS) bias += uniform64(park_get<N, Strides2>(N - 1).a);
         }
         if constexpr (kPark) out = park_get<N, Pointers2<E>>(4);
     }
@@ -914,7 +748,8 @@ __global__ __launch_bounds__(kBlock) void k_attn_add_pieces_gqa(GroupPieces g, i
 // one grid per kernel for all heads: x is what a call of one head launches, y the query head within its group of `group`, z
 // the group (the K/V head); group = 1 for the _heads calls.  gqa (backward_kv only): the _gqa call, which sums the heads of a
 // group (k_attn_bwd_kv_rows_gqa, k_attn_add_pieces_gqa; also at group = 1).
-// bb: the call's bias (a _bias entry point: the _bias twins of the seven span kernels run) or null
+// bb: the call's bias (a _bias entry point) or null.  The seven kernels that run a span are launched through with_bias: each
+// once, with *bb as its last argument (the <..., AttnBias> instantiation) or without one.
 template <int PASS, int V, bool VEC, typename E>
 int launch_attn_v(const spmv_csr &h, const AttnArgsT<E> &a, const AttnBias *bb, int heads, int group, bool gqa, const char *what,
                   hipStream_t s)
@@ -925,34 +760,29 @@ int launch_attn_v(const spmv_csr &h, const AttnArgsT<E> &a, const AttnBias *bb, 
     const GroupRows g = group_rows(h, V, nblocks);
     const unsigned kv_heads = (unsigned)(heads / group);
     const dim3 grid((unsigned)nblocks, (unsigned)group, kv_heads), block(kBlock);
-    if (bb) {
-        if constexpr (PASS == kPassForward) hipLaunchKernelGGL((k_attn_fwd_rows_bias<V, VEC, E>), grid, block, 0, s, g, a, *bb);
-        else if constexpr (PASS == kPassBackwardQ) hipLaunchKernelGGL((k_attn_bwd_q_rows_bias<V, VEC, E>), grid, block, 0, s, g, a, *bb);
-        else if (gqa) hipLaunchKernelGGL((k_attn_bwd_kv_rows_gqa_bias<V, VEC, E>), dim3((unsigned)nblocks, kv_heads), block, 0, s, g, a, group, *bb);
-        else hipLaunchKernelGGL((k_attn_bwd_kv_rows_bias<V, VEC, E>), grid, block, 0, s, g, a, *bb);
-    } else if constexpr (PASS == kPassForward) hipLaunchKernelGGL((k_attn_fwd_rows<V, VEC, E>), grid, block, 0, s, g, a);
-    else if constexpr (PASS == kPassBackwardQ) hipLaunchKernelGGL((k_attn_bwd_q_rows<V, VEC, E>), grid, block, 0, s, g, a);
-    else if (gqa) hipLaunchKernelGGL((k_attn_bwd_kv_rows_gqa<V, VEC, E>), dim3((unsigned)nblocks, kv_heads), block, 0, s, g, a, group);
-    else hipLaunchKernelGGL((k_attn_bwd_kv_rows<V, VEC, E>), grid, block, 0, s, g, a);
+    const auto with_bias = [&](auto launch) { bb ? launch(*bb) : launch(); };
+    with_bias([&](auto... bias) {
+        if constexpr (PASS == kPassForward) hipLaunchKernelGGL((k_attn_fwd_rows<V, VEC, E, decltype(bias)...>), grid, block, 0, s, g, a, bias...);
+        else if constexpr (PASS == kPassBackwardQ) hipLaunchKernelGGL((k_attn_bwd_q_rows<V, VEC, E, decltype(bias)...>), grid, block, 0, s, g, a, bias...);
+        else if (gqa) hipLaunchKernelGGL((k_attn_bwd_kv_rows_gqa<V, VEC, E, decltype(bias)...>), dim3((unsigned)nblocks, kv_heads), block, 0, s, g, a, group, bias...);
+        else hipLaunchKernelGGL((k_attn_bwd_kv_rows<V, VEC, E, decltype(bias)...>), grid, block, 0, s, g, a, bias...);
+    });
     SPMV_LAUNCHED("k_attn_*_rows");
     if (!p.n_long) return SPMV_OK;
     const GroupPieces q = group_pieces(h, h.plan_attn.d_scratch.get());
     const dim3 pgrid(group_grid(p.pieces, V).x, (unsigned)group, kv_heads), lgrid(group_grid(p.n_long, V).x, (unsigned)heads);
     if constexpr (PASS == kPassForward) {
-        if (bb) hipLaunchKernelGGL((k_attn_fwd_pieces_bias<V, VEC, E>), pgrid, block, 0, s, q, a, *bb);
-        else hipLaunchKernelGGL((k_attn_fwd_pieces<V, VEC, E>), pgrid, block, 0, s, q, a);
+        with_bias([&](auto... bias) { hipLaunchKernelGGL((k_attn_fwd_pieces<V, VEC, E, decltype(bias)...>), pgrid, block, 0, s, q, a, bias...); });
         SPMV_LAUNCHED("k_attn_fwd_pieces");
         hipLaunchKernelGGL((k_attn_fwd_combine<V, VEC, E>), dim3(lgrid.x, (unsigned)group, kv_heads), block, 0, s, q, a);
         SPMV_LAUNCHED("k_attn_fwd_combine");
     } else if constexpr (PASS == kPassBackwardQ) {
-        if (bb) hipLaunchKernelGGL((k_attn_bwd_q_pieces_bias<V, VEC, E>), pgrid, block, 0, s, q, a, *bb);
-        else hipLaunchKernelGGL((k_attn_bwd_q_pieces<V, VEC, E>), pgrid, block, 0, s, q, a);
+        with_bias([&](auto... bias) { hipLaunchKernelGGL((k_attn_bwd_q_pieces<V, VEC, E, decltype(bias)...>), pgrid, block, 0, s, q, a, bias...); });
         SPMV_LAUNCHED("k_attn_bwd_q_pieces");
         hipLaunchKernelGGL((k_attn_add_pieces<V, VEC, E>), lgrid, block, 0, s, q, kAtSums, a.out0, a.ld0, a.k, a.h0);
         SPMV_LAUNCHED("k_attn_add_pieces");
     } else {
-        if (bb) hipLaunchKernelGGL((k_attn_bwd_kv_pieces_bias<V, VEC, E>), pgrid, block, 0, s, q, a, *bb);
-        else hipLaunchKernelGGL((k_attn_bwd_kv_pieces<V, VEC, E>), pgrid, block, 0, s, q, a);
+        with_bias([&](auto... bias) { hipLaunchKernelGGL((k_attn_bwd_kv_pieces<V, VEC, E, decltype(bias)...>), pgrid, block, 0, s, q, a, bias...); });
         SPMV_LAUNCHED("k_attn_bwd_kv_pieces");
         if (gqa) {
             const dim3 cgrid(lgrid.x, kv_heads);

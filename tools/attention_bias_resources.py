@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""tools/attention_bias_resources.py [LOG] -- every k_attn_*_bias kernel of csrc/kernels_attention.hip beside its unbiased twin.
+"""tools/attention_bias_resources.py [LOG] -- every biased kernel of csrc/kernels_attention.hip beside its unbiased twin.
 
 Compiles the file's device code for gfx950 with the Makefile's flags and -Rpass-analysis=kernel-resource-usage (or reads the
-remarks of such a compile from LOG) and prints, per kernel<V, VEC>, as fp32/bf16/fp16 with the twin's figure in brackets:
+remarks of such a compile from LOG) and prints, per kernel<V, VEC>, as fp32/bf16/fp16 with the twin's figure in brackets
+(k_attn_X_bias<V, VEC> is the row of the instantiations k_attn_X<V, VEC, E, AttnBias>, its twin k_attn_X<V, VEC, E>):
 VGPRs, waves per SIMD, SGPRs, scratch bytes per lane, scalar registers kept in vector lanes, LDS bytes per block.  It is the
 last table of profiles/lane_group_resource_usage.md, and what kBiasEarly and bias_waves in the kernel file were read off.
 Exit status 1 if a _bias kernel has scratch; a kernel below its twin's waves or with scalar registers in vector lanes is
@@ -31,16 +32,17 @@ def remarks() -> str:
 def main() -> int:
     table = {}
     for block in re.split(r"remark: Function Name: ", remarks())[1:]:
-        m = re.match(r"\S*?\d+(k_attn_[a-z_]+)ILi(\d+)ELb([01])E(f|DF16_|NS_4bf16E)E", block)
+        m = re.match(r"\S*?\d+(k_attn_[a-z_]+)ILi(\d+)ELb([01])E(f|DF16_|NS_4bf16E)(?:J(NS_8AttnBiasE)?E)?E", block)
         if not m:
             continue
+        name = m.group(1) + ("_bias" if m.group(5) else "")
         get = lambda key: int(re.search(re.escape(key) + r": (\d+)", block).group(1))      # noqa: E731
-        table[(m.group(1), int(m.group(2)), m.group(3) == "1", ELEMENTS[m.group(4)])] = dict(
+        table[(name, int(m.group(2)), m.group(3) == "1", ELEMENTS[m.group(4)])] = dict(
             vgpr=get("VGPRs"), sgpr=get("TotalSGPRs"), scratch=get("ScratchSize [bytes/lane]"), waves=get("Occupancy [waves/SIMD]"),
             lanes=get("SGPRs Spill") + get("VGPRs Spill"), lds=get("LDS Size [bytes/block]"))
     names = sorted({n for n, _, _, _ in table if n.endswith("_bias")})
     if not names:
-        print("no k_attn_*_bias kernel found")
+        print("no k_attn_* kernel with a bias found")
         return 1
     print("| kernel<V, VEC> | VGPRs (twin's) | waves / SIMD (twin's) | SGPRs | scratch | SGPRs in vector lanes | LDS bytes |")
     print("|---|---|---|---|---|---|---|")

@@ -12,7 +12,7 @@
 // head order from the first head's value.  Then the same four heads on two K/V heads on 16-bit matrices (bf16 and fp16; (6, 10)
 // and (40, 64); both load paths): every array an exactly sized heap block of 2-byte elements, O, dQ, dK and dV bit for bit the
 // program's own fp32 _gqa runs on the widened data, rounded to nearest even by a conversion written here, stats and delta those
-// runs' bits.  Then the additive bias (the _bias kernels through launch_attention with an AttnBias): the same four heads on two
+// runs' bits.  Then the additive bias (the <..., AttnBias> kernels through launch_attention with an AttnBias): the same four heads on two
 // K/V heads at (6, 10) and (40, 64) on both load paths, fp32 and bf16 matrices, a bias per query head and nonzero, bias, bias_t
 // (the bias in the transposed pattern's order) and dBias exactly sized heap blocks of floats with head strides that are
 // multiples of nothing, rows and transposed rows in pieces: O, dQ, dBias, dK and dV against a serial fp64 attention with bias

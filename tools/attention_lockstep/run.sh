@@ -10,7 +10,7 @@
 # on two K/V heads (the head within its group in blockIdx.y, the K/V head in blockIdx.z; backward_kv's sum over the heads of a
 # group in k_attn_bwd_kv_rows_gqa and k_attn_add_pieces_gqa) bit for bit the single-head runs folded in head order; and the
 # same four heads on 16-bit matrices (bf16 and fp16, exactly sized blocks of 2-byte elements, the 8-byte and the 2-byte load path)
-# bit for bit the fp32 runs on the widened data, rounded to nearest even; and the _bias kernels (fp32 and bf16, (6, 10) and
+# bit for bit the fp32 runs on the widened data, rounded to nearest even; and the kernels with a bias (<..., AttnBias>; fp32 and bf16, (6, 10) and
 # (40, 64), both load paths, four query heads on two K/V heads, bias, bias_t and dBias exactly sized blocks, rows in pieces on
 # the pattern and on its transpose) against a serial fp64 attention with bias.  Needs no device: a check of the kernels' logic, bounds and alignment, not of the GPU.  The kernel
 # files, lane_group.hpp and attention_args.hpp are copied beside the stubs so that their #include "spmv_internal.hpp" finds the stub.
