@@ -677,6 +677,66 @@ SPMV_API int spmv_csr_attention_backward_kv_bias(spmv_csr_t *t, const spmv_attn_
                                                  const void *d_dO, int64_t lddo, const float *d_stats, const float *d_delta,
                                                  void *d_dK, int64_t lddk, void *d_dV, int64_t lddv, void *stream);
 
+/* ---- Fused attention at head widths up to 128: the most general calls once more, on lane groups of 32 -----------------------
+ * The three passes take exactly the argument lists of the _bias calls.  What differs from _bias, and nothing else:
+ *   - 1 <= k <= 128 and 1 <= kv <= 128;
+ *   - d_bias (d_bias_t) may be NULL: no bias, and the unbiased kernels run.  A non-null d_dbias with a null d_bias is refused;
+ *   - dtype is SPMV_ATTN_FP32, SPMV_ATTN_BF16 or SPMV_ATTN_FP16 as for _bias;
+ *   - the calls need spmv_csr_attention_plan_wide(h, heads) to cover hs->heads, else SPMV_ERR_NOT_PLANNED: one rule at every
+ *     width, which also holds on a handle without a long row.
+ * spmv_csr_attention_plan_wide does what spmv_csr_attention_plan_heads(h, heads) does and allocates a scratch of its own for
+ * the long rows' pieces at widths above 64: per head and piece 4 + 2 * 128 = 260 floats (m_p, l_p and, from a 16-byte
+ * boundary, two sets of 128 partial sums: backward_kv's dK_p and dV_p).  It is a separate allocation: the scratch of the other
+ * calls keeps its size and layout, and spmv_csr_attention_plan_bytes counts the wide scratch only once _plan_wide has been
+ * called.  It only grows, waits for the stream before it replaces a scratch, and a repeated call changes nothing.
+ * spmv_csr_attention_max_heads_wide applies the launch limit of spmv_csr_attention_max_heads (rows x lanes per row x heads <
+ * 2^32 on the row blocks and on the blocks of the pieces, heads <= 65535) with 32 lanes per row where max(k, kv) > 64; up to
+ * 64 it returns what spmv_csr_attention_max_heads returns.
+ * Refusals come in the _bias call's order with the width range replaced; the message names the _wide function; nothing is
+ * launched and every output stays untouched.  After the plan the calls allocate nothing and never wait: graph-capturable.
+ *
+ * The contract (part of the interface).
+ * max(k, kv) <= 64: the call launches the very kernels the _bias call launches (bias non-null), or the _gqa (dtype 0) or _16
+ *   call's (bias null): it is that call bit for bit.
+ * max(k, kv) > 64: a group of V = 32 lanes owns a row or a piece, and lane s owns columns [4s, 4s + 4) as everywhere else.
+ *   The documented order of "Fused attention" (and of csrc/lane_group.hpp) holds word for word with V = 32: lane partials by
+ *   fma from +0 over the lane's columns below the width, then the xor butterfly over the levels m = 16, 8, 4, 2, 1;
+ *   t = fl(fl(scale * s) + bias) when there is a bias; the online softmax rescaled once per step; stats = (M, 1/l); p, ds and
+ *   dBias with their three roundings; the chains in storage order from +0, the pieces in piece order, the GQA fold from head
+ *   0's value.
+ *   The step is T_wide = SPMV_ATTN_WIDE_STEP = 8 nonzeros (stated because the forward bits depend on it: one rescale per
+ *   step): 64 registers of gathered fp32 slices per lane, the register picture of the V = 8 kernels; a step of 32 would need
+ *   256.  A step is thus narrower than its group: lanes 0 .. 7 of the group each own one nonzero of the step (its column
+ *   index, its bias, its stats and delta, its expf, its dBias).
+ *   16-bit: the contract of the _16 calls carries over unchanged.  A 16-bit wide call is the fp32 wide call on the widened
+ *   operands, each output rounded once, to nearest even, at the store; a lane still holds 4 elements per slice.
+ *   SDDMM: above width 64 there is no spmv_csr_sddmm for a score to be equal to (its k ends at 64); the score is the dot
+ *   product in the order just stated.
+ * Zero padding (what ties the geometry of 32 lanes to the others).  Pad every operand with zero columns from (k, kv) <= 64 up
+ *   to (128, 128).  On caller-made stats (and, in backward_kv, delta) the wide call's scores, dp, delta, ds, dBias,
+ *   dQ[:, :k], dK[:, :k] and dV[:, :kv] are then bit for bit the narrow call's on the unpadded operands, and the padded
+ *   output columns are +0: the extra lanes hold +0, a partial is never -0, and the extra levels run first.  The forward pass
+ *   shares this only on data whose every expf argument is +-0, at most -128 or -Inf: T differs between the two geometries and
+ *   the rescale is per step, so on general data O and stats agree to rounding, not bit for bit. */
+#define SPMV_ATTN_WIDE_STEP 8
+SPMV_API int spmv_csr_attention_plan_wide(spmv_csr_t *h, int heads, void *stream);
+SPMV_API int spmv_csr_attention_max_heads_wide(const spmv_csr_t *h, int k, int kv);
+SPMV_API int spmv_csr_attention_forward_wide(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, int dtype, const float *d_bias,
+                                             int64_t bias_stride, float scale, int k, const void *d_Q, int64_t ldq,
+                                             const void *d_K, int64_t ldk, int kv, const void *d_V, int64_t ldv, void *d_O,
+                                             int64_t ldo, float *d_stats, void *stream);
+SPMV_API int spmv_csr_attention_backward_q_wide(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, int dtype,
+                                                const float *d_bias, int64_t bias_stride, float *d_dbias, int64_t dbias_stride,
+                                                float scale, int k, const void *d_Q, int64_t ldq, const void *d_K, int64_t ldk,
+                                                int kv, const void *d_V, int64_t ldv, const void *d_O, int64_t ldo,
+                                                const void *d_dO, int64_t lddo, const float *d_stats, float *d_delta,
+                                                void *d_dQ, int64_t lddq, void *stream);
+SPMV_API int spmv_csr_attention_backward_kv_wide(spmv_csr_t *t, const spmv_attn_heads_t *hs, int group, int dtype,
+                                                 const float *d_bias_t, int64_t bias_stride, float scale, int k, const void *d_Q,
+                                                 int64_t ldq, const void *d_K, int64_t ldk, int kv, const void *d_V, int64_t ldv,
+                                                 const void *d_dO, int64_t lddo, const float *d_stats, const float *d_delta,
+                                                 void *d_dK, int64_t lddk, void *d_dV, int64_t lddv, void *stream);
+
 /* ---- dense baselines (reference slots cublas / naive / tiling) ---------
  * y[i] = sum_j x[j] * A[j*N+i] on the dense device matrix.
  * replaces: cublas_gemv_gpu (cublas.cu:4-44), naive_kernel (naive.cu:4-11),

@@ -72,6 +72,8 @@ SIGNATURES = {
     "spmv_csr_attention_plan_bytes": (C.c_int64, [_H]),
     "spmv_csr_attention_plan_heads": (C.c_int, [_H, C.c_int, _vp]),
     "spmv_csr_attention_max_heads": (C.c_int, [_H, C.c_int, C.c_int]),
+    "spmv_csr_attention_plan_wide": (C.c_int, [_H, C.c_int, _vp]),
+    "spmv_csr_attention_max_heads_wide": (C.c_int, [_H, C.c_int, C.c_int]),
     "spmv_csr_plan_get": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int32)]),
     "spmv_csr_plan_set": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int32), _vp]),
     "spmv_csr_plan_like": (C.c_int, [_H, _H, C.c_int, _vp]),
@@ -133,6 +135,8 @@ for _pass, _ops in _ATTN_PASSES.items():
     # the biased call of the pass: the _16 arguments with (bias, bias_stride) -- backward_q: and (dBias, dbias_stride) -- after dtype
     SIGNATURES[f"spmv_csr_attention_{_pass}_bias"] = (C.c_int, [_H, _HS, C.c_int, C.c_int] + [_f32p, C.c_int64] * (2 if _pass == "backward_q" else 1)
                                                       + [C.c_float, C.c_int] + _tail + [_vp])
+    # the wide call of the pass (widths up to 128): exactly the _bias arguments; a null bias means none
+    SIGNATURES[f"spmv_csr_attention_{_pass}_wide"] = SIGNATURES[f"spmv_csr_attention_{_pass}_bias"]
 ATTN_FP32, ATTN_BF16, ATTN_FP16 = 0, 1, 2      # enums of include/spmv_hip.h: the dtype of a _16 call (1, 2) or a _bias call
 # test only: the bounds-checked build of the library (SPMV_CHECK_BOUNDS) and its sites (csrc/spmv_internal.hpp BoundsSite)
 CHECKED_LIB_PATH = PKG_DIR / "lib" / "libspmv_hip_checked.so"
@@ -516,9 +520,40 @@ class CsrMatrix:
         order (:meth:`transpose_gather` makes it)."""
         self._attention_call("backward_kv", "gqa", (Q, K, V, dO, stats, delta, dK, dV), scale, stream, bias=(bias_t,))
 
+    # -- fused attention at widths up to 128 (spmv_csr_attention_*_wide; the _bias arguments, the bias optional) ----------------
+    def attention_plan_wide(self, heads: int, stream=None) -> None:
+        """attention_plan_heads(heads) and the scratch of the long rows' pieces at widths above 64 (it only grows).  The _wide
+        calls need it at every width."""
+        check(lib().spmv_csr_attention_plan_wide(self._h, heads, _stream_handle(stream)))
+
+    def attention_max_heads_wide(self, k: int, kv: int) -> int:
+        """The most heads one _wide call on this handle takes at these widths (up to 128)."""
+        n = lib().spmv_csr_attention_max_heads_wide(self._h, k, kv)
+        if n < 0:
+            check(n)
+        return n
+
+    def attention_forward_wide(self, Q, K, V, O, stats, bias=None, scale: float = 1.0, stream=None) -> None:
+        """attention_forward_bias (bias given) or attention_forward_gqa (bias=None) at widths k, kv <= 128, float32, bfloat16 or
+        float16 matrices: Q, O: (H, rows, .), K, V: (H_kv, cols, .).  Up to width 64 it is that call bit for bit."""
+        self._attention_call("forward", "gqa", (Q, K, V, O, stats), scale, stream, bias=(bias,), wide=True)
+
+    def attention_backward_q_wide(self, Q, K, V, O, dO, stats, delta, dQ, bias=None, dBias=None, scale: float = 1.0, stream=None) -> None:
+        """attention_backward_q_bias or, with bias=None (then dBias must be None), attention_backward_q_gqa at widths up to 128."""
+        self._attention_call("backward_q", "gqa", (Q, K, V, O, dO, stats, delta, dQ), scale, stream, bias=(bias, dBias), wide=True)
+
+    def attention_backward_kv_wide(self, Q, K, V, dO, stats, delta, dK, dV, bias_t=None, scale: float = 1.0, stream=None) -> None:
+        """On the handle of the TRANSPOSED pattern: attention_backward_kv_bias or, with bias_t=None, attention_backward_kv_gqa at
+        widths up to 128."""
+        self._attention_call("backward_kv", "gqa", (Q, K, V, dO, stats, delta, dK, dV), scale, stream, bias=(bias_t,), wide=True)
+
     def _attention_bias(self, what: str, heads: int, bias, dBias=None) -> list:
         """The C arguments of a _bias call's bias: (pointer, stride) of the bias and, if the pass has one, of dBias."""
         import torch
+        if bias is None and what.endswith("_wide"):      # (no bias: the unbiased kernels; the library refuses a dBias then)
+            if dBias is not None:
+                raise ValueError(f"{what}: dBias without a bias")
+            return [None, 0, None, 0]
         if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or bias.stride(-1) != 1 \
                 or tuple(bias.shape) not in ((self.nnz,), (heads, self.nnz)):
             raise ValueError(f"{what}: bias must be a float32 tensor of ({self.nnz},) or ({heads}, {self.nnz}) with stride(-1) == 1")
@@ -528,13 +563,14 @@ class CsrMatrix:
             raise ValueError(f"{what}: dBias must be None or a float32 tensor of ({heads}, {self.nnz}) with stride(-1) == 1")
         return args + [_ptr(dBias) if dBias is not None else None, dBias.stride(0) if dBias is not None and heads > 1 else 0]
 
-    def _attention_call(self, spec: str, mode: str, tensors, scale: float, stream, bias=None) -> None:
+    def _attention_call(self, spec: str, mode: str, tensors, scale: float, stream, bias=None, wide: bool = False) -> None:
         """Every attention call: pass `spec` of _ATTN_PASSES in `mode` of _ATTN_MODES on `tensors` in the spec's order.
         Matrices that are all torch.bfloat16 or all torch.float16 (stats and delta stay float32) go to the pass's _16 call: the
         same layout rules, every ld and stride counted in elements; a call of one head is one head with every stride 0, a
-        _heads call a group of 1.  bias: (bias,) or (bias, dBias) of a _bias call (mode "gqa"), which takes all three dtypes."""
+        _heads call a group of 1.  bias: (bias,) or (bias, dBias) of a _bias call (mode "gqa"), which takes all three dtypes.
+        wide: the pass's _wide call, the _bias call's arguments with a bias that may be None."""
         import torch
-        what, ops = f"attention_{spec}{'_bias' if bias else _ATTN_MODES[mode]}", _ATTN_PASSES[spec]
+        what, ops = f"attention_{spec}{'_wide' if wide else '_bias' if bias else _ATTN_MODES[mode]}", _ATTN_PASSES[spec]
         t = dict(zip((o[0] for o in ops), tensors))
         d16 = {torch.bfloat16: ATTN_BF16, torch.float16: ATTN_FP16}.get(getattr(t["Q"], "dtype", None))
         dt = t["Q"].dtype if d16 else None

@@ -689,13 +689,32 @@ int spmv_csr_attention_plan_heads(spmv_csr_t *h, int heads, void *stream)
     return plan_attention_heads(*h, heads, (hipStream_t)stream);
 }
 
-static int attention_widths(int k, int kv, const char *what)
+// widest: 64, or 128 in the _wide calls
+static int attention_widths(int k, int kv, const char *what, int widest = 64)
 {
-    if (k < 1 || k > 64 || kv < 1 || kv > 64) {
-        set_error("%s: k = %d, kv = %d (need 1 <= k <= 64 and 1 <= kv <= 64)", what, k, kv);
+    if (k < 1 || k > widest || kv < 1 || kv > widest) {
+        set_error("%s: k = %d, kv = %d (need 1 <= k <= %d and 1 <= kv <= %d)", what, k, kv, widest, widest);
         return SPMV_ERR_INVALID;
     }
     return SPMV_OK;
+}
+
+int spmv_csr_attention_plan_wide(spmv_csr_t *h, int heads, void *stream)
+{
+    const char *what = "spmv_csr_attention_plan_wide";
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (heads < 1 || heads > kMaxHeads) { set_error("%s: heads = %d (need 1 <= heads <= %d)", what, heads, kMaxHeads); return SPMV_ERR_INVALID; }
+    if (int rc = require_current(h->device, what)) return rc;
+    return plan_attention_wide(*h, heads, (hipStream_t)stream);
+}
+
+int spmv_csr_attention_max_heads_wide(const spmv_csr_t *h, int k, int kv)
+{
+    const char *what = "spmv_csr_attention_max_heads_wide";
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (int rc = attention_widths(k, kv, what, 128)) return rc;
+    if (!h->plan_spmm.ready) { set_error("%s used before spmv_csr_attention_plan", what); return SPMV_ERR_NOT_PLANNED; }
+    return attention_max_heads(*h, k > kv ? k : kv);
 }
 
 int spmv_csr_attention_max_heads(const spmv_csr_t *h, int k, int kv)
@@ -749,9 +768,10 @@ static int attention_header(const spmv_csr_t *h, const spmv_attn_heads_t *hs, in
 
 // and after it, in this order: every head stride (they read k and kv as given); k and kv; the scale; every matrix (ld,
 // presence, alignment to four elements of `elem` bytes: 16 bytes of floats, 8 of 16-bit elements; 64-bit byte offsets); the
-// vectors (presence, then stats 8-byte and delta 4-byte aligned); the device; the plan and the heads it covers
+// vectors (presence, then stats 8-byte and delta 4-byte aligned); the device; the plan and the heads it covers.
+// wide: a _wide call, whose widths end at 128 and whose plan is spmv_csr_attention_plan_wide's, at every width.
 static int attention_operands(const spmv_csr_t *h, int heads, int group, float scale, int k, int kv, const AttnOperand *ops, size_t n_ops,
-                              int elem, const char *what)
+                              int elem, const char *what, bool wide = false)
 {
     for (size_t i = 0; i < n_ops; ++i) {
         const AttnOperand &o = ops[i];
@@ -769,7 +789,7 @@ static int attention_operands(const spmv_csr_t *h, int heads, int group, float s
             return SPMV_ERR_INVALID;
         }
     }
-    if (int rc = attention_widths(k, kv, what)) return rc;
+    if (int rc = attention_widths(k, kv, what, wide ? 128 : 64)) return rc;
     if (!(scale - scale == 0.0f)) { set_error("%s: scale must be finite", what); return SPMV_ERR_INVALID; }
     for (size_t i = 0; i < n_ops; ++i) {
         const AttnOperand &o = ops[i];
@@ -790,6 +810,17 @@ static int attention_operands(const spmv_csr_t *h, int heads, int group, float s
             return SPMV_ERR_INVALID;
         }
     if (int rc = require_current(h->device, what)) return rc;
+    if (wide) {
+        if (!h->plan_attn.ready || !h->plan_spmm.ready || !h->plan_attn.wide_heads) {
+            set_error("%s used before spmv_csr_attention_plan_wide", what);
+            return SPMV_ERR_NOT_PLANNED;
+        }
+        if (heads > h->plan_attn.wide_heads) {
+            set_error("%s: %d heads, the wide plan covers %d (spmv_csr_attention_plan_wide)", what, heads, h->plan_attn.wide_heads);
+            return SPMV_ERR_NOT_PLANNED;
+        }
+        return SPMV_OK;      // (plan_wide covers at least as many heads in the narrow plan)
+    }
     if (!h->plan_attn.ready || !h->plan_spmm.ready) { set_error("%s used before spmv_csr_attention_plan", what); return SPMV_ERR_NOT_PLANNED; }
     if (heads > h->plan_attn.heads) {
         set_error("%s: %d heads, the plan covers %d (spmv_csr_attention_plan_heads)", what, heads, h->plan_attn.heads);
@@ -801,18 +832,18 @@ static int attention_operands(const spmv_csr_t *h, int heads, int group, float s
 extern "C++" {      // (templates: this file is otherwise C linkage)
 // The three passes.  Each is every entry point of its pass: hs->heads query heads, `group` of them per K/V head;
 // sum_group: backward_kv adds the heads of a group in the kernel (the _gqa call).  E: float for the nine fp32 entry points,
-// bf16 or fp16 for the _16 one.
+// bf16 or fp16 for the _16 one.  wide: a _wide entry point (attention_operands).
 template <typename E>
 static int attention_forward(const char *what, spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, bool sum_group, float scale,
                              int k, const E *d_Q, int64_t ldq, const E *d_K, int64_t ldk, int kv, const E *d_V,
-                             int64_t ldv, E *d_O, int64_t ldo, float *d_stats, void *stream, const AttnBias *bb = nullptr)
+                             int64_t ldv, E *d_O, int64_t ldo, float *d_stats, void *stream, const AttnBias *bb = nullptr, bool wide = false)
 {
     if (int rc = attention_header(h, hs, group, what)) return rc;
     const int64_t rows = h->rows, cols = h->cols;
     const AttnOperand ops[] = {{"Q", d_Q, ldq, rows, k, hs->q, 4, kIn, kQHeads}, {"K", d_K, ldk, cols, k, hs->k, 4, kIn, kKVHeads},
                                {"V", d_V, ldv, cols, kv, hs->v, 4, kIn, kKVHeads}, {"O", d_O, ldo, rows, kv, hs->o, 4, kOut, kQHeads},
                                {"stats", d_stats, 0, rows, 2, hs->stats, 2, kOut, kQHeads}};
-    if (int rc = attention_operands(h, hs->heads, group, scale, k, kv, ops, sizeof ops / sizeof *ops, (int)sizeof(E), what)) return rc;
+    if (int rc = attention_operands(h, hs->heads, group, scale, k, kv, ops, sizeof ops / sizeof *ops, (int)sizeof(E), what, wide)) return rc;
     AttnArgsT<E> a{};
     a.scale = scale, a.k = k, a.kv = kv;
     a.Q = d_Q, a.ldq = ldq, a.hq = hs->q, a.K = d_K, a.ldk = ldk, a.hk = hs->k, a.V = d_V, a.ldv = ldv, a.hv = hs->v;
@@ -824,7 +855,7 @@ template <typename E>
 static int attention_backward_q(const char *what, spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, bool sum_group, float scale,
                                 int k, const E *d_Q, int64_t ldq, const E *d_K, int64_t ldk, int kv, const E *d_V,
                                 int64_t ldv, const E *d_O, int64_t ldo, const E *d_dO, int64_t lddo, const float *d_stats,
-                                float *d_delta, E *d_dQ, int64_t lddq, void *stream, const AttnBias *bb = nullptr)
+                                float *d_delta, E *d_dQ, int64_t lddq, void *stream, const AttnBias *bb = nullptr, bool wide = false)
 {
     if (int rc = attention_header(h, hs, group, what)) return rc;
     const int64_t rows = h->rows, cols = h->cols;
@@ -832,7 +863,7 @@ static int attention_backward_q(const char *what, spmv_csr_t *h, const spmv_attn
                                {"V", d_V, ldv, cols, kv, hs->v, 4, kIn, kKVHeads}, {"O", d_O, ldo, rows, kv, hs->o, 4, kIn, kQHeads},
                                {"dO", d_dO, lddo, rows, kv, hs->d_o, 4, kIn, kQHeads}, {"stats", d_stats, 0, rows, 2, hs->stats, 2, kIn, kQHeads},
                                {"delta", d_delta, 0, rows, 1, hs->delta, 1, kOut, kQHeads}, {"dQ", d_dQ, lddq, rows, k, hs->dq, 4, kOut, kQHeads}};
-    if (int rc = attention_operands(h, hs->heads, group, scale, k, kv, ops, sizeof ops / sizeof *ops, (int)sizeof(E), what)) return rc;
+    if (int rc = attention_operands(h, hs->heads, group, scale, k, kv, ops, sizeof ops / sizeof *ops, (int)sizeof(E), what, wide)) return rc;
     AttnArgsT<E> a{};
     a.scale = scale, a.k = k, a.kv = kv;
     a.Q = d_Q, a.ldq = ldq, a.hq = hs->q, a.K = d_K, a.ldk = ldk, a.hk = hs->k, a.V = d_V, a.ldv = ldv, a.hv = hs->v;
@@ -847,7 +878,7 @@ template <typename E>
 static int attention_backward_kv(const char *what, spmv_csr_t *t, const spmv_attn_heads_t *hs, int group, bool sum_group, float scale,
                                  int k, const E *d_Q, int64_t ldq, const E *d_K, int64_t ldk, int kv, const E *d_V,
                                  int64_t ldv, const E *d_dO, int64_t lddo, const float *d_stats, const float *d_delta,
-                                 E *d_dK, int64_t lddk, E *d_dV, int64_t lddv, void *stream, const AttnBias *bb = nullptr)
+                                 E *d_dK, int64_t lddk, E *d_dV, int64_t lddv, void *stream, const AttnBias *bb = nullptr, bool wide = false)
 {
     if (int rc = attention_header(t, hs, group, what)) return rc;
     const int64_t keys = t->rows, queries = t->cols;
@@ -856,7 +887,7 @@ static int attention_backward_kv(const char *what, spmv_csr_t *t, const spmv_att
                                {"stats", d_stats, 0, queries, 2, hs->stats, 2, kIn, kQHeads},
                                {"delta", d_delta, 0, queries, 1, hs->delta, 1, kIn, kQHeads}, {"dK", d_dK, lddk, keys, k, hs->dk, 4, kOut, kKVHeads},
                                {"dV", d_dV, lddv, keys, kv, hs->dv, 4, kOut, kKVHeads}};
-    if (int rc = attention_operands(t, hs->heads, group, scale, k, kv, ops, sizeof ops / sizeof *ops, (int)sizeof(E), what)) return rc;
+    if (int rc = attention_operands(t, hs->heads, group, scale, k, kv, ops, sizeof ops / sizeof *ops, (int)sizeof(E), what, wide)) return rc;
     AttnArgsT<E> a{};
     a.scale = scale, a.k = k, a.kv = kv;
     a.Q = d_Q, a.ldq = ldq, a.hq = hs->q, a.K = d_K, a.ldk = ldk, a.hk = hs->k, a.V = d_V, a.ldv = ldv, a.hv = hs->v;
@@ -1004,15 +1035,18 @@ int spmv_csr_attention_backward_kv_16(spmv_csr_t *t, const spmv_attn_heads_t *hs
 // ---- the same three passes with an additive fp32 bias per nonzero (fp32, bf16 or fp16 matrices): the most general form only ------
 // What the _bias calls check of their bias arguments, after the header and the dtype and before everything the unbiased call
 // of that dtype checks.  d_dbias: backward_q's output (may be null: not written); has_dbias: the call has one at all.
+// optional: a _wide call, where a null bias means no bias (and then a dBias is refused).
 static int attention_bias(const spmv_csr_t *h, int heads, int dtype, const float *d_bias, int64_t bias_stride, bool has_dbias,
-                          const float *d_dbias, int64_t dbias_stride, const char *what)
+                          const float *d_dbias, int64_t dbias_stride, const char *what, bool optional = false)
 {
     if (dtype != SPMV_ATTN_FP32 && dtype != SPMV_ATTN_BF16 && dtype != SPMV_ATTN_FP16) {
         set_error("%s: dtype = %d (need SPMV_ATTN_FP32 = %d, SPMV_ATTN_BF16 = %d or SPMV_ATTN_FP16 = %d)", what, dtype, (int)SPMV_ATTN_FP32,
                   (int)SPMV_ATTN_BF16, (int)SPMV_ATTN_FP16);
         return SPMV_ERR_INVALID;
     }
-    if (!d_bias && h->nnz > 0) { set_error("%s: null bias", what); return SPMV_ERR_INVALID; }
+    if (optional) {
+        if (!d_bias && d_dbias) { set_error("%s: dBias without a bias", what); return SPMV_ERR_INVALID; }
+    } else if (!d_bias && h->nnz > 0) { set_error("%s: null bias", what); return SPMV_ERR_INVALID; }
     if (reinterpret_cast<uintptr_t>(d_bias) % 4 != 0 || reinterpret_cast<uintptr_t>(d_dbias) % 4 != 0) {
         set_error("%s: bias and dBias must be 4-byte aligned", what);
         return SPMV_ERR_INVALID;
@@ -1081,6 +1115,63 @@ int spmv_csr_attention_backward_kv_bias(spmv_csr_t *t, const spmv_attn_heads_t *
         using E = decltype(e);
         return attention_backward_kv<E>(what, t, hs, group, true, scale, k, (const E *)d_Q, ldq, (const E *)d_K, ldk, kv, (const E *)d_V,
                                         ldv, (const E *)d_dO, lddo, d_stats, d_delta, (E *)d_dK, lddk, (E *)d_dV, lddv, stream, &bb);
+    };
+    return dtype == SPMV_ATTN_FP32 ? run(float{}) : dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+}
+
+// ---- the same three passes at widths up to 128: the _bias calls' arguments, an optional bias, the plan of _plan_wide -----------
+// Up to width 64 they launch what the _bias call (or, without a bias, the _gqa or _16 call) launches; above, the kernels at
+// V = 32 (kernels_attention.hip).  A null bias means none: the unbiased kernels run.
+int spmv_csr_attention_forward_wide(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, int dtype, const float *d_bias,
+                                    int64_t bias_stride, float scale, int k, const void *d_Q, int64_t ldq, const void *d_K, int64_t ldk,
+                                    int kv, const void *d_V, int64_t ldv, void *d_O, int64_t ldo, float *d_stats, void *stream)
+{
+    const char *what = "spmv_csr_attention_forward_wide";
+    if (int rc = attention_header(h, hs, group, what)) return rc;
+    if (int rc = attention_bias(h, hs->heads, dtype, d_bias, bias_stride, false, nullptr, 0, what, true)) return rc;
+    const AttnBias bb{d_bias, bias_stride, nullptr, 0};
+    auto run = [&](auto e) {
+        using E = decltype(e);
+        return attention_forward<E>(what, h, hs, group, false, scale, k, (const E *)d_Q, ldq, (const E *)d_K, ldk, kv, (const E *)d_V, ldv,
+                                    (E *)d_O, ldo, d_stats, stream, d_bias ? &bb : nullptr, true);
+    };
+    return dtype == SPMV_ATTN_FP32 ? run(float{}) : dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+}
+
+int spmv_csr_attention_backward_q_wide(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, int dtype, const float *d_bias,
+                                       int64_t bias_stride, float *d_dbias, int64_t dbias_stride, float scale, int k, const void *d_Q,
+                                       int64_t ldq, const void *d_K, int64_t ldk, int kv, const void *d_V, int64_t ldv, const void *d_O,
+                                       int64_t ldo, const void *d_dO, int64_t lddo, const float *d_stats, float *d_delta, void *d_dQ,
+                                       int64_t lddq, void *stream)
+{
+    const char *what = "spmv_csr_attention_backward_q_wide";
+    if (int rc = attention_header(h, hs, group, what)) return rc;
+    if (int rc = attention_bias(h, hs->heads, dtype, d_bias, bias_stride, true, d_dbias, dbias_stride, what, true)) return rc;
+    const AttnBias bb{d_bias, bias_stride, d_dbias, dbias_stride};
+    auto run = [&](auto e) {
+        using E = decltype(e);
+        return attention_backward_q<E>(what, h, hs, group, false, scale, k, (const E *)d_Q, ldq, (const E *)d_K, ldk, kv, (const E *)d_V,
+                                       ldv, (const E *)d_O, ldo, (const E *)d_dO, lddo, d_stats, d_delta, (E *)d_dQ, lddq, stream,
+                                       d_bias ? &bb : nullptr, true);
+    };
+    return dtype == SPMV_ATTN_FP32 ? run(float{}) : dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+}
+
+int spmv_csr_attention_backward_kv_wide(spmv_csr_t *t, const spmv_attn_heads_t *hs, int group, int dtype, const float *d_bias_t,
+                                        int64_t bias_stride, float scale, int k, const void *d_Q, int64_t ldq, const void *d_K,
+                                        int64_t ldk, int kv, const void *d_V, int64_t ldv, const void *d_dO, int64_t lddo,
+                                        const float *d_stats, const float *d_delta, void *d_dK, int64_t lddk, void *d_dV, int64_t lddv,
+                                        void *stream)
+{
+    const char *what = "spmv_csr_attention_backward_kv_wide";
+    if (int rc = attention_header(t, hs, group, what)) return rc;
+    if (int rc = attention_bias(t, hs->heads, dtype, d_bias_t, bias_stride, false, nullptr, 0, what, true)) return rc;
+    const AttnBias bb{d_bias_t, bias_stride, nullptr, 0};
+    auto run = [&](auto e) {
+        using E = decltype(e);
+        return attention_backward_kv<E>(what, t, hs, group, true, scale, k, (const E *)d_Q, ldq, (const E *)d_K, ldk, kv, (const E *)d_V,
+                                        ldv, (const E *)d_dO, lddo, d_stats, d_delta, (E *)d_dK, lddk, (E *)d_dV, lddv, stream,
+                                        d_bias_t ? &bb : nullptr, true);
     };
     return dtype == SPMV_ATTN_FP32 ? run(float{}) : dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
 }

@@ -2,7 +2,9 @@
 // that never store a score, a probability or their gradients (spmv_csr_attention_forward, spmv_csr_attention_backward_q,
 // spmv_csr_attention_backward_kv, include/spmv_hip.h "Fused attention").  Of nnz size only col_idx is read, once per pass.
 //
-// The lane groups, their steps and the plan are lane_group.hpp's, with V = pow2 >= ceil(max(k, kv) / 4).  Lane s keeps
+// The lane groups, their steps and the plan are lane_group.hpp's, with V = pow2 >= ceil(max(k, kv) / 4): 1 to 16 up to width 64,
+// and through the _wide entry points alone V = 32 for widths 65 to 128, in steps of kWideStep = 8 nonzeros that the lanes
+// sub < 8 of the group own (a scratch slot of 260 floats per piece there: at_slots, AttnPlan::d_scratch_wide).  Lane s keeps
 // columns [4s, 4s+4) of the row's own operands in registers (Q_i; dO_i; K_j and V_j on the transposed handle).  Per step a
 // lane issues all its gathers (2 T slices, and on the transposed handle the 12 bytes stats[2i], stats[2i+1], delta[i] per
 // nonzero, loaded by the lane that owns the nonzero) and only then computes.  The scores of a step go through
@@ -67,6 +69,10 @@
 
 #pragma clang fp contract(off)
 
+#ifdef SPMV_ATTN_WIDE_STEP      // (include/spmv_hip.h states the step of the wide calls: its bits are part of the interface)
+static_assert(spmv::kWideStep == SPMV_ATTN_WIDE_STEP, "lane_group.hpp and include/spmv_hip.h disagree on T_wide");
+#endif
+
 namespace spmv {
 
 namespace {
@@ -74,6 +80,14 @@ namespace {
 constexpr int kAtSlots = 132;     // floats of scratch per piece
 constexpr int kAtSums = 4;        // where a piece's partial sums start (16-byte aligned)
 constexpr int kAtSums2 = 68;      // the second set of backward_kv (dV)
+// V = 32 (the _wide entry points at 64 < max(k, kv) <= 128) has a scratch of its own (AttnPlan::d_scratch_wide): per head and
+// piece [0] m_p, [1] l_p, [4, 132) up to 128 partial sums, [132, 260) backward_kv's second 128
+constexpr int kAtSlotsWide = 4 + 2 * 128;
+constexpr int kAtSums2Wide = 4 + 128;
+template <int V>
+constexpr int at_slots = V > 16 ? kAtSlotsWide : kAtSlots;
+template <int V>
+constexpr int at_sums2 = V > 16 ? kAtSums2Wide : kAtSums2;
 
 // the query head of the block: blockIdx.y within its group of gridDim.y heads, the group (= the K/V head) in blockIdx.z
 __device__ __forceinline__ int64_t query_head() { return (int64_t)blockIdx.z * gridDim.y + blockIdx.y; }
@@ -106,9 +120,10 @@ __device__ __forceinline__ AttnArgsT<E> at_head(AttnArgsT<E> a)
 }
 
 // the scratch of the block's head: query head y owns the slice at y * pieces * kAtSlots (formed at entry like the bases above)
+template <int V>
 __device__ __forceinline__ float *at_head_scratch(const GroupPieces &g)
 {
-    float *s = g.scratch + query_head() * g.npieces * kAtSlots;
+    float *s = g.scratch + query_head() * g.npieces * at_slots<V>;
 #if defined(__HIP_DEVICE_COMPILE__)
     asm("" : "+s"(s));
 #endif
@@ -134,7 +149,7 @@ __device__ __forceinline__ AttnBias at_head(AttnBias b)
 }
 
 // The bias of the step's nonzeros kb + i V + sub, one coalesced 4-byte load per nonzero by the lane that ends up with its
-// score (0 past the end e: no load).  A span issues it with the step's gathers (kBiasEarly) or, where that costs the kernel
+// score (0 past the end e, and in a lane that owns no nonzero of a step narrower than the group: no load).  A span issues it with the step's gathers (kBiasEarly) or, where that costs the kernel
 // a register it does not have, after reduce_scatter; the bits are the same.
 template <int V>
 __device__ __forceinline__ void load_bias(const float *__restrict__ bias, int64_t kb, int64_t e, int sub, float (&bl)[LaneGeom<V>::L])
@@ -142,7 +157,7 @@ __device__ __forceinline__ void load_bias(const float *__restrict__ bias, int64_
 #pragma unroll
     for (int i = 0; i < LaneGeom<V>::L; ++i) {
         const int64_t n = kb + (int64_t)i * V + sub;
-        bl[i] = n < e ? bias[n] : 0.0f;
+        bl[i] = LaneGeom<V>::owner(sub) && n < e ? bias[n] : 0.0f;
     }
 }
 
@@ -199,13 +214,14 @@ __device__ __forceinline__ void fwd_span(int lane, int64_t b, int64_t e, const A
         float p[T];
 #pragma unroll
         for (int t = 0; t < T; ++t) p[t] = dot_partial(q, widen<E>(xk[t]), nk);
-        reduce_scatter<V, T>(p, sub);
+        reduce_scatter<V, T>(p, sub, gbase);
         if constexpr (BIAS && !kEarly) load_bias<V>(bias, kb, e, sub, bl);
         float tl[L], sm = -INFINITY;
 #pragma unroll
         for (int i = 0; i < L; ++i) {
-            if constexpr (BIAS) tl[i] = kb + i * V + sub < e ? a.scale * p[i * V] + bl[i] : -INFINITY;
-            else tl[i] = kb + i * V + sub < e ? a.scale * p[i * V] : -INFINITY;
+            const bool in = LaneGeom<V>::owner(sub) && kb + i * V + sub < e;
+            if constexpr (BIAS) tl[i] = in ? a.scale * p[i * V] + bl[i] : -INFINITY;
+            else tl[i] = in ? a.scale * p[i * V] : -INFINITY;
             sm = fmaxf(sm, tl[i]);
         }
         const float mn = fmaxf(m, group_max<V>(sm));
@@ -277,7 +293,7 @@ __global__ __launch_bounds__(kBlock) void k_attn_fwd_pieces(GroupPieces g, AttnA
     const AttnArgsT<E> a = at_head(a0);
     [[maybe_unused]] const float *bias = nullptr;
     if constexpr (BIAS) bias = at_head(bias_of(bb...)).bias;
-    float *const scratch = at_head_scratch(g);
+    float *const scratch = at_head_scratch<V>(g);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     int lo;
     const int64_t p = group_piece<V>(g, lo);
@@ -288,7 +304,7 @@ __global__ __launch_bounds__(kBlock) void k_attn_fwd_pieces(GroupPieces g, AttnA
     float m, l;
     float4 acc;
     fwd_span<V, VEC, E, BIAS>(lane, b, e, a, q, g.col_idx, c0, m, l, acc, bias);
-    float *s = scratch + p * kAtSlots;
+    float *s = scratch + p * at_slots<V>;
     if (sub == 0) *reinterpret_cast<float2 *>(s) = make_float2(m, l);
     if (c0 < a.kv) *reinterpret_cast<float4 *>(s + kAtSums + c0) = acc;
 }
@@ -303,14 +319,14 @@ __global__ __launch_bounds__(kBlock) void k_attn_fwd_combine(GroupPieces g, Attn
     if (i >= g.n_long) return;
     const int64_t r = g.long_row[i];
     const int f = g.long_first[i], n = g.long_first[i + 1];
-    const float *scratch = at_head_scratch(g);
+    const float *scratch = at_head_scratch<V>(g);
     float M = -INFINITY;
-    for (int p = f; p < n; ++p) M = fmaxf(M, scratch[(int64_t)p * kAtSlots]);
+    for (int p = f; p < n; ++p) M = fmaxf(M, scratch[(int64_t)p * at_slots<V>]);
     const float z = M == -INFINITY ? 0.0f : M;
     float l = 0.0f;
     float4 acc = zero4();
     for (int p = f; p < n; ++p) {
-        const float *s = scratch + (int64_t)p * kAtSlots;
+        const float *s = scratch + (int64_t)p * at_slots<V>;
         const float w = expf(s[0] - z);
         l = fmaf(s[1], w, l);
         if (c0 < a.kv) {
@@ -354,8 +370,8 @@ __device__ __forceinline__ float4 bwdq_span(int lane, int64_t b, int64_t e, cons
             ps[t] = dot_partial(q, widen<E>(xk[t]), nk);
             pd[t] = dot_partial(g, widen<E>(xv[t]), nv);
         }
-        reduce_scatter<V, T>(ps, sub);
-        reduce_scatter<V, T>(pd, sub);
+        reduce_scatter<V, T>(ps, sub, gbase);
+        reduce_scatter<V, T>(pd, sub, gbase);
         if constexpr (BIAS && !kEarly) load_bias<V>(bias, kb, e, sub, bl);
         float dl[L], dt[T];
 #pragma unroll
@@ -365,7 +381,11 @@ __device__ __forceinline__ float4 bwdq_span(int lane, int64_t b, int64_t e, cons
                 const float p = expf(t - M) * rinv;
                 const float db = p * (pd[i * V] - delta);
                 const int64_t n = kb + (int64_t)i * V + sub;
-                if (dbias && n < e) dbias[n] = db;
+                if constexpr (T < V) {
+                    if (dbias && sub < T && n < e) dbias[n] = db;
+                } else {
+                    if (dbias && n < e) dbias[n] = db;
+                }
                 dl[i] = a.scale * db;
             } else {
                 const float t = a.scale * ps[i * V];
@@ -434,7 +454,7 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_q_pieces(GroupPieces g, Att
     const AttnArgsT<E> a = at_head(a0);
     [[maybe_unused]] AttnBias bi{};
     if constexpr (BIAS) bi = at_head(bias_of(bb...));
-    float *const scratch = at_head_scratch(g);
+    float *const scratch = at_head_scratch<V>(g);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     int lo;
     const int64_t p = group_piece<V>(g, lo);
@@ -446,7 +466,7 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_q_pieces(GroupPieces g, Att
     const float4 q = c0 < a.k ? load_wide<VEC>(a.Q, a.ldq, r, c0, a.k) : zero4();
     const float2 st = *reinterpret_cast<const float2 *>(a.stats_in + 2 * r);
     const float4 dq = bwdq_span<V, VEC, E, BIAS>(lane, b, e, a, q, go, st.x, st.y, delta, g.col_idx, c0, bi.bias, bi.dbias);
-    if (c0 < a.k) *reinterpret_cast<float4 *>(scratch + p * kAtSlots + kAtSums + c0) = dq;
+    if (c0 < a.k) *reinterpret_cast<float4 *>(scratch + p * at_slots<V> + kAtSums + c0) = dq;
     if (sub == 0 && p == g.long_first[lo]) a.delta[r] = delta;
 }
 
@@ -459,11 +479,11 @@ __global__ __launch_bounds__(kBlock) void k_attn_add_pieces(GroupPieces g, int o
     const int sub = threadIdx.x & (V - 1), c0 = 4 * sub;
     const int64_t i = (int64_t)blockIdx.x * (kBlock / V) + threadIdx.x / V;
     if (i >= g.n_long || c0 >= w) return;
-    const float *scratch = at_head_scratch(g);
+    const float *scratch = at_head_scratch<V>(g);
     out += query_head() * hout;
     float4 acc = zero4();
     for (int p = g.long_first[i]; p < g.long_first[i + 1]; ++p) {
-        const float4 x = *reinterpret_cast<const float4 *>(scratch + (int64_t)p * kAtSlots + off + c0);
+        const float4 x = *reinterpret_cast<const float4 *>(scratch + (int64_t)p * at_slots<V> + off + c0);
         acc.x = acc.x + x.x;
         acc.y = acc.y + x.y;
         acc.z = acc.z + x.z;
@@ -496,7 +516,7 @@ __device__ __forceinline__ void bwdkv_span(int lane, int64_t b, int64_t e, const
         float de[L];
 #pragma unroll
         for (int i = 0; i < L; ++i) {
-            const bool in = kb + i * V + sub < e;
+            const bool in = LaneGeom<V>::owner(sub) && kb + i * V + sub < e;
             st[i] = in ? *reinterpret_cast<const float2 *>(a.stats_in + 2 * (int64_t)c[i]) : make_float2(0.0f, 0.0f);
             de[i] = in ? a.delta_in[c[i]] : 0.0f;
         }
@@ -513,8 +533,8 @@ __device__ __forceinline__ void bwdkv_span(int lane, int64_t b, int64_t e, const
             ps[t] = dot_partial(kj, widen<E>(xq[t]), nk);
             pd[t] = dot_partial(vj, widen<E>(xg[t]), nv);
         }
-        reduce_scatter<V, T>(ps, sub);
-        reduce_scatter<V, T>(pd, sub);
+        reduce_scatter<V, T>(ps, sub, gbase);
+        reduce_scatter<V, T>(pd, sub, gbase);
         if constexpr (BIAS && !kEarly) load_bias<V>(bias, kb, e, sub, bl);
         float pl[L], dl[L], pt[T], dt[T];
 #pragma unroll
@@ -573,7 +593,7 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_pieces(GroupPieces g, At
     const AttnArgsT<E> a = at_head(a0);
     [[maybe_unused]] const float *bias = nullptr;
     if constexpr (BIAS) bias = at_head(bias_of(bb...)).bias;
-    float *const scratch = at_head_scratch(g);
+    float *const scratch = at_head_scratch<V>(g);
     const int lane = threadIdx.x & (kWave - 1), sub = lane & (V - 1), c0 = 4 * sub;
     int lo;
     const int64_t p = group_piece<V>(g, lo);
@@ -584,9 +604,9 @@ __global__ __launch_bounds__(kBlock) void k_attn_bwd_kv_pieces(GroupPieces g, At
     const float4 vj = c0 < a.kv ? load_wide<VEC>(a.V, a.ldv, r, c0, a.kv) : zero4();
     float4 dk, dv;
     bwdkv_span<V, VEC, E, BIAS>(lane, b, e, a, kj, vj, g.col_idx, c0, dk, dv, bias);
-    float *s = scratch + p * kAtSlots;
+    float *s = scratch + p * at_slots<V>;
     if (c0 < a.k) *reinterpret_cast<float4 *>(s + kAtSums + c0) = dk;
-    if (c0 < a.kv) *reinterpret_cast<float4 *>(s + kAtSums2 + c0) = dv;
+    if (c0 < a.kv) *reinterpret_cast<float4 *>(s + at_sums2<V> + c0) = dv;
 }
 
 
@@ -733,13 +753,13 @@ __global__ __launch_bounds__(kBlock) void k_attn_add_pieces_gqa(GroupPieces g, i
     const int sub = threadIdx.x & (V - 1), c0 = 4 * sub;
     const int64_t i = (int64_t)blockIdx.x * (kBlock / V) + threadIdx.x / V;
     if (i >= g.n_long || c0 >= w) return;
-    const int64_t c = blockIdx.y, slice = (int64_t)g.npieces * kAtSlots;
+    const int64_t c = blockIdx.y, slice = (int64_t)g.npieces * at_slots<V>;
     const float *scratch = g.scratch + c * group * slice;
     float4 acc = zero4();
     for (int y = 0; y < group; ++y, scratch += slice) {
         float4 sum = zero4();
         for (int p = g.long_first[i]; p < g.long_first[i + 1]; ++p)
-            sum = add4(sum, *reinterpret_cast<const float4 *>(scratch + (int64_t)p * kAtSlots + off + c0));
+            sum = add4(sum, *reinterpret_cast<const float4 *>(scratch + (int64_t)p * at_slots<V> + off + c0));
         acc = y ? add4(acc, sum) : sum;
     }
     store_slice<VEC>(out + c * hout + (int64_t)g.long_row[i] * ld + c0, acc, c0, w);
@@ -769,7 +789,7 @@ int launch_attn_v(const spmv_csr &h, const AttnArgsT<E> &a, const AttnBias *bb, 
     });
     SPMV_LAUNCHED("k_attn_*_rows");
     if (!p.n_long) return SPMV_OK;
-    const GroupPieces q = group_pieces(h, h.plan_attn.d_scratch.get());
+    const GroupPieces q = group_pieces(h, V > 16 ? h.plan_attn.d_scratch_wide.get() : h.plan_attn.d_scratch.get());
     const dim3 pgrid(group_grid(p.pieces, V).x, (unsigned)group, kv_heads), lgrid(group_grid(p.n_long, V).x, (unsigned)heads);
     if constexpr (PASS == kPassForward) {
         with_bias([&](auto... bias) { hipLaunchKernelGGL((k_attn_fwd_pieces<V, VEC, E, decltype(bias)...>), pgrid, block, 0, s, q, a, bias...); });
@@ -788,13 +808,13 @@ int launch_attn_v(const spmv_csr &h, const AttnArgsT<E> &a, const AttnBias *bb, 
             const dim3 cgrid(lgrid.x, kv_heads);
             hipLaunchKernelGGL((k_attn_add_pieces_gqa<V, VEC, E>), cgrid, block, 0, s, q, kAtSums, a.out0, a.ld0, a.k, a.h0, group);
             SPMV_LAUNCHED("k_attn_add_pieces_gqa");
-            hipLaunchKernelGGL((k_attn_add_pieces_gqa<V, VEC, E>), cgrid, block, 0, s, q, kAtSums2, a.out1, a.ld1, a.kv, a.h1, group);
+            hipLaunchKernelGGL((k_attn_add_pieces_gqa<V, VEC, E>), cgrid, block, 0, s, q, at_sums2<V>, a.out1, a.ld1, a.kv, a.h1, group);
             SPMV_LAUNCHED("k_attn_add_pieces_gqa");
             return SPMV_OK;
         }
         hipLaunchKernelGGL((k_attn_add_pieces<V, VEC, E>), lgrid, block, 0, s, q, kAtSums, a.out0, a.ld0, a.k, a.h0);
         SPMV_LAUNCHED("k_attn_add_pieces");
-        hipLaunchKernelGGL((k_attn_add_pieces<V, VEC, E>), lgrid, block, 0, s, q, kAtSums2, a.out1, a.ld1, a.kv, a.h1);
+        hipLaunchKernelGGL((k_attn_add_pieces<V, VEC, E>), lgrid, block, 0, s, q, at_sums2<V>, a.out1, a.ld1, a.kv, a.h1);
         SPMV_LAUNCHED("k_attn_add_pieces");
     }
     return SPMV_OK;
@@ -805,7 +825,13 @@ int launch_attn(const spmv_csr &h, const AttnArgsT<E> &a, const AttnBias *bb, in
                 hipStream_t s)
 {
     if (h.rows == 0) return SPMV_OK;
-    return dispatch_lanes(((a.k > a.kv ? a.k : a.kv) + 3) / 4, [&](auto v) {
+    const int slices = ((a.k > a.kv ? a.k : a.kv) + 3) / 4;
+    // the sixth geometry, V = 32 in steps of kWideStep: only a _wide entry point admits such widths (capi.hip), and it has made
+    // sure of the wide scratch (plan_attention_wide)
+    if (slices > 16)
+        return vec ? launch_attn_v<PASS, 32, true, E>(h, a, bb, heads, group, gqa, what, s)
+                   : launch_attn_v<PASS, 32, false, E>(h, a, bb, heads, group, gqa, what, s);
+    return dispatch_lanes(slices, [&](auto v) {
         constexpr int V = decltype(v)::value;
         return vec ? launch_attn_v<PASS, V, true, E>(h, a, bb, heads, group, gqa, what, s)
                    : launch_attn_v<PASS, V, false, E>(h, a, bb, heads, group, gqa, what, s);
@@ -828,12 +854,26 @@ int plan_attention_heads(spmv_csr &h, int heads, hipStream_t s)
 {
     if (int rc = plan_spmm(h, s)) return rc;
     if (h.plan_attn.ready && h.plan_attn.heads >= heads) return SPMV_OK;
-    AttnPlan p;
-    if (h.plan_spmm.n_long) SPMV_HIP_TRY(p.d_scratch.alloc((size_t)heads * (size_t)h.plan_spmm.pieces * kAtSlots));
-    p.heads = heads;
-    p.ready = true;
+    DevPtr<float> scratch;
+    if (h.plan_spmm.n_long) SPMV_HIP_TRY(scratch.alloc((size_t)heads * (size_t)h.plan_spmm.pieces * kAtSlots));
     if (h.plan_attn.ready) SPMV_HIP_TRY(hipStreamSynchronize(s));
-    h.plan_attn = std::move(p);
+    h.plan_attn.d_scratch = std::move(scratch);     // (the wide scratch, if there is one, stays)
+    h.plan_attn.heads = heads;
+    h.plan_attn.ready = true;
+    return SPMV_OK;
+}
+
+// The plan of the _wide entry points: the plan above for `heads` heads and, for V = 32, a scratch of its own of pieces *
+// kAtSlotsWide floats per head, a separate allocation that grows like the other (the narrow scratch keeps its layout).
+int plan_attention_wide(spmv_csr &h, int heads, hipStream_t s)
+{
+    if (int rc = plan_attention_heads(h, heads, s)) return rc;
+    if (h.plan_attn.wide_heads >= heads) return SPMV_OK;
+    DevPtr<float> scratch;
+    if (h.plan_spmm.n_long) SPMV_HIP_TRY(scratch.alloc((size_t)heads * (size_t)h.plan_spmm.pieces * kAtSlotsWide));
+    if (h.plan_attn.wide_heads) SPMV_HIP_TRY(hipStreamSynchronize(s));
+    h.plan_attn.d_scratch_wide = std::move(scratch);
+    h.plan_attn.wide_heads = heads;
     return SPMV_OK;
 }
 
@@ -842,11 +882,13 @@ int plan_attention(spmv_csr &h, hipStream_t s) { return plan_attention_heads(h, 
 int64_t attention_plan_bytes(const spmv_csr &h)
 {
     if (!h.plan_attn.ready) return 0;
-    return spmm_plan_bytes(h) + (h.plan_spmm.n_long ? (int64_t)h.plan_attn.heads * h.plan_spmm.pieces * kAtSlots * 4 : 0);
+    const int64_t floats = (int64_t)h.plan_attn.heads * kAtSlots + (int64_t)h.plan_attn.wide_heads * kAtSlotsWide;
+    return spmm_plan_bytes(h) + (h.plan_spmm.n_long ? floats * h.plan_spmm.pieces * 4 : 0);
 }
 
 int attention_max_heads(const spmv_csr &h, int width)
 {
+    if (width > 64) return (int)group_max_heads(h, 32);     // (the _wide entry points only)
     return dispatch_lanes((width + 3) / 4, [&](auto v) { return (int)group_max_heads(h, decltype(v)::value); });
 }
 

@@ -8,7 +8,8 @@
 // of the group holds the slice [4s, 4s+4) of the columns: of the row's own operands in registers, and of every operand
 // row the CSR row refers to.  A workgroup is kBlock = 256 lanes, 256 / V groups; the row blocks are dealt so that each of
 // the 8 XCDs takes one contiguous range of them (xcd_item64: neighbouring rows share lines of the gathered operand in
-// that XCD's L2).  The groups take the rows in the plan's order (stably by length inside blocks of 4096 rows, so the rows a
+// that XCD's L2).  Fused attention's _wide entry points add a sixth group, V = 32, for operands of 65 to 128 columns: see
+// "A step narrower than the group" below; SpMM and SDDMM end at 64 columns.  The groups take the rows in the plan's order (stably by length inside blocks of 4096 rows, so the rows a
 // wavefront walks side by side end at nearly the same step), except at V = 1: see group_rows.
 // Heads (fused attention only).  A launch may carry several heads of one pattern in blockIdx.y and blockIdx.z (the query head
 // within its group of heads that share K and V, and the group; kernels_attention.hip); group_row, group_piece and
@@ -20,6 +21,11 @@
 // kb + i V + s, i < L = T / V, coalesced (0 past the end), the group broadcasts them with shuffles (group_columns), every
 // lane issues all its gathers of the step, one slice per nonzero and operand (load_slice), and only then computes.
 // All lanes of a group run every step and every shuffle together: the exits (group_row, group_piece) are group-uniform.
+// A step narrower than the group (V = 32: T = kWideStep = 8 < V, L = 1).  T = V would hold 2 x 32 gathered slices of 4
+// registers per lane.  Lanes s < T load the step's column indices kb + s and own those nonzeros (what a kernel loads or
+// stores per nonzero is theirs); the lanes from T on own none and idle between the butterfly and the broadcast.  The order
+// below holds word for word with V = 32: every lane still forms its partial of every dot product of the step, and
+// reduce_scatter runs the butterfly's levels m = 16, 8, 4, 2, 1 for each result.
 //
 // The order of the fp32 operations, as far as it is shared.  No function here holds a product followed by a sum but
 // where fmaf is written, so the floating-point contraction of the including file does not reach in.
@@ -53,11 +59,22 @@
 
 namespace spmv {
 
+// The step of a group of 32 lanes (fused attention at 64 < max(k, kv) <= 128, the _wide entry points only): T_wide of
+// include/spmv_hip.h.  T = V = 32 would keep 2 x 32 gathered slices of 4 registers each per lane, the whole register file;
+// 8 nonzeros per step keep 64, the register picture of V = 8.  Such a step is narrower than its group (T < V): lanes
+// sub < T each own one nonzero of the step (its column index, its bias, its stats and delta, its expf, its dBias), the other
+// lanes of the group own none.  The forward pass's bits depend on T (one rescale per step); nothing else does.
+constexpr int kWideStep = 8;
+
 template <int V>
 struct LaneGeom {
-    static constexpr int T = V > 8 ? V : 8;   // nonzeros per step: T slice gathers in flight per lane and operand
-    static constexpr int L = T / V;           // of which a lane loads the column indices of L and ends with L results
+    static constexpr int T = V > 16 ? kWideStep : V > 8 ? V : 8;   // nonzeros per step: T slice gathers in flight per lane and operand
+    static constexpr int L = T >= V ? T / V : 1;   // of which a lane loads the column indices of L and ends with L results
+                                                   // (T < V: one, and only in the lanes sub < T)
+    // whether lane `sub` owns a nonzero in its slot i < L of a step at all (always, unless the step is narrower than the group)
+    static constexpr bool owner(int sub) { return T >= V || sub < T; }
 };
+static_assert(LaneGeom<32>::T == 8 && LaneGeom<32>::L == 1 && LaneGeom<16>::T == 16 && LaneGeom<4>::L == 2, "the geometry of the header");
 
 // block b of the grid takes item xcd_item64(b, n): blocks are dealt round-robin over the 8 XCDs, so each XCD gets one
 // contiguous range of the n row blocks
@@ -232,10 +249,32 @@ __device__ __forceinline__ float dot_partial(float4 u, float4 x, int n1)
 }
 
 // the xor butterfly over the group as a reduce-scatter: of results i*V + [0, V) lane `sub` ends with result i*V + sub in
-// p[i*V]
+// p[i*V].
+// A step narrower than the group (T < V; gbase: the group's first lane in the wavefront, which only this case reads): the
+// levels m = V/2 .. V/T each halve the results a lane still holds (the lane with bit m keeps the upper half), which leaves one;
+// the levels below are the all-reduce of that one, p <- p + p_(sub xor m).  Every result has then gone through the additions of
+// group_sum<V> in its order of levels, m = V/2, .., 1.  Result t sits in the V/T lanes t V/T + [0, V/T); one more shuffle
+// hands it to its owner, lane t < T, in p[0].
 template <int V, int T>
-__device__ __forceinline__ void reduce_scatter(float (&p)[T], int sub)
+__device__ __forceinline__ void reduce_scatter(float (&p)[T], int sub, [[maybe_unused]] int gbase = 0)
 {
+    if constexpr (T < V) {
+        constexpr int W = V / T;        // lanes that end up with the same result
+#pragma unroll
+        for (int m = V / 2, n = T / 2; n >= 1; m /= 2, n /= 2) {
+            const bool up = (sub & m) != 0;
+#pragma unroll
+            for (int j = 0; j < n; ++j) {
+                const float lo = p[j], hi = p[j + n];
+                const float keep = up ? hi : lo, send = up ? lo : hi;
+                p[j] = keep + __shfl_xor(send, m);
+            }
+        }
+#pragma unroll
+        for (int m = W / 2; m >= 1; m /= 2) p[0] = p[0] + __shfl_xor(p[0], m);
+        p[0] = __shfl(p[0], gbase + (sub & (T - 1)) * W);
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < T / V; ++i) {
 #pragma unroll
@@ -251,10 +290,11 @@ __device__ __forceinline__ void reduce_scatter(float (&p)[T], int sub)
     }
 }
 
-// what lane `sub` holds for nonzero i*V + sub of the step, in every lane of the group
+// what lane `sub` holds for nonzero i*V + sub of the step, in every lane of the group (T < V: lane t < T holds nonzero t's)
 template <int V, int T, typename X>
-__device__ __forceinline__ void group_bcast(const X (&w)[T / V], X (&wt)[T], int gbase)
+__device__ __forceinline__ void group_bcast(const X (&w)[LaneGeom<V>::L], X (&wt)[T], int gbase)
 {
+    static_assert(T == LaneGeom<V>::T, "a step of the geometry");
 #pragma unroll
     for (int t = 0; t < T; ++t) wt[t] = V == 1 ? w[t] : __shfl(w[t / V], gbase + t % V);
 }
@@ -275,15 +315,16 @@ __device__ __forceinline__ float group_sum(float x)
     return x;
 }
 
-// the step's column indices: lane `sub` loads nonzeros kb + i*V + sub (0 past the end e), every lane gets all T
+// the step's column indices: lane `sub` loads nonzeros kb + i*V + sub (0 past the end e; T < V: the lanes sub < T one each,
+// the others none), every lane gets all T
 template <int V, int T>
 __device__ __forceinline__ void group_columns(int64_t kb, int64_t e, int sub, int gbase, const int32_t *__restrict__ col_idx,
-                                              int32_t (&c)[T / V], int32_t (&ct)[T])
+                                              int32_t (&c)[LaneGeom<V>::L], int32_t (&ct)[T])
 {
 #pragma unroll
-    for (int i = 0; i < T / V; ++i) {
+    for (int i = 0; i < LaneGeom<V>::L; ++i) {
         const int64_t n = kb + (int64_t)i * V + sub;
-        c[i] = n < e ? col_idx[n] : 0;
+        c[i] = LaneGeom<V>::owner(sub) && n < e ? col_idx[n] : 0;
     }
     group_bcast<V, T>(c, ct, gbase);
 }

@@ -266,6 +266,8 @@ struct AttnPlan {
     bool ready = false;
     int heads = 0;                    // heads one launch may carry (spmv_csr_attention_plan: 1; _plan_heads grows it)
     DevPtr<float> d_scratch;          // [heads * pieces * 132] per head and piece (m, l) and up to 128 partial sums (empty: no long row)
+    int wide_heads = 0;               // heads the _wide calls may carry (spmv_csr_attention_plan_wide; 0: never called)
+    DevPtr<float> d_scratch_wide;     // [wide_heads * pieces * 260] the same for widths above 64: (m, l) and up to 2 x 128 partial sums
 };
 
 }  // namespace spmv
@@ -379,8 +381,9 @@ int launch_row_softmax_backward(const spmv_csr &h, float scale, const float *P, 
 // kernels_attention.hip: spmv_csr_attention_* (on the plan of plan_spmm and a scratch of its own)
 int plan_attention(spmv_csr &h, hipStream_t s);
 int plan_attention_heads(spmv_csr &h, int heads, hipStream_t s);
+int plan_attention_wide(spmv_csr &h, int heads, hipStream_t s);     // the same and the scratch of widths above 64
 int64_t attention_plan_bytes(const spmv_csr &h);
-int attention_max_heads(const spmv_csr &h, int width);   // heads one launch takes at operands of `width` columns (>= 0)
+int attention_max_heads(const spmv_csr &h, int width);   // heads one launch takes at operands of `width` <= 128 columns (>= 0)
 // (one call of any of the nine entry points: `a` filled and checked by capi.hip; `heads` query heads, `group` of them per K/V head;
 // sum_group: backward_kv adds the heads of a group in the kernel, as the _gqa call does; `what` names the caller in a refusal;
 // bb: the bias of a _bias entry point, null for every other call)

@@ -33,18 +33,19 @@ import torch
 from . import capi
 
 MAX_K = 64
+WIDE_MAX_K = 128     # a FusedSparseAttention made with wide=True (spmv_csr_attention_*_wide)
 FUSED_DTYPES = (torch.float32, torch.bfloat16, torch.float16)      # what the fused passes take (all matrices of a call alike)
 
 
-def _operand(t, name: str, rows: int, k=None, dtypes=(torch.float32,)):
+def _operand(t, name: str, rows: int, k=None, dtypes=(torch.float32,), max_k: int = MAX_K):
     """t as the library takes it: 2-D float32 (or another of `dtypes`), stride(1) == 1, stride(0) >= k, aligned to four
     elements: 16 bytes of floats, 8 of 16-bit elements (copied if it is not)."""
     if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in dtypes:
         raise ValueError(f"SparseAttention: {name} must be a 2-D {' or '.join(str(d).replace('torch.', '') for d in dtypes)} tensor")
     if t.shape[0] != rows:
         raise ValueError(f"SparseAttention: {name} has {t.shape[0]} rows, the pattern needs {rows}")
-    if not 1 <= t.shape[1] <= MAX_K:
-        raise ValueError(f"SparseAttention: {name} has {t.shape[1]} columns (1 <= k <= {MAX_K})")
+    if not 1 <= t.shape[1] <= max_k:
+        raise ValueError(f"SparseAttention: {name} has {t.shape[1]} columns (1 <= k <= {max_k})")
     if k is not None and t.shape[1] != k:
         raise ValueError(f"SparseAttention: {name} has {t.shape[1]} columns, its partner has {k}")
     if t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.data_ptr() % (4 * t.element_size()) == 0:
@@ -137,14 +138,14 @@ def _fused_operand(t, name: str, rows: int, k=None):
     return _heads_empty(t.shape[0], rows, w, t.device, t.dtype).copy_(t)
 
 
-def _batched_operand(t, name: str, rows: int, k=None):
+def _batched_operand(t, name: str, rows: int, k=None, max_k: int = MAX_K):
     """A (heads, rows, k) operand as one _heads call takes it: stride(2) == 1, stride(1) >= k, head 0 on a boundary of four
     elements (16 bytes of floats, 8 of 16-bit elements) and, with more than one head, a head stride that is a multiple of 4
     elements (0: one head shared by all).  Stacked heads and the column blocks of a (rows, heads * k) tensor with k % 4 == 0
     are; anything else is copied once."""
     if t.shape[0] < 1:
         raise ValueError(f"SparseAttention: {name} has no heads")
-    _operand(t[0], name, rows, k, FUSED_DTYPES)       # (dtype and shape)
+    _operand(t[0], name, rows, k, FUSED_DTYPES, max_k)       # (dtype and shape)
     w = t.shape[2]
     if t.stride(2) == 1 and t.stride(1) >= w and t.data_ptr() % (4 * t.element_size()) == 0 \
             and (t.shape[0] == 1 or t.stride(0) % 4 == 0):
@@ -276,7 +277,9 @@ class BiasedFusedSparseAttentionFunction(torch.autograd.Function):
     on the three _bias passes: operands as FusedSparseAttentionFunction takes them (a 2-D call is one head), bias float32
     (nnz,) -- one for all heads -- or (heads, nnz), in the storage order of the pattern.  Saved for backward: Q, K, V, O,
     stats and bias.  Backward makes bias_t (the bias in T's order, one gather) only when dK or dV is asked for, and dBias
-    (heads, nnz) only when the bias requires grad; a shared bias gets dBias summed over the heads."""
+    (heads, nnz) only when the bias requires grad; a shared bias gets dBias summed over the heads.
+    On a holder made with wide=True every pass is the _wide call instead: widths up to WIDE_MAX_K, and bias may be None (no
+    bias: the unbiased kernels)."""
 
     @staticmethod
     def _runs(att, heads: int, k: int, kv: int, g: int):
@@ -295,24 +298,30 @@ class BiasedFusedSparseAttentionFunction(torch.autograd.Function):
         flat = Q.dim() == 2
         if flat:
             Q, K, V = Q[None], K[None], V[None]
-        Q = _batched_operand(Q, "Q", A.rows)
-        K = _batched_operand(K, "K", A.cols, Q.shape[-1])
-        V = _batched_operand(V, "V", A.cols)
+        max_k = WIDE_MAX_K if att.wide else MAX_K
+        Q = _batched_operand(Q, "Q", A.rows, None, max_k)
+        K = _batched_operand(K, "K", A.cols, Q.shape[-1], max_k)
+        V = _batched_operand(V, "V", A.cols, None, max_k)
         for name, t in (("K", K), ("V", V)):
             if t.dtype != Q.dtype:
                 raise ValueError(f"SparseAttention: {name} is {t.dtype}, Q is {Q.dtype} (Q, K and V share one dtype)")
         heads, kv = Q.shape[0], V.shape[-1]
         if K.shape[0] != V.shape[0] or heads % K.shape[0] != 0:
             raise ValueError(f"SparseAttention: Q has {heads} heads, K {K.shape[0]} and V {V.shape[0]}")
-        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) not in ((A.nnz,), (heads, A.nnz)):
+        if bias is None and att.wide:
+            pass
+        elif not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) not in ((A.nnz,), (heads, A.nnz)):
             raise ValueError(f"SparseAttention: bias must be a float32 tensor of ({A.nnz},) or ({heads}, {A.nnz})")
-        bias = bias if bias.stride(-1) == 1 else bias.contiguous()
+        bias = bias if bias is None or bias.stride(-1) == 1 else bias.contiguous()
         g = heads // K.shape[0]
         O = _heads_empty(heads, A.rows, kv, V.device, V.dtype)
         stats = torch.empty((heads, A.rows, 2), dtype=torch.float32, device=V.device)
         for lo, hi in BiasedFusedSparseAttentionFunction._runs(att, heads, Q.shape[-1], kv, g):
-            A.attention_forward_bias(Q[lo:hi], K[lo // g:hi // g], V[lo // g:hi // g], bias if bias.dim() == 1 else bias[lo:hi],
-                                     O[lo:hi], stats[lo:hi], att.scale)
+            b = bias if bias is None or bias.dim() == 1 else bias[lo:hi]
+            if att.wide:
+                A.attention_forward_wide(Q[lo:hi], K[lo // g:hi // g], V[lo // g:hi // g], O[lo:hi], stats[lo:hi], b, att.scale)
+            else:
+                A.attention_forward_bias(Q[lo:hi], K[lo // g:hi // g], V[lo // g:hi // g], b, O[lo:hi], stats[lo:hi], att.scale)
         ctx.att, ctx.flat = att, flat
         ctx.save_for_backward(Q, K, V, O, stats, bias)
         return O[0] if flat else O
@@ -325,11 +334,11 @@ class BiasedFusedSparseAttentionFunction(torch.autograd.Function):
         need_q, need_k, need_v, need_b = ctx.needs_input_grad[1:5]
         if not (need_q or need_k or need_v or need_b):
             return None, None, None, None, None
-        dO = _batched_operand(dO[None] if ctx.flat else dO, "dO", A.rows, V.shape[-1])
+        dO = _batched_operand(dO[None] if ctx.flat else dO, "dO", A.rows, V.shape[-1], WIDE_MAX_K if att.wide else MAX_K)
         if dO.shape[0] != Q.shape[0] or dO.dtype != Q.dtype:
             raise ValueError(f"SparseAttention: dO is {dO.dtype} with {dO.shape[0]} heads, Q {Q.dtype} with {Q.shape[0]}")
         heads, g = Q.shape[0], Q.shape[0] // K.shape[0]
-        shared = bias.dim() == 1
+        shared = bias is not None and bias.dim() == 1
         # backward_q also makes delta, which backward_kv reads: it runs whichever gradient is asked for
         dQ = _heads_empty(*Q.shape, Q.device, Q.dtype)
         delta = torch.empty(O.shape[:-1], dtype=torch.float32, device=O.device)
@@ -337,15 +346,24 @@ class BiasedFusedSparseAttentionFunction(torch.autograd.Function):
         dK = dV = bias_t = None
         if need_k or need_v:
             dK, dV = _heads_empty(*K.shape, K.device, K.dtype), _heads_empty(*V.shape, V.device, V.dtype)
-            bias_t = torch.empty_like(bias)
-            T.transpose_gather(bias, bias_t)
+            if bias is not None:
+                bias_t = torch.empty_like(bias)
+                T.transpose_gather(bias, bias_t)
         for lo, hi in BiasedFusedSparseAttentionFunction._runs(att, heads, Q.shape[-1], V.shape[-1], g):
             at = lambda t, lo=lo, hi=hi: t[lo:hi]       # noqa: E731
             kv = lambda t, lo=lo // g, hi=hi // g: t[lo:hi]       # noqa: E731  (the run's K/V heads)
-            A.attention_backward_q_bias(at(Q), kv(K), kv(V), bias if shared else at(bias), at(O), at(dO), at(stats), at(delta), at(dQ),
+            per_head = (lambda b: b) if shared or bias is None else at
+            if att.wide:
+                A.attention_backward_q_wide(at(Q), kv(K), kv(V), at(O), at(dO), at(stats), at(delta), at(dQ), per_head(bias),
+                                            at(dBias) if need_b else None, att.scale)
+                if dK is not None:
+                    T.attention_backward_kv_wide(at(Q), kv(K), kv(V), at(dO), at(stats), at(delta), kv(dK), kv(dV), per_head(bias_t),
+                                                 att.scale)
+                continue
+            A.attention_backward_q_bias(at(Q), kv(K), kv(V), per_head(bias), at(O), at(dO), at(stats), at(delta), at(dQ),
                                         at(dBias) if need_b else None, att.scale)
             if dK is not None:
-                T.attention_backward_kv_bias(at(Q), kv(K), kv(V), bias_t if shared else at(bias_t), at(dO), at(stats), at(delta),
+                T.attention_backward_kv_bias(at(Q), kv(K), kv(V), per_head(bias_t), at(dO), at(stats), at(delta),
                                              kv(dK), kv(dV), att.scale)
         if need_b and shared:
             dBias = dBias[0] if heads == 1 else dBias.sum(0)
@@ -375,9 +393,14 @@ class FusedSparseAttention:
     ``bias=True``: ``att(Q, K, V, bias)`` adds ``bias`` -- float32 (nnz,), shared by all heads, or (heads, nnz), in the storage
     order of ``col_idx`` -- to the scaled scores before the softmax and is differentiable in it
     (BiasedFusedSparseAttentionFunction); T then keeps its map (4 bytes per nonzero), which brings the bias into T's order in
-    backward.  Every layout and dtype above works; "loop" runs one call per K/V head, "batched" as many groups as fit."""
+    backward.  Every layout and dtype above works; "loop" runs one call per K/V head, "batched" as many groups as fit.
+    ``wide=True``: k and kv up to 128 (WIDE_MAX_K) on spmv_csr_attention_*_wide, with or without ``bias=True``, in both
+    ``heads`` modes, with grouped-query heads and 16-bit tensors: both handles are planned wide and every pass is a _wide call,
+    one per K/V head ("loop") or as many groups as fit a launch ("batched").  Up to width 64 those are the calls above bit for
+    bit.  The default is the holder described above, unchanged."""
 
-    def __init__(self, rows: int, cols: int, row_ptr, col_idx, scale: float = 1.0, heads: str = "loop", bias: bool = False):
+    def __init__(self, rows: int, cols: int, row_ptr, col_idx, scale: float = 1.0, heads: str = "loop", bias: bool = False,
+                 wide: bool = False):
         if heads not in ("loop", "batched"):
             raise ValueError(f"SparseAttention: heads = {heads!r} (\"loop\" or \"batched\")")
         if not math.isfinite(scale):
@@ -389,14 +412,18 @@ class FusedSparseAttention:
         vals = torch.zeros(int(col_idx.numel()), dtype=torch.float32, device=col_idx.device)
         self.A = capi.CsrMatrix.from_device(rows, cols, row_ptr, col_idx, vals)
         self.bias = bool(bias)
+        self.wide = bool(wide)
         self.T = self.A.transpose(keep_map=self.bias)
         self.A.attention_plan()
         self.T.attention_plan()
+        if self.wide:
+            self.A.attention_plan_wide(1)
+            self.T.attention_plan_wide(1)
 
     def __call__(self, Q, K, V, bias=None):
         if self.bias != (bias is not None):
             raise ValueError("SparseAttention: a holder made with bias=True takes att(Q, K, V, bias), any other att(Q, K, V)")
-        if bias is not None:
+        if bias is not None or self.wide:
             return BiasedFusedSparseAttentionFunction.apply(self, Q, K, V, bias)
         return FusedSparseAttentionFunction.apply(self, Q, K, V)
 
@@ -404,7 +431,10 @@ class FusedSparseAttention:
         """[(lo, hi)]: the fewest runs of heads that each fit one launch on A and on T at these widths (the library says how
         many fit: spmv_csr_attention_max_heads).  Grows both plans to the largest run.  With ``group`` > 1 (grouped-query
         heads) a run is whole groups; None when not even one group fits a launch (the caller then runs the heads in a loop)."""
-        fit = min(self.A.attention_max_heads(k, kv), self.T.attention_max_heads(k, kv))
+        if self.wide:
+            fit = min(self.A.attention_max_heads_wide(k, kv), self.T.attention_max_heads_wide(k, kv))
+        else:
+            fit = min(self.A.attention_max_heads(k, kv), self.T.attention_max_heads(k, kv))
         fit = max(1, min(fit, self.max_heads or fit))      # (not even one: the call itself says why)
         if group > 1:
             if fit < group:
@@ -420,8 +450,9 @@ class FusedSparseAttention:
     def plan_heads(self, heads: int) -> None:
         """Grow both plans to `heads` heads of one launch (an allocation: not inside a graph capture)."""
         if heads > self._planned:
-            self.A.attention_plan_heads(heads)
-            self.T.attention_plan_heads(heads)
+            plan = "attention_plan_wide" if self.wide else "attention_plan_heads"
+            getattr(self.A, plan)(heads)
+            getattr(self.T, plan)(heads)
             self._planned = heads
 
     def close(self) -> None:

@@ -49,7 +49,7 @@ def main() -> int:
     below = lanes = scratch = total = 0
     join = lambda xs: "/".join(str(x) for x in xs)      # noqa: E731
     for name in names:
-        for V in (1, 2, 4, 8, 16):
+        for V in (1, 2, 4, 8, 16, 32):
             for vec in (True, False):
                 ours = [table[(name, V, vec, e)] for e in ELEMENTS.values()]
                 twin = [table[(name[:-5], V, vec, e)] for e in ELEMENTS.values()]

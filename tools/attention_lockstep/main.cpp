@@ -17,7 +17,10 @@
 // (the bias in the transposed pattern's order) and dBias exactly sized heap blocks of floats with head strides that are
 // multiples of nothing, rows and transposed rows in pieces: O, dQ, dBias, dK and dV against a serial fp64 attention with bias
 // written here (fp32: 2e-5 of the magnitude; bf16: 2^-7 more: half an ulp, 2^-8, for the rounded output and as much for the delta
-// formed from the rounded O), and every position of dBias written.
+// formed from the rounded O), and every position of dBias written.  Then V = 32 (the kernels of the _wide entry points): the
+// same bias runs at (128, 128) and (65, 100) on the wide scratch (260 floats per piece, exactly sized), with a bias and
+// without one (the unbiased kernels), and zero padding: (64, 20), (8, 40) and (16, 12) padded to (128, 128) give the narrow
+// geometry's delta, dBias, dQ, dK and dV bit for bit on its stats and delta, and +0 in every padded column.
 #include "kernels_attention.hip"
 #include "kernels_sddmm.hip"
 #include <algorithm>
@@ -67,8 +70,16 @@ static spmv_csr make_handle(const Pattern &a, std::vector<void *> &owned)
 static void plan_heads(spmv_csr &h, int heads)
 {
     free(h.plan_attn.d_scratch.p);
+    free(h.plan_attn.d_scratch_wide.p);
     h.plan_attn = AttnPlan{};
     if (plan_attention_heads(h, heads, nullptr) != SPMV_OK || h.plan_attn.heads != heads) abort();
+}
+
+// the same and the wide scratch (V = 32) for exactly `heads` heads: an exactly sized block of heads x pieces x 260 floats
+static void plan_wide(spmv_csr &h, int heads)
+{
+    plan_heads(h, heads);
+    if (plan_attention_wide(h, heads, nullptr) != SPMV_OK || h.plan_attn.wide_heads != heads) abort();
 }
 
 // `heads` heads of rows x w floats: head y at p + y * stride, its rows ld apart; one exactly sized block that ends where the
@@ -507,16 +518,20 @@ template <typename E> static E *as_elements(const HeadsMatrix &m, int heads, int
     else return twin16<E>(m, heads, rows, w, vec, fill);
 }
 
-template <typename E> static int bias_runs(const char *name, spmv_csr &A, spmv_csr &T, const Pattern &a, const Pattern &t, float scale, std::mt19937 &rng)
+// v32: the V = 32 section instead: (128, 128) and (65, 100) on the wide scratch, with a bias and (with_bias = false) without one:
+// the unbiased kernels, a bias of zeros in the serial statement, no dBias
+template <typename E> static int bias_runs(const char *name, spmv_csr &A, spmv_csr &T, const Pattern &a, const Pattern &t, float scale, std::mt19937 &rng,
+                                           bool v32 = false, bool with_bias = true)
 {
     constexpr int H = 4, G = 2, C2 = H / G;
     constexpr bool wide = std::is_same<E, float>::value;
     const double tol = wide ? 2e-5 : 2e-5 + 1.0 / 128;
-    const int shapes[][2] = {{6, 10}, {40, 64}};
+    const int narrow_shapes[][2] = {{6, 10}, {40, 64}}, wide_shapes[][2] = {{128, 128}, {65, 100}};
+    const auto &shapes = v32 ? wide_shapes : narrow_shapes;
     const int64_t R = a.rows, C = a.cols, nnz = A.nnz;
     int status = 0;
-    plan_heads(A, H);
-    plan_heads(T, H);
+    (v32 ? plan_wide : plan_heads)(A, H);
+    (v32 ? plan_wide : plan_heads)(T, H);
     // map[i]: the position in a of nonzero i of t (the stable order of transpose() above)
     std::vector<int32_t> map((size_t)nnz), at(t.rp.begin(), t.rp.end() - 1);
     for (int64_t r = 0; r < R; ++r)
@@ -550,7 +565,7 @@ template <typename E> static int bias_runs(const char *name, spmv_csr &A, spmv_c
             for (int64_t i = 0; i < (H - 1) * sb + nnz; ++i) bias[i] = bias_t[i] = NAN;
             for (int64_t i = 0; i < (H - 1) * sdb + nnz; ++i) dbias[i] = NAN;
             for (int y = 0; y < H; ++y) {
-                for (int64_t n = 0; n < nnz; ++n) bias[y * sb + n] = nd(rng);
+                for (int64_t n = 0; n < nnz; ++n) bias[y * sb + n] = with_bias ? nd(rng) : 0.0f;
                 for (int64_t i = 0; i < nnz; ++i) bias_t[y * sb + i] = bias[y * sb + map[(size_t)i]];
             }
             E *Q = as_elements<E>(hQ, H, R, k, vec, true), *K = as_elements<E>(hK, C2, C, k, vec, true), *Vm = as_elements<E>(hV, C2, C, kv, vec, true);
@@ -562,13 +577,13 @@ template <typename E> static int bias_runs(const char *name, spmv_csr &A, spmv_c
             AttnArgsT<E> f = in, bq = in, bk = in;
             const AttnBias bf{bias, sb, nullptr, 0}, bqb{bias, sb, dbias, sdb}, bkb{bias_t, sb, nullptr, 0};
             f.out0 = O, f.ld0 = hO.ld, f.h0 = hO.stride, f.stats = stats, f.hstats = sstats;
-            status |= launch_attention(kPassForward, A, f, &bf, H, G, false, "forward_bias", nullptr);
+            status |= launch_attention(kPassForward, A, f, with_bias ? &bf : nullptr, H, G, false, "forward_bias", nullptr);
             bq.O = O, bq.ldo = hO.ld, bq.ho = hO.stride, bq.dO = dO, bq.lddo = hdO.ld, bq.hdo = hdO.stride;
             bq.stats_in = stats, bq.hstats_in = sstats, bq.delta = delta, bq.hdelta = sdelta, bq.out0 = dQ, bq.ld0 = hdQ.ld, bq.h0 = hdQ.stride;
-            status |= launch_attention(kPassBackwardQ, A, bq, &bqb, H, G, false, "backward_q_bias", nullptr);
+            status |= launch_attention(kPassBackwardQ, A, bq, with_bias ? &bqb : nullptr, H, G, false, "backward_q_bias", nullptr);
             bk.dO = dO, bk.lddo = hdO.ld, bk.hdo = hdO.stride, bk.stats_in = stats, bk.hstats_in = sstats, bk.delta_in = delta, bk.hdelta_in = sdelta;
             bk.out0 = dK, bk.ld0 = hdK.ld, bk.h0 = hdK.stride, bk.out1 = dV, bk.ld1 = hdV.ld, bk.h1 = hdV.stride;
-            status |= launch_attention(kPassBackwardKV, T, bk, &bkb, H, G, true, "backward_kv_bias", nullptr);
+            status |= launch_attention(kPassBackwardKV, T, bk, with_bias ? &bkb : nullptr, H, G, true, "backward_kv_bias", nullptr);
             // serial fp64 attention with bias, per query head; dK and dV summed over the heads of a group
             double worst = 0.0;
             long unwritten = 0;
@@ -605,8 +620,10 @@ template <typename E> static int bias_runs(const char *name, spmv_csr &A, spmv_c
                     for (int n = 0; n < L; ++n) {
                         const double gb = p[n] * (dp[n] - dot), agb = p[n] * (adp[n] + adot + 1e-3);
                         const float got = dbias[y * sdb + b + n];
-                        unwritten += got != got;
-                        err(got, gb, agb);
+                        if (with_bias) {
+                            unwritten += got != got;
+                            err(got, gb, agb);
+                        }
                         for (int c = 0; c < k; ++c) {
                             rdK[(size_t)((c2 * C + a.ci[b + n]) * k + c)] += scale * gb * q[i * hQ.ld + c];
                             mK[(size_t)((c2 * C + a.ci[b + n]) * k + c)] += scale * agb * std::fabs(q[i * hQ.ld + c]);
@@ -632,13 +649,115 @@ template <typename E> static int bias_runs(const char *name, spmv_csr &A, spmv_c
                     for (int c = 0; c < k; ++c) err(elem<E>(dK, c2 * hdK.stride + j * hdK.ld + c), rdK[(size_t)((c2 * C + j) * k + c)], mK[(size_t)((c2 * C + j) * k + c)] + none);
                     for (int c = 0; c < kv; ++c) err(elem<E>(dV, c2 * hdV.stride + j * hdV.ld + c), rdV[(size_t)((c2 * C + j) * kv + c)], mV[(size_t)((c2 * C + j) * kv + c)] + none);
                 }
-            printf("bias %s heads %d group %d k %d kv %d V %d %s: status %d, worst normalised error %.3g (allowed %.3g), %ld positions of dBias unwritten\n",
-                   name, H, G, k, kv, V, odd ? "scalar path" : "vector path", status, worst, tol, unwritten);
+            printf("%s %s heads %d group %d k %d kv %d V %d %s: status %d, worst normalised error %.3g (allowed %.3g), %ld positions of dBias unwritten\n",
+                   with_bias ? "bias" : "no bias", name, H, G, k, kv, V, odd ? "scalar path" : "vector path", status, worst, tol, unwritten);
             if (!(worst <= tol) || unwritten) status |= 512;
             if constexpr (!wide)
                 for (void *p : {(void *)Q, (void *)K, (void *)Vm, (void *)dO, (void *)O, (void *)dQ, (void *)dK, (void *)dV}) free(p);
             for (void *p : {(void *)hQ.p, (void *)hK.p, (void *)hV.p, (void *)hdO.p, (void *)hO.p, (void *)hdQ.p, (void *)hdK.p, (void *)hdV.p,
                             (void *)stats, (void *)delta, (void *)bias, (void *)bias_t, (void *)dbias})
+                free(p);
+        }
+    return status;
+}
+
+// ---- V = 32 against the other geometries: zero padding ------------------------------------------------------------------------
+// Four query heads on two K/V heads with a bias at (k, kv) <= 64, both load paths: the narrow run (forward, then both backward
+// passes on its O, stats and delta), then the same operands padded with zero columns to (128, 128) through the V = 32 kernels on
+// exactly sized blocks and the wide scratch, the backward passes on the narrow run's stats and delta (and its O, padded).  delta,
+// dBias, dQ[:, :k], dK[:, :k], dV[:, :kv] bit for bit, the padded columns +0.  (The forward pass shares the bits only where every
+// expf argument is exact: T differs, and the rescale is per step.)
+static int padding_runs(spmv_csr &A, spmv_csr &T, const Pattern &a, const Pattern &t, float scale, std::mt19937 &rng)
+{
+    constexpr int H = 4, G = 2, C2 = H / G, W = 128;
+    const int shapes[][2] = {{64, 20}, {8, 40}, {16, 12}};
+    const int64_t R = a.rows, C = a.cols, nnz = A.nnz;
+    int status = 0;
+    plan_wide(A, H);
+    plan_wide(T, H);
+    std::vector<int32_t> map((size_t)nnz), at(t.rp.begin(), t.rp.end() - 1);
+    for (int64_t r = 0; r < R; ++r)
+        for (int n = a.rp[r]; n < a.rp[r + 1]; ++n) map[(size_t)at[a.ci[n]]++] = n;
+    for (auto &kk : shapes)
+        for (int odd = 0; odd < 2; ++odd) {
+            const int k = kk[0], kv = kk[1];
+            const bool vec = !odd;
+            auto ld = [&](int w) { return (int64_t)(odd ? w + 1 + ((w + 1) % 4 == 0) : (w + 3) / 4 * 4 + 4); };
+            auto make = [&](int heads, int64_t rows, int w) { return heads_matrix(heads, rows, w, ld(w), (rows * ld(w) + 3) / 4 * 4 + 8, vec); };
+            std::normal_distribution<float> nd(0.f, 1.f);
+            // n: the narrow operands; w: the same padded with zeros (inputs) or NaN-filled (outputs)
+            HeadsMatrix nQ = make(H, R, k), nK = make(C2, C, k), nV = make(C2, C, kv), ndO = make(H, R, kv), nO = make(H, R, kv),
+                        ndQ = make(H, R, k), ndK = make(C2, C, k), ndV = make(C2, C, kv);
+            HeadsMatrix wQ = make(H, R, W), wK = make(C2, C, W), wV = make(C2, C, W), wdO = make(H, R, W), wO = make(H, R, W),
+                        wdQ = make(H, R, W), wdK = make(C2, C, W), wdV = make(C2, C, W);
+            auto fill = [&](const HeadsMatrix &m, const HeadsMatrix &p, int heads, int64_t rows, int w) {
+                for (int y = 0; y < heads; ++y)
+                    for (int64_t r = 0; r < rows; ++r)
+                        for (int c = 0; c < W; ++c) {
+                            const float x = c < w ? nd(rng) : 0.0f;
+                            if (c < w) m.p[y * m.stride + r * m.ld + c] = x;
+                            p.p[y * p.stride + r * p.ld + c] = x;
+                        }
+            };
+            fill(nQ, wQ, H, R, k), fill(nK, wK, C2, C, k), fill(nV, wV, C2, C, kv), fill(ndO, wdO, H, R, kv);
+            const int64_t sstats = 2 * R + 2, sdelta = R + 3, sb = nnz + 3, sdb = nnz + 1;
+            float *stats = (float *)malloc(4 * (size_t)((H - 1) * sstats + 2 * R)), *delta = (float *)malloc(4 * (size_t)((H - 1) * sdelta + R));
+            float *wdelta = (float *)malloc(4 * (size_t)((H - 1) * sdelta + R));
+            float *bias = (float *)malloc(4 * (size_t)((H - 1) * sb + nnz)), *bias_t = (float *)malloc(4 * (size_t)((H - 1) * sb + nnz));
+            float *dbias = (float *)malloc(4 * (size_t)((H - 1) * sdb + nnz)), *wdbias = (float *)malloc(4 * (size_t)((H - 1) * sdb + nnz));
+            for (int64_t i = 0; i < (H - 1) * sb + nnz; ++i) bias[i] = bias_t[i] = NAN;
+            for (int64_t i = 0; i < (H - 1) * sdb + nnz; ++i) dbias[i] = wdbias[i] = NAN;
+            for (int y = 0; y < H; ++y) {
+                for (int64_t n = 0; n < nnz; ++n) bias[y * sb + n] = nd(rng);
+                for (int64_t i = 0; i < nnz; ++i) bias_t[y * sb + i] = bias[y * sb + map[(size_t)i]];
+            }
+            const AttnBias bf{bias, sb, nullptr, 0}, bkb{bias_t, sb, nullptr, 0};
+            auto passes = [&](int w_k, int w_kv, const HeadsMatrix &Q, const HeadsMatrix &K, const HeadsMatrix &V, const HeadsMatrix &dO,
+                              const HeadsMatrix &O, const HeadsMatrix &dQ, const HeadsMatrix &dK, const HeadsMatrix &dV, float *del, float *db,
+                              bool fwd) {
+                int lanes = 1;
+                while (4 * lanes < std::max(w_k, w_kv)) lanes *= 2;
+                g_group_lanes = lanes;
+                AttnArgs in = attn_inputs(scale, w_k, w_kv, Q, K, V);
+                AttnArgs f = in, bq = in, bk = in;
+                f.out0 = O.p, f.ld0 = O.ld, f.h0 = O.stride, f.stats = stats, f.hstats = sstats;
+                if (fwd) status |= launch_attention(kPassForward, A, f, &bf, H, G, false, "forward", nullptr);
+                const AttnBias bqb{bias, sb, db, sdb};
+                bq.O = O.p, bq.ldo = O.ld, bq.ho = O.stride, bq.dO = dO.p, bq.lddo = dO.ld, bq.hdo = dO.stride;
+                bq.stats_in = stats, bq.hstats_in = sstats, bq.delta = del, bq.hdelta = sdelta, bq.out0 = dQ.p, bq.ld0 = dQ.ld, bq.h0 = dQ.stride;
+                status |= launch_attention(kPassBackwardQ, A, bq, &bqb, H, G, false, "backward_q", nullptr);
+                bk.dO = dO.p, bk.lddo = dO.ld, bk.hdo = dO.stride, bk.stats_in = stats, bk.hstats_in = sstats, bk.delta_in = delta, bk.hdelta_in = sdelta;
+                bk.out0 = dK.p, bk.ld0 = dK.ld, bk.h0 = dK.stride, bk.out1 = dV.p, bk.ld1 = dV.ld, bk.h1 = dV.stride;
+                status |= launch_attention(kPassBackwardKV, T, bk, &bkb, H, G, true, "backward_kv", nullptr);
+            };
+            passes(k, kv, nQ, nK, nV, ndO, nO, ndQ, ndK, ndV, delta, dbias, true);
+            // the narrow O, padded, is the wide backward_q's O
+            for (int y = 0; y < H; ++y)
+                for (int64_t r = 0; r < R; ++r)
+                    for (int c = 0; c < W; ++c) wO.p[y * wO.stride + r * wO.ld + c] = c < kv ? nO.p[y * nO.stride + r * nO.ld + c] : 0.0f;
+            passes(W, W, wQ, wK, wV, wdO, wO, wdQ, wdK, wdV, wdelta, wdbias, false);
+            // bit for bit in the original columns, +0 in the padded ones
+            auto cmp = [&](const HeadsMatrix &n, const HeadsMatrix &w, int heads, int64_t rows, int width) {
+                long bad = 0;
+                const float zero = 0.0f;
+                for (int y = 0; y < heads; ++y)
+                    for (int64_t r = 0; r < rows; ++r) {
+                        bad += std::memcmp(n.p + y * n.stride + r * n.ld, w.p + y * w.stride + r * w.ld, 4 * (size_t)width) != 0;
+                        for (int c = width; c < W; ++c) bad += std::memcmp(w.p + y * w.stride + r * w.ld + c, &zero, 4) != 0;
+                    }
+                return bad;
+            };
+            long bad = cmp(ndQ, wdQ, H, R, k) + cmp(ndK, wdK, C2, C, k) + cmp(ndV, wdV, C2, C, kv);
+            for (int y = 0; y < H; ++y) {
+                bad += std::memcmp(delta + y * sdelta, wdelta + y * sdelta, 4 * (size_t)R) != 0;
+                bad += std::memcmp(dbias + y * sdb, wdbias + y * sdb, 4 * (size_t)nnz) != 0;
+            }
+            printf("zero padding (%d, %d) -> (%d, %d), V 32 against the narrow run, %s: status %d, %ld rows differ in a bit\n", k, kv, W, W,
+                   odd ? "4-byte path" : "16-byte path", status, bad);
+            if (bad) status |= 1024;
+            for (void *p : {(void *)nQ.p, (void *)nK.p, (void *)nV.p, (void *)ndO.p, (void *)nO.p, (void *)ndQ.p, (void *)ndK.p, (void *)ndV.p,
+                            (void *)wQ.p, (void *)wK.p, (void *)wV.p, (void *)wdO.p, (void *)wO.p, (void *)wdQ.p, (void *)wdK.p, (void *)wdV.p,
+                            (void *)stats, (void *)delta, (void *)wdelta, (void *)bias, (void *)bias_t, (void *)dbias, (void *)wdbias})
                 free(p);
         }
     return status;
@@ -766,8 +885,16 @@ int main()
     status |= runs16<fp16>("fp16", A, T, a, scale, rng);
     status |= bias_runs<float>("fp32", A, T, a, t, scale, rng);
     status |= bias_runs<bf16>("bf16", A, T, a, t, scale, rng);
+    // V = 32: widths above 64 on the wide scratch, with and without a bias, and against the narrow geometries by zero padding
+    for (bool with_bias : {true, false}) {
+        status |= bias_runs<float>("fp32", A, T, a, t, scale, rng, true, with_bias);
+        status |= bias_runs<bf16>("bf16", A, T, a, t, scale, rng, true, with_bias);
+    }
+    status |= padding_runs(A, T, a, t, scale, rng);
     for (void *p : owned) free(p);
     free(A.plan_attn.d_scratch.p);
     free(T.plan_attn.d_scratch.p);
+    free(A.plan_attn.d_scratch_wide.p);
+    free(T.plan_attn.d_scratch_wide.p);
     return status != 0 || !(worst <= 2e-5);
 }

@@ -12,7 +12,11 @@
 # same four heads on 16-bit matrices (bf16 and fp16, exactly sized blocks of 2-byte elements, the 8-byte and the 2-byte load path)
 # bit for bit the fp32 runs on the widened data, rounded to nearest even; and the kernels with a bias (<..., AttnBias>; fp32 and bf16, (6, 10) and
 # (40, 64), both load paths, four query heads on two K/V heads, bias, bias_t and dBias exactly sized blocks, rows in pieces on
-# the pattern and on its transpose) against a serial fp64 attention with bias.  Needs no device: a check of the kernels' logic, bounds and alignment, not of the GPU.  The kernel
+# the pattern and on its transpose) against a serial fp64 attention with bias; and the V = 32 kernels of the _wide entry points
+# ((128, 128) and (65, 100), fp32 and bf16, both load paths, with and without a bias, the same four heads, rows in pieces on both
+# handles, every matrix and the wide scratch of 260 floats per piece an exactly sized block) against the same serial fp64
+# attention, and their zero-padding property: operands of (64, 20), (8, 40) and (16, 12) padded to (128, 128) give the narrow
+# run's delta, dBias, dQ, dK and dV bit for bit and +0 in the padded columns.  Needs no device: a check of the kernels' logic, bounds and alignment, not of the GPU.  The kernel
 # files, lane_group.hpp and attention_args.hpp are copied beside the stubs so that their #include "spmv_internal.hpp" finds the stub.
 set -euo pipefail
 here=$(cd "$(dirname "$0")" && pwd)

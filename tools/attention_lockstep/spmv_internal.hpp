@@ -22,7 +22,7 @@ template <class T> struct DevPtr {       // (exactly sized heap blocks; freed by
 };
 struct SpmmPlan { bool ready = true; int n_long = 0, pieces = 0, row_cap = 512, piece_len = 512;
     DevPtr<int32_t> d_order, d_long_row, d_long_first, d_piece_k0, d_piece_len; DevPtr<float> d_partial; };
-struct AttnPlan { bool ready = false; int heads = 0; DevPtr<float> d_scratch; };
+struct AttnPlan { bool ready = false; int heads = 0; DevPtr<float> d_scratch; int wide_heads = 0; DevPtr<float> d_scratch_wide; };
 }
 struct spmv_csr { int64_t rows = 0, cols = 0, nnz = 0; const int32_t *d_row_ptr = nullptr, *d_col_idx = nullptr;
     spmv::SpmmPlan plan_spmm; spmv::AttnPlan plan_attn; };

@@ -50,6 +50,8 @@ allocates.  Nothing here sets a threshold.
 
     python tools/attention_time.py --bias [--workloads c2:8192,c2:0,c3:8192,c3:0] [--ks 16,32,64]
                                    [--out profiles/attention_bias.jsonl]
+--wide: the holder made with wide=True at k = kv = 128 (spmv_csr_attention_*_wide) against the unchanged holder at k = kv = 64
+on the same pattern arrays, float32 and 16-bit operands (wide_main).
 """
 import argparse
 import json
@@ -314,6 +316,55 @@ def dtype_main(a, emit):
         torch.cuda.empty_cache()
 
 
+def wide_main(a, emit):
+    """--wide: FusedSparseAttention(wide=True) at k = kv = 128 (spmv_csr_attention_*_wide on lane groups of 32) against the
+    unchanged FusedSparseAttention at k = kv = 64, the yardstick, on the same pattern arrays in one process, float32 and (--dtype,
+    default bf16) 16-bit operands; the windows alternate, median of --reps with the lowest and the highest kept.  A pass gathers
+    twice the bytes per nonzero at twice the width, so the expectation is a ratio of 2.0."""
+    import torch
+    pkg = ge.load_package()
+    capi, W, SA = pkg.capi, pkg.workloads, pkg.sparse_attention
+    dev = torch.device("cuda:0")
+    scales = dict((s.split("=")[0], float(s.split("=")[1])) for s in a.scale.split(",") if s)
+    dtypes = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
+    med, r4 = statistics.median, lambda x: round(x, 4)      # noqa: E731
+    for spec in (a.workloads or "c2:8192,c2:0,c3:8192,c3:0").split(","):
+        name, rows, cols, d_rp, d_ci = heads_pattern(spec.partition("@")[0], capi, W, dev, scales)
+        wide = SA.FusedSparseAttention(rows, cols, d_rp, d_ci, scale=0.125, wide=True)
+        narrow = SA.FusedSparseAttention(rows, cols, d_rp, d_ci, scale=0.125)
+        for dname in ["fp32"] + (a.dtype or "bf16").split(","):
+            sets = {}
+            for att, k in ((wide, 128), (narrow, 64)):
+                gen = torch.Generator(device=dev).manual_seed(k)
+                Q, K, V, dO = (torch.randn((n, k), generator=gen, device=dev).to(dtypes[dname]) for n in (rows, cols, cols, rows))
+                sets[att] = (Q, K, V, dO) + tuple(t.clone().requires_grad_(True) for t in (Q, K, V))
+
+            def forward(att):
+                Q, K, V = sets[att][:3]
+                with torch.no_grad():
+                    att(Q, K, V)
+
+            def step(att):
+                dO, q, kk, v = sets[att][3:]
+                att(q, kk, v).backward(dO)
+                q.grad = kk.grad = v.grad = None
+
+            w_f, n_f, it_f = timed_windows(lambda: forward(wide), lambda: forward(narrow), a.window_ms, a.reps, a.max_iters)
+            w_s, n_s, it_s = timed_windows(lambda: step(wide), lambda: step(narrow), a.window_ms, a.reps, a.max_iters)
+            emit(workload=name, dtype=dname, rows=rows, cols=cols, nnz=int(d_ci.numel()), plan=wide.A.spmm_describe(),
+                 plan_T=wide.T.spmm_describe(), iters_forward=it_f, iters_step=it_s, reps=a.reps,
+                 wide128_forward_ms=r4(med(w_f)), narrow64_forward_ms=r4(med(n_f)), forward_ratio=round(med(w_f) / med(n_f), 3),
+                 wide128_forward_windows=[r4(min(w_f)), r4(max(w_f))], narrow64_forward_windows=[r4(min(n_f)), r4(max(n_f))],
+                 wide128_step_ms=r4(med(w_s)), narrow64_step_ms=r4(med(n_s)), step_ratio=round(med(w_s) / med(n_s), 3),
+                 wide128_step_windows=[r4(min(w_s)), r4(max(w_s))], narrow64_step_windows=[r4(min(n_s)), r4(max(n_s))])
+            del sets
+            torch.cuda.empty_cache()
+        wide.close()
+        narrow.close()
+        del d_rp, d_ci
+        torch.cuda.empty_cache()
+
+
 def bias_main(a, emit):
     """The biased fused holder against the unbiased one and against the composed path with a torch add (see the module docstring)."""
     import torch
@@ -426,6 +477,7 @@ def main():
     ap.add_argument("--gqa-heads", type=int, default=16, help="query heads of the --gqa runs")
     ap.add_argument("--dtype", default=None, help="bf16[,fp16]: time 16-bit operands against float32 ones on the fused passes")
     ap.add_argument("--bias", action="store_true", help="time FusedSparseAttention(bias=True) against the unbiased and the composed path")
+    ap.add_argument("--wide", action="store_true", help="time FusedSparseAttention(wide=True) at k = kv = 128 against the unchanged holder at 64")
     ap.add_argument("--scale", default="", help="name=fraction of the rows, e.g. c4=0.5 where the memory does not hold the full size")
     ap.add_argument("--window-ms", type=float, default=200.0)
     ap.add_argument("--max-iters", type=int, default=50)
@@ -448,6 +500,9 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if a.wide:
+        wide_main(a, emit)
+        return
     if a.bias:
         a.ks = a.ks or "16,32,64"
         bias_main(a, emit)
