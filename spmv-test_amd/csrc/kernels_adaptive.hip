@@ -309,17 +309,67 @@ struct ChunkShared {
     int long_count, huge_count;
 };
 
+// acc + the acc of lane + O of the same 16-lane DPP row, in the lanes whose lane + O lies in the row (the others add 0): a row
+// shift in the vector unit, v_add_f32_dpp row_shl:O.  __shfl_down is ds_bpermute_b32 -- an address, a trip through the LDS
+// crossbar and a wait -- per step.
+template <int O>
+__device__ __forceinline__ float add_row_shl(float acc)
+{
+    return acc + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0x100 + O, 0xf, 0xf, true));
+}
+
+// Lane 0 of every kGroup-lane group ends with the tree acc += acc[lane + 8], [lane + 4], [lane + 2], [lane + 1]; what the
+// other lanes end with is not used.  Lane 0's tree reads lanes 0..15 of its own group only, and the groups of a wave are
+// active or idle as a whole, so no source lane of it is ever disabled.  LEAN: the same tree with __shfl_down.
+template <bool LEAN>
+__device__ __forceinline__ float group_tree(float acc)
+{
+    if constexpr (!LEAN) {
+        static_assert(kGroup == 16, "the DPP tree takes a lane group to be one DPP row (SPMV_T_GROUP is a build knob)");
+        acc = add_row_shl<8>(acc);
+        acc = add_row_shl<4>(acc);
+        acc = add_row_shl<2>(acc);
+        return add_row_shl<1>(acc);
+    } else {
+#pragma unroll
+        for (int o = kGroup / 2; o > 0; o >>= 1) acc += __shfl_down(acc, o, kGroup);
+        return acc;
+    }
+}
+
+// Words a lane reads ahead of its adds in the row sums.  The reads behind a segment's last word are not clamped: they stay
+// inside the workgroup's LDS region, which is kReadAhead words longer than the padded products at every workgroup size, and
+// what they return is replaced by +0 before it is added (no partial sum here is ever -0 -- each starts from +0 -- so adding +0
+// changes no bit).  The clamped and predicated form gave the same bits and cost a v_min and a v_add per word.
+constexpr int kLongBatch = 4;    // words per lane and trip of a kGroup-lane group (A/B: 2 and 8 were no faster)
+constexpr int kShortBatch = 16;  // words of a short segment in flight
+constexpr int kReadAhead = (kLongBatch - 1) * kGroup > 4 ? (kLongBatch - 1) * kGroup : 4;
+static_assert(region_words(256) >= prod_words(256) + kReadAhead && region_words(512) >= prod_words(512) + kReadAhead &&
+                  region_words(1024) >= prod_words(1024) + kReadAhead,
+              "the unclamped reads of the row sums stay inside the LDS region");
+
 // The row reduction of one chunk, products already staged in `smem` (a barrier behind them):
 //   short segments (<= kShortSeg): one lane each, sequential (the oracle's order);
-//   17..kHugeSeg: queued in LDS with their bounds, summed by kGroup-lane groups (__shfl_down tree);
+//   longer ones up to kHugeSeg: queued in LDS with their bounds, summed by kGroup-lane groups: lane l adds the padded words
+//     l, l + 16, .. of the segment from +0, then the tree of group_tree;
 //   longer (a power-law row can fill the chunk): one wavefront each.
+// The order of every sum is fixed (tests/_tiled_order.py states it in numpy); how the LDS reads are issued is not part of it:
+// a lane reads a batch of words and then adds them, so that one LDS latency is waited for per batch and not per word.
 // PREF: this lane's first row bounds were prefetched into rb0/re0.
+// LEAN: 0 all of that; 1 the short segments keep their one-batch-at-a-time loop (the 16-bit body with block lists: it
+// spills 20 bytes as it is and the read-ahead made that 28 to 36); 2 also the long loop one word at a time and the
+// __shfl_down tree (the persistent forms, whose registers hold the next chunk's stream through the row sums: 20 -> 36 bytes
+// of scratch otherwise).  profiles/tiled_rowsums_resources.md
 // (Round 3, tried and dropped: summing the segments longer than kHugeSeg from the products every lane still holds in
 // registers, by all wavefronts at once instead of one wavefront per segment reading LDS.  Slower on power-law rows -- c3 band
 // 8192 0.2409 ms against 0.2309, a chunk holds up to 16 such segments and every lane then runs 16 compare-and-adds per
 // segment -- and its 2 KiB of partials pushed the 1024-thread workgroup from two per CU to one (band 65 536: 0.49 -> 0.67 ms):
 // the static LDS beside the region is budgeted to the last half KiB.  profiles/r03_huge_segments_from_registers_ab.jsonl)
-template <int BLOCK, bool PREF>
+// (Tried and dropped with the read-ahead, profiles/tiled_rowsums_ab.jsonl: the queue entry of the next round read under this
+// round's sums and two pairs in flight in the wavefront loop -- both within 0.2 % at c4 and c3; the bounds of a lane's second
+// segment prefetched with the stream -- even packed into one more register the 16-bit body then spills 20 bytes, and with
+// that spill it ran 8 % slower.)
+template <int BLOCK, bool PREF, int LEAN = 0>
 __device__ __forceinline__ void reduce_chunk(const float *smem, ChunkShared<BLOCK> &sh, int tid, int c, int lb0, int m,
                                              int64_t base, int64_t lim, const int32_t *__restrict__ row_ptr,
                                              float *__restrict__ y, float *__restrict__ carry, int32_t rb0, int32_t re0)
@@ -333,13 +383,41 @@ __device__ __forceinline__ void reduce_chunk(const float *smem, ChunkShared<BLOC
         if (g.e - g.s <= kShortSeg) {
             float acc = 0.0f;
             const float *w = smem + ps;
-            int i = 0;
             const int n = pe - ps;
-            for (; i + 3 < n; i += 4) {
-                const float a0 = w[i], a1 = w[i + 1], a2 = w[i + 2], a3 = w[i + 3];
-                acc = (((acc + a0) + a1) + a2) + a3;
+            if constexpr (LEAN == 0) {
+                // left to right from +0: the whole fours, kShortBatch words read before the first of them is added, then
+                // the one to three words behind them
+                static_assert(kShortSeg <= 32 && kShortBatch % 4 == 0, "a short segment crosses one pad word at most");
+                constexpr int kWords = (kShortSeg + 1) & ~3;   // n <= kShortSeg + 1: the whole fours end here
+                const int nt = n & ~3;
+#pragma unroll
+                for (int i0 = 0; i0 < kWords; i0 += kShortBatch) {
+                    if (i0 < nt) {
+                        float b[kShortBatch];
+#pragma unroll
+                        for (int i = 0; i < kShortBatch; i += 4)
+                            if (i == 0 || i0 + i < nt) {
+#pragma unroll
+                                for (int q = 0; q < 4; ++q) b[i + q] = w[i0 + i + q];
+                            }
+#pragma unroll
+                        for (int i = 0; i < kShortBatch; i += 4)
+                            if (i == 0 || i0 + i < nt) acc = (((acc + b[i]) + b[i + 1]) + b[i + 2]) + b[i + 3];
+                    }
+                }
+                const float *wt = w + nt;
+                const float t0 = wt[0], t1 = wt[1], t2 = wt[2];
+                acc += nt < n ? t0 : 0.0f;
+                acc += nt + 1 < n ? t1 : 0.0f;
+                acc += nt + 2 < n ? t2 : 0.0f;
+            } else {
+                int i = 0;
+                for (; i + 3 < n; i += 4) {
+                    const float a0 = w[i], a1 = w[i + 1], a2 = w[i + 2], a3 = w[i + 3];
+                    acc = (((acc + a0) + a1) + a2) + a3;
+                }
+                for (; i < n; ++i) acc += w[i];
             }
-            for (; i < n; ++i) acc += w[i];
             *g.dst = acc;
         } else if (g.e - g.s <= kHugeSeg) {
             const int slot = atomicAdd(&sh.long_count, 1);
@@ -357,9 +435,19 @@ __device__ __forceinline__ void reduce_chunk(const float *smem, ChunkShared<BLOC
         const int2 q = sh.long_seg[i];
         const int qe = (int)((unsigned)q.y >> 16);
         float acc = 0.0f;
-        for (int k = (q.y & 0xffff) + sub; k < qe; k += kGroup) acc += smem[k];
+        if constexpr (LEAN < 2) {
+            for (int k = (q.y & 0xffff) + sub; k < qe; k += kLongBatch * kGroup) {
+                float v[kLongBatch];
 #pragma unroll
-        for (int o = kGroup / 2; o > 0; o >>= 1) acc += __shfl_down(acc, o, kGroup);
+                for (int j = 0; j < kLongBatch; ++j) v[j] = smem[k + j * kGroup];
+                acc += v[0];
+#pragma unroll
+                for (int j = 1; j < kLongBatch; ++j) acc += k + j * kGroup < qe ? v[j] : 0.0f;
+            }
+        } else {
+            for (int k = (q.y & 0xffff) + sub; k < qe; k += kGroup) acc += smem[k];
+        }
+        acc = group_tree<LEAN == 2>(acc);
         if (sub == 0) {
             if (q.x == 0) carry[c] = acc;
             else y[(int64_t)lb0 + q.x - 1] = acc;
@@ -382,8 +470,15 @@ __device__ __forceinline__ void reduce_chunk(const float *smem, ChunkShared<BLOC
         }
         if (k < qe) a0 += smem[k];
         float acc = a0 + a1;
+        // the steps 32 and 16 cross DPP rows; after them lanes 0..15 hold what lane 0's steps 8..1 read
+        acc += __shfl_down(acc, 32, kWave);
+        acc += __shfl_down(acc, 16, kWave);
+        if constexpr (LEAN < 2) {
+            acc = group_tree<false>(acc);
+        } else {
 #pragma unroll
-        for (int o = kWave / 2; o > 0; o >>= 1) acc += __shfl_down(acc, o, kWave);
+            for (int o = 8; o > 0; o >>= 1) acc += __shfl_down(acc, o, kWave);
+        }
         if (lane == 0) {
             if (q.x == 0) carry[c] = acc;
             else y[(int64_t)lb0 + q.x - 1] = acc;
@@ -630,7 +725,8 @@ __device__ __forceinline__ void adaptive_body(float *smem, ChunkShared<BLOCK> &s
         __syncthreads();
 
         // ---- rows of this chunk
-        reduce_chunk<BLOCK, !TILED>(smem, sh, tid, c, lb0, m, base, lim, row_ptr, y, carry, rb0, re0);
+        // (the persistent form has no register for the read-ahead of the row sums: LEAN = 2)
+        reduce_chunk<BLOCK, !TILED, PERSIST ? 2 : 0>(smem, sh, tid, c, lb0, m, base, lim, row_ptr, y, carry, rb0, re0);
 
         if (!more) break;
         __syncthreads();  // the region and the queues are reused by the next chunk
@@ -771,7 +867,7 @@ __device__ __forceinline__ void tiled16_body(float *smem, ChunkShared<BLOCK> &sh
 #ifdef SPMV_T_NOREDUCE  // (A/B builds only: the kernel without its row sums -- results are wrong)
     if (tid <= m && rb0 == 0x7fffffff) y[lb0 + tid] = smem[tid] + (float)re0;
 #else
-    reduce_chunk<BLOCK, true>(smem, sh, tid, c, lb0, m, base, lim, row_ptr, y, carry, rb0, re0);
+    reduce_chunk<BLOCK, true, BLOCKS ? 1 : 0>(smem, sh, tid, c, lb0, m, base, lim, row_ptr, y, carry, rb0, re0);
 #endif
 }
 
