@@ -264,6 +264,7 @@ SPMV_API int64_t spmv_csr_transpose_map_bytes(const spmv_csr_t *t);
  *   spmv_csr_spmm                             rows x lanes per row < 2^32 (one launch): any handle up to k = 8,
  *                                             rows < 2^30 up to k = 16, < 2^29 up to k = 32, < 2^28 up to k = 64
  *   spmv_csr_sddmm                            the same as spmv_csr_spmm (rows x lanes per row < 2^32); any nnz < 2^31
+ *   spmv_csr_spmm_16, spmv_csr_sddmm_16       the same as spmv_csr_spmm and spmv_csr_sddmm (the lanes per row are those of k)
  *   spmv_csr_row_softmax                      any handle (rows, nnz < 2^31; a wavefront per 64 rows, byte offsets 64-bit)
  *   spmv_csr_row_softmax_backward             the same as spmv_csr_row_softmax
  *   spmv_csr_attention_forward, _backward_q,  the same as spmv_csr_spmm with max(k, kv) in the place of k (rows x lanes per
@@ -625,6 +626,39 @@ SPMV_API int spmv_csr_attention_backward_kv_16(spmv_csr_t *t, const spmv_attn_he
                                                const void *d_V, int64_t ldv, const void *d_dO, int64_t lddo,
                                                const float *d_stats, const float *d_delta, void *d_dK, int64_t lddk,
                                                void *d_dV, int64_t lddv, void *stream);
+
+/* ---- SpMM and SDDMM on 16-bit matrices: bf16 or fp16 dense operands, fp32 values and sums ------------------------------------
+ * spmv_csr_spmm and spmv_csr_sddmm with the dense matrices stored as bf16 (dtype = SPMV_ATTN_BF16) or IEEE half
+ * (SPMV_ATTN_FP16), the enum of the _16 attention calls: X and Y of spmv_csr_spmm_16, U and X of spmv_csr_sddmm_16, all of one
+ * dtype.  The handle's vals (the master weights of a layer), d_out (the gradient of those values) and the scratch of the long
+ * rows stay fp32.  SPMV_ATTN_FP32 is refused here: the fp32 calls are spmv_csr_spmm and spmv_csr_sddmm.
+ * Units: every ld counts ELEMENTS of the dtype (2 bytes).
+ * The rounding contract (part of the interface, beside the order of the sums under "SpMM" and "SDDMM").  An operand element
+ * is widened exactly to fp32 where it enters an fma; every accumulator, every partial of a long row and every butterfly is
+ * the fp32 order stated there, unchanged; an element of Y is rounded to the dtype once, to nearest even, at its store (a long
+ * row's after its pieces' fp32 partials are added in piece order).  Nothing is accumulated in 16 bits and vals is never
+ * rounded.
+ *   SpMM.   Every element of Y is, bit for bit, the round-to-nearest-even conversion to the dtype of what spmv_csr_spmm
+ *           writes for the same handle on X widened to fp32.  Batch invariance carries over: a column's bits do not depend
+ *           on k, ldx, ldy, its position in the batch or the other columns.  Y at columns >= k is never written; X at
+ *           columns >= k is never read into a sum.
+ *   SDDMM.  d_out holds the bits of spmv_csr_sddmm on U and X widened to fp32.  The symmetry with the transposed handle
+ *           carries over: T.sddmm_16(X, U) is A.sddmm_16(U, X) through the transpose's permutation, bit for bit.
+ *   Conversions.  No conversion flushes a subnormal; a NaN is stored as a NaN of the dtype (payload unspecified); fp16
+ *           overflows to +-Inf as round-to-nearest-even says.
+ * The plan is spmv_csr_spmm_plan's, unchanged, with the same bytes (spmv_csr_spmm_plan_bytes); SPMV_ERR_NOT_PLANNED without it.
+ * After the plan the calls allocate nothing and never wait: graph-capturable.
+ * Loads and stores: a lane's slice is 4 elements, 8 bytes.  With every ld of the call a multiple of 4 it is one 8-byte access
+ * (the last slice of a k that is no multiple of 4 is read whole inside its row's ld elements and stored below k only);
+ * otherwise the kernels use 2-byte accesses of the columns below k only.
+ * Limits: 1 <= k <= 64, every ld >= k, rows x lanes per row < 2^32 ("Limits of the layouts" above).
+ * Refusals (SPMV_ERR_INVALID, a message that names the function, nothing launched, every output untouched): a dtype other
+ * than the two; a matrix that is not 8-byte aligned; and everything the fp32 call refuses: a null handle, k or an ld out of
+ * range, a missing pointer (with the fp32 call's exceptions for empty dimensions), another current device, d_out not 4-byte
+ * aligned. */
+SPMV_API int spmv_csr_spmm_16(spmv_csr_t *h, int dtype, int k, const void *d_X, int64_t ldx, void *d_Y, int64_t ldy, void *stream);
+SPMV_API int spmv_csr_sddmm_16(spmv_csr_t *h, int dtype, int k, const void *d_U, int64_t ldu, const void *d_X, int64_t ldx,
+                               float *d_out, void *stream);
 
 /* ---- Fused attention with an additive bias per nonzero, and the bias's gradient: all three passes ---------------------------
  * O = softmax_rows(scale * Q K^T + B at the pattern) V with one fp32 number per (query, key) pair of the pattern: a

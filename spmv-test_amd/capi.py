@@ -66,6 +66,9 @@ SIGNATURES = {
     "spmv_csr_spmm_plan_bytes": (C.c_int64, [_H]),
     "spmv_csr_spmm_describe": (C.c_int, [_H, C.c_char_p, C.c_int]),
     "spmv_csr_sddmm": (C.c_int, [_H, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, _f32p, _vp]),
+    # the 16-bit calls: `int dtype` after the handle, every dense matrix a void *
+    "spmv_csr_spmm_16": (C.c_int, [_H, C.c_int, C.c_int, _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "spmv_csr_sddmm_16": (C.c_int, [_H, C.c_int, C.c_int, _vp, C.c_int64, _vp, C.c_int64, _f32p, _vp]),
     "spmv_csr_row_softmax": (C.c_int, [_H, C.c_float, _f32p, _f32p, _vp]),
     "spmv_csr_row_softmax_backward": (C.c_int, [_H, C.c_float, _f32p, _f32p, _f32p, _vp]),
     "spmv_csr_attention_plan": (C.c_int, [_H, _vp]),
@@ -313,17 +316,33 @@ class CsrMatrix:
         """The plan of spmv_csr_spmm (a function of row_ptr; reads it back and waits for the stream once)."""
         check(lib().spmv_csr_spmm_plan(self._h, _stream_handle(stream)))
 
-    def spmm(self, X, Y, stream=None) -> None:
-        """Enqueue Y[:, :k] = A X with k = X.shape[1].  X: (cols, k) and Y: (rows, k or more) 2-D float32 device tensors
-        with stride(1) == 1; the leading dimensions are their stride(0).  Y's columns from k on are not written."""
+    @staticmethod
+    def _dense_dtype(what: str, **matrices) -> int:
+        """The ATTN_* dtype of a call's dense matrices: 2-D tensors with stride(1) == 1, all float32, all bfloat16 or all
+        float16 (the first decides; any other dtype, or a partner of another one, is a ValueError that names the matrix)."""
         import torch
-        for name, t in (("X", X), ("Y", Y)):
-            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1:
-                raise ValueError(f"spmm: {name} must be a 2-D float32 tensor with stride(1) == 1")
+        codes = {torch.float32: ATTN_FP32, torch.bfloat16: ATTN_BF16, torch.float16: ATTN_FP16}
+        first = next(iter(matrices.values()))
+        want = first.dtype if isinstance(first, torch.Tensor) and first.dtype in codes else torch.float32
+        for name, t in matrices.items():
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != want or t.stride(1) != 1:
+                kind = "float32" if want == torch.float32 else f"{want} (as {next(iter(matrices))})"
+                raise ValueError(f"{what}: {name} must be a 2-D {kind} tensor with stride(1) == 1")
+        return codes[want]
+
+    def spmm(self, X, Y, stream=None) -> None:
+        """Enqueue Y[:, :k] = A X with k = X.shape[1].  X: (cols, k) and Y: (rows, k or more) 2-D device tensors with
+        stride(1) == 1, both float32 (spmv_csr_spmm) or both bfloat16 or float16 (spmv_csr_spmm_16: fp32 values and sums,
+        Y rounded once at its store); the leading dimensions are their stride(0), in elements.  Y's columns from k on are
+        not written."""
+        dtype = self._dense_dtype("spmm", X=X, Y=Y)
         k = X.shape[1]
         if X.shape[0] != self.cols or Y.shape[0] != self.rows or Y.shape[1] < k:
             raise ValueError(f"spmm: X {tuple(X.shape)} and Y {tuple(Y.shape)} do not fit a {self.rows} x {self.cols} matrix")
-        check(lib().spmv_csr_spmm(self._h, k, _ptr(X), X.stride(0), _ptr(Y), Y.stride(0), _stream_handle(stream)))
+        if dtype == ATTN_FP32:
+            check(lib().spmv_csr_spmm(self._h, k, _ptr(X), X.stride(0), _ptr(Y), Y.stride(0), _stream_handle(stream)))
+        else:
+            check(lib().spmv_csr_spmm_16(self._h, dtype, k, _ptr(X), X.stride(0), _ptr(Y), Y.stride(0), _stream_handle(stream)))
 
     def spmm_describe(self) -> str:
         buf = C.create_string_buffer(256)
@@ -339,20 +358,23 @@ class CsrMatrix:
     # -- SDDMM: U X^T sampled at the pattern (spmv_csr_sddmm; the plan is spmm_plan's) ------------------------------
     def sddmm(self, U, X, out, stream=None) -> None:
         """Enqueue out[n] = U[row(n), :k] . X[col(n), :k] for every stored nonzero n, k = U.shape[1] = X.shape[1].
-        U: (rows, k) and X: (cols, k) 2-D float32 device tensors with stride(1) == 1 (the leading dimensions are their
-        stride(0)); out: nnz float32, contiguous, in this matrix's storage order."""
+        U: (rows, k) and X: (cols, k) 2-D device tensors with stride(1) == 1, both float32 (spmv_csr_sddmm) or both
+        bfloat16 or float16 (spmv_csr_sddmm_16: widened exactly, the fp32 call's sums); the leading dimensions are their
+        stride(0), in elements; out: nnz float32 whatever U and X are, contiguous, in this matrix's storage order."""
         import torch
-        for name, t in (("U", U), ("X", X)):
-            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1:
-                raise ValueError(f"sddmm: {name} must be a 2-D float32 tensor with stride(1) == 1")
+        dtype = self._dense_dtype("sddmm", U=U, X=X)
         if not isinstance(out, torch.Tensor) or out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous():
             raise ValueError("sddmm: out must be a contiguous 1-D float32 tensor")
         k = U.shape[1]
         if U.shape[0] != self.rows or X.shape[0] != self.cols or X.shape[1] != k or out.shape[0] != self.nnz:
             raise ValueError(f"sddmm: U {tuple(U.shape)}, X {tuple(X.shape)} and out {tuple(out.shape)} do not fit a "
                              f"{self.rows} x {self.cols} matrix with {self.nnz} nonzeros")
-        check(lib().spmv_csr_sddmm(self._h, k, _ptr(U), U.stride(0), _ptr(X), X.stride(0), _ptr(out),
-                                   _stream_handle(stream)))
+        if dtype == ATTN_FP32:
+            check(lib().spmv_csr_sddmm(self._h, k, _ptr(U), U.stride(0), _ptr(X), X.stride(0), _ptr(out),
+                                       _stream_handle(stream)))
+        else:
+            check(lib().spmv_csr_sddmm_16(self._h, dtype, k, _ptr(U), U.stride(0), _ptr(X), X.stride(0), _ptr(out),
+                                          _stream_handle(stream)))
 
     # -- row softmax over the pattern and its backward (spmv_csr_row_softmax; the plan is spmm_plan's) ---------------
     def _nnz_arrays(self, what: str, **arrays) -> None:

@@ -637,6 +637,63 @@ int spmv_csr_sddmm(spmv_csr_t *h, int k, const float *d_U, int64_t ldu, const fl
     return launch_sddmm(*h, k, d_U, ldu, d_X, ldx, d_out, (hipStream_t)stream);
 }
 
+// ---- the same two products on 16-bit matrices (bf16 or fp16 storage; vals, out and every sum fp32) ------------------------
+static int attention_dtype(int dtype, const char *what);      // SPMV_ATTN_BF16 or SPMV_ATTN_FP16, or `what`'s refusal (below)
+static bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+
+int spmv_csr_spmm_16(spmv_csr_t *h, int dtype, int k, const void *d_X, int64_t ldx, void *d_Y, int64_t ldy, void *stream)
+{
+    const char *what = "spmv_csr_spmm_16";
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (int rc = attention_dtype(dtype, what)) return rc;
+    if (k < 1 || k > 64 || ldx < k || ldy < k) {
+        set_error("%s: k = %d, ldx = %lld, ldy = %lld (need 1 <= k <= 64, ldx >= k, ldy >= k)", what, k, (long long)ldx, (long long)ldy);
+        return SPMV_ERR_INVALID;
+    }
+    if ((!d_X && h->cols > 0) || (!d_Y && h->rows > 0)) { set_error("%s: null X or Y", what); return SPMV_ERR_INVALID; }
+    if (!aligned8(d_X) || !aligned8(d_Y)) { set_error("%s: X and Y must be 8-byte aligned", what); return SPMV_ERR_INVALID; }
+    if (ldx > INT64_MAX / 2 / (h->cols > 0 ? h->cols : 1) || ldy > INT64_MAX / 2 / (h->rows > 0 ? h->rows : 1)) {
+        set_error("%s: ldx = %lld or ldy = %lld overflows 64-bit byte offsets", what, (long long)ldx, (long long)ldy);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(h->device, what)) return rc;
+    if (!h->plan_spmm.ready) { set_error("%s used before spmv_csr_spmm_plan", what); return SPMV_ERR_NOT_PLANNED; }
+    auto run = [&](auto e) {
+        using E = decltype(e);
+        return launch_spmm(*h, k, (const E *)d_X, ldx, (E *)d_Y, ldy, (hipStream_t)stream);
+    };
+    return dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+}
+
+int spmv_csr_sddmm_16(spmv_csr_t *h, int dtype, int k, const void *d_U, int64_t ldu, const void *d_X, int64_t ldx, float *d_out,
+                      void *stream)
+{
+    const char *what = "spmv_csr_sddmm_16";
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (int rc = attention_dtype(dtype, what)) return rc;
+    if (k < 1 || k > 64 || ldu < k || ldx < k) {
+        set_error("%s: k = %d, ldu = %lld, ldx = %lld (need 1 <= k <= 64, ldu >= k, ldx >= k)", what, k, (long long)ldu, (long long)ldx);
+        return SPMV_ERR_INVALID;
+    }
+    if ((!d_U && h->rows > 0) || (!d_X && h->cols > 0) || (!d_out && h->nnz > 0)) {
+        set_error("%s: null U, X or out", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (!aligned8(d_U) || !aligned8(d_X)) { set_error("%s: U and X must be 8-byte aligned", what); return SPMV_ERR_INVALID; }
+    if (reinterpret_cast<uintptr_t>(d_out) % 4 != 0) { set_error("%s: out must be 4-byte aligned", what); return SPMV_ERR_INVALID; }
+    if (ldu > INT64_MAX / 2 / (h->rows > 0 ? h->rows : 1) || ldx > INT64_MAX / 2 / (h->cols > 0 ? h->cols : 1)) {
+        set_error("%s: ldu = %lld or ldx = %lld overflows 64-bit byte offsets", what, (long long)ldu, (long long)ldx);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(h->device, what)) return rc;
+    if (!h->plan_spmm.ready) { set_error("%s used before spmv_csr_spmm_plan", what); return SPMV_ERR_NOT_PLANNED; }
+    auto run = [&](auto e) {
+        using E = decltype(e);
+        return launch_sddmm(*h, k, (const E *)d_U, ldu, (const E *)d_X, ldx, d_out, (hipStream_t)stream);
+    };
+    return dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+}
+
 // what spmv_csr_row_softmax and its backward check alike: a finite scale; with nnz > 0 every array present and 4-byte
 // aligned; the handle's device current; the SpMM plan made
 static int softmax_args(const spmv_csr_t *h, float scale, const void *const *arrays, int n_arrays, const char *what)

@@ -12,6 +12,12 @@
 // the xor butterfly as reduce_scatter).  Nothing depends on ldu, ldx, the load path, the nonzero's position in its row,
 // the row's length, the pieces or other rows; and fma(u, x, p) == fma(x, u, p), so the operands may trade places
 // (T.sddmm(X, U) on the transposed pattern).
+//
+// Element types.  Every kernel here takes the element type E of U and X as its last template argument: float
+// (spmv_csr_sddmm) or 16-bit storage (bf16, fp16: spmv_csr_sddmm_16).  With 16-bit E the row's U slice is widened once
+// (load_wide) and stays in registers as floats, a step's gathered X slices wait packed as loaded (slice_t<E>) and are
+// widened exactly where dot_partial multiplies them, and every operation above is the same fp32 operation: out, which is
+// float always, holds the bits of the fp32 call on the widened operands.
 #include "lane_group.hpp"
 
 namespace spmv {
@@ -20,9 +26,9 @@ namespace {
 
 // the results of the nonzeros [b, e) of the group's row (or piece), whose U slice is u.  All lanes of a group call it
 // with the same b, e; lanes with c0 >= k load nothing and contribute +0 (their shuffles still run).
-template <int V, bool VEC>
+template <int V, bool VEC, typename E>
 __device__ __forceinline__ void sddmm_span(int lane, int64_t b, int64_t e, float4 u, const int32_t *__restrict__ col_idx,
-                                           const float *__restrict__ X, int64_t ldx, float *__restrict__ out, int c0, int k)
+                                           const E *__restrict__ X, int64_t ldx, float *__restrict__ out, int c0, int k)
 {
     constexpr int T = LaneGeom<V>::T, L = LaneGeom<V>::L;
     const int sub = lane & (V - 1), gbase = lane & ~(V - 1);
@@ -30,12 +36,12 @@ __device__ __forceinline__ void sddmm_span(int lane, int64_t b, int64_t e, float
     for (int64_t kb = b; kb < e; kb += T) {
         int32_t c[L], ct[T];
         group_columns<V, T>(kb, e, sub, gbase, col_idx, c, ct);
-        float4 xt[T];
+        slice_t<E> xt[T];
         float p[T];
 #pragma unroll
-        for (int t = 0; t < T; ++t) xt[t] = (n1 > 0 && kb + t < e) ? load_slice<VEC>(X, ldx, ct[t], c0, k) : zero4();
+        for (int t = 0; t < T; ++t) xt[t] = (n1 > 0 && kb + t < e) ? load_slice<VEC>(X, ldx, ct[t], c0, k) : zero_slice<E>();
 #pragma unroll
-        for (int t = 0; t < T; ++t) p[t] = dot_partial(u, xt[t], n1);
+        for (int t = 0; t < T; ++t) p[t] = dot_partial(u, widen_again<E>(xt[t]), n1);    // (no slice widened before its turn)
         reduce_scatter<V, T>(p, sub);
 #pragma unroll
         for (int i = 0; i < L; ++i) {
@@ -45,32 +51,33 @@ __device__ __forceinline__ void sddmm_span(int lane, int64_t b, int64_t e, float
     }
 }
 
-// the operands of a launch (by value)
+// the operands of a launch (by value); E: the element type of U and X, whose ld count elements of E
+template <typename E>
 struct SddmmArgs {
-    const float *U;
+    const E *U;
     int64_t ldu;
-    const float *X;
+    const E *X;
     int64_t ldx;
     float *out;
     int k;
 };
 
 // a group of V lanes per row; rows of more than row_cap nonzeros are left to the pieces
-template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_sddmm_rows(GroupRows g, SddmmArgs a)
+template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) void k_sddmm_rows(GroupRows g, SddmmArgs<E> a)
 {
     const int lane = threadIdx.x & (kWave - 1), c0 = 4 * (lane & (V - 1));
     const int64_t r = group_row<V>(g);
     if (r < 0) return;
     const int64_t b = g.row_ptr[r], e = g.row_ptr[r + 1];
     if (e == b || e - b > g.row_cap) return;   // (the U row of an empty row is not even loaded)
-    const float4 u = c0 < a.k ? load_slice<VEC>(a.U, a.ldu, r, c0, a.k) : zero4();
-    sddmm_span<V, VEC>(lane, b, e, u, g.col_idx, a.X, a.ldx, a.out, c0, a.k);
+    const float4 u = c0 < a.k ? load_wide<VEC>(a.U, a.ldu, r, c0, a.k) : zero4();
+    sddmm_span<V, VEC, E>(lane, b, e, u, g.col_idx, a.X, a.ldx, a.out, c0, a.k);
 }
 
 // a group of V lanes per piece of a long row
-template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_sddmm_pieces(GroupPieces g, SddmmArgs a)
+template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) void k_sddmm_pieces(GroupPieces g, SddmmArgs<E> a)
 {
     const int lane = threadIdx.x & (kWave - 1), c0 = 4 * (lane & (V - 1));
     int lo;
@@ -78,22 +85,34 @@ __global__ __launch_bounds__(kBlock) void k_sddmm_pieces(GroupPieces g, SddmmArg
     if (p < 0) return;
     const int64_t r = g.long_row[lo];
     const int64_t b = g.piece_k0[p], e = b + g.piece_len[p];
-    const float4 u = c0 < a.k ? load_slice<VEC>(a.U, a.ldu, r, c0, a.k) : zero4();
-    sddmm_span<V, VEC>(lane, b, e, u, g.col_idx, a.X, a.ldx, a.out, c0, a.k);
+    const float4 u = c0 < a.k ? load_wide<VEC>(a.U, a.ldu, r, c0, a.k) : zero4();
+    sddmm_span<V, VEC, E>(lane, b, e, u, g.col_idx, a.X, a.ldx, a.out, c0, a.k);
 }
 
-template <int V, bool VEC>
-int launch_sddmm_v(const spmv_csr &h, const SddmmArgs &a, hipStream_t s)
+template <int V, bool VEC, typename E>
+int launch_sddmm_v(const spmv_csr &h, const SddmmArgs<E> &a, hipStream_t s)
 {
-    const int64_t nblocks = group_row_blocks("spmv_csr_sddmm", h, V);
+    const int64_t nblocks = group_row_blocks(kIs16<E> ? "spmv_csr_sddmm_16" : "spmv_csr_sddmm", h, V);
     if (nblocks < 0) return SPMV_ERR_INVALID;
-    hipLaunchKernelGGL((k_sddmm_rows<V, VEC>), dim3((unsigned)nblocks), dim3(kBlock), 0, s, group_rows(h, V, nblocks), a);
+    hipLaunchKernelGGL((k_sddmm_rows<V, VEC, E>), dim3((unsigned)nblocks), dim3(kBlock), 0, s, group_rows(h, V, nblocks), a);
     SPMV_LAUNCHED("k_sddmm_rows");
     if (!h.plan_spmm.n_long) return SPMV_OK;
-    hipLaunchKernelGGL((k_sddmm_pieces<V, VEC>), group_grid(h.plan_spmm.pieces, V), dim3(kBlock), 0, s,
+    hipLaunchKernelGGL((k_sddmm_pieces<V, VEC, E>), group_grid(h.plan_spmm.pieces, V), dim3(kBlock), 0, s,
                        group_pieces(h, nullptr), a);
     SPMV_LAUNCHED("k_sddmm_pieces");
     return SPMV_OK;
+}
+
+template <typename E>
+int launch_sddmm_e(const spmv_csr &h, int k, const E *U, int64_t ldu, const E *X, int64_t ldx, float *out, hipStream_t s)
+{
+    if (h.rows == 0 || h.nnz == 0) return SPMV_OK;
+    const SddmmArgs<E> a{U, ldu, X, ldx, out, k};
+    const bool vec = ldu % 4 == 0 && ldx % 4 == 0;
+    return dispatch_lanes((k + 3) / 4, [&](auto v) {
+        constexpr int V = decltype(v)::value;
+        return vec ? launch_sddmm_v<V, true, E>(h, a, s) : launch_sddmm_v<V, false, E>(h, a, s);
+    });
 }
 
 }  // namespace
@@ -101,13 +120,18 @@ int launch_sddmm_v(const spmv_csr &h, const SddmmArgs &a, hipStream_t s)
 // arguments checked by spmv_csr_sddmm: 1 <= k <= 64, ld >= k, U / X 16-byte aligned, the SpMM plan made
 int launch_sddmm(const spmv_csr &h, int k, const float *U, int64_t ldu, const float *X, int64_t ldx, float *out, hipStream_t s)
 {
-    if (h.rows == 0 || h.nnz == 0) return SPMV_OK;
-    const SddmmArgs a{U, ldu, X, ldx, out, k};
-    const bool vec = ldu % 4 == 0 && ldx % 4 == 0;
-    return dispatch_lanes((k + 3) / 4, [&](auto v) {
-        constexpr int V = decltype(v)::value;
-        return vec ? launch_sddmm_v<V, true>(h, a, s) : launch_sddmm_v<V, false>(h, a, s);
-    });
+    return launch_sddmm_e<float>(h, k, U, ldu, X, ldx, out, s);
+}
+
+// and by spmv_csr_sddmm_16: the same with U / X 8-byte aligned and every ld in 16-bit elements
+int launch_sddmm(const spmv_csr &h, int k, const bf16 *U, int64_t ldu, const bf16 *X, int64_t ldx, float *out, hipStream_t s)
+{
+    return launch_sddmm_e<bf16>(h, k, U, ldu, X, ldx, out, s);
+}
+
+int launch_sddmm(const spmv_csr &h, int k, const fp16 *U, int64_t ldu, const fp16 *X, int64_t ldx, float *out, hipStream_t s)
+{
+    return launch_sddmm_e<fp16>(h, k, U, ldu, X, ldx, out, s);
 }
 
 }  // namespace spmv

@@ -12,6 +12,13 @@
 // order (from +0).  Nothing here depends on k but how many columns are computed and stored.
 //
 // X and Y may exceed 4 GiB (c4 at k = 64 is 4.3 GB each).  A lane whose slice starts at or past k does nothing.
+//
+// Element types.  Every kernel here takes the element type E of X and Y as its last template argument: float
+// (spmv_csr_spmm) or 16-bit storage (bf16, fp16: spmv_csr_spmm_16).  The text above is E = float.  With 16-bit E nothing
+// of the order changes: a step's gathered slices wait packed as loaded (slice_t<E>, 2 registers per slice), each is
+// widened exactly to fp32 where it enters its fmaf, vals, the accumulators and the long rows' partials are fp32, and an
+// element of Y is rounded to E once, to nearest even, at its store (store_slice; a long row's in k_spmm_combine, after
+// the partials are added in piece order).  So Y of a 16-bit call is the fp32 call's Y on the widened X, rounded once.
 #include <algorithm>
 #include <numeric>
 #include <vector>
@@ -28,9 +35,9 @@ constexpr int kSpmmSortRows = 4096; // the plan orders the rows of each block of
 
 // sum over the nonzeros [b, e) of the group's row (or piece) of vals[n] * X[col_idx[n]][c0 .. c0+3], in storage order.
 // All lanes of a group call it with the same b, e; lanes with c0 >= k load and add nothing (their shuffles still run).
-template <int V, bool VEC>
+template <int V, bool VEC, typename E>
 __device__ __forceinline__ float4 row_dot(int lane, int64_t b, int64_t e, const int32_t *__restrict__ col_idx,
-                                          const float *__restrict__ vals, const float *__restrict__ X, int64_t ldx, int c0,
+                                          const float *__restrict__ vals, const E *__restrict__ X, int64_t ldx, int c0,
                                           int k)
 {
     constexpr int T = LaneGeom<V>::T, L = LaneGeom<V>::L;
@@ -53,34 +60,39 @@ __device__ __forceinline__ float4 row_dot(int lane, int64_t b, int64_t e, const 
             ct[t] = V == 1 ? c[t] : __shfl(c[t / V], gbase + t % V);
             vt[t] = V == 1 ? v[t] : __shfl(v[t / V], gbase + t % V);
         }
-        float4 xt[T];
+        slice_t<E> xt[T];
 #pragma unroll
-        for (int t = 0; t < T; ++t) xt[t] = (active && kb + t < e) ? load_slice<VEC>(X, ldx, ct[t], c0, k) : zero4();
+        for (int t = 0; t < T; ++t) xt[t] = (active && kb + t < e) ? load_slice<VEC>(X, ldx, ct[t], c0, k) : zero_slice<E>();
 #pragma unroll
         for (int t = 0; t < T; ++t) {
             if (kb + t < e) {     // (a slot past the end adds nothing, not even +0: lane_group.hpp)
-                acc.x = fmaf(vt[t], xt[t].x, acc.x);
-                acc.y = fmaf(vt[t], xt[t].y, acc.y);
-                acc.z = fmaf(vt[t], xt[t].z, acc.z);
-                acc.w = fmaf(vt[t], xt[t].w, acc.w);
+                // (16-bit E: the packed words pass through widen_again's empty statement, so that no slice is widened
+                // before its turn and waits in 4 registers instead of 2)
+                const float4 x = widen_again<E>(xt[t]);
+                acc.x = fmaf(vt[t], x.x, acc.x);
+                acc.y = fmaf(vt[t], x.y, acc.y);
+                acc.z = fmaf(vt[t], x.z, acc.z);
+                acc.w = fmaf(vt[t], x.w, acc.w);
             }
         }
     }
     return acc;
 }
 
-// the operands of a launch (by value)
+// the operands of a launch (by value); E: the element type of X and Y, whose ld count elements of E
+template <typename E>
 struct SpmmArgs {
-    const float *vals, *X;
+    const float *vals;
+    const E *X;
     int64_t ldx;
-    float *Y;
+    E *Y;
     int64_t ldy;
     int k;
 };
 
 // a group of V lanes per row; rows of more than row_cap nonzeros are left to the pieces and the combine
-template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_spmm_rows(GroupRows g, SpmmArgs a)
+template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) void k_spmm_rows(GroupRows g, SpmmArgs<E> a)
 {
     const int lane = threadIdx.x & (kWave - 1), c0 = 4 * (lane & (V - 1));
     const int64_t r = group_row<V>(g);
@@ -92,8 +104,8 @@ __global__ __launch_bounds__(kBlock) void k_spmm_rows(GroupRows g, SpmmArgs a)
 }
 
 // a group of V lanes per piece of a long row: scratch[p][0 .. 4V) (the plan's d_partial, kSpmmMaxK floats per piece)
-template <int V, bool VEC>
-__global__ __launch_bounds__(kBlock) void k_spmm_pieces(GroupPieces g, SpmmArgs a)
+template <int V, bool VEC, typename E>
+__global__ __launch_bounds__(kBlock) void k_spmm_pieces(GroupPieces g, SpmmArgs<E> a)
 {
     const int lane = threadIdx.x & (kWave - 1), c0 = 4 * (lane & (V - 1));
     const int64_t p = group_piece<V>(g);
@@ -103,10 +115,11 @@ __global__ __launch_bounds__(kBlock) void k_spmm_pieces(GroupPieces g, SpmmArgs 
     if (c0 < a.k) *reinterpret_cast<float4 *>(g.scratch + p * kSpmmMaxK + c0) = acc;
 }
 
-// one thread per (long row, column < k): the row's partials added in piece order
+// one thread per (long row, column < k): the row's partials added in piece order, the sum rounded to E at its store
+template <typename E>
 __global__ __launch_bounds__(kBlock) void k_spmm_combine(int n_long, const int32_t *__restrict__ long_row,
                                                              const int32_t *__restrict__ long_first,
-                                                             const float *__restrict__ partial, float *__restrict__ Y,
+                                                             const float *__restrict__ partial, E *__restrict__ Y,
                                                              int64_t ldy, int k)
 {
     const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -115,7 +128,7 @@ __global__ __launch_bounds__(kBlock) void k_spmm_combine(int n_long, const int32
     if (i >= n_long) return;
     float acc = 0.0f;
     for (int p = long_first[i]; p < long_first[i + 1]; ++p) acc += partial[(int64_t)p * kSpmmMaxK + c];
-    Y[(int64_t)long_row[i] * ldy + c] = acc;
+    store_slice<false>(Y + (int64_t)long_row[i] * ldy + c, make_float4(acc, 0.0f, 0.0f, 0.0f), 0, 1);     // (one column)
 }
 
 }  // namespace
@@ -192,34 +205,51 @@ int64_t spmm_plan_bytes(const spmv_csr &h)
     return h.rows * 4 + (int64_t)p.n_long * 4 + ((int64_t)p.n_long + 1) * 4 + (int64_t)p.pieces * 8 + (int64_t)p.pieces * kSpmmMaxK * 4;
 }
 
-template <int V, bool VEC>
-static int launch_spmm_v(const spmv_csr &h, const SpmmArgs &a, hipStream_t s)
+template <int V, bool VEC, typename E>
+static int launch_spmm_v(const spmv_csr &h, const SpmmArgs<E> &a, hipStream_t s)
 {
     const SpmmPlan &p = h.plan_spmm;
-    const int64_t nblocks = group_row_blocks("spmv_csr_spmm", h, V);
+    const int64_t nblocks = group_row_blocks(kIs16<E> ? "spmv_csr_spmm_16" : "spmv_csr_spmm", h, V);
     if (nblocks < 0) return SPMV_ERR_INVALID;
-    hipLaunchKernelGGL((k_spmm_rows<V, VEC>), dim3((unsigned)nblocks), dim3(kBlock), 0, s, group_rows(h, V, nblocks), a);
+    hipLaunchKernelGGL((k_spmm_rows<V, VEC, E>), dim3((unsigned)nblocks), dim3(kBlock), 0, s, group_rows(h, V, nblocks), a);
     SPMV_LAUNCHED("k_spmm_rows");
     if (!p.n_long) return SPMV_OK;
-    hipLaunchKernelGGL((k_spmm_pieces<V, VEC>), group_grid(p.pieces, V), dim3(kBlock), 0, s, group_pieces(h, p.d_partial), a);
+    hipLaunchKernelGGL((k_spmm_pieces<V, VEC, E>), group_grid(p.pieces, V), dim3(kBlock), 0, s, group_pieces(h, p.d_partial), a);
     SPMV_LAUNCHED("k_spmm_pieces");
     const int64_t threads = (int64_t)p.n_long * a.k;
-    hipLaunchKernelGGL(k_spmm_combine, dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, p.n_long,
+    hipLaunchKernelGGL(k_spmm_combine<E>, dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, p.n_long,
                        p.d_long_row, p.d_long_first, p.d_partial, a.Y, a.ldy, a.k);
     SPMV_LAUNCHED("k_spmm_combine");
     return SPMV_OK;
 }
 
-// arguments checked by spmv_csr_spmm: 1 <= k <= 64, ld >= k, X / Y 16-byte aligned, the plan made
-int launch_spmm(const spmv_csr &h, int k, const float *X, int64_t ldx, float *Y, int64_t ldy, hipStream_t s)
+template <typename E>
+static int launch_spmm_e(const spmv_csr &h, int k, const E *X, int64_t ldx, E *Y, int64_t ldy, hipStream_t s)
 {
     if (h.rows == 0) return SPMV_OK;
-    const SpmmArgs a{h.d_vals, X, ldx, Y, ldy, k};
+    const SpmmArgs<E> a{h.d_vals, X, ldx, Y, ldy, k};
     const bool vec = ldx % 4 == 0 && ldy % 4 == 0;
     return dispatch_lanes((k + 3) / 4, [&](auto v) {
         constexpr int V = decltype(v)::value;
-        return vec ? launch_spmm_v<V, true>(h, a, s) : launch_spmm_v<V, false>(h, a, s);
+        return vec ? launch_spmm_v<V, true, E>(h, a, s) : launch_spmm_v<V, false, E>(h, a, s);
     });
+}
+
+// arguments checked by spmv_csr_spmm: 1 <= k <= 64, ld >= k, X / Y 16-byte aligned, the plan made
+int launch_spmm(const spmv_csr &h, int k, const float *X, int64_t ldx, float *Y, int64_t ldy, hipStream_t s)
+{
+    return launch_spmm_e<float>(h, k, X, ldx, Y, ldy, s);
+}
+
+// and by spmv_csr_spmm_16: the same with X / Y 8-byte aligned and every ld in 16-bit elements
+int launch_spmm(const spmv_csr &h, int k, const bf16 *X, int64_t ldx, bf16 *Y, int64_t ldy, hipStream_t s)
+{
+    return launch_spmm_e<bf16>(h, k, X, ldx, Y, ldy, s);
+}
+
+int launch_spmm(const spmv_csr &h, int k, const fp16 *X, int64_t ldx, fp16 *Y, int64_t ldy, hipStream_t s)
+{
+    return launch_spmm_e<fp16>(h, k, X, ldx, Y, ldy, s);
 }
 
 }  // namespace spmv

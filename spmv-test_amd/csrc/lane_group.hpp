@@ -50,9 +50,9 @@
 // are 16-byte aligned: the C ABI checks) a slice is one 16-byte access (VEC); the last slice of a k that is no multiple
 // of 4 is then read whole, inside its row's ld floats, and stored below k only.  Otherwise the kernels read and store
 // 4-byte elements, columns below k only.
-// Fused attention also runs on 16-bit matrices (element type E below): a slice is then 8 bytes, bases are 8-byte aligned, the
-// ld % 4 rule decides between one 8-byte access and 2-byte ones, and nothing of the order above changes: an element is widened
-// exactly where it is used and a result is rounded once where it is stored.
+// All three also run on 16-bit dense matrices (element type E below; SpMM's vals and SDDMM's out stay float): a slice is then
+// 8 bytes, bases are 8-byte aligned, the ld % 4 rule decides between one 8-byte access and 2-byte ones, and nothing of the
+// order above changes: an element is widened exactly where it is used and a result is rounded once where it is stored.
 #pragma once
 #include <type_traits>
 #include "spmv_internal.hpp"
@@ -87,7 +87,7 @@ __device__ __forceinline__ int64_t xcd_item64(int64_t bid, int64_t n)
 
 __device__ __forceinline__ float4 zero4() { return make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
 
-// ---- the element type E of a matrix: float, or 16-bit storage (fused attention only: bf16, fp16 of attention_args.hpp) ----
+// ---- the element type E of a dense matrix: float, or 16-bit storage (bf16, fp16 of attention_args.hpp) -------------------
 // A 16-bit element is widened exactly to fp32 where it is used and an fp32 result is rounded to E once, to nearest even, where
 // it is stored; nothing in between is 16-bit.  Neither direction flushes a subnormal; a NaN stays a NaN (payload unspecified).
 // bf16 is plain integer code; fp16 is the compiler's _Float16 conversions (the host compiles both).

@@ -372,9 +372,13 @@ double binned_tile_nonzeros(const spmv_csr &h, int bin_rows);
 // kernels_spmm.hip: spmv_csr_spmm
 int plan_spmm(spmv_csr &h, hipStream_t s);
 int launch_spmm(const spmv_csr &h, int k, const float *X, int64_t ldx, float *Y, int64_t ldy, hipStream_t s);
+int launch_spmm(const spmv_csr &h, int k, const bf16 *X, int64_t ldx, bf16 *Y, int64_t ldy, hipStream_t s);     // spmv_csr_spmm_16:
+int launch_spmm(const spmv_csr &h, int k, const fp16 *X, int64_t ldx, fp16 *Y, int64_t ldy, hipStream_t s);     // every ld in elements
 int64_t spmm_plan_bytes(const spmv_csr &h);
 // kernels_sddmm.hip: spmv_csr_sddmm (on the plan of plan_spmm)
 int launch_sddmm(const spmv_csr &h, int k, const float *U, int64_t ldu, const float *X, int64_t ldx, float *out, hipStream_t s);
+int launch_sddmm(const spmv_csr &h, int k, const bf16 *U, int64_t ldu, const bf16 *X, int64_t ldx, float *out, hipStream_t s);   // spmv_csr_sddmm_16
+int launch_sddmm(const spmv_csr &h, int k, const fp16 *U, int64_t ldu, const fp16 *X, int64_t ldx, float *out, hipStream_t s);
 // kernels_softmax.hip: spmv_csr_row_softmax / spmv_csr_row_softmax_backward (on the plan of plan_spmm and its scratch)
 int launch_row_softmax(const spmv_csr &h, float scale, const float *scores, float *out, hipStream_t s);
 int launch_row_softmax_backward(const spmv_csr &h, float scale, const float *P, const float *dP, float *dS, hipStream_t s);

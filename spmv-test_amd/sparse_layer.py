@@ -4,8 +4,10 @@
     backward   dX    = A^T dY              spmv_csr_spmm on T = transpose(A), its values refreshed by spmv_csr_transpose_values
                dvals = (dY X^T) at A's pattern     spmv_csr_sddmm on A
 
-Plumbing that shows the primitives compose, not a framework: fp32, one device, a batch of k <= 64 columns.  Every product
-runs in the HIP library; there is no torch fallback.
+Plumbing that shows the primitives compose, not a framework: one device, a batch of k <= 64 columns.  X may be float32, or
+bfloat16 or float16 (the _16 calls of the same primitives): Y and dX then have X's dtype, rounded once at their store, while
+``vals`` and dvals stay float32 and every sum is the fp32 call's.  Every product runs in the HIP library; there is no torch
+fallback.
 """
 from __future__ import annotations
 
@@ -16,15 +18,21 @@ from . import capi
 MAX_K = 64
 
 
-def _operand(t, name: str, rows: int):
-    """t as the library takes it: 2-D float32, stride(1) == 1, stride(0) >= k, 16-byte aligned (copied if it is not)."""
-    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
+_DTYPES_16 = (torch.bfloat16, torch.float16)
+
+
+def _operand(t, name: str, rows: int, like=None):
+    """t as the library takes it: 2-D float32 (or bfloat16 / float16), stride(1) == 1, stride(0) >= k, 16-byte aligned (a
+    16-bit tensor: 8-byte), copied if it is not.  like: the tensor whose dtype t must share (dY against X)."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or (t.dtype != torch.float32 and t.dtype not in _DTYPES_16):
         raise ValueError(f"SparseMatmul: {name} must be a 2-D float32 tensor")
+    if like is not None and t.dtype != like.dtype:
+        raise ValueError(f"SparseMatmul: {name} is {t.dtype}, X was {like.dtype}")
     if t.shape[0] != rows:
         raise ValueError(f"SparseMatmul: {name} has {t.shape[0]} rows, the matrix needs {rows}")
     if not 1 <= t.shape[1] <= MAX_K:
         raise ValueError(f"SparseMatmul: {name} has {t.shape[1]} columns (1 <= k <= {MAX_K})")
-    if t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0:
+    if t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.data_ptr() % (8 if t.dtype in _DTYPES_16 else 16) == 0:
         return t
     return torch.empty(t.shape, dtype=t.dtype, device=t.device).copy_(t)
 
@@ -35,7 +43,7 @@ class SparseMatmul(torch.autograd.Function):
     @staticmethod
     def forward(ctx, layer, vals, X):
         X = _operand(X, "X", layer.A.cols)
-        Y = torch.empty((layer.A.rows, X.shape[1]), dtype=torch.float32, device=X.device)
+        Y = torch.empty((layer.A.rows, X.shape[1]), dtype=X.dtype, device=X.device)
         layer.A.spmm(X, Y)
         ctx.layer = layer
         ctx.save_for_backward(X)
@@ -45,13 +53,13 @@ class SparseMatmul(torch.autograd.Function):
     def backward(ctx, dY):
         layer = ctx.layer
         X, = ctx.saved_tensors
-        dY = _operand(dY, "dY", layer.A.rows)
+        dY = _operand(dY, "dY", layer.A.rows, like=X)
         dvals = dX = None
         if ctx.needs_input_grad[1]:
             dvals = torch.empty(layer.A.nnz, dtype=torch.float32, device=dY.device)
             layer.A.sddmm(dY, X, dvals)
         if ctx.needs_input_grad[2]:
-            dX = torch.empty((layer.A.cols, dY.shape[1]), dtype=torch.float32, device=dY.device)
+            dX = torch.empty((layer.A.cols, dY.shape[1]), dtype=dY.dtype, device=dY.device)
             layer.T.transpose_values(layer.A)      # A's values as they are now
             layer.T.spmm(dY, dX)
         return None, dvals, dX
@@ -61,7 +69,8 @@ class SparseLayer:
     """A rows x cols CSR matrix whose values are a torch leaf.  Borrows ``row_ptr``, ``col_idx`` (int32) and ``vals``
     (float32, may require grad), all on one device; owns the handle of A, of T = A^T (with the map that refreshes T's
     values) and both SpMM plans.  The pattern is fixed; ``vals`` may be updated in place (an optimizer step): the next
-    forward and backward follow the new values without a new plan."""
+    forward and backward follow the new values without a new plan.  X may be float32, bfloat16 or float16 from one call to
+    the next; ``vals`` and its gradient are float32 always."""
 
     def __init__(self, rows: int, cols: int, row_ptr, col_idx, vals):
         self.vals = vals

@@ -13,16 +13,27 @@ Which kernel of NEW is which of OLD is read off the mangled symbol itself (c++fi
 k_attn_* kernel is its name, V, VEC, its element type (float where the symbol has none, as before the 16-bit calls) and
 whether AttnBias is among its arguments.  So k_attn_X_bias<V, VEC, E>(..., AttnBias), the twin kernels of before, and
 k_attn_X<V, VEC, E, AttnBias>(..., AttnBias), one template with a trailing argument pack, are the same kernel, and so are
-k_attn_X<V, VEC, E>(...) and k_attn_X<V, VEC, E>(...) with an empty pack.  Any other symbol is its own key.
+k_attn_X<V, VEC, E>(...) and k_attn_X<V, VEC, E>(...) with an empty pack.  The kernels of kernels_spmm.hip and
+kernels_sddmm.hip are read the same way: k_spmm_rows, k_spmm_pieces, k_sddmm_rows and k_sddmm_pieces are their name, V, VEC and
+element type (float where the symbol has none, as before the 16-bit calls, whose argument struct was no template either), and
+k_spmm_combine its name and element type.  Any other symbol is its own key.
 Exit status 0: every kernel of OLD is in NEW with the same text."""
 import re
 import sys
 
 ELEMENTS = {None: "float", "f": "float", "NS_4bf16E": "bf16", "DF16_": "fp16"}
 ATTN = re.compile(r"_ZN4spmv12_GLOBAL__N_1\d+(k_attn_[a-z_]+?)(?:_bias)?ILi(\d+)ELb([01])E(f|NS_4bf16E|DF16_)?(?:J(?:NS_8AttnBiasE)?E)?EEv")
+GROUPS = re.compile(r"_ZN4spmv12_GLOBAL__N_1\d+(k_(?:spmm|sddmm)_(?:rows|pieces))ILi(\d+)ELb([01])E(f|NS_4bf16E|DF16_)?EEv")
+COMBINE = re.compile(r"_ZN4spmv12_GLOBAL__N_1\d+(k_spmm_combine)(?:I(f|NS_4bf16E|DF16_)E)?E")
 
 
 def key(symbol: str) -> str:
+    m = GROUPS.match(symbol)
+    if m:
+        return f"{m.group(1)}<{m.group(2)}, {'true' if m.group(3) == '1' else 'false'}, {ELEMENTS[m.group(4)]}>"
+    m = COMBINE.match(symbol)
+    if m:
+        return f"{m.group(1)}<{ELEMENTS[m.group(2)]}>"
     m = ATTN.match(symbol)
     if not m:
         return symbol

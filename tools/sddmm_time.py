@@ -9,6 +9,11 @@ tensor on this device -- torch.sparse.sampled_addmm(beta = 0) with its largest d
 not, the line says why.  Times: HIP events, warmed up, median of --reps windows of --iters launches.
 
     python tools/sddmm_time.py [--workloads c2:8192,c2:0,c3:8192,c3:0,c4:8192,c4:0] [--ks 1,4,8,16,32,64] [--out FILE]
+
+--dtype fp32,bf16[,fp16] times spmv_csr_sddmm_16 instead, as tools/spmm_time.py --dtype does for SpMM (its interleaved
+windows and its JSON line): the fp32 call and each 16-bit call on the same numbers, alternating in one process; out of the
+16-bit call must be, bit for bit, the fp32 call's on the widened operands.  Appended to profiles/spmm_16bit.jsonl unless
+--out names another file; the comparisons above are not run in this mode.
 """
 import argparse
 import json
@@ -18,6 +23,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tools"))
 import __graft_entry__ as ge  # noqa: E402
 
 PEAK_BPS = 8e12
@@ -46,12 +52,20 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-torch", action="store_true", help="skip torch.sparse.sampled_addmm")
+    ap.add_argument("--dtype", default="fp32", help="fp32 (the comparisons of the first paragraph), or fp32,bf16[,fp16]")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
     pkg = ge.load_package()
     capi, W = pkg.capi, pkg.workloads
     dev = torch.device("cuda:0")
+    dtypes = a.dtype.split(",")
+    sixteen = [d for d in dtypes if d != "fp32"]
+    if sixteen:
+        from spmm_time import DTYPES, OUT_16BIT, compare_16bit      # (loads rocSPARSE's bindings, not rocSPARSE)
+        if any(d not in DTYPES for d in dtypes) or "fp32" not in dtypes:
+            ap.error("--dtype lists fp32 and any of bf16, fp16")
+        a.out = a.out or str(OUT_16BIT)
     out = open(a.out, "a") if a.out else None
 
     def emit(**kv):
@@ -79,6 +93,22 @@ def main():
             X = torch.randn((w.cols, k), generator=gen, device=dev)
             Y = torch.empty((w.rows, k), dtype=torch.float32, device=dev)
             res = torch.empty(nnz, dtype=torch.float32, device=dev)
+            if sixteen:
+                U16 = {d: U.to(getattr(torch, DTYPES[d])) for d in sixteen}
+                X16 = {d: X.to(getattr(torch, DTYPES[d])) for d in sixteen}
+                res16 = torch.empty(nnz, dtype=torch.float32, device=dev)
+                same = {}
+                for d in sixteen:
+                    A.sddmm(U16[d].to(torch.float32), X16[d].to(torch.float32), res)
+                    A.sddmm(U16[d], X16[d], res16)
+                    torch.cuda.synchronize()
+                    same[d] = bool(torch.equal(res.view(torch.int32), res16.view(torch.int32)))
+                calls = {"fp32": lambda: A.sddmm(U, X, res)}
+                calls.update({d: (lambda d=d: A.sddmm(U16[d], X16[d], res16)) for d in sixteen})
+                emit(**compare_16bit("sddmm", label, k, calls, same, a.iters, a.reps))
+                del U, X, Y, res, res16, U16, X16
+                torch.cuda.empty_cache()
+                continue
             ms = timed(lambda: A.sddmm(U, X, res), a.iters, a.reps)
             ms_spmm = timed(lambda: A.spmm(X, Y), a.iters, a.reps)
             B = 4 * (w.rows + 1) + 8 * nnz + 4 * k * (w.cols + w.rows)

@@ -8,6 +8,13 @@ with ctypes as tools/vendor_compare.py loads rocSPARSE) with its largest differe
 median of --reps windows of --iters launches.
 
     python tools/spmm_time.py [--workloads c2:8192,c2:0,c3:8192,c3:0,c4:8192,c4:0] [--ks 1,4,8,16,32,64] [--out FILE]
+
+--dtype fp32,bf16[,fp16] times spmv_csr_spmm_16 instead: per (workload, k) the fp32 call and each 16-bit call on the same
+numbers (X rounded to the dtype; the fp32 call runs on the fp32 X), in windows that alternate between them in one process,
+so that a drift of the device's clocks falls on all alike.  One JSON line each: the median of every call's windows, the
+ratio 16-bit / fp32, the spread of the fp32 call's own windows ((max - min) / median: what a ratio has to be read against),
+and whether Y of the 16-bit call is, bit for bit, the fp32 call's Y on the widened X rounded by torch.  Appended to
+profiles/spmm_16bit.jsonl unless --out names another file; the comparisons above are not run in this mode.
 """
 import argparse
 import ctypes
@@ -42,6 +49,42 @@ def timed(fn, iters, reps):
         torch.cuda.synchronize()
         out.append(e0.elapsed_time(e1) / iters)
     return statistics.median(out)
+
+
+DTYPES = {"fp32": "float32", "bf16": "bfloat16", "fp16": "float16"}
+OUT_16BIT = ROOT / "profiles" / "spmm_16bit.jsonl"
+
+
+def interleaved(fns, iters, reps):
+    """{name: [ms per call of each of `reps` windows of `iters` launches]}: the windows of the calls alternate."""
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for fn in fns.values():
+        for _ in range(3):
+            fn()
+    out = {name: [] for name in fns}
+    for _ in range(reps):
+        for name, fn in fns.items():
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out[name].append(e0.elapsed_time(e1) / iters)
+    return out
+
+
+def compare_16bit(kind, label, k, calls, same, iters, reps):
+    """The JSON line of one (workload, k): calls = {dtype name: fn}, fp32 among them; same = {dtype name: bool}."""
+    w = interleaved(calls, iters, reps)
+    med = {n: statistics.median(v) for n, v in w.items()}
+    row = dict(call=kind, workload=label, k=k, iters=iters, reps=reps, fp32_ms=round(med["fp32"], 4),
+               fp32_spread=round((max(w["fp32"]) - min(w["fp32"])) / med["fp32"], 4))
+    for n in calls:
+        if n != "fp32":
+            row.update({f"{n}_ms": round(med[n], 4), f"{n}_over_fp32": round(med[n] / med["fp32"], 3),
+                        f"{n}_spread": round((max(w[n]) - min(w[n])) / med[n], 4), f"{n}_is_fp32_rounded_once": same[n]})
+    return row
 
 
 def rocsparse_spmm(rs, rows, cols, nnz, d_rp, d_ci, d_va, X, Y, iters, reps):
@@ -89,14 +132,21 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-rocsparse", action="store_true")
+    ap.add_argument("--dtype", default="fp32", help="fp32 (the comparisons of the first paragraph), or fp32,bf16[,fp16]")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
     pkg = ge.load_package()
     capi, W = pkg.capi, pkg.workloads
     dev = torch.device("cuda:0")
+    dtypes = a.dtype.split(",")
+    if any(d not in DTYPES for d in dtypes) or "fp32" not in dtypes:
+        ap.error("--dtype lists fp32 and any of bf16, fp16")
+    sixteen = [d for d in dtypes if d != "fp32"]
+    if sixteen and not a.out:
+        a.out = str(OUT_16BIT)
     out = open(a.out, "a") if a.out else None
-    rs = None if a.no_rocsparse else RocSparse()
+    rs = None if a.no_rocsparse or sixteen else RocSparse()
     if rs is not None:
         rs._ok(rs.L.rocsparse_set_stream(rs.h, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "set_stream")
 
@@ -121,11 +171,27 @@ def main():
         t0 = time.perf_counter()
         A.spmm_plan()
         plan_ms = (time.perf_counter() - t0) * 1e3
-        A.plan(capi.AUTO)
+        if not sixteen:
+            A.plan(capi.AUTO)
         label = f"{name}_band{band}"
         for k in (int(s) for s in a.ks.split(",")):
             X = torch.randn((w.cols, k), generator=torch.Generator(device=dev).manual_seed(k), device=dev)
             Y = torch.empty((w.rows, k), dtype=torch.float32, device=dev)
+            if sixteen:
+                X16 = {d: X.to(getattr(torch, DTYPES[d])) for d in sixteen}
+                Y16 = {d: torch.empty((w.rows, k), dtype=X16[d].dtype, device=dev) for d in sixteen}
+                same = {}
+                for d in sixteen:
+                    A.spmm(X16[d].to(torch.float32), Y)
+                    A.spmm(X16[d], Y16[d])
+                    torch.cuda.synchronize()
+                    same[d] = bool(torch.equal(Y.to(X16[d].dtype).view(torch.int16), Y16[d].view(torch.int16)))
+                calls = {"fp32": lambda: A.spmm(X, Y)}
+                calls.update({d: (lambda d=d: A.spmm(X16[d], Y16[d])) for d in sixteen})
+                emit(**compare_16bit("spmm", label, k, calls, same, a.iters, a.reps))
+                del X, Y, X16, Y16
+                torch.cuda.empty_cache()
+                continue
             ms = timed(lambda: A.spmm(X, Y), a.iters, a.reps)
             xs = [X[:, c].contiguous() for c in range(k)]
             ys = [torch.empty(w.rows, dtype=torch.float32, device=dev) for _ in range(k)]
