@@ -1,4 +1,6 @@
-// kernels_adaptive.hip -- nnz-balanced CSR SpMV with LDS staging (SPMV_ADAPTIVE / SPMV_TILED).
+// kernels_adaptive.hip -- nnz-balanced CSR SpMV with LDS staging (SPMV_ADAPTIVE / SPMV_TILED): the run kernels and their launch.
+// The plan they run from -- chunk boundaries, column windows, 16-bit columns, sorted words, chunk lists -- is built in
+// plan_adaptive.hip; tiled_chunks.hpp holds what both files share.
 //
 // Role of the reference's adaptive family -- awsp_kernel_v0/1/2
 // (/root/reference/src/kernels/awsp.cu:5-317), awsp_ref_kernel (awsp_ref.cu:6-185) -- and of its
@@ -28,50 +30,19 @@
 //     floats at the same LDS bytes per wave; the plan picks the smallest workgroup whose region
 //     covers the windows of >= 90 % of the chunks, and a chunk whose window does not fit
 //     gathers from global memory.
-#include <atomic>
-#include <climits>
-#include <cstdlib>
-#include <cstring>
 #include "spmv_internal.hpp"
+#include "tiled_chunks.hpp"
 
 namespace spmv {
 
-using i4 = int __attribute__((ext_vector_type(4)));
-using f4 = float __attribute__((ext_vector_type(4)));
-
-#ifndef SPMV_T_GROUP
-#define SPMV_T_GROUP 16
-#endif
-constexpr int kGroup = SPMV_T_GROUP;  // lanes that share one long segment
-
-__host__ __device__ constexpr int chunk_of(int block) { return block * kNnzPerThread; }
-__host__ __device__ constexpr int prod_words(int block) { return chunk_of(block) + (chunk_of(block) >> 5); }
-// LDS region per workgroup: the padded product buffer (4224 floats per 256 threads) rounded up to
-// what still lets 2048 threads share a CU's 160 KiB next to the segment queues (1.1 KiB per 256
-// threads): 4832 / 9664 / 19328 floats.
-__host__ __device__ constexpr int region_words(int block) { return (block / 256) * 4832; }
-static_assert(region_words(256) >= prod_words(256), "region must hold the products");
-__host__ __device__ constexpr int max_long(int block) { return chunk_of(block) / (kShortSeg + 1) + 2; }
-#ifndef SPMV_T_HUGE
-#define SPMV_T_HUGE 512
-#endif
-constexpr int kHugeSeg = SPMV_T_HUGE;  // segments longer than this are summed by one wavefront each
-__host__ __device__ constexpr int max_huge(int block) { return chunk_of(block) / (kHugeSeg + 1) + 2; }
-
-#ifdef SPMV_T_NOPAD   // (A/B builds only)
-__device__ __forceinline__ int pad_idx(int i) { return i; }
-#else
 __device__ __forceinline__ int pad_idx(int i) { return i + (i >> 5); }
-#endif
 // The pad words themselves (slot 32 of every 33) hold 0.0f while the products are in LDS: the row sums then walk the PADDED
 // positions [pad_idx(s), pad_idx(e)) of a segment with constant offsets -- no index arithmetic per product, the holes add
 // +0.0 (round 3: two vector instructions per LDS read less; the kernel's vector units were busy two thirds of its time).
 template <int BLOCK>
 __device__ __forceinline__ void zero_pad_words(float *smem, int tid)
 {
-#ifndef SPMV_T_NOPAD
     for (int h = tid; h < (chunk_of(BLOCK) >> 5); h += BLOCK) smem[h * 33 + 32] = 0.0f;
-#endif
 }
 
 // chunk handled by this block: XCD j = blockIdx % 8 gets a contiguous range
@@ -83,207 +54,70 @@ __device__ __forceinline__ int xcd_chunk(int bid, int n)
 }
 
 // ---------------------------------------------------------------------------
-// plan: lb[c] = first row r with row_ptr[r] >= c*chunk   (c = 0..nchunks-1), lb[nchunks] = rows
-__global__ void k_plan_chunks(int64_t rows, int nchunks, int chunk, const int32_t *__restrict__ row_ptr,
-                              int32_t *__restrict__ lb)
-{
-    int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c > nchunks) return;
-    if (c == nchunks) { lb[c] = (int32_t)rows; return; }
-    const int64_t key = (int64_t)c * chunk;
-    int64_t lo = 0, hi = rows;  // row_ptr[rows] = nnz > key, so the answer is <= rows
-    while (lo < hi) {
-        int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)row_ptr[mid] < key) lo = mid + 1; else hi = mid;
-    }
-    lb[c] = (int32_t)lo;
-}
-
-// plan (TILED): what part of x chunk c stages in LDS.
-//   win[2c]   = first staged column w0 (multiple of 4)
-//   win[2c+1] = staged length wlen in floats (0 = nothing staged) | kOutsideBit when some of the
-//               chunk's columns lie outside [w0, w0+wlen) and are gathered from global memory
-// A chunk whose whole column span [min, max] fits `maxpass` LDS regions is staged completely (in
-// ceil(span/region) passes).  A wider one stages ONE region centred on the mean column (the dense
-// part of a banded chunk that also holds a few very long rows) if that covers >= 1/4 of its
-// nonzeros.  stats[0] = chunks staged in a single pass with nothing outside, stats[1] = chunks
-// staged completely (any number of passes).
-constexpr int kOutsideBit = 1 << 30;
-constexpr int kCol16Bit = 1 << 29;   // the chunk's columns also exist as 16-bit offsets from w0 (plan.d_col16)
-constexpr int kBlockBit = 1 << 28;   // ... as 16-bit indices into a LIST of staged 256-column blocks (plan.d_blk)
-constexpr int kSortedBit = 1 << 27;  // nothing is staged: the chunk gathers x in COLUMN order (plan.d_perm), see sorted_body
-constexpr int kLenMask = kSortedBit - 1;
-#ifndef SPMV_T_SORTED_FROM
-#define SPMV_T_SORTED_FROM (-1)   // -1: staged or sorted by modelled cost, per chunk
-#endif
-constexpr int kSortedFromDefault = SPMV_T_SORTED_FROM;
-// Sorted chunks: one 32-bit word per nonzero = position in the chunk (log2(chunk) bits, high) | column - w0 (the rest,
-// 18 bits: the plan's counting sort keeps one LDS counter per 128-byte line of the span).
-__host__ __device__ constexpr int sorted_pos_bits(int block) { return block == 1024 ? 14 : (block == 512 ? 13 : 12); }
-__host__ __device__ constexpr int sorted_col_bits(int) { return 18; }   // 8192 lines = 32 KiB of counters in the plan kernel
-static_assert(sorted_pos_bits(1024) + sorted_col_bits(1024) <= 32, "one word per nonzero");
-#ifndef SPMV_T_BLKBITS
-#define SPMV_T_BLKBITS 8
-#endif
-constexpr int kBlkBits = SPMV_T_BLKBITS;
-constexpr int kBlkCols = 1 << kBlkBits;      // columns per staged block (256: one 1-KiB LDS-DMA piece per wave)
-constexpr int kBlkMax = 65536 / kBlkCols;    // blocks per chunk: 65 536 staged floats is what a 16-bit index reaches
-
-// Modelled time of one full chunk, in 1/1024 of the time a chunk of that size takes to stream 8 bytes per nonzero with
-// cache-resident gathers.  Fitted on one MI355X to c4 with bands of 8192 ... 200 000 columns and to c3, both workgroup
-// sizes, every chunk forced staged and forced sorted (tools/exp/r02_calibrate.json -> profiles/r02_plan_calibration.jsonl;
-// DESIGN.md section 4):
-//   staged, 16-bit columns                 0.77 + 0.107 per pass            (1 ... 7 passes, 512 and 1024 threads)
-//   staged, 32-bit columns (span >= 65536)  1.05 + 0.12  per pass
-//   sorted                                  1.05 + 1.75 (512 threads) | 1.45 (1024) x 128-byte lines of the span per nonzero
-//   sorted, <= 16 rows in the chunk         0.2 less: the inside of a long row whose columns ascend is an (almost)
-//                                           identity permutation -- the LDS scatter is conflict-free
-//   gathers from L2/fabric unsorted         3
-struct PlanCost {
-    int c16_base = 788, c16_pass = 110, c32_base = 1075, c32_pass = 123, sorted_base = 1075, sorted_line_512 = 1792,
-        sorted_line_1024 = 1485, sorted_few_rows = 205, unstaged = 3072, long_piece = 512;
-};
-
-__global__ __launch_bounds__(256) void k_plan_windows(int64_t nnz, int64_t cols, int nchunks, int chunk,
-                                                      const int32_t *__restrict__ col_idx,
-                                                      int32_t *__restrict__ win, int32_t *__restrict__ stats,
-                                                      int region, int maxpass, int sorted_from, int sorted_span,
-                                                      PlanCost cost, const int32_t *__restrict__ lb,
-                                                      const int32_t *__restrict__ row_ptr)
-{
-    __shared__ int s_min[4], s_max[4], s_cnt[4];
-    __shared__ long long s_sum[4];
-    __shared__ int s_w0;
-    const int c = blockIdx.x;
-    const int wv = threadIdx.x >> 6;
-    const bool lane0 = (threadIdx.x & (kWave - 1)) == 0;
-    const int64_t base = (int64_t)c * chunk;
-    const int n = (int)((nnz - base) < chunk ? (nnz - base) : chunk);
-    int mn = 0x7fffffff, mx = -1;
-    long long sum = 0;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        int v = col_idx[base + i];
-        mn = v < mn ? v : mn;
-        mx = v > mx ? v : mx;
-        sum += v;
-    }
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        int a = __shfl_down(mn, o, kWave), b = __shfl_down(mx, o, kWave);
-        mn = a < mn ? a : mn;
-        mx = b > mx ? b : mx;
-        sum += __shfl_down(sum, o, kWave);
-    }
-    if (lane0) { s_min[wv] = mn; s_max[wv] = mx; s_sum[wv] = sum; }
-    __syncthreads();
-    for (int w = 0; w < 4; ++w) {  // every thread folds the four partials
-        mn = w == 0 ? s_min[0] : (s_min[w] < mn ? s_min[w] : mn);
-        mx = w == 0 ? s_max[0] : (s_max[w] > mx ? s_max[w] : mx);
-    }
-    // Staged or sorted?  Every staging pass re-reads `region` floats of x from L2 and costs a barrier pair and 16
-    // predicated LDS reads per lane; the sorted gather (sorted_body) touches every 128-byte line of the span about
-    // once, with no barrier, but streams 8 bytes per nonzero where a staged chunk with 16-bit columns streams 6.  The
-    // plan prices both for this chunk with the constants of PlanCost (fitted to measurements, DESIGN.md section 4) and
-    // takes the cheaper; the sum of the chunk prices is how the plan compares workgroup sizes.  sorted_from = 0:
-    // never sort; > 0: sort from that many passes on, whatever the prices (tuning knob SPMV_SORTED_FROM).
-    {
-        const int w0_line = mn & ~31;
-        const int64_t span_l = (int64_t)mx + 1 - w0_line;
-        const int64_t span4 = (int64_t)mx + 1 - (mn & ~3);
-        const int64_t passes = (span4 + region - 1) / region;
-        const int lines = (int)((span_l + 31) >> 5);
-        const int cost_staged = passes > maxpass ? cost.unstaged
-                                : (span4 < 65536 ? cost.c16_base + cost.c16_pass * (int)passes
-                                                 : cost.c32_base + cost.c32_pass * (int)passes);
-        const int rows_here = lb[c + 1] - lb[c];
-        // the longest piece of a row inside this chunk (the head segment included)
-        int longest = 0;
-        {
-            const int64_t lim = base + n;
-            for (int t = threadIdx.x; t <= rows_here; t += 256) {
-                const int64_t a = t == 0 ? base : (int64_t)row_ptr[lb[c] + t - 1];
-                int64_t b = t == 0 ? (int64_t)row_ptr[lb[c]] : (int64_t)row_ptr[lb[c] + t];
-                b = b < lim ? b : lim;
-                const int len = (int)(b - (a > base ? a : base));
-                longest = len > longest ? len : longest;
-            }
-#pragma unroll
-            for (int o = kWave / 2; o > 0; o >>= 1) {
-                const int v = __shfl_down(longest, o, kWave);
-                longest = v > longest ? v : longest;
-            }
-            __syncthreads();                 // s_cnt is free here (its first use comes later, behind another barrier)
-            if (lane0) s_cnt[wv] = longest;
-            __syncthreads();
-            longest = s_cnt[0];
-            for (int w = 1; w < 4; ++w) longest = s_cnt[w] > longest ? s_cnt[w] : longest;
-        }
-        const int cost_sorted = cost.sorted_base + (int)((int64_t)(chunk >= 16384 ? cost.sorted_line_1024 : cost.sorted_line_512) * lines / chunk) -
-                                (rows_here <= 16 ? cost.sorted_few_rows : 0);
-        const bool eligible = sorted_from != 0 && n == chunk && span_l <= sorted_span;
-        // ... and one rule the prices do not capture: a chunk that holds a piece of a long row (more than kHugeSeg
-        // nonzeros: power-law rows, whose own column window is what makes the span wide) is sorted from three passes on
-        // -- measured on c3 (4Mi rows, mean 32): 57.2 -> 60.2 % of peak over the priced choice
-        const bool long_row_rule = longest > cost.long_piece && passes >= 3;
-        const bool sort = eligible && (sorted_from > 0 ? span_l > (int64_t)region * (sorted_from - 1)
-                                                       : (cost_sorted < cost_staged || long_row_rule));
-        if (threadIdx.x == 0) {
-            atomicAdd(reinterpret_cast<unsigned long long *>(stats + 4), (unsigned long long)(sort ? cost_sorted : cost_staged));
-            if (long_row_rule) atomicAdd(&stats[3], 1);
-        }
-        if (sort) {
-            if (threadIdx.x == 0) {
-                win[2 * c] = w0_line;
-                win[2 * c + 1] = kSortedBit;
-                atomicAdd(&stats[2], 1);
-            }
-            return;
-        }
-    }
-    const int w0_full = mn & ~3;
-    const int64_t span = (int64_t)mx + 1 - w0_full;
-    if (span <= (int64_t)region * maxpass) {
-        if (threadIdx.x == 0) {
-            win[2 * c] = w0_full;
-            win[2 * c + 1] = (int32_t)span;
-            if (span <= region) atomicAdd(&stats[0], 1);
-            atomicAdd(&stats[1], 1);
-        }
-        return;
-    }
-    // too wide: one region around the mean column, if it is worth it
-    if (threadIdx.x == 0) {
-        const long long tot = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
-        long long w0 = tot / (n > 0 ? n : 1) - region / 2;
-        if (w0 > cols - region) w0 = cols - region;
-        if (w0 < 0) w0 = 0;
-        s_w0 = (int)(w0 & ~3ll);
-    }
-    __syncthreads();
-    const int w0 = s_w0;
-    int cnt = 0;
-    for (int i = threadIdx.x; i < n; i += 256) cnt += ((unsigned)(col_idx[base + i] - w0) < (unsigned)region) ? 1 : 0;
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, kWave);
-    if (lane0) s_cnt[wv] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        cnt = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-        const bool stage = 4 * (int64_t)cnt >= n;
-        int64_t wl = region;
-        if (w0 + wl > cols) wl = cols - w0;
-        win[2 * c] = w0;
-        win[2 * c + 1] = stage ? ((int32_t)wl | kOutsideBit) : 0;
-    }
-}
-
-// ---------------------------------------------------------------------------
 // Segment t of chunk c: t = 0 is the head (the row inherited from chunk c-1, summed into
 // carry[c]); t = 1..m are the rows that START in this chunk (summed into y).
 struct Segment {
     int s, e;
     float *dst;
 };
+
+// Static LDS of a workgroup besides the dynamic region.
+template <int BLOCK>
+struct ChunkShared {
+    int2 long_seg[max_long(BLOCK)];  // {segment id, first product | end product << 16}
+    int2 huge_seg[max_huge(BLOCK)];
+    int long_count, huge_count;
+};
+
+// The steps the three bodies share.  They take and return small values: handed a struct or a lane's array of vectors by
+// reference, or the whole ChunkHead where a few of its fields do, the compiler chose other registers or addressing in some
+// kernel (profiles/tiled_sources_asm.md), so reduce_chunk keeps scalar arguments and the 32-bit body its own bound prefetch.
+// What every body reads first about its chunk c: its nonzeros are [base, lim), the m rows lb0 .. lb0 + m - 1 start in it.
+struct ChunkHead {
+    int c;
+    int64_t base, lim;
+    int lb0, m;
+};
+
+// ... read, and the two segment queues emptied by lane 0.  nnz: where the stream ends (left out by a body that only sees full chunks)
+template <int BLOCK>
+__device__ __forceinline__ ChunkHead chunk_head(ChunkShared<BLOCK> &sh, int tid, int c, const int32_t *chunk_lb,
+                                                int64_t nnz = INT64_MAX)
+{
+    constexpr int kChunkT = chunk_of(BLOCK);
+    ChunkHead h;
+    h.c = c;
+    h.base = (int64_t)c * kChunkT;
+    h.lim = h.base + (int)((nnz - h.base) < kChunkT ? (nnz - h.base) : kChunkT);
+    if (tid == 0) { sh.long_count = 0; sh.huge_count = 0; }
+    h.lb0 = chunk_lb[c];
+    h.m = chunk_lb[c + 1] - h.lb0;
+    return h;
+}
+
+// the sum of segment t to where it goes
+__device__ __forceinline__ void store_sum(int t, int c, int lb0, float *y, float *carry, float acc)
+{
+    if (t == 0) carry[c] = acc;
+    else y[(int64_t)lb0 + t - 1] = acc;
+}
+
+// The row pointers that bound the first segment of lane `tid` (rb = row_ptr[lb0] for the head: lb0 <= rows and row_ptr[rows] =
+// nnz), read while the stream is in flight: two registers; without them the row phase starts with an exposed L2/HBM round
+// trip (+3.4 % at c4, A/B)
+struct RowBounds {
+    int32_t rb, re;
+};
+
+__device__ __forceinline__ RowBounds first_bounds(int tid, const ChunkHead h, const int32_t *row_ptr)
+{
+    RowBounds b = {0, 0};
+    if (tid <= h.m) {
+        b.rb = row_ptr[tid == 0 ? h.lb0 : h.lb0 + tid - 1];
+        b.re = tid == 0 ? 0 : row_ptr[h.lb0 + tid];
+    }
+    return b;
+}
 
 __device__ __forceinline__ Segment make_segment(int t, int lb0, int64_t base, int64_t lim, int32_t rb, int32_t re,
                                                 float *__restrict__ y, float *__restrict__ carry, int c)
@@ -301,13 +135,27 @@ __device__ __forceinline__ Segment make_segment(int t, int lb0, int64_t base, in
     return g;
 }
 
-// Static LDS of a workgroup besides the dynamic region.
-template <int BLOCK>
-struct ChunkShared {
-    int2 long_seg[max_long(BLOCK)];  // {segment id, first product | end product << 16}
-    int2 huge_seg[max_huge(BLOCK)];
-    int long_count, huge_count;
-};
+// The j-th 16-byte vector lane tid takes of a stream (values, columns, 16-bit offsets, sorted words) of the chunk that begins
+// at `chunk`: elements 4 (j BLOCK + tid) .. + 3 of 32-bit ones; non-temporal (read once), 1 KiB contiguous per wave instruction.
+template <int BLOCK, typename V>
+__device__ __forceinline__ V stream_load(const V *chunk, int tid, int j)
+{
+    return __builtin_nontemporal_load(&chunk[j * BLOCK + tid]);
+}
+
+// The products of a chunk into LDS, padded one word per 32 (lane-per-row reads then spread over the banks), the pad words
+// zeroed.  x_of(j, q, w): the x that meets element q of value vector j, whose product goes to word w.
+template <int BLOCK, typename X>
+__device__ __forceinline__ void stage_products(float *smem, int tid, const f4 (&vv)[kNnzPerThread / 4], X x_of)
+{
+    zero_pad_words<BLOCK>(smem, tid);
+#pragma unroll
+    for (int j = 0; j < kNnzPerThread / 4; ++j) {
+        const int p0 = pad_idx((j * BLOCK + tid) * 4);  // a multiple of 4: the four words never straddle a pad slot
+#pragma unroll
+        for (int q = 0; q < 4; ++q) smem[p0 + q] = vv[j][q] * x_of(j, q, p0 + q);
+    }
+}
 
 // acc + the acc of lane + O of the same 16-lane DPP row, in the lanes whose lane + O lies in the row (the others add 0): a row
 // shift in the vector unit, v_add_f32_dpp row_shl:O.  __shfl_down is ds_bpermute_b32 -- an address, a trip through the LDS
@@ -448,10 +296,7 @@ __device__ __forceinline__ void reduce_chunk(const float *smem, ChunkShared<BLOC
             for (int k = (q.y & 0xffff) + sub; k < qe; k += kGroup) acc += smem[k];
         }
         acc = group_tree<LEAN == 2>(acc);
-        if (sub == 0) {
-            if (q.x == 0) carry[c] = acc;
-            else y[(int64_t)lb0 + q.x - 1] = acc;
-        }
+        if (sub == 0) store_sum(q.x, c, lb0, y, carry, acc);
     }
 
     // longer segments: one WAVE each, lanes striding the segment (no workgroup barrier: a chunk of a dense-ish
@@ -479,10 +324,7 @@ __device__ __forceinline__ void reduce_chunk(const float *smem, ChunkShared<BLOC
 #pragma unroll
             for (int o = 8; o > 0; o >>= 1) acc += __shfl_down(acc, o, kWave);
         }
-        if (lane == 0) {
-            if (q.x == 0) carry[c] = acc;
-            else y[(int64_t)lb0 + q.x - 1] = acc;
-        }
+        if (lane == 0) store_sum(q.x, c, lb0, y, carry, acc);
     }
 }
 
@@ -499,8 +341,8 @@ __device__ __forceinline__ void load_stream(int64_t base, int n, int pad_col, co
         const f4 *v4 = reinterpret_cast<const f4 *>(vals + base);
 #pragma unroll
         for (int j = 0; j < kVec; ++j) {
-            cc[j] = __builtin_nontemporal_load(&c4[j * BLOCK + tid]);
-            vv[j] = __builtin_nontemporal_load(&v4[j * BLOCK + tid]);
+            cc[j] = stream_load<BLOCK>(c4, tid, j);
+            vv[j] = stream_load<BLOCK>(v4, tid, j);
         }
     } else {
         // last chunk: guarded scalar loads, same element->lane map; padded lanes use an in-window
@@ -577,9 +419,6 @@ __device__ __forceinline__ void stage_slice(const float *__restrict__ x, int64_t
     }
 }
 
-// The body of k_adaptive for workgroup `bid` of `grid` (a device function so that k_tiled_mixed can run it beside
-// the 16-bit body in one launch).  smem: one dynamic LDS region, used twice: first as the x window (TILED), then
-// -- after the gathers have landed in registers -- as the product staging buffer.
 // A slice of a chunk's BLOCK LIST, global -> LDS: block ids[b] (kBlkCols columns of x) lands at smem + kBlkCols b.  One wave
 // per block and trip, one 1-KiB LDS-DMA piece each.  The last block of x is copied element by element.
 template <int BLOCK>
@@ -602,6 +441,9 @@ __device__ __forceinline__ void stage_blocks(const float *__restrict__ x, const 
     }
 }
 
+// The body of k_adaptive for workgroup `bid` of `grid` (a device function so that k_tiled_mixed can run it beside
+// the 16-bit body in one launch).  smem: one dynamic LDS region, used twice: first as the x window (TILED), then
+// -- after the gathers have landed in registers -- as the product staging buffer.
 template <int BLOCK, bool TILED, bool PERSIST>
 __device__ __forceinline__ void adaptive_body(float *smem, ChunkShared<BLOCK> &sh, int bid, int grid, int64_t rows,
                                               int64_t nnz, int64_t cols, int chunk0, int nrun,
@@ -639,14 +481,9 @@ __device__ __forceinline__ void adaptive_body(float *smem, ChunkShared<BLOCK> &s
         // loop it costs ~28 VGPRs and spills
         int tid = tid0;
         if (PERSIST) asm volatile("" : "+v"(tid));
-        const int c = wk.c;
-        const int64_t base = (int64_t)c * kChunkT;
-        const int n = (int)((nnz - base) < kChunkT ? (nnz - base) : kChunkT);
-        const int64_t lim = base + n;
-        if (tid == 0) { sh.long_count = 0; sh.huge_count = 0; }
-
-        const int lb0 = chunk_lb[c], lb1 = chunk_lb[c + 1];
-        const int m = lb1 - lb0;
+        const ChunkHead h = chunk_head<BLOCK>(sh, tid, wk.c, chunk_lb, nnz);
+        const int c = h.c, lb0 = h.lb0, m = h.m;
+        const int64_t base = h.base, lim = h.lim;
         int w0 = 0, wlen = 0;
         bool outside = false;
         if (TILED) {
@@ -658,7 +495,8 @@ __device__ __forceinline__ void adaptive_body(float *smem, ChunkShared<BLOCK> &s
 
         // ---- row pointers of this lane's first segment, in flight together with the stream
         //      (ADAPTIVE and k_tiled16 only: the 32-bit TILED form spills 20 bytes with them, wherever they
-        //      are issued, and runs 5 % slower -- A/B)
+        //      are issued, and runs 5 % slower -- A/B).  first_bounds written out: through it k_adaptive<256, false, false>
+        //      initialises the two registers in the other order.
         int32_t rb0 = 0, re0 = 0;
         if (!TILED && tid <= m) {
             rb0 = row_ptr[tid == 0 ? lb0 : lb0 + tid - 1];  // lb0 <= rows and row_ptr[rows] = nnz
@@ -704,15 +542,7 @@ __device__ __forceinline__ void adaptive_body(float *smem, ChunkShared<BLOCK> &s
         }
 
         // ---- stage the products (padded one word per 32: lane-per-row reads spread over banks)
-        zero_pad_words<BLOCK>(smem, tid);
-#pragma unroll
-        for (int j = 0; j < kVec; ++j) {
-            const int p0 = pad_idx((j * BLOCK + tid) * 4);  // i0 % 4 == 0: never straddles a pad slot
-            smem[p0] = vv[j][0] * xv[j][0];
-            smem[p0 + 1] = vv[j][1] * xv[j][1];
-            smem[p0 + 2] = vv[j][2] * xv[j][2];
-            smem[p0 + 3] = vv[j][3] * xv[j][3];
-        }
+        stage_products<BLOCK>(smem, tid, vv, [&](int j, int q, int) { return xv[j][q]; });
 
         // ---- the next chunk's stream, into the registers the products just left
         const int cn = c + wk.stride;
@@ -753,7 +583,15 @@ void k_adaptive(int64_t rows, int64_t nnz, int64_t cols, int chunk0, int nrun, c
 // two 16-byte loads, and k_tiled16 streams 6 bytes per nonzero instead of 8 (HBM traffic of config 4:
 // 1.8 GB against 2.35 GB algorithmic).  One-shot workgroups over the list of such chunks; the others
 // (outliers gathered from global memory, the ragged last chunk) go through k_adaptive.
-using u4 = unsigned __attribute__((ext_vector_type(4)));
+
+// 16-bit offset of element q of value vector j: a lane's sixteen offsets are two 16-byte loads of eight, element (j, q) is
+// offset e = (j & 1) * 4 + q of load j >> 1
+__device__ __forceinline__ unsigned col16_at(const u4 (&raw)[2], int j, int q)
+{
+    const int e = (j & 1) * 4 + q;
+    const unsigned word = raw[j >> 1][e >> 1];
+    return (e & 1) ? (word >> 16) : (word & 0xffffu);
+}
 
 template <int BLOCK, bool BLOCKS>
 __device__ __forceinline__ void tiled16_body(float *smem, ChunkShared<BLOCK> &sh, int bid, int64_t rows, int64_t cols,
@@ -764,7 +602,6 @@ __device__ __forceinline__ void tiled16_body(float *smem, ChunkShared<BLOCK> &sh
                                              const int32_t *__restrict__ win, const int32_t *__restrict__ list,
                                              int kRegionArg, const int32_t *__restrict__ blk)
 {
-    constexpr int kChunkT = chunk_of(BLOCK);
     constexpr int kVec = kNnzPerThread / 4;
     static_assert(kNnzPerThread == 16, "the col16 lane layout is two 16-byte loads of eight offsets");
 
@@ -772,12 +609,8 @@ __device__ __forceinline__ void tiled16_body(float *smem, ChunkShared<BLOCK> &sh
     // list == nullptr: every chunk has 16-bit columns (the list would be the identity) -- the stream addresses
     // then depend on blockIdx only and the loads leave one dependent global load earlier
     const int ci = xcd_chunk(bid, nrun);
-    const int c = list ? list[ci] : ci;
-    const int64_t base = (int64_t)c * kChunkT;
-    const int64_t lim = base + kChunkT;
-    if (tid == 0) { sh.long_count = 0; sh.huge_count = 0; }
-    const int lb0 = chunk_lb[c], lb1 = chunk_lb[c + 1];
-    const int m = lb1 - lb0;
+    const ChunkHead h = chunk_head<BLOCK>(sh, tid, list ? list[ci] : ci, chunk_lb);
+    const int c = h.c;
     const int w0 = win[2 * c];
     const int wl = win[2 * c + 1];
     const int wlen = wl & kLenMask;
@@ -790,21 +623,15 @@ __device__ __forceinline__ void tiled16_body(float *smem, ChunkShared<BLOCK> &sh
     u4 raw[2];
     f4 vv[kVec];
     {
-        const u4 *c8 = reinterpret_cast<const u4 *>(col16 + base);
-        const f4 *v4 = reinterpret_cast<const f4 *>(vals + base);
-        raw[0] = __builtin_nontemporal_load(&c8[tid]);
+        const u4 *c8 = reinterpret_cast<const u4 *>(col16 + h.base);
+        const f4 *v4 = reinterpret_cast<const f4 *>(vals + h.base);
+        raw[0] = __builtin_nontemporal_load(&c8[tid]);   // (not stream_load: the 1024-thread kernel then shares an offset register)
         raw[1] = __builtin_nontemporal_load(&c8[BLOCK + tid]);
 #pragma unroll
-        for (int j = 0; j < kVec; ++j) vv[j] = __builtin_nontemporal_load(&v4[j * BLOCK + tid]);
+        for (int j = 0; j < kVec; ++j) vv[j] = stream_load<BLOCK>(v4, tid, j);
     }
-
-    // the bounds of this lane's first segment ride along with the stream (they only depend on chunk_lb): two
-    // registers; without them the row phase starts with an exposed L2/HBM round trip (+3.4 % at c4, A/B)
-    int32_t rb0 = 0, re0 = 0;
-    if (tid <= m) {
-        rb0 = row_ptr[tid == 0 ? lb0 : lb0 + tid - 1];
-        re0 = tid == 0 ? 0 : row_ptr[lb0 + tid];
-    }
+    // the bounds of this lane's first segment ride along with the stream (they only depend on chunk_lb)
+    const RowBounds b0 = first_bounds(tid, h, row_ptr);
 
     // ---- gather x from the staged slices (every column of the chunk lies in [w0, w0+wlen))
     f4 xv[kVec];
@@ -812,7 +639,6 @@ __device__ __forceinline__ void tiled16_body(float *smem, ChunkShared<BLOCK> &sh
     for (int j = 0; j < kVec; ++j)
 #pragma unroll
         for (int q = 0; q < 4; ++q) xv[j][q] = 0.0f;
-#ifndef SPMV_T_NOSTAGE
     if (wlen <= kRegion && wlen > 0) {
         // one pass (nearly every chunk): every offset lies inside the staged window, no range check per element
         if (by_blocks) stage_blocks<BLOCK>(x, blk + (int64_t)c * kBlkMax, wlen / kBlkCols, cols, smem, tid);
@@ -821,67 +647,38 @@ __device__ __forceinline__ void tiled16_body(float *smem, ChunkShared<BLOCK> &sh
 #pragma unroll
         for (int j = 0; j < kVec; ++j)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int e = (j & 1) * 4 + q;
-                const unsigned word = raw[j >> 1][e >> 1];
-                xv[j][q] = smem[(e & 1) ? (word >> 16) : (word & 0xffffu)];
-            }
+            for (int q = 0; q < 4; ++q) xv[j][q] = smem[col16_at(raw, j, q)];
         __syncthreads();  // every gather has its value before the products overwrite the window
-    } else
-#endif
-#ifdef SPMV_T_NOSTAGE   // (A/B builds only: the kernel without its x window -- results are wrong)
-    for (int off = 0; off < 0; off += kRegion) {
-#else
-    for (int off = 0; off < wlen; off += kRegion) {
-#endif
-        const int len = (wlen - off) < kRegion ? (wlen - off) : kRegion;
-        const int64_t g0 = (int64_t)w0 + off;
-        if (by_blocks) stage_blocks<BLOCK>(x, blk + (int64_t)c * kBlkMax + off / kBlkCols, len / kBlkCols, cols, smem, tid);
-        else stage_slice<BLOCK, true>(x, g0, len, cols, smem, tid);
-        __syncthreads();
+    } else {
+        for (int off = 0; off < wlen; off += kRegion) {
+            const int len = (wlen - off) < kRegion ? (wlen - off) : kRegion;
+            const int64_t g0 = (int64_t)w0 + off;
+            if (by_blocks) stage_blocks<BLOCK>(x, blk + (int64_t)c * kBlkMax + off / kBlkCols, len / kBlkCols, cols, smem, tid);
+            else stage_slice<BLOCK, true>(x, g0, len, cols, smem, tid);
+            __syncthreads();
 #pragma unroll
-        for (int j = 0; j < kVec; ++j)
+            for (int j = 0; j < kVec; ++j)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                // element (j, q) of this lane is offset e = (j&1)*4 + q of load j>>1
-                const int e = (j & 1) * 4 + q;
-                const unsigned word = raw[j >> 1][e >> 1];
-                const unsigned cl = (e & 1) ? (word >> 16) : (word & 0xffffu);
-                const unsigned o = cl - (unsigned)off;
-                if (o < (unsigned)len) xv[j][q] = smem[o];
-            }
-        __syncthreads();  // every gather has its value before the slice is overwritten
+                for (int q = 0; q < 4; ++q) {
+                    const unsigned o = col16_at(raw, j, q) - (unsigned)off;
+                    if (o < (unsigned)len) xv[j][q] = smem[o];
+                }
+            __syncthreads();  // every gather has its value before the slice is overwritten
+        }
     }
 
     // ---- products, then the rows of the chunk
-    zero_pad_words<BLOCK>(smem, tid);
-#pragma unroll
-    for (int j = 0; j < kVec; ++j) {
-        const int p0 = pad_idx((j * BLOCK + tid) * 4);
-        smem[p0] = vv[j][0] * xv[j][0];
-        smem[p0 + 1] = vv[j][1] * xv[j][1];
-        smem[p0 + 2] = vv[j][2] * xv[j][2];
-        smem[p0 + 3] = vv[j][3] * xv[j][3];
-    }
+    stage_products<BLOCK>(smem, tid, vv, [&](int j, int q, int) { return xv[j][q]; });
     __syncthreads();
-#ifdef SPMV_T_NOREDUCE  // (A/B builds only: the kernel without its row sums -- results are wrong)
-    if (tid <= m && rb0 == 0x7fffffff) y[lb0 + tid] = smem[tid] + (float)re0;
-#else
-    reduce_chunk<BLOCK, true, BLOCKS ? 1 : 0>(smem, sh, tid, c, lb0, m, base, lim, row_ptr, y, carry, rb0, re0);
-#endif
+    reduce_chunk<BLOCK, true, BLOCKS ? 1 : 0>(smem, sh, tid, h.c, h.lb0, h.m, h.base, h.lim, row_ptr, y, carry, b0.rb, b0.re);
 }
 
 template <int BLOCK, bool BLOCKS>
-__global__ __launch_bounds__(BLOCK, 8) void k_tiled16(int64_t rows, int64_t cols, int nrun,
-                                                      const int32_t *__restrict__ row_ptr,
-                                                      const uint16_t *__restrict__ col16,
-                                                      const float *__restrict__ vals,
-                                                      const float *__restrict__ x, float *__restrict__ y,
-                                                      const int32_t *__restrict__ chunk_lb,
-                                                      float *__restrict__ carry,
-                                                      const int32_t *__restrict__ win,
-                                                      const int32_t *__restrict__ list, int kRegion,
-                                                      const int32_t *__restrict__ blk)
+__global__ __launch_bounds__(BLOCK, 8)
+void k_tiled16(int64_t rows, int64_t cols, int nrun, const int32_t *__restrict__ row_ptr, const uint16_t *__restrict__ col16,
+               const float *__restrict__ vals, const float *__restrict__ x, float *__restrict__ y,
+               const int32_t *__restrict__ chunk_lb, float *__restrict__ carry, const int32_t *__restrict__ win,
+               const int32_t *__restrict__ list, int kRegion, const int32_t *__restrict__ blk)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ ChunkShared<BLOCK> sh;
@@ -915,36 +712,20 @@ __device__ __forceinline__ void sorted_body(float *smem, ChunkShared<BLOCK> &sh,
 
     const int tid = threadIdx.x;
     const int ci = xcd_chunk(bid, nrun);          // position in the list of sorted chunks = slot of its words in perm[]
-    const int c = list[ci];
-    const int64_t base = (int64_t)c * kChunkT;
-    const int64_t lim = base + kChunkT;
-    if (tid == 0) { sh.long_count = 0; sh.huge_count = 0; }
-    const int lb0 = chunk_lb[c], lb1 = chunk_lb[c + 1];
-    const int m = lb1 - lb0;
-    const float *xw = x + win[2 * c];
+    const ChunkHead h = chunk_head<BLOCK>(sh, tid, list[ci], chunk_lb);
+    const float *xw = x + win[2 * h.c];
 
     u4 pw[kVec];
     f4 vv[kVec];
     {
         const u4 *p4 = reinterpret_cast<const u4 *>(perm + (int64_t)ci * kChunkT);
-        const f4 *v4 = reinterpret_cast<const f4 *>(vals + base);
-#ifdef SPMV_SORTED_FAKE7      // A/B build (wrong y): three quarters of the words' bytes are read -- what a 3-byte word would stream
+        const f4 *v4 = reinterpret_cast<const f4 *>(vals + h.base);
 #pragma unroll
-        for (int j = 0; j < kVec - 1; ++j) pw[j] = __builtin_nontemporal_load(&p4[j * BLOCK + tid]);
-        // (the fourth vector made up from the third: other positions, other lines of x -- the gathers and the LDS scatter keep their work)
-        for (int q = 0; q < 4; ++q) pw[kVec - 1][q] = (pw[kVec - 2][q] ^ (1u << kColBits)) + 37u;
-#else
+        for (int j = 0; j < kVec; ++j) pw[j] = stream_load<BLOCK>(p4, tid, j);
 #pragma unroll
-        for (int j = 0; j < kVec; ++j) pw[j] = __builtin_nontemporal_load(&p4[j * BLOCK + tid]);
-#endif
-#pragma unroll
-        for (int j = 0; j < kVec; ++j) vv[j] = __builtin_nontemporal_load(&v4[j * BLOCK + tid]);
+        for (int j = 0; j < kVec; ++j) vv[j] = stream_load<BLOCK>(v4, tid, j);
     }
-    int32_t rb0 = 0, re0 = 0;
-    if (tid <= m) {
-        rb0 = row_ptr[tid == 0 ? lb0 : lb0 + tid - 1];
-        re0 = tid == 0 ? 0 : row_ptr[lb0 + tid];
-    }
+    const RowBounds b0 = first_bounds(tid, h, row_ptr);
 
     // gather in column order, scatter to the row-major position of each nonzero
 #pragma unroll
@@ -957,82 +738,21 @@ __device__ __forceinline__ void sorted_body(float *smem, ChunkShared<BLOCK> &sh,
     }
     __syncthreads();
     // this lane's values meet their x; the products take the same LDS words
-    zero_pad_words<BLOCK>(smem, tid);
-#pragma unroll
-    for (int j = 0; j < kVec; ++j) {
-        const int p0 = pad_idx((j * BLOCK + tid) * 4);
-        smem[p0] = vv[j][0] * smem[p0];
-        smem[p0 + 1] = vv[j][1] * smem[p0 + 1];
-        smem[p0 + 2] = vv[j][2] * smem[p0 + 2];
-        smem[p0 + 3] = vv[j][3] * smem[p0 + 3];
-    }
+    stage_products<BLOCK>(smem, tid, vv, [&](int, int, int w) { return smem[w]; });
     __syncthreads();
-    reduce_chunk<BLOCK, true>(smem, sh, tid, c, lb0, m, base, lim, row_ptr, y, carry, rb0, re0);
+    reduce_chunk<BLOCK, true>(smem, sh, tid, h.c, h.lb0, h.m, h.base, h.lim, row_ptr, y, carry, b0.rb, b0.re);
 }
 
 template <int BLOCK>
-__global__ __launch_bounds__(BLOCK, 8) void k_sorted(int64_t rows, int nrun, const int32_t *__restrict__ row_ptr,
-                                                     const uint32_t *__restrict__ perm, const float *__restrict__ vals,
-                                                     const float *__restrict__ x, float *__restrict__ y,
-                                                     const int32_t *__restrict__ chunk_lb, float *__restrict__ carry,
-                                                     const int32_t *__restrict__ win, const int32_t *__restrict__ list)
+__global__ __launch_bounds__(BLOCK, 8)
+void k_sorted(int64_t rows, int nrun, const int32_t *__restrict__ row_ptr, const uint32_t *__restrict__ perm,
+              const float *__restrict__ vals, const float *__restrict__ x, float *__restrict__ y,
+              const int32_t *__restrict__ chunk_lb, float *__restrict__ carry, const int32_t *__restrict__ win,
+              const int32_t *__restrict__ list)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ ChunkShared<BLOCK> sh;
     sorted_body<BLOCK>(smem, sh, (int)blockIdx.x, rows, nrun, row_ptr, perm, vals, x, y, chunk_lb, carry, win, list);
-}
-
-// plan: counting sort of one chunk's nonzeros by the 128-byte line of x their column lies in (the order inside a line
-// does not matter: the gathers of a line coalesce whatever their order, and no arithmetic depends on it).
-template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void k_plan_sorted(const int32_t *__restrict__ col_idx,
-                                                       const int32_t *__restrict__ win, const int32_t *__restrict__ slot,
-                                                       uint32_t *__restrict__ perm)
-{
-    constexpr int kChunkT = chunk_of(BLOCK);
-    constexpr int kColBits = sorted_col_bits(BLOCK);
-    constexpr int kLines = 1 << (kColBits - 5);
-    constexpr int kPer = kLines / BLOCK;
-    static_assert(kLines % BLOCK == 0, "bins per thread");
-    __shared__ int hist[kLines];
-    __shared__ int part[BLOCK];
-    const int c = blockIdx.x, tid = threadIdx.x;
-    if (!(win[2 * c + 1] & kSortedBit)) return;   // chunk-uniform
-    const int w0 = win[2 * c];
-    const int64_t base = (int64_t)c * kChunkT;
-    uint32_t *out = perm + (int64_t)slot[c] * kChunkT;   // perm[] holds the sorted chunks only, in list order
-    for (int i = tid; i < kLines; i += BLOCK) hist[i] = 0;
-    __syncthreads();
-    for (int i = tid; i < kChunkT; i += BLOCK) atomicAdd(&hist[(col_idx[base + i] - w0) >> 5], 1);
-    __syncthreads();
-    int sum = 0;
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) sum += hist[tid * kPer + k];
-    part[tid] = sum;
-    __syncthreads();
-    for (int o = 1; o < BLOCK; o <<= 1) {
-        const int v = tid >= o ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int run = part[tid] - sum;
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-        const int v = hist[tid * kPer + k];
-        hist[tid * kPer + k] = run;
-        run += v;
-    }
-    __syncthreads();
-    for (int i = tid; i < kChunkT; i += BLOCK) {
-        const int off = col_idx[base + i] - w0;
-        const int d = atomicAdd(&hist[off >> 5], 1);
-        // sorted element d goes where lane d % BLOCK finds it as component q of its j-th 16-byte load, (j, q) =
-        // divmod(d / BLOCK, 4): the 64 lanes of ONE gather instruction then hold 64 CONSECUTIVE sorted elements (a
-        // few neighbouring lines), not elements four apart whose lines the other three components would ask for again
-        const int t = d % BLOCK, jq = d / BLOCK;
-        out[((jq >> 2) * BLOCK + t) * 4 + (jq & 3)] = ((unsigned)i << kColBits) | (unsigned)off;
-    }
 }
 
 // All kinds of chunk in ONE launch: workgroups [0, n32) run the 32-bit body over list32 (the slow chunks -- outliers
@@ -1040,20 +760,13 @@ __global__ __launch_bounds__(BLOCK) void k_plan_sorted(const int32_t *__restrict
 // 16-bit body over list16.  Two launches
 // would each end with a partly idle chip (power-law rows: 1758 such chunks took 71 us after the 209 us of the rest).
 template <int BLOCK, bool BLOCKS>
-__global__ __launch_bounds__(BLOCK, 8) void k_tiled_mixed(int64_t rows, int64_t nnz, int64_t cols, int n32, int nsorted,
-                                                          int n16, const int32_t *__restrict__ row_ptr,
-                                                          const int32_t *__restrict__ col_idx,
-                                                          const uint16_t *__restrict__ col16,
-                                                          const uint32_t *__restrict__ perm,
-                                                          const float *__restrict__ vals,
-                                                          const float *__restrict__ x, float *__restrict__ y,
-                                                          const int32_t *__restrict__ chunk_lb,
-                                                          float *__restrict__ carry,
-                                                          const int32_t *__restrict__ win,
-                                                          const int32_t *__restrict__ list32,
-                                                          const int32_t *__restrict__ list_sorted,
-                                                          const int32_t *__restrict__ list16, int kRegion,
-                                                          const int32_t *__restrict__ blk)
+__global__ __launch_bounds__(BLOCK, 8)
+void k_tiled_mixed(int64_t rows, int64_t nnz, int64_t cols, int n32, int nsorted, int n16, const int32_t *__restrict__ row_ptr,
+                   const int32_t *__restrict__ col_idx, const uint16_t *__restrict__ col16, const uint32_t *__restrict__ perm,
+                   const float *__restrict__ vals, const float *__restrict__ x, float *__restrict__ y,
+                   const int32_t *__restrict__ chunk_lb, float *__restrict__ carry, const int32_t *__restrict__ win,
+                   const int32_t *__restrict__ list32, const int32_t *__restrict__ list_sorted,
+                   const int32_t *__restrict__ list16, int kRegion, const int32_t *__restrict__ blk)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ ChunkShared<BLOCK> sh;
@@ -1066,165 +779,6 @@ __global__ __launch_bounds__(BLOCK, 8) void k_tiled_mixed(int64_t rows, int64_t 
     else
         tiled16_body<BLOCK, BLOCKS>(smem, sh, b - n32 - nsorted, rows, cols, n16, row_ptr, col16, vals, x, y, chunk_lb,
                                     carry, win, list16, kRegion, blk);
-}
-
-// plan: 16-bit offsets of every eligible chunk (full chunk, whole span staged, span < 65536), in the
-// lane layout of k_tiled16; flags[c] = 1 for those chunks and kCol16Bit is set in win[2c+1].
-template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void k_plan_col16(int64_t nnz, const int32_t *__restrict__ col_idx,
-                                                      int32_t *__restrict__ win, uint16_t *__restrict__ col16,
-                                                      int32_t *__restrict__ flags, int region, int maxpass,
-                                                      int32_t *__restrict__ blk, int32_t *__restrict__ blk_chunks,
-                                                      int dry)
-{
-    constexpr int kChunkT = chunk_of(BLOCK);
-    __shared__ int s_min, s_max, s_total;
-    __shared__ unsigned bits[BLOCK];   // occupancy of the 256-column blocks [s_min, s_min + 32 BLOCK)
-    __shared__ int pref[BLOCK];        // occupied blocks before word t
-    const int c = blockIdx.x, tid = threadIdx.x;
-    const int64_t base = (int64_t)c * kChunkT;
-    const int wl = win[2 * c + 1];
-    const int wlen = wl & kLenMask;
-    const bool full_chunk = (nnz - base) >= kChunkT;
-    const bool contiguous = full_chunk && wlen > 0 && wlen < 65536 && !(wl & kOutsideBit);
-    const int w0 = win[2 * c];
-    if (tid == 0) { s_min = INT_MAX; s_max = -1; }
-    __syncthreads();  // (also: everyone has read win before lane 0 rewrites it)
-
-    // ---- a LIST of 256-column blocks instead of one span?  Tried where the span is not staged in one pass (or not
-    //      at all): columns in a few clusters far apart (3-D stencils: r, r+-n, r+-n^2) occupy a handful of blocks.
-    bool by_blocks = false;
-    if (full_chunk && blk && !(contiguous && wlen <= region)) {   // chunk-uniform
-        int bmin = INT_MAX, bmax = -1;
-        for (int i = tid; i < kChunkT; i += BLOCK) {
-            const int b = col_idx[base + i] >> kBlkBits;
-            bmin = b < bmin ? b : bmin;
-            bmax = b > bmax ? b : bmax;
-        }
-        atomicMin(&s_min, bmin);
-        atomicMax(&s_max, bmax);
-        bits[tid] = 0u;
-        __syncthreads();
-        const int lo = s_min;
-        if (s_max - lo < 32 * BLOCK) {   // chunk-uniform
-            for (int i = tid; i < kChunkT; i += BLOCK) {
-                const int d = (col_idx[base + i] >> kBlkBits) - lo;
-                atomicOr(&bits[d >> 5], 1u << (d & 31));
-            }
-            __syncthreads();
-            const int mine = __popc(bits[tid]);
-            pref[tid] = mine;
-            __syncthreads();
-            for (int o = 1; o < BLOCK; o <<= 1) {
-                const int v = tid >= o ? pref[tid - o] : 0;
-                __syncthreads();
-                pref[tid] += v;
-                __syncthreads();
-            }
-            if (tid == BLOCK - 1) s_total = pref[tid];
-            const int before = pref[tid] - mine;
-            __syncthreads();
-            pref[tid] = before;
-            __syncthreads();
-            const int total = s_total;
-            const int cap = (region / kBlkCols) * kBlkCols;
-            // worth it only when the blocks fit ONE pass (a multi-pass list is no better than a multi-pass span)
-            by_blocks = total <= kBlkMax && total * kBlkCols <= cap && (!contiguous || total * kBlkCols < wlen);
-            (void)maxpass;
-            if (by_blocks && dry) {   // counting run: how many chunks would switch (the plan decides, see build_col16)
-                if (tid == 0) atomicAdd(blk_chunks, 1);
-                return;
-            }
-            if (by_blocks) {
-                unsigned w = bits[tid];
-                int slot = before;
-                while (w) {
-                    const int j = __ffs(w) - 1;
-                    w &= w - 1;
-                    blk[(int64_t)c * kBlkMax + slot++] = lo + tid * 32 + j;
-                }
-                if (tid == 0) {
-                    flags[c] = 1;
-                    win[2 * c + 1] = (total * kBlkCols) | kCol16Bit | kBlockBit;
-                    atomicAdd(blk_chunks, 1);
-                }
-                u4 *out = reinterpret_cast<u4 *>(col16 + base);
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    unsigned v[8];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const int jj = 2 * k + (e >> 2), q = e & 3;
-                        const int col = col_idx[base + (jj * BLOCK + tid) * 4 + q];
-                        const int d = (col >> kBlkBits) - lo;
-                        const int sl = pref[d >> 5] + __popc(bits[d >> 5] & ((1u << (d & 31)) - 1u));
-                        v[e] = (unsigned)(sl * kBlkCols + (col & (kBlkCols - 1)));
-                    }
-                    u4 wv;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) wv[i] = v[2 * i] | (v[2 * i + 1] << 16);
-                    out[k * BLOCK + tid] = wv;
-                }
-            }
-        }
-    }
-    if (by_blocks || dry) return;
-
-    // ---- one contiguous span: offsets from its first column
-    if (tid == 0) {
-        flags[c] = contiguous ? 1 : 0;
-        if (contiguous) win[2 * c + 1] = wl | kCol16Bit;
-    }
-    if (!contiguous) return;
-    u4 *out = reinterpret_cast<u4 *>(col16 + base);
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        unsigned v[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int j = 2 * k + (e >> 2), q = e & 3;
-            v[e] = (unsigned)(col_idx[base + (j * BLOCK + tid) * 4 + q] - w0);
-        }
-        u4 w;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) w[i] = v[2 * i] | (v[2 * i + 1] << 16);
-        out[k * BLOCK + tid] = w;
-    }
-}
-
-// plan: the 16-bit copy was dropped -- chunks that had switched to a block list go back to "nothing staged"
-// (their win[] no longer describes a contiguous span; the 32-bit kernel then gathers them from global memory)
-__global__ void k_plan_unblock(int nchunks, int32_t *__restrict__ win)
-{
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= nchunks) return;
-    const int wl = win[2 * c + 1];
-    if (wl & kBlockBit) win[2 * c + 1] = 0;
-    else if (wl & kCol16Bit) win[2 * c + 1] = wl & ~kCol16Bit;
-}
-
-// plan: the kind of every chunk from its window word: f16[c] = has 16-bit columns, fs[c] = sorted
-__global__ void k_plan_kinds(int nchunks, const int32_t *__restrict__ win, int32_t *__restrict__ f16,
-                             int32_t *__restrict__ fs)
-{
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= nchunks) return;
-    const int wl = win[2 * c + 1];
-    f16[c] = (wl & kCol16Bit) ? 1 : 0;
-    fs[c] = (!(wl & kCol16Bit) && (wl & kSortedBit)) ? 1 : 0;
-}
-
-// plan: chunk lists from the exclusive scans of the two flag arrays (p16, ps hold the scans, win the kinds)
-__global__ void k_plan_lists(int nchunks, const int32_t *__restrict__ win, const int32_t *__restrict__ p16,
-                             const int32_t *__restrict__ ps, int32_t *__restrict__ list16,
-                             int32_t *__restrict__ list_sorted, int32_t *__restrict__ list32)
-{
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= nchunks) return;
-    const int wl = win[2 * c + 1];
-    if (wl & kCol16Bit) list16[p16[c]] = c;
-    else if (wl & kSortedBit) list_sorted[ps[c]] = c;
-    else list32[c - p16[c] - ps[c]] = c;
 }
 
 // rows that continue past their owner chunk: y[r] += carry[c+1] + carry[c+2] + ... in chunk order
@@ -1244,466 +798,153 @@ __global__ void k_carry_fixup(int nchunks, int chunk, const int32_t *__restrict_
     y[r] = s;
 }
 
-// plan: how many rows continue past their owner chunk (0 -> the fix-up launch is skipped)
-__global__ void k_plan_spans(int nchunks, int chunk, const int32_t *__restrict__ row_ptr,
-                             const int32_t *__restrict__ chunk_lb, int32_t *__restrict__ count)
+// ---------------------------------------------------------------------------
+// plan (TILED): what part of x chunk c stages in LDS.
+// (win[2c] = first staged column, win[2c+1] = staged length | flag bits: tiled_chunks.hpp)
+// A chunk whose whole column span [min, max] fits `maxpass` LDS regions is staged completely (in
+// ceil(span/region) passes).  A wider one stages ONE region centred on the mean column (the dense
+// part of a banded chunk that also holds a few very long rows) if that covers >= 1/4 of its
+// nonzeros.  stats[0] = chunks staged in a single pass with nothing outside, stats[1] = chunks
+// staged completely (any number of passes).
+__global__ __launch_bounds__(256)
+void k_plan_windows(int64_t nnz, int64_t cols, int nchunks, int chunk, const int32_t *__restrict__ col_idx,
+                    int32_t *__restrict__ win, int32_t *__restrict__ stats, int region, int maxpass, int sorted_from,
+                    int sorted_span, PlanCost cost, const int32_t *__restrict__ lb, const int32_t *__restrict__ row_ptr)
 {
-    int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= nchunks - 1) return;
-    const int lb0 = chunk_lb[c], lb1 = chunk_lb[c + 1];
-    if (lb1 == lb0) return;
-    if ((int64_t)row_ptr[lb1] > (int64_t)(c + 1) * chunk) atomicAdd(count, 1);
+    __shared__ int s_min[4], s_max[4], s_cnt[4];
+    __shared__ long long s_sum[4];
+    __shared__ int s_w0;
+    const int c = blockIdx.x;
+    const int wv = threadIdx.x >> 6;
+    const bool lane0 = (threadIdx.x & (kWave - 1)) == 0;
+    const int64_t base = (int64_t)c * chunk;
+    const int n = (int)((nnz - base) < chunk ? (nnz - base) : chunk);
+    int mn = 0x7fffffff, mx = -1;
+    long long sum = 0;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        int v = col_idx[base + i];
+        mn = v < mn ? v : mn;
+        mx = v > mx ? v : mx;
+        sum += v;
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        int a = __shfl_down(mn, o, kWave), b = __shfl_down(mx, o, kWave);
+        mn = a < mn ? a : mn;
+        mx = b > mx ? b : mx;
+        sum += __shfl_down(sum, o, kWave);
+    }
+    if (lane0) { s_min[wv] = mn; s_max[wv] = mx; s_sum[wv] = sum; }
+    __syncthreads();
+    for (int w = 0; w < 4; ++w) {  // every thread folds the four partials
+        mn = w == 0 ? s_min[0] : (s_min[w] < mn ? s_min[w] : mn);
+        mx = w == 0 ? s_max[0] : (s_max[w] > mx ? s_max[w] : mx);
+    }
+    // Staged or sorted?  Every staging pass re-reads `region` floats of x from L2 and costs a barrier pair and 16
+    // predicated LDS reads per lane; the sorted gather (sorted_body) touches every 128-byte line of the span about
+    // once, with no barrier, but streams 8 bytes per nonzero where a staged chunk with 16-bit columns streams 6.  The
+    // plan prices both for this chunk with the constants of PlanCost (fitted to measurements, DESIGN.md section 4) and
+    // takes the cheaper; the sum of the chunk prices is how the plan compares workgroup sizes.  sorted_from = 0:
+    // never sort; > 0: sort from that many passes on, whatever the prices (tuning knob SPMV_SORTED_FROM).
+    {
+        const int w0_line = mn & ~31;
+        const int64_t span_l = (int64_t)mx + 1 - w0_line;
+        const int64_t span4 = (int64_t)mx + 1 - (mn & ~3);
+        const int64_t passes = (span4 + region - 1) / region;
+        const int lines = (int)((span_l + 31) >> 5);
+        const int cost_staged = passes > maxpass ? cost.unstaged
+                                : (span4 < 65536 ? cost.c16_base + cost.c16_pass * (int)passes
+                                                 : cost.c32_base + cost.c32_pass * (int)passes);
+        const int rows_here = lb[c + 1] - lb[c];
+        // the longest piece of a row inside this chunk (the head segment included)
+        int longest = 0;
+        {
+            const int64_t lim = base + n;
+            for (int t = threadIdx.x; t <= rows_here; t += 256) {
+                const int64_t a = t == 0 ? base : (int64_t)row_ptr[lb[c] + t - 1];
+                int64_t b = t == 0 ? (int64_t)row_ptr[lb[c]] : (int64_t)row_ptr[lb[c] + t];
+                b = b < lim ? b : lim;
+                const int len = (int)(b - (a > base ? a : base));
+                longest = len > longest ? len : longest;
+            }
+#pragma unroll
+            for (int o = kWave / 2; o > 0; o >>= 1) {
+                const int v = __shfl_down(longest, o, kWave);
+                longest = v > longest ? v : longest;
+            }
+            __syncthreads();                 // s_cnt is free here (its first use comes later, behind another barrier)
+            if (lane0) s_cnt[wv] = longest;
+            __syncthreads();
+            longest = s_cnt[0];
+            for (int w = 1; w < 4; ++w) longest = s_cnt[w] > longest ? s_cnt[w] : longest;
+        }
+        const int cost_sorted = cost.sorted_base + (int)((int64_t)(chunk >= 16384 ? cost.sorted_line_1024 : cost.sorted_line_512) * lines / chunk) -
+                                (rows_here <= 16 ? cost.sorted_few_rows : 0);
+        const bool eligible = sorted_from != 0 && n == chunk && span_l <= sorted_span;
+        // ... and one rule the prices do not capture: a chunk that holds a piece of a long row (more than kHugeSeg
+        // nonzeros: power-law rows, whose own column window is what makes the span wide) is sorted from three passes on
+        // -- measured on c3 (4Mi rows, mean 32): 57.2 -> 60.2 % of peak over the priced choice
+        const bool long_row_rule = longest > cost.long_piece && passes >= 3;
+        const bool sort = eligible && (sorted_from > 0 ? span_l > (int64_t)region * (sorted_from - 1)
+                                                       : (cost_sorted < cost_staged || long_row_rule));
+        if (threadIdx.x == 0) {
+            atomicAdd(reinterpret_cast<unsigned long long *>(stats + 4), (unsigned long long)(sort ? cost_sorted : cost_staged));
+            if (long_row_rule) atomicAdd(&stats[3], 1);
+        }
+        if (sort) {
+            if (threadIdx.x == 0) {
+                win[2 * c] = w0_line;
+                win[2 * c + 1] = kSortedBit;
+                atomicAdd(&stats[2], 1);
+            }
+            return;
+        }
+    }
+    const int w0_full = mn & ~3;
+    const int64_t span = (int64_t)mx + 1 - w0_full;
+    if (span <= (int64_t)region * maxpass) {
+        if (threadIdx.x == 0) {
+            win[2 * c] = w0_full;
+            win[2 * c + 1] = (int32_t)span;
+            if (span <= region) atomicAdd(&stats[0], 1);
+            atomicAdd(&stats[1], 1);
+        }
+        return;
+    }
+    // too wide: one region around the mean column, if it is worth it
+    if (threadIdx.x == 0) {
+        const long long tot = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+        long long w0 = tot / (n > 0 ? n : 1) - region / 2;
+        if (w0 > cols - region) w0 = cols - region;
+        if (w0 < 0) w0 = 0;
+        s_w0 = (int)(w0 & ~3ll);
+    }
+    __syncthreads();
+    const int w0 = s_w0;
+    int cnt = 0;
+    for (int i = threadIdx.x; i < n; i += 256) cnt += ((unsigned)(col_idx[base + i] - w0) < (unsigned)region) ? 1 : 0;
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) cnt += __shfl_down(cnt, o, kWave);
+    if (lane0) s_cnt[wv] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        cnt = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        const bool stage = 4 * (int64_t)cnt >= n;
+        int64_t wl = region;
+        if (w0 + wl > cols) wl = cols - w0;
+        win[2 * c] = w0;
+        win[2 * c + 1] = stage ? ((int32_t)wl | kOutsideBit) : 0;
+    }
+}
+
+int launch_plan_windows(const spmv_csr &h, const ChunkPlan &p, int32_t *d_stats, const PlanCost &cost, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_plan_windows, dim3(p.nchunks), dim3(256), 0, s, h.nnz, h.cols, p.nchunks, chunk_of(p.block), h.d_col_idx,
+                       p.d_win, d_stats, p.region, p.maxpass, p.sorted_from, 1 << sorted_col_bits(p.block), cost, p.d_lb, h.d_row_ptr);
+    return check_launch("k_plan_windows");
 }
 
 // ---------------------------------------------------------------------------
-static int default_passes(int block) { return block == 1024 ? 12 : (block == 512 ? 4 : 2); }
-
-
-static int build_plan_impl(const spmv_csr &h, int block, int maxpass, hipStream_t s, ChunkPlan &p, int *single, int *full);
-
-// chunk boundaries (+ column windows when `maxpass` > 0) for workgroups of `block` threads; a failure leaves no plan
-static int build_plan(const spmv_csr &h, int block, int maxpass, hipStream_t s, ChunkPlan &p, int *single, int *full)
-{
-    const int rc = build_plan_impl(h, block, maxpass, s, p, single, full);
-    if (rc) p = ChunkPlan{};
-    return rc;
-}
-
-static int build_plan_impl(const spmv_csr &h, int block, int maxpass, hipStream_t s, ChunkPlan &p, int *single, int *full)
-{
-    const bool windows = maxpass > 0;
-    p = ChunkPlan{};
-    p.block = block;
-    p.maxpass = maxpass;
-    // LDS region: what 2048 resident threads per CU allow (a 144 KiB region with one 1024-thread
-    // workgroup per CU halves the staging passes of wide spans but measured 25-50 % slower)
-    p.region = region_words(block);
-    // tuning knob SPMV_PERSIST=0|1, read when the plan is made (default 0: the persistent form
-    // needs 80 VGPRs -> 6 waves/SIMD, and lost 7-40 % against 8 waves/SIMD one-shot workgroups)
-    if (const char *e = getenv("SPMV_PERSIST")) p.persist = atoi(e) != 0;
-    // tuning knob SPMV_SORTED_FROM=n: chunks whose span needs n staging passes or more gather in column order
-    // instead (0 = never; default -1: staged or sorted by the modelled cost of each chunk, PlanCost above)
-    p.sorted_from = windows && !p.persist ? kSortedFromDefault : 0;
-    if (const char *e = getenv("SPMV_SORTED_FROM")) {
-        const int v = atoi(e);
-        if (windows && !p.persist && v >= -1 && v <= 64) p.sorted_from = v;
-    }
-    PlanCost cost;
-    if (const char *e = getenv("SPMV_PLAN_COST")) {   // the fields of PlanCost in order (calibration runs): nine or all ten
-        int v[10];
-        const int got = sscanf(e, "%d,%d,%d,%d,%d,%d,%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &v[8], &v[9]);
-        if (got >= 9) {
-            cost.c16_base = v[0]; cost.c16_pass = v[1]; cost.c32_base = v[2]; cost.c32_pass = v[3];
-            cost.sorted_base = v[4]; cost.sorted_line_512 = v[5]; cost.sorted_line_1024 = v[6]; cost.sorted_few_rows = v[7];
-            cost.unstaged = v[8];
-            if (got == 10) cost.long_piece = v[9];
-        }
-    }
-    const int chunk = chunk_of(block);
-    p.nchunks = (int)((h.nnz + chunk - 1) / chunk);
-    if (single) *single = 0;
-    if (full) *full = 0;
-    if (p.nchunks == 0) return SPMV_OK;
-    SPMV_HIP_TRY(p.d_lb.alloc((size_t)p.nchunks + 1));
-    SPMV_HIP_TRY(p.d_carry.alloc((size_t)p.nchunks));
-    hipLaunchKernelGGL(k_plan_chunks, dim3((p.nchunks + 1 + 255) / 256), dim3(256), 0, s, h.rows, p.nchunks, chunk,
-                       h.d_row_ptr, p.d_lb);
-    int rc = check_launch("k_plan_chunks");
-    if (rc) return rc;
-    {
-        DevPtr<int32_t> cnt;
-        SPMV_HIP_TRY(cnt.alloc(1));
-        SPMV_HIP_TRY(hipMemsetAsync(cnt.get(), 0, sizeof(int32_t), s));
-        if (p.nchunks > 1) {
-            hipLaunchKernelGGL(k_plan_spans, dim3((p.nchunks - 1 + 255) / 256), dim3(256), 0, s, p.nchunks, chunk,
-                               h.d_row_ptr, p.d_lb, cnt.get());
-            if ((rc = check_launch("k_plan_spans"))) return rc;
-        }
-        int32_t spans = 0;
-        SPMV_HIP_TRY(hipMemcpyAsync(&spans, cnt.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        SPMV_HIP_TRY(hipStreamSynchronize(s));
-        p.spanning_rows = spans;
-    }
-    if (windows) {
-        // [2*nchunks] windows + 6 words of statistics (the last two: the 64-bit sum of the modelled chunk costs)
-        SPMV_HIP_TRY(p.d_win.alloc(2 * (size_t)p.nchunks + 6));
-        int32_t *d_stats = p.d_win + 2 * (size_t)p.nchunks;
-        SPMV_HIP_TRY(hipMemsetAsync(d_stats, 0, 6 * sizeof(int32_t), s));
-        hipLaunchKernelGGL(k_plan_windows, dim3(p.nchunks), dim3(256), 0, s, h.nnz, h.cols, p.nchunks, chunk,
-                           h.d_col_idx, p.d_win, d_stats, p.region, maxpass, p.sorted_from, 1 << sorted_col_bits(block),
-                           cost, p.d_lb, h.d_row_ptr);
-        if ((rc = check_launch("k_plan_windows"))) return rc;
-        int32_t stats[6] = {0, 0, 0, 0, 0, 0};
-        SPMV_HIP_TRY(hipMemcpyAsync(stats, d_stats, sizeof stats, hipMemcpyDeviceToHost, s));
-        SPMV_HIP_TRY(hipStreamSynchronize(s));
-        p.staged_single = stats[0];
-        p.staged_full = stats[1];
-        p.nsorted_marked = stats[2];
-        p.long_piece_chunks = stats[3];
-        uint64_t total_cost;
-        memcpy(&total_cost, &stats[4], sizeof total_cost);
-        p.model_cost = (double)total_cost * (double)chunk / 1024.0 / (double)(h.nnz > 0 ? h.nnz : 1);
-        if (single) *single = stats[0];
-        if (full) *full = stats[1];
-    }
-    return SPMV_OK;
-}
-
-template <int BLOCK>
-static int launch_plan_col16(const spmv_csr &h, ChunkPlan &p, int32_t *d_flags, int32_t *d_blk_chunks, const int32_t *d_blk_arg,
-                             int dry, hipStream_t s)
-{
-    hipLaunchKernelGGL((k_plan_col16<BLOCK>), dim3(p.nchunks), dim3(BLOCK), 0, s, h.nnz, h.d_col_idx, p.d_win, p.d_col16,
-                       d_flags, p.region, p.maxpass, const_cast<int32_t *>(d_blk_arg), d_blk_chunks, dry);
-    return check_launch("k_plan_col16");
-}
-
-// 16-bit column offsets + the two chunk lists for a finished TILED plan
-static int build_col16(const spmv_csr &h, ChunkPlan &p, hipStream_t s)
-{
-    p.col16_wanted = true;
-    if (p.nchunks == 0 || !p.d_win || p.persist) return SPMV_OK;
-    if (const char *e = getenv("SPMV_COL16")) {  // tuning knob: 0 keeps 32-bit columns everywhere
-        if (atoi(e) == 0) return SPMV_OK;
-    }
-    const size_t chunk = (size_t)chunk_of(p.block);
-    DevPtr<int32_t> flags, pos, total;
-    SPMV_HIP_TRY(flags.alloc((size_t)p.nchunks));
-    SPMV_HIP_TRY(pos.alloc((size_t)p.nchunks));
-    SPMV_HIP_TRY(total.alloc(1));
-    SPMV_HIP_TRY(p.d_col16.alloc(chunk * (size_t)p.nchunks));
-    // block lists (kBlkMax ids per chunk): SPMV_BLOCKS=0 keeps contiguous windows only
-    bool want_blocks = true;
-    if (const char *e = getenv("SPMV_BLOCKS")) want_blocks = atoi(e) != 0;
-    DevPtr<int32_t> nblk;
-    SPMV_HIP_TRY(nblk.alloc(1));
-    SPMV_HIP_TRY(hipMemsetAsync(nblk.get(), 0, sizeof(int32_t), s));
-    if (want_blocks) SPMV_HIP_TRY(p.d_blk.alloc((size_t)kBlkMax * (size_t)p.nchunks));
-    int rc;
-    auto run = [&](const int32_t *blk_arg, int dry) {
-        if (p.block == 256) return launch_plan_col16<256>(h, p, flags.get(), nblk.get(), blk_arg, dry, s);
-        if (p.block == 512) return launch_plan_col16<512>(h, p, flags.get(), nblk.get(), blk_arg, dry, s);
-        return launch_plan_col16<1024>(h, p, flags.get(), nblk.get(), blk_arg, dry, s);
-    };
-    if (want_blocks) {
-        // counting run first: the block-list instantiation of the kernel costs every chunk a few percent (spills),
-        // so lists are used only where at least a quarter of the chunks want one (a stencil: all of them; a few wide
-        // chunks among power-law rows: not worth it)
-        if ((rc = run(p.d_blk, 1))) return rc;
-        int32_t cand = 0;
-        SPMV_HIP_TRY(hipMemcpyAsync(&cand, nblk.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        SPMV_HIP_TRY(hipStreamSynchronize(s));
-        if (4 * (int64_t)cand < p.nchunks) (void)p.d_blk.reset();
-        SPMV_HIP_TRY(hipMemsetAsync(nblk.get(), 0, sizeof(int32_t), s));
-    }
-    if ((rc = run(p.d_blk, 0))) return rc;
-    SPMV_HIP_TRY(hipMemcpyAsync(pos.get(), flags.get(), sizeof(int32_t) * (size_t)p.nchunks, hipMemcpyDeviceToDevice, s));
-    if ((rc = exclusive_scan_i32(pos.get(), p.nchunks, total.get(), s))) return rc;
-    int32_t n16 = 0, nb = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&n16, total.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipMemcpyAsync(&nb, nblk.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipStreamSynchronize(s));
-    p.nblk_chunks = nb;
-    if (nb == 0) (void)p.d_blk.reset();
-    // too few eligible chunks to pay for the 2-byte copy (counting the sorted chunks with them: those read 4 bytes of
-    // perm instead of col_idx either way): back to 32-bit columns
-    if (2 * ((int64_t)n16 + p.nsorted_marked) < p.nchunks) {
-        hipLaunchKernelGGL(k_plan_unblock, dim3((p.nchunks + 255) / 256), dim3(256), 0, s, p.nchunks, p.d_win);
-        if ((rc = check_launch("k_plan_unblock"))) return rc;
-        SPMV_HIP_TRY(hipStreamSynchronize(s));
-        p.nblk_chunks = 0;
-        (void)p.d_col16.reset();
-        (void)p.d_blk.reset();
-    }
-    return SPMV_OK;
-}
-
-// how many chunks of the plan in `p` would stage a LIST of 256-column blocks in one pass (a counting run of k_plan_col16:
-// nothing is written)
-static int count_block_list_chunks(const spmv_csr &h, ChunkPlan &p, hipStream_t s, int *out)
-{
-    *out = 0;
-    if (p.nchunks == 0 || !p.d_win) return SPMV_OK;
-    DevPtr<int32_t> nblk, some;
-    SPMV_HIP_TRY(nblk.alloc(1));
-    SPMV_HIP_TRY(some.alloc(1));   // a non-null list pointer turns the block analysis on; a counting run never writes it
-    SPMV_HIP_TRY(hipMemsetAsync(nblk.get(), 0, sizeof(int32_t), s));
-    int rc;
-    if (p.block == 256) rc = launch_plan_col16<256>(h, p, nullptr, nblk.get(), some.get(), 1, s);
-    else if (p.block == 512) rc = launch_plan_col16<512>(h, p, nullptr, nblk.get(), some.get(), 1, s);
-    else rc = launch_plan_col16<1024>(h, p, nullptr, nblk.get(), some.get(), 1, s);
-    if (rc) return rc;
-    int32_t cnt = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&cnt, nblk.get(), sizeof cnt, hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipStreamSynchronize(s));
-    *out = cnt;
-    return SPMV_OK;
-}
-
-template <int BLOCK>
-static int launch_plan_sorted(const spmv_csr &h, ChunkPlan &p, const int32_t *d_slot, hipStream_t s)
-{
-    hipLaunchKernelGGL((k_plan_sorted<BLOCK>), dim3(p.nchunks), dim3(BLOCK), 0, s, h.d_col_idx, p.d_win, d_slot, p.d_perm);
-    return check_launch("k_plan_sorted");
-}
-
-// The last step of a TILED plan: the column-sorted words of the chunks marked kSortedBit, and the three chunk lists
-// (16-bit / sorted / 32-bit) the launch walks.
-static int build_lists(const spmv_csr &h, ChunkPlan &p, hipStream_t s)
-{
-    (void)p.d_list16.reset();
-    (void)p.d_list32.reset();
-    (void)p.d_list_sorted.reset();
-    (void)p.d_perm.reset();
-    p.n16 = p.nsorted = 0;
-    if (p.nchunks == 0 || !p.d_win || p.persist) return SPMV_OK;
-    int rc;
-    DevPtr<int32_t> f16, fs, t16, ts;
-    SPMV_HIP_TRY(f16.alloc((size_t)p.nchunks));
-    SPMV_HIP_TRY(fs.alloc((size_t)p.nchunks));
-    SPMV_HIP_TRY(t16.alloc(1));
-    SPMV_HIP_TRY(ts.alloc(1));
-    const unsigned g = (unsigned)((p.nchunks + 255) / 256);
-    hipLaunchKernelGGL(k_plan_kinds, dim3(g), dim3(256), 0, s, p.nchunks, p.d_win, f16.get(), fs.get());
-    if ((rc = check_launch("k_plan_kinds"))) return rc;
-    if ((rc = exclusive_scan_i32(f16.get(), p.nchunks, t16.get(), s))) return rc;
-    if ((rc = exclusive_scan_i32(fs.get(), p.nchunks, ts.get(), s))) return rc;
-    int32_t n16 = 0, ns = 0;
-    SPMV_HIP_TRY(hipMemcpyAsync(&n16, t16.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipMemcpyAsync(&ns, ts.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipStreamSynchronize(s));
-    p.n16 = n16;
-    p.nsorted = ns;
-    if (n16 == 0 && ns == 0) return SPMV_OK;   // every chunk runs the 32-bit body: no lists needed
-    SPMV_HIP_TRY(p.d_list16.alloc((size_t)n16));
-    SPMV_HIP_TRY(p.d_list_sorted.alloc((size_t)ns));
-    SPMV_HIP_TRY(p.d_list32.alloc((size_t)(p.nchunks - n16 - ns)));
-    hipLaunchKernelGGL(k_plan_lists, dim3(g), dim3(256), 0, s, p.nchunks, p.d_win, f16.get(), fs.get(), p.d_list16, p.d_list_sorted,
-                       p.d_list32);
-    if ((rc = check_launch("k_plan_lists"))) return rc;
-    if (ns > 0) {
-        // one slot of chunk words per SORTED chunk (fs.get(): its rank among them, the order of list_sorted)
-        SPMV_HIP_TRY(p.d_perm.alloc((size_t)chunk_of(p.block) * (size_t)ns));
-        if (p.block == 256) rc = launch_plan_sorted<256>(h, p, fs.get(), s);
-        else if (p.block == 512) rc = launch_plan_sorted<512>(h, p, fs.get(), s);
-        else rc = launch_plan_sorted<1024>(h, p, fs.get(), s);
-        if (rc) return rc;
-    }
-    SPMV_HIP_TRY(hipStreamSynchronize(s));   // the scans' temporaries are freed on return
-    return SPMV_OK;
-}
-
-int launch_adaptive(const spmv_csr &h, const float *x, float *y, bool tiled, hipStream_t s);
-
-// 16-bit column copy (where it pays) and the chunk lists of the plan in h.plan_tiled
-// A failure (an allocation of the 2-4 bytes per nonzero these copies take) leaves NO plan behind: k_plan_col16 may
-// already have rewritten win[] for columns that then never got their list, and a later spmv_csr_plan must not take the
-// half-built plan for a finished one.
-static int finish_tiled(spmv_csr &h, bool col16, hipStream_t s)
-{
-    int rc = col16 ? build_col16(h, h.plan_tiled, s) : SPMV_OK;
-    if (rc == SPMV_OK) rc = build_lists(h, h.plan_tiled, s);
-    if (rc) h.plan_tiled = ChunkPlan{};
-    return rc;
-}
-
-int plan_tiled_with(spmv_csr &h, int block, int maxpass, bool col16, hipStream_t s)
-{
-    if ((block != 256 && block != 512 && block != 1024) || maxpass < 1 || maxpass > 64) {
-        set_error("tiled plan: block %d / maxpass %d outside 256|512|1024 / 1..64", block, maxpass);
-        return SPMV_ERR_INVALID;
-    }
-    int rc = build_plan(h, block, maxpass, s, h.plan_tiled, nullptr, nullptr);
-    if (rc == SPMV_OK && col16) rc = build_col16(h, h.plan_tiled, s);
-    if (rc == SPMV_OK) rc = build_lists(h, h.plan_tiled, s);
-    if (rc) h.plan_tiled = ChunkPlan{};
-    return rc;
-}
-
-int plan_adaptive_with(spmv_csr &h, int block, hipStream_t s)
-{
-    if (block != 256) {   // the plain kernel is instantiated for 256-thread workgroups only
-        set_error("adaptive plan: block %d (only 256)", block);
-        return SPMV_ERR_INVALID;
-    }
-    return build_plan(h, 256, 0, s, h.plan_adaptive, nullptr, nullptr);
-}
-
-int plan_adaptive(spmv_csr &h, bool tiled, hipStream_t s)
-{
-    if (!tiled) {
-        if (h.plan_adaptive.block) return SPMV_OK;
-        return build_plan(h, 256, 0, s, h.plan_adaptive, nullptr, nullptr);
-    }
-    if (h.plan_tiled.block) return SPMV_OK;
-
-    // tuning knobs: SPMV_TILED_BLOCK = 256|512|1024 and SPMV_MAXPASS = 1..64 pin the geometry
-    int forced = 0, forced_pass = 0;
-    if (const char *e = getenv("SPMV_TILED_BLOCK")) forced = atoi(e);
-    if (forced != 256 && forced != 512 && forced != 1024) forced = 0;
-    if (const char *e = getenv("SPMV_MAXPASS")) forced_pass = atoi(e);
-    if (forced_pass < 1 || forced_pass > 64) forced_pass = 0;
-    if (forced) {
-        int rc = build_plan(h, forced, forced_pass ? forced_pass : default_passes(forced), s, h.plan_tiled, nullptr, nullptr);
-        return rc ? rc : finish_tiled(h, true, s);
-    }
-
-    // The default plan is a pure function of the matrix (chunk statistics below): two handles of the same matrix --
-    // two ranks, two runs -- get the same workgroup size, hence the same chunk cuts and bit-identical y.
-    // SPMV_AUTOTUNE=1 replaces it with timed trials (a few percent on some inputs, but the pick then depends on
-    // the device and the moment; spmv_csr_plan_get/_set carry such a pick to other handles).
-    bool autotune = false;
-    if (const char *e = getenv("SPMV_AUTOTUNE")) autotune = atoi(e) != 0 && h.nnz >= (1 << 20);
-    if (!autotune) {
-        // The smallest workgroup whose LDS region holds the whole column span of >= 90 % of the chunks in ONE pass
-        // (same LDS bytes and waves per CU for all three, but a larger workgroup pays more per barrier).  Failing
-        // that, 512 threads: the chunks whose span needs three passes or more gather in column order anyway (sorted
-        // chunks: no passes), and what is left stages in one or two.
-        const int cands[3] = {256, 512, 1024};
-        for (int k = 0; k < 3; ++k) {
-            int single = 0, full = 0;
-            int rc = build_plan(h, cands[k], default_passes(cands[k]), s, h.plan_tiled, &single, &full);
-            if (rc) return rc;
-            if (h.plan_tiled.nchunks == 0 || single >= 0.9 * h.plan_tiled.nchunks) return finish_tiled(h, true, s);
-        }
-        // Columns in a few clusters far apart (a 3-D stencil: r, r +- n, r +- n^2): no contiguous window holds a chunk's span,
-        // but a LIST of 256-column blocks does, in one pass -- then the smallest workgroup whose region holds the lists of
-        // >= 90 % of the chunks, like above (a 7-point stencil on 200^3 / 256^3 unknowns, forced sizes in one process: 256
-        // threads 72.0 / 77.8 % of peak, 512 71.5 / 76.1 %, 1024 64.6 / 69.3 %; round 1's timed trials picked 256 too.
-        // Round 2's prices know nothing of block lists and chose 1024: the regression of VERDICT round 2, item 1.)
-        {
-            bool want_blocks = true;
-            if (const char *e = getenv("SPMV_BLOCKS")) want_blocks = atoi(e) != 0;
-            for (int k = 0; k < 3 && want_blocks; ++k) {
-                int rc = build_plan(h, cands[k], default_passes(cands[k]), s, h.plan_tiled, nullptr, nullptr);
-                if (rc) return rc;
-                int lists = 0;
-                if ((rc = count_block_list_chunks(h, h.plan_tiled, s, &lists))) { h.plan_tiled = ChunkPlan{}; return rc; }
-                if (lists >= 0.9 * h.plan_tiled.nchunks) return finish_tiled(h, true, s);
-            }
-        }
-        // no workgroup size stages (nearly) everything in one pass: compare the modelled cost of 512 threads / 8
-        // passes and 1024 / 12 (a wide band gains from the larger chunk: more nonzeros per line of x; the inside of a
-        // power-law row does not, and the larger workgroup pays more per barrier: 3 % handicap)
-        int rc = build_plan(h, 1024, 12, s, h.plan_tiled, nullptr, nullptr);
-        if (rc) return rc;
-        const double cost1024 = h.plan_tiled.model_cost * 1.03;
-        // power-law rows: where most of the chunks that are not staged in one pass hold a piece of a long row, the span
-        // grows with the chunk (a row's columns spread over 8x its length or so), the larger chunk buys nothing and 512
-        // threads measured 9 % faster (c3: 61.1 % against 55.9 % of peak)
-        const ChunkPlan &q = h.plan_tiled;
-        const bool long_rows = 2 * (int64_t)q.long_piece_chunks >= (int64_t)q.nchunks - q.staged_single;
-        if ((rc = build_plan(h, 512, 8, s, h.plan_tiled, nullptr, nullptr))) return rc;
-        if (!long_rows && cost1024 < h.plan_tiled.model_cost && (rc = build_plan(h, 1024, 12, s, h.plan_tiled, nullptr, nullptr)))
-            return rc;
-        return finish_tiled(h, true, s);
-    }
-
-    // Autotune (the default for real sizes): the best (workgroup size, pass budget) depends on how the
-    // column spans are distributed -- a band, a band plus a few long rows, power-law rows -- and on
-    // how many chunks end up with 16-bit columns, so the plan times the kernels themselves on the
-    // candidates and keeps the fastest.  Costs a few launches,
-    // once per matrix (the reference pays a host-side format build per launcher call).
-    struct Cand { int block, maxpass; };
-    const Cand cands[] = {{256, 2}, {512, 4}, {512, 8}, {1024, 6}, {1024, 12}};
-    {
-        // nothing to tune when no candidate can stage a single chunk (columns without locality: every trial
-        // would run the same global-gather kernel, 100 ms of trials at 2^28 nonzeros) -- SPMV_PANEL's case
-        const Cand widest[] = {{1024, 12}, {512, 8}, {256, 2}};
-        bool any = false;
-        for (const Cand &c : widest) {
-            int single = 0, full = 0;
-            int rc0 = build_plan(h, c.block, c.maxpass, s, h.plan_tiled, &single, &full);
-            if (rc0) return rc0;
-            if (h.plan_tiled.nchunks == 0 || full > 0 || h.plan_tiled.nsorted_marked > 0) { any = true; break; }
-        }
-        if (!any) {
-            // no contiguous span fits -- but a few column clusters far apart (a big 3-D stencil) fit as block lists
-            int rc0 = build_plan(h, 512, 8, s, h.plan_tiled, nullptr, nullptr);
-            if (rc0 == SPMV_OK) rc0 = build_col16(h, h.plan_tiled, s);
-            if (rc0) return rc0;
-            any = h.plan_tiled.nblk_chunks > 0;
-        }
-        if (!any) return build_plan(h, 256, 2, s, h.plan_tiled, nullptr, nullptr);   // plain kernel, no 16-bit copy
-    }
-    DevPtr<float> xt, yt;
-    SPMV_HIP_TRY(xt.alloc((size_t)h.cols));
-    SPMV_HIP_TRY(yt.alloc((size_t)h.rows));
-    SPMV_HIP_TRY(hipMemsetAsync(xt.get(), 0, sizeof(float) * (size_t)(h.cols ? h.cols : 1), s));
-    hipEvent_t e0, e1;
-    SPMV_HIP_TRY(hipEventCreate(&e0));
-    SPMV_HIP_TRY(hipEventCreate(&e1));
-    struct Pick { int block = 0, maxpass = 0, narrow = 0, single = 0, chunks = 0; float ms = 0.0f; bool set = false; };
-    Pick best, second;
-    int rc = SPMV_OK;
-    // the plan in h.plan_tiled as it stands: two warm launches (code object, attribute, caches), then the best of
-    // `reps` timed groups of `launches` -- candidates differ by a few percent and one cold measurement picked the
-    // slower one every other run
-    auto time_plan = [&](int reps, int launches, float &ms) -> int {
-        int r = SPMV_OK;
-        for (int i = 0; i < 2 && r == SPMV_OK; ++i) r = launch_adaptive(h, xt.get(), yt.get(), true, s);
-        bool timed = true;
-        for (int rep = 0; rep < reps && timed && r == SPMV_OK; ++rep) {
-            timed = hipEventRecord(e0, s) == hipSuccess;
-            for (int i = 0; i < launches && r == SPMV_OK; ++i) r = launch_adaptive(h, xt.get(), yt.get(), true, s);
-            timed = timed && hipEventRecord(e1, s) == hipSuccess && hipEventSynchronize(e1) == hipSuccess;
-            float t = 0.0f;
-            timed = timed && hipEventElapsedTime(&t, e0, e1) == hipSuccess;
-            t /= (float)launches;
-            if (rep == 0 || t < ms) ms = t;
-        }
-        return r ? r : (timed ? SPMV_OK : SPMV_ERR_HIP);
-    };
-    for (const Cand &c : cands) {
-        ChunkPlan &p = h.plan_tiled;
-        int single = 0, full = 0;
-        if ((rc = build_plan(h, c.block, c.maxpass, s, p, &single, &full))) break;
-        if (p.nchunks == 0) break;
-        // time the candidate with 32-bit columns, then with the 16-bit copy: the copy usually wins
-        // (6 instead of 8 bytes per nonzero) but can lose on power-law rows
-        for (int narrow = 0; narrow < 2 && rc == SPMV_OK; ++narrow) {
-            if (narrow) {
-                if ((rc = build_col16(h, p, s))) break;
-                if (!p.d_col16) break;  // nothing eligible: same configuration as just timed
-            }
-            if ((rc = build_lists(h, p, s))) break;
-            float ms = 0.0f;
-            if ((rc = time_plan(3, 2, ms))) break;
-            Pick cur;
-            cur.block = c.block; cur.maxpass = c.maxpass; cur.narrow = narrow; cur.single = single; cur.chunks = p.nchunks;
-            cur.ms = ms; cur.set = true;
-            if (getenv("SPMV_AUTOTUNE_LOG"))
-                fprintf(stderr, "[spmv autotune] block=%d maxpass=%d col16=%d: %.4f ms\n", c.block, c.maxpass, narrow, ms);
-            if (!best.set || ms < best.ms) { second = best; best = cur; }
-            else if (!second.set || ms < second.ms) second = cur;
-        }
-        if (rc) break;
-        // every chunk already staged in one pass: larger workgroups only add barrier cost
-        if (best.single == best.chunks && best.block == c.block) break;
-    }
-    // a close runner-up gets a rematch with more launches (512- and 1024-thread workgroups are within a few percent
-    // of each other on most devices, and which one is ahead depends on the device)
-    if (rc == SPMV_OK && best.set && second.set && second.ms <= 1.08f * best.ms) {
-        Pick *both[2] = {&best, &second};
-        for (Pick *q : both) {
-            if ((rc = build_plan(h, q->block, q->maxpass, s, h.plan_tiled, nullptr, nullptr))) break;
-            if ((rc = finish_tiled(h, q->narrow != 0, s))) break;
-            if ((rc = time_plan(4, 4, q->ms))) break;
-            if (getenv("SPMV_AUTOTUNE_LOG"))
-                fprintf(stderr, "[spmv autotune] rematch block=%d maxpass=%d col16=%d: %.4f ms\n", q->block, q->maxpass,
-                        q->narrow, q->ms);
-        }
-        if (rc == SPMV_OK && second.ms < best.ms) best = second;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (rc) { h.plan_tiled = ChunkPlan{}; return rc; }
-    if (!best.set) return SPMV_OK;  // no nonzeros: the (empty) plan built last stands
-    // rebuild the winner (plans are cheap next to the trials)
-    if ((rc = build_plan(h, best.block, best.maxpass, s, h.plan_tiled, nullptr, nullptr))) return rc;
-    return finish_tiled(h, best.narrow != 0, s);
-}
-
 static int resident_workgroups(int device, int block, int waves_simd)
 {
     int per_cu = (waves_simd * 4 * kWave) / block;  // workgroups per CU by waves
@@ -1711,73 +952,58 @@ static int resident_workgroups(int device, int block, int waves_simd)
     return device_cus(device) * per_cu;
 }
 
+// One launch of a run kernel: `grid` workgroups of `block` threads with the plan's LDS region as dynamic LDS (the product buffer;
+// a staged x slice is never wider: plan cap = region).  More than 64 KiB of it (1024 threads) needs an opt-in per (kernel,
+// device), remembered in a static of this function: one per instantiation, that is, per kernel.
+template <auto Kernel, typename... Args>
+static int launch_region(const char *name, const spmv_csr &h, const ChunkPlan &p, int grid, int block, hipStream_t s,
+                         const Args &...args)
+{
+    const size_t lds = sizeof(float) * (size_t)p.region;
+    static LdsOptIn optin;
+    if (int rc = optin.ensure(reinterpret_cast<const void *>(Kernel), h.device, (int)lds)) return rc;
+    hipLaunchKernelGGL(Kernel, dim3(grid), dim3(block), lds, s, args...);
+    return check_launch(name);
+}
+
 template <int BLOCK, bool TILED, bool PERSIST>
-static int launch_range(const spmv_csr &h, const ChunkPlan &p, int chunk0, int nrun, const float *x, float *y,
-                        hipStream_t s, const int32_t *list = nullptr)
+static int launch_range(const spmv_csr &h, const ChunkPlan &p, int chunk0, int nrun, const float *x, float *y, hipStream_t s)
 {
     if (nrun <= 0) return SPMV_OK;
-    // dynamic LDS: the product buffer; a staged x slice is never wider (plan cap = region)
-    const size_t lds = sizeof(float) * (size_t)p.region;
-    static LdsOptIn optin;  // > 64 KiB of dynamic LDS needs the opt-in (BLOCK = 1024), once per device
-    if (int rc = optin.ensure(reinterpret_cast<const void *>(&k_adaptive<BLOCK, TILED, PERSIST>), h.device, (int)lds)) return rc;
     int grid = nrun;
     if (PERSIST) {
         const int res = resident_workgroups(h.device, BLOCK, waves_per_simd(BLOCK, true));
         if (grid > res) grid = res;
     }
-    hipLaunchKernelGGL((k_adaptive<BLOCK, TILED, PERSIST>), dim3(grid), dim3(BLOCK), lds, s, h.rows, h.nnz, h.cols,
-                       chunk0, nrun, h.d_row_ptr, h.d_col_idx, h.d_vals, x, y, p.d_lb, p.d_carry, p.d_win, list, p.region);
-    return check_launch("k_adaptive");
+    return launch_region<k_adaptive<BLOCK, TILED, PERSIST>>("k_adaptive", h, p, grid, BLOCK, s, h.rows, h.nnz, h.cols, chunk0, nrun,
+                                                            h.d_row_ptr, h.d_col_idx, h.d_vals, x, y, p.d_lb, p.d_carry, p.d_win,
+                                                            (const int32_t *)nullptr, p.region);
 }
 
+// BLOCKS: the block-list staging is compiled in only for plans that have such chunks
 template <int BLOCK, bool BLOCKS>
-static int launch_tiled16_t(const spmv_csr &h, const ChunkPlan &p, const float *x, float *y, hipStream_t s)
-{
-    const size_t lds = sizeof(float) * (size_t)p.region;
-    static LdsOptIn optin;
-    if (int rc = optin.ensure(reinterpret_cast<const void *>(&k_tiled16<BLOCK, BLOCKS>), h.device, (int)lds)) return rc;
-    hipLaunchKernelGGL((k_tiled16<BLOCK, BLOCKS>), dim3(p.n16), dim3(BLOCK), lds, s, h.rows, h.cols, p.n16, h.d_row_ptr,
-                       p.d_col16, h.d_vals, x, y, p.d_lb, p.d_carry, p.d_win,
-                       p.n16 == p.nchunks ? (const int32_t *)nullptr : p.d_list16, p.region, p.d_blk);
-    return check_launch("k_tiled16");
-}
-
-template <int BLOCK>
 static int launch_tiled16(const spmv_csr &h, const ChunkPlan &p, const float *x, float *y, hipStream_t s)
 {
     if (p.n16 <= 0) return SPMV_OK;
-    // the block-list staging is compiled in only for plans that have such chunks
-    return p.nblk_chunks > 0 ? launch_tiled16_t<BLOCK, true>(h, p, x, y, s) : launch_tiled16_t<BLOCK, false>(h, p, x, y, s);
+    return launch_region<k_tiled16<BLOCK, BLOCKS>>("k_tiled16", h, p, p.n16, BLOCK, s, h.rows, h.cols, p.n16, h.d_row_ptr, p.d_col16,
+                                                   h.d_vals, x, y, p.d_lb, p.d_carry, p.d_win,
+                                                   p.n16 == p.nchunks ? (const int32_t *)nullptr : p.d_list16.get(), p.region, p.d_blk);
 }
 
 template <int BLOCK, bool BLOCKS>
-static int launch_mixed_t(const spmv_csr &h, const ChunkPlan &p, const float *x, float *y, hipStream_t s)
-{
-    const size_t lds = sizeof(float) * (size_t)p.region;
-    static LdsOptIn optin;
-    if (int rc = optin.ensure(reinterpret_cast<const void *>(&k_tiled_mixed<BLOCK, BLOCKS>), h.device, (int)lds)) return rc;
-    const int n32 = p.nchunks - p.n16 - p.nsorted;
-    hipLaunchKernelGGL((k_tiled_mixed<BLOCK, BLOCKS>), dim3(p.nchunks), dim3(BLOCK), lds, s, h.rows, h.nnz, h.cols, n32,
-                       p.nsorted, p.n16, h.d_row_ptr, h.d_col_idx, p.d_col16, p.d_perm, h.d_vals, x, y, p.d_lb, p.d_carry,
-                       p.d_win, p.d_list32, p.d_list_sorted, p.d_list16, p.region, p.d_blk);
-    return check_launch("k_tiled_mixed");
-}
-
-template <int BLOCK>
 static int launch_mixed(const spmv_csr &h, const ChunkPlan &p, const float *x, float *y, hipStream_t s)
 {
-    return p.nblk_chunks > 0 ? launch_mixed_t<BLOCK, true>(h, p, x, y, s) : launch_mixed_t<BLOCK, false>(h, p, x, y, s);
+    const int n32 = p.nchunks - p.n16 - p.nsorted;
+    return launch_region<k_tiled_mixed<BLOCK, BLOCKS>>("k_tiled_mixed", h, p, p.nchunks, BLOCK, s, h.rows, h.nnz, h.cols, n32, p.nsorted,
+                                                       p.n16, h.d_row_ptr, h.d_col_idx, p.d_col16, p.d_perm, h.d_vals, x, y, p.d_lb,
+                                                       p.d_carry, p.d_win, p.d_list32, p.d_list_sorted, p.d_list16, p.region, p.d_blk);
 }
 
 template <int BLOCK>
 static int launch_sorted(const spmv_csr &h, const ChunkPlan &p, const float *x, float *y, hipStream_t s)
 {
-    const size_t lds = sizeof(float) * (size_t)p.region;
-    static LdsOptIn optin;
-    if (int rc = optin.ensure(reinterpret_cast<const void *>(&k_sorted<BLOCK>), h.device, (int)lds)) return rc;
-    hipLaunchKernelGGL((k_sorted<BLOCK>), dim3(p.nsorted), dim3(BLOCK), lds, s, h.rows, p.nsorted, h.d_row_ptr, p.d_perm,
-                       h.d_vals, x, y, p.d_lb, p.d_carry, p.d_win, p.d_list_sorted);
-    return check_launch("k_sorted");
+    return launch_region<k_sorted<BLOCK>>("k_sorted", h, p, p.nsorted, BLOCK, s, h.rows, p.nsorted, h.d_row_ptr, p.d_perm, h.d_vals, x,
+                                          y, p.d_lb, p.d_carry, p.d_win, p.d_list_sorted);
 }
 
 template <int BLOCK, bool TILED>
@@ -1786,9 +1012,10 @@ static int launch_either(bool persist, const spmv_csr &h, const ChunkPlan &p, co
     if constexpr (TILED) {
         if (!persist && (p.n16 > 0 || p.nsorted > 0)) {
             // every chunk has 16-bit columns: the lean kernel; otherwise all kinds in one launch
-            if (p.n16 == p.nchunks) return launch_tiled16<BLOCK>(h, p, x, y, s);
+            const bool lists = p.nblk_chunks > 0;
+            if (p.n16 == p.nchunks) return lists ? launch_tiled16<BLOCK, true>(h, p, x, y, s) : launch_tiled16<BLOCK, false>(h, p, x, y, s);
             if (p.nsorted == p.nchunks) return launch_sorted<BLOCK>(h, p, x, y, s);
-            return launch_mixed<BLOCK>(h, p, x, y, s);
+            return lists ? launch_mixed<BLOCK, true>(h, p, x, y, s) : launch_mixed<BLOCK, false>(h, p, x, y, s);
         }
     }
     if (!persist) return launch_range<BLOCK, TILED, false>(h, p, 0, p.nchunks, x, y, s);
@@ -1817,9 +1044,7 @@ int launch_adaptive(const spmv_csr &h, const float *x, float *y, bool tiled, hip
     // 32-bit tiled form has no registers for)
     const bool nothing_staged = tiled && p.block == 256 && p.staged_full == 0 && p.n16 == 0 && p.nsorted == 0;
     if (!tiled || nothing_staged) rc = launch_either<256, false>(persist, h, p, x, y, s);
-    else if (p.block == 256) rc = launch_either<256, true>(persist, h, p, x, y, s);
-    else if (p.block == 512) rc = launch_either<512, true>(persist, h, p, x, y, s);
-    else rc = launch_either<1024, true>(persist, h, p, x, y, s);
+    else rc = dispatch_block(p.block, [&](auto B) { return launch_either<decltype(B)::value, true>(persist, h, p, x, y, s); });
     if (rc) return rc;
     if (p.nchunks > 1 && p.spanning_rows > 0) {  // chunk boundaries that all fall on row boundaries need no fix-up
         hipLaunchKernelGGL(k_carry_fixup, dim3((p.nchunks - 1 + 255) / 256), dim3(256), 0, s, p.nchunks,

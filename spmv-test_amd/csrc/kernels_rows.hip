@@ -21,13 +21,6 @@
 
 namespace spmv {
 
-// A/B builds (tools/build_variant.sh): what a kernel costs without its gathers / its long rows / its in-order sums
-#ifdef SPMV_R_NOGATHER
-#define XG(c, k) x[((c) & 0) + ((k) & 1023)]
-#else
-#define XG(c, k) x[(c)]
-#endif
-
 // One row by the whole wave IN THE ORACLE'S ORDER: 64 lane-consecutive products per trip (coalesced, each rounded
 // once, the next trip's loads already in flight), then added in order -- lane 0's first -- through a readlane chain.
 // Every lane returns the sum.
@@ -90,17 +83,13 @@ __global__ __launch_bounds__(kBlock) void k_scalar(int64_t rows, const int32_t *
     const int32_t b = r < rows ? row_ptr[r] : 0, e = r < rows ? row_ptr[r + 1] : 0;
     if (we - wb <= kScalarCap) {
         for (uint32_t k = (uint32_t)wb + threadIdx.x; k < (uint32_t)we; k += kBlock) {   // (unsigned: k + kBlock may pass INT_MAX)
-            const float p = XG(col_idx[k], k) * vals[k];
+            const float p = x[col_idx[k]] * vals[k];
             prod[k - (uint32_t)wb] = p;
         }
         __syncthreads();
         if (r < rows) {
             float acc = 0.0f;
-#ifdef SPMV_R_NOSUM
-            if (e > b) acc = prod[b - wb];
-#else
             for (int32_t k = b; k < e; ++k) acc = acc + prod[k - wb];
-#endif
             y[r] = acc;
         }
     } else {
@@ -335,11 +324,7 @@ __device__ __forceinline__ void bundle_multiply(int lane, int32_t len, __amdgpu_
             float xv[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-#ifdef SPMV_R_NOGATHER
-                const int32_t cc = (lo < 0 ? 0 : lo) + (((t + u) * kWave + lane) & 1023);
-#else
                 const int32_t cc = c[t + u];
-#endif
                 if (win) xv[u] = win[min((uint32_t)(cc - lo), wlast)];   // (slots past the end hold column 0; lo = 0: cc is an offset)
                 else xv[u] = BUFX ? buf_f32(xr, cc << 2) : x[cc];
             }
@@ -895,7 +880,6 @@ int launch_wave(spmv_csr &h, const float *x, float *y, bool pipelined, hipStream
         // gather goes to memory, from three workgroups per CU
         if (p.windows && !plain_bundle) launch_bundle<1>(h, p, x, y, p.d_blk_lo, p.d_col16, s);
         else launch_bundle<0>(h, p, x, y, nullptr, nullptr, s);
-#ifndef SPMV_R_NOLONG
         if (p.n_long) {
             if (int rc = check_launch("k_wave_bundle")) return rc;
             const dim3 pgrid((unsigned)((p.pieces + kRowsPerBlock - 1) / kRowsPerBlock));
@@ -909,7 +893,6 @@ int launch_wave(spmv_csr &h, const float *x, float *y, bool pipelined, hipStream
             hipLaunchKernelGGL(k_wave_combine, dim3((unsigned)((p.n_long + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, p.n_long,
                                p.d_long_row, p.d_long_first, p.d_partial, y);
         }
-#endif
     } else {
         launch_row_slices(blocks, kRowsPerBlock, [&](dim3 grid, int64_t row0) {
             hipLaunchKernelGGL(k_wave<false>, grid, dim3(kBlock), 0, s, row0, h.rows, h.d_row_ptr, h.d_col_idx, h.d_vals, x, y);

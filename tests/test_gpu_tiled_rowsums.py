@@ -13,7 +13,8 @@ Two problems per workgroup size (tests/_tiled_order.py, Problem):
            33 words), more 16-lane segments than one round of groups takes and fewer, rows whose products are all -0.0 and
            rows that hold +Inf or -Inf beside finite rows, and a ragged last chunk.
 Each runs at SPMV_TILED_BLOCK = 256, 512 and 1024 through the 16-bit body, the 32-bit body (SPMV_COL16=0), the sorted body
-(SPMV_SORTED_FROM=1 with SPMV_BLOCKS=0), the 16-bit body over block lists (SPMV_SORTED_FROM=1) and SPMV_ADAPTIVE.
+(SPMV_SORTED_FROM=1 with SPMV_BLOCKS=0), the 16-bit body over block lists (SPMV_SORTED_FROM=1), SPMV_ADAPTIVE and the
+persistent form of the 32-bit body (SPMV_PERSIST=1).
 """
 import re
 
@@ -32,6 +33,8 @@ MODES = {
     "sorted": ("tiled", {"SPMV_SORTED_FROM": "1", "SPMV_BLOCKS": "0"}, {"sorted_chunks": "most"}),
     "blocks": ("tiled", {"SPMV_SORTED_FROM": "1"}, {"block_list_chunks": "most"}),
     "adaptive": ("adaptive", {}, {}),
+    # (the persistent 32-bit body: resident workgroups that walk their XCD's chunks, the row sums one word at a time)
+    "persist": ("tiled", {"SPMV_PERSIST": "1"}, {"col16_chunks": "none", "sorted_chunks": "none"}),
 }
 
 
@@ -82,6 +85,8 @@ def test_row_sums_have_the_documented_order(pkg, gpu, device_problem, monkeypatc
             n = _field(plan, name)
             # (the ragged last chunk always takes the 32-bit body)
             assert (n == 0) if how == "none" else (n >= chunks - 1), (name, how, plan)
+        if mode == "persist":
+            assert _field(plan, "persist") == 1, plan
         y = torch.full((P.rows,), float("nan"), dtype=torch.float32, device=gpu)
         A.run(v, d_x, y)
         torch.cuda.synchronize()

@@ -87,8 +87,8 @@ def _wrapped_sum(c, r, k_true, chunk):
 
 @pytest.mark.parametrize("name", "AB")
 def test_a_wrapped_chunk_offset_changes_the_row_sums(name):
-    """What the (int64_t) casts of c * chunk in kernels_adaptive.hip protect: past 2^29 nonzeros a signed 32-bit byte
-    offset wraps, past 2^30 an unsigned one does.  The wrapped offset selects other nonzeros of the same valid array,
+    """What the (int64_t) casts of c * chunk in kernels_adaptive.hip and plan_adaptive.hip protect: past 2^29 nonzeros a signed
+    32-bit byte offset wraps, past 2^30 an unsigned one does.  The wrapped offset selects other nonzeros of the same valid array,
     whose formula values give another row sum -- wrong, finite, and invisible to every test below 2^29 nonzeros."""
     c = L.case(name)
     for chunk in (4096, 8192, 16384):

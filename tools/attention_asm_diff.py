@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""tools/attention_asm_diff.py OLD.s NEW.s -- do the kernels of two builds of a kernel file have the same code?
+"""tools/attention_asm_diff.py OLD.s NEW.s [NEW2.s ...] -- do the kernels of two builds of a kernel file have the same code?
 
 Both files are device assembly of one csrc/*.hip file (hipcc --offload-arch=gfx950 -O3 --cuda-device-only -S, the Makefile's
-other flags), OLD at an earlier commit, NEW at this one.  The text of every kernel (from its .globl line to the next
-kernel's: the instruction stream, the .amdhsa_ block, the .set lines of its resource counts) is compared after what only
+other flags), OLD at an earlier commit, NEW at this one.  Where the file has been split since, name every part: OLD is
+compared against the union of their kernels, and a kernel must not appear in two of them.  The text of every kernel (from
+its .globl line to the next kernel's: the instruction stream, the .amdhsa_ block, the .set lines of its resource counts) is compared after what only
 names it is normalised: the kernel's own symbol becomes a placeholder, the function numbers in local labels (.LBB12_3,
 .Lfunc_end12) and in the comments that name a loop (Header=BB12_3, Child Loop BB12_5) are dropped: they count the kernels
-before this one in the file (so do the blanks that align a label's comment), and the .section lines that only name the next
-kernel are left out.
+before this one in the file (so do the blanks that align a label's comment), and the lines that only lead in the next
+kernel (.section, .text, its .protected line) or pad the text behind a file's last kernel are left out: which kernel
+follows changes when a file is split.
 
 Which kernel of NEW is which of OLD is read off the mangled symbol itself (c++filt does not know every element type): a
 k_attn_* kernel is its name, V, VEC, its element type (float where the symbol has none, as before the 16-bit calls) and
@@ -24,6 +26,8 @@ import sys
 ELEMENTS = {None: "float", "f": "float", "NS_4bf16E": "bf16", "DF16_": "fp16"}
 ATTN = re.compile(r"_ZN4spmv12_GLOBAL__N_1\d+(k_attn_[a-z_]+?)(?:_bias)?ILi(\d+)ELb([01])E(f|NS_4bf16E|DF16_)?(?:J(?:NS_8AttnBiasE)?E)?EEv")
 GROUPS = re.compile(r"_ZN4spmv12_GLOBAL__N_1\d+(k_(?:spmm|sddmm)_(?:rows|pieces))ILi(\d+)ELb([01])E(f|NS_4bf16E|DF16_)?EEv")
+# (the lines that lead in the next kernel, or pad the text behind a file's last one)
+NEXT = re.compile(r"\t\.text$|\t\.(?:protected|weak|hidden)\t\w+ +; -- Begin function |\t\.p2alignl 6, 3212836864$|\t\.fill 256, 4, 3212836864$")
 COMBINE = re.compile(r"_ZN4spmv12_GLOBAL__N_1\d+(k_spmm_combine)(?:I(f|NS_4bf16E|DF16_)E)?E")
 
 
@@ -54,12 +58,17 @@ def kernels(path: str) -> dict:
         symbol = re.match(r"\t\.globl\t(\w+)", chunk).group(1)
         chunk = re.sub(r"\b" + symbol + r"\b", "{kernel}", chunk)
         assert key(symbol) not in out, key(symbol)
-        out[key(symbol)] = "\n".join(l for l in chunk.splitlines() if not l.startswith("\t.section\t.text"))
+        out[key(symbol)] = "\n".join(l for l in chunk.splitlines() if not l.startswith("\t.section\t.text") and not NEXT.match(l))
     return out
 
 
 def main() -> int:
-    old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
+    old, new = kernels(sys.argv[1]), {}
+    for path in sys.argv[2:]:
+        more = kernels(path)
+        twice = [n for n in more if n in new]
+        assert not twice, f"{path}: in an earlier NEW file too: {twice}"
+        new.update(more)
     missing = [n for n in old if n not in new]
     differ = [n for n in old if n in new and old[n] != new[n]]
     extra = [n for n in new if n not in old]
