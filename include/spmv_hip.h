@@ -265,6 +265,8 @@ SPMV_API int64_t spmv_csr_transpose_map_bytes(const spmv_csr_t *t);
  *                                             rows < 2^30 up to k = 16, < 2^29 up to k = 32, < 2^28 up to k = 64
  *   spmv_csr_sddmm                            the same as spmv_csr_spmm (rows x lanes per row < 2^32); any nnz < 2^31
  *   spmv_csr_spmm_16, spmv_csr_sddmm_16       the same as spmv_csr_spmm and spmv_csr_sddmm (the lanes per row are those of k)
+ *   spmv_csr_spmm_cols                        rows x 16 lanes x ceil(k / 64) column tiles < 2^32 (one launch carries all tiles)
+ *   spmv_csr_sddmm_cols                       rows x 16 lanes < 2^32 (rows < 2^28) at every k
  *   spmv_csr_row_softmax                      any handle (rows, nnz < 2^31; a wavefront per 64 rows, byte offsets 64-bit)
  *   spmv_csr_row_softmax_backward             the same as spmv_csr_row_softmax
  *   spmv_csr_attention_forward, _backward_q,  the same as spmv_csr_spmm with max(k, kv) in the place of k (rows x lanes per
@@ -659,6 +661,38 @@ SPMV_API int spmv_csr_attention_backward_kv_16(spmv_csr_t *t, const spmv_attn_he
 SPMV_API int spmv_csr_spmm_16(spmv_csr_t *h, int dtype, int k, const void *d_X, int64_t ldx, void *d_Y, int64_t ldy, void *stream);
 SPMV_API int spmv_csr_sddmm_16(spmv_csr_t *h, int dtype, int k, const void *d_U, int64_t ldu, const void *d_X, int64_t ldx,
                                float *d_out, void *stream);
+
+/* ---- SpMM and SDDMM at any k: column tiles of 64 in one call -------------------------------------------------------------------
+ * spmv_csr_spmm and spmv_csr_sddmm (and their _16 forms) for 1 <= k <= SPMV_COLS_MAX_K columns in one call.  dtype is
+ * SPMV_ATTN_FP32 (fp32 matrices, 16-byte aligned, every ld in floats), SPMV_ATTN_BF16 or SPMV_ATTN_FP16 (8-byte aligned, every
+ * ld in 16-bit elements), the codes of the _wide attention calls; vals, d_out and every sum are fp32 as in the narrow calls.
+ * Column tile t of a call at width k is the columns [64t, 64t + k_t), k_t = min(64, k - 64t), of m = ceil(k / 64) tiles.
+ *   SpMM.   Y[:, c] is bit for bit what spmv_csr_spmm (spmv_csr_spmm_16) writes for that column in any narrow call that
+ *           contains it: the order per column is unchanged -- fma in storage order from +0; a row of more than 512 nonzeros per
+ *           piece of 512, the pieces' sums added in piece order from +0; a 16-bit Y rounded once at its store -- and batch
+ *           invariance now holds at every k.  Y at columns [k, ldy) is never written; X at columns >= k is never read into a sum.
+ *   SDDMM.  out[n] = (..((r_0 + r_1) + r_2) .. + r_(m-1)): fp32 additions in tile order, starting from r_0's value and not from
+ *           +0 (a result of -0 in a single tile stays -0).  r_t is exactly the number spmv_csr_sddmm defines for U[:, tile t] and
+ *           X[:, tile t] at width k_t: lane partials by fma from +0, then the xor butterfly ("SDDMM" above).  No lane partial is
+ *           carried from one tile into the next tile's butterfly.  At k <= 64 the bits are the narrow call's.  16-bit operands
+ *           are widened exactly; out is fp32.  out is written once per nonzero and never read; vals is never read; nothing
+ *           depends on any ld, on the row's length or pieces, on other rows or on the handle.
+ * The plan: spmv_csr_spmm_plan_cols(h, k_max) does what spmv_csr_spmm_plan does and also allocates a scratch of its own for the
+ * long rows' SpMM partials, pieces x ceil(k_max / 64) x 64 floats: a separate allocation, so the narrow calls' scratch and
+ * spmv_csr_spmm_describe's line keep their size and text; spmv_csr_spmm_plan_bytes counts it once it exists.  It only grows,
+ * waits for the stream before it replaces an allocation, and a repeated call changes nothing.  Both _cols calls need it to
+ * cover k, else SPMV_ERR_NOT_PLANNED: one rule at every width, also on a handle without a long row.  After the plan the two
+ * calls allocate nothing and never wait: graph-capturable.  Runs of spmv_csr_spmm_cols on one handle must be stream-ordered.
+ * Limits: 1 <= k, k_max <= SPMV_COLS_MAX_K; every ld >= k; rows x 16 lanes x m tiles < 2^32 work-items for SpMM (one launch
+ * carries all tiles), rows x 16 lanes < 2^32 for SDDMM (the tiles are walked inside the kernel).
+ * Refusals (SPMV_ERR_INVALID, a message that names the function, nothing launched, Y / out untouched): a dtype other than the
+ * three, k or k_max out of range, an ld below k, a matrix not aligned for its dtype, d_out not 4-byte aligned, a missing
+ * pointer (with the narrow calls' exceptions for empty dimensions), a null handle, another current device. */
+#define SPMV_COLS_MAX_K 65536
+SPMV_API int spmv_csr_spmm_plan_cols(spmv_csr_t *h, int k_max, void *stream);
+SPMV_API int spmv_csr_spmm_cols(spmv_csr_t *h, int dtype, int k, const void *d_X, int64_t ldx, void *d_Y, int64_t ldy, void *stream);
+SPMV_API int spmv_csr_sddmm_cols(spmv_csr_t *h, int dtype, int k, const void *d_U, int64_t ldu, const void *d_X, int64_t ldx,
+                                 float *d_out, void *stream);
 
 /* ---- Fused attention with an additive bias per nonzero, and the bias's gradient: all three passes ---------------------------
  * O = softmax_rows(scale * Q K^T + B at the pattern) V with one fp32 number per (query, key) pair of the pattern: a

@@ -69,6 +69,9 @@ SIGNATURES = {
     # the 16-bit calls: `int dtype` after the handle, every dense matrix a void *
     "spmv_csr_spmm_16": (C.c_int, [_H, C.c_int, C.c_int, _vp, C.c_int64, _vp, C.c_int64, _vp]),
     "spmv_csr_sddmm_16": (C.c_int, [_H, C.c_int, C.c_int, _vp, C.c_int64, _vp, C.c_int64, _f32p, _vp]),
+    "spmv_csr_spmm_plan_cols": (C.c_int, [_H, C.c_int, _vp]),
+    "spmv_csr_spmm_cols": (C.c_int, [_H, C.c_int, C.c_int, _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "spmv_csr_sddmm_cols": (C.c_int, [_H, C.c_int, C.c_int, _vp, C.c_int64, _vp, C.c_int64, _f32p, _vp]),
     "spmv_csr_row_softmax": (C.c_int, [_H, C.c_float, _f32p, _f32p, _vp]),
     "spmv_csr_row_softmax_backward": (C.c_int, [_H, C.c_float, _f32p, _f32p, _f32p, _vp]),
     "spmv_csr_attention_plan": (C.c_int, [_H, _vp]),
@@ -141,6 +144,7 @@ for _pass, _ops in _ATTN_PASSES.items():
     # the wide call of the pass (widths up to 128): exactly the _bias arguments; a null bias means none
     SIGNATURES[f"spmv_csr_attention_{_pass}_wide"] = SIGNATURES[f"spmv_csr_attention_{_pass}_bias"]
 ATTN_FP32, ATTN_BF16, ATTN_FP16 = 0, 1, 2      # enums of include/spmv_hip.h: the dtype of a _16 call (1, 2) or a _bias call
+COLS_MAX_K = 65536                             # SPMV_COLS_MAX_K: the widest k of spmm_cols / sddmm_cols
 # test only: the bounds-checked build of the library (SPMV_CHECK_BOUNDS) and its sites (csrc/spmv_internal.hpp BoundsSite)
 CHECKED_LIB_PATH = PKG_DIR / "lib" / "libspmv_hip_checked.so"
 BOUNDS_SITES = ("k_bs_sums prod", "k_bs_sums acc", "k_bin_sums prod", "k_bin_sums r16", "k_bs_products c16",
@@ -375,6 +379,34 @@ class CsrMatrix:
         else:
             check(lib().spmv_csr_sddmm_16(self._h, dtype, k, _ptr(U), U.stride(0), _ptr(X), X.stride(0), _ptr(out),
                                           _stream_handle(stream)))
+
+    # -- both products at any k, in column tiles of 64 (spmv_csr_spmm_cols, spmv_csr_sddmm_cols) --------------------------
+    def spmm_plan_cols(self, k_max: int, stream=None) -> None:
+        """spmm_plan() and the scratch of the long rows' partials for spmm_cols at up to k_max columns (it only grows).  Both
+        _cols calls need it to cover their k."""
+        check(lib().spmv_csr_spmm_plan_cols(self._h, k_max, _stream_handle(stream)))
+
+    def spmm_cols(self, X, Y, stream=None) -> None:
+        """spmm(X, Y) for any k = X.shape[1] up to COLS_MAX_K in one call: every column's bits are the narrow call's."""
+        dtype = self._dense_dtype("spmm_cols", X=X, Y=Y)
+        k = X.shape[1]
+        if X.shape[0] != self.cols or Y.shape[0] != self.rows or Y.shape[1] < k:
+            raise ValueError(f"spmm_cols: X {tuple(X.shape)} and Y {tuple(Y.shape)} do not fit a {self.rows} x {self.cols} matrix")
+        check(lib().spmv_csr_spmm_cols(self._h, dtype, k, _ptr(X), X.stride(0), _ptr(Y), Y.stride(0), _stream_handle(stream)))
+
+    def sddmm_cols(self, U, X, out, stream=None) -> None:
+        """sddmm(U, X, out) for any k up to COLS_MAX_K in one call: per column tile of 64 the narrow call's number, the tiles'
+        numbers added in fp32 in tile order from tile 0's."""
+        import torch
+        dtype = self._dense_dtype("sddmm_cols", U=U, X=X)
+        if not isinstance(out, torch.Tensor) or out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("sddmm_cols: out must be a contiguous 1-D float32 tensor")
+        k = U.shape[1]
+        if U.shape[0] != self.rows or X.shape[0] != self.cols or X.shape[1] != k or out.shape[0] != self.nnz:
+            raise ValueError(f"sddmm_cols: U {tuple(U.shape)}, X {tuple(X.shape)} and out {tuple(out.shape)} do not fit a "
+                             f"{self.rows} x {self.cols} matrix with {self.nnz} nonzeros")
+        check(lib().spmv_csr_sddmm_cols(self._h, dtype, k, _ptr(U), U.stride(0), _ptr(X), X.stride(0), _ptr(out),
+                                        _stream_handle(stream)))
 
     # -- row softmax over the pattern and its backward (spmv_csr_row_softmax; the plan is spmm_plan's) ---------------
     def _nnz_arrays(self, what: str, **arrays) -> None:

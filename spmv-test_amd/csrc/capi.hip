@@ -694,6 +694,85 @@ int spmv_csr_sddmm_16(spmv_csr_t *h, int dtype, int k, const void *d_U, int64_t 
     return dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
 }
 
+// ---- the same two products at any k, in column tiles of 64 (fp32, bf16 or fp16 matrices; kernels_spmm.hip, kernels_sddmm.hip) ----
+int spmv_csr_spmm_plan_cols(spmv_csr_t *h, int k_max, void *stream)
+{
+    const char *what = "spmv_csr_spmm_plan_cols";
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (k_max < 1 || k_max > SPMV_COLS_MAX_K) {
+        set_error("%s: k_max = %d (need 1 <= k_max <= %d)", what, k_max, (int)SPMV_COLS_MAX_K);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(h->device, what)) return rc;
+    return plan_spmm_cols(*h, k_max, (hipStream_t)stream);
+}
+
+// What the two _cols calls check alike, in the order of the narrow calls: the dtype, 1 <= k <= SPMV_COLS_MAX_K and both ld >= k
+// (na, nb: the names of the two matrices and of their ld), the pointers (pa of ra rows, pb of rb rows) present and aligned for
+// the dtype (16 bytes of floats, 8 of 16-bit elements), the byte offsets, the device, the plan.  out: SDDMM's, else null.
+static int cols_args(const spmv_csr_t *h, int dtype, int k, const char *na, const void *pa, int64_t lda, int64_t ra, const char *nb,
+                     const void *pb, int64_t ldb, int64_t rb, bool has_out, const float *d_out, const char *what)
+{
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (dtype != SPMV_ATTN_FP32 && dtype != SPMV_ATTN_BF16 && dtype != SPMV_ATTN_FP16) {
+        set_error("%s: dtype = %d (need SPMV_ATTN_FP32 = %d, SPMV_ATTN_BF16 = %d or SPMV_ATTN_FP16 = %d)", what, dtype, (int)SPMV_ATTN_FP32,
+                  (int)SPMV_ATTN_BF16, (int)SPMV_ATTN_FP16);
+        return SPMV_ERR_INVALID;
+    }
+    const bool f32 = dtype == SPMV_ATTN_FP32;
+    const char *lc = has_out ? "u" : "x", *ld2 = has_out ? "x" : "y";     // (ldu, ldx of SDDMM; ldx, ldy of SpMM)
+    if (k < 1 || k > SPMV_COLS_MAX_K || lda < k || ldb < k) {
+        set_error("%s: k = %d, ld%s = %lld, ld%s = %lld (need 1 <= k <= %d, ld%s >= k, ld%s >= k)", what, k, lc, (long long)lda, ld2,
+                  (long long)ldb, (int)SPMV_COLS_MAX_K, lc, ld2);
+        return SPMV_ERR_INVALID;
+    }
+    if ((!pa && ra > 0) || (!pb && rb > 0) || (has_out && !d_out && h->nnz > 0)) {
+        if (has_out) set_error("%s: null %s, %s or out", what, na, nb);
+        else set_error("%s: null %s or %s", what, na, nb);
+        return SPMV_ERR_INVALID;
+    }
+    if (f32 ? !aligned16(pa) || !aligned16(pb) : !aligned8(pa) || !aligned8(pb)) {
+        set_error("%s: %s and %s must be %d-byte aligned", what, na, nb, f32 ? 16 : 8);
+        return SPMV_ERR_INVALID;
+    }
+    if (has_out && reinterpret_cast<uintptr_t>(d_out) % 4 != 0) { set_error("%s: out must be 4-byte aligned", what); return SPMV_ERR_INVALID; }
+    const int64_t es = f32 ? 4 : 2;
+    if (lda > INT64_MAX / es / (ra > 0 ? ra : 1) || ldb > INT64_MAX / es / (rb > 0 ? rb : 1)) {
+        set_error("%s: ld%s = %lld or ld%s = %lld overflows 64-bit byte offsets", what, lc, (long long)lda, ld2, (long long)ldb);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(h->device, what)) return rc;
+    if (!h->plan_spmm.ready || !h->plan_spmm.cols_k) { set_error("%s used before spmv_csr_spmm_plan_cols", what); return SPMV_ERR_NOT_PLANNED; }
+    if (k > h->plan_spmm.cols_k) {
+        set_error("%s: k = %d, the plan covers %d (spmv_csr_spmm_plan_cols)", what, k, h->plan_spmm.cols_k);
+        return SPMV_ERR_NOT_PLANNED;
+    }
+    return SPMV_OK;
+}
+
+int spmv_csr_spmm_cols(spmv_csr_t *h, int dtype, int k, const void *d_X, int64_t ldx, void *d_Y, int64_t ldy, void *stream)
+{
+    if (int rc = cols_args(h, dtype, k, "X", d_X, ldx, h ? h->cols : 0, "Y", d_Y, ldy, h ? h->rows : 0, false, nullptr, "spmv_csr_spmm_cols"))
+        return rc;
+    auto run = [&](auto e) {
+        using E = decltype(e);
+        return launch_spmm_cols(*h, k, (const E *)d_X, ldx, (E *)d_Y, ldy, (hipStream_t)stream);
+    };
+    return dtype == SPMV_ATTN_FP32 ? run(float{}) : dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+}
+
+int spmv_csr_sddmm_cols(spmv_csr_t *h, int dtype, int k, const void *d_U, int64_t ldu, const void *d_X, int64_t ldx, float *d_out,
+                        void *stream)
+{
+    if (int rc = cols_args(h, dtype, k, "U", d_U, ldu, h ? h->rows : 0, "X", d_X, ldx, h ? h->cols : 0, true, d_out, "spmv_csr_sddmm_cols"))
+        return rc;
+    auto run = [&](auto e) {
+        using E = decltype(e);
+        return launch_sddmm_cols(*h, k, (const E *)d_U, ldu, (const E *)d_X, ldx, d_out, (hipStream_t)stream);
+    };
+    return dtype == SPMV_ATTN_FP32 ? run(float{}) : dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+}
+
 // what spmv_csr_row_softmax and its backward check alike: a finite scale; with nnz > 0 every array present and 4-byte
 // aligned; the handle's device current; the SpMM plan made
 static int softmax_args(const spmv_csr_t *h, float scale, const void *const *arrays, int n_arrays, const char *what)

@@ -1,4 +1,5 @@
-// kernels_spmm.hip -- Y = A X for k <= 64 right-hand sides at once (spmv_csr_spmm, include/spmv_hip.h "SpMM").
+// kernels_spmm.hip -- Y = A X for k <= 64 right-hand sides at once (spmv_csr_spmm, include/spmv_hip.h "SpMM"), and for any
+// k in column tiles of 64 (spmv_csr_spmm_cols: "Column tiles" below).
 //
 // The lane groups and their steps are lane_group.hpp's; the plan they share with SDDMM and attention is made here.  X is
 // cols rows of ldx floats (row-major), Y rows rows of ldy floats.  Lane s of a row's group holds columns [4s, 4s+4) of
@@ -19,6 +20,14 @@
 // widened exactly to fp32 where it enters its fmaf, vals, the accumulators and the long rows' partials are fp32, and an
 // element of Y is rounded to E once, to nearest even, at its store (store_slice; a long row's in k_spmm_combine, after
 // the partials are added in piece order).  So Y of a 16-bit call is the fp32 call's Y on the widened X, rounded once.
+//
+// Column tiles (spmv_csr_spmm_cols, the TILED instantiations).  Tile t of a call at width k is the columns [64t, 64t + k_t),
+// k_t = min(64, k - 64t), of m = ceil(k / 64) tiles.  The three kernels run once per tile in one launch each: the tile index
+// rides in the grid (cols_tile), a tile's workgroups see X and Y advanced by 64t elements and k_t in the place of k, and do
+// what the narrow call does on that column block at V = 16 (the idle lanes of a narrower last tile load nothing), so a
+// column's bits are the narrow call's.  Each tile re-reads (col_idx, vals): 8 bytes per nonzero against up to 256 bytes of
+// gathered X.  The long rows' partials go to a scratch of the plan's own (spmv_csr_spmm_plan_cols): piece p holds m * 64
+// floats, column c of the call at offset c (64-bit offsets).
 #include <algorithm>
 #include <numeric>
 #include <vector>
@@ -32,6 +41,31 @@ constexpr int kSpmmRowCap = 512;    // rows of more nonzeros go in pieces
 constexpr int kSpmmPiece = 512;     // nonzeros of a piece
 constexpr int kSpmmMaxK = 64;       // columns of a piece's partial (the scratch is sized for k = 64 at plan time)
 constexpr int kSpmmSortRows = 4096; // the plan orders the rows of each block of this many by length (a wave's rows alike)
+
+// Where the tile index of a TILED launch rides.  The default is blockIdx.y, as the heads of fused attention: workgroups are
+// dispatched x-fastest, so all row blocks of tile 0 run before tile 1's.  SPMV_COLS_TILE_MINOR (an A/B build,
+// tools/build_variant.sh) puts it in the low part of blockIdx.x instead: the m tiles of one row block run next to each
+// other in time and re-read that block's (col_idx, vals) from cache.  DESIGN.md section 22 has both timings.
+#ifdef SPMV_COLS_TILE_MINOR
+constexpr bool kTileMinor = true;
+#else
+constexpr bool kTileMinor = false;
+#endif
+
+// (the tile of the workgroup, the index of its row block or block of pieces) of a TILED launch at width k
+__device__ __forceinline__ int cols_tile(int k, int64_t &bid)
+{
+    if constexpr (kTileMinor) {
+        const int m = cols_tiles(k);
+        bid = blockIdx.x / m;
+        return (int)(blockIdx.x % m);
+    } else {
+        bid = blockIdx.x;
+        return (int)blockIdx.y;
+    }
+}
+
+inline dim3 cols_grid(int64_t blocks, int m) { return kTileMinor ? dim3((unsigned)(blocks * m)) : dim3((unsigned)blocks, (unsigned)m); }
 
 // sum over the nonzeros [b, e) of the group's row (or piece) of vals[n] * X[col_idx[n]][c0 .. c0+3], in storage order.
 // All lanes of a group call it with the same b, e; lanes with c0 >= k load and add nothing (their shuffles still run).
@@ -90,12 +124,29 @@ struct SpmmArgs {
     int k;
 };
 
+// the launch's operands as tile `tile` sees them: X and Y advanced to the tile's first column, k its width
+template <typename E>
+__device__ __forceinline__ void cols_advance(SpmmArgs<E> &a, int tile)
+{
+    a.X += (int64_t)kColsTile * tile;
+    a.Y += (int64_t)kColsTile * tile;
+    a.k = min(kColsTile, a.k - kColsTile * tile);
+}
+
 // a group of V lanes per row; rows of more than row_cap nonzeros are left to the pieces and the combine
-template <int V, bool VEC, typename E>
+// (TILED: per column tile of a _cols call, a.k the call's whole width)
+template <int V, bool VEC, typename E, bool TILED = false>
 __global__ __launch_bounds__(kBlock) void k_spmm_rows(GroupRows g, SpmmArgs<E> a)
 {
     const int lane = threadIdx.x & (kWave - 1), c0 = 4 * (lane & (V - 1));
-    const int64_t r = group_row<V>(g);
+    int64_t r;
+    if constexpr (TILED) {
+        int64_t bid;
+        cols_advance(a, cols_tile(a.k, bid));
+        r = group_row<V>(g, bid);
+    } else {
+        r = group_row<V>(g);
+    }
     if (r < 0) return;
     const int64_t b = g.row_ptr[r], e = g.row_ptr[r + 1];
     if (e - b > g.row_cap) return;
@@ -104,24 +155,49 @@ __global__ __launch_bounds__(kBlock) void k_spmm_rows(GroupRows g, SpmmArgs<E> a
 }
 
 // a group of V lanes per piece of a long row: scratch[p][0 .. 4V) (the plan's d_partial, kSpmmMaxK floats per piece)
-template <int V, bool VEC, typename E>
+// (TILED: scratch[p][64 tile + (0 .. 4V)) of the plan's d_partial_cols, cols_tiles(k) * 64 floats per piece)
+template <int V, bool VEC, typename E, bool TILED = false>
 __global__ __launch_bounds__(kBlock) void k_spmm_pieces(GroupPieces g, SpmmArgs<E> a)
 {
     const int lane = threadIdx.x & (kWave - 1), c0 = 4 * (lane & (V - 1));
-    const int64_t p = group_piece<V>(g);
+    int64_t p, at;
+    if constexpr (TILED) {
+        int64_t bid;
+        const int m = cols_tiles(a.k), tile = cols_tile(a.k, bid);
+        cols_advance(a, tile);
+        p = group_piece<V>(g, bid);
+        at = (p * m + tile) * kColsTile;
+    } else {
+        p = group_piece<V>(g);
+        at = p * kSpmmMaxK;
+    }
     if (p < 0) return;
     const int64_t b = g.piece_k0[p], e = b + g.piece_len[p];
     const float4 acc = row_dot<V, VEC>(lane, b, e, g.col_idx, a.vals, a.X, a.ldx, c0, a.k);
-    if (c0 < a.k) *reinterpret_cast<float4 *>(g.scratch + p * kSpmmMaxK + c0) = acc;
+    if (c0 < a.k) *reinterpret_cast<float4 *>(g.scratch + at + c0) = acc;
 }
 
 // one thread per (long row, column < k): the row's partials added in piece order, the sum rounded to E at its store
-template <typename E>
+// (TILED: per column tile, one thread per (long row, column of the tile); a piece's partials are cols_tiles(k) * 64 floats)
+template <typename E, bool TILED = false>
 __global__ __launch_bounds__(kBlock) void k_spmm_combine(int n_long, const int32_t *__restrict__ long_row,
                                                              const int32_t *__restrict__ long_first,
                                                              const float *__restrict__ partial, E *__restrict__ Y,
                                                              int64_t ldy, int k)
 {
+    if constexpr (TILED) {
+        int64_t bid;
+        const int m = cols_tiles(k), tile = cols_tile(k, bid);
+        const int kt = min(kColsTile, k - kColsTile * tile);
+        const int64_t t = bid * kBlock + threadIdx.x;
+        const int64_t i = t / kt;
+        const int c = kColsTile * tile + (int)(t % kt);
+        if (i >= n_long) return;
+        float acc = 0.0f;
+        for (int p = long_first[i]; p < long_first[i + 1]; ++p) acc += partial[(int64_t)p * m * kColsTile + c];
+        store_slice<false>(Y + (int64_t)long_row[i] * ldy + c, make_float4(acc, 0.0f, 0.0f, 0.0f), 0, 1);
+        return;
+    }
     const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const int64_t i = t / k;
     const int c = (int)(t % k);
@@ -198,11 +274,30 @@ int plan_spmm(spmv_csr &h, hipStream_t s)
     return SPMV_OK;
 }
 
+// The plan of the _cols calls: the plan above and, for the long rows' partials at widths up to k_max, a scratch of its own
+// of pieces * cols_tiles(k_max) * 64 floats: a separate allocation, the narrow calls' d_partial keeps its size.  It only
+// grows; the scratch it replaces may still be read by work on `s`, so that is waited for before the old block goes.
+int plan_spmm_cols(spmv_csr &h, int k_max, hipStream_t s)
+{
+    if (int rc = plan_spmm(h, s)) return rc;
+    SpmmPlan &p = h.plan_spmm;
+    if (p.cols_k >= k_max) return SPMV_OK;
+    if (cols_tiles(k_max) > cols_tiles(p.cols_k)) {
+        DevPtr<float> scratch;
+        SPMV_HIP_TRY(scratch.alloc((size_t)p.pieces * (size_t)cols_tiles(k_max) * kColsTile));
+        if (p.cols_k) SPMV_HIP_TRY(hipStreamSynchronize(s));
+        p.d_partial_cols = std::move(scratch);
+    }
+    p.cols_k = k_max;
+    return SPMV_OK;
+}
+
 int64_t spmm_plan_bytes(const spmv_csr &h)
 {
     const SpmmPlan &p = h.plan_spmm;
     if (!p.ready) return 0;
-    return h.rows * 4 + (int64_t)p.n_long * 4 + ((int64_t)p.n_long + 1) * 4 + (int64_t)p.pieces * 8 + (int64_t)p.pieces * kSpmmMaxK * 4;
+    return h.rows * 4 + (int64_t)p.n_long * 4 + ((int64_t)p.n_long + 1) * 4 + (int64_t)p.pieces * 8 + (int64_t)p.pieces * kSpmmMaxK * 4 +
+           (int64_t)p.pieces * cols_tiles(p.cols_k) * kColsTile * 4;
 }
 
 template <int V, bool VEC, typename E>
@@ -233,6 +328,56 @@ static int launch_spmm_e(const spmv_csr &h, int k, const E *X, int64_t ldx, E *Y
         constexpr int V = decltype(v)::value;
         return vec ? launch_spmm_v<V, true, E>(h, a, s) : launch_spmm_v<V, false, E>(h, a, s);
     });
+}
+
+// the three launches of a _cols call, each over all m tiles
+template <bool VEC, typename E>
+static int launch_spmm_cols_v(const spmv_csr &h, const SpmmArgs<E> &a, hipStream_t s)
+{
+    constexpr int V = kColsV;
+    const SpmmPlan &p = h.plan_spmm;
+    const int m = cols_tiles(a.k);
+    const int64_t nblocks = group_tile_blocks("spmv_csr_spmm_cols", h, V, m);
+    if (nblocks < 0) return SPMV_ERR_INVALID;
+    hipLaunchKernelGGL((k_spmm_rows<V, VEC, E, true>), cols_grid(nblocks, m), dim3(kBlock), 0, s, group_rows(h, V, nblocks), a);
+    SPMV_LAUNCHED("k_spmm_rows");
+    if (!p.n_long) return SPMV_OK;
+    hipLaunchKernelGGL((k_spmm_pieces<V, VEC, E, true>), cols_grid(group_grid(p.pieces, V).x, m), dim3(kBlock), 0, s,
+                       group_pieces(h, p.d_partial_cols), a);
+    SPMV_LAUNCHED("k_spmm_pieces");
+    const int64_t threads = (int64_t)p.n_long * kColsTile;     // (of a tile; a narrower last tile leaves some idle)
+    if ((threads + kBlock - 1) / kBlock * m * kBlock >= (1LL << 32)) {
+        set_error("spmv_csr_spmm_cols: %d long rows x %d column tiles reach the launch limit of 2^32 work-items", p.n_long, m);
+        return SPMV_ERR_INVALID;
+    }
+    hipLaunchKernelGGL((k_spmm_combine<E, true>), cols_grid((threads + kBlock - 1) / kBlock, m), dim3(kBlock), 0, s, p.n_long,
+                       p.d_long_row, p.d_long_first, p.d_partial_cols, a.Y, a.ldy, a.k);
+    SPMV_LAUNCHED("k_spmm_combine");
+    return SPMV_OK;
+}
+
+template <typename E>
+static int launch_spmm_cols_e(const spmv_csr &h, int k, const E *X, int64_t ldx, E *Y, int64_t ldy, hipStream_t s)
+{
+    if (h.rows == 0) return SPMV_OK;
+    const SpmmArgs<E> a{h.d_vals, X, ldx, Y, ldy, k};
+    return ldx % 4 == 0 && ldy % 4 == 0 ? launch_spmm_cols_v<true, E>(h, a, s) : launch_spmm_cols_v<false, E>(h, a, s);
+}
+
+// arguments checked by spmv_csr_spmm_cols: 1 <= k <= SPMV_COLS_MAX_K, ld >= k, X / Y aligned for E, the _cols plan covers k
+int launch_spmm_cols(const spmv_csr &h, int k, const float *X, int64_t ldx, float *Y, int64_t ldy, hipStream_t s)
+{
+    return launch_spmm_cols_e<float>(h, k, X, ldx, Y, ldy, s);
+}
+
+int launch_spmm_cols(const spmv_csr &h, int k, const bf16 *X, int64_t ldx, bf16 *Y, int64_t ldy, hipStream_t s)
+{
+    return launch_spmm_cols_e<bf16>(h, k, X, ldx, Y, ldy, s);
+}
+
+int launch_spmm_cols(const spmv_csr &h, int k, const fp16 *X, int64_t ldx, fp16 *Y, int64_t ldy, hipStream_t s)
+{
+    return launch_spmm_cols_e<fp16>(h, k, X, ldx, Y, ldy, s);
 }
 
 // arguments checked by spmv_csr_spmm: 1 <= k <= 64, ld >= k, X / Y 16-byte aligned, the plan made

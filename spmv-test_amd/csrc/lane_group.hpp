@@ -9,7 +9,7 @@
 // row the CSR row refers to.  A workgroup is kBlock = 256 lanes, 256 / V groups; the row blocks are dealt so that each of
 // the 8 XCDs takes one contiguous range of them (xcd_item64: neighbouring rows share lines of the gathered operand in
 // that XCD's L2).  Fused attention's _wide entry points add a sixth group, V = 32, for operands of 65 to 128 columns: see
-// "A step narrower than the group" below; SpMM and SDDMM end at 64 columns.  The groups take the rows in the plan's order (stably by length inside blocks of 4096 rows, so the rows a
+// "A step narrower than the group" below; SpMM and SDDMM go past 64 columns in tiles of 64 at V = 16 ("Column tiles" below).  The groups take the rows in the plan's order (stably by length inside blocks of 4096 rows, so the rows a
 // wavefront walks side by side end at nearly the same step), except at V = 1: see group_rows.
 // Heads (fused attention only).  A launch may carry several heads of one pattern in blockIdx.y and blockIdx.z (the query head
 // within its group of heads that share K and V, and the group; kernels_attention.hip); group_row, group_piece and
@@ -358,6 +358,30 @@ __device__ __forceinline__ int64_t group_piece(const GroupPieces &g)
     return p < g.npieces ? p : -1;
 }
 
+// Column tiles (the _cols calls of SpMM and SDDMM only).  A call at any width k runs as m = cols_tiles(k) tiles of
+// kColsTile = 64 columns, tile t the columns [64t, 64t + k_t) with k_t = min(64, k - 64t): each tile is the model above at
+// V = 16 on operands advanced by 64t elements (which keeps the 16-byte / 8-byte path wherever the lds allow it).  SpMM
+// carries the tile in the grid, so blockIdx.x alone no longer names the row block there: the two functions below take
+// the index of the row block (of the block of pieces) from the kernel.  SDDMM walks the tiles inside a step.
+constexpr int kColsTile = 64;
+constexpr int kColsV = 16;          // the lane group of every tile (kColsTile / 4 lanes)
+__host__ __device__ constexpr int cols_tiles(int k) { return (k + kColsTile - 1) / kColsTile; }
+
+template <int V>
+__device__ __forceinline__ int64_t group_row(const GroupRows &g, int64_t bid)
+{
+    const int64_t slot = xcd_item64(bid, g.nblocks) * (kBlock / V) + threadIdx.x / V;
+    if (slot >= g.rows) return -1;
+    return g.order ? g.order[slot] : slot;
+}
+
+template <int V>
+__device__ __forceinline__ int64_t group_piece(const GroupPieces &g, int64_t bid)
+{
+    const int64_t p = bid * (kBlock / V) + threadIdx.x / V;
+    return p < g.npieces ? p : -1;
+}
+
 // the same and the index of its long row: long_first[lo] <= p < long_first[lo + 1]  (long_first[0] = 0,
 // long_first[n_long] = npieces)
 template <int V>
@@ -432,6 +456,20 @@ inline int64_t group_head_blocks(const char *who, const spmv_csr &h, int V, int 
     if (heads > group_max_heads(h, V)) {
         set_error("%s: %lld rows (%d pieces of long rows) x %d lanes per row x %d heads reach the launch limit of 2^32 work-items",
                   who, (long long)h.rows, h.plan_spmm.pieces, V, heads);
+        return -1;
+    }
+    return nblocks;
+}
+
+// group_row_blocks for a launch that carries `tiles` column tiles in its grid (SpMM's _cols call), or -1 and `who`'s error:
+// like the heads, no grid of the call may reach 2^32 work-items over all tiles, nor its y extent pass kMaxHeads
+inline int64_t group_tile_blocks(const char *who, const spmv_csr &h, int V, int tiles)
+{
+    const int64_t nblocks = group_row_blocks(who, h, V);
+    if (nblocks < 0) return -1;
+    if (tiles > group_max_heads(h, V)) {
+        set_error("%s: %lld rows (%d pieces of long rows) x %d lanes per row x %d column tiles reach the launch limit of 2^32 work-items",
+                  who, (long long)h.rows, h.plan_spmm.pieces, V, tiles);
         return -1;
     }
     return nblocks;

@@ -259,6 +259,8 @@ struct SpmmPlan {
     DevPtr<int32_t> d_piece_len;      // [pieces] its length
     DevPtr<float> d_partial;          // [pieces * 64] scratch of a run: a piece's sums of up to 64 columns (SpMM), a piece's
                                       // maximum / sum / dot and its row's in slots 0 .. 3 (row softmax)
+    int cols_k = 0;                   // the widest k the _cols calls may take (spmv_csr_spmm_plan_cols; 0: never called)
+    DevPtr<float> d_partial_cols;     // [pieces * ceil(cols_k / 64) * 64] scratch of spmv_csr_spmm_cols: a piece's sums per column tile
 };
 
 // spmv_csr_attention_* (kernels_attention.hip): on the SpMM plan, plus the scratch of the long rows' pieces
@@ -375,10 +377,19 @@ int launch_spmm(const spmv_csr &h, int k, const float *X, int64_t ldx, float *Y,
 int launch_spmm(const spmv_csr &h, int k, const bf16 *X, int64_t ldx, bf16 *Y, int64_t ldy, hipStream_t s);     // spmv_csr_spmm_16:
 int launch_spmm(const spmv_csr &h, int k, const fp16 *X, int64_t ldx, fp16 *Y, int64_t ldy, hipStream_t s);     // every ld in elements
 int64_t spmm_plan_bytes(const spmv_csr &h);
+// the same at any k, in column tiles of 64 (spmv_csr_spmm_cols; fp32, bf16 or fp16 matrices), and their plan
+int plan_spmm_cols(spmv_csr &h, int k_max, hipStream_t s);
+int launch_spmm_cols(const spmv_csr &h, int k, const float *X, int64_t ldx, float *Y, int64_t ldy, hipStream_t s);
+int launch_spmm_cols(const spmv_csr &h, int k, const bf16 *X, int64_t ldx, bf16 *Y, int64_t ldy, hipStream_t s);
+int launch_spmm_cols(const spmv_csr &h, int k, const fp16 *X, int64_t ldx, fp16 *Y, int64_t ldy, hipStream_t s);
 // kernels_sddmm.hip: spmv_csr_sddmm (on the plan of plan_spmm)
 int launch_sddmm(const spmv_csr &h, int k, const float *U, int64_t ldu, const float *X, int64_t ldx, float *out, hipStream_t s);
 int launch_sddmm(const spmv_csr &h, int k, const bf16 *U, int64_t ldu, const bf16 *X, int64_t ldx, float *out, hipStream_t s);   // spmv_csr_sddmm_16
 int launch_sddmm(const spmv_csr &h, int k, const fp16 *U, int64_t ldu, const fp16 *X, int64_t ldx, float *out, hipStream_t s);
+// the same at any k: the tiles' results added in tile order (spmv_csr_sddmm_cols)
+int launch_sddmm_cols(const spmv_csr &h, int k, const float *U, int64_t ldu, const float *X, int64_t ldx, float *out, hipStream_t s);
+int launch_sddmm_cols(const spmv_csr &h, int k, const bf16 *U, int64_t ldu, const bf16 *X, int64_t ldx, float *out, hipStream_t s);
+int launch_sddmm_cols(const spmv_csr &h, int k, const fp16 *U, int64_t ldu, const fp16 *X, int64_t ldx, float *out, hipStream_t s);
 // kernels_softmax.hip: spmv_csr_row_softmax / spmv_csr_row_softmax_backward (on the plan of plan_spmm and its scratch)
 int launch_row_softmax(const spmv_csr &h, float scale, const float *scores, float *out, hipStream_t s);
 int launch_row_softmax_backward(const spmv_csr &h, float scale, const float *P, const float *dP, float *dS, hipStream_t s);

@@ -4,7 +4,9 @@
     backward   dX    = A^T dY              spmv_csr_spmm on T = transpose(A), its values refreshed by spmv_csr_transpose_values
                dvals = (dY X^T) at A's pattern     spmv_csr_sddmm on A
 
-Plumbing that shows the primitives compose, not a framework: one device, a batch of k <= 64 columns.  X may be float32, or
+Plumbing that shows the primitives compose, not a framework: one device, a batch of k <= 64 columns -- or, for a layer made
+with ``k_max``, of up to k_max columns through the _cols calls of the same primitives (spmv_csr_spmm_cols and
+spmv_csr_sddmm_cols: column tiles of 64 in one call, every column's bits the narrow call's).  X may be float32, or
 bfloat16 or float16 (the _16 calls of the same primitives): Y and dX then have X's dtype, rounded once at their store, while
 ``vals`` and dvals stay float32 and every sum is the fp32 call's.  Every product runs in the HIP library; there is no torch
 fallback.
@@ -21,17 +23,19 @@ MAX_K = 64
 _DTYPES_16 = (torch.bfloat16, torch.float16)
 
 
-def _operand(t, name: str, rows: int, like=None):
+def _operand(t, name: str, rows: int, like=None, max_k=None):
     """t as the library takes it: 2-D float32 (or bfloat16 / float16), stride(1) == 1, stride(0) >= k, 16-byte aligned (a
-    16-bit tensor: 8-byte), copied if it is not.  like: the tensor whose dtype t must share (dY against X)."""
+    16-bit tensor: 8-byte), copied if it is not.  like: the tensor whose dtype t must share (dY against X).  max_k: the
+    layer's k_max (None: MAX_K, the narrow calls)."""
+    max_k = MAX_K if max_k is None else max_k
     if not isinstance(t, torch.Tensor) or t.dim() != 2 or (t.dtype != torch.float32 and t.dtype not in _DTYPES_16):
         raise ValueError(f"SparseMatmul: {name} must be a 2-D float32 tensor")
     if like is not None and t.dtype != like.dtype:
         raise ValueError(f"SparseMatmul: {name} is {t.dtype}, X was {like.dtype}")
     if t.shape[0] != rows:
         raise ValueError(f"SparseMatmul: {name} has {t.shape[0]} rows, the matrix needs {rows}")
-    if not 1 <= t.shape[1] <= MAX_K:
-        raise ValueError(f"SparseMatmul: {name} has {t.shape[1]} columns (1 <= k <= {MAX_K})")
+    if not 1 <= t.shape[1] <= max_k:
+        raise ValueError(f"SparseMatmul: {name} has {t.shape[1]} columns (1 <= k <= {max_k})")
     if t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.data_ptr() % (8 if t.dtype in _DTYPES_16 else 16) == 0:
         return t
     return torch.empty(t.shape, dtype=t.dtype, device=t.device).copy_(t)
@@ -42,9 +46,9 @@ class SparseMatmul(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, layer, vals, X):
-        X = _operand(X, "X", layer.A.cols)
+        X = _operand(X, "X", layer.A.cols, max_k=layer.k_max)
         Y = torch.empty((layer.A.rows, X.shape[1]), dtype=X.dtype, device=X.device)
-        layer.A.spmm(X, Y)
+        (layer.A.spmm if layer.k_max is None else layer.A.spmm_cols)(X, Y)
         ctx.layer = layer
         ctx.save_for_backward(X)
         return Y
@@ -53,15 +57,16 @@ class SparseMatmul(torch.autograd.Function):
     def backward(ctx, dY):
         layer = ctx.layer
         X, = ctx.saved_tensors
-        dY = _operand(dY, "dY", layer.A.rows, like=X)
+        dY = _operand(dY, "dY", layer.A.rows, like=X, max_k=layer.k_max)
+        wide = layer.k_max is not None
         dvals = dX = None
         if ctx.needs_input_grad[1]:
             dvals = torch.empty(layer.A.nnz, dtype=torch.float32, device=dY.device)
-            layer.A.sddmm(dY, X, dvals)
+            (layer.A.sddmm_cols if wide else layer.A.sddmm)(dY, X, dvals)
         if ctx.needs_input_grad[2]:
             dX = torch.empty((layer.A.cols, dY.shape[1]), dtype=dY.dtype, device=dY.device)
             layer.T.transpose_values(layer.A)      # A's values as they are now
-            layer.T.spmm(dY, dX)
+            (layer.T.spmm_cols if wide else layer.T.spmm)(dY, dX)
         return None, dvals, dX
 
 
@@ -70,14 +75,23 @@ class SparseLayer:
     (float32, may require grad), all on one device; owns the handle of A, of T = A^T (with the map that refreshes T's
     values) and both SpMM plans.  The pattern is fixed; ``vals`` may be updated in place (an optimizer step): the next
     forward and backward follow the new values without a new plan.  X may be float32, bfloat16 or float16 from one call to
-    the next; ``vals`` and its gradient are float32 always."""
+    the next; ``vals`` and its gradient are float32 always.  ``k_max`` (an int from 1 to capi.COLS_MAX_K): the layer takes
+    1 .. k_max columns, both handles are planned with spmm_plan_cols(k_max) and forward, dX and dvals go through the _cols
+    calls; None (the default) is the layer of the narrow calls, 1 .. MAX_K columns."""
 
-    def __init__(self, rows: int, cols: int, row_ptr, col_idx, vals):
+    def __init__(self, rows: int, cols: int, row_ptr, col_idx, vals, k_max=None):
+        if k_max is not None and (isinstance(k_max, bool) or not isinstance(k_max, int) or not 1 <= k_max <= capi.COLS_MAX_K):
+            raise ValueError(f"SparseLayer: k_max must be None or an int in [1, {capi.COLS_MAX_K}], not {k_max!r}")
+        self.k_max = k_max
         self.vals = vals
         self.A = capi.CsrMatrix.from_device(rows, cols, row_ptr, col_idx, vals)
         self.T = self.A.transpose(keep_map=True)
-        self.A.spmm_plan()
-        self.T.spmm_plan()
+        if k_max is None:
+            self.A.spmm_plan()
+            self.T.spmm_plan()
+        else:
+            self.A.spmm_plan_cols(k_max)
+            self.T.spmm_plan_cols(k_max)
 
     def __call__(self, X):
         return SparseMatmul.apply(self, self.vals, X)

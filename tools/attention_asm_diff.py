@@ -18,26 +18,28 @@ k_attn_X<V, VEC, E, AttnBias>(..., AttnBias), one template with a trailing argum
 k_attn_X<V, VEC, E>(...) and k_attn_X<V, VEC, E>(...) with an empty pack.  The kernels of kernels_spmm.hip and
 kernels_sddmm.hip are read the same way: k_spmm_rows, k_spmm_pieces, k_sddmm_rows and k_sddmm_pieces are their name, V, VEC and
 element type (float where the symbol has none, as before the 16-bit calls, whose argument struct was no template either), and
-k_spmm_combine its name and element type.  Any other symbol is its own key.
+k_spmm_combine its name and element type; SpMM's three kernels may end in a TILED flag (the instantiations of the _cols call),
+and a kernel without the flag, as before that call, is the one with TILED = false.  Any other symbol is its own key.
 Exit status 0: every kernel of OLD is in NEW with the same text."""
 import re
 import sys
 
 ELEMENTS = {None: "float", "f": "float", "NS_4bf16E": "bf16", "DF16_": "fp16"}
+TILED = {None: "", "0": "", "1": ", TILED"}     # the trailing flag of SpMM's kernels (the _cols call's column tiles; absent before it)
 ATTN = re.compile(r"_ZN4spmv12_GLOBAL__N_1\d+(k_attn_[a-z_]+?)(?:_bias)?ILi(\d+)ELb([01])E(f|NS_4bf16E|DF16_)?(?:J(?:NS_8AttnBiasE)?E)?EEv")
-GROUPS = re.compile(r"_ZN4spmv12_GLOBAL__N_1\d+(k_(?:spmm|sddmm)_(?:rows|pieces))ILi(\d+)ELb([01])E(f|NS_4bf16E|DF16_)?EEv")
+GROUPS = re.compile(r"_ZN4spmv12_GLOBAL__N_1\d+(k_(?:spmm|sddmm)_(?:rows|pieces))ILi(\d+)ELb([01])E(f|NS_4bf16E|DF16_)?(?:Lb([01])E)?EEv")
 # (the lines that lead in the next kernel, or pad the text behind a file's last one)
 NEXT = re.compile(r"\t\.text$|\t\.(?:protected|weak|hidden)\t\w+ +; -- Begin function |\t\.p2alignl 6, 3212836864$|\t\.fill 256, 4, 3212836864$")
-COMBINE = re.compile(r"_ZN4spmv12_GLOBAL__N_1\d+(k_spmm_combine)(?:I(f|NS_4bf16E|DF16_)E)?E")
+COMBINE = re.compile(r"_ZN4spmv12_GLOBAL__N_1\d+(k_spmm_combine)(?:I(f|NS_4bf16E|DF16_)(?:Lb([01])E)?E)?E")
 
 
 def key(symbol: str) -> str:
     m = GROUPS.match(symbol)
     if m:
-        return f"{m.group(1)}<{m.group(2)}, {'true' if m.group(3) == '1' else 'false'}, {ELEMENTS[m.group(4)]}>"
+        return f"{m.group(1)}<{m.group(2)}, {'true' if m.group(3) == '1' else 'false'}, {ELEMENTS[m.group(4)]}{TILED[m.group(5)]}>"
     m = COMBINE.match(symbol)
     if m:
-        return f"{m.group(1)}<{ELEMENTS[m.group(2)]}>"
+        return f"{m.group(1)}<{ELEMENTS[m.group(2)]}{TILED[m.group(3)]}>"
     m = ATTN.match(symbol)
     if not m:
         return symbol

@@ -14,6 +14,10 @@ not, the line says why.  Times: HIP events, warmed up, median of --reps windows 
 windows and its JSON line): the fp32 call and each 16-bit call on the same numbers, alternating in one process; out of the
 16-bit call must be, bit for bit, the fp32 call's on the widened operands.  Appended to profiles/spmm_16bit.jsonl unless
 --out names another file; the comparisons above are not run in this mode.
+
+--cols 128,256,512 times spmv_csr_sddmm_cols as tools/spmm_time.py --cols does for SpMM (its windows, its JSON line, its
+output file): against the loop of narrow calls over the column blocks of 64, which also needs an nnz-sized temporary and one
+nnz-sized torch add per further block; out of the call must be, bit for bit, the loop's.
 """
 import argparse
 import json
@@ -54,7 +58,13 @@ def main():
     ap.add_argument("--no-torch", action="store_true", help="skip torch.sparse.sampled_addmm")
     ap.add_argument("--dtype", default="fp32", help="fp32 (the comparisons of the first paragraph), or fp32,bf16[,fp16]")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--cols", default=None, help="widths above 64, e.g. 128,256,512: time spmv_csr_sddmm_cols against the loop of narrow calls")
+    ap.add_argument("--lib", default=None, help="--cols: another build of libspmv_hip.so, for an A/B run")
     a = ap.parse_args()
+    if a.cols:
+        from spmm_time import run_cols
+        run_cols("sddmm", a)
+        return
     import torch
     pkg = ge.load_package()
     capi, W = pkg.capi, pkg.workloads

@@ -15,6 +15,13 @@ so that a drift of the device's clocks falls on all alike.  One JSON line each: 
 ratio 16-bit / fp32, the spread of the fp32 call's own windows ((max - min) / median: what a ratio has to be read against),
 and whether Y of the 16-bit call is, bit for bit, the fp32 call's Y on the widened X rounded by torch.  Appended to
 profiles/spmm_16bit.jsonl unless --out names another file; the comparisons above are not run in this mode.
+
+--cols 128,256,512 times spmv_csr_spmm_cols (one call at any k) against what a caller did before it: the loop of narrow
+calls over the column blocks of 64, on views of the same X and Y.  Per (workload, k, dtype of --dtype, default fp32,bf16) the
+two run in windows that alternate in one process; before the clocks start Y of the call must be, bit for bit, Y of the loop.
+One JSON line each -- both medians, their ratio, both spreads ((max - min) / median of the windows) and whether the call is
+slower than the loop by more than twice the larger spread -- appended to profiles/spmm_cols.jsonl unless --out names another
+file.  Default workloads: configs 2 and 3, band 8192 and uniform.  --lib names another build of the library for an A/B run.
 """
 import argparse
 import ctypes
@@ -87,6 +94,98 @@ def compare_16bit(kind, label, k, calls, same, iters, reps):
     return row
 
 
+OUT_COLS = ROOT / "profiles" / "spmm_cols.jsonl"
+
+
+def cols_sweep(kind, a, emit):
+    """--cols of this tool (kind "spmm") and of tools/sddmm_time.py ("sddmm"): one JSON line per (workload, k, dtype)."""
+    import torch
+    pkg = ge.load_package()
+    capi, W = pkg.capi, pkg.workloads
+    if a.lib:
+        capi.use_library(a.lib)
+    dev = torch.device("cuda:0")
+    widths = [int(s) for s in a.cols.split(",")]
+    dtypes = a.dtype.split(",")
+    bits = lambda t: t.view(torch.int16 if t.element_size() == 2 else torch.int32)      # noqa: E731
+    for spec in a.workloads.split(","):
+        name, band = spec.split(":")
+        w = W.config(name, band=int(band))
+        rp = W.row_ptr(w)
+        nnz = int(rp[-1])
+        d_rp = torch.from_numpy(rp).to(dev)
+        d_ci = torch.empty(nnz, dtype=torch.int32, device=dev)
+        d_va = torch.empty(nnz, dtype=torch.float32, device=dev)
+        capi.synth_fill(w.seed, 0, w.rows, w.rows, w.cols, w.band, d_rp, d_ci, d_va)
+        A = capi.CsrMatrix.from_device(w.rows, w.cols, d_rp, d_ci, d_va)
+        A.spmm_plan_cols(max(widths))
+        for k in widths:
+            blocks = [(c, min(c + 64, k)) for c in range(0, k, 64)]
+            for d in dtypes:
+                dt = getattr(torch, DTYPES[d])
+                gen = torch.Generator(device=dev).manual_seed(k)
+                X = torch.randn((w.cols, k), generator=gen, device=dev).to(dt)
+                if kind == "spmm":
+                    Y, Yl = torch.empty((w.rows, k), dtype=dt, device=dev), torch.empty((w.rows, k), dtype=dt, device=dev)
+
+                    def call():
+                        A.spmm_cols(X, Y)
+
+                    def loop():                              # what a caller does without the call: one narrow call per column block
+                        for c0, c1 in blocks:
+                            A.spmm(X[:, c0:c1], Yl[:, c0:c1])
+                    got, want = Y, Yl
+                else:
+                    U = torch.randn((w.rows, k), generator=gen, device=dev).to(dt)
+                    got, want = (torch.empty(nnz, dtype=torch.float32, device=dev) for _ in range(2))
+                    tmp = torch.empty(nnz, dtype=torch.float32, device=dev)      # the loop's nnz-sized temporary
+
+                    def call():
+                        A.sddmm_cols(U, X, got)
+
+                    def loop():                              # the first block into the result, every further one added by torch
+                        for i, (c0, c1) in enumerate(blocks):
+                            A.sddmm(U[:, c0:c1], X[:, c0:c1], tmp if i else want)
+                            if i:
+                                want.add_(tmp)
+                # the bit check at the timed size, before the clocks start
+                call(), loop()
+                torch.cuda.synchronize()
+                same = bool(torch.equal(bits(got), bits(want)))
+                win = interleaved({"cols": call, "loop": loop}, a.iters, a.reps)
+                med = {n: statistics.median(v) for n, v in win.items()}
+                spread = {n: (max(v) - min(v)) / med[n] for n, v in win.items()}
+                emit(call=f"{kind}_cols", workload=f"{name}_band{band}", k=k, dtype=d, iters=a.iters, reps=a.reps,
+                     cols_ms=round(med["cols"], 4), loop_ms=round(med["loop"], 4), cols_over_loop=round(med["cols"] / med["loop"], 3),
+                     cols_spread=round(spread["cols"], 4), loop_spread=round(spread["loop"], 4),
+                     slower_than_twice_the_spread=bool(med["cols"] - med["loop"] > 2 * max(spread.values()) * med["loop"]),
+                     same_bits_as_loop=same, lib=Path(capi.LIB_PATH).name)
+                del X, got, want
+                if kind == "spmm":
+                    del Y, Yl
+                else:
+                    del U, tmp
+                torch.cuda.empty_cache()
+        A.close()
+        del d_rp, d_ci, d_va
+        torch.cuda.empty_cache()
+
+
+def run_cols(kind, a):
+    """The --cols mode of both tools: appends to profiles/spmm_cols.jsonl unless --out names another file."""
+    if a.workloads == "c2:8192,c2:0,c3:8192,c3:0,c4:8192,c4:0":     # (the default: c4's X at these widths does not fit the purpose)
+        a.workloads = "c2:8192,c2:0,c3:8192,c3:0"
+    if a.dtype == "fp32":
+        a.dtype = "fp32,bf16"
+    with open(a.out or OUT_COLS, "a") as out:
+        def emit(**kv):
+            line = json.dumps(kv)
+            print(line, flush=True)
+            out.write(line + "\n")
+            out.flush()
+        cols_sweep(kind, a, emit)
+
+
 def rocsparse_spmm(rs, rows, cols, nnz, d_rp, d_ci, d_va, X, Y, iters, reps):
     """(ms per call, preprocess ms) of rocsparse_spmm with the default algorithm; Y receives its result."""
     import torch
@@ -134,7 +233,12 @@ def main():
     ap.add_argument("--no-rocsparse", action="store_true")
     ap.add_argument("--dtype", default="fp32", help="fp32 (the comparisons of the first paragraph), or fp32,bf16[,fp16]")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--cols", default=None, help="widths above 64, e.g. 128,256,512: time spmv_csr_spmm_cols against the loop of narrow calls")
+    ap.add_argument("--lib", default=None, help="--cols: another build of libspmv_hip.so (tools/build_variant.sh), for an A/B run")
     a = ap.parse_args()
+    if a.cols:
+        run_cols("spmm", a)
+        return
     import torch
     pkg = ge.load_package()
     capi, W = pkg.capi, pkg.workloads
