@@ -662,6 +662,36 @@ SPMV_API int spmv_csr_spmm_16(spmv_csr_t *h, int dtype, int k, const void *d_X, 
 SPMV_API int spmv_csr_sddmm_16(spmv_csr_t *h, int dtype, int k, const void *d_U, int64_t ldu, const void *d_X, int64_t ldx,
                                float *d_out, void *stream);
 
+/* ---- SpMV on 16-bit values: bf16 or fp16 matrix values, fp32 x, y and sums ----------------------------------------------------
+ * spmv_csr_run with the values of A taken from d_vals16 instead of the handle's fp32 vals: nnz elements of bf16 (dtype =
+ * SPMV_ATTN_BF16) or IEEE half (SPMV_ATTN_FP16), the enum of the _16 calls, in the handle's storage order -- element n belongs
+ * to col_idx[n].  The array is borrowed and read live on every call (overwrite it between calls freely; nothing is copied and
+ * spmv_csr_values_changed is not needed).  The handle's own vals is never read by this call (creation still wants the array, as
+ * for the attention calls); x and y stay fp32.  SPMV_ATTN_FP32 is refused here: the fp32 call is spmv_csr_run.
+ * The contract (part of the interface).  Every value is widened exactly to fp32 where it is used, its product with x is one
+ * fp32 multiplication, and every sum is the fp32 kernel's: y is, bit for bit, what spmv_csr_run(h', variant, x, y) writes on
+ * a handle h' that has the same pattern, the same plan and vals[n] = widen(vals16[n]).  The order of every sum is therefore
+ * the one tests/_tiled_order.py states for SPMV_TILED and SPMV_ADAPTIVE, and row blocks planned alike reproduce the whole
+ * matrix as they do in fp32.  No conversion flushes a subnormal: an fp16 or bf16 subnormal widens to its exact fp32 value; an
+ * Inf or a NaN widens to an Inf or a NaN.  Nothing is accumulated or multiplied in 16 bits.
+ * Variants.  SPMV_TILED and SPMV_ADAPTIVE run, and SPMV_AUTO where its plan resolved to SPMV_TILED.  Every other variant is
+ * SPMV_ERR_VARIANT with a message that names the function and what the variant resolved to -- SPMV_AUTO resolved to SPMV_PANEL
+ * among them: the panel layouts hold a re-ordered copy of the fp32 values.  A variant that spmv_csr_plan has not seen is
+ * SPMV_ERR_NOT_PLANNED.
+ * The plan is spmv_csr_plan's own and is not changed: it is a function of the pattern, so one plan serves both calls, with the
+ * same bytes (spmv_csr_plan_bytes) and the same line (spmv_csr_plan_describe).  A plan made with SPMV_PERSIST=1 runs this call
+ * through the one-shot kernels (the persistent form exists for fp32 values only); the sums are the same, by the documented order.
+ * After the plan the call allocates nothing and never waits: graph-capturable.  Runs of one handle must be stream-ordered, with
+ * each other and with spmv_csr_run: the plan's carries are shared.
+ * Loads: a lane reads four values in one 8-byte load; the ragged last chunk reads 2-byte elements below nnz only.  Nothing
+ * outside y[0, rows) is written; d_y needs only its natural 4 bytes (a row block of a larger y is fine).  nnz == 0 gives
+ * y = 0; rows == 0 returns SPMV_OK.
+ * Refusals (SPMV_ERR_INVALID, a message that names the function, nothing launched, y untouched): a null handle; a dtype other
+ * than the two; a null d_vals16 while nnz > 0; a d_vals16 or d_x that is not 16-byte aligned; a null x or y as in
+ * spmv_csr_run; another current device than the handle's. */
+SPMV_API int spmv_csr_run_vals16(spmv_csr_t *h, int variant, int dtype, const void *d_vals16, const float *d_x, float *d_y,
+                                 void *stream);
+
 /* ---- SpMM and SDDMM at any k: column tiles of 64 in one call -------------------------------------------------------------------
  * spmv_csr_spmm and spmv_csr_sddmm (and their _16 forms) for 1 <= k <= SPMV_COLS_MAX_K columns in one call.  dtype is
  * SPMV_ATTN_FP32 (fp32 matrices, 16-byte aligned, every ld in floats), SPMV_ATTN_BF16 or SPMV_ATTN_FP16 (8-byte aligned, every

@@ -60,6 +60,7 @@ SIGNATURES = {
     "spmv_csr_transpose_map_bytes": (C.c_int64, [_H]),
     "spmv_csr_plan": (C.c_int, [_H, C.c_int, _vp]),
     "spmv_csr_run": (C.c_int, [_H, C.c_int, _f32p, _f32p, _vp]),
+    "spmv_csr_run_vals16": (C.c_int, [_H, C.c_int, C.c_int, _vp, _f32p, _f32p, _vp]),
     "spmv_csr_values_changed": (C.c_int, [_H]),
     "spmv_csr_spmm_plan": (C.c_int, [_H, _vp]),
     "spmv_csr_spmm": (C.c_int, [_H, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, _vp]),
@@ -273,6 +274,19 @@ class CsrMatrix:
         """Enqueue y = A x on torch's current stream (or ``stream``).  x, y: float32 device tensors."""
         assert x.numel() >= self.cols and y.numel() >= self.rows
         check(lib().spmv_csr_run(self._h, variant, _ptr(x), _ptr(y), _stream_handle(stream)))
+
+    def run_vals16(self, variant: int, vals16, x, y, stream=None) -> None:
+        """Enqueue y = A x with the values of A read from ``vals16`` (spmv_csr_run_vals16): a 1-D contiguous bfloat16 or
+        float16 device tensor of nnz elements in the handle's storage order, borrowed and read live.  x, y: float32 device
+        tensors; every sum is the fp32 call's on the widened values.  SPMV_TILED, SPMV_ADAPTIVE, or SPMV_AUTO resolved to tiled."""
+        import torch
+        if not isinstance(vals16, torch.Tensor) or vals16.dim() != 1 or not vals16.is_contiguous() or vals16.numel() != self.nnz:
+            raise ValueError(f"run_vals16: vals16 must be a contiguous 1-D tensor of nnz = {self.nnz} elements")
+        dtype = self._dense_dtype("run_vals16", vals16=vals16.view(vals16.numel(), 1))
+        if dtype == ATTN_FP32:
+            raise ValueError("run_vals16: vals16 must be bfloat16 or float16 (float32 values are the handle's own: run)")
+        assert x.numel() >= self.cols and y.numel() >= self.rows
+        check(lib().spmv_csr_run_vals16(self._h, variant, dtype, _ptr(vals16), _ptr(x), _ptr(y), _stream_handle(stream)))
 
     def column_range(self, stream=None):
         """(smallest, largest) column index referenced; (cols, -1) for a matrix without nonzeros."""

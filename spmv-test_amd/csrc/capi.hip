@@ -573,6 +573,39 @@ int spmv_csr_run(spmv_csr_t *h, int variant, const float *d_x, float *d_y, void 
     }
 }
 
+static int attention_dtype(int dtype, const char *what);      // SPMV_ATTN_BF16 or SPMV_ATTN_FP16, or `what`'s refusal (below)
+
+// y = A x with the values of A read from nnz bf16 / fp16 elements of the caller's (include/spmv_hip.h, "SpMV on 16-bit values")
+int spmv_csr_run_vals16(spmv_csr_t *h, int variant, int dtype, const void *d_vals16, const float *d_x, float *d_y, void *stream)
+{
+    const char *what = "spmv_csr_run_vals16";
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (int rc = attention_dtype(dtype, what)) return rc;
+    if ((!d_vals16 && h->nnz > 0) || (!d_x && h->cols > 0) || (!d_y && h->rows > 0)) {
+        set_error("%s: null vals16, x or y", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (!aligned16(d_vals16) || !aligned16(d_x)) {
+        set_error("%s: vals16 and x must be 16-byte aligned", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(h->device, what)) return rc;
+    int resolved = variant;
+    if (variant == SPMV_AUTO) {
+        if (h->auto_variant < 0) { set_error("%s: SPMV_AUTO used before spmv_csr_plan", what); return SPMV_ERR_NOT_PLANNED; }
+        resolved = h->auto_variant;
+    }
+    if (resolved != SPMV_TILED && resolved != SPMV_ADAPTIVE) {
+        if (variant == SPMV_AUTO)
+            set_error("%s: SPMV_AUTO resolved to %s, whose layout holds a copy of the fp32 values (need SPMV_TILED or SPMV_ADAPTIVE)",
+                      what, spmv_variant_name(resolved));
+        else set_error("%s: variant %d (%s) does not read 16-bit values (need SPMV_TILED, SPMV_ADAPTIVE, or SPMV_AUTO resolved to SPMV_TILED)",
+                       what, variant, spmv_variant_name(variant));
+        return SPMV_ERR_VARIANT;
+    }
+    return launch_adaptive_vals16(*h, dtype, d_vals16, d_x, d_y, resolved == SPMV_TILED, (hipStream_t)stream);
+}
+
 int spmv_csr_spmm_plan(spmv_csr_t *h, void *stream)
 {
     if (!h) { set_error("spmv_csr_spmm_plan: null handle"); return SPMV_ERR_INVALID; }

@@ -30,8 +30,16 @@
 //     floats at the same LDS bytes per wave; the plan picks the smallest workgroup whose region
 //     covers the windows of >= 90 % of the chunks, and a chunk whose window does not fit
 //     gathers from global memory.
+//
+// The values' element type E.  Every run kernel is a template on it: float (spmv_csr_run: the handle's vals) or bf16 / fp16
+// (spmv_csr_run_vals16: a borrowed array of nnz 16-bit elements in the handle's storage order).  A lane keeps its element ->
+// lane map -- nonzeros 4 (j BLOCK + tid) .. + 3 for j = 0..3 -- and a 16-bit stream vector is one 8-byte non-temporal load that
+// waits packed, two registers, until stage_products widens each element exactly to fp32 (widen16 of lane_group.hpp) for its
+// one fp32 multiplication.  The products, their LDS words and every sum are the float kernels': y is, bit for bit,
+// spmv_csr_run on the widened values.  The persistent form is float only.
 #include "spmv_internal.hpp"
 #include "tiled_chunks.hpp"
+#include "lane_group.hpp"
 
 namespace spmv {
 
@@ -143,17 +151,41 @@ __device__ __forceinline__ V stream_load(const V *chunk, int tid, int j)
     return __builtin_nontemporal_load(&chunk[j * BLOCK + tid]);
 }
 
+// Four values of a lane as they wait in registers between their load and stage_products: f4, or the 8 bytes of four 16-bit
+// elements as loaded (element q in half q & 1 of word q >> 1)
+using u2 = unsigned __attribute__((ext_vector_type(2)));
+template <typename E>
+using vals4_t = std::conditional_t<kIs16<E>, u2, f4>;
+
+// the values of the full chunk that begins at element `base`, as the vectors stream_load takes
+template <typename E>
+__device__ __forceinline__ const vals4_t<E> *value_vectors(const E *__restrict__ vals, int64_t base)
+{
+    return reinterpret_cast<const vals4_t<E> *>(vals + base);
+}
+
 // The products of a chunk into LDS, padded one word per 32 (lane-per-row reads then spread over the banks), the pad words
 // zeroed.  x_of(j, q, w): the x that meets element q of value vector j, whose product goes to word w.
-template <int BLOCK, typename X>
-__device__ __forceinline__ void stage_products(float *smem, int tid, const f4 (&vv)[kNnzPerThread / 4], X x_of)
+// 16-bit values are widened here and nowhere earlier: the packed words pass through an empty statement, so that no float of
+// them is alive across the gathers (that would undo the packing: 16 registers instead of 8).
+template <int BLOCK, typename E = float, typename X>
+__device__ __forceinline__ void stage_products(float *smem, int tid, const vals4_t<E> (&vv)[kNnzPerThread / 4], X x_of)
 {
     zero_pad_words<BLOCK>(smem, tid);
 #pragma unroll
     for (int j = 0; j < kNnzPerThread / 4; ++j) {
         const int p0 = pad_idx((j * BLOCK + tid) * 4);  // a multiple of 4: the four words never straddle a pad slot
+        if constexpr (kIs16<E>) {
+            unsigned lo = vv[j][0], hi = vv[j][1];
+            asm("" : "+v"(lo));
+            asm("" : "+v"(hi));
+            const float v[4] = {widen16<E>(lo & 0xffffu), widen16<E>(lo >> 16), widen16<E>(hi & 0xffffu), widen16<E>(hi >> 16)};
 #pragma unroll
-        for (int q = 0; q < 4; ++q) smem[p0 + q] = vv[j][q] * x_of(j, q, p0 + q);
+            for (int q = 0; q < 4; ++q) smem[p0 + q] = v[q] * x_of(j, q, p0 + q);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) smem[p0 + q] = vv[j][q] * x_of(j, q, p0 + q);
+        }
     }
 }
 
@@ -330,15 +362,17 @@ __device__ __forceinline__ void reduce_chunk(const float *smem, ChunkShared<BLOC
 
 // The stream of one chunk: 16 B per lane per load (1 KiB contiguous per wave instruction),
 // non-temporal (read once), all 8 loads issued back to back.
-template <int BLOCK, bool FULL_ONLY>
+// (16-bit values: 8 B per lane per value load, 512 B contiguous per wave instruction; the ragged chunk reads them with guarded
+// 2-byte loads and a padded lane takes the bits of +0)
+template <int BLOCK, bool FULL_ONLY, typename E = float>
 __device__ __forceinline__ void load_stream(int64_t base, int n, int pad_col, const int32_t *__restrict__ col_idx,
-                                            const float *__restrict__ vals, int tid, i4 (&cc)[kNnzPerThread / 4],
-                                            f4 (&vv)[kNnzPerThread / 4])
+                                            const E *__restrict__ vals, int tid, i4 (&cc)[kNnzPerThread / 4],
+                                            vals4_t<E> (&vv)[kNnzPerThread / 4])
 {
     constexpr int kVec = kNnzPerThread / 4;
     if (FULL_ONLY || n == chunk_of(BLOCK)) {
         const i4 *c4 = reinterpret_cast<const i4 *>(col_idx + base);
-        const f4 *v4 = reinterpret_cast<const f4 *>(vals + base);
+        const vals4_t<E> *v4 = value_vectors(vals, base);
 #pragma unroll
         for (int j = 0; j < kVec; ++j) {
             cc[j] = stream_load<BLOCK>(c4, tid, j);
@@ -350,11 +384,13 @@ __device__ __forceinline__ void load_stream(int64_t base, int n, int pad_col, co
 #pragma unroll
         for (int j = 0; j < kVec; ++j) {
             const int i0 = (j * BLOCK + tid) * 4;
+            if constexpr (kIs16<E>) vv[j] = u2{0u, 0u};
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const bool ok = (i0 + q) < n;
                 cc[j][q] = ok ? col_idx[base + i0 + q] : pad_col;
-                vv[j][q] = ok ? vals[base + i0 + q] : 0.0f;
+                if constexpr (kIs16<E>) vv[j][q >> 1] |= (ok ? (unsigned)bits16(vals)[base + i0 + q] : 0u) << (16 * (q & 1));
+                else vv[j][q] = ok ? vals[base + i0 + q] : 0.0f;
             }
         }
     }
@@ -444,11 +480,11 @@ __device__ __forceinline__ void stage_blocks(const float *__restrict__ x, const 
 // The body of k_adaptive for workgroup `bid` of `grid` (a device function so that k_tiled_mixed can run it beside
 // the 16-bit body in one launch).  smem: one dynamic LDS region, used twice: first as the x window (TILED), then
 // -- after the gathers have landed in registers -- as the product staging buffer.
-template <int BLOCK, bool TILED, bool PERSIST>
+template <int BLOCK, bool TILED, bool PERSIST, typename E = float>
 __device__ __forceinline__ void adaptive_body(float *smem, ChunkShared<BLOCK> &sh, int bid, int grid, int64_t rows,
                                               int64_t nnz, int64_t cols, int chunk0, int nrun,
                                               const int32_t *__restrict__ row_ptr,
-                                              const int32_t *__restrict__ col_idx, const float *__restrict__ vals,
+                                              const int32_t *__restrict__ col_idx, const E *__restrict__ vals,
                                               const float *__restrict__ x, float *__restrict__ y,
                                               const int32_t *__restrict__ chunk_lb, float *__restrict__ carry,
                                               const int32_t *__restrict__ win, const int32_t *__restrict__ list,
@@ -456,6 +492,7 @@ __device__ __forceinline__ void adaptive_body(float *smem, ChunkShared<BLOCK> &s
 {
     constexpr int kChunkT = chunk_of(BLOCK);
     constexpr int kVec = kNnzPerThread / 4;
+    static_assert(!(PERSIST && kIs16<E>), "the persistent form is float only");
 
     const int tid0 = threadIdx.x;
     Walk wk = first_chunk(PERSIST, bid, grid, nrun);
@@ -469,11 +506,11 @@ __device__ __forceinline__ void adaptive_body(float *smem, ChunkShared<BLOCK> &s
     }
 
     i4 cc[kVec];
-    f4 vv[kVec];
+    vals4_t<E> vv[kVec];
     {
         const int64_t b0 = (int64_t)wk.c * kChunkT;
         const int n0 = (int)((nnz - b0) < kChunkT ? (nnz - b0) : kChunkT);
-        load_stream<BLOCK, PERSIST>(b0, n0, TILED ? win[2 * wk.c] : 0, col_idx, vals, tid0, cc, vv);
+        load_stream<BLOCK, PERSIST, E>(b0, n0, TILED ? win[2 * wk.c] : 0, col_idx, vals, tid0, cc, vv);
     }
 
     for (;;) {
@@ -542,7 +579,7 @@ __device__ __forceinline__ void adaptive_body(float *smem, ChunkShared<BLOCK> &s
         }
 
         // ---- stage the products (padded one word per 32: lane-per-row reads spread over banks)
-        stage_products<BLOCK>(smem, tid, vv, [&](int j, int q, int) { return xv[j][q]; });
+        stage_products<BLOCK, E>(smem, tid, vv, [&](int j, int q, int) { return xv[j][q]; });
 
         // ---- the next chunk's stream, into the registers the products just left
         const int cn = c + wk.stride;
@@ -550,7 +587,7 @@ __device__ __forceinline__ void adaptive_body(float *smem, ChunkShared<BLOCK> &s
         if (more) {
             const int64_t bn = (int64_t)cn * kChunkT;
             const int nn = (int)((nnz - bn) < kChunkT ? (nnz - bn) : kChunkT);
-            load_stream<BLOCK, PERSIST>(bn, nn, TILED ? win[2 * cn] : 0, col_idx, vals, tid, cc, vv);
+            load_stream<BLOCK, PERSIST, E>(bn, nn, TILED ? win[2 * cn] : 0, col_idx, vals, tid, cc, vv);
         }
         __syncthreads();
 
@@ -564,17 +601,17 @@ __device__ __forceinline__ void adaptive_body(float *smem, ChunkShared<BLOCK> &s
     }
 }
 
-template <int BLOCK, bool TILED, bool PERSIST>
+template <int BLOCK, bool TILED, bool PERSIST, typename E = float>
 __global__ __launch_bounds__(BLOCK, waves_per_simd(BLOCK, PERSIST))
 void k_adaptive(int64_t rows, int64_t nnz, int64_t cols, int chunk0, int nrun, const int32_t *__restrict__ row_ptr,
-                const int32_t *__restrict__ col_idx, const float *__restrict__ vals, const float *__restrict__ x,
+                const int32_t *__restrict__ col_idx, const E *__restrict__ vals, const float *__restrict__ x,
                 float *__restrict__ y, const int32_t *__restrict__ chunk_lb, float *__restrict__ carry,
                 const int32_t *__restrict__ win, const int32_t *__restrict__ list, int kRegion)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ ChunkShared<BLOCK> sh;
-    adaptive_body<BLOCK, TILED, PERSIST>(smem, sh, (int)blockIdx.x, (int)gridDim.x, rows, nnz, cols, chunk0, nrun, row_ptr,
-                                         col_idx, vals, x, y, chunk_lb, carry, win, list, kRegion);
+    adaptive_body<BLOCK, TILED, PERSIST, E>(smem, sh, (int)blockIdx.x, (int)gridDim.x, rows, nnz, cols, chunk0, nrun, row_ptr,
+                                            col_idx, vals, x, y, chunk_lb, carry, win, list, kRegion);
 }
 
 // ---------------------------------------------------------------------------
@@ -593,10 +630,10 @@ __device__ __forceinline__ unsigned col16_at(const u4 (&raw)[2], int j, int q)
     return (e & 1) ? (word >> 16) : (word & 0xffffu);
 }
 
-template <int BLOCK, bool BLOCKS>
+template <int BLOCK, bool BLOCKS, typename E = float>
 __device__ __forceinline__ void tiled16_body(float *smem, ChunkShared<BLOCK> &sh, int bid, int64_t rows, int64_t cols,
                                              int nrun, const int32_t *__restrict__ row_ptr,
-                                             const uint16_t *__restrict__ col16, const float *__restrict__ vals,
+                                             const uint16_t *__restrict__ col16, const E *__restrict__ vals,
                                              const float *__restrict__ x, float *__restrict__ y,
                                              const int32_t *__restrict__ chunk_lb, float *__restrict__ carry,
                                              const int32_t *__restrict__ win, const int32_t *__restrict__ list,
@@ -619,12 +656,12 @@ __device__ __forceinline__ void tiled16_body(float *smem, ChunkShared<BLOCK> &sh
     const bool by_blocks = BLOCKS && (wl & kBlockBit);
     const int kRegion = by_blocks ? (kRegionArg / kBlkCols) * kBlkCols : kRegionArg;
 
-    // ---- stream: 2 x 16 B of offsets + 4 x 16 B of values per lane, non-temporal
+    // ---- stream: 2 x 16 B of offsets + 4 x 16 B of values (16-bit values: 4 x 8 B) per lane, non-temporal
     u4 raw[2];
-    f4 vv[kVec];
+    vals4_t<E> vv[kVec];
     {
         const u4 *c8 = reinterpret_cast<const u4 *>(col16 + h.base);
-        const f4 *v4 = reinterpret_cast<const f4 *>(vals + h.base);
+        const vals4_t<E> *v4 = value_vectors(vals, h.base);
         raw[0] = __builtin_nontemporal_load(&c8[tid]);   // (not stream_load: the 1024-thread kernel then shares an offset register)
         raw[1] = __builtin_nontemporal_load(&c8[BLOCK + tid]);
 #pragma unroll
@@ -668,22 +705,22 @@ __device__ __forceinline__ void tiled16_body(float *smem, ChunkShared<BLOCK> &sh
     }
 
     // ---- products, then the rows of the chunk
-    stage_products<BLOCK>(smem, tid, vv, [&](int j, int q, int) { return xv[j][q]; });
+    stage_products<BLOCK, E>(smem, tid, vv, [&](int j, int q, int) { return xv[j][q]; });
     __syncthreads();
     reduce_chunk<BLOCK, true, BLOCKS ? 1 : 0>(smem, sh, tid, h.c, h.lb0, h.m, h.base, h.lim, row_ptr, y, carry, b0.rb, b0.re);
 }
 
-template <int BLOCK, bool BLOCKS>
+template <int BLOCK, bool BLOCKS, typename E = float>
 __global__ __launch_bounds__(BLOCK, 8)
 void k_tiled16(int64_t rows, int64_t cols, int nrun, const int32_t *__restrict__ row_ptr, const uint16_t *__restrict__ col16,
-               const float *__restrict__ vals, const float *__restrict__ x, float *__restrict__ y,
+               const E *__restrict__ vals, const float *__restrict__ x, float *__restrict__ y,
                const int32_t *__restrict__ chunk_lb, float *__restrict__ carry, const int32_t *__restrict__ win,
                const int32_t *__restrict__ list, int kRegion, const int32_t *__restrict__ blk)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ ChunkShared<BLOCK> sh;
-    tiled16_body<BLOCK, BLOCKS>(smem, sh, (int)blockIdx.x, rows, cols, nrun, row_ptr, col16, vals, x, y, chunk_lb, carry, win,
-                                list, kRegion, blk);
+    tiled16_body<BLOCK, BLOCKS, E>(smem, sh, (int)blockIdx.x, rows, cols, nrun, row_ptr, col16, vals, x, y, chunk_lb, carry, win,
+                                   list, kRegion, blk);
 }
 
 // ---------------------------------------------------------------------------
@@ -697,10 +734,10 @@ void k_tiled16(int64_t rows, int64_t cols, int nrun, const int32_t *__restrict__
 // positions their nonzeros have in the row-major stream, where the lane that holds the VALUES of those positions
 // (read live from vals, original order: nothing is copied) picks them up, multiplies and leaves the products for
 // the same row reduction as everywhere else.  Same products, same order of every sum as the other bodies.
-template <int BLOCK>
+template <int BLOCK, typename E = float>
 __device__ __forceinline__ void sorted_body(float *smem, ChunkShared<BLOCK> &sh, int bid, int64_t rows, int nrun,
                                             const int32_t *__restrict__ row_ptr, const uint32_t *__restrict__ perm,
-                                            const float *__restrict__ vals, const float *__restrict__ x,
+                                            const E *__restrict__ vals, const float *__restrict__ x,
                                             float *__restrict__ y, const int32_t *__restrict__ chunk_lb,
                                             float *__restrict__ carry, const int32_t *__restrict__ win,
                                             const int32_t *__restrict__ list)
@@ -716,10 +753,10 @@ __device__ __forceinline__ void sorted_body(float *smem, ChunkShared<BLOCK> &sh,
     const float *xw = x + win[2 * h.c];
 
     u4 pw[kVec];
-    f4 vv[kVec];
+    vals4_t<E> vv[kVec];
     {
         const u4 *p4 = reinterpret_cast<const u4 *>(perm + (int64_t)ci * kChunkT);
-        const f4 *v4 = reinterpret_cast<const f4 *>(vals + h.base);
+        const vals4_t<E> *v4 = value_vectors(vals, h.base);
 #pragma unroll
         for (int j = 0; j < kVec; ++j) pw[j] = stream_load<BLOCK>(p4, tid, j);
 #pragma unroll
@@ -738,32 +775,32 @@ __device__ __forceinline__ void sorted_body(float *smem, ChunkShared<BLOCK> &sh,
     }
     __syncthreads();
     // this lane's values meet their x; the products take the same LDS words
-    stage_products<BLOCK>(smem, tid, vv, [&](int, int, int w) { return smem[w]; });
+    stage_products<BLOCK, E>(smem, tid, vv, [&](int, int, int w) { return smem[w]; });
     __syncthreads();
     reduce_chunk<BLOCK, true>(smem, sh, tid, h.c, h.lb0, h.m, h.base, h.lim, row_ptr, y, carry, b0.rb, b0.re);
 }
 
-template <int BLOCK>
+template <int BLOCK, typename E = float>
 __global__ __launch_bounds__(BLOCK, 8)
 void k_sorted(int64_t rows, int nrun, const int32_t *__restrict__ row_ptr, const uint32_t *__restrict__ perm,
-              const float *__restrict__ vals, const float *__restrict__ x, float *__restrict__ y,
+              const E *__restrict__ vals, const float *__restrict__ x, float *__restrict__ y,
               const int32_t *__restrict__ chunk_lb, float *__restrict__ carry, const int32_t *__restrict__ win,
               const int32_t *__restrict__ list)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ ChunkShared<BLOCK> sh;
-    sorted_body<BLOCK>(smem, sh, (int)blockIdx.x, rows, nrun, row_ptr, perm, vals, x, y, chunk_lb, carry, win, list);
+    sorted_body<BLOCK, E>(smem, sh, (int)blockIdx.x, rows, nrun, row_ptr, perm, vals, x, y, chunk_lb, carry, win, list);
 }
 
 // All kinds of chunk in ONE launch: workgroups [0, n32) run the 32-bit body over list32 (the slow chunks -- outliers
 // gathered from global memory, the ragged last chunk -- start first), the next nsorted the sorted body, the rest the
 // 16-bit body over list16.  Two launches
 // would each end with a partly idle chip (power-law rows: 1758 such chunks took 71 us after the 209 us of the rest).
-template <int BLOCK, bool BLOCKS>
+template <int BLOCK, bool BLOCKS, typename E = float>
 __global__ __launch_bounds__(BLOCK, 8)
 void k_tiled_mixed(int64_t rows, int64_t nnz, int64_t cols, int n32, int nsorted, int n16, const int32_t *__restrict__ row_ptr,
                    const int32_t *__restrict__ col_idx, const uint16_t *__restrict__ col16, const uint32_t *__restrict__ perm,
-                   const float *__restrict__ vals, const float *__restrict__ x, float *__restrict__ y,
+                   const E *__restrict__ vals, const float *__restrict__ x, float *__restrict__ y,
                    const int32_t *__restrict__ chunk_lb, float *__restrict__ carry, const int32_t *__restrict__ win,
                    const int32_t *__restrict__ list32, const int32_t *__restrict__ list_sorted,
                    const int32_t *__restrict__ list16, int kRegion, const int32_t *__restrict__ blk)
@@ -772,13 +809,13 @@ void k_tiled_mixed(int64_t rows, int64_t nnz, int64_t cols, int n32, int nsorted
     __shared__ ChunkShared<BLOCK> sh;
     const int b = (int)blockIdx.x;
     if (b < n32)
-        adaptive_body<BLOCK, true, false>(smem, sh, b, n32, rows, nnz, cols, 0, n32, row_ptr, col_idx, vals, x,
-                                          y, chunk_lb, carry, win, list32, kRegion);
+        adaptive_body<BLOCK, true, false, E>(smem, sh, b, n32, rows, nnz, cols, 0, n32, row_ptr, col_idx, vals, x,
+                                             y, chunk_lb, carry, win, list32, kRegion);
     else if (b < n32 + nsorted)
-        sorted_body<BLOCK>(smem, sh, b - n32, rows, nsorted, row_ptr, perm, vals, x, y, chunk_lb, carry, win, list_sorted);
+        sorted_body<BLOCK, E>(smem, sh, b - n32, rows, nsorted, row_ptr, perm, vals, x, y, chunk_lb, carry, win, list_sorted);
     else
-        tiled16_body<BLOCK, BLOCKS>(smem, sh, b - n32 - nsorted, rows, cols, n16, row_ptr, col16, vals, x, y, chunk_lb,
-                                    carry, win, list16, kRegion, blk);
+        tiled16_body<BLOCK, BLOCKS, E>(smem, sh, b - n32 - nsorted, rows, cols, n16, row_ptr, col16, vals, x, y, chunk_lb,
+                                       carry, win, list16, kRegion, blk);
 }
 
 // rows that continue past their owner chunk: y[r] += carry[c+1] + carry[c+2] + ... in chunk order
@@ -966,8 +1003,11 @@ static int launch_region(const char *name, const spmv_csr &h, const ChunkPlan &p
     return check_launch(name);
 }
 
-template <int BLOCK, bool TILED, bool PERSIST>
-static int launch_range(const spmv_csr &h, const ChunkPlan &p, int chunk0, int nrun, const float *x, float *y, hipStream_t s)
+// The launches below take the values as an argument: the handle's own fp32 array (launch_adaptive) or the caller's 16-bit
+// one (launch_adaptive_vals16), element type E.
+template <int BLOCK, bool TILED, bool PERSIST, typename E>
+static int launch_range(const spmv_csr &h, const ChunkPlan &p, const E *vals, int chunk0, int nrun, const float *x, float *y,
+                        hipStream_t s)
 {
     if (nrun <= 0) return SPMV_OK;
     int grid = nrun;
@@ -975,58 +1015,67 @@ static int launch_range(const spmv_csr &h, const ChunkPlan &p, int chunk0, int n
         const int res = resident_workgroups(h.device, BLOCK, waves_per_simd(BLOCK, true));
         if (grid > res) grid = res;
     }
-    return launch_region<k_adaptive<BLOCK, TILED, PERSIST>>("k_adaptive", h, p, grid, BLOCK, s, h.rows, h.nnz, h.cols, chunk0, nrun,
-                                                            h.d_row_ptr, h.d_col_idx, h.d_vals, x, y, p.d_lb, p.d_carry, p.d_win,
-                                                            (const int32_t *)nullptr, p.region);
+    return launch_region<k_adaptive<BLOCK, TILED, PERSIST, E>>("k_adaptive", h, p, grid, BLOCK, s, h.rows, h.nnz, h.cols, chunk0, nrun,
+                                                               h.d_row_ptr, h.d_col_idx, vals, x, y, p.d_lb, p.d_carry, p.d_win,
+                                                               (const int32_t *)nullptr, p.region);
 }
 
 // BLOCKS: the block-list staging is compiled in only for plans that have such chunks
-template <int BLOCK, bool BLOCKS>
-static int launch_tiled16(const spmv_csr &h, const ChunkPlan &p, const float *x, float *y, hipStream_t s)
+template <int BLOCK, bool BLOCKS, typename E>
+static int launch_tiled16(const spmv_csr &h, const ChunkPlan &p, const E *vals, const float *x, float *y, hipStream_t s)
 {
     if (p.n16 <= 0) return SPMV_OK;
-    return launch_region<k_tiled16<BLOCK, BLOCKS>>("k_tiled16", h, p, p.n16, BLOCK, s, h.rows, h.cols, p.n16, h.d_row_ptr, p.d_col16,
-                                                   h.d_vals, x, y, p.d_lb, p.d_carry, p.d_win,
-                                                   p.n16 == p.nchunks ? (const int32_t *)nullptr : p.d_list16.get(), p.region, p.d_blk);
+    return launch_region<k_tiled16<BLOCK, BLOCKS, E>>("k_tiled16", h, p, p.n16, BLOCK, s, h.rows, h.cols, p.n16, h.d_row_ptr, p.d_col16,
+                                                      vals, x, y, p.d_lb, p.d_carry, p.d_win,
+                                                      p.n16 == p.nchunks ? (const int32_t *)nullptr : p.d_list16.get(), p.region, p.d_blk);
 }
 
-template <int BLOCK, bool BLOCKS>
-static int launch_mixed(const spmv_csr &h, const ChunkPlan &p, const float *x, float *y, hipStream_t s)
+template <int BLOCK, bool BLOCKS, typename E>
+static int launch_mixed(const spmv_csr &h, const ChunkPlan &p, const E *vals, const float *x, float *y, hipStream_t s)
 {
     const int n32 = p.nchunks - p.n16 - p.nsorted;
-    return launch_region<k_tiled_mixed<BLOCK, BLOCKS>>("k_tiled_mixed", h, p, p.nchunks, BLOCK, s, h.rows, h.nnz, h.cols, n32, p.nsorted,
-                                                       p.n16, h.d_row_ptr, h.d_col_idx, p.d_col16, p.d_perm, h.d_vals, x, y, p.d_lb,
-                                                       p.d_carry, p.d_win, p.d_list32, p.d_list_sorted, p.d_list16, p.region, p.d_blk);
+    return launch_region<k_tiled_mixed<BLOCK, BLOCKS, E>>("k_tiled_mixed", h, p, p.nchunks, BLOCK, s, h.rows, h.nnz, h.cols, n32, p.nsorted,
+                                                          p.n16, h.d_row_ptr, h.d_col_idx, p.d_col16, p.d_perm, vals, x, y, p.d_lb,
+                                                          p.d_carry, p.d_win, p.d_list32, p.d_list_sorted, p.d_list16, p.region, p.d_blk);
 }
 
-template <int BLOCK>
-static int launch_sorted(const spmv_csr &h, const ChunkPlan &p, const float *x, float *y, hipStream_t s)
+template <int BLOCK, typename E>
+static int launch_sorted(const spmv_csr &h, const ChunkPlan &p, const E *vals, const float *x, float *y, hipStream_t s)
 {
-    return launch_region<k_sorted<BLOCK>>("k_sorted", h, p, p.nsorted, BLOCK, s, h.rows, p.nsorted, h.d_row_ptr, p.d_perm, h.d_vals, x,
-                                          y, p.d_lb, p.d_carry, p.d_win, p.d_list_sorted);
+    return launch_region<k_sorted<BLOCK, E>>("k_sorted", h, p, p.nsorted, BLOCK, s, h.rows, p.nsorted, h.d_row_ptr, p.d_perm, vals, x,
+                                             y, p.d_lb, p.d_carry, p.d_win, p.d_list_sorted);
 }
 
-template <int BLOCK, bool TILED>
-static int launch_either(bool persist, const spmv_csr &h, const ChunkPlan &p, const float *x, float *y, hipStream_t s)
+template <int BLOCK, bool TILED, typename E>
+static int launch_either(bool persist, const spmv_csr &h, const ChunkPlan &p, const E *vals, const float *x, float *y, hipStream_t s)
 {
     if constexpr (TILED) {
         if (!persist && (p.n16 > 0 || p.nsorted > 0)) {
             // every chunk has 16-bit columns: the lean kernel; otherwise all kinds in one launch
             const bool lists = p.nblk_chunks > 0;
-            if (p.n16 == p.nchunks) return lists ? launch_tiled16<BLOCK, true>(h, p, x, y, s) : launch_tiled16<BLOCK, false>(h, p, x, y, s);
-            if (p.nsorted == p.nchunks) return launch_sorted<BLOCK>(h, p, x, y, s);
-            return lists ? launch_mixed<BLOCK, true>(h, p, x, y, s) : launch_mixed<BLOCK, false>(h, p, x, y, s);
+            if (p.n16 == p.nchunks)
+                return lists ? launch_tiled16<BLOCK, true>(h, p, vals, x, y, s) : launch_tiled16<BLOCK, false>(h, p, vals, x, y, s);
+            if (p.nsorted == p.nchunks) return launch_sorted<BLOCK>(h, p, vals, x, y, s);
+            return lists ? launch_mixed<BLOCK, true>(h, p, vals, x, y, s) : launch_mixed<BLOCK, false>(h, p, vals, x, y, s);
         }
     }
-    if (!persist) return launch_range<BLOCK, TILED, false>(h, p, 0, p.nchunks, x, y, s);
-    // persistent launch over the full chunks, one-shot launch for a trailing partial chunk
-    const int nfull = (int)(h.nnz / chunk_of(BLOCK));
-    int rc = launch_range<BLOCK, TILED, true>(h, p, 0, nfull, x, y, s);
-    if (rc == SPMV_OK && p.nchunks > nfull) rc = launch_range<BLOCK, TILED, false>(h, p, nfull, p.nchunks - nfull, x, y, s);
-    return rc;
+    if constexpr (kIs16<E>) {
+        // no persistent form for 16-bit values: the one-shot kernel over the same chunks (persist is false here)
+        return launch_range<BLOCK, TILED, false>(h, p, vals, 0, p.nchunks, x, y, s);
+    } else {
+        if (!persist) return launch_range<BLOCK, TILED, false>(h, p, vals, 0, p.nchunks, x, y, s);
+        // persistent launch over the full chunks, one-shot launch for a trailing partial chunk
+        const int nfull = (int)(h.nnz / chunk_of(BLOCK));
+        int rc = launch_range<BLOCK, TILED, true>(h, p, vals, 0, nfull, x, y, s);
+        if (rc == SPMV_OK && p.nchunks > nfull) rc = launch_range<BLOCK, TILED, false>(h, p, vals, nfull, p.nchunks - nfull, x, y, s);
+        return rc;
+    }
 }
 
-int launch_adaptive(const spmv_csr &h, const float *x, float *y, bool tiled, hipStream_t s)
+// y = A x with the values `vals` (element type E) in the place of the handle's: every launch of a run.  A plan with persist = 1
+// runs 16-bit values through the one-shot kernels over the same chunks: the sums are the same by the documented order.
+template <typename E>
+static int launch_adaptive_with(const spmv_csr &h, const E *vals, const float *x, float *y, bool tiled, hipStream_t s)
 {
     const ChunkPlan &p = tiled ? h.plan_tiled : h.plan_adaptive;
     if (!p.block) {
@@ -1038,13 +1087,13 @@ int launch_adaptive(const spmv_csr &h, const float *x, float *y, bool tiled, hip
         SPMV_HIP_TRY(hipMemsetAsync(y, 0, sizeof(float) * (size_t)h.rows, s));
         return SPMV_OK;
     }
-    const bool persist = p.persist;
+    const bool persist = p.persist && !kIs16<E>;
     int rc;
     // a tiled plan that stages nothing runs the plain kernel (same chunks; it keeps the row-bound prefetch the
     // 32-bit tiled form has no registers for)
     const bool nothing_staged = tiled && p.block == 256 && p.staged_full == 0 && p.n16 == 0 && p.nsorted == 0;
-    if (!tiled || nothing_staged) rc = launch_either<256, false>(persist, h, p, x, y, s);
-    else rc = dispatch_block(p.block, [&](auto B) { return launch_either<decltype(B)::value, true>(persist, h, p, x, y, s); });
+    if (!tiled || nothing_staged) rc = launch_either<256, false>(persist, h, p, vals, x, y, s);
+    else rc = dispatch_block(p.block, [&](auto B) { return launch_either<decltype(B)::value, true>(persist, h, p, vals, x, y, s); });
     if (rc) return rc;
     if (p.nchunks > 1 && p.spanning_rows > 0) {  // chunk boundaries that all fall on row boundaries need no fix-up
         hipLaunchKernelGGL(k_carry_fixup, dim3((p.nchunks - 1 + 255) / 256), dim3(256), 0, s, p.nchunks,
@@ -1052,6 +1101,17 @@ int launch_adaptive(const spmv_csr &h, const float *x, float *y, bool tiled, hip
         rc = check_launch("k_carry_fixup");
     }
     return rc;
+}
+
+int launch_adaptive(const spmv_csr &h, const float *x, float *y, bool tiled, hipStream_t s)
+{
+    return launch_adaptive_with(h, (const float *)h.d_vals, x, y, tiled, s);
+}
+
+int launch_adaptive_vals16(const spmv_csr &h, int dtype, const void *vals16, const float *x, float *y, bool tiled, hipStream_t s)
+{
+    return dtype == SPMV_ATTN_BF16 ? launch_adaptive_with(h, (const bf16 *)vals16, x, y, tiled, s)
+                                   : launch_adaptive_with(h, (const fp16 *)vals16, x, y, tiled, s);
 }
 
 }  // namespace spmv

@@ -332,6 +332,8 @@ int launch_wave(spmv_csr &h, const float *x, float *y, bool pipelined, hipStream
 int plan_wave(spmv_csr &h, hipStream_t s);
 int launch_vector(const spmv_csr &h, const float *x, float *y, hipStream_t s);
 int launch_adaptive(const spmv_csr &h, const float *x, float *y, bool tiled, hipStream_t s);
+// the same run on nnz 16-bit values of the caller's (dtype SPMV_ATTN_BF16 | SPMV_ATTN_FP16) in the place of h.d_vals
+int launch_adaptive_vals16(const spmv_csr &h, int dtype, const void *vals16, const float *x, float *y, bool tiled, hipStream_t s);
 
 int plan_xskip(spmv_csr &h, hipStream_t s);
 int launch_xskip(const spmv_csr &h, const float *x, float *y, hipStream_t s);

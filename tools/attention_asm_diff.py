@@ -19,7 +19,11 @@ k_attn_X<V, VEC, E>(...) and k_attn_X<V, VEC, E>(...) with an empty pack.  The k
 kernels_sddmm.hip are read the same way: k_spmm_rows, k_spmm_pieces, k_sddmm_rows and k_sddmm_pieces are their name, V, VEC and
 element type (float where the symbol has none, as before the 16-bit calls, whose argument struct was no template either), and
 k_spmm_combine its name and element type; SpMM's three kernels may end in a TILED flag (the instantiations of the _cols call),
-and a kernel without the flag, as before that call, is the one with TILED = false.  Any other symbol is its own key.
+and a kernel without the flag, as before that call, is the one with TILED = false.  The run kernels of kernels_adaptive.hip --
+k_tiled16, k_sorted, k_adaptive, k_tiled_mixed -- are their name, their integer and boolean template arguments and the element
+type of the matrix values (float where the symbol has none, as before spmv_csr_run_vals16); what follows the template
+arguments in the symbol, the argument list, spells the values' pointer through the template parameter since then and is not
+part of the key.  Any other symbol is its own key.
 Exit status 0: every kernel of OLD is in NEW with the same text."""
 import re
 import sys
@@ -30,6 +34,7 @@ ATTN = re.compile(r"_ZN4spmv12_GLOBAL__N_1\d+(k_attn_[a-z_]+?)(?:_bias)?ILi(\d+)
 GROUPS = re.compile(r"_ZN4spmv12_GLOBAL__N_1\d+(k_(?:spmm|sddmm)_(?:rows|pieces))ILi(\d+)ELb([01])E(f|NS_4bf16E|DF16_)?(?:Lb([01])E)?EEv")
 # (the lines that lead in the next kernel, or pad the text behind a file's last one)
 NEXT = re.compile(r"\t\.text$|\t\.(?:protected|weak|hidden)\t\w+ +; -- Begin function |\t\.p2alignl 6, 3212836864$|\t\.fill 256, 4, 3212836864$")
+TILED_RUN = re.compile(r"_ZN4spmv\d+(k_tiled16|k_sorted|k_adaptive|k_tiled_mixed)I((?:L[ib]\d+E)+)(f|NS_4bf16E|DF16_)?EEv")
 COMBINE = re.compile(r"_ZN4spmv12_GLOBAL__N_1\d+(k_spmm_combine)(?:I(f|NS_4bf16E|DF16_)(?:Lb([01])E)?E)?E")
 
 
@@ -40,6 +45,10 @@ def key(symbol: str) -> str:
     m = COMBINE.match(symbol)
     if m:
         return f"{m.group(1)}<{ELEMENTS[m.group(2)]}{TILED[m.group(3)]}>"
+    m = TILED_RUN.match(symbol)
+    if m:
+        args = [a[1:] if a[0] == "i" else ("true" if a[1:] == "1" else "false") for a in re.findall(r"L([ib]\d+)E", m.group(2))]
+        return f"{m.group(1)}<{', '.join(args)}, {ELEMENTS[m.group(3)]}>"
     m = ATTN.match(symbol)
     if not m:
         return symbol
