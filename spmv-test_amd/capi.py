@@ -146,6 +146,15 @@ for _pass, _ops in _ATTN_PASSES.items():
     SIGNATURES[f"spmv_csr_attention_{_pass}_wide"] = SIGNATURES[f"spmv_csr_attention_{_pass}_bias"]
 ATTN_FP32, ATTN_BF16, ATTN_FP16 = 0, 1, 2      # enums of include/spmv_hip.h: the dtype of a _16 call (1, 2) or a _bias call
 COLS_MAX_K = 65536                             # SPMV_COLS_MAX_K: the widest k of spmm_cols / sddmm_cols
+# CsrMatrix.spmm / spmm_cols / sddmm / sddmm_cols: (method, ATTN_* dtype of its matrices) -> (the C call, its dtype argument
+# as a tuple: the narrow fp32 calls take none).  Built here, not per call.
+_PRODUCT_CALLS = {}
+for _m in ("spmm", "sddmm"):
+    _PRODUCT_CALLS[_m, ATTN_FP32] = (f"spmv_csr_{_m}", ())
+    for _d in (ATTN_BF16, ATTN_FP16):
+        _PRODUCT_CALLS[_m, _d] = (f"spmv_csr_{_m}_16", (_d,))
+    for _d in (ATTN_FP32, ATTN_BF16, ATTN_FP16):
+        _PRODUCT_CALLS[_m + "_cols", _d] = (f"spmv_csr_{_m}_cols", (_d,))
 # test only: the bounds-checked build of the library (SPMV_CHECK_BOUNDS) and its sites (csrc/spmv_internal.hpp BoundsSite)
 CHECKED_LIB_PATH = PKG_DIR / "lib" / "libspmv_hip_checked.so"
 BOUNDS_SITES = ("k_bs_sums prod", "k_bs_sums acc", "k_bin_sums prod", "k_bin_sums r16", "k_bs_products c16",
@@ -348,19 +357,21 @@ class CsrMatrix:
                 raise ValueError(f"{what}: {name} must be a 2-D {kind} tensor with stride(1) == 1")
         return codes[want]
 
+    def _spmm(self, what: str, X, Y, stream) -> None:
+        """spmm and spmm_cols (`what`): their checks, then the C call of `what` and the matrices' dtype."""
+        dtype = self._dense_dtype(what, X=X, Y=Y)
+        k = X.shape[1]
+        if X.shape[0] != self.cols or Y.shape[0] != self.rows or Y.shape[1] < k:
+            raise ValueError(f"{what}: X {tuple(X.shape)} and Y {tuple(Y.shape)} do not fit a {self.rows} x {self.cols} matrix")
+        call, head = _PRODUCT_CALLS[what, dtype]
+        check(getattr(lib(), call)(self._h, *head, k, _ptr(X), X.stride(0), _ptr(Y), Y.stride(0), _stream_handle(stream)))
+
     def spmm(self, X, Y, stream=None) -> None:
         """Enqueue Y[:, :k] = A X with k = X.shape[1].  X: (cols, k) and Y: (rows, k or more) 2-D device tensors with
         stride(1) == 1, both float32 (spmv_csr_spmm) or both bfloat16 or float16 (spmv_csr_spmm_16: fp32 values and sums,
         Y rounded once at its store); the leading dimensions are their stride(0), in elements.  Y's columns from k on are
         not written."""
-        dtype = self._dense_dtype("spmm", X=X, Y=Y)
-        k = X.shape[1]
-        if X.shape[0] != self.cols or Y.shape[0] != self.rows or Y.shape[1] < k:
-            raise ValueError(f"spmm: X {tuple(X.shape)} and Y {tuple(Y.shape)} do not fit a {self.rows} x {self.cols} matrix")
-        if dtype == ATTN_FP32:
-            check(lib().spmv_csr_spmm(self._h, k, _ptr(X), X.stride(0), _ptr(Y), Y.stride(0), _stream_handle(stream)))
-        else:
-            check(lib().spmv_csr_spmm_16(self._h, dtype, k, _ptr(X), X.stride(0), _ptr(Y), Y.stride(0), _stream_handle(stream)))
+        self._spmm("spmm", X, Y, stream)
 
     def spmm_describe(self) -> str:
         buf = C.create_string_buffer(256)
@@ -374,25 +385,25 @@ class CsrMatrix:
         return n
 
     # -- SDDMM: U X^T sampled at the pattern (spmv_csr_sddmm; the plan is spmm_plan's) ------------------------------
+    def _sddmm(self, what: str, U, X, out, stream) -> None:
+        """sddmm and sddmm_cols (`what`): their checks, then the C call of `what` and the matrices' dtype."""
+        import torch
+        dtype = self._dense_dtype(what, U=U, X=X)
+        if not isinstance(out, torch.Tensor) or out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"{what}: out must be a contiguous 1-D float32 tensor")
+        k = U.shape[1]
+        if U.shape[0] != self.rows or X.shape[0] != self.cols or X.shape[1] != k or out.shape[0] != self.nnz:
+            raise ValueError(f"{what}: U {tuple(U.shape)}, X {tuple(X.shape)} and out {tuple(out.shape)} do not fit a "
+                             f"{self.rows} x {self.cols} matrix with {self.nnz} nonzeros")
+        call, head = _PRODUCT_CALLS[what, dtype]
+        check(getattr(lib(), call)(self._h, *head, k, _ptr(U), U.stride(0), _ptr(X), X.stride(0), _ptr(out), _stream_handle(stream)))
+
     def sddmm(self, U, X, out, stream=None) -> None:
         """Enqueue out[n] = U[row(n), :k] . X[col(n), :k] for every stored nonzero n, k = U.shape[1] = X.shape[1].
         U: (rows, k) and X: (cols, k) 2-D device tensors with stride(1) == 1, both float32 (spmv_csr_sddmm) or both
         bfloat16 or float16 (spmv_csr_sddmm_16: widened exactly, the fp32 call's sums); the leading dimensions are their
         stride(0), in elements; out: nnz float32 whatever U and X are, contiguous, in this matrix's storage order."""
-        import torch
-        dtype = self._dense_dtype("sddmm", U=U, X=X)
-        if not isinstance(out, torch.Tensor) or out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError("sddmm: out must be a contiguous 1-D float32 tensor")
-        k = U.shape[1]
-        if U.shape[0] != self.rows or X.shape[0] != self.cols or X.shape[1] != k or out.shape[0] != self.nnz:
-            raise ValueError(f"sddmm: U {tuple(U.shape)}, X {tuple(X.shape)} and out {tuple(out.shape)} do not fit a "
-                             f"{self.rows} x {self.cols} matrix with {self.nnz} nonzeros")
-        if dtype == ATTN_FP32:
-            check(lib().spmv_csr_sddmm(self._h, k, _ptr(U), U.stride(0), _ptr(X), X.stride(0), _ptr(out),
-                                       _stream_handle(stream)))
-        else:
-            check(lib().spmv_csr_sddmm_16(self._h, dtype, k, _ptr(U), U.stride(0), _ptr(X), X.stride(0), _ptr(out),
-                                          _stream_handle(stream)))
+        self._sddmm("sddmm", U, X, out, stream)
 
     # -- both products at any k, in column tiles of 64 (spmv_csr_spmm_cols, spmv_csr_sddmm_cols) --------------------------
     def spmm_plan_cols(self, k_max: int, stream=None) -> None:
@@ -402,25 +413,12 @@ class CsrMatrix:
 
     def spmm_cols(self, X, Y, stream=None) -> None:
         """spmm(X, Y) for any k = X.shape[1] up to COLS_MAX_K in one call: every column's bits are the narrow call's."""
-        dtype = self._dense_dtype("spmm_cols", X=X, Y=Y)
-        k = X.shape[1]
-        if X.shape[0] != self.cols or Y.shape[0] != self.rows or Y.shape[1] < k:
-            raise ValueError(f"spmm_cols: X {tuple(X.shape)} and Y {tuple(Y.shape)} do not fit a {self.rows} x {self.cols} matrix")
-        check(lib().spmv_csr_spmm_cols(self._h, dtype, k, _ptr(X), X.stride(0), _ptr(Y), Y.stride(0), _stream_handle(stream)))
+        self._spmm("spmm_cols", X, Y, stream)
 
     def sddmm_cols(self, U, X, out, stream=None) -> None:
         """sddmm(U, X, out) for any k up to COLS_MAX_K in one call: per column tile of 64 the narrow call's number, the tiles'
         numbers added in fp32 in tile order from tile 0's."""
-        import torch
-        dtype = self._dense_dtype("sddmm_cols", U=U, X=X)
-        if not isinstance(out, torch.Tensor) or out.dim() != 1 or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError("sddmm_cols: out must be a contiguous 1-D float32 tensor")
-        k = U.shape[1]
-        if U.shape[0] != self.rows or X.shape[0] != self.cols or X.shape[1] != k or out.shape[0] != self.nnz:
-            raise ValueError(f"sddmm_cols: U {tuple(U.shape)}, X {tuple(X.shape)} and out {tuple(out.shape)} do not fit a "
-                             f"{self.rows} x {self.cols} matrix with {self.nnz} nonzeros")
-        check(lib().spmv_csr_sddmm_cols(self._h, dtype, k, _ptr(U), U.stride(0), _ptr(X), X.stride(0), _ptr(out),
-                                        _stream_handle(stream)))
+        self._sddmm("sddmm_cols", U, X, out, stream)
 
     # -- row softmax over the pattern and its backward (spmv_csr_row_softmax; the plan is spmm_plan's) ---------------
     def _nnz_arrays(self, what: str, **arrays) -> None:

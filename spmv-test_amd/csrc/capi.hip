@@ -1,4 +1,5 @@
 // capi.hip -- the extern "C" entry points of include/spmv_hip.h.
+#include <cctype>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdlib>
@@ -80,6 +81,25 @@ int require_current(int device, const char *what)
 }
 
 static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+
+// Is `dtype` one a call takes -- SPMV_ATTN_BF16, SPMV_ATTN_FP16 and, with fp32_too, SPMV_ATTN_FP32?  Else `what`'s refusal.
+static int dtype_ok(int dtype, bool fp32_too, const char *what)
+{
+    if (dtype == SPMV_ATTN_BF16 || dtype == SPMV_ATTN_FP16 || (fp32_too && dtype == SPMV_ATTN_FP32)) return SPMV_OK;
+    if (fp32_too)
+        set_error("%s: dtype = %d (need SPMV_ATTN_FP32 = %d, SPMV_ATTN_BF16 = %d or SPMV_ATTN_FP16 = %d)", what, dtype, (int)SPMV_ATTN_FP32,
+                  (int)SPMV_ATTN_BF16, (int)SPMV_ATTN_FP16);
+    else set_error("%s: dtype = %d (need SPMV_ATTN_BF16 = %d or SPMV_ATTN_FP16 = %d)", what, dtype, (int)SPMV_ATTN_BF16, (int)SPMV_ATTN_FP16);
+    return SPMV_ERR_INVALID;
+}
+
+// f(E{}) for the element type E that a dtype accepted by dtype_ok names: float, bf16 or fp16
+template <typename F>
+static int with_element(int dtype, F &&f)
+{
+    return dtype == SPMV_ATTN_FP32 ? f(float{}) : dtype == SPMV_ATTN_BF16 ? f(bf16{}) : f(fp16{});
+}
 
 // The host-buffer conveniences time two launches: the reference's TIME_KERNEL (kernel.hpp:31-48) times a single COLD
 // launch, code object load included -- that figure is kept (spmv_last_first_launch_ms); *kernel_ms is the second launch:
@@ -573,14 +593,12 @@ int spmv_csr_run(spmv_csr_t *h, int variant, const float *d_x, float *d_y, void 
     }
 }
 
-static int attention_dtype(int dtype, const char *what);      // SPMV_ATTN_BF16 or SPMV_ATTN_FP16, or `what`'s refusal (below)
-
 // y = A x with the values of A read from nnz bf16 / fp16 elements of the caller's (include/spmv_hip.h, "SpMV on 16-bit values")
 int spmv_csr_run_vals16(spmv_csr_t *h, int variant, int dtype, const void *d_vals16, const float *d_x, float *d_y, void *stream)
 {
     const char *what = "spmv_csr_run_vals16";
     if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
-    if (int rc = attention_dtype(dtype, what)) return rc;
+    if (int rc = dtype_ok(dtype, false, what)) return rc;
     if ((!d_vals16 && h->nnz > 0) || (!d_x && h->cols > 0) || (!d_y && h->rows > 0)) {
         set_error("%s: null vals16, x or y", what);
         return SPMV_ERR_INVALID;
@@ -613,23 +631,94 @@ int spmv_csr_spmm_plan(spmv_csr_t *h, void *stream)
     return plan_spmm(*h, (hipStream_t)stream);
 }
 
+// ---- SpMM and SDDMM: one description of a run call, checked in one place ------------------------------
+// A dense matrix of a call: its name in the messages ("X"; its ld is "ldx"), pointer and ld, and whether the handle's cols
+// (else its rows) count its rows.
+struct DenseArg {
+    const char *name;
+    const void *p;
+    int64_t ld;
+    bool by_cols;
+};
+
+// One of the six run calls: its name, its two matrices in argument order, SDDMM's out (has_out), whether dtype may be
+// SPMV_ATTN_FP32 (the fp32 calls pass that constant), and whether it runs in column tiles: then k goes up to SPMV_COLS_MAX_K
+// and the plan is spmv_csr_spmm_plan_cols' and has to cover k, else k <= 64 on the plan of spmv_csr_spmm_plan.
+struct ProductCall {
+    const char *what;
+    bool fp32_too, cols;
+    DenseArg a, b;
+    bool has_out;
+    const float *out;
+};
+
+// What every one of them checks, in this order: the handle, the dtype, 1 <= k <= the widest and both ld >= k, the pointers
+// present and aligned for the dtype (16 bytes of floats, 8 of 16-bit elements; out 4), the byte offsets, the device, the plan.
+static int product_args(const ProductCall &c, const spmv_csr_t *h, int dtype, int k)
+{
+    const char *what = c.what, *na = c.a.name, *nb = c.b.name;
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (int rc = dtype_ok(dtype, c.fp32_too, what)) return rc;
+    const int max_k = c.cols ? (int)SPMV_COLS_MAX_K : 64;
+    const char la = (char)tolower(na[0]), lb = (char)tolower(nb[0]);
+    if (k < 1 || k > max_k || c.a.ld < k || c.b.ld < k) {
+        set_error("%s: k = %d, ld%c = %lld, ld%c = %lld (need 1 <= k <= %d, ld%c >= k, ld%c >= k)", what, k, la, (long long)c.a.ld, lb,
+                  (long long)c.b.ld, max_k, la, lb);
+        return SPMV_ERR_INVALID;
+    }
+    const int64_t ra = c.a.by_cols ? h->cols : h->rows, rb = c.b.by_cols ? h->cols : h->rows;
+    if ((!c.a.p && ra > 0) || (!c.b.p && rb > 0) || (c.has_out && !c.out && h->nnz > 0)) {
+        if (c.has_out) set_error("%s: null %s, %s or out", what, na, nb);
+        else set_error("%s: null %s or %s", what, na, nb);
+        return SPMV_ERR_INVALID;
+    }
+    const bool f32 = dtype == SPMV_ATTN_FP32;
+    if (f32 ? !aligned16(c.a.p) || !aligned16(c.b.p) : !aligned8(c.a.p) || !aligned8(c.b.p)) {
+        set_error("%s: %s and %s must be %d-byte aligned", what, na, nb, f32 ? 16 : 8);
+        return SPMV_ERR_INVALID;
+    }
+    if (c.has_out && reinterpret_cast<uintptr_t>(c.out) % 4 != 0) { set_error("%s: out must be 4-byte aligned", what); return SPMV_ERR_INVALID; }
+    const int64_t es = f32 ? 4 : 2;
+    if (c.a.ld > INT64_MAX / es / (ra > 0 ? ra : 1) || c.b.ld > INT64_MAX / es / (rb > 0 ? rb : 1)) {
+        set_error("%s: ld%c = %lld or ld%c = %lld overflows 64-bit byte offsets", what, la, (long long)c.a.ld, lb, (long long)c.b.ld);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(h->device, what)) return rc;
+    if (!h->plan_spmm.ready || (c.cols && !h->plan_spmm.cols_k)) {
+        set_error("%s used before %s", what, c.cols ? "spmv_csr_spmm_plan_cols" : "spmv_csr_spmm_plan");
+        return SPMV_ERR_NOT_PLANNED;
+    }
+    if (c.cols && k > h->plan_spmm.cols_k) {
+        set_error("%s: k = %d, the plan covers %d (spmv_csr_spmm_plan_cols)", what, k, h->plan_spmm.cols_k);
+        return SPMV_ERR_NOT_PLANNED;
+    }
+    return SPMV_OK;
+}
+
+// Y = A X (kernels_spmm.hip) and out = (U X^T)[pattern] (kernels_sddmm.hip) for any of their three entry points each
+static int run_spmm(const char *what, bool fp32_too, bool cols, spmv_csr_t *h, int dtype, int k, const void *d_X, int64_t ldx, void *d_Y,
+                    int64_t ldy, void *stream)
+{
+    if (int rc = product_args({what, fp32_too, cols, {"X", d_X, ldx, true}, {"Y", d_Y, ldy, false}, false, nullptr}, h, dtype, k)) return rc;
+    return with_element(dtype, [&](auto e) {
+        using E = decltype(e);
+        return launch_spmm<E>(*h, what, cols, k, (const E *)d_X, ldx, (E *)d_Y, ldy, (hipStream_t)stream);
+    });
+}
+
+static int run_sddmm(const char *what, bool fp32_too, bool cols, spmv_csr_t *h, int dtype, int k, const void *d_U, int64_t ldu,
+                     const void *d_X, int64_t ldx, float *d_out, void *stream)
+{
+    if (int rc = product_args({what, fp32_too, cols, {"U", d_U, ldu, false}, {"X", d_X, ldx, true}, true, d_out}, h, dtype, k)) return rc;
+    return with_element(dtype, [&](auto e) {
+        using E = decltype(e);
+        return launch_sddmm<E>(*h, what, cols, k, (const E *)d_U, ldu, (const E *)d_X, ldx, d_out, (hipStream_t)stream);
+    });
+}
+
 int spmv_csr_spmm(spmv_csr_t *h, int k, const float *d_X, int64_t ldx, float *d_Y, int64_t ldy, void *stream)
 {
-    if (!h) { set_error("spmv_csr_spmm: null handle"); return SPMV_ERR_INVALID; }
-    if (k < 1 || k > 64 || ldx < k || ldy < k) {
-        set_error("spmv_csr_spmm: k = %d, ldx = %lld, ldy = %lld (need 1 <= k <= 64, ldx >= k, ldy >= k)", k, (long long)ldx,
-                  (long long)ldy);
-        return SPMV_ERR_INVALID;
-    }
-    if ((!d_X && h->cols > 0) || (!d_Y && h->rows > 0)) { set_error("spmv_csr_spmm: null X or Y"); return SPMV_ERR_INVALID; }
-    if (!aligned16(d_X) || !aligned16(d_Y)) { set_error("spmv_csr_spmm: X and Y must be 16-byte aligned"); return SPMV_ERR_INVALID; }
-    if (ldx > INT64_MAX / 4 / (h->cols > 0 ? h->cols : 1) || ldy > INT64_MAX / 4 / (h->rows > 0 ? h->rows : 1)) {
-        set_error("spmv_csr_spmm: ldx = %lld or ldy = %lld overflows 64-bit byte offsets", (long long)ldx, (long long)ldy);
-        return SPMV_ERR_INVALID;
-    }
-    if (int rc = require_current(h->device, "spmv_csr_spmm")) return rc;
-    if (!h->plan_spmm.ready) { set_error("spmv_csr_spmm used before spmv_csr_spmm_plan"); return SPMV_ERR_NOT_PLANNED; }
-    return launch_spmm(*h, k, d_X, ldx, d_Y, ldy, (hipStream_t)stream);
+    return run_spmm("spmv_csr_spmm", true, false, h, SPMV_ATTN_FP32, k, d_X, ldx, d_Y, ldy, stream);
 }
 
 int64_t spmv_csr_spmm_plan_bytes(const spmv_csr_t *h)
@@ -649,82 +738,19 @@ int spmv_csr_spmm_describe(const spmv_csr_t *h, char *buf, int n)
 
 int spmv_csr_sddmm(spmv_csr_t *h, int k, const float *d_U, int64_t ldu, const float *d_X, int64_t ldx, float *d_out, void *stream)
 {
-    if (!h) { set_error("spmv_csr_sddmm: null handle"); return SPMV_ERR_INVALID; }
-    if (k < 1 || k > 64 || ldu < k || ldx < k) {
-        set_error("spmv_csr_sddmm: k = %d, ldu = %lld, ldx = %lld (need 1 <= k <= 64, ldu >= k, ldx >= k)", k, (long long)ldu,
-                  (long long)ldx);
-        return SPMV_ERR_INVALID;
-    }
-    if ((!d_U && h->rows > 0) || (!d_X && h->cols > 0) || (!d_out && h->nnz > 0)) {
-        set_error("spmv_csr_sddmm: null U, X or out");
-        return SPMV_ERR_INVALID;
-    }
-    if (!aligned16(d_U) || !aligned16(d_X)) { set_error("spmv_csr_sddmm: U and X must be 16-byte aligned"); return SPMV_ERR_INVALID; }
-    if (reinterpret_cast<uintptr_t>(d_out) % 4 != 0) { set_error("spmv_csr_sddmm: out must be 4-byte aligned"); return SPMV_ERR_INVALID; }
-    if (ldu > INT64_MAX / 4 / (h->rows > 0 ? h->rows : 1) || ldx > INT64_MAX / 4 / (h->cols > 0 ? h->cols : 1)) {
-        set_error("spmv_csr_sddmm: ldu = %lld or ldx = %lld overflows 64-bit byte offsets", (long long)ldu, (long long)ldx);
-        return SPMV_ERR_INVALID;
-    }
-    if (int rc = require_current(h->device, "spmv_csr_sddmm")) return rc;
-    if (!h->plan_spmm.ready) { set_error("spmv_csr_sddmm used before spmv_csr_spmm_plan"); return SPMV_ERR_NOT_PLANNED; }
-    return launch_sddmm(*h, k, d_U, ldu, d_X, ldx, d_out, (hipStream_t)stream);
+    return run_sddmm("spmv_csr_sddmm", true, false, h, SPMV_ATTN_FP32, k, d_U, ldu, d_X, ldx, d_out, stream);
 }
 
 // ---- the same two products on 16-bit matrices (bf16 or fp16 storage; vals, out and every sum fp32) ------------------------
-static int attention_dtype(int dtype, const char *what);      // SPMV_ATTN_BF16 or SPMV_ATTN_FP16, or `what`'s refusal (below)
-static bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
-
 int spmv_csr_spmm_16(spmv_csr_t *h, int dtype, int k, const void *d_X, int64_t ldx, void *d_Y, int64_t ldy, void *stream)
 {
-    const char *what = "spmv_csr_spmm_16";
-    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
-    if (int rc = attention_dtype(dtype, what)) return rc;
-    if (k < 1 || k > 64 || ldx < k || ldy < k) {
-        set_error("%s: k = %d, ldx = %lld, ldy = %lld (need 1 <= k <= 64, ldx >= k, ldy >= k)", what, k, (long long)ldx, (long long)ldy);
-        return SPMV_ERR_INVALID;
-    }
-    if ((!d_X && h->cols > 0) || (!d_Y && h->rows > 0)) { set_error("%s: null X or Y", what); return SPMV_ERR_INVALID; }
-    if (!aligned8(d_X) || !aligned8(d_Y)) { set_error("%s: X and Y must be 8-byte aligned", what); return SPMV_ERR_INVALID; }
-    if (ldx > INT64_MAX / 2 / (h->cols > 0 ? h->cols : 1) || ldy > INT64_MAX / 2 / (h->rows > 0 ? h->rows : 1)) {
-        set_error("%s: ldx = %lld or ldy = %lld overflows 64-bit byte offsets", what, (long long)ldx, (long long)ldy);
-        return SPMV_ERR_INVALID;
-    }
-    if (int rc = require_current(h->device, what)) return rc;
-    if (!h->plan_spmm.ready) { set_error("%s used before spmv_csr_spmm_plan", what); return SPMV_ERR_NOT_PLANNED; }
-    auto run = [&](auto e) {
-        using E = decltype(e);
-        return launch_spmm(*h, k, (const E *)d_X, ldx, (E *)d_Y, ldy, (hipStream_t)stream);
-    };
-    return dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+    return run_spmm("spmv_csr_spmm_16", false, false, h, dtype, k, d_X, ldx, d_Y, ldy, stream);
 }
 
 int spmv_csr_sddmm_16(spmv_csr_t *h, int dtype, int k, const void *d_U, int64_t ldu, const void *d_X, int64_t ldx, float *d_out,
                       void *stream)
 {
-    const char *what = "spmv_csr_sddmm_16";
-    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
-    if (int rc = attention_dtype(dtype, what)) return rc;
-    if (k < 1 || k > 64 || ldu < k || ldx < k) {
-        set_error("%s: k = %d, ldu = %lld, ldx = %lld (need 1 <= k <= 64, ldu >= k, ldx >= k)", what, k, (long long)ldu, (long long)ldx);
-        return SPMV_ERR_INVALID;
-    }
-    if ((!d_U && h->rows > 0) || (!d_X && h->cols > 0) || (!d_out && h->nnz > 0)) {
-        set_error("%s: null U, X or out", what);
-        return SPMV_ERR_INVALID;
-    }
-    if (!aligned8(d_U) || !aligned8(d_X)) { set_error("%s: U and X must be 8-byte aligned", what); return SPMV_ERR_INVALID; }
-    if (reinterpret_cast<uintptr_t>(d_out) % 4 != 0) { set_error("%s: out must be 4-byte aligned", what); return SPMV_ERR_INVALID; }
-    if (ldu > INT64_MAX / 2 / (h->rows > 0 ? h->rows : 1) || ldx > INT64_MAX / 2 / (h->cols > 0 ? h->cols : 1)) {
-        set_error("%s: ldu = %lld or ldx = %lld overflows 64-bit byte offsets", what, (long long)ldu, (long long)ldx);
-        return SPMV_ERR_INVALID;
-    }
-    if (int rc = require_current(h->device, what)) return rc;
-    if (!h->plan_spmm.ready) { set_error("%s used before spmv_csr_spmm_plan", what); return SPMV_ERR_NOT_PLANNED; }
-    auto run = [&](auto e) {
-        using E = decltype(e);
-        return launch_sddmm(*h, k, (const E *)d_U, ldu, (const E *)d_X, ldx, d_out, (hipStream_t)stream);
-    };
-    return dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+    return run_sddmm("spmv_csr_sddmm_16", false, false, h, dtype, k, d_U, ldu, d_X, ldx, d_out, stream);
 }
 
 // ---- the same two products at any k, in column tiles of 64 (fp32, bf16 or fp16 matrices; kernels_spmm.hip, kernels_sddmm.hip) ----
@@ -740,70 +766,15 @@ int spmv_csr_spmm_plan_cols(spmv_csr_t *h, int k_max, void *stream)
     return plan_spmm_cols(*h, k_max, (hipStream_t)stream);
 }
 
-// What the two _cols calls check alike, in the order of the narrow calls: the dtype, 1 <= k <= SPMV_COLS_MAX_K and both ld >= k
-// (na, nb: the names of the two matrices and of their ld), the pointers (pa of ra rows, pb of rb rows) present and aligned for
-// the dtype (16 bytes of floats, 8 of 16-bit elements), the byte offsets, the device, the plan.  out: SDDMM's, else null.
-static int cols_args(const spmv_csr_t *h, int dtype, int k, const char *na, const void *pa, int64_t lda, int64_t ra, const char *nb,
-                     const void *pb, int64_t ldb, int64_t rb, bool has_out, const float *d_out, const char *what)
-{
-    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
-    if (dtype != SPMV_ATTN_FP32 && dtype != SPMV_ATTN_BF16 && dtype != SPMV_ATTN_FP16) {
-        set_error("%s: dtype = %d (need SPMV_ATTN_FP32 = %d, SPMV_ATTN_BF16 = %d or SPMV_ATTN_FP16 = %d)", what, dtype, (int)SPMV_ATTN_FP32,
-                  (int)SPMV_ATTN_BF16, (int)SPMV_ATTN_FP16);
-        return SPMV_ERR_INVALID;
-    }
-    const bool f32 = dtype == SPMV_ATTN_FP32;
-    const char *lc = has_out ? "u" : "x", *ld2 = has_out ? "x" : "y";     // (ldu, ldx of SDDMM; ldx, ldy of SpMM)
-    if (k < 1 || k > SPMV_COLS_MAX_K || lda < k || ldb < k) {
-        set_error("%s: k = %d, ld%s = %lld, ld%s = %lld (need 1 <= k <= %d, ld%s >= k, ld%s >= k)", what, k, lc, (long long)lda, ld2,
-                  (long long)ldb, (int)SPMV_COLS_MAX_K, lc, ld2);
-        return SPMV_ERR_INVALID;
-    }
-    if ((!pa && ra > 0) || (!pb && rb > 0) || (has_out && !d_out && h->nnz > 0)) {
-        if (has_out) set_error("%s: null %s, %s or out", what, na, nb);
-        else set_error("%s: null %s or %s", what, na, nb);
-        return SPMV_ERR_INVALID;
-    }
-    if (f32 ? !aligned16(pa) || !aligned16(pb) : !aligned8(pa) || !aligned8(pb)) {
-        set_error("%s: %s and %s must be %d-byte aligned", what, na, nb, f32 ? 16 : 8);
-        return SPMV_ERR_INVALID;
-    }
-    if (has_out && reinterpret_cast<uintptr_t>(d_out) % 4 != 0) { set_error("%s: out must be 4-byte aligned", what); return SPMV_ERR_INVALID; }
-    const int64_t es = f32 ? 4 : 2;
-    if (lda > INT64_MAX / es / (ra > 0 ? ra : 1) || ldb > INT64_MAX / es / (rb > 0 ? rb : 1)) {
-        set_error("%s: ld%s = %lld or ld%s = %lld overflows 64-bit byte offsets", what, lc, (long long)lda, ld2, (long long)ldb);
-        return SPMV_ERR_INVALID;
-    }
-    if (int rc = require_current(h->device, what)) return rc;
-    if (!h->plan_spmm.ready || !h->plan_spmm.cols_k) { set_error("%s used before spmv_csr_spmm_plan_cols", what); return SPMV_ERR_NOT_PLANNED; }
-    if (k > h->plan_spmm.cols_k) {
-        set_error("%s: k = %d, the plan covers %d (spmv_csr_spmm_plan_cols)", what, k, h->plan_spmm.cols_k);
-        return SPMV_ERR_NOT_PLANNED;
-    }
-    return SPMV_OK;
-}
-
 int spmv_csr_spmm_cols(spmv_csr_t *h, int dtype, int k, const void *d_X, int64_t ldx, void *d_Y, int64_t ldy, void *stream)
 {
-    if (int rc = cols_args(h, dtype, k, "X", d_X, ldx, h ? h->cols : 0, "Y", d_Y, ldy, h ? h->rows : 0, false, nullptr, "spmv_csr_spmm_cols"))
-        return rc;
-    auto run = [&](auto e) {
-        using E = decltype(e);
-        return launch_spmm_cols(*h, k, (const E *)d_X, ldx, (E *)d_Y, ldy, (hipStream_t)stream);
-    };
-    return dtype == SPMV_ATTN_FP32 ? run(float{}) : dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+    return run_spmm("spmv_csr_spmm_cols", true, true, h, dtype, k, d_X, ldx, d_Y, ldy, stream);
 }
 
 int spmv_csr_sddmm_cols(spmv_csr_t *h, int dtype, int k, const void *d_U, int64_t ldu, const void *d_X, int64_t ldx, float *d_out,
                         void *stream)
 {
-    if (int rc = cols_args(h, dtype, k, "U", d_U, ldu, h ? h->rows : 0, "X", d_X, ldx, h ? h->cols : 0, true, d_out, "spmv_csr_sddmm_cols"))
-        return rc;
-    auto run = [&](auto e) {
-        using E = decltype(e);
-        return launch_sddmm_cols(*h, k, (const E *)d_U, ldu, (const E *)d_X, ldx, d_out, (hipStream_t)stream);
-    };
-    return dtype == SPMV_ATTN_FP32 ? run(float{}) : dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+    return run_sddmm("spmv_csr_sddmm_cols", true, true, h, dtype, k, d_U, ldu, d_X, ldx, d_out, stream);
 }
 
 // what spmv_csr_row_softmax and its backward check alike: a finite scale; with nnz > 0 every array present and 4-byte
@@ -1147,26 +1118,18 @@ int spmv_csr_attention_backward_kv_gqa(spmv_csr_t *t, const spmv_attn_heads_t *h
 }
 
 // ---- the same three passes on 16-bit matrices (bf16 or fp16 storage, fp32 sums): the most general form only ---------------
-static int attention_dtype(int dtype, const char *what)
-{
-    if (dtype == SPMV_ATTN_BF16 || dtype == SPMV_ATTN_FP16) return SPMV_OK;
-    set_error("%s: dtype = %d (need SPMV_ATTN_BF16 = %d or SPMV_ATTN_FP16 = %d)", what, dtype, (int)SPMV_ATTN_BF16, (int)SPMV_ATTN_FP16);
-    return SPMV_ERR_INVALID;
-}
-
 int spmv_csr_attention_forward_16(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, int dtype, float scale, int k,
                                   const void *d_Q, int64_t ldq, const void *d_K, int64_t ldk, int kv, const void *d_V, int64_t ldv,
                                   void *d_O, int64_t ldo, float *d_stats, void *stream)
 {
     const char *what = "spmv_csr_attention_forward_16";
     if (int rc = attention_header(h, hs, group, what)) return rc;
-    if (int rc = attention_dtype(dtype, what)) return rc;
-    auto run = [&](auto e) {
+    if (int rc = dtype_ok(dtype, false, what)) return rc;
+    return with_element(dtype, [&](auto e) {
         using E = decltype(e);
         return attention_forward<E>(what, h, hs, group, false, scale, k, (const E *)d_Q, ldq, (const E *)d_K, ldk, kv, (const E *)d_V, ldv,
                                     (E *)d_O, ldo, d_stats, stream);
-    };
-    return dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+    });
 }
 
 int spmv_csr_attention_backward_q_16(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, int dtype, float scale, int k,
@@ -1176,13 +1139,12 @@ int spmv_csr_attention_backward_q_16(spmv_csr_t *h, const spmv_attn_heads_t *hs,
 {
     const char *what = "spmv_csr_attention_backward_q_16";
     if (int rc = attention_header(h, hs, group, what)) return rc;
-    if (int rc = attention_dtype(dtype, what)) return rc;
-    auto run = [&](auto e) {
+    if (int rc = dtype_ok(dtype, false, what)) return rc;
+    return with_element(dtype, [&](auto e) {
         using E = decltype(e);
         return attention_backward_q<E>(what, h, hs, group, false, scale, k, (const E *)d_Q, ldq, (const E *)d_K, ldk, kv, (const E *)d_V,
                                        ldv, (const E *)d_O, ldo, (const E *)d_dO, lddo, d_stats, d_delta, (E *)d_dQ, lddq, stream);
-    };
-    return dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+    });
 }
 
 int spmv_csr_attention_backward_kv_16(spmv_csr_t *t, const spmv_attn_heads_t *hs, int group, int dtype, float scale, int k,
@@ -1192,13 +1154,12 @@ int spmv_csr_attention_backward_kv_16(spmv_csr_t *t, const spmv_attn_heads_t *hs
 {
     const char *what = "spmv_csr_attention_backward_kv_16";
     if (int rc = attention_header(t, hs, group, what)) return rc;
-    if (int rc = attention_dtype(dtype, what)) return rc;
-    auto run = [&](auto e) {
+    if (int rc = dtype_ok(dtype, false, what)) return rc;
+    return with_element(dtype, [&](auto e) {
         using E = decltype(e);
         return attention_backward_kv<E>(what, t, hs, group, true, scale, k, (const E *)d_Q, ldq, (const E *)d_K, ldk, kv, (const E *)d_V,
                                         ldv, (const E *)d_dO, lddo, d_stats, d_delta, (E *)d_dK, lddk, (E *)d_dV, lddv, stream);
-    };
-    return dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+    });
 }
 
 // ---- the same three passes with an additive fp32 bias per nonzero (fp32, bf16 or fp16 matrices): the most general form only ------
@@ -1208,11 +1169,7 @@ int spmv_csr_attention_backward_kv_16(spmv_csr_t *t, const spmv_attn_heads_t *hs
 static int attention_bias(const spmv_csr_t *h, int heads, int dtype, const float *d_bias, int64_t bias_stride, bool has_dbias,
                           const float *d_dbias, int64_t dbias_stride, const char *what, bool optional = false)
 {
-    if (dtype != SPMV_ATTN_FP32 && dtype != SPMV_ATTN_BF16 && dtype != SPMV_ATTN_FP16) {
-        set_error("%s: dtype = %d (need SPMV_ATTN_FP32 = %d, SPMV_ATTN_BF16 = %d or SPMV_ATTN_FP16 = %d)", what, dtype, (int)SPMV_ATTN_FP32,
-                  (int)SPMV_ATTN_BF16, (int)SPMV_ATTN_FP16);
-        return SPMV_ERR_INVALID;
-    }
+    if (int rc = dtype_ok(dtype, true, what)) return rc;
     if (optional) {
         if (!d_bias && d_dbias) { set_error("%s: dBias without a bias", what); return SPMV_ERR_INVALID; }
     } else if (!d_bias && h->nnz > 0) { set_error("%s: null bias", what); return SPMV_ERR_INVALID; }
@@ -1244,12 +1201,11 @@ int spmv_csr_attention_forward_bias(spmv_csr_t *h, const spmv_attn_heads_t *hs, 
     if (int rc = attention_header(h, hs, group, what)) return rc;
     if (int rc = attention_bias(h, hs->heads, dtype, d_bias, bias_stride, false, nullptr, 0, what)) return rc;
     const AttnBias bb{d_bias, bias_stride, nullptr, 0};
-    auto run = [&](auto e) {
+    return with_element(dtype, [&](auto e) {
         using E = decltype(e);
         return attention_forward<E>(what, h, hs, group, false, scale, k, (const E *)d_Q, ldq, (const E *)d_K, ldk, kv, (const E *)d_V, ldv,
                                     (E *)d_O, ldo, d_stats, stream, &bb);
-    };
-    return dtype == SPMV_ATTN_FP32 ? run(float{}) : dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+    });
 }
 
 int spmv_csr_attention_backward_q_bias(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, int dtype, const float *d_bias,
@@ -1262,12 +1218,11 @@ int spmv_csr_attention_backward_q_bias(spmv_csr_t *h, const spmv_attn_heads_t *h
     if (int rc = attention_header(h, hs, group, what)) return rc;
     if (int rc = attention_bias(h, hs->heads, dtype, d_bias, bias_stride, true, d_dbias, dbias_stride, what)) return rc;
     const AttnBias bb{d_bias, bias_stride, d_dbias, dbias_stride};
-    auto run = [&](auto e) {
+    return with_element(dtype, [&](auto e) {
         using E = decltype(e);
         return attention_backward_q<E>(what, h, hs, group, false, scale, k, (const E *)d_Q, ldq, (const E *)d_K, ldk, kv, (const E *)d_V,
                                        ldv, (const E *)d_O, ldo, (const E *)d_dO, lddo, d_stats, d_delta, (E *)d_dQ, lddq, stream, &bb);
-    };
-    return dtype == SPMV_ATTN_FP32 ? run(float{}) : dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+    });
 }
 
 int spmv_csr_attention_backward_kv_bias(spmv_csr_t *t, const spmv_attn_heads_t *hs, int group, int dtype, const float *d_bias_t,
@@ -1280,12 +1235,11 @@ int spmv_csr_attention_backward_kv_bias(spmv_csr_t *t, const spmv_attn_heads_t *
     if (int rc = attention_header(t, hs, group, what)) return rc;
     if (int rc = attention_bias(t, hs->heads, dtype, d_bias_t, bias_stride, false, nullptr, 0, what)) return rc;
     const AttnBias bb{d_bias_t, bias_stride, nullptr, 0};
-    auto run = [&](auto e) {
+    return with_element(dtype, [&](auto e) {
         using E = decltype(e);
         return attention_backward_kv<E>(what, t, hs, group, true, scale, k, (const E *)d_Q, ldq, (const E *)d_K, ldk, kv, (const E *)d_V,
                                         ldv, (const E *)d_dO, lddo, d_stats, d_delta, (E *)d_dK, lddk, (E *)d_dV, lddv, stream, &bb);
-    };
-    return dtype == SPMV_ATTN_FP32 ? run(float{}) : dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+    });
 }
 
 // ---- the same three passes at widths up to 128: the _bias calls' arguments, an optional bias, the plan of _plan_wide -----------
@@ -1299,12 +1253,11 @@ int spmv_csr_attention_forward_wide(spmv_csr_t *h, const spmv_attn_heads_t *hs, 
     if (int rc = attention_header(h, hs, group, what)) return rc;
     if (int rc = attention_bias(h, hs->heads, dtype, d_bias, bias_stride, false, nullptr, 0, what, true)) return rc;
     const AttnBias bb{d_bias, bias_stride, nullptr, 0};
-    auto run = [&](auto e) {
+    return with_element(dtype, [&](auto e) {
         using E = decltype(e);
         return attention_forward<E>(what, h, hs, group, false, scale, k, (const E *)d_Q, ldq, (const E *)d_K, ldk, kv, (const E *)d_V, ldv,
                                     (E *)d_O, ldo, d_stats, stream, d_bias ? &bb : nullptr, true);
-    };
-    return dtype == SPMV_ATTN_FP32 ? run(float{}) : dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+    });
 }
 
 int spmv_csr_attention_backward_q_wide(spmv_csr_t *h, const spmv_attn_heads_t *hs, int group, int dtype, const float *d_bias,
@@ -1317,13 +1270,12 @@ int spmv_csr_attention_backward_q_wide(spmv_csr_t *h, const spmv_attn_heads_t *h
     if (int rc = attention_header(h, hs, group, what)) return rc;
     if (int rc = attention_bias(h, hs->heads, dtype, d_bias, bias_stride, true, d_dbias, dbias_stride, what, true)) return rc;
     const AttnBias bb{d_bias, bias_stride, d_dbias, dbias_stride};
-    auto run = [&](auto e) {
+    return with_element(dtype, [&](auto e) {
         using E = decltype(e);
         return attention_backward_q<E>(what, h, hs, group, false, scale, k, (const E *)d_Q, ldq, (const E *)d_K, ldk, kv, (const E *)d_V,
                                        ldv, (const E *)d_O, ldo, (const E *)d_dO, lddo, d_stats, d_delta, (E *)d_dQ, lddq, stream,
                                        d_bias ? &bb : nullptr, true);
-    };
-    return dtype == SPMV_ATTN_FP32 ? run(float{}) : dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+    });
 }
 
 int spmv_csr_attention_backward_kv_wide(spmv_csr_t *t, const spmv_attn_heads_t *hs, int group, int dtype, const float *d_bias_t,
@@ -1336,13 +1288,12 @@ int spmv_csr_attention_backward_kv_wide(spmv_csr_t *t, const spmv_attn_heads_t *
     if (int rc = attention_header(t, hs, group, what)) return rc;
     if (int rc = attention_bias(t, hs->heads, dtype, d_bias_t, bias_stride, false, nullptr, 0, what, true)) return rc;
     const AttnBias bb{d_bias_t, bias_stride, nullptr, 0};
-    auto run = [&](auto e) {
+    return with_element(dtype, [&](auto e) {
         using E = decltype(e);
         return attention_backward_kv<E>(what, t, hs, group, true, scale, k, (const E *)d_Q, ldq, (const E *)d_K, ldk, kv, (const E *)d_V,
                                         ldv, (const E *)d_dO, lddo, d_stats, d_delta, (E *)d_dK, lddk, (E *)d_dV, lddv, stream,
                                         d_bias_t ? &bb : nullptr, true);
-    };
-    return dtype == SPMV_ATTN_FP32 ? run(float{}) : dtype == SPMV_ATTN_BF16 ? run(bf16{}) : run(fp16{});
+    });
 }
 
 int spmv_csr_values_changed(spmv_csr_t *h)

@@ -1,6 +1,7 @@
 // kernels_sddmm.hip -- out[n] = U[row(n), :k] . X[col(n), :k] for every stored nonzero n of a CSR handle, k <= 64
 // (spmv_csr_sddmm, include/spmv_hip.h "SDDMM"): the dense-dense product U X^T sampled at the handle's pattern.  Any k in
-// column tiles of 64: spmv_csr_sddmm_cols (sddmm_span_cols below).
+// column tiles of 64: spmv_csr_sddmm_cols (sddmm_span_cols below; the COLS instantiations of the two kernels, which differ
+// from the narrow ones in that one call).  launch_sddmm<E> is the one way in for the three entry points of an element type.
 //
 // The lane groups, their steps and the plan are lane_group.hpp's.  U is rows rows of ldu floats (row-major), X cols rows
 // of ldx floats.  Lane s of a row's group loads columns [4s, 4s+4) of the row's U row once and keeps them in registers;
@@ -102,7 +103,8 @@ struct SddmmArgs {
 };
 
 // a group of V lanes per row; rows of more than row_cap nonzeros are left to the pieces
-template <int V, bool VEC, typename E>
+// (COLS: the kernel of spmv_csr_sddmm_cols, V = kColsV and a.k any width)
+template <int V, bool VEC, typename E, bool COLS = false>
 __global__ __launch_bounds__(kBlock) void k_sddmm_rows(GroupRows g, SddmmArgs<E> a)
 {
     const int lane = threadIdx.x & (kWave - 1), c0 = 4 * (lane & (V - 1));
@@ -110,128 +112,67 @@ __global__ __launch_bounds__(kBlock) void k_sddmm_rows(GroupRows g, SddmmArgs<E>
     if (r < 0) return;
     const int64_t b = g.row_ptr[r], e = g.row_ptr[r + 1];
     if (e == b || e - b > g.row_cap) return;   // (the U row of an empty row is not even loaded)
-    const float4 u = c0 < a.k ? load_wide<VEC>(a.U, a.ldu, r, c0, a.k) : zero4();
-    sddmm_span<V, VEC, E>(lane, b, e, u, g.col_idx, a.X, a.ldx, a.out, c0, a.k);
+    if constexpr (COLS) {
+        sddmm_span_cols<VEC, E>(lane, r, b, e, g.col_idx, a.U, a.ldu, a.X, a.ldx, a.out, a.k);
+    } else {
+        const float4 u = c0 < a.k ? load_wide<VEC>(a.U, a.ldu, r, c0, a.k) : zero4();
+        sddmm_span<V, VEC, E>(lane, b, e, u, g.col_idx, a.X, a.ldx, a.out, c0, a.k);
+    }
 }
 
-// a group of V lanes per piece of a long row
-template <int V, bool VEC, typename E>
+// a group of V lanes per piece of a long row (COLS: as above)
+template <int V, bool VEC, typename E, bool COLS = false>
 __global__ __launch_bounds__(kBlock) void k_sddmm_pieces(GroupPieces g, SddmmArgs<E> a)
 {
     const int lane = threadIdx.x & (kWave - 1), c0 = 4 * (lane & (V - 1));
     int lo;
     const int64_t p = group_piece<V>(g, lo);
     if (p < 0) return;
-    const int64_t r = g.long_row[lo];
-    const int64_t b = g.piece_k0[p], e = b + g.piece_len[p];
-    const float4 u = c0 < a.k ? load_wide<VEC>(a.U, a.ldu, r, c0, a.k) : zero4();
-    sddmm_span<V, VEC, E>(lane, b, e, u, g.col_idx, a.X, a.ldx, a.out, c0, a.k);
+    // (the three loads in this order: with long_row first the COLS instantiations schedule differently)
+    const int64_t b = g.piece_k0[p], r = g.long_row[lo], e = b + g.piece_len[p];
+    if constexpr (COLS) {
+        sddmm_span_cols<VEC, E>(lane, r, b, e, g.col_idx, a.U, a.ldu, a.X, a.ldx, a.out, a.k);
+    } else {
+        const float4 u = c0 < a.k ? load_wide<VEC>(a.U, a.ldu, r, c0, a.k) : zero4();
+        sddmm_span<V, VEC, E>(lane, b, e, u, g.col_idx, a.X, a.ldx, a.out, c0, a.k);
+    }
 }
 
-// the two kernels of spmv_csr_sddmm_cols: a group of kColsV lanes per row, and per piece of a long row (a.k: any width)
-template <bool VEC, typename E>
-__global__ __launch_bounds__(kBlock) void k_sddmm_cols_rows(GroupRows g, SddmmArgs<E> a)
+// the two launches of a call; who: the entry point, for a refusal
+template <int V, bool VEC, typename E, bool COLS>
+int launch_sddmm_v(const spmv_csr &h, const char *who, const SddmmArgs<E> &a, hipStream_t s)
 {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t r = group_row<kColsV>(g);
-    if (r < 0) return;
-    const int64_t b = g.row_ptr[r], e = g.row_ptr[r + 1];
-    if (e == b || e - b > g.row_cap) return;
-    sddmm_span_cols<VEC, E>(lane, r, b, e, g.col_idx, a.U, a.ldu, a.X, a.ldx, a.out, a.k);
-}
-
-template <bool VEC, typename E>
-__global__ __launch_bounds__(kBlock) void k_sddmm_cols_pieces(GroupPieces g, SddmmArgs<E> a)
-{
-    const int lane = threadIdx.x & (kWave - 1);
-    int lo;
-    const int64_t p = group_piece<kColsV>(g, lo);
-    if (p < 0) return;
-    const int64_t b = g.piece_k0[p];
-    sddmm_span_cols<VEC, E>(lane, g.long_row[lo], b, b + g.piece_len[p], g.col_idx, a.U, a.ldu, a.X, a.ldx, a.out, a.k);
-}
-
-template <bool VEC, typename E>
-int launch_sddmm_cols_v(const spmv_csr &h, const SddmmArgs<E> &a, hipStream_t s)
-{
-    constexpr int V = kColsV;
-    const int64_t nblocks = group_row_blocks("spmv_csr_sddmm_cols", h, V);
+    const int64_t nblocks = group_row_blocks(who, h, V);
     if (nblocks < 0) return SPMV_ERR_INVALID;
-    hipLaunchKernelGGL((k_sddmm_cols_rows<VEC, E>), dim3((unsigned)nblocks), dim3(kBlock), 0, s, group_rows(h, V, nblocks), a);
-    SPMV_LAUNCHED("k_sddmm_cols_rows");
-    if (!h.plan_spmm.n_long) return SPMV_OK;
-    hipLaunchKernelGGL((k_sddmm_cols_pieces<VEC, E>), group_grid(h.plan_spmm.pieces, V), dim3(kBlock), 0, s, group_pieces(h, nullptr), a);
-    SPMV_LAUNCHED("k_sddmm_cols_pieces");
-    return SPMV_OK;
-}
-
-template <typename E>
-int launch_sddmm_cols_e(const spmv_csr &h, int k, const E *U, int64_t ldu, const E *X, int64_t ldx, float *out, hipStream_t s)
-{
-    if (h.rows == 0 || h.nnz == 0) return SPMV_OK;
-    const SddmmArgs<E> a{U, ldu, X, ldx, out, k};
-    return ldu % 4 == 0 && ldx % 4 == 0 ? launch_sddmm_cols_v<true, E>(h, a, s) : launch_sddmm_cols_v<false, E>(h, a, s);
-}
-
-template <int V, bool VEC, typename E>
-int launch_sddmm_v(const spmv_csr &h, const SddmmArgs<E> &a, hipStream_t s)
-{
-    const int64_t nblocks = group_row_blocks(kIs16<E> ? "spmv_csr_sddmm_16" : "spmv_csr_sddmm", h, V);
-    if (nblocks < 0) return SPMV_ERR_INVALID;
-    hipLaunchKernelGGL((k_sddmm_rows<V, VEC, E>), dim3((unsigned)nblocks), dim3(kBlock), 0, s, group_rows(h, V, nblocks), a);
+    hipLaunchKernelGGL((k_sddmm_rows<V, VEC, E, COLS>), dim3((unsigned)nblocks), dim3(kBlock), 0, s, group_rows(h, V, nblocks), a);
     SPMV_LAUNCHED("k_sddmm_rows");
     if (!h.plan_spmm.n_long) return SPMV_OK;
-    hipLaunchKernelGGL((k_sddmm_pieces<V, VEC, E>), group_grid(h.plan_spmm.pieces, V), dim3(kBlock), 0, s,
+    hipLaunchKernelGGL((k_sddmm_pieces<V, VEC, E, COLS>), group_grid(h.plan_spmm.pieces, V), dim3(kBlock), 0, s,
                        group_pieces(h, nullptr), a);
     SPMV_LAUNCHED("k_sddmm_pieces");
     return SPMV_OK;
 }
 
+}  // namespace
+
+// Arguments checked by capi.hip (product_args): ld >= k, U / X aligned for E, and 1 <= k <= 64 with the SpMM plan made or, with
+// `cols`, 1 <= k <= SPMV_COLS_MAX_K with the _cols plan covering k.  V = pow2 >= ceil(k / 4), or kColsV whatever k is.
 template <typename E>
-int launch_sddmm_e(const spmv_csr &h, int k, const E *U, int64_t ldu, const E *X, int64_t ldx, float *out, hipStream_t s)
+int launch_sddmm(const spmv_csr &h, const char *who, bool cols, int k, const E *U, int64_t ldu, const E *X, int64_t ldx, float *out,
+                 hipStream_t s)
 {
     if (h.rows == 0 || h.nnz == 0) return SPMV_OK;
     const SddmmArgs<E> a{U, ldu, X, ldx, out, k};
     const bool vec = ldu % 4 == 0 && ldx % 4 == 0;
+    if (cols) return vec ? launch_sddmm_v<kColsV, true, E, true>(h, who, a, s) : launch_sddmm_v<kColsV, false, E, true>(h, who, a, s);
     return dispatch_lanes((k + 3) / 4, [&](auto v) {
         constexpr int V = decltype(v)::value;
-        return vec ? launch_sddmm_v<V, true, E>(h, a, s) : launch_sddmm_v<V, false, E>(h, a, s);
+        return vec ? launch_sddmm_v<V, true, E, false>(h, who, a, s) : launch_sddmm_v<V, false, E, false>(h, who, a, s);
     });
 }
 
-}  // namespace
-
-// arguments checked by spmv_csr_sddmm: 1 <= k <= 64, ld >= k, U / X 16-byte aligned, the SpMM plan made
-int launch_sddmm(const spmv_csr &h, int k, const float *U, int64_t ldu, const float *X, int64_t ldx, float *out, hipStream_t s)
-{
-    return launch_sddmm_e<float>(h, k, U, ldu, X, ldx, out, s);
-}
-
-// and by spmv_csr_sddmm_16: the same with U / X 8-byte aligned and every ld in 16-bit elements
-int launch_sddmm(const spmv_csr &h, int k, const bf16 *U, int64_t ldu, const bf16 *X, int64_t ldx, float *out, hipStream_t s)
-{
-    return launch_sddmm_e<bf16>(h, k, U, ldu, X, ldx, out, s);
-}
-
-int launch_sddmm(const spmv_csr &h, int k, const fp16 *U, int64_t ldu, const fp16 *X, int64_t ldx, float *out, hipStream_t s)
-{
-    return launch_sddmm_e<fp16>(h, k, U, ldu, X, ldx, out, s);
-}
-
-// arguments checked by spmv_csr_sddmm_cols: 1 <= k <= SPMV_COLS_MAX_K, ld >= k, U / X aligned for E, the _cols plan covers k
-int launch_sddmm_cols(const spmv_csr &h, int k, const float *U, int64_t ldu, const float *X, int64_t ldx, float *out, hipStream_t s)
-{
-    return launch_sddmm_cols_e<float>(h, k, U, ldu, X, ldx, out, s);
-}
-
-int launch_sddmm_cols(const spmv_csr &h, int k, const bf16 *U, int64_t ldu, const bf16 *X, int64_t ldx, float *out, hipStream_t s)
-{
-    return launch_sddmm_cols_e<bf16>(h, k, U, ldu, X, ldx, out, s);
-}
-
-int launch_sddmm_cols(const spmv_csr &h, int k, const fp16 *U, int64_t ldu, const fp16 *X, int64_t ldx, float *out, hipStream_t s)
-{
-    return launch_sddmm_cols_e<fp16>(h, k, U, ldu, X, ldx, out, s);
-}
+template int launch_sddmm(const spmv_csr &, const char *, bool, int, const float *, int64_t, const float *, int64_t, float *, hipStream_t);
+template int launch_sddmm(const spmv_csr &, const char *, bool, int, const bf16 *, int64_t, const bf16 *, int64_t, float *, hipStream_t);
+template int launch_sddmm(const spmv_csr &, const char *, bool, int, const fp16 *, int64_t, const fp16 *, int64_t, float *, hipStream_t);
 
 }  // namespace spmv

@@ -28,6 +28,12 @@
 // column's bits are the narrow call's.  Each tile re-reads (col_idx, vals): 8 bytes per nonzero against up to 256 bytes of
 // gathered X.  The long rows' partials go to a scratch of the plan's own (spmv_csr_spmm_plan_cols): piece p holds m * 64
 // floats, column c of the call at offset c (64-bit offsets).
+//
+// One body per kernel, one launch function.  A kernel without TILED is the TILED one at m = 1, tile 0, the row block
+// blockIdx.x: its `if constexpr (TILED)` is the only place that differs.  launch_spmm<E> is the one way in for the three
+// entry points of an element type (`cols`: column tiles; `who`: the entry point's name for a refusal); launch_spmm_v
+// issues the three launches of either kind: V from dispatch_lanes or kColsV, the grid plain or cols_grid, the scratch
+// d_partial or d_partial_cols.
 #include <algorithm>
 #include <numeric>
 #include <vector>
@@ -139,14 +145,9 @@ template <int V, bool VEC, typename E, bool TILED = false>
 __global__ __launch_bounds__(kBlock) void k_spmm_rows(GroupRows g, SpmmArgs<E> a)
 {
     const int lane = threadIdx.x & (kWave - 1), c0 = 4 * (lane & (V - 1));
-    int64_t r;
-    if constexpr (TILED) {
-        int64_t bid;
-        cols_advance(a, cols_tile(a.k, bid));
-        r = group_row<V>(g, bid);
-    } else {
-        r = group_row<V>(g);
-    }
+    int64_t bid = blockIdx.x;
+    if constexpr (TILED) cols_advance(a, cols_tile(a.k, bid));
+    const int64_t r = group_row<V>(g, bid);
     if (r < 0) return;
     const int64_t b = g.row_ptr[r], e = g.row_ptr[r + 1];
     if (e - b > g.row_cap) return;
@@ -160,21 +161,17 @@ template <int V, bool VEC, typename E, bool TILED = false>
 __global__ __launch_bounds__(kBlock) void k_spmm_pieces(GroupPieces g, SpmmArgs<E> a)
 {
     const int lane = threadIdx.x & (kWave - 1), c0 = 4 * (lane & (V - 1));
-    int64_t p, at;
+    int64_t bid = blockIdx.x;
+    int m = 1, tile = 0;
     if constexpr (TILED) {
-        int64_t bid;
-        const int m = cols_tiles(a.k), tile = cols_tile(a.k, bid);
+        m = cols_tiles(a.k), tile = cols_tile(a.k, bid);
         cols_advance(a, tile);
-        p = group_piece<V>(g, bid);
-        at = (p * m + tile) * kColsTile;
-    } else {
-        p = group_piece<V>(g);
-        at = p * kSpmmMaxK;
     }
+    const int64_t p = group_piece<V>(g, bid);
     if (p < 0) return;
     const int64_t b = g.piece_k0[p], e = b + g.piece_len[p];
     const float4 acc = row_dot<V, VEC>(lane, b, e, g.col_idx, a.vals, a.X, a.ldx, c0, a.k);
-    if (c0 < a.k) *reinterpret_cast<float4 *>(g.scratch + at + c0) = acc;
+    if (c0 < a.k) *reinterpret_cast<float4 *>(g.scratch + (p * m + tile) * kColsTile + c0) = acc;
 }
 
 // one thread per (long row, column < k): the row's partials added in piece order, the sum rounded to E at its store
@@ -185,25 +182,18 @@ __global__ __launch_bounds__(kBlock) void k_spmm_combine(int n_long, const int32
                                                              const float *__restrict__ partial, E *__restrict__ Y,
                                                              int64_t ldy, int k)
 {
+    int64_t bid = blockIdx.x;
+    int m = 1, tile = 0, kt = k;
     if constexpr (TILED) {
-        int64_t bid;
-        const int m = cols_tiles(k), tile = cols_tile(k, bid);
-        const int kt = min(kColsTile, k - kColsTile * tile);
-        const int64_t t = bid * kBlock + threadIdx.x;
-        const int64_t i = t / kt;
-        const int c = kColsTile * tile + (int)(t % kt);
-        if (i >= n_long) return;
-        float acc = 0.0f;
-        for (int p = long_first[i]; p < long_first[i + 1]; ++p) acc += partial[(int64_t)p * m * kColsTile + c];
-        store_slice<false>(Y + (int64_t)long_row[i] * ldy + c, make_float4(acc, 0.0f, 0.0f, 0.0f), 0, 1);
-        return;
+        m = cols_tiles(k), tile = cols_tile(k, bid);
+        kt = min(kColsTile, k - kColsTile * tile);
     }
-    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int64_t i = t / k;
-    const int c = (int)(t % k);
+    const int64_t t = bid * kBlock + threadIdx.x;
+    const int64_t i = t / kt;
+    const int c = kColsTile * tile + (int)(t % kt);
     if (i >= n_long) return;
     float acc = 0.0f;
-    for (int p = long_first[i]; p < long_first[i + 1]; ++p) acc += partial[(int64_t)p * kSpmmMaxK + c];
+    for (int p = long_first[i]; p < long_first[i + 1]; ++p) acc += partial[(int64_t)p * m * kColsTile + c];
     store_slice<false>(Y + (int64_t)long_row[i] * ldy + c, make_float4(acc, 0.0f, 0.0f, 0.0f), 0, 1);     // (one column)
 }
 
@@ -300,101 +290,50 @@ int64_t spmm_plan_bytes(const spmv_csr &h)
            (int64_t)p.pieces * cols_tiles(p.cols_k) * kColsTile * 4;
 }
 
-template <int V, bool VEC, typename E>
-static int launch_spmm_v(const spmv_csr &h, const SpmmArgs<E> &a, hipStream_t s)
+// the three launches of a call (TILED: each over all m column tiles); who: the entry point, for a refusal
+template <int V, bool VEC, typename E, bool TILED>
+static int launch_spmm_v(const spmv_csr &h, const char *who, const SpmmArgs<E> &a, hipStream_t s)
 {
     const SpmmPlan &p = h.plan_spmm;
-    const int64_t nblocks = group_row_blocks(kIs16<E> ? "spmv_csr_spmm_16" : "spmv_csr_spmm", h, V);
+    const int m = TILED ? cols_tiles(a.k) : 1;
+    const int64_t nblocks = TILED ? group_tile_blocks(who, h, V, m) : group_row_blocks(who, h, V);
     if (nblocks < 0) return SPMV_ERR_INVALID;
-    hipLaunchKernelGGL((k_spmm_rows<V, VEC, E>), dim3((unsigned)nblocks), dim3(kBlock), 0, s, group_rows(h, V, nblocks), a);
+    const auto grid = [&](int64_t blocks) { return TILED ? cols_grid(blocks, m) : dim3((unsigned)blocks); };
+    float *partial = TILED ? p.d_partial_cols : p.d_partial;
+    hipLaunchKernelGGL((k_spmm_rows<V, VEC, E, TILED>), grid(nblocks), dim3(kBlock), 0, s, group_rows(h, V, nblocks), a);
     SPMV_LAUNCHED("k_spmm_rows");
     if (!p.n_long) return SPMV_OK;
-    hipLaunchKernelGGL((k_spmm_pieces<V, VEC, E>), group_grid(p.pieces, V), dim3(kBlock), 0, s, group_pieces(h, p.d_partial), a);
+    hipLaunchKernelGGL((k_spmm_pieces<V, VEC, E, TILED>), grid(group_grid(p.pieces, V).x), dim3(kBlock), 0, s, group_pieces(h, partial), a);
     SPMV_LAUNCHED("k_spmm_pieces");
-    const int64_t threads = (int64_t)p.n_long * a.k;
-    hipLaunchKernelGGL(k_spmm_combine<E>, dim3((unsigned)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, p.n_long,
-                       p.d_long_row, p.d_long_first, p.d_partial, a.Y, a.ldy, a.k);
+    // (TILED: the threads of a tile; a narrower last tile leaves some idle)
+    const int64_t blocks = ((int64_t)p.n_long * (TILED ? kColsTile : a.k) + kBlock - 1) / kBlock;
+    if (TILED && blocks * m * kBlock >= (1LL << 32)) {
+        set_error("%s: %d long rows x %d column tiles reach the launch limit of 2^32 work-items", who, p.n_long, m);
+        return SPMV_ERR_INVALID;
+    }
+    hipLaunchKernelGGL((k_spmm_combine<E, TILED>), grid(blocks), dim3(kBlock), 0, s, p.n_long, p.d_long_row, p.d_long_first, partial,
+                       a.Y, a.ldy, a.k);
     SPMV_LAUNCHED("k_spmm_combine");
     return SPMV_OK;
 }
 
+// Arguments checked by capi.hip (product_args): ld >= k, X / Y aligned for E, and 1 <= k <= 64 with the plan made or, with
+// `cols`, 1 <= k <= SPMV_COLS_MAX_K with the _cols plan covering k.  V = pow2 >= ceil(k / 4), or kColsV per column tile.
 template <typename E>
-static int launch_spmm_e(const spmv_csr &h, int k, const E *X, int64_t ldx, E *Y, int64_t ldy, hipStream_t s)
+int launch_spmm(const spmv_csr &h, const char *who, bool cols, int k, const E *X, int64_t ldx, E *Y, int64_t ldy, hipStream_t s)
 {
     if (h.rows == 0) return SPMV_OK;
     const SpmmArgs<E> a{h.d_vals, X, ldx, Y, ldy, k};
     const bool vec = ldx % 4 == 0 && ldy % 4 == 0;
+    if (cols) return vec ? launch_spmm_v<kColsV, true, E, true>(h, who, a, s) : launch_spmm_v<kColsV, false, E, true>(h, who, a, s);
     return dispatch_lanes((k + 3) / 4, [&](auto v) {
         constexpr int V = decltype(v)::value;
-        return vec ? launch_spmm_v<V, true, E>(h, a, s) : launch_spmm_v<V, false, E>(h, a, s);
+        return vec ? launch_spmm_v<V, true, E, false>(h, who, a, s) : launch_spmm_v<V, false, E, false>(h, who, a, s);
     });
 }
 
-// the three launches of a _cols call, each over all m tiles
-template <bool VEC, typename E>
-static int launch_spmm_cols_v(const spmv_csr &h, const SpmmArgs<E> &a, hipStream_t s)
-{
-    constexpr int V = kColsV;
-    const SpmmPlan &p = h.plan_spmm;
-    const int m = cols_tiles(a.k);
-    const int64_t nblocks = group_tile_blocks("spmv_csr_spmm_cols", h, V, m);
-    if (nblocks < 0) return SPMV_ERR_INVALID;
-    hipLaunchKernelGGL((k_spmm_rows<V, VEC, E, true>), cols_grid(nblocks, m), dim3(kBlock), 0, s, group_rows(h, V, nblocks), a);
-    SPMV_LAUNCHED("k_spmm_rows");
-    if (!p.n_long) return SPMV_OK;
-    hipLaunchKernelGGL((k_spmm_pieces<V, VEC, E, true>), cols_grid(group_grid(p.pieces, V).x, m), dim3(kBlock), 0, s,
-                       group_pieces(h, p.d_partial_cols), a);
-    SPMV_LAUNCHED("k_spmm_pieces");
-    const int64_t threads = (int64_t)p.n_long * kColsTile;     // (of a tile; a narrower last tile leaves some idle)
-    if ((threads + kBlock - 1) / kBlock * m * kBlock >= (1LL << 32)) {
-        set_error("spmv_csr_spmm_cols: %d long rows x %d column tiles reach the launch limit of 2^32 work-items", p.n_long, m);
-        return SPMV_ERR_INVALID;
-    }
-    hipLaunchKernelGGL((k_spmm_combine<E, true>), cols_grid((threads + kBlock - 1) / kBlock, m), dim3(kBlock), 0, s, p.n_long,
-                       p.d_long_row, p.d_long_first, p.d_partial_cols, a.Y, a.ldy, a.k);
-    SPMV_LAUNCHED("k_spmm_combine");
-    return SPMV_OK;
-}
-
-template <typename E>
-static int launch_spmm_cols_e(const spmv_csr &h, int k, const E *X, int64_t ldx, E *Y, int64_t ldy, hipStream_t s)
-{
-    if (h.rows == 0) return SPMV_OK;
-    const SpmmArgs<E> a{h.d_vals, X, ldx, Y, ldy, k};
-    return ldx % 4 == 0 && ldy % 4 == 0 ? launch_spmm_cols_v<true, E>(h, a, s) : launch_spmm_cols_v<false, E>(h, a, s);
-}
-
-// arguments checked by spmv_csr_spmm_cols: 1 <= k <= SPMV_COLS_MAX_K, ld >= k, X / Y aligned for E, the _cols plan covers k
-int launch_spmm_cols(const spmv_csr &h, int k, const float *X, int64_t ldx, float *Y, int64_t ldy, hipStream_t s)
-{
-    return launch_spmm_cols_e<float>(h, k, X, ldx, Y, ldy, s);
-}
-
-int launch_spmm_cols(const spmv_csr &h, int k, const bf16 *X, int64_t ldx, bf16 *Y, int64_t ldy, hipStream_t s)
-{
-    return launch_spmm_cols_e<bf16>(h, k, X, ldx, Y, ldy, s);
-}
-
-int launch_spmm_cols(const spmv_csr &h, int k, const fp16 *X, int64_t ldx, fp16 *Y, int64_t ldy, hipStream_t s)
-{
-    return launch_spmm_cols_e<fp16>(h, k, X, ldx, Y, ldy, s);
-}
-
-// arguments checked by spmv_csr_spmm: 1 <= k <= 64, ld >= k, X / Y 16-byte aligned, the plan made
-int launch_spmm(const spmv_csr &h, int k, const float *X, int64_t ldx, float *Y, int64_t ldy, hipStream_t s)
-{
-    return launch_spmm_e<float>(h, k, X, ldx, Y, ldy, s);
-}
-
-// and by spmv_csr_spmm_16: the same with X / Y 8-byte aligned and every ld in 16-bit elements
-int launch_spmm(const spmv_csr &h, int k, const bf16 *X, int64_t ldx, bf16 *Y, int64_t ldy, hipStream_t s)
-{
-    return launch_spmm_e<bf16>(h, k, X, ldx, Y, ldy, s);
-}
-
-int launch_spmm(const spmv_csr &h, int k, const fp16 *X, int64_t ldx, fp16 *Y, int64_t ldy, hipStream_t s)
-{
-    return launch_spmm_e<fp16>(h, k, X, ldx, Y, ldy, s);
-}
+template int launch_spmm(const spmv_csr &, const char *, bool, int, const float *, int64_t, float *, int64_t, hipStream_t);
+template int launch_spmm(const spmv_csr &, const char *, bool, int, const bf16 *, int64_t, bf16 *, int64_t, hipStream_t);
+template int launch_spmm(const spmv_csr &, const char *, bool, int, const fp16 *, int64_t, fp16 *, int64_t, hipStream_t);
 
 }  // namespace spmv

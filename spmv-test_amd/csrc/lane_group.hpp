@@ -9,11 +9,12 @@
 // row the CSR row refers to.  A workgroup is kBlock = 256 lanes, 256 / V groups; the row blocks are dealt so that each of
 // the 8 XCDs takes one contiguous range of them (xcd_item64: neighbouring rows share lines of the gathered operand in
 // that XCD's L2).  Fused attention's _wide entry points add a sixth group, V = 32, for operands of 65 to 128 columns: see
-// "A step narrower than the group" below; SpMM and SDDMM go past 64 columns in tiles of 64 at V = 16 ("Column tiles" below).  The groups take the rows in the plan's order (stably by length inside blocks of 4096 rows, so the rows a
-// wavefront walks side by side end at nearly the same step), except at V = 1: see group_rows.
+// "A step narrower than the group" below; SpMM and SDDMM go past 64 columns in tiles of 64 at V = 16 ("Column tiles" below).
+// The groups take the rows in the plan's order (stably by length inside blocks of 4096 rows, so the rows a wavefront walks
+// side by side end at nearly the same step), except at V = 1: see group_rows.
 // Heads (fused attention only).  A launch may carry several heads of one pattern in blockIdx.y and blockIdx.z (the query head
-// within its group of heads that share K and V, and the group; kernels_attention.hip); group_row, group_piece and
-// xcd_item64 keep reading blockIdx.x alone.  Workgroups are dispatched x-fastest, so the blocks of one head that an XCD sees
+// within its group of heads that share K and V, and the group; kernels_attention.hip); group_row and group_piece keep
+// reading blockIdx.x alone (their default `bid`).  Workgroups are dispatched x-fastest, so the blocks of one head that an XCD sees
 // are still one residue class of blockIdx.x mod 8, which xcd_item64 still maps to one contiguous range of row blocks: the
 // L2 argument above holds head by head (where the grid's x extent is no multiple of 8 the class an XCD takes shifts from
 // one head to the next, and stays one class).  This is reasoning from the dispatch order, not a measurement.
@@ -341,48 +342,33 @@ struct GroupPieces {
     float *scratch;     // the caller's floats per piece
 };
 
-// the row of slot `threadIdx.x / V` of the block, or -1 (group-uniform: a group never splits here)
-template <int V>
-__device__ __forceinline__ int64_t group_row(const GroupRows &g)
-{
-    const int64_t slot = xcd_item64(blockIdx.x, g.nblocks) * (kBlock / V) + threadIdx.x / V;
-    if (slot >= g.rows) return -1;
-    return g.order ? g.order[slot] : slot;
-}
-
-// the piece of the group, or -1 (group-uniform)
-template <int V>
-__device__ __forceinline__ int64_t group_piece(const GroupPieces &g)
-{
-    const int64_t p = (int64_t)blockIdx.x * (kBlock / V) + threadIdx.x / V;
-    return p < g.npieces ? p : -1;
-}
-
 // Column tiles (the _cols calls of SpMM and SDDMM only).  A call at any width k runs as m = cols_tiles(k) tiles of
 // kColsTile = 64 columns, tile t the columns [64t, 64t + k_t) with k_t = min(64, k - 64t): each tile is the model above at
 // V = 16 on operands advanced by 64t elements (which keeps the 16-byte / 8-byte path wherever the lds allow it).  SpMM
-// carries the tile in the grid, so blockIdx.x alone no longer names the row block there: the two functions below take
-// the index of the row block (of the block of pieces) from the kernel.  SDDMM walks the tiles inside a step.
+// carries the tile in the grid, so blockIdx.x alone no longer names the row block there: its TILED kernels hand `bid`, the
+// index of the row block (of the block of pieces), to the two functions below.  SDDMM walks the tiles inside a step.
 constexpr int kColsTile = 64;
 constexpr int kColsV = 16;          // the lane group of every tile (kColsTile / 4 lanes)
 __host__ __device__ constexpr int cols_tiles(int k) { return (k + kColsTile - 1) / kColsTile; }
 
+// the row of slot `threadIdx.x / V` of row block `bid`, or -1 (group-uniform: a group never splits here)
 template <int V>
-__device__ __forceinline__ int64_t group_row(const GroupRows &g, int64_t bid)
+__device__ __forceinline__ int64_t group_row(const GroupRows &g, int64_t bid = blockIdx.x)
 {
     const int64_t slot = xcd_item64(bid, g.nblocks) * (kBlock / V) + threadIdx.x / V;
     if (slot >= g.rows) return -1;
     return g.order ? g.order[slot] : slot;
 }
 
+// the piece of the group in block `bid` of the pieces, or -1 (group-uniform)
 template <int V>
-__device__ __forceinline__ int64_t group_piece(const GroupPieces &g, int64_t bid)
+__device__ __forceinline__ int64_t group_piece(const GroupPieces &g, int64_t bid = blockIdx.x)
 {
     const int64_t p = bid * (kBlock / V) + threadIdx.x / V;
     return p < g.npieces ? p : -1;
 }
 
-// the same and the index of its long row: long_first[lo] <= p < long_first[lo + 1]  (long_first[0] = 0,
+// the same (of block blockIdx.x) and the index of its long row: long_first[lo] <= p < long_first[lo + 1]  (long_first[0] = 0,
 // long_first[n_long] = npieces)
 template <int V>
 __device__ __forceinline__ int64_t group_piece(const GroupPieces &g, int &lo)

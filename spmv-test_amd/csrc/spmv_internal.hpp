@@ -375,23 +375,17 @@ void scatter_describe(const ScatteredPlan &p, const spmv_csr &h, char *buf, int 
 double binned_tile_nonzeros(const spmv_csr &h, int bin_rows);
 // kernels_spmm.hip: spmv_csr_spmm
 int plan_spmm(spmv_csr &h, hipStream_t s);
-int launch_spmm(const spmv_csr &h, int k, const float *X, int64_t ldx, float *Y, int64_t ldy, hipStream_t s);
-int launch_spmm(const spmv_csr &h, int k, const bf16 *X, int64_t ldx, bf16 *Y, int64_t ldy, hipStream_t s);     // spmv_csr_spmm_16:
-int launch_spmm(const spmv_csr &h, int k, const fp16 *X, int64_t ldx, fp16 *Y, int64_t ldy, hipStream_t s);     // every ld in elements
+int plan_spmm_cols(spmv_csr &h, int k_max, hipStream_t s);      // and the scratch of the _cols calls at up to k_max columns
 int64_t spmm_plan_bytes(const spmv_csr &h);
-// the same at any k, in column tiles of 64 (spmv_csr_spmm_cols; fp32, bf16 or fp16 matrices), and their plan
-int plan_spmm_cols(spmv_csr &h, int k_max, hipStream_t s);
-int launch_spmm_cols(const spmv_csr &h, int k, const float *X, int64_t ldx, float *Y, int64_t ldy, hipStream_t s);
-int launch_spmm_cols(const spmv_csr &h, int k, const bf16 *X, int64_t ldx, bf16 *Y, int64_t ldy, hipStream_t s);
-int launch_spmm_cols(const spmv_csr &h, int k, const fp16 *X, int64_t ldx, fp16 *Y, int64_t ldy, hipStream_t s);
+// One launch function per product, instantiated for E = float, bf16 and fp16 (every ld in elements of E).  who: the entry
+// point's name, for a refusal.  cols = false: k <= 64, a lane group sized by k (spmv_csr_spmm, _16; spmv_csr_sddmm, _16);
+// cols = true: any k in column tiles of 64 on the plan of plan_spmm_cols (spmv_csr_spmm_cols, spmv_csr_sddmm_cols).
+template <typename E>
+int launch_spmm(const spmv_csr &h, const char *who, bool cols, int k, const E *X, int64_t ldx, E *Y, int64_t ldy, hipStream_t s);
 // kernels_sddmm.hip: spmv_csr_sddmm (on the plan of plan_spmm)
-int launch_sddmm(const spmv_csr &h, int k, const float *U, int64_t ldu, const float *X, int64_t ldx, float *out, hipStream_t s);
-int launch_sddmm(const spmv_csr &h, int k, const bf16 *U, int64_t ldu, const bf16 *X, int64_t ldx, float *out, hipStream_t s);   // spmv_csr_sddmm_16
-int launch_sddmm(const spmv_csr &h, int k, const fp16 *U, int64_t ldu, const fp16 *X, int64_t ldx, float *out, hipStream_t s);
-// the same at any k: the tiles' results added in tile order (spmv_csr_sddmm_cols)
-int launch_sddmm_cols(const spmv_csr &h, int k, const float *U, int64_t ldu, const float *X, int64_t ldx, float *out, hipStream_t s);
-int launch_sddmm_cols(const spmv_csr &h, int k, const bf16 *U, int64_t ldu, const bf16 *X, int64_t ldx, float *out, hipStream_t s);
-int launch_sddmm_cols(const spmv_csr &h, int k, const fp16 *U, int64_t ldu, const fp16 *X, int64_t ldx, float *out, hipStream_t s);
+template <typename E>
+int launch_sddmm(const spmv_csr &h, const char *who, bool cols, int k, const E *U, int64_t ldu, const E *X, int64_t ldx, float *out,
+                 hipStream_t s);
 // kernels_softmax.hip: spmv_csr_row_softmax / spmv_csr_row_softmax_backward (on the plan of plan_spmm and its scratch)
 int launch_row_softmax(const spmv_csr &h, float scale, const float *scores, float *out, hipStream_t s);
 int launch_row_softmax_backward(const spmv_csr &h, float scale, const float *P, const float *dP, float *dS, hipStream_t s);

@@ -48,7 +48,7 @@ class SparseMatmul(torch.autograd.Function):
     def forward(ctx, layer, vals, X):
         X = _operand(X, "X", layer.A.cols, max_k=layer.k_max)
         Y = torch.empty((layer.A.rows, X.shape[1]), dtype=X.dtype, device=X.device)
-        (layer.A.spmm if layer.k_max is None else layer.A.spmm_cols)(X, Y)
+        layer._forward(X, Y)
         ctx.layer = layer
         ctx.save_for_backward(X)
         return Y
@@ -58,15 +58,14 @@ class SparseMatmul(torch.autograd.Function):
         layer = ctx.layer
         X, = ctx.saved_tensors
         dY = _operand(dY, "dY", layer.A.rows, like=X, max_k=layer.k_max)
-        wide = layer.k_max is not None
         dvals = dX = None
         if ctx.needs_input_grad[1]:
             dvals = torch.empty(layer.A.nnz, dtype=torch.float32, device=dY.device)
-            (layer.A.sddmm_cols if wide else layer.A.sddmm)(dY, X, dvals)
+            layer._dvals(dY, X, dvals)
         if ctx.needs_input_grad[2]:
             dX = torch.empty((layer.A.cols, dY.shape[1]), dtype=dY.dtype, device=dY.device)
             layer.T.transpose_values(layer.A)      # A's values as they are now
-            (layer.T.spmm_cols if wide else layer.T.spmm)(dY, dX)
+            layer._dx(dY, dX)
         return None, dvals, dX
 
 
@@ -86,12 +85,15 @@ class SparseLayer:
         self.vals = vals
         self.A = capi.CsrMatrix.from_device(rows, cols, row_ptr, col_idx, vals)
         self.T = self.A.transpose(keep_map=True)
+        # the narrow calls or the _cols calls, chosen here once: what SparseMatmul runs for Y, dvals and dX
         if k_max is None:
             self.A.spmm_plan()
             self.T.spmm_plan()
+            self._forward, self._dvals, self._dx = self.A.spmm, self.A.sddmm, self.T.spmm
         else:
             self.A.spmm_plan_cols(k_max)
             self.T.spmm_plan_cols(k_max)
+            self._forward, self._dvals, self._dx = self.A.spmm_cols, self.A.sddmm_cols, self.T.spmm_cols
 
     def __call__(self, X):
         return SparseMatmul.apply(self, self.vals, X)

@@ -21,6 +21,7 @@ import numpy as np
 
 HERE = Path(__file__).resolve().parent
 GOLDEN = HERE / "attention_refusals.json"
+PREFIX = "spmv_csr_attention_"
 
 N, W, LD, HEADS, GROUP, SCALE = 8, 8, 8, 4, 2, 0.25
 INT64_MAX = 2 ** 63 - 1
@@ -154,20 +155,17 @@ class Fixture:
             a.close()
 
 
-PREFIX = "spmv_csr_attention_"
-
-
-def write_golden(results):
+def write_golden(results, golden=GOLDEN, prefix=lambda call: PREFIX + call):
     """results: {call: {case name: (status, text)}} in the order of CALLS and cases().  The file keeps it whole in little
-    space.  "messages": the distinct (status, text), the call's name at the start of a text written as "@".  Per call,
-    "singles": {corruption: message index}; "pairs": a digit per pair of cases() in order, 0 or 1 where the pair answers
-    what its first or its second corruption answers alone, 2 where it answers something else, which "others" lists by
-    name."""
+    space.  "messages": the distinct (status, text), the call's name (prefix(call)) at the start of a text written as "@".
+    Per call, "singles": {corruption: message index}; "pairs": a digit per pair of cases() in order, 0 or 1 where the pair
+    answers what its first or its second corruption answers alone, 2 where it answers something else, which "others" lists
+    by name."""
     messages, calls = [], {}
 
     def index(call, status, text):
-        assert text.startswith(PREFIX + call) and "@" not in text
-        m = [status, "@" + text[len(PREFIX + call):]]
+        assert text.startswith(prefix(call)) and "@" not in text
+        m = [status, "@" + text[len(prefix(call)):]]
         if m not in messages:
             messages.append(m)
         return messages.index(m)
@@ -184,20 +182,21 @@ def write_golden(results):
         calls[call] = dict(singles=single, pairs=[digits[i:i + 120] for i in range(0, len(digits), 120)], others=others)
     body = ",\n".join(f" {json.dumps(c)}: {json.dumps(rec, separators=(',', ':'))}" for c, rec in calls.items())
     rows = ",\n".join(" " + json.dumps(m) for m in messages)
-    GOLDEN.write_text('{"messages": [\n' + rows + '],\n"calls": {\n' + body + "\n}}\n")
-    assert read_golden() == results
+    golden.write_text('{"messages": [\n' + rows + '],\n"calls": {\n' + body + "\n}}\n")
+    assert read_golden(golden, prefix, {c: list(rec) for c, rec in results.items()}) == results
 
 
-def read_golden():
-    """{call: {case name: (status, text)}} of the file, every case of cases() spelled out."""
-    g = json.loads(GOLDEN.read_text())
+def read_golden(golden=GOLDEN, prefix=lambda call: PREFIX + call, names=None):
+    """{call: {case name: (status, text)}} of the file, every case spelled out.  names: {call: its case names in order}
+    (the nine attention calls' by default)."""
+    g = json.loads(golden.read_text())
+    names = names or {call_name(pas, mode): [n for n, _ in cases(pas, mode)] for pas, mode in CALLS}
     out = {}
-    for pas, mode in CALLS:
-        call = call_name(pas, mode)
+    for call, all_names in names.items():
         rec = g["calls"][call]
-        msg = lambda i: (g["messages"][i][0], PREFIX + call + g["messages"][i][1][1:])       # noqa: E731
+        msg = lambda i: (g["messages"][i][0], prefix(call) + g["messages"][i][1][1:])       # noqa: E731
         res = out[call] = {n: msg(i) for n, i in rec["singles"].items()}
-        pairs = [n for n, _ in cases(pas, mode) if " " in n]
+        pairs = [n for n in all_names if " " in n]
         digits = "".join(rec["pairs"])
         assert len(digits) == len(pairs)
         for n, d in zip(pairs, digits):

@@ -19,7 +19,9 @@ k_attn_X<V, VEC, E>(...) and k_attn_X<V, VEC, E>(...) with an empty pack.  The k
 kernels_sddmm.hip are read the same way: k_spmm_rows, k_spmm_pieces, k_sddmm_rows and k_sddmm_pieces are their name, V, VEC and
 element type (float where the symbol has none, as before the 16-bit calls, whose argument struct was no template either), and
 k_spmm_combine its name and element type; SpMM's three kernels may end in a TILED flag (the instantiations of the _cols call),
-and a kernel without the flag, as before that call, is the one with TILED = false.  The run kernels of kernels_adaptive.hip --
+and a kernel without the flag, as before that call, is the one with TILED = false.  SDDMM's two kernels may end in a COLS flag
+in the same way (the kernels of its _cols call), and k_sddmm_cols_rows<VEC, E> and k_sddmm_cols_pieces<VEC, E>, the twin kernels
+of before, are k_sddmm_rows<16, VEC, E, COLS> and k_sddmm_pieces<16, VEC, E, COLS>.  The run kernels of kernels_adaptive.hip --
 k_tiled16, k_sorted, k_adaptive, k_tiled_mixed -- are their name, their integer and boolean template arguments and the element
 type of the matrix values (float where the symbol has none, as before spmv_csr_run_vals16); what follows the template
 arguments in the symbol, the argument list, spells the values' pointer through the template parameter since then and is not
@@ -29,19 +31,26 @@ import re
 import sys
 
 ELEMENTS = {None: "float", "f": "float", "NS_4bf16E": "bf16", "DF16_": "fp16"}
-TILED = {None: "", "0": "", "1": ", TILED"}     # the trailing flag of SpMM's kernels (the _cols call's column tiles; absent before it)
+# the trailing flag of SpMM's and of SDDMM's kernels (the instantiations of their _cols calls; absent before those)
+TILED = {None: "", "0": "", "1": ", TILED"}
+COLS = {None: "", "0": "", "1": ", COLS"}
 ATTN = re.compile(r"_ZN4spmv12_GLOBAL__N_1\d+(k_attn_[a-z_]+?)(?:_bias)?ILi(\d+)ELb([01])E(f|NS_4bf16E|DF16_)?(?:J(?:NS_8AttnBiasE)?E)?EEv")
 GROUPS = re.compile(r"_ZN4spmv12_GLOBAL__N_1\d+(k_(?:spmm|sddmm)_(?:rows|pieces))ILi(\d+)ELb([01])E(f|NS_4bf16E|DF16_)?(?:Lb([01])E)?EEv")
 # (the lines that lead in the next kernel, or pad the text behind a file's last one)
 NEXT = re.compile(r"\t\.text$|\t\.(?:protected|weak|hidden)\t\w+ +; -- Begin function |\t\.p2alignl 6, 3212836864$|\t\.fill 256, 4, 3212836864$")
 TILED_RUN = re.compile(r"_ZN4spmv\d+(k_tiled16|k_sorted|k_adaptive|k_tiled_mixed)I((?:L[ib]\d+E)+)(f|NS_4bf16E|DF16_)?EEv")
+SDDMM_COLS = re.compile(r"_ZN4spmv12_GLOBAL__N_1\d+k_sddmm_cols_(rows|pieces)ILb([01])E(f|NS_4bf16E|DF16_)EEv")     # (the twins of before)
 COMBINE = re.compile(r"_ZN4spmv12_GLOBAL__N_1\d+(k_spmm_combine)(?:I(f|NS_4bf16E|DF16_)(?:Lb([01])E)?E)?E")
 
 
 def key(symbol: str) -> str:
     m = GROUPS.match(symbol)
     if m:
-        return f"{m.group(1)}<{m.group(2)}, {'true' if m.group(3) == '1' else 'false'}, {ELEMENTS[m.group(4)]}{TILED[m.group(5)]}>"
+        flag = (COLS if "sddmm" in m.group(1) else TILED)[m.group(5)]
+        return f"{m.group(1)}<{m.group(2)}, {'true' if m.group(3) == '1' else 'false'}, {ELEMENTS[m.group(4)]}{flag}>"
+    m = SDDMM_COLS.match(symbol)
+    if m:
+        return f"k_sddmm_{m.group(1)}<16, {'true' if m.group(2) == '1' else 'false'}, {ELEMENTS[m.group(3)]}, COLS>"
     m = COMBINE.match(symbol)
     if m:
         return f"{m.group(1)}<{ELEMENTS[m.group(2)]}{TILED[m.group(3)]}>"

@@ -18,7 +18,6 @@ import attention_asm_diff as D  # noqa: E402
 PKG = ROOT / "spmv-test_amd"
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
          f"-I{ROOT / 'include'}", f"-I{PKG / 'csrc'}", "--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage"]
-SDDMM_COLS = re.compile(r"_ZN4spmv12_GLOBAL__N_1\d+(k_sddmm_cols_(?:rows|pieces))ILb([01])E(f|NS_4bf16E|DF16_)E")
 
 
 def remarks(source):
@@ -36,20 +35,13 @@ def remarks(source):
     return out
 
 
-def name(symbol):
-    m = SDDMM_COLS.match(symbol)
-    if m:
-        return f"{m.group(1)}<{'true' if m.group(2) == '1' else 'false'}, {D.ELEMENTS[m.group(3)]}>"
-    return D.key(symbol)
-
-
 def main():
     bad = 0
     print("| kernel | | VGPRs | AGPRs | SGPRs | waves / SIMD | scratch bytes / lane | VGPR spills |\n|---|---|---|---|---|---|---|---|")
     for source in ("kernels_spmm.hip", "kernels_sddmm.hip"):
         for symbol, r in remarks(PKG / "csrc" / source).items():
-            n = name(symbol)
-            new = "TILED" in n or "_cols_" in n
+            n = D.key(symbol)
+            new = n.endswith((", TILED>", ", COLS>"))      # (the instantiations of the _cols calls)
             if not (new or re.match(r"k_(spmm|sddmm)_(rows|pieces)<16,", n) or n.startswith("k_spmm_combine")):
                 continue
             bad += new and (r["ScratchSize [bytes/lane]"] != "0" or r["VGPRs Spill"] != "0" or r["SGPRs Spill"] != "0")
