@@ -222,6 +222,82 @@ SPMV_API int spmv_csr_transpose_gather(const spmv_csr_t *t, int count, const voi
                                        int64_t dst_stride, void *stream);
 SPMV_API int64_t spmv_csr_transpose_map_bytes(const spmv_csr_t *t);
 
+/* ---- selection -------------------------------------------------------------
+ * A new pattern from an old one: per row the k best-scored nonzeros (spmv_csr_select_topk) or the nonzeros whose score is
+ * at or above a threshold (spmv_csr_select_threshold), as a new handle on a's device.  It is the middle step of a dynamic
+ * sparse attention (score a candidate pattern with spmv_csr_sddmm, keep the k best keys per query, attend on what is
+ * left) and of magnitude pruning (keep the k largest |vals| per row).  Selection is pure structure -- integer keys, no
+ * floating-point sum -- so the contract below holds bit for bit (tests/_select.py states it in numpy).
+ *
+ *   Scores.  d_score holds a.nnz floats in a's storage order; NULL means a's own vals, read live.
+ *   Key.  The nonzero at storage position p gets a 32-bit unsigned key from s = score[p] (with SPMV_SELECT_ABS in flags:
+ * from |s|, the sign bit cleared).  A NaN of either sign and any payload gets key 0.  Otherwise u = bits(s + 0.0f), so that
+ * -0 and +0 are one key, and the key is ~u if the sign bit of u is set, else u | 0x80000000: the usual order-preserving map.
+ * Every number, -Inf included, ranks above every NaN.
+ *   Order.  Nonzero p ranks before nonzero q of the same row iff key(p) > key(q), or the keys are equal and p < q.
+ *   spmv_csr_select_topk keeps, in every row, the first min(k, len) nonzeros of that ranking.
+ *   spmv_csr_select_threshold keeps nonzero p iff s >= threshold (|s| >= threshold with SPMV_SELECT_ABS) as an IEEE
+ * comparison: a NaN score is never kept, -0 >= +0 holds.
+ *   The output handle.  *out has a's rows and cols, owns its three arrays (spmv_csr_destroy frees them), is accepted by
+ * every spmv_csr_* call and has no plans yet.  A row lists its kept nonzeros in ASCENDING STORAGE POSITION of a: sorted rows
+ * stay sorted, unsorted rows and repeated columns keep their relative order.  With map[m] the position in a of out's
+ * nonzero m:
+ *     out.col_idx[m] = a.col_idx[map[m]]
+ *     out.vals[m]    = a.vals[map[m]]        (the bits are copied: NaN payloads, -0.0, subnormals)
+ *     map            kept with keep_map = 1: 4 bytes per kept nonzero
+ *   Purity.  The result is a pure function of a's arrays, the scores and k or the threshold: two calls, two handles of one
+ * matrix, any stream and any neighbouring rows give the same bytes.  No place is taken from the value an atomic returns
+ * (the only atomics are integer LDS counters whose result is not used: a count does not depend on the order of arrival).
+ *   Copy case.  k >= the longest row, or threshold = -Inf on NaN-free scores, reproduces a's arrays bit for bit.
+ *   Like spmv_csr_transpose each call allocates, enqueues on `stream` and waits for it before it returns (out.nnz is a
+ * result).  `a` is only read and keeps its plans; it may own or borrow its arrays, be a whole matrix or a row block.
+ *   SPMV_ERR_INVALID (the message names the function, *out untouched, nothing launched): a null `a` or `out`; k < 1; a NaN
+ * threshold; a flag bit other than SPMV_SELECT_ABS; keep_map other than 0 / 1; a d_score that is not 4-byte aligned;
+ * another current device than a's.  SPMV_ERR_HIP when an allocation fails (what was allocated is released, `a` stays
+ * usable); SPMV_ERR_NO_DEVICE as everywhere.  Every handle is admitted (rows, cols, nnz < 2^31): positions are unsigned
+ * 32-bit numbers, byte offsets 64-bit; nnz = 0, rows = 0 and a result without nonzeros work.
+ *   Device memory: out itself takes 4 (rows + 1) + 8 kept bytes (+ 4 kept for the map), kept = out.nnz.  While the call
+ * runs it holds at most 8 rows + 4 ceil(rows / 4096) + 64 bytes more (top-k: a cut of 8 bytes per row; the tile sums of the
+ * scan of the row counts), freed on return: 12 rows + 12 kept bytes at the peak.  Nothing of a.nnz elements is allocated.
+ *   The route (spmv-test_amd/csrc/kernels_select.hip): per row a cut (the k-th key tau and how many nonzeros with key ==
+ * tau are admitted, by storage position) -- rows of at most 512 nonzeros in registers by bisection over the key bits, longer
+ * rows by an 8-bit radix select of four passes --, a scan of the row counts, and a compaction that re-reads the scores.
+ *
+ * spmv_csr_select_values: s.vals[m] = a.vals[map[m]] for a handle made with keep_map = 1, then what
+ * spmv_csr_values_changed(s) does (see spmv_csr_transpose_values).  `a` must have s's shape, the nnz of s's parent (the
+ * handle records it) and live on s's device; that it still has the parent's PATTERN is the caller's promise.
+ *
+ * spmv_csr_select_gather:  dst[c * dst_stride + m] = src[c * src_stride + map[m]]
+ * spmv_csr_select_scatter: dst[c * dst_stride + map[m]] = src[c * src_stride + m]; every other word of dst is left
+ * untouched (zero-fill first for a dense gradient; map entries are distinct, so nothing races)
+ * for c < count, m < s.nnz, on 32-bit words copied as bits; strides count words; src and dst need 4-byte alignment only and
+ * must not overlap.  The arrays in the parent's order hold the parent's nnz words, those in s's order s.nnz.
+ * SPMV_ERR_INVALID, nothing launched: a handle without a select map; count < 1; a null array while s.nnz > 0; an array that
+ * is not 4-byte aligned; a negative stride; dst_stride below the words of one array of dst with count > 1.
+ *
+ * _values, _gather, _scatter and spmv_csr_copy_arrays are asynchronous, allocate nothing, never wait: graph-capturable.
+ *
+ * One map per handle: a handle made by spmv_csr_transpose is refused by the _select_* companions, a handle made by a select
+ * call by the _transpose_* companions, and spmv_csr_transpose_map_bytes is 0 for a selected handle.
+ * spmv_csr_select_map_bytes: device bytes of the kept map (4 * nnz; 0 without one; < 0: null handle).
+ *
+ * spmv_csr_copy_arrays: device-to-device copies of a handle's arrays (rows + 1, nnz, nnz elements) into the caller's
+ * buffers on the handle's device, enqueued on `stream`; any pointer may be NULL.  This is how an owned pattern reaches
+ * arrays that another handle borrows (spmv_csr_download goes to the host only).  SPMV_ERR_INVALID: a null handle, another
+ * current device than the handle's. */
+enum { SPMV_SELECT_ABS = 1 };   /* rank by |score| (sign bit cleared) */
+SPMV_API int spmv_csr_select_topk(const spmv_csr_t *a, const float *d_score, int k, int flags, int keep_map, void *stream,
+                                  spmv_csr_t **out);
+SPMV_API int spmv_csr_select_threshold(const spmv_csr_t *a, const float *d_score, float threshold, int flags, int keep_map,
+                                       void *stream, spmv_csr_t **out);
+SPMV_API int spmv_csr_select_values(spmv_csr_t *s, const spmv_csr_t *a, void *stream);
+SPMV_API int spmv_csr_select_gather(const spmv_csr_t *s, int count, const void *d_src, int64_t src_stride, void *d_dst,
+                                    int64_t dst_stride, void *stream);
+SPMV_API int spmv_csr_select_scatter(const spmv_csr_t *s, int count, const void *d_src, int64_t src_stride, void *d_dst,
+                                     int64_t dst_stride, void *stream);
+SPMV_API int64_t spmv_csr_select_map_bytes(const spmv_csr_t *s);
+SPMV_API int spmv_csr_copy_arrays(const spmv_csr_t *h, int32_t *d_row_ptr, int32_t *d_col_idx, float *d_vals, void *stream);
+
 /* ---- the hot path ------------------------------------------------------
  * spmv_csr_plan: one-off device-side preprocessing a variant needs (chunk
  * boundaries, column windows, for SPMV_TILED also a 16-bit copy of the column
@@ -275,6 +351,7 @@ SPMV_API int64_t spmv_csr_transpose_map_bytes(const spmv_csr_t *t);
  *   _backward_q_heads, _backward_kv_heads     call is one launch) and heads <= 65535; where the long rows have more pieces
  *                                             than the handle has rows, the pieces stand in the place of the rows
  *   spmv_csr_transpose                        any handle
+ *   spmv_csr_select_topk, _select_threshold   any handle (rows, nnz < 2^31; a wavefront per 64 rows, byte offsets 64-bit)
  * (tests/test_gpu_limits.py runs every path on either side of these; the _heads calls' limits are refused and queried on
  * either side in tests/test_gpu_attention_heads.py, where a launch at the limit itself would write 64 GiB.) */
 SPMV_API int spmv_csr_plan(spmv_csr_t *h, int variant, void *stream);

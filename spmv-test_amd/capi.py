@@ -58,6 +58,13 @@ SIGNATURES = {
     "spmv_csr_transpose_values": (C.c_int, [_H, _H, _vp]),
     "spmv_csr_transpose_gather": (C.c_int, [_H, C.c_int, _vp, C.c_int64, _vp, C.c_int64, _vp]),
     "spmv_csr_transpose_map_bytes": (C.c_int64, [_H]),
+    "spmv_csr_select_topk": (C.c_int, [_H, _f32p, C.c_int, C.c_int, C.c_int, _vp, _HP]),
+    "spmv_csr_select_threshold": (C.c_int, [_H, _f32p, C.c_float, C.c_int, C.c_int, _vp, _HP]),
+    "spmv_csr_select_values": (C.c_int, [_H, _H, _vp]),
+    "spmv_csr_select_gather": (C.c_int, [_H, C.c_int, _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "spmv_csr_select_scatter": (C.c_int, [_H, C.c_int, _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "spmv_csr_select_map_bytes": (C.c_int64, [_H]),
+    "spmv_csr_copy_arrays": (C.c_int, [_H, _i32p, _i32p, _f32p, _vp]),
     "spmv_csr_plan": (C.c_int, [_H, C.c_int, _vp]),
     "spmv_csr_run": (C.c_int, [_H, C.c_int, _f32p, _f32p, _vp]),
     "spmv_csr_run_vals16": (C.c_int, [_H, C.c_int, C.c_int, _vp, _f32p, _f32p, _vp]),
@@ -337,6 +344,104 @@ class CsrMatrix:
         if n < 0:
             check(n)
         return n
+
+    # -- selection (spmv_csr_select_*) ------------------------------------------------------------------------------
+    SELECT_ABS = 1      # SPMV_SELECT_ABS
+
+    def _select_score(self, who: str, score):
+        import torch
+        if score is None:
+            return None
+        if not isinstance(score, torch.Tensor) or score.dtype != torch.float32 or score.dim() != 1 \
+                or not score.is_contiguous() or score.numel() != self.nnz or not score.is_cuda:
+            raise ValueError(f"{who}: score must be a contiguous 1-D float32 device tensor of nnz = {self.nnz} elements")
+        return score
+
+    def _selected(self, h) -> "CsrMatrix":
+        s = CsrMatrix(h.value)
+        s.select_parent_nnz = self.nnz
+        return s
+
+    def select_topk(self, k: int, score=None, abs: bool = False, keep_map: bool = False, stream=None) -> "CsrMatrix":
+        """Per row the ``min(k, len)`` nonzeros of the largest ``score`` (``None``: this matrix's own values; ``abs``: by
+        ``|score|``), ties to the earlier storage position, as a new handle that owns its arrays (waits for the stream).
+        Rows keep their storage order.  ``keep_map=True`` keeps the map :meth:`select_values`, :meth:`select_gather` and
+        :meth:`select_scatter` need."""
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f"select_topk: k = {k!r} (an int >= 1)")
+        score = self._select_score("select_topk", score)
+        h = C.c_void_p()
+        check(lib().spmv_csr_select_topk(self._h, _ptr(score), min(k, 2 ** 31 - 1), self.SELECT_ABS if abs else 0,
+                                         1 if keep_map else 0, _stream_handle(stream), C.byref(h)))
+        return self._selected(h)
+
+    def select_threshold(self, threshold: float, score=None, abs: bool = False, keep_map: bool = False, stream=None) -> "CsrMatrix":
+        """The nonzeros with ``score >= threshold`` (``abs``: ``|score| >= threshold``; a NaN score is never kept) as a new
+        handle that owns its arrays (waits for the stream).  The arguments are those of :meth:`select_topk`."""
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError("select_threshold: the threshold is a NaN")
+        score = self._select_score("select_threshold", score)
+        h = C.c_void_p()
+        check(lib().spmv_csr_select_threshold(self._h, _ptr(score), threshold, self.SELECT_ABS if abs else 0,
+                                              1 if keep_map else 0, _stream_handle(stream), C.byref(h)))
+        return self._selected(h)
+
+    def select_values(self, a: "CsrMatrix", stream=None) -> None:
+        """Refresh this handle's values (made by ``a.select_*(keep_map=True)``) from ``a``'s values as they are now: one
+        gather launch, asynchronous, graph-capturable; then what :meth:`values_changed` does."""
+        check(lib().spmv_csr_select_values(self._h, a._h, _stream_handle(stream)))
+
+    def _select_move(self, who: str, fn, src, dst, n_src: int, n_dst: int, stream) -> None:
+        import torch
+        for name, t, n in (("src", src, n_src), ("dst", dst, n_dst)):
+            if not isinstance(t, torch.Tensor) or t.dim() not in (1, 2) or t.element_size() != 4 or t.stride(-1) != 1 \
+                    or t.shape[-1] != n or not t.is_cuda:
+                raise ValueError(f"{who}: {name} must be a device tensor ({n},) or (count, {n}) of 4-byte elements with stride(-1) == 1")
+        if src.dtype != dst.dtype or src.dim() != dst.dim() or src.shape[:-1] != dst.shape[:-1] or src.device != dst.device:
+            raise ValueError(f"{who}: src is {src.dtype} {tuple(src.shape)} on {src.device}, dst {dst.dtype} {tuple(dst.shape)} on {dst.device}")
+        count = src.shape[0] if src.dim() == 2 else 1
+        if count < 1:
+            raise ValueError(f"{who}: count = 0")
+        stride = lambda t: t.stride(0) if count > 1 else 0
+        check(fn(self._h, count, _ptr(src), stride(src), _ptr(dst), stride(dst), _stream_handle(stream)))
+
+    def _parent_nnz(self, who: str) -> int:
+        n = getattr(self, "select_parent_nnz", None)
+        if n is None:
+            raise ValueError(f"{who}: this handle was not made by select_topk / select_threshold")
+        return n
+
+    def select_gather(self, src, dst, stream=None) -> None:
+        """On a handle made by ``a.select_*(keep_map=True)``: ``dst[..., m] = src[..., map[m]]`` -- arrays of 32-bit elements in
+        ``a``'s storage order (``a.nnz`` each) brought into this handle's (``nnz`` each).  src, dst: 1-D or (count, n) of one
+        4-byte dtype with stride(-1) == 1; copied as bits, in one launch."""
+        self._select_move("select_gather", lib().spmv_csr_select_gather, src, dst, self._parent_nnz("select_gather"), self.nnz, stream)
+
+    def select_scatter(self, src, dst, stream=None) -> None:
+        """The other way: ``dst[..., map[m]] = src[..., m]``; every other element of dst is left as it is (zero-fill dst first
+        for a dense gradient in the parent's order)."""
+        self._select_move("select_scatter", lib().spmv_csr_select_scatter, src, dst, self.nnz, self._parent_nnz("select_scatter"), stream)
+
+    def select_map_bytes(self) -> int:
+        n = lib().spmv_csr_select_map_bytes(self._h)
+        if n < 0:
+            check(n)
+        return n
+
+    def copy_arrays(self, row_ptr, col_idx, vals=None, stream=None) -> None:
+        """Device-to-device copies of this handle's arrays into the caller's contiguous device tensors (int32 of rows + 1,
+        int32 of nnz, float32 of nnz; any may be ``None``), enqueued on the stream: how an owned pattern reaches tensors that
+        another handle or a layer borrows."""
+        import torch
+        for name, t, dt, n in (("row_ptr", row_ptr, torch.int32, self.rows + 1), ("col_idx", col_idx, torch.int32, self.nnz),
+                               ("vals", vals, torch.float32, self.nnz)):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.numel() != n \
+                    or not t.is_cuda:
+                raise ValueError(f"copy_arrays: {name} must be a contiguous 1-D {dt} device tensor of {n} elements")
+        check(lib().spmv_csr_copy_arrays(self._h, _ptr(row_ptr), _ptr(col_idx), _ptr(vals), _stream_handle(stream)))
 
     # -- SpMM: k right-hand sides at once (spmv_csr_spmm) ---------------------------------------------------------
     def spmm_plan(self, stream=None) -> None:

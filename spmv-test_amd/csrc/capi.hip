@@ -447,6 +447,125 @@ int64_t spmv_csr_transpose_map_bytes(const spmv_csr_t *t)
     return t->transpose_map ? 4 * t->nnz : 0;
 }
 
+// ---- selection (kernels_select.hip) ------------------------------------------------------------------------------------
+// what spmv_csr_select_topk and _threshold refuse alike; nothing is launched before it has passed
+static int select_check(const char *what, const spmv_csr_t *a, const float *d_score, int flags, int keep_map, spmv_csr_t **out)
+{
+    if (!a || !out) { set_error("%s: null argument", what); return SPMV_ERR_INVALID; }
+    if (flags & ~SPMV_SELECT_ABS) { set_error("%s: flags = 0x%x (SPMV_SELECT_ABS or 0)", what, (unsigned)flags); return SPMV_ERR_INVALID; }
+    if (keep_map != 0 && keep_map != 1) { set_error("%s: keep_map = %d (0 or 1)", what, keep_map); return SPMV_ERR_INVALID; }
+    if (reinterpret_cast<uintptr_t>(d_score) % 4 != 0) { set_error("%s: d_score must be 4-byte aligned", what); return SPMV_ERR_INVALID; }
+    if (int rc = require_device()) return rc;
+    return require_current(a->device, what);
+}
+
+int spmv_csr_select_topk(const spmv_csr_t *a, const float *d_score, int k, int flags, int keep_map, void *stream, spmv_csr_t **out)
+{
+    const char *what = "spmv_csr_select_topk";
+    if (a && out && k < 1) { set_error("%s: k = %d (need k >= 1)", what, k); return SPMV_ERR_INVALID; }
+    if (int rc = select_check(what, a, d_score, flags, keep_map, out)) return rc;
+    return select(*a, d_score, false, k, 0u, (flags & SPMV_SELECT_ABS) != 0, keep_map == 1, (hipStream_t)stream, out);
+}
+
+int spmv_csr_select_threshold(const spmv_csr_t *a, const float *d_score, float threshold, int flags, int keep_map, void *stream,
+                              spmv_csr_t **out)
+{
+    const char *what = "spmv_csr_select_threshold";
+    if (a && out && threshold != threshold) { set_error("%s: the threshold is a NaN", what); return SPMV_ERR_INVALID; }
+    if (int rc = select_check(what, a, d_score, flags, keep_map, out)) return rc;
+    // (|s| >= t and s >= t are comparisons of keys: the key of the threshold itself is never taken from |t|)
+    return select(*a, d_score, true, 0, select_key(threshold, false), (flags & SPMV_SELECT_ABS) != 0, keep_map == 1,
+                  (hipStream_t)stream, out);
+}
+
+int spmv_csr_select_values(spmv_csr_t *s, const spmv_csr_t *a, void *stream)
+{
+    const char *what = "spmv_csr_select_values";
+    if (!s || !a) { set_error("%s: null argument", what); return SPMV_ERR_INVALID; }
+    if (!s->select_map) {
+        set_error("%s: the handle has no map (it was not made by a spmv_csr_select call with keep_map = 1)", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (a->rows != s->rows || a->cols != s->cols || a->nnz != s->select_parent_nnz) {
+        set_error("%s: a is %lld x %lld with %lld nonzeros, s was selected from %lld x %lld with %lld", what, (long long)a->rows,
+                  (long long)a->cols, (long long)a->nnz, (long long)s->rows, (long long)s->cols, (long long)s->select_parent_nnz);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(s->device, what)) return rc;
+    if (a->device != s->device) {
+        set_error("%s: a lives on device %d, s on device %d", what, a->device, s->device);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = select_move(*s, false, 1, a->d_vals, 0, s->own_vals.get(), 0, (hipStream_t)stream)) return rc;
+    ++s->values_gen;
+    return SPMV_OK;
+}
+
+static int select_move_checked(const char *what, bool scatter, const spmv_csr_t *s, int count, const void *d_src, int64_t src_stride,
+                               void *d_dst, int64_t dst_stride, void *stream)
+{
+    if (!s) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (!s->select_map) {
+        set_error("%s: the handle has no map (it was not made by a spmv_csr_select call with keep_map = 1)", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (count < 1) { set_error("%s: count = %d (need count >= 1)", what, count); return SPMV_ERR_INVALID; }
+    if ((!d_src || !d_dst) && s->nnz > 0) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
+    if (reinterpret_cast<uintptr_t>(d_src) % 4 != 0 || reinterpret_cast<uintptr_t>(d_dst) % 4 != 0) {
+        set_error("%s: src and dst must be 4-byte aligned", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (src_stride < 0 || dst_stride < 0) {
+        set_error("%s: src_stride = %lld, dst_stride = %lld (a stride is not negative)", what, (long long)src_stride, (long long)dst_stride);
+        return SPMV_ERR_INVALID;
+    }
+    if (src_stride > INT64_MAX / 4 / count || dst_stride > INT64_MAX / 4 / count) {
+        set_error("%s: a stride overflows 64-bit byte offsets", what);
+        return SPMV_ERR_INVALID;
+    }
+    const int64_t dst_len = scatter ? s->select_parent_nnz : s->nnz;      // words of one array of dst
+    if (count > 1 && dst_stride < dst_len) {
+        set_error("%s: dst_stride = %lld is below the %lld words of an array with count = %d", what, (long long)dst_stride,
+                  (long long)dst_len, count);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(s->device, what)) return rc;
+    return select_move(*s, scatter, count, d_src, src_stride, d_dst, dst_stride, (hipStream_t)stream);
+}
+
+int spmv_csr_select_gather(const spmv_csr_t *s, int count, const void *d_src, int64_t src_stride, void *d_dst, int64_t dst_stride,
+                           void *stream)
+{
+    return select_move_checked("spmv_csr_select_gather", false, s, count, d_src, src_stride, d_dst, dst_stride, stream);
+}
+
+int spmv_csr_select_scatter(const spmv_csr_t *s, int count, const void *d_src, int64_t src_stride, void *d_dst, int64_t dst_stride,
+                            void *stream)
+{
+    return select_move_checked("spmv_csr_select_scatter", true, s, count, d_src, src_stride, d_dst, dst_stride, stream);
+}
+
+int64_t spmv_csr_select_map_bytes(const spmv_csr_t *s)
+{
+    if (!s) { set_error("spmv_csr_select_map_bytes: null handle"); return SPMV_ERR_INVALID; }
+    return s->select_map ? 4 * s->nnz : 0;
+}
+
+int spmv_csr_copy_arrays(const spmv_csr_t *h, int32_t *d_row_ptr, int32_t *d_col_idx, float *d_vals, void *stream)
+{
+    const char *what = "spmv_csr_copy_arrays";
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (int rc = require_current(h->device, what)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (d_row_ptr)
+        SPMV_HIP_TRY(hipMemcpyAsync(d_row_ptr, h->d_row_ptr, sizeof(int32_t) * ((size_t)h->rows + 1), hipMemcpyDeviceToDevice, st));
+    if (d_col_idx && h->nnz)
+        SPMV_HIP_TRY(hipMemcpyAsync(d_col_idx, h->d_col_idx, sizeof(int32_t) * (size_t)h->nnz, hipMemcpyDeviceToDevice, st));
+    if (d_vals && h->nnz)
+        SPMV_HIP_TRY(hipMemcpyAsync(d_vals, h->d_vals, sizeof(float) * (size_t)h->nnz, hipMemcpyDeviceToDevice, st));
+    return SPMV_OK;
+}
+
 // SPMV_AUTO.  TILED's plan is made first (cheap: a few passes over col_idx, no trial launches) and priced (model_cost,
 // in units of "a chunk that streams 8 bytes per nonzero with cache-resident gathers").
 //   1. It stages (nearly) everything in one or two passes (model_cost <= 1.20: bands up to ~60 000 columns at config 4): TILED.

@@ -284,6 +284,9 @@ struct spmv_csr {
     spmv::DevPtr<int32_t> own_row_ptr, own_col_idx;   // the handle's own copies behind the views (empty: the caller's arrays)
     spmv::DevPtr<float> own_vals;
     spmv::DevPtr<uint32_t> transpose_map;   // [nnz] spmv_csr_transpose(keep_map = 1): vals[i] = the parent's vals[map[i]] (empty: no map)
+    // a handle has at most one of the two maps: which member is set says which call made it
+    spmv::DevPtr<uint32_t> select_map;      // [nnz] spmv_csr_select_*(keep_map = 1): the same, positions ascending inside a row (empty: no map)
+    int64_t select_parent_nnz = -1;         // the parent's nnz when a select call made this handle (every map entry is below it); -1: another maker
     int device = 0;
 
     // plan state
@@ -409,6 +412,14 @@ int transpose(const spmv_csr &a, bool keep_map, hipStream_t s, spmv_csr_t **out)
 int transpose_values(spmv_csr &t, const spmv_csr &a, hipStream_t s);
 // dst[c * dst_stride + i] = src[c * src_stride + map[i]] for c < count through t's map (spmv_csr_transpose_gather)
 int transpose_gather(const spmv_csr &t, int count, const void *src, int64_t src_stride, void *dst, int64_t dst_stride, hipStream_t s);
+// kernels_select.hip: spmv_csr_select_topk (thresh = false: k) / spmv_csr_select_threshold (thresh = true: thr_key = select_key of
+// the threshold); score null: a's vals
+int select(const spmv_csr &a, const float *score, bool thresh, int k, uint32_t thr_key, bool abs, bool keep_map, hipStream_t s,
+           spmv_csr_t **out);
+uint32_t select_key(float score, bool abs);
+// through sh's select map, for c < count, m < sh.nnz: dst[c][m] = src[c][map[m]], or (scatter) dst[c][map[m]] = src[c][m]
+int select_move(const spmv_csr &sh, bool scatter, int count, const void *src, int64_t src_stride, void *dst, int64_t dst_stride,
+                hipStream_t s);
 
 int dense_to_csr(int M, int N, const float *d_A, hipStream_t s, spmv_csr_t **out);
 int dense_gemv(int M, int N, const float *d_A, const float *d_x, float *d_y, int mode, hipStream_t s);

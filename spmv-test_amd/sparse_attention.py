@@ -122,6 +122,37 @@ class SparseAttention:
         self.A.close()
 
 
+def topk_pattern(A, Q, K, k: int, scale: float = 1.0):
+    """The k best keys of every query among the candidates of ``A`` (a capi.CsrMatrix of queries x keys): the scores
+    ``scale * Q K^T`` at A's pattern (spmv_csr_sddmm: one head, float32, Q rows x w and K cols x w with w <= MAX_K), then
+    ``A.select_topk(k, score)`` -- ties go to the earlier candidate, a NaN score ranks last, rows keep A's storage order.
+    Returns ``(row_ptr, col_idx)`` as int32 device tensors, ready for ``FusedSparseAttention(rows, cols, row_ptr, col_idx,
+    ...)``.  The selection is a discrete choice: no gradient flows through it (Q and K are read detached); the attention
+    on the returned pattern differentiates with respect to Q, K and V as usual.  A's values are not read."""
+    if not isinstance(A, capi.CsrMatrix):
+        raise ValueError("topk_pattern: A must be a capi.CsrMatrix (the candidate pattern)")
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"topk_pattern: k = {k!r} (an int >= 1)")
+    if not math.isfinite(scale):
+        raise ValueError(f"topk_pattern: scale = {scale} is not finite")
+    if not isinstance(Q, torch.Tensor) or not isinstance(K, torch.Tensor):
+        raise ValueError("topk_pattern: Q and K must be 2-D float32 tensors")
+    Q = _operand(Q.detach(), "Q", A.rows)
+    K = _operand(K.detach(), "K", A.cols, Q.shape[1])
+    A.spmm_plan()
+    score = torch.empty(A.nnz, dtype=torch.float32, device=Q.device)
+    A.sddmm(Q, K, score)
+    if scale != 1.0:
+        score.mul_(float(scale))
+    sel = A.select_topk(k, score)
+    row_ptr = torch.empty(sel.rows + 1, dtype=torch.int32, device=Q.device)
+    col_idx = torch.empty(sel.nnz, dtype=torch.int32, device=Q.device)
+    sel.copy_arrays(row_ptr, col_idx)
+    torch.cuda.current_stream().synchronize()      # the copies read sel's arrays, which close() frees
+    sel.close()
+    return row_ptr, col_idx
+
+
 def _fused_operand(t, name: str, rows: int, k=None):
     """A 2-D operand as _operand takes it, or (heads, rows, k): every head t[h] must itself be acceptable to the library
     (a column block of a (rows, heads * k) tensor with k % 4 == 0 is); otherwise the whole tensor is copied once into

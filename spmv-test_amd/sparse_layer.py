@@ -98,6 +98,29 @@ class SparseLayer:
     def __call__(self, X):
         return SparseMatmul.apply(self, self.vals, X)
 
+    def pruned(self, k: int) -> "SparseLayer":
+        """A new SparseLayer on the per-row top-k of ``|vals|`` (spmv_csr_select_topk with SPMV_SELECT_ABS: magnitude pruning,
+        ties to the earlier nonzero, rows in their storage order).  Its ``row_ptr`` and ``col_idx`` are fresh device tensors
+        and its ``vals`` a fresh leaf (requires_grad as the parent's) filled by select_gather; ``.selection`` is the select
+        handle with its map, so a caller can bring optimizer state along the same way
+        (``new.selection.select_gather(state, new_state)``) or scatter a gradient back.  The parent layer is untouched."""
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f"SparseLayer.pruned: k = {k!r} (an int >= 1)")
+        sel = self.A.select_topk(k, abs=True, keep_map=True)
+        dev = self.vals.device
+        row_ptr = torch.empty(sel.rows + 1, dtype=torch.int32, device=dev)
+        col_idx = torch.empty(sel.nnz, dtype=torch.int32, device=dev)
+        vals = torch.empty(sel.nnz, dtype=torch.float32, device=dev)
+        sel.copy_arrays(row_ptr, col_idx)
+        sel.select_gather(self.vals.detach(), vals)
+        vals.requires_grad_(self.vals.requires_grad)
+        layer = SparseLayer(sel.rows, sel.cols, row_ptr, col_idx, vals, k_max=self.k_max)
+        layer.selection = sel
+        return layer
+
     def close(self) -> None:
+        sel = getattr(self, "selection", None)
+        if sel is not None:
+            sel.close()
         self.T.close()
         self.A.close()
