@@ -298,6 +298,60 @@ SPMV_API int spmv_csr_select_scatter(const spmv_csr_t *s, int count, const void 
 SPMV_API int64_t spmv_csr_select_map_bytes(const spmv_csr_t *s);
 SPMV_API int spmv_csr_copy_arrays(const spmv_csr_t *h, int32_t *d_row_ptr, int32_t *d_col_idx, float *d_vals, void *stream);
 
+/* ---- the sparse product ------------------------------------------------------
+ * A pattern from two patterns: C = A B for two CSR handles (SpGEMM), as a new handle on their device.  It is how A A^T
+ * becomes a candidate pattern for a top-k selection, how two hops of a graph or R A P are formed, and how two sparse layers
+ * without an activation between them fold into one.  The contract below holds bit for bit (tests/_spgemm.py states it in
+ * numpy).
+ *
+ *   Shapes.  a is m x n, b is n x p, both on one device; *out is m x p, owns its three arrays (spmv_csr_destroy frees
+ * them), is accepted by every spmv_csr_* call and has no plans of a variant yet.  a and b are only read and keep their
+ * plans; either may own or borrow its arrays and be a whole matrix or a row block; a == b is allowed.
+ *   Pattern.  Row i of C lists every column j that occurs in a row b[col] for some col among the entries of a's row i, each
+ * once, in ascending order: the rows of C are sorted and duplicate-free whatever the rows of a and b are.  The pattern is
+ * structural: an entry stays when its value is 0, -0 or a NaN and when its terms cancel; stored zeros of a and b count as
+ * nonzeros.
+ *   Values.  Every term counts, and a repeated column adds each of its terms.  For the entry (i, j): walk a's row i in
+ * ascending storage position s, inside each s walk b's row a.col_idx[s] in ascending storage position q, and for every q
+ * with b.col_idx[q] == j do acc = fma(a.vals[s], b.vals[q], acc), starting from +0 -- the chain of spmv_csr_spmm restricted
+ * to the terms that exist.  IEEE rules, subnormals kept; a NaN result is a NaN of the hardware's sign and payload.  The
+ * order holds for every row, however long it is and however the kernels divide the work.
+ *   Purity.  C is a pure function of the six input arrays: two calls, two handles, any stream and any neighbouring rows
+ * give the same bytes, and the rows of spgemm(row block of a, b) are the corresponding rows of spgemm(a, b).  No place and
+ * no sum depends on the order in which anything arrives: a row's columns come out of a sort, the only atomic is an integer
+ * LDS add whose result is not used, and there is no float atomic.
+ *   *products (may be NULL) = the sum over all entries s of a of the length of b's row a.col_idx[s]: the number of terms,
+ * a 64-bit number.  It is set once the bounds are known, also when the call is refused afterwards for its result's size.
+ *   Like spmv_csr_transpose the call allocates, enqueues on `stream` and waits for it before it returns (out.nnz is a
+ * result); it also reads one 64-bit bound per row of a back to the host, where the rows are sorted into classes.
+ *   SPMV_ERR_INVALID (the message names the function, *out untouched, nothing left allocated): a null a, b or out;
+ * a.cols != b.rows; a and b on different devices, or another current device than theirs; keep_plan other than 0 / 1; a
+ * result of 2^31 or more nonzeros (refused after the count; the message carries the count); a single row of a with more
+ * than 2^30 terms.  SPMV_ERR_HIP when an allocation fails (what was allocated is released, a and b stay usable);
+ * SPMV_ERR_NO_DEVICE as everywhere.  m = 0, n = 0, p = 0, nnz = 0 on either side and a result without nonzeros work.
+ *   Classes.  A row of a with t terms is taken by the smallest class of SPMV_SPGEMM_CLASS_SLOTS that holds t words (a
+ * wavefront sorts the t columns in that much LDS); a row beyond the last class is OVERSIZED: a workgroup sorts its columns
+ * in a scratch of global memory (slow: DESIGN.md section 26).  The result does not depend on the class.
+ *   Device memory.  C itself takes 4 (m + 1) + 8 nnz(C) bytes.  With L = the rows of a that have at least one term,
+ * V = the oversized rows among them and S = the sum over the oversized rows of (their terms rounded up to a power of two),
+ * the call holds at most max(8 m, 8 nnz(C)) + 4 L + 8 (V + 1) + 4 S + 4 ceil(m / 4096) + 80 bytes beside 4 (m + 1) of C at the
+ * peak (the bounds, freed before col_idx and vals are allocated; the row lists; the scratch offsets and the scratch; the
+ * totals and the tile sums of the scan).  Kept with keep_plan = 1: the row lists, 4 L bytes -- what
+ * spmv_csr_spgemm_plan_bytes returns (0 without a plan; < 0: null handle).
+ *
+ * spmv_csr_spgemm_values: for a c made with keep_plan = 1, c.vals recomputed from the values a and b hold now, under the
+ * same contract (the numeric pass of the first call: at most four launches).  Asynchronous, allocates nothing, never waits:
+ * graph-capturable.  Afterwards it does for c what spmv_csr_values_changed(c) does (see spmv_csr_transpose_values).  a must
+ * be c.rows x n and b n x c.cols with the nnz of c's parents (the handle records n and both) on c's device, else
+ * SPMV_ERR_INVALID; that their PATTERNS are unchanged is the caller's promise.  On a handle without a plan (keep_plan = 0,
+ * or not made by spmv_csr_spgemm): SPMV_ERR_INVALID, nothing launched.  A product handle carries no transpose or select
+ * map: those companions refuse it. */
+#define SPMV_SPGEMM_CLASS_SLOTS 64, 512, 4096, 32768   /* words of LDS per row of each class, ascending */
+SPMV_API int spmv_csr_spgemm(const spmv_csr_t *a, const spmv_csr_t *b, int keep_plan, void *stream, spmv_csr_t **out,
+                             int64_t *products /* may be NULL */);
+SPMV_API int spmv_csr_spgemm_values(spmv_csr_t *c, const spmv_csr_t *a, const spmv_csr_t *b, void *stream);
+SPMV_API int64_t spmv_csr_spgemm_plan_bytes(const spmv_csr_t *c);
+
 /* ---- the hot path ------------------------------------------------------
  * spmv_csr_plan: one-off device-side preprocessing a variant needs (chunk
  * boundaries, column windows, for SPMV_TILED also a 16-bit copy of the column
@@ -352,6 +406,8 @@ SPMV_API int spmv_csr_copy_arrays(const spmv_csr_t *h, int32_t *d_row_ptr, int32
  *                                             than the handle has rows, the pieces stand in the place of the rows
  *   spmv_csr_transpose                        any handle
  *   spmv_csr_select_topk, _select_threshold   any handle (rows, nnz < 2^31; a wavefront per 64 rows, byte offsets 64-bit)
+ *   spmv_csr_spgemm                           any two handles whose product has fewer than 2^31 nonzeros and whose rows of a
+ *                                             have at most 2^30 terms each
  * (tests/test_gpu_limits.py runs every path on either side of these; the _heads calls' limits are refused and queried on
  * either side in tests/test_gpu_attention_heads.py, where a launch at the limit itself would write 64 GiB.) */
 SPMV_API int spmv_csr_plan(spmv_csr_t *h, int variant, void *stream);

@@ -65,6 +65,9 @@ SIGNATURES = {
     "spmv_csr_select_scatter": (C.c_int, [_H, C.c_int, _vp, C.c_int64, _vp, C.c_int64, _vp]),
     "spmv_csr_select_map_bytes": (C.c_int64, [_H]),
     "spmv_csr_copy_arrays": (C.c_int, [_H, _i32p, _i32p, _f32p, _vp]),
+    "spmv_csr_spgemm": (C.c_int, [_H, _H, C.c_int, _vp, _HP, C.POINTER(C.c_int64)]),
+    "spmv_csr_spgemm_values": (C.c_int, [_H, _H, _H, _vp]),
+    "spmv_csr_spgemm_plan_bytes": (C.c_int64, [_H]),
     "spmv_csr_plan": (C.c_int, [_H, C.c_int, _vp]),
     "spmv_csr_run": (C.c_int, [_H, C.c_int, _f32p, _f32p, _vp]),
     "spmv_csr_run_vals16": (C.c_int, [_H, C.c_int, C.c_int, _vp, _f32p, _f32p, _vp]),
@@ -152,6 +155,7 @@ for _pass, _ops in _ATTN_PASSES.items():
     # the wide call of the pass (widths up to 128): exactly the _bias arguments; a null bias means none
     SIGNATURES[f"spmv_csr_attention_{_pass}_wide"] = SIGNATURES[f"spmv_csr_attention_{_pass}_bias"]
 ATTN_FP32, ATTN_BF16, ATTN_FP16 = 0, 1, 2      # enums of include/spmv_hip.h: the dtype of a _16 call (1, 2) or a _bias call
+SPGEMM_CLASS_SLOTS = (64, 512, 4096, 32768)     # SPMV_SPGEMM_CLASS_SLOTS: the words of LDS a row of each class of spgemm sorts in
 COLS_MAX_K = 65536                             # SPMV_COLS_MAX_K: the widest k of spmm_cols / sddmm_cols
 # CsrMatrix.spmm / spmm_cols / sddmm / sddmm_cols: (method, ATTN_* dtype of its matrices) -> (the C call, its dtype argument
 # as a tuple: the narrow fp32 calls take none).  Built here, not per call.
@@ -442,6 +446,32 @@ class CsrMatrix:
                     or not t.is_cuda:
                 raise ValueError(f"copy_arrays: {name} must be a contiguous 1-D {dt} device tensor of {n} elements")
         check(lib().spmv_csr_copy_arrays(self._h, _ptr(row_ptr), _ptr(col_idx), _ptr(vals), _stream_handle(stream)))
+
+    # -- the sparse product (spmv_csr_spgemm) ------------------------------------------------------------------------
+    def spgemm(self, b: "CsrMatrix", keep_plan: bool = False, stream=None) -> "CsrMatrix":
+        """``self @ b`` as a new handle that owns its arrays (waits for the stream): rows sorted and duplicate-free, the
+        pattern structural, every value one fma chain over its terms in storage order.  ``keep_plan=True`` keeps the row lists
+        :meth:`spgemm_values` needs.  The result's ``spgemm_products`` is the number of terms."""
+        if not isinstance(b, CsrMatrix):
+            raise TypeError("spgemm: b must be a CsrMatrix")
+        if self.cols != b.rows:
+            raise ValueError(f"spgemm: self is {self.rows} x {self.cols}, b is {b.rows} x {b.cols}")
+        h, products = C.c_void_p(), C.c_int64(-1)
+        check(lib().spmv_csr_spgemm(self._h, b._h, 1 if keep_plan else 0, _stream_handle(stream), C.byref(h), C.byref(products)))
+        c = CsrMatrix(h.value)
+        c.spgemm_products = products.value
+        return c
+
+    def spgemm_values(self, a: "CsrMatrix", b: "CsrMatrix", stream=None) -> None:
+        """Recompute this handle's values (made by ``a.spgemm(b, keep_plan=True)``) from the values ``a`` and ``b`` hold now: the
+        numeric pass alone, asynchronous, graph-capturable; then what :meth:`values_changed` does."""
+        check(lib().spmv_csr_spgemm_values(self._h, a._h, b._h, _stream_handle(stream)))
+
+    def spgemm_plan_bytes(self) -> int:
+        n = lib().spmv_csr_spgemm_plan_bytes(self._h)
+        if n < 0:
+            check(n)
+        return n
 
     # -- SpMM: k right-hand sides at once (spmv_csr_spmm) ---------------------------------------------------------
     def spmm_plan(self, stream=None) -> None:

@@ -566,6 +566,58 @@ int spmv_csr_copy_arrays(const spmv_csr_t *h, int32_t *d_row_ptr, int32_t *d_col
     return SPMV_OK;
 }
 
+// ---- the sparse product (kernels_spgemm.hip) ------------------------------------------------------------------------------
+int spmv_csr_spgemm(const spmv_csr_t *a, const spmv_csr_t *b, int keep_plan, void *stream, spmv_csr_t **out, int64_t *products)
+{
+    const char *what = "spmv_csr_spgemm";
+    if (!a || !b || !out) { set_error("%s: null argument", what); return SPMV_ERR_INVALID; }
+    if (a->cols != b->rows) {
+        set_error("%s: a is %lld x %lld, b is %lld x %lld (a.cols must be b.rows)", what, (long long)a->rows, (long long)a->cols,
+                  (long long)b->rows, (long long)b->cols);
+        return SPMV_ERR_INVALID;
+    }
+    if (keep_plan != 0 && keep_plan != 1) { set_error("%s: keep_plan = %d (0 or 1)", what, keep_plan); return SPMV_ERR_INVALID; }
+    if (int rc = require_device()) return rc;
+    if (a->device != b->device) {
+        set_error("%s: a lives on device %d, b on device %d", what, a->device, b->device);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(a->device, what)) return rc;
+    return spgemm(*a, *b, keep_plan == 1, (hipStream_t)stream, out, products);
+}
+
+int spmv_csr_spgemm_values(spmv_csr_t *c, const spmv_csr_t *a, const spmv_csr_t *b, void *stream)
+{
+    const char *what = "spmv_csr_spgemm_values";
+    if (!c || !a || !b) { set_error("%s: null argument", what); return SPMV_ERR_INVALID; }
+    const SpgemmPlan &p = c->plan_spgemm;
+    if (!p.ready || !c->own_vals) {
+        set_error("%s: the handle has no plan (it was not made by spmv_csr_spgemm with keep_plan = 1)", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (a->rows != c->rows || a->cols != p.inner || b->rows != p.inner || b->cols != c->cols || a->nnz != p.a_nnz || b->nnz != p.b_nnz) {
+        set_error("%s: a is %lld x %lld with %lld nonzeros and b %lld x %lld with %lld, c was made from %lld x %lld with %lld and "
+                  "%lld x %lld with %lld", what, (long long)a->rows, (long long)a->cols, (long long)a->nnz, (long long)b->rows,
+                  (long long)b->cols, (long long)b->nnz, (long long)c->rows, (long long)p.inner, (long long)p.a_nnz, (long long)p.inner,
+                  (long long)c->cols, (long long)p.b_nnz);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(c->device, what)) return rc;
+    if (a->device != c->device || b->device != c->device) {
+        set_error("%s: a lives on device %d, b on device %d, c on device %d", what, a->device, b->device, c->device);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = spgemm_values(*c, *a, *b, (hipStream_t)stream)) return rc;
+    ++c->values_gen;
+    return SPMV_OK;
+}
+
+int64_t spmv_csr_spgemm_plan_bytes(const spmv_csr_t *c)
+{
+    if (!c) { set_error("spmv_csr_spgemm_plan_bytes: null handle"); return SPMV_ERR_INVALID; }
+    return spgemm_plan_bytes(*c);
+}
+
 // SPMV_AUTO.  TILED's plan is made first (cheap: a few passes over col_idx, no trial launches) and priced (model_cost,
 // in units of "a chunk that streams 8 bytes per nonzero with cache-resident gathers").
 //   1. It stages (nearly) everything in one or two passes (model_cost <= 1.20: bands up to ~60 000 columns at config 4): TILED.

@@ -272,6 +272,14 @@ struct AttnPlan {
     DevPtr<float> d_scratch_wide;     // [wide_heads * pieces * 260] the same for widths above 64: (m, l) and up to 2 x 128 partial sums
 };
 
+// spmv_csr_spgemm(keep_plan = 1) (kernels_spgemm.hip): what the numeric pass needs to start without a host decision
+struct SpgemmPlan {
+    bool ready = false;
+    int64_t inner = 0, a_nnz = 0, b_nnz = 0;   // a.cols = b.rows and the parents' nonzeros when the product was made
+    int64_t cls[6] = {0, 0, 0, 0, 0, 0};       // cls[c] .. cls[c + 1]: the rows of class c in d_order (class 4: oversized)
+    DevPtr<int32_t> d_order;                   // [cls[5]] the rows of a with at least one term, class by class, ascending inside
+};
+
 }  // namespace spmv
 
 
@@ -300,6 +308,7 @@ struct spmv_csr {
     spmv::WavePlan plan_wave;      // SPMV_WAVE_PIPE
     spmv::SpmmPlan plan_spmm;      // spmv_csr_spmm
     spmv::AttnPlan plan_attn;      // spmv_csr_attention_*
+    spmv::SpgemmPlan plan_spgemm;  // spmv_csr_spgemm_values (a handle made by spmv_csr_spgemm with keep_plan = 1)
     int auto_variant = -1;         // SPMV_AUTO: the variant its plan chose (-1 = not planned)
     uint64_t values_gen = 0;       // bumped by spmv_csr_values_changed: plans that copied vals before that are stale
 };
@@ -420,6 +429,11 @@ uint32_t select_key(float score, bool abs);
 // through sh's select map, for c < count, m < sh.nnz: dst[c][m] = src[c][map[m]], or (scatter) dst[c][map[m]] = src[c][m]
 int select_move(const spmv_csr &sh, bool scatter, int count, const void *src, int64_t src_stride, void *dst, int64_t dst_stride,
                 hipStream_t s);
+
+// kernels_spgemm.hip: spmv_csr_spgemm / spmv_csr_spgemm_values (the numeric pass alone, on c's plan)
+int spgemm(const spmv_csr &a, const spmv_csr &b, bool keep_plan, hipStream_t s, spmv_csr_t **out, int64_t *products);
+int spgemm_values(spmv_csr &c, const spmv_csr &a, const spmv_csr &b, hipStream_t s);
+int64_t spgemm_plan_bytes(const spmv_csr &c);
 
 int dense_to_csr(int M, int N, const float *d_A, hipStream_t s, spmv_csr_t **out);
 int dense_gemv(int M, int N, const float *d_A, const float *d_x, float *d_y, int mode, hipStream_t s);

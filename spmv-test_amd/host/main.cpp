@@ -4,11 +4,15 @@
 //   sparse_sgemv --csrbin FILE [--variant NAME] [--transpose] [--out Y.txt]
 //        y = A * ones through the C ABI on a matrix from disk (row f-4), checked against a host walk;
 //        --transpose: y = A^T * ones (x of `rows` ones, y of `cols` entries) through spmv_csr_transpose
+//   sparse_sgemv --mtx A.mtx --spgemm B.mtx [--out C.mtx]
+//        C = A * B through spmv_csr_spgemm, checked against a host walk of the same fma chains (pattern and bits), written
+//        as a Matrix Market coordinate file
 // $SPMV_SEED makes the random inputs reproducible.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 #include "kernel.hpp"
@@ -22,9 +26,60 @@ static int variant_by_name(const std::string &n)
     return -1;
 }
 
+// C = A B through the C ABI against the contract of include/spmv_hip.h "the sparse product", walked on the host
+static int run_spgemm(const HostCsr &a, const std::string &b_path, const std::string &out)
+{
+    HostCsr b;
+    std::string err = read_matrix_market(b_path, b);
+    if (!err.empty()) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    std::printf("times matrix %lld x %lld, nnz %lld\n", (long long)b.rows, (long long)b.cols, (long long)b.nnz());
+    spmv_csr_t *A = nullptr, *B = nullptr, *Cm = nullptr;
+    SPMV_CHECK(spmv_csr_create_host(a.rows, a.cols, a.nnz(), a.row_ptr.data(), a.col_idx.data(), a.vals.data(), &A));
+    SPMV_CHECK(spmv_csr_create_host(b.rows, b.cols, b.nnz(), b.row_ptr.data(), b.col_idx.data(), b.vals.data(), &B));
+    int64_t products = 0, rows = 0, cols = 0, nnz = 0;
+    SPMV_CHECK(spmv_csr_spgemm(A, B, 0, nullptr, &Cm, &products));
+    SPMV_CHECK(spmv_csr_dims(Cm, &rows, &cols, &nnz));
+    HostCsr c;
+    c.rows = rows; c.cols = cols;
+    c.row_ptr.resize((size_t)rows + 1); c.col_idx.resize((size_t)nnz); c.vals.resize((size_t)nnz);
+    SPMV_CHECK(spmv_csr_download(Cm, c.row_ptr.data(), c.col_idx.data(), c.vals.data()));
+    SPMV_CHECK(spmv_csr_destroy(Cm));
+    SPMV_CHECK(spmv_csr_destroy(B));
+    SPMV_CHECK(spmv_csr_destroy(A));
+    std::printf("spmv_csr_spgemm: %lld x %lld, nnz %lld from %lld products\n", (long long)rows, (long long)cols, (long long)nnz, (long long)products);
+    int64_t bad = 0, at = 0;
+    for (int64_t i = 0; i < a.rows; ++i) {
+        std::map<int32_t, float> acc;
+        for (int32_t s = a.row_ptr[i]; s < a.row_ptr[i + 1]; ++s)
+            for (int32_t q = b.row_ptr[a.col_idx[s]]; q < b.row_ptr[a.col_idx[s] + 1]; ++q) {
+                float &v = acc.emplace(b.col_idx[q], 0.0f).first->second;
+                v = std::fmaf(a.vals[s], b.vals[q], v);
+            }
+        if (c.row_ptr[i] != at || c.row_ptr[i + 1] - c.row_ptr[i] != (int64_t)acc.size()) { ++bad; at = c.row_ptr[i + 1]; continue; }
+        for (const auto &e : acc) {
+            const bool same = c.col_idx[at] == e.first && (std::memcmp(&c.vals[at], &e.second, 4) == 0 || (std::isnan(c.vals[at]) && std::isnan(e.second)));
+            if (!same) {
+                if (bad < 16) std::fprintf(stderr, "[row %lld] cpu: (%d, %g), gpu: (%d, %g)\n", (long long)i, e.first, e.second, c.col_idx[at], c.vals[at]);
+                ++bad;
+            }
+            ++at;
+        }
+    }
+    if (!out.empty()) {
+        FILE *f = std::fopen(out.c_str(), "w");
+        if (!f) { std::fprintf(stderr, "error: cannot write %s\n", out.c_str()); return 2; }
+        std::fprintf(f, "%%%%MatrixMarket matrix coordinate real general\n%lld %lld %lld\n", (long long)rows, (long long)cols, (long long)nnz);
+        for (int64_t i = 0; i < rows; ++i)
+            for (int32_t k = c.row_ptr[i]; k < c.row_ptr[i + 1]; ++k) std::fprintf(f, "%lld %d %.9g\n", (long long)i + 1, c.col_idx[k] + 1, c.vals[k]);
+        if (std::fclose(f) != 0) { std::fprintf(stderr, "error: cannot write %s\n", out.c_str()); return 2; }
+    }
+    std::printf(bad ? "====== %lld MISMATCHES ======\n" : "========== OK ===========\n", (long long)bad);
+    return bad ? 1 : 0;
+}
+
 static int run_file(int argc, char **argv)
 {
-    std::string mtx, bin, out, save, vname = "tiled";
+    std::string mtx, bin, out, save, spgemm_b, vname = "tiled";
     bool parse_only = false, transpose = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -36,6 +91,7 @@ static int run_file(int argc, char **argv)
         else if (a == "--variant") vname = next();
         else if (a == "--parse-only") parse_only = true;
         else if (a == "--transpose") transpose = true;
+        else if (a == "--spgemm") spgemm_b = next();
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     HostCsr m;
@@ -44,6 +100,7 @@ static int run_file(int argc, char **argv)
     std::printf("matrix %lld x %lld, nnz %lld\n", (long long)m.rows, (long long)m.cols, (long long)m.nnz());
     if (!save.empty() && !(err = write_csr_binary(save, m)).empty()) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
     if (parse_only) return 0;
+    if (!spgemm_b.empty()) return run_spgemm(m, spgemm_b, out);
     const int variant = variant_by_name(vname);
     if (variant < 0) { std::fprintf(stderr, "unknown variant %s\n", vname.c_str()); return 2; }
 

@@ -118,6 +118,30 @@ class SparseLayer:
         layer.selection = sel
         return layer
 
+    def composed(self, first: "SparseLayer") -> "SparseLayer":
+        """A new SparseLayer on ``self.A @ first.A`` (spmv_csr_spgemm), so that ``new(X)`` approximates ``self(first(X))`` --
+        two layers without an activation between them folded into one; the sums are taken in another order, so the bits
+        differ.  Its ``row_ptr`` and ``col_idx`` are fresh device tensors (copy_arrays) and its ``vals`` a fresh leaf
+        (requires_grad as this layer's); ``k_max`` is this layer's.  No gradient flows to the parents, which are untouched."""
+        if not isinstance(first, SparseLayer):
+            raise ValueError("SparseLayer.composed: first must be a SparseLayer")
+        if self.A.cols != first.A.rows:
+            raise ValueError(f"SparseLayer.composed: self is {self.A.rows} x {self.A.cols}, first is {first.A.rows} x {first.A.cols} "
+                             "(self's columns must be first's rows)")
+        prod = self.A.spgemm(first.A)
+        try:
+            dev = self.vals.device
+            row_ptr = torch.empty(prod.rows + 1, dtype=torch.int32, device=dev)
+            col_idx = torch.empty(prod.nnz, dtype=torch.int32, device=dev)
+            vals = torch.empty(prod.nnz, dtype=torch.float32, device=dev)
+            prod.copy_arrays(row_ptr, col_idx, vals)
+            torch.cuda.current_stream().synchronize()      # the copies are done before the product's arrays are freed
+            rows, cols = prod.rows, prod.cols
+        finally:
+            prod.close()
+        vals.requires_grad_(self.vals.requires_grad)
+        return SparseLayer(rows, cols, row_ptr, col_idx, vals, k_max=self.k_max)
+
     def close(self) -> None:
         sel = getattr(self, "selection", None)
         if sel is not None:
