@@ -352,6 +352,78 @@ SPMV_API int spmv_csr_spgemm(const spmv_csr_t *a, const spmv_csr_t *b, int keep_
 SPMV_API int spmv_csr_spgemm_values(spmv_csr_t *c, const spmv_csr_t *a, const spmv_csr_t *b, void *stream);
 SPMV_API int64_t spmv_csr_spgemm_plan_bytes(const spmv_csr_t *c);
 
+/* ---- the sparse sum ----------------------------------------------------------
+ * A pattern from two patterns of one shape: C = alpha A + beta B on the union, the intersection or the difference of the two
+ * patterns, as a new handle on their device.  It is how an attention pattern is put together (a band UNION a top-k selection
+ * UNION a few global columns), how a candidate pattern is masked (INTERSECT) or already-attended keys are removed (MINUS), how a
+ * pruned layer grows again (the old pattern UNION new positions, which start at +0), and how A + A^T or A - sigma I are formed.
+ * The contract below holds bit for bit (tests/_add.py states it in numpy).
+ *
+ *   Shapes.  a and b are both m x n on one device; *out is m x n, owns its three arrays (spmv_csr_destroy frees them), is
+ * accepted by every spmv_csr_* call and has no plans of a variant yet.  a and b are only read and keep their plans; either may
+ * own or borrow its arrays and be a whole matrix or a row block; a == b is allowed.
+ *   Pattern.  Row i of C lists each of these columns once, in ascending order -- SPMV_ADD_UNION: a column that occurs in row
+ * i of a or of b; SPMV_ADD_INTERSECT: a column that occurs in both; SPMV_ADD_MINUS: a column that occurs in a and not in b.
+ * The rows of C are sorted and duplicate-free whatever the rows of a and b are (unsorted, repeated columns).  The pattern is
+ * structural: stored zeros of a and b count, and an entry stays when its value is 0, -0 or a NaN and when its terms cancel.
+ *   Values.  The terms of entry (i, j) come in this order: the storage positions s of a's row i with a.col_idx[s] == j,
+ * ascending, then the positions q of b's row i with b.col_idx[q] == j, ascending.  A term has the coefficient of its side
+ * (alpha for a, beta for b).  The first term gives acc = fl(coef * v), every later one acc = fma(coef, v, acc).  A side whose
+ * coefficient is +0 or -0 contributes to the pattern and has NO terms (its values, NaN and Inf included, are not read into
+ * the sum); an entry without terms is +0.  Under SPMV_ADD_MINUS only a has terms and beta is ignored.  A NaN or infinite
+ * coefficient follows IEEE rules; subnormals are kept; a NaN result is a NaN of the hardware's sign and payload.
+ *   So: add(A, empty, 1, x, UNION) is A with every row stably sorted by column (A itself bit for bit when its rows are sorted
+ * and duplicate-free); add(A, M, 1, 0, INTERSECT) restricts A to M's pattern whatever M's values are; add(A, G, 1, 0, UNION) is
+ * A widened by G's positions at +0.
+ *   Purity.  C is a pure function of the six input arrays, the coefficients and op: two calls, two handles, any stream and any
+ * neighbouring rows give the same bytes, and the rows of add(row block of a, the same block of b) are the corresponding rows
+ * of add(a, b).  There is no atomic in the route, so no place and no sum depends on the order in which anything arrives.
+ *   Like spmv_csr_transpose the call allocates, enqueues on `stream` and waits for it before it returns (out.nnz is a
+ * result).  There are no row classes: every row, however long, takes the same launches.
+ *   SPMV_ERR_INVALID (the message names the function, *out untouched, nothing left allocated): a null a, b or out; shapes
+ * that differ (the message gives both); a and b on different devices, or another current device than theirs; op outside the
+ * enum; keep_plan other than 0 / 1; a result of 2^31 or more entries (refused after the count and before anything of that
+ * size is allocated; the message carries the count).  SPMV_ERR_HIP when an allocation fails (what was allocated is released,
+ * a and b stay usable); SPMV_ERR_NO_DEVICE as everywhere.  m = 0, n = 0, nnz = 0 on either side and an empty result work.
+ *   Plan.  The call builds the kept terms in C's order: per kept term a 32-bit word (the side in the top bit, the storage
+ * position in that side below it) and per entry of C where its terms start.  The kept terms T are the nonzeros of a whose
+ * column is an entry of C and, under UNION and INTERSECT, those of b -- whatever the coefficients are.  With keep_plan = 1
+ * the handle keeps both arrays: 4 T + 4 (nnz(C) + 1) bytes, what spmv_csr_add_plan_bytes returns (0 without a plan; < 0: null
+ * handle).
+ *   Device memory.  C itself takes 4 (m + 1) + 8 nnz(C) bytes.  Sorted operands (every row non-decreasing): the call holds at
+ * most 4 (nnz(a) + 1) + 4 (nnz(b) + 1) [b's under UNION only] + 4 (nnz(C) + 1) + 4 T + 4 ceil(max(nnz(a), nnz(b), nnz(C), m) /
+ * 4096) + 16 bytes more (the ranks of the kept heads, freed before the terms are allocated; the plan's two arrays, freed on
+ * return without keep_plan; the tile sums of a scan).  An operand x with an unsorted row is replaced by its stably
+ * row-sorted view, transpose(transpose(x)) with both maps composed: 12 nnz(x) + 4 (m + 1) bytes more for the whole call, and
+ * while the view is built the transpose's peak above (24.25 nnz(x) + 4 n, beside 12 nnz(x) + 4 (n + 1) of the first
+ * transpose).
+ *
+ * spmv_csr_add_values: for a c made with keep_plan = 1, c.vals recomputed under the contract above from the values a and b
+ * hold now, with the coefficients given now (one that is +0 or -0 now drops that side's terms, as in the first call): the value
+ * kernel of the first call, a lane per entry of C that walks its run.  One launch; asynchronous, allocates nothing, never
+ * waits: graph-capturable.  Afterwards it does for c what spmv_csr_values_changed(c) does (see spmv_csr_transpose_values).  a
+ * and b must have c's shape and the nnz of c's parents (the handle records both) on c's device, else SPMV_ERR_INVALID; that
+ * their PATTERNS are unchanged is the caller's promise.  On a handle without a plan: SPMV_ERR_INVALID, nothing launched.
+ *
+ * spmv_csr_add_gather: dst[k * dst_stride + p] = src[k * src_stride + e] for every kept term at storage position p of the
+ * chosen side (0: a, 1: b) whose entry of C is e, for k < count: 32-bit words copied as bits; every other word of dst is left
+ * untouched (the targets are distinct, so nothing races).  It is how a gradient on C's pattern reaches the operands (dA =
+ * alpha * gathered) and how state kept in C's order is read back.  The arrays in C's order hold c.nnz words, those in the
+ * side's order that side's nnz; strides count words; src and dst need 4-byte alignment only and must not overlap.
+ * Asynchronous, allocates nothing, never waits: graph-capturable.  SPMV_ERR_INVALID, nothing launched: a handle without a
+ * plan; side other than 0 / 1; count < 1; a null array while c.nnz > 0; an array that is not 4-byte aligned; a negative
+ * stride; dst_stride below the words of one array of dst with count > 1.
+ *
+ * One map per handle: a sum handle carries no transpose map, select map or product plan, so those companions refuse it, and
+ * the companions here refuse a handle made by another call. */
+enum { SPMV_ADD_UNION = 0, SPMV_ADD_INTERSECT = 1, SPMV_ADD_MINUS = 2 };
+SPMV_API int spmv_csr_add(const spmv_csr_t *a, const spmv_csr_t *b, float alpha, float beta, int op, int keep_plan, void *stream,
+                          spmv_csr_t **out);
+SPMV_API int spmv_csr_add_values(spmv_csr_t *c, const spmv_csr_t *a, const spmv_csr_t *b, float alpha, float beta, void *stream);
+SPMV_API int spmv_csr_add_gather(const spmv_csr_t *c, int side /* 0: a, 1: b */, int count, const void *d_src, int64_t src_stride,
+                                 void *d_dst, int64_t dst_stride, void *stream);
+SPMV_API int64_t spmv_csr_add_plan_bytes(const spmv_csr_t *c);
+
 /* ---- the hot path ------------------------------------------------------
  * spmv_csr_plan: one-off device-side preprocessing a variant needs (chunk
  * boundaries, column windows, for SPMV_TILED also a 16-bit copy of the column

@@ -68,6 +68,10 @@ SIGNATURES = {
     "spmv_csr_spgemm": (C.c_int, [_H, _H, C.c_int, _vp, _HP, C.POINTER(C.c_int64)]),
     "spmv_csr_spgemm_values": (C.c_int, [_H, _H, _H, _vp]),
     "spmv_csr_spgemm_plan_bytes": (C.c_int64, [_H]),
+    "spmv_csr_add": (C.c_int, [_H, _H, C.c_float, C.c_float, C.c_int, C.c_int, _vp, _HP]),
+    "spmv_csr_add_values": (C.c_int, [_H, _H, _H, C.c_float, C.c_float, _vp]),
+    "spmv_csr_add_gather": (C.c_int, [_H, C.c_int, C.c_int, _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "spmv_csr_add_plan_bytes": (C.c_int64, [_H]),
     "spmv_csr_plan": (C.c_int, [_H, C.c_int, _vp]),
     "spmv_csr_run": (C.c_int, [_H, C.c_int, _f32p, _f32p, _vp]),
     "spmv_csr_run_vals16": (C.c_int, [_H, C.c_int, C.c_int, _vp, _f32p, _f32p, _vp]),
@@ -156,6 +160,8 @@ for _pass, _ops in _ATTN_PASSES.items():
     SIGNATURES[f"spmv_csr_attention_{_pass}_wide"] = SIGNATURES[f"spmv_csr_attention_{_pass}_bias"]
 ATTN_FP32, ATTN_BF16, ATTN_FP16 = 0, 1, 2      # enums of include/spmv_hip.h: the dtype of a _16 call (1, 2) or a _bias call
 SPGEMM_CLASS_SLOTS = (64, 512, 4096, 32768)     # SPMV_SPGEMM_CLASS_SLOTS: the words of LDS a row of each class of spgemm sorts in
+ADD_UNION, ADD_INTERSECT, ADD_MINUS = 0, 1, 2   # enums of include/spmv_hip.h: the op of spmv_csr_add
+_ADD_OPS = {"union": ADD_UNION, "intersect": ADD_INTERSECT, "minus": ADD_MINUS}
 COLS_MAX_K = 65536                             # SPMV_COLS_MAX_K: the widest k of spmm_cols / sddmm_cols
 # CsrMatrix.spmm / spmm_cols / sddmm / sddmm_cols: (method, ATTN_* dtype of its matrices) -> (the C call, its dtype argument
 # as a tuple: the narrow fp32 calls take none).  Built here, not per call.
@@ -469,6 +475,53 @@ class CsrMatrix:
 
     def spgemm_plan_bytes(self) -> int:
         n = lib().spmv_csr_spgemm_plan_bytes(self._h)
+        if n < 0:
+            check(n)
+        return n
+
+    # -- the sparse sum (spmv_csr_add) ------------------------------------------------------------------------------
+    def add(self, b: "CsrMatrix", alpha: float = 1.0, beta: float = 1.0, op="union", keep_plan: bool = False, stream=None) -> "CsrMatrix":
+        """``alpha * self + beta * b`` on the union, the intersection or the difference (``op``: "union" | "intersect" | "minus"
+        or an ``ADD_*`` constant) of the two patterns, as a new handle that owns its arrays (waits for the stream): rows sorted
+        and duplicate-free, the pattern structural, every value one chain over ``self``'s terms and then ``b``'s in storage order;
+        a side whose coefficient is 0 gives its pattern and no terms.  ``keep_plan=True`` keeps the terms :meth:`add_values` and
+        :meth:`add_gather` need."""
+        if not isinstance(b, CsrMatrix):
+            raise TypeError("add: b must be a CsrMatrix")
+        if (self.rows, self.cols) != (b.rows, b.cols):
+            raise ValueError(f"add: self is {self.rows} x {self.cols}, b is {b.rows} x {b.cols}")
+        if isinstance(op, str):
+            if op not in _ADD_OPS:
+                raise ValueError(f"add: op = {op!r} (one of {sorted(_ADD_OPS)})")
+            op = _ADD_OPS[op]
+        if isinstance(op, bool) or not isinstance(op, int):
+            raise ValueError(f"add: op = {op!r}")
+        h = C.c_void_p()
+        check(lib().spmv_csr_add(self._h, b._h, float(alpha), float(beta), op, 1 if keep_plan else 0, _stream_handle(stream), C.byref(h)))
+        c = CsrMatrix(h.value)
+        c.add_parent_nnz = (self.nnz, b.nnz)
+        return c
+
+    def add_values(self, a: "CsrMatrix", b: "CsrMatrix", alpha: float = 1.0, beta: float = 1.0, stream=None) -> None:
+        """Recompute this handle's values (made by ``a.add(b, ..., keep_plan=True)``) from the values ``a`` and ``b`` hold now with
+        the coefficients given now: one launch, asynchronous, graph-capturable; then what :meth:`values_changed` does."""
+        if not isinstance(a, CsrMatrix) or not isinstance(b, CsrMatrix):
+            raise TypeError("add_values: a and b must be CsrMatrix")
+        check(lib().spmv_csr_add_values(self._h, a._h, b._h, float(alpha), float(beta), _stream_handle(stream)))
+
+    def add_gather(self, side: int, src, dst, stream=None) -> None:
+        """On a handle made by ``a.add(b, ..., keep_plan=True)``: ``dst[..., p] = src[..., e]`` for every kept term at storage
+        position p of ``side`` (0: a, 1: b) whose entry of this handle is e; every other element of dst is left as it is.  src:
+        (nnz,) or (count, nnz) in this handle's order, dst: the same over that side's nnz; one 4-byte dtype, stride(-1) == 1."""
+        if isinstance(side, bool) or side not in (0, 1):
+            raise ValueError(f"add_gather: side = {side!r} (0: a, 1: b)")
+        n = getattr(self, "add_parent_nnz", None)
+        if n is None:
+            raise ValueError("add_gather: this handle was not made by add")
+        self._select_move("add_gather", lambda h, *rest: lib().spmv_csr_add_gather(h, side, *rest), src, dst, self.nnz, n[side], stream)
+
+    def add_plan_bytes(self) -> int:
+        n = lib().spmv_csr_add_plan_bytes(self._h)
         if n < 0:
             check(n)
         return n

@@ -618,6 +618,95 @@ int64_t spmv_csr_spgemm_plan_bytes(const spmv_csr_t *c)
     return spgemm_plan_bytes(*c);
 }
 
+// ---- the sparse sum (kernels_add.hip) ----------------------------------------------------------------------------------------
+int spmv_csr_add(const spmv_csr_t *a, const spmv_csr_t *b, float alpha, float beta, int op, int keep_plan, void *stream, spmv_csr_t **out)
+{
+    const char *what = "spmv_csr_add";
+    if (!a || !b || !out) { set_error("%s: null argument", what); return SPMV_ERR_INVALID; }
+    if (a->rows != b->rows || a->cols != b->cols) {
+        set_error("%s: a is %lld x %lld, b is %lld x %lld (the shapes must be equal)", what, (long long)a->rows, (long long)a->cols,
+                  (long long)b->rows, (long long)b->cols);
+        return SPMV_ERR_INVALID;
+    }
+    if (op != SPMV_ADD_UNION && op != SPMV_ADD_INTERSECT && op != SPMV_ADD_MINUS) {
+        set_error("%s: op = %d (SPMV_ADD_UNION, SPMV_ADD_INTERSECT or SPMV_ADD_MINUS)", what, op);
+        return SPMV_ERR_INVALID;
+    }
+    if (keep_plan != 0 && keep_plan != 1) { set_error("%s: keep_plan = %d (0 or 1)", what, keep_plan); return SPMV_ERR_INVALID; }
+    if (int rc = require_device()) return rc;
+    if (a->device != b->device) {
+        set_error("%s: a lives on device %d, b on device %d", what, a->device, b->device);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(a->device, what)) return rc;
+    return add(*a, *b, alpha, beta, op, keep_plan == 1, (hipStream_t)stream, out);
+}
+
+int spmv_csr_add_values(spmv_csr_t *c, const spmv_csr_t *a, const spmv_csr_t *b, float alpha, float beta, void *stream)
+{
+    const char *what = "spmv_csr_add_values";
+    if (!c || !a || !b) { set_error("%s: null argument", what); return SPMV_ERR_INVALID; }
+    const AddPlan &p = c->plan_add;
+    if (!p.ready || !c->own_vals) {
+        set_error("%s: the handle has no plan (it was not made by spmv_csr_add with keep_plan = 1)", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (a->rows != c->rows || a->cols != c->cols || b->rows != c->rows || b->cols != c->cols || a->nnz != p.a_nnz || b->nnz != p.b_nnz) {
+        set_error("%s: a is %lld x %lld with %lld nonzeros and b %lld x %lld with %lld, c was made from two %lld x %lld operands with "
+                  "%lld and %lld", what, (long long)a->rows, (long long)a->cols, (long long)a->nnz, (long long)b->rows, (long long)b->cols,
+                  (long long)b->nnz, (long long)c->rows, (long long)c->cols, (long long)p.a_nnz, (long long)p.b_nnz);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(c->device, what)) return rc;
+    if (a->device != c->device || b->device != c->device) {
+        set_error("%s: a lives on device %d, b on device %d, c on device %d", what, a->device, b->device, c->device);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = add_values(*c, *a, *b, alpha, beta, (hipStream_t)stream)) return rc;
+    ++c->values_gen;
+    return SPMV_OK;
+}
+
+int spmv_csr_add_gather(const spmv_csr_t *c, int side, int count, const void *d_src, int64_t src_stride, void *d_dst, int64_t dst_stride,
+                        void *stream)
+{
+    const char *what = "spmv_csr_add_gather";
+    if (!c) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (!c->plan_add.ready) {
+        set_error("%s: the handle has no plan (it was not made by spmv_csr_add with keep_plan = 1)", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (side != 0 && side != 1) { set_error("%s: side = %d (0: a, 1: b)", what, side); return SPMV_ERR_INVALID; }
+    if (count < 1) { set_error("%s: count = %d (need count >= 1)", what, count); return SPMV_ERR_INVALID; }
+    if ((!d_src || !d_dst) && c->nnz > 0) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
+    if (reinterpret_cast<uintptr_t>(d_src) % 4 != 0 || reinterpret_cast<uintptr_t>(d_dst) % 4 != 0) {
+        set_error("%s: src and dst must be 4-byte aligned", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (src_stride < 0 || dst_stride < 0) {
+        set_error("%s: src_stride = %lld, dst_stride = %lld (a stride is not negative)", what, (long long)src_stride, (long long)dst_stride);
+        return SPMV_ERR_INVALID;
+    }
+    if (src_stride > INT64_MAX / 4 / count || dst_stride > INT64_MAX / 4 / count) {
+        set_error("%s: a stride overflows 64-bit byte offsets", what);
+        return SPMV_ERR_INVALID;
+    }
+    const int64_t dst_len = side ? c->plan_add.b_nnz : c->plan_add.a_nnz;      // words of one array of dst
+    if (count > 1 && dst_stride < dst_len) {
+        set_error("%s: dst_stride = %lld is below the %lld words of an array with count = %d", what, (long long)dst_stride,
+                  (long long)dst_len, count);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(c->device, what)) return rc;
+    return add_gather(*c, side, count, d_src, src_stride, d_dst, dst_stride, (hipStream_t)stream);
+}
+
+int64_t spmv_csr_add_plan_bytes(const spmv_csr_t *c)
+{
+    if (!c) { set_error("spmv_csr_add_plan_bytes: null handle"); return SPMV_ERR_INVALID; }
+    return add_plan_bytes(*c);
+}
+
 // SPMV_AUTO.  TILED's plan is made first (cheap: a few passes over col_idx, no trial launches) and priced (model_cost,
 // in units of "a chunk that streams 8 bytes per nonzero with cache-resident gathers").
 //   1. It stages (nearly) everything in one or two passes (model_cost <= 1.20: bands up to ~60 000 columns at config 4): TILED.

@@ -280,6 +280,15 @@ struct SpgemmPlan {
     DevPtr<int32_t> d_order;                   // [cls[5]] the rows of a with at least one term, class by class, ascending inside
 };
 
+// spmv_csr_add(keep_plan = 1) (kernels_add.hip): the kept terms in c's order, what spmv_csr_add_values and _gather walk
+struct AddPlan {
+    bool ready = false;
+    int op = 0;                                // SPMV_ADD_*
+    int64_t a_nnz = 0, b_nnz = 0, terms = 0;   // the parents' nonzeros when the sum was made; the kept terms
+    DevPtr<uint32_t> d_term;                   // [terms] side << 31 | storage position in that side, entry by entry, a's before b's
+    DevPtr<int32_t> d_start;                   // [nnz + 1] the first term of every entry of c
+};
+
 }  // namespace spmv
 
 
@@ -309,6 +318,7 @@ struct spmv_csr {
     spmv::SpmmPlan plan_spmm;      // spmv_csr_spmm
     spmv::AttnPlan plan_attn;      // spmv_csr_attention_*
     spmv::SpgemmPlan plan_spgemm;  // spmv_csr_spgemm_values (a handle made by spmv_csr_spgemm with keep_plan = 1)
+    spmv::AddPlan plan_add;        // spmv_csr_add_values / _gather (a handle made by spmv_csr_add with keep_plan = 1)
     int auto_variant = -1;         // SPMV_AUTO: the variant its plan chose (-1 = not planned)
     uint64_t values_gen = 0;       // bumped by spmv_csr_values_changed: plans that copied vals before that are stale
 };
@@ -434,6 +444,12 @@ int select_move(const spmv_csr &sh, bool scatter, int count, const void *src, in
 int spgemm(const spmv_csr &a, const spmv_csr &b, bool keep_plan, hipStream_t s, spmv_csr_t **out, int64_t *products);
 int spgemm_values(spmv_csr &c, const spmv_csr &a, const spmv_csr &b, hipStream_t s);
 int64_t spgemm_plan_bytes(const spmv_csr &c);
+
+// kernels_add.hip: spmv_csr_add / spmv_csr_add_values (the value pass alone, on c's plan) / spmv_csr_add_gather
+int add(const spmv_csr &a, const spmv_csr &b, float alpha, float beta, int op, bool keep_plan, hipStream_t s, spmv_csr_t **out);
+int add_values(spmv_csr &c, const spmv_csr &a, const spmv_csr &b, float alpha, float beta, hipStream_t s);
+int add_gather(const spmv_csr &c, int side, int count, const void *src, int64_t src_stride, void *dst, int64_t dst_stride, hipStream_t s);
+int64_t add_plan_bytes(const spmv_csr &c);
 
 int dense_to_csr(int M, int N, const float *d_A, hipStream_t s, spmv_csr_t **out);
 int dense_gemv(int M, int N, const float *d_A, const float *d_x, float *d_y, int mode, hipStream_t s);

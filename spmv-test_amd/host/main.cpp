@@ -7,11 +7,15 @@
 //   sparse_sgemv --mtx A.mtx --spgemm B.mtx [--out C.mtx]
 //        C = A * B through spmv_csr_spgemm, checked against a host walk of the same fma chains (pattern and bits), written
 //        as a Matrix Market coordinate file
+//   sparse_sgemv --mtx A.mtx --add B.mtx [--alpha x --beta y --op union|intersect|minus] [--out C.mtx]
+//        C = alpha A + beta B through spmv_csr_add, checked against a host walk of the same chains (pattern and bits), written
+//        as a Matrix Market coordinate file
 // $SPMV_SEED makes the random inputs reproducible.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <iterator>
 #include <map>
 #include <string>
 #include <vector>
@@ -77,9 +81,70 @@ static int run_spgemm(const HostCsr &a, const std::string &b_path, const std::st
     return bad ? 1 : 0;
 }
 
+// C = alpha A + beta B through the C ABI against the contract of include/spmv_hip.h "the sparse sum", walked on the host
+static int run_add(const HostCsr &a, const std::string &b_path, float alpha, float beta, int op, const std::string &out)
+{
+    HostCsr b;
+    std::string err = read_matrix_market(b_path, b);
+    if (!err.empty()) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    std::printf("plus matrix %lld x %lld, nnz %lld\n", (long long)b.rows, (long long)b.cols, (long long)b.nnz());
+    spmv_csr_t *A = nullptr, *B = nullptr, *Cm = nullptr;
+    SPMV_CHECK(spmv_csr_create_host(a.rows, a.cols, a.nnz(), a.row_ptr.data(), a.col_idx.data(), a.vals.data(), &A));
+    SPMV_CHECK(spmv_csr_create_host(b.rows, b.cols, b.nnz(), b.row_ptr.data(), b.col_idx.data(), b.vals.data(), &B));
+    int64_t rows = 0, cols = 0, nnz = 0;
+    SPMV_CHECK(spmv_csr_add(A, B, alpha, beta, op, 0, nullptr, &Cm));
+    SPMV_CHECK(spmv_csr_dims(Cm, &rows, &cols, &nnz));
+    HostCsr c;
+    c.rows = rows; c.cols = cols;
+    c.row_ptr.resize((size_t)rows + 1); c.col_idx.resize((size_t)nnz); c.vals.resize((size_t)nnz);
+    SPMV_CHECK(spmv_csr_download(Cm, c.row_ptr.data(), c.col_idx.data(), c.vals.data()));
+    SPMV_CHECK(spmv_csr_destroy(Cm));
+    SPMV_CHECK(spmv_csr_destroy(B));
+    SPMV_CHECK(spmv_csr_destroy(A));
+    std::printf("spmv_csr_add: %lld x %lld, nnz %lld\n", (long long)rows, (long long)cols, (long long)nnz);
+    struct Entry { bool in_a = false, in_b = false, any = false; float acc = 0.0f; };
+    int64_t bad = 0, at = 0;
+    for (int64_t i = 0; i < a.rows; ++i) {
+        std::map<int32_t, Entry> acc;
+        auto term = [](Entry &e, float coef, float v) {
+            if (coef == 0.0f) return;                                   // +0 or -0: the pattern, no terms
+            volatile float first = coef * v;                            // one rounding of its own
+            e.acc = e.any ? std::fmaf(coef, v, e.acc) : first;
+            e.any = true;
+        };
+        for (int32_t s = a.row_ptr[i]; s < a.row_ptr[i + 1]; ++s) { Entry &e = acc[a.col_idx[s]]; e.in_a = true; term(e, alpha, a.vals[s]); }
+        for (int32_t q = b.row_ptr[i]; q < b.row_ptr[i + 1]; ++q) { Entry &e = acc[b.col_idx[q]]; e.in_b = true; if (op != SPMV_ADD_MINUS) term(e, beta, b.vals[q]); }
+        for (auto it = acc.begin(); it != acc.end();) {
+            const bool kept = op == SPMV_ADD_UNION ? true : op == SPMV_ADD_INTERSECT ? (it->second.in_a && it->second.in_b) : (it->second.in_a && !it->second.in_b);
+            it = kept ? std::next(it) : acc.erase(it);
+        }
+        if (c.row_ptr[i] != at || c.row_ptr[i + 1] - c.row_ptr[i] != (int64_t)acc.size()) { ++bad; at = c.row_ptr[i + 1]; continue; }
+        for (const auto &e : acc) {
+            const float want = e.second.acc;
+            const bool same = c.col_idx[at] == e.first && (std::memcmp(&c.vals[at], &want, 4) == 0 || (std::isnan(c.vals[at]) && std::isnan(want)));
+            if (!same) {
+                if (bad < 16) std::fprintf(stderr, "[row %lld] cpu: (%d, %g), gpu: (%d, %g)\n", (long long)i, e.first, want, c.col_idx[at], c.vals[at]);
+                ++bad;
+            }
+            ++at;
+        }
+    }
+    if (!out.empty()) {
+        FILE *f = std::fopen(out.c_str(), "w");
+        if (!f) { std::fprintf(stderr, "error: cannot write %s\n", out.c_str()); return 2; }
+        std::fprintf(f, "%%%%MatrixMarket matrix coordinate real general\n%lld %lld %lld\n", (long long)rows, (long long)cols, (long long)nnz);
+        for (int64_t i = 0; i < rows; ++i)
+            for (int32_t k = c.row_ptr[i]; k < c.row_ptr[i + 1]; ++k) std::fprintf(f, "%lld %d %.9g\n", (long long)i + 1, c.col_idx[k] + 1, c.vals[k]);
+        if (std::fclose(f) != 0) { std::fprintf(stderr, "error: cannot write %s\n", out.c_str()); return 2; }
+    }
+    std::printf(bad ? "====== %lld MISMATCHES ======\n" : "========== OK ===========\n", (long long)bad);
+    return bad ? 1 : 0;
+}
+
 static int run_file(int argc, char **argv)
 {
-    std::string mtx, bin, out, save, spgemm_b, vname = "tiled";
+    std::string mtx, bin, out, save, spgemm_b, add_b, add_op = "union", vname = "tiled";
+    float alpha = 1.0f, beta = 1.0f;
     bool parse_only = false, transpose = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -92,6 +157,10 @@ static int run_file(int argc, char **argv)
         else if (a == "--parse-only") parse_only = true;
         else if (a == "--transpose") transpose = true;
         else if (a == "--spgemm") spgemm_b = next();
+        else if (a == "--add") add_b = next();
+        else if (a == "--alpha") alpha = std::strtof(next().c_str(), nullptr);
+        else if (a == "--beta") beta = std::strtof(next().c_str(), nullptr);
+        else if (a == "--op") add_op = next();
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     HostCsr m;
@@ -101,6 +170,11 @@ static int run_file(int argc, char **argv)
     if (!save.empty() && !(err = write_csr_binary(save, m)).empty()) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
     if (parse_only) return 0;
     if (!spgemm_b.empty()) return run_spgemm(m, spgemm_b, out);
+    if (!add_b.empty()) {
+        const int op = add_op == "union" ? SPMV_ADD_UNION : add_op == "intersect" ? SPMV_ADD_INTERSECT : add_op == "minus" ? SPMV_ADD_MINUS : -1;
+        if (op < 0) { std::fprintf(stderr, "unknown op %s (union, intersect or minus)\n", add_op.c_str()); return 2; }
+        return run_add(m, add_b, alpha, beta, op, out);
+    }
     const int variant = variant_by_name(vname);
     if (variant < 0) { std::fprintf(stderr, "unknown variant %s\n", vname.c_str()); return 2; }
 

@@ -153,6 +153,38 @@ def topk_pattern(A, Q, K, k: int, scale: float = 1.0):
     return row_ptr, col_idx
 
 
+def _combined_pattern(who: str, A, B, op: str):
+    for name, m in (("A", A), ("B", B)):
+        if not isinstance(m, capi.CsrMatrix):
+            raise ValueError(f"{who}: {name} must be a capi.CsrMatrix")
+    if (A.rows, A.cols) != (B.rows, B.cols):
+        raise ValueError(f"{who}: A is {A.rows} x {A.cols}, B is {B.rows} x {B.cols}")
+    c = A.add(B, 0.0, 0.0, op)                      # (coefficients of 0: the patterns alone, no value of A or B is read)
+    try:
+        dev = torch.device("cuda", torch.cuda.current_device())
+        row_ptr = torch.empty(c.rows + 1, dtype=torch.int32, device=dev)
+        col_idx = torch.empty(c.nnz, dtype=torch.int32, device=dev)
+        c.copy_arrays(row_ptr, col_idx)
+        torch.cuda.current_stream().synchronize()      # the copies read c's arrays, which close() frees
+    finally:
+        c.close()
+    return row_ptr, col_idx
+
+
+def union_pattern(A, B):
+    """The union of two patterns of queries x keys (capi.CsrMatrix handles of one shape; spmv_csr_add with SPMV_ADD_UNION):
+    a local band with the per-row top-k of :func:`topk_pattern` with a few global columns, two at a time.  Returns ``(row_ptr,
+    col_idx)`` as fresh int32 device tensors with sorted, duplicate-free rows, ready for ``FusedSparseAttention``.  No value
+    of A or B is read."""
+    return _combined_pattern("union_pattern", A, B, "union")
+
+
+def mask_pattern(A, M):
+    """The positions of A that M has too (spmv_csr_add with SPMV_ADD_INTERSECT): a candidate pattern under a causal or block
+    mask.  Returns ``(row_ptr, col_idx)`` as :func:`union_pattern` does."""
+    return _combined_pattern("mask_pattern", A, M, "intersect")
+
+
 def _fused_operand(t, name: str, rows: int, k=None):
     """A 2-D operand as _operand takes it, or (heads, rows, k): every head t[h] must itself be acceptable to the library
     (a column block of a (rows, heads * k) tensor with k % 4 == 0 is); otherwise the whole tensor is copied once into

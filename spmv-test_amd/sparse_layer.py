@@ -142,9 +142,60 @@ class SparseLayer:
         vals.requires_grad_(self.vals.requires_grad)
         return SparseLayer(rows, cols, row_ptr, col_idx, vals, k_max=self.k_max)
 
+    def _on_sum(self, c) -> "SparseLayer":
+        """A new layer on fresh copies of the arrays of the sum handle ``c`` (vals a fresh leaf, requires_grad as this layer's)."""
+        dev = self.vals.device
+        row_ptr = torch.empty(c.rows + 1, dtype=torch.int32, device=dev)
+        col_idx = torch.empty(c.nnz, dtype=torch.int32, device=dev)
+        vals = torch.empty(c.nnz, dtype=torch.float32, device=dev)
+        c.copy_arrays(row_ptr, col_idx, vals)
+        torch.cuda.current_stream().synchronize()      # the copies are done before the sum's arrays may be freed
+        vals.requires_grad_(self.vals.requires_grad)
+        return SparseLayer(c.rows, c.cols, row_ptr, col_idx, vals, k_max=self.k_max)
+
+    def grown(self, row_ptr, col_idx) -> "SparseLayer":
+        """A new SparseLayer on the union of this layer's pattern with the given one (int32 device tensors of rows + 1 and of
+        nnz' elements; spmv_csr_add(A, G, 1, 0, SPMV_ADD_UNION)): the counterpart of :meth:`pruned`.  The old values are carried
+        bit for bit (this layer's rows must be free of repeated columns for that: a repeated column's values are added), the
+        new positions start at +0, the rows come out sorted.  Its ``vals`` is a fresh leaf (requires_grad as the parent's);
+        ``.growth`` is the sum handle with its plan, so optimizer state follows: ``new.growth.add_values(old.A, G, 1, 0)`` with
+        a handle on the state in place of the values, or ``new.growth.add_gather(0, new_state, old_state)`` back.  The parent
+        layer is untouched."""
+        for name, t in (("row_ptr", row_ptr), ("col_idx", col_idx)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() \
+                    or t.device != self.vals.device:
+                raise ValueError(f"SparseLayer.grown: {name} must be a contiguous 1-D int32 tensor on {self.vals.device}")
+        if row_ptr.numel() != self.A.rows + 1:
+            raise ValueError(f"SparseLayer.grown: row_ptr holds {row_ptr.numel()} elements, the layer has {self.A.rows} rows")
+        zeros = torch.zeros(col_idx.numel(), dtype=torch.float32, device=self.vals.device)
+        G = capi.CsrMatrix.from_device(self.A.rows, self.A.cols, row_ptr, col_idx, zeros)
+        try:
+            growth = self.A.add(G, 1.0, 0.0, "union", keep_plan=True)
+        finally:
+            G.close()
+        layer = self._on_sum(growth)
+        layer.growth = growth
+        return layer
+
+    def summed(self, other: "SparseLayer", alpha: float = 1.0, beta: float = 1.0) -> "SparseLayer":
+        """A new SparseLayer on ``alpha * self.A + beta * other.A`` (spmv_csr_add on the union of the two patterns), so that
+        ``new(X)`` approximates ``alpha * self(X) + beta * other(X)``; the sums are taken in another order, so the bits differ.
+        Its arrays are fresh device tensors and its ``vals`` a fresh leaf (requires_grad as this layer's); ``k_max`` is this
+        layer's.  No gradient flows to the parents, which are untouched."""
+        if not isinstance(other, SparseLayer):
+            raise ValueError("SparseLayer.summed: other must be a SparseLayer")
+        if (self.A.rows, self.A.cols) != (other.A.rows, other.A.cols):
+            raise ValueError(f"SparseLayer.summed: self is {self.A.rows} x {self.A.cols}, other is {other.A.rows} x {other.A.cols}")
+        c = self.A.add(other.A, alpha, beta, "union")
+        try:
+            return self._on_sum(c)
+        finally:
+            c.close()
+
     def close(self) -> None:
-        sel = getattr(self, "selection", None)
-        if sel is not None:
-            sel.close()
+        for name in ("selection", "growth"):
+            h = getattr(self, name, None)
+            if h is not None:
+                h.close()
         self.T.close()
         self.A.close()
