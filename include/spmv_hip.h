@@ -204,7 +204,8 @@ SPMV_API int spmv_csr_destroy(spmv_csr_t *h);
  * and then does for t what spmv_csr_values_changed(t) does: the plans of t that read vals live (SPMV_SCALAR ... SPMV_TILED,
  * SpMM) use the new values on their next run, the plans that hold a copy (SPMV_PANEL, SPMV_XSKIP, SPMV_AUTO where it
  * resolved to one of them) answer SPMV_ERR_STALE_PLAN until re-planned.  On a handle without a map (keep_map = 0, or not
- * made by spmv_csr_transpose): SPMV_ERR_INVALID, nothing launched.
+ * made by spmv_csr_transpose): SPMV_ERR_INVALID, nothing launched.  `a` must not be t itself (t's values would be read while
+ * they are written): SPMV_ERR_INVALID, nothing launched.
  *
  * spmv_csr_transpose_gather: dst[c * dst_stride + i] = src[c * src_stride + map[i]] for c < count, i < nnz, through the map of
  * a handle made with keep_map = 1: `count` arrays of nnz 32-bit words in the parent's storage order brought into t's, copied
@@ -265,7 +266,8 @@ SPMV_API int64_t spmv_csr_transpose_map_bytes(const spmv_csr_t *t);
  *
  * spmv_csr_select_values: s.vals[m] = a.vals[map[m]] for a handle made with keep_map = 1, then what
  * spmv_csr_values_changed(s) does (see spmv_csr_transpose_values).  `a` must have s's shape, the nnz of s's parent (the
- * handle records it) and live on s's device; that it still has the parent's PATTERN is the caller's promise.
+ * handle records it) and live on s's device; that it still has the parent's PATTERN is the caller's promise.  `a` must not
+ * be s itself (s's values would be read while they are written): SPMV_ERR_INVALID, nothing launched.
  *
  * spmv_csr_select_gather:  dst[c * dst_stride + m] = src[c * src_stride + map[m]]
  * spmv_csr_select_scatter: dst[c * dst_stride + map[m]] = src[c * src_stride + m]; every other word of dst is left
@@ -344,8 +346,9 @@ SPMV_API int spmv_csr_copy_arrays(const spmv_csr_t *h, int32_t *d_row_ptr, int32
  * graph-capturable.  Afterwards it does for c what spmv_csr_values_changed(c) does (see spmv_csr_transpose_values).  a must
  * be c.rows x n and b n x c.cols with the nnz of c's parents (the handle records n and both) on c's device, else
  * SPMV_ERR_INVALID; that their PATTERNS are unchanged is the caller's promise.  On a handle without a plan (keep_plan = 0,
- * or not made by spmv_csr_spgemm): SPMV_ERR_INVALID, nothing launched.  A product handle carries no transpose or select
- * map: those companions refuse it. */
+ * or not made by spmv_csr_spgemm): SPMV_ERR_INVALID, nothing launched.  Neither a nor b may be c itself (c's values would be
+ * read while they are written): SPMV_ERR_INVALID, nothing launched; a == b stays allowed.  A product handle carries no
+ * transpose or select map: those companions refuse it. */
 #define SPMV_SPGEMM_CLASS_SLOTS 64, 512, 4096, 32768   /* words of LDS per row of each class, ascending */
 SPMV_API int spmv_csr_spgemm(const spmv_csr_t *a, const spmv_csr_t *b, int keep_plan, void *stream, spmv_csr_t **out,
                              int64_t *products /* may be NULL */);
@@ -404,6 +407,8 @@ SPMV_API int64_t spmv_csr_spgemm_plan_bytes(const spmv_csr_t *c);
  * waits: graph-capturable.  Afterwards it does for c what spmv_csr_values_changed(c) does (see spmv_csr_transpose_values).  a
  * and b must have c's shape and the nnz of c's parents (the handle records both) on c's device, else SPMV_ERR_INVALID; that
  * their PATTERNS are unchanged is the caller's promise.  On a handle without a plan: SPMV_ERR_INVALID, nothing launched.
+ * Neither a nor b may be c itself (c's values would be read while they are written): SPMV_ERR_INVALID, nothing launched; a == b
+ * stays allowed.
  *
  * spmv_csr_add_gather: dst[k * dst_stride + p] = src[k * src_stride + e] for every kept term at storage position p of the
  * chosen side (0: a, 1: b) whose entry of C is e, for k < count: 32-bit words copied as bits; every other word of dst is left

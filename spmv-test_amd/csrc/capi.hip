@@ -394,6 +394,10 @@ int spmv_csr_transpose_values(spmv_csr_t *t, const spmv_csr_t *a, void *stream)
         set_error("spmv_csr_transpose_values: the handle has no map (it was not made by spmv_csr_transpose with keep_map = 1)");
         return SPMV_ERR_INVALID;
     }
+    if (a == t) {
+        set_error("spmv_csr_transpose_values: a is t itself (t's values would be read while they are written)");
+        return SPMV_ERR_INVALID;
+    }
     if (a->rows != t->cols || a->cols != t->rows || a->nnz != t->nnz) {
         set_error("spmv_csr_transpose_values: a is %lld x %lld with %lld nonzeros, the transpose of t would be %lld x %lld with %lld",
                   (long long)a->rows, (long long)a->cols, (long long)a->nnz, (long long)t->cols, (long long)t->rows,
@@ -486,6 +490,7 @@ int spmv_csr_select_values(spmv_csr_t *s, const spmv_csr_t *a, void *stream)
         set_error("%s: the handle has no map (it was not made by a spmv_csr_select call with keep_map = 1)", what);
         return SPMV_ERR_INVALID;
     }
+    if (a == s) { set_error("%s: a is s itself (s's values would be read while they are written)", what); return SPMV_ERR_INVALID; }
     if (a->rows != s->rows || a->cols != s->cols || a->nnz != s->select_parent_nnz) {
         set_error("%s: a is %lld x %lld with %lld nonzeros, s was selected from %lld x %lld with %lld", what, (long long)a->rows,
                   (long long)a->cols, (long long)a->nnz, (long long)s->rows, (long long)s->cols, (long long)s->select_parent_nnz);
@@ -595,6 +600,10 @@ int spmv_csr_spgemm_values(spmv_csr_t *c, const spmv_csr_t *a, const spmv_csr_t 
         set_error("%s: the handle has no plan (it was not made by spmv_csr_spgemm with keep_plan = 1)", what);
         return SPMV_ERR_INVALID;
     }
+    if (a == c || b == c) {
+        set_error("%s: %s is c itself (c's values would be read while they are written)", what, a == c ? "a" : "b");
+        return SPMV_ERR_INVALID;
+    }
     if (a->rows != c->rows || a->cols != p.inner || b->rows != p.inner || b->cols != c->cols || a->nnz != p.a_nnz || b->nnz != p.b_nnz) {
         set_error("%s: a is %lld x %lld with %lld nonzeros and b %lld x %lld with %lld, c was made from %lld x %lld with %lld and "
                   "%lld x %lld with %lld", what, (long long)a->rows, (long long)a->cols, (long long)a->nnz, (long long)b->rows,
@@ -649,6 +658,10 @@ int spmv_csr_add_values(spmv_csr_t *c, const spmv_csr_t *a, const spmv_csr_t *b,
     const AddPlan &p = c->plan_add;
     if (!p.ready || !c->own_vals) {
         set_error("%s: the handle has no plan (it was not made by spmv_csr_add with keep_plan = 1)", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (a == c || b == c) {
+        set_error("%s: %s is c itself (c's values would be read while they are written)", what, a == c ? "a" : "b");
         return SPMV_ERR_INVALID;
     }
     if (a->rows != c->rows || a->cols != c->cols || b->rows != c->rows || b->cols != c->cols || a->nnz != p.a_nnz || b->nnz != p.b_nnz) {

@@ -287,14 +287,16 @@ __global__ __launch_bounds__(kBlock) void k_cb_sort(const int32_t *__restrict__ 
 //   units [0, usimple[b])            the groups: slot = unit*256 + lane*4 + (group & 3)
 //   units [usimple[b], uend[b]-ubeg) the tail, same slot map, so that one instruction holds 64 CONSECUTIVE tail nonzeros:
 //                                    runs of equal rows, folded by a segmented scan at run time
-// A block that runs out of units (cannot happen with the long rows taken out, short of adversarial input) becomes all tail.
+// A block that runs out of units (cannot happen with the long rows taken out, short of adversarial input) becomes all tail,
+// and so does a block with all_tail[b] set: one whose units k_cb_pack found too wide for a column offset (a tail unit stores
+// whole columns).
 __global__ __launch_bounds__(kWave) void k_cb_groups(const int32_t *__restrict__ brow, const int32_t *__restrict__ row_ptr,
                                                      const int32_t *__restrict__ ubeg, const int32_t *__restrict__ nshort,
                                                      int32_t *__restrict__ t_col, uint16_t *__restrict__ t_row,
                                                      float *__restrict__ t_val, int32_t *__restrict__ o_col,
                                                      uint16_t *__restrict__ o_row, float *__restrict__ o_val,
                                                      int32_t *__restrict__ usimple, int32_t *__restrict__ uend,
-                                                     unsigned long long *__restrict__ stats)
+                                                     unsigned long long *__restrict__ stats, const int32_t *__restrict__ all_tail)
 {
     __shared__ int tag[kCbRowsMax];   // grouping: who holds a row in this round; afterwards: the counters of the tail sort
     __shared__ int q_col[kWave];      // the nonzeros that wait for the next group
@@ -319,7 +321,7 @@ __global__ __launch_bounds__(kWave) void k_cb_groups(const int32_t *__restrict__
     int front = 0, back = cap, pos = 0, qn = 0, round = 0;
     int c_col = 0, c_row = 0;
     float c_val = 0.0f;
-    bool failed = false;
+    bool failed = all_tail[b] != 0;   // block-uniform
     // One GROUP per trip: 64 candidates -- first the ones that waited (low lanes), then the next of the sorted stream.  The
     // lowest lane that holds a row wins it (atomicMax of a key that grows with the round and falls with the lane); the
     // others wait for the next group, at most kCbQueue of them -- more are set aside for the tail.
@@ -327,7 +329,7 @@ __global__ __launch_bounds__(kWave) void k_cb_groups(const int32_t *__restrict__
     // No faster -- the add chain is not what bounds the kernel -- and in a narrow band, where 256 neighbours in column
     // order sit on two lines of x, most of the block ends up waiting.)
     int loaded = 0;   // nonzeros of the stream in the ring so far: [pos, loaded) are waiting there
-    while (pos < ns || qn > 0) {
+    while (!failed && (pos < ns || qn > 0)) {
         if (loaded - pos < 2 * kWave && loaded < ns) {   // wave-uniform: refill (the slots of [pos - ..., pos) are free)
             int rc_[kBuf / 2 / kWave], rr_[kBuf / 2 / kWave];
             float rv_[kBuf / 2 / kWave];
@@ -457,14 +459,15 @@ __global__ void k_cb_tail_units(int nblocks, const int32_t *__restrict__ ubeg, c
 
 // Step 3: one wavefront per unit, o_col rewritten in place as packed:
 //   a unit of groups:  ubase = smallest column of the unit, packed = row << 19 | column - ubase, empty slots = the lane's
-//                      dummy row (fail |= 2 when the unit spans 2^19 columns or more);
+//                      dummy row (when the unit spans 2^19 columns or more: fail |= 2 and all_tail[its block] = 1);
 //   a tail unit:       packed = the column itself (a long row's last nonzeros and the next row's first ones can lie a whole
 //                      band apart), ubase = 0, the rows go to trow[] (0xFFFF = empty slot), compact over the tail units.
 __global__ __launch_bounds__(kBlock) void k_cb_pack(int64_t units, int rows_cap, int nblocks, const int32_t *__restrict__ ubeg,
                                                     const int32_t *__restrict__ usimple, const int32_t *__restrict__ uend,
                                                     const int32_t *__restrict__ tbeg, uint32_t *__restrict__ packed,
                                                     const uint16_t *__restrict__ o_row, int32_t *__restrict__ ubase,
-                                                    uint16_t *__restrict__ trow, int32_t *__restrict__ fail)
+                                                    uint16_t *__restrict__ trow, int32_t *__restrict__ fail,
+                                                    int32_t *__restrict__ all_tail)
 {
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t u = (int64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
@@ -505,7 +508,10 @@ __global__ __launch_bounds__(kBlock) void k_cb_pack(int64_t units, int rows_cap,
     }
     if (mx < 0) mn = 0;   // an empty unit
     const int colbits = cb_colbits(rows_cap);
-    if (mx >= 0 && mx - mn >= (1 << colbits) && lane == 0) atomicOr(fail, 2);
+    if (mx >= 0 && mx - mn >= (1 << colbits) && lane == 0) {
+        atomicOr(fail, 2);
+        all_tail[b] = 1;
+    }
 #pragma unroll
     for (int q = 0; q < 4; ++q)
         c[q] = r4[q] != 0xFFFFu ? ((unsigned)r4[q] << colbits) | (unsigned)((int)c[q] - mn)
@@ -734,8 +740,6 @@ static int build_colsort(spmv_csr &h, SortedBlocksPlan &p, int rows_cap, hipStre
     SPMV_HIP_TRY(nshort.alloc((size_t)p.nblocks));
     SPMV_HIP_TRY(fail.alloc(1));
     SPMV_HIP_TRY(stats.alloc(3));
-    SPMV_HIP_TRY(hipMemsetAsync(fail.get(), 0, sizeof(int32_t), s));
-    SPMV_HIP_TRY(hipMemsetAsync(stats.get(), 0, 3 * sizeof(unsigned long long), s));
     const unsigned gb = (unsigned)((p.nblocks + 255) / 256);
     k_cb_units<<<dim3(gb), dim3(256), 0, s>>>(p.nblocks, p.d_brow.get(), h.d_row_ptr, p.d_ubeg.get());
     if ((rc = check_launch("k_cb_units"))) return rc;
@@ -754,9 +758,11 @@ static int build_colsort(spmv_csr &h, SortedBlocksPlan &p, int rows_cap, hipStre
     SPMV_HIP_TRY(t_col.alloc((size_t)h.nnz));
     SPMV_HIP_TRY(t_row.alloc((size_t)h.nnz));
     SPMV_HIP_TRY(t_val.alloc((size_t)h.nnz));
-    SPMV_HIP_TRY(hipMemsetAsync(p.d_packed.get(), 0, sizeof(uint32_t) * slots, s));
-    SPMV_HIP_TRY(hipMemsetAsync(p.d_pvals.get(), 0, sizeof(float) * slots, s));
-    SPMV_HIP_TRY(hipMemsetAsync(o_row.get(), 0xFF, sizeof(uint16_t) * slots, s));
+    // blocks whose units come out too wide for a column offset are laid out again as all tail: at most two passes
+    DevPtr<int32_t> all_tail;
+    SPMV_HIP_TRY(all_tail.alloc((size_t)p.nblocks));
+    SPMV_HIP_TRY(hipMemsetAsync(all_tail.get(), 0, sizeof(int32_t) * (size_t)p.nblocks, s));
+    int nbins = 1024;
     if (h.nnz > 0) {
         if ((rc = panel_rowloc(h, p.d_brow.get(), p.nblocks, rowloc.get(), s))) return rc;
         // counters for the widest block at 32 columns each (wider blocks than kCbBins counters reach use coarser bins)
@@ -766,41 +772,52 @@ static int build_colsort(spmv_csr &h, SortedBlocksPlan &p, int rows_cap, hipStre
         if ((rc = check_launch("k_cb_span"))) return rc;
         SPMV_HIP_TRY(hipMemcpyAsync(&widest, total.get(), sizeof widest, hipMemcpyDeviceToHost, s));
         SPMV_HIP_TRY(hipStreamSynchronize(s));
-        int nbins = 1024;
         while (nbins < kCbBins && (widest >> 5) >= nbins) nbins <<= 1;
-        const size_t lds = sizeof(int) * (size_t)nbins;
         static LdsOptIn optin;
         if ((rc = optin.ensure(reinterpret_cast<const void *>(&k_cb_sort), h.device, (int)(sizeof(int) * (size_t)kCbBins)))) return rc;
-        k_cb_sort<<<dim3((unsigned)p.nblocks), dim3(kBlock), lds, s>>>(p.d_brow.get(), h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.get(),
-                                                                        t_col.get(), t_row.get(), t_val.get(), nshort.get(), stats.get(), nbins);
-        if ((rc = check_launch("k_cb_sort"))) return rc;
-        k_cb_groups<<<dim3((unsigned)p.nblocks), dim3(kWave), 0, s>>>(p.d_brow.get(), h.d_row_ptr, p.d_ubeg.get(), nshort.get(), t_col.get(), t_row.get(),
-                                                                       t_val.get(), reinterpret_cast<int32_t *>(p.d_packed.get()), o_row.get(),
-                                                                       p.d_pvals.get(), p.d_usimple.get(), p.d_uend.get(), stats.get());
-        if ((rc = check_launch("k_cb_groups"))) return rc;
-    } else {
-        SPMV_HIP_TRY(hipMemsetAsync(p.d_usimple.get(), 0, sizeof(int32_t) * (size_t)p.nblocks, s));
-        SPMV_HIP_TRY(hipMemcpyAsync(p.d_uend.get(), p.d_ubeg.get(), sizeof(int32_t) * (size_t)p.nblocks, hipMemcpyDeviceToDevice, s));   // no units in use
     }
-    // the rows of the tail units, compact: tbeg[b] = the block's first unit in trow
-    DevPtr<int32_t> ttotal;
-    SPMV_HIP_TRY(p.d_tbeg.alloc((size_t)p.nblocks));
-    SPMV_HIP_TRY(ttotal.alloc(1));
-    k_cb_tail_units<<<dim3(gb), dim3(256), 0, s>>>(p.nblocks, p.d_ubeg.get(), p.d_usimple.get(), p.d_uend.get(), p.d_tbeg.get());
-    if ((rc = check_launch("k_cb_tail_units"))) return rc;
-    int32_t tunits = 0;
-    if ((rc = scan_offsets_i32(p.d_tbeg.get(), p.nblocks, ttotal.get(), false, s, &tunits))) return rc;
-    p.tail_units = tunits;
-    SPMV_HIP_TRY(p.d_trow.alloc((size_t)tunits * kCbUnit));
-    k_cb_pack<<<dim3((unsigned)((units + 3) / 4)), dim3(kBlock), 0, s>>>((int64_t)units, rows_cap, p.nblocks, p.d_ubeg.get(), p.d_usimple.get(), p.d_uend.get(),
-                                                                         p.d_tbeg.get(), p.d_packed.get(), o_row.get(), p.d_ubase.get(), p.d_trow.get(), fail.get());
-    if ((rc = check_launch("k_cb_pack"))) return rc;
     int32_t failed = 0;
     unsigned long long st[3] = {0, 0, 0};
-    SPMV_HIP_TRY(hipMemcpyAsync(&failed, fail.get(), sizeof failed, hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipMemcpyAsync(st, stats.get(), sizeof st, hipMemcpyDeviceToHost, s));
-    SPMV_HIP_TRY(hipStreamSynchronize(s));   // (the temporaries are freed on return)
-    if (failed) {
+    for (int pass = 0; pass < 2; ++pass) {
+        SPMV_HIP_TRY(hipMemsetAsync(fail.get(), 0, sizeof(int32_t), s));
+        SPMV_HIP_TRY(hipMemsetAsync(stats.get(), 0, 3 * sizeof(unsigned long long), s));
+        SPMV_HIP_TRY(hipMemsetAsync(p.d_packed.get(), 0, sizeof(uint32_t) * slots, s));
+        SPMV_HIP_TRY(hipMemsetAsync(p.d_pvals.get(), 0, sizeof(float) * slots, s));
+        SPMV_HIP_TRY(hipMemsetAsync(o_row.get(), 0xFF, sizeof(uint16_t) * slots, s));
+        if (h.nnz > 0) {
+            const size_t lds = sizeof(int) * (size_t)nbins;
+            k_cb_sort<<<dim3((unsigned)p.nblocks), dim3(kBlock), lds, s>>>(p.d_brow.get(), h.d_row_ptr, h.d_col_idx, h.d_vals, rowloc.get(),
+                                                                            t_col.get(), t_row.get(), t_val.get(), nshort.get(), stats.get(), nbins);
+            if ((rc = check_launch("k_cb_sort"))) return rc;
+            k_cb_groups<<<dim3((unsigned)p.nblocks), dim3(kWave), 0, s>>>(p.d_brow.get(), h.d_row_ptr, p.d_ubeg.get(), nshort.get(), t_col.get(), t_row.get(),
+                                                                           t_val.get(), reinterpret_cast<int32_t *>(p.d_packed.get()), o_row.get(),
+                                                                           p.d_pvals.get(), p.d_usimple.get(), p.d_uend.get(), stats.get(),
+                                                                           all_tail.get());
+            if ((rc = check_launch("k_cb_groups"))) return rc;
+        } else {
+            SPMV_HIP_TRY(hipMemsetAsync(p.d_usimple.get(), 0, sizeof(int32_t) * (size_t)p.nblocks, s));
+            SPMV_HIP_TRY(hipMemcpyAsync(p.d_uend.get(), p.d_ubeg.get(), sizeof(int32_t) * (size_t)p.nblocks, hipMemcpyDeviceToDevice, s));   // no units in use
+        }
+        // the rows of the tail units, compact: tbeg[b] = the block's first unit in trow
+        DevPtr<int32_t> ttotal;
+        SPMV_HIP_TRY(p.d_tbeg.alloc((size_t)p.nblocks));
+        SPMV_HIP_TRY(ttotal.alloc(1));
+        k_cb_tail_units<<<dim3(gb), dim3(256), 0, s>>>(p.nblocks, p.d_ubeg.get(), p.d_usimple.get(), p.d_uend.get(), p.d_tbeg.get());
+        if ((rc = check_launch("k_cb_tail_units"))) return rc;
+        int32_t tunits = 0;
+        if ((rc = scan_offsets_i32(p.d_tbeg.get(), p.nblocks, ttotal.get(), false, s, &tunits))) return rc;
+        p.tail_units = tunits;
+        SPMV_HIP_TRY(p.d_trow.alloc((size_t)tunits * kCbUnit));
+        k_cb_pack<<<dim3((unsigned)((units + 3) / 4)), dim3(kBlock), 0, s>>>((int64_t)units, rows_cap, p.nblocks, p.d_ubeg.get(), p.d_usimple.get(), p.d_uend.get(),
+                                                                             p.d_tbeg.get(), p.d_packed.get(), o_row.get(), p.d_ubase.get(), p.d_trow.get(), fail.get(),
+                                                                             all_tail.get());
+        if ((rc = check_launch("k_cb_pack"))) return rc;
+        SPMV_HIP_TRY(hipMemcpyAsync(&failed, fail.get(), sizeof failed, hipMemcpyDeviceToHost, s));
+        SPMV_HIP_TRY(hipMemcpyAsync(st, stats.get(), sizeof st, hipMemcpyDeviceToHost, s));
+        SPMV_HIP_TRY(hipStreamSynchronize(s));   // (the temporaries are freed on return)
+        if (!failed) break;
+    }
+    if (failed) {   // (an all-tail block has no unit with a column offset: the second pass cannot end here)
         set_error("spmv_csr_plan(panel, sorted blocks): 256 neighbouring nonzeros (in column order) of the short rows of a block of "
                   "%d rows span 2^%d columns or more -- this layout is for matrices with at least that much to share in a line of x",
                   rows_cap, cb_colbits(rows_cap));

@@ -198,22 +198,35 @@ def _exact_on_T(s, name):
 def _run_paths_on_T(pkg, monkeypatch, gpu, s, st, problems):
     """Every entry of PATHS on a fresh A.transpose() per path and problem; returns the failures and the labels that ran."""
     capi = pkg.capi
+
+    def make(arrays):
+        A = capi.CsrMatrix.from_device(s.rows, s.cols, *arrays)
+        T = A.transpose()
+        A.close()
+        return T
+
+    return _run_paths_on_handle(pkg, monkeypatch, gpu, st, [(label, _upload(gpu, s.rp, s.ci, va), x, want)
+                                                            for label, va, x, want in problems], make)
+
+
+def _run_paths_on_handle(pkg, monkeypatch, gpu, st, problems, make):
+    """Every entry of PATHS on a fresh derived handle per path and problem: make(payload) builds it, st is its structure,
+    problems = [(label, payload, x, expected y)]; returns the failures and the labels that ran."""
+    capi = pkg.capi
     failures, ran = [], set()
     for k in KNOBS:
         monkeypatch.delenv(k, raising=False)
     devs = []
-    for label, va, x, want in problems:
+    for label, payload, x, want in problems:
         d = _Dev(gpu, st, np.zeros(st.nnz, np.float32))          # (its arrays are not used: y, the guards and the cases are)
         d.add(label, x, want)
-        devs.append((d, _upload(gpu, s.rp, s.ci, va)))
+        devs.append((d, payload))
     for label, v, env, params, want_desc in PATHS:
         with monkeypatch.context() as mp:
             for k, val in env.items():
                 mp.setenv(k, val)
-            for d, arrays in devs:
-                A = capi.CsrMatrix.from_device(s.rows, s.cols, *arrays)
-                T = A.transpose()
-                A.close()
+            for d, payload in devs:
+                T = make(payload)
                 try:
                     try:
                         T.plan(v) if params is None else T.plan_set(v, params)
