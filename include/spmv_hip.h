@@ -429,6 +429,68 @@ SPMV_API int spmv_csr_add_gather(const spmv_csr_t *c, int side /* 0: a, 1: b */,
                                  void *d_dst, int64_t dst_stride, void *stream);
 SPMV_API int64_t spmv_csr_add_plan_bytes(const spmv_csr_t *c);
 
+/* ---- the triangular solve -----------------------------------------------------
+ * x = T^-1 b for the lower or the upper triangle T of a square handle, level by level: what a Gauss-Seidel or SSOR sweep and
+ * the application of an ILU / IC factor repeat.  spmv_csr_trsv_plan analyses the pattern once (on the device); spmv_csr_trsv
+ * enqueues one solve.  The contract below holds bit for bit (tests/_trsv.py states it in numpy).
+ *
+ *   Shapes.  h is square (rows == cols) and may own or borrow its arrays; rows may be unsorted and may repeat columns.  h may
+ * be a full matrix: SPMV_TRSV_LOWER reads only the entries with col <= row, SPMV_TRSV_UPPER only those with col >= row; the
+ * values of the other triangle, whatever they are, are never read into a result (the fill-mode convention of the vendor
+ * libraries).  So Gauss-Seidel runs on A's own handle.
+ *   Terms.  The terms of row i are its storage positions s, ascending, with col_idx[s] < i (UPPER: > i).  A column that
+ * repeats gives several terms.
+ *   Diagonal.  SPMV_TRSV_NON_UNIT needs exactly one storage position with col_idx[s] == i in every row; the plan records the
+ * first row with none or several, and a NON_UNIT solve on such a plan is refused (the message names the row; nothing is
+ * launched).  Under SPMV_TRSV_UNIT diagonal entries are ignored: a stored NaN there changes nothing.  A diagonal whose VALUE
+ * is 0 is no error: the result follows IEEE rules.
+ *   Values.  For the n terms t_0 .. t_(n-1) of a row (value v_t, column c_t): n <= SPMV_TRSV_SERIAL_MAX: s = +0, then
+ * s = fma(v_t, x[c_t], s) in term order.  Larger n: 64 chains, chain l over the terms l, l + 64, ... by the same fma from
+ * +0; then p[l] += p[l + w] for l < w, for w = 32, 16, 8, 4, 2, 1, and s = p[0].  Then x_i = fl(fl(b_i - s) / d_i), under
+ * UNIT x_i = fl(b_i - s); the division is the correctly rounded one.  NaN, Inf, -0 and subnormals follow IEEE rules.
+ *   Purity.  x is a pure function of the three arrays, b, uplo and diag: it does not depend on thin_rows, on how levels were
+ * merged into launches, on the stream or on a second handle of the same arrays.  Values are read live at every solve and the
+ * plan is a function of the pattern alone: a borrowed vals rewritten between two solves needs no new plan.  No atomic, no
+ * flag, no grid barrier and no cooperative launch is on the solve path: the only waits are kernel boundaries and the
+ * workgroup barrier, and every loop bound comes from the plan.
+ *   Aliasing.  d_x == d_b is allowed (in place); any other overlap is the caller's error.
+ *   The plan.  level[i] = 0 for a row without terms, else 1 + the largest level among its terms' columns.  `order` lists the
+ * rows by (level, row) ascending and `level_ptr` where each level starts (spmv_csr_trsv_plan_rows returns exactly these,
+ * level_ptr[levels + 1] and order[rows], to host arrays).  A level of more than thin_rows rows is one grid launch; a maximal
+ * run of consecutive levels of at most thin_rows rows each is one launch of ONE workgroup, which walks the run with a
+ * workgroup barrier between levels; a run is cut every SPMV_TRSV_LEVEL_CAP levels.  thin_rows = 0 takes
+ * SPMV_TRSV_THIN_DEFAULT.  A handle keeps one plan per uplo; planning again replaces it.  The call allocates, enqueues on
+ * `stream` and waits for it.
+ *   Device memory.  The plan keeps 4 rows (order) + 4 rows (the diagonal's position) + 4 (levels + 1) (level_ptr) + 4 (rows
+ * + 1) + 4 L bytes (where the L terms of the rows of more than SPMV_TRSV_SERIAL_MAX terms are, listed by storage position):
+ * what spmv_csr_trsv_plan_bytes returns (0 without a plan; < 0: null handle).  While the plan is built the call also holds
+ * the transpose of the pattern (12 nnz + 4 (rows + 1) bytes, and while that is made the transpose's own peak) beside 16 rows
+ * + 32 bytes of term counters, levels and two frontiers; then, that transpose, the counters and the frontiers freed, the rows
+ * x levels pattern of one entry per row and its transpose (the levels kept, 8 rows + 4 more for the pattern, 4 rows for the
+ * transpose's values beside order and level_ptr, and the transpose's peak at nnz = rows).
+ *   The solve enqueues its launches (info[1] of them, one after the other on `stream`), allocates nothing and never waits:
+ * graph-capturable, and the captured graph has no parallel branches.
+ *   spmv_csr_trsv_plan_info: info[0] levels, [1] launches of one solve, [2] rows of the widest level, [3] rows of more than
+ * SPMV_TRSV_SERIAL_MAX terms, [4] the first row whose diagonal is missing or repeated (-1: none), [5] the thin threshold in
+ * force, [6] the cap of levels per merged launch, [7] 0.  spmv_csr_trsv_describe: the same as a line of text.
+ *   SPMV_ERR_INVALID (the message names the function; nothing launched or left allocated): a null handle, or a null array
+ * while rows > 0; a handle that is not square; uplo or diag outside the enums; a negative thin_rows; a solve, plan_info,
+ * plan_rows or describe without a plan for that uplo; another current device than the handle's; a pattern whose levels do
+ * not close (arrays that are no valid CSR).  rows = 0 and nnz = 0 work: with nnz = 0 and rows > 0, UNIT gives x = b and
+ * NON_UNIT is the diagonal refusal. */
+enum { SPMV_TRSV_LOWER = 0, SPMV_TRSV_UPPER = 1 };
+enum { SPMV_TRSV_NON_UNIT = 0, SPMV_TRSV_UNIT = 1 };
+#define SPMV_TRSV_SERIAL_MAX 32     /* terms of a row summed as one chain; see Values */
+#define SPMV_TRSV_THIN_DEFAULT 256  /* thin_rows = 0: levels of at most this many rows are merged into one-workgroup launches */
+#define SPMV_TRSV_LEVEL_CAP 1024    /* levels of one merged launch at the most */
+SPMV_API int spmv_csr_trsv_plan(spmv_csr_t *h, int uplo, int thin_rows /* 0: default */, void *stream);
+SPMV_API int spmv_csr_trsv(spmv_csr_t *h, int uplo, int diag, const float *d_b, float *d_x, void *stream);
+SPMV_API int64_t spmv_csr_trsv_plan_bytes(const spmv_csr_t *h, int uplo);
+SPMV_API int spmv_csr_trsv_plan_info(const spmv_csr_t *h, int uplo, int64_t info[8]);
+SPMV_API int spmv_csr_trsv_plan_rows(const spmv_csr_t *h, int uplo, int32_t *level_ptr /* levels + 1, host */,
+                                     int32_t *order /* rows, host */);
+SPMV_API int spmv_csr_trsv_describe(const spmv_csr_t *h, int uplo, char *buf, int n);
+
 /* ---- the hot path ------------------------------------------------------
  * spmv_csr_plan: one-off device-side preprocessing a variant needs (chunk
  * boundaries, column windows, for SPMV_TILED also a 16-bit copy of the column

@@ -72,6 +72,12 @@ SIGNATURES = {
     "spmv_csr_add_values": (C.c_int, [_H, _H, _H, C.c_float, C.c_float, _vp]),
     "spmv_csr_add_gather": (C.c_int, [_H, C.c_int, C.c_int, _vp, C.c_int64, _vp, C.c_int64, _vp]),
     "spmv_csr_add_plan_bytes": (C.c_int64, [_H]),
+    "spmv_csr_trsv_plan": (C.c_int, [_H, C.c_int, C.c_int, _vp]),
+    "spmv_csr_trsv": (C.c_int, [_H, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "spmv_csr_trsv_plan_bytes": (C.c_int64, [_H, C.c_int]),
+    "spmv_csr_trsv_plan_info": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int64)]),
+    "spmv_csr_trsv_plan_rows": (C.c_int, [_H, C.c_int, _vp, _vp]),
+    "spmv_csr_trsv_describe": (C.c_int, [_H, C.c_int, C.c_char_p, C.c_int]),
     "spmv_csr_plan": (C.c_int, [_H, C.c_int, _vp]),
     "spmv_csr_run": (C.c_int, [_H, C.c_int, _f32p, _f32p, _vp]),
     "spmv_csr_run_vals16": (C.c_int, [_H, C.c_int, C.c_int, _vp, _f32p, _f32p, _vp]),
@@ -162,6 +168,10 @@ ATTN_FP32, ATTN_BF16, ATTN_FP16 = 0, 1, 2      # enums of include/spmv_hip.h: th
 SPGEMM_CLASS_SLOTS = (64, 512, 4096, 32768)     # SPMV_SPGEMM_CLASS_SLOTS: the words of LDS a row of each class of spgemm sorts in
 ADD_UNION, ADD_INTERSECT, ADD_MINUS = 0, 1, 2   # enums of include/spmv_hip.h: the op of spmv_csr_add
 _ADD_OPS = {"union": ADD_UNION, "intersect": ADD_INTERSECT, "minus": ADD_MINUS}
+TRSV_LOWER, TRSV_UPPER = 0, 1                  # enums of include/spmv_hip.h: the uplo of spmv_csr_trsv
+TRSV_NON_UNIT, TRSV_UNIT = 0, 1                # ... and its diag
+_TRSV_UPLO = {"lower": TRSV_LOWER, "upper": TRSV_UPPER}
+SPMV_TRSV_SERIAL_MAX = 32                      # SPMV_TRSV_SERIAL_MAX: the terms of a row that trsv sums as one chain
 COLS_MAX_K = 65536                             # SPMV_COLS_MAX_K: the widest k of spmm_cols / sddmm_cols
 # CsrMatrix.spmm / spmm_cols / sddmm / sddmm_cols: (method, ATTN_* dtype of its matrices) -> (the C call, its dtype argument
 # as a tuple: the narrow fp32 calls take none).  Built here, not per call.
@@ -525,6 +535,71 @@ class CsrMatrix:
         if n < 0:
             check(n)
         return n
+
+    # -- the triangular solve (spmv_csr_trsv) ----------------------------------------------------------------------
+    @staticmethod
+    def _trsv_uplo(what: str, uplo) -> int:
+        if isinstance(uplo, str):
+            if uplo not in _TRSV_UPLO:
+                raise ValueError(f"{what}: uplo = {uplo!r} (one of {sorted(_TRSV_UPLO)})")
+            return _TRSV_UPLO[uplo]
+        if isinstance(uplo, bool) or not isinstance(uplo, int):
+            raise ValueError(f"{what}: uplo = {uplo!r}")
+        return uplo
+
+    def trsv_plan(self, uplo="lower", thin_rows: int = 0, stream=None) -> None:
+        """Analyse one triangle (``uplo``: "lower" | "upper" or a ``TRSV_*`` constant) for :meth:`trsv`: the rows by level, on
+        the device (waits for the stream).  Levels of at most ``thin_rows`` rows (0: the library's default) are merged into
+        launches of one workgroup.  The plan depends on the pattern alone; planning again replaces it."""
+        uplo = self._trsv_uplo("trsv_plan", uplo)
+        if isinstance(thin_rows, bool) or not isinstance(thin_rows, int):
+            raise ValueError(f"trsv_plan: thin_rows = {thin_rows!r}")
+        check(lib().spmv_csr_trsv_plan(self._h, uplo, thin_rows, _stream_handle(stream)))
+
+    def trsv(self, b, x=None, uplo="lower", unit: bool = False, stream=None):
+        """Enqueue ``x = T^-1 b`` for the planned triangle T of this (square) matrix; entries of the other triangle are never
+        read.  b, x: contiguous float32 device tensors of ``rows`` elements; ``x`` None makes a new one, ``x is b`` solves in
+        place.  ``unit=True`` ignores the stored diagonal.  Asynchronous, allocates nothing in the library: graph-capturable.
+        Returns x."""
+        import torch
+        uplo = self._trsv_uplo("trsv", uplo)
+        if not isinstance(unit, (bool, int)):
+            raise ValueError(f"trsv: unit = {unit!r}")
+        if x is None:
+            x = torch.empty_like(b)
+        for name, t in (("b", b), ("x", x)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous() or t.numel() < self.rows:
+                raise ValueError(f"trsv: {name} must be a contiguous 1-D float32 tensor of at least rows = {self.rows} elements")
+        check(lib().spmv_csr_trsv(self._h, uplo, TRSV_UNIT if unit else TRSV_NON_UNIT, _ptr(b), _ptr(x), _stream_handle(stream)))
+        return x
+
+    def trsv_plan_bytes(self, uplo="lower") -> int:
+        n = lib().spmv_csr_trsv_plan_bytes(self._h, self._trsv_uplo("trsv_plan_bytes", uplo))
+        if n < 0:
+            check(n)
+        return n
+
+    def trsv_plan_info(self, uplo="lower") -> dict:
+        """levels, launches of one solve, rows of the widest level, rows of more than SPMV_TRSV_SERIAL_MAX terms, the first row
+        whose diagonal is missing or repeated (-1: none), the thin threshold and the cap of levels per merged launch."""
+        info = (C.c_int64 * 8)()
+        check(lib().spmv_csr_trsv_plan_info(self._h, self._trsv_uplo("trsv_plan_info", uplo), info))
+        keys = ("levels", "launches", "widest", "long_rows", "bad_diag_row", "thin_rows", "level_cap")
+        return dict(zip(keys, (int(v) for v in info)))
+
+    def trsv_plan_rows(self, uplo="lower"):
+        """(level_ptr, order) as numpy int32 arrays: the rows by (level, row) ascending and where every level starts."""
+        import numpy as np
+        u = self._trsv_uplo("trsv_plan_rows", uplo)
+        levels = self.trsv_plan_info(u)["levels"]
+        level_ptr, order = np.empty(levels + 1, np.int32), np.empty(self.rows, np.int32)
+        check(lib().spmv_csr_trsv_plan_rows(self._h, u, _ptr(level_ptr), _ptr(order)))
+        return level_ptr, order
+
+    def trsv_describe(self, uplo="lower") -> str:
+        buf = C.create_string_buffer(256)
+        check(lib().spmv_csr_trsv_describe(self._h, self._trsv_uplo("trsv_describe", uplo), buf, len(buf)))
+        return buf.value.decode()
 
     # -- SpMM: k right-hand sides at once (spmv_csr_spmm) ---------------------------------------------------------
     def spmm_plan(self, stream=None) -> None:

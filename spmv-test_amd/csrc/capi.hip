@@ -720,6 +720,110 @@ int64_t spmv_csr_add_plan_bytes(const spmv_csr_t *c)
     return add_plan_bytes(*c);
 }
 
+// ---- the triangular solve (kernels_trsv.hip) -------------------------------------------------------------------------------
+// what every trsv entry point checks of its handle and uplo
+static int trsv_check(const spmv_csr_t *h, int uplo, const char *what)
+{
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (uplo != SPMV_TRSV_LOWER && uplo != SPMV_TRSV_UPPER) {
+        set_error("%s: uplo = %d (SPMV_TRSV_LOWER or SPMV_TRSV_UPPER)", what, uplo);
+        return SPMV_ERR_INVALID;
+    }
+    if (h->rows != h->cols) {
+        set_error("%s: the handle is %lld x %lld (a triangular solve needs a square one)", what, (long long)h->rows, (long long)h->cols);
+        return SPMV_ERR_INVALID;
+    }
+    return SPMV_OK;
+}
+
+static int trsv_planned(const spmv_csr_t *h, int uplo, const char *what)
+{
+    if (int rc = trsv_check(h, uplo, what)) return rc;
+    if (!h->plan_trsv[uplo].ready) {
+        set_error("%s: the handle has no plan for the %s triangle (spmv_csr_trsv_plan)", what, uplo == SPMV_TRSV_UPPER ? "upper" : "lower");
+        return SPMV_ERR_INVALID;
+    }
+    return SPMV_OK;
+}
+
+int spmv_csr_trsv_plan(spmv_csr_t *h, int uplo, int thin_rows, void *stream)
+{
+    const char *what = "spmv_csr_trsv_plan";
+    if (int rc = trsv_check(h, uplo, what)) return rc;
+    if (thin_rows < 0) { set_error("%s: thin_rows = %d (0: the default, or a positive number of rows)", what, thin_rows); return SPMV_ERR_INVALID; }
+    if (h->rows > 0 && (!h->d_row_ptr || (h->nnz > 0 && (!h->d_col_idx || !h->d_vals)))) {
+        set_error("%s: null array", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_device()) return rc;
+    if (int rc = require_current(h->device, what)) return rc;
+    return trsv_plan(*h, uplo == SPMV_TRSV_UPPER, thin_rows, (hipStream_t)stream);
+}
+
+int spmv_csr_trsv(spmv_csr_t *h, int uplo, int diag, const float *d_b, float *d_x, void *stream)
+{
+    const char *what = "spmv_csr_trsv";
+    if (int rc = trsv_check(h, uplo, what)) return rc;
+    if (diag != SPMV_TRSV_NON_UNIT && diag != SPMV_TRSV_UNIT) {
+        set_error("%s: diag = %d (SPMV_TRSV_NON_UNIT or SPMV_TRSV_UNIT)", what, diag);
+        return SPMV_ERR_INVALID;
+    }
+    if (h->rows > 0 && (!d_b || !d_x)) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
+    if (int rc = trsv_planned(h, uplo, what)) return rc;
+    const TrsvPlan &p = h->plan_trsv[uplo];
+    if (diag == SPMV_TRSV_NON_UNIT && p.bad_diag_row >= 0) {
+        set_error("%s: row %lld has no diagonal entry or more than one (SPMV_TRSV_NON_UNIT needs exactly one in every row)", what,
+                  (long long)p.bad_diag_row);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(h->device, what)) return rc;
+    return trsv_solve(*h, uplo == SPMV_TRSV_UPPER, diag == SPMV_TRSV_UNIT, d_b, d_x, (hipStream_t)stream);
+}
+
+int64_t spmv_csr_trsv_plan_bytes(const spmv_csr_t *h, int uplo)
+{
+    if (int rc = trsv_check(h, uplo, "spmv_csr_trsv_plan_bytes")) return rc;
+    return trsv_plan_bytes(h->plan_trsv[uplo], h->rows);
+}
+
+int spmv_csr_trsv_plan_info(const spmv_csr_t *h, int uplo, int64_t info[8])
+{
+    const char *what = "spmv_csr_trsv_plan_info";
+    if (int rc = trsv_planned(h, uplo, what)) return rc;
+    if (!info) { set_error("%s: null info", what); return SPMV_ERR_INVALID; }
+    const TrsvPlan &p = h->plan_trsv[uplo];
+    const int64_t v[8] = {p.levels, p.nsteps, p.widest, p.long_rows, p.bad_diag_row, p.thin, p.cap, 0};
+    for (int i = 0; i < 8; ++i) info[i] = v[i];
+    return SPMV_OK;
+}
+
+int spmv_csr_trsv_plan_rows(const spmv_csr_t *h, int uplo, int32_t *level_ptr, int32_t *order)
+{
+    const char *what = "spmv_csr_trsv_plan_rows";
+    if (int rc = trsv_planned(h, uplo, what)) return rc;
+    if (!level_ptr || (h->rows > 0 && !order)) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
+    if (int rc = require_current(h->device, what)) return rc;
+    const TrsvPlan &p = h->plan_trsv[uplo];
+    for (int64_t k = 0; k <= p.levels; ++k) level_ptr[k] = p.level_ptr[k];
+    if (h->rows > 0) {
+        SPMV_HIP_TRY(hipMemcpy(order, p.d_order.get(), sizeof(int32_t) * (size_t)h->rows, hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < h->rows; ++i) order[i] &= INT32_MAX;      // (bit 31: the kernels' mark of a long row)
+    }
+    return SPMV_OK;
+}
+
+int spmv_csr_trsv_describe(const spmv_csr_t *h, int uplo, char *buf, int n)
+{
+    const char *what = "spmv_csr_trsv_describe";
+    if (int rc = trsv_planned(h, uplo, what)) return rc;
+    if (!buf || n < 1) { set_error("%s: a buffer of n = %d bytes at %p", what, n, (void *)buf); return SPMV_ERR_INVALID; }
+    const TrsvPlan &p = h->plan_trsv[uplo];
+    snprintf(buf, (size_t)n, "trsv %s levels=%lld launches=%lld widest=%lld long_rows=%lld bad_diag_row=%lld thin=%d cap=%d bytes=%lld",
+             uplo == SPMV_TRSV_UPPER ? "upper" : "lower", (long long)p.levels, (long long)p.nsteps, (long long)p.widest, (long long)p.long_rows,
+             (long long)p.bad_diag_row, p.thin, p.cap, (long long)trsv_plan_bytes(p, h->rows));
+    return SPMV_OK;
+}
+
 // SPMV_AUTO.  TILED's plan is made first (cheap: a few passes over col_idx, no trial launches) and priced (model_cost,
 // in units of "a chunk that streams 8 bytes per nonzero with cache-resident gathers").
 //   1. It stages (nearly) everything in one or two passes (model_cost <= 1.20: bands up to ~60 000 columns at config 4): TILED.

@@ -289,6 +289,43 @@ struct AddPlan {
     DevPtr<int32_t> d_start;                   // [nnz + 1] the first term of every entry of c
 };
 
+// spmv_csr_trsv (kernels_trsv.hip): the rows of one triangle by level, and the launches of one solve
+struct TrsvStep {
+    int32_t first = 0, last = 0;               // the levels [first, last) of the launch
+    bool merged = false;                       // one workgroup walks them (each of at most thin_rows rows); else first + 1 == last
+};
+struct TrsvPlan {
+    bool ready = false;
+    int64_t levels = 0, widest = 0, long_rows = 0, long_terms = 0;
+    int64_t bad_diag_row = -1;                 // the first row whose diagonal is missing or repeated
+    int thin = 0, cap = 0;                     // the thin threshold and the cap of levels per merged launch in force
+    DevPtr<int32_t> d_order;                   // [rows] the rows by (level, row) ascending
+    DevPtr<int32_t> d_level_ptr;               // [levels + 1] where every level starts in d_order
+    DevPtr<int32_t> d_diag;                    // [rows] the storage position of the diagonal, -1: none
+    DevPtr<int32_t> d_lstart;                  // [rows + 1] where a long row's terms start in d_lterm (a short row: none)
+    DevPtr<uint32_t> d_lterm;                  // [long_terms] the storage positions of the long rows' terms, ascending per row
+    int32_t *level_ptr = nullptr;              // [levels + 1] the host's copy (new[]; what the steps were formed from)
+    TrsvStep *steps = nullptr;                 // [nsteps] (new[])
+    int64_t nsteps = 0;
+    TrsvPlan() = default;
+    TrsvPlan(const TrsvPlan &) = delete;
+    TrsvPlan &operator=(const TrsvPlan &) = delete;
+    TrsvPlan &operator=(TrsvPlan &&o) noexcept
+    {
+        if (this == &o) return *this;
+        delete[] level_ptr;
+        delete[] steps;
+        ready = o.ready; levels = o.levels; widest = o.widest; long_rows = o.long_rows; long_terms = o.long_terms;
+        bad_diag_row = o.bad_diag_row; thin = o.thin; cap = o.cap;
+        d_order = std::move(o.d_order); d_level_ptr = std::move(o.d_level_ptr); d_diag = std::move(o.d_diag);
+        d_lstart = std::move(o.d_lstart); d_lterm = std::move(o.d_lterm);
+        level_ptr = o.level_ptr; steps = o.steps; nsteps = o.nsteps;
+        o.level_ptr = nullptr; o.steps = nullptr; o.nsteps = 0; o.ready = false;
+        return *this;
+    }
+    ~TrsvPlan() { delete[] level_ptr; delete[] steps; }
+};
+
 }  // namespace spmv
 
 
@@ -319,6 +356,7 @@ struct spmv_csr {
     spmv::AttnPlan plan_attn;      // spmv_csr_attention_*
     spmv::SpgemmPlan plan_spgemm;  // spmv_csr_spgemm_values (a handle made by spmv_csr_spgemm with keep_plan = 1)
     spmv::AddPlan plan_add;        // spmv_csr_add_values / _gather (a handle made by spmv_csr_add with keep_plan = 1)
+    spmv::TrsvPlan plan_trsv[2];   // spmv_csr_trsv: one slot per uplo (SPMV_TRSV_LOWER, SPMV_TRSV_UPPER)
     int auto_variant = -1;         // SPMV_AUTO: the variant its plan chose (-1 = not planned)
     uint64_t values_gen = 0;       // bumped by spmv_csr_values_changed: plans that copied vals before that are stale
 };
@@ -450,6 +488,11 @@ int add(const spmv_csr &a, const spmv_csr &b, float alpha, float beta, int op, b
 int add_values(spmv_csr &c, const spmv_csr &a, const spmv_csr &b, float alpha, float beta, hipStream_t s);
 int add_gather(const spmv_csr &c, int side, int count, const void *src, int64_t src_stride, void *dst, int64_t dst_stride, hipStream_t s);
 int64_t add_plan_bytes(const spmv_csr &c);
+
+// kernels_trsv.hip: spmv_csr_trsv_plan / spmv_csr_trsv (upper: SPMV_TRSV_UPPER; unit: SPMV_TRSV_UNIT)
+int trsv_plan(spmv_csr &h, bool upper, int thin_rows, hipStream_t s);
+int trsv_solve(const spmv_csr &h, bool upper, bool unit, const float *b, float *x, hipStream_t s);
+int64_t trsv_plan_bytes(const TrsvPlan &p, int64_t rows);
 
 int dense_to_csr(int M, int N, const float *d_A, hipStream_t s, spmv_csr_t **out);
 int dense_gemv(int M, int N, const float *d_A, const float *d_x, float *d_y, int mode, hipStream_t s);

@@ -10,6 +10,9 @@
 //   sparse_sgemv --mtx A.mtx --add B.mtx [--alpha x --beta y --op union|intersect|minus] [--out C.mtx]
 //        C = alpha A + beta B through spmv_csr_add, checked against a host walk of the same chains (pattern and bits), written
 //        as a Matrix Market coordinate file
+//   sparse_sgemv --mtx A.mtx --trsv lower|upper [--unit] [--out x.txt]
+//        x = T^-1 ones for the chosen triangle of a square A through spmv_csr_trsv (the other triangle is never read), checked
+//        bit for bit against a host walk of the contract of include/spmv_hip.h "the triangular solve"
 // $SPMV_SEED makes the random inputs reproducible.
 #include <cmath>
 #include <cstdio>
@@ -19,6 +22,7 @@
 #include <map>
 #include <string>
 #include <vector>
+#include <hip/hip_runtime_api.h>
 #include "kernel.hpp"
 #include "mtx_io.hpp"
 #include "tester.hpp"
@@ -141,11 +145,74 @@ static int run_add(const HostCsr &a, const std::string &b_path, float alpha, flo
     return bad ? 1 : 0;
 }
 
+// x = T^-1 ones through the C ABI against the contract of include/spmv_hip.h "the triangular solve", walked on the host
+static int run_trsv(const HostCsr &a, bool upper, bool unit, const std::string &out)
+{
+    const int64_t n = a.rows;
+    const int uplo = upper ? SPMV_TRSV_UPPER : SPMV_TRSV_LOWER;
+    std::vector<float> b((size_t)n, 1.0f), x((size_t)n, NAN), ref((size_t)n, 0.0f);
+    spmv_csr_t *A = nullptr;
+    SPMV_CHECK(spmv_csr_create_host(a.rows, a.cols, a.nnz(), a.row_ptr.data(), a.col_idx.data(), a.vals.data(), &A));
+    SPMV_CHECK(spmv_csr_trsv_plan(A, uplo, 0, nullptr));
+    char line[256];
+    SPMV_CHECK(spmv_csr_trsv_describe(A, uplo, line, (int)sizeof line));
+    std::printf("spmv_csr_trsv: %s\n", line);
+    float *d_b = nullptr, *d_x = nullptr;
+    const size_t bytes = sizeof(float) * (size_t)(n ? n : 1);
+    if (hipMalloc((void **)&d_b, bytes) != hipSuccess || hipMalloc((void **)&d_x, bytes) != hipSuccess ||
+        hipMemcpy(d_b, b.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_x, x.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) {
+        std::fprintf(stderr, "error: no device memory for b and x\n");
+        return 2;
+    }
+    SPMV_CHECK(spmv_csr_trsv(A, uplo, unit ? SPMV_TRSV_UNIT : SPMV_TRSV_NON_UNIT, d_b, d_x, nullptr));
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(x.data(), d_x, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) {
+        std::fprintf(stderr, "error: the solve failed on the device\n");
+        return 2;
+    }
+    (void)hipFree(d_b);
+    (void)hipFree(d_x);
+    SPMV_CHECK(spmv_csr_destroy(A));
+    // the contract, row after row in dependency order (lower: ascending; upper: descending)
+    for (int64_t step = 0; step < n; ++step) {
+        const int64_t i = upper ? n - 1 - step : step;
+        std::vector<int32_t> terms;
+        float d = 1.0f;
+        for (int32_t s = a.row_ptr[i]; s < a.row_ptr[i + 1]; ++s) {
+            const int32_t c = a.col_idx[s];
+            if (c == i) { if (!unit) d = a.vals[s]; }
+            else if (upper ? c > i : c < i) terms.push_back(s);
+        }
+        float sum = 0.0f;
+        if ((int64_t)terms.size() <= SPMV_TRSV_SERIAL_MAX) {
+            for (int32_t s : terms) sum = std::fmaf(a.vals[s], ref[a.col_idx[s]], sum);
+        } else {
+            float p[64] = {};
+            for (size_t t = 0; t < terms.size(); ++t) p[t % 64] = std::fmaf(a.vals[terms[t]], ref[a.col_idx[terms[t]]], p[t % 64]);
+            for (int w = 32; w >= 1; w >>= 1)
+                for (int l = 0; l < w; ++l) p[l] += p[l + w];
+            sum = p[0];
+        }
+        const float num = b[i] - sum;
+        ref[i] = unit ? num : num / d;
+    }
+    int64_t bad = 0;
+    for (int64_t i = 0; i < n; ++i)
+        if (std::memcmp(&ref[i], &x[i], 4) != 0 && !(std::isnan(ref[i]) && std::isnan(x[i]))) {
+            if (bad < 16) std::fprintf(stderr, "[row %lld] cpu: %.9g, gpu: %.9g\n", (long long)i, ref[i], x[i]);
+            ++bad;
+        }
+    std::string err;
+    if (!out.empty() && !(err = write_vector_text(out, x)).empty()) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    std::printf(bad ? "====== %lld MISMATCHES ======\n" : "========== OK ===========\n", (long long)bad);
+    return bad ? 1 : 0;
+}
+
 static int run_file(int argc, char **argv)
 {
-    std::string mtx, bin, out, save, spgemm_b, add_b, add_op = "union", vname = "tiled";
+    std::string mtx, bin, out, save, spgemm_b, add_b, add_op = "union", trsv, vname = "tiled";
     float alpha = 1.0f, beta = 1.0f;
-    bool parse_only = false, transpose = false;
+    bool parse_only = false, transpose = false, unit = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> std::string { return i + 1 < argc ? argv[++i] : ""; };
@@ -161,6 +228,8 @@ static int run_file(int argc, char **argv)
         else if (a == "--alpha") alpha = std::strtof(next().c_str(), nullptr);
         else if (a == "--beta") beta = std::strtof(next().c_str(), nullptr);
         else if (a == "--op") add_op = next();
+        else if (a == "--trsv") trsv = next();
+        else if (a == "--unit") unit = true;
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     HostCsr m;
@@ -174,6 +243,11 @@ static int run_file(int argc, char **argv)
         const int op = add_op == "union" ? SPMV_ADD_UNION : add_op == "intersect" ? SPMV_ADD_INTERSECT : add_op == "minus" ? SPMV_ADD_MINUS : -1;
         if (op < 0) { std::fprintf(stderr, "unknown op %s (union, intersect or minus)\n", add_op.c_str()); return 2; }
         return run_add(m, add_b, alpha, beta, op, out);
+    }
+    if (!trsv.empty()) {
+        if (trsv != "lower" && trsv != "upper") { std::fprintf(stderr, "unknown triangle %s (lower or upper)\n", trsv.c_str()); return 2; }
+        if (m.rows != m.cols) { std::fprintf(stderr, "error: --trsv needs a square matrix\n"); return 2; }
+        return run_trsv(m, trsv == "upper", unit, out);
     }
     const int variant = variant_by_name(vname);
     if (variant < 0) { std::fprintf(stderr, "unknown variant %s\n", vname.c_str()); return 2; }

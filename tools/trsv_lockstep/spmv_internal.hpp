@@ -1,0 +1,104 @@
+#pragma once
+// tools/trsv_lockstep: the few names of csrc/spmv_internal.hpp that csrc/kernels_trsv.hip uses, without HIP; include/spmv_hip.h
+// is the real one, copied beside this file.  The scan and the transpose (other files of the library, with lockstep tools or GPU
+// tests of their own) are serial statements of their contracts here.
+#include <hip/hip_runtime.h>
+#include "spmv_hip.h"
+#include <cstdarg>
+#include <cstdio>
+#include <numeric>
+#include <utility>
+#define SPMV_HIP_TRY(call) do { if ((call) != hipSuccess) return SPMV_ERR_HIP; } while (0)
+namespace spmv {
+constexpr int kWave = 64; constexpr int kBlock = 256;
+inline bool g_quiet = false;             // the refusals of never-validated operands are expected: not printed
+inline void set_error(const char *f, ...) { if (g_quiet) return; va_list a; va_start(a, f); vfprintf(stderr, f, a); va_end(a); fputc('\n', stderr); }
+inline int check_launch(const char *) { return SPMV_OK; }
+inline int hip_fail(hipError_t, const char *, const char *, int) { return SPMV_ERR_HIP; }
+template <class T> struct DevPtr {       // an exactly sized heap block (an empty array: one element, as the library's)
+    T *p = nullptr;
+    DevPtr() = default;
+    DevPtr(DevPtr &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DevPtr &operator=(DevPtr &&o) noexcept { T *q = o.p; o.p = nullptr; free(p); p = q; return *this; }
+    ~DevPtr() { free(p); }
+    T *get() const { return p; }
+    operator T *() const { return p; }
+    hipError_t alloc(size_t n) { free(p); p = (T *)malloc(sizeof(T) * (n ? n : 1)); return p ? hipSuccess : 1; }
+    hipError_t reset() { free(p); p = nullptr; return hipSuccess; }
+};
+struct TrsvStep { int32_t first = 0, last = 0; bool merged = false; };
+struct TrsvPlan {
+    bool ready = false;
+    int64_t levels = 0, widest = 0, long_rows = 0, long_terms = 0, bad_diag_row = -1;
+    int thin = 0, cap = 0;
+    DevPtr<int32_t> d_order, d_level_ptr, d_diag, d_lstart;
+    DevPtr<uint32_t> d_lterm;
+    int32_t *level_ptr = nullptr;
+    TrsvStep *steps = nullptr;
+    int64_t nsteps = 0;
+    TrsvPlan() = default;
+    TrsvPlan(const TrsvPlan &) = delete;
+    TrsvPlan &operator=(const TrsvPlan &) = delete;
+    TrsvPlan &operator=(TrsvPlan &&o) noexcept
+    {
+        if (this == &o) return *this;
+        delete[] level_ptr; delete[] steps;
+        ready = o.ready; levels = o.levels; widest = o.widest; long_rows = o.long_rows; long_terms = o.long_terms;
+        bad_diag_row = o.bad_diag_row; thin = o.thin; cap = o.cap;
+        d_order = std::move(o.d_order); d_level_ptr = std::move(o.d_level_ptr); d_diag = std::move(o.d_diag);
+        d_lstart = std::move(o.d_lstart); d_lterm = std::move(o.d_lterm);
+        level_ptr = o.level_ptr; steps = o.steps; nsteps = o.nsteps;
+        o.level_ptr = nullptr; o.steps = nullptr; o.nsteps = 0; o.ready = false;
+        return *this;
+    }
+    ~TrsvPlan() { delete[] level_ptr; delete[] steps; }
+};
+}
+struct spmv_csr { int64_t rows = 0, cols = 0, nnz = 0; const int32_t *d_row_ptr = nullptr, *d_col_idx = nullptr; const float *d_vals = nullptr;
+    spmv::DevPtr<int32_t> own_row_ptr, own_col_idx; spmv::DevPtr<float> own_vals; spmv::DevPtr<uint32_t> transpose_map; int device = 0;
+    spmv::TrsvPlan plan_trsv[2]; };
+inline int spmv_csr_destroy(spmv_csr_t *h) { delete h; return SPMV_OK; }
+namespace spmv {
+// the library's scan (kernels_dense.hip), serial here: d_data[i] = sum of d_data[0 .. i), the total appended and returned
+inline int scan_offsets_i32(int32_t *d_data, int64_t n, int32_t *d_total, bool append_total, hipStream_t, int32_t *total_host)
+{
+    uint32_t run = 0;
+    for (int64_t i = 0; i < n; ++i) { const uint32_t v = (uint32_t)d_data[i]; d_data[i] = (int32_t)run; run += v; }
+    *d_total = (int32_t)run;
+    *total_host = (int32_t)run;
+    if (append_total) d_data[n] = (int32_t)run;
+    return SPMV_OK;
+}
+// the library's transpose (kernels_transpose.hip) as its header states it: a stable sort of the positions by column.  Like
+// the library's it keeps every position whatever the arrays hold and reads nothing outside them: the row of a position is
+// found by bisection, and a column out of range sorts as the unsigned number it is and counts in no row of the result.
+inline int transpose(const spmv_csr &a, bool keep_map, hipStream_t, spmv_csr_t **out)
+{
+    std::vector<int32_t> row_of((size_t)a.nnz, 0);
+    for (int64_t k = 0; k < a.nnz && a.rows > 0; ++k) {
+        int64_t lo = 0, hi = a.rows;
+        while (hi - lo > 1) { const int64_t mid = lo + (hi - lo) / 2; if ((int64_t)a.d_row_ptr[mid] <= k) lo = mid; else hi = mid; }
+        row_of[k] = (int32_t)lo;
+    }
+    std::vector<uint32_t> perm((size_t)a.nnz);
+    std::iota(perm.begin(), perm.end(), 0u);
+    std::stable_sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) { return (uint32_t)a.d_col_idx[x] < (uint32_t)a.d_col_idx[y]; });
+    spmv_csr *t = new spmv_csr();
+    t->rows = a.cols; t->cols = a.rows; t->nnz = a.nnz;
+    if (t->own_row_ptr.alloc((size_t)t->rows + 1) || t->own_col_idx.alloc(perm.size()) || t->own_vals.alloc(perm.size()) ||
+        t->transpose_map.alloc(perm.size())) { delete t; return SPMV_ERR_HIP; }
+    for (int64_t r = 0; r <= t->rows; ++r) t->own_row_ptr.get()[r] = 0;
+    for (uint32_t k : perm)
+        if (a.d_col_idx[k] >= 0 && a.d_col_idx[k] < a.cols) ++t->own_row_ptr.get()[a.d_col_idx[k] + 1];
+    for (int64_t r = 0; r < t->rows; ++r) t->own_row_ptr.get()[r + 1] += t->own_row_ptr.get()[r];
+    for (size_t i = 0; i < perm.size(); ++i) {
+        t->own_col_idx.get()[i] = row_of[perm[i]];
+        t->own_vals.get()[i] = a.d_vals[perm[i]];
+        t->transpose_map.get()[i] = perm[i];
+    }
+    t->d_row_ptr = t->own_row_ptr; t->d_col_idx = t->own_col_idx; t->d_vals = t->own_vals;
+    if (!keep_map) (void)t->transpose_map.reset();
+    *out = t;
+    return SPMV_OK;
+}
+}
