@@ -491,6 +491,57 @@ SPMV_API int spmv_csr_trsv_plan_rows(const spmv_csr_t *h, int uplo, int32_t *lev
                                      int32_t *order /* rows, host */);
 SPMV_API int spmv_csr_trsv_describe(const spmv_csr_t *h, int uplo, char *buf, int n);
 
+/* ---- the incomplete factorisation ---------------------------------------------
+ * M = ILU(0) of a square handle: the factor the triangular solve applies, made on the device.  M has a's pattern; L (unit
+ * lower, its ones not stored) and U (upper, the diagonal included) live in ONE handle, so spmv_csr_trsv LOWER / UNIT followed
+ * by UPPER / NON_UNIT on it applies (L U)^-1: that is spmv_csr_ilu0_solve.  The contract below holds bit for bit
+ * (tests/_ilu0.py states it in numpy).
+ *
+ *   Shapes.  a is square and owns or borrows its arrays.  Every row of a is strictly ascending (sorted, no repeated column)
+ * and stores its diagonal entry; otherwise SPMV_ERR_INVALID, and the message names the first offending row and which of the
+ * two rules it breaks (spmv_csr_add(A, empty, 1, 0, SPMV_ADD_UNION) sorts a matrix, spmv_csr_add(A, I, 1, 0, SPMV_ADD_UNION)
+ * gives it a diagonal).  *out owns copies of row_ptr and col_idx and its own vals; every spmv_csr_* call accepts it.  It
+ * carries both trsv plans, lower and upper, made with thin_rows (0: SPMV_TRSV_THIN_DEFAULT), and records a's rows and nnz.
+ * The call allocates, enqueues on `stream` and waits for it.  rows = 0 works.
+ *   Values.  Rows are taken in ascending i.  w starts as a copy of a's row i.  For each storage position p of row i with
+ * column k < i, ascending: (1) w[p] = fl(w[p] / M[diag_k]), the correctly rounded division, l = w[p]; (2) for each position q
+ * of row k of M with column j > k, ascending: if j is stored in row i at position r, w[r] = fma(-l, M[q], w[r]).  Row i of M
+ * is then w.  Equivalently entry (i, j) is a_ij with the terms k < min(i, j) that have (i, k) and (k, j) both stored, applied
+ * in ascending k, then divided by u_jj if j < i: which lane did the work cannot matter.  A pivot of value 0 is no error; NaN,
+ * Inf, -0 and subnormals follow IEEE rules.
+ *   Purity.  M's vals are a pure function of a's three arrays: they do not depend on thin_rows, on how levels were merged
+ * into launches, on whether a lane or a wavefront took a row (rows that store more than SPMV_ILU0_SERIAL_MAX entries take a
+ * wavefront), on the stream or on a second handle.  No atomic touches a value; no flag, no spin, no grid barrier and no
+ * cooperative launch is on the path: the only waits are kernel boundaries and the workgroup barrier, and every loop bound
+ * comes from row_ptr or the plan.
+ *   spmv_csr_ilu0_values(m, a) factors again from the values a holds now: asynchronous, allocates nothing, never waits,
+ * graph-capturable (no parallel branches).  a must have the recorded rows and nnz; an unchanged pattern is the caller's
+ * promise; a == m is refused.  A row's own lanes copy a's row into m first, so there is no copy launch: the launches are the
+ * steps of the lower plan (spmv_csr_trsv_plan_info info[1]) plus one that resets the pivot word.  Afterwards it does what
+ * spmv_csr_values_changed(m) does.
+ *   spmv_csr_ilu0_solve(m, r, z): z = U^-1 (L^-1 r), the two solves above on `stream`, the second in place; no kernel of its
+ * own, allocates nothing, graph-capturable; d_z == d_r is allowed.
+ *   spmv_csr_ilu0_pivot: the smallest row whose pivot u_ii is +-0 or not finite after the last factorisation, -1: none.  The
+ * factor kernel takes an integer minimum on one device word (independent of arrival order; it reaches no value); this call
+ * copies the word on `stream` and waits.
+ *   One map per handle, as elsewhere: a factor handle has no transpose or select map and no spgemm or add plan, so those
+ * companions (_values, _gather, _scatter) refuse it, and _ilu0_values, _solve and _pivot refuse every handle that
+ * spmv_csr_ilu0 did not make.
+ *   Device memory.  M itself: 4 (rows + 1) + 8 nnz bytes.  Beyond its three arrays the handle keeps the two trsv plans
+ * (spmv_csr_trsv_plan_bytes of each uplo) and the 4 bytes of the pivot word: what spmv_csr_ilu0_plan_bytes returns (0 for a
+ * handle that is no factor handle; < 0: null handle).  While spmv_csr_ilu0 runs it also holds 8 bytes of the check's two
+ * minima and the build peak of one trsv plan at a time (see the triangular solve), the lower one first.  _values, _solve and
+ * _pivot allocate nothing.
+ *   SPMV_ERR_INVALID (the message names the function; *out untouched, nothing left allocated): a null argument, or a null
+ * array while rows > 0; a handle that is not square; a negative thin_rows; a row that is not strictly ascending or stores no
+ * diagonal; another current device than the handle's; for _values also a == m, or an a of other rows or nnz than recorded. */
+#define SPMV_ILU0_SERIAL_MAX 32   /* stored entries of a row factored by one lane; longer rows take a wavefront */
+SPMV_API int spmv_csr_ilu0(const spmv_csr_t *a, int thin_rows /* 0: default */, void *stream, spmv_csr_t **out);
+SPMV_API int spmv_csr_ilu0_values(spmv_csr_t *m, const spmv_csr_t *a, void *stream);
+SPMV_API int spmv_csr_ilu0_solve(spmv_csr_t *m, const float *d_r, float *d_z, void *stream);      /* z = U^-1 (L^-1 r) */
+SPMV_API int spmv_csr_ilu0_pivot(const spmv_csr_t *m, void *stream, int64_t *row);                /* waits; -1: none */
+SPMV_API int64_t spmv_csr_ilu0_plan_bytes(const spmv_csr_t *m);
+
 /* ---- the hot path ------------------------------------------------------
  * spmv_csr_plan: one-off device-side preprocessing a variant needs (chunk
  * boundaries, column windows, for SPMV_TILED also a 16-bit copy of the column

@@ -8,7 +8,7 @@ workload definitions (``workloads``), the multi-GPU row-block layer on torch.dis
 the ctypes binding of the C++ one (``dist_native``: include/spmv_dist.h, RCCL called from C++), ``sparse_layer``
 (Y = A X as a torch.autograd.Function on SpMM, the transpose and SDDMM) and ``sparse_attention`` (softmax(Q K^T) V on a
 CSR pattern as a torch.autograd.Function on SDDMM, the row softmax, SpMM and the transpose) and ``solvers`` (Gauss-Seidel
-sweeps on the triangular solve).
+sweeps on the triangular solve; PCG and BiCGStab preconditioned by the ILU(0) factor of ``CsrMatrix.ilu0``).
 PyTorch is used only for device memory, streams and ``torch.distributed``.
 
 The directory name contains a hyphen, so import it through ``__graft_entry__.load_package()``,

@@ -78,6 +78,11 @@ SIGNATURES = {
     "spmv_csr_trsv_plan_info": (C.c_int, [_H, C.c_int, C.POINTER(C.c_int64)]),
     "spmv_csr_trsv_plan_rows": (C.c_int, [_H, C.c_int, _vp, _vp]),
     "spmv_csr_trsv_describe": (C.c_int, [_H, C.c_int, C.c_char_p, C.c_int]),
+    "spmv_csr_ilu0": (C.c_int, [_H, C.c_int, _vp, C.POINTER(_H)]),
+    "spmv_csr_ilu0_values": (C.c_int, [_H, _H, _vp]),
+    "spmv_csr_ilu0_solve": (C.c_int, [_H, _vp, _vp, _vp]),
+    "spmv_csr_ilu0_pivot": (C.c_int, [_H, _vp, C.POINTER(C.c_int64)]),
+    "spmv_csr_ilu0_plan_bytes": (C.c_int64, [_H]),
     "spmv_csr_plan": (C.c_int, [_H, C.c_int, _vp]),
     "spmv_csr_run": (C.c_int, [_H, C.c_int, _f32p, _f32p, _vp]),
     "spmv_csr_run_vals16": (C.c_int, [_H, C.c_int, C.c_int, _vp, _f32p, _f32p, _vp]),
@@ -172,6 +177,7 @@ TRSV_LOWER, TRSV_UPPER = 0, 1                  # enums of include/spmv_hip.h: th
 TRSV_NON_UNIT, TRSV_UNIT = 0, 1                # ... and its diag
 _TRSV_UPLO = {"lower": TRSV_LOWER, "upper": TRSV_UPPER}
 SPMV_TRSV_SERIAL_MAX = 32                      # SPMV_TRSV_SERIAL_MAX: the terms of a row that trsv sums as one chain
+SPMV_ILU0_SERIAL_MAX = 32                      # SPMV_ILU0_SERIAL_MAX: the stored entries of a row that ilu0 factors in one lane
 COLS_MAX_K = 65536                             # SPMV_COLS_MAX_K: the widest k of spmm_cols / sddmm_cols
 # CsrMatrix.spmm / spmm_cols / sddmm / sddmm_cols: (method, ATTN_* dtype of its matrices) -> (the C call, its dtype argument
 # as a tuple: the narrow fp32 calls take none).  Built here, not per call.
@@ -600,6 +606,50 @@ class CsrMatrix:
         buf = C.create_string_buffer(256)
         check(lib().spmv_csr_trsv_describe(self._h, self._trsv_uplo("trsv_describe", uplo), buf, len(buf)))
         return buf.value.decode()
+
+    # -- the incomplete factorisation (spmv_csr_ilu0) ----------------------------------------------------------------
+    def ilu0(self, thin_rows: int = 0, stream=None) -> "CsrMatrix":
+        """M = ILU(0) of this (square) matrix as a new handle that owns its arrays, built on the device (waits for the stream):
+        this matrix's pattern, L (unit lower) and U (upper) in one handle, with both ``trsv`` plans made with ``thin_rows`` (0:
+        the library's default).  Every row must be strictly ascending and store its diagonal (``add`` with an empty matrix sorts,
+        ``add`` with I gives a diagonal).  The values are the contract of include/spmv_hip.h, bit for bit."""
+        if isinstance(thin_rows, bool) or not isinstance(thin_rows, int):
+            raise ValueError(f"ilu0: thin_rows = {thin_rows!r}")
+        h = C.c_void_p()
+        check(lib().spmv_csr_ilu0(self._h, thin_rows, _stream_handle(stream), C.byref(h)))
+        return CsrMatrix(h.value)
+
+    def ilu0_values(self, a: "CsrMatrix", stream=None) -> None:
+        """Factor again (this handle was made by ``a.ilu0()``) from the values ``a`` holds now, the pattern unchanged:
+        asynchronous, allocates nothing, graph-capturable; then what :meth:`values_changed` does."""
+        if not isinstance(a, CsrMatrix):
+            raise TypeError("ilu0_values: a must be a CsrMatrix")
+        check(lib().spmv_csr_ilu0_values(self._h, a._h, _stream_handle(stream)))
+
+    def ilu0_solve(self, r, z=None, stream=None):
+        """Enqueue ``z = U^-1 (L^-1 r)`` on a factor handle: ``trsv`` lower / unit, then upper / non-unit in place.  r, z:
+        contiguous float32 device tensors of ``rows`` elements; ``z`` None makes a new one, ``z is r`` solves in place.
+        Asynchronous, allocates nothing in the library: graph-capturable.  Returns z."""
+        import torch
+        if z is None:
+            z = torch.empty_like(r)
+        for name, t in (("r", r), ("z", z)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous() or t.numel() < self.rows:
+                raise ValueError(f"ilu0_solve: {name} must be a contiguous 1-D float32 tensor of at least rows = {self.rows} elements")
+        check(lib().spmv_csr_ilu0_solve(self._h, _ptr(r), _ptr(z), _stream_handle(stream)))
+        return z
+
+    def ilu0_pivot(self, stream=None) -> int:
+        """The smallest row whose pivot u_ii is +-0 or not finite after the last factorisation, -1: none (waits for the stream)."""
+        row = C.c_int64(-2)
+        check(lib().spmv_csr_ilu0_pivot(self._h, _stream_handle(stream), C.byref(row)))
+        return row.value
+
+    def ilu0_plan_bytes(self) -> int:
+        n = lib().spmv_csr_ilu0_plan_bytes(self._h)
+        if n < 0:
+            check(n)
+        return n
 
     # -- SpMM: k right-hand sides at once (spmv_csr_spmm) ---------------------------------------------------------
     def spmm_plan(self, stream=None) -> None:

@@ -824,6 +824,83 @@ int spmv_csr_trsv_describe(const spmv_csr_t *h, int uplo, char *buf, int n)
     return SPMV_OK;
 }
 
+// ---- the incomplete factorisation (kernels_ilu0.hip) -------------------------------------------------------------------------
+// what _values, _solve and _pivot check of their handle
+static int ilu0_factor_handle(const spmv_csr_t *m, const char *what)
+{
+    if (!m) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (!m->plan_ilu0.ready || !m->own_vals || !m->plan_trsv[0].ready || !m->plan_trsv[1].ready) {
+        set_error("%s: the handle is no factor handle (it was not made by spmv_csr_ilu0)", what);
+        return SPMV_ERR_INVALID;
+    }
+    return SPMV_OK;
+}
+
+int spmv_csr_ilu0(const spmv_csr_t *a, int thin_rows, void *stream, spmv_csr_t **out)
+{
+    const char *what = "spmv_csr_ilu0";
+    if (!a || !out) { set_error("%s: null argument", what); return SPMV_ERR_INVALID; }
+    if (a->rows != a->cols) {
+        set_error("%s: the handle is %lld x %lld (a factorisation needs a square one)", what, (long long)a->rows, (long long)a->cols);
+        return SPMV_ERR_INVALID;
+    }
+    if (thin_rows < 0) { set_error("%s: thin_rows = %d (0: the default, or a positive number of rows)", what, thin_rows); return SPMV_ERR_INVALID; }
+    if (a->rows > 0 && (!a->d_row_ptr || (a->nnz > 0 && (!a->d_col_idx || !a->d_vals)))) {
+        set_error("%s: null array", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_device()) return rc;
+    if (int rc = require_current(a->device, what)) return rc;
+    return ilu0(*a, thin_rows, (hipStream_t)stream, out);
+}
+
+int spmv_csr_ilu0_values(spmv_csr_t *m, const spmv_csr_t *a, void *stream)
+{
+    const char *what = "spmv_csr_ilu0_values";
+    if (!a) { set_error("%s: null argument", what); return SPMV_ERR_INVALID; }
+    if (int rc = ilu0_factor_handle(m, what)) return rc;
+    if (a == m) { set_error("%s: a is m itself (m's values would be read while they are written)", what); return SPMV_ERR_INVALID; }
+    if (a->rows != m->plan_ilu0.a_rows || a->cols != a->rows || a->nnz != m->plan_ilu0.a_nnz) {
+        set_error("%s: a is %lld x %lld with %lld nonzeros, m was factored from %lld x %lld with %lld", what, (long long)a->rows,
+                  (long long)a->cols, (long long)a->nnz, (long long)m->plan_ilu0.a_rows, (long long)m->plan_ilu0.a_rows,
+                  (long long)m->plan_ilu0.a_nnz);
+        return SPMV_ERR_INVALID;
+    }
+    if (a->nnz > 0 && !a->d_vals) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
+    if (int rc = require_current(m->device, what)) return rc;
+    if (a->device != m->device) {
+        set_error("%s: a lives on device %d, m on device %d", what, a->device, m->device);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = ilu0_values(*m, *a, (hipStream_t)stream)) return rc;
+    ++m->values_gen;
+    return SPMV_OK;
+}
+
+int spmv_csr_ilu0_solve(spmv_csr_t *m, const float *d_r, float *d_z, void *stream)
+{
+    const char *what = "spmv_csr_ilu0_solve";
+    if (int rc = ilu0_factor_handle(m, what)) return rc;
+    if (m->rows > 0 && (!d_r || !d_z)) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
+    if (int rc = require_current(m->device, what)) return rc;
+    return ilu0_solve(*m, d_r, d_z, (hipStream_t)stream);
+}
+
+int spmv_csr_ilu0_pivot(const spmv_csr_t *m, void *stream, int64_t *row)
+{
+    const char *what = "spmv_csr_ilu0_pivot";
+    if (int rc = ilu0_factor_handle(m, what)) return rc;
+    if (!row) { set_error("%s: null row", what); return SPMV_ERR_INVALID; }
+    if (int rc = require_current(m->device, what)) return rc;
+    return ilu0_pivot(*m, (hipStream_t)stream, row);
+}
+
+int64_t spmv_csr_ilu0_plan_bytes(const spmv_csr_t *m)
+{
+    if (!m) { set_error("spmv_csr_ilu0_plan_bytes: null handle"); return SPMV_ERR_INVALID; }
+    return ilu0_plan_bytes(*m);
+}
+
 // SPMV_AUTO.  TILED's plan is made first (cheap: a few passes over col_idx, no trial launches) and priced (model_cost,
 // in units of "a chunk that streams 8 bytes per nonzero with cache-resident gathers").
 //   1. It stages (nearly) everything in one or two passes (model_cost <= 1.20: bands up to ~60 000 columns at config 4): TILED.

@@ -326,6 +326,13 @@ struct TrsvPlan {
     ~TrsvPlan() { delete[] level_ptr; delete[] steps; }
 };
 
+// spmv_csr_ilu0 (kernels_ilu0.hip): what makes a handle a factor handle (its schedule is plan_trsv[SPMV_TRSV_LOWER])
+struct Ilu0Plan {
+    bool ready = false;
+    int64_t a_rows = 0, a_nnz = 0;             // a's rows and nonzeros when the factor was made
+    DevPtr<int32_t> d_pivot;                   // [1] the smallest row whose pivot is +-0 or not finite, INT32_MAX: none
+};
+
 }  // namespace spmv
 
 
@@ -357,6 +364,7 @@ struct spmv_csr {
     spmv::SpgemmPlan plan_spgemm;  // spmv_csr_spgemm_values (a handle made by spmv_csr_spgemm with keep_plan = 1)
     spmv::AddPlan plan_add;        // spmv_csr_add_values / _gather (a handle made by spmv_csr_add with keep_plan = 1)
     spmv::TrsvPlan plan_trsv[2];   // spmv_csr_trsv: one slot per uplo (SPMV_TRSV_LOWER, SPMV_TRSV_UPPER)
+    spmv::Ilu0Plan plan_ilu0;      // spmv_csr_ilu0_values / _solve / _pivot (a handle made by spmv_csr_ilu0)
     int auto_variant = -1;         // SPMV_AUTO: the variant its plan chose (-1 = not planned)
     uint64_t values_gen = 0;       // bumped by spmv_csr_values_changed: plans that copied vals before that are stale
 };
@@ -493,6 +501,13 @@ int64_t add_plan_bytes(const spmv_csr &c);
 int trsv_plan(spmv_csr &h, bool upper, int thin_rows, hipStream_t s);
 int trsv_solve(const spmv_csr &h, bool upper, bool unit, const float *b, float *x, hipStream_t s);
 int64_t trsv_plan_bytes(const TrsvPlan &p, int64_t rows);
+
+// kernels_ilu0.hip: spmv_csr_ilu0 / _values (the factorisation alone, on m's lower trsv plan) / _solve / _pivot
+int ilu0(const spmv_csr &a, int thin_rows, hipStream_t s, spmv_csr_t **out);
+int ilu0_values(spmv_csr &m, const spmv_csr &a, hipStream_t s);
+int ilu0_solve(const spmv_csr &m, const float *r, float *z, hipStream_t s);
+int ilu0_pivot(const spmv_csr &m, hipStream_t s, int64_t *row);
+int64_t ilu0_plan_bytes(const spmv_csr &m);
 
 int dense_to_csr(int M, int N, const float *d_A, hipStream_t s, spmv_csr_t **out);
 int dense_gemv(int M, int N, const float *d_A, const float *d_x, float *d_y, int mode, hipStream_t s);

@@ -13,6 +13,10 @@
 //   sparse_sgemv --mtx A.mtx --trsv lower|upper [--unit] [--out x.txt]
 //        x = T^-1 ones for the chosen triangle of a square A through spmv_csr_trsv (the other triangle is never read), checked
 //        bit for bit against a host walk of the contract of include/spmv_hip.h "the triangular solve"
+//   sparse_sgemv --mtx A.mtx --ilu0 [--out m.txt]
+//        M = ILU(0) of a square A through spmv_csr_ilu0 (the reader sorts every row; every row must store its diagonal), M's
+//        values in storage order checked bit for bit against a host walk of the contract of include/spmv_hip.h "the incomplete
+//        factorisation"
 // $SPMV_SEED makes the random inputs reproducible.
 #include <cmath>
 #include <cstdio>
@@ -208,11 +212,71 @@ static int run_trsv(const HostCsr &a, bool upper, bool unit, const std::string &
     return bad ? 1 : 0;
 }
 
+// M = ILU(0) of a through the C ABI against the contract of include/spmv_hip.h "the incomplete factorisation", walked on the host
+static int run_ilu0(const HostCsr &a, const std::string &out)
+{
+    const int64_t n = a.rows, nnz = a.nnz();
+    spmv_csr_t *A = nullptr, *M = nullptr;
+    SPMV_CHECK(spmv_csr_create_host(a.rows, a.cols, nnz, a.row_ptr.data(), a.col_idx.data(), a.vals.data(), &A));
+    SPMV_CHECK(spmv_csr_ilu0(A, 0, nullptr, &M));
+    int64_t pivot = -1, info[8] = {};
+    SPMV_CHECK(spmv_csr_ilu0_pivot(M, nullptr, &pivot));
+    SPMV_CHECK(spmv_csr_trsv_plan_info(M, SPMV_TRSV_LOWER, info));
+    std::printf("spmv_csr_ilu0: rows=%lld nnz=%lld levels=%lld launches=%lld pivot=%lld bytes=%lld\n", (long long)n, (long long)nnz,
+                (long long)info[0], (long long)(info[1] + 1), (long long)pivot, (long long)spmv_csr_ilu0_plan_bytes(M));
+    std::vector<float> m((size_t)nnz, NAN), ref(a.vals);
+    float *d_m = nullptr;
+    if (hipMalloc((void **)&d_m, sizeof(float) * (size_t)(nnz ? nnz : 1)) != hipSuccess) {
+        std::fprintf(stderr, "error: no device memory for M's values\n");
+        return 2;
+    }
+    SPMV_CHECK(spmv_csr_copy_arrays(M, nullptr, nullptr, d_m, nullptr));
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(m.data(), d_m, sizeof(float) * (size_t)nnz, hipMemcpyDeviceToHost) != hipSuccess) {
+        std::fprintf(stderr, "error: the factorisation failed on the device\n");
+        return 2;
+    }
+    (void)hipFree(d_m);
+    SPMV_CHECK(spmv_csr_destroy(M));
+    SPMV_CHECK(spmv_csr_destroy(A));
+    // the contract, row after row
+    std::vector<int32_t> diag((size_t)n, -1);
+    for (int64_t i = 0; i < n; ++i)
+        for (int32_t s = a.row_ptr[i]; s < a.row_ptr[i + 1]; ++s)
+            if (a.col_idx[s] == i) diag[i] = s;
+    int64_t ref_pivot = -1;
+    for (int64_t i = 0; i < n; ++i) {
+        for (int32_t p = a.row_ptr[i]; p < a.row_ptr[i + 1]; ++p) {
+            const int32_t k = a.col_idx[p];
+            if (k >= i) break;
+            const float l = ref[p] / ref[diag[k]];
+            ref[p] = l;
+            int32_t r = p + 1;
+            for (int32_t q = diag[k] + 1; q < a.row_ptr[k + 1]; ++q) {
+                while (r < a.row_ptr[i + 1] && a.col_idx[r] < a.col_idx[q]) ++r;
+                if (r < a.row_ptr[i + 1] && a.col_idx[r] == a.col_idx[q]) ref[r] = std::fmaf(-l, ref[q], ref[r]);
+            }
+        }
+        const float u = ref[diag[i]];
+        if (ref_pivot < 0 && (u == 0.0f || !std::isfinite(u))) ref_pivot = i;
+    }
+    int64_t bad = pivot == ref_pivot ? 0 : 1;
+    if (bad) std::fprintf(stderr, "[pivot] cpu: %lld, gpu: %lld\n", (long long)ref_pivot, (long long)pivot);
+    for (int64_t s = 0; s < nnz; ++s)
+        if (std::memcmp(&ref[s], &m[s], 4) != 0 && !(std::isnan(ref[s]) && std::isnan(m[s]))) {
+            if (bad < 16) std::fprintf(stderr, "[position %lld] cpu: %.9g, gpu: %.9g\n", (long long)s, ref[s], m[s]);
+            ++bad;
+        }
+    std::string err;
+    if (!out.empty() && !(err = write_vector_text(out, m)).empty()) { std::fprintf(stderr, "error: %s\n", err.c_str()); return 2; }
+    std::printf(bad ? "====== %lld MISMATCHES ======\n" : "========== OK ===========\n", (long long)bad);
+    return bad ? 1 : 0;
+}
+
 static int run_file(int argc, char **argv)
 {
     std::string mtx, bin, out, save, spgemm_b, add_b, add_op = "union", trsv, vname = "tiled";
     float alpha = 1.0f, beta = 1.0f;
-    bool parse_only = false, transpose = false, unit = false;
+    bool parse_only = false, transpose = false, unit = false, ilu0 = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> std::string { return i + 1 < argc ? argv[++i] : ""; };
@@ -230,6 +294,7 @@ static int run_file(int argc, char **argv)
         else if (a == "--op") add_op = next();
         else if (a == "--trsv") trsv = next();
         else if (a == "--unit") unit = true;
+        else if (a == "--ilu0") ilu0 = true;
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     HostCsr m;
@@ -248,6 +313,15 @@ static int run_file(int argc, char **argv)
         if (trsv != "lower" && trsv != "upper") { std::fprintf(stderr, "unknown triangle %s (lower or upper)\n", trsv.c_str()); return 2; }
         if (m.rows != m.cols) { std::fprintf(stderr, "error: --trsv needs a square matrix\n"); return 2; }
         return run_trsv(m, trsv == "upper", unit, out);
+    }
+    if (ilu0) {
+        if (m.rows != m.cols) { std::fprintf(stderr, "error: --ilu0 needs a square matrix\n"); return 2; }
+        for (int64_t i = 0; i < m.rows; ++i) {
+            bool have = false;
+            for (int32_t s = m.row_ptr[i]; s < m.row_ptr[i + 1]; ++s) have = have || m.col_idx[s] == i;
+            if (!have) { std::fprintf(stderr, "error: --ilu0 needs a diagonal entry in every row (row %lld has none)\n", (long long)(i + 1)); return 2; }
+        }
+        return run_ilu0(m, out);
     }
     const int variant = variant_by_name(vname);
     if (variant < 0) { std::fprintf(stderr, "unknown variant %s\n", vname.c_str()); return 2; }
