@@ -542,6 +542,90 @@ SPMV_API int spmv_csr_ilu0_solve(spmv_csr_t *m, const float *d_r, float *d_z, vo
 SPMV_API int spmv_csr_ilu0_pivot(const spmv_csr_t *m, void *stream, int64_t *row);                /* waits; -1: none */
 SPMV_API int64_t spmv_csr_ilu0_plan_bytes(const spmv_csr_t *m);
 
+/* ---- the multicolour ordering -----------------------------------------------
+ * A colouring of a square handle's graph, the relabelled handle B = P A Q^T, and what moves values and vectors between the
+ * two orders.  With the rows of one colour contiguous and no stored entry between two rows of a colour, the lower and the
+ * upper dependency graph of P A P^T are at most as deep as there are colours: spmv_csr_trsv_plan finds those few levels by
+ * itself and spmv_csr_ilu0 reuses them.  Everything here is structure -- integer keys, no floating-point sum -- so the
+ * contract holds bit for bit (tests/_color.py states it in numpy).
+ *
+ * spmv_csr_color.  a is square and owns or borrows its arrays; rows may be unsorted and may repeat columns; vals are never
+ * read.  The graph is the symmetrised pattern, N(i) = { j != i : (i, j) stored or (j, i) stored }, so a pattern that is not
+ * structurally symmetric is coloured correctly (the other direction comes from the library's transpose, freed before the call
+ * returns).  key(i) = fmix32((uint32_t)i ^ seed), compared unsigned, with fmix32(h): h ^= h >> 16; h *= 0x85ebca6b;
+ * h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16 in 32-bit arithmetic -- a bijection, so keys never tie.  color[i] is the
+ * smallest c >= 0 that is not in { color[j] : j in N(i), key(j) > key(i) }: the sequential greedy colouring in descending key
+ * order (Jones-Plassmann), at most the maximum degree + 1 colours.  d_perm lists the rows by (colour, row) ascending and
+ * color_ptr[c] is where colour c starts in it (the transpose of the rows x colours pattern with one entry per row: the
+ * library's stable sort, no atomic).  color_ptr is a HOST array of `cap` entries: min(colours + 1, cap) of them are filled.
+ *   info[0] colours; [1] rounds = max_i round(i), round(i) = 1 + max(round(j) : j in N(i), key(j) > key(i)) and 1 where there
+ * is no such j; [2] launches of the colouring loop; [3] / [4] the rows of the largest / smallest colour; [5] neighbour
+ * entries a full sweep visits (the stored entries of a and of its transpose); [6] device bytes the call held at its peak;
+ * [7] 0.  [0], [1], [3] and [4] belong to the contract.  rows = 0: no colour, no round.  nnz = 0: one colour, one round, the
+ * identity.
+ *   Purity.  color, perm, color_ptr and info[0], [1], [3], [4] are a pure function of row_ptr, col_idx and seed: they do not
+ * depend on timing, on the stream, on whether a lane or a wavefront took a row (rows of more than SPMV_COLOR_SERIAL_MAX
+ * neighbour entries, a's and its transpose's counted together, take a wavefront) or on how rounds were merged into launches.
+ * A row reads a neighbour's colour only when an EARLIER round wrote it (every colour carries the number of its round; a
+ * merged launch of one workgroup separates its rounds by the workgroup barrier).  The only atomic decides a row's place in
+ * the list of the rows still uncoloured, whose order reaches no output.  No flag, no spin, no grid barrier and no cooperative
+ * launch: the only waits are kernel boundaries and the workgroup barrier; every loop bound is an argument or comes from a
+ * row_ptr; the host loop makes at most `rows` trips with one read each and fails if a trip colours nothing.
+ *   Device memory.  Nothing is kept.  At the peak (info[6]): the transpose of a (4 (rows + 1) + 8 nnz) with its temporaries
+ * while it is made (see the transpose), then beside it 4 bytes per row of round numbers, two lists of 4 bytes per row and 32
+ * bytes of state; then, the transpose freed, the rows x colours pattern and its transpose (24 bytes per row and their
+ * temporaries).
+ *   SPMV_ERR_INVALID, nothing launched, outputs untouched: a null handle or a null d_color; a handle that is not square;
+ * cap < 0; color_ptr non-NULL with cap == 0; another current device than the handle's.
+ *
+ * spmv_csr_permute.  B = P A Q^T as a new handle that owns its arrays.  Both permutations use one convention: new index r
+ * holds old index perm[r] (NULL: the identity).  Row r of B is row d_row_perm[r] of a; an entry in column j of a lands in the
+ * column c with d_col_perm[c] = j.  Inside a row of B the entries ascend by (new column, storage position in a): rows are
+ * always sorted, repeated columns stay repeated in a's order, values are copied as bits.  With SPMV_PERMUTE_KEEP_MAP the
+ * handle keeps map[i], a's storage position of B's entry i (4 bytes per nonzero).  d_row_perm = d_col_perm = perm of
+ * spmv_csr_color gives P A P^T; where a's rows are strictly ascending with a stored diagonal spmv_csr_ilu0 accepts it.  a may
+ * be rectangular, owning or borrowing, and keeps its plans.  The call allocates, enqueues on `stream` and waits for it.
+ *   Both arrays are checked on the device to be permutations (a mark per index); the first index whose entry is out of range
+ * or was taken by an earlier index is an integer minimum: SPMV_ERR_INVALID, the message names the array and the index, *out
+ * untouched, nothing left allocated.
+ *   Two routes, the same bytes.  Direct: the row lengths gathered and scanned into row_ptr; a row of at most 64 entries is
+ * ranked inside a wavefront (a lane per entry, the others' columns through the cross-lane shuffle), a row of at most 4096
+ * entries is a bitonic sort of the 64-bit keys (column << 32 | position) of one workgroup in LDS.  Via the transpose
+ * (SPMV_PERMUTE_VIA_TRANSPOSE, and every call with a longer row): the columns relabelled, the library's transpose, its columns
+ * (a's rows) relabelled by the inverse row permutation, the transpose again, the two maps composed: linear in nnz for any
+ * row length.
+ *   spmv_csr_permute_values(b, a): b.vals[i] = a.vals[map[i]], then what spmv_csr_values_changed(b) does.
+ * spmv_csr_permute_gather: dst[c * dst_stride + i] = src[c * src_stride + map[i]] for c < count, arrays of nnz 32-bit words
+ * from a's order into b's.  Each is one launch, asynchronous, allocates nothing, never waits: graph-capturable.  They refuse
+ * what spmv_csr_transpose_values / _gather refuse: a handle without a map; a == b; an a of another shape or nnz or device;
+ * count < 1; a null array while nnz > 0; an array that is not 4-byte aligned; a negative or overflowing stride; dst_stride <
+ * nnz with count > 1.  One map per handle, as elsewhere: B has no transpose or select map, so those companions refuse it, and
+ * these two refuse every handle spmv_csr_permute did not make.  spmv_csr_permute_map_bytes: 4 nnz with a map, else 0 (< 0:
+ * null handle).
+ *   Device memory.  B: 4 (rows + 1) + 8 nnz bytes, and 4 nnz of the map when kept.  While the call runs also 4 bytes per row
+ * and per column for the inverse permutations and 16 bytes of state; the direct route adds 4 bytes per row (the list of the
+ * rows of more than 64 entries), the route via the transpose the relabelled columns (4 nnz), one intermediate transpose with
+ * its map (4 (cols + 1) + 12 nnz) and the temporaries of one transpose at a time.
+ *   SPMV_ERR_INVALID: a null handle or a null out; flags outside the two; an array that is no permutation; nnz of 2^31 or more
+ * or a dimension of 0x7f7f7f7f or more (the marks are 32-bit); another current device.
+ *
+ * spmv_permute_vector: dst[r] = src[perm[r]] for r < n, or with inverse = 1 dst[perm[r]] = src[r]; bits copied, one launch,
+ * asynchronous, graph-capturable.  An entry of perm outside [0, n) moves nothing.  SPMV_ERR_INVALID: a null array while
+ * n > 0, n < 0, inverse outside {0, 1}, src and dst that overlap (a pointer equal to the other included). */
+#define SPMV_COLOR_SERIAL_MAX 32        /* neighbour entries (a's row plus its transpose's) of a row coloured by one lane */
+#define SPMV_PERMUTE_KEEP_MAP 1
+#define SPMV_PERMUTE_VIA_TRANSPOSE 2
+SPMV_API int spmv_csr_color(const spmv_csr_t *a, uint32_t seed, void *stream, int32_t *d_color /* rows */,
+                            int32_t *d_perm /* rows, or NULL */, int32_t *color_ptr /* host, or NULL */, int cap /* entries of color_ptr */,
+                            int64_t info[8]);
+SPMV_API int spmv_csr_permute(const spmv_csr_t *a, const int32_t *d_row_perm /* NULL: identity */,
+                              const int32_t *d_col_perm /* NULL: identity */, int flags, void *stream, spmv_csr_t **out);
+SPMV_API int spmv_csr_permute_values(spmv_csr_t *b, const spmv_csr_t *a, void *stream);
+SPMV_API int spmv_csr_permute_gather(const spmv_csr_t *b, int count, const void *d_src, int64_t src_stride, void *d_dst,
+                                     int64_t dst_stride, void *stream);
+SPMV_API int64_t spmv_csr_permute_map_bytes(const spmv_csr_t *b);
+SPMV_API int spmv_permute_vector(const int32_t *d_perm, int64_t n, int inverse, const float *d_src, float *d_dst, void *stream);
+
 /* ---- the hot path ------------------------------------------------------
  * spmv_csr_plan: one-off device-side preprocessing a variant needs (chunk
  * boundaries, column windows, for SPMV_TILED also a 16-bit copy of the column

@@ -83,6 +83,12 @@ SIGNATURES = {
     "spmv_csr_ilu0_solve": (C.c_int, [_H, _vp, _vp, _vp]),
     "spmv_csr_ilu0_pivot": (C.c_int, [_H, _vp, C.POINTER(C.c_int64)]),
     "spmv_csr_ilu0_plan_bytes": (C.c_int64, [_H]),
+    "spmv_csr_color": (C.c_int, [_H, C.c_uint32, _vp, _i32p, _i32p, _i32p, C.c_int, C.POINTER(C.c_int64)]),
+    "spmv_csr_permute": (C.c_int, [_H, _i32p, _i32p, C.c_int, _vp, _HP]),
+    "spmv_csr_permute_values": (C.c_int, [_H, _H, _vp]),
+    "spmv_csr_permute_gather": (C.c_int, [_H, C.c_int, _vp, C.c_int64, _vp, C.c_int64, _vp]),
+    "spmv_csr_permute_map_bytes": (C.c_int64, [_H]),
+    "spmv_permute_vector": (C.c_int, [_i32p, C.c_int64, C.c_int, _f32p, _f32p, _vp]),
     "spmv_csr_plan": (C.c_int, [_H, C.c_int, _vp]),
     "spmv_csr_run": (C.c_int, [_H, C.c_int, _f32p, _f32p, _vp]),
     "spmv_csr_run_vals16": (C.c_int, [_H, C.c_int, C.c_int, _vp, _f32p, _f32p, _vp]),
@@ -178,6 +184,8 @@ TRSV_NON_UNIT, TRSV_UNIT = 0, 1                # ... and its diag
 _TRSV_UPLO = {"lower": TRSV_LOWER, "upper": TRSV_UPPER}
 SPMV_TRSV_SERIAL_MAX = 32                      # SPMV_TRSV_SERIAL_MAX: the terms of a row that trsv sums as one chain
 SPMV_ILU0_SERIAL_MAX = 32                      # SPMV_ILU0_SERIAL_MAX: the stored entries of a row that ilu0 factors in one lane
+SPMV_COLOR_SERIAL_MAX = 32                     # SPMV_COLOR_SERIAL_MAX: the neighbour entries of a row that color takes in one lane
+PERMUTE_KEEP_MAP, PERMUTE_VIA_TRANSPOSE = 1, 2  # flags of spmv_csr_permute
 COLS_MAX_K = 65536                             # SPMV_COLS_MAX_K: the widest k of spmm_cols / sddmm_cols
 # CsrMatrix.spmm / spmm_cols / sddmm / sddmm_cols: (method, ATTN_* dtype of its matrices) -> (the C call, its dtype argument
 # as a tuple: the narrow fp32 calls take none).  Built here, not per call.
@@ -647,6 +655,86 @@ class CsrMatrix:
 
     def ilu0_plan_bytes(self) -> int:
         n = lib().spmv_csr_ilu0_plan_bytes(self._h)
+        if n < 0:
+            check(n)
+        return n
+
+    # -- the multicolour ordering (spmv_csr_color, spmv_csr_permute) -------------------------------------------------
+    _COLOR_INFO = ("colors", "rounds", "launches", "largest", "smallest", "sweep_entries", "peak_bytes")
+
+    def color(self, seed: int = 0, stream=None):
+        """``(color, perm, color_ptr, info)`` of this (square) matrix's symmetrised pattern: the greedy colouring in descending
+        order of ``fmix32(row ^ seed)`` (include/spmv_hip.h "the multicolour ordering", bit for bit).  ``color`` and ``perm`` are
+        int32 device tensors of ``rows`` elements -- ``perm`` lists the rows by (colour, row) -- ``color_ptr`` a numpy int32
+        array of colours + 1 entries (where every colour starts in ``perm``) and ``info`` a dict of the call's counts.  Waits
+        for the stream."""
+        import numpy as np
+        import torch
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 32:
+            raise ValueError(f"color: seed = {seed!r}")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        color = torch.empty(max(self.rows, 1), dtype=torch.int32, device=dev)                   # (never a null pointer)
+        perm = torch.empty(max(self.rows, 1), dtype=torch.int32, device=dev)
+        info = (C.c_int64 * 8)()
+        cap = 64
+        while True:
+            color_ptr = np.zeros(cap, np.int32)
+            check(lib().spmv_csr_color(self._h, seed, _stream_handle(stream), _ptr(color), _ptr(perm), _ptr(color_ptr), cap, info))
+            if info[0] + 1 <= cap:
+                break
+            cap = int(info[0]) + 1                             # the second call: cap was too small
+        return color[:self.rows], perm[:self.rows], color_ptr[:int(info[0]) + 1].copy(), dict(zip(self._COLOR_INFO, (int(v) for v in info)))
+
+    @staticmethod
+    def _permutation(who: str, name: str, perm, n: int):
+        import torch
+        if perm is None:
+            return None
+        if not isinstance(perm, torch.Tensor) or perm.dtype != torch.int32 or perm.dim() != 1 or not perm.is_contiguous() \
+                or perm.numel() != n or not perm.is_cuda:
+            raise ValueError(f"{who}: {name} must be a contiguous 1-D int32 device tensor of {n} elements")
+        return perm
+
+    def permute(self, row_perm=None, col_perm=None, keep_map: bool = False, via_transpose: bool = False, stream=None) -> "CsrMatrix":
+        """B = P A Q^T as a new handle that owns its arrays (waits for the stream): row r of B is row ``row_perm[r]`` of this
+        matrix, an entry in column j lands in the column c with ``col_perm[c] == j`` (None: the identity), and every row of B
+        ascends by (new column, storage position here).  ``keep_map=True`` keeps the 4-byte-per-nonzero map that
+        :meth:`permute_values` and :meth:`permute_gather` need; ``via_transpose=True`` forces the route through two transposes
+        (the same bytes).  An array that is no permutation is refused with the first offending index."""
+        row_perm = self._permutation("permute", "row_perm", row_perm, self.rows)
+        col_perm = self._permutation("permute", "col_perm", col_perm, self.cols)
+        flags = (PERMUTE_KEEP_MAP if keep_map else 0) | (PERMUTE_VIA_TRANSPOSE if via_transpose else 0)
+        h = C.c_void_p()
+        check(lib().spmv_csr_permute(self._h, _ptr(row_perm), _ptr(col_perm), flags, _stream_handle(stream), C.byref(h)))
+        return CsrMatrix(h.value)
+
+    def permute_values(self, a: "CsrMatrix", stream=None) -> None:
+        """Refresh this handle's values (made by ``a.permute(..., keep_map=True)``) from ``a``'s values as they are now: one
+        gather launch, asynchronous, graph-capturable; then what :meth:`values_changed` does."""
+        if not isinstance(a, CsrMatrix):
+            raise TypeError("permute_values: a must be a CsrMatrix")
+        check(lib().spmv_csr_permute_values(self._h, a._h, _stream_handle(stream)))
+
+    def permute_gather(self, src, dst=None, stream=None):
+        """On a handle made by ``a.permute(..., keep_map=True)``: ``dst[..., i] = src[..., map[i]]``, arrays of nnz 32-bit
+        elements in ``a``'s storage order brought into this handle's.  src, dst: (nnz,) or (count, nnz) of one 4-byte dtype with
+        stride(-1) == 1 (``dst`` None makes a new one); copied as bits, in one launch.  Returns dst."""
+        import torch
+        if dst is None and isinstance(src, torch.Tensor):
+            dst = torch.empty_like(src)
+        for name, t in (("src", src), ("dst", dst)):
+            if not isinstance(t, torch.Tensor) or t.dim() not in (1, 2) or t.element_size() != 4 or t.stride(-1) != 1 \
+                    or t.shape[-1] != self.nnz:
+                raise ValueError(f"permute_gather: {name} must be (nnz,) or (count, nnz) of 4-byte elements with stride(-1) == 1")
+        if src.dtype != dst.dtype or src.shape != dst.shape:
+            raise ValueError(f"permute_gather: src is {src.dtype} {tuple(src.shape)}, dst {dst.dtype} {tuple(dst.shape)}")
+        count = src.shape[0] if src.dim() == 2 else 1
+        stride = lambda t: t.stride(0) if count > 1 else 0
+        check(lib().spmv_csr_permute_gather(self._h, count, _ptr(src), stride(src), _ptr(dst), stride(dst), _stream_handle(stream)))
+        return dst
+
+    def permute_map_bytes(self) -> int:
+        n = lib().spmv_csr_permute_map_bytes(self._h)
         if n < 0:
             check(n)
         return n
@@ -1191,6 +1279,20 @@ def asp_gemv(M: int, N: int, asp, x, y, workspace, stream=None) -> None:
     """y = A^T x from the ASP layout, rows with x == 0 skipped; ``workspace``: dense_gemv_workspace_bytes(N, 3) bytes."""
     check(lib().spmv_asp_gemv_ws(M, N, _ptr(asp), _ptr(x), _ptr(y), _ptr(workspace),
                                  workspace.numel() * workspace.element_size(), _stream_handle(stream)))
+
+
+def permute_vector(perm, src, dst=None, inverse: bool = False, stream=None):
+    """``dst[r] = src[perm[r]]``, or with ``inverse=True`` ``dst[perm[r]] = src[r]`` (spmv_permute_vector): one launch, bits copied.
+    perm: int32, src / dst: float32, contiguous 1-D device tensors of one length; ``dst`` None makes a new one; src and dst must
+    not overlap.  Returns dst."""
+    import torch
+    if dst is None and isinstance(src, torch.Tensor):
+        dst = torch.empty_like(src)
+    for name, t, dt in (("perm", perm, torch.int32), ("src", src, torch.float32), ("dst", dst, torch.float32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or not t.is_contiguous() or t.numel() != perm.numel():
+            raise ValueError(f"permute_vector: {name} must be a contiguous 1-D {dt} tensor of perm's length")
+    check(lib().spmv_permute_vector(_ptr(perm), perm.numel(), 1 if inverse else 0, _ptr(src), _ptr(dst), _stream_handle(stream)))
+    return dst
 
 
 def synth_fill(seed, row0, n_local, rows, cols, band, row_ptr, col_idx, vals, stream=None) -> None:

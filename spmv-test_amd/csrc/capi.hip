@@ -901,6 +901,119 @@ int64_t spmv_csr_ilu0_plan_bytes(const spmv_csr_t *m)
     return ilu0_plan_bytes(*m);
 }
 
+// ---- the multicolour ordering (kernels_color.hip, kernels_permute.hip) ----------------------------------------------------
+int spmv_csr_color(const spmv_csr_t *a, uint32_t seed, void *stream, int32_t *d_color, int32_t *d_perm, int32_t *color_ptr, int cap,
+                   int64_t info[8])
+{
+    const char *what = "spmv_csr_color";
+    if (!a) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (!d_color) { set_error("%s: null d_color", what); return SPMV_ERR_INVALID; }
+    if (a->rows != a->cols) {
+        set_error("%s: the handle is %lld x %lld (a colouring needs a square one)", what, (long long)a->rows, (long long)a->cols);
+        return SPMV_ERR_INVALID;
+    }
+    if (cap < 0) { set_error("%s: cap = %d (the entries of color_ptr are not negative)", what, cap); return SPMV_ERR_INVALID; }
+    if (color_ptr && cap == 0) { set_error("%s: color_ptr with cap = 0", what); return SPMV_ERR_INVALID; }
+    if (a->rows > 0 && (!a->d_row_ptr || (a->nnz > 0 && !a->d_col_idx))) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
+    if (int rc = require_device()) return rc;
+    if (int rc = require_current(a->device, what)) return rc;
+    return color(*a, seed, (hipStream_t)stream, d_color, d_perm, color_ptr, cap, info);
+}
+
+int spmv_csr_permute(const spmv_csr_t *a, const int32_t *d_row_perm, const int32_t *d_col_perm, int flags, void *stream, spmv_csr_t **out)
+{
+    const char *what = "spmv_csr_permute";
+    if (!a || !out) { set_error("%s: null argument", what); return SPMV_ERR_INVALID; }
+    if (flags & ~(SPMV_PERMUTE_KEEP_MAP | SPMV_PERMUTE_VIA_TRANSPOSE)) {
+        set_error("%s: flags = 0x%x (SPMV_PERMUTE_KEEP_MAP | SPMV_PERMUTE_VIA_TRANSPOSE or 0)", what, (unsigned)flags);
+        return SPMV_ERR_INVALID;
+    }
+    if (a->rows >= 0x7f7f7f7f || a->cols >= 0x7f7f7f7f || a->nnz > INT32_MAX) {
+        set_error("%s: the handle is %lld x %lld with %lld nonzeros (too large for 32-bit marks)", what, (long long)a->rows, (long long)a->cols,
+                  (long long)a->nnz);
+        return SPMV_ERR_INVALID;
+    }
+    if (a->rows > 0 && (!a->d_row_ptr || (a->nnz > 0 && (!a->d_col_idx || !a->d_vals)))) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
+    if (int rc = require_device()) return rc;
+    if (int rc = require_current(a->device, what)) return rc;
+    return permute(*a, d_row_perm, d_col_perm, (flags & SPMV_PERMUTE_KEEP_MAP) != 0, (flags & SPMV_PERMUTE_VIA_TRANSPOSE) != 0,
+                   (hipStream_t)stream, out);
+}
+
+int spmv_csr_permute_values(spmv_csr_t *b, const spmv_csr_t *a, void *stream)
+{
+    const char *what = "spmv_csr_permute_values";
+    if (!b || !a) { set_error("%s: null argument", what); return SPMV_ERR_INVALID; }
+    if (!b->permute_map) {
+        set_error("%s: the handle has no map (it was not made by spmv_csr_permute with SPMV_PERMUTE_KEEP_MAP)", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (a == b) { set_error("%s: a is b itself (b's values would be read while they are written)", what); return SPMV_ERR_INVALID; }
+    if (a->rows != b->rows || a->cols != b->cols || a->nnz != b->nnz) {
+        set_error("%s: a is %lld x %lld with %lld nonzeros, b was permuted from %lld x %lld with %lld", what, (long long)a->rows,
+                  (long long)a->cols, (long long)a->nnz, (long long)b->rows, (long long)b->cols, (long long)b->nnz);
+        return SPMV_ERR_INVALID;
+    }
+    if (a->nnz > 0 && !a->d_vals) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
+    if (int rc = require_current(b->device, what)) return rc;
+    if (a->device != b->device) {
+        set_error("%s: a lives on device %d, b on device %d", what, a->device, b->device);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = permute_gather(*b, 1, a->d_vals, 0, b->own_vals.get(), 0, (hipStream_t)stream)) return rc;
+    ++b->values_gen;
+    return SPMV_OK;
+}
+
+int spmv_csr_permute_gather(const spmv_csr_t *b, int count, const void *d_src, int64_t src_stride, void *d_dst, int64_t dst_stride,
+                            void *stream)
+{
+    const char *what = "spmv_csr_permute_gather";
+    if (!b) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (!b->permute_map) {
+        set_error("%s: the handle has no map (it was not made by spmv_csr_permute with SPMV_PERMUTE_KEEP_MAP)", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (count < 1) { set_error("%s: count = %d (need count >= 1)", what, count); return SPMV_ERR_INVALID; }
+    if ((!d_src || !d_dst) && b->nnz > 0) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
+    if (reinterpret_cast<uintptr_t>(d_src) % 4 != 0 || reinterpret_cast<uintptr_t>(d_dst) % 4 != 0) {
+        set_error("%s: src and dst must be 4-byte aligned", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (src_stride < 0 || dst_stride < 0) {
+        set_error("%s: src_stride = %lld, dst_stride = %lld (a stride is not negative)", what, (long long)src_stride, (long long)dst_stride);
+        return SPMV_ERR_INVALID;
+    }
+    if (src_stride > INT64_MAX / 4 / count || dst_stride > INT64_MAX / 4 / count) {
+        set_error("%s: a stride overflows 64-bit byte offsets", what);
+        return SPMV_ERR_INVALID;
+    }
+    if (count > 1 && dst_stride < b->nnz) {
+        set_error("%s: dst_stride = %lld is below nnz = %lld with count = %d", what, (long long)dst_stride, (long long)b->nnz, count);
+        return SPMV_ERR_INVALID;
+    }
+    if (int rc = require_current(b->device, what)) return rc;
+    return permute_gather(*b, count, d_src, src_stride, d_dst, dst_stride, (hipStream_t)stream);
+}
+
+int64_t spmv_csr_permute_map_bytes(const spmv_csr_t *b)
+{
+    if (!b) { set_error("spmv_csr_permute_map_bytes: null handle"); return SPMV_ERR_INVALID; }
+    return b->permute_map ? 4 * b->nnz : 0;
+}
+
+int spmv_permute_vector(const int32_t *d_perm, int64_t n, int inverse, const float *d_src, float *d_dst, void *stream)
+{
+    const char *what = "spmv_permute_vector";
+    if (n < 0) { set_error("%s: n = %lld", what, (long long)n); return SPMV_ERR_INVALID; }
+    if (inverse != 0 && inverse != 1) { set_error("%s: inverse = %d (0 or 1)", what, inverse); return SPMV_ERR_INVALID; }
+    if (n > 0 && (!d_perm || !d_src || !d_dst)) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst), bytes = (uintptr_t)n * 4;
+    if (n > 0 && s0 < d0 + bytes && d0 < s0 + bytes) { set_error("%s: src and dst overlap", what); return SPMV_ERR_INVALID; }
+    if (int rc = require_device()) return rc;
+    return permute_vector(d_perm, n, inverse == 1, d_src, d_dst, (hipStream_t)stream);
+}
+
 // SPMV_AUTO.  TILED's plan is made first (cheap: a few passes over col_idx, no trial launches) and priced (model_cost,
 // in units of "a chunk that streams 8 bytes per nonzero with cache-resident gathers").
 //   1. It stages (nearly) everything in one or two passes (model_cost <= 1.20: bands up to ~60 000 columns at config 4): TILED.

@@ -348,6 +348,7 @@ struct spmv_csr {
     // a handle has at most one of the two maps: which member is set says which call made it
     spmv::DevPtr<uint32_t> select_map;      // [nnz] spmv_csr_select_*(keep_map = 1): the same, positions ascending inside a row (empty: no map)
     int64_t select_parent_nnz = -1;         // the parent's nnz when a select call made this handle (every map entry is below it); -1: another maker
+    spmv::DevPtr<uint32_t> permute_map;     // [nnz] spmv_csr_permute(SPMV_PERMUTE_KEEP_MAP): vals[i] = the parent's vals[map[i]] (empty: no map)
     int device = 0;
 
     // plan state
@@ -508,6 +509,14 @@ int ilu0_values(spmv_csr &m, const spmv_csr &a, hipStream_t s);
 int ilu0_solve(const spmv_csr &m, const float *r, float *z, hipStream_t s);
 int ilu0_pivot(const spmv_csr &m, hipStream_t s, int64_t *row);
 int64_t ilu0_plan_bytes(const spmv_csr &m);
+
+// kernels_color.hip: spmv_csr_color (perm may be null; color_ptr: the host's, cap entries, may be null; info may be null)
+int color(const spmv_csr &a, uint32_t seed, hipStream_t s, int32_t *d_color, int32_t *d_perm, int32_t *color_ptr, int cap, int64_t info[8]);
+// kernels_permute.hip: spmv_csr_permute / _values / _gather (through b's permute map) / spmv_permute_vector
+int permute(const spmv_csr &a, const int32_t *row_perm, const int32_t *col_perm, bool keep_map, bool via_transpose, hipStream_t s,
+            spmv_csr_t **out);
+int permute_gather(const spmv_csr &b, int count, const void *src, int64_t src_stride, void *dst, int64_t dst_stride, hipStream_t s);
+int permute_vector(const int32_t *perm, int64_t n, bool inverse, const float *src, float *dst, hipStream_t s);
 
 int dense_to_csr(int M, int N, const float *d_A, hipStream_t s, spmv_csr_t **out);
 int dense_gemv(int M, int N, const float *d_A, const float *d_x, float *d_y, int mode, hipStream_t s);

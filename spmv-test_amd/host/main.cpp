@@ -17,13 +17,21 @@
 //        M = ILU(0) of a square A through spmv_csr_ilu0 (the reader sorts every row; every row must store its diagonal), M's
 //        values in storage order checked bit for bit against a host walk of the contract of include/spmv_hip.h "the incomplete
 //        factorisation"
+//   sparse_sgemv --mtx A.mtx --color [--seed S] [--ilu0] --out B.mtx
+//        colours a square A through spmv_csr_color (seed S, default 0), builds P A P^T through spmv_csr_permute and writes it as a
+//        Matrix Market coordinate file; prints colours, rounds and the levels of both triangles of P A P^T; color and P A P^T's
+//        bytes are checked against a host walk of the contract of include/spmv_hip.h "the multicolour ordering"; with --ilu0 it
+//        also factors P A P^T and checks the factor as --ilu0 does
 // $SPMV_SEED makes the random inputs reproducible.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <iterator>
 #include <map>
+#include <numeric>
+#include <set>
 #include <string>
 #include <vector>
 #include <hip/hip_runtime_api.h>
@@ -272,11 +280,129 @@ static int run_ilu0(const HostCsr &a, const std::string &out)
     return bad ? 1 : 0;
 }
 
+// P A P^T by the colouring of a through the C ABI against the contract of include/spmv_hip.h "the multicolour ordering", walked on the host
+static int run_color(const HostCsr &a, uint32_t seed, bool ilu0, const std::string &out)
+{
+    const int64_t n = a.rows, nnz = a.nnz();
+    spmv_csr_t *A = nullptr, *B = nullptr;
+    SPMV_CHECK(spmv_csr_create_host(a.rows, a.cols, nnz, a.row_ptr.data(), a.col_idx.data(), a.vals.data(), &A));
+    int32_t *d_color = nullptr, *d_perm = nullptr;
+    const size_t bytes = sizeof(int32_t) * (size_t)(n ? n : 1);
+    if (hipMalloc((void **)&d_color, bytes) != hipSuccess || hipMalloc((void **)&d_perm, bytes) != hipSuccess) {
+        std::fprintf(stderr, "error: no device memory for color and perm\n");
+        return 2;
+    }
+    std::vector<int32_t> color((size_t)n, -1), perm((size_t)n, -1), color_ptr((size_t)n + 1, -1);
+    int64_t info[8] = {}, lower[8] = {}, upper[8] = {};
+    SPMV_CHECK(spmv_csr_color(A, seed, nullptr, d_color, d_perm, color_ptr.data(), (int)color_ptr.size(), info));
+    SPMV_CHECK(spmv_csr_permute(A, d_perm, d_perm, 0, nullptr, &B));
+    if (hipMemcpy(color.data(), d_color, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(perm.data(), d_perm, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) {
+        std::fprintf(stderr, "error: the colouring failed on the device\n");
+        return 2;
+    }
+    (void)hipFree(d_color);
+    (void)hipFree(d_perm);
+    HostCsr b;
+    b.rows = n; b.cols = n;
+    b.row_ptr.resize((size_t)n + 1); b.col_idx.resize((size_t)nnz); b.vals.resize((size_t)nnz);
+    SPMV_CHECK(spmv_csr_download(B, b.row_ptr.data(), b.col_idx.data(), b.vals.data()));
+    SPMV_CHECK(spmv_csr_trsv_plan(B, SPMV_TRSV_LOWER, 0, nullptr));
+    SPMV_CHECK(spmv_csr_trsv_plan(B, SPMV_TRSV_UPPER, 0, nullptr));
+    SPMV_CHECK(spmv_csr_trsv_plan_info(B, SPMV_TRSV_LOWER, lower));
+    SPMV_CHECK(spmv_csr_trsv_plan_info(B, SPMV_TRSV_UPPER, upper));
+    SPMV_CHECK(spmv_csr_destroy(B));
+    SPMV_CHECK(spmv_csr_destroy(A));
+    std::printf("spmv_csr_color: rows=%lld colors=%lld rounds=%lld launches=%lld largest=%lld smallest=%lld\n", (long long)n, (long long)info[0],
+                (long long)info[1], (long long)info[2], (long long)info[3], (long long)info[4]);
+    std::printf("P A P^T: levels lower=%lld upper=%lld\n", (long long)lower[0], (long long)upper[0]);
+    // the contract: the rows in descending key order take the smallest colour no coloured neighbour has
+    auto key = [seed](uint32_t i) {
+        uint32_t h = i ^ seed;
+        h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+        return h;
+    };
+    std::vector<std::vector<int32_t>> nb((size_t)n);
+    for (int64_t i = 0; i < n; ++i)
+        for (int32_t s = a.row_ptr[i]; s < a.row_ptr[i + 1]; ++s)
+            if (a.col_idx[s] != i) { nb[i].push_back(a.col_idx[s]); nb[a.col_idx[s]].push_back((int32_t)i); }
+    std::vector<int32_t> by_key((size_t)n), ref((size_t)n, -1), round((size_t)n, 0);
+    std::iota(by_key.begin(), by_key.end(), 0);
+    std::sort(by_key.begin(), by_key.end(), [&](int32_t x, int32_t y) { return key((uint32_t)x) > key((uint32_t)y); });
+    int64_t bad = 0, colors = 0, rounds = 0;
+    for (int32_t i : by_key) {
+        std::set<int32_t> used;
+        int32_t r = 0;
+        for (int32_t j : nb[i])
+            if (ref[j] >= 0) { used.insert(ref[j]); r = std::max(r, round[j]); }
+        int32_t c = 0;
+        while (used.count(c)) ++c;
+        ref[i] = c;
+        round[i] = r + 1;
+        colors = std::max<int64_t>(colors, c + 1);
+        rounds = std::max<int64_t>(rounds, r + 1);
+    }
+    if (colors != info[0] || rounds != info[1]) {
+        std::fprintf(stderr, "[counts] cpu: %lld colours in %lld rounds, gpu: %lld in %lld\n", (long long)colors, (long long)rounds, (long long)info[0], (long long)info[1]);
+        ++bad;
+    }
+    for (int64_t i = 0; i < n; ++i)
+        if (ref[i] != color[i]) {
+            if (bad < 16) std::fprintf(stderr, "[row %lld] cpu: colour %d, gpu: %d\n", (long long)i, ref[i], color[i]);
+            ++bad;
+        }
+    // perm: the rows by (colour, row); P A P^T: every row by (new column, position)
+    std::vector<int32_t> want_perm((size_t)n), inv((size_t)n, 0);
+    std::iota(want_perm.begin(), want_perm.end(), 0);
+    std::stable_sort(want_perm.begin(), want_perm.end(), [&](int32_t x, int32_t y) { return ref[x] < ref[y]; });
+    for (int64_t r = 0; r < n; ++r) {
+        if (want_perm[r] != perm[r]) { if (bad < 16) std::fprintf(stderr, "[perm %lld] cpu: %d, gpu: %d\n", (long long)r, want_perm[r], perm[r]); ++bad; }
+        inv[want_perm[r]] = (int32_t)r;
+    }
+    for (int64_t c = 0; c <= colors; ++c) {
+        const int64_t start = std::lower_bound(want_perm.begin(), want_perm.end(), (int32_t)c, [&](int32_t x, int32_t v) { return ref[x] < v; }) - want_perm.begin();
+        if (color_ptr[c] != start) { if (bad < 16) std::fprintf(stderr, "[color_ptr %lld] cpu: %lld, gpu: %d\n", (long long)c, (long long)start, color_ptr[c]); ++bad; }
+    }
+    int64_t at = 0;
+    for (int64_t r = 0; r < n && bad == 0; ++r) {
+        const int32_t old = want_perm[r];
+        std::vector<std::pair<int32_t, int32_t>> e;
+        for (int32_t s = a.row_ptr[old]; s < a.row_ptr[old + 1]; ++s) e.push_back({inv[a.col_idx[s]], s});
+        std::sort(e.begin(), e.end());
+        if (b.row_ptr[r] != at) ++bad;
+        for (const auto &x : e) {
+            if (b.col_idx[at] != x.first || std::memcmp(&b.vals[at], &a.vals[x.second], 4) != 0) {
+                if (bad < 16) std::fprintf(stderr, "[P A P^T row %lld] cpu: (%d, %g), gpu: (%d, %g)\n", (long long)r, x.first, a.vals[x.second], b.col_idx[at], b.vals[at]);
+                ++bad;
+            }
+            ++at;
+        }
+    }
+    if (bad == 0 && b.row_ptr[n] != nnz) ++bad;
+    if (!out.empty()) {
+        FILE *f = std::fopen(out.c_str(), "w");
+        if (!f) { std::fprintf(stderr, "error: cannot write %s\n", out.c_str()); return 2; }
+        std::fprintf(f, "%%%%MatrixMarket matrix coordinate real general\n%lld %lld %lld\n", (long long)n, (long long)n, (long long)nnz);
+        for (int64_t i = 0; i < n; ++i)
+            for (int32_t k = b.row_ptr[i]; k < b.row_ptr[i + 1]; ++k) std::fprintf(f, "%lld %d %.9g\n", (long long)i + 1, b.col_idx[k] + 1, b.vals[k]);
+        if (std::fclose(f) != 0) { std::fprintf(stderr, "error: cannot write %s\n", out.c_str()); return 2; }
+    }
+    if (bad) {
+        std::printf("====== %lld MISMATCHES ======\n", (long long)bad);
+        return 1;
+    }
+    std::printf("color check ok\n");
+    if (ilu0) return run_ilu0(b, "");
+    std::printf("========== OK ===========\n");
+    return 0;
+}
+
 static int run_file(int argc, char **argv)
 {
     std::string mtx, bin, out, save, spgemm_b, add_b, add_op = "union", trsv, vname = "tiled";
     float alpha = 1.0f, beta = 1.0f;
-    bool parse_only = false, transpose = false, unit = false, ilu0 = false;
+    bool parse_only = false, transpose = false, unit = false, ilu0 = false, color = false;
+    uint32_t seed = 0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> std::string { return i + 1 < argc ? argv[++i] : ""; };
@@ -295,6 +421,8 @@ static int run_file(int argc, char **argv)
         else if (a == "--trsv") trsv = next();
         else if (a == "--unit") unit = true;
         else if (a == "--ilu0") ilu0 = true;
+        else if (a == "--color") color = true;
+        else if (a == "--seed") seed = (uint32_t)std::strtoul(next().c_str(), nullptr, 0);
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     HostCsr m;
@@ -314,6 +442,7 @@ static int run_file(int argc, char **argv)
         if (m.rows != m.cols) { std::fprintf(stderr, "error: --trsv needs a square matrix\n"); return 2; }
         return run_trsv(m, trsv == "upper", unit, out);
     }
+    if (color && m.rows != m.cols) { std::fprintf(stderr, "error: --color needs a square matrix\n"); return 2; }
     if (ilu0) {
         if (m.rows != m.cols) { std::fprintf(stderr, "error: --ilu0 needs a square matrix\n"); return 2; }
         for (int64_t i = 0; i < m.rows; ++i) {
@@ -321,8 +450,9 @@ static int run_file(int argc, char **argv)
             for (int32_t s = m.row_ptr[i]; s < m.row_ptr[i + 1]; ++s) have = have || m.col_idx[s] == i;
             if (!have) { std::fprintf(stderr, "error: --ilu0 needs a diagonal entry in every row (row %lld has none)\n", (long long)(i + 1)); return 2; }
         }
-        return run_ilu0(m, out);
+        if (!color) return run_ilu0(m, out);
     }
+    if (color) return run_color(m, seed, ilu0, out);
     const int variant = variant_by_name(vname);
     if (variant < 0) { std::fprintf(stderr, "unknown variant %s\n", vname.c_str()); return 2; }
 

@@ -1,5 +1,6 @@
 """Stationary and Krylov iterations on a CSR handle: the downstream users of ``CsrMatrix.trsv`` and ``CsrMatrix.ilu0``.
 
+``multicolor`` reorders a matrix by a colouring of its graph, so that its ILU(0) factor has no more levels than colours.
 ``gauss_seidel`` runs on A's own handle: the triangular solve reads the triangle it is asked for and never the other one, so
 neither D + L nor D + U is ever formed.  ``pcg`` and ``bicgstab`` take an ILU(0) factor handle as their preconditioner and apply
 it with ``ilu0_solve``.  Every step is a library launch or a torch elementwise kernel or dot product on the current stream.
@@ -8,7 +9,7 @@ from __future__ import annotations
 
 from . import capi
 
-__all__ = ["GaussSeidel", "gauss_seidel", "Krylov", "KrylovResult", "pcg", "bicgstab"]
+__all__ = ["GaussSeidel", "gauss_seidel", "Krylov", "KrylovResult", "pcg", "bicgstab", "Reordering", "multicolor"]
 
 
 class GaussSeidel:
@@ -208,3 +209,77 @@ def bicgstab(A, b, x, M=None, tol: float = 1e-5, maxiter=None, state: Krylov | N
         rr, rho, den, tt, ts, _, _, omega = sc.tolist()    # the one host read of the iteration
         if rr == 0.0:                                      # (s vanished: t . t = 0 is no breakdown then)
             tt = omega = 1.0
+
+
+# ---- the multicolour ordering: the downstream user of ``CsrMatrix.color`` and ``CsrMatrix.permute`` ----------------------------
+class Reordering:
+    """P A P^T by a colouring of A's graph (:func:`multicolor`): ``matrix`` (a handle of its own), ``perm`` (row r of ``matrix`` is
+    row ``perm[r]`` of A), ``color``, ``color_ptr`` (numpy: where every colour starts in ``perm``) and ``colors``.  No stored entry
+    joins two rows of a colour, so each triangle of ``matrix`` has at most ``colors`` levels."""
+
+    def __init__(self, A: "capi.CsrMatrix", seed: int = 0, keep_map: bool = False):
+        if not isinstance(A, capi.CsrMatrix):
+            raise TypeError("multicolor: A must be a CsrMatrix")
+        if A.rows != A.cols:
+            raise ValueError(f"multicolor: A is {A.rows} x {A.cols} (a square matrix is needed)")
+        self.color, self.perm, self.color_ptr, self.info = A.color(seed)
+        self.colors = self.info["colors"]
+        self.keep_map = bool(keep_map)
+        self.matrix = A.permute(self.perm, self.perm, keep_map=self.keep_map)
+        self._b = self._x = None
+        self._states = {}
+
+    def _vector(self, who, v, out):
+        import torch
+        if out is None and isinstance(v, torch.Tensor):
+            out = torch.empty_like(v)
+        for name, t in (("v", v), ("out", out)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous() or t.numel() != self.matrix.rows:
+                raise ValueError(f"multicolor: {who}: {name} must be a contiguous 1-D float32 tensor of {self.matrix.rows} elements")
+        return out
+
+    def forward(self, v, out=None):
+        """P v: ``out[r] = v[perm[r]]``, a vector of A's order brought into ``matrix``'s."""
+        out = self._vector("forward", v, out)
+        return capi.permute_vector(self.perm, v, out, inverse=False)
+
+    def backward(self, v, out=None):
+        """P^T v: ``out[perm[r]] = v[r]``, a vector of ``matrix``'s order brought back into A's."""
+        out = self._vector("backward", v, out)
+        return capi.permute_vector(self.perm, v, out, inverse=True)
+
+    def solve(self, solver, b, x, M=None, **kw):
+        """``solver(self.matrix, P b, P x, M=M, **kw)`` (:func:`pcg` or :func:`bicgstab`; ``M``: ``self.matrix.ilu0()`` or None), then x
+        brought back in place.  The two work vectors and the solver's state are kept across calls.  Returns the solver's result."""
+        import torch
+        self._vector("solve", b, x)
+        if self._b is None or self._b.device != b.device:
+            self._b, self._x = torch.empty_like(b), torch.empty_like(b)
+        self.forward(b, self._b)
+        self.forward(x, self._x)
+        key = (solver, id(M))
+        if key in self._states and "state" not in kw:
+            kw["state"] = self._states[key]
+        res = solver(self.matrix, self._b, self._x, M=M, **kw)
+        self._states = {key: res.state}
+        self.backward(self._x, x)
+        return res
+
+    def refresh(self, A: "capi.CsrMatrix") -> None:
+        """``matrix``'s values again from the values A holds now (``permute_values``); needs ``keep_map=True``."""
+        if not self.keep_map:
+            raise ValueError("multicolor: refresh needs keep_map=True")
+        self.matrix.permute_values(A)
+
+    def close(self) -> None:
+        self._states = {}
+        self._b = self._x = None
+        if self.matrix is not None:
+            self.matrix.close()
+            self.matrix = None
+
+
+def multicolor(A, seed: int = 0, keep_map: bool = False) -> Reordering:
+    """Colour A's graph (``A.color(seed)``) and build P A P^T with the rows of one colour contiguous.  ``R.matrix.ilu0()`` then has at
+    most ``R.colors`` levels in each triangle, and ``R.solve(pcg, b, x, M=M)`` solves the original system through it."""
+    return Reordering(A, seed, keep_map)
