@@ -1,7 +1,7 @@
 """Carriers and programs: how the tests put known data on a handle that a builder made, and how they chain builders (host
-only, numpy).  The builders are spmv_csr_transpose, _select_topk / _select_threshold, _spgemm and _add; their contracts in numpy
-are test_transpose_host.host_transpose, tests/_select.py, tests/_spgemm.py and tests/_add.py, and nothing here computes an
-expectation in any other way.
+only, numpy).  The builders are spmv_csr_transpose, _select_topk / _select_threshold, _spgemm, _add, _permute and _ilu0; their
+contracts in numpy are test_transpose_host.host_transpose, tests/_select.py, tests/_spgemm.py, tests/_add.py, _color.permute and
+_ilu0.factor, and nothing here computes an expectation in any other way.
 
 A matrix is (rows, cols, (row_ptr, col_idx, vals)), as in _spgemm.py and _add.py.  A step is (name, op, operand names,
 keywords) with op one of OPS; host_step runs one through its numpy model and run_host a list of them over named leaves.
@@ -19,6 +19,15 @@ contract returns the target's pattern with exactly those values:
              scores lie below the threshold (or are NaN), the target's at or above it
   topk       k is the longest row; decoys sit only in rows of that length, score below every entry of the target or tie the
              lowest from behind the row's last entry (a tie goes to the earlier position)
+  permuted   p and q are random permutations of the rows and the columns; the parent holds the target's row r in its row p[r],
+             every column c relabelled q[c], the entries of a row in random storage order; C = permute(P, p, q) is the target
+             with every row stably sorted by column, repeats in the parent's order.  Values travel as bits.
+             permuted-via-transpose: the same operands through SPMV_PERMUTE_VIA_TRANSPOSE, the same bytes
+  factor-upper, factor-lower
+             with n = max(rows, cols) every entry (i, j) of the target mirrored to (min, max) (lower: (max, min)), the diagonal
+             added, repeats merged, rows sorted; for factor-lower the diagonal values are 1.  C = ilu0(A) is A itself bit for
+             bit: an upper-triangular row has no position with col < i, a lower-triangular row divides by a pivot of 1 and
+             has no update.  base and out are that square structure
 
 Where a row of the target repeats a column, sum and product merge the repeats into one entry: `base` is the target with the
 repeats merged, the values live on base, and the first repeat carries the value while the others carry +0 (v + 0 = v).  `out`
@@ -30,26 +39,41 @@ import functools
 import numpy as np
 
 import _add
+import _color
 import _exact as E
+import _ilu0
 import _select
 import _spgemm
+import _trsv
 from test_transpose_host import host_transpose
 
 f32 = np.float32
-OPS = ("transpose", "select_topk", "select_threshold", "spgemm", "add")
+OPS = ("transpose", "select_topk", "select_threshold", "spgemm", "add", "permute", "ilu0")
 THIRD = float(f32(1) / f32(3))
 KINDS = ("threshold", "topk", "product", "sum", "sum-grown")
+PERMUTED_KINDS = ("permuted", "permuted-via-transpose")
+FACTOR_KINDS = ("factor-upper", "factor-lower")
+ALL_KINDS = KINDS + PERMUTED_KINDS + FACTOR_KINDS
+# the structures the factor kinds run on: mirrored, they still hold rows above SPMV_ILU0_SERIAL_MAX
+FACTOR_ON = ("lengths_around_short_threshold", "not_multiple_of_anything", "long_row_between_short_rows")
 # the structures of _exact every path runs on, per builder; the product of the 120 000-entry row is the oversized route, which
 # the program "oversized_then_selected" covers once
 STRUCTURES = ("wave_pipe_thresholds", "rows_near_64", "odd_last_chunk", "stencil7_32", "wide_window", "long_row_between_short_rows",
               "rows_exactly_chunk_aligned", "chunk_ends_on_row_boundary_then_empties", "all_rows_empty", "leading_empty_rows",
               "trailing_empty_rows", "single_element", "lengths_around_short_threshold", "not_multiple_of_anything")
 CASES = [(k, n) for k in KINDS for n in STRUCTURES] + [(k, "one_row_spanning_30_chunks") for k in KINDS if k != "product"]
+NEW_CASES = [(k, n) for k in PERMUTED_KINDS for n in STRUCTURES + ("one_row_spanning_30_chunks",)] + \
+            [(k, n) for k in FACTOR_KINDS for n in FACTOR_ON]
 # the structures the other consumers run on
 SPMM_ON = ("wave_pipe_thresholds", "not_multiple_of_anything", "leading_empty_rows")
 SDDMM_ON = ("wave_pipe_thresholds", "lengths_around_short_threshold")
 VALS16_ON = ("odd_last_chunk", "long_row_between_short_rows")
 SPMM_K, SPMM_COLS_K, SDDMM_K = (1, 4, 17), (65, 130), (3, 16, 64)
+
+
+def consumer_cases(on):
+    """(kind, structure) of one of the other consumers: every kind on the consumer's structures, the factor kinds on theirs."""
+    return [(k, n) for k in KINDS + PERMUTED_KINDS for n in on] + [(k, FACTOR_ON[0]) for k in FACTOR_KINDS]
 
 
 # ---- the builders on the host ----------------------------------------------------------------------------------------------------
@@ -73,6 +97,13 @@ def host_step(builder, mats, **kw):
         a, b = mats
         assert a[:2] == b[:2]
         return a[0], a[1], _add.add(a[2], b[2], kw.get("alpha", 1.0), kw.get("beta", 1.0), kw.get("op", "union"), cols=a[1])[:3]
+    if builder == "permute":
+        (m, n, (rp, ci, va)), = mats
+        return m, n, _color.permute(rp, ci, va, row_perm=kw.get("row_perm"), col_perm=kw.get("col_perm"), cols=n)[:3]
+    if builder == "ilu0":
+        (m, n, (rp, ci, va)), = mats
+        assert m == n
+        return m, n, (np.asarray(rp, np.int32), np.asarray(ci, np.int32), _ilu0.factor(rp, ci, va))
     raise KeyError(builder)
 
 
@@ -116,9 +147,11 @@ class Carrier:
     leaves(vals on base) -> the operands; out_vals(vals on base) -> the values on out."""
 
     def __init__(self, kind, target, seed_name, wrong=None):
-        assert kind in KINDS
+        assert kind in ALL_KINDS
         self.kind, self.target, self.wrong = kind, target, wrong
-        self.rng = np.random.default_rng([sum(map(ord, seed_name)) * 7919 + len(seed_name), KINDS.index(kind)])
+        self._diag = None
+        seed_kind = "permuted" if kind in PERMUTED_KINDS else kind          # both routes get the same operands
+        self.rng = np.random.default_rng([sum(map(ord, seed_name)) * 7919 + len(seed_name), ALL_KINDS.index(seed_kind)])
         getattr(self, "_" + kind.replace("-", "_"))()
         # the pattern the model returns for these operands is the expectation; on a right carrier it is `out`
         zeros = np.zeros(self.base.nnz, f32)
@@ -130,6 +163,8 @@ class Carrier:
         return run_host(self.leaves(vals), self.steps)["C"]
 
     def out_vals(self, vals):
+        if self.kind == "factor-lower":
+            return self._unit_diagonal(vals, f32(1))
         if self._out_from_base is None:
             return np.asarray(vals, f32)
         v = np.zeros(self.out.nnz, f32)
@@ -221,9 +256,66 @@ class Carrier:
         self._parent(per_row, rng.choice(np.array([1.0, 2.0, 7.0], f32), st.nnz), d_score)
         self.steps = [("C", "select_topk", ("P",), dict(k=max(longest, 1), score=self._score))]
 
+    # -- permute -----------------------------------------------------------------------------------------------------------------
+    def _permuted(self, via_transpose=False):
+        st, rng = self.target, self.rng
+        p, q = rng.permutation(st.rows), rng.permutation(st.cols)
+        parent_row = p[st.row_of]
+        order = np.lexsort((rng.random(st.nnz), parent_row))            # the parent's storage order, of the target's nonzeros
+        pos = np.empty(st.nnz, np.int64)
+        pos[order] = np.arange(st.nnz)                                  # where the parent stores the target's nonzero t
+        self._p_rp = _rp(parent_row, st.rows)
+        self._p_ci = q[st.ci.astype(np.int64)][order].astype(np.int32) if st.nnz else np.zeros(0, np.int32)
+        # every row stably sorted by column, repeats in the parent's order ("unstable": in the reverse of it)
+        by = np.lexsort((-pos if self.wrong == "unstable" else pos, st.ci, st.row_of))
+        self.base = self.out = E.Structure(st.rows, st.cols, st.rp, st.ci[by])
+        self._out_from_base = None
+        self._pos_of_out = pos[by]
+        if self.wrong == "inverse":                                     # "new index perm[r] holds old index r"
+            p, q = _color.inverse(p), _color.inverse(q)
+        self.steps = [("C", "permute", ("P",), dict(row_perm=p.astype(np.int32), col_perm=q.astype(np.int32),
+                                                    via_transpose=via_transpose))]
+
+    def _permuted_via_transpose(self):
+        self._permuted(via_transpose=True)
+
+    # -- ilu0 --------------------------------------------------------------------------------------------------------------------
+    def _factor(self, lower):
+        st = self.target
+        n = max(st.rows, st.cols)
+        i, j = st.row_of, st.ci.astype(np.int64)
+        lo, hi = np.minimum(i, j), np.maximum(i, j)
+        d = np.arange(n, dtype=np.int64)
+        keys = np.unique(np.concatenate([(hi * n + lo) if lower else (lo * n + hi), d * n + d]))
+        self.base = self.out = E.Structure(n, n, _rp(keys // n, n), keys % n)
+        self._out_from_base = None
+        self._diag = np.flatnonzero(self.base.row_of == self.base.ci)
+        self.steps = [("C", "ilu0", ("A",), {})]
+
+    def _factor_upper(self):
+        self._factor(False)
+
+    def _factor_lower(self):
+        self._factor(True)
+
+    def _unit_diagonal(self, vals, one):
+        v = np.array(vals, f32)
+        v[self._diag] = one
+        return v
+
     # -- the operands ------------------------------------------------------------------------------------------------------------
     def leaves(self, vals):
         st = self.target
+        if self.kind in PERMUTED_KINDS:
+            pv = np.empty(st.nnz, f32)
+            pv[self._pos_of_out] = np.asarray(vals, f32)
+            return {"P": (st.rows, st.cols, (self._p_rp, self._p_ci, pv))}
+        if self.kind in FACTOR_KINDS:
+            b = self.base
+            va = np.asarray(vals, f32)
+            if self.kind == "factor-lower":
+                va = self._unit_diagonal(vals, f32(2) if self.wrong == "diagonal_not_one" else f32(1))
+            return {"A": (b.rows, b.cols, (b.rp, b.ci, va))}
         if self.kind in ("threshold", "topk"):
             pv = np.full(self._is_target.size, np.nan, f32)
             pv[self._is_target] = np.asarray(vals, f32)
@@ -250,10 +342,35 @@ def carrier(kind, name, pkg=None, oracle=None):
     return Carrier(kind, E.structure(name, pkg, oracle), name)
 
 
+def exact_on(c, seed_name, scaled=True):
+    """_exact.Exact on the carrier's base.  factor-lower: the diagonal's k is 1 and no row is scaled, so that vals() holds the 1
+    the carrier needs there and the integer sums stay exact."""
+    ex = E.Exact(c.base, seed_name, scaled=scaled and c.kind != "factor-lower")
+    if c.kind == "factor-lower":
+        ex.k[c._diag] = 1
+    return ex
+
+
 def exact_problems(c, seed_name):
-    """Exact data on the carrier's base: the Exact and [(label, vals on base, x, expected y)] (integer and subnormal)."""
-    ex = E.Exact(c.base, seed_name)
-    return ex, [("int", ex.vals(), ex.x(), ex.expected()), ("subnormal", ex.sub_vals(), ex.sub_x(), ex.sub_expected())]
+    """Exact data on the carrier's base: the Exact and [(label, vals on base, x, expected y)] (integer and subnormal).
+
+    factor-lower, subnormal: the diagonal is 1 among values k 2^-75, so row i holds one term m_i 2^-74 beside terms that are
+    multiples of 2^-149 and sum to less than 2^-125 in magnitude.  A partial sum without the diagonal term is such a multiple,
+    exact; one with it (m_i != 0) is m_i 2^-74 plus less than 2^-125, which rounds back to m_i 2^-74 (half an ulp is at least
+    2^-98).  So in every order y_i = m_i 2^-74 where m_i != 0 and the exact sum of the other terms where m_i = 0."""
+    ex = exact_on(c, seed_name)
+    sub_vals, sub_want = ex.sub_vals(), None
+    if c.kind == "factor-lower":
+        on_diag = np.zeros(c.base.nnz, bool)
+        on_diag[c._diag] = True
+        sub_vals = c._unit_diagonal(sub_vals, f32(1))
+        others = ex.int_sums(keep=~on_diag)
+        assert np.abs(others).max(initial=0) < 1 << 24
+        sub_want = np.where(ex.m != 0, np.ldexp(ex.m.astype(np.float64), E.SUB_X_EXP),
+                            np.ldexp(others.astype(np.float64), E.SUB_VAL_EXP + E.SUB_X_EXP)).astype(f32)
+    else:
+        sub_want = ex.sub_expected()
+    return ex, [("int", ex.vals(), ex.x(), ex.expected()), ("subnormal", sub_vals, ex.sub_x(), sub_want)]
 
 
 def spmm_problem(ex, k, seed):
@@ -315,9 +432,9 @@ def _empty(rows, cols):
 
 
 class Program:
-    def __init__(self, name, leaves, steps, equal_patterns=(), empty=()):
+    def __init__(self, name, leaves, steps, equal_patterns=(), empty=(), equal_bytes=()):
         self.name, self.leaves, self.steps = name, leaves, steps
-        self.equal_patterns, self.empty = tuple(equal_patterns), tuple(empty)
+        self.equal_patterns, self.empty, self.equal_bytes = tuple(equal_patterns), tuple(empty), tuple(equal_bytes)
 
     @functools.cached_property
     def host(self):
@@ -325,9 +442,21 @@ class Program:
         return run_host(self.leaves, self.steps)
 
 
-def _feed(z, partner, sq):
-    """An empty m x n handle `z` fed to every builder; `partner` has z's shape, `sq` is n x m."""
-    return [(z + "_x_sq", "spgemm", (z, sq), {}), ("sq_x_" + z, "spgemm", (sq, z), {}),
+def _perm(seed, n):
+    return np.random.default_rng(seed).permutation(n).astype(np.int32)
+
+
+def identity(n):
+    """I of order n."""
+    return n, n, (np.arange(n + 1, dtype=np.int32), np.arange(n, dtype=np.int32), np.ones(n, f32))
+
+
+def _feed(z, partner, sq, rows, cols):
+    """An empty rows x cols handle `z` fed to every builder; `partner` has z's shape, `sq` is cols x rows."""
+    return [(z + "_same", "permute", (z,), {}),
+            (z + "_moved", "permute", (z,), dict(row_perm=_perm(3130 + rows, rows), col_perm=_perm(3131 + cols, cols))),
+            (z + "_moved_by_transposes", "permute", (z,), dict(row_perm=_perm(3132 + rows, rows), via_transpose=True)),
+            (z + "_x_sq", "spgemm", (z, sq), {}), ("sq_x_" + z, "spgemm", (sq, z), {}),
             (z + "_or_p", "add", (z, partner), dict(alpha=THIRD, beta=3.0, op="union")),
             ("p_minus_" + z, "add", (partner, z), dict(alpha=THIRD, beta=3.0, op="minus")),
             ("p_and_" + z, "add", (partner, z), dict(alpha=THIRD, beta=3.0, op="intersect")),
@@ -363,22 +492,64 @@ def programs():
         # columns name empty rows of b), and leaves with m = 0 and n = 0
         Program("empty_intersection", {"A": _columns(3112, 257, 257, 40, 0, 257, 2), "B": _columns(3113, 257, 257, 40, 1, 257, 2),
                                        "SQ": leaf(3114, 257, 257, 20)},
-                [("Z", "add", ("A", "B"), dict(mix, op="intersect"))] + _feed("Z", "A", "SQ"), empty=("Z",)),
+                [("Z", "add", ("A", "B"), dict(mix, op="intersect"))] + _feed("Z", "A", "SQ", 257, 257), empty=("Z",)),
         Program("product_without_terms", {"A": _columns(3115, 257, 193, 40, 0, 100),
                                           "B": _rows_from(100, leaf(3116, 93, 257, 40)), "P0": leaf(3117, 257, 257, 20)},
-                [("Z", "spgemm", ("A", "B"), {})] + _feed("Z", "P0", "P0"), empty=("Z",)),
+                [("Z", "spgemm", ("A", "B"), {})] + _feed("Z", "P0", "P0", 257, 257), empty=("Z",)),
         Program("no_rows", {"Z": _empty(0, 193), "P0": _empty(0, 193), "SQ": _empty(193, 0)},
-                _feed("Z", "P0", "SQ"), empty=("Z",)),
+                _feed("Z", "P0", "SQ", 0, 193), empty=("Z",)),
         Program("no_columns", {"Z": _empty(257, 0), "P0": _empty(257, 0), "SQ": _empty(0, 257)},
-                _feed("Z", "P0", "SQ"), empty=("Z",)),
+                _feed("Z", "P0", "SQ", 257, 0), empty=("Z",)),
         Program("self_operands", {"A": leaf(3119, 257, 257, 24)},
                 [("T", "transpose", ("A",), {}), ("C", "add", ("A", "T"), dict(mix, op="union")),
                  ("CC", "spgemm", ("C", "C"), {}), ("C2", "add", ("C", "C"), dict(mix, op="union"))]),
         # (i) a row of 1500 entries over rows of 0 .. 60: more than 32768 terms on 3001 columns
         Program("oversized_then_selected", {"A": leaf(3120, 257, 193, long_row=1500), "B": leaf(3121, 193, 3001, 60)},
                 [("P", "spgemm", ("A", "B"), {}), ("K", "select_topk", ("P",), dict(k=5, abs=True))]),
+        # permute(transpose(A), q, p) and transpose(permute(A, p, q)): the same pattern and the same bytes (repeats stay in A's
+        # storage order on both ways)
+        Program("permute_commutes", {"A": leaf(3122, 257, 193, long_row=LONG_ROW)},
+                [("T", "transpose", ("A",), {}), ("L", "permute", ("T",), dict(row_perm=_perm(3123, 193), col_perm=_perm(3124, 257))),
+                 ("B", "permute", ("A",), dict(row_perm=_perm(3124, 257), col_perm=_perm(3123, 193))), ("R", "transpose", ("B",), {})],
+                equal_patterns=[("L", "R")], equal_bytes=[("L", "R")]),
+        # (P A Q^T) (Q B R^T) against P (A B) R^T: the same pattern; the sums of a row take their terms in another order
+        Program("permuted_product", {"A": leaf(3125, 257, 193), "B": leaf(3126, 193, 257)},
+                [("PA", "permute", ("A",), dict(row_perm=_perm(3127, 257), col_perm=_perm(3128, 193))),
+                 ("PB", "permute", ("B",), dict(row_perm=_perm(3128, 193), col_perm=_perm(3129, 257), via_transpose=True)),
+                 ("L", "spgemm", ("PA", "PB"), {}), ("P", "spgemm", ("A", "B"), {}),
+                 ("R", "permute", ("P",), dict(row_perm=_perm(3127, 257), col_perm=_perm(3129, 257)))], equal_patterns=[("L", "R")]),
     ]
     return {p.name: p for p in out}
+
+
+@functools.lru_cache(maxsize=None)
+def colour_of_a_product():
+    """P = A A^T, S = P + I (sorted, with a diagonal), the colouring of S, B = permute(S, perm, perm), M = ILU(0) of B and
+    z = U^-1 L^-1 r, all on the host: leaves, env (T, P, S, B, M), color (colour, perm, color_ptr, info), r, z."""
+    leaves = {"A": leaf(3140, 257, 193, 6, special=0.0), "I": identity(257)}
+    env = run_host(leaves, [("T", "transpose", ("A",), {}), ("P", "spgemm", ("A", "T"), {}), ("S", "add", ("P", "I"), dict(op="union"))])
+    rp, ci, _ = env["S"][2]
+    coloring = _color.color(rp, ci)
+    perm = coloring[1]
+    env["B"] = host_step("permute", [env["S"]], row_perm=perm, col_perm=perm)
+    env["M"] = host_step("ilu0", [env["B"]])
+    r = _trsv.rhs(257, np.random.default_rng(3141))
+    return dict(leaves=leaves, env=env, color=coloring, r=r, z=_ilu0.apply(*env["M"][2], r))
+
+
+SOLVED = ("a_plus_at", "self_operands")          # the programs whose square steps are planned and solved, and a top-k of each
+SOLVED_K = 5
+
+
+def triangles(mat):
+    """{uplo: (level_ptr, order, the UNIT solve's x)} of a square matrix by tests/_trsv.py, and the right-hand side."""
+    n, _, (rp, ci, va) = mat
+    b = _trsv.rhs(n, np.random.default_rng(3142))
+    out = {}
+    for uplo in _trsv.UPLOS:
+        lev = _trsv.levels(rp, ci, uplo)
+        out[uplo] = _trsv.order(lev) + (_trsv.solve(rp, ci, va, b, uplo, unit=True, lev=lev),)
+    return out, b
 
 
 def _rows_from(first, mat):
@@ -388,4 +559,5 @@ def _rows_from(first, mat):
 
 
 PROGRAMS = ("a_plus_at", "aat_topk", "pattern_algebra", "distributive", "transpose_of_product", "threshold_transposed",
-            "empty_intersection", "product_without_terms", "no_rows", "no_columns", "self_operands", "oversized_then_selected")
+            "empty_intersection", "product_without_terms", "no_rows", "no_columns", "self_operands", "oversized_then_selected",
+            "permute_commutes", "permuted_product")

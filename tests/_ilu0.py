@@ -244,14 +244,19 @@ def _bad(v):
 
 
 def _dot(a, b):
-    return f32(np.dot(a, b))
+    return a.dtype.type(np.dot(a, b))
 
 
-def pcg(spmv, prec, b, x, tol=1e-5, maxiter=1000):
-    """(x, iterations, converged): float32 throughout; `spmv(v)` gives A v, `prec(r)` M^-1 r (None: r).  The steps of solvers.pcg."""
-    b, x = np.asarray(b, f32), np.array(x, f32)
+KRYLOV_WRONG = ("beta_inverted", "p_sign")      # other iterations that still converge on the test systems: 1 / beta for beta, p
+                                                # updated with the opposite sign of its old direction
+
+
+def pcg(spmv, prec, b, x, tol=1e-5, maxiter=1000, dtype=f32, wrong=None):
+    """(x, iterations, converged): `dtype` throughout; `spmv(v)` gives A v, `prec(r)` M^-1 r (None: r).  The steps of solvers.pcg."""
+    assert wrong is None or wrong in KRYLOV_WRONG
+    b, x = np.asarray(b, dtype), np.array(x, dtype)
     prec = prec or (lambda v: v.copy())
-    r = (b - spmv(x)).astype(f32)
+    r = (b - spmv(x)).astype(dtype)
     z = prec(r)
     p = z.copy()
     q = spmv(p)
@@ -262,33 +267,35 @@ def pcg(spmv, prec, b, x, tol=1e-5, maxiter=1000):
             return x, it, True
         if it >= maxiter or _bad(rho) or _bad(den) or np.isnan(rr):
             return x, it, False
-        alpha = f32(float(rho) / float(den))
-        x = (x + alpha * p).astype(f32)
-        r = (r - alpha * q).astype(f32)
+        alpha = dtype(float(rho) / float(den))
+        x = (x + alpha * p).astype(dtype)
+        r = (r - alpha * q).astype(dtype)
         it += 1
         z = prec(r)
         rr, rho_new = _dot(r, r), _dot(r, z)
-        p = (z + f32(rho_new / rho) * p).astype(f32)
+        beta = dtype(rho / rho_new) if wrong == "beta_inverted" else dtype(rho_new / rho)
+        p = (z - beta * p).astype(dtype) if wrong == "p_sign" else (z + beta * p).astype(dtype)
         q = spmv(p)
         den, rho = _dot(p, q), rho_new
 
 
-def bicgstab(spmv, prec, b, x, tol=1e-5, maxiter=1000):
-    """(x, iterations, converged): right-preconditioned BiCGStab, float32 throughout.  The steps of solvers.bicgstab."""
-    b, x = np.asarray(b, f32), np.array(x, f32)
+def bicgstab(spmv, prec, b, x, tol=1e-5, maxiter=1000, dtype=f32, wrong=None):
+    """(x, iterations, converged): right-preconditioned BiCGStab, `dtype` throughout.  The steps of solvers.bicgstab."""
+    assert wrong is None or wrong in KRYLOV_WRONG
+    b, x = np.asarray(b, dtype), np.array(x, dtype)
     prec = prec or (lambda v: v.copy())
     n = b.size
-    r = (b - spmv(x)).astype(f32)
+    r = (b - spmv(x)).astype(dtype)
     rhat = r.copy()
-    p, v = np.zeros(n, f32), np.zeros(n, f32)
+    p, v = np.zeros(n, dtype), np.zeros(n, dtype)
     rr, bb = _dot(r, r), _dot(b, b)
-    rho = alpha = omega = den = tt = f32(1)
+    rho = alpha = omega = den = tt = dtype(1)
     it = 0
 
     def guarded(num, d):
         with np.errstate(all="ignore"):
-            qv = f32(num) / f32(d)
-        return qv if np.isfinite(qv) and d != 0 else f32(0)
+            qv = dtype(num) / dtype(d)
+        return qv if np.isfinite(qv) and d != 0 else dtype(0)
 
     while True:
         if float(rr) <= tol * tol * float(bb):
@@ -297,19 +304,66 @@ def bicgstab(spmv, prec, b, x, tol=1e-5, maxiter=1000):
             return x, it, False
         it += 1
         rho_new = _dot(rhat, r)
-        beta = guarded(rho_new * alpha, rho * omega)
-        p = (r + beta * (p - omega * v)).astype(f32)
+        beta = guarded(rho * omega, rho_new * alpha) if wrong == "beta_inverted" else guarded(rho_new * alpha, rho * omega)
+        p = (r - beta * (p - omega * v)).astype(dtype) if wrong == "p_sign" else (r + beta * (p - omega * v)).astype(dtype)
         y = prec(p)
         v = spmv(y)
         den = _dot(rhat, v)
         alpha = guarded(rho_new, den)
-        s = (r - alpha * v).astype(f32)
+        s = (r - alpha * v).astype(dtype)
         z = prec(s)
         t = spmv(z)
         tt, ts = _dot(t, t), _dot(t, s)
         omega = guarded(ts, tt)
-        x = (x + alpha * y + omega * z).astype(f32)
-        r = (s - omega * t).astype(f32)
+        x = (x + alpha * y + omega * z).astype(dtype)
+        r = (s - omega * t).astype(dtype)
         rr, rho = _dot(r, r), rho_new
         if rr == 0:
-            tt = omega = f32(1)
+            tt = omega = dtype(1)
+
+
+# ---- the iterates of the twins: what tests/test_gpu_krylov.py compares the solvers' x with --------------------------------------
+KRYLOV_KS = (1, 2, 4)
+NEVER = 1e-20             # a tol no iterate meets: the iteration stops at maxiter
+
+
+def krylov_systems(pkg):
+    """kind -> (the system, the twin): the 512-row versions of the systems of tests/test_gpu_krylov.py."""
+    return {"pcg": (symmetric_stencil(pkg, 8), pcg), "bicgstab": (stencil_case(pkg, 8), bicgstab)}
+
+
+def apply64(rp, ci, M):
+    """r -> U^-1 (L^-1 r) in float64 with the float32 factor M widened: dense solves (the systems here have 512 rows)."""
+    D = dense(rp, ci, M)
+    L, U = np.tril(D, -1) + np.eye(D.shape[0]), np.triu(D)
+    return lambda r: np.linalg.solve(U, np.linalg.solve(L, np.asarray(r, f64)))
+
+
+def twin_iterates(twin, system, b, with_m, dtype, spmv32=None, wrong=None, ks=KRYLOV_KS):
+    """{k: x after k iterations from x = 0}: float64 (csr_spmv64, apply64) or float32 (spmv32: a float32 product such as the
+    oracle's serial sum; apply()), in both with the factor of factor()."""
+    n, rp, ci, va = system
+    M = factor(rp, ci, va) if with_m else None
+    if dtype is f64:
+        spmv = lambda v: csr_spmv64(rp, ci, va, v)
+        prec = apply64(rp, ci, M) if with_m else None
+    else:
+        spmv = lambda v: spmv32(rp, ci, va, v)
+        prec = (lambda v: apply(rp, ci, M, v)) if with_m else None
+    out = {}
+    for k in ks:
+        x, it, _ = twin(spmv, prec, np.asarray(b, dtype), np.zeros(n, dtype), NEVER, k, dtype=dtype, wrong=wrong)
+        assert it == k, (it, k)
+        out[k] = x
+    return out
+
+
+def deviation(x, ref):
+    """max |x - ref| / max |ref| in float64."""
+    return float(np.max(np.abs(np.asarray(x, f64) - np.asarray(ref, f64))) / np.max(np.abs(np.asarray(ref, f64))))
+
+
+def krylov_bound(d, k):
+    """What a float32 solver may deviate from the float64 twin after k iterations: 8 max(d(k), k 2^-23), d(k) the float32 twin's
+    own deviation; the factor 8 is for another order of the dot products and of the rows' sums."""
+    return 8 * max(d, k * 2.0 ** -23)

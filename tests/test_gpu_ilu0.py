@@ -119,6 +119,64 @@ def test_level_sizes_around_an_explicit_thin_threshold(pkg, gpu):
     A.close()
 
 
+EDGE_STAIRS = (255, 256, 257, 256, 255, 1, 257)             # around the peel's workgroup of 256 rows and SPMV_TRSV_THIN_DEFAULT
+
+
+@pytest.mark.gpu
+def test_a_chain_deeper_than_one_launch_of_the_small_peel(pkg, gpu):
+    """4100 levels of one row: the plans' one-workgroup peel retires 4096 levels a launch and the host loop goes on from the live
+    frontier.  The factor, the factor again from new values, and the solve, bit for bit."""
+    import torch
+    n, rp, ci, va = G.tridiagonal_case(4100)
+    A, (_, _, d_va) = _borrowed(pkg.capi, gpu, n, rp, ci, va)
+    M = A.ilu0()
+    lo, up = M.trsv_plan_info("lower"), M.trsv_plan_info("upper")
+    for uplo, info in (("lower", lo), ("upper", up)):
+        assert (info["levels"], info["widest"], info["launches"]) == (n, 1, -(-n // info["level_cap"])), info
+        lp, od = T.order(T.levels(rp, ci, uplo))
+        got_lp, got_od = M.trsv_plan_rows(uplo)
+        assert np.array_equal(got_lp, lp) and np.array_equal(got_od, od), f"{uplo}: the plan's rows"
+    want = G.factor(rp, ci, va)
+    assert G.same(_vals(M), want) is None, G.same(_vals(M), want)
+    r = T.rhs(n, np.random.default_rng(5))
+    z = M.ilu0_solve(_dev(gpu, r))
+    torch.cuda.synchronize()
+    assert G.same(z.cpu().numpy(), G.apply(rp, ci, want, r)) is None
+    row = np.repeat(np.arange(n), np.diff(rp))
+    nv = np.where(ci == row, va * f32(1.5), va * f32(0.75)).astype(f32)          # still dominant
+    d_va.copy_(_dev(gpu, nv))
+    M.ilu0_values(A)
+    want2 = G.factor(rp, ci, nv)
+    assert G.differs(want, want2) > n and G.same(_vals(M), want2) is None, "after ilu0_values"
+    z = M.ilu0_solve(_dev(gpu, r))
+    torch.cuda.synchronize()
+    assert G.same(z.cpu().numpy(), G.apply(rp, ci, want2, r)) is None
+    assert M.ilu0_pivot() == -1
+    M.close()
+    A.close()
+
+
+@pytest.mark.gpu
+def test_level_sizes_around_the_peel_workgroup_and_the_default_thin_threshold(pkg, gpu):
+    n, rp, ci, va = G.stairs_case(EDGE_STAIRS)
+    A = _owned(pkg.capi, n, rp, ci, va)
+    M = A.ilu0(thin_rows=0)
+    lo = M.trsv_plan_info("lower")
+    assert np.array_equal(np.diff(M.trsv_plan_rows("lower")[0]), EDGE_STAIRS)
+    assert lo["thin_rows"] == 256 and lo["launches"] == 4                       # [255, 256] [257] [256, 255, 1] [257]
+    lp, od = T.order(T.levels(rp, ci, "upper"))
+    got_lp, got_od = M.trsv_plan_rows("upper")
+    assert np.array_equal(got_lp, lp) and np.array_equal(got_od, od)
+    want = G.factor(rp, ci, va)
+    bad = G.same(_vals(M), want)
+    assert bad is None, bad
+    r = T.rhs(n, np.random.default_rng(6))
+    z = M.ilu0_solve(_dev(gpu, r))
+    assert G.same(z.cpu().numpy(), G.apply(rp, ci, want, r)) is None
+    M.close()
+    A.close()
+
+
 # ---- 2. purity -----------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 def test_purity_streams_and_owners(pkg, gpu):

@@ -11,13 +11,26 @@ the plain iterations: the twins measured a third, the margin is for torch's diff
 residual computed on the host is at most 2 tol: the recurrence residual the solvers stop on drifts from the true one by
 rounding only.  On system 2 the twin took 35 iterations of BiCGStab without and 10 with ILU(0) (5.9e-6 and 4.9e-6): the test
 asserts no more iterations with M than without, and the same residual bound.
+
+The iterates.  Convergence alone passes a wrong coefficient that still converges, so x after k = 1, 2 and 4 iterations from x = 0
+(maxiter = k, a tol nothing meets) is compared with the numpy twin run in float64 on the 512-row versions of both systems, with
+and without M (the factor of _ilu0.factor in both).  The bound is 8 max(d(k), k 2^-23) with d(k) the FLOAT32 twin's deviation
+from the float64 twin (max norm, relative to x), computed again here and never taken from the solver; the factor 8 is for torch's
+order of the dot products.  tests/test_ilu0_host.py measured d(k) and shows that 1 / beta for beta and p updated with the
+opposite sign leave the bound by k = 4 (deviations of 3.4e-4 .. 0.69 against bounds below 4e-6):
+    pcg       without M  d = 7.4e-8, 1.6e-7, 7.7e-8     with M  d = 7.9e-8, 1.2e-7, 1.4e-7
+    bicgstab  without M  d = 8.7e-8, 7.8e-8, 7.8e-8     with M  d = 1.7e-7, 1.5e-7, 1.2e-7
+On an MI355X the solvers deviated by 6.6e-8 .. 1.7e-7 (each case prints d(k), the device's deviation and the bound).
+solvers.multicolor(A).solve gets the same check through the permutation: the iterate it brings back against the twin run on
+_color.permute's matrix and un-permuted on the host.
 """
 import numpy as np
 import pytest
 
+import _color
 import _ilu0 as G
 
-f32 = np.float32
+f32, f64 = np.float32, np.float64
 TOL = 1e-5
 
 
@@ -63,6 +76,79 @@ def test_bicgstab_with_ilu0_takes_no_more_iterations(pkg, gpu):
     assert ok0 and ok1
     assert it1 <= it0, (it0, it1)
     assert res0 <= 2 * TOL and res1 <= 2 * TOL, (res0, res1)
+
+
+def _check_iterates(what, got, ref, f32_twin):
+    """got, ref, f32_twin: {k: x}.  Prints d(k) beside the device's deviation and asserts the bound."""
+    for k in G.KRYLOV_KS:
+        d, dev = G.deviation(f32_twin[k], ref[k]), G.deviation(got[k], ref[k])
+        print(f"{what} k={k}: d(k) = {d:.2e}, the device's deviation {dev:.2e}, the bound {G.krylov_bound(d, k):.2e}")
+        assert np.all(np.isfinite(got[k])) and dev <= G.krylov_bound(d, k), f"{what} k={k}: {dev:.3g} against {G.krylov_bound(d, k):.3g}"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_m", (False, True))
+@pytest.mark.parametrize("kind", ("pcg", "bicgstab"))
+def test_the_iterates_are_the_float64_twins(pkg, oracle, gpu, kind, with_m):
+    import torch
+    system, twin = G.krylov_systems(pkg)[kind]
+    n, rp, ci, va = system
+    b = G.krylov_rhs(n)
+    ref = G.twin_iterates(twin, system, b, with_m, f64)
+    f32_twin = G.twin_iterates(twin, system, b, with_m, f32, spmv32=oracle.spmv)
+    A = pkg.capi.CsrMatrix.from_host(n, n, rp, ci, va)
+    M = A.ilu0() if with_m else None
+    d_b = _dev(gpu, b)
+    got = {}
+    for k in G.KRYLOV_KS:
+        x = torch.zeros(n, device=gpu)
+        res = getattr(pkg.solvers, kind)(A, d_b, x, M=M, tol=G.NEVER, maxiter=k)
+        torch.cuda.synchronize()
+        assert res.iterations == k and not res.converged
+        got[k] = x.cpu().numpy()
+    _check_iterates(f"{kind} {'with' if with_m else 'without'} M", got, ref, f32_twin)
+    if M is not None:
+        M.close()
+    A.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ("pcg", "bicgstab"))
+def test_the_iterates_through_the_multicolour_ordering(pkg, oracle, gpu, kind):
+    """Reordering.solve: P b and P x forward, the solver on P A P^T with its ILU(0), x brought back by backward.  The twin runs
+    on _color.permute's matrix with b[perm], and its x goes back by x[perm[r]] = x_B[r]."""
+    import torch
+    (n, rp, ci, va), twin = G.krylov_systems(pkg)[kind]
+    b = G.krylov_rhs(n)
+    perm = _color.color(rp, ci)[1]
+    brp, bci, bva, _ = _color.permute(rp, ci, va, perm, perm)
+    system = (n, brp, bci, bva)
+
+    def back(xs):
+        out = {}
+        for k, xb in xs.items():
+            out[k] = np.empty_like(xb)
+            out[k][perm] = xb
+        return out
+
+    ref = back(G.twin_iterates(twin, system, b[perm], True, f64))
+    f32_twin = back(G.twin_iterates(twin, system, b[perm], True, f32, spmv32=oracle.spmv))
+    A = pkg.capi.CsrMatrix.from_host(n, n, rp, ci, va)
+    R = pkg.solvers.multicolor(A)
+    assert np.array_equal(R.perm.cpu().numpy(), perm)
+    M = R.matrix.ilu0()
+    d_b = _dev(gpu, b)
+    got = {}
+    for k in G.KRYLOV_KS:
+        x = torch.zeros(n, device=gpu)
+        res = R.solve(getattr(pkg.solvers, kind), d_b, x, M=M, tol=G.NEVER, maxiter=k)
+        torch.cuda.synchronize()
+        assert res.iterations == k and not res.converged
+        got[k] = x.cpu().numpy()
+    _check_iterates(f"{kind} through the multicolour ordering", got, ref, f32_twin)
+    M.close()
+    R.close()
+    A.close()
 
 
 @pytest.mark.gpu

@@ -155,6 +155,45 @@ def test_level_sizes_around_an_explicit_thin_threshold(pkg, gpu, uplo):
     A.close()
 
 
+DEEP_CHAINS = ((4097, "lower"), (8193, "upper"))           # more levels than one launch of the plan's small peel retires (4096)
+EDGE_STAIRS = (255, 256, 257, 256, 255, 1, 257)             # around the peel's workgroup of 256 rows and SPMV_TRSV_THIN_DEFAULT
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,uplo", DEEP_CHAINS)
+def test_chains_deeper_than_one_launch_of_the_small_peel(pkg, gpu, n, uplo):
+    """The plan's one-workgroup peel stops after 4096 levels and hands a live frontier back to the host loop, which starts the
+    next launch one level further (4097: once, with one row left; 8193: twice).  Levels, order and x against numpy, under the
+    three thin thresholds."""
+    n, rp, ci, va, b = G.chain_case(n, uplo)
+    want = G.solve(rp, ci, va, b, uplo)
+    for thin in (1, 0, 1 << 30):
+        A = _owned(pkg.capi, n, rp, ci, va)
+        A.trsv_plan(uplo, thin_rows=thin)
+        info = _check_plan(A, rp, ci, uplo, thin=thin)       # (plan_rows against _trsv.order, launches by the merging rule)
+        assert (info["levels"], info["widest"]) == (n, 1)
+        assert info["launches"] == -(-n // info["level_cap"]), info
+        bad = G.same(_solve(gpu, A, b, uplo), want)
+        assert bad is None, f"thin_rows={thin}: {bad}"
+        A.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("uplo", UPLOS)
+def test_level_sizes_around_the_peel_workgroup_and_the_default_thin_threshold(pkg, gpu, uplo):
+    """Frontiers of 255, 256, 257, 256, 255, 1, 257 rows: the plan's peel changes between its one-workgroup and its grid kernel
+    in both directions at the edge, and the solve crosses the default thin threshold at the same sizes."""
+    n, rp, ci, va, b = G.stairs_case(EDGE_STAIRS, uplo)
+    A = _owned(pkg.capi, n, rp, ci, va)
+    A.trsv_plan(uplo, thin_rows=0)
+    info = _check_plan(A, rp, ci, uplo)
+    assert info["thin_rows"] == 256 and info["launches"] == 4   # [255, 256] [257] [256, 255, 1] [257]
+    assert np.array_equal(np.diff(A.trsv_plan_rows(uplo)[0]), EDGE_STAIRS)
+    bad = G.same(_solve(gpu, A, b, uplo), G.solve(rp, ci, va, b, uplo))
+    assert bad is None, bad
+    A.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("uplo", UPLOS)
 def test_stencil7(pkg, gpu, uplo):

@@ -203,6 +203,49 @@ def test_the_numpy_krylov_twins_converge_and_ilu0_helps(pkg, oracle, kind):
     assert (2 * it1 <= it0) if kind == "pcg" else (it1 <= it0)
 
 
+def test_the_cases_beyond_the_per_launch_caps_have_the_levels_they_claim():
+    """tridiagonal_case(4100): 4100 levels of one row in both triangles, more than one launch of the plans' small peel retires
+    (4096); stairs_case around the peel's workgroup of 256 rows: lower levels of exactly these sizes.  Both stay dominant."""
+    n, rp, ci, va = G.tridiagonal_case(4100)
+    assert n == 4100 and np.array_equal(T.levels(rp, ci, "lower"), np.arange(n)) and np.array_equal(T.levels(rp, ci, "upper"), np.arange(n)[::-1])
+    sizes = (255, 256, 257, 256, 255, 1, 257)
+    m, srp, sci, sva = G.stairs_case(sizes)
+    assert m == sum(sizes) and np.array_equal(np.diff(T.order(T.levels(srp, sci, "lower"))[0]), sizes)
+    assert T.levels(srp, sci, "upper").max() >= 1
+    for name, (k, a, b, c) in (("tridiagonal", (n, rp, ci, va)), ("stairs", (m, srp, sci, sva))):
+        assert G.is_sorted(a, b) and G.dominance(a, b, c) <= 0.9 * (1 + 1e-6), name
+        M = G.factor(a, b, c)
+        assert np.all(np.isfinite(M)) and G.differs(M, c) > k // 2, name
+
+
+# ---- (f) the iterates of the twins -------------------------------------------------------------------------------------------
+def _iterates(pkg, oracle, kind, with_m, wrong=None, dtype=f64):
+    system, twin = G.krylov_systems(pkg)[kind]
+    return G.twin_iterates(twin, system, G.krylov_rhs(system[0]), with_m, dtype, spmv32=oracle.spmv, wrong=wrong)
+
+
+@pytest.mark.parametrize("with_m", (False, True))
+@pytest.mark.parametrize("kind", ("pcg", "bicgstab"))
+def test_the_float32_twins_stay_close_to_the_float64_twins_and_wrong_ones_do_not(pkg, oracle, kind, with_m):
+    """d(k): the float32 twin's deviation from the float64 twin after k = 1, 2, 4 iterations from x = 0 (max norm, relative to
+    the float64 x), printed; tests/test_gpu_krylov.py allows the solvers 8 max(d(k), k 2^-23).  Two wrong iterations -- 1 / beta
+    for beta, and p updated with the opposite sign -- are the same as the right one at k = 1 (no beta yet) and exceed that bound
+    by k = 4, in float64 and in float32 alike: the bound tells them apart."""
+    ref = _iterates(pkg, oracle, kind, with_m)
+    f32_twin = _iterates(pkg, oracle, kind, with_m, dtype=f32)
+    d = {k: G.deviation(f32_twin[k], ref[k]) for k in G.KRYLOV_KS}
+    print(f"{kind} {'with' if with_m else 'without'} M: d(k) = " + ", ".join(f"{k}: {d[k]:.2e}" for k in G.KRYLOV_KS))
+    for k in G.KRYLOV_KS:
+        assert np.all(np.isfinite(ref[k])) and d[k] <= 1e-5, (k, d[k])
+    for wrong in G.KRYLOV_WRONG:
+        for dtype in (f64, f32):
+            bad = _iterates(pkg, oracle, kind, with_m, wrong=wrong, dtype=dtype)
+            dev = {k: G.deviation(bad[k], ref[k]) for k in G.KRYLOV_KS}
+            print(f"  {wrong} in {dtype.__name__}: " + ", ".join(f"{k}: {dev[k]:.2e}" for k in G.KRYLOV_KS))
+            assert dev[1] <= G.krylov_bound(d[1], 1), (wrong, dev)
+            assert dev[4] > G.krylov_bound(d[4], 4), f"{wrong}: {dev[4]:.3g} is inside the bound {G.krylov_bound(d[4], 4):.3g}"
+
+
 def test_the_twins_report_a_breakdown():
     b = np.array([1.0, -2.0, 0.5, 3.0], f32)
     zero = lambda v: np.zeros(4, f32)

@@ -185,6 +185,28 @@ def test_the_shared_cases_have_the_rows_they_claim():
     assert np.array_equal(np.diff(G.order(G.levels(rp, ci, "lower"))[0]), (10, 5000))
 
 
+def test_the_cases_beyond_the_per_launch_caps_have_the_levels_they_claim():
+    """The chains deeper than one launch of the plan's small peel (4096 levels), and level sizes on either side of its
+    workgroup of 256 rows: the level counts and sizes by the serial definition, so that a wrong reference cannot hide a wrong
+    kernel; every x is finite and the chain's rows depend on their one neighbour."""
+    for n, u in ((4097, "lower"), (8193, "upper")):
+        m, rp, ci, va, b = G.chain_case(n, u)
+        lev = G.levels(rp, ci, u)
+        assert m == n and np.array_equal(lev, np.arange(n) if u == "lower" else np.arange(n)[::-1])
+        lp, od = G.order(lev)
+        assert np.all(np.diff(lp) == 1) and np.array_equal(od, np.arange(n) if u == "lower" else np.arange(n)[::-1])
+        count = G.terms(rp, ci, u)[3]
+        assert count.sum() == n - 1 and count.max() == 1
+        x = G.solve(rp, ci, va, b, u)
+        assert np.all(np.isfinite(x)) and np.all(x != 0)
+        assert G.differs(x, G.solve(rp, ci, va, b, u, wrong="from_b")) >= 1
+    sizes = (255, 256, 257, 256, 255, 1, 257)
+    for u in G.UPLOS:
+        n, rp, ci, va, b = G.stairs_case(sizes, u)
+        assert n == sum(sizes) and np.array_equal(np.diff(G.order(G.levels(rp, ci, u))[0]), sizes)
+        assert np.all(np.isfinite(G.solve(rp, ci, va, b, u)))
+
+
 def test_gauss_seidel_twin_reduces_the_residual(pkg):
     n, rp, ci, va, b = G.stencil_case(pkg)
     A = np.zeros((n, n))
