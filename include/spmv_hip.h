@@ -727,6 +727,13 @@ SPMV_API int64_t spmv_csr_plan_bytes(const spmv_csr_t *h, int variant);
  * written to buf (NUL-terminated, truncated to n). */
 SPMV_API int spmv_csr_plan_describe(const spmv_csr_t *h, int variant, char *buf, int n);
 
+/* The order in which the one launch of a SPMV_TILED plan with chunks of several kinds takes them (SPMV_AUTO: where it
+ * resolved to SPMV_TILED): 0 = no such launch (every chunk is of one kind, or the plan is persistent), 1 = lists (the
+ * 32-bit chunks first, then the sorted, then the 16-bit ones), 2 = identity (workgroup b takes chunk b of its XCD's range,
+ * no chunk list is read).  The plan picks it from the share of chunks without 16-bit columns; SPMV_TILED_ORDER=identity|lists
+ * in the environment forces one when the plan is made.  y does not depend on it.  Negative: an error code. */
+SPMV_API int spmv_csr_plan_chunk_order(const spmv_csr_t *h, int variant);
+
 /* Run `iters` back-to-back launches on `stream` between two HIP events
  * recorded on that same stream; returns the mean milliseconds per launch.
  * replaces: TIME_KERNEL (src/include/kernel.hpp:31-48). */

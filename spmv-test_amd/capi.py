@@ -117,6 +117,7 @@ SIGNATURES = {
     "spmv_csr_plan_like": (C.c_int, [_H, _H, C.c_int, _vp]),
     "spmv_csr_plan_bytes": (C.c_int64, [_H, C.c_int]),
     "spmv_csr_plan_describe": (C.c_int, [_H, C.c_int, C.c_char_p, C.c_int]),
+    "spmv_csr_plan_chunk_order": (C.c_int, [_H, C.c_int]),
     "spmv_csr_time": (C.c_int, [_H, C.c_int, _f32p, _f32p, C.c_int, _vp, C.POINTER(C.c_float)]),
     "spmv_csr_run_host": (C.c_int, [_H, C.c_int, _f32p, _f32p, C.POINTER(C.c_float)]),
     "spmv_dense_gemv": (C.c_int, [C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_int, _vp]),
@@ -1118,6 +1119,13 @@ class CsrMatrix:
 
     def plan_bytes(self, variant: int) -> int:
         return lib().spmv_csr_plan_bytes(self._h, variant)
+
+    def plan_chunk_order(self, variant: int) -> int:
+        """spmv_csr_plan_chunk_order: 0 = no launch of several chunk kinds, 1 = lists, 2 = identity."""
+        rc = lib().spmv_csr_plan_chunk_order(self._h, variant)
+        if rc < 0:
+            check(rc)
+        return rc
 
     def download(self):
         import numpy as np

@@ -1955,8 +1955,10 @@ int64_t spmv_csr_plan_bytes(const spmv_csr_t *h, int variant)
         case SPMV_ADAPTIVE:  // chunk_lb read + carry written and re-read
             return (int64_t)(h->plan_adaptive.nchunks + 1) * 4 + (int64_t)h->plan_adaptive.nchunks * 8;
         case SPMV_TILED:     // + the two window words per chunk, the chunk lists, the 16-bit offsets and the sorted words
+                             // (identity order: no lists, one slot word per chunk where some chunks are sorted)
             return (int64_t)(h->plan_tiled.nchunks + 1) * 4 + (int64_t)h->plan_tiled.nchunks * 16 +
-                   ((h->plan_tiled.n16 || h->plan_tiled.nsorted) ? (int64_t)h->plan_tiled.nchunks * 4 : 0) +
+                   ((h->plan_tiled.identity_order ? h->plan_tiled.nsorted : (h->plan_tiled.n16 || h->plan_tiled.nsorted))
+                        ? (int64_t)h->plan_tiled.nchunks * 4 : 0) +
                    (int64_t)h->plan_tiled.n16 * 2 * h->plan_tiled.block * kNnzPerThread +
                    (int64_t)h->plan_tiled.nsorted * 4 * h->plan_tiled.block * kNnzPerThread +
                    (int64_t)h->plan_tiled.nblk_chunks * 256 * 4;   // block lists: up to 256 ids per chunk that has one
@@ -1972,6 +1974,17 @@ int64_t spmv_csr_plan_bytes(const spmv_csr_t *h, int variant)
             return (int64_t)h->plan_wave.n_long * 8 + (int64_t)h->plan_wave.pieces * 16 + h->plan_wave.blocks * 8;
         default: return 0;
     }
+}
+
+int spmv_csr_plan_chunk_order(const spmv_csr_t *h, int variant)
+{
+    if (!h) { set_error("spmv_csr_plan_chunk_order: null handle"); return SPMV_ERR_INVALID; }
+    if (variant == SPMV_AUTO) variant = h->auto_variant;
+    if (variant != SPMV_TILED) { set_error("spmv_csr_plan_chunk_order: SPMV_TILED, or SPMV_AUTO resolved to it"); return SPMV_ERR_VARIANT; }
+    const ChunkPlan &p = h->plan_tiled;
+    if (!p.block) { set_error("SPMV_TILED used before spmv_csr_plan"); return SPMV_ERR_NOT_PLANNED; }
+    const bool mixed = !p.persist && (p.n16 > 0 || p.nsorted > 0) && p.n16 != p.nchunks && p.nsorted != p.nchunks;
+    return !mixed ? 0 : (p.identity_order ? 2 : 1);
 }
 
 int spmv_csr_plan_describe(const spmv_csr_t *h, int variant, char *buf, int n)

@@ -630,23 +630,31 @@ __device__ __forceinline__ unsigned col16_at(const u4 (&raw)[2], int j, int q)
     return (e & 1) ? (word >> 16) : (word & 0xffffu);
 }
 
-template <int BLOCK, bool BLOCKS, typename E = float>
-__device__ __forceinline__ void tiled16_body(float *smem, ChunkShared<BLOCK> &sh, int bid, int64_t rows, int64_t cols,
-                                             int nrun, const int32_t *__restrict__ row_ptr,
+// The chunk of workgroup `bid` of a launch over the `nrun` chunks of `list`.
+// list == nullptr: every chunk is of the launch's kind (the list would be the identity) -- the stream addresses
+// then depend on blockIdx only and the loads leave one dependent global load earlier
+__device__ __forceinline__ int listed_chunk(int bid, int nrun, const int32_t *__restrict__ list)
+{
+    const int ci = xcd_chunk(bid, nrun);
+    return list ? list[ci] : ci;
+}
+
+// The 16-bit body on chunk c0.  PRE: the caller has loaded the chunk's values into pre[] (the identity order of k_tiled_mixed,
+// which issues them before it knows the kind of the chunk).
+template <int BLOCK, bool BLOCKS, typename E = float, bool PRE = false>
+__device__ __forceinline__ void tiled16_body(float *smem, ChunkShared<BLOCK> &sh, int c0, int64_t rows, int64_t cols,
+                                             const int32_t *__restrict__ row_ptr,
                                              const uint16_t *__restrict__ col16, const E *__restrict__ vals,
                                              const float *__restrict__ x, float *__restrict__ y,
                                              const int32_t *__restrict__ chunk_lb, float *__restrict__ carry,
-                                             const int32_t *__restrict__ win, const int32_t *__restrict__ list,
-                                             int kRegionArg, const int32_t *__restrict__ blk)
+                                             const int32_t *__restrict__ win, int kRegionArg,
+                                             const int32_t *__restrict__ blk, const vals4_t<E> *pre = nullptr)
 {
     constexpr int kVec = kNnzPerThread / 4;
     static_assert(kNnzPerThread == 16, "the col16 lane layout is two 16-byte loads of eight offsets");
 
     const int tid = threadIdx.x;
-    // list == nullptr: every chunk has 16-bit columns (the list would be the identity) -- the stream addresses
-    // then depend on blockIdx only and the loads leave one dependent global load earlier
-    const int ci = xcd_chunk(bid, nrun);
-    const ChunkHead h = chunk_head<BLOCK>(sh, tid, list ? list[ci] : ci, chunk_lb);
+    const ChunkHead h = chunk_head<BLOCK>(sh, tid, c0, chunk_lb);
     const int c = h.c;
     const int w0 = win[2 * c];
     const int wl = win[2 * c + 1];
@@ -665,9 +673,24 @@ __device__ __forceinline__ void tiled16_body(float *smem, ChunkShared<BLOCK> &sh
         raw[0] = __builtin_nontemporal_load(&c8[tid]);   // (not stream_load: the 1024-thread kernel then shares an offset register)
         raw[1] = __builtin_nontemporal_load(&c8[BLOCK + tid]);
 #pragma unroll
-        for (int j = 0; j < kVec; ++j) vv[j] = stream_load<BLOCK>(v4, tid, j);
+        for (int j = 0; j < kVec; ++j) {
+            if constexpr (PRE) vv[j] = pre[j];
+            else vv[j] = stream_load<BLOCK>(v4, tid, j);
+        }
     }
-    // the bounds of this lane's first segment ride along with the stream (they only depend on chunk_lb)
+    // The bounds of this lane's first segment ride along with the stream (they only depend on chunk_lb).  The compiler widens
+    // `re` inside the branch of first_bounds, behind an s_waitcnt vmcnt(0): every load issued before it has landed when the
+    // wave goes on, so the window of a one-pass chunk (nearly every chunk) leaves for L2 when the stream is in.  kWindowFirst
+    // (tiled_chunks.hpp, A/B) issues the window in front of the bounds, under the stream -- and measured 1.3 to 2.1 % slower
+    // on the headline: the shipped order is this one.  The body with block lists has it in every build:
+    // with the window first it spills 36 bytes instead of 20.
+    const bool one_pass = wlen <= kRegion && wlen > 0;
+    auto stage_window = [&] {
+        if (by_blocks) stage_blocks<BLOCK>(x, blk + (int64_t)c * kBlkMax, wlen / kBlkCols, cols, smem, tid);
+        else stage_slice<BLOCK, true>(x, (int64_t)w0, wlen, cols, smem, tid);
+    };
+    constexpr bool kFirst = kWindowFirst && !BLOCKS;
+    if (kFirst && one_pass) stage_window();
     const RowBounds b0 = first_bounds(tid, h, row_ptr);
 
     // ---- gather x from the staged slices (every column of the chunk lies in [w0, w0+wlen))
@@ -676,10 +699,9 @@ __device__ __forceinline__ void tiled16_body(float *smem, ChunkShared<BLOCK> &sh
     for (int j = 0; j < kVec; ++j)
 #pragma unroll
         for (int q = 0; q < 4; ++q) xv[j][q] = 0.0f;
-    if (wlen <= kRegion && wlen > 0) {
-        // one pass (nearly every chunk): every offset lies inside the staged window, no range check per element
-        if (by_blocks) stage_blocks<BLOCK>(x, blk + (int64_t)c * kBlkMax, wlen / kBlkCols, cols, smem, tid);
-        else stage_slice<BLOCK, true>(x, (int64_t)w0, wlen, cols, smem, tid);
+    if (one_pass) {
+        // every offset lies inside the staged window, no range check per element
+        if (!kFirst) stage_window();
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < kVec; ++j)
@@ -719,8 +741,8 @@ void k_tiled16(int64_t rows, int64_t cols, int nrun, const int32_t *__restrict__
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ ChunkShared<BLOCK> sh;
-    tiled16_body<BLOCK, BLOCKS, E>(smem, sh, (int)blockIdx.x, rows, cols, nrun, row_ptr, col16, vals, x, y, chunk_lb, carry, win,
-                                   list, kRegion, blk);
+    tiled16_body<BLOCK, BLOCKS, E>(smem, sh, listed_chunk((int)blockIdx.x, nrun, list), rows, cols, row_ptr, col16, vals, x, y,
+                                   chunk_lb, carry, win, kRegion, blk);
 }
 
 // ---------------------------------------------------------------------------
@@ -734,13 +756,15 @@ void k_tiled16(int64_t rows, int64_t cols, int nrun, const int32_t *__restrict__
 // positions their nonzeros have in the row-major stream, where the lane that holds the VALUES of those positions
 // (read live from vals, original order: nothing is copied) picks them up, multiplies and leaves the products for
 // the same row reduction as everywhere else.  Same products, same order of every sum as the other bodies.
-template <int BLOCK, typename E = float>
-__device__ __forceinline__ void sorted_body(float *smem, ChunkShared<BLOCK> &sh, int bid, int64_t rows, int nrun,
+// The sorted body on chunk c0, whose words are slot `ci` of perm[] (its position in the list of sorted chunks).  PRE: its values
+// are in pre[] already (as in tiled16_body).
+template <int BLOCK, typename E = float, bool PRE = false>
+__device__ __forceinline__ void sorted_body(float *smem, ChunkShared<BLOCK> &sh, int c0, int ci, int64_t rows,
                                             const int32_t *__restrict__ row_ptr, const uint32_t *__restrict__ perm,
                                             const E *__restrict__ vals, const float *__restrict__ x,
                                             float *__restrict__ y, const int32_t *__restrict__ chunk_lb,
                                             float *__restrict__ carry, const int32_t *__restrict__ win,
-                                            const int32_t *__restrict__ list)
+                                            const vals4_t<E> *pre = nullptr)
 {
     constexpr int kChunkT = chunk_of(BLOCK);
     constexpr int kVec = kNnzPerThread / 4;
@@ -748,8 +772,7 @@ __device__ __forceinline__ void sorted_body(float *smem, ChunkShared<BLOCK> &sh,
     constexpr unsigned kColMask = (1u << kColBits) - 1u;
 
     const int tid = threadIdx.x;
-    const int ci = xcd_chunk(bid, nrun);          // position in the list of sorted chunks = slot of its words in perm[]
-    const ChunkHead h = chunk_head<BLOCK>(sh, tid, list[ci], chunk_lb);
+    const ChunkHead h = chunk_head<BLOCK>(sh, tid, c0, chunk_lb);
     const float *xw = x + win[2 * h.c];
 
     u4 pw[kVec];
@@ -760,7 +783,10 @@ __device__ __forceinline__ void sorted_body(float *smem, ChunkShared<BLOCK> &sh,
 #pragma unroll
         for (int j = 0; j < kVec; ++j) pw[j] = stream_load<BLOCK>(p4, tid, j);
 #pragma unroll
-        for (int j = 0; j < kVec; ++j) vv[j] = stream_load<BLOCK>(v4, tid, j);
+        for (int j = 0; j < kVec; ++j) {
+            if constexpr (PRE) vv[j] = pre[j];
+            else vv[j] = stream_load<BLOCK>(v4, tid, j);
+        }
     }
     const RowBounds b0 = first_bounds(tid, h, row_ptr);
 
@@ -789,13 +815,19 @@ void k_sorted(int64_t rows, int nrun, const int32_t *__restrict__ row_ptr, const
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ ChunkShared<BLOCK> sh;
-    sorted_body<BLOCK, E>(smem, sh, (int)blockIdx.x, rows, nrun, row_ptr, perm, vals, x, y, chunk_lb, carry, win, list);
+    const int ci = xcd_chunk((int)blockIdx.x, nrun);   // position in the list of sorted chunks = slot of its words in perm[]
+    sorted_body<BLOCK, E>(smem, sh, list[ci], ci, rows, row_ptr, perm, vals, x, y, chunk_lb, carry, win);
 }
 
-// All kinds of chunk in ONE launch: workgroups [0, n32) run the 32-bit body over list32 (the slow chunks -- outliers
-// gathered from global memory, the ragged last chunk -- start first), the next nsorted the sorted body, the rest the
-// 16-bit body over list16.  Two launches
-// would each end with a partly idle chip (power-law rows: 1758 such chunks took 71 us after the 209 us of the rest).
+// All kinds of chunk in ONE launch, in one of two orders (the plan decides: ChunkPlan::identity_order, tiled_chunks.hpp).
+// Two launches would each end with a partly idle chip (power-law rows: 1758 such chunks took 71 us after the 209 us of the rest).
+// Lists: workgroups [0, n32) run the 32-bit body over list32 (the slow chunks -- outliers gathered from global memory, the
+// ragged last chunk -- start first), the next nsorted the sorted body, the rest the 16-bit body over list16.
+// Identity (list16 == nullptr; list_sorted then holds ChunkPlan::d_sorted_slot, one word per chunk): workgroup b takes chunk
+// xcd_chunk(b) of all n32 + nsorted + n16 and reads no list.  The values of a full chunk lie at the same addresses whatever
+// its kind, so their loads are issued first, from blockIdx alone; win[] then says which body goes on with them, and only a
+// sorted chunk reads more: its slot in perm[], sorted_slot[c].  The ragged last chunk (always 32-bit, the slowest, guarded
+// loads) changes places with the first chunk of its XCD's range, so that it starts with the launch and not at its end.
 template <int BLOCK, bool BLOCKS, typename E = float>
 __global__ __launch_bounds__(BLOCK, 8)
 void k_tiled_mixed(int64_t rows, int64_t nnz, int64_t cols, int n32, int nsorted, int n16, const int32_t *__restrict__ row_ptr,
@@ -808,14 +840,53 @@ void k_tiled_mixed(int64_t rows, int64_t nnz, int64_t cols, int n32, int nsorted
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ ChunkShared<BLOCK> sh;
     const int b = (int)blockIdx.x;
+    // (The order has no argument of its own: with two more scalar arguments the 16-bit path spilled scalars to a vector
+    // register and, one VGPR short, a just-loaded value vector to scratch.  Not compiled in for plans with block lists,
+    // BLOCKS: that kernel spills 20 bytes as it is, and 36 with this path in it.)
+    if (kIdentityOrder && !BLOCKS && list16 == nullptr) {
+        const int32_t *__restrict__ sorted_slot = list_sorted;
+        constexpr int kChunkT = chunk_of(BLOCK);
+        constexpr int kVec = kNnzPerThread / 4;
+        const int nchunks = n32 + nsorted + n16;
+        int c = xcd_chunk(b, nchunks);
+        bool full = true;
+        if ((int64_t)nchunks * kChunkT != nnz) {   // a ragged last chunk
+            const int last = nchunks - 1, q = nchunks / kXcds;
+            const int first = q > 0 ? nchunks - q : last;   // where the range of the last XCD that has chunks begins
+            c = c == first ? last : (c == last ? first : c);
+            full = c != last;
+        }
+        if (full) {
+            vals4_t<E> vv[kVec];
+            const vals4_t<E> *v4 = value_vectors(vals, (int64_t)c * kChunkT);
+#pragma unroll
+            for (int j = 0; j < kVec; ++j) vv[j] = stream_load<BLOCK>(v4, (int)threadIdx.x, j);
+            const int wl = win[2 * c + 1];
+            if (wl & kCol16Bit) {
+                tiled16_body<BLOCK, BLOCKS, E, true>(smem, sh, c, rows, cols, row_ptr, col16, vals, x, y, chunk_lb, carry, win,
+                                                     kRegion, blk, vv);
+                return;
+            }
+            if (wl & kSortedBit) {
+                sorted_body<BLOCK, E, true>(smem, sh, c, sorted_slot[c], rows, row_ptr, perm, vals, x, y, chunk_lb, carry, win, vv);
+                return;
+            }
+        }
+        // the few 32-bit chunks load their stream again, columns and values in the order that body keeps its registers by
+        // (handed the values, it spilled 36 bytes instead of 20)
+        adaptive_body<BLOCK, true, false, E>(smem, sh, 0, 1, rows, nnz, cols, c, 1, row_ptr, col_idx, vals, x, y, chunk_lb,
+                                             carry, win, nullptr, kRegion);
+        return;
+    }
     if (b < n32)
         adaptive_body<BLOCK, true, false, E>(smem, sh, b, n32, rows, nnz, cols, 0, n32, row_ptr, col_idx, vals, x,
                                              y, chunk_lb, carry, win, list32, kRegion);
-    else if (b < n32 + nsorted)
-        sorted_body<BLOCK, E>(smem, sh, b - n32, rows, nsorted, row_ptr, perm, vals, x, y, chunk_lb, carry, win, list_sorted);
-    else
-        tiled16_body<BLOCK, BLOCKS, E>(smem, sh, b - n32 - nsorted, rows, cols, n16, row_ptr, col16, vals, x, y, chunk_lb,
-                                       carry, win, list16, kRegion, blk);
+    else if (b < n32 + nsorted) {
+        const int ci = xcd_chunk(b - n32, nsorted);
+        sorted_body<BLOCK, E>(smem, sh, list_sorted[ci], ci, rows, row_ptr, perm, vals, x, y, chunk_lb, carry, win);
+    } else
+        tiled16_body<BLOCK, BLOCKS, E>(smem, sh, listed_chunk(b - n32 - nsorted, n16, list16), rows, cols, row_ptr, col16, vals,
+                                       x, y, chunk_lb, carry, win, kRegion, blk);
 }
 
 // rows that continue past their owner chunk: y[r] += carry[c+1] + carry[c+2] + ... in chunk order
@@ -1034,9 +1105,12 @@ template <int BLOCK, bool BLOCKS, typename E>
 static int launch_mixed(const spmv_csr &h, const ChunkPlan &p, const E *vals, const float *x, float *y, hipStream_t s)
 {
     const int n32 = p.nchunks - p.n16 - p.nsorted;
+    // identity order: no list16 (that is how the kernel knows), and the sorted chunks' slots where their list would be
+    const int32_t *list_sorted = p.identity_order ? p.d_sorted_slot.get() : p.d_list_sorted.get();
+    const int32_t *list16 = p.identity_order ? nullptr : p.d_list16.get();
     return launch_region<k_tiled_mixed<BLOCK, BLOCKS, E>>("k_tiled_mixed", h, p, p.nchunks, BLOCK, s, h.rows, h.nnz, h.cols, n32, p.nsorted,
                                                           p.n16, h.d_row_ptr, h.d_col_idx, p.d_col16, p.d_perm, vals, x, y, p.d_lb,
-                                                          p.d_carry, p.d_win, p.d_list32, p.d_list_sorted, p.d_list16, p.region, p.d_blk);
+                                                          p.d_carry, p.d_win, p.d_list32, list_sorted, list16, p.region, p.d_blk);
 }
 
 template <int BLOCK, typename E>

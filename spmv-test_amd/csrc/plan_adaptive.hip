@@ -6,7 +6,8 @@
 //                   chosen per chunk by the modelled cost of both (PlanCost); launch_plan_windows, tiled_chunks.hpp
 //   k_plan_col16    16-bit column offsets of the chunks whose span is staged whole, or indices into a LIST of 256-column blocks
 //   k_plan_sorted   the column-sorted words of the sorted chunks
-//   k_plan_kinds / k_plan_lists   the three chunk lists (16-bit / sorted / 32-bit) a launch walks
+//   k_plan_kinds / k_plan_lists   the three chunk lists (16-bit / sorted / 32-bit) a launch walks -- or, where nearly every
+//                   chunk is a 16-bit one, no list: the launch over all kinds takes its chunks in identity order (build_lists)
 // and the host code that picks the workgroup size: a pure function of the matrix by default, timed trials under
 // SPMV_AUTOTUNE=1 (they call launch_adaptive of kernels_adaptive.hip).  tiled_chunks.hpp holds what both files share.
 #include <climits>
@@ -430,6 +431,19 @@ static int count_block_list_chunks(const spmv_csr &h, ChunkPlan &p, hipStream_t 
     return SPMV_OK;
 }
 
+// The order of a mixed launch over `nchunks` chunks of which n16 have 16-bit columns: identity where the others are at most
+// one chunk in kIdentityShare (tiled_chunks.hpp).  Tuning knob SPMV_TILED_ORDER=identity|lists forces one (anything else: the
+// rule), read when the plan is made.
+static bool want_identity_order(int nchunks, int n16)
+{
+    if (!kIdentityOrder) return false;
+    if (const char *e = getenv("SPMV_TILED_ORDER")) {
+        if (!strcmp(e, "identity")) return true;
+        if (!strcmp(e, "lists")) return false;
+    }
+    return kIdentityShare > 0 && (int64_t)(nchunks - n16) * kIdentityShare <= nchunks;
+}
+
 // The last step of a TILED plan: the column-sorted words of the chunks marked kSortedBit, and the three chunk lists
 // (16-bit / sorted / 32-bit) the launch walks.
 static int build_lists(const spmv_csr &h, ChunkPlan &p, hipStream_t s)
@@ -438,6 +452,8 @@ static int build_lists(const spmv_csr &h, ChunkPlan &p, hipStream_t s)
     (void)p.d_list32.reset();
     (void)p.d_list_sorted.reset();
     (void)p.d_perm.reset();
+    (void)p.d_sorted_slot.reset();
+    p.identity_order = false;
     p.n16 = p.nsorted = 0;
     if (p.nchunks == 0 || !p.d_win || p.persist) return SPMV_OK;
     int rc;
@@ -458,12 +474,18 @@ static int build_lists(const spmv_csr &h, ChunkPlan &p, hipStream_t s)
     p.n16 = n16;
     p.nsorted = ns;
     if (n16 == 0 && ns == 0) return SPMV_OK;   // every chunk runs the 32-bit body: no lists needed
-    SPMV_HIP_TRY(p.d_list16.alloc((size_t)n16));
-    SPMV_HIP_TRY(p.d_list_sorted.alloc((size_t)ns));
-    SPMV_HIP_TRY(p.d_list32.alloc((size_t)(p.nchunks - n16 - ns)));
-    hipLaunchKernelGGL(k_plan_lists, dim3(g), dim3(256), 0, s, p.nchunks, p.d_win, f16.get(), fs.get(), p.d_list16, p.d_list_sorted,
-                       p.d_list32);
-    if ((rc = check_launch("k_plan_lists"))) return rc;
+    // one launch of all kinds (neither all 16-bit nor all sorted): in identity order it reads no list (a plan with block
+    // lists keeps its lists: the identity order is not compiled into that kernel)
+    const bool mixed = n16 != p.nchunks && ns != p.nchunks;
+    p.identity_order = mixed && p.nblk_chunks == 0 && want_identity_order(p.nchunks, n16);
+    if (!p.identity_order) {
+        SPMV_HIP_TRY(p.d_list16.alloc((size_t)n16));
+        SPMV_HIP_TRY(p.d_list_sorted.alloc((size_t)ns));
+        SPMV_HIP_TRY(p.d_list32.alloc((size_t)(p.nchunks - n16 - ns)));
+        hipLaunchKernelGGL(k_plan_lists, dim3(g), dim3(256), 0, s, p.nchunks, p.d_win, f16.get(), fs.get(), p.d_list16,
+                           p.d_list_sorted, p.d_list32);
+        if ((rc = check_launch("k_plan_lists"))) return rc;
+    }
     if (ns > 0) {
         // one slot of chunk words per SORTED chunk (fs.get(): its rank among them, the order of list_sorted)
         SPMV_HIP_TRY(p.d_perm.alloc((size_t)chunk_of(p.block) * (size_t)ns));
@@ -475,6 +497,7 @@ static int build_lists(const spmv_csr &h, ChunkPlan &p, hipStream_t s)
         if (rc) return rc;
     }
     SPMV_HIP_TRY(hipStreamSynchronize(s));   // the scans' temporaries are freed on return
+    if (p.identity_order && ns > 0) p.d_sorted_slot = std::move(fs);   // ... but the ranks, which stand in for list_sorted
     return SPMV_OK;
 }
 

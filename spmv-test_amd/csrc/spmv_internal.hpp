@@ -108,6 +108,8 @@ struct ChunkPlan {
     // sorted chunks (TILED): spans of several LDS regions gather x in column order instead of staging it
     DevPtr<uint32_t> d_perm;           // [nsorted * chunk] position << 18 | column - w0 of the sorted chunks (list order), read INSTEAD of col_idx
     DevPtr<int32_t> d_list_sorted;     // [nsorted]
+    DevPtr<int32_t> d_sorted_slot;     // [nchunks] identity order: sorted chunks before chunk c = the slot of a sorted c in d_perm
+    bool identity_order = false;       // the mixed launch takes its chunks in identity order and has no lists (tiled_chunks.hpp)
     int nsorted = 0;                   // chunks run by the sorted body
     int nsorted_marked = 0;            // chunks the window pass marked (a few may still switch to a block list)
     int sorted_from = 0;               // -1: sorted where the modelled cost is lower; 0: never; n: from n passes on

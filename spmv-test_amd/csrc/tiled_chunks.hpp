@@ -57,6 +57,25 @@ constexpr int kSortedFromDefault = SPMV_T_SORTED_FROM;
 __host__ __device__ constexpr int sorted_pos_bits(int block) { return block == 1024 ? 14 : (block == 512 ? 13 : 12); }
 __host__ __device__ constexpr int sorted_col_bits(int) { return 18; }   // 8192 lines = 32 KiB of counters in the plan kernel
 static_assert(sorted_pos_bits(1024) + sorted_col_bits(1024) <= 32, "one word per nonzero");
+// The order of the mixed launch (k_tiled_mixed).  Lists: the 32-bit chunks first, then the sorted, then the 16-bit ones, each
+// kind through its chunk list.  Identity: workgroup b takes chunk xcd_chunk(b) whatever its kind and reads no list -- the value
+// loads leave before anything about the chunk is known -- but the slow chunks no longer start first.  The plan takes identity
+// where at most one chunk in kIdentityShare is not a 16-bit one (0: never; SPMV_TILED_ORDER overrides at plan time).
+#ifndef SPMV_T_IDENTITY_SHARE
+#define SPMV_T_IDENTITY_SHARE 8
+#endif
+constexpr int kIdentityShare = SPMV_T_IDENTITY_SHARE;
+#ifndef SPMV_T_IDENTITY_ORDER
+#define SPMV_T_IDENTITY_ORDER 1   // 0: the identity order is not compiled in -- plan and kernel as they were without it (A/B)
+#endif
+constexpr bool kIdentityOrder = SPMV_T_IDENTITY_ORDER != 0;
+// When the 16-bit body issues the x window of a one-pass chunk.  0: behind the row bounds, whose branch ends in an s_waitcnt
+// vmcnt(0), so the window leaves when the stream has landed.  1: right behind the stream loads, the bounds last (A/B: slower on
+// the headline).
+#ifndef SPMV_T_WINDOW_FIRST
+#define SPMV_T_WINDOW_FIRST 0
+#endif
+constexpr bool kWindowFirst = SPMV_T_WINDOW_FIRST != 0;
 #ifndef SPMV_T_BLKBITS
 #define SPMV_T_BLKBITS 8
 #endif

@@ -3,7 +3,8 @@
 # compiled differently: spmv-test_amd/lib/libspmv_hip_NAME.so (tools/explore.py takes it as {"lib": "spmv-test_amd/lib/libspmv_hip_NAME.so"})
 # A knob that two files read has to be compiled into both: SPMV_T_BLKBITS and SPMV_T_NPT (tiled_chunks.hpp, spmv_internal.hpp)
 # take kernels_adaptive.hip,plan_adaptive.hip; SPMV_T_GROUP, SPMV_T_HUGE and SPMV_T_SHORT are read by kernels_adaptive.hip alone,
-# SPMV_T_SORTED_FROM by plan_adaptive.hip alone.
+# SPMV_T_SORTED_FROM by plan_adaptive.hip alone.  SPMV_T_IDENTITY_ORDER takes both files, SPMV_T_IDENTITY_SHARE plan_adaptive.hip,
+# SPMV_T_WINDOW_FIRST kernels_adaptive.hip (tiled_chunks.hpp; several libraries side by side: tools/ab_libs.py).
 set -e
 NAME=$1; FILES=${2//,/ }; DEFS=$3
 PKG=$(cd "$(dirname "$0")/../spmv-test_amd" && pwd)
