@@ -363,22 +363,10 @@ class CsrMatrix:
         """On a handle made by ``a.transpose(keep_map=True)``: ``dst[..., i] = src[..., map[i]]``, arrays of nnz 32-bit elements
         in ``a``'s storage order brought into this handle's (the bias of the _bias attention calls for backward_kv).  src, dst:
         (nnz,) or (count, nnz) of one 4-byte dtype with stride(-1) == 1; copied as bits, in one launch."""
-        import torch
-        for name, t in (("src", src), ("dst", dst)):
-            if not isinstance(t, torch.Tensor) or t.dim() not in (1, 2) or t.element_size() != 4 or t.stride(-1) != 1 \
-                    or t.shape[-1] != self.nnz:
-                raise ValueError(f"transpose_gather: {name} must be (nnz,) or (count, nnz) of 4-byte elements with stride(-1) == 1")
-        if src.dtype != dst.dtype or src.shape != dst.shape:
-            raise ValueError(f"transpose_gather: src is {src.dtype} {tuple(src.shape)}, dst {dst.dtype} {tuple(dst.shape)}")
-        count = src.shape[0] if src.dim() == 2 else 1
-        stride = lambda t: t.stride(0) if count > 1 else 0
-        check(lib().spmv_csr_transpose_gather(self._h, count, _ptr(src), stride(src), _ptr(dst), stride(dst), _stream_handle(stream)))
+        self._move("transpose_gather", lib().spmv_csr_transpose_gather, src, dst, self.nnz, self.nnz, stream)
 
     def transpose_map_bytes(self) -> int:
-        n = lib().spmv_csr_transpose_map_bytes(self._h)
-        if n < 0:
-            check(n)
-        return n
+        return self._bytes(lib().spmv_csr_transpose_map_bytes)
 
     # -- selection (spmv_csr_select_*) ------------------------------------------------------------------------------
     SELECT_ABS = 1      # SPMV_SELECT_ABS
@@ -427,7 +415,8 @@ class CsrMatrix:
         gather launch, asynchronous, graph-capturable; then what :meth:`values_changed` does."""
         check(lib().spmv_csr_select_values(self._h, a._h, _stream_handle(stream)))
 
-    def _select_move(self, who: str, fn, src, dst, n_src: int, n_dst: int, stream) -> None:
+    def _move(self, who: str, fn, src, dst, n_src: int, n_dst: int, stream) -> None:
+        """The strided move fn of a derived handle: src (n_src,) or (count, n_src), dst the same over n_dst."""
         import torch
         for name, t, n in (("src", src, n_src), ("dst", dst, n_dst)):
             if not isinstance(t, torch.Tensor) or t.dim() not in (1, 2) or t.element_size() != 4 or t.stride(-1) != 1 \
@@ -451,18 +440,22 @@ class CsrMatrix:
         """On a handle made by ``a.select_*(keep_map=True)``: ``dst[..., m] = src[..., map[m]]`` -- arrays of 32-bit elements in
         ``a``'s storage order (``a.nnz`` each) brought into this handle's (``nnz`` each).  src, dst: 1-D or (count, n) of one
         4-byte dtype with stride(-1) == 1; copied as bits, in one launch."""
-        self._select_move("select_gather", lib().spmv_csr_select_gather, src, dst, self._parent_nnz("select_gather"), self.nnz, stream)
+        self._move("select_gather", lib().spmv_csr_select_gather, src, dst, self._parent_nnz("select_gather"), self.nnz, stream)
 
     def select_scatter(self, src, dst, stream=None) -> None:
         """The other way: ``dst[..., map[m]] = src[..., m]``; every other element of dst is left as it is (zero-fill dst first
         for a dense gradient in the parent's order)."""
-        self._select_move("select_scatter", lib().spmv_csr_select_scatter, src, dst, self.nnz, self._parent_nnz("select_scatter"), stream)
+        self._move("select_scatter", lib().spmv_csr_select_scatter, src, dst, self.nnz, self._parent_nnz("select_scatter"), stream)
 
-    def select_map_bytes(self) -> int:
-        n = lib().spmv_csr_select_map_bytes(self._h)
+    def _bytes(self, fn) -> int:
+        """What a _map_bytes / _plan_bytes call answers (below 0: a status)."""
+        n = fn(self._h)
         if n < 0:
             check(n)
         return n
+
+    def select_map_bytes(self) -> int:
+        return self._bytes(lib().spmv_csr_select_map_bytes)
 
     def copy_arrays(self, row_ptr, col_idx, vals=None, stream=None) -> None:
         """Device-to-device copies of this handle's arrays into the caller's contiguous device tensors (int32 of rows + 1,
@@ -499,10 +492,7 @@ class CsrMatrix:
         check(lib().spmv_csr_spgemm_values(self._h, a._h, b._h, _stream_handle(stream)))
 
     def spgemm_plan_bytes(self) -> int:
-        n = lib().spmv_csr_spgemm_plan_bytes(self._h)
-        if n < 0:
-            check(n)
-        return n
+        return self._bytes(lib().spmv_csr_spgemm_plan_bytes)
 
     # -- the sparse sum (spmv_csr_add) ------------------------------------------------------------------------------
     def add(self, b: "CsrMatrix", alpha: float = 1.0, beta: float = 1.0, op="union", keep_plan: bool = False, stream=None) -> "CsrMatrix":
@@ -543,13 +533,10 @@ class CsrMatrix:
         n = getattr(self, "add_parent_nnz", None)
         if n is None:
             raise ValueError("add_gather: this handle was not made by add")
-        self._select_move("add_gather", lambda h, *rest: lib().spmv_csr_add_gather(h, side, *rest), src, dst, self.nnz, n[side], stream)
+        self._move("add_gather", lambda h, *rest: lib().spmv_csr_add_gather(h, side, *rest), src, dst, self.nnz, n[side], stream)
 
     def add_plan_bytes(self) -> int:
-        n = lib().spmv_csr_add_plan_bytes(self._h)
-        if n < 0:
-            check(n)
-        return n
+        return self._bytes(lib().spmv_csr_add_plan_bytes)
 
     # -- the triangular solve (spmv_csr_trsv) ----------------------------------------------------------------------
     @staticmethod
@@ -723,22 +710,11 @@ class CsrMatrix:
         import torch
         if dst is None and isinstance(src, torch.Tensor):
             dst = torch.empty_like(src)
-        for name, t in (("src", src), ("dst", dst)):
-            if not isinstance(t, torch.Tensor) or t.dim() not in (1, 2) or t.element_size() != 4 or t.stride(-1) != 1 \
-                    or t.shape[-1] != self.nnz:
-                raise ValueError(f"permute_gather: {name} must be (nnz,) or (count, nnz) of 4-byte elements with stride(-1) == 1")
-        if src.dtype != dst.dtype or src.shape != dst.shape:
-            raise ValueError(f"permute_gather: src is {src.dtype} {tuple(src.shape)}, dst {dst.dtype} {tuple(dst.shape)}")
-        count = src.shape[0] if src.dim() == 2 else 1
-        stride = lambda t: t.stride(0) if count > 1 else 0
-        check(lib().spmv_csr_permute_gather(self._h, count, _ptr(src), stride(src), _ptr(dst), stride(dst), _stream_handle(stream)))
+        self._move("permute_gather", lib().spmv_csr_permute_gather, src, dst, self.nnz, self.nnz, stream)
         return dst
 
     def permute_map_bytes(self) -> int:
-        n = lib().spmv_csr_permute_map_bytes(self._h)
-        if n < 0:
-            check(n)
-        return n
+        return self._bytes(lib().spmv_csr_permute_map_bytes)
 
     # -- SpMM: k right-hand sides at once (spmv_csr_spmm) ---------------------------------------------------------
     def spmm_plan(self, stream=None) -> None:

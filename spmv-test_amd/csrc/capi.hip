@@ -387,44 +387,39 @@ int spmv_csr_transpose(const spmv_csr_t *a, int keep_map, void *stream, spmv_csr
     return transpose(*a, keep_map == 1, (hipStream_t)stream, out);
 }
 
-int spmv_csr_transpose_values(spmv_csr_t *t, const spmv_csr_t *a, void *stream)
+// ---- the companions of a derived handle: _values, _gather / _scatter, _map_bytes ------------------------------------------
+// One description per maker of what its companions' checks say differently; the checks themselves are written once below, and
+// fire in one order for every maker.
+struct Companions {
+    MapMaker maker;             // whose map the calls take (none: spmv_csr_add, whose plan stands in the map's place)
+    char letter;                // the handle's name in a message
+    const char *missing;        // the refusal of a handle without that map or plan
+    const char *parent;         // _values: how a message introduces the parent's shape
+    bool stride_names_nnz;      // the dst_stride refusal says "is below nnz = ...", not "is below the ... words of an array"
+};
+static const Companions kOfTranspose = {MapMaker::transpose, 't', "the handle has no map (it was not made by spmv_csr_transpose with keep_map = 1)",
+                                        "the transpose of t would be", true};
+static const Companions kOfSelect = {MapMaker::select, 's', "the handle has no map (it was not made by a spmv_csr_select call with keep_map = 1)",
+                                     "s was selected from", false};
+static const Companions kOfPermute = {MapMaker::permute, 'b', "the handle has no map (it was not made by spmv_csr_permute with SPMV_PERMUTE_KEEP_MAP)",
+                                      "b was permuted from", true};
+static const Companions kOfAdd = {MapMaker::none, 'c', "the handle has no plan (it was not made by spmv_csr_add with keep_plan = 1)", nullptr, false};
+
+static bool made_by(const Companions &m, const spmv_csr_t *h)
 {
-    if (!t || !a) { set_error("spmv_csr_transpose_values: null argument"); return SPMV_ERR_INVALID; }
-    if (!t->transpose_map) {
-        set_error("spmv_csr_transpose_values: the handle has no map (it was not made by spmv_csr_transpose with keep_map = 1)");
-        return SPMV_ERR_INVALID;
-    }
-    if (a == t) {
-        set_error("spmv_csr_transpose_values: a is t itself (t's values would be read while they are written)");
-        return SPMV_ERR_INVALID;
-    }
-    if (a->rows != t->cols || a->cols != t->rows || a->nnz != t->nnz) {
-        set_error("spmv_csr_transpose_values: a is %lld x %lld with %lld nonzeros, the transpose of t would be %lld x %lld with %lld",
-                  (long long)a->rows, (long long)a->cols, (long long)a->nnz, (long long)t->cols, (long long)t->rows,
-                  (long long)t->nnz);
-        return SPMV_ERR_INVALID;
-    }
-    if (int rc = require_current(t->device, "spmv_csr_transpose_values")) return rc;
-    if (a->device != t->device) {
-        set_error("spmv_csr_transpose_values: a lives on device %d, t on device %d", a->device, t->device);
-        return SPMV_ERR_INVALID;
-    }
-    if (int rc = transpose_values(*t, *a, (hipStream_t)stream)) return rc;
-    ++t->values_gen;
-    return SPMV_OK;
+    return m.maker == MapMaker::none ? h->plan_add.ready : h->map.maker == m.maker;
 }
 
-int spmv_csr_transpose_gather(const spmv_csr_t *t, int count, const void *d_src, int64_t src_stride, void *d_dst, int64_t dst_stride,
-                              void *stream)
+// What every strided move refuses; nothing is launched before it has passed.  side: spmv_csr_add_gather's, null for the maps;
+// scatter: dst is in the parent's order.
+static int move_check(const char *what, const Companions &m, const spmv_csr_t *h, const int *side, bool scatter, int count,
+                      const void *d_src, int64_t src_stride, const void *d_dst, int64_t dst_stride)
 {
-    const char *what = "spmv_csr_transpose_gather";
-    if (!t) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
-    if (!t->transpose_map) {
-        set_error("%s: the handle has no map (it was not made by spmv_csr_transpose with keep_map = 1)", what);
-        return SPMV_ERR_INVALID;
-    }
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    if (!made_by(m, h)) { set_error("%s: %s", what, m.missing); return SPMV_ERR_INVALID; }
+    if (side && *side != 0 && *side != 1) { set_error("%s: side = %d (0: a, 1: b)", what, *side); return SPMV_ERR_INVALID; }
     if (count < 1) { set_error("%s: count = %d (need count >= 1)", what, count); return SPMV_ERR_INVALID; }
-    if ((!d_src || !d_dst) && t->nnz > 0) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
+    if ((!d_src || !d_dst) && h->nnz > 0) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
     if (reinterpret_cast<uintptr_t>(d_src) % 4 != 0 || reinterpret_cast<uintptr_t>(d_dst) % 4 != 0) {
         set_error("%s: src and dst must be 4-byte aligned", what);
         return SPMV_ERR_INVALID;
@@ -437,19 +432,75 @@ int spmv_csr_transpose_gather(const spmv_csr_t *t, int count, const void *d_src,
         set_error("%s: a stride overflows 64-bit byte offsets", what);
         return SPMV_ERR_INVALID;
     }
-    if (count > 1 && dst_stride < t->nnz) {
-        set_error("%s: dst_stride = %lld is below nnz = %lld with count = %d", what, (long long)dst_stride, (long long)t->nnz, count);
+    // words of one array of dst
+    const int64_t dst_len = side ? (*side ? h->plan_add.b_nnz : h->plan_add.a_nnz) : scatter ? h->map.parent_len : h->nnz;
+    if (count > 1 && dst_stride < dst_len) {
+        if (m.stride_names_nnz)
+            set_error("%s: dst_stride = %lld is below nnz = %lld with count = %d", what, (long long)dst_stride, (long long)dst_len, count);
+        else
+            set_error("%s: dst_stride = %lld is below the %lld words of an array with count = %d", what, (long long)dst_stride,
+                      (long long)dst_len, count);
         return SPMV_ERR_INVALID;
     }
-    if (int rc = require_current(t->device, what)) return rc;
-    return transpose_gather(*t, count, d_src, src_stride, d_dst, dst_stride, (hipStream_t)stream);
+    return require_current(h->device, what);
 }
 
-int64_t spmv_csr_transpose_map_bytes(const spmv_csr_t *t)
+// a gather or a scatter through h's own map
+static int map_move_checked(const char *what, const Companions &m, const spmv_csr_t *h, bool scatter, int count, const void *d_src,
+                            int64_t src_stride, void *d_dst, int64_t dst_stride, void *stream)
 {
-    if (!t) { set_error("spmv_csr_transpose_map_bytes: null handle"); return SPMV_ERR_INVALID; }
-    return t->transpose_map ? 4 * t->nnz : 0;
+    if (int rc = move_check(what, m, h, nullptr, scatter, count, d_src, src_stride, d_dst, dst_stride)) return rc;
+    return map_move(h->map, h->nnz, scatter, count, d_src, src_stride, d_dst, dst_stride, (hipStream_t)stream);
 }
+
+// h's values again from its parent's (one parent, through h's map), and what spmv_csr_values_changed does
+static int map_values(const char *what, const Companions &m, spmv_csr_t *h, const spmv_csr_t *a, void *stream)
+{
+    if (!h || !a) { set_error("%s: null argument", what); return SPMV_ERR_INVALID; }
+    if (!made_by(m, h)) { set_error("%s: %s", what, m.missing); return SPMV_ERR_INVALID; }
+    if (a == h) {
+        set_error("%s: a is %c itself (%c's values would be read while they are written)", what, m.letter, m.letter);
+        return SPMV_ERR_INVALID;
+    }
+    const bool transposed = m.maker == MapMaker::transpose;
+    const int64_t rows = transposed ? h->cols : h->rows, cols = transposed ? h->rows : h->cols;
+    if (a->rows != rows || a->cols != cols || a->nnz != h->map.parent_len) {
+        set_error("%s: a is %lld x %lld with %lld nonzeros, %s %lld x %lld with %lld", what, (long long)a->rows, (long long)a->cols,
+                  (long long)a->nnz, m.parent, (long long)rows, (long long)cols, (long long)h->map.parent_len);
+        return SPMV_ERR_INVALID;
+    }
+    if (m.maker == MapMaker::permute && a->nnz > 0 && !a->d_vals) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
+    if (int rc = require_current(h->device, what)) return rc;
+    if (a->device != h->device) {
+        set_error("%s: a lives on device %d, %c on device %d", what, a->device, m.letter, h->device);
+        return SPMV_ERR_INVALID;
+    }
+    const hipStream_t s = (hipStream_t)stream;
+    // (the transpose's values land in the library's own allocation: four words per lane, kernels_transpose.hip)
+    if (int rc = transposed ? transpose_values(*h, *a, s) : map_move(h->map, h->nnz, false, 1, a->d_vals, 0, h->own_vals.get(), 0, s))
+        return rc;
+    ++h->values_gen;
+    return SPMV_OK;
+}
+
+static int64_t map_bytes(const char *what, const Companions &m, const spmv_csr_t *h)
+{
+    if (!h) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
+    return h->map.maker == m.maker ? 4 * h->nnz : 0;
+}
+
+int spmv_csr_transpose_values(spmv_csr_t *t, const spmv_csr_t *a, void *stream)
+{
+    return map_values("spmv_csr_transpose_values", kOfTranspose, t, a, stream);
+}
+
+int spmv_csr_transpose_gather(const spmv_csr_t *t, int count, const void *d_src, int64_t src_stride, void *d_dst, int64_t dst_stride,
+                              void *stream)
+{
+    return map_move_checked("spmv_csr_transpose_gather", kOfTranspose, t, false, count, d_src, src_stride, d_dst, dst_stride, stream);
+}
+
+int64_t spmv_csr_transpose_map_bytes(const spmv_csr_t *t) { return map_bytes("spmv_csr_transpose_map_bytes", kOfTranspose, t); }
 
 // ---- selection (kernels_select.hip) ------------------------------------------------------------------------------------
 // what spmv_csr_select_topk and _threshold refuse alike; nothing is launched before it has passed
@@ -484,77 +535,22 @@ int spmv_csr_select_threshold(const spmv_csr_t *a, const float *d_score, float t
 
 int spmv_csr_select_values(spmv_csr_t *s, const spmv_csr_t *a, void *stream)
 {
-    const char *what = "spmv_csr_select_values";
-    if (!s || !a) { set_error("%s: null argument", what); return SPMV_ERR_INVALID; }
-    if (!s->select_map) {
-        set_error("%s: the handle has no map (it was not made by a spmv_csr_select call with keep_map = 1)", what);
-        return SPMV_ERR_INVALID;
-    }
-    if (a == s) { set_error("%s: a is s itself (s's values would be read while they are written)", what); return SPMV_ERR_INVALID; }
-    if (a->rows != s->rows || a->cols != s->cols || a->nnz != s->select_parent_nnz) {
-        set_error("%s: a is %lld x %lld with %lld nonzeros, s was selected from %lld x %lld with %lld", what, (long long)a->rows,
-                  (long long)a->cols, (long long)a->nnz, (long long)s->rows, (long long)s->cols, (long long)s->select_parent_nnz);
-        return SPMV_ERR_INVALID;
-    }
-    if (int rc = require_current(s->device, what)) return rc;
-    if (a->device != s->device) {
-        set_error("%s: a lives on device %d, s on device %d", what, a->device, s->device);
-        return SPMV_ERR_INVALID;
-    }
-    if (int rc = select_move(*s, false, 1, a->d_vals, 0, s->own_vals.get(), 0, (hipStream_t)stream)) return rc;
-    ++s->values_gen;
-    return SPMV_OK;
-}
-
-static int select_move_checked(const char *what, bool scatter, const spmv_csr_t *s, int count, const void *d_src, int64_t src_stride,
-                               void *d_dst, int64_t dst_stride, void *stream)
-{
-    if (!s) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
-    if (!s->select_map) {
-        set_error("%s: the handle has no map (it was not made by a spmv_csr_select call with keep_map = 1)", what);
-        return SPMV_ERR_INVALID;
-    }
-    if (count < 1) { set_error("%s: count = %d (need count >= 1)", what, count); return SPMV_ERR_INVALID; }
-    if ((!d_src || !d_dst) && s->nnz > 0) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
-    if (reinterpret_cast<uintptr_t>(d_src) % 4 != 0 || reinterpret_cast<uintptr_t>(d_dst) % 4 != 0) {
-        set_error("%s: src and dst must be 4-byte aligned", what);
-        return SPMV_ERR_INVALID;
-    }
-    if (src_stride < 0 || dst_stride < 0) {
-        set_error("%s: src_stride = %lld, dst_stride = %lld (a stride is not negative)", what, (long long)src_stride, (long long)dst_stride);
-        return SPMV_ERR_INVALID;
-    }
-    if (src_stride > INT64_MAX / 4 / count || dst_stride > INT64_MAX / 4 / count) {
-        set_error("%s: a stride overflows 64-bit byte offsets", what);
-        return SPMV_ERR_INVALID;
-    }
-    const int64_t dst_len = scatter ? s->select_parent_nnz : s->nnz;      // words of one array of dst
-    if (count > 1 && dst_stride < dst_len) {
-        set_error("%s: dst_stride = %lld is below the %lld words of an array with count = %d", what, (long long)dst_stride,
-                  (long long)dst_len, count);
-        return SPMV_ERR_INVALID;
-    }
-    if (int rc = require_current(s->device, what)) return rc;
-    return select_move(*s, scatter, count, d_src, src_stride, d_dst, dst_stride, (hipStream_t)stream);
+    return map_values("spmv_csr_select_values", kOfSelect, s, a, stream);
 }
 
 int spmv_csr_select_gather(const spmv_csr_t *s, int count, const void *d_src, int64_t src_stride, void *d_dst, int64_t dst_stride,
                            void *stream)
 {
-    return select_move_checked("spmv_csr_select_gather", false, s, count, d_src, src_stride, d_dst, dst_stride, stream);
+    return map_move_checked("spmv_csr_select_gather", kOfSelect, s, false, count, d_src, src_stride, d_dst, dst_stride, stream);
 }
 
 int spmv_csr_select_scatter(const spmv_csr_t *s, int count, const void *d_src, int64_t src_stride, void *d_dst, int64_t dst_stride,
                             void *stream)
 {
-    return select_move_checked("spmv_csr_select_scatter", true, s, count, d_src, src_stride, d_dst, dst_stride, stream);
+    return map_move_checked("spmv_csr_select_scatter", kOfSelect, s, true, count, d_src, src_stride, d_dst, dst_stride, stream);
 }
 
-int64_t spmv_csr_select_map_bytes(const spmv_csr_t *s)
-{
-    if (!s) { set_error("spmv_csr_select_map_bytes: null handle"); return SPMV_ERR_INVALID; }
-    return s->select_map ? 4 * s->nnz : 0;
-}
+int64_t spmv_csr_select_map_bytes(const spmv_csr_t *s) { return map_bytes("spmv_csr_select_map_bytes", kOfSelect, s); }
 
 int spmv_csr_copy_arrays(const spmv_csr_t *h, int32_t *d_row_ptr, int32_t *d_col_idx, float *d_vals, void *stream)
 {
@@ -683,34 +679,7 @@ int spmv_csr_add_values(spmv_csr_t *c, const spmv_csr_t *a, const spmv_csr_t *b,
 int spmv_csr_add_gather(const spmv_csr_t *c, int side, int count, const void *d_src, int64_t src_stride, void *d_dst, int64_t dst_stride,
                         void *stream)
 {
-    const char *what = "spmv_csr_add_gather";
-    if (!c) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
-    if (!c->plan_add.ready) {
-        set_error("%s: the handle has no plan (it was not made by spmv_csr_add with keep_plan = 1)", what);
-        return SPMV_ERR_INVALID;
-    }
-    if (side != 0 && side != 1) { set_error("%s: side = %d (0: a, 1: b)", what, side); return SPMV_ERR_INVALID; }
-    if (count < 1) { set_error("%s: count = %d (need count >= 1)", what, count); return SPMV_ERR_INVALID; }
-    if ((!d_src || !d_dst) && c->nnz > 0) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
-    if (reinterpret_cast<uintptr_t>(d_src) % 4 != 0 || reinterpret_cast<uintptr_t>(d_dst) % 4 != 0) {
-        set_error("%s: src and dst must be 4-byte aligned", what);
-        return SPMV_ERR_INVALID;
-    }
-    if (src_stride < 0 || dst_stride < 0) {
-        set_error("%s: src_stride = %lld, dst_stride = %lld (a stride is not negative)", what, (long long)src_stride, (long long)dst_stride);
-        return SPMV_ERR_INVALID;
-    }
-    if (src_stride > INT64_MAX / 4 / count || dst_stride > INT64_MAX / 4 / count) {
-        set_error("%s: a stride overflows 64-bit byte offsets", what);
-        return SPMV_ERR_INVALID;
-    }
-    const int64_t dst_len = side ? c->plan_add.b_nnz : c->plan_add.a_nnz;      // words of one array of dst
-    if (count > 1 && dst_stride < dst_len) {
-        set_error("%s: dst_stride = %lld is below the %lld words of an array with count = %d", what, (long long)dst_stride,
-                  (long long)dst_len, count);
-        return SPMV_ERR_INVALID;
-    }
-    if (int rc = require_current(c->device, what)) return rc;
+    if (int rc = move_check("spmv_csr_add_gather", kOfAdd, c, &side, false, count, d_src, src_stride, d_dst, dst_stride)) return rc;
     return add_gather(*c, side, count, d_src, src_stride, d_dst, dst_stride, (hipStream_t)stream);
 }
 
@@ -942,65 +911,16 @@ int spmv_csr_permute(const spmv_csr_t *a, const int32_t *d_row_perm, const int32
 
 int spmv_csr_permute_values(spmv_csr_t *b, const spmv_csr_t *a, void *stream)
 {
-    const char *what = "spmv_csr_permute_values";
-    if (!b || !a) { set_error("%s: null argument", what); return SPMV_ERR_INVALID; }
-    if (!b->permute_map) {
-        set_error("%s: the handle has no map (it was not made by spmv_csr_permute with SPMV_PERMUTE_KEEP_MAP)", what);
-        return SPMV_ERR_INVALID;
-    }
-    if (a == b) { set_error("%s: a is b itself (b's values would be read while they are written)", what); return SPMV_ERR_INVALID; }
-    if (a->rows != b->rows || a->cols != b->cols || a->nnz != b->nnz) {
-        set_error("%s: a is %lld x %lld with %lld nonzeros, b was permuted from %lld x %lld with %lld", what, (long long)a->rows,
-                  (long long)a->cols, (long long)a->nnz, (long long)b->rows, (long long)b->cols, (long long)b->nnz);
-        return SPMV_ERR_INVALID;
-    }
-    if (a->nnz > 0 && !a->d_vals) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
-    if (int rc = require_current(b->device, what)) return rc;
-    if (a->device != b->device) {
-        set_error("%s: a lives on device %d, b on device %d", what, a->device, b->device);
-        return SPMV_ERR_INVALID;
-    }
-    if (int rc = permute_gather(*b, 1, a->d_vals, 0, b->own_vals.get(), 0, (hipStream_t)stream)) return rc;
-    ++b->values_gen;
-    return SPMV_OK;
+    return map_values("spmv_csr_permute_values", kOfPermute, b, a, stream);
 }
 
 int spmv_csr_permute_gather(const spmv_csr_t *b, int count, const void *d_src, int64_t src_stride, void *d_dst, int64_t dst_stride,
                             void *stream)
 {
-    const char *what = "spmv_csr_permute_gather";
-    if (!b) { set_error("%s: null handle", what); return SPMV_ERR_INVALID; }
-    if (!b->permute_map) {
-        set_error("%s: the handle has no map (it was not made by spmv_csr_permute with SPMV_PERMUTE_KEEP_MAP)", what);
-        return SPMV_ERR_INVALID;
-    }
-    if (count < 1) { set_error("%s: count = %d (need count >= 1)", what, count); return SPMV_ERR_INVALID; }
-    if ((!d_src || !d_dst) && b->nnz > 0) { set_error("%s: null array", what); return SPMV_ERR_INVALID; }
-    if (reinterpret_cast<uintptr_t>(d_src) % 4 != 0 || reinterpret_cast<uintptr_t>(d_dst) % 4 != 0) {
-        set_error("%s: src and dst must be 4-byte aligned", what);
-        return SPMV_ERR_INVALID;
-    }
-    if (src_stride < 0 || dst_stride < 0) {
-        set_error("%s: src_stride = %lld, dst_stride = %lld (a stride is not negative)", what, (long long)src_stride, (long long)dst_stride);
-        return SPMV_ERR_INVALID;
-    }
-    if (src_stride > INT64_MAX / 4 / count || dst_stride > INT64_MAX / 4 / count) {
-        set_error("%s: a stride overflows 64-bit byte offsets", what);
-        return SPMV_ERR_INVALID;
-    }
-    if (count > 1 && dst_stride < b->nnz) {
-        set_error("%s: dst_stride = %lld is below nnz = %lld with count = %d", what, (long long)dst_stride, (long long)b->nnz, count);
-        return SPMV_ERR_INVALID;
-    }
-    if (int rc = require_current(b->device, what)) return rc;
-    return permute_gather(*b, count, d_src, src_stride, d_dst, dst_stride, (hipStream_t)stream);
+    return map_move_checked("spmv_csr_permute_gather", kOfPermute, b, false, count, d_src, src_stride, d_dst, dst_stride, stream);
 }
 
-int64_t spmv_csr_permute_map_bytes(const spmv_csr_t *b)
-{
-    if (!b) { set_error("spmv_csr_permute_map_bytes: null handle"); return SPMV_ERR_INVALID; }
-    return b->permute_map ? 4 * b->nnz : 0;
-}
+int64_t spmv_csr_permute_map_bytes(const spmv_csr_t *b) { return map_bytes("spmv_csr_permute_map_bytes", kOfPermute, b); }
 
 int spmv_permute_vector(const int32_t *d_perm, int64_t n, int inverse, const float *d_src, float *d_dst, void *stream)
 {

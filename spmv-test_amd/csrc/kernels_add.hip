@@ -255,7 +255,7 @@ int add_view(const spmv_csr &x, hipStream_t s, int32_t *d_flag, AddView &v)
         set_error("spmv_csr_add: out of device memory for the row-sorted view");
         rc = SPMV_ERR_HIP;
     }
-    if (rc == SPMV_OK) rc = transpose_gather(*v.sorted, 1, t1->transpose_map.get(), 0, v.perm.get(), 0, s);
+    if (rc == SPMV_OK) rc = map_move(v.sorted->map, v.sorted->nnz, false, 1, t1->map.words.get(), 0, v.perm.get(), 0, s);
     if (rc == SPMV_OK && hipStreamSynchronize(s) != hipSuccess) {
         set_error("spmv_csr_add: hipStreamSynchronize failed");
         rc = SPMV_ERR_HIP;

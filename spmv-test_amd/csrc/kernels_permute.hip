@@ -185,16 +185,6 @@ __global__ __launch_bounds__(kBlock) void k_perm_relabel(int64_t nnz, int64_t n,
     out[k] = (relabel && j >= 0 && (int64_t)j < n) ? relabel[j] : j;
 }
 
-// dst[c][i] = src[c][map[i]] for c < count, 32-bit words copied as bits
-__global__ __launch_bounds__(kBlock) void k_perm_gather(int64_t n, int count, const uint32_t *__restrict__ map, const uint32_t *__restrict__ src,
-                                                        int64_t src_stride, uint32_t *__restrict__ dst, int64_t dst_stride)
-{
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t m = map[i];
-    for (int c = 0; c < count; ++c) dst[c * dst_stride + i] = (int64_t)m < n ? src[c * src_stride + m] : 0u;
-}
-
 // map[i] = first[map[i]], in place
 __global__ __launch_bounds__(kBlock) void k_perm_compose(int64_t n, const uint32_t *__restrict__ first, uint32_t *map)
 {
@@ -244,7 +234,11 @@ int perm_finish(const spmv_csr &a, DevPtr<int32_t> &rp, DevPtr<int32_t> &ci, Dev
     h->device = a.device;
     h->d_row_ptr = rp; h->d_col_idx = ci; h->d_vals = va;
     h->own_row_ptr = std::move(rp); h->own_col_idx = std::move(ci); h->own_vals = std::move(va);
-    if (keep_map) h->permute_map = std::move(map);
+    if (keep_map) {
+        h->map.words = std::move(map);
+        h->map.parent_len = a.nnz;
+        h->map.maker = MapMaker::permute;
+    }
     *out = h;
     return SPMV_OK;
 }
@@ -277,8 +271,8 @@ int permute_via_transpose(const spmv_csr &a, const int32_t *inv_row, const int32
     if (rc == SPMV_OK) rc = transpose(*t1, true, s, &b);
     if (rc == SPMV_OK && keep_map && nnz > 0) {
         // b's map holds positions of t1: through t1's map they are positions of A
-        hipLaunchKernelGGL(k_perm_compose, dim3(perm_blocks(nnz)), dim3(kBlock), 0, s, nnz, (const uint32_t *)t1->transpose_map.get(),
-                           b->transpose_map.get());
+        hipLaunchKernelGGL(k_perm_compose, dim3(perm_blocks(nnz)), dim3(kBlock), 0, s, nnz, (const uint32_t *)t1->map.words.get(),
+                           b->map.words.get());
         rc = check_launch("k_perm_compose");
     }
     if (rc == SPMV_OK && hipStreamSynchronize(s) != hipSuccess) rc = perm_fail("the stream failed");
@@ -287,8 +281,8 @@ int permute_via_transpose(const spmv_csr &a, const int32_t *inv_row, const int32
         if (b) (void)spmv_csr_destroy(b);
         return rc;
     }
-    if (keep_map) b->permute_map = std::move(b->transpose_map);
-    else (void)b->transpose_map.reset();
+    if (keep_map) b->map.maker = MapMaker::permute;      // b's own map, now of positions of A: relabelled, not moved
+    else b->map = PosMap();
     *out = b;
     return SPMV_OK;
 }
@@ -370,14 +364,6 @@ int permute(const spmv_csr &a, const int32_t *row_perm, const int32_t *col_perm,
         if (b) { *out = b; return SPMV_OK; }
     }
     return permute_via_transpose(a, irow, icol, keep_map, s, out);
-}
-
-int permute_gather(const spmv_csr &b, int count, const void *src, int64_t src_stride, void *dst, int64_t dst_stride, hipStream_t s)
-{
-    if (b.nnz <= 0) return SPMV_OK;
-    hipLaunchKernelGGL(k_perm_gather, dim3(perm_blocks(b.nnz)), dim3(kBlock), 0, s, b.nnz, count, (const uint32_t *)b.permute_map.get(),
-                       (const uint32_t *)src, src_stride, (uint32_t *)dst, dst_stride);
-    return check_launch("k_perm_gather");
 }
 
 int permute_vector(const int32_t *perm, int64_t n, bool inverse, const float *src, float *dst, hipStream_t s)

@@ -442,22 +442,6 @@ __global__ __launch_bounds__(kBlock) void k_sel_compact(int64_t rows, int64_t nb
     });
 }
 
-// gather: dst[c][m] = src[c][map[m]]; scatter: dst[c][map[m]] = src[c][m], for m < n, every map entry below parent_nnz
-template <bool SCATTER>
-__global__ __launch_bounds__(kBlock) void k_sel_move(int64_t n, int64_t parent_nnz, int count, const uint32_t *__restrict__ map,
-                                                     const uint32_t *__restrict__ src, int64_t src_stride, uint32_t *__restrict__ dst,
-                                                     int64_t dst_stride)
-{
-    const int64_t m = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (m >= n) return;
-    const int64_t p = (int64_t)map[m];
-    if (p >= parent_nnz) return;
-    for (int c = 0; c < count; ++c) {
-        if (SCATTER) dst[c * dst_stride + p] = src[c * src_stride + m];
-        else dst[c * dst_stride + m] = src[c * src_stride + p];
-    }
-}
-
 }  // namespace
 
 uint32_t select_key(float score, bool abs)
@@ -466,20 +450,6 @@ uint32_t select_key(float score, bool abs)
     static_assert(sizeof u == sizeof score, "a float is 32 bits");
     __builtin_memcpy(&u, &score, sizeof u);
     return sel_key(u, abs ? 0x7fffffffu : ~0u);
-}
-
-int select_move(const spmv_csr &sh, bool scatter, int count, const void *src, int64_t src_stride, void *dst, int64_t dst_stride,
-                hipStream_t s)
-{
-    if (sh.nnz <= 0) return SPMV_OK;
-    const unsigned blocks = (unsigned)((sh.nnz + kBlock - 1) / kBlock);
-    if (scatter)
-        hipLaunchKernelGGL(k_sel_move<true>, dim3(blocks), dim3(kBlock), 0, s, sh.nnz, sh.select_parent_nnz, count,
-                           (const uint32_t *)sh.select_map.get(), (const uint32_t *)src, src_stride, (uint32_t *)dst, dst_stride);
-    else
-        hipLaunchKernelGGL(k_sel_move<false>, dim3(blocks), dim3(kBlock), 0, s, sh.nnz, sh.select_parent_nnz, count,
-                           (const uint32_t *)sh.select_map.get(), (const uint32_t *)src, src_stride, (uint32_t *)dst, dst_stride);
-    return check_launch("k_sel_move");
 }
 
 // Device memory while the call runs, beside out's own arrays (4 (rows + 1) + 8 kept bytes, + 4 kept for the map):
@@ -528,8 +498,11 @@ int select(const spmv_csr &a, const float *score, bool thresh, int k, uint32_t t
     h->device = a.device;
     h->d_row_ptr = rp; h->d_col_idx = ci; h->d_vals = va;
     h->own_row_ptr = std::move(rp); h->own_col_idx = std::move(ci); h->own_vals = std::move(va);
-    h->select_map = std::move(map);
-    h->select_parent_nnz = a.nnz;
+    h->map.parent_len = a.nnz;
+    if (keep_map) {
+        h->map.words = std::move(map);
+        h->map.maker = MapMaker::select;
+    }
     *out = h;
     return SPMV_OK;
 }

@@ -234,18 +234,6 @@ __global__ __launch_bounds__(kBlock) void k_tr_gather(int64_t n, const uint32_t 
     }
 }
 
-// dst[c][i] = src[c][map[i]] for `count` arrays at once: the map is read once, and a caller's dst needs no more than the
-// 4-byte alignment of a float (k_tr_gather's 16-byte stores are for the allocations made here), so a word per lane.
-__global__ __launch_bounds__(kBlock) void k_tr_gather_arrays(int64_t n, int count, const uint32_t *__restrict__ map,
-                                                             const uint32_t *__restrict__ src, int64_t src_stride,
-                                                             uint32_t *__restrict__ dst, int64_t dst_stride)
-{
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t m = map[i];
-    for (int c = 0; c < count; ++c) dst[c * dst_stride + i] = (int64_t)m < n ? src[c * src_stride + m] : 0u;
-}
-
 unsigned blocks_of4(int64_t n) { return (unsigned)((n + (int64_t)kBlock * 4 - 1) / ((int64_t)kBlock * 4)); }
 
 int launch_gather(int64_t n, const uint32_t *map, const void *src, void *dst, hipStream_t s)
@@ -259,16 +247,7 @@ int launch_gather(int64_t n, const uint32_t *map, const void *src, void *dst, hi
 
 int transpose_values(spmv_csr &t, const spmv_csr &a, hipStream_t s)
 {
-    return launch_gather(t.nnz, t.transpose_map.get(), a.d_vals, t.own_vals.get(), s);
-}
-
-int transpose_gather(const spmv_csr &t, int count, const void *src, int64_t src_stride, void *dst, int64_t dst_stride, hipStream_t s)
-{
-    if (t.nnz <= 0) return SPMV_OK;
-    const unsigned blocks = (unsigned)((t.nnz + kBlock - 1) / kBlock);
-    k_tr_gather_arrays<<<dim3(blocks), dim3(kBlock), 0, s>>>(t.nnz, count, t.transpose_map.get(), (const uint32_t *)src, src_stride,
-                                                             (uint32_t *)dst, dst_stride);
-    return check_launch("k_tr_gather_arrays");
+    return launch_gather(t.nnz, t.map.words.get(), a.d_vals, t.own_vals.get(), s);
 }
 
 // Device memory while the call runs, beside T's own arrays (8 nnz + 4 (cols + 1) bytes):
@@ -342,7 +321,11 @@ int transpose(const spmv_csr &a, bool keep_map, hipStream_t s, spmv_csr_t **out)
     h->device = a.device;
     h->d_row_ptr = rp; h->d_col_idx = ci; h->d_vals = va;
     h->own_row_ptr = std::move(rp); h->own_col_idx = std::move(ci); h->own_vals = std::move(va);
-    if (keep_map) h->transpose_map = std::move(pos[final_pos]);
+    if (keep_map) {
+        h->map.words = std::move(pos[final_pos]);
+        h->map.parent_len = nnz;
+        h->map.maker = MapMaker::transpose;
+    }
     *out = h;
     return SPMV_OK;
 }

@@ -335,6 +335,16 @@ struct Ilu0Plan {
     DevPtr<int32_t> d_pivot;                   // [1] the smallest row whose pivot is +-0 or not finite, INT32_MAX: none
 };
 
+// A derived handle's map of storage positions back into its parent: vals[i] = the parent's vals[words[i]].  spmv_csr_transpose
+// (keep_map = 1), spmv_csr_select_* (keep_map = 1; positions ascending inside a row) and spmv_csr_permute
+// (SPMV_PERMUTE_KEEP_MAP) keep one; `maker` says which, and each family of companions takes its own maker's map alone.
+enum class MapMaker { none = 0, transpose, select, permute };
+struct PosMap {
+    DevPtr<uint32_t> words;            // [the handle's nnz]
+    int64_t parent_len = 0;            // the length of the parent's arrays: every entry lies below it (a select call notes it without a map too)
+    MapMaker maker = MapMaker::none;   // none: the handle has no map
+};
+
 }  // namespace spmv
 
 
@@ -346,11 +356,7 @@ struct spmv_csr {
     const float *d_vals = nullptr;
     spmv::DevPtr<int32_t> own_row_ptr, own_col_idx;   // the handle's own copies behind the views (empty: the caller's arrays)
     spmv::DevPtr<float> own_vals;
-    spmv::DevPtr<uint32_t> transpose_map;   // [nnz] spmv_csr_transpose(keep_map = 1): vals[i] = the parent's vals[map[i]] (empty: no map)
-    // a handle has at most one of the two maps: which member is set says which call made it
-    spmv::DevPtr<uint32_t> select_map;      // [nnz] spmv_csr_select_*(keep_map = 1): the same, positions ascending inside a row (empty: no map)
-    int64_t select_parent_nnz = -1;         // the parent's nnz when a select call made this handle (every map entry is below it); -1: another maker
-    spmv::DevPtr<uint32_t> permute_map;     // [nnz] spmv_csr_permute(SPMV_PERMUTE_KEEP_MAP): vals[i] = the parent's vals[map[i]] (empty: no map)
+    spmv::PosMap map;              // where every entry sits in the parent's arrays (a handle of spmv_csr_transpose, _select_*, _permute)
     int device = 0;
 
     // plan state
@@ -478,16 +484,17 @@ int launch_attention(AttnPass pass, const spmv_csr &h, const AttnArgsT<fp16> &a,
 // kernels_transpose.hip: spmv_csr_transpose / spmv_csr_transpose_values
 int transpose(const spmv_csr &a, bool keep_map, hipStream_t s, spmv_csr_t **out);
 int transpose_values(spmv_csr &t, const spmv_csr &a, hipStream_t s);
-// dst[c * dst_stride + i] = src[c * src_stride + map[i]] for c < count through t's map (spmv_csr_transpose_gather)
-int transpose_gather(const spmv_csr &t, int count, const void *src, int64_t src_stride, void *dst, int64_t dst_stride, hipStream_t s);
+// kernels_map.hip: the one strided move through a map over n entries (the handle's nnz), 32-bit words copied as bits, for
+// c < count, i < n: dst[c * dst_stride + i] = src[c * src_stride + words[i]], or (scatter) dst[c * dst_stride + words[i]] =
+// src[c * src_stride + i].  An entry at or beyond parent_len (the library builds none): a transpose or permute map's gather
+// stores 0, a select map's and every scatter leave the word as it is.
+int map_move(const PosMap &map, int64_t n, bool scatter, int count, const void *src, int64_t src_stride, void *dst, int64_t dst_stride,
+             hipStream_t s);
 // kernels_select.hip: spmv_csr_select_topk (thresh = false: k) / spmv_csr_select_threshold (thresh = true: thr_key = select_key of
 // the threshold); score null: a's vals
 int select(const spmv_csr &a, const float *score, bool thresh, int k, uint32_t thr_key, bool abs, bool keep_map, hipStream_t s,
            spmv_csr_t **out);
 uint32_t select_key(float score, bool abs);
-// through sh's select map, for c < count, m < sh.nnz: dst[c][m] = src[c][map[m]], or (scatter) dst[c][map[m]] = src[c][m]
-int select_move(const spmv_csr &sh, bool scatter, int count, const void *src, int64_t src_stride, void *dst, int64_t dst_stride,
-                hipStream_t s);
 
 // kernels_spgemm.hip: spmv_csr_spgemm / spmv_csr_spgemm_values (the numeric pass alone, on c's plan)
 int spgemm(const spmv_csr &a, const spmv_csr &b, bool keep_plan, hipStream_t s, spmv_csr_t **out, int64_t *products);
@@ -514,10 +521,9 @@ int64_t ilu0_plan_bytes(const spmv_csr &m);
 
 // kernels_color.hip: spmv_csr_color (perm may be null; color_ptr: the host's, cap entries, may be null; info may be null)
 int color(const spmv_csr &a, uint32_t seed, hipStream_t s, int32_t *d_color, int32_t *d_perm, int32_t *color_ptr, int cap, int64_t info[8]);
-// kernels_permute.hip: spmv_csr_permute / _values / _gather (through b's permute map) / spmv_permute_vector
+// kernels_permute.hip: spmv_csr_permute / spmv_permute_vector (_permute_values and _gather: map_move)
 int permute(const spmv_csr &a, const int32_t *row_perm, const int32_t *col_perm, bool keep_map, bool via_transpose, hipStream_t s,
             spmv_csr_t **out);
-int permute_gather(const spmv_csr &b, int count, const void *src, int64_t src_stride, void *dst, int64_t dst_stride, hipStream_t s);
 int permute_vector(const int32_t *perm, int64_t n, bool inverse, const float *src, float *dst, hipStream_t s);
 
 int dense_to_csr(int M, int N, const float *d_A, hipStream_t s, spmv_csr_t **out);

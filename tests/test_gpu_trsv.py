@@ -16,6 +16,7 @@ contract's order from three wrong ones is proved in tests/test_trsv_host.py.
 """
 import ctypes as C
 import functools
+import gc
 
 import numpy as np
 import pytest
@@ -479,6 +480,7 @@ def test_gauss_seidel_equals_the_numpy_composition(pkg, gpu, oracle, symmetric):
     A = _owned(pkg.capi, n, rp, ci, va)
     d_b, x = _dev(gpu, b), torch.zeros(n, device=gpu)
     state = pkg.solvers.gauss_seidel(A, d_b, x, sweeps=1, symmetric=symmetric)
+    gc.collect()        # (tensors of earlier tests that wait in a reference cycle go now, not during the sweeps below)
     held = torch.cuda.memory_allocated()
     pkg.solvers.gauss_seidel(A, d_b, x, sweeps=2, symmetric=symmetric, state=state)
     assert torch.cuda.memory_allocated() == held, "a sweep after the first allocates nothing"

@@ -24,10 +24,13 @@ template <class T> struct DevPtr {       // an exactly sized heap block (an empt
     hipError_t alloc(size_t n) { free(p); p = (T *)malloc(sizeof(T) * (n ? n : 1)); return p ? hipSuccess : 1; }
     hipError_t reset() { free(p); p = nullptr; return hipSuccess; }
 };
+// the handle's position map (csrc/spmv_internal.hpp)
+enum class MapMaker { none = 0, transpose, select, permute };
+struct PosMap { DevPtr<uint32_t> words; int64_t parent_len = 0; MapMaker maker = MapMaker::none; };
 struct AddPlan { bool ready = false; int op = 0; int64_t a_nnz = 0, b_nnz = 0, terms = 0; DevPtr<uint32_t> d_term; DevPtr<int32_t> d_start; };
 }
 struct spmv_csr { int64_t rows = 0, cols = 0, nnz = 0; const int32_t *d_row_ptr = nullptr, *d_col_idx = nullptr; const float *d_vals = nullptr;
-    spmv::DevPtr<int32_t> own_row_ptr, own_col_idx; spmv::DevPtr<float> own_vals; spmv::DevPtr<uint32_t> transpose_map; int device = 0;
+    spmv::DevPtr<int32_t> own_row_ptr, own_col_idx; spmv::DevPtr<float> own_vals; spmv::PosMap map; int device = 0;
     spmv::AddPlan plan_add; };
 inline int spmv_csr_destroy(spmv_csr_t *h) { delete h; return SPMV_OK; }
 namespace spmv {
@@ -58,7 +61,7 @@ inline int transpose(const spmv_csr &a, bool keep_map, hipStream_t, spmv_csr_t *
     spmv_csr *t = new spmv_csr();
     t->rows = a.cols; t->cols = a.rows; t->nnz = a.nnz;
     if (t->own_row_ptr.alloc((size_t)t->rows + 1) || t->own_col_idx.alloc(perm.size()) || t->own_vals.alloc(perm.size()) ||
-        t->transpose_map.alloc(perm.size())) { delete t; return SPMV_ERR_HIP; }
+        t->map.words.alloc(perm.size())) { delete t; return SPMV_ERR_HIP; }
     for (int64_t r = 0; r <= t->rows; ++r) t->own_row_ptr.get()[r] = 0;
     for (uint32_t k : perm)
         if (a.d_col_idx[k] >= 0 && a.d_col_idx[k] < a.cols) ++t->own_row_ptr.get()[a.d_col_idx[k] + 1];
@@ -66,18 +69,24 @@ inline int transpose(const spmv_csr &a, bool keep_map, hipStream_t, spmv_csr_t *
     for (size_t i = 0; i < perm.size(); ++i) {
         t->own_col_idx.get()[i] = row_of[perm[i]];
         t->own_vals.get()[i] = a.d_vals[perm[i]];
-        t->transpose_map.get()[i] = perm[i];
+        t->map.words.get()[i] = perm[i];
     }
     t->d_row_ptr = t->own_row_ptr; t->d_col_idx = t->own_col_idx; t->d_vals = t->own_vals;
-    if (!keep_map) (void)t->transpose_map.reset();
+    t->map.parent_len = a.nnz; t->map.maker = MapMaker::transpose;
+    if (!keep_map) t->map = PosMap();
     *out = t;
     return SPMV_OK;
 }
-inline int transpose_gather(const spmv_csr &t, int count, const void *src, int64_t src_stride, void *dst, int64_t dst_stride, hipStream_t)
+// the library's move through a map (kernels_map.hip), serial here
+inline int map_move(const PosMap &map, int64_t n, bool scatter, int count, const void *src, int64_t src_stride, void *dst, int64_t dst_stride,
+                    hipStream_t)
 {
     for (int c = 0; c < count; ++c)
-        for (int64_t i = 0; i < t.nnz; ++i)
-            ((uint32_t *)dst)[c * dst_stride + i] = ((const uint32_t *)src)[c * src_stride + t.transpose_map.get()[i]];
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t m = map.words.get()[i];
+            if (scatter) ((uint32_t *)dst)[c * dst_stride + m] = ((const uint32_t *)src)[c * src_stride + i];
+            else ((uint32_t *)dst)[c * dst_stride + i] = ((const uint32_t *)src)[c * src_stride + m];
+        }
     return SPMV_OK;
 }
 }

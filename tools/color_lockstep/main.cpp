@@ -5,6 +5,7 @@
 // spmv_permute_vector.  Every array is an exactly sized heap block.
 #include "kernels_color.hip"
 #include "kernels_permute.hip"
+#include "kernels_map.hip"
 
 #include <algorithm>
 #include <cstdio>
@@ -156,8 +157,8 @@ void compare_permuted(const char *what, const char *stage, const spmv_csr &b, co
     if (std::memcmp(b.d_row_ptr, want.rp.data(), 4 * want.rp.size()) != 0) fail(what, stage, 1);
     if (!want.ci.empty() && std::memcmp(b.d_col_idx, want.ci.data(), 4 * want.ci.size()) != 0) fail(what, stage, 2);
     if (!want.ci.empty() && std::memcmp(b.d_vals, want.va.data(), 4 * want.va.size()) != 0) fail(what, stage, 3);
-    if (keep_map != (bool)b.permute_map || b.transpose_map) fail(what, stage, 4);
-    if (keep_map && !want.ci.empty() && std::memcmp(b.permute_map.get(), want.map.data(), 4 * want.map.size()) != 0) fail(what, stage, 5);
+    if (keep_map != (bool)b.map.words || b.map.maker != (keep_map ? spmv::MapMaker::permute : spmv::MapMaker::none)) fail(what, stage, 4);
+    if (keep_map && !want.ci.empty() && std::memcmp(b.map.words.get(), want.map.data(), 4 * want.map.size()) != 0) fail(what, stage, 5);
 }
 
 std::vector<int32_t> shuffled(int64_t n, uint32_t seed)
@@ -191,13 +192,13 @@ void check_permute(const char *what, const Csr &a)
                 if (keep) {
                     // the companions: the values again after a rewrite, and two arrays at once
                     for (int64_t k = 0; k < d.h.nnz; ++k) d.va[k] = float_of(0x7fc00001u + (uint32_t)k);
-                    if (spmv::permute_gather(*b, 1, d.va, 0, b->own_vals.get(), 0, nullptr) != SPMV_OK) fail(what, "values", mode);
+                    if (spmv::map_move(b->map, b->nnz, false, 1, d.va, 0, b->own_vals.get(), 0, nullptr) != SPMV_OK) fail(what, "values", mode);
                     for (int64_t k = 0; k < d.h.nnz; ++k)
                         if (bits_of(b->d_vals[k]) != 0x7fc00001u + want.map[k]) fail(what, "values", k);
                     std::vector<uint32_t> src(2 * (size_t)d.h.nnz + 1), dst(2 * (size_t)d.h.nnz + 1, 0xdeadbeefu);
                     for (size_t k = 0; k < src.size(); ++k) src[k] = (uint32_t)(k * 3 + 1);
                     uint32_t *ds = exact_copy(src), *dd = exact_copy(dst);
-                    if (spmv::permute_gather(*b, 2, ds, d.h.nnz, dd, d.h.nnz, nullptr) != SPMV_OK) fail(what, "gather", mode);
+                    if (spmv::map_move(b->map, b->nnz, false, 2, ds, d.h.nnz, dd, d.h.nnz, nullptr) != SPMV_OK) fail(what, "gather", mode);
                     for (int c = 0; c < 2; ++c)
                         for (int64_t k = 0; k < d.h.nnz; ++k)
                             if (dd[c * d.h.nnz + k] != src[c * d.h.nnz + want.map[k]]) fail(what, "gather", k);

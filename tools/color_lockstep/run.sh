@@ -18,7 +18,8 @@ here=$(cd "$(dirname "$0")" && pwd)
 work=$(mktemp -d)
 trap 'rm -rf "$work"' EXIT
 cp -r "$here"/../trsv_lockstep/hip "$here"/spmv_internal.hpp "$here"/main.cpp "$work"/
-cp "$here"/../../spmv-test_amd/csrc/kernels_color.hip "$here"/../../spmv-test_amd/csrc/kernels_permute.hip "$here"/../../include/spmv_hip.h "$work"/
+cp "$here"/../../spmv-test_amd/csrc/kernels_color.hip "$here"/../../spmv-test_amd/csrc/kernels_permute.hip "$here"/../../spmv-test_amd/csrc/kernels_map.hip \
+   "$here"/../../include/spmv_hip.h "$work"/
 ${CXX:-clang++} -std=c++20 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I"$work" -x c++ "$work"/main.cpp -o "$work"/lockstep -lpthread
 "$work"/lockstep
 echo "color lockstep ok"

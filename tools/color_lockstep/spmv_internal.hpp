@@ -1,5 +1,5 @@
 #pragma once
-// tools/color_lockstep: the few names of csrc/spmv_internal.hpp that csrc/kernels_color.hip and csrc/kernels_permute.hip use,
+// tools/color_lockstep: the few names of csrc/spmv_internal.hpp that csrc/kernels_color.hip, csrc/kernels_permute.hip and csrc/kernels_map.hip use,
 // without HIP (hip/hip_runtime.h is the stub of tools/trsv_lockstep); include/spmv_hip.h is the real one, copied beside this
 // file.  The scan, the column range and the transpose (other files of the library) are serial statements of their contracts.
 #include <hip/hip_runtime.h>
@@ -40,9 +40,14 @@ template <class T> struct DevPtr {       // an exactly sized heap block (an empt
     hipError_t alloc(size_t n) { free(p); p = (T *)malloc(sizeof(T) * (n ? n : 1)); return p ? hipSuccess : 1; }
     hipError_t reset() { free(p); p = nullptr; return hipSuccess; }
 };
+// the handle's position map and its one move (csrc/spmv_internal.hpp; csrc/kernels_map.hip is the real one, copied beside this file)
+enum class MapMaker { none = 0, transpose, select, permute };
+struct PosMap { DevPtr<uint32_t> words; int64_t parent_len = 0; MapMaker maker = MapMaker::none; };
+int map_move(const PosMap &map, int64_t n, bool scatter, int count, const void *src, int64_t src_stride, void *dst, int64_t dst_stride,
+             hipStream_t s);
 }
 struct spmv_csr { int64_t rows = 0, cols = 0, nnz = 0; const int32_t *d_row_ptr = nullptr, *d_col_idx = nullptr; const float *d_vals = nullptr;
-    spmv::DevPtr<int32_t> own_row_ptr, own_col_idx; spmv::DevPtr<float> own_vals; spmv::DevPtr<uint32_t> transpose_map, permute_map; int device = 0; };
+    spmv::DevPtr<int32_t> own_row_ptr, own_col_idx; spmv::DevPtr<float> own_vals; spmv::PosMap map; int device = 0; };
 inline int spmv_csr_destroy(spmv_csr_t *h) { delete h; return SPMV_OK; }
 namespace spmv {
 // the library's scan (kernels_dense.hip), serial here: d_data[i] = sum of d_data[0 .. i), the total appended and returned
@@ -79,7 +84,7 @@ inline int transpose(const spmv_csr &a, bool keep_map, hipStream_t, spmv_csr_t *
     spmv_csr *t = new spmv_csr();
     t->rows = a.cols; t->cols = a.rows; t->nnz = a.nnz;
     if (t->own_row_ptr.alloc((size_t)t->rows + 1) || t->own_col_idx.alloc(perm.size()) || t->own_vals.alloc(perm.size()) ||
-        t->transpose_map.alloc(perm.size())) { delete t; return SPMV_ERR_HIP; }
+        t->map.words.alloc(perm.size())) { delete t; return SPMV_ERR_HIP; }
     for (int64_t r = 0; r <= t->rows; ++r) t->own_row_ptr.get()[r] = 0;
     for (uint32_t k : perm)
         if (a.d_col_idx[k] >= 0 && a.d_col_idx[k] < a.cols) ++t->own_row_ptr.get()[a.d_col_idx[k] + 1];
@@ -87,10 +92,11 @@ inline int transpose(const spmv_csr &a, bool keep_map, hipStream_t, spmv_csr_t *
     for (size_t i = 0; i < perm.size(); ++i) {
         t->own_col_idx.get()[i] = row_of[perm[i]];
         std::memcpy(&t->own_vals.get()[i], &a.d_vals[perm[i]], 4);
-        t->transpose_map.get()[i] = perm[i];
+        t->map.words.get()[i] = perm[i];
     }
     t->d_row_ptr = t->own_row_ptr; t->d_col_idx = t->own_col_idx; t->d_vals = t->own_vals;
-    if (!keep_map) (void)t->transpose_map.reset();
+    t->map.parent_len = a.nnz; t->map.maker = spmv::MapMaker::transpose;
+    if (!keep_map) t->map = spmv::PosMap();
     *out = t;
     return SPMV_OK;
 }

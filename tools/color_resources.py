@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""tools/color_resources.py -- registers, LDS and scratch of every kernel of csrc/kernels_color.hip and csrc/kernels_permute.hip.
+"""tools/color_resources.py -- registers, LDS and scratch of every kernel of csrc/kernels_color.hip and csrc/kernels_permute.hip, and
+of the gather through the map that spmv_csr_permute_values and _permute_gather launch (csrc/kernels_map.hip).
 
 Compiles the files' device code for gfx950 with the Makefile's flags and -Rpass-analysis=kernel-resource-usage and prints one row
 per kernel: VGPRs, AGPRs, waves per SIMD by registers, SGPRs, scratch bytes per lane, registers spilled, LDS bytes per block.
@@ -19,7 +20,8 @@ NAMES = {
                             "k_perm_rankILi8E": "k_perm_rank<8> (rows of at most 8 entries)",
                             "k_perm_rankILi64E": "k_perm_rank<64> (rows of 9 .. 64 entries)",
                             "k_perm_bitonic": "k_perm_bitonic (rows of 65 .. 4096 entries)", "k_perm_relabel": "k_perm_relabel",
-                            "k_perm_gather": "k_perm_gather", "k_perm_compose": "k_perm_compose", "k_perm_vector": "k_perm_vector"},
+                            "k_perm_compose": "k_perm_compose", "k_perm_vector": "k_perm_vector"},
+    "kernels_map.hip": {"k_map_moveILb0ELb1E": "k_map_move<false, true> (the gather of a transpose or permute map)"},
 }
 
 

@@ -3,6 +3,7 @@
 // include/spmv_hip.h "selection": row_ptr, col_idx, the bits of vals and the map, bit for bit; then gather and scatter through
 // the map.  Every array is an exactly sized heap block.
 #include "kernels_select.hip"
+#include "kernels_map.hip"
 
 #include <algorithm>
 #include <cstdio>
@@ -86,11 +87,11 @@ void check(const char *what, const Csr &a, const std::vector<float> *score, bool
     for (int keep_map = 0; keep_map < 2; ++keep_map) {
         spmv_csr_t *out = nullptr;
         const int rc = spmv::select(h, sc, thresh, k, spmv::select_key(thr, false), abs, keep_map == 1, nullptr, &out);
-        bool ok = rc == 0 && out && out->rows == a.rows && out->nnz == (int64_t)want.ci.size() && out->select_parent_nnz == h.nnz &&
-                  (out->select_map.get() != nullptr) == (keep_map == 1);
+        bool ok = rc == 0 && out && out->rows == a.rows && out->nnz == (int64_t)want.ci.size() && out->map.parent_len == h.nnz &&
+                  (out->map.words.get() != nullptr) == (keep_map == 1) && (out->map.maker == spmv::MapMaker::select) == (keep_map == 1);
         auto same = [](const void *got, const auto &w) { return w.empty() || std::memcmp(got, w.data(), 4 * w.size()) == 0; };
         ok = ok && same(out->d_row_ptr, want.rp) && same(out->d_col_idx, want.ci) && same(out->d_vals, want.va);
-        if (ok && keep_map) ok = same(out->select_map.get(), want.map);
+        if (ok && keep_map) ok = same(out->map.words.get(), want.map);
         if (ok && keep_map && out->nnz > 0) {
             // gather three strided arrays, scatter them back into zeros: the identity on the kept positions
             const int64_t n = h.nnz, m = out->nnz, ss = n + 3, ds = m + 2;
@@ -98,8 +99,8 @@ void check(const char *what, const Csr &a, const std::vector<float> *score, bool
             for (size_t i = 0; i < src.size(); ++i) src[i] = 0x9e3779b9u * (uint32_t)(i + 1);
             uint32_t *d_src = exact_copy(src), *d_back = exact_copy(zero);
             uint32_t *d_mid = (uint32_t *)malloc(4 * (3 * ds - 2));
-            ok = spmv::select_move(*out, false, 3, d_src, ss, d_mid, ds, nullptr) == 0 &&
-                 spmv::select_move(*out, true, 3, d_mid, ds, d_back, ss, nullptr) == 0;
+            ok = spmv::map_move(out->map, out->nnz, false, 3, d_src, ss, d_mid, ds, nullptr) == 0 &&
+                 spmv::map_move(out->map, out->nnz, true, 3, d_mid, ds, d_back, ss, nullptr) == 0;
             std::vector<char> is_kept(n, 0);
             for (uint32_t p : want.map) is_kept[p] = 1;
             for (int c = 0; ok && c < 3; ++c)

@@ -1,5 +1,5 @@
 #pragma once
-// tools/select_lockstep: the few names of csrc/spmv_internal.hpp that csrc/lane_group.hpp and csrc/kernels_select.hip use,
+// tools/select_lockstep: the few names of csrc/spmv_internal.hpp that csrc/lane_group.hpp, csrc/kernels_select.hip and csrc/kernels_map.hip use,
 // without HIP; csrc/attention_args.hpp is the real one, copied beside this file
 #include <hip/hip_runtime.h>
 #include "attention_args.hpp"
@@ -28,10 +28,15 @@ template <class T> struct DevPtr {       // an exactly sized heap block (an empt
 struct SpmmPlan { bool ready = true; int n_long = 0, pieces = 0, row_cap = 512, piece_len = 512;
     DevPtr<int32_t> d_order, d_long_row, d_long_first, d_piece_k0, d_piece_len; DevPtr<float> d_partial; };
 struct AttnPlan { bool ready = false; int heads = 0; DevPtr<float> d_scratch; int wide_heads = 0; DevPtr<float> d_scratch_wide; };
+// the handle's position map and its one move (csrc/spmv_internal.hpp; csrc/kernels_map.hip is the real one, copied beside this file)
+enum class MapMaker { none = 0, transpose, select, permute };
+struct PosMap { DevPtr<uint32_t> words; int64_t parent_len = 0; MapMaker maker = MapMaker::none; };
+int map_move(const PosMap &map, int64_t n, bool scatter, int count, const void *src, int64_t src_stride, void *dst, int64_t dst_stride,
+             hipStream_t s);
 }
 struct spmv_csr { int64_t rows = 0, cols = 0, nnz = 0; const int32_t *d_row_ptr = nullptr, *d_col_idx = nullptr; const float *d_vals = nullptr;
-    spmv::DevPtr<int32_t> own_row_ptr, own_col_idx; spmv::DevPtr<float> own_vals; spmv::DevPtr<uint32_t> select_map;
-    int64_t select_parent_nnz = -1; int device = 0; spmv::SpmmPlan plan_spmm; spmv::AttnPlan plan_attn; };
+    spmv::DevPtr<int32_t> own_row_ptr, own_col_idx; spmv::DevPtr<float> own_vals; spmv::PosMap map;
+    int device = 0; spmv::SpmmPlan plan_spmm; spmv::AttnPlan plan_attn; };
 typedef spmv_csr spmv_csr_t;
 namespace spmv {
 inline int plan_spmm(spmv_csr &, hipStream_t) { return SPMV_OK; }

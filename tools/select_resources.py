@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""tools/select_resources.py [LOG] -- registers, LDS and scratch of every kernel of csrc/kernels_select.hip.
+"""tools/select_resources.py [LOG] -- registers, LDS and scratch of every kernel of csrc/kernels_select.hip and of the move through
+the map that its companions launch (csrc/kernels_map.hip).
 
-Compiles the file's device code for gfx950 with the Makefile's flags and -Rpass-analysis=kernel-resource-usage (or reads the
+Compiles the files' device code for gfx950 with the Makefile's flags and -Rpass-analysis=kernel-resource-usage (or reads the
 remarks of such a compile from LOG) and prints one row per instantiation: VGPRs, AGPRs, waves per SIMD, SGPRs, scratch bytes
 per lane, registers spilled, LDS bytes per block.  profiles/select_resources.md is its output.  Exit status 1 if a kernel
 has scratch.  A compile, not a run: it needs no device."""
@@ -14,8 +15,8 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "spmv-test_amd" / "csrc"
 NAMES = {"k_sel_cutILb0E": "k_sel_cut<false> (top-k: cut and count)", "k_sel_cutILb1E": "k_sel_cut<true> (threshold: count)",
-         "k_sel_compact": "k_sel_compact", "k_sel_moveILb0E": "k_sel_move<false> (gather, values)",
-         "k_sel_moveILb1E": "k_sel_move<true> (scatter)"}
+         "k_sel_compact": "k_sel_compact", "k_map_moveILb0ELb0E": "k_map_move<false, false> (gather, values)",
+         "k_map_moveILb1ELb0E": "k_map_move<true, false> (scatter)"}
 
 
 def remarks() -> str:
@@ -23,9 +24,9 @@ def remarks() -> str:
         return Path(sys.argv[1]).read_text()
     hipcc = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
     cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
-           f"-I{ROOT / 'include'}", f"-I{CSRC}", "--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage",
-           str(CSRC / "kernels_select.hip"), "-o", os.devnull]
-    return subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
+           f"-I{ROOT / 'include'}", f"-I{CSRC}", "--cuda-device-only", "-S", "-Rpass-analysis=kernel-resource-usage"]
+    return "".join(subprocess.run(cmd + [str(CSRC / name), "-o", os.devnull], capture_output=True, text=True, check=True).stderr
+                   for name in ("kernels_select.hip", "kernels_map.hip"))
 
 
 def main() -> int:
